@@ -9,13 +9,16 @@ launch).  value = env-steps of all ranks / max-over-ranks wall time.  The episod
 reset()), so a 4096-env batch (64 workgroups on 256 CUs) has four of them in flight; the like-for-like figure with ONE episode in
 flight per env is reported next to it (config.strict, and the `sequential_episodes` key).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--horizon 200] [--sweep] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--horizon 200] [--full] [--dump-outputs DIR] [--sweep] [--no-cpu]
   N > 1: either under the launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...), or
          plain `python bench.py --gpus N`: without WORLD_SIZE in the environment main() starts that launcher itself as a child process (self_launch)
 
-Prints ONE JSON line (rank 0).  Extra keys: "roofline" (fused rollout kernel: algorithmic bytes / HIP-event time
-vs 8 TB/s), "cpu_baseline" (the C oracle on the host cores, bounded sample), "step_api" (the same workload
-through per-step launches of the gym-style step()), and with --sweep "sweep" (throughput vs N).
+Prints ONE JSON line (rank 0).  A plain run times the headline and nothing else: set-up, --settle-launches + --warmup untimed launches, --steps timed
+ones, "roofline" from that one window (fused rollout kernel: algorithmic bytes / HIP-event time vs 8 TB/s), the outputs of the last timed launch
+with --dump-outputs.  --full adds everything else the line has carried: the first launches of the process, five roofline windows, the one-episode
+and sustained legs, "cpu_baseline" (the C oracle and the host build on the host cores, bounded samples), "step_api" (the same workload through
+per-step launches of the gym-style step()), the policy-in-the-loop leg, the sawyer_door / sawyer_peg / kitchen / minitaur lines and the
+simulator probe.  --sweep adds "sweep" (throughput vs N).
 """
 import argparse
 import importlib.util
@@ -38,6 +41,7 @@ HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.2
 BYTES_PER_ENV_STEP_ROLLOUT = 66  # act 12 B in; obs 48 + reward 4 + done 1 + success 1 B out
 BYTES_PER_ENV_STEP_STEP = 144    # + fp64 state in/out per launch: qpos 2x32, attached 2x1, goal_idx 4, steps 2x4
 STATE_BYTES_PER_ENV_LAUNCH = 2 * (32 + 1 + 4) + 4   # rollout: state read+written once per launch
+DUMP_BYTES = 60 << 20            # --dump-outputs writes at most this many bytes of data in all (under 64 MB with the .npy headers)
 
 
 def parse(argv=None):
@@ -72,7 +76,41 @@ def parse(argv=None):
   p.add_argument('--cpu-child-args', default='{}', help=argparse.SUPPRESS)
   p.add_argument('--workload', default='tabletop', choices=['tabletop', 'sawyer_door', 'sawyer_peg', 'kitchen', 'minitaur'],
                  help='tabletop = BASELINE configs[1] (the default, the quoted metric); sawyer_door / sawyer_peg = configs[2] shape, N=8192 each (next rows)')
-  return p.parse_args(argv)
+  p.add_argument('--full', action='store_true',
+                 help='also run every leg besides the headline (CPU baselines, simulator probe, early / sustained / one-episode windows, the extra roofline '
+                      'windows, step API, policy in the loop, the other workloads\' lines); without it the --no-* switches are all on and one roofline window is taken')
+  p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                 help='write what the last timed step computed to DIR/<name>.npy (float32 / float64, rows = the flattened leading axes; '
+                      f'a fixed seeded sample of the rows when all of them would exceed {DUMP_BYTES >> 20} MiB)')
+  a = p.parse_args(argv)
+  if not a.full:
+    a.no_cpu = a.no_single = a.no_step_api = a.no_sawyer = a.no_kitchen = a.no_minitaur = True
+    a.roofline_windows = 1
+  return a
+
+
+def dump_outputs(directory, arrays, lead):
+  """`arrays`: name -> tensor, all with the same `lead` leading axes (the step's [E,] T, N).  Writes directory/<name>.npy with those axes flattened into
+  rows: floating point as it is (f32 / f64), flags and codes as float32.  When all rows would exceed DUMP_BYTES, the same fixed seeded sample of rows
+  (sorted) is taken from every array, so that two builds given the same arguments write files that compare entry by entry."""
+  import numpy as np
+  import torch
+  shape = next(iter(arrays.values())).shape[:lead]
+  rows = int(np.prod(shape))
+  flat = {}
+  for k, v in arrays.items():
+    assert v.shape[:lead] == shape, (k, tuple(v.shape), tuple(shape))
+    flat[k] = v.reshape(rows, -1) if v.dim() > lead else v.reshape(rows)
+    if flat[k].dtype not in (torch.float32, torch.float64):
+      flat[k] = flat[k].to(torch.float32)
+  row_bytes = sum(v[:1].numel() * v.element_size() for v in flat.values())
+  keep = min(rows, DUMP_BYTES // row_bytes)
+  if keep < rows:
+    idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))).to(next(iter(flat.values())).device)
+    flat = {k: v.index_select(0, idx) for k, v in flat.items()}
+  os.makedirs(directory, exist_ok=True)
+  for k, v in flat.items():
+    np.save(os.path.join(directory, f'{k}.npy'), v.cpu().numpy())
 
 
 def make_env(torch, n, horizon, reward, rank, device):
@@ -520,10 +558,10 @@ def sawyer_cpu_baseline(T_sample, seconds, task='sawyer_door', n=8192, reps=3):
           'single_core': sweep[1], 'by_threads': {str(k): v for k, v in sweep.items()}, 'runs': {str(k): v for k, v in detail.items()}, 'host': host_cpu_info()}
 
 
-def run_sawyer(a, torch, dist, world, rank, device, workload, steps, warmup, n=8192, T=None, cpu_seconds=None):
+def run_sawyer(a, torch, dist, world, rank, device, workload, steps, warmup, n=8192, T=None, cpu_seconds=None, dump=None):
   """BASELINE configs[2] shape: n envs per GPU, reset + one fused T-step rollout per bench step, barrier + synchronize on both sides, max
   over ranks.  The dynamics are this build's own stepper (own contact model, parity with MuJoCo unpinned) -- see DESIGN.md.
-  -> result dict on rank 0 (None elsewhere)"""
+  `dump`: directory for the outputs of the last timed step (rank 0's envs).  -> result dict on rank 0 (None elsewhere)"""
   from earl_benchmark_amd.envs.sawyer_door import SawyerDoor
   from earl_benchmark_amd.envs.sawyer_peg import SawyerPeg
   from earl_benchmark_amd.wrappers import PersistentStateWrapper
@@ -568,6 +606,8 @@ def run_sawyer(a, torch, dist, world, rank, device, workload, steps, warmup, n=8
   diverged = int(out['status'].sum())
   if rank != 0:
     return None
+  if dump:
+    dump_outputs(dump, out, 2)
   # algorithmic HBM bytes per env step: action 16 in; obs 14 x 8 + reward 4 + done 1 + success 1 + status 1 out; the last-stable state row
   # (qpos, qvel, mocap) written after every env step; per launch the state read once and the last observation written once
   state_row = (nq + nv + 3) * 8
@@ -676,11 +716,12 @@ def predicted_scaling(workload, n_global, world):
   return {'strong': strong, 'weak': weak, 'predicted_speedup_vs_1_gpu': strong['predicted_speedup_vs_1_gpu'], 'basis': strong['basis']}
 
 
-def run_kitchen(a, torch, dist, world, rank, device, steps, warmup, n_global=2048, T=400, cpu_seconds=None, env_factory=None):
+def run_kitchen(a, torch, dist, world, rank, device, steps, warmup, n_global=2048, T=400, cpu_seconds=None, env_factory=None, dump=None):
   """BASELINE configs[3]: kitchen, 2048 envs in total range-sharded over the GPUs (n_global / world per GPU: STRONG scaling), one bench step =
   reset + T = 400 env steps (the reference's eval horizon) of 40 timesteps each in ONE fused launch (earl_kitchen_rollout); the per-step surface
   (env.step(): one launch per env step) is timed beside it as `step_api`.
-  Own stepper, reduced collision set, parity with MuJoCo unpinned (envs/kitchen.py).  -> result dict on rank 0"""
+  Own stepper, reduced collision set, parity with MuJoCo unpinned (envs/kitchen.py).  `dump`: directory for the outputs of the last timed step
+  (rank 0's envs).  -> result dict on rank 0"""
   from earl_benchmark_amd.envs.kitchen import Kitchen
   from earl_benchmark_amd.wrappers import PersistentStateWrapper
   from earl_benchmark_amd import sharding
@@ -729,6 +770,8 @@ def run_kitchen(a, torch, dist, world, rank, device, steps, warmup, n_global=204
     dt = float(tmax.item())
   assert bool(done.all()) and bool(torch.isfinite(o).all())
   fails = int(env.unwrapped.fail_count.sum())
+  if dump and rank == 0:
+    dump_outputs(dump, outbuf, 2)
   clk.sync()
   t1 = time.perf_counter()
   if not a.no_step_api:                                # (profiling runs skip it: env.step() launches the same kernel with T = 1, which would mix into its statistics)
@@ -800,10 +843,11 @@ def minitaur_cpu_baseline(seconds, n=4096, reps=2):
           'single_core': sweep[1], 'by_threads': {str(k): v for k, v in sweep.items()}, 'runs': {str(k): v for k, v in detail.items()}, 'host': host_cpu_info()}
 
 
-def run_minitaur(a, torch, dist, world, rank, device, steps, warmup, n_global=4096, T=1000, cpu_seconds=None, env_factory=None):
+def run_minitaur(a, torch, dist, world, rank, device, steps, warmup, n_global=4096, T=1000, cpu_seconds=None, env_factory=None, dump=None):
   """BASELINE configs[4]: minitaur, 4096 envs in total range-sharded over the GPUs (STRONG scaling, like the kitchen line), one bench step = reset
   (incl. its 100 settle timesteps) + T = 1000 env steps (the reference's eval horizon) of 5 timesteps each in ONE fused launch (earl_minitaur_rollout).
-  Own robot model and stepper: parity with the reference's PyBullet simulation is unpinned and model-less (envs/minitaur.py).  -> result dict on rank 0"""
+  Own robot model and stepper: parity with the reference's PyBullet simulation is unpinned and model-less (envs/minitaur.py).  `dump`: directory for the
+  outputs of the last timed step (rank 0's envs).  -> result dict on rank 0"""
   from earl_benchmark_amd.envs.minitaur import Minitaur
   from earl_benchmark_amd.wrappers import PersistentStateWrapper
   from earl_benchmark_amd import sharding
@@ -847,6 +891,8 @@ def run_minitaur(a, torch, dist, world, rank, device, steps, warmup, n_global=40
   fails = int(env.unwrapped.fail_count.sum())
   if rank != 0:
     return None
+  if dump:
+    dump_outputs(dump, res, 2)
   prof = {}
   tpath = os.path.join(REPO, 'profiles', 'traffic.json')
   if os.path.exists(tpath) and (n_global, T, world) == (4096, 1000, 1):
@@ -978,7 +1024,8 @@ def emit(res):
 def main_sawyer(a, torch, dist, world, rank, device):
   n = a.envs if a.envs != 4096 else 8192
   T = a.horizon if a.horizon != 200 else None
-  r = run_sawyer(a, torch, dist, world, rank, device, a.workload, a.steps, a.warmup, n=n, T=T, cpu_seconds=None if a.no_cpu else max(2.0, a.cpu_seconds / 5))
+  r = run_sawyer(a, torch, dist, world, rank, device, a.workload, a.steps, a.warmup, n=n, T=T, cpu_seconds=None if a.no_cpu else max(2.0, a.cpu_seconds / 5),
+                 dump=a.dump_outputs)
   if rank == 0:
     res = {'metric': 'env steps/sec (aggregate) at N parallel envs', 'value': r['value'], 'unit': 'env-steps/s', 'n_gpus': world, 'steps': a.steps,
            'warmup': a.warmup, 'ms_per_step': r['ms_per_step'], 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64',
@@ -1046,7 +1093,7 @@ def main(argv=None):
       h = json.load(open(pre))
       SIMULATORS = h['simulators']
       CPU_RESULTS.update(h['cpu'])
-    else:
+    elif a.full:
       SIMULATORS = probe_reference_simulators()
       if not a.no_cpu:                                         # N > 1 under a launcher: the line's own CPU legs only (the other ranks wait in the rendezvous meanwhile)
         collect_cpu_baselines(a, world)
@@ -1070,7 +1117,7 @@ def main(argv=None):
   if a.workload in ('sawyer_door', 'sawyer_peg'):
     return main_sawyer(a, torch, dist, world, rank, device)
   if a.workload == 'minitaur':
-    r = run_minitaur(a, torch, dist, world, rank, device, min(a.steps, 3), min(a.warmup, 1), cpu_seconds=None if a.no_cpu else 5.0)
+    r = run_minitaur(a, torch, dist, world, rank, device, a.steps, a.warmup, cpu_seconds=None if a.no_cpu else 5.0, dump=a.dump_outputs)
     if rank == 0:
       emit({'metric': 'env steps/sec (aggregate) at N parallel envs', 'value': r['value'], 'unit': 'env-steps/s', 'n_gpus': world,
             'steps': r['steps'], 'warmup': r['warmup'], 'ms_per_step': r['ms_per_step'], 'higher_is_better': True, 'scaling': 'strong',
@@ -1081,7 +1128,7 @@ def main(argv=None):
       dist.destroy_process_group()
     return
   if a.workload == 'kitchen':
-    r = run_kitchen(a, torch, dist, world, rank, device, min(a.steps, 3), min(a.warmup, 1), cpu_seconds=None if a.no_cpu else 5.0)
+    r = run_kitchen(a, torch, dist, world, rank, device, a.steps, a.warmup, cpu_seconds=None if a.no_cpu else 5.0, dump=a.dump_outputs)
     if rank == 0:
       emit({'metric': 'env steps/sec (aggregate) at N parallel envs', 'value': r['value'], 'unit': 'env-steps/s', 'n_gpus': world,
             'steps': r['steps'], 'warmup': r['warmup'], 'ms_per_step': r['ms_per_step'], 'higher_is_better': True, 'scaling': 'strong',
@@ -1097,25 +1144,31 @@ def main(argv=None):
   wgs = (n + 63) // 64
   in_flight = min(E, max(1, 256 // wgs)) if (E > 1 and wgs * 2 <= 256) else 1     # csrc/tabletop.hip do_rollout: episode groups side by side
 
-  if a.test_env_factory:
-    mod, fn = a.test_env_factory.split(':')
-    env = getattr(importlib.import_module(mod), fn)(n=n, T=T, rank=rank, world=world)
-  else:
-    env = make_env(torch, n, T, a.reward, rank, device)
+  def new_env():
+    if a.test_env_factory:
+      mod, fn = a.test_env_factory.split(':')
+      return getattr(importlib.import_module(mod), fn)(n=n, T=T, rank=rank, world=world)
+    return make_env(torch, n, T, a.reward, rank, device)
+  env = new_env()
   R = max(1, a.action_sets)
   # [E, T, n, 3] x R: every episode of a launch has its own actions, and consecutive launches read different tensors
   act_sets = [synth_actions(torch, T, n, rank + 1000 * r, device, E) for r in range(R)]
   acts = act_sets[0]
   acts1 = acts[0] if E > 1 else acts
   out = alloc_out(torch, T, n, device, E)
-  # the process's first launches (what rounds 1-3 quoted as `value`): 5-15 % faster than the sustained power state; kept as a side key
-  edt, ekm, _, _, el = time_rollouts(torch, dist, env, act_sets, out, a.steps, a.warmup, world, device)
-  early = {'value': a.steps * E * n * T * world / edt, 'unit': 'env-steps/s', 'kernel_ms_mean': ekm[0], 'launches': el,
-           'note': f'the first launches of the process ({a.warmup} warm-up + {a.steps} timed), before the board settles into its sustained power state: NOT the headline'}
+  early = None
+  if a.full:
+    # the process's first launches (what rounds 1-3 quoted as `value`): 5-15 % faster than the sustained power state; kept as a side key.  On an env of
+    # their own, so that the headline's env has the same launch history (Philox counter) with and without --full and the outputs it computes are the same
+    edt, ekm, _, _, el = time_rollouts(torch, dist, new_env(), act_sets, out, a.steps, a.warmup, world, device)
+    early = {'value': a.steps * E * n * T * world / edt, 'unit': 'env-steps/s', 'kernel_ms_mean': ekm[0], 'launches': el,
+             'note': f'the first launches of the process ({a.warmup} warm-up + {a.steps} timed), before the board settles into its sustained power state: NOT the headline'}
   # headline: --settle-launches more untimed launches first (about 10 ms of back-to-back traffic), then the --warmup ones, then EXACTLY --steps timed
   dt, kern_ms, gathered, _, launches = time_rollouts(torch, dist, env, act_sets, out, a.steps, a.warmup + max(0, a.settle_launches), world, device)
   if world > 1:
     assert gathered.shape == (n * world, 2)
+  if a.dump_outputs and rank == 0:     # before any later launch writes `out` again
+    dump_outputs(a.dump_outputs, dict(zip(('obs', 'reward', 'done', 'success'), out)), 3 if E > 1 else 2)
   # roofline: the kernel's launch duration over several timed windows of the same shape (the first is the headline's own), median with min / max: one window
   # moved 0.64 <-> 0.71 of peak between boxes / runs in round 4
   window_ms = [kern_ms[0]]
@@ -1201,8 +1254,8 @@ def main(argv=None):
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
         'config': {'workload': f'tabletop_manipulation {a.reward}, {n} envs/GPU; bench step = 1 launch = {E} eval episodes (reset+{T} steps), own actions',
                    'envs_per_gpu': n, 'episodes_per_bench_step': E, 'episodes_in_flight': in_flight, 'env_instances_resident': n * in_flight,
-                   'strict': strict, 'launches': launches, 'settle_launches': max(0, a.settle_launches), 'untimed_launches_before_the_timed_region': a.warmup + a.steps + a.warmup + max(0, a.settle_launches),
-                   'early_window': early['value'], 'global_envs': n * world, 'horizon': T, 'env_steps_per_bench_step': E * n * T * world,
+                   'strict': strict, 'launches': launches, 'settle_launches': max(0, a.settle_launches), 'untimed_launches_before_the_timed_region': (a.warmup + a.steps if a.full else 0) + a.warmup + max(0, a.settle_launches),
+                   'early_window': None if early is None else early['value'], 'global_envs': n * world, 'horizon': T, 'env_steps_per_bench_step': E * n * T * world,
                    'actions': f'{R} x [{E}, {T}, {n}, 3] f32 per GPU ({R * E * T * n * 12 / 1e6:.0f} MB): distinct per episode, launches read the {R} tensors round-robin',
                    'action_sets': R,
                    'next_rows': {k: (v or {}).get('value') for k, v in sawyer.items()},

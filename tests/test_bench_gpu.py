@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import REPO
@@ -22,9 +23,11 @@ def run(*flags):
   return json.loads(lines[0]), json.loads(full[0][len('bench_full: '):])
 
 
-def test_default_line_schema_and_accounting_at_a_reduced_size():
-  d, full = run('--steps', '20', '--warmup', '5', '--envs', '1024', '--horizon', '40', '--episodes-per-launch', '6', '--action-sets', '2', '--cpu-seconds', '0.5',
-          '--no-sawyer', '--no-kitchen', '--no-minitaur')
+REDUCED = ('--steps', '20', '--warmup', '5', '--envs', '1024', '--horizon', '40', '--episodes-per-launch', '6', '--action-sets', '2')
+
+
+def test_default_line_schema_and_accounting_at_a_reduced_size(tmp_path):
+  d, full = run(*REDUCED, '--full', '--cpu-seconds', '0.5', '--no-sawyer', '--no-kitchen', '--no-minitaur', '--dump-outputs', str(tmp_path / 'full'))
   for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data', 'config', 'roofline',
             'cpu_baseline'):
     assert k in d, k
@@ -49,9 +52,22 @@ def test_default_line_schema_and_accounting_at_a_reduced_size():
   assert cb['kind'] == 'port' and cb['cores'] >= 1 and cb['value'] > 0 and cb['sample'] and cb['value'] >= max(cb['oracle_c'], cb['host_build']) * (1 - 1e-5)
   assert 'host' in full['cpu_baseline_oracle_c'] and full['step_api']['value'] > 0 and full['value'] == d['value']
   assert json.load(open(os.path.join(REPO, 'bench_full.json')))['value'] == d['value']
+  # the plain line: the headline alone, one roofline window; the outputs of its last timed launch are those of the --full run's headline, bit for bit
+  p, pfull = run(*REDUCED, '--dump-outputs', str(tmp_path / 'plain'))
+  assert p['steps'] == 20 and p['cpu_baseline'] is None and p['roofline']['windows'] == 1 and 'step_api' not in pfull and pfull['early_window'] is None
+  assert abs(p['value'] - p['config']['env_steps_per_bench_step'] * 1e3 / p['ms_per_step']) < 1e-6 * p['value']
+  for name, cols in (('obs', (12,)), ('reward', ()), ('done', ()), ('success', ())):
+    got = np.load(tmp_path / 'plain' / f'{name}.npy')
+    assert got.dtype == np.float32 and got.shape == (E * T * n,) + cols
+    np.testing.assert_array_equal(got, np.load(tmp_path / 'full' / f'{name}.npy'))
+  assert np.load(tmp_path / 'plain' / 'done.npy').reshape(E, T, n)[:, -1].all()
 
 
-def test_minitaur_line():
-  d, full = run('--workload', 'minitaur', '--steps', '1', '--warmup', '0', '--no-cpu')
+def test_minitaur_line(tmp_path):
+  d, full = run('--workload', 'minitaur', '--steps', '1', '--warmup', '0', '--no-cpu', '--dump-outputs', str(tmp_path))
   assert d['config']['envs_global'] == 4096 and d['config']['horizon'] == 1000 and full['diverged_env_steps'] <= 4 and d['value'] > 1e5
-  assert d['roofline']['bound'] == 'valu' and d['scaling'] == 'strong'
+  assert d['roofline']['bound'] == 'valu' and d['scaling'] == 'strong' and d['steps'] == 1
+  # a fixed sample of the [T, N] rows (all of them would exceed the dump's budget): float64 observations, same rows in every file
+  obs, done = np.load(tmp_path / 'obs.npy'), np.load(tmp_path / 'done.npy')
+  assert obs.dtype == np.float64 and obs.shape[1] == 32 and done.dtype == np.float32 and done.shape == obs.shape[:1] < (1000 * 4096,)
+  assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) < 64e6 and np.isfinite(obs).all()

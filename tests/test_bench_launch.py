@@ -11,7 +11,7 @@ import sys
 from conftest import REPO
 
 ARGS = ['--steps', '3', '--warmup', '1', '--envs', '48', '--horizon', '7', '--episodes-per-launch', '3', '--action-sets', '2', '--settle-launches', '0',
-        '--roofline-windows', '3', '--no-cpu', '--no-step-api', '--no-single', '--no-sawyer', '--no-kitchen', '--no-minitaur',
+        '--full', '--roofline-windows', '3', '--no-cpu', '--no-step-api', '--no-single', '--no-sawyer', '--no-kitchen', '--no-minitaur',
         '--test-env-factory', 'tests.bench_stub_env:make', '--test-backend', 'gloo']
 
 
@@ -77,3 +77,29 @@ def test_child_failure_is_the_exit_code():
                      capture_output=True, text=True, timeout=600, cwd=REPO,
                      env={k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')})
   assert r.returncode != 0 and not [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_last_step(tmp_path):
+  """without --full: no CPU leg, one roofline window (the headline's own), no side leg in the full object; --dump-outputs writes the four arrays the
+  last timed launch returned, rows = (episode, step, env) flattened, float32, equal to what the stub wrote -- and the same with --full"""
+  import numpy as np
+  from test_bench_sequence import synthetic
+  E, T, n = 3, 7, 48
+  base = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--envs', str(n), '--horizon', str(T),
+          '--episodes-per-launch', str(E), '--action-sets', '2', '--test-env-factory', 'tests.bench_stub_env:make']
+  env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+  r = subprocess.run(base + ['--dump-outputs', str(tmp_path / 'plain')], capture_output=True, text=True, timeout=600, env=env, cwd=REPO)
+  d, full = _the_line(r)
+  assert d['steps'] == 3 and d['cpu_baseline'] is None and d['roofline']['windows'] == 1 and full['early_window'] is None
+  assert not {'step_api', 'policy_in_the_loop', 'single_episode_launch', 'sustained', 'sawyer_door', 'kitchen', 'minitaur'} & set(full)
+  want = [np.stack([synthetic(T, 0, n, shift=E - 1 - e)[k].numpy() for e in range(E)]) for k in range(4)]
+  for name, w in zip(('obs', 'reward', 'done', 'success'), want):
+    got = np.load(tmp_path / 'plain' / f'{name}.npy')
+    assert got.dtype == np.float32 and got.shape == (E * T * n,) + w.shape[3:]
+    np.testing.assert_array_equal(got, w.reshape(got.shape).astype(np.float32))
+  r = subprocess.run(base + ['--full', '--no-cpu', '--no-step-api', '--no-sawyer', '--no-kitchen', '--no-minitaur', '--dump-outputs', str(tmp_path / 'full')],
+                     capture_output=True, text=True, timeout=600, env=env, cwd=REPO)
+  d, full = _the_line(r)
+  assert d['roofline']['windows'] == 5 and full['early_window']['value'] > 0 and full['sustained']['value'] > 0
+  for name in ('obs', 'reward', 'done', 'success'):
+    np.testing.assert_array_equal(np.load(tmp_path / 'full' / f'{name}.npy'), np.load(tmp_path / 'plain' / f'{name}.npy'))

@@ -1,5 +1,5 @@
 // minitaur_device.h -- the reference's numpy around Bullet for the minitaur, as device functions shared by csrc/glue.hip (the batched glue entry
-// points of include/earl_glue.h, pinned bit-exact against goldens recorded from the reference's own functions) and the env kernel in csrc/physics.hip.
+// points of include/earl_glue.h, pinned bit-exact against goldens recorded from the reference's own functions) and the env kernel of csrc/physics_mt.hip.
 //   Minitaur.ConvertFromLegModel   earl_benchmark/envs/minitaur.py:434-457
 //   MotorModel.convert_to_torque   earl_benchmark/envs/motor.py:49-94
 // fp64 like the reference; callers compile these with FMA contraction off (the expressions are separately rounded).

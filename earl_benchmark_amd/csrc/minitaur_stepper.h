@@ -1,6 +1,6 @@
 // minitaur_stepper.h -- the minitaur's timestep written ON THE MODEL'S TREE: a floating root body (dofs 0-5) carrying four legs
 // of four hinges each (leg k = dofs 6 + 4 k ... 9 + 4 k: upper / lower link of the L chain, upper / lower link of the R chain, the two lower links tied
-// by the leg's connect constraint).  Included by physics.hip inside its anonymous namespace when built as physics_mt.hip (EARL_PHYS_VARIANT_MT).
+// by the leg's connect constraint).  Included by physics_mt.hip inside its anonymous namespace, after the stepper (physics_stepper.h).
 //
 // Same algorithm and the same numbers (to rounding) as the generic substep<22> of physics.hip, which it replaces on the product path (the generic
 // one stays selectable: earl_debug_set_minitaur_stepper, tests/test_minitaur_gpu.py compares the two); reference: oracle/physics_oracle.py

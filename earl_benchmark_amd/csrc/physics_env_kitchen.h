@@ -1,5 +1,5 @@
 // physics_env_kitchen.h -- the kitchen env kernels: the small per-step kernels around the stepper and the fused rollout
-// A section of csrc/physics.hip (included there, inside its anonymous namespace, after the stepper): split out in round 5 so that a change to one env's kernels
+// Included by physics_kitchen.hip, inside the anonymous namespace, after the stepper (physics_stepper.h): split out in round 5 so that a change to one env's kernels
 // recompiles only the translation units that hold them (csrc/Makefile lists the headers per unit).
 
 // ------------------------------------------------------------------------------------------------ kitchen env step (include/earl_physics.h)

@@ -1,5 +1,5 @@
 // physics_env_minitaur.h -- the minitaur env kernel: reset incl. its settle steps and the fused rollout, on the tree-structured timestep of minitaur_stepper.h or the generic one
-// A section of csrc/physics.hip (included there, inside its anonymous namespace, after the stepper): split out in round 5 so that a change to one env's kernels
+// Included by physics_mt.hip, inside the anonymous namespace, after the stepper (physics_stepper.h): split out in round 5 so that a change to one env's kernels
 // recompiles only the translation units that hold them (csrc/Makefile lists the headers per unit).
 
 // ------------------------------------------------------------------------------------------------ minitaur env (include/earl_physics.h; physics_mt.hip)

@@ -1,5 +1,5 @@
-// physics_env_sawyer.h -- the Sawyer door / peg env kernels: fused rollout (optionally time-sliced), reset / observe, reward and info kernels
-// A section of csrc/physics.hip (included there, inside its anonymous namespace, after the stepper): split out in round 5 so that a change to one env's kernels
+// physics_env_sawyer.h -- the Sawyer door / peg env kernels: fused rollout (optionally time-sliced), reset / observe; the reward / info kernels of given observations are in physics.hip
+// Included by physics.hip, physics_w8.hip and physics_l64.hip, inside the anonymous namespace, after the stepper (physics_stepper.h): split out in round 5 so that a change to one env's kernels
 // recompiles only the translation units that hold them (csrc/Makefile lists the headers per unit).
 
 // ------------------------------------------------------------------------------------------------ Sawyer env kernels
@@ -477,37 +477,3 @@ __global__ __launch_bounds__(64 * Lim<NV>::WPB) void sawyer_reset_kernel(const S
     oi[sub] = sub < 3 ? s.qp[cfg.obj_dof + sub] : s.emit.att[3][sub - 3];
   }
 }
-
-#ifndef EARL_PHYS_NOT_MAIN
-// compute_reward / is_successful on given observations (sawyer_door.py:141-177), one lane per row
-__global__ void sawyer_door_reward_kernel(const int n, const double* __restrict__ obs, const earl_sawyer_cfg cfg, float* __restrict__ reward,
-                                          uint8_t* __restrict__ success) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double* o = obs + (size_t)i * 14;
-  double r; bool ok;
-  door_reward(cfg, ld3(o), ld3(o + 4), ld3(o + 11), r, ok);
-  if (reward) reward[i] = (float)r;
-  if (success) success[i] = ok ? 1 : 0;
-}
-#endif
-
-#ifndef EARL_PHYS_NOT_MAIN
-// SawyerDoorV2.evaluate_state's info dict (sawyer_door.py:127-139) of given observation rows: every entry is a function of the observation (and of the
-// reward type), so the rollout kernel need not carry it; one lane per row
-__global__ void sawyer_door_info_kernel(const int n, const double* __restrict__ obs, const earl_sawyer_cfg cfg, const uint8_t* __restrict__ status, double* __restrict__ info) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double* o = obs + (size_t)i * 14;
-  double r, row[EARL_SAWYER_INFO]; bool ok;
-  double* mine = info + (size_t)i * EARL_SAWYER_INFO;
-  // a goal-switch row of a lifelong rollout (cfg.goal_change_frequency > 0: only then has the rollout kernel written the marker, for every row): the target its reward used
-  // (the row's goal block holds the NEW goal).  Without goal switching the slot is output only.
-  const V3 target = (cfg.goal_change_frequency > 0 && mine[7] == 1.0) ? ld3(mine) : ld3(o + 11);
-  door_reward(cfg, ld3(o), ld3(o + 4), target, r, ok, row);
-  const bool rolled_back = status && status[i] != 0;
-#pragma unroll
-  for (int k = 0; k < EARL_SAWYER_INFO; ++k) info[(size_t)i * EARL_SAWYER_INFO + k] = rolled_back ? 0.0 : row[k];
-}
-#endif
-

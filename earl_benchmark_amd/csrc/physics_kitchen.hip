@@ -1,7 +1,78 @@
 // physics_kitchen.hip -- fifth build of the articulated-body stepper: the KITCHEN (BASELINE configs[3]).
 //
-// physics.hip instantiated for nv = 23 (32 lanes per env, arm block + fixtures solver, joint couplings, dry friction, springs, force-limited actuators) plus the kitchen env
+// The stepper (physics_stepper.h) instantiated for nv = 23 (32 lanes per env, arm block + fixtures solver, joint couplings, dry friction, springs, force-limited actuators) plus the kitchen env
 // kernels (physics_env_kitchen.h: the per-step kernels, the fused rollout) and the entry points earl_kitchen_step / earl_kitchen_rollout; earl_physics_step / _forward of the
 // main unit forward nv = 23 here.  A translation unit of its own (round 5): the main unit's compile time was 50 s with it.
-#define EARL_PHYS_UNIT_KITCHEN 1
-#include "physics.hip"
+#include "physics_stepper.h"
+
+namespace {
+#include "physics_env_kitchen.h"
+}  // namespace
+
+#include "physics_launch.h"
+
+extern "C" {
+
+void earl_unit_kitchen_physics(const void* pargs, int integrate, void* stream) {
+  const PArgs& a = *static_cast<const PArgs*>(pargs);
+  const hipStream_t st = (hipStream_t)stream;
+  if (integrate) physics_kernel<23, 32, true><<<grid_for<23, 32>(a.n), block_for<23>(), 0, st>>>(a);     // 32 lanes per env: two envs per wave
+  else physics_kernel<23, 32, false><<<grid_for<23, 32>(a.n), block_for<23>(), 0, st>>>(a);
+}
+int earl_kitchen_step(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                      const earl_kitchen_state* st, const float* action, const earl_kitchen_out* out, earl_stream_t stream) {
+  if (!model || !params || !cfg || !st || !action || !out || cfg->n < 0 || cfg->n_att < 10 || cfg->frame_skip < 0) return EARL_ERR_ARG;
+  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !st->last_qp_robot || !st->att_xpos || !st->steps_since_reset || !st->last_obs) return EARL_ERR_ARG;
+  if (!st->action64 || !st->ctrl9 || !st->qpos_bak || !st->qvel_bak || !st->sites || !st->bad || !st->mocap_bak || !st->att_bak || (cfg->sensor_noise && !st->noise)) return EARL_ERR_ARG;
+  if (!out->obs || !out->reward || !out->done || !out->success) return EARL_ERR_ARG;
+  for (int k = 0; k < 8; ++k) if (cfg->site_att[k] < 0 || cfg->site_att[k] >= cfg->n_att) return EARL_ERR_ARG;
+  const int n = cfg->n;
+  if (n == 0) return EARL_OK;
+  const hipStream_t hs = (hipStream_t)stream;
+  if (int rc = check_cone(col, false, hs, "kitchen_step")) return rc;
+  KitchenArgs k{*cfg, *st, *out, action, cfg->n_att};
+  kitchen_pre_kernel<<<(n * 23 + 255) / 256, 256, 0, hs>>>(k);
+  // KitchenV0.step up to do_simulation: mocap target, the nine position targets (csrc/glue.hip)
+  if (int rc = earl_kitchen_action(n, params, st->action64, st->mocap_pos, st->last_qp_robot, st->ctrl9, stream)) return rc;
+  // do_simulation: ctrl[i] = targets[i] for i < nu = 2, frame_skip timesteps (adept_envs/mujoco_env.py:148-157)
+  PArgs a{model, col, n, cfg->frame_skip, st->qpos, st->qvel, st->mocap_pos, cfg->mocap_quat_dev, st->ctrl9, st->att_xpos, nullptr, nullptr, 9, 0};
+  earl_unit_kitchen_physics(&a, 1, stream);
+  kitchen_guard_kernel<<<(n + 255) / 256, 256, 0, hs>>>(k);
+  // Robot.get_obs + KitchenV0._get_obs: sensor noise from Philox draws keyed by the global env id
+  if (cfg->sensor_noise)
+    if (int rc = earl_philox_uniform(n, 46, cfg->seed, cfg->counter, cfg->env_offset, 0x4B00u, -1.0, 1.0, st->noise, stream)) return rc;
+  if (int rc = earl_kitchen_obs(n, params, st->qpos, st->goal, cfg->sensor_noise ? st->noise : nullptr, out->obs, stream)) return rc;
+  if (int rc = earl_kitchen_reward(n, out->obs, st->mocap_pos, st->sites, out->reward, out->success, stream)) return rc;
+  kitchen_finish_kernel<<<(n + 255) / 256, 256, 0, hs>>>(k);
+  return launched("kitchen_step");
+}
+
+int earl_kitchen_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                         const earl_kitchen_state* st, const float* action, int32_t T, const earl_kitchen_out* out, earl_stream_t stream) {
+  if (!model || !params || !cfg || !st || !action || !out || cfg->n < 0 || T < 0 || cfg->n_att < 10 || cfg->n_att > 32 || cfg->frame_skip < 0) return EARL_ERR_ARG;
+  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !st->last_qp_robot || !st->att_xpos || !st->steps_since_reset || !st->last_obs) return EARL_ERR_ARG;
+  if (!out->obs || !out->reward || !out->done || !out->success || !cfg->mocap_quat_dev) return EARL_ERR_ARG;
+  for (int k = 0; k < 8; ++k) if (cfg->site_att[k] < 0 || cfg->site_att[k] >= cfg->n_att) return EARL_ERR_ARG;
+  if (cfg->n == 0 || T == 0) return EARL_OK;
+  if (int rc = check_cone(col, false, (hipStream_t)stream, "kitchen_rollout")) return rc;
+  KitchenRolloutArgs k{model, col, *params, *cfg, *st, *out, action, T, solo_mode(cfg->n)};
+  if (k.solo == 2 && g_solo < 0) k.solo = 3;   // one env per workgroup: four waves per env (rows | mass matrix | bias forces | collision, then one wave's active set)
+  if (g_solo < 0 && k.solo == 1 && cfg->n <= 2 * cu_count()) k.solo = 4;      // at most two envs per CU: two envs per workgroup, two waves per env
+  if (k.solo == 3) kitchen_rollout_kernel<1><<<cfg->n, block_for<23>(), 0, (hipStream_t)stream>>>(k);
+  else if (k.solo == 4) kitchen_rollout_kernel<2><<<(cfg->n + 1) / 2, block_for<23>(), 0, (hipStream_t)stream>>>(k);
+  else kitchen_rollout_kernel<0><<<solo_grid(cfg->n, k.solo, Lim<23>::WPB), block_for<23>(), 0, (hipStream_t)stream>>>(k);
+  return launched("kitchen_rollout");
+}
+
+int earl_debug_set_solo(int mode) {          // -1 = by batch size, 0 = two envs per wave, 1 = one env per wave, 2 = one env per workgroup (one wave), 3 = one env per workgroup, four waves, 4 = two envs per workgroup, two waves each (kitchen launches)
+  const int prev = g_solo;
+  if (mode >= -1 && mode <= 4) g_solo = mode;
+  return prev;
+}
+#ifdef EARL_PHYS_PROF
+int earl_debug_set_prof_wave_kitchen(int block, int thread) { return prof_set_wave(block, thread); }     // (tools/prof_kitchen_phases.py)
+int earl_debug_read_wave_cycles_kitchen(unsigned long long* out) { return prof_read_wave_cycles(out); }
+int earl_debug_read_phys_profile_kitchen(unsigned long long* out, int reset) { return prof_read_phases(out, reset); }
+#endif
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // physics_lds.h -- per-model limits (Lim<NV>), the per-env LDS block (Shared<NV>), packed symmetric matrices, friction-cone weights, the collision block table and its staging
-// A section of csrc/physics.hip (included there, inside its anonymous namespace): split out in round 5.
+// A section of csrc/physics_stepper.h (included there, inside its anonymous namespace): split out in round 5.
 
 // Symmetric NV x NV matrix in LDS.  Big models (nv > 10) keep the lower triangle packed row-major (row i, column j <= i at
 // i (i + 1) / 2 + j): half the LDS of a square array, and the env block is what limits the number of waves on a CU.  Small models

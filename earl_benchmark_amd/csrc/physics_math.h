@@ -1,5 +1,5 @@
 // physics_math.h -- small fp64 vector / quaternion algebra, reciprocal / root iterations, impedance formulas
-// A section of csrc/physics.hip (included there, inside its anonymous namespace): split out in round 5.
+// A section of csrc/physics_stepper.h (included there, inside its anonymous namespace): split out in round 5.
 
 __device__ __forceinline__ void fence() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -1,9 +1,93 @@
 // physics_mt.hip -- third build of the articulated-body stepper: the MINITAUR (BASELINE configs[4]).
 //
-// physics.hip instantiated for nv = 22 (Lim<22>: a floating root body + 16 hinges in ONE tree, 32 lanes per env, dense lane-cooperative in-LDS
+// The stepper (physics_stepper.h) instantiated for nv = 22 (Lim<22>: a floating root body + 16 hinges in ONE tree, 32 lanes per env, dense lane-cooperative in-LDS
 // factorisations, connect constraints for the four knee closures, the motor model's torques handed in per timestep, no mocap weld, no joint damping)
 // plus the env kernel (minitaur_kernel: reset incl. its settle steps, fused T-step rollout) and the entry points earl_minitaur_rollout /
 // earl_minitaur_reset.  A translation unit of its own so that the three builds compile side by side.
-#define EARL_PHYS_VARIANT_MT 1
 #include "minitaur_device.h"
-#include "physics.hip"
+#include "physics_stepper.h"
+
+namespace {
+#include "minitaur_stepper.h"
+#include "physics_env_minitaur.h"
+}  // namespace
+
+#include "physics_launch.h"
+
+namespace {
+
+int g_mt_stepper = 1;     // earl_debug_set_minitaur_stepper: 1 = the tree-structured timestep (minitaur_stepper.h), 0 = the generic substep<22>
+int g_mt_duo = EARL_MT_DUO_DEFAULT;   // earl_debug_set_minitaur_duo: 1 = the two-waves-per-SIMD rollout (minitaur_duo_kernel), 0 = the one-wave kernel, -1 = by batch size
+
+// minitaur rollout, packed launches: the one-wave kernel holds 8 envs per CU, the two-wave kernel 16 at 1.6 x the time per round (measured: 4096 x 1000 in 174 ms = two rounds of
+// 87 against one round of 139): whichever needs less time for the batch's rounds
+bool mt_use_duo(int n) {
+  const int cus = cu_count();
+  const long rounds_one = (n + 8L * cus - 1) / (8L * cus), rounds_two = (n + 16L * cus - 1) / (16L * cus);
+  return 16 * rounds_two < 10 * rounds_one;
+}
+
+}  // namespace
+
+extern "C" {
+
+int earl_minitaur_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                          const float* action, int32_t T, const earl_minitaur_out* out, earl_stream_t stream) {
+  if (!model24 || !cfg || !st || !out || !action || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
+  if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
+  if (!out->obs || !out->reward || !out->done || !out->success || !cfg->goal_table || cfg->n_goals < 1 || cfg->num_substeps < 0) return EARL_ERR_ARG;
+  if (cfg->n == 0 || T == 0) return EARL_OK;
+  if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_rollout")) return rc;
+  MinitaurArgs a{model24, col, *cfg, *st, *out, action, T, nullptr, nullptr, solo_mode(cfg->n)};
+  // two waves per SIMD by role (minitaur_duo_kernel: 16 envs per workgroup of eight waves) for batches that fill the chip's wave slots in the packed form anyway
+  if (g_mt_stepper && a.solo == 0 && cfg->num_substeps > 0 && (g_mt_duo > 0 || (g_mt_duo < 0 && mt_use_duo(cfg->n)))) {      // (num_substeps = 0: nothing to split)
+    minitaur_duo_kernel<<<(unsigned)((cfg->n + 16 * MT_DUO_PAIRS / 4 - 1) / (4 * MT_DUO_PAIRS)), 128 * MT_DUO_PAIRS, 0, (hipStream_t)stream>>>(a);
+    return launched("minitaur_rollout (two waves per SIMD)");
+  }
+  if (g_mt_stepper) minitaur_kernel<false, true><<<solo_grid(cfg->n, a.solo, EARL_MT_WPB), 64 * EARL_MT_WPB, 0, (hipStream_t)stream>>>(a);
+  else minitaur_kernel<false, false><<<solo_grid(cfg->n, a.solo, Lim<22>::WPB), block_for<22>(), 0, (hipStream_t)stream>>>(a);
+  return launched("minitaur_rollout");
+}
+int earl_minitaur_reset(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                        const uint8_t* mask, double* obs, earl_stream_t stream) {
+  if (!model24 || !cfg || !st || cfg->n < 0) return EARL_ERR_ARG;
+  if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
+  if (!cfg->goal_table || !cfg->reset_qpos || cfg->n_goals < 1 || cfg->settle_steps < 0) return EARL_ERR_ARG;
+  if (cfg->n == 0) return EARL_OK;
+  if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_reset")) return rc;
+  MinitaurArgs a{model24, col, *cfg, *st, earl_minitaur_out{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr, 0, mask, obs, solo_mode(cfg->n)};
+  if (g_mt_stepper) minitaur_kernel<true, true><<<solo_grid(cfg->n, a.solo, EARL_MT_WPB), 64 * EARL_MT_WPB, 0, (hipStream_t)stream>>>(a);
+  else minitaur_kernel<true, false><<<solo_grid(cfg->n, a.solo, Lim<22>::WPB), block_for<22>(), 0, (hipStream_t)stream>>>(a);
+  return launched("minitaur_reset");
+}
+int earl_minitaur_cfg_size(void) { return (int)sizeof(earl_minitaur_cfg); }
+int earl_debug_set_solo_mt(int mode) {       // this unit's copy of the small-batch switch (earl_debug_set_solo): the minitaur launches
+  const int prev = g_solo;
+  if (mode >= -1 && mode <= 2) g_solo = mode;
+  return prev;
+}
+int earl_debug_set_minitaur_stepper(int tree) {          // 1 (default): minitaur_stepper.h, 0: the generic substep<22> (comparison / measurement)
+  if (tree != 0 && tree != 1) return EARL_ERR_ARG;
+  g_mt_stepper = tree;
+  return EARL_OK;
+}
+int earl_debug_set_minitaur_duo(int mode) {              // 1: the two-waves-per-SIMD rollout kernel for every packed launch, 0: never, -1: by batch size (default).  Returns the previous setting
+  const int prev = g_mt_duo;
+  if (mode >= -1 && mode <= 1) g_mt_duo = mode;
+  return prev;
+}
+#ifdef EARL_MT_DEBUG
+int earl_debug_read_mt_dbg(int* out_i, double* out_d) {
+  if (hipMemcpyFromSymbol(out_i, HIP_SYMBOL(g_mt_dbg), sizeof(int) * 4096 * 8 * 32) != hipSuccess) return EARL_ERR_LAUNCH;
+  if (hipMemcpyFromSymbol(out_d, HIP_SYMBOL(g_mt_dbg_al), sizeof(double) * 4096 * 8 * 32) != hipSuccess) return EARL_ERR_LAUNCH;
+  if (hipMemcpyFromSymbol(out_d + 4096 * 8 * 32, HIP_SYMBOL(g_mt_dbg_x), sizeof(double) * 5 * 4096 * 8 * 32) != hipSuccess) return EARL_ERR_LAUNCH;
+  return hipMemcpyFromSymbol(out_d + 6 * 4096 * 8 * 32, HIP_SYMBOL(g_mt_dbg_ph), sizeof(double) * 8 * 4096 * 8 * 32) == hipSuccess ? EARL_OK : EARL_ERR_LAUNCH;
+}
+#endif
+#ifdef EARL_PHYS_PROF
+int earl_debug_set_prof_wave_mt(int block, int thread) { return prof_set_wave(block, thread); }     // (minitaur_duo_kernel: thread 0 = a first-half wave, thread 256 = its partner)
+int earl_debug_read_wave_cycles_mt(unsigned long long* out) { return prof_read_wave_cycles(out); }
+int earl_debug_read_phys_profile_mt(unsigned long long* out, int reset) { return prof_read_phases(out, reset); }     // (tools/prof_minitaur.py)
+#endif
+
+}  // extern "C"

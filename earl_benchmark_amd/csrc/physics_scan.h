@@ -1,5 +1,5 @@
 // physics_scan.h -- DPP row shifts and the prefix / suffix scans along the arm chain (Lim<NV>::ARMSCAN)
-// A section of csrc/physics.hip (included there, inside its anonymous namespace): split out in round 5.
+// A section of csrc/physics_stepper.h (included there, inside its anonymous namespace): split out in round 5.
 
 // DPP moves within a 16-lane row: lane l reads lane l - K (shr) / l + K (shl) of its row, 0 beyond the row
 template <int CTRL>

@@ -1,5 +1,5 @@
 // physics_solve.h -- Cholesky factorisations and solves: register-resident (per lane, redundant), lane-cooperative in LDS, row-distributed, leading-block and Schur-complement forms
-// A section of csrc/physics.hip (included there, inside its anonymous namespace): split out in round 5.
+// A section of csrc/physics_stepper.h (included there, inside its anonymous namespace): split out in round 5.
 
 // Cholesky of an SPD matrix held in registers (lower triangle, row-major packed); the diagonal is left INVERTED.
 // NA < NV: the matrix is block diagonal, rows / columns [0, NA) and [NA, NV) -- the arm and the free object are separate

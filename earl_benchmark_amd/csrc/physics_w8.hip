@@ -12,5 +12,27 @@
                                 // while this build still reloaded spilled values inside the timestep -- 73.1 against 77.4 ms; with those gone it is the
                                 // slower one: 60.3 against 57.5 ms.)
 #define EARL_NO_PREFETCH 1      // no prefetch of the first near block's pair record: the second wave hides that latency, the 22 registers are worth more
-#define EARL_PHYS_VARIANT_W8 1
-#include "physics.hip"
+#include "physics_stepper.h"
+
+namespace {
+#include "physics_env_sawyer.h"
+}  // namespace
+
+#include "physics_launch.h"
+
+extern "C" {
+
+int earl_sawyer_rollout_door_w8(const earl_link_model* model, const earl_collision_model* col, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream) {
+  SawyerArgs a{model, col, *cfg, *st, action, T, *out, nullptr, nullptr, nullptr, nullptr, 0};
+  sawyer_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
+  return launched("sawyer_rollout (door, 8 waves per CU)");
+}
+
+#ifdef EARL_PHYS_PROF
+int earl_debug_set_prof_wave_w8(int block, int thread) { return prof_set_wave(block, thread); }     // (eight-wave workgroups: thread = 64 x the wave)
+int earl_debug_read_wave_cycles_w8(unsigned long long* out) { return prof_read_wave_cycles(out); }
+int earl_debug_read_phys_profile_w8(unsigned long long* out, int reset) { return prof_read_phases(out, reset); }
+#endif
+
+}  // extern "C"

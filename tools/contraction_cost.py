@@ -1,5 +1,5 @@
 """What does floating-point contraction buy the four articulated-body steppers?  The shipped units compile under `#pragma clang fp contract(fast)`
-(csrc/physics.hip); tools/build_phys_variant.sh nocontract -DEARL_PHYS_NO_CONTRACT builds them under -ffp-contract=off (explicit fma() only, as the tabletop path and the
+(csrc/physics_stepper.h); tools/build_phys_variant.sh nocontract -DEARL_PHYS_NO_CONTRACT builds them under -ffp-contract=off (explicit fma() only, as the tabletop path and the
 C restatement are built).  This script times the bench's four launches through both libraries on one MI355X and reports how far the observations of the two builds
 are apart after one full-horizon rollout.
 

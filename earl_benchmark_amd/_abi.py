@@ -148,6 +148,11 @@ SIGNATURES = {
     'earl_kitchen_rollout': [C.c_void_p, C.c_void_p, _P(KitchenParams), _P(KitchenCfg), _P(KitchenState), C.c_void_p, C.c_int32, _P(KitchenOut), C.c_void_p],
     'earl_sawyer_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), C.c_void_p, C.c_int32, _P(SawyerOut), C.c_void_p],
     'earl_minitaur_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_int32, _P(MinitaurOut), C.c_void_p],
+    # the clocked forms (include/earl_physics.h): a DEVICE pointer to two uint64 (NULL = zero) before `out`
+    'earl_sawyer_rollout_clocked': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), C.c_void_p, C.c_int32, C.c_void_p, _P(SawyerOut), C.c_void_p],
+    'earl_kitchen_rollout_clocked': [C.c_void_p, C.c_void_p, _P(KitchenParams), _P(KitchenCfg), _P(KitchenState), C.c_void_p, C.c_int32, C.c_void_p, _P(KitchenOut),
+                                     C.c_void_p],
+    'earl_minitaur_rollout_clocked': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_int32, C.c_void_p, _P(MinitaurOut), C.c_void_p],
     'earl_minitaur_reset': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_minitaur_cfg_size': [],
     'earl_debug_set_minitaur_stepper': [C.c_int],

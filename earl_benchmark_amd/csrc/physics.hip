@@ -111,15 +111,15 @@ int earl_physics_forward(const void* model, const earl_collision_model* col, int
   return launched("physics_forward");
 }
 
-int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
-                        const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream) {
+int earl_sawyer_rollout_clocked(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                const float* action, int32_t T, const uint64_t* clock, const earl_sawyer_out* out, earl_stream_t stream) {
   if (!model || !cfg || !st || !out || !action || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !out->obs) return EARL_ERR_ARG;
   if (cfg->frame_skip < 0 || cfg->att_hand < 0 || cfg->att_right < 0 || cfg->att_left < 0 || cfg->att_obj < 0) return EARL_ERR_ARG;
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (nv != 10 && nv != 15) return EARL_ERR_ARG;
   if (int rc = check_cone(col, true, (hipStream_t)stream, "sawyer_rollout")) return rc;
-  SawyerArgs a{model, col, *cfg, *st, action, T, *out, nullptr, nullptr, nullptr, nullptr, 0};
+  SawyerArgs a{model, col, *cfg, *st, action, T, *out, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
   if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && (!st->obj_init || cfg->att_grasp < 0 || cfg->att_lpad < 0 || cfg->att_rpad < 0))
     return EARL_ERR_ARG;                                  // the peg's dense reward needs the reset-time state and the pad / grasp attachments
   if (nv == 10 && g_lpe != 64 && g_door_variant == 3 && st->sched && T > 1) {
@@ -129,7 +129,7 @@ int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model
     return launched("sawyer_rollout (door, time-sliced)");
   }
   if (nv == 10 && g_lpe != 64 && (g_door_variant == 2 || (g_door_variant == 0 && cfg->n > 4096)))
-    return earl_sawyer_rollout_door_w8(model, col, cfg, st, action, T, out, stream);      // eight waves per CU: wins from two rounds of 4096 envs on
+    return earl_unit_w8_sawyer_rollout(&a, stream);      // eight waves per CU: wins from two rounds of 4096 envs on
   if (nv == 10) {
     if (g_lpe == 64) earl_unit_l64_sawyer_rollout(&a, 10, stream);
     else sawyer_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
@@ -146,6 +146,10 @@ int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model
   } else return EARL_ERR_ARG;
   return launched("sawyer_rollout");
 }
+int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                        const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream) {
+  return earl_sawyer_rollout_clocked(model, col, nv, cfg, st, action, T, nullptr, out, stream);
+}
 
 int earl_sawyer_reset(const earl_link_model* model, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                       const double* reset_qpos, const double* reset_qvel, const uint8_t* mask, double* obs,
@@ -156,7 +160,7 @@ int earl_sawyer_reset(const earl_link_model* model, int32_t nv, const earl_sawye
   if (cfg->obj_kind >= 1 && cfg->obj_dof + 6 > nv) return EARL_ERR_ARG;
   if (cfg->obj_kind == 2 && (cfg->n_wide <= 0 || !cfg->wide_table)) return EARL_ERR_ARG;
   if (cfg->n == 0) return EARL_OK;
-  SawyerArgs a{model, nullptr, *cfg, *st, nullptr, 0, earl_sawyer_out{nullptr, nullptr, nullptr, nullptr, nullptr}, reset_qpos, reset_qvel, mask, obs, 0};
+  SawyerArgs a{model, nullptr, *cfg, *st, nullptr, 0, earl_sawyer_out{nullptr, nullptr, nullptr, nullptr, nullptr}, reset_qpos, reset_qvel, mask, obs, 0, 0, nullptr};
   if (nv == 10) sawyer_reset_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
   else if (nv == 15) sawyer_reset_kernel<15, 16><<<grid_for<15, 16>(cfg->n), block_for<15>(), 0, (hipStream_t)stream>>>(a);
   else return EARL_ERR_ARG;
@@ -168,7 +172,7 @@ int earl_sawyer_observe(const earl_link_model* model, int32_t nv, const earl_saw
   if (!model || !cfg || !st || !obs || cfg->n < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal) return EARL_ERR_ARG;
   if (cfg->n == 0) return EARL_OK;
-  SawyerArgs a{model, nullptr, *cfg, *st, nullptr, 0, earl_sawyer_out{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, nullptr, obs, 1};
+  SawyerArgs a{model, nullptr, *cfg, *st, nullptr, 0, earl_sawyer_out{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, nullptr, obs, 1, 0, nullptr};
   if (nv == 10) sawyer_reset_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
   else if (nv == 15) sawyer_reset_kernel<15, 16><<<grid_for<15, 16>(cfg->n), block_for<15>(), 0, (hipStream_t)stream>>>(a);
   else return EARL_ERR_ARG;

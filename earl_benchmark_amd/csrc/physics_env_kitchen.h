@@ -73,6 +73,7 @@ struct KitchenRolloutArgs {
   int solo;                      // small batches (round 5): 1 = ONE env per wave -- the wave's second 32-lane group shadows the first one's env (same state, same actions, same
                                  // branches; stores nothing), so the env's chain of timesteps is not held up by a wave-mate on a longer path; 2 = also one wave per workgroup
                                  // (waves 1-3 leave after the tables are staged): every env has a CU's LDS and issue slots to itself.  Same numbers as the packed launch.
+  const uint64_t* clock;         // earl_kitchen_rollout_clocked: DEVICE words, [0] added to cfg.counter (NULL = zero); read where the noise is drawn, once per env step
 };
 __device__ __forceinline__ double kit_norm_diff(const double* a, const double* b, const int n) {     // glue.hip norm_diff
   double d = 0.0;
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(64 * Lim<23>::WPB) void kitchen_rollout_kernel(cons
       }
       // Robot.get_obs + KitchenV0._get_obs: 46 draws of U(-1, 1) per env (uniform_kernel: one Philox block = two draws), then kitchen_obs_kernel
       if (cfg.sensor_noise && sub < 23) {
-        const uint64_t ctr = cfg.counter + (uint64_t)t;
+        const uint64_t ctr = cfg.counter + (a.clock ? a.clock[0] : 0) + (uint64_t)t;      // + the clock word of a graph-captured launch (earl_kitchen_rollout_clocked)
         const earl::U4 b = earl::philox4x32_10(earl::U4{0x4B00u + (uint32_t)sub, (uint32_t)(cfg.env_offset + env), (uint32_t)ctr, (uint32_t)(ctr >> 32)},
                                                (uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32));
         const double lo = -1.0, hi = 1.0;

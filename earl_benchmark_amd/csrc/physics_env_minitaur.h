@@ -15,6 +15,7 @@ struct MinitaurArgs {
   const float* action; int T;
   const uint8_t* mask; double* reset_obs;
   int solo;                      // as KitchenRolloutArgs::solo
+  const uint64_t* clock;         // earl_minitaur_rollout_clocked: DEVICE words, [1] added to cfg.step_counter (NULL = zero); read where a goal-switch draw is made
 };
 __device__ __forceinline__ double mt_draw(const earl_minitaur_cfg& cfg, const uint32_t stream, const int env, const uint64_t counter) {
   const earl::U4 b = earl::philox4x32_10(earl::U4{stream, (uint32_t)(cfg.env_offset + env), (uint32_t)counter, (uint32_t)(counter >> 32)},
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(64 * mt_wpb<ARROW>(), ARROW ? EARL_MT_BLOCKS : 1) v
       }
       if (gcf > 0 && ++sgc >= gcf) {                      // LifelongWrapper.step (lifelong_wrapper.py:36-42): new goal, the observation re-read with it
         sgc = 0;
-        int gi = (int)(mt_draw(cfg, 0xFFFEu, env, cfg.step_counter + (uint64_t)t) * (double)cfg.n_goals);
+        int gi = (int)(mt_draw(cfg, 0xFFFEu, env, cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t) * (double)cfg.n_goals);
         gi = gi >= cfg.n_goals ? cfg.n_goals - 1 : gi;
         goal0 = cfg.goal_table[2 * gi]; goal1 = cfg.goal_table[2 * gi + 1];
         if (live && sub >= 30) a.out.obs[row * 32 + sub] = sub == 30 ? goal0 : goal1;
@@ -374,7 +375,7 @@ __global__ __launch_bounds__(128 * MT_DUO_PAIRS, 1) void minitaur_duo_kernel(con
     fence();
     if (gcf > 0 && ++sgc >= gcf) {                      // LifelongWrapper.step (lifelong_wrapper.py:36-42): new goal, the observation re-read with it
       sgc = 0;
-      int gi = (int)(mt_draw(cfg, 0xFFFEu, env, cfg.step_counter + (uint64_t)t) * (double)cfg.n_goals);
+      int gi = (int)(mt_draw(cfg, 0xFFFEu, env, cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t) * (double)cfg.n_goals);
       gi = gi >= cfg.n_goals ? cfg.n_goals - 1 : gi;
       goal0 = cfg.goal_table[2 * gi]; goal1 = cfg.goal_table[2 * gi + 1];
       if (live && sub >= 30) a.out.obs[row * 32 + sub] = sub == 30 ? goal0 : goal1;

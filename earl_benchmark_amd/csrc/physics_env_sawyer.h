@@ -13,6 +13,7 @@ struct SawyerArgs {
   const double* reset_qpos; const double* reset_qvel; const uint8_t* mask; double* reset_obs;
   int observe_only;
   int slice;                     // SLICED rollout: env steps per work item (0: one item = the whole rollout of a group)
+  const uint64_t* clock;         // earl_sawyer_rollout_clocked: DEVICE words added to cfg.counter / cfg.step_counter (NULL = zero); [1] is read where a goal-switch draw is made
 };
 
 // Work queue of the time-sliced rollout (earl_sawyer_state.sched: progress[G] then lock[G], zero on entry).  An env group's state is in HBM after every env
@@ -342,7 +343,9 @@ __global__ __launch_bounds__(64 * Lim<NV>::WPB, EARL_WAVES_PER_EU) void sawyer_r
       // goal (same simulator state: only the goal block changes); the reward above used the old goal
       sgc = 0;
       if (cfg.n_goal_rows > 0 && cfg.goal_table && sub >= 7 && sub < 14 && live) {      // the lanes that wrote the goal block of this row
-        const uint64_t ev = cfg.step_counter + (uint64_t)t;
+        // the host's step counter plus the clock word of a graph-captured launch (earl_sawyer_rollout_clocked), read here -- a goal-switch step -- and not at kernel
+        // entry: a value held across the rollout loop costs the time-sliced peg build 32 B of scratch per lane and the 64-lane door build two AGPRs
+        const uint64_t ev = cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t;
         const earl::U4 b = earl::philox4x32_10(earl::U4{0xFFFEu, (uint32_t)(cfg.env_offset + env), (uint32_t)ev, (uint32_t)(ev >> 32)},
                                                (uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32));
         int grow = (int)(earl::u01(b.x, b.y) * (double)cfg.n_goal_rows);

@@ -47,21 +47,25 @@ int earl_kitchen_step(const void* model, const earl_collision_model* col, const 
   return launched("kitchen_step");
 }
 
-int earl_kitchen_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
-                         const earl_kitchen_state* st, const float* action, int32_t T, const earl_kitchen_out* out, earl_stream_t stream) {
+int earl_kitchen_rollout_clocked(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                                 const earl_kitchen_state* st, const float* action, int32_t T, const uint64_t* clock, const earl_kitchen_out* out, earl_stream_t stream) {
   if (!model || !params || !cfg || !st || !action || !out || cfg->n < 0 || T < 0 || cfg->n_att < 10 || cfg->n_att > 32 || cfg->frame_skip < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !st->last_qp_robot || !st->att_xpos || !st->steps_since_reset || !st->last_obs) return EARL_ERR_ARG;
   if (!out->obs || !out->reward || !out->done || !out->success || !cfg->mocap_quat_dev) return EARL_ERR_ARG;
   for (int k = 0; k < 8; ++k) if (cfg->site_att[k] < 0 || cfg->site_att[k] >= cfg->n_att) return EARL_ERR_ARG;
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "kitchen_rollout")) return rc;
-  KitchenRolloutArgs k{model, col, *params, *cfg, *st, *out, action, T, solo_mode(cfg->n)};
+  KitchenRolloutArgs k{model, col, *params, *cfg, *st, *out, action, T, solo_mode(cfg->n), clock};
   if (k.solo == 2 && g_solo < 0) k.solo = 3;   // one env per workgroup: four waves per env (rows | mass matrix | bias forces | collision, then one wave's active set)
   if (g_solo < 0 && k.solo == 1 && cfg->n <= 2 * cu_count()) k.solo = 4;      // at most two envs per CU: two envs per workgroup, two waves per env
   if (k.solo == 3) kitchen_rollout_kernel<1><<<cfg->n, block_for<23>(), 0, (hipStream_t)stream>>>(k);
   else if (k.solo == 4) kitchen_rollout_kernel<2><<<(cfg->n + 1) / 2, block_for<23>(), 0, (hipStream_t)stream>>>(k);
   else kitchen_rollout_kernel<0><<<solo_grid(cfg->n, k.solo, Lim<23>::WPB), block_for<23>(), 0, (hipStream_t)stream>>>(k);
   return launched("kitchen_rollout");
+}
+int earl_kitchen_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                         const earl_kitchen_state* st, const float* action, int32_t T, const earl_kitchen_out* out, earl_stream_t stream) {
+  return earl_kitchen_rollout_clocked(model, col, params, cfg, st, action, T, nullptr, out, stream);
 }
 
 int earl_debug_set_solo(int mode) {          // -1 = by batch size, 0 = two envs per wave, 1 = one env per wave, 2 = one env per workgroup (one wave), 3 = one env per workgroup, four waves, 4 = two envs per workgroup, two waves each (kitchen launches)

@@ -31,14 +31,14 @@ bool mt_use_duo(int n) {
 
 extern "C" {
 
-int earl_minitaur_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
-                          const float* action, int32_t T, const earl_minitaur_out* out, earl_stream_t stream) {
+int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                  const float* action, int32_t T, const uint64_t* clock, const earl_minitaur_out* out, earl_stream_t stream) {
   if (!model24 || !cfg || !st || !out || !action || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
   if (!out->obs || !out->reward || !out->done || !out->success || !cfg->goal_table || cfg->n_goals < 1 || cfg->num_substeps < 0) return EARL_ERR_ARG;
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_rollout")) return rc;
-  MinitaurArgs a{model24, col, *cfg, *st, *out, action, T, nullptr, nullptr, solo_mode(cfg->n)};
+  MinitaurArgs a{model24, col, *cfg, *st, *out, action, T, nullptr, nullptr, solo_mode(cfg->n), clock};
   // two waves per SIMD by role (minitaur_duo_kernel: 16 envs per workgroup of eight waves) for batches that fill the chip's wave slots in the packed form anyway
   if (g_mt_stepper && a.solo == 0 && cfg->num_substeps > 0 && (g_mt_duo > 0 || (g_mt_duo < 0 && mt_use_duo(cfg->n)))) {      // (num_substeps = 0: nothing to split)
     minitaur_duo_kernel<<<(unsigned)((cfg->n + 16 * MT_DUO_PAIRS / 4 - 1) / (4 * MT_DUO_PAIRS)), 128 * MT_DUO_PAIRS, 0, (hipStream_t)stream>>>(a);
@@ -48,6 +48,10 @@ int earl_minitaur_rollout(const void* model24, const earl_collision_model* col, 
   else minitaur_kernel<false, false><<<solo_grid(cfg->n, a.solo, Lim<22>::WPB), block_for<22>(), 0, (hipStream_t)stream>>>(a);
   return launched("minitaur_rollout");
 }
+int earl_minitaur_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                          const float* action, int32_t T, const earl_minitaur_out* out, earl_stream_t stream) {
+  return earl_minitaur_rollout_clocked(model24, col, cfg, st, action, T, nullptr, out, stream);
+}
 int earl_minitaur_reset(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                         const uint8_t* mask, double* obs, earl_stream_t stream) {
   if (!model24 || !cfg || !st || cfg->n < 0) return EARL_ERR_ARG;
@@ -55,7 +59,7 @@ int earl_minitaur_reset(const void* model24, const earl_collision_model* col, co
   if (!cfg->goal_table || !cfg->reset_qpos || cfg->n_goals < 1 || cfg->settle_steps < 0) return EARL_ERR_ARG;
   if (cfg->n == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_reset")) return rc;
-  MinitaurArgs a{model24, col, *cfg, *st, earl_minitaur_out{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr, 0, mask, obs, solo_mode(cfg->n)};
+  MinitaurArgs a{model24, col, *cfg, *st, earl_minitaur_out{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr, 0, mask, obs, solo_mode(cfg->n), nullptr};
   if (g_mt_stepper) minitaur_kernel<true, true><<<solo_grid(cfg->n, a.solo, EARL_MT_WPB), 64 * EARL_MT_WPB, 0, (hipStream_t)stream>>>(a);
   else minitaur_kernel<true, false><<<solo_grid(cfg->n, a.solo, Lim<22>::WPB), block_for<22>(), 0, (hipStream_t)stream>>>(a);
   return launched("minitaur_reset");

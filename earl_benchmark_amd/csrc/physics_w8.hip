@@ -22,11 +22,15 @@ namespace {
 
 extern "C" {
 
+int earl_unit_w8_sawyer_rollout(const void* sawyer_args, void* stream) {
+  const SawyerArgs& a = *static_cast<const SawyerArgs*>(sawyer_args);
+  sawyer_rollout_kernel<10, 16><<<grid_for<10, 16>(a.cfg.n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
+  return launched("sawyer_rollout (door, 8 waves per CU)");
+}
 int earl_sawyer_rollout_door_w8(const earl_link_model* model, const earl_collision_model* col, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                 const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream) {
-  SawyerArgs a{model, col, *cfg, *st, action, T, *out, nullptr, nullptr, nullptr, nullptr, 0};
-  sawyer_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
-  return launched("sawyer_rollout (door, 8 waves per CU)");
+  SawyerArgs a{model, col, *cfg, *st, action, T, *out, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr};
+  return earl_unit_w8_sawyer_rollout(&a, stream);
 }
 
 #ifdef EARL_PHYS_PROF

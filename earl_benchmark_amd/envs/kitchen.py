@@ -21,6 +21,7 @@ right counter and the floor are not collided).  **PARITY WITH MUJOCO IS UNPINNED
 run here.  What is pinned: the numpy glue around the simulator (bit-exact on goldens recorded from the reference's own methods),
 the model tables' provenance, and the kernel against this build's CPU statement (oracle/physics_oracle.LinkModel).
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -28,6 +29,7 @@ import torch
 
 from .. import _abi, glue, physics, tables
 from ..spaces import Box
+from .physics_step_graph import PhysicsStepGraph
 
 INT32_MAX = 2**31 - 1
 FRAME_SKIP = 40                                           # kitchen_multitask_v0.py:40
@@ -228,6 +230,51 @@ class Kitchen:
     if self.scalar_api:
       return obs[0].cpu().numpy(), float(rew[0]), bool(done[0]), info
     return obs, rew, done, info
+
+  def make_step_graph(self, T, policy=None):
+    """Closed-loop stepping without the per-call host cost: T step() launches (the fused rollout with T = 1, sensor noise drawn on the replay's counters)
+    captured into a HIP graph, replayed with one host call (see `PhysicsStepGraph`).  The lifelong goal switch runs on the host: ValueError with
+    goal_change_frequency > 0.  The graph's info is 'success' / 'is_successful' / 'status', not the full env_info."""
+    return PhysicsStepGraph(self, T, policy)
+
+  # hooks of PhysicsStepGraph: one captured step = the clocked fused launch with T = 1 into the graph's output rows
+  _graph_bounds = None
+
+  def _graph_check(self):
+    if int(self._cfg.goal_change_frequency) > 0:
+      raise ValueError('kitchen: the lifelong goal switch runs on the host (goal_change_frequency > 0) and cannot be captured by make_step_graph')
+
+  def _new_graph_out(self, T):
+    n, kw = self.num_envs, dict(device=self.device)
+    return dict(obs=torch.empty(T, n, self.OBS_DIM, dtype=torch.float64, **kw), reward=torch.empty(T, n, dtype=torch.float64, **kw),
+                done=torch.empty(T, n, dtype=torch.bool, **kw), success=torch.empty(T, n, dtype=torch.bool, **kw), status=torch.empty(T, n, dtype=torch.uint8, **kw))
+
+  @contextlib.contextmanager
+  def _graph_capture(self):
+    c = self._cfg.counter
+    try:
+      yield
+    finally:
+      self._cfg.counter = c
+
+  def _graph_step(self, t, action, out, clock):
+    o = _abi.KitchenOut(obs=out['obs'].data_ptr(), reward=out['reward'].data_ptr(), done=out['done'].data_ptr(), success=out['success'].data_ptr(),
+                        status=out['status'].data_ptr())
+    self._cfg.counter = t                                  # the noise draws of the captured step t: clock[0] + t
+    with torch.cuda.device(self.device):
+      _abi.check(self._lib.earl_kitchen_rollout_clocked(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._params), C.byref(self._cfg),
+                                                        C.byref(self._st), action.data_ptr(), 1, clock, C.byref(o), self._stream()), 'earl_kitchen_rollout_clocked')
+
+  def _graph_clock(self):
+    return self._counter, self.total_step_count
+
+  def _graph_advance(self, T, out):
+    self._counter += T
+    self.total_step_count += T
+    self._last_success = out['success'][-1]
+
+  def _graph_info(self, out):
+    return {'success': out['success'], 'is_successful': out['success'], 'status': out['status']}
 
   def _env_info(self, obs, rew, suc, status, counter):
     """The env_info dict of KitchenV0.step (reference adept_envs/franka/kitchen_multitask_v0.py:116-123): 'time' (simulation time of the observation: sim.reset()

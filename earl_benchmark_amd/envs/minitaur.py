@@ -13,6 +13,7 @@ this build's own authoring on this build's own stepper (MuJoCo-style soft constr
 [UPSTREAM pybullet_envs.bullet.minitaur_env_randomizer, restated from memory] is built in the reset kernel: battery voltage, motor damping, base /
 leg-link / motor masses, foot friction, through the semantics of the reference's own setters (envs/minitaur.py:468-508).  DESIGN.md section 14.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -20,6 +21,7 @@ import torch
 
 from .. import _abi, physics
 from ..spaces import Box
+from .physics_step_graph import PhysicsStepGraph
 
 INT32_MAX = 2**31 - 1
 NUM_SUBSTEPS, SETTLE_STEPS = 5, 100                       # minitaur_gym_env.py:25, 161-164; :265-269
@@ -169,6 +171,48 @@ class Minitaur:
     if self.scalar_api:
       return obs[0].cpu().numpy(), float(rew[0]), bool(done[0]), {'success': float(suc[0])}
     return obs, rew, done, {'success': suc, 'status': res['status'][0]}
+
+  def make_step_graph(self, T, policy=None):
+    """Closed-loop stepping without the per-call host cost: T step() launches captured into a HIP graph, replayed with one host call (see `PhysicsStepGraph`).
+    An out-of-bounds action cannot raise inside the graph: g.check_actions() raises the reference's ValueError after a replay."""
+    return PhysicsStepGraph(self, T, policy)
+
+  # hooks of PhysicsStepGraph: one captured step = the clocked T = 1 launch into the graph's output rows
+  _graph_bounds = (-ACTION_BOUND - ACTION_EPS, ACTION_BOUND + ACTION_EPS)      # minitaur_gym_env.py:276-281 (flagged per step, see _actions)
+
+  def _graph_check(self):
+    pass
+
+  def _new_graph_out(self, T):
+    return self._new_out((T,))
+
+  @contextlib.contextmanager
+  def _graph_capture(self):
+    sc = self._cfg.step_counter
+    try:
+      yield
+    finally:
+      self._cfg.step_counter = sc
+
+  def _graph_step(self, t, action, out, clock):
+    o = _abi.MinitaurOut(obs=out['obs'].data_ptr(), reward=out['reward'].data_ptr(), done=out['done'].data_ptr(), success=out['success'].data_ptr(),
+                         status=out['status'].data_ptr())
+    self._cfg.step_counter = t                             # the goal-switch draws of the captured step t: clock[1] + t
+    with torch.cuda.device(self.device):
+      _abi.check(self._lib.earl_minitaur_rollout_clocked(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), action.data_ptr(), 1,
+                                                         clock, C.byref(o), self._stream()), 'earl_minitaur_rollout_clocked')
+      if int(self._cfg.goal_change_frequency) > 0:
+        self.lifelong_return_t += out['reward'].reshape(1, -1).sum(0)
+
+  def _graph_clock(self):
+    return self._counter, self.total_step_count
+
+  def _graph_advance(self, T, out):
+    self.total_step_count += T
+    self._last_success = out['success'][-1]
+
+  def _graph_info(self, out):
+    return {'success': out['success'], 'status': out['status']}
 
   def _get_obs(self):
     """GetObservation + goal of the CURRENT state (:541-546): no simulation, the newest observed torques"""

@@ -12,6 +12,7 @@ pinned: the sparse success rule (bit-exact on the reference's demonstrations), t
 (the reference's recorded handle / hand positions), the reset pose (6 mm).  `SawyerXYZEnv.step` semantics are upstream
 metaworld behaviour restated from SURVEY.md Appendix D.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -19,6 +20,7 @@ import torch
 
 from .. import _abi, physics
 from ..spaces import Box
+from .physics_step_graph import PhysicsStepGraph
 
 INT32_MAX = 2**31 - 1
 
@@ -205,25 +207,33 @@ class SawyerDoor:
             'info': torch.empty(*lead, self.num_envs, _abi.SAWYER_INFO, dtype=torch.float64, **kw)}
 
   def _launch_rollout(self, actions, T, out):
+    self._cfg.step_counter = self.total_step_count
+    self._issue_rollout(actions, T, out)
+    self.total_step_count += T
+    if self._cfg.goal_change_frequency:
+      self.lifelong_return_t += out['reward'].reshape(T, -1).sum(0, dtype=torch.float64)
+    self._last_success = out['success'][-1] if out['success'].dim() == 2 else out['success']
+
+  def _issue_rollout(self, actions, T, out, clock=None):
+    """the launches of T env steps into `out` (the door's info launch included); clock: the device words of earl_sawyer_rollout_clocked (None: earl_sawyer_rollout)"""
     info = out.get('info')
     in_kernel = info is not None and self.nv >= 15        # the peg's dict needs simulator state: the rollout kernel's epilogue writes it
     # door, lifelong goal switching: the kernel leaves the PRE-switch target on goal-switch rows (slots 0-2, marker in slot 7) for earl_sawyer_door_info
     stash = info is not None and self.nv < 15 and bool(self._cfg.goal_change_frequency)
     o = _abi.SawyerOut(obs=out['obs'].data_ptr(), reward=_ptr(out.get('reward')), done=_ptr(out.get('done')),
                        success=_ptr(out.get('success')), status=_ptr(out.get('status')), info=_ptr(info) if (in_kernel or stash) else None)
-    self._cfg.step_counter = self.total_step_count
     with torch.cuda.device(self.device):
       if self.sched is not None and T > 1 and self._uses_queue(T):
         self.sched.zero_()                                 # (the queue of the time-sliced schedule: zero on entry)
-      _abi.check(self._lib.earl_sawyer_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, actions.data_ptr(),
-                                               T, C.byref(o), self._stream()), 'earl_sawyer_rollout')
+      if clock is None:
+        _abi.check(self._lib.earl_sawyer_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, actions.data_ptr(),
+                                                 T, C.byref(o), self._stream()), 'earl_sawyer_rollout')
+      else:
+        _abi.check(self._lib.earl_sawyer_rollout_clocked(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref,
+                                                         actions.data_ptr(), T, clock, C.byref(o), self._stream()), 'earl_sawyer_rollout_clocked')
       if info is not None and not in_kernel:               # the door's dict is a function of the emitted observation rows
         _abi.check(self._lib.earl_sawyer_door_info(self._cfg_ref, T * self.num_envs, out['obs'].data_ptr(), _ptr(out.get('status')), info.data_ptr(),
                                                    self._stream()), 'earl_sawyer_door_info')
-    self.total_step_count += T
-    if self._cfg.goal_change_frequency:
-      self.lifelong_return_t += out['reward'].reshape(T, -1).sum(0, dtype=torch.float64)
-    self._last_success = out['success'][-1] if out['success'].dim() == 2 else out['success']
 
   def _actions(self, action, lead):
     a = torch.as_tensor(np.asarray(action, dtype=np.float32) if not torch.is_tensor(action) else action, device=self.device)
@@ -254,6 +264,43 @@ class SawyerDoor:
     self._launch_rollout(self._actions(action, ()), 1, out)
     return (out['obs'][0].cpu().numpy(), float(out['reward'][0]), bool(out['done'][0]), self._info_dict(out)) if self.scalar_api else \
         (out['obs'], out['reward'], out['done'], self._info_dict(out))
+
+  def make_step_graph(self, T, policy=None):
+    """Closed-loop stepping without the per-call host cost: T step() launches captured into a HIP graph, replayed with one host call (see `PhysicsStepGraph`)."""
+    return PhysicsStepGraph(self, T, policy)
+
+  # hooks of PhysicsStepGraph: one captured step = the clocked T = 1 launch (+ the door's info launch) into the graph's output rows
+  _graph_bounds = None
+
+  def _graph_check(self):
+    pass
+
+  def _new_graph_out(self, T):
+    return self._new_out((T,))
+
+  @contextlib.contextmanager
+  def _graph_capture(self):
+    sc = self._cfg.step_counter
+    try:
+      yield
+    finally:
+      self._cfg.step_counter = sc
+
+  def _graph_step(self, t, action, out, clock):
+    self._cfg.step_counter = t                             # the goal-switch draws of the captured step t: clock[1] + t
+    self._issue_rollout(action, 1, out, clock)
+    if self._cfg.goal_change_frequency:
+      self.lifelong_return_t += out['reward'].reshape(1, -1).sum(0, dtype=torch.float64)
+
+  def _graph_clock(self):
+    return self._cfg.counter, self.total_step_count
+
+  def _graph_advance(self, T, out):
+    self.total_step_count += T
+    self._last_success = out['success'][-1]
+
+  def _graph_info(self, out):
+    return self._info_dict(out)
 
   def info_from_obs(self, obs):
     """the reference's info dict (door: evaluate_state, sawyer_door.py:127-139) of given observation rows [M, 14] -> dict of [M] float64 tensors"""

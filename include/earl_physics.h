@@ -274,6 +274,12 @@ typedef struct earl_sawyer_out {
  * env step that ended finite -- they are the "last stable state" a diverged step rolls back to).  action: float32 [T, n, 4]. */
 int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                         const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream);
+/* As earl_sawyer_rollout, but the step-dependent Philox counters are cfg->counter + clock[0] and cfg->step_counter + clock[1], where `clock` is DEVICE memory
+ * holding two uint64 that the kernel reads when it runs (NULL = zero; the rollout draws with step_counter only: clock[0] has no use here).  For launches
+ * captured into a HIP graph: the captured launch of step t passes cfg->step_counter = t, and the host writes the base into the clock before each replay.
+ * Every kernel the launcher picks (door default / eight-wave / 64-lane, peg) honours it; earl_sawyer_rollout is this with clock = NULL. */
+int earl_sawyer_rollout_clocked(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                const float* action, int32_t T, const uint64_t* clock, const earl_sawyer_out* out, earl_stream_t stream);
 
 /* reset the envs with mask[i] != 0 (mask NULL = all): state <- the settled post-_reset_hand state (reset_qpos [nq], reset_qvel
  * [nv], device), object re-initialised as cfg.obj_kind says, mocap <- hand_init_pos, counters cleared; obs [n,14]
@@ -363,6 +369,12 @@ int earl_kitchen_step(const void* model24, const earl_collision_model* col, cons
  * over the T steps instead of T times the slowest wave of a step.  The lifelong wrapper's goal switch is not part of it (callers step those). */
 int earl_kitchen_rollout(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                          const earl_kitchen_state* st, const float* action /* [T, n, 9] */, int32_t T, const earl_kitchen_out* out, earl_stream_t stream);
+/* As earl_kitchen_rollout, with the sensor-noise counter cfg->counter + clock[0], where `clock` is DEVICE memory holding two uint64 read when the kernel runs
+ * (NULL = zero; clock[1] has no use here).  For graph capture, as earl_sawyer_rollout_clocked.  earl_kitchen_rollout is this with clock = NULL; the eight-launch
+ * earl_kitchen_step has no clocked form (its noise comes from earl_philox_uniform with the host's counter). */
+int earl_kitchen_rollout_clocked(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                                 const earl_kitchen_state* st, const float* action /* [T, n, 9] */, int32_t T, const uint64_t* clock, const earl_kitchen_out* out,
+                                 earl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Minitaur env (BASELINE configs[4]) on the same stepper: floating base + 16 hinges (nv = 22, nq = 23), four connect
@@ -431,6 +443,11 @@ typedef struct earl_minitaur_out {
  * same collision pair as at the timestep before starts from the edge set its passes ENDED with (same fixed point, fewer passes: 2.05 -> 1.66 per timestep on random actions). */
 int earl_minitaur_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                           const float* action, int32_t T, const earl_minitaur_out* out, earl_stream_t stream);
+/* As earl_minitaur_rollout, with the goal-switch counter cfg->step_counter + clock[1], where `clock` is DEVICE memory holding two uint64 read when the kernel
+ * runs (NULL = zero; the rollout draws with step_counter only: clock[0] has no use here).  For graph capture, as earl_sawyer_rollout_clocked.  Every rollout
+ * kernel honours it: the two-wave and one-wave kernels and the generic stepper (earl_debug_set_minitaur_stepper(0)).  earl_minitaur_rollout is this with clock = NULL. */
+int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                  const float* action, int32_t T, const uint64_t* clock, const earl_minitaur_out* out, earl_stream_t stream);
 /* reset the envs with mask[i] != 0 (NULL = all); obs [n, 32] (may be NULL) is written for the reset envs only */
 int earl_minitaur_reset(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                         const uint8_t* mask, double* obs, earl_stream_t stream);

@@ -116,12 +116,15 @@ int earl_sawyer_rollout_clocked(const earl_link_model* model, const earl_collisi
   if (!model || !cfg || !st || !out || !action || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !out->obs) return EARL_ERR_ARG;
   if (cfg->frame_skip < 0 || cfg->att_hand < 0 || cfg->att_right < 0 || cfg->att_left < 0 || cfg->att_obj < 0) return EARL_ERR_ARG;
+  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;   // (NULL is allowed without goal switching only)
+  if (cfg->n_goal_rows > 0 && !cfg->goal_table) return EARL_ERR_ARG;
+  if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && (!st->obj_init || cfg->att_grasp < 0 || cfg->att_lpad < 0 || cfg->att_rpad < 0))
+    return EARL_ERR_ARG;                                  // the peg's dense reward needs the reset-time state and the pad / grasp attachments
+  if (nv == 15 && cfg->obj_kind >= 1 && out->info && !st->obj_init) return EARL_ERR_ARG;     // (so does the peg's info dict: without it the rows were left unwritten)
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (nv != 10 && nv != 15) return EARL_ERR_ARG;
   if (int rc = check_cone(col, true, (hipStream_t)stream, "sawyer_rollout")) return rc;
   SawyerArgs a{model, col, *cfg, *st, action, T, *out, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
-  if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && (!st->obj_init || cfg->att_grasp < 0 || cfg->att_lpad < 0 || cfg->att_rpad < 0))
-    return EARL_ERR_ARG;                                  // the peg's dense reward needs the reset-time state and the pad / grasp attachments
   if (nv == 10 && g_lpe != 64 && g_door_variant == 3 && st->sched && T > 1) {
     // (measurement switch: the single-wave build, four workgroups per CU, under the time-sliced work queue of the peg -- tools/bench_variant.py)
     a.slice = g_peg_sliced >= 2 ? g_peg_sliced : EARL_PEG_SLICE;
@@ -159,6 +162,9 @@ int earl_sawyer_reset(const earl_link_model* model, int32_t nv, const earl_sawye
   if (cfg->obj_dof < 0 || cfg->obj_dof >= nv || cfg->obj_kind < 0 || cfg->obj_kind > 2) return EARL_ERR_ARG;
   if (cfg->obj_kind >= 1 && cfg->obj_dof + 6 > nv) return EARL_ERR_ARG;
   if (cfg->obj_kind == 2 && (cfg->n_wide <= 0 || !cfg->wide_table)) return EARL_ERR_ARG;
+  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;   // (the reset clears the counter the rollout will read)
+  if (cfg->n_goal_rows > 0 && !cfg->goal_table) return EARL_ERR_ARG;
+  if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && !st->obj_init) return EARL_ERR_ARG;      // (the peg's dense reward reads what the reset keeps there)
   if (cfg->n == 0) return EARL_OK;
   SawyerArgs a{model, nullptr, *cfg, *st, nullptr, 0, earl_sawyer_out{nullptr, nullptr, nullptr, nullptr, nullptr}, reset_qpos, reset_qvel, mask, obs, 0, 0, nullptr};
   if (nv == 10) sawyer_reset_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);

@@ -36,6 +36,7 @@ int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_mode
   if (!model24 || !cfg || !st || !out || !action || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
   if (!out->obs || !out->reward || !out->done || !out->success || !cfg->goal_table || cfg->n_goals < 1 || cfg->num_substeps < 0) return EARL_ERR_ARG;
+  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;   // (NULL is allowed without goal switching only)
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_rollout")) return rc;
   MinitaurArgs a{model24, col, *cfg, *st, *out, action, T, nullptr, nullptr, solo_mode(cfg->n), clock};
@@ -57,6 +58,7 @@ int earl_minitaur_reset(const void* model24, const earl_collision_model* col, co
   if (!model24 || !cfg || !st || cfg->n < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
   if (!cfg->goal_table || !cfg->reset_qpos || cfg->n_goals < 1 || cfg->settle_steps < 0) return EARL_ERR_ARG;
+  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;   // (the reset clears the counter the rollout will read)
   if (cfg->n == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_reset")) return rc;
   MinitaurArgs a{model24, col, *cfg, *st, earl_minitaur_out{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr, 0, mask, obs, solo_mode(cfg->n), nullptr};

@@ -214,7 +214,7 @@ typedef struct earl_sawyer_cfg {
   double hand_init_pos[3], obj_init_pos[3];
   double obj_init_angle, angle_noise[2];
   double obj_low[3], obj_high[3], obj_reject_xy[2], obj_reject_radius;
-  const double* goal_table;                /* device, [n_goal_rows, 7] or NULL */
+  const double* goal_table;                /* device, [n_goal_rows, 7]; may be NULL when n_goal_rows == 0 (otherwise EARL_ERR_ARG) */
   const double* wide_table;                /* device, [n_wide, 3] or NULL */
   double wide_shift[3], wide_noise;
   double init_tcp[3];                      /* peg dense reward: midpoint of the finger sites after _reset_hand (SawyerXYZEnv.init_tcp [UPSTREAM]) */
@@ -229,12 +229,15 @@ typedef struct earl_sawyer_state {
   double* mocap_pos;            /* [n, 3] */
   double* goal;                 /* [n, 7] */
   int32_t* steps_since_reset;   /* [n] */
-  int32_t* steps_since_goal_change;   /* [n]; may be NULL when cfg.goal_change_frequency == 0 */
+  int32_t* steps_since_goal_change;   /* [n]; may be NULL when cfg.goal_change_frequency == 0 (otherwise the rollout and the reset return EARL_ERR_ARG) */
   double* obj_init;             /* [n, 6] obj_init_pos, peg_head_pos_init as reset_model leaves them (sawyer_peg.py:213-215); may be NULL
-                                   for sparse rewards; written by earl_sawyer_reset, read by the peg's dense reward */
+                                   for sparse rewards without out.info (a peg with dense rewards or with out.info and NULL here: EARL_ERR_ARG
+                                   from the rollout; with dense rewards from the reset too);
+                                   written by earl_sawyer_reset, read by the peg's dense reward */
   double* last_obs;             /* [n, 14] may be NULL: the observation last returned for each env (SawyerXYZEnv._last_stable_obs [UPSTREAM]);
                                    written by earl_sawyer_reset and at the end of earl_sawyer_rollout, read when the FIRST step of a launch
-                                   diverges (later steps copy the previous row of the launch's own output) */
+                                   diverges (later steps copy the previous row of the launch's own output).  NULL and the first step diverges:
+                                   that row of out.obs is NaN, and so are the rows that copy it */
   int32_t* fail_count;          /* [n] may be NULL: env steps that diverged and were rolled back (see earl_sawyer_out.status) */
   int32_t* sched;               /* may be NULL.  Scratch of the TIME-SLICED schedule of earl_sawyer_rollout: 2 * ceil(n / 4) int32, ZERO on entry (the caller clears it
                                    before every call).  When given, and the batch is larger than what the GPU holds at once (peg model: more than 16 envs per CU),
@@ -346,7 +349,7 @@ typedef struct earl_kitchen_state {
   /* scratch, caller-owned like everything else: */
   double* action64;              /* [n, 9] */
   double* ctrl9;                 /* [n, 9] */
-  double* noise;                 /* [n, 46] (may be NULL when sensor_noise == 0) */
+  double* noise;                 /* [n, 46] (may be NULL when sensor_noise == 0; otherwise earl_kitchen_step returns EARL_ERR_ARG) */
   double* qpos_bak; double* qvel_bak;   /* [n, 23] the state a diverged step is rolled back to */
   double* sites;                 /* [n, 8, 3] */
   uint8_t* bad;                  /* [n] */
@@ -364,8 +367,8 @@ int earl_kitchen_step(const void* model24, const earl_collision_model* col, cons
                       const earl_kitchen_state* st, const float* action /* [n, 9] */, const earl_kitchen_out* out, earl_stream_t stream);
 
 /* T env steps of every env in ONE launch: action [T, n, 9] float32, the rows of `out` are [T, n, ...].  Equal, bit for bit, to T calls of
- * earl_kitchen_step with cfg.counter, cfg.counter + 1, ... (state, scratch-free: action64 / ctrl9 / noise / qpos_bak / qvel_bak / sites / bad of
- * `st` are not used and may be NULL); every wave walks its envs through the whole rollout on its own, so the launch costs the slowest wave's SUM
+ * earl_kitchen_step with cfg.counter, cfg.counter + 1, ... (state, scratch-free: action64 / ctrl9 / noise / qpos_bak / qvel_bak / sites / bad / mocap_bak /
+ * att_bak of `st` are not used and may be NULL); every wave walks its envs through the whole rollout on its own, so the launch costs the slowest wave's SUM
  * over the T steps instead of T times the slowest wave of a step.  The lifelong wrapper's goal switch is not part of it (callers step those). */
 int earl_kitchen_rollout(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                          const earl_kitchen_state* st, const float* action /* [T, n, 9] */, int32_t T, const earl_kitchen_out* out, earl_stream_t stream);
@@ -428,9 +431,9 @@ typedef struct earl_minitaur_state {
   int32_t* overheat;               /* [n, 8] Minitaur._overheat_counter */
   uint8_t* motor_enabled;          /* [n, 8] Minitaur._motor_enabled_list */
   int32_t* steps_since_reset;      /* [n] */
-  int32_t* steps_since_goal_change;   /* [n]; may be NULL when cfg.goal_change_frequency == 0 */
+  int32_t* steps_since_goal_change;   /* [n]; may be NULL when cfg.goal_change_frequency == 0 (otherwise the rollout and the reset return EARL_ERR_ARG) */
   int32_t* fail_count;             /* [n] may be NULL */
-  double* last_obs;                /* [n, 32] may be NULL (as in earl_sawyer_state) */
+  double* last_obs;                /* [n, 32] may be NULL (as in earl_sawyer_state: NaN rows when the first step of a launch diverges) */
 } earl_minitaur_state;
 typedef struct earl_minitaur_out {
   double* obs;                     /* [T, n, 32] */

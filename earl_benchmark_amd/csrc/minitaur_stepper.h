@@ -43,7 +43,7 @@ __device__ __forceinline__ double kc(double x) {
   asm volatile("" : "+s"(x));
   return x;
 }
-// sincos_mod of physics.hip with such constants (same operations in the same order: identical results)
+// sincos_mod of physics_math.h with such constants (same operations in the same order: identical results -- bit for bit on 1e6 arguments, tests/test_physics_primitives_gpu.py test_sincos_mod_and_kc)
 __device__ __forceinline__ void sincos_kc(double x, double& sn, double& cs) {
   const double k = rint(x * kc(6.36619772367581382433e-01));
   double r = fma(-k, kc(1.57079632673412561417e+00), x);
@@ -94,7 +94,7 @@ __device__ __forceinline__ void stage_pairs_mt(PairTabMT& t, const earl_collisio
     t.link[i] = col->pair_rec[i].sph_link; t.cls[i] = col->pair_rec[i].cls;
   }
 }
-// chol_regs of physics.hip (dense, diagonal left inverted) with the two-step reciprocal root
+// chol_regs<N, N, true> of physics_solve.h (dense, diagonal left inverted, the two-step reciprocal root): the same bits (tests/test_physics_primitives_gpu.py test_chol_small_is_chol_regs_fast_and_accurate)
 template <int N>
 __device__ __forceinline__ void chol_small(double (&L)[N * (N + 1) / 2]) {
 #pragma unroll

@@ -6,7 +6,8 @@
 // trees, so the mass matrix always is, and the Hessian is unless a contact joins the two.  The entries of the off-diagonal block
 // are then never read or written (their registers are dead on that path).
 // (every multiply-subtract is an explicit fma in the same order as chol_coop / solve_lds below: the register-resident and the in-LDS
-// factorisation then produce the same bits, which is what lets earl_sawyer_rollout switch between its two door builds by batch size)
+// factorisation then produce the same bits, which is what lets earl_sawyer_rollout switch between its two door builds by batch size; stated where it lives, on
+// square and on packed storage: tests/test_physics_primitives_gpu.py test_bit_identities_of_the_solve_forms)
 template <int NV, int NA, bool FAST = false>
 __device__ __forceinline__ void chol_regs(double (&L)[NV * (NV + 1) / 2]) {
 #pragma unroll
@@ -196,50 +197,10 @@ __device__ __forceinline__ double chol_solve_rows(SymLds<NV>& H, const double (&
   return t;
 }
 
-// the same on the leading N x N block only (a model whose first N dofs are one tree and whose other dofs are decoupled from it: the kitchen's arm)
-template <int NV, int N>
-__device__ __forceinline__ void chol_coop_lead(SymLds<NV>& H, const double (&dl)[NV], const int l, const bool isl) {
-  const int ltri = l * (l + 1) / 2;
-  const bool mine = isl && l < N;
-  double r[N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) r[j] = H.sym(j, l < N ? l : 0, l < N ? ltri : 0);
-  if (mine) H.rowl(l, ltri, l) = r[l] + dl[l];
-  fence();
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    double sj = H.lo(j, j), si = r[j] + (l == j ? dl[l] : 0.0);
-#pragma unroll
-    for (int p = 0; p < j; ++p) {
-      const double pj = H.lo(j, p);
-      sj = fma(-pj, pj, sj);
-      si = fma(-r[p], pj, si);
-    }
-    const double inv = rsq_nr(sj);
-    r[j] = si * inv;
-    if (mine && l >= j) H.rowl(l, ltri, j) = l == j ? inv : r[j];
-    fence();
-  }
-}
-template <int NV, int N>
-__device__ __forceinline__ void solve_lds_lead(const SymLds<NV>& H, double (&x)[NV]) {   // leading block of (L L') x' = x
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double s = x[i];
-#pragma unroll
-    for (int p = 0; p < i; ++p) s = fma(-H.lo(i, p), x[p], s);
-    x[i] = s * H.lo(i, i);
-  }
-#pragma unroll
-  for (int i = N - 1; i >= 0; --i) {
-    double s = x[i];
-#pragma unroll
-    for (int p = i + 1; p < N; ++p) s = fma(-H.lo(p, i), x[p], s);
-    x[i] = s * H.lo(i, i);
-  }
-}
-// the leading N x N block factorised and solved in REGISTERS, redundantly per lane (chol_regs / solve_regs on a copy: same operations in the same order
-// as chol_coop_lead / solve_lds_lead, which cost nine plus eighteen LDS round trips in a row)
+// the leading N x N block only (a model whose first N dofs are one tree and whose other dofs are decoupled from it: the kitchen's arm), factorised and solved in
+// REGISTERS, redundantly per lane: chol_regs<N, N, true> / solve_regs on a copy.  (The lane-cooperative in-LDS form of it -- nine plus eighteen LDS round trips in a
+// row, and rsq_nr where this one takes rsq2, so NOT the same bits -- had no caller left and is gone.)  What the launch forms rely on is that the kitchen's helper wave,
+// which runs the same chol_regs<NA, NA, true> on the same entries, leaves the same factor: tests/test_physics_primitives_gpu.py test_bit_identities_of_the_solve_forms
 template <int NV, int N, typename D>
 __device__ __forceinline__ void solve_lead_regs(const SymLds<NV>& H, D diag, double (&x)[NV]) {
   double L[N * (N + 1) / 2], y[N];

@@ -1765,8 +1765,8 @@ __device__ __forceinline__ void substep(Shared<NV>& s, const typename ModelOf<NV
         KSTAMP(14);
 #pragma unroll
         for (int i = 0; i < NA; ++i) a[i] = s.con.rc[i] + s.con.rl[i];
-        // (the Schur complement is factorised and solved in registers, redundantly per lane, like the arm's block without contacts: the lane-cooperative
-        // in-LDS form -- chol_coop_lead + solve_lds_lead, nine plus eighteen dependent LDS round trips -- was a third of this path)
+        // (the Schur complement is factorised and solved in registers, redundantly per lane, like the arm's block without contacts: a lane-cooperative
+        // in-LDS form -- nine plus eighteen dependent LDS round trips -- was a third of this path)
         solve_lead_regs<NV, NA>(s.con.Hc, [&](int i) { return s.con.dl[i]; }, a);
         KSTAMP(15);
         if (isl && l >= NA) {                             // t_f = B_f . x_arm

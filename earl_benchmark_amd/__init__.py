@@ -219,3 +219,10 @@ def load_demo(directory):
   with open(os.path.join(directory, 'demo_data.pkl'), 'rb') as f:
     demo = pickle.load(f)
   return {k: np.asarray(demo[k]) for k in DEMO_KEYS}
+
+
+def __getattr__(name):          # `earl_benchmark_amd.MLPPolicy` without importing torch at package import (tables / demos work without it)
+  if name == 'MLPPolicy':
+    from .policy import MLPPolicy
+    return MLPPolicy
+  raise AttributeError(name)

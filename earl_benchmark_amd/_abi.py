@@ -29,6 +29,15 @@ class TabletopOut(C.Structure):
   _fields_ = [('obs', C.c_void_p), ('reward', C.c_void_p), ('done', C.c_void_p), ('success', C.c_void_p), ('reward_f64', C.c_void_p)]
 
 
+ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
+ACTIVATIONS = {'none': ACT_NONE, 'relu': ACT_RELU, 'tanh': ACT_TANH}
+
+
+class MlpPolicy(C.Structure):     # struct earl_mlp_policy (include/earl_tabletop.h)
+  _fields_ = [('n_layers', C.c_int32), ('dims', C.c_int32 * 4), ('hidden_act', C.c_int32), ('out_act', C.c_int32), ('precision', C.c_int32),
+              ('params', C.c_void_p)]
+
+
 class MotorParams(C.Structure):   # struct earl_motor_params (include/earl_glue.h)
   _fields_ = [('kp', C.c_double), ('kd', C.c_double), ('voltage', C.c_double), ('viscous_damping', C.c_double),
               ('torque_control', C.c_int32)]
@@ -111,6 +120,7 @@ SIGNATURES = {
     'earl_tabletop_rollout': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_void_p, _P(TabletopOut), C.c_void_p],
     'earl_tabletop_reset_rollout': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_void_p, _P(TabletopOut), C.c_void_p],
     'earl_tabletop_eval_episodes': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _P(TabletopOut), C.c_void_p],
+    'earl_tabletop_policy_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), C.c_int32, C.c_int32, C.c_int32, _P(TabletopOut), C.c_void_p, C.c_void_p],
     'earl_tabletop_reset': [_P(TabletopCfg), _P(TabletopState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_tabletop_observe': [_P(TabletopCfg), _P(TabletopState), _P(TabletopOut), C.c_void_p],
     'earl_tabletop_reward': [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],

@@ -7,6 +7,7 @@
 
 #include "tabletop_hostside.h"
 #include "tabletop_step.h"
+#include "tabletop_policy.h"
 
 #ifdef _OPENMP
 #include <omp.h>
@@ -129,6 +130,15 @@ int earl_tabletop_eval_episodes_cpu(const earl_tabletop_cfg* cfg, const earl_tab
                               out->success ? out->success + rows : nullptr, nullptr};
     if (int rc = do_rollout<1>(&c, st, T, act + (size_t)e * (size_t)act_episode_stride, &o, true)) return rc;
   }
+  return EARL_OK;
+}
+int earl_tabletop_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, int32_t episodes, int32_t T,
+                                     int32_t reset_first, const earl_tabletop_out* out, float* act_out) {
+  if (int rc = check_policy(cfg, st, policy, episodes, T, reset_first, out)) return rc;
+  if (cfg->n == 0) return EARL_OK;
+  const PolicyArgs a{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, thresholds()}, *policy, act_out, episodes, reset_first};
+  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) for_each_env(cfg->n, [&](int i) { policy_rollout_env<true>(a, i); });
+  else for_each_env(cfg->n, [&](int i) { policy_rollout_env<false>(a, i); });
   return EARL_OK;
 }
 int earl_tabletop_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, const int32_t* next_goal_idx, float* obs) {

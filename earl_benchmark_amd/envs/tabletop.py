@@ -287,6 +287,38 @@ class TabletopManipulation:
     self._last_success = outs[3][-1, -1]
     return outs
 
+  def rollout_policy(self, policy, T, episodes=None, reset_first=True, out=None):
+    """Closed loop in ONE kernel launch (include/earl_tabletop.h: earl_tabletop_policy_rollout): `policy` (an `MLPPolicy`) is evaluated inside the
+    kernel between the env steps, observation -> MLP -> action -> step.  reset_first=True: `episodes` (default 1) evaluation episodes, each reset() +
+    T steps; reset_first=False: T steps continuing from the current state (lifelong switching and auto-reset included).
+    -> (obs [E,T,N,D], reward [E,T,N], done, success, actions [E,T,N,3]) -- without the E axis when reset_first=False.  Bit-identical to
+    rollout_episodes(actions) / rollout(actions) fed with the returned actions."""
+    if self.NOBJ != 1:
+      raise NotImplementedError('rollout_policy: single-object env only')
+    if reset_first:
+      E = 1 if episodes is None else int(episodes)
+      lead = (E, int(T), self.num_envs)
+    else:
+      if episodes not in (None, 1):
+        raise ValueError('rollout_policy: a continuing rollout (reset_first=False) is one episode')
+      E, lead = 1, (int(T), self.num_envs)
+    if policy.device != self.device:
+      raise ValueError(f'rollout_policy: the policy is on {policy.device}, the env on {self.device} (policy.to(device))')
+    with self._ctx():
+      if out is None:
+        outs, ostruct = self._new_out(lead)
+      else:
+        outs = tuple(out)
+        ostruct = self._out_struct(outs, lead)
+      actions = torch.empty(*lead, 3, dtype=torch.float32, device=self.device)
+      rc = self._lib.earl_tabletop_policy_rollout(self._cfg_ref, self._st_ref, C.byref(policy.struct), E, int(T), int(bool(reset_first)), C.byref(ostruct),
+                                                  actions.data_ptr(), self._stream())
+    self._check(rc, 'policy_rollout')
+    self._cfg.counter += E * (int(T) + 1) if reset_first else int(T)
+    self.total_step_count += E * int(T)
+    self._last_success = outs[3][-1, -1] if reset_first else outs[3][-1]
+    return outs + (actions,)
+
   def make_step_graph(self, T, policy=None):
     """Closed-loop stepping without the per-call host cost: a captured HIP graph of T step launches (see `StepGraph`)."""
     return StepGraph(self, T, policy)

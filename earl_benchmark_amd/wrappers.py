@@ -47,6 +47,9 @@ class PersistentStateWrapper(Wrapper):
   def rollout_episodes(self, actions, **kwargs):
     return self.env.rollout_episodes(actions, **kwargs)
 
+  def rollout_policy(self, policy, T, **kwargs):
+    return self.env.rollout_policy(policy, T, **kwargs)
+
   def is_successful(self, obs=None):
     return self.env.is_successful(obs)
 
@@ -80,6 +83,9 @@ class LifelongWrapper(Wrapper):
 
   def rollout(self, actions, **kwargs):
     return self.env.rollout(actions, **kwargs)
+
+  def rollout_policy(self, policy, T, **kwargs):
+    return self.env.rollout_policy(policy, T, **kwargs)
 
   @property
   def lifelong_return(self):

@@ -115,6 +115,33 @@ int earl_tabletop_reset_rollout(const earl_tabletop_cfg* cfg, const earl_tableto
 int earl_tabletop_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t episodes, int32_t T, const float* act,
                                 int64_t act_episode_stride, const earl_tabletop_out* out, earl_stream_t stream);
 
+/* ---- closed loop: an MLP policy evaluated INSIDE the rollout kernel ----
+ * The reference's evaluation / training loop is closed (`obs = env.reset(); while not done: obs, ... = env.step(policy(obs))`); the entry points above
+ * need every action up front.  This one takes the policy instead: a float32 MLP 12 -> hidden (-> hidden) -> 3, evaluated on gfx950 with
+ * v_mfma_f32_16x16x4_f32 next to the fp64 recurrence, weights resident in registers for the whole launch. */
+enum { EARL_ACT_NONE = 0, EARL_ACT_RELU = 1, EARL_ACT_TANH = 2 };
+typedef struct earl_mlp_policy {
+  int32_t n_layers;     /* linear layers: 2 (one hidden) or 3 (two hidden) */
+  int32_t dims[4];      /* dims[0] = 12, dims[n_layers] = 3; hidden widths multiples of 16 in 16..256; unused = 0 */
+  int32_t hidden_act;   /* EARL_ACT_RELU or EARL_ACT_TANH */
+  int32_t out_act;      /* EARL_ACT_NONE (the env clips to [-1, 1] itself, tabletop_manipulation.py:130) or EARL_ACT_TANH */
+  int32_t precision;    /* 0 = fp32; anything else is EARL_ERR_ARG (reserved) */
+  const float* params;  /* layer by layer: W_l [dims[l+1], dims[l]] row-major (= torch.nn.Linear.weight), then b_l [dims[l+1]] */
+} earl_mlp_policy;
+
+/* reset (reset_first = 1) + T closed-loop steps, `episodes` times, in ONE launch.  Step t's action is pi(o), o the float32 observation the env last
+ * produced: the reset's observation (reset_first = 1) or _get_obs() of the incoming state (reset_first = 0; episodes must be 1) for t = 0, otherwise row
+ * t - 1 of out->obs (after a lifelong goal switch: the re-read row).  act_out (may be NULL) [episodes, T, n, 3] receives the actions as the policy
+ * produced them, before the env's own clip / rescale.  out as for earl_tabletop_eval_episodes ([episodes, T, n, ..]); any of its pointers may be NULL.
+ * Bit-identical to the open-loop entry point fed with act_out: reset_first = 1 == earl_tabletop_eval_episodes(cfg, st, episodes, T, act_out, T*n*3, out),
+ * reset_first = 0 == earl_tabletop_rollout(cfg, st, T, act_out, out) -- outputs, state left behind, wrapper counters, Philox counter use
+ * (episodes * (T + 1) resp. T).
+ * Policy arithmetic (a contract: libearl_host.so states it as plain loops and the device agrees bit for bit): every pre-activation is
+ * acc = b_j; for k ascending: acc = fmaf(x_k, W_jk, acc) in float32; ReLU is acc > 0 ? acc : +0 (= fmaxf(acc, 0) with -0 -> +0, NaN -> 0);
+ * tanh is this build's own tanh_f32 (csrc/tabletop_policy.h: fma, +, *, / and integer operations only, no libm). */
+int earl_tabletop_policy_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, int32_t episodes, int32_t T,
+                                 int32_t reset_first, const earl_tabletop_out* out, float* act_out, earl_stream_t stream);
+
 /* PersistentStateWrapper.reset() + TabletopManipulation.reset() for the envs with mask[i] != 0
  * (mask == NULL: all).  Replaces wrappers/persistent_state_wrapper.py:17-20 and
  * envs/tabletop_manipulation.py:105-126 (incl. is_valid_init :89-97, get_next_goal :62-76).
@@ -161,6 +188,8 @@ int earl_tabletop_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_
 int earl_tabletop_reset_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t T, const float* act, const earl_tabletop_out* out);
 int earl_tabletop_eval_episodes_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t episodes, int32_t T, const float* act,
                                     int64_t act_episode_stride, const earl_tabletop_out* out);
+int earl_tabletop_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, int32_t episodes, int32_t T,
+                                     int32_t reset_first, const earl_tabletop_out* out, float* act_out);
 int earl_tabletop_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, const int32_t* next_goal_idx, float* obs);
 int earl_tabletop_observe_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_tabletop_out* out);
 int earl_tabletop_reward_cpu(int32_t n, const float* obs, int32_t reward_type, int32_t wide_init, float* reward, uint8_t* success);

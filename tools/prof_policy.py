@@ -1,0 +1,49 @@
+"""Where a step of the closed-loop policy kernel spends its cycles: runs the stamped build (tools/build_policy_stamped.sh) at N = 4096, T = 200 for the
+probe's two policy shapes and prints / writes the per-phase s_memtime sums of wave 0 of workgroup 0 per step (ticks of the constant-rate counter) and each
+phase's share of the step.  The stamps cost
+time of their own; the shipped kernel's timings are those of tools/policy_rollout_probe.py.
+
+  bash tools/build_policy_stamped.sh && python tools/prof_policy.py [--out profiles/policy_rollout_phases.json]"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from earl_benchmark_amd import _abi  # noqa: E402
+
+_abi.LIB_PATH = os.path.join(REPO, 'tools', 'ubench', 'libearl_policy_stamped.so')
+import torch  # noqa: E402
+import earl_benchmark_amd as eb  # noqa: E402
+from policy_rollout_probe import random_policy  # noqa: E402
+
+PHASES = ('obs_to_lds+barrier', 'layer0+barrier', 'hidden_layer+barrier', 'output_layer+barrier', 'env_step')
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'policy_rollout_phases.json'))
+  args = ap.parse_args()
+  n, T, dev = 4096, 200, 'cuda:0'
+  lib = _abi.load()
+  res = {'n': n, 'T': T, 'unit': 's_memtime ticks per step and share of the step, wave 0 of workgroup 0, stamped build', 'shapes': {}}
+  for name, hidden in (('12-64-3', (64,)), ('12-256-256-3', (256, 256))):
+    pi = random_policy(hidden, 1, dev)
+    _, env = eb.EARLEnvs('tabletop_manipulation', reward_type='sparse', num_envs=n, device=dev, seed=5, eval_horizon=T).get_envs()
+    for _ in range(3):
+      env.rollout_policy(pi, T, episodes=1)
+    torch.cuda.synchronize()
+    buf = (C.c_uint64 * 5)()
+    assert lib._handle and C.CDLL(_abi.LIB_PATH).earl_debug_read_policy_profile(buf) == 0
+    ticks = [v / T for v in buf]
+    res['shapes'][name] = {'ticks_per_step': dict(zip(PHASES, ticks), total=sum(ticks)), 'share': {k: v / sum(ticks) for k, v in zip(PHASES, ticks)}}
+    print(name, res['shapes'][name])
+  with open(args.out, 'w') as f:
+    json.dump(res, f, indent=1)
+    f.write('\n')
+
+
+if __name__ == '__main__':
+  main()

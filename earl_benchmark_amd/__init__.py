@@ -225,4 +225,7 @@ def __getattr__(name):          # `earl_benchmark_amd.MLPPolicy` without importi
   if name == 'MLPPolicy':
     from .policy import MLPPolicy
     return MLPPolicy
+  if name == 'GaussianMLPPolicy':
+    from .policy import GaussianMLPPolicy
+    return GaussianMLPPolicy
   raise AttributeError(name)

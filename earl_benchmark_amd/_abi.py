@@ -38,6 +38,15 @@ class MlpPolicy(C.Structure):     # struct earl_mlp_policy (include/earl_tableto
               ('params', C.c_void_p)]
 
 
+HEAD_MEAN, HEAD_SAMPLE = 0, 1
+LOGSTD_CLAMP, LOGSTD_TANH = 0, 1
+LOGSTD_MAPS = {'clamp': LOGSTD_CLAMP, 'tanh': LOGSTD_TANH}
+
+
+class GaussianHead(C.Structure):  # struct earl_gaussian_head (include/earl_tabletop.h)
+  _fields_ = [('mode', C.c_int32), ('log_std_map', C.c_int32), ('log_std_min', C.c_float), ('log_std_max', C.c_float), ('eps_out', C.c_void_p)]
+
+
 class MotorParams(C.Structure):   # struct earl_motor_params (include/earl_glue.h)
   _fields_ = [('kp', C.c_double), ('kd', C.c_double), ('voltage', C.c_double), ('viscous_damping', C.c_double),
               ('torque_control', C.c_int32)]
@@ -121,6 +130,8 @@ SIGNATURES = {
     'earl_tabletop_reset_rollout': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_void_p, _P(TabletopOut), C.c_void_p],
     'earl_tabletop_eval_episodes': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _P(TabletopOut), C.c_void_p],
     'earl_tabletop_policy_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), C.c_int32, C.c_int32, C.c_int32, _P(TabletopOut), C.c_void_p, C.c_void_p],
+    'earl_tabletop_policy_rollout_gaussian': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), _P(GaussianHead), C.c_int32, C.c_int32, C.c_int32, _P(TabletopOut),
+                                              C.c_void_p, C.c_void_p],
     'earl_tabletop_reset': [_P(TabletopCfg), _P(TabletopState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_tabletop_observe': [_P(TabletopCfg), _P(TabletopState), _P(TabletopOut), C.c_void_p],
     'earl_tabletop_reward': [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],

@@ -141,6 +141,18 @@ int earl_tabletop_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_ta
   else for_each_env(cfg->n, [&](int i) { policy_rollout_env<false>(a, i); });
   return EARL_OK;
 }
+int earl_tabletop_policy_rollout_gaussian_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
+                                              const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
+                                              const earl_tabletop_out* out, float* act_out) {
+  if (int rc = check_policy_gaussian(cfg, st, policy, head, episodes, T, reset_first, out)) return rc;
+  if (cfg->n == 0) return EARL_OK;
+  GaussianPolicyArgs a;
+  static_cast<PolicyArgs&>(a) = PolicyArgs{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, thresholds()}, *policy, act_out, episodes, reset_first};
+  a.head = *head;
+  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) for_each_env(cfg->n, [&](int i) { gaussian_rollout_env<true>(a, i); });
+  else for_each_env(cfg->n, [&](int i) { gaussian_rollout_env<false>(a, i); });
+  return EARL_OK;
+}
 int earl_tabletop_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, const int32_t* next_goal_idx, float* obs) {
   return do_reset<1>(cfg, st, mask, next_goal_idx, obs);
 }

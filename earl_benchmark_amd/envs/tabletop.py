@@ -287,12 +287,19 @@ class TabletopManipulation:
     self._last_success = outs[3][-1, -1]
     return outs
 
-  def rollout_policy(self, policy, T, episodes=None, reset_first=True, out=None):
+  def rollout_policy(self, policy, T, episodes=None, reset_first=True, out=None, sample=True, return_noise=False):
     """Closed loop in ONE kernel launch (include/earl_tabletop.h: earl_tabletop_policy_rollout): `policy` (an `MLPPolicy`) is evaluated inside the
     kernel between the env steps, observation -> MLP -> action -> step.  reset_first=True: `episodes` (default 1) evaluation episodes, each reset() +
     T steps; reset_first=False: T steps continuing from the current state (lifelong switching and auto-reset included).
     -> (obs [E,T,N,D], reward [E,T,N], done, success, actions [E,T,N,3]) -- without the E axis when reset_first=False.  Bit-identical to
-    rollout_episodes(actions) / rollout(actions) fed with the returned actions."""
+    rollout_episodes(actions) / rollout(actions) fed with the returned actions.
+    A `GaussianMLPPolicy` goes to earl_tabletop_policy_rollout_gaussian: sample=True draws the actions inside the kernel (tanh(mean + exp(log_std) eps),
+    eps from the env's Philox stream keyed by the global env id and the step's counter), sample=False evaluates the actor at its mean;
+    return_noise=True appends eps [E,T,N,3], the standard-normal draws as used.  Both are for Gaussian policies only."""
+    from ..policy import GaussianMLPPolicy
+    gaussian = isinstance(policy, GaussianMLPPolicy)
+    if not gaussian and (return_noise or not sample):
+      raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
     if self.NOBJ != 1:
       raise NotImplementedError('rollout_policy: single-object env only')
     if reset_first:
@@ -311,12 +318,20 @@ class TabletopManipulation:
         outs = tuple(out)
         ostruct = self._out_struct(outs, lead)
       actions = torch.empty(*lead, 3, dtype=torch.float32, device=self.device)
-      rc = self._lib.earl_tabletop_policy_rollout(self._cfg_ref, self._st_ref, C.byref(policy.struct), E, int(T), int(bool(reset_first)), C.byref(ostruct),
-                                                  actions.data_ptr(), self._stream())
+      if gaussian:
+        eps = torch.empty(*lead, 3, dtype=torch.float32, device=self.device) if return_noise else None
+        head = policy.head(sample=bool(sample), eps_out=eps)
+        rc = self._lib.earl_tabletop_policy_rollout_gaussian(self._cfg_ref, self._st_ref, C.byref(policy.struct), C.byref(head), E, int(T),
+                                                             int(bool(reset_first)), C.byref(ostruct), actions.data_ptr(), self._stream())
+      else:
+        rc = self._lib.earl_tabletop_policy_rollout(self._cfg_ref, self._st_ref, C.byref(policy.struct), E, int(T), int(bool(reset_first)), C.byref(ostruct),
+                                                    actions.data_ptr(), self._stream())
     self._check(rc, 'policy_rollout')
     self._cfg.counter += E * (int(T) + 1) if reset_first else int(T)
     self.total_step_count += E * int(T)
     self._last_success = outs[3][-1, -1] if reset_first else outs[3][-1]
+    if return_noise:
+      return outs + (actions, eps)
     return outs + (actions,)
 
   def make_step_graph(self, T, policy=None):

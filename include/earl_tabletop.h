@@ -122,7 +122,7 @@ int earl_tabletop_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tableto
 enum { EARL_ACT_NONE = 0, EARL_ACT_RELU = 1, EARL_ACT_TANH = 2 };
 typedef struct earl_mlp_policy {
   int32_t n_layers;     /* linear layers: 2 (one hidden) or 3 (two hidden) */
-  int32_t dims[4];      /* dims[0] = 12, dims[n_layers] = 3; hidden widths multiples of 16 in 16..256; unused = 0 */
+  int32_t dims[4];      /* dims[0] = 12, dims[n_layers] = 3 (6 with a Gaussian head, below); hidden widths multiples of 16 in 16..256; unused = 0 */
   int32_t hidden_act;   /* EARL_ACT_RELU or EARL_ACT_TANH */
   int32_t out_act;      /* EARL_ACT_NONE (the env clips to [-1, 1] itself, tabletop_manipulation.py:130) or EARL_ACT_TANH */
   int32_t precision;    /* 0 = fp32; anything else is EARL_ERR_ARG (reserved) */
@@ -141,6 +141,34 @@ typedef struct earl_mlp_policy {
  * tanh is this build's own tanh_f32 (csrc/tabletop_policy.h: fma, +, *, / and integer operations only, no libm). */
 int earl_tabletop_policy_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, int32_t episodes, int32_t T,
                                  int32_t reset_first, const earl_tabletop_out* out, float* act_out, earl_stream_t stream);
+
+/* ---- closed loop with exploration: a tanh-Gaussian head sampled INSIDE the rollout kernel ----
+ * The reference's training loops collect every transition with a stochastic actor (`action = agent.act(obs, sample=True); obs, ... = env.step(action)` around
+ * envs/tabletop_manipulation.py:128-138; the actor is the user's SAC-style network, not the reference's): mean and log_std from one Linear(H, 6), chunked,
+ * action = tanh(mean + exp(log_std) eps).  Evaluation runs the same actor at its mean. */
+enum { EARL_HEAD_MEAN = 0, EARL_HEAD_SAMPLE = 1 };
+enum { EARL_LOGSTD_CLAMP = 0, EARL_LOGSTD_TANH = 1 };
+typedef struct earl_gaussian_head {
+  int32_t mode;          /* EARL_HEAD_MEAN: u = mean.  EARL_HEAD_SAMPLE: u = fmaf(sigma, eps, mean), sigma = exp_f32(ls) */
+  int32_t log_std_map;   /* CLAMP: ls = min(max(raw, lo), hi).  TANH: ls = lo + 0.5 (hi - lo) (tanh_f32(raw) + 1)  (the pytorch_sac / DrQ actor) */
+  float log_std_min;     /* lo and hi: finite, min <= max, inside [-20, 4] */
+  float log_std_max;
+  float* eps_out;        /* may be NULL: [episodes, T, n, 3] the standard-normal draws as used (written in both modes) */
+} earl_gaussian_head;
+
+/* earl_tabletop_policy_rollout with a Gaussian head: `policy` is the same struct with dims[n_layers] == 6 -- output rows 0..2 are the mean, rows 3..5 the raw
+ * log_std, no activation on either; policy->out_act is applied to u (EARL_ACT_TANH: SAC's squashing; EARL_ACT_NONE leaves the clip to the env) and act_out
+ * receives out_act(u).  This replaces the closed loop of the reference's training scripts (agent.act(obs, sample=True) between env.step calls,
+ * envs/tabletop_manipulation.py:128-138) in SAMPLE mode and of its evaluation scripts (sample=False) in MEAN mode, for the whole batch in ONE launch.
+ * eps: one Philox4x32-10 block per (env, step), key = cfg->seed, counter words {0x504F4C00, env_offset + env, counter lo, counter hi} with the counter of that env
+ * step; words x, y, z -> dimensions 0, 1, 2; k = word >> 8, u = (k + 0.5) 2^-24, eps = Phi^-1(u) within 5 float32 ulp (csrc/tabletop_policy.h states the
+ * arithmetic).  The draws depend on (seed, global env id, counter) only: not on n, the shard split, episodes or mode, and they take no counter values of
+ * their own -- everything earl_tabletop_policy_rollout promises carries over: reset_first / episodes rules, NULL-able outputs, argument errors before any HIP
+ * call, Philox counter use (episodes * (T + 1) resp. T), and the launch is bit-identical to earl_tabletop_eval_episodes / earl_tabletop_rollout fed with
+ * act_out.  EARL_HEAD_MEAN is bit-identical to earl_tabletop_policy_rollout on the 3-output policy made of rows 0..2 of the last layer. */
+int earl_tabletop_policy_rollout_gaussian(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
+                                          const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out,
+                                          float* act_out, earl_stream_t stream);
 
 /* PersistentStateWrapper.reset() + TabletopManipulation.reset() for the envs with mask[i] != 0
  * (mask == NULL: all).  Replaces wrappers/persistent_state_wrapper.py:17-20 and
@@ -190,6 +218,11 @@ int earl_tabletop_eval_episodes_cpu(const earl_tabletop_cfg* cfg, const earl_tab
                                     int64_t act_episode_stride, const earl_tabletop_out* out);
 int earl_tabletop_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, int32_t episodes, int32_t T,
                                      int32_t reset_first, const earl_tabletop_out* out, float* act_out);
+/* host twin of earl_tabletop_policy_rollout_gaussian: the closed loop with the sampled actor (agent.act(obs, sample=...) around
+ * envs/tabletop_manipulation.py:128-138), the contract's arithmetic as plain loops; eps_out is a HOST pointer */
+int earl_tabletop_policy_rollout_gaussian_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
+                                              const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
+                                              const earl_tabletop_out* out, float* act_out);
 int earl_tabletop_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, const int32_t* next_goal_idx, float* obs);
 int earl_tabletop_observe_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_tabletop_out* out);
 int earl_tabletop_reward_cpu(int32_t n, const float* obs, int32_t reward_type, int32_t wide_init, float* reward, uint8_t* success);

@@ -3,7 +3,9 @@ probe's two policy shapes and prints / writes the per-phase s_memtime sums of wa
 phase's share of the step.  The stamps cost
 time of their own; the shipped kernel's timings are those of tools/policy_rollout_probe.py.
 
-  bash tools/build_policy_stamped.sh && python tools/prof_policy.py [--out profiles/policy_rollout_phases.json]"""
+  bash tools/build_policy_stamped.sh && python tools/prof_policy.py [--out profiles/policy_rollout_phases.json]
+  python tools/prof_policy.py --gaussian [--out profiles/policy_gaussian_phases.json]     # the Gaussian-head kernels in SAMPLE mode: a sixth phase, the head on
+                                                                                          # wave 0 (the draws run on wave 1 under the output layer's phase)"""
 import argparse
 import ctypes as C
 import json
@@ -17,28 +19,34 @@ from earl_benchmark_amd import _abi  # noqa: E402
 _abi.LIB_PATH = os.path.join(REPO, 'tools', 'ubench', 'libearl_policy_stamped.so')
 import torch  # noqa: E402
 import earl_benchmark_amd as eb  # noqa: E402
-from policy_rollout_probe import random_policy  # noqa: E402
+from policy_rollout_probe import random_gaussian_policy, random_policy  # noqa: E402
 
 PHASES = ('obs_to_lds+barrier', 'layer0+barrier', 'hidden_layer+barrier', 'output_layer+barrier', 'env_step')
+GAUSSIAN_PHASES = PHASES + ('gaussian_head',)
 
 
 def main():
   ap = argparse.ArgumentParser()
-  ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'policy_rollout_phases.json'))
+  ap.add_argument('--out', default=None)
+  ap.add_argument('--gaussian', action='store_true', help='the Gaussian-head kernels (SAMPLE mode) -> profiles/policy_gaussian_phases.json')
   args = ap.parse_args()
+  args.out = args.out or os.path.join(REPO, 'profiles', 'policy_gaussian_phases.json' if args.gaussian else 'policy_rollout_phases.json')
+  phases = GAUSSIAN_PHASES if args.gaussian else PHASES
+  shapes = (('12-64-6', (64,)), ('12-256-256-6', (256, 256))) if args.gaussian else (('12-64-3', (64,)), ('12-256-256-3', (256, 256)))
   n, T, dev = 4096, 200, 'cuda:0'
   lib = _abi.load()
   res = {'n': n, 'T': T, 'unit': 's_memtime ticks per step and share of the step, wave 0 of workgroup 0, stamped build', 'shapes': {}}
-  for name, hidden in (('12-64-3', (64,)), ('12-256-256-3', (256, 256))):
-    pi = random_policy(hidden, 1, dev)
+  for name, hidden in shapes:
+    pi = random_gaussian_policy(hidden, 1, dev)[0] if args.gaussian else random_policy(hidden, 1, dev)
     _, env = eb.EARLEnvs('tabletop_manipulation', reward_type='sparse', num_envs=n, device=dev, seed=5, eval_horizon=T).get_envs()
     for _ in range(3):
       env.rollout_policy(pi, T, episodes=1)
     torch.cuda.synchronize()
-    buf = (C.c_uint64 * 5)()
-    assert lib._handle and C.CDLL(_abi.LIB_PATH).earl_debug_read_policy_profile(buf) == 0
+    buf = (C.c_uint64 * len(phases))()
+    reader = 'earl_debug_read_policy_gaussian_profile' if args.gaussian else 'earl_debug_read_policy_profile'     # (each unit reads its own sums)
+    assert lib._handle and getattr(C.CDLL(_abi.LIB_PATH), reader)(buf) == 0
     ticks = [v / T for v in buf]
-    res['shapes'][name] = {'ticks_per_step': dict(zip(PHASES, ticks), total=sum(ticks)), 'share': {k: v / sum(ticks) for k, v in zip(PHASES, ticks)}}
+    res['shapes'][name] = {'ticks_per_step': dict(zip(phases, ticks), total=sum(ticks)), 'share': {k: v / sum(ticks) for k, v in zip(phases, ticks)}}
     print(name, res['shapes'][name])
   with open(args.out, 'w') as f:
     json.dump(res, f, indent=1)

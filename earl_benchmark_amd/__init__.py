@@ -228,4 +228,7 @@ def __getattr__(name):          # `earl_benchmark_amd.MLPPolicy` without importi
   if name == 'GaussianMLPPolicy':
     from .policy import GaussianMLPPolicy
     return GaussianMLPPolicy
+  if name == 'PolicyPopulation':
+    from .policy import PolicyPopulation
+    return PolicyPopulation
   raise AttributeError(name)

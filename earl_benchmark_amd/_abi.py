@@ -47,6 +47,14 @@ class GaussianHead(C.Structure):  # struct earl_gaussian_head (include/earl_tabl
   _fields_ = [('mode', C.c_int32), ('log_std_map', C.c_int32), ('log_std_min', C.c_float), ('log_std_max', C.c_float), ('eps_out', C.c_void_p)]
 
 
+class PolicyPopulation(C.Structure):   # struct earl_policy_population (include/earl_tabletop.h)
+  _fields_ = [('n_policies', C.c_int32), ('envs_per_policy', C.c_int32), ('param_stride', C.c_int64)]
+
+
+class EpisodeSummary(C.Structure):     # struct earl_episode_summary (include/earl_tabletop.h)
+  _fields_ = [('ret', C.c_void_p), ('success_last', C.c_void_p), ('first_success', C.c_void_p)]
+
+
 class MotorParams(C.Structure):   # struct earl_motor_params (include/earl_glue.h)
   _fields_ = [('kp', C.c_double), ('kd', C.c_double), ('voltage', C.c_double), ('viscous_damping', C.c_double),
               ('torque_control', C.c_int32)]
@@ -132,6 +140,8 @@ SIGNATURES = {
     'earl_tabletop_policy_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), C.c_int32, C.c_int32, C.c_int32, _P(TabletopOut), C.c_void_p, C.c_void_p],
     'earl_tabletop_policy_rollout_gaussian': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), _P(GaussianHead), C.c_int32, C.c_int32, C.c_int32, _P(TabletopOut),
                                               C.c_void_p, C.c_void_p],
+    'earl_tabletop_population_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), _P(PolicyPopulation), _P(GaussianHead), C.c_int32, C.c_int32, C.c_int32,
+                                         _P(TabletopOut), C.c_void_p, _P(EpisodeSummary), C.c_void_p],
     'earl_tabletop_reset': [_P(TabletopCfg), _P(TabletopState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_tabletop_observe': [_P(TabletopCfg), _P(TabletopState), _P(TabletopOut), C.c_void_p],
     'earl_tabletop_reward': [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],

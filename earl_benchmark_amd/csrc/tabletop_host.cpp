@@ -137,8 +137,8 @@ int earl_tabletop_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_ta
   if (int rc = check_policy(cfg, st, policy, episodes, T, reset_first, out)) return rc;
   if (cfg->n == 0) return EARL_OK;
   const PolicyArgs a{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, thresholds()}, *policy, act_out, episodes, reset_first};
-  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) for_each_env(cfg->n, [&](int i) { policy_rollout_env<true>(a, i); });
-  else for_each_env(cfg->n, [&](int i) { policy_rollout_env<false>(a, i); });
+  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) for_each_env(cfg->n, [&](int i) { policy_rollout_env<true>(a, i, a.p.params); });
+  else for_each_env(cfg->n, [&](int i) { policy_rollout_env<false>(a, i, a.p.params); });
   return EARL_OK;
 }
 int earl_tabletop_policy_rollout_gaussian_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
@@ -149,8 +149,22 @@ int earl_tabletop_policy_rollout_gaussian_cpu(const earl_tabletop_cfg* cfg, cons
   GaussianPolicyArgs a;
   static_cast<PolicyArgs&>(a) = PolicyArgs{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, thresholds()}, *policy, act_out, episodes, reset_first};
   a.head = *head;
-  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) for_each_env(cfg->n, [&](int i) { gaussian_rollout_env<true>(a, i); });
-  else for_each_env(cfg->n, [&](int i) { gaussian_rollout_env<false>(a, i); });
+  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) for_each_env(cfg->n, [&](int i) { gaussian_rollout_env<true>(a, i, a.p.params); });
+  else for_each_env(cfg->n, [&](int i) { gaussian_rollout_env<false>(a, i, a.p.params); });
+  return EARL_OK;
+}
+int earl_tabletop_population_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
+                                         const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
+                                         const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary) {
+  if (int rc = check_population(cfg, st, policy, pop, head, episodes, T, reset_first, out)) return rc;
+  if (cfg->n == 0) return EARL_OK;
+  const PopulationArgs a = population_args(cfg, st, policy, pop, head, episodes, T, reset_first, out, act_out, summary, thresholds());
+  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  for_each_env(cfg->n, [&](int i) {                       // the env with global id env_offset + i runs its member's parameters
+    const float* params = a.p.params + population_param_offset(a.pop, a.k.cfg.env_offset + i);
+    if (head) general ? gaussian_rollout_env<true>(a, i, params, &a.sum) : gaussian_rollout_env<false>(a, i, params, &a.sum);
+    else general ? policy_rollout_env<true>(a, i, params, &a.sum) : policy_rollout_env<false>(a, i, params, &a.sum);
+  });
   return EARL_OK;
 }
 int earl_tabletop_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, const int32_t* next_goal_idx, float* obs) {

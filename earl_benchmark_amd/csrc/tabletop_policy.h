@@ -2,7 +2,9 @@
 // launch (include/earl_tabletop.h: earl_tabletop_policy_rollout).  Shared by the gfx950 kernel (tabletop_policy.hip) and its host twin
 // (tabletop_host.cpp, -DEARL_HOST_BUILD); the per-env step is tabletop_step.h's wrapped_step<1, GENERAL>, not restated here.  The same kernel with a
 // Gaussian head (12 -> hidden (-> hidden) -> 6, actions sampled inside the launch: earl_tabletop_policy_rollout_gaussian) is instantiated in
-// tabletop_policy_gaussian.hip; its sampling contract follows the deterministic one below.
+// tabletop_policy_gaussian.hip; its sampling contract follows the deterministic one below.  Both heads for a POPULATION of policies (every 16-env workgroup its own
+// member's parameters) with per-episode summaries (earl_tabletop_population_rollout) are instantiated in tabletop_policy_population.hip; the kernel body the
+// three units share is tabletop_policy_kernel.inc.
 //
 // The policy arithmetic is a contract, stated here once for both builds:
 //   pre-activation   acc = b_j;  for k = 0 .. K-1 ascending:  acc = fmaf(x_k, W_jk, acc)     (float32, one rounding per fused multiply-add)
@@ -196,6 +198,28 @@ template <bool GAUSS>
 struct PolicyArgsOf { using type = PolicyArgs; };
 template <>
 struct PolicyArgsOf<true> { using type = GaussianPolicyArgs; };
+// earl_tabletop_population_rollout: both heads take this one (head unused without GAUSS).  pop.envs_per_policy == 0 = one policy (pop was NULL)
+struct PopulationArgs : GaussianPolicyArgs {
+  earl_policy_population pop;
+  earl_episode_summary sum;
+};
+// the per-episode summary of one env, kept in registers over the T steps (earl_episode_summary)
+struct EpisodeSum {
+  double ret;
+  int32_t first;
+  bool last;
+};
+__host__ __device__ __forceinline__ void episode_sum_begin(EpisodeSum& s) { s.ret = 0.0; s.first = -1; s.last = false; }
+__host__ __device__ __forceinline__ void episode_sum_step(EpisodeSum& s, int t, float reward, bool succ) {
+  s.ret += (double)reward;
+  if (succ && s.first < 0) s.first = t;
+  s.last = succ;
+}
+__host__ __device__ __forceinline__ void episode_sum_store(const earl_episode_summary& d, size_t row, const EpisodeSum& s) {
+  if (d.ret) d.ret[row] = s.ret;
+  if (d.success_last) d.success_last[row] = s.last;
+  if (d.first_success) d.first_success[row] = s.first;
+}
 
 namespace hostside {
 
@@ -232,7 +256,41 @@ inline int check_policy_gaussian(const earl_tabletop_cfg* cfg, const earl_tablet
   return EARL_OK;
 }
 
+// earl_tabletop_population_rollout: the checks of the head's single-policy entry point, then the population's
+inline int check_population(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_policy_population* pop,
+                            const earl_gaussian_head* h, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out) {
+  if (int rc = h ? check_policy_gaussian(cfg, st, p, h, episodes, T, reset_first, out) : check_policy(cfg, st, p, episodes, T, reset_first, out)) return rc;
+  if (!pop) return EARL_OK;
+  if (pop->n_policies < 1) return fail(EARL_ERR_ARG, "population n_policies = %d < 1", pop->n_policies);
+  if (pop->envs_per_policy < kPolicyEnvsPerWg || pop->envs_per_policy % kPolicyEnvsPerWg)
+    return fail(EARL_ERR_ARG, "population envs_per_policy = %d: a multiple of 16, >= 16", pop->envs_per_policy);
+  int64_t count = 0;
+  for (int l = 0; l < p->n_layers; ++l) count += (int64_t)p->dims[l + 1] * (p->dims[l] + 1);
+  if (pop->param_stride < count) return fail(EARL_ERR_ARG, "population param_stride = %lld < %lld parameters of one policy", (long long)pop->param_stride, (long long)count);
+  if (cfg->env_offset < 0) return fail(EARL_ERR_ARG, "population: env_offset = %d < 0", cfg->env_offset);
+  if (cfg->n > 0 && ((int64_t)cfg->env_offset + cfg->n - 1) / pop->envs_per_policy >= pop->n_policies)
+    return fail(EARL_ERR_ARG, "population: global env id %lld runs policy %lld of %d", (long long)cfg->env_offset + cfg->n - 1,
+                ((long long)cfg->env_offset + cfg->n - 1) / pop->envs_per_policy, pop->n_policies);
+  return EARL_OK;
+}
+
+inline PopulationArgs population_args(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_policy_population* pop,
+                                      const earl_gaussian_head* h, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out,
+                                      const earl_episode_summary* sum, const Thresholds& th) {
+  PopulationArgs a;
+  static_cast<PolicyArgs&>(a) = PolicyArgs{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, th}, *p, act_out, episodes, reset_first};
+  a.head = h ? *h : earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr};
+  a.pop = pop ? *pop : earl_policy_population{1, 0, 0};
+  a.sum = sum ? *sum : earl_episode_summary{nullptr, nullptr, nullptr};
+  return a;
+}
+
 }  // namespace hostside
+
+// the member of a population that the env with global id `gid` runs, as an offset into policy->params
+__host__ __device__ __forceinline__ size_t population_param_offset(const earl_policy_population& pop, int gid) {
+  return pop.envs_per_policy > 0 ? (size_t)(gid / pop.envs_per_policy) * (size_t)pop.param_stride : 0;
+}
 
 // the env's side of one closed-loop launch, shared by the kernel's env lanes and the host loop: what happens to ONE env before episode e's first step
 // (reset_body's reset on register state, or nothing) and the observation the first action is computed from
@@ -255,30 +313,36 @@ __device__ __forceinline__ uint64_t policy_step_counter(const PolicyArgs& a, int
 
 // one closed-loop step of one env given the policy's action (a0, a1, a2): act_out, wrapped_step, outputs
 template <bool GENERAL>
-__device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int e, int t, Lane<1>& L, float (&g)[6], float a0, float a1, float a2, float (&o)[12]) {
+__device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int e, int t, Lane<1>& L, float (&g)[6], float a0, float a1, float a2, float (&o)[12],
+                                                float& reward, bool& succ) {
   const size_t row = ((size_t)e * (size_t)a.k.T + (size_t)t) * (size_t)a.k.cfg.n + (size_t)i;
   if (a.act_out) {
     float* ap = a.act_out + row * 3;
     ap[0] = a0; ap[1] = a1; ap[2] = a2;
   }
   const uint64_t counter = policy_step_counter(a, e, t);
-  float reward;
-  bool done, succ;
+  bool done;
   wrapped_step<1, GENERAL>(a.k, i, counter, L, g, a0, a1, a2, o, reward, done, succ);
   if (a.k.out.obs) store_obs<1>(a.k.out.obs + row * 12, o);
   if (a.k.out.reward) a.k.out.reward[row] = reward;
   if (a.k.out.done) a.k.out.done[row] = done;
   if (a.k.out.success) a.k.out.success[row] = succ;
 }
+template <bool GENERAL>
+__device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int e, int t, Lane<1>& L, float (&g)[6], float a0, float a1, float a2, float (&o)[12]) {
+  float reward;
+  bool succ;
+  policy_env_step<GENERAL>(a, i, e, t, L, g, a0, a1, a2, o, reward, succ);
+}
 
 #ifdef EARL_HOST_BUILD
 // ------------------------------------------------------------------------------------------------
 // host twin: the MLP as the plain loops of the contract, one env at a time
 // ------------------------------------------------------------------------------------------------
-inline void mlp_layers(const earl_mlp_policy& p, const float (&x)[12], float* act, int last_act) {
+inline void mlp_layers(const earl_mlp_policy& p, const float* params, const float (&x)[12], float* act, int last_act) {
   float h[2][kPolicyMaxWidth];
   const float* in = x;
-  const float* w = p.params;
+  const float* w = params;
   for (int l = 0; l < p.n_layers; ++l) {
     const int K = p.dims[l], N = p.dims[l + 1];
     const float* b = w + (size_t)N * K;
@@ -293,37 +357,46 @@ inline void mlp_layers(const earl_mlp_policy& p, const float (&x)[12], float* ac
     w = b + N;
   }
 }
-inline void mlp_forward(const earl_mlp_policy& p, const float (&x)[12], float (&act)[3]) { mlp_layers(p, x, act, p.out_act); }
+inline void mlp_forward(const earl_mlp_policy& p, const float* params, const float (&x)[12], float (&act)[3]) { mlp_layers(p, params, x, act, p.out_act); }
 
+// `params`: the parameters this env runs (a population: its member's); `sum`: NULL or the per-episode summary arrays
 template <bool GENERAL>
-inline void policy_rollout_env(const PolicyArgs& a, int i) {
+inline void policy_rollout_env(const PolicyArgs& a, int i, const float* params, const earl_episode_summary* sum = nullptr) {
   Lane<1> L;
   load_lane<1>(a.k, i, L);
   float g[6], o[12];
   load_goal<1>(a.k.st.goal_table, L.goal_idx, g);
   for (int e = 0; e < a.episodes; ++e) {
     policy_episode_begin<GENERAL>(a, i, e, L, g, o);
+    EpisodeSum es;
+    episode_sum_begin(es);
     for (int t = 0; t < a.k.T; ++t) {
-      float act[3];
-      mlp_forward(a.p, o, act);
-      policy_env_step<GENERAL>(a, i, e, t, L, g, act[0], act[1], act[2], o);
+      float act[3], reward;
+      bool succ;
+      mlp_forward(a.p, params, o, act);
+      policy_env_step<GENERAL>(a, i, e, t, L, g, act[0], act[1], act[2], o, reward, succ);
+      episode_sum_step(es, t, reward, succ);
     }
+    if (sum) episode_sum_store(*sum, (size_t)e * (size_t)a.k.cfg.n + (size_t)i, es);
   }
   store_lane<1>(a.k, i, L);
 }
 
 // the Gaussian head: the 6-wide last layer without activation, then the contract's head per dimension
 template <bool GENERAL>
-inline void gaussian_rollout_env(const GaussianPolicyArgs& a, int i) {
+inline void gaussian_rollout_env(const GaussianPolicyArgs& a, int i, const float* params, const earl_episode_summary* sum = nullptr) {
   Lane<1> L;
   load_lane<1>(a.k, i, L);
   float g[6], o[12];
   load_goal<1>(a.k.st.goal_table, L.goal_idx, g);
   for (int e = 0; e < a.episodes; ++e) {
     policy_episode_begin<GENERAL>(a, i, e, L, g, o);
+    EpisodeSum es;
+    episode_sum_begin(es);
     for (int t = 0; t < a.k.T; ++t) {
-      float y[6], act[3];
-      mlp_layers(a.p, o, y, EARL_ACT_NONE);
+      float y[6], act[3], reward;
+      bool succ;
+      mlp_layers(a.p, params, o, y, EARL_ACT_NONE);
       const U4 b = draw_block(a.k.cfg, policy_step_counter(a, e, t), i, kGaussDraw);
       const uint32_t word[3] = {b.x, b.y, b.z};
       const size_t row = ((size_t)e * (size_t)a.k.T + (size_t)t) * (size_t)a.k.cfg.n + (size_t)i;
@@ -332,8 +405,10 @@ inline void gaussian_rollout_env(const GaussianPolicyArgs& a, int i) {
         act[d] = gaussian_head_action(a.head, a.p.out_act, y[d], y[3 + d], eps);
         if (a.head.eps_out) a.head.eps_out[row * 3 + d] = eps;
       }
-      policy_env_step<GENERAL>(a, i, e, t, L, g, act[0], act[1], act[2], o);
+      policy_env_step<GENERAL>(a, i, e, t, L, g, act[0], act[1], act[2], o, reward, succ);
+      episode_sum_step(es, t, reward, succ);
     }
+    if (sum) episode_sum_store(*sum, (size_t)e * (size_t)a.k.cfg.n + (size_t)i, es);
   }
   store_lane<1>(a.k, i, L);
 }
@@ -390,208 +465,23 @@ __device__ __forceinline__ int pol_idx(int row, int k, int K) { return row * K +
 //           eps = normal_quantile_f32, eps -> LDS and eps_out.  The output layer's barrier publishes it.
 //   head    wave 0, after that barrier: log_std map, sigma, u, out_act; the action is written over the mean in the action row, and the env lanes, same
 //           wave, read the row after a wavefront fence.  No workgroup barrier is added, and the three serial tanh_f32 leave the env lane.
+//
+// POP (policy_population_kernel, instantiated in tabletop_policy_population.hip only; argument PopulationArgs): a population of policies and per-episode summaries.
+//   addressing  workgroups are aligned to GLOBAL env ids: workgroup b owns global ids 16 (floor(env_offset / 16) + b) .. + 15, its lanes whose local index falls
+//               outside [0, n) idle like the ragged last workgroup's.  envs_per_policy being a multiple of 16, a workgroup never straddles two members
+//   weights     the prologue's bases gain member * param_stride: wave-uniform scalar arithmetic, once
+//   summaries   on the env lanes, in registers over the T steps, stored once per episode: no atomics, no LDS, no barrier
+//   (the body both kernels share is tabletop_policy_kernel.inc)
+
 template <int NT2, bool GENERAL, bool GAUSS = false>
 __global__ __launch_bounds__(256) void policy_rollout_kernel(const typename PolicyArgsOf<GAUSS>::type a) {
-  constexpr int NOUT = GAUSS ? 6 : 3, ACTW = GAUSS ? 8 : 4, WO_OFF = GAUSS ? kPolWoG : kPolWo;
-  __shared__ __attribute__((aligned(16))) float lds[GAUSS ? kPolLdsG : kPolLds];
-  const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int H1 = a.p.dims[1], HL = a.p.dims[a.p.n_layers - 1], H2 = NT2 > 0 ? a.p.dims[2] : 0;
-  const float* __restrict__ W0 = a.p.params;
-  const float* __restrict__ B0 = W0 + H1 * 12;
-  const float* __restrict__ W1 = B0 + H1;
-  const float* __restrict__ B1 = W1 + H2 * H1;
-  const float* __restrict__ WO = NT2 > 0 ? B1 + H2 : W1;
-  const float* __restrict__ BO = WO + NOUT * HL;
-
-  // ---- prologue: weights into registers, once
-  const int nt0 = (H1 / 16 - wave + 3) >> 2;                          // this wave's N-tiles of layer 0: tl = wave + 4 j, j < nt0
-  float w0[4][3], b0[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int n = (wave + 4 * j) * 16 + c;
-    const bool ok = j < nt0;
-#pragma unroll
-    for (int s = 0; s < 3; ++s) w0[j][s] = ok ? W0[n * 12 + 4 * s + q] : 0.0f;
-    b0[j] = ok ? B0[n] : 0.0f;
-  }
-  constexpr int NT2A = NT2 > 0 ? NT2 : 1;
-  const int nt1 = NT2 > 0 ? (H2 / 16 - wave + 3) >> 2 : 0;
-  float w1[NT2A][64], b1[NT2A];
-  if constexpr (NT2 > 0) {
-#pragma unroll
-    for (int j = 0; j < NT2; ++j) {
-      const int n = (wave + 4 * j) * 16 + c;
-      const bool ok = j < nt1;
-#pragma unroll
-      for (int s = 0; s < 64; ++s) w1[j][s] = (ok && 4 * s < H1) ? W1[n * H1 + 4 * s + q] : 0.0f;
-      b1[j] = ok ? B1[n] : 0.0f;
-    }
-  }
-  // the output layer's B operand: registers too, except beside a 256-wide second hidden layer (NT2 = 4), whose 256 weight registers per lane leave no
-  // room for 64 more -- there it stays in LDS in the order a lane reads it (3 KB, one 16-byte read per four k-steps, independent of the MFMA chain)
-  constexpr bool WO_LDS = GAUSS ? NT2 >= 3 : NT2 == 4;                  // (the Gaussian head's own registers: from NT2 = 3 on)
-  float wo[WO_LDS ? 1 : 64], bo;
-  if constexpr (WO_LDS) {
-    for (int k = (int)threadIdx.x; k < NOUT * HL; k += 256) {
-      const int j = k / HL, kk = k - j * HL;
-      lds[WO_OFF + (j * 4 + (kk & 3)) * (HL >> 2) + (kk >> 2)] = WO[k];
-    }
-    wo[0] = 0.0f;
-  } else {
-#pragma unroll
-    for (int s = 0; s < 64; ++s) wo[s] = (wave == 0 && c < NOUT && 4 * s < HL) ? WO[c * HL + 4 * s + q] : 0.0f;
-  }
-  bo = c < NOUT ? BO[c] : 0.0f;
-
-  // ---- env lanes
-  const int i = blockIdx.x * kPolicyEnvsPerWg + (int)threadIdx.x;
-  const bool env_lane = threadIdx.x < kPolicyEnvsPerWg && i < a.k.cfg.n;
-  Lane<1> L;
-  float g[6], o[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) o[k] = 0.0f;
-  if (env_lane) {
-    load_lane<1>(a.k, i, L);
-    load_goal<1>(a.k.st.goal_table, L.goal_idx, g);
-  }
-  float* const X = lds + kPolX;
-  float* const A1 = lds + kPolH1;
-  float* const A2 = lds + kPolH2;
-  float* const AL = NT2 > 0 ? A2 : A1;
-  float* const ACT = lds + kPolAct;
-
-#ifdef EARL_POLICY_STAMPS
-  unsigned long long prof[6] = {0, 0, 0, 0, 0, 0}, last_ = 0;
-#endif
-  for (int e = 0; e < a.episodes; ++e) {
-    if (env_lane) policy_episode_begin<GENERAL>(a, i, e, L, g, o);
-#ifdef EARL_POLICY_STAMPS
-    last_ = pol_clock();
-#endif
-    for (int t = 0; t < a.k.T; ++t) {
-      if (threadIdx.x < kPolicyEnvsPerWg) {                           // (rows of a ragged last workgroup: zeros, results never read)
-#pragma unroll
-        for (int k = 0; k < 12; ++k) X[pol_idx((int)threadIdx.x, k, 12)] = o[k];
-      }
-      __syncthreads();
-      POL_STAMP(0);
-      // ---- layer 0: 12 -> H1
-      {
-        float xa[3];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) xa[s] = X[c * 12 + q * 3 + s];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (j < nt0) {
-            f32x4 acc = {b0[j], b0[j], b0[j], b0[j]};
-#pragma unroll
-            for (int s = 0; s < 3; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[s], w0[j][s], acc, 0, 0, 0);
-            const int n = (wave + 4 * j) * 16 + c;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) A1[pol_idx(q * 4 + r, n, H1)] = policy_act(acc[r], a.p.hidden_act);
-          }
-        }
-      }
-      __syncthreads();
-      POL_STAMP(1);
-      // ---- hidden layer: H1 -> H2
-      if constexpr (NT2 > 0) {
-        f32x4 acc[NT2];
-#pragma unroll
-        for (int j = 0; j < NT2; ++j) acc[j] = f32x4{b1[j], b1[j], b1[j], b1[j]};
-        if (nt1 > 0) {
-          const float* arow = A1 + c * H1 + q * (H1 >> 2);
-#pragma unroll
-          for (int s4 = 0; s4 < 16; ++s4) {
-            if (s4 * 16 < H1) {
-              const f32x4 av = *reinterpret_cast<const f32x4*>(arow + 4 * s4);
-#pragma unroll
-              for (int s = 0; s < 4; ++s) {
-#pragma unroll
-                for (int j = 0; j < NT2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], w1[j][4 * s4 + s], acc[j], 0, 0, 0);
-              }
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < NT2; ++j) {
-            if (j < nt1) {
-              const int n = (wave + 4 * j) * 16 + c;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) A2[pol_idx(q * 4 + r, n, H2)] = policy_act(acc[j][r], a.p.hidden_act);
-            }
-          }
-        }
-        __syncthreads();
-      }
-      POL_STAMP(2);
-      if constexpr (GAUSS) {
-        // ---- the step's draws on wave 1, beside the output layer: lane = (env, dimension)
-        if (wave == 1 && lane < 3 * kPolicyEnvsPerWg) {
-          const int is = blockIdx.x * kPolicyEnvsPerWg + c;             // (q = the dimension)
-          const U4 b = draw_block(a.k.cfg, policy_step_counter(a, e, t), is, kGaussDraw);
-          const float eps = normal_quantile_f32((q == 0 ? b.x : (q == 1 ? b.y : b.z)) >> 8);
-          lds[kPolEpsG + c * 4 + q] = eps;
-          if (a.head.eps_out && is < a.k.cfg.n) a.head.eps_out[(((size_t)e * (size_t)a.k.T + (size_t)t) * (size_t)a.k.cfg.n + (size_t)is) * 3 + q] = eps;
-        }
-      }
-      // ---- output layer on wave 0: one accumulator, HL / 4 dependent MFMAs
-      if (wave == 0) {
-        f32x4 acc = {bo, bo, bo, bo};
-        const float* arow = AL + c * HL + q * (HL >> 2);
-#pragma unroll
-        for (int s4 = 0; s4 < 16; ++s4) {
-          if (s4 * 16 < HL) {
-            const f32x4 av = *reinterpret_cast<const f32x4*>(arow + 4 * s4);
-            if constexpr (WO_LDS) {
-              f32x4 bv = {0.0f, 0.0f, 0.0f, 0.0f};
-              if (c < NOUT) bv = *reinterpret_cast<const f32x4*>(lds + WO_OFF + (c * 4 + q) * (HL >> 2) + 4 * s4);
-#pragma unroll
-              for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc, 0, 0, 0);
-            } else {
-#pragma unroll
-              for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], wo[4 * s4 + s], acc, 0, 0, 0);
-            }
-          }
-        }
-        if (c < NOUT) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ACT[(q * 4 + r) * ACTW + c] = acc[r];
-        }
-      }
-      __syncthreads();
-      POL_STAMP(3);
-      if constexpr (GAUSS) {
-        // ---- the head, one lane per (env, dimension): lanes 0..47 of wave 0
-        if (threadIdx.x < 3 * kPolicyEnvsPerWg) {
-          const float act = gaussian_head_action(a.head, a.p.out_act, ACT[c * ACTW + q], ACT[c * ACTW + 3 + q], lds[kPolEpsG + c * 4 + q]);
-          ACT[c * ACTW + q] = act;
-        }
-        if (wave == 0) {                                                // the env lanes are lanes of this wave: a wavefront fence, no workgroup barrier
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-        }
-        POL_STAMP(5);
-      }
-      // ---- env step, one lane per env
-      if (env_lane) {
-        const f32x4 av = *reinterpret_cast<const f32x4*>(ACT + (int)threadIdx.x * ACTW);
-        float a0 = av[0], a1 = av[1], a2 = av[2];
-        if constexpr (!GAUSS) {
-          a0 = policy_act(a0, a.p.out_act); a1 = policy_act(a1, a.p.out_act); a2 = policy_act(a2, a.p.out_act);
-        }
-        policy_env_step<GENERAL>(a, i, e, t, L, g, a0, a1, a2, o);
-      }
-      POL_STAMP(4);
-    }
-  }
-#ifdef EARL_POLICY_STAMPS
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) g_policy_prof[k] = prof[k];
-  }
-#endif
-  if (env_lane) store_lane<1>(a.k, i, L);
+  constexpr bool POP = false;
+#include "tabletop_policy_kernel.inc"
+}
+template <int NT2, bool GENERAL, bool GAUSS>
+__global__ __launch_bounds__(256) void policy_population_kernel(const PopulationArgs a) {
+  constexpr bool POP = true;
+#include "tabletop_policy_kernel.inc"
 }
 #endif  // EARL_HOST_BUILD
 

@@ -295,9 +295,11 @@ class TabletopManipulation:
     rollout_episodes(actions) / rollout(actions) fed with the returned actions.
     A `GaussianMLPPolicy` goes to earl_tabletop_policy_rollout_gaussian: sample=True draws the actions inside the kernel (tanh(mean + exp(log_std) eps),
     eps from the env's Philox stream keyed by the global env id and the step's counter), sample=False evaluates the actor at its mean;
-    return_noise=True appends eps [E,T,N,3], the standard-normal draws as used.  Both are for Gaussian policies only."""
-    from ..policy import GaussianMLPPolicy
-    gaussian = isinstance(policy, GaussianMLPPolicy)
+    return_noise=True appends eps [E,T,N,3], the standard-normal draws as used.  Both are for Gaussian policies only.
+    A `PolicyPopulation` goes to earl_tabletop_population_rollout: the env with global id g runs member g // envs_per_policy, same returns."""
+    from ..policy import GaussianMLPPolicy, PolicyPopulation
+    population = isinstance(policy, PolicyPopulation)
+    gaussian = policy.gaussian if population else isinstance(policy, GaussianMLPPolicy)
     if not gaussian and (return_noise or not sample):
       raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
     if self.NOBJ != 1:
@@ -318,8 +320,10 @@ class TabletopManipulation:
         outs = tuple(out)
         ostruct = self._out_struct(outs, lead)
       actions = torch.empty(*lead, 3, dtype=torch.float32, device=self.device)
-      if gaussian:
-        eps = torch.empty(*lead, 3, dtype=torch.float32, device=self.device) if return_noise else None
+      eps = torch.empty(*lead, 3, dtype=torch.float32, device=self.device) if return_noise else None
+      if population:
+        rc = self._population_launch(policy, E, int(T), reset_first, ostruct, actions, eps, sample, None)
+      elif gaussian:
         head = policy.head(sample=bool(sample), eps_out=eps)
         rc = self._lib.earl_tabletop_policy_rollout_gaussian(self._cfg_ref, self._st_ref, C.byref(policy.struct), C.byref(head), E, int(T),
                                                              int(bool(reset_first)), C.byref(ostruct), actions.data_ptr(), self._stream())
@@ -333,6 +337,43 @@ class TabletopManipulation:
     if return_noise:
       return outs + (actions, eps)
     return outs + (actions,)
+
+  def _population_launch(self, policy, E, T, reset_first, ostruct, actions, eps, sample, summary):
+    """earl_tabletop_population_rollout for a PolicyPopulation (pop) or one policy (pop = NULL); -> the return code"""
+    from ..policy import GaussianMLPPolicy, PolicyPopulation
+    population = isinstance(policy, PolicyPopulation)
+    head = policy.head(sample=bool(sample), eps_out=eps) if (policy.gaussian if population else isinstance(policy, GaussianMLPPolicy)) else None
+    return self._lib.earl_tabletop_population_rollout(self._cfg_ref, self._st_ref, C.byref(policy.struct), C.byref(policy.pop_struct) if population else None,
+                                                      None if head is None else C.byref(head), E, T, int(bool(reset_first)), C.byref(ostruct), _ptr(actions),
+                                                      None if summary is None else C.byref(summary), self._stream())
+
+  def evaluate_policy(self, policy, T, episodes=1, sample=False):
+    """`episodes` evaluation episodes (each reset() + T closed-loop steps) of `policy` -- an MLPPolicy, a GaussianMLPPolicy (sample=False: at its mean) or a
+    `PolicyPopulation` (the env with global id g runs member g // envs_per_policy) -- in ONE launch that writes only per-episode summaries
+    (include/earl_tabletop.h: earl_tabletop_population_rollout with every `out` pointer NULL): nothing of size T is allocated.
+    -> {'ret': [E, N] float64 undiscounted return (the float32 step rewards summed in float64, t ascending), 'success': [E, N] bool success at the last step,
+        'first_success': [E, N] int32 first successful step, -1 if none}; each equals its definition applied to what rollout_policy would have returned.
+    Philox counter and total_step_count advance as in rollout_policy."""
+    from ..policy import GaussianMLPPolicy, PolicyPopulation
+    gaussian = policy.gaussian if isinstance(policy, PolicyPopulation) else isinstance(policy, GaussianMLPPolicy)
+    if sample and not gaussian:
+      raise ValueError('evaluate_policy: sample=True needs a Gaussian policy (an MLPPolicy is deterministic)')
+    if self.NOBJ != 1:
+      raise NotImplementedError('evaluate_policy: single-object env only')
+    if policy.device != self.device:
+      raise ValueError(f'evaluate_policy: the policy is on {policy.device}, the env on {self.device} (policy.to(device))')
+    E, T, n = int(episodes), int(T), self.num_envs
+    with self._ctx():
+      ret = torch.empty(E, n, dtype=torch.float64, device=self.device)
+      succ = torch.empty(E, n, dtype=torch.bool, device=self.device)
+      first = torch.empty(E, n, dtype=torch.int32, device=self.device)
+      summary = _abi.EpisodeSummary(ret=ret.data_ptr(), success_last=succ.data_ptr(), first_success=first.data_ptr())
+      rc = self._population_launch(policy, E, T, True, _abi.TabletopOut(None, None, None, None), None, None, sample, summary)
+    self._check(rc, 'population_rollout')
+    self._cfg.counter += E * (T + 1)
+    self.total_step_count += E * T
+    self._last_success = succ[-1]
+    return {'ret': ret, 'success': succ, 'first_success': first}
 
   def make_step_graph(self, T, policy=None):
     """Closed-loop stepping without the per-call host cost: a captured HIP graph of T step launches (see `StepGraph`)."""

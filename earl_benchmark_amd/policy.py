@@ -14,7 +14,15 @@ earl_tabletop_policy_rollout_gaussian: the actions are SAMPLED inside the kernel
   pi = GaussianMLPPolicy(actor_trunk, squash=True, log_std_bounds=(-5.0, 2.0), log_std_map='tanh', device='cuda')
   obs, reward, done, success, actions = env.rollout_policy(pi, T=200, episodes=4)                     # exploration: tanh(mean + exp(log_std) eps)
   obs, reward, done, success, actions, eps = env.rollout_policy(pi, T=200, return_noise=True)         # ... and the standard-normal draws as used
-  obs, reward, done, success, actions = env.rollout_policy(pi, T=200, episodes=4, sample=False)       # evaluation at the mean, same packed network"""
+  obs, reward, done, success, actions = env.rollout_policy(pi, T=200, episodes=4, sample=False)       # evaluation at the mean, same packed network
+
+`PolicyPopulation` is P networks of ONE architecture (checkpoints, seeds, the perturbed copies of an evolution strategy) for earl_tabletop_population_rollout: the env
+with global id g runs member g // envs_per_policy, all in one launch, and `evaluate_policy` returns one return / success per episode instead of [T] arrays.
+
+  pop = PolicyPopulation([pi_0, ..., pi_255], envs_per_policy=16, device='cuda')                      # or PolicyPopulation(pi, params=theta)  with theta [P, n_params]
+  s = env.evaluate_policy(pop, T=200, episodes=4)                                                     # {'ret': [4, N] float64, 'success': [4, N] bool, 'first_success': [4, N] int32}
+  fitness = sharding.population_fitness(s, env_offset, pop.envs_per_policy, pop.n_policies)           # [P, 3]: return sum, success count, rows -- additive over shards
+  pop.params.add_(sigma * noise)                                                                      # [P, stride], read by the next launch as it is"""
 import numpy as np
 import torch
 
@@ -145,3 +153,112 @@ class GaussianMLPPolicy(MLPPolicy):
     mean, log_std = self._mean_and_log_std(obs)
     u = mean + torch.exp(log_std) * torch.as_tensor(eps, dtype=torch.float32, device=mean.device)
     return torch.tanh(u) if self.squash else u
+
+
+class PolicyPopulation:
+  """P members of one architecture behind struct earl_policy_population: `policies` is a list of MLPPolicy or of GaussianMLPPolicy (same dims, activations and,
+  for the Gaussian head, squash / bounds / map -- only the parameters differ), or ONE template policy with `params` [P, n_params] (n_params <= the row length:
+  a wider row is the stride).  The env with GLOBAL id g runs member g // envs_per_policy (a multiple of 16: a member owns whole 16-env workgroups of the kernel).
+  `.params` [P, stride] float32 holds every member in MLPPolicy's packing order (W0, b0, W1, b1, ...) and is what the kernel reads: write into it in place."""
+
+  def __init__(self, policies, envs_per_policy=16, device=None, params=None):
+    G = int(envs_per_policy)
+    if G < 16 or G % 16:
+      raise ValueError(f'PolicyPopulation: envs_per_policy = {envs_per_policy}: a multiple of 16, >= 16')
+    if isinstance(policies, MLPPolicy):
+      if params is None:
+        raise ValueError('PolicyPopulation: a template policy needs params [P, n_params]')
+      template, members = policies, None
+    else:
+      members = list(policies)
+      if not members or not all(isinstance(m, MLPPolicy) for m in members):
+        raise ValueError('PolicyPopulation: a non-empty list of MLPPolicy / GaussianMLPPolicy, or one template policy with params=')
+      if params is not None:
+        raise ValueError('PolicyPopulation: params= goes with ONE template policy, not with a list')
+      template = members[0]
+      for p, m in enumerate(members):
+        for what in ('__class__', 'dims', 'hidden_act', 'out_act') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
+          if getattr(m, what) != getattr(template, what):
+            raise ValueError(f'PolicyPopulation: member {p} has {what.strip("_")} = {getattr(m, what)!r}, member 0 has {getattr(template, what)!r} '
+                             '(the members of a population share one architecture)')
+    self.template, self.envs_per_policy = template, G
+    self.gaussian = isinstance(template, GaussianMLPPolicy)
+    self.dims, self.hidden_act, self.out_act, self.macs = list(template.dims), template.hidden_act, template.out_act, template.macs
+    self.n_params = sum(n * (k + 1) for k, n in zip(self.dims[:-1], self.dims[1:]))
+    if members is not None:
+      host = torch.stack([m.params.detach().to('cpu', torch.float32) for m in members])
+    else:
+      host = torch.as_tensor(params).detach().to('cpu', torch.float32)
+      if host.dim() != 2 or host.shape[0] < 1 or host.shape[1] < self.n_params:
+        raise ValueError(f'PolicyPopulation: params {tuple(host.shape)}: [P, >= {self.n_params}] (one row per member, packed like MLPPolicy.params)')
+    self.n_policies = int(host.shape[0])
+    self.params = host.clone().contiguous()
+    self.to(template.device if device is None else device)
+
+  @property
+  def stride(self):
+    return int(self.params.shape[1])
+
+  def to(self, device):
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+      dev = torch.device('cuda', torch.cuda.current_device())
+    self.device = dev
+    self.params = self.params.to(dev).contiguous()
+    dims = self.dims + [0] * (4 - len(self.dims))
+    self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
+                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=0, params=self.params.data_ptr())
+    self.pop_struct = _abi.PolicyPopulation(n_policies=self.n_policies, envs_per_policy=self.envs_per_policy, param_stride=self.stride)
+    return self
+
+  def head(self, sample=True, eps_out=None):
+    return self.template.head(sample=sample, eps_out=eps_out)
+
+  def _layers_of(self, rows):
+    """rows [..., stride] -> [(W [..., out, in], b [..., out]), ...] views in the packing order"""
+    layers, at = [], 0
+    for k, n in zip(self.dims[:-1], self.dims[1:]):
+      w = rows[..., at:at + n * k].reshape(*rows.shape[:-1], n, k)
+      b = rows[..., at + n * k:at + n * k + n]
+      layers.append((w, b))
+      at += n * k + n
+    return layers
+
+  def member(self, p):
+    """member p as a policy of its own (a copy of its row of .params)"""
+    layers = [(w.clone(), b.clone()) for w, b in self._layers_of(self.params[int(p)].detach().cpu())]
+    t = self.template
+    if self.gaussian:
+      return GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, device=self.device)
+    return MLPPolicy(layers, t.hidden_act, t.out_act, device=self.device)
+
+  def policy_index(self, global_ids):
+    """the member each GLOBAL env id runs"""
+    g = torch.as_tensor(global_ids)
+    return torch.div(g, self.envs_per_policy, rounding_mode='floor')
+
+  def __call__(self, obs, env_offset=0):
+    """obs [..., N, 12] of the envs with global ids env_offset .. env_offset + N - 1 -> actions [..., N, 3] (a Gaussian population: at the mean), every env
+    through its own member: one batched matmul per layer over the members present (torch's summation order: close to the kernel, not bit-identical)"""
+    x = obs.to(torch.float32)
+    lead, N, G = x.shape[:-2], int(x.shape[-2]), self.envs_per_policy
+    m0, m1 = int(env_offset) // G, (int(env_offset) + N - 1) // G
+    if env_offset < 0 or m1 >= self.n_policies:
+      raise ValueError(f'PolicyPopulation: global env ids {env_offset} .. {env_offset + N - 1} need members {m0} .. {m1} of {self.n_policies}')
+    M = m1 - m0 + 1
+    slot = torch.arange(N, device=x.device) + (int(env_offset) - m0 * G)            # where the env sits in the members' [M, G] grid
+    x = x.reshape(-1, N, x.shape[-1])
+    L = x.shape[0]
+    grid = x.new_zeros(L, M * G, x.shape[-1])
+    grid[:, slot] = x
+    h = grid.reshape(L, M, G, -1).permute(1, 0, 2, 3).reshape(M, L * G, -1)
+    layers = self._layers_of(self.params[m0:m1 + 1].to(x.device))
+    for l, (w, b) in enumerate(layers):
+      h = torch.baddbmm(b[:, None, :], h, w.transpose(1, 2))
+      if l + 1 < len(layers):
+        h = torch.relu(h) if self.hidden_act == 'relu' else torch.tanh(h)
+    h = h[..., :ACT_DIM]
+    if self.out_act == 'tanh':
+      h = torch.tanh(h)
+    out = h.reshape(M, L, G, ACT_DIM).permute(1, 0, 2, 3).reshape(L, M * G, ACT_DIM)[:, slot]
+    return out.reshape(*lead, N, ACT_DIM)

@@ -33,6 +33,20 @@ def rollout_summary(reward, success):
   return torch.stack([reward.sum(0), success[-1].to(reward.dtype)], 1).contiguous()
 
 
+def population_fitness(summary, env_offset, envs_per_policy, n_policies):
+  """[P, 3] float64 table of one shard of a population evaluation (`env.evaluate_policy(PolicyPopulation, ...)` -> summary): per member the sum of the
+  episode returns, the number of episodes successful at their last step, and the number of (episode, env) rows it owns in this shard.  The env with
+  global id g = env_offset + i belongs to member g // envs_per_policy.  The table is ADDITIVE over shards: one all-reduce (sum) finishes it, and
+  mean return = [:, 0] / [:, 2], success rate = [:, 1] / [:, 2]."""
+  ret, succ = summary['ret'], summary['success']
+  E, n = ret.shape
+  member = torch.div(torch.arange(n, device=ret.device) + int(env_offset), int(envs_per_policy), rounding_mode='floor')
+  if n and (int(member[0]) < 0 or int(member[-1]) >= int(n_policies)):
+    raise ValueError(f'population_fitness: global env ids {env_offset} .. {env_offset + n - 1} need members up to {int(member[-1])} of {n_policies}')
+  cols = torch.stack([ret.to(torch.float64), succ.to(torch.float64), torch.ones_like(ret, dtype=torch.float64)], -1).sum(0)      # [n, 3]
+  return torch.zeros(int(n_policies), 3, dtype=torch.float64, device=ret.device).index_add_(0, member, cols)
+
+
 def gather_summary(summary, group=None, sizes=None):
   """The single collective of an evaluation job: every rank receives the [N_global, 2] table (rank order = env order).
   One all_gather_into_tensor of the (padded, if the shards are ragged) per-rank tables.  `sizes` (rows per rank), when

@@ -50,6 +50,9 @@ class PersistentStateWrapper(Wrapper):
   def rollout_policy(self, policy, T, **kwargs):
     return self.env.rollout_policy(policy, T, **kwargs)
 
+  def evaluate_policy(self, policy, T, **kwargs):
+    return self.env.evaluate_policy(policy, T, **kwargs)
+
   def is_successful(self, obs=None):
     return self.env.is_successful(obs)
 
@@ -86,6 +89,9 @@ class LifelongWrapper(Wrapper):
 
   def rollout_policy(self, policy, T, **kwargs):
     return self.env.rollout_policy(policy, T, **kwargs)
+
+  def evaluate_policy(self, policy, T, **kwargs):
+    return self.env.evaluate_policy(policy, T, **kwargs)
 
   @property
   def lifelong_return(self):

@@ -170,6 +170,39 @@ int earl_tabletop_policy_rollout_gaussian(const earl_tabletop_cfg* cfg, const ea
                                           const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out,
                                           float* act_out, earl_stream_t stream);
 
+/* ---- closed loop for a POPULATION of policies, with per-episode summaries ----
+ * The EARL protocol evaluates many checkpoints and seeds of one agent, evolution strategies and population-based training evaluate hundreds of perturbed copies
+ * of one network, and both mostly want one return and one success flag per episode (`for _ in range(num_eval_episodes): ...; returns.append(sum(rewards))`
+ * around envs/tabletop_manipulation.py:128-138).  One launch serves all members: every workgroup of the kernel is 16 envs and loads its weights once, so it can
+ * load its OWN member's.  All members share one earl_mlp_policy (dims, activations, precision = 0) and one earl_gaussian_head; only the parameters differ. */
+typedef struct earl_policy_population {
+  int32_t n_policies;        /* P >= 1 */
+  int32_t envs_per_policy;   /* G: a multiple of 16, >= 16.  The env with GLOBAL id g = cfg->env_offset + i runs policy g / G */
+  int64_t param_stride;      /* floats between consecutive policies in policy->params ([P, param_stride]); >= the parameter count of one policy */
+} earl_policy_population;
+
+typedef struct earl_episode_summary {   /* every pointer may be NULL; rows [episodes, n] */
+  double*  ret;            /* sum over t ascending of (double)reward_t, reward_t the float32 value out->reward gets */
+  uint8_t* success_last;   /* success of step T-1 */
+  int32_t* first_success;  /* smallest t with success, -1 if none */
+} earl_episode_summary;
+
+/* earl_tabletop_policy_rollout (head == NULL: policy->dims[n_layers] == 3) or earl_tabletop_policy_rollout_gaussian (head != NULL: == 6) with
+ *   pop      NULL = one policy, as those two; otherwise member g / G of policy->params for the env with global id g.  The member of an env depends on its
+ *            global id only -- not on n or on how the batch is sharded; env_offset need not be a multiple of 16 or of G.  The launch is bit-identical to
+ *            cutting the shard at the global ids that are multiples of G and calling the single-policy entry point on each piece (env_offset = its first
+ *            global id, n = its length, the matching state rows) with that member's parameters: outputs, act_out, eps_out, state left behind, wrapper
+ *            counters, Philox counter use.  With pop == NULL it is bit-identical to the single-policy entry point of the same head.
+ *   summary  NULL, or per-episode reductions kept in registers over the T steps and stored once per episode: each array equals its definition applied to
+ *            this launch's own out->reward / out->success, exactly, whether or not out's pointers / act_out are given (evaluation without any [T] array).
+ * Everything else as the two single-policy entry points: reset_first / episodes rules, every `out` pointer / act_out / eps_out may be NULL (`out` itself
+ * may not), Philox counter use episodes * (T + 1) resp. T, the Gaussian draw contract (seed, global env id, counter), lifelong switching and auto-reset,
+ * argument errors before any HIP call -- to which it adds: G % 16 != 0, G < 16, P < 1, param_stride below the parameter count, env_offset < 0 with pop,
+ * (env_offset + n - 1) / G >= P, head and dims[n_layers] disagreeing.  Single-object env only (the 3-object variant has no policy entry point). */
+int earl_tabletop_population_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
+                                     const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
+                                     const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary, earl_stream_t stream);
+
 /* PersistentStateWrapper.reset() + TabletopManipulation.reset() for the envs with mask[i] != 0
  * (mask == NULL: all).  Replaces wrappers/persistent_state_wrapper.py:17-20 and
  * envs/tabletop_manipulation.py:105-126 (incl. is_valid_init :89-97, get_next_goal :62-76).
@@ -223,6 +256,10 @@ int earl_tabletop_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_ta
 int earl_tabletop_policy_rollout_gaussian_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
                                               const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
                                               const earl_tabletop_out* out, float* act_out);
+/* host twin of earl_tabletop_population_rollout: per env, the member's parameters and the summary's plain loops; bit-identical under the sparse reward */
+int earl_tabletop_population_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
+                                         const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
+                                         const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary);
 int earl_tabletop_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, const int32_t* next_goal_idx, float* obs);
 int earl_tabletop_observe_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_tabletop_out* out);
 int earl_tabletop_reward_cpu(int32_t n, const float* obs, int32_t reward_type, int32_t wide_init, float* reward, uint8_t* success);

@@ -13,7 +13,15 @@ for the policy shapes 12 -> 64 -> 3 (ReLU, tanh out) and 12 -> 256 -> 256 -> 3 (
   (c)  today's deterministic fused launch of the 3-output twin (rows 0..2 of the last layer)
   (c') the fused launch in SAMPLE mode                           -- env.rollout_policy(pi, T, episodes=E): the draws on wave 1 beside the output layer, the head on
        lanes 0..47 of wave 0
-and writes profiles/policy_gaussian_probe.json: (c') over (b') is the bar (>= 1), (c') over (c) the price of sampling."""
+and writes profiles/policy_gaussian_probe.json: (c') over (b') is the bar (>= 1), (c') over (c) the price of sampling.
+
+--population: one launch for a population of policies (earl_tabletop_population_rollout), same method, for 12 -> 64 -> 3 and 12 -> 256 -> 256 -> 3:
+  (c) today's single-policy fused launch, through the unchanged entry point  -- env.rollout_policy(pi, T, episodes=E)
+  (p) the population launch, P = N / 16 members of 16 envs, full outputs     -- env.rollout_policy(PolicyPopulation, T, episodes=E)
+  (s) the same launch with summaries only                                    -- env.evaluate_policy(PolicyPopulation, T, episodes=E)
+  (u) what a user could do before: P launches of the single-policy entry point on 16-env shards, one stream
+and writes profiles/policy_population_probe.json.  The bar: (p) no slower than (c) beyond max(5 %, 3 x the round-to-round spread of (c) in this run), the
+spread being (max - min) / median of (c)'s rounds; (s) is reported against (p) and (u) as the baseline, neither with a bar."""
 import argparse
 import json
 import os
@@ -26,7 +34,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import earl_benchmark_amd as eb  # noqa: E402
-from earl_benchmark_amd.policy import GaussianMLPPolicy, MLPPolicy  # noqa: E402
+from earl_benchmark_amd.policy import GaussianMLPPolicy, MLPPolicy, PolicyPopulation  # noqa: E402
 
 FP32_PEAK = 157.3e12      # MI355X dense fp32 FLOP/s (vector = f32-input MFMA rate)
 
@@ -98,6 +106,58 @@ def gaussian_main(args):
   print('wrote', args.out)
 
 
+def population_main(args):
+  n, T, E, G, dev = args.n, args.steps, args.episodes, 16, 'cuda:0'
+  P = n // G
+  assert n % G == 0, 'the population legs give every member 16 envs: --n a multiple of 16'
+  result = {'n': n, 'T': T, 'episodes': E, 'rounds': args.rounds, 'n_policies': P, 'envs_per_policy': G, 'device': torch.cuda.get_device_name(0), 'shapes': {}}
+  for name, hidden in (('12-64-3', (64,)), ('12-256-256-3', (256, 256))):
+    members = [random_policy(hidden, 1 + p, dev) for p in range(P)]
+    pop = PolicyPopulation(members, envs_per_policy=G, device=dev)
+
+    def make_env(num=n, offset=0):
+      _, env = eb.EARLEnvs('tabletop_manipulation', reward_type='sparse', num_envs=num, env_offset=offset, device=dev, seed=5, eval_horizon=T).get_envs()
+      return env
+    env_c, env_p, env_s = make_env(), make_env(), make_env()
+    shards = [make_env(G, G * p) for p in range(P)]
+
+    def per_policy_launches():
+      for env, pi in zip(shards, members):
+        env.rollout_policy(pi, T, episodes=E)
+    legs = {'c_single_policy_fused_launch': lambda: env_c.rollout_policy(members[0], T, episodes=E), 'p_population_launch_full_outputs': lambda: env_p.rollout_policy(pop, T, episodes=E),
+            's_population_launch_summary_only': lambda: env_s.evaluate_policy(pop, T, episodes=E), 'u_one_launch_per_policy_on_16_env_shards': per_policy_launches}
+    for fn in legs.values():             # warm-up
+      fn()
+      fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in legs}
+    for _ in range(args.rounds):         # interleaved rounds in one process
+      for k, fn in legs.items():
+        times[k].append(timed(fn))
+    steps = n * T * E
+    shape = {'macs_per_env_step': members[0].macs, 'population_parameter_bytes': pop.params.numel() * 4}
+    for k in legs:
+      med, best = statistics.median(times[k]), min(times[k])
+      shape[k] = {'env_steps_per_s_median': steps / med, 'env_steps_per_s_best': steps / best, 'seconds_median': med, 'seconds_rounds': times[k], 'us_per_step_median': med / (T * E) * 1e6}
+    sec = lambda k: shape[k]['seconds_median']
+    tc = times['c_single_policy_fused_launch']
+    spread = (max(tc) - min(tc)) / statistics.median(tc)
+    shape['spread_of_c'] = spread
+    shape['margin'] = max(0.05, 3 * spread)
+    shape['p_over_c_seconds'] = sec('p_population_launch_full_outputs') / sec('c_single_policy_fused_launch')
+    shape['p_within_margin_of_c'] = shape['p_over_c_seconds'] <= 1 + shape['margin']
+    shape['s_over_p_seconds'] = sec('s_population_launch_summary_only') / sec('p_population_launch_full_outputs')
+    shape['u_over_p_seconds'] = sec('u_one_launch_per_policy_on_16_env_shards') / sec('p_population_launch_full_outputs')
+    result['shapes'][name] = shape
+    print(name, json.dumps(shape))
+    del shards
+  os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+  with open(args.out, 'w') as f:
+    json.dump(result, f, indent=1)
+    f.write('\n')
+  print('wrote', args.out)
+
+
 def timed(fn):
   a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
   a.record()
@@ -111,14 +171,18 @@ def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--out', default=None)
   ap.add_argument('--gaussian', action='store_true', help="the stochastic legs (b'), (c), (c') -> profiles/policy_gaussian_probe.json")
+  ap.add_argument('--population', action='store_true', help='the population legs (c), (p), (s), (u) -> profiles/policy_population_probe.json')
   ap.add_argument('--n', type=int, default=4096)
   ap.add_argument('--steps', type=int, default=200)
   ap.add_argument('--episodes', type=int, default=4)
   ap.add_argument('--rounds', type=int, default=9)
   args = ap.parse_args()
-  args.out = args.out or os.path.join(REPO, 'profiles', 'policy_gaussian_probe.json' if args.gaussian else 'policy_rollout_probe.json')
+  args.out = args.out or os.path.join(REPO, 'profiles', 'policy_gaussian_probe.json' if args.gaussian else
+                                      'policy_population_probe.json' if args.population else 'policy_rollout_probe.json')
   if args.gaussian:
     return gaussian_main(args)
+  if args.population:
+    return population_main(args)
   n, T, E, dev = args.n, args.steps, args.episodes, 'cuda:0'
   result = {'n': n, 'T': T, 'episodes': E, 'rounds': args.rounds, 'device': torch.cuda.get_device_name(0), 'fp32_peak_flops': FP32_PEAK, 'shapes': {}}
   for name, hidden in (('12-64-3', (64,)), ('12-256-256-3', (256, 256))):

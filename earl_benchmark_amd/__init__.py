@@ -231,4 +231,7 @@ def __getattr__(name):          # `earl_benchmark_amd.MLPPolicy` without importi
   if name == 'PolicyPopulation':
     from .policy import PolicyPopulation
     return PolicyPopulation
+  if name == 'AgentPair':
+    from .policy import AgentPair
+    return AgentPair
   raise AttributeError(name)

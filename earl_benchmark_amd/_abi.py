@@ -55,6 +55,14 @@ class EpisodeSummary(C.Structure):     # struct earl_episode_summary (include/ea
   _fields_ = [('ret', C.c_void_p), ('success_last', C.c_void_p), ('first_success', C.c_void_p)]
 
 
+class AgentPair(C.Structure):          # struct earl_agent_pair (include/earl_tabletop.h)
+  _fields_ = [('switch_every', C.c_int32 * 2), ('switch_on_success', C.c_int32), ('pad_', C.c_int32), ('param_stride', C.c_int64), ('backward_goal', C.c_void_p),
+              ('phase', C.c_void_p), ('steps_in_phase', C.c_void_p), ('agent_out', C.c_void_p), ('forward_success', C.c_void_p), ('backward_success', C.c_void_p)]
+
+
+PAIR_MAX_H2 = 128                      # EARL_PAIR_MAX_H2: the widest second hidden layer of an agent pair
+
+
 class MotorParams(C.Structure):   # struct earl_motor_params (include/earl_glue.h)
   _fields_ = [('kp', C.c_double), ('kd', C.c_double), ('voltage', C.c_double), ('viscous_damping', C.c_double),
               ('torque_control', C.c_int32)]
@@ -142,6 +150,8 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p],
     'earl_tabletop_population_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), _P(PolicyPopulation), _P(GaussianHead), C.c_int32, C.c_int32, C.c_int32,
                                          _P(TabletopOut), C.c_void_p, _P(EpisodeSummary), C.c_void_p],
+    'earl_tabletop_pair_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), _P(AgentPair), _P(GaussianHead), C.c_int32, C.c_int32, C.c_int32, _P(TabletopOut),
+                                   C.c_void_p, C.c_void_p],
     'earl_tabletop_reset': [_P(TabletopCfg), _P(TabletopState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_tabletop_observe': [_P(TabletopCfg), _P(TabletopState), _P(TabletopOut), C.c_void_p],
     'earl_tabletop_reward': [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],

@@ -167,6 +167,14 @@ int earl_tabletop_population_rollout_cpu(const earl_tabletop_cfg* cfg, const ear
   });
   return EARL_OK;
 }
+int earl_tabletop_pair_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair,
+                                   const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out) {
+  if (int rc = check_pair(cfg, st, policy, pair, head, episodes, T, reset_first, out)) return rc;
+  if (cfg->n == 0) return EARL_OK;
+  const PairArgs a = pair_args(cfg, st, policy, pair, head, episodes, T, reset_first, out, act_out, thresholds());
+  for_each_env(cfg->n, [&](int i) { pair_rollout_env(a, i, head != nullptr); });
+  return EARL_OK;
+}
 int earl_tabletop_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, const int32_t* next_goal_idx, float* obs) {
   return do_reset<1>(cfg, st, mask, next_goal_idx, obs);
 }

@@ -203,6 +203,12 @@ struct PopulationArgs : GaussianPolicyArgs {
   earl_policy_population pop;
   earl_episode_summary sum;
 };
+// earl_tabletop_pair_rollout: both heads take this one (head unused without one).  p.params is [2, pair.param_stride]
+struct PairArgs : GaussianPolicyArgs {
+  earl_agent_pair pair;
+};
+// the widest second hidden layer of an agent pair: two weight sets share the 512 registers of one wave per SIMD (tabletop_policy_pair.hip has the table)
+constexpr int kPairMaxH2 = EARL_PAIR_MAX_H2;
 // the per-episode summary of one env, kept in registers over the T steps (earl_episode_summary)
 struct EpisodeSum {
   double ret;
@@ -285,6 +291,34 @@ inline PopulationArgs population_args(const earl_tabletop_cfg* cfg, const earl_t
   return a;
 }
 
+// earl_tabletop_pair_rollout: the checks of the head's single-policy entry point, then the pair's
+inline int check_pair(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_agent_pair* pair, const earl_gaussian_head* h,
+                      int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out) {
+  if (int rc = h ? check_policy_gaussian(cfg, st, p, h, episodes, T, reset_first, out) : check_policy(cfg, st, p, episodes, T, reset_first, out)) return rc;
+  if (!pair) return fail(EARL_ERR_ARG, "pair is NULL");
+  if (!pair->phase || !pair->steps_in_phase) return fail(EARL_ERR_ARG, "pair phase/steps_in_phase is NULL");
+  for (int k = 0; k < 2; ++k)
+    if (pair->switch_every[k] < 1) return fail(EARL_ERR_ARG, "pair switch_every[%d] = %d < 1", k, pair->switch_every[k]);
+  if (pair->switch_on_success != 0 && pair->switch_on_success != 1) return fail(EARL_ERR_ARG, "pair switch_on_success = %d", pair->switch_on_success);
+  int64_t count = 0;
+  for (int l = 0; l < p->n_layers; ++l) count += (int64_t)p->dims[l + 1] * (p->dims[l] + 1);
+  if (pair->param_stride < count) return fail(EARL_ERR_ARG, "pair param_stride = %lld < %lld parameters of one agent", (long long)pair->param_stride, (long long)count);
+  if (cfg->goal_change_frequency > 0)
+    return fail(EARL_ERR_ARG, "pair: goal_change_frequency = %d > 0 (the pair is the lifelong mechanism: the two clocks would fight over the same draw)", cfg->goal_change_frequency);
+  if (p->n_layers == 3 && p->dims[2] > kPairMaxH2)
+    return fail(EARL_ERR_ARG, "pair: second hidden width %d > EARL_PAIR_MAX_H2 = %d (two weight sets in one wave's registers)", p->dims[2], kPairMaxH2);
+  return EARL_OK;
+}
+
+inline PairArgs pair_args(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_agent_pair* pair, const earl_gaussian_head* h,
+                          int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out, const Thresholds& th) {
+  PairArgs a;
+  static_cast<PolicyArgs&>(a) = PolicyArgs{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, th}, *p, act_out, episodes, reset_first};
+  a.head = h ? *h : earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr};
+  a.pair = *pair;
+  return a;
+}
+
 }  // namespace hostside
 
 // the member of a population that the env with global id `gid` runs, as an offset into policy->params
@@ -333,6 +367,99 @@ __device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int 
   float reward;
   bool succ;
   policy_env_step<GENERAL>(a, i, e, t, L, g, a0, a1, a2, o, reward, succ);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The agent pair (include/earl_tabletop.h: earl_tabletop_pair_rollout), the env's side, shared by the kernel's env lanes (tabletop_policy_pair.hip) and the
+// host loop: the phase state of one env and what a step does to it.  The order of pair_env_step IS the contract of record's items 3 .. 6.
+// ------------------------------------------------------------------------------------------------
+struct PairLane {
+  int phase;   // 0 forward, 1 reset
+  int sip;     // steps in phase
+  int fs, bs;  // forward / reset phases of this episode that ended by success
+};
+
+// the goal in force: the reset agent's row if there is one, otherwise the env's stored task goal
+__device__ __forceinline__ void pair_goal(const PairArgs& a, const Lane<1>& L, int phase, float (&g)[6]) {
+  if (phase && a.pair.backward_goal) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) g[k] = (float)a.pair.backward_goal[k];
+  } else {
+    load_goal<1>(a.k.st.goal_table, L.goal_idx, g);
+  }
+}
+
+__device__ __forceinline__ void pair_load(const PairArgs& a, int i, const Lane<1>& L, PairLane& P, float (&g)[6]) {
+  P.phase = a.pair.phase[i] != 0;
+  P.sip = a.pair.steps_in_phase[i];
+  P.fs = 0;
+  P.bs = 0;
+  pair_goal(a, L, P.phase, g);
+}
+
+// episode e's begin: policy_episode_begin, and a reset puts the env into the forward phase
+__device__ __forceinline__ void pair_episode_begin(const PairArgs& a, int i, int e, Lane<1>& L, PairLane& P, float (&g)[6], float (&o)[12]) {
+  if (a.reset_first) {
+    P.phase = 0;
+    P.sip = 0;
+  }
+  P.fs = 0;
+  P.bs = 0;
+  policy_episode_begin<true>(a, i, e, L, g, o);
+}
+
+__device__ __forceinline__ void pair_episode_end(const PairArgs& a, int i, int e, const PairLane& P) {
+  const size_t row = (size_t)e * (size_t)a.k.cfg.n + (size_t)i;
+  if (a.pair.forward_success) a.pair.forward_success[row] = P.fs;
+  if (a.pair.backward_success) a.pair.backward_success[row] = P.bs;
+}
+
+__device__ __forceinline__ void pair_store(const PairArgs& a, int i, const Lane<1>& L, const PairLane& P) {
+  store_lane<1>(a.k, i, L);
+  a.k.st.goal_idx[i] = L.goal_idx;                  // (store_lane writes it under lifelong / reset only)
+  a.pair.phase[i] = (int8_t)P.phase;
+  a.pair.steps_in_phase[i] = P.sip;
+}
+
+// one closed-loop step of one env given ITS agent's action: agent_out, act_out, wrapped_step, the handover, outputs
+__device__ __forceinline__ void pair_env_step(const PairArgs& a, int i, int e, int t, Lane<1>& L, PairLane& P, float (&g)[6], float a0, float a1, float a2,
+                                              float (&o)[12]) {
+  const size_t row = ((size_t)e * (size_t)a.k.T + (size_t)t) * (size_t)a.k.cfg.n + (size_t)i;
+  if (a.pair.agent_out) a.pair.agent_out[row] = (int8_t)P.phase;
+  if (a.act_out) {
+    float* ap = a.act_out + row * 3;
+    ap[0] = a0; ap[1] = a1; ap[2] = a2;
+  }
+  const uint64_t counter = policy_step_counter(a, e, t);
+  const int resets = L.resets;
+  float reward;
+  bool done, succ;
+  wrapped_step<1, true>(a.k, i, counter, L, g, a0, a1, a2, o, reward, done, succ);
+  if (L.resets != resets) {                         // auto-reset: back to the forward agent (g is the new task goal already), nothing else
+    P.phase = 0;
+    P.sip = 0;
+  } else {
+    P.sip += 1;
+    const bool by_success = a.pair.switch_on_success && succ;
+    if (by_success || P.sip >= (P.phase ? a.pair.switch_every[1] : a.pair.switch_every[0])) {
+      if (by_success) {
+        if (P.phase) P.bs += 1;
+        else P.fs += 1;
+      }
+      P.phase ^= 1;
+      P.sip = 0;
+      if (P.phase == 0) L.goal_idx = sample_goal(a.k.cfg, counter, i, nullptr);      // the draw the lifelong switch makes
+      if (P.phase == 0 || a.pair.backward_goal) {
+        pair_goal(a, L, P.phase, g);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) o[6 + k] = g[k];                                   // obs re-read with the new goal
+      }
+    }
+  }
+  if (a.k.out.obs) store_obs<1>(a.k.out.obs + row * 12, o);
+  if (a.k.out.reward) a.k.out.reward[row] = reward;
+  if (a.k.out.done) a.k.out.done[row] = done;
+  if (a.k.out.success) a.k.out.success[row] = succ;
 }
 
 #ifdef EARL_HOST_BUILD
@@ -413,6 +540,39 @@ inline void gaussian_rollout_env(const GaussianPolicyArgs& a, int i, const float
   store_lane<1>(a.k, i, L);
 }
 
+// the agent pair: per step the network of the env's phase, the head's draw (phase-independent), pair_env_step
+inline void pair_rollout_env(const PairArgs& a, int i, bool gauss) {
+  Lane<1> L;
+  load_lane<1>(a.k, i, L);
+  PairLane P;
+  float g[6], o[12];
+  pair_load(a, i, L, P, g);
+  for (int e = 0; e < a.episodes; ++e) {
+    pair_episode_begin(a, i, e, L, P, g, o);
+    for (int t = 0; t < a.k.T; ++t) {
+      const float* params = a.p.params + (size_t)P.phase * (size_t)a.pair.param_stride;
+      float act[3];
+      if (gauss) {
+        float y[6];
+        mlp_layers(a.p, params, o, y, EARL_ACT_NONE);
+        const U4 b = draw_block(a.k.cfg, policy_step_counter(a, e, t), i, kGaussDraw);
+        const uint32_t word[3] = {b.x, b.y, b.z};
+        const size_t row = ((size_t)e * (size_t)a.k.T + (size_t)t) * (size_t)a.k.cfg.n + (size_t)i;
+        for (int d = 0; d < 3; ++d) {
+          const float eps = normal_quantile_f32(word[d] >> 8);
+          act[d] = gaussian_head_action(a.head, a.p.out_act, y[d], y[3 + d], eps);
+          if (a.head.eps_out) a.head.eps_out[row * 3 + d] = eps;
+        }
+      } else {
+        mlp_forward(a.p, params, o, act);
+      }
+      pair_env_step(a, i, e, t, L, P, g, act[0], act[1], act[2], o);
+    }
+    pair_episode_end(a, i, e, P);
+  }
+  pair_store(a, i, L, P);
+}
+
 #else
 // ------------------------------------------------------------------------------------------------
 // gfx950 kernel.  One workgroup = 16 envs (the M of v_mfma_f32_16x16x4_f32) x four waves.
@@ -444,7 +604,7 @@ constexpr int kPolLdsG = kPolEpsG + 16 * 4;
 // workgroup 0 at the end of each phase of a step, summed over the launch: [0] observation -> LDS + barrier, [1] layer 0 + barrier, [2] hidden layer +
 // barrier, [3] output layer + barrier (GAUSS: wave 1 makes the step's draws meanwhile), [4] env step (action read, tanh, wrapped_step, stores), [5] GAUSS only:
 // the head on lanes 0..47 of wave 0 + the wavefront fence.  Each unit that instantiates the kernel has its own copy of the sums and its own reader
-// (earl_debug_read_policy_profile: 5 words; earl_debug_read_policy_gaussian_profile: 6).
+// (earl_debug_read_policy_profile: 5 words; earl_debug_read_policy_gaussian_profile: 6; earl_debug_read_policy_pair_profile: 6, [0] with the phase ballot).
 #ifdef EARL_POLICY_STAMPS
 static __device__ unsigned long long g_policy_prof[8];
 __device__ __forceinline__ unsigned long long pol_clock() {

@@ -2,6 +2,8 @@
 // POP = false; policy_population_kernel: POP = true).  In scope: the template parameters NT2, GENERAL, GAUSS, a constexpr bool POP, and the kernel argument `a`.
 // It is text, not a function: routed through a __forceinline__ function the single-policy kernels compile to different register allocations
 // (profiles/policy_kernel_resources.txt), and their twenty instantiations are to stay exactly what they were.
+// TWIN: tabletop_policy_pair.hip restates this step body (layer 0, hidden layer, output chain, head, fence) per agent; the pair's actions are held bit for bit to
+// this chain, so a change to the arithmetic or its order here is mirrored there by hand (tests/test_policy_pair.py, test 1, compares the two).
   constexpr int NOUT = GAUSS ? 6 : 3, ACTW = GAUSS ? 8 : 4, WO_OFF = GAUSS ? kPolWoG : kPolWo;
   __shared__ __attribute__((aligned(16))) float lds[GAUSS ? kPolLdsG : kPolLds];
   const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;

@@ -107,6 +107,9 @@ class TabletopManipulation:
     self.lifelong_return_t = torch.zeros(n, dtype=torch.float64, **kw)
     self.total_step_count = 0
     self._last_success = None
+    self.agent_phase = None                                          # [N] int8 / [N] int32, allocated by the first rollout_agents: an env that never saw an
+    self.steps_in_phase = None                                       # agent pair behaves and serialises as it always did
+    self._pair_counts = None
 
     self._cfg = _abi.TabletopCfg(n=n, env_offset=int(env_offset), reward_type=_abi.REWARD_TYPES[reward_type],
                                  wide_init=int(self._wide_init_distr), reset_at_goal=int(self._reset_at_goal),
@@ -203,6 +206,14 @@ class TabletopManipulation:
     (optional, [N]) injects the goal-table rows instead of sampling, like `reset_goal(goal)` in the reference."""
     with self._ctx():
       obs = self._reset_kernel(mask, goal_idx)
+      if self.agent_phase is not None:                               # a reset env is the forward agent's again
+        if mask is None:
+          self.agent_phase.zero_()
+          self.steps_in_phase.zero_()
+        else:
+          m = torch.as_tensor(mask, device=self.device).bool()
+          self.agent_phase[m] = 0
+          self.steps_in_phase[m] = 0
     return obs[0].cpu().numpy() if self.scalar_api else obs
 
   def _out_struct(self, outs, lead):
@@ -375,6 +386,68 @@ class TabletopManipulation:
     self._last_success = succ[-1]
     return {'ret': ret, 'success': succ, 'first_success': first}
 
+  def rollout_agents(self, pair, T, episodes=None, reset_first=False, sample=True, return_noise=False, out=None):
+    """The forward / reset agent pair of autonomous RL alternating inside ONE kernel launch (include/earl_tabletop.h: earl_tabletop_pair_rollout): every env is
+    driven by the agent of its phase (`env.agent_phase`: 0 forward, 1 reset) and handed over after pair.switch_every[phase] steps or, with
+    pair.switch_on_success, after a step whose success flag is set.  The default is the continuing form -- T steps from the current state, the training
+    stream; reset_first=True: `episodes` evaluation episodes, each reset() + T steps starting with the forward agent.
+    -> (obs [T,N,D], reward [T,N], done, success, actions [T,N,3], agent [T,N] int8 = the agent that computed the action) -- with a leading E axis when
+    reset_first=True; return_noise=True (Gaussian agents) appends eps.  `env.pair_counts` = (forward phases, reset phases) [E, N] that ended by success in
+    this launch.  The reset agent sees pair.backward_goal in its observation's goal slots; `goal_idx` keeps the env's task goal throughout."""
+    from ..policy import AgentPair
+    if not isinstance(pair, AgentPair):
+      raise ValueError('rollout_agents: pair is an AgentPair')
+    if self.NOBJ != 1:
+      raise NotImplementedError('rollout_agents: single-object env only')
+    if self._cfg.goal_change_frequency > 0:
+      raise ValueError('rollout_agents: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
+                       'not under a LifelongWrapper, whose clock would fight the pair\'s over the same draw')
+    if not pair.gaussian and (return_noise or not sample):
+      raise ValueError('rollout_agents: sample=False / return_noise=True need Gaussian agents (MLPPolicy agents are deterministic)')
+    if reset_first:
+      E = 1 if episodes is None else int(episodes)
+      lead = (E, int(T), self.num_envs)
+    else:
+      if episodes not in (None, 1):
+        raise ValueError('rollout_agents: a continuing rollout (reset_first=False) is one episode')
+      E, lead = 1, (int(T), self.num_envs)
+    if pair.device != self.device:
+      raise ValueError(f'rollout_agents: the pair is on {pair.device}, the env on {self.device} (pair.to(device))')
+    with self._ctx():
+      if self.agent_phase is None:
+        self.agent_phase = torch.zeros(self.num_envs, dtype=torch.int8, device=self.device)
+        self.steps_in_phase = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+      if out is None:
+        outs, ostruct = self._new_out(lead)
+      else:
+        outs = tuple(out)
+        ostruct = self._out_struct(outs, lead)
+      actions = torch.empty(*lead, 3, dtype=torch.float32, device=self.device)
+      agent = torch.empty(*lead, dtype=torch.int8, device=self.device)
+      eps = torch.empty(*lead, 3, dtype=torch.float32, device=self.device) if return_noise else None
+      fwd = torch.empty(E, self.num_envs, dtype=torch.int32, device=self.device)
+      bwd = torch.empty(E, self.num_envs, dtype=torch.int32, device=self.device)
+      goal = pair.goal_row(self)
+      ps = _abi.AgentPair(switch_every=(_abi.C.c_int32 * 2)(*pair.switch_every), switch_on_success=int(pair.switch_on_success), pad_=0, param_stride=pair.stride,
+                          backward_goal=_ptr(goal), phase=self.agent_phase.data_ptr(), steps_in_phase=self.steps_in_phase.data_ptr(),
+                          agent_out=agent.data_ptr(), forward_success=fwd.data_ptr(), backward_success=bwd.data_ptr())
+      head = pair.head(sample=bool(sample), eps_out=eps) if pair.gaussian else None
+      rc = self._lib.earl_tabletop_pair_rollout(self._cfg_ref, self._st_ref, C.byref(pair.struct), C.byref(ps), None if head is None else C.byref(head), E, int(T),
+                                                int(bool(reset_first)), C.byref(ostruct), actions.data_ptr(), self._stream())
+    self._check(rc, 'pair_rollout')
+    self._cfg.counter += E * (int(T) + 1) if reset_first else int(T)
+    self.total_step_count += E * int(T)
+    self._last_success = outs[3][-1, -1] if reset_first else outs[3][-1]
+    self._pair_counts = (fwd, bwd)
+    if return_noise:
+      return outs + (actions, agent, eps)
+    return outs + (actions, agent)
+
+  @property
+  def pair_counts(self):
+    """(forward_success, backward_success) [E, N] int32 of the last rollout_agents launch: the phases that ended by success; None before the first"""
+    return self._pair_counts
+
   def make_step_graph(self, T, policy=None):
     """Closed-loop stepping without the per-call host cost: a captured HIP graph of T step launches (see `StepGraph`)."""
     return StepGraph(self, T, policy)
@@ -515,11 +588,14 @@ class TabletopManipulation:
 
   # ------------------------------------------------------------------ checkpoint / counters
   def state_dict(self):
-    return {'qpos': self.qpos.clone(), 'attached': self.attached.clone(), 'goal_idx': self.goal_idx.clone(),
-            'goal_table': self.goal_table.clone(), 'steps_since_reset': self.steps_since_reset.clone(),
-            'interventions': self.interventions.clone(), 'steps_since_goal_change': self.steps_since_goal_change.clone(),
-            'lifelong_return': self.lifelong_return_t.clone(), 'total_step_count': self.total_step_count,
-            'rng_counter': int(self._cfg.counter), 'seed': int(self._cfg.seed)}
+    sd = {'qpos': self.qpos.clone(), 'attached': self.attached.clone(), 'goal_idx': self.goal_idx.clone(),
+          'goal_table': self.goal_table.clone(), 'steps_since_reset': self.steps_since_reset.clone(),
+          'interventions': self.interventions.clone(), 'steps_since_goal_change': self.steps_since_goal_change.clone(),
+          'lifelong_return': self.lifelong_return_t.clone(), 'total_step_count': self.total_step_count,
+          'rng_counter': int(self._cfg.counter), 'seed': int(self._cfg.seed)}
+    if self.agent_phase is not None:                                 # the agent pair's state, once a pair launch has created it -- and only then
+      sd['agent_phase'], sd['steps_in_phase'] = self.agent_phase.clone(), self.steps_in_phase.clone()
+    return sd
 
   def load_state_dict(self, sd):
     self.goal_table = sd['goal_table'].to(self.device).clone().contiguous()
@@ -530,6 +606,12 @@ class TabletopManipulation:
     self.total_step_count = int(sd['total_step_count'])
     self._cfg.counter = int(sd['rng_counter'])
     self._cfg.seed = int(sd['seed'])
+    if 'agent_phase' in sd:
+      self.agent_phase = sd['agent_phase'].to(self.device).clone().contiguous()
+      self.steps_in_phase = sd['steps_in_phase'].to(self.device).clone().contiguous()
+    elif self.agent_phase is not None:                               # a checkpoint from before any pair launch: every env is the forward agent's
+      self.agent_phase.zero_()
+      self.steps_in_phase.zero_()
     self._sync_state_ptrs()
 
 

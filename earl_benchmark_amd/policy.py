@@ -22,7 +22,14 @@ with global id g runs member g // envs_per_policy, all in one launch, and `evalu
   pop = PolicyPopulation([pi_0, ..., pi_255], envs_per_policy=16, device='cuda')                      # or PolicyPopulation(pi, params=theta)  with theta [P, n_params]
   s = env.evaluate_policy(pop, T=200, episodes=4)                                                     # {'ret': [4, N] float64, 'success': [4, N] bool, 'first_success': [4, N] int32}
   fitness = sharding.population_fitness(s, env_offset, pop.envs_per_policy, pop.n_policies)           # [P, 3]: return sum, success count, rows -- additive over shards
-  pop.params.add_(sigma * noise)                                                                      # [P, stride], read by the next launch as it is"""
+  pop.params.add_(sigma * noise)                                                                      # [P, stride], read by the next launch as it is
+
+`AgentPair` is the forward / reset agent pair of autonomous RL for earl_tabletop_pair_rollout: two networks of ONE architecture that hand every env to each other
+after a fixed number of steps or as soon as the acting agent has succeeded, inside one launch.
+
+  pair = AgentPair(forward_pi, backward_pi, switch_every=(200, 200), switch_on_success=True, backward_goal='initial', device='cuda')
+  obs, reward, done, success, actions, agent = env.rollout_agents(pair, T=1000)                       # the training stream: continuing, agent [T, N] int8 = who acted
+  env.agent_phase, env.steps_in_phase, env.pair_counts                                                # the state the next launch continues from; successes of the last one"""
 import numpy as np
 import torch
 
@@ -262,3 +269,104 @@ class PolicyPopulation:
       h = torch.tanh(h)
     out = h.reshape(M, L, G, ACT_DIM).permute(1, 0, 2, 3).reshape(L, M * G, ACT_DIM)[:, slot]
     return out.reshape(*lead, N, ACT_DIM)
+
+
+class AgentPair:
+  """The forward and the reset (backward) agent behind struct earl_agent_pair: both `MLPPolicy`, or both `GaussianMLPPolicy`, of one architecture (dims, activations
+  and, for the Gaussian head, squash / bounds / map -- only the parameters differ).  `.params` [2, stride] float32 holds row 0 = forward, row 1 = reset in MLPPolicy's
+  packing order and is what the kernel reads: write into it in place.  switch_every: steps after which the acting agent hands over, one int for both or (forward,
+  reset); switch_on_success: also hand over after a step whose success flag is set; backward_goal: the goal row the reset agent is conditioned on -- 'initial' (the
+  env's initial state, resolved by the env at launch), None (the reset agent keeps seeing the task goal) or a 6-vector in goal-table format.
+  A second hidden layer may be at most 128 wide (EARL_PAIR_MAX_H2: two weight sets share one wave's registers); one hidden layer may have every width."""
+
+  def __init__(self, forward, backward, switch_every=200, switch_on_success=True, backward_goal='initial', device=None):
+    members = [forward, backward]
+    if not all(isinstance(m, MLPPolicy) for m in members):
+      raise ValueError('AgentPair: forward and backward are MLPPolicy / GaussianMLPPolicy')
+    template = forward
+    for p, m in enumerate(members):
+      for what in ('__class__', 'dims', 'hidden_act', 'out_act') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
+        if getattr(m, what) != getattr(template, what):
+          raise ValueError(f'AgentPair: member {p} has {what.strip("_")} = {getattr(m, what)!r}, member 0 has {getattr(template, what)!r} '
+                           '(the two agents of a pair share one architecture)')
+    if len(template.dims) == 4 and template.dims[2] > _abi.PAIR_MAX_H2:
+      raise ValueError(f'AgentPair: second hidden width {template.dims[2]} > {_abi.PAIR_MAX_H2} (EARL_PAIR_MAX_H2: two weight sets share one wave\'s registers)')
+    se = (switch_every, switch_every) if np.ndim(switch_every) == 0 else tuple(switch_every)
+    if len(se) != 2 or any(int(v) != v or int(v) < 1 for v in se):
+      raise ValueError(f'AgentPair: switch_every = {switch_every!r}: one int >= 1, or (forward, reset)')
+    self.switch_every, self.switch_on_success = (int(se[0]), int(se[1])), bool(switch_on_success)
+    if backward_goal is None or (isinstance(backward_goal, str) and backward_goal == 'initial'):
+      self.backward_goal = backward_goal
+    else:
+      g = torch.as_tensor(np.asarray(backward_goal, dtype=np.float64) if not torch.is_tensor(backward_goal) else backward_goal).detach().to('cpu', torch.float64).reshape(-1)
+      if g.numel() != 6:
+        raise ValueError(f"AgentPair: backward_goal is 'initial', None or ONE goal row of 6 values, got {g.numel()}")
+      self.backward_goal = g.clone()
+    self.template, self.gaussian = template, isinstance(template, GaussianMLPPolicy)
+    self.dims, self.hidden_act, self.out_act, self.macs = list(template.dims), template.hidden_act, template.out_act, template.macs
+    self.n_params = sum(n * (k + 1) for k, n in zip(self.dims[:-1], self.dims[1:]))
+    self.params = torch.stack([m.params.detach().to('cpu', torch.float32) for m in members]).contiguous()
+    self.to(template.device if device is None else device)
+
+  @property
+  def stride(self):
+    return int(self.params.shape[1])
+
+  def to(self, device):
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+      dev = torch.device('cuda', torch.cuda.current_device())
+    self.device = dev
+    self.params = self.params.to(dev).contiguous()
+    self._goal_dev = None if not torch.is_tensor(self.backward_goal) else self.backward_goal.to(dev).contiguous()
+    self._initial_dev = None                                         # ('initial' as numpy, its row on `dev`), filled by goal_row
+    dims = self.dims + [0] * (4 - len(self.dims))
+    self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
+                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=0, params=self.params.data_ptr())
+    return self
+
+  def head(self, sample=True, eps_out=None):
+    return self.template.head(sample=sample, eps_out=eps_out)
+
+  def goal_row(self, env):
+    """the reset agent's goal row as a float64 tensor [6] on the pair's device, or None; 'initial' is `env.initial_state`"""
+    if self.backward_goal is None:
+      return None
+    if self._goal_dev is not None:
+      return self._goal_dev
+    init = np.asarray(env.initial_state, dtype=np.float64).reshape(-1)
+    if self._initial_dev is None or not np.array_equal(self._initial_dev[0], init):      # one upload per (pair, device, initial state), not one per launch
+      self._initial_dev = (init.copy(), torch.as_tensor(init, device=self.device).contiguous())
+    return self._initial_dev[1]
+
+  def _layers_of(self, row):
+    """one row of .params -> [(W [n, k], b [n])] as views of it, in MLPPolicy's packing order"""
+    layers, at = [], 0
+    for k, n in zip(self.dims[:-1], self.dims[1:]):
+      layers.append((row[at:at + n * k].reshape(n, k), row[at + n * k:at + n * k + n]))
+      at += n * k + n
+    return layers
+
+  def agent(self, k):
+    """agent k (0 forward, 1 reset) as a policy of its own (a copy of its row of .params)"""
+    layers = [(w.cpu().clone(), b.cpu().clone()) for w, b in self._layers_of(self.params[int(k)].detach())]
+    t = self.template
+    if self.gaussian:
+      return GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, device=self.device)
+    return MLPPolicy(layers, t.hidden_act, t.out_act, device=self.device)
+
+  def __call__(self, obs, phase):
+    """obs [..., N, 12], phase [N] or [..., N] (0 forward, 1 reset) -> actions [..., N, 3] (Gaussian agents: at the mean): torch's statement -- close to the kernel,
+    not bit-identical"""
+    ph = torch.as_tensor(phase, device=obs.device).bool()
+    acts = []
+    for row in self.params.detach().to(obs.device):                  # the layers are views of .params: no copy, and in-place updates are seen
+      x = obs.to(torch.float32).reshape(-1, obs.shape[-1])
+      layers = self._layers_of(row)
+      for l, (w, b) in enumerate(layers):
+        x = torch.addmm(b, x, w.t())
+        if l + 1 < len(layers):
+          x = torch.relu(x) if self.hidden_act == 'relu' else torch.tanh(x)
+      x = x[:, :ACT_DIM]                                             # (Gaussian agents: the mean)
+      acts.append((torch.tanh(x) if self.out_act == 'tanh' else x).reshape(*obs.shape[:-1], ACT_DIM))
+    return torch.where(ph[..., None], acts[1], acts[0])

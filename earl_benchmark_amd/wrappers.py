@@ -53,6 +53,9 @@ class PersistentStateWrapper(Wrapper):
   def evaluate_policy(self, policy, T, **kwargs):
     return self.env.evaluate_policy(policy, T, **kwargs)
 
+  def rollout_agents(self, pair, T, **kwargs):
+    return self.env.rollout_agents(pair, T, **kwargs)
+
   def is_successful(self, obs=None):
     return self.env.is_successful(obs)
 
@@ -92,6 +95,10 @@ class LifelongWrapper(Wrapper):
 
   def evaluate_policy(self, policy, T, **kwargs):
     return self.env.evaluate_policy(policy, T, **kwargs)
+
+  def rollout_agents(self, pair, T, **kwargs):
+    raise ValueError('rollout_agents under a LifelongWrapper: the agent pair IS the lifelong mechanism (its forward handover makes the lifelong switch\'s goal '
+                     'draw); the wrapper\'s clock would fight the pair\'s over the same draw -- use the env without the wrapper')
 
   @property
   def lifelong_return(self):

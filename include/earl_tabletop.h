@@ -203,6 +203,52 @@ int earl_tabletop_population_rollout(const earl_tabletop_cfg* cfg, const earl_ta
                                      const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
                                      const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary, earl_stream_t stream);
 
+/* ---- closed loop for the AGENT PAIR of autonomous RL: a forward and a reset agent alternating inside one rollout ----
+ * EARL's training stream is non-episodic: a forward agent works on the task goal, a reset (backward) agent brings the env back towards the initial state, and
+ * they hand the env to each other after a fixed number of steps or as soon as the acting agent has succeeded.  Both agents share one earl_mlp_policy (dims,
+ * activations) and one earl_gaussian_head; only the parameters differ: policy->params is [2, param_stride], row 0 the forward agent, row 1 the reset agent. */
+typedef struct earl_agent_pair {
+  int32_t switch_every[2];     /* steps after which agent 0 (forward) / agent 1 (reset) hands over; each >= 1 */
+  int32_t switch_on_success;   /* 1 = also hand over after a step whose success flag is set; 0 = the clocks only */
+  int32_t pad_;                /* unused (keeps param_stride 8-byte aligned in every compiler's layout) */
+  int64_t param_stride;        /* floats between the two rows of policy->params; >= the parameter count of one policy */
+  const double* backward_goal; /* NULL, or ONE goal row (6 doubles, goal-table format) the reset agent is conditioned on */
+  int8_t*  phase;              /* [n] caller-owned state: 0 forward, 1 reset */
+  int32_t* steps_in_phase;     /* [n] caller-owned state: steps the env has spent in its phase */
+  int8_t*  agent_out;          /* NULL or [episodes, T, n]: the agent that computed the action of step t */
+  int32_t* forward_success;    /* NULL or [episodes, n]: forward phases of the episode that ended by success */
+  int32_t* backward_success;   /* NULL or [episodes, n]: reset phases of the episode that ended by success */
+} earl_agent_pair;
+
+/* earl_tabletop_policy_rollout (head == NULL: policy->dims[n_layers] == 3) or earl_tabletop_policy_rollout_gaussian (head != NULL: == 6) with two agents.
+ * Per env and step, in this order (the order is the contract; libearl_host.so states it as plain loops and the device agrees bit for bit under the sparse reward):
+ *   1. the action is computed from the current observation by the network of the env's current `phase`: the same k-ascending fmaf chain, tanh_f32 and head
+ *      as the single-policy entry points;
+ *   2. with a head, the step's one Philox draw is the one earl_tabletop_policy_rollout_gaussian makes (seed, global env id, counter): it does not depend on
+ *      the phase;
+ *   3. agent_out and act_out are written;
+ *   4. the wrapped env step runs; reward and success refer to the goal in force during the step;
+ *   5. if the step auto-reset the env (cfg->auto_reset): phase = 0, steps_in_phase = 0, nothing else; the next action is computed from the observation the
+ *      single-policy entry points hand on;
+ *   6. otherwise steps_in_phase += 1, and the env hands over if (switch_on_success && success) || steps_in_phase >= switch_every[phase]:
+ *      phase ^= 1, steps_in_phase = 0; forward_success / backward_success of the phase that ended is incremented if switch_on_success && success (a step
+ *      where the clock ran out as well counts as ended by success).  Entering the reset phase with backward_goal != NULL, the goal in force becomes that
+ *      row; state.goal_idx is NOT changed -- the env's stored goal stays a task goal, and every other entry point keeps working on the state a pair launch
+ *      leaves behind.  Entering the forward phase, goal_idx = the draw the lifelong switch makes (Philox counter of this step, draw 0) and the goal in force
+ *      becomes that table row.  The observation's goal slots are re-read with the goal in force, and the out->obs row carries them.
+ * Launch entry: an env in the reset phase with backward_goal != NULL starts from that row, not from goal_table[goal_idx].  reset_first = 1 sets phase = 0,
+ * steps_in_phase = 0 at each episode's reset.  Launch exit: phase, steps_in_phase and goal_idx are stored.
+ * Never switching (switch_every > T, switch_on_success = 0, all envs in phase 0) the launch is bit-identical to the single-policy entry point of the same
+ * head on row 0.  Everything else as those entry points: reset_first / episodes rules, NULL-able outputs / act_out / eps_out, Philox counter use
+ * episodes * (T + 1) resp. T, argument errors before any HIP call -- to which it adds: NULL pair / phase / steps_in_phase, switch_every[k] < 1,
+ * switch_on_success not 0 or 1, param_stride below the parameter count, cfg->goal_change_frequency > 0 (the pair IS the lifelong mechanism: the two clocks
+ * would fight over the same draw), and a second hidden layer wider than EARL_PAIR_MAX_H2 (two weight sets share the registers of one wave per SIMD; one
+ * hidden layer may have every legal width).  Single-object env only. */
+#define EARL_PAIR_MAX_H2 128
+int earl_tabletop_pair_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair,
+                               const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out,
+                               earl_stream_t stream);
+
 /* PersistentStateWrapper.reset() + TabletopManipulation.reset() for the envs with mask[i] != 0
  * (mask == NULL: all).  Replaces wrappers/persistent_state_wrapper.py:17-20 and
  * envs/tabletop_manipulation.py:105-126 (incl. is_valid_init :89-97, get_next_goal :62-76).
@@ -260,6 +306,9 @@ int earl_tabletop_policy_rollout_gaussian_cpu(const earl_tabletop_cfg* cfg, cons
 int earl_tabletop_population_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
                                          const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
                                          const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary);
+/* host twin of earl_tabletop_pair_rollout: the plain loops of its contract, one env at a time; every pointer of `pair` is a HOST pointer; refuses the same shapes */
+int earl_tabletop_pair_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair,
+                                   const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out);
 int earl_tabletop_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, const int32_t* next_goal_idx, float* obs);
 int earl_tabletop_observe_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_tabletop_out* out);
 int earl_tabletop_reward_cpu(int32_t n, const float* obs, int32_t reward_type, int32_t wide_init, float* reward, uint8_t* success);

@@ -1,5 +1,5 @@
 #!/bin/bash
-# build tools/ubench/libearl_policy_stamped.so = the shipped library with tabletop_policy.hip and tabletop_policy_gaussian.hip recompiled under
+# build tools/ubench/libearl_policy_stamped.so = the shipped library with tabletop_policy.hip, tabletop_policy_gaussian.hip and tabletop_policy_pair.hip recompiled under
 # -DEARL_POLICY_STAMPS (per-phase s_memtime stamps of the closed-loop policy kernel, csrc/tabletop_policy.h; read by tools/prof_policy.py, each unit through
 # its own reader).  Needs the shipped objects (make -C earl_benchmark_amd/csrc).
 set -e
@@ -8,6 +8,7 @@ FLAGS="-DEARL_POLICY_STAMPS --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=o
 mkdir -p ../../tools/ubench
 /opt/rocm/bin/hipcc $FLAGS -c -o ../../tools/ubench/tabletop_policy_stamped.o tabletop_policy.hip
 /opt/rocm/bin/hipcc $FLAGS -c -o ../../tools/ubench/tabletop_policy_gaussian_stamped.o tabletop_policy_gaussian.hip
-/opt/rocm/bin/hipcc $FLAGS -shared -o ../../tools/ubench/libearl_policy_stamped.so ../../tools/ubench/tabletop_policy_stamped.o ../../tools/ubench/tabletop_policy_gaussian_stamped.o tabletop_policy_population.o tabletop.o glue.o physics.o physics_w8.o physics_mt.o physics_l64.o physics_kitchen.o
-rm -f ../../tools/ubench/tabletop_policy_stamped.o ../../tools/ubench/tabletop_policy_gaussian_stamped.o
+/opt/rocm/bin/hipcc $FLAGS -c -o ../../tools/ubench/tabletop_policy_pair_stamped.o tabletop_policy_pair.hip
+/opt/rocm/bin/hipcc $FLAGS -shared -o ../../tools/ubench/libearl_policy_stamped.so ../../tools/ubench/tabletop_policy_stamped.o ../../tools/ubench/tabletop_policy_gaussian_stamped.o ../../tools/ubench/tabletop_policy_pair_stamped.o tabletop_policy_population.o tabletop.o glue.o physics.o physics_w8.o physics_mt.o physics_l64.o physics_kitchen.o
+rm -f ../../tools/ubench/tabletop_policy_stamped.o ../../tools/ubench/tabletop_policy_gaussian_stamped.o ../../tools/ubench/tabletop_policy_pair_stamped.o
 echo built libearl_policy_stamped.so

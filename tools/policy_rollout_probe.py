@@ -21,7 +21,18 @@ and writes profiles/policy_gaussian_probe.json: (c') over (b') is the bar (>= 1)
   (s) the same launch with summaries only                                    -- env.evaluate_policy(PolicyPopulation, T, episodes=E)
   (u) what a user could do before: P launches of the single-policy entry point on 16-env shards, one stream
 and writes profiles/policy_population_probe.json.  The bar: (p) no slower than (c) beyond max(5 %, 3 x the round-to-round spread of (c) in this run), the
-spread being (max - min) / median of (c)'s rounds; (s) is reported against (p) and (u) as the baseline, neither with a bar."""
+spread being (max - min) / median of (c)'s rounds; (s) is reported against (p) and (u) as the baseline, neither with a bar.
+
+--pair: the forward / reset agent pair alternating inside one launch (earl_tabletop_pair_rollout), same method, continuing form, switch_every = (25, 25), for
+12 -> 64 -> 3 and 12 -> 256 -> 128 -> 3 (the widest two-hidden-layer shape a pair takes):
+  (c) the unchanged single-policy entry point, T steps                        -- env.rollout_policy(forward, T, reset_first=False)
+  (u) today's way for clock-only switching: T / 25 alternating 25-step single-policy launches, the goal installed by torch ops in between
+  (k) the pair launch, switch_on_success = 0 (every workgroup uniform)        -- env.rollout_agents(pair, T)
+  (m) the pair launch, switch_on_success = 1, on an input with mixed workgroups (envs reset at their goals, random starting phases); reports the mixed share
+  (b) today's only way to switch on success: the captured per-step loop with both actors in torch and torch.where on the phase
+and writes profiles/policy_pair_probe.json.  The bars, each against code that existed before the pair: (k) no slower than (u), (m) no slower than (b), beyond
+max(5 %, 3 x the spread of (u) resp. (b)); (k) / (c) (the price of the ballot and the second weight set) and (m) / (k) (the price of evaluating both networks)
+are reported without a bar."""
 import argparse
 import json
 import os
@@ -34,7 +45,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import earl_benchmark_amd as eb  # noqa: E402
-from earl_benchmark_amd.policy import GaussianMLPPolicy, MLPPolicy, PolicyPopulation  # noqa: E402
+from earl_benchmark_amd.policy import AgentPair, GaussianMLPPolicy, MLPPolicy, PolicyPopulation  # noqa: E402
 
 FP32_PEAK = 157.3e12      # MI355X dense fp32 FLOP/s (vector = f32-input MFMA rate)
 
@@ -158,6 +169,110 @@ def population_main(args):
   print('wrote', args.out)
 
 
+def pair_main(args):
+  n, T, dev, se = args.n, args.steps, 'cuda:0', 25
+  assert T % (2 * se) == 0, '--steps a multiple of 50: whole forward + reset periods'
+  result = {'n': n, 'T': T, 'switch_every': [se, se], 'rounds': args.rounds, 'form': 'continuing (reset_first = 0)', 'device': torch.cuda.get_device_name(0), 'shapes': {}}
+  for name, hidden in (('12-64-3', (64,)), ('12-256-128-3', (256, 128))):
+    agents = [random_policy(hidden, 1 + k, dev) for k in range(2)]
+    pair_k = AgentPair(agents[0], agents[1], switch_every=se, switch_on_success=False, backward_goal='initial', device=dev)
+    pair_m = AgentPair(agents[0], agents[1], switch_every=se, switch_on_success=True, backward_goal='initial', device=dev)
+
+    def make_env(at_goal=False):
+      env, _ = eb.EARLEnvs('tabletop_manipulation', reward_type='sparse', reset_train_env_at_goal=at_goal, wide_init_distr=at_goal, num_envs=n, device=dev, seed=5,
+                           train_horizon=2**31 - 1).get_envs()
+      return env
+    env_c, env_u, env_k, env_m, env_b = make_env(), make_env(), make_env(), make_env(True), make_env(True)
+    gen = torch.Generator(device=dev).manual_seed(7)
+
+    # (u): the reset agent's goal as one more row of the goal table, goal_idx pointed at it / at a fresh task row by torch ops between the launches
+    uu = env_u.unwrapped
+    uu.goal_table = torch.cat([uu.goal_table, torch.as_tensor(uu.initial_state, dtype=torch.float64, device=dev)[None]], 0).contiguous()
+    uu._sync_state_ptrs()
+    row = uu.goal_table.shape[0] - 1
+
+    def alternating_launches():
+      for chunk in range(T // se):
+        k = chunk & 1
+        env_u.rollout_policy(agents[k], se, reset_first=False)
+        if k == 0:
+          uu.goal_idx.fill_(row)
+        else:
+          uu.goal_idx.copy_(torch.randint(0, 4, (n,), device=dev, generator=gen).to(torch.int32))
+
+    # (m): random starting phases and clocks on envs that sit at their goals -> success and clock handovers at different steps inside one workgroup
+    um = env_m.unwrapped
+    env_m.rollout_agents(pair_m, 1)
+    um.agent_phase.copy_(torch.randint(0, 2, (n,), device=dev, generator=gen).to(torch.int8))
+    um.steps_in_phase.copy_(torch.randint(0, se, (n,), device=dev, generator=gen).to(torch.int32))
+    last = {}
+
+    def mixed_launch():
+      last['agent'] = env_m.rollout_agents(pair_m, T)[5]
+
+    # (b): the captured per-step loop; the phase state, the handover rule and the goal install are torch ops beside the two actors
+    ub = env_b.unwrapped
+    ub.goal_table = torch.cat([ub.goal_table, torch.as_tensor(ub.initial_state, dtype=torch.float64, device=dev)[None]], 0).contiguous()
+    ub._sync_state_ptrs()
+    phase = torch.randint(0, 2, (n,), device=dev, generator=gen).bool()
+    sip = torch.randint(0, se, (n,), device=dev, generator=gen).to(torch.int32)
+    task = ub.goal_idx.clone()
+    draws, at = torch.randint(0, 4, (T + 1, n), device=dev, generator=gen).to(torch.int32), [0]
+
+    def both_actors(obs):
+      succ = (obs[:, 2:4] - obs[:, 8:10]).square().sum(1).sqrt() <= 0.2            # the success flag of the step that produced obs (wide_init: the mug only)
+      sip.add_(1)
+      over = succ | (sip >= se)
+      to_forward = over & phase
+      task.copy_(torch.where(to_forward, draws[at[0] % (T + 1)], task))
+      at[0] += 1
+      phase.logical_xor_(over)
+      sip.mul_(~over)
+      ub.goal_idx.copy_(torch.where(phase, torch.full_like(task, ub.goal_table.shape[0] - 1), task))
+      return torch.where(phase[:, None], agents[1](obs), agents[0](obs))
+    g_b = env_b.make_step_graph(T, policy=both_actors)
+
+    legs = {'c_single_policy_fused_launch': lambda: env_c.rollout_policy(agents[0], T, reset_first=False), 'u_alternating_25_step_launches': alternating_launches,
+            'k_pair_launch_clock_only': lambda: env_k.rollout_agents(pair_k, T), 'm_pair_launch_switch_on_success_mixed': mixed_launch,
+            'b_captured_loop_both_actors_torch_where': g_b.replay}
+    for fn in legs.values():             # warm-up
+      fn()
+      fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in legs}
+    for _ in range(args.rounds):         # interleaved rounds in one process
+      for k, fn in legs.items():
+        times[k].append(timed(fn))
+    steps = n * T
+    shape = {'macs_per_env_step': agents[0].macs}
+    for k in legs:
+      med, best = statistics.median(times[k]), min(times[k])
+      shape[k] = {'env_steps_per_s_median': steps / med, 'env_steps_per_s_best': steps / best, 'seconds_median': med, 'seconds_rounds': times[k], 'us_per_step_median': med / T * 1e6,
+                  'spread': (max(times[k]) - min(times[k])) / med}
+    sec = lambda k: shape[k]['seconds_median']
+    a = last['agent'].reshape(T, n // 16, 16) if n % 16 == 0 else last['agent'][:, :n // 16 * 16].reshape(T, n // 16, 16)
+    any1, any0 = (a == 1).any(-1), (a == 0).any(-1)
+    shape['m_share_of_workgroup_steps'] = {'mixed': float((any1 & any0).float().mean()), 'uniform_forward': float((any0 & ~any1).float().mean()),
+                                           'uniform_reset': float((any1 & ~any0).float().mean())}
+    ak = env_k.rollout_agents(pair_k, T)[5].reshape(T, -1)
+    shape['k_share_of_workgroup_steps_mixed'] = float(((ak == 1).any(-1) & (ak == 0).any(-1)).float().mean())      # (over the whole batch: 0 = every workgroup uniform)
+    for leg, base in (('k_pair_launch_clock_only', 'u_alternating_25_step_launches'), ('m_pair_launch_switch_on_success_mixed', 'b_captured_loop_both_actors_torch_where')):
+      tag = leg[0] + '_over_' + base[0]
+      shape[f'margin_of_{base[0]}'] = max(0.05, 3 * shape[base]['spread'])
+      shape[tag + '_seconds'] = sec(leg) / sec(base)
+      shape[tag + '_within_margin'] = shape[tag + '_seconds'] <= 1 + shape[f'margin_of_{base[0]}']
+    shape['k_over_c_seconds'] = sec('k_pair_launch_clock_only') / sec('c_single_policy_fused_launch')
+    shape['k_within_margin_of_c'] = shape['k_over_c_seconds'] <= 1 + max(0.05, 3 * shape['c_single_policy_fused_launch']['spread'])
+    shape['m_over_k_seconds'] = sec('m_pair_launch_switch_on_success_mixed') / sec('k_pair_launch_clock_only')
+    result['shapes'][name] = shape
+    print(name, json.dumps(shape))
+  os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+  with open(args.out, 'w') as f:
+    json.dump(result, f, indent=1)
+    f.write('\n')
+  print('wrote', args.out)
+
+
 def timed(fn):
   a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
   a.record()
@@ -172,17 +287,20 @@ def main():
   ap.add_argument('--out', default=None)
   ap.add_argument('--gaussian', action='store_true', help="the stochastic legs (b'), (c), (c') -> profiles/policy_gaussian_probe.json")
   ap.add_argument('--population', action='store_true', help='the population legs (c), (p), (s), (u) -> profiles/policy_population_probe.json')
+  ap.add_argument('--pair', action='store_true', help='the agent-pair legs (c), (u), (k), (m), (b) -> profiles/policy_pair_probe.json')
   ap.add_argument('--n', type=int, default=4096)
   ap.add_argument('--steps', type=int, default=200)
   ap.add_argument('--episodes', type=int, default=4)
   ap.add_argument('--rounds', type=int, default=9)
   args = ap.parse_args()
   args.out = args.out or os.path.join(REPO, 'profiles', 'policy_gaussian_probe.json' if args.gaussian else
-                                      'policy_population_probe.json' if args.population else 'policy_rollout_probe.json')
+                                      'policy_population_probe.json' if args.population else 'policy_pair_probe.json' if args.pair else 'policy_rollout_probe.json')
   if args.gaussian:
     return gaussian_main(args)
   if args.population:
     return population_main(args)
+  if args.pair:
+    return pair_main(args)
   n, T, E, dev = args.n, args.steps, args.episodes, 'cuda:0'
   result = {'n': n, 'T': T, 'episodes': E, 'rounds': args.rounds, 'device': torch.cuda.get_device_name(0), 'fp32_peak_flops': FP32_PEAK, 'shapes': {}}
   for name, hidden in (('12-64-3', (64,)), ('12-256-256-3', (256, 256))):

@@ -194,6 +194,9 @@ SIGNATURES = {
     'earl_kitchen_rollout_clocked': [C.c_void_p, C.c_void_p, _P(KitchenParams), _P(KitchenCfg), _P(KitchenState), C.c_void_p, C.c_int32, C.c_void_p, _P(KitchenOut),
                                      C.c_void_p],
     'earl_minitaur_rollout_clocked': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_int32, C.c_void_p, _P(MinitaurOut), C.c_void_p],
+    # the closed loop inside the Sawyer rollout kernel: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
+    'earl_sawyer_policy_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p,
+                                   C.c_void_p, _P(SawyerOut), C.c_void_p],
     'earl_minitaur_reset': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_minitaur_cfg_size': [],
     'earl_debug_set_minitaur_stepper': [C.c_int],
@@ -244,6 +247,14 @@ def load():
 HOST_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'libearl_host.so')
 HOST_SIGNATURES = {name + '_cpu': argtypes[:-1] for name, argtypes in SIGNATURES.items()
                    if name.startswith(('earl_tabletop_', 'earl_tabletop3_'))}            # same arguments minus the stream
+# what libearl_host.so exports besides the tabletop's `_cpu` twins (include/earl_physics.h): the policy contract on the host -- the oracle of the in-kernel policies'
+# actions, no twin of a device entry point -- and the contract's scalar functions; name -> (argtypes, restype)
+HOST_EXTRA_SIGNATURES = {
+    'earl_mlp_policy_forward_cpu': ([_P(MlpPolicy), _P(GaussianHead), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
+    'earl_tanh_f32': ([C.c_float], C.c_float),
+    'earl_exp_f32': ([C.c_float], C.c_float),
+    'earl_normal_quantile_f32': ([C.c_uint32], C.c_float),
+}
 _host = None
 
 
@@ -258,6 +269,10 @@ class HostLib:
       fn.argtypes, fn.restype = argtypes, C.c_int
       setattr(self, name, fn)
       setattr(self, name[:-4], (lambda f: (lambda *a: f(*a[:-1])))(fn))
+    for name, (argtypes, restype) in HOST_EXTRA_SIGNATURES.items():
+      fn = getattr(cdll, name)
+      fn.argtypes, fn.restype = argtypes, restype
+      setattr(self, name, fn)
     cdll.earl_host_last_error.restype = C.c_char_p
     cdll.earl_host_version.restype = C.c_char_p
     cdll.earl_host_set_threads.argtypes = [C.c_int]

@@ -2,6 +2,7 @@
 // stepper's own entry points earl_physics_step / _forward (nv = 23 forwarded to physics_kitchen.hip, 64 lanes per env to physics_l64.hip), the Sawyer env's
 // entry points (the door's eight-wave rollout forwarded to physics_w8.hip), the collision-table cone cache of all units, and the size queries and debug switches.
 #include "physics_stepper.h"
+#include "policy_math.h"
 
 #include <mutex>
 #include <unordered_map>
@@ -152,6 +153,56 @@ int earl_sawyer_rollout_clocked(const earl_link_model* model, const earl_collisi
 int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                         const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream) {
   return earl_sawyer_rollout_clocked(model, col, nv, cfg, st, action, T, nullptr, out, stream);
+}
+
+// include/earl_physics.h: T closed-loop env steps in one launch of the rollout kernel, the policy evaluated by the wave that owns the env.  The launch forms are
+// earl_sawyer_rollout's (door: four one-wave workgroups per CU, eight waves per CU above 4096 envs; peg: whole rollouts or the time-sliced queue); the 64-lane
+// measurement builds (earl_debug_set_physics_lanes(64)) and the door's time-sliced measurement variant have no policy form
+int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
+                               const earl_sawyer_out* out, earl_stream_t stream) {
+  if (!model || !cfg || !st || !out || !policy || !obs0 || !actions || T < 1 || cfg->n < 0) return EARL_ERR_ARG;
+  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !out->obs) return EARL_ERR_ARG;
+  if (nv != 10 && nv != 15) return EARL_ERR_ARG;
+  if (!policy->params || ((uintptr_t)policy->params & 15) || policy->precision != 0) return EARL_ERR_ARG;      // (16-byte loads of the weight rows)
+  if (policy->n_layers != 2 && policy->n_layers != 3) return EARL_ERR_ARG;
+  if (policy->dims[0] != 14 || policy->dims[policy->n_layers] != (head ? 8 : 4)) return EARL_ERR_ARG;
+  for (int l = 1; l < policy->n_layers; ++l)
+    if (policy->dims[l] < 16 || policy->dims[l] > earl::kPolicyMaxWidth || policy->dims[l] % 16) return EARL_ERR_ARG;
+  if (policy->n_layers == 2 && policy->dims[3] != 0) return EARL_ERR_ARG;
+  if (policy->hidden_act != EARL_ACT_RELU && policy->hidden_act != EARL_ACT_TANH) return EARL_ERR_ARG;
+  if (policy->out_act != EARL_ACT_NONE && policy->out_act != EARL_ACT_TANH) return EARL_ERR_ARG;
+  if (head) {
+    if (head->mode != EARL_HEAD_MEAN && head->mode != EARL_HEAD_SAMPLE) return EARL_ERR_ARG;
+    if (head->log_std_map != EARL_LOGSTD_CLAMP && head->log_std_map != EARL_LOGSTD_TANH) return EARL_ERR_ARG;
+    if (!(head->log_std_min >= -20.0f && head->log_std_max <= 4.0f && head->log_std_min <= head->log_std_max)) return EARL_ERR_ARG;      // (NaN fails every comparison)
+  }
+  if (cfg->frame_skip < 0 || cfg->att_hand < 0 || cfg->att_right < 0 || cfg->att_left < 0 || cfg->att_obj < 0) return EARL_ERR_ARG;
+  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;
+  if (cfg->n_goal_rows > 0 && !cfg->goal_table) return EARL_ERR_ARG;
+  if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && (!st->obj_init || cfg->att_grasp < 0 || cfg->att_lpad < 0 || cfg->att_rpad < 0)) return EARL_ERR_ARG;
+  if (nv == 15 && cfg->obj_kind >= 1 && out->info && !st->obj_init) return EARL_ERR_ARG;
+  if (g_lpe == 64) return EARL_ERR_ARG;                   // (the 64-lane measurement builds: no policy form)
+  if (cfg->n == 0) return EARL_OK;
+  if (int rc = check_cone(col, true, (hipStream_t)stream, "sawyer_policy_rollout")) return rc;
+  SawyerPolicyArgs a;
+  static_cast<SawyerArgs&>(a) = SawyerArgs{model, col, *cfg, *st, nullptr, T, *out, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
+  a.pol = *policy;
+  a.head = head ? *head : earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr};
+  a.gauss = head ? 1 : 0;
+  a.obs0 = obs0;
+  a.act_out = actions;
+  if (nv == 10) {
+    if (g_door_variant == 2 || (g_door_variant != 1 && cfg->n > 4096)) return earl_unit_w8_sawyer_policy_rollout(&a, stream);
+    sawyer_policy_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
+  } else {
+    const int cus = cu_count();
+    if (st->sched && g_peg_sliced && grid_for<15, 16>(cfg->n) > cus && T > 1) {
+      a.slice = g_peg_sliced >= 2 ? g_peg_sliced : EARL_PEG_SLICE;
+      sawyer_policy_rollout_kernel<15, 16, true><<<cus, block_for<15>(), 0, (hipStream_t)stream>>>(a);
+    } else sawyer_policy_rollout_kernel<15, 16><<<grid_for<15, 16>(cfg->n), block_for<15>(), 0, (hipStream_t)stream>>>(a);
+  }
+  return launched("sawyer_policy_rollout");
 }
 
 int earl_sawyer_reset(const earl_link_model* model, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,

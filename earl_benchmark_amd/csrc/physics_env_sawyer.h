@@ -15,6 +15,14 @@ struct SawyerArgs {
   int slice;                     // SLICED rollout: env steps per work item (0: one item = the whole rollout of a group)
   const uint64_t* clock;         // earl_sawyer_rollout_clocked: DEVICE words added to cfg.counter / cfg.step_counter (NULL = zero); [1] is read where a goal-switch draw is made
 };
+// earl_sawyer_policy_rollout: the rollout's arguments (action unused) plus the policy.  A struct of its own so that the plain kernels' argument stays what it was
+struct SawyerPolicyArgs : SawyerArgs {
+  earl_mlp_policy pol;           // dims[0] = 14, dims[n_layers] = 4 (8 with the head)
+  earl_gaussian_head head;       // read when gauss != 0
+  int gauss;
+  const double* obs0;            // [n, 14]: what the policy sees at step 0
+  float* act_out;                // [T, n, 4]: the actions as the policy produced them (the open-loop entry points fed with it walk through the same bits)
+};
 
 // Work queue of the time-sliced rollout (earl_sawyer_state.sched: progress[G] then lock[G], zero on entry).  An env group's state is in HBM after every env
 // step (the failure guard's "last stable state"), so ANY wave can take the group's next slice of env steps; a wave claims the unlocked group that has come
@@ -221,6 +229,144 @@ __device__ __forceinline__ void sawyer_emit(Shared<NV>& s, const typename ModelO
   fence();
 }
 
+
+// ------------------------------------------------------------------------------------------------ the policy phase of sawyer_policy_rollout_kernel
+// A float32 MLP 14 -> H1 (-> H2) -> 4 | 8 evaluated by the 16 lanes of an env between two env steps, under the contract of policy_math.h / tabletop_policy.h:
+// acc = b_j; for k ascending: acc = fmaf(x_k, W_jk, acc).  No LDS (the stepper's workgroups leave none): a layer's activations live in registers, element k on
+// lane k & 15 of the env's group in register k >> 4, and x_k reaches the group's other lanes by a width-16 __shfl (ds_bpermute_b32: the LDS crossbar, no allocation).
+// Lane `sub` owns outputs j = 16 i + sub.  One pass of pol_layer's outer loop carries FOUR of them (i = 4 g .. 4 g + 3): four independent fmaf chains per lane share
+// every x_k, so a shuffle feeds four multiply-adds and the chains hide one another's latency.  Weights come from global memory (params is [N][K] row-major, as
+// torch.nn.Linear.weight): a lane walks its own rows in 16-byte pieces, so every cache line it touches is used whole over consecutive loads, and the four env
+// groups of a wave read the same addresses (one fetch serves them).  The network sits in L2 (14 -> 256 -> 256 -> 4: 280 KB).
+// Register arrays are indexed by constants only: instead of indexing by the (runtime) k-tile / output-group number the arrays are rotated by one tile per iteration.
+template <bool VEC>
+__device__ __forceinline__ void pol_layer(const float* __restrict__ W, const float* __restrict__ B, const int K, const int N, const int kind, const int sub,
+                                          float (&h)[16]) {
+#pragma clang fp contract(off)
+  float out[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) out[i] = 0.f;
+  const int nt = (N + 15) >> 4, nk = (K + 15) >> 4;
+#pragma unroll 1
+  for (int g = 0; g < 4; ++g) {
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
+    if (4 * g < nt) {                                   // (wave-uniform)
+      // rows past the layer's last one (a width that is not a multiple of 64; the 4- or 8-wide output layer) are clamped: computed on row N - 1 and never read
+      const int j0 = min(64 * g + sub, N - 1), j1 = min(64 * g + 16 + sub, N - 1), j2 = min(64 * g + 32 + sub, N - 1), j3 = min(64 * g + 48 + sub, N - 1);
+      const float* __restrict__ w0 = W + (size_t)j0 * K;
+      const float* __restrict__ w1 = W + (size_t)j1 * K;
+      const float* __restrict__ w2 = W + (size_t)j2 * K;
+      const float* __restrict__ w3 = W + (size_t)j3 * K;
+      r0 = B[j0]; r1 = B[j1]; r2 = B[j2]; r3 = B[j3];
+      float cur[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) cur[i] = h[i];
+#pragma unroll 1
+      for (int kt = 0; kt < nk; ++kt) {
+        const float x = cur[0];
+        if constexpr (VEC) {                            // K a multiple of 16, rows 16-byte aligned
+#pragma unroll
+          for (int kk = 0; kk < 16; kk += 4) {
+            const float4 v0 = *reinterpret_cast<const float4*>(w0 + 16 * kt + kk), v1 = *reinterpret_cast<const float4*>(w1 + 16 * kt + kk);
+            const float4 v2 = *reinterpret_cast<const float4*>(w2 + 16 * kt + kk), v3 = *reinterpret_cast<const float4*>(w3 + 16 * kt + kk);
+            const float x0 = __shfl(x, kk, 16), x1 = __shfl(x, kk + 1, 16), x2 = __shfl(x, kk + 2, 16), x3 = __shfl(x, kk + 3, 16);
+            r0 = __builtin_fmaf(x0, v0.x, r0); r1 = __builtin_fmaf(x0, v1.x, r1); r2 = __builtin_fmaf(x0, v2.x, r2); r3 = __builtin_fmaf(x0, v3.x, r3);
+            r0 = __builtin_fmaf(x1, v0.y, r0); r1 = __builtin_fmaf(x1, v1.y, r1); r2 = __builtin_fmaf(x1, v2.y, r2); r3 = __builtin_fmaf(x1, v3.y, r3);
+            r0 = __builtin_fmaf(x2, v0.z, r0); r1 = __builtin_fmaf(x2, v1.z, r1); r2 = __builtin_fmaf(x2, v2.z, r2); r3 = __builtin_fmaf(x2, v3.z, r3);
+            r0 = __builtin_fmaf(x3, v0.w, r0); r1 = __builtin_fmaf(x3, v1.w, r1); r2 = __builtin_fmaf(x3, v2.w, r2); r3 = __builtin_fmaf(x3, v3.w, r3);
+          }
+        } else {                                        // the input layer: K = 14, rows 56 bytes apart
+#pragma unroll
+          for (int kk = 0; kk < 16; ++kk) {
+            const int k = 16 * kt + kk;
+            if (k < K) {                                // (wave-uniform)
+              const float xk = __shfl(x, kk, 16);
+              r0 = __builtin_fmaf(xk, w0[k], r0); r1 = __builtin_fmaf(xk, w1[k], r1); r2 = __builtin_fmaf(xk, w2[k], r2); r3 = __builtin_fmaf(xk, w3[k], r3);
+            }
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 15; ++i) cur[i] = cur[i + 1];
+      }
+      r0 = earl::policy_act(r0, kind); r1 = earl::policy_act(r1, kind); r2 = earl::policy_act(r2, kind); r3 = earl::policy_act(r3, kind);
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) out[i] = out[i + 4];   // after the four passes group g's results stand at out[4 g .. 4 g + 3]
+    out[12] = r0; out[13] = r1; out[14] = r2; out[15] = r3;
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) h[i] = out[i];
+}
+
+// the action of env step t of one env, on all 16 lanes of its group: observation (element `sub` on lane `sub`, 0 beyond 13) -> MLP -> head -> float4.
+// `row` = t n + env; a group that is not live computes on zeros and writes nothing.
+// The policy's kernel arguments are read HERE, through the kernel-argument pointer the caller passed through an empty asm (the register-pinning recipe of DESIGN 2, on
+// scalar registers): read as `a.pol...` they are loaded once at kernel entry and held in some twenty scalar registers across the whole env-step loop -- through substep, where the
+// scalar file is full already; the extra scalar spills took vector registers away and the stepper's own constants went to scratch, reloaded inside the timestep loop.
+#define EARL_KARG __attribute__((address_space(4)))
+__device__ __noinline__ float4 sawyer_policy_action(const uint64_t ka_bits, const uint64_t ev, const uint32_t gid, const uint64_t seed, const double* __restrict__ seen, const int env,
+                                                       const size_t row, const int sub, const bool live) {
+#pragma clang fp contract(off)
+  // (`ka_bits`: the kernel's own kernel-argument pointer, handed over by the caller -- inside a called function __builtin_amdgcn_kernarg_segment_ptr() is null -- and
+  // made wave-uniform again, so that the reads below are scalar loads)
+  const EARL_KARG SawyerPolicyArgs* ka = (const EARL_KARG SawyerPolicyArgs*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ka_bits >> 32)) << 32) |
+                                                                            (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ka_bits));
+  const int n_layers = ka->pol.n_layers, d0 = ka->pol.dims[0], d1 = ka->pol.dims[1], d2 = ka->pol.dims[2], d3 = ka->pol.dims[3];
+  const int hidden_act = ka->pol.hidden_act, out_act = ka->pol.out_act;
+  if (!seen) seen = ka->obs0 + (size_t)env * 14;       // step 0
+  float h[16];
+  h[0] = (sub < 14 && live) ? (float)seen[sub] : 0.f;
+#pragma unroll
+  for (int i = 1; i < 16; ++i) h[i] = 0.f;
+  const float* w = ka->pol.params;
+  pol_layer<false>(w, w + (size_t)d1 * d0, d0, d1, hidden_act, sub, h);
+  w += (size_t)d1 * (d0 + 1);
+  if (n_layers == 3) {
+    pol_layer<true>(w, w + (size_t)d2 * d1, d1, d2, hidden_act, sub, h);
+    w += (size_t)d2 * (d1 + 1);
+  }
+  const int KL = n_layers == 3 ? d2 : d1, NL = n_layers == 3 ? d3 : d2;
+  pol_layer<true>(w, w + (size_t)NL * KL, KL, NL, EARL_ACT_NONE, sub, h);       // lane j < NL holds output j
+  float u;
+  if (ka->gauss) {
+    // lanes 0..3 are the head's four dimensions: mean on the lane itself, raw log_std four lanes up
+    const float raw = __shfl(h[0], (sub & 3) + 4, 16);
+    // ONE Philox block per (env, env step), keyed like the goal-switch draw of the same step: ev = the host's step counter plus the clock word of a graph-captured
+    // launch, plus t.  The draw index earl::kGaussDraw = 0x504F4C00 keeps the stream disjoint from every other draw made with these counter words: the reset's
+    // (indices 0 .. 31, 0xFFF0 .. 0xFFF2, 0xFFFF) and the goal switch's (0xFFFE).  Words x, y, z, w serve action dimensions 0 .. 3.
+    const earl::U4 b = earl::philox4x32_10(earl::U4{earl::kGaussDraw, gid, (uint32_t)ev, (uint32_t)(ev >> 32)}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const int d = sub & 3;
+    const float eps = earl::normal_quantile_f32((d == 0 ? b.x : (d == 1 ? b.y : (d == 2 ? b.z : b.w))) >> 8);
+    u = earl::gaussian_head_action(earl_gaussian_head{ka->head.mode, ka->head.log_std_map, ka->head.log_std_min, ka->head.log_std_max, nullptr}, out_act, h[0], raw, eps);
+    float* eps_out = ka->head.eps_out;
+    if (sub < 4 && live && eps_out) eps_out[row * 4 + sub] = eps;
+  } else {
+    u = earl::policy_act(h[0], out_act);
+  }
+  float* act_out = ka->act_out;
+  if (sub < 4 && live) act_out[row * 4 + sub] = u;
+  return float4{__shfl(u, 0, 16), __shfl(u, 1, 16), __shfl(u, 2, 16), __shfl(u, 3, 16)};
+}
+
+// the action of env step t: given (the plain rollout) or computed here (POLICY).  `A` is the kernel's argument struct
+template <bool POLICY, class A>
+__device__ __forceinline__ float4 sawyer_step_action(const A& a, const int t, const int n, const int env, const int sub, const bool live) {
+  if constexpr (POLICY) {
+    // what the policy sees: the row this env emitted last, exactly as it stands in out.obs (a rolled-back step's repeated row, the goal block a goal switch
+    // patched), each double rounded to float32; at step 0 the caller's obs0.  Lane `sub` reads the element lane `sub` wrote (sawyer_emit, the rollback and the
+    // goal switch all write element `sub` from lane `sub`), so inside a wave's run of env steps this is the lane's own store in program order; the first step of
+    // a time slice reads a row another wave wrote, ordered by sched_release's release fence and sched_claim's acquire fence exactly as the qpos / qvel rows are.
+    const double* seen = t > 0 ? a.out.obs + ((size_t)(t - 1) * n + env) * 14 : nullptr;
+    const uint64_t ev = a.cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t;      // (read per step, like the goal switch's: see there)
+    // (offset 0 of the kernel-argument segment is the kernel's one argument, the SawyerPolicyArgs: see sawyer_policy_rollout_kernel)
+    const EARL_KARG void* ka = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    return sawyer_policy_action((uint64_t)ka, ev, (uint32_t)(a.cfg.env_offset + env), a.cfg.seed, seen, env, (size_t)t * n + env, sub, live);
+  } else {
+    return *reinterpret_cast<const float4*>(a.action + ((size_t)t * n + env) * 4);
+  }
+}
+
 #ifndef EARL_WAVES_PER_EU
 #define EARL_WAVES_PER_EU 1
 #endif
@@ -228,154 +374,18 @@ __device__ __forceinline__ void sawyer_emit(Shared<NV>& s, const typename ModelO
 // whole rollout of one group per wave
 template <int NV, int LPE, bool SLICED = false>
 __global__ __launch_bounds__(64 * Lim<NV>::WPB, EARL_WAVES_PER_EU) void sawyer_rollout_kernel(const SawyerArgs a) {
-  static_assert(LPE >= 14, "the observation is written by 14 lanes");
-  constexpr int EPW = 64 / LPE, WPB = Lim<NV>::WPB;
-  __shared__ alignas(16) typename ModelOf<NV>::T m;
-  __shared__ alignas(16) BlkTable<Lim<NV>::MB, Lim<NV>::KBT> bt;
-  __shared__ alignas(16) Shared<NV> sh[EPW * WPB];
-  stage_blocks(bt, a.col);
-  stage_kb<NV>(bt, a.m, a.col);
-  stage_model(m, a.m);
-  const earl_sawyer_cfg& cfg = a.cfg;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), sub = lane % LPE, grp = lane / LPE, n = cfg.n;
-#ifdef EARL_PHYS_PROF
-  const unsigned long long wave_t0 = __builtin_readcyclecounter();
-#endif
-  Shared<NV>& s = sh[wave * EPW + grp];
-  if constexpr (Lim<NV>::TS < Lim<NV>::NT) {            // the mass-matrix entries between the two trees are never written (K5): zero, once
-    for (int k = sub; k < (int)(sizeof(s.M.v) / sizeof(double)); k += LPE) s.M.v[k] = 0.0;
-  }
-  const Q4 mq = ldq(cfg.mocap_quat);                     // as given, NOT normalised (include/earl_physics.h)
-  const int gcf = a.st.steps_since_goal_change ? cfg.goal_change_frequency : 0;
-  const float scale = (float)cfg.action_scale;
-  const int G = (n + EPW - 1) / EPW;                     // env groups (one per wave at a time)
-  for (;;) {
-  int group = blockIdx.x * WPB + wave, t_begin = 0, t_end = a.T;
-  if constexpr (SLICED) {
-    group = sched_claim(a.st.sched, G, a.T, lane, (int)(((blockIdx.x * WPB + wave) * 2) % G), t_begin);
-    if (group < 0) break;
-    t_end = t_begin + a.slice < a.T ? t_begin + a.slice : a.T;
-  }
-  const int env_raw = group * EPW + grp;
-  const bool live = env_raw < n;
-  const int env = live ? env_raw : n - 1;
-  load_state<NV>(s, m, a.st.qpos + (size_t)env * m.nq, a.st.qvel + (size_t)env * NV, sub);
-  if (sub < 3) s.mocap[sub] = a.st.mocap_pos[(size_t)env * 3 + sub];
-  fence();
-  int steps = a.st.steps_since_reset ? a.st.steps_since_reset[env] : 0;
-  int sgc = gcf > 0 ? a.st.steps_since_goal_change[env] : 0;
-  RSTART();
-  for (int t = t_begin; t < t_end; ++t) {
-    const float4 act = *reinterpret_cast<const float4*>(a.action + ((size_t)t * n + env) * 4);
-    // set_xyz_action [UPSTREAM]: clip, float32 product with the scale, float64 add, box clip
-    const float cx = fminf(fmaxf(act.x, -1.f), 1.f) * scale, cy = fminf(fmaxf(act.y, -1.f), 1.f) * scale, cz = fminf(fmaxf(act.z, -1.f), 1.f) * scale;
-    if (sub < 3) {                                      // lane k moves coordinate k
-      const float ck = sub == 0 ? cx : (sub == 1 ? cy : cz);
-      s.mocap[sub] = fmin(fmax(s.mocap[sub] + (double)ck, cfg.mocap_low[sub]), cfg.mocap_high[sub]);
-    }
-    fence();
-    const double ctrl[EARL_MAXACT] = {(double)act.w, -(double)act.w, 0, 0};
-    RSTAMP(12);
-    for (int ts = 0; ts < cfg.frame_skip; ++ts) {
-      // The lane's index is passed through an empty asm at the head of every timestep: the per-lane LDS addresses derived from it are then recomputed
-      // inside the timestep (a few integer adds) instead of being hoisted out of the rollout loop, where dozens of them lived across the whole kernel
-      // and went to scratch memory under the register cap -- every reload is a global-memory round trip on the timestep's critical path (scratch per
-      // lane: eight-wave door build 296 -> 212 B, peg 36 -> 0 B).  (Doing the same to the block pointer hides that it is an LDS address: 640 B.)
-      // (Small model only: the peg build, with 512 registers, loses 2 % to the recomputation although its last 36 B of scratch go too.)
-      int sub_ = sub, grp_ = grp;
-      if constexpr (NV <= 10) asm volatile("" : "+v"(sub_));
-      else asm volatile("" : "+v"(grp_));               // (peg: the block's base address was what got spilled, and reloaded six times per timestep)
-      __builtin_assume(sub_ >= 0 && sub_ < LPE);
-      __builtin_assume(grp_ >= 0 && grp_ < EPW);
-      substep<NV, LPE, true>(sh[wave * EPW + grp_], m, bt, a.col, sub_, grp_, mq, ctrl, ts > 0, nullptr, nullptr);   // (every env step starts cold: step() x T == rollout(T))
-    }
-    RSTAMP(13);
-    const size_t row = (size_t)t * n + env;
-    // failure guard (MuJoCo's mj_checkPos / mj_checkVel; metaworld's `except MujocoException` in SawyerXYZEnv.step [UPSTREAM]): an env whose
-    // state went NaN or beyond EARL_BAD_VALUE is rolled back to its last stable state (the rows in HBM) and re-emits its last stable
-    // observation with reward 0; its neighbours in the wavefront never see it (a group only reads its own LDS block)
-    const bool bad_lane = (sub < NV && !(fabs(s.qp[sub]) < EARL_BAD_VALUE && fabs(s.qv[sub]) < EARL_BAD_VALUE)) || (sub < 4 && !(fabs(s.bq[sub]) < 2.0));
-    const bool failed = group_any<LPE>(bad_lane, grp);
-    sawyer_emit<NV>(s, m, cfg, sub, live && !failed, a.st.goal + (size_t)env * 7, a.out.obs + row * 14, a.out.reward ? a.out.reward + row : nullptr,
-                    a.out.success ? a.out.success + row : nullptr, a.st.obj_init ? a.st.obj_init + (size_t)env * 6 : nullptr, (double)act.w, nullptr,
-                    (NV >= 15 && a.out.info) ? a.out.info + row * EARL_SAWYER_INFO : nullptr);
-    RSTAMP(14);
-    if (sub == 0 && live && a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
-    if (!failed) {
-      // this state is the env's last stable one from here on
-      if (live) {
-        store_state<NV>(s, m, a.st.qpos + (size_t)env * m.nq, a.st.qvel + (size_t)env * NV, sub);
-        if (sub < 3) a.st.mocap_pos[(size_t)env * 3 + sub] = s.mocap[sub];
-      }
-      if constexpr (NV >= 15) {
-        // the free body's orientation as load_state would read it back from the row just stored (re-normalised, the same expression): a rollout, its
-        // time slices taken by different waves, and T single-step launches then walk through the same bits (like the minitaur kernel)
-        if (m.ball_dof >= 0) {
-          const double qn = renormalised_quat_entry<NV>(s, sub);
-          fence();
-          if (sub < 4) s.bq[sub] = qn;
-          fence();
-        }
-      }
-    } else {
-      load_state<NV>(s, m, a.st.qpos + (size_t)env * m.nq, a.st.qvel + (size_t)env * NV, sub);
-      if (sub < 3) s.mocap[sub] = a.st.mocap_pos[(size_t)env * 3 + sub];
-      if (live) {
-        const double* prev = t > 0 ? a.out.obs + ((size_t)(t - 1) * n + env) * 14 : (a.st.last_obs ? a.st.last_obs + (size_t)env * 14 : nullptr);
-        if (sub < 14) a.out.obs[row * 14 + sub] = prev ? prev[sub] : __builtin_nan("");
-        if (sub == 0) {
-          if (a.out.reward) a.out.reward[row] = 0.f;
-          if (a.out.success) a.out.success[row] = 0;
-          if (a.st.fail_count) a.st.fail_count[env] += 1;
-        }
-        if (NV >= 15 && a.out.info && sub < EARL_SAWYER_INFO) a.out.info[row * EARL_SAWYER_INFO + sub] = 0.0;
-      }
-    }
-    fence();
-    ++steps;
-    RSTAMP(15);
-    if (sub == 0 && live && a.out.done) a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
-    // door with goal switching: slot 7 of EVERY row's info block is this kernel's to write -- 0, or 1 on a goal-switch row (below) -- so that earl_sawyer_door_info never reads
-    // a marker the caller left behind (the Python side used to zero the column with a launch of its own before every call)
-    if (NV < 15 && gcf > 0 && a.out.info && sub == 11 && live) a.out.info[row * EARL_SAWYER_INFO + 7] = 0.0;
-    if (gcf > 0 && ++sgc >= gcf) {
-      // LifelongWrapper.step (lifelong_wrapper.py:36-42): reset_goal() -> get_next_goal(), then the observation is re-read with the new
-      // goal (same simulator state: only the goal block changes); the reward above used the old goal
-      sgc = 0;
-      if (cfg.n_goal_rows > 0 && cfg.goal_table && sub >= 7 && sub < 14 && live) {      // the lanes that wrote the goal block of this row
-        // the host's step counter plus the clock word of a graph-captured launch (earl_sawyer_rollout_clocked), read here -- a goal-switch step -- and not at kernel
-        // entry: a value held across the rollout loop costs the time-sliced peg build 32 B of scratch per lane and the 64-lane door build two AGPRs
-        const uint64_t ev = cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t;
-        const earl::U4 b = earl::philox4x32_10(earl::U4{0xFFFEu, (uint32_t)(cfg.env_offset + env), (uint32_t)ev, (uint32_t)(ev >> 32)},
-                                               (uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32));
-        int grow = (int)(earl::u01(b.x, b.y) * (double)cfg.n_goal_rows);
-        grow = grow < cfg.n_goal_rows ? grow : cfg.n_goal_rows - 1;
-        const double gv = cfg.goal_table[(size_t)grow * 7 + (sub - 7)];
-        if (NV < 15 && a.out.info && sub >= 11) {
-          // the door's info dict is worked out after the launch from the emitted rows (earl_sawyer_door_info), whose goal block is about to change: this
-          // row's info slots 0-2 carry the target the row's reward was computed with, slot 7 marks it (evaluate_state runs before reset_goal:
-          // lifelong_wrapper.py:30-44; include/earl_physics.h)
-          a.out.info[row * EARL_SAWYER_INFO + (sub - 11)] = a.st.goal[(size_t)env * 7 + (sub - 7)];
-          if (sub == 11) a.out.info[row * EARL_SAWYER_INFO + 7] = 1.0;
-        }
-        a.st.goal[(size_t)env * 7 + (sub - 7)] = gv;
-        a.out.obs[row * 14 + sub] = gv;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");      // the next step's observation reads the goal row back through global memory
-    }
-  }
-  if (live) {
-    // (qpos / qvel / mocap_pos were written back after the last stable step)
-    if (t_end == a.T && a.st.last_obs && a.T > 0 && sub < 14) a.st.last_obs[(size_t)env * 14 + sub] = a.out.obs[((size_t)(a.T - 1) * n + env) * 14 + sub];
-    if (sub == 0 && a.st.steps_since_reset) a.st.steps_since_reset[env] = steps;
-    if (sub == 0 && gcf > 0) a.st.steps_since_goal_change[env] = sgc;
-  }
-  if constexpr (SLICED) sched_release(a.st.sched, G, group, t_end, lane);
-  else break;
-  }
-#ifdef EARL_PHYS_PROF
-  if (lane == 0 && blockIdx.x * WPB + wave < 4096) g_wave_cycles[blockIdx.x * WPB + wave] = __builtin_readcyclecounter() - wave_t0;
-#endif
+  constexpr bool POLICY = false;
+#include "physics_env_sawyer_rollout.inc"
+}
+// The same rollout with the policy inside (earl_sawyer_policy_rollout): 16 lanes per env only (the policy phase is laid out over an env's 16 lanes)
+// `a` must stay the kernel's ONLY argument: the policy phase reads a.pol / a.head / a.gauss / a.obs0 / a.act_out through the kernel-argument segment pointer cast to
+// SawyerPolicyArgs* (sawyer_step_action, sawyer_policy_action), which is `a` only while `a` sits at offset 0 of the segment
+static_assert(std::is_standard_layout<SawyerArgs>::value && std::is_trivially_copyable<SawyerPolicyArgs>::value, "the policy phase reads SawyerPolicyArgs as laid out in the kernel-argument segment");
+template <int NV, int LPE, bool SLICED = false>
+__global__ __launch_bounds__(64 * Lim<NV>::WPB, EARL_WAVES_PER_EU) void sawyer_policy_rollout_kernel(const SawyerPolicyArgs a) {
+  static_assert(LPE == 16, "the policy phase is laid out over 16 lanes per env");
+  constexpr bool POLICY = true;
+#include "physics_env_sawyer_rollout.inc"
 }
 
 // reset (masked) / observe: both end with the kinematics of the current state and the observation

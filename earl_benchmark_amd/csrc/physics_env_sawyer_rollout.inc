@@ -1,0 +1,157 @@
+// physics_env_sawyer_rollout.inc -- the body of the Sawyer door / peg rollout kernels (physics_env_sawyer.h): sawyer_rollout_kernel includes it with POLICY = false
+// (every action given), sawyer_policy_rollout_kernel with POLICY = true (the action of env step t computed by the env's own 16 lanes from the observation the env
+// last emitted).  Template parameters NV, LPE, SLICED and the kernel argument `a` are the including kernel's.
+  static_assert(LPE >= 14, "the observation is written by 14 lanes");
+  constexpr int EPW = 64 / LPE, WPB = Lim<NV>::WPB;
+  __shared__ alignas(16) typename ModelOf<NV>::T m;
+  __shared__ alignas(16) BlkTable<Lim<NV>::MB, Lim<NV>::KBT> bt;
+  __shared__ alignas(16) Shared<NV> sh[EPW * WPB];
+  stage_blocks(bt, a.col);
+  stage_kb<NV>(bt, a.m, a.col);
+  stage_model(m, a.m);
+  const earl_sawyer_cfg& cfg = a.cfg;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), sub = lane % LPE, grp = lane / LPE, n = cfg.n;
+#ifdef EARL_PHYS_PROF
+  const unsigned long long wave_t0 = __builtin_readcyclecounter();
+#endif
+  Shared<NV>& s = sh[wave * EPW + grp];
+  if constexpr (Lim<NV>::TS < Lim<NV>::NT) {            // the mass-matrix entries between the two trees are never written (K5): zero, once
+    for (int k = sub; k < (int)(sizeof(s.M.v) / sizeof(double)); k += LPE) s.M.v[k] = 0.0;
+  }
+  const Q4 mq = ldq(cfg.mocap_quat);                     // as given, NOT normalised (include/earl_physics.h)
+  const int gcf = a.st.steps_since_goal_change ? cfg.goal_change_frequency : 0;
+  const float scale = (float)cfg.action_scale;
+  const int G = (n + EPW - 1) / EPW;                     // env groups (one per wave at a time)
+  for (;;) {
+  int group = blockIdx.x * WPB + wave, t_begin = 0, t_end = a.T;
+  if constexpr (SLICED) {
+    group = sched_claim(a.st.sched, G, a.T, lane, (int)(((blockIdx.x * WPB + wave) * 2) % G), t_begin);
+    if (group < 0) break;
+    t_end = t_begin + a.slice < a.T ? t_begin + a.slice : a.T;
+  }
+  const int env_raw = group * EPW + grp;
+  const bool live = env_raw < n;
+  const int env = live ? env_raw : n - 1;
+  load_state<NV>(s, m, a.st.qpos + (size_t)env * m.nq, a.st.qvel + (size_t)env * NV, sub);
+  if (sub < 3) s.mocap[sub] = a.st.mocap_pos[(size_t)env * 3 + sub];
+  fence();
+  int steps = a.st.steps_since_reset ? a.st.steps_since_reset[env] : 0;
+  int sgc = gcf > 0 ? a.st.steps_since_goal_change[env] : 0;
+  RSTART();
+  for (int t = t_begin; t < t_end; ++t) {
+    const float4 act = sawyer_step_action<POLICY>(a, t, n, env, sub, live);
+    // set_xyz_action [UPSTREAM]: clip, float32 product with the scale, float64 add, box clip
+    const float cx = fminf(fmaxf(act.x, -1.f), 1.f) * scale, cy = fminf(fmaxf(act.y, -1.f), 1.f) * scale, cz = fminf(fmaxf(act.z, -1.f), 1.f) * scale;
+    if (sub < 3) {                                      // lane k moves coordinate k
+      const float ck = sub == 0 ? cx : (sub == 1 ? cy : cz);
+      s.mocap[sub] = fmin(fmax(s.mocap[sub] + (double)ck, cfg.mocap_low[sub]), cfg.mocap_high[sub]);
+    }
+    fence();
+    const double ctrl[EARL_MAXACT] = {(double)act.w, -(double)act.w, 0, 0};
+    RSTAMP(12);
+    for (int ts = 0; ts < cfg.frame_skip; ++ts) {
+      // The lane's index is passed through an empty asm at the head of every timestep: the per-lane LDS addresses derived from it are then recomputed
+      // inside the timestep (a few integer adds) instead of being hoisted out of the rollout loop, where dozens of them lived across the whole kernel
+      // and went to scratch memory under the register cap -- every reload is a global-memory round trip on the timestep's critical path (scratch per
+      // lane: eight-wave door build 296 -> 212 B, peg 36 -> 0 B).  (Doing the same to the block pointer hides that it is an LDS address: 640 B.)
+      // (Small model only: the peg build, with 512 registers, loses 2 % to the recomputation although its last 36 B of scratch go too.)
+      int sub_ = sub, grp_ = grp;
+      if constexpr (POLICY) {
+        // (the policy phase is a call: what lives across it sits in the callee-saved registers or is spilled around it, and the allocator chose `sub` -- reloaded
+        // here, at the head of every timestep.  The lane's index costs two instructions to read again and nothing to keep.)
+        const int lane_ = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        sub_ = lane_ % LPE; grp_ = lane_ / LPE;
+      }
+      if constexpr (NV <= 10) asm volatile("" : "+v"(sub_));
+      else asm volatile("" : "+v"(grp_));               // (peg: the block's base address was what got spilled, and reloaded six times per timestep)
+      __builtin_assume(sub_ >= 0 && sub_ < LPE);
+      __builtin_assume(grp_ >= 0 && grp_ < EPW);
+      substep<NV, LPE, true>(sh[wave * EPW + grp_], m, bt, a.col, sub_, grp_, mq, ctrl, ts > 0, nullptr, nullptr);   // (every env step starts cold: step() x T == rollout(T))
+    }
+    RSTAMP(13);
+    const size_t row = (size_t)t * n + env;
+    // failure guard (MuJoCo's mj_checkPos / mj_checkVel; metaworld's `except MujocoException` in SawyerXYZEnv.step [UPSTREAM]): an env whose
+    // state went NaN or beyond EARL_BAD_VALUE is rolled back to its last stable state (the rows in HBM) and re-emits its last stable
+    // observation with reward 0; its neighbours in the wavefront never see it (a group only reads its own LDS block)
+    const bool bad_lane = (sub < NV && !(fabs(s.qp[sub]) < EARL_BAD_VALUE && fabs(s.qv[sub]) < EARL_BAD_VALUE)) || (sub < 4 && !(fabs(s.bq[sub]) < 2.0));
+    const bool failed = group_any<LPE>(bad_lane, grp);
+    sawyer_emit<NV>(s, m, cfg, sub, live && !failed, a.st.goal + (size_t)env * 7, a.out.obs + row * 14, a.out.reward ? a.out.reward + row : nullptr,
+                    a.out.success ? a.out.success + row : nullptr, a.st.obj_init ? a.st.obj_init + (size_t)env * 6 : nullptr, (double)act.w, nullptr,
+                    (NV >= 15 && a.out.info) ? a.out.info + row * EARL_SAWYER_INFO : nullptr);
+    RSTAMP(14);
+    if (sub == 0 && live && a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
+    if (!failed) {
+      // this state is the env's last stable one from here on
+      if (live) {
+        store_state<NV>(s, m, a.st.qpos + (size_t)env * m.nq, a.st.qvel + (size_t)env * NV, sub);
+        if (sub < 3) a.st.mocap_pos[(size_t)env * 3 + sub] = s.mocap[sub];
+      }
+      if constexpr (NV >= 15) {
+        // the free body's orientation as load_state would read it back from the row just stored (re-normalised, the same expression): a rollout, its
+        // time slices taken by different waves, and T single-step launches then walk through the same bits (like the minitaur kernel)
+        if (m.ball_dof >= 0) {
+          const double qn = renormalised_quat_entry<NV>(s, sub);
+          fence();
+          if (sub < 4) s.bq[sub] = qn;
+          fence();
+        }
+      }
+    } else {
+      load_state<NV>(s, m, a.st.qpos + (size_t)env * m.nq, a.st.qvel + (size_t)env * NV, sub);
+      if (sub < 3) s.mocap[sub] = a.st.mocap_pos[(size_t)env * 3 + sub];
+      if (live) {
+        const double* prev = t > 0 ? a.out.obs + ((size_t)(t - 1) * n + env) * 14 : (a.st.last_obs ? a.st.last_obs + (size_t)env * 14 : nullptr);
+        if (sub < 14) a.out.obs[row * 14 + sub] = prev ? prev[sub] : __builtin_nan("");
+        if (sub == 0) {
+          if (a.out.reward) a.out.reward[row] = 0.f;
+          if (a.out.success) a.out.success[row] = 0;
+          if (a.st.fail_count) a.st.fail_count[env] += 1;
+        }
+        if (NV >= 15 && a.out.info && sub < EARL_SAWYER_INFO) a.out.info[row * EARL_SAWYER_INFO + sub] = 0.0;
+      }
+    }
+    fence();
+    ++steps;
+    RSTAMP(15);
+    if (sub == 0 && live && a.out.done) a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
+    // door with goal switching: slot 7 of EVERY row's info block is this kernel's to write -- 0, or 1 on a goal-switch row (below) -- so that earl_sawyer_door_info never reads
+    // a marker the caller left behind (ADVICE r05: the Python side used to zero the column with a launch of its own before every call)
+    if (NV < 15 && gcf > 0 && a.out.info && sub == 11 && live) a.out.info[row * EARL_SAWYER_INFO + 7] = 0.0;
+    if (gcf > 0 && ++sgc >= gcf) {
+      // LifelongWrapper.step (lifelong_wrapper.py:36-42): reset_goal() -> get_next_goal(), then the observation is re-read with the new
+      // goal (same simulator state: only the goal block changes); the reward above used the old goal
+      sgc = 0;
+      if (cfg.n_goal_rows > 0 && cfg.goal_table && sub >= 7 && sub < 14 && live) {      // the lanes that wrote the goal block of this row
+        // the host's step counter plus the clock word of a graph-captured launch (earl_sawyer_rollout_clocked), read here -- a goal-switch step -- and not at kernel
+        // entry: a value held across the rollout loop costs the time-sliced peg build 32 B of scratch per lane and the 64-lane door build two AGPRs
+        const uint64_t ev = cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t;
+        const earl::U4 b = earl::philox4x32_10(earl::U4{0xFFFEu, (uint32_t)(cfg.env_offset + env), (uint32_t)ev, (uint32_t)(ev >> 32)},
+                                               (uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32));
+        int grow = (int)(earl::u01(b.x, b.y) * (double)cfg.n_goal_rows);
+        grow = grow < cfg.n_goal_rows ? grow : cfg.n_goal_rows - 1;
+        const double gv = cfg.goal_table[(size_t)grow * 7 + (sub - 7)];
+        if (NV < 15 && a.out.info && sub >= 11) {
+          // the door's info dict is worked out after the launch from the emitted rows (earl_sawyer_door_info), whose goal block is about to change: this
+          // row's info slots 0-2 carry the target the row's reward was computed with, slot 7 marks it (evaluate_state runs before reset_goal:
+          // lifelong_wrapper.py:30-44; include/earl_physics.h)
+          a.out.info[row * EARL_SAWYER_INFO + (sub - 11)] = a.st.goal[(size_t)env * 7 + (sub - 7)];
+          if (sub == 11) a.out.info[row * EARL_SAWYER_INFO + 7] = 1.0;
+        }
+        a.st.goal[(size_t)env * 7 + (sub - 7)] = gv;
+        a.out.obs[row * 14 + sub] = gv;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");      // the next step's observation reads the goal row back through global memory
+    }
+  }
+  if (live) {
+    // (qpos / qvel / mocap_pos were written back after the last stable step)
+    if (t_end == a.T && a.st.last_obs && a.T > 0 && sub < 14) a.st.last_obs[(size_t)env * 14 + sub] = a.out.obs[((size_t)(a.T - 1) * n + env) * 14 + sub];
+    if (sub == 0 && a.st.steps_since_reset) a.st.steps_since_reset[env] = steps;
+    if (sub == 0 && gcf > 0) a.st.steps_since_goal_change[env] = sgc;
+  }
+  if constexpr (SLICED) sched_release(a.st.sched, G, group, t_end, lane);
+  else break;
+  }
+#ifdef EARL_PHYS_PROF
+  if (lane == 0 && blockIdx.x * WPB + wave < 4096) g_wave_cycles[blockIdx.x * WPB + wave] = __builtin_readcyclecounter() - wave_t0;
+#endif

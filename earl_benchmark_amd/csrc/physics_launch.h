@@ -12,6 +12,8 @@ extern "C" __attribute__((visibility("hidden"))) void earl_unit_kitchen_physics(
 // the door's eight-wave rollout (physics_w8.hip): earl_sawyer_rollout(_clocked) hands it its argument struct (the clock included); earl_sawyer_rollout_door_w8 is
 // exported like the other entry points
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_w8_sawyer_rollout(const void* sawyer_args, void* stream);
+// the same hand-over for the rollout with the policy inside (earl_sawyer_policy_rollout; the argument is a SawyerPolicyArgs)
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_w8_sawyer_policy_rollout(const void* sawyer_policy_args, void* stream);
 extern "C" int earl_sawyer_rollout_door_w8(const earl_link_model* model, const earl_collision_model* col, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                            const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream);
 

@@ -13,6 +13,7 @@
                                 // slower one: 60.3 against 57.5 ms.)
 #define EARL_NO_PREFETCH 1      // no prefetch of the first near block's pair record: the second wave hides that latency, the 22 registers are worth more
 #include "physics_stepper.h"
+#include "policy_math.h"
 
 namespace {
 #include "physics_env_sawyer.h"
@@ -26,6 +27,11 @@ int earl_unit_w8_sawyer_rollout(const void* sawyer_args, void* stream) {
   const SawyerArgs& a = *static_cast<const SawyerArgs*>(sawyer_args);
   sawyer_rollout_kernel<10, 16><<<grid_for<10, 16>(a.cfg.n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
   return launched("sawyer_rollout (door, 8 waves per CU)");
+}
+int earl_unit_w8_sawyer_policy_rollout(const void* sawyer_policy_args, void* stream) {
+  const SawyerPolicyArgs& a = *static_cast<const SawyerPolicyArgs*>(sawyer_policy_args);
+  sawyer_policy_rollout_kernel<10, 16><<<grid_for<10, 16>(a.cfg.n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
+  return launched("sawyer_policy_rollout (door, 8 waves per CU)");
 }
 int earl_sawyer_rollout_door_w8(const earl_link_model* model, const earl_collision_model* col, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                 const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream) {

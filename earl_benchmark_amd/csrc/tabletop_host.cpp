@@ -8,6 +8,7 @@
 #include "tabletop_hostside.h"
 #include "tabletop_step.h"
 #include "tabletop_policy.h"
+#include "../../include/earl_physics.h"
 
 #ifdef _OPENMP
 #include <omp.h>
@@ -215,6 +216,51 @@ int earl_tabletop3_reward_cpu(int32_t n, const float* obs, int32_t reward_type, 
   for_each_env(n, [&](int i) { reward_body<3>(i, obs, reward_type, 0, reward, success, th); });
   return EARL_OK;
 }
+
+// include/earl_physics.h: the policy contract as plain loops, any input / action width (the oracle of the Sawyer rollout's in-kernel policy)
+int32_t earl_mlp_policy_forward_cpu(const earl_mlp_policy* p, const earl_gaussian_head* h, int32_t n, const float* obs, const float* eps, float* actions) {
+  if (!p || !p->params || !obs || !actions || n < 0) return fail(EARL_ERR_ARG, "policy/params/obs/actions is NULL or n < 0");
+  if (p->precision != 0) return fail(EARL_ERR_ARG, "policy precision = %d: only 0 (fp32) exists", p->precision);
+  if (p->n_layers != 2 && p->n_layers != 3) return fail(EARL_ERR_ARG, "policy n_layers = %d: 2 (one hidden layer) or 3 (two)", p->n_layers);
+  for (int l = 0; l < p->n_layers; ++l)
+    if (p->dims[l] < 1 || p->dims[l] > kPolicyMaxWidth) return fail(EARL_ERR_ARG, "policy dims[%d] = %d: 1..256", l, p->dims[l]);
+  const int NL = p->dims[p->n_layers];
+  if (NL < 1 || NL > kPolicyMaxWidth || (h && NL % 2)) return fail(EARL_ERR_ARG, "policy output width %d", NL);
+  if (p->hidden_act != EARL_ACT_RELU && p->hidden_act != EARL_ACT_TANH) return fail(EARL_ERR_ARG, "policy hidden_act = %d", p->hidden_act);
+  if (p->out_act != EARL_ACT_NONE && p->out_act != EARL_ACT_TANH) return fail(EARL_ERR_ARG, "policy out_act = %d", p->out_act);
+  if (h) {
+    if (h->mode != EARL_HEAD_MEAN && h->mode != EARL_HEAD_SAMPLE) return fail(EARL_ERR_ARG, "head mode = %d", h->mode);
+    if (h->log_std_map != EARL_LOGSTD_CLAMP && h->log_std_map != EARL_LOGSTD_TANH) return fail(EARL_ERR_ARG, "head log_std_map = %d", h->log_std_map);
+    if (!(h->log_std_min >= -20.0f && h->log_std_max <= 4.0f && h->log_std_min <= h->log_std_max)) return fail(EARL_ERR_ARG, "head log_std bounds");
+  }
+  const int A = h ? NL / 2 : NL;
+  earl_gaussian_head head = h ? *h : earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr};
+  if (!eps) head.mode = EARL_HEAD_MEAN;
+  for_each_env(n, [&](int i) {
+    float buf[2][kPolicyMaxWidth];
+    const float* in = obs + (size_t)i * p->dims[0];
+    const float* w = p->params;
+    for (int l = 0; l < p->n_layers; ++l) {
+      const int K = p->dims[l], N = p->dims[l + 1];
+      const float* b = w + (size_t)N * K;
+      float* dst = buf[l & 1];
+      for (int j = 0; j < N; ++j) {
+        float acc = b[j];
+        for (int k = 0; k < K; ++k) acc = fmaf(in[k], w[(size_t)j * K + k], acc);
+        dst[j] = l + 1 < p->n_layers ? policy_act(acc, p->hidden_act) : acc;
+      }
+      in = dst;
+      w = b + N;
+    }
+    for (int d = 0; d < A; ++d)
+      actions[(size_t)i * A + d] = h ? gaussian_head_action(head, p->out_act, in[d], in[A + d], eps ? eps[(size_t)i * A + d] : 0.0f) : policy_act(in[d], p->out_act);
+  });
+  return EARL_OK;
+}
+// the contract's scalar functions (csrc/policy_math.h), for callers that restate a policy on the host
+float earl_tanh_f32(float x) { return tanh_f32(x); }
+float earl_exp_f32(float x) { return exp_f32(x); }
+float earl_normal_quantile_f32(uint32_t k24) { return normal_quantile_f32(k24 & 0xFFFFFFu); }
 
 int earl_host_set_threads(int n) {
 #ifdef _OPENMP

@@ -107,6 +107,7 @@ class SawyerDoor:
     self.lifelong_return_t = torch.zeros(n, dtype=torch.float64, **kw)
     self.last_obs = torch.zeros(n, self.OBS_DIM, dtype=torch.float64, **kw)   # SawyerXYZEnv._last_stable_obs [UPSTREAM]
     self.fail_count = torch.zeros(n, dtype=torch.int32, **kw)                 # env steps rolled back by the failure guard (include/earl_physics.h)
+    self._last_obs_stale = False      # last_obs no longer describes (state, goal): set by set_state() / reset_goal(), cleared by whatever rewrites every row
     self.total_step_count = 0
 
     cfg = _abi.SawyerCfg(n=n, env_offset=int(env_offset), reward_type=_abi.REWARD_TYPES[reward_type], horizon=INT32_MAX,
@@ -206,16 +207,19 @@ class SawyerDoor:
             # the reference's per-step info dict (evaluate_state: sawyer_door.py:127-139 / sawyer_peg.py:165-184), slots _abi.SAWYER_INFO_KEYS
             'info': torch.empty(*lead, self.num_envs, _abi.SAWYER_INFO, dtype=torch.float64, **kw)}
 
-  def _launch_rollout(self, actions, T, out):
+  def _launch_rollout(self, actions, T, out, policy=None):
+    """T env steps and their bookkeeping; policy: None (the actions are given) or what _issue_rollout takes for the closed loop"""
     self._cfg.step_counter = self.total_step_count
-    self._issue_rollout(actions, T, out)
+    self._issue_rollout(actions, T, out, policy=policy)
     self.total_step_count += T
     if self._cfg.goal_change_frequency:
       self.lifelong_return_t += out['reward'].reshape(T, -1).sum(0, dtype=torch.float64)
     self._last_success = out['success'][-1] if out['success'].dim() == 2 else out['success']
+    self._last_obs_stale = False                           # (every env's last_obs row was rewritten)
 
-  def _issue_rollout(self, actions, T, out, clock=None):
-    """the launches of T env steps into `out` (the door's info launch included); clock: the device words of earl_sawyer_rollout_clocked (None: earl_sawyer_rollout)"""
+  def _issue_rollout(self, actions, T, out, clock=None, policy=None):
+    """the launches of T env steps into `out` (the door's info launch included); clock: the device words of earl_sawyer_rollout_clocked (None: earl_sawyer_rollout);
+    policy: None, or (policy, head struct or None, obs0) -- earl_sawyer_policy_rollout computes the actions itself and leaves them in out['actions']"""
     info = out.get('info')
     in_kernel = info is not None and self.nv >= 15        # the peg's dict needs simulator state: the rollout kernel's epilogue writes it
     # door, lifelong goal switching: the kernel leaves the PRE-switch target on goal-switch rows (slots 0-2, marker in slot 7) for earl_sawyer_door_info
@@ -225,7 +229,12 @@ class SawyerDoor:
     with torch.cuda.device(self.device):
       if self.sched is not None and T > 1 and self._uses_queue(T):
         self.sched.zero_()                                 # (the queue of the time-sliced schedule: zero on entry)
-      if clock is None:
+      if policy is not None:
+        pi, head, obs0 = policy
+        _abi.check(self._lib.earl_sawyer_policy_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pi.struct),
+                                                        None if head is None else C.byref(head), obs0.data_ptr(), T, clock, out['actions'].data_ptr(), C.byref(o),
+                                                        self._stream()), 'earl_sawyer_policy_rollout')
+      elif clock is None:
         _abi.check(self._lib.earl_sawyer_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, actions.data_ptr(),
                                                  T, C.byref(o), self._stream()), 'earl_sawyer_rollout')
       else:
@@ -254,6 +263,7 @@ class SawyerDoor:
     self._cfg.counter += 1
     if mask is None:
       self.interventions += 1
+      self._last_obs_stale = False
     else:
       self.interventions += mask.to(torch.int32)
       obs = torch.where(mask.bool()[:, None], obs, obs_prev)
@@ -297,6 +307,7 @@ class SawyerDoor:
 
   def _graph_advance(self, T, out):
     self.total_step_count += T
+    self._last_obs_stale = False
     self._last_success = out['success'][-1]
 
   def _graph_info(self, out):
@@ -334,6 +345,43 @@ class SawyerDoor:
     T = a.shape[0]
     out = out if out is not None else self._new_out((T,))
     self._launch_rollout(self._actions(a, (T,)), T, out)
+    return out
+
+  def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
+    """Closed loop in ONE launch of the rollout kernel (include/earl_physics.h: earl_sawyer_policy_rollout): `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy`
+    built with obs_dim=14, act_dim=4 -- is evaluated between the env steps by the lanes that own the env: observation -> float32 MLP -> action -> env step.
+    -> rollout()'s dict plus 'actions' [T, N, 4] float32 (as the policy produced them) and, with return_noise=True, 'eps' [T, N, 4] (the standard-normal draws as
+    used).  Bit-identical to rollout(out['actions']) from the same state.  The first action is computed from the observation the env last returned (`last_obs`: the row
+    the previous step / rollout / reset emitted, so T launches of one step equal one launch of T); after set_state() or reset_goal() from _get_obs() of the
+    current state and goal.  reset_first=True calls reset() before (a launch of its own).  A Gaussian policy is sampled inside the kernel (sample=True: tanh(mean + exp(log_std) eps), eps from the env's Philox
+    stream keyed by seed, global env id and step counter) or evaluated at its mean (sample=False); both flags are for Gaussian policies only."""
+    from ..policy import GaussianMLPPolicy, MLPPolicy
+    if not isinstance(policy, MLPPolicy):
+      raise ValueError('rollout_policy: an MLPPolicy or a GaussianMLPPolicy (populations and agent pairs are tabletop only)')
+    gaussian = isinstance(policy, GaussianMLPPolicy)
+    if not gaussian and (return_noise or not sample):
+      raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
+    if (policy.obs_dim, policy.act_dim) != (self.OBS_DIM, 4):
+      raise ValueError(f'rollout_policy: a policy of observation width {policy.obs_dim} and action width {policy.act_dim}; this env takes {self.OBS_DIM} and 4 '
+                       '(MLPPolicy(..., obs_dim=14, act_dim=4))')
+    if policy.device != self.device:
+      raise ValueError(f'rollout_policy: the policy is on {policy.device}, the env on {self.device} (policy.to(device))')
+    T = int(T)
+    if T < 1:
+      raise ValueError(f'rollout_policy: T = {T} < 1')
+    if reset_first:
+      self.reset()
+    out = out if out is not None else self._new_out((T,))
+    if 'actions' not in out:
+      out['actions'] = torch.empty(T, self.num_envs, 4, dtype=torch.float32, device=self.device)
+    if return_noise and 'eps' not in out:
+      out['eps'] = torch.empty(T, self.num_envs, 4, dtype=torch.float32, device=self.device)
+    # what the policy sees first: the observation the env last returned (st.last_obs: the row the previous step / rollout / reset emitted, goal block as patched) --
+    # T launches of one step then consume the very rows one launch of T consumes; after set_state() / reset_goal() that row no longer describes the env and the
+    # observation of the current state and goal is recomputed
+    obs0 = self._get_obs_t() if self._last_obs_stale else self.last_obs
+    head = policy.head(sample=bool(sample), eps_out=out['eps'] if return_noise else None) if gaussian else None
+    self._launch_rollout(None, T, out, policy=(policy, head, obs0))
     return out
 
   def _get_obs_t(self):
@@ -380,6 +428,7 @@ class SawyerDoor:
     else:
       m = torch.as_tensor(mask, device=self.device).bool()
       self.goal_t[m] = g[m]
+    self._last_obs_stale = True                            # (last_obs carries the old goal block: rollout_policy recomputes its first observation)
 
   @property
   def goal(self):
@@ -387,13 +436,15 @@ class SawyerDoor:
 
   # ------------------------------------------------------------------ state access
   def set_state(self, qpos, qvel):
+    self._last_obs_stale = True                            # (last_obs no longer belongs to the state: rollout_policy recomputes its first observation)
     self.qpos.copy_(torch.as_tensor(qpos, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.nq))
     self.qvel.copy_(torch.as_tensor(qvel, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.nv))
 
   def state_dict(self):
     return {k: getattr(self, k).clone() for k in ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'steps_since_reset', 'interventions',
                                                   'steps_since_goal_change', 'lifelong_return_t', 'obj_init', 'last_obs', 'fail_count')} | {
-                                                      'counter': int(self._cfg.counter), 'total_step_count': self.total_step_count}
+                                                      'counter': int(self._cfg.counter), 'total_step_count': self.total_step_count,
+                                                      'last_obs_stale': bool(self._last_obs_stale)}
 
   def load_state_dict(self, sd):
     for k in ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'steps_since_reset', 'interventions', 'steps_since_goal_change',
@@ -402,3 +453,4 @@ class SawyerDoor:
         getattr(self, k).copy_(sd[k])
     self._cfg.counter = int(sd['counter'])
     self.total_step_count = int(sd['total_step_count'])
+    self._last_obs_stale = bool(sd.get('last_obs_stale', 'last_obs' not in sd))      # (a dict without the row leaves the env's own, which belongs to another state)

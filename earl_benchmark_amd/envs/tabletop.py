@@ -308,8 +308,9 @@ class TabletopManipulation:
     eps from the env's Philox stream keyed by the global env id and the step's counter), sample=False evaluates the actor at its mean;
     return_noise=True appends eps [E,T,N,3], the standard-normal draws as used.  Both are for Gaussian policies only.
     A `PolicyPopulation` goes to earl_tabletop_population_rollout: the env with global id g runs member g // envs_per_policy, same returns."""
-    from ..policy import GaussianMLPPolicy, PolicyPopulation
+    from ..policy import GaussianMLPPolicy, PolicyPopulation, require_tabletop_widths
     population = isinstance(policy, PolicyPopulation)
+    require_tabletop_widths(policy.template if population else policy, 'rollout_policy')
     gaussian = policy.gaussian if population else isinstance(policy, GaussianMLPPolicy)
     if not gaussian and (return_noise or not sample):
       raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
@@ -365,7 +366,8 @@ class TabletopManipulation:
     -> {'ret': [E, N] float64 undiscounted return (the float32 step rewards summed in float64, t ascending), 'success': [E, N] bool success at the last step,
         'first_success': [E, N] int32 first successful step, -1 if none}; each equals its definition applied to what rollout_policy would have returned.
     Philox counter and total_step_count advance as in rollout_policy."""
-    from ..policy import GaussianMLPPolicy, PolicyPopulation
+    from ..policy import GaussianMLPPolicy, PolicyPopulation, require_tabletop_widths
+    require_tabletop_widths(policy.template if isinstance(policy, PolicyPopulation) else policy, 'evaluate_policy')
     gaussian = policy.gaussian if isinstance(policy, PolicyPopulation) else isinstance(policy, GaussianMLPPolicy)
     if sample and not gaussian:
       raise ValueError('evaluate_policy: sample=True needs a Gaussian policy (an MLPPolicy is deterministic)')

@@ -1,4 +1,4 @@
-"""A float32 MLP policy 12 -> hidden (-> hidden) -> 3 in the form the fused closed-loop rollout takes (include/earl_tabletop.h: struct
+"""A float32 MLP policy 12 -> hidden (-> hidden) -> 3 (tabletop; obs_dim=14, act_dim=4: the Sawyer door and peg) in the form the fused closed-loop rollout takes (include/earl_tabletop.h: struct
 earl_mlp_policy, earl_tabletop_policy_rollout): the parameters packed once, layer by layer (W_l row-major like torch.nn.Linear.weight, then b_l).
 
   pi = MLPPolicy([(w0, b0), (w1, b1)], hidden_act='relu', out_act='tanh', device='cuda')      # or MLPPolicy(torch.nn.Sequential(...))
@@ -7,6 +7,11 @@ earl_mlp_policy, earl_tabletop_policy_rollout): the parameters packed once, laye
 
 `pi(obs)` evaluates the same network with torch (matmul order is torch's: close to, not bit-identical with, the fused kernel, whose arithmetic is the
 k-ascending fmaf chain that csrc/tabletop_policy.h states).
+
+The Sawyer door and peg take the same two classes with obs_dim=14, act_dim=4 (include/earl_physics.h: earl_sawyer_policy_rollout):
+
+  pi = MLPPolicy(layers, 'relu', 'tanh', device='cuda', obs_dim=14, act_dim=4)
+  out = door.rollout_policy(pi, T=300)                                                          # rollout()'s dict plus 'actions' [T, N, 4], ONE launch
 
 `GaussianMLPPolicy` is the SAC-style actor with a tanh-Gaussian head, 12 -> hidden (-> hidden) -> 6 (rows 0..2 mean, rows 3..5 raw log_std), for
 earl_tabletop_policy_rollout_gaussian: the actions are SAMPLED inside the kernel from the env's counter-based RNG.
@@ -64,8 +69,14 @@ def _layers_of_sequential(seq):
 class MLPPolicy:
   OUT_DIM, OUT_WHAT = ACT_DIM, 'action'
 
-  def __init__(self, layers, hidden_act='relu', out_act='tanh', device='cpu'):
+  def __init__(self, layers, hidden_act='relu', out_act='tanh', device='cpu', obs_dim=OBS_DIM, act_dim=ACT_DIM):
+    """obs_dim / act_dim: the env's observation and action widths -- the tabletop's 12 / 3 by default, 14 / 4 for the Sawyer door and peg (`env.rollout_policy`)"""
     name = type(self).__name__                                        # (MLPPolicy's own messages read as they always did)
+    self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+    if self.obs_dim < 1 or self.act_dim < 1:
+      raise ValueError(f'{name}: obs_dim = {obs_dim}, act_dim = {act_dim}: both >= 1')
+    out_dim = self.act_dim * (self.OUT_DIM // ACT_DIM)                  # (the Gaussian head: twice the action width)
+    what = 'tabletop observation' if self.obs_dim == OBS_DIM else 'observation'
     if isinstance(layers, torch.nn.Sequential):
       layers, hidden_act, out_act = _layers_of_sequential(layers)
     layers = [(torch.as_tensor(np.asarray(w) if not torch.is_tensor(w) else w).detach().to('cpu', torch.float32),
@@ -81,10 +92,10 @@ class MLPPolicy:
       if w.dim() != 2 or b.dim() != 1 or w.shape[1] != dims[-1] or b.shape[0] != w.shape[0]:
         raise ValueError(f'{name}: layer {l} has weight {tuple(w.shape)} and bias {tuple(b.shape)} after width {dims[-1]}')
       dims.append(int(w.shape[0]))
-    if dims[0] != OBS_DIM:
-      raise ValueError(f'{name}: the input is the {OBS_DIM}-wide tabletop observation, got width {dims[0]}')
-    if dims[-1] != self.OUT_DIM:
-      raise ValueError(f'{name}: the output is the {self.OUT_DIM}-wide {self.OUT_WHAT}, got width {dims[-1]}')
+    if dims[0] != self.obs_dim:
+      raise ValueError(f'{name}: the input is the {self.obs_dim}-wide {what}, got width {dims[0]}')
+    if dims[-1] != out_dim:
+      raise ValueError(f'{name}: the output is the {out_dim}-wide {self.OUT_WHAT}, got width {dims[-1]}')
     for h in dims[1:-1]:
       if h < MIN_WIDTH or h > MAX_WIDTH or h % 16:
         raise ValueError(f'{name}: hidden width {h}: a multiple of 16 in {MIN_WIDTH}..{MAX_WIDTH}')
@@ -122,7 +133,7 @@ class GaussianMLPPolicy(MLPPolicy):
   standard-normal eps -- torch's statement of csrc/tabletop_policy.h's contract, close to but not bit-identical with the kernel."""
   OUT_DIM, OUT_WHAT = 2 * ACT_DIM, 'mean and raw log_std of the action'
 
-  def __init__(self, layers, hidden_act='relu', squash=True, log_std_bounds=(-5.0, 2.0), log_std_map='tanh', device='cpu'):
+  def __init__(self, layers, hidden_act='relu', squash=True, log_std_bounds=(-5.0, 2.0), log_std_map='tanh', device='cpu', obs_dim=OBS_DIM, act_dim=ACT_DIM):
     if isinstance(layers, torch.nn.Sequential):
       layers, hidden_act, last = _layers_of_sequential(layers)
       if last != 'none':
@@ -133,10 +144,10 @@ class GaussianMLPPolicy(MLPPolicy):
     if not (-20.0 <= lo <= hi <= 4.0):                       # (NaN fails the chain)
       raise ValueError(f'GaussianMLPPolicy: log_std_bounds {tuple(log_std_bounds)}: finite, min <= max, inside [-20, 4]')
     self.squash, self.log_std_bounds, self.log_std_map = bool(squash), (lo, hi), log_std_map
-    super().__init__(layers, hidden_act, 'tanh' if squash else 'none', device)
+    super().__init__(layers, hidden_act, 'tanh' if squash else 'none', device, obs_dim=obs_dim, act_dim=act_dim)
 
   def head(self, sample=True, eps_out=None):
-    """struct earl_gaussian_head for one launch; eps_out: a float32 tensor [E, T, N, 3] on the policy's device, or None"""
+    """struct earl_gaussian_head for one launch; eps_out: a float32 tensor [E, T, N, act_dim] on the policy's device, or None"""
     return _abi.GaussianHead(mode=_abi.HEAD_SAMPLE if sample else _abi.HEAD_MEAN, log_std_map=_abi.LOGSTD_MAPS[self.log_std_map],
                              log_std_min=self.log_std_bounds[0], log_std_max=self.log_std_bounds[1],
                              eps_out=None if eps_out is None else eps_out.data_ptr())
@@ -147,7 +158,7 @@ class GaussianMLPPolicy(MLPPolicy):
       x = torch.addmm(b, x.reshape(-1, x.shape[-1]), w.t()).reshape(*x.shape[:-1], w.shape[0])
       if l + 1 < len(self.layers):
         x = torch.relu(x) if self.hidden_act == 'relu' else torch.tanh(x)
-    mean, raw = x[..., :ACT_DIM], x[..., ACT_DIM:]
+    mean, raw = x[..., :self.act_dim], x[..., self.act_dim:]
     lo, hi = self.log_std_bounds
     log_std = lo + 0.5 * (hi - lo) * (torch.tanh(raw) + 1.0) if self.log_std_map == 'tanh' else torch.clamp(raw, lo, hi)
     return mean, log_std
@@ -160,6 +171,13 @@ class GaussianMLPPolicy(MLPPolicy):
     mean, log_std = self._mean_and_log_std(obs)
     u = mean + torch.exp(log_std) * torch.as_tensor(eps, dtype=torch.float32, device=mean.device)
     return torch.tanh(u) if self.squash else u
+
+
+def require_tabletop_widths(policy, who):
+  """the tabletop kernels (and the population / pair containers built for them) take 12 -> .. -> 3 networks only"""
+  od, ad = getattr(policy, 'obs_dim', OBS_DIM), getattr(policy, 'act_dim', ACT_DIM)
+  if (od, ad) != (OBS_DIM, ACT_DIM):
+    raise ValueError(f'{who}: a policy of observation width {od} and action width {ad}; the tabletop takes {OBS_DIM} and {ACT_DIM}')
 
 
 class PolicyPopulation:
@@ -176,6 +194,7 @@ class PolicyPopulation:
       if params is None:
         raise ValueError('PolicyPopulation: a template policy needs params [P, n_params]')
       template, members = policies, None
+      require_tabletop_widths(template, 'PolicyPopulation')
     else:
       members = list(policies)
       if not members or not all(isinstance(m, MLPPolicy) for m in members):
@@ -183,6 +202,8 @@ class PolicyPopulation:
       if params is not None:
         raise ValueError('PolicyPopulation: params= goes with ONE template policy, not with a list')
       template = members[0]
+      for m in members:
+        require_tabletop_widths(m, 'PolicyPopulation')
       for p, m in enumerate(members):
         for what in ('__class__', 'dims', 'hidden_act', 'out_act') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
           if getattr(m, what) != getattr(template, what):
@@ -283,6 +304,8 @@ class AgentPair:
     members = [forward, backward]
     if not all(isinstance(m, MLPPolicy) for m in members):
       raise ValueError('AgentPair: forward and backward are MLPPolicy / GaussianMLPPolicy')
+    for m in members:
+      require_tabletop_widths(m, 'AgentPair')
     template = forward
     for p, m in enumerate(members):
       for what in ('__class__', 'dims', 'hidden_act', 'out_act') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):

@@ -284,6 +284,36 @@ int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model
 int earl_sawyer_rollout_clocked(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                 const float* action, int32_t T, const uint64_t* clock, const earl_sawyer_out* out, earl_stream_t stream);
 
+/* ---- closed loop: an MLP policy evaluated INSIDE the Sawyer rollout kernel ----
+ * T closed-loop env steps of the door (nv = 10) or the peg (nv = 15) in ONE launch of the rollout kernel: between two env steps the 16 lanes that own an env evaluate
+ * the policy, observation -> float32 MLP 14 -> hidden (-> hidden) -> 4 -> action -> next env step.  earl_mlp_policy / earl_gaussian_head are earl_tabletop.h's, with
+ * dims[0] = 14 and dims[n_layers] = 4 (head = NULL) or 8 (head given: output rows 0..3 the mean, rows 4..7 the raw log_std); hidden widths multiples of 16 in 16..256;
+ * policy->params 16-byte aligned (the kernel reads the weight rows in 16-byte pieces).
+ * What the policy sees: at step 0 obs0 [n, 14] (device); at step t > 0 row t - 1 of THIS launch's out->obs exactly as emitted -- the repeated row of a rolled-back
+ * step and the goal block patched by a lifelong goal switch included -- each double rounded to float32.
+ * Arithmetic: the contract of earl_tabletop_policy_rollout (acc = b_j; k ascending: acc = fmaf(x_k, W_jk, acc); relu_f32, tanh_f32; the head's exp_f32,
+ * normal_quantile_f32, log_std maps and u = fmaf(exp_f32(ls), eps, mean): csrc/policy_math.h); earl_mlp_policy_forward_cpu below states it on the host.
+ * Draws of the head: ONE Philox4x32-10 block per (env, env step), key = cfg->seed, counter words {0x504F4C00, cfg->env_offset + env, ev lo, ev hi} with
+ * ev = cfg->step_counter + clock[1] + t (the value the goal-switch draw of that step uses; its draw index is 0xFFFE, the reset's are 0 .. 31, 0xFFF0 .. 0xFFF2 and
+ * 0xFFFF: the streams are disjoint); words x, y, z, w -> action dimensions 0 .. 3.  head->eps_out (may be NULL) is [T, n, 4] here, written in both modes.
+ * actions [T, n, 4] (device, required) receives the actions as the policy produced them; the launch is bit-identical to earl_sawyer_rollout_clocked fed with it:
+ * outputs, state left behind, counters.  clock as for earl_sawyer_rollout_clocked (may be NULL).
+ * EARL_ERR_ARG before any HIP call: NULL policy / obs0 / actions / out->obs, dims[0] != 14, a last layer that is not 4 (8 with a head) wide, hidden widths outside the
+ * rule, n_layers not 2 or 3, activations or head fields out of range (as earl_tabletop_policy_rollout_gaussian), precision != 0, misaligned params, T < 1, nv not 10 or
+ * 15, and everything earl_sawyer_rollout refuses.  The 64-lanes-per-env measurement builds (earl_debug_set_physics_lanes(64)) have no policy form: EARL_ERR_ARG. */
+int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
+                               const earl_sawyer_out* out, earl_stream_t stream);
+/* The policy contract on the host (libearl_host.so; host pointers): actions [n, A] of n observation rows obs [n, dims[0]], dims[0] in 1..256, hidden widths in 1..256,
+ * the last layer A wide (head = NULL) or 2 A wide (rows 0..A-1 the mean, A..2A-1 the raw log_std), A >= 1.  eps [n, A] = the standard-normal draws to use with a
+ * head in EARL_HEAD_SAMPLE mode; NULL (or EARL_HEAD_MEAN, or no head) evaluates the mean / the deterministic policy.  policy->out_act is applied last, as on the
+ * device.  The oracle of the in-kernel policies' actions; EARL_OK or EARL_ERR_ARG.  (Not the `_cpu` twin of a device entry point: there is none.) */
+int32_t earl_mlp_policy_forward_cpu(const earl_mlp_policy* policy, const earl_gaussian_head* head, int32_t n, const float* obs, const float* eps, float* actions);
+/* the contract's scalar functions as compiled into libearl_host.so (csrc/policy_math.h): tanh_f32, exp_f32 and normal_quantile_f32 of a 24-bit k = word >> 8 */
+float earl_tanh_f32(float x);
+float earl_exp_f32(float x);
+float earl_normal_quantile_f32(uint32_t k24);
+
 /* reset the envs with mask[i] != 0 (mask NULL = all): state <- the settled post-_reset_hand state (reset_qpos [nq], reset_qvel
  * [nv], device), object re-initialised as cfg.obj_kind says, mocap <- hand_init_pos, counters cleared; obs [n,14]
  * (may be NULL: the state, st.obj_init and st.last_obs are still written) is written for the reset envs only. */

@@ -138,7 +138,7 @@ typedef struct earl_mlp_policy {
  * (episodes * (T + 1) resp. T).
  * Policy arithmetic (a contract: libearl_host.so states it as plain loops and the device agrees bit for bit): every pre-activation is
  * acc = b_j; for k ascending: acc = fmaf(x_k, W_jk, acc) in float32; ReLU is acc > 0 ? acc : +0 (= fmaxf(acc, 0) with -0 -> +0, NaN -> 0);
- * tanh is this build's own tanh_f32 (csrc/tabletop_policy.h: fma, +, *, / and integer operations only, no libm). */
+ * tanh is this build's own tanh_f32 (csrc/policy_math.h: fma, +, *, / and integer operations only, no libm). */
 int earl_tabletop_policy_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, int32_t episodes, int32_t T,
                                  int32_t reset_first, const earl_tabletop_out* out, float* act_out, earl_stream_t stream);
 
@@ -161,7 +161,7 @@ typedef struct earl_gaussian_head {
  * receives out_act(u).  This replaces the closed loop of the reference's training scripts (agent.act(obs, sample=True) between env.step calls,
  * envs/tabletop_manipulation.py:128-138) in SAMPLE mode and of its evaluation scripts (sample=False) in MEAN mode, for the whole batch in ONE launch.
  * eps: one Philox4x32-10 block per (env, step), key = cfg->seed, counter words {0x504F4C00, env_offset + env, counter lo, counter hi} with the counter of that env
- * step; words x, y, z -> dimensions 0, 1, 2; k = word >> 8, u = (k + 0.5) 2^-24, eps = Phi^-1(u) within 5 float32 ulp (csrc/tabletop_policy.h states the
+ * step; words x, y, z -> dimensions 0, 1, 2; k = word >> 8, u = (k + 0.5) 2^-24, eps = Phi^-1(u) within 5 float32 ulp (csrc/policy_math.h states the
  * arithmetic).  The draws depend on (seed, global env id, counter) only: not on n, the shard split, episodes or mode, and they take no counter values of
  * their own -- everything earl_tabletop_policy_rollout promises carries over: reset_first / episodes rules, NULL-able outputs, argument errors before any HIP
  * call, Philox counter use (episodes * (T + 1) resp. T), and the launch is bit-identical to earl_tabletop_eval_episodes / earl_tabletop_rollout fed with

@@ -17,7 +17,8 @@ constexpr int kPolicyMaxWidth = 256;   // hidden widths: multiples of 16 in 16 .
 // ------------------------------------------------------------------------------------------------
 // tanh_f32: float32 in, float32 out, evaluated in fp64 out of fma, +, *, the correctly rounded / and integer operations only (no libm / ocml call), and
 // rounded to float32 ONCE -- host and device agree bit for bit, and the single rounding of a 1e-15-accurate value is what makes it odd, monotone over
-// every float32 and within 0.5 ulp (+ 1e-8) of tanh (tests/test_policy_rollout.py sweeps every float32 in 2^-12 <= |x| <= 16).
+// every float32 and within 0.5 ulp (+ 1e-8) of tanh (tests/test_policy_rollout.py sweeps every float32 in 2^-12 <= |x| <= 16 on the host;
+// tests/test_policy_math_gpu.py sweeps the same range on the device, in the tabletop units' context and under the stepper's contract(fast): device == host).
 //   |x| <  2^-6 : x + x z (-1/3 + z (2/15 + z (-17/315 + z 62/2835))), z = x^2                 (next term 1382/155925 z^5 < 1e-20 relative)
 //   |x| <  10   : t = exp(-2|x|) = 2^k e^r, k = round(-2|x| log2 e), r in two Cody-Waite steps, e^r by its Taylor series to r^12 / 12!
 //                 (|r| <= 0.35: remainder 3e-16); tanh = (1 - t) / (1 + t)
@@ -85,7 +86,9 @@ __host__ __device__ __forceinline__ float policy_act(float x, int kind) {
 //               TANH : ls = lo + (0.5f * (hi - lo)) * (tanh_f32(raw) + 1.0f), every operation rounded to float32 once
 //   action      MEAN: u = mean.  SAMPLE: u = fmaf(exp_f32(ls), eps, mean).  act = policy_act(u, out_act) (NONE or tanh_f32)
 // exp_f32 and normal_quantile_f32 are, like tanh_f32, made of fma / fmaf, +, *, the correctly rounded / and float32 sqrt and integer operations only (no
-// libm / ocml call): host and device agree bit for bit (tests/test_policy_gaussian.py sweeps all 2^24 quantile inputs and every float32 of [-20, 4]).
+// libm / ocml call): host and device agree bit for bit (tests/test_policy_gaussian.py sweeps all 2^24 quantile inputs and every float32 of [-20, 4] on the
+// host against double; tests/test_policy_math_gpu.py runs the same sweeps and 2^20 rows of gaussian_head_action per mode / map / bounds on the device in both
+// compile contexts and holds them to the host's bits).
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kGaussDraw = 0x504F4C00u;
 

@@ -11,6 +11,8 @@
 //   ReLU             acc > 0 ? acc : +0                                                     (= fmaxf(acc, 0) with -0 -> +0 and NaN -> 0 pinned)
 //   tanh             tanh_f32 (policy_math.h, with the Gaussian head's arithmetic)
 // On gfx950 the chain is v_mfma_f32_16x16x4_f32: per output element bit for bit a k-ordered fmaf chain, C input = the bias.  The host states the loops.
+// Held on the device by tests/test_policy_widths_gpu.py: every instantiation (NT2 x GENERAL x head x POP, and the pair's) and every hidden width 16 .. 256 at
+// every layer position against the host twin bit for bit, the wide shapes also against an exact integer reference (the lane maps).
 #pragma once
 #include "policy_math.h"
 #include "tabletop_hostside.h"

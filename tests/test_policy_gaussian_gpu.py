@@ -1,6 +1,7 @@
 """earl_tabletop_policy_rollout_gaussian on the MI355X: the GAUSS instantiations of csrc/tabletop_policy.h's kernel held to the host twin bit for bit -- the test of
 the lane = (env, dimension) hand-over through LDS, of the 6-column output tile and of the float32 sqrt and / of normal_quantile_f32 on the device -- and to the
-open-loop kernels."""
+open-loop kernels.
+The width and instantiation matrix of the GAUSS instantiations lives in tests/test_policy_widths_gpu.py; the head's scalar functions are swept in tests/test_policy_math_gpu.py."""
 import numpy as np
 import pytest
 import torch

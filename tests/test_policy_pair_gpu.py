@@ -1,6 +1,7 @@
 """earl_tabletop_pair_rollout on the MI355X: the pair kernel (csrc/tabletop_policy_pair.hip: both agents' weights in registers, the per-step ballot of the phase, the
 uniform and the mixed path) held to its host twin bit for bit on inputs that take all three paths, to the open-loop kernels, to itself across shards and split
-launches, and the Python surface on the device."""
+launches, and the Python surface on the device.
+The width matrix of the pair kernel (every width it takes, its 6 instantiations) lives in tests/test_policy_widths_gpu.py."""
 import numpy as np
 import pytest
 import torch

@@ -1,6 +1,7 @@
 """earl_tabletop_population_rollout on the MI355X: the population kernel (csrc/tabletop_policy.h with POP: workgroups aligned to global env ids, per-workgroup
 weights, summaries on the env lanes) held to its host twin bit for bit, to per-policy launches of the existing kernels, to the open-loop kernels, to itself
-across shards and with its outputs switched off, and the Python surface on the device."""
+across shards and with its outputs switched off, and the Python surface on the device.
+The width and instantiation matrix (all 20 population instantiations) lives in tests/test_policy_widths_gpu.py."""
 import numpy as np
 import pytest
 import torch

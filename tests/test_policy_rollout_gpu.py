@@ -1,5 +1,6 @@
 """earl_tabletop_policy_rollout on the MI355X: the kernel of csrc/tabletop_policy.h (v_mfma_f32_16x16x4_f32 beside the fp64 recurrence) held to its host
-twin bit for bit -- the test of the MFMA lane maps, of the k order of the accumulation and of tanh_f32 on the device -- and to the open-loop kernels."""
+twin bit for bit -- the test of the MFMA lane maps, of the k order of the accumulation and of tanh_f32 on the device -- and to the open-loop kernels.
+The width and instantiation matrix (every hidden width, every NT2 x GENERAL instantiation) lives in tests/test_policy_widths_gpu.py."""
 import numpy as np
 import pytest
 import torch

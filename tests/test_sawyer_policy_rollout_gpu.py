@@ -4,7 +4,9 @@ kernel, the policy evaluated by the lanes that own the env.
      (the eight-wave build), at a peg batch the time-sliced schedule takes, and under a LifelongWrapper whose goal switch fires inside the launch;
   6. the actions are the contract: every (t, env) action equals earl_mlp_policy_forward_cpu (libearl_host.so) on float32(obs[t - 1]) (obs0 for t = 0), bit for
      bit; a sampled head with the returned eps, and the eps equal to normal_quantile_f32 of the Philox words recomputed on the host;
-  7. one launch of T == T launches of one, and the draws depend on (seed, global env id, step counter) only."""
+  7. one launch of T == T launches of one, and the draws depend on (seed, global env id, step counter) only.
+
+The width matrix (every hidden width, partial groups of 64 output rows, the eight-wave build) lives in tests/test_sawyer_policy_widths_gpu.py."""
 
 import numpy as np
 import pytest

@@ -197,6 +197,9 @@ SIGNATURES = {
     # the closed loop inside the Sawyer rollout kernel: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
     'earl_sawyer_policy_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, _P(SawyerOut), C.c_void_p],
+    # ... for a population's member per env, with per-env episode summaries, every [T] output optional: pop after policy, summary after `out`
+    'earl_sawyer_population_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(MlpPolicy), _P(PolicyPopulation), _P(GaussianHead), C.c_void_p,
+                                       C.c_int32, C.c_void_p, C.c_void_p, _P(SawyerOut), _P(EpisodeSummary), C.c_void_p],
     'earl_minitaur_reset': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_minitaur_cfg_size': [],
     'earl_debug_set_minitaur_stepper': [C.c_int],

@@ -155,14 +155,16 @@ int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model
   return earl_sawyer_rollout_clocked(model, col, nv, cfg, st, action, T, nullptr, out, stream);
 }
 
-// include/earl_physics.h: T closed-loop env steps in one launch of the rollout kernel, the policy evaluated by the wave that owns the env.  The launch forms are
+// include/earl_physics.h: T closed-loop env steps in one launch of the rollout kernel, the policy evaluated by the wave that owns the env -- one policy or a
+// population's member per env, every [T] output optional, per-env episode summaries.  The launch forms are
 // earl_sawyer_rollout's (door: four one-wave workgroups per CU, eight waves per CU above 4096 envs; peg: whole rollouts or the time-sliced queue); the 64-lane
 // measurement builds (earl_debug_set_physics_lanes(64)) and the door's time-sliced measurement variant have no policy form
-int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
-                               const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
-                               const earl_sawyer_out* out, earl_stream_t stream) {
-  if (!model || !cfg || !st || !out || !policy || !obs0 || !actions || T < 1 || cfg->n < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !out->obs) return EARL_ERR_ARG;
+int earl_sawyer_population_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                   const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                                   const uint64_t* clock, float* actions, const earl_sawyer_out* out, const earl_episode_summary* summary, earl_stream_t stream) {
+  if (!model || !cfg || !st || !out || !policy || !obs0 || T < 1 || cfg->n < 0) return EARL_ERR_ARG;
+  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal) return EARL_ERR_ARG;
+  if (!out->obs && !st->last_obs) return EARL_ERR_ARG;    // (without out->obs the env's row of last_obs is the one observation row the launch keeps)
   if (nv != 10 && nv != 15) return EARL_ERR_ARG;
   if (!policy->params || ((uintptr_t)policy->params & 15) || policy->precision != 0) return EARL_ERR_ARG;      // (16-byte loads of the weight rows)
   if (policy->n_layers != 2 && policy->n_layers != 3) return EARL_ERR_ARG;
@@ -182,6 +184,14 @@ int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collisio
   if (cfg->n_goal_rows > 0 && !cfg->goal_table) return EARL_ERR_ARG;
   if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && (!st->obj_init || cfg->att_grasp < 0 || cfg->att_lpad < 0 || cfg->att_rpad < 0)) return EARL_ERR_ARG;
   if (nv == 15 && cfg->obj_kind >= 1 && out->info && !st->obj_init) return EARL_ERR_ARG;
+  if (pop) {
+    // the tabletop population's rules (include/earl_tabletop.h), and strides of whole 16-byte pieces: every member's rows are read as float4
+    int64_t count = 0;
+    for (int l = 0; l < policy->n_layers; ++l) count += (int64_t)policy->dims[l + 1] * (policy->dims[l] + 1);
+    if (pop->n_policies < 1 || pop->envs_per_policy < 16 || pop->envs_per_policy % 16 || pop->param_stride < count || pop->param_stride % 4) return EARL_ERR_ARG;
+    if (cfg->env_offset < 0) return EARL_ERR_ARG;
+    if (cfg->n > 0 && ((int64_t)cfg->env_offset + cfg->n - 1) / pop->envs_per_policy >= pop->n_policies) return EARL_ERR_ARG;
+  }
   if (g_lpe == 64) return EARL_ERR_ARG;                   // (the 64-lane measurement builds: no policy form)
   if (cfg->n == 0) return EARL_OK;
   if (int rc = check_cone(col, true, (hipStream_t)stream, "sawyer_policy_rollout")) return rc;
@@ -192,6 +202,11 @@ int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collisio
   a.gauss = head ? 1 : 0;
   a.obs0 = obs0;
   a.act_out = actions;
+  a.pop_G = pop ? pop->envs_per_policy : 0;
+  a.pop_stride = pop ? pop->param_stride : 0;
+  a.sum_ret = summary ? summary->ret : nullptr;
+  a.sum_last = summary ? summary->success_last : nullptr;
+  a.sum_first = summary ? summary->first_success : nullptr;
   if (nv == 10) {
     if (g_door_variant == 2 || (g_door_variant != 1 && cfg->n > 4096)) return earl_unit_w8_sawyer_policy_rollout(&a, stream);
     sawyer_policy_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
@@ -203,6 +218,13 @@ int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collisio
     } else sawyer_policy_rollout_kernel<15, 16><<<grid_for<15, 16>(cfg->n), block_for<15>(), 0, (hipStream_t)stream>>>(a);
   }
   return launched("sawyer_policy_rollout");
+}
+// one policy, every [T] row kept: the population entry point without a population and without a summary (the same launch, bit for bit)
+int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
+                               const earl_sawyer_out* out, earl_stream_t stream) {
+  if (!actions || !out || !out->obs) return EARL_ERR_ARG;
+  return earl_sawyer_population_rollout(model, col, nv, cfg, st, policy, nullptr, head, obs0, T, clock, actions, out, nullptr, stream);
 }
 
 int earl_sawyer_reset(const earl_link_model* model, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,

@@ -21,7 +21,13 @@ struct SawyerPolicyArgs : SawyerArgs {
   earl_gaussian_head head;       // read when gauss != 0
   int gauss;
   const double* obs0;            // [n, 14]: what the policy sees at step 0
-  float* act_out;                // [T, n, 4]: the actions as the policy produced them (the open-loop entry points fed with it walk through the same bits)
+  float* act_out;                // NULL or [T, n, 4]: the actions as the policy produced them (the open-loop entry points fed with it walk through the same bits)
+  // earl_sawyer_population_rollout (new fields go HERE, never into SawyerArgs: the plain kernels' argument and machine code stay what they were)
+  int pop_G;                     // envs per member of a population (0: one policy); the env with global id g reads its parameters at pol.params + (g / pop_G) pop_stride
+  int64_t pop_stride;            // floats between consecutive members (a multiple of 4: every member's rows are read in 16-byte pieces)
+  double* sum_ret;               // earl_episode_summary of the launch, each NULL or [n]: lane 0 of the env keeps its three words up to date in HBM after every env step
+  uint8_t* sum_last;             // (step 0 initialises them), so a time slice handed to another wave finds them where it finds qpos
+  int32_t* sum_first;
 };
 
 // Work queue of the time-sliced rollout (earl_sawyer_state.sched: progress[G] then lock[G], zero on entry).  An env group's state is in HBM after every env
@@ -318,7 +324,10 @@ __device__ __noinline__ float4 sawyer_policy_action(const uint64_t ka_bits, cons
   h[0] = (sub < 14 && live) ? (float)seen[sub] : 0.f;
 #pragma unroll
   for (int i = 1; i < 16; ++i) h[i] = 0.f;
+  // a population: the member of this env, from its GLOBAL id alone (a wave whose four envs belong to two members walks two sets of rows: correct, only slower)
+  const int pop_G = ka->pop_G;
   const float* w = ka->pol.params;
+  if (pop_G > 0) w += (size_t)(gid / (uint32_t)pop_G) * (size_t)ka->pop_stride;
   pol_layer<false>(w, w + (size_t)d1 * d0, d0, d1, hidden_act, sub, h);
   w += (size_t)d1 * (d0 + 1);
   if (n_layers == 3) {
@@ -344,7 +353,7 @@ __device__ __noinline__ float4 sawyer_policy_action(const uint64_t ka_bits, cons
     u = earl::policy_act(h[0], out_act);
   }
   float* act_out = ka->act_out;
-  if (sub < 4 && live) act_out[row * 4 + sub] = u;
+  if (sub < 4 && live && act_out) act_out[row * 4 + sub] = u;
   return float4{__shfl(u, 0, 16), __shfl(u, 1, 16), __shfl(u, 2, 16), __shfl(u, 3, 16)};
 }
 
@@ -356,7 +365,8 @@ __device__ __forceinline__ float4 sawyer_step_action(const A& a, const int t, co
     // patched), each double rounded to float32; at step 0 the caller's obs0.  Lane `sub` reads the element lane `sub` wrote (sawyer_emit, the rollback and the
     // goal switch all write element `sub` from lane `sub`), so inside a wave's run of env steps this is the lane's own store in program order; the first step of
     // a time slice reads a row another wave wrote, ordered by sched_release's release fence and sched_claim's acquire fence exactly as the qpos / qvel rows are.
-    const double* seen = t > 0 ? a.out.obs + ((size_t)(t - 1) * n + env) * 14 : nullptr;
+    // Without out.obs (earl_sawyer_population_rollout) the env's row of st.last_obs is the one observation row the launch keeps: written, patched and read like the row of out.obs.
+    const double* seen = t > 0 ? (a.out.obs ? a.out.obs + ((size_t)(t - 1) * n + env) * 14 : a.st.last_obs + (size_t)env * 14) : nullptr;
     const uint64_t ev = a.cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t;      // (read per step, like the goal switch's: see there)
     // (offset 0 of the kernel-argument segment is the kernel's one argument, the SawyerPolicyArgs: see sawyer_policy_rollout_kernel)
     const EARL_KARG void* ka = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();

@@ -70,11 +70,27 @@
     }
     RSTAMP(13);
     const size_t row = (size_t)t * n + env;
+    // where this step's observation row goes: row t of out.obs, or -- POLICY, out.obs == NULL (earl_sawyer_population_rollout) -- the env's row of st.last_obs, the one
+    // observation row such a launch keeps: emitted, re-emitted by the rollback (it then simply stays), patched by the goal switch and read by the policy of step t + 1,
+    // lane `sub` reading what lane `sub` wrote; across a time slice it travels under sched_release / sched_claim like qpos
+    // (POLICY only: the plain kernels keep their statements, and with them their machine code)
+    [[maybe_unused]] double* obs_row = nullptr;
+    [[maybe_unused]] bool carried = false;
+    [[maybe_unused]] float rew = 0.f;               // what out.reward / out.success hold or would hold for this step, for the episode summary
+    [[maybe_unused]] uint8_t suc = 0;
+    if constexpr (POLICY) {
+      carried = a.out.obs == nullptr;
+      obs_row = carried ? a.st.last_obs + (size_t)env * 14 : a.out.obs + row * 14;
+    }
     // failure guard (MuJoCo's mj_checkPos / mj_checkVel; metaworld's `except MujocoException` in SawyerXYZEnv.step [UPSTREAM]): an env whose
     // state went NaN or beyond EARL_BAD_VALUE is rolled back to its last stable state (the rows in HBM) and re-emits its last stable
     // observation with reward 0; its neighbours in the wavefront never see it (a group only reads its own LDS block)
     const bool bad_lane = (sub < NV && !(fabs(s.qp[sub]) < EARL_BAD_VALUE && fabs(s.qv[sub]) < EARL_BAD_VALUE)) || (sub < 4 && !(fabs(s.bq[sub]) < 2.0));
     const bool failed = group_any<LPE>(bad_lane, grp);
+    if constexpr (POLICY)
+      sawyer_emit<NV>(s, m, cfg, sub, live && !failed, a.st.goal + (size_t)env * 7, obs_row, &rew, &suc, a.st.obj_init ? a.st.obj_init + (size_t)env * 6 : nullptr,
+                      (double)act.w, nullptr, (NV >= 15 && a.out.info) ? a.out.info + row * EARL_SAWYER_INFO : nullptr);
+    else
     sawyer_emit<NV>(s, m, cfg, sub, live && !failed, a.st.goal + (size_t)env * 7, a.out.obs + row * 14, a.out.reward ? a.out.reward + row : nullptr,
                     a.out.success ? a.out.success + row : nullptr, a.st.obj_init ? a.st.obj_init + (size_t)env * 6 : nullptr, (double)act.w, nullptr,
                     (NV >= 15 && a.out.info) ? a.out.info + row * EARL_SAWYER_INFO : nullptr);
@@ -100,6 +116,13 @@
       load_state<NV>(s, m, a.st.qpos + (size_t)env * m.nq, a.st.qvel + (size_t)env * NV, sub);
       if (sub < 3) s.mocap[sub] = a.st.mocap_pos[(size_t)env * 3 + sub];
       if (live) {
+        if constexpr (POLICY) {
+          if (!carried) {          // (a carried row IS the last stable observation already; reward 0 and success 0 are written with the summary below)
+            const double* prev = t > 0 ? a.out.obs + ((size_t)(t - 1) * n + env) * 14 : (a.st.last_obs ? a.st.last_obs + (size_t)env * 14 : nullptr);
+            if (sub < 14) a.out.obs[row * 14 + sub] = prev ? prev[sub] : __builtin_nan("");
+          }
+          if (sub == 0 && a.st.fail_count) a.st.fail_count[env] += 1;
+        } else {
         const double* prev = t > 0 ? a.out.obs + ((size_t)(t - 1) * n + env) * 14 : (a.st.last_obs ? a.st.last_obs + (size_t)env * 14 : nullptr);
         if (sub < 14) a.out.obs[row * 14 + sub] = prev ? prev[sub] : __builtin_nan("");
         if (sub == 0) {
@@ -107,7 +130,30 @@
           if (a.out.success) a.out.success[row] = 0;
           if (a.st.fail_count) a.st.fail_count[env] += 1;
         }
+        }
         if (NV >= 15 && a.out.info && sub < EARL_SAWYER_INFO) a.out.info[row * EARL_SAWYER_INFO + sub] = 0.0;
+      }
+    }
+    if constexpr (POLICY) {
+      // reward and success of the step (a rolled-back step: 0 and 0) to their rows, and into the env's episode summary: each word is its definition applied to exactly
+      // these values.  The summary pointers are read through the kernel-argument segment here, where they are used (see sawyer_policy_action on why).
+      if (sub == 0 && live) {
+        const float r_t = failed ? 0.f : rew;
+        const uint8_t s_t = failed ? (uint8_t)0 : suc;
+        if (a.out.reward) a.out.reward[row] = r_t;
+        if (a.out.success) a.out.success[row] = s_t;
+        const EARL_KARG void* kp = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kp));
+        const EARL_KARG SawyerPolicyArgs* ka = (const EARL_KARG SawyerPolicyArgs*)kp;
+        double* const sum_ret = ka->sum_ret;
+        uint8_t* const sum_last = ka->sum_last;
+        int32_t* const sum_first = ka->sum_first;
+        if (sum_ret) sum_ret[env] = (t > 0 ? sum_ret[env] : 0.0) + (double)r_t;      // sum over t ascending of (double)reward_t
+        if (sum_last) sum_last[env] = s_t;                                               // (the one of step T - 1 stays)
+        if (sum_first) {
+          const int32_t f = t > 0 ? sum_first[env] : -1;
+          sum_first[env] = (f < 0 && s_t) ? t : f;
+        }
       }
     }
     fence();
@@ -138,13 +184,17 @@
           if (sub == 11) a.out.info[row * EARL_SAWYER_INFO + 7] = 1.0;
         }
         a.st.goal[(size_t)env * 7 + (sub - 7)] = gv;
-        a.out.obs[row * 14 + sub] = gv;
+        if constexpr (POLICY) obs_row[sub] = gv;
+        else a.out.obs[row * 14 + sub] = gv;
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");      // the next step's observation reads the goal row back through global memory
     }
   }
   if (live) {
     // (qpos / qvel / mocap_pos were written back after the last stable step)
+    if constexpr (POLICY) {      // (a carried row is in place)
+      if (t_end == a.T && a.st.last_obs && a.out.obs && a.T > 0 && sub < 14) a.st.last_obs[(size_t)env * 14 + sub] = a.out.obs[((size_t)(a.T - 1) * n + env) * 14 + sub];
+    } else
     if (t_end == a.T && a.st.last_obs && a.T > 0 && sub < 14) a.st.last_obs[(size_t)env * 14 + sub] = a.out.obs[((size_t)(a.T - 1) * n + env) * 14 + sub];
     if (sub == 0 && a.st.steps_since_reset) a.st.steps_since_reset[env] = steps;
     if (sub == 0 && gcf > 0) a.st.steps_since_goal_change[env] = sgc;

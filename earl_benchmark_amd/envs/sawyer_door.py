@@ -217,23 +217,26 @@ class SawyerDoor:
     self._last_success = out['success'][-1] if out['success'].dim() == 2 else out['success']
     self._last_obs_stale = False                           # (every env's last_obs row was rewritten)
 
-  def _issue_rollout(self, actions, T, out, clock=None, policy=None):
+  def _issue_rollout(self, actions, T, out, clock=None, policy=None, summary=None):
     """the launches of T env steps into `out` (the door's info launch included); clock: the device words of earl_sawyer_rollout_clocked (None: earl_sawyer_rollout);
-    policy: None, or (policy, head struct or None, obs0) -- earl_sawyer_policy_rollout computes the actions itself and leaves them in out['actions']"""
+    policy: None, or (policy or population, head struct or None, obs0) -- earl_sawyer_population_rollout computes the actions itself and leaves them in
+    out['actions']; then `out` may lack any key, 'obs' included (the env's row of last_obs carries the observation), and summary is None or an _abi.EpisodeSummary"""
     info = out.get('info')
     in_kernel = info is not None and self.nv >= 15        # the peg's dict needs simulator state: the rollout kernel's epilogue writes it
     # door, lifelong goal switching: the kernel leaves the PRE-switch target on goal-switch rows (slots 0-2, marker in slot 7) for earl_sawyer_door_info
     stash = info is not None and self.nv < 15 and bool(self._cfg.goal_change_frequency)
-    o = _abi.SawyerOut(obs=out['obs'].data_ptr(), reward=_ptr(out.get('reward')), done=_ptr(out.get('done')),
+    o = _abi.SawyerOut(obs=_ptr(out.get('obs')), reward=_ptr(out.get('reward')), done=_ptr(out.get('done')),
                        success=_ptr(out.get('success')), status=_ptr(out.get('status')), info=_ptr(info) if (in_kernel or stash) else None)
     with torch.cuda.device(self.device):
       if self.sched is not None and T > 1 and self._uses_queue(T):
         self.sched.zero_()                                 # (the queue of the time-sliced schedule: zero on entry)
       if policy is not None:
         pi, head, obs0 = policy
-        _abi.check(self._lib.earl_sawyer_policy_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pi.struct),
-                                                        None if head is None else C.byref(head), obs0.data_ptr(), T, clock, out['actions'].data_ptr(), C.byref(o),
-                                                        self._stream()), 'earl_sawyer_policy_rollout')
+        pop = getattr(pi, 'pop_struct', None)             # a PolicyPopulation: the env with global id g runs member g // envs_per_policy
+        _abi.check(self._lib.earl_sawyer_population_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pi.struct),
+                                                            None if pop is None else C.byref(pop), None if head is None else C.byref(head), obs0.data_ptr(), T, clock,
+                                                            _ptr(out.get('actions')), C.byref(o), None if summary is None else C.byref(summary), self._stream()),
+                   'earl_sawyer_population_rollout')
       elif clock is None:
         _abi.check(self._lib.earl_sawyer_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, actions.data_ptr(),
                                                  T, C.byref(o), self._stream()), 'earl_sawyer_rollout')
@@ -347,25 +350,34 @@ class SawyerDoor:
     self._launch_rollout(self._actions(a, (T,)), T, out)
     return out
 
+  def _check_policy(self, policy, who):
+    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy / PolicyPopulation of this env's widths on this env's device"""
+    from ..policy import GaussianMLPPolicy, MLPPolicy, PolicyPopulation
+    population = isinstance(policy, PolicyPopulation)
+    if not population and not isinstance(policy, MLPPolicy):
+      raise ValueError(f'{who}: an MLPPolicy, a GaussianMLPPolicy or a PolicyPopulation of them (agent pairs are tabletop only)')
+    if (policy.obs_dim, policy.act_dim) != (self.OBS_DIM, 4):
+      raise ValueError(f'{who}: a policy of observation width {policy.obs_dim} and action width {policy.act_dim}; this env takes {self.OBS_DIM} and 4 '
+                       '(MLPPolicy(..., obs_dim=14, act_dim=4))')
+    if policy.device != self.device:
+      raise ValueError(f'{who}: the policy is on {policy.device}, the env on {self.device} (policy.to(device))')
+    if population:
+      lo, hi = int(self._cfg.env_offset), int(self._cfg.env_offset) + self.num_envs - 1
+      if lo < 0 or hi // policy.envs_per_policy >= policy.n_policies:
+        raise ValueError(f'{who}: global env ids {lo} .. {hi} need members up to {hi // policy.envs_per_policy} of {policy.n_policies}')
+    return policy.gaussian if population else isinstance(policy, GaussianMLPPolicy)
+
   def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """Closed loop in ONE launch of the rollout kernel (include/earl_physics.h: earl_sawyer_policy_rollout): `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy`
-    built with obs_dim=14, act_dim=4 -- is evaluated between the env steps by the lanes that own the env: observation -> float32 MLP -> action -> env step.
+    """Closed loop in ONE launch of the rollout kernel (include/earl_physics.h: earl_sawyer_population_rollout): `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy`
+    built with obs_dim=14, act_dim=4, or a `PolicyPopulation` of them (the env with global id g runs member g // envs_per_policy; same returns) -- is evaluated between the env steps by the lanes that own the env: observation -> float32 MLP -> action -> env step.
     -> rollout()'s dict plus 'actions' [T, N, 4] float32 (as the policy produced them) and, with return_noise=True, 'eps' [T, N, 4] (the standard-normal draws as
     used).  Bit-identical to rollout(out['actions']) from the same state.  The first action is computed from the observation the env last returned (`last_obs`: the row
     the previous step / rollout / reset emitted, so T launches of one step equal one launch of T); after set_state() or reset_goal() from _get_obs() of the
     current state and goal.  reset_first=True calls reset() before (a launch of its own).  A Gaussian policy is sampled inside the kernel (sample=True: tanh(mean + exp(log_std) eps), eps from the env's Philox
     stream keyed by seed, global env id and step counter) or evaluated at its mean (sample=False); both flags are for Gaussian policies only."""
-    from ..policy import GaussianMLPPolicy, MLPPolicy
-    if not isinstance(policy, MLPPolicy):
-      raise ValueError('rollout_policy: an MLPPolicy or a GaussianMLPPolicy (populations and agent pairs are tabletop only)')
-    gaussian = isinstance(policy, GaussianMLPPolicy)
+    gaussian = self._check_policy(policy, 'rollout_policy')
     if not gaussian and (return_noise or not sample):
       raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
-    if (policy.obs_dim, policy.act_dim) != (self.OBS_DIM, 4):
-      raise ValueError(f'rollout_policy: a policy of observation width {policy.obs_dim} and action width {policy.act_dim}; this env takes {self.OBS_DIM} and 4 '
-                       '(MLPPolicy(..., obs_dim=14, act_dim=4))')
-    if policy.device != self.device:
-      raise ValueError(f'rollout_policy: the policy is on {policy.device}, the env on {self.device} (policy.to(device))')
     T = int(T)
     if T < 1:
       raise ValueError(f'rollout_policy: T = {T} < 1')
@@ -383,6 +395,44 @@ class SawyerDoor:
     head = policy.head(sample=bool(sample), eps_out=out['eps'] if return_noise else None) if gaussian else None
     self._launch_rollout(None, T, out, policy=(policy, head, obs0))
     return out
+
+  def evaluate_policy(self, policy, T, episodes=1, sample=False, reset_first=True):
+    """`episodes` evaluation episodes of `policy` -- an MLPPolicy, a GaussianMLPPolicy (sample=False: at its mean) or a `PolicyPopulation` -- each a reset() launch plus ONE
+    launch of the rollout kernel that writes only per-env summaries (include/earl_physics.h: earl_sawyer_population_rollout with `actions` and every `out` pointer NULL;
+    the env's row of last_obs carries the observation from step to step): no tensor with a T axis is allocated.
+    -> {'ret': [E, N] float64 undiscounted return (the float32 step rewards summed in float64, t ascending), 'success': [E, N] bool success at the last step,
+        'first_success': [E, N] int32 first successful step, -1 if none, 'guard_steps': [E, N] int32 env steps the failure guard rolled back (the growth of fail_count over
+        the episode: such steps count with reward 0 and no success, and a summary must not hide them)}; the first three equal their definitions applied to what
+    rollout_policy would have returned.  reset_first=False: one episode that continues from the current state.  State and bookkeeping end as after rollout_policy."""
+    gaussian = self._check_policy(policy, 'evaluate_policy')
+    if sample and not gaussian:
+      raise ValueError('evaluate_policy: sample=True needs a Gaussian policy (an MLPPolicy is deterministic)')
+    E, T, n = int(episodes), int(T), self.num_envs
+    if T < 1 or E < 1:
+      raise ValueError(f'evaluate_policy: T = {T}, episodes = {E}: both >= 1')
+    if not reset_first and E != 1:
+      raise ValueError('evaluate_policy: a continuing evaluation (reset_first=False) is one episode')
+    kw = dict(device=self.device)
+    ret = torch.empty(E, n, dtype=torch.float64, **kw)
+    succ = torch.empty(E, n, dtype=torch.bool, **kw)
+    first = torch.empty(E, n, dtype=torch.int32, **kw)
+    guard = torch.empty(E, n, dtype=torch.int32, **kw)
+    for e in range(E):
+      if reset_first:
+        self.reset()
+      before = self.fail_count.clone()
+      obs0 = self._get_obs_t() if self._last_obs_stale else self.last_obs
+      head = policy.head(sample=bool(sample), eps_out=None) if gaussian else None
+      summary = _abi.EpisodeSummary(ret=ret[e].data_ptr(), success_last=succ[e].data_ptr(), first_success=first[e].data_ptr())
+      self._cfg.step_counter = self.total_step_count
+      self._issue_rollout(None, T, {}, policy=(policy, head, obs0), summary=summary)
+      self.total_step_count += T
+      if self._cfg.goal_change_frequency:
+        self.lifelong_return_t += ret[e]
+      self._last_success = succ[e]
+      self._last_obs_stale = False                         # (every env's last_obs row was rewritten)
+      guard[e] = self.fail_count - before
+    return {'ret': ret, 'success': succ, 'first_success': first, 'guard_steps': guard}
 
   def _get_obs_t(self):
     obs = torch.empty(self.num_envs, self.OBS_DIM, dtype=torch.float64, device=self.device)

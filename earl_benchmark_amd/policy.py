@@ -29,6 +29,12 @@ with global id g runs member g // envs_per_policy, all in one launch, and `evalu
   fitness = sharding.population_fitness(s, env_offset, pop.envs_per_policy, pop.n_policies)           # [P, 3]: return sum, success count, rows -- additive over shards
   pop.params.add_(sigma * noise)                                                                      # [P, stride], read by the next launch as it is
 
+The Sawyer door and peg take populations of 14 / 4 members (include/earl_physics.h: earl_sawyer_population_rollout), one episode per launch:
+
+  pop = PolicyPopulation([pi_0, ..., pi_511], envs_per_policy=16, device='cuda', obs_dim=14, act_dim=4)
+  out = door.rollout_policy(pop, T=300)                                                               # what it returns for one policy
+  s = door.evaluate_policy(pop, T=300, episodes=4)                                                    # the tabletop's dict plus 'guard_steps' [4, N] int32; no [T] tensor
+
 `AgentPair` is the forward / reset agent pair of autonomous RL for earl_tabletop_pair_rollout: two networks of ONE architecture that hand every env to each other
 after a fixed number of steps or as soon as the acting agent has succeeded, inside one launch.
 
@@ -173,20 +179,29 @@ class GaussianMLPPolicy(MLPPolicy):
     return torch.tanh(u) if self.squash else u
 
 
-def require_tabletop_widths(policy, who):
-  """the tabletop kernels (and the population / pair containers built for them) take 12 -> .. -> 3 networks only"""
+def require_widths(policy, who, obs_dim, act_dim):
+  """a container or a launch of declared widths takes networks of those widths only (the tabletop's 12 -> .. -> 3 unless said otherwise)"""
   od, ad = getattr(policy, 'obs_dim', OBS_DIM), getattr(policy, 'act_dim', ACT_DIM)
-  if (od, ad) != (OBS_DIM, ACT_DIM):
-    raise ValueError(f'{who}: a policy of observation width {od} and action width {ad}; the tabletop takes {OBS_DIM} and {ACT_DIM}')
+  if (od, ad) != (obs_dim, act_dim):
+    takes = f'the tabletop takes {OBS_DIM} and {ACT_DIM}' if (obs_dim, act_dim) == (OBS_DIM, ACT_DIM) else f'{obs_dim} and {act_dim} were declared'
+    raise ValueError(f'{who}: a policy of observation width {od} and action width {ad}; {takes}')
+
+
+def require_tabletop_widths(policy, who):
+  """the tabletop kernels (and the pair container built for them) take 12 -> .. -> 3 networks only"""
+  require_widths(policy, who, OBS_DIM, ACT_DIM)
 
 
 class PolicyPopulation:
   """P members of one architecture behind struct earl_policy_population: `policies` is a list of MLPPolicy or of GaussianMLPPolicy (same dims, activations and,
   for the Gaussian head, squash / bounds / map -- only the parameters differ), or ONE template policy with `params` [P, n_params] (n_params <= the row length:
   a wider row is the stride).  The env with GLOBAL id g runs member g // envs_per_policy (a multiple of 16: a member owns whole 16-env workgroups of the kernel).
-  `.params` [P, stride] float32 holds every member in MLPPolicy's packing order (W0, b0, W1, b1, ...) and is what the kernel reads: write into it in place."""
+  `.params` [P, stride] float32 holds every member in MLPPolicy's packing order (W0, b0, W1, b1, ...) and is what the kernel reads: write into it in place.
+  obs_dim / act_dim: the members' widths -- the tabletop's 12 / 3 by default, as MLPPolicy's; 14 / 4 for the Sawyer door and peg (earl_sawyer_population_rollout,
+  whose rows are then padded to a stride of whole 16-byte pieces)."""
 
-  def __init__(self, policies, envs_per_policy=16, device=None, params=None):
+  def __init__(self, policies, envs_per_policy=16, device=None, params=None, obs_dim=OBS_DIM, act_dim=ACT_DIM):
+    self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
     G = int(envs_per_policy)
     if G < 16 or G % 16:
       raise ValueError(f'PolicyPopulation: envs_per_policy = {envs_per_policy}: a multiple of 16, >= 16')
@@ -194,7 +209,7 @@ class PolicyPopulation:
       if params is None:
         raise ValueError('PolicyPopulation: a template policy needs params [P, n_params]')
       template, members = policies, None
-      require_tabletop_widths(template, 'PolicyPopulation')
+      require_widths(template, 'PolicyPopulation', self.obs_dim, self.act_dim)
     else:
       members = list(policies)
       if not members or not all(isinstance(m, MLPPolicy) for m in members):
@@ -203,7 +218,7 @@ class PolicyPopulation:
         raise ValueError('PolicyPopulation: params= goes with ONE template policy, not with a list')
       template = members[0]
       for m in members:
-        require_tabletop_widths(m, 'PolicyPopulation')
+        require_widths(m, 'PolicyPopulation', self.obs_dim, self.act_dim)
       for p, m in enumerate(members):
         for what in ('__class__', 'dims', 'hidden_act', 'out_act') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
           if getattr(m, what) != getattr(template, what):
@@ -220,6 +235,8 @@ class PolicyPopulation:
       if host.dim() != 2 or host.shape[0] < 1 or host.shape[1] < self.n_params:
         raise ValueError(f'PolicyPopulation: params {tuple(host.shape)}: [P, >= {self.n_params}] (one row per member, packed like MLPPolicy.params)')
     self.n_policies = int(host.shape[0])
+    if (self.obs_dim, self.act_dim) != (OBS_DIM, ACT_DIM) and host.shape[1] % 4:      # (the Sawyer kernel reads every member's rows in 16-byte pieces)
+      host = torch.nn.functional.pad(host, (0, -host.shape[1] % 4))
     self.params = host.clone().contiguous()
     self.to(template.device if device is None else device)
 
@@ -257,8 +274,9 @@ class PolicyPopulation:
     layers = [(w.clone(), b.clone()) for w, b in self._layers_of(self.params[int(p)].detach().cpu())]
     t = self.template
     if self.gaussian:
-      return GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, device=self.device)
-    return MLPPolicy(layers, t.hidden_act, t.out_act, device=self.device)
+      return GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, device=self.device,
+                               obs_dim=self.obs_dim, act_dim=self.act_dim)
+    return MLPPolicy(layers, t.hidden_act, t.out_act, device=self.device, obs_dim=self.obs_dim, act_dim=self.act_dim)
 
   def policy_index(self, global_ids):
     """the member each GLOBAL env id runs"""
@@ -266,7 +284,7 @@ class PolicyPopulation:
     return torch.div(g, self.envs_per_policy, rounding_mode='floor')
 
   def __call__(self, obs, env_offset=0):
-    """obs [..., N, 12] of the envs with global ids env_offset .. env_offset + N - 1 -> actions [..., N, 3] (a Gaussian population: at the mean), every env
+    """obs [..., N, obs_dim] of the envs with global ids env_offset .. env_offset + N - 1 -> actions [..., N, act_dim] (a Gaussian population: at the mean), every env
     through its own member: one batched matmul per layer over the members present (torch's summation order: close to the kernel, not bit-identical)"""
     x = obs.to(torch.float32)
     lead, N, G = x.shape[:-2], int(x.shape[-2]), self.envs_per_policy
@@ -285,11 +303,12 @@ class PolicyPopulation:
       h = torch.baddbmm(b[:, None, :], h, w.transpose(1, 2))
       if l + 1 < len(layers):
         h = torch.relu(h) if self.hidden_act == 'relu' else torch.tanh(h)
-    h = h[..., :ACT_DIM]
+    A = self.act_dim
+    h = h[..., :A]
     if self.out_act == 'tanh':
       h = torch.tanh(h)
-    out = h.reshape(M, L, G, ACT_DIM).permute(1, 0, 2, 3).reshape(L, M * G, ACT_DIM)[:, slot]
-    return out.reshape(*lead, N, ACT_DIM)
+    out = h.reshape(M, L, G, A).permute(1, 0, 2, 3).reshape(L, M * G, A)[:, slot]
+    return out.reshape(*lead, N, A)
 
 
 class AgentPair:

@@ -304,6 +304,27 @@ int earl_sawyer_rollout_clocked(const earl_link_model* model, const earl_collisi
 int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
                                const earl_sawyer_out* out, earl_stream_t stream);
+/* ---- the same closed loop for a POPULATION of policies, with per-env episode summaries and without any [T] array ----
+ * earl_policy_population / earl_episode_summary are earl_tabletop.h's, as they are.  One episode per launch: the summary rows are [n].
+ *   pop      NULL = one policy: bit-identical to earl_sawyer_policy_rollout, which is this call with pop = summary = NULL.  Otherwise the env with GLOBAL id
+ *            g = cfg->env_offset + i runs member g / G, whose parameters start at policy->params + (g / G) * param_stride.  The member depends on the global id only:
+ *            env_offset need not be a multiple of 4, 16 or G, and a wavefront whose four envs belong to two members is correct, only slower.  The launch is
+ *            bit-identical to cutting the batch at the global ids that are multiples of G and running the single-policy entry point on each piece (env_offset = its
+ *            first global id, n = its length, the matching state rows) with that member's parameters: outputs, actions, eps_out, state, fail_count, counters.
+ *   summary  NULL, or: ret = sum over t ascending of (double)reward_t; success_last = the success flag of step T - 1; first_success = the smallest t with success,
+ *            or -1.  Each is exactly its definition applied to what out->reward / out->success hold or would hold, rolled-back rows (reward 0, success 0)
+ *            included.  The env's lane 0 keeps the three words up to date in device memory after every env step (step 0 initialises them), so a time slice of
+ *            the peg's schedule that another wavefront takes finds them where it finds qpos.
+ *   actions and every pointer of `out`, out->obs included, may be NULL (`out` itself may not).  With out->obs == NULL the env's row of st->last_obs (then
+ *            required) is the one observation row the launch keeps: every emitted row, the rollback's re-emission and the goal switch's patch are written to it, and
+ *            the policy of step t + 1 reads it (lane by lane what that lane wrote; across a time slice under the release / acquire that carries qpos).  The state
+ *            left behind, last_obs included, equals the full launch's.
+ * EARL_ERR_ARG before any HIP call: everything earl_sawyer_policy_rollout refuses (but NULL actions / out->obs), and G % 16 != 0, G < 16, P < 1, param_stride below
+ * the parameter count, param_stride % 4 != 0 (every member's rows are read in 16-byte pieces), env_offset < 0 with pop, (env_offset + n - 1) / G >= P,
+ * out->obs == NULL with st->last_obs == NULL. */
+int earl_sawyer_population_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                   const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                                   const uint64_t* clock, float* actions, const earl_sawyer_out* out, const earl_episode_summary* summary, earl_stream_t stream);
 /* The policy contract on the host (libearl_host.so; host pointers): actions [n, A] of n observation rows obs [n, dims[0]], dims[0] in 1..256, hidden widths in 1..256,
  * the last layer A wide (head = NULL) or 2 A wide (rows 0..A-1 the mean, A..2A-1 the raw log_std), A >= 1.  eps [n, A] = the standard-normal draws to use with a
  * head in EARL_HEAD_SAMPLE mode; NULL (or EARL_HEAD_MEAN, or no head) evaluates the mean / the deterministic policy.  policy->out_act is applied last, as on the

@@ -200,6 +200,9 @@ SIGNATURES = {
     # ... for a population's member per env, with per-env episode summaries, every [T] output optional: pop after policy, summary after `out`
     'earl_sawyer_population_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(MlpPolicy), _P(PolicyPopulation), _P(GaussianHead), C.c_void_p,
                                        C.c_int32, C.c_void_p, C.c_void_p, _P(SawyerOut), _P(EpisodeSummary), C.c_void_p],
+    # ... for the forward / reset agent pair: pair after policy (backward_goal a row of 7, agent_out [T, n], the counters [n])
+    'earl_sawyer_pair_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(MlpPolicy), _P(AgentPair), _P(GaussianHead), C.c_void_p,
+                                 C.c_int32, C.c_void_p, C.c_void_p, _P(SawyerOut), C.c_void_p],
     'earl_minitaur_reset': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_minitaur_cfg_size': [],
     'earl_debug_set_minitaur_stepper': [C.c_int],

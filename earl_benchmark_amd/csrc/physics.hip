@@ -159,9 +159,11 @@ int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model
 // population's member per env, every [T] output optional, per-env episode summaries.  The launch forms are
 // earl_sawyer_rollout's (door: four one-wave workgroups per CU, eight waves per CU above 4096 envs; peg: whole rollouts or the time-sliced queue); the 64-lane
 // measurement builds (earl_debug_set_physics_lanes(64)) and the door's time-sliced measurement variant have no policy form
-int earl_sawyer_population_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
-                                   const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
-                                   const uint64_t* clock, float* actions, const earl_sawyer_out* out, const earl_episode_summary* summary, earl_stream_t stream) {
+// (the body of the closed-loop entry points: a population with summaries, or an agent pair -- never both)
+static int sawyer_closed_loop(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                              const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_agent_pair* pair, bool paired, const earl_gaussian_head* head,
+                              const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_sawyer_out* out, const earl_episode_summary* summary,
+                              earl_stream_t stream) {
   if (!model || !cfg || !st || !out || !policy || !obs0 || T < 1 || cfg->n < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal) return EARL_ERR_ARG;
   if (!out->obs && !st->last_obs) return EARL_ERR_ARG;    // (without out->obs the env's row of last_obs is the one observation row the launch keeps)
@@ -192,6 +194,17 @@ int earl_sawyer_population_rollout(const earl_link_model* model, const earl_coll
     if (cfg->env_offset < 0) return EARL_ERR_ARG;
     if (cfg->n > 0 && ((int64_t)cfg->env_offset + cfg->n - 1) / pop->envs_per_policy >= pop->n_policies) return EARL_ERR_ARG;
   }
+  if (paired) {
+    // include/earl_physics.h, earl_sawyer_pair_rollout: the tabletop pair's rules, the population's stride rule, and a backward goal only where the forward one can be restored
+    int64_t count = 0;
+    for (int l = 0; l < policy->n_layers; ++l) count += (int64_t)policy->dims[l + 1] * (policy->dims[l] + 1);
+    if (!pair || !pair->phase || !pair->steps_in_phase) return EARL_ERR_ARG;
+    if (pair->switch_every[0] < 1 || pair->switch_every[1] < 1) return EARL_ERR_ARG;
+    if (pair->switch_on_success != 0 && pair->switch_on_success != 1) return EARL_ERR_ARG;
+    if (pair->param_stride < count || pair->param_stride % 4) return EARL_ERR_ARG;
+    if (cfg->goal_change_frequency > 0) return EARL_ERR_ARG;               // (the pair IS the lifelong mechanism)
+    if (pair->backward_goal && cfg->n_goal_rows == 0) return EARL_ERR_ARG;   // (the forward goal could not be restored)
+  }
   if (g_lpe == 64) return EARL_ERR_ARG;                   // (the 64-lane measurement builds: no policy form)
   if (cfg->n == 0) return EARL_OK;
   if (int rc = check_cone(col, true, (hipStream_t)stream, "sawyer_policy_rollout")) return rc;
@@ -207,6 +220,16 @@ int earl_sawyer_population_rollout(const earl_link_model* model, const earl_coll
   a.sum_ret = summary ? summary->ret : nullptr;
   a.sum_last = summary ? summary->success_last : nullptr;
   a.sum_first = summary ? summary->first_success : nullptr;
+  a.pair_phase = paired ? pair->phase : nullptr;
+  a.pair_sip = paired ? pair->steps_in_phase : nullptr;
+  a.pair_stride = paired ? pair->param_stride : 0;
+  a.pair_goal = paired ? pair->backward_goal : nullptr;
+  a.pair_se[0] = paired ? pair->switch_every[0] : 0;
+  a.pair_se[1] = paired ? pair->switch_every[1] : 0;
+  a.pair_sos = paired ? pair->switch_on_success : 0;
+  a.pair_agent = paired ? pair->agent_out : nullptr;
+  a.pair_fs = paired ? pair->forward_success : nullptr;
+  a.pair_bs = paired ? pair->backward_success : nullptr;
   if (nv == 10) {
     if (g_door_variant == 2 || (g_door_variant != 1 && cfg->n > 4096)) return earl_unit_w8_sawyer_policy_rollout(&a, stream);
     sawyer_policy_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
@@ -218,6 +241,17 @@ int earl_sawyer_population_rollout(const earl_link_model* model, const earl_coll
     } else sawyer_policy_rollout_kernel<15, 16><<<grid_for<15, 16>(cfg->n), block_for<15>(), 0, (hipStream_t)stream>>>(a);
   }
   return launched("sawyer_policy_rollout");
+}
+int earl_sawyer_population_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                   const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                                   const uint64_t* clock, float* actions, const earl_sawyer_out* out, const earl_episode_summary* summary, earl_stream_t stream) {
+  return sawyer_closed_loop(model, col, nv, cfg, st, policy, pop, nullptr, false, head, obs0, T, clock, actions, out, summary, stream);
+}
+// the forward / reset agent pair: the same launch with the phase state machine switched on (no population, no summary)
+int earl_sawyer_pair_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                             const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                             const uint64_t* clock, float* actions, const earl_sawyer_out* out, earl_stream_t stream) {
+  return sawyer_closed_loop(model, col, nv, cfg, st, policy, nullptr, pair, true, head, obs0, T, clock, actions, out, nullptr, stream);
 }
 // one policy, every [T] row kept: the population entry point without a population and without a summary (the same launch, bit for bit)
 int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,

@@ -28,6 +28,17 @@ struct SawyerPolicyArgs : SawyerArgs {
   double* sum_ret;               // earl_episode_summary of the launch, each NULL or [n]: lane 0 of the env keeps its three words up to date in HBM after every env step
   uint8_t* sum_last;             // (step 0 initialises them), so a time slice handed to another wave finds them where it finds qpos
   int32_t* sum_first;
+  // earl_sawyer_pair_rollout: the forward / reset agent pair (pair_phase == NULL: no pair, and nothing below is read).  The env's phase word travels through HBM like the
+  // summary words: lane 0 stores it after the handover decision, an agent-scope fence follows, and all 16 lanes read it back where the next action is computed
+  int8_t* pair_phase;            // [n] 0 forward, anything else reset; the network of the phase starts at pol.params + phase * pair_stride
+  int32_t* pair_sip;             // [n] steps the env has spent in its phase
+  int64_t pair_stride;           // floats between the two agents' rows (a multiple of 4)
+  const double* pair_goal;       // NULL or the ONE row of 7 doubles that becomes the env's st.goal row on entering the reset phase
+  int pair_se[2];                // switch_every
+  int pair_sos;                  // switch_on_success
+  int8_t* pair_agent;            // NULL or [T, n]
+  int32_t* pair_fs;              // NULL or [n]: forward phases that ended by success (step 0 of the launch starts them at 0)
+  int32_t* pair_bs;              // NULL or [n]: reset phases that ended by success
 };
 
 // Work queue of the time-sliced rollout (earl_sawyer_state.sched: progress[G] then lock[G], zero on entry).  An env group's state is in HBM after every env
@@ -328,6 +339,15 @@ __device__ __noinline__ float4 sawyer_policy_action(const uint64_t ka_bits, cons
   const int pop_G = ka->pop_G;
   const float* w = ka->pol.params;
   if (pop_G > 0) w += (size_t)(gid / (uint32_t)pop_G) * (size_t)ka->pop_stride;
+  // an agent pair: the network of the env's phase, the word lane 0 stored after the last handover decision (a wave whose four envs are in two phases walks two sets
+  // of rows, like a wave of two members)
+  const int8_t* pair_phase = ka->pair_phase;
+  if (pair_phase) {
+    const int ph = pair_phase[env] != 0 ? 1 : 0;
+    if (ph) w += (size_t)ka->pair_stride;
+    int8_t* agent_out = ka->pair_agent;
+    if (sub == 0 && live && agent_out) agent_out[row] = (int8_t)ph;
+  }
   pol_layer<false>(w, w + (size_t)d1 * d0, d0, d1, hidden_act, sub, h);
   w += (size_t)d1 * (d0 + 1);
   if (n_layers == 3) {

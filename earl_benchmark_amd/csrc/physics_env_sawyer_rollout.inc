@@ -163,11 +163,47 @@
     // door with goal switching: slot 7 of EVERY row's info block is this kernel's to write -- 0, or 1 on a goal-switch row (below) -- so that earl_sawyer_door_info never reads
     // a marker the caller left behind (ADVICE r05: the Python side used to zero the column with a launch of its own before every call)
     if (NV < 15 && gcf > 0 && a.out.info && sub == 11 && live) a.out.info[row * EARL_SAWYER_INFO + 7] = 0.0;
-    if (gcf > 0 && ++sgc >= gcf) {
+    // does this step end with a new goal row?  The lifelong switch's clock, or -- POLICY, earl_sawyer_pair_rollout -- a handover of the agent pair that changes the goal:
+    // `fixed` is then the row to install (entering the reset phase) or NULL (entering the forward phase: the lifelong switch's own draw)
+    // (the plain kernels: `POLICY && ...` folds away in the front end, and their statements -- and machine code -- are what they were)
+    [[maybe_unused]] bool pair_sw = false;
+    [[maybe_unused]] const double* fixed = nullptr;
+    [[maybe_unused]] bool pair_on = false;
+    if constexpr (POLICY) {
+      // The pair's state machine (include/earl_physics.h, item 5), worked out by all 16 lanes of the env from the same words: the step's success flag from lane 0, phase
+      // and steps_in_phase from HBM, where lane 0 stores them again -- nothing of it lives across substep.  The pointers are read through the kernel-argument segment
+      // here, where they are used (see sawyer_policy_action on why).
+      const EARL_KARG void* kp = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(kp));
+      const EARL_KARG SawyerPolicyArgs* ka = (const EARL_KARG SawyerPolicyArgs*)kp;
+      int8_t* const pair_phase = ka->pair_phase;
+      if (pair_phase) {                                  // (wave-uniform)
+        pair_on = true;
+        int32_t* const pair_sip = ka->pair_sip;
+        const bool by_s = ka->pair_sos != 0 && __shfl((int)((!failed && suc) ? 1 : 0), 0, 16) != 0;
+        int ph = pair_phase[env] != 0 ? 1 : 0;
+        int sip = pair_sip[env] + 1;                     // (a rolled-back step counts, with success 0)
+        const bool over = by_s || sip >= (ph ? ka->pair_se[1] : ka->pair_se[0]);
+        if (sub == 0 && live) {
+          int32_t* const fs = ka->pair_fs;
+          int32_t* const bs = ka->pair_bs;
+          if (fs) fs[env] = (t > 0 ? fs[env] : 0) + ((by_s && ph == 0) ? 1 : 0);      // (a step where the clock ran out as well counts as ended by success)
+          if (bs) bs[env] = (t > 0 ? bs[env] : 0) + ((by_s && ph != 0) ? 1 : 0);
+        }
+        if (over) {
+          ph ^= 1;
+          sip = 0;
+          if (ph) { fixed = ka->pair_goal; pair_sw = fixed != nullptr; }      // entering the reset phase: the backward row, if there is one
+          else pair_sw = cfg.n_goal_rows > 0;                                   // entering the forward phase: the lifelong switch's draw for this step
+        }
+        if (sub == 0 && live) { pair_phase[env] = (int8_t)ph; pair_sip[env] = sip; }
+      }
+    }
+    if ((gcf > 0 && ++sgc >= gcf) || (POLICY && pair_sw)) {
       // LifelongWrapper.step (lifelong_wrapper.py:36-42): reset_goal() -> get_next_goal(), then the observation is re-read with the new
       // goal (same simulator state: only the goal block changes); the reward above used the old goal
       sgc = 0;
-      if (cfg.n_goal_rows > 0 && cfg.goal_table && sub >= 7 && sub < 14 && live) {      // the lanes that wrote the goal block of this row
+      if (((POLICY && fixed) || (cfg.n_goal_rows > 0 && cfg.goal_table)) && sub >= 7 && sub < 14 && live) {      // the lanes that wrote the goal block of this row
         // the host's step counter plus the clock word of a graph-captured launch (earl_sawyer_rollout_clocked), read here -- a goal-switch step -- and not at kernel
         // entry: a value held across the rollout loop costs the time-sliced peg build 32 B of scratch per lane and the 64-lane door build two AGPRs
         const uint64_t ev = cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t;
@@ -175,7 +211,7 @@
                                                (uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32));
         int grow = (int)(earl::u01(b.x, b.y) * (double)cfg.n_goal_rows);
         grow = grow < cfg.n_goal_rows ? grow : cfg.n_goal_rows - 1;
-        const double gv = cfg.goal_table[(size_t)grow * 7 + (sub - 7)];
+        const double gv = (POLICY && fixed) ? fixed[sub - 7] : cfg.goal_table[(size_t)grow * 7 + (sub - 7)];
         if (NV < 15 && a.out.info && sub >= 11) {
           // the door's info dict is worked out after the launch from the emitted rows (earl_sawyer_door_info), whose goal block is about to change: this
           // row's info slots 0-2 carry the target the row's reward was computed with, slot 7 marks it (evaluate_state runs before reset_goal:
@@ -188,6 +224,8 @@
         else a.out.obs[row * 14 + sub] = gv;
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");      // the next step's observation reads the goal row back through global memory
+    } else if constexpr (POLICY) {
+      if (pair_on) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");      // (the same fence for the phase words: all 16 lanes read what lane 0 stored)
     }
   }
   if (live) {

@@ -107,6 +107,8 @@ class SawyerDoor:
     self.lifelong_return_t = torch.zeros(n, dtype=torch.float64, **kw)
     self.last_obs = torch.zeros(n, self.OBS_DIM, dtype=torch.float64, **kw)   # SawyerXYZEnv._last_stable_obs [UPSTREAM]
     self.fail_count = torch.zeros(n, dtype=torch.int32, **kw)                 # env steps rolled back by the failure guard (include/earl_physics.h)
+    self.agent_phase = self.steps_in_phase = None      # the agent pair's per-env state (rollout_agents allocates it: 0 forward / 1 reset, steps spent in the phase)
+    self._pair_counts = None
     self._last_obs_stale = False      # last_obs no longer describes (state, goal): set by set_state() / reset_goal(), cleared by whatever rewrites every row
     self.total_step_count = 0
 
@@ -146,6 +148,7 @@ class SawyerDoor:
     self.obj_init_angle = 0.0 if self._reset_at_goal else -np.pi / 3
     self.obj_init_pos = np.array([0.1, 0.95, 0.1], dtype=np.float32)
     self.hand_init_pos = np.array([0.29, 0.74, 0.1] if self._reset_at_goal else [0, 0.4, 0.2], dtype=np.float32)
+    self.initial_states = initial_states.copy()
     self.goal_states = goal_states.copy()
 
   def _task_cfg(self, cfg, names):
@@ -220,7 +223,8 @@ class SawyerDoor:
   def _issue_rollout(self, actions, T, out, clock=None, policy=None, summary=None):
     """the launches of T env steps into `out` (the door's info launch included); clock: the device words of earl_sawyer_rollout_clocked (None: earl_sawyer_rollout);
     policy: None, or (policy or population, head struct or None, obs0) -- earl_sawyer_population_rollout computes the actions itself and leaves them in
-    out['actions']; then `out` may lack any key, 'obs' included (the env's row of last_obs carries the observation), and summary is None or an _abi.EpisodeSummary"""
+    out['actions']; then `out` may lack any key, 'obs' included (the env's row of last_obs carries the observation), and summary is None or an _abi.EpisodeSummary;
+    or (AgentPair, head struct or None, obs0, _abi.AgentPair) -- earl_sawyer_pair_rollout"""
     info = out.get('info')
     in_kernel = info is not None and self.nv >= 15        # the peg's dict needs simulator state: the rollout kernel's epilogue writes it
     # door, lifelong goal switching: the kernel leaves the PRE-switch target on goal-switch rows (slots 0-2, marker in slot 7) for earl_sawyer_door_info
@@ -230,7 +234,12 @@ class SawyerDoor:
     with torch.cuda.device(self.device):
       if self.sched is not None and T > 1 and self._uses_queue(T):
         self.sched.zero_()                                 # (the queue of the time-sliced schedule: zero on entry)
-      if policy is not None:
+      if policy is not None and len(policy) == 4:
+        pi, head, obs0, ps = policy
+        _abi.check(self._lib.earl_sawyer_pair_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pi.struct), C.byref(ps),
+                                                      None if head is None else C.byref(head), obs0.data_ptr(), T, clock, _ptr(out.get('actions')), C.byref(o),
+                                                      self._stream()), 'earl_sawyer_pair_rollout')
+      elif policy is not None:
         pi, head, obs0 = policy
         pop = getattr(pi, 'pop_struct', None)             # a PolicyPopulation: the env with global id g runs member g // envs_per_policy
         _abi.check(self._lib.earl_sawyer_population_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pi.struct),
@@ -267,8 +276,14 @@ class SawyerDoor:
     if mask is None:
       self.interventions += 1
       self._last_obs_stale = False
+      if self.agent_phase is not None:                     # (a reset env starts with the forward agent)
+        self.agent_phase.zero_()
+        self.steps_in_phase.zero_()
     else:
       self.interventions += mask.to(torch.int32)
+      if self.agent_phase is not None:
+        self.agent_phase.masked_fill_(mask.bool(), 0)
+        self.steps_in_phase.masked_fill_(mask.bool(), 0)
       obs = torch.where(mask.bool()[:, None], obs, obs_prev)
     return obs[0].cpu().numpy() if self.scalar_api else obs
 
@@ -355,7 +370,7 @@ class SawyerDoor:
     from ..policy import GaussianMLPPolicy, MLPPolicy, PolicyPopulation
     population = isinstance(policy, PolicyPopulation)
     if not population and not isinstance(policy, MLPPolicy):
-      raise ValueError(f'{who}: an MLPPolicy, a GaussianMLPPolicy or a PolicyPopulation of them (agent pairs are tabletop only)')
+      raise ValueError(f'{who}: an MLPPolicy, a GaussianMLPPolicy or a PolicyPopulation of them (an AgentPair goes to rollout_agents)')
     if (policy.obs_dim, policy.act_dim) != (self.OBS_DIM, 4):
       raise ValueError(f'{who}: a policy of observation width {policy.obs_dim} and action width {policy.act_dim}; this env takes {self.OBS_DIM} and 4 '
                        '(MLPPolicy(..., obs_dim=14, act_dim=4))')
@@ -395,6 +410,58 @@ class SawyerDoor:
     head = policy.head(sample=bool(sample), eps_out=out['eps'] if return_noise else None) if gaussian else None
     self._launch_rollout(None, T, out, policy=(policy, head, obs0))
     return out
+
+  def rollout_agents(self, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
+    """The forward / reset agent pair of autonomous RL alternating inside ONE launch of the rollout kernel (include/earl_physics.h: earl_sawyer_pair_rollout): `pair` -- an
+    `AgentPair` built with obs_dim=14, act_dim=4 -- drives every env by the agent of its phase (`env.agent_phase`: 0 forward, 1 reset; `env.steps_in_phase`) and hands it
+    over after pair.switch_every[phase] steps or, with pair.switch_on_success, after a step whose success flag is set.  Entering the reset phase the env's goal becomes
+    pair.backward_goal ('initial': env.initial_states[0] on the door, its only row; the peg has fifteen and wants the row itself; None: the goal stays); entering the forward
+    phase it becomes the goal-table row the lifelong switch would draw at that step.  `goal_t` IS the goal in force and stays as the launch leaves it.
+    -> rollout_policy()'s dict plus 'agent' [T, N] int8 (the agent that computed the action); the door's dict has no 'info' (the peg's is written in the kernel and stays).
+    Bookkeeping, the first observation, sample / return_noise and reset_first as rollout_policy.  `env.pair_counts`: the phases of this launch that ended by success."""
+    from ..policy import AgentPair
+    if not isinstance(pair, AgentPair):
+      raise ValueError('rollout_agents: pair is an AgentPair')
+    if (pair.obs_dim, pair.act_dim) != (self.OBS_DIM, 4):
+      raise ValueError(f'rollout_agents: a pair of observation width {pair.obs_dim} and action width {pair.act_dim}; this env takes {self.OBS_DIM} and 4 '
+                       '(AgentPair(..., obs_dim=14, act_dim=4))')
+    if pair.device != self.device:
+      raise ValueError(f'rollout_agents: the pair is on {pair.device}, the env on {self.device} (pair.to(device))')
+    if self._cfg.goal_change_frequency > 0:
+      raise ValueError('rollout_agents: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
+                       'not under a LifelongWrapper, whose clock would fight the pair\'s over the same draw')
+    if not pair.gaussian and (return_noise or not sample):
+      raise ValueError('rollout_agents: sample=False / return_noise=True need Gaussian agents (MLPPolicy agents are deterministic)')
+    T = int(T)
+    if T < 1:
+      raise ValueError(f'rollout_agents: T = {T} < 1')
+    goal = pair.goal_row(self)                              # ('initial' on the peg: a ValueError naming env.initial_states)
+    if reset_first:
+      self.reset()
+    n, kw = self.num_envs, dict(device=self.device)
+    if self.agent_phase is None:
+      self.agent_phase = torch.zeros(n, dtype=torch.int8, **kw)
+      self.steps_in_phase = torch.zeros(n, dtype=torch.int32, **kw)
+    if out is None:
+      out = self._new_out((T,), info=self.nv >= 15 and self.info_mode == 'full')
+    for k, shape, dt in (('actions', (T, n, 4), torch.float32), ('agent', (T, n), torch.int8)) + ((('eps', (T, n, 4), torch.float32),) if return_noise else ()):
+      if k not in out:
+        out[k] = torch.empty(*shape, dtype=dt, **kw)
+    fwd, bwd = torch.empty(n, dtype=torch.int32, **kw), torch.empty(n, dtype=torch.int32, **kw)
+    ps = _abi.AgentPair(switch_every=(C.c_int32 * 2)(*pair.switch_every), switch_on_success=int(pair.switch_on_success), pad_=0, param_stride=pair.stride,
+                        backward_goal=_ptr(goal), phase=self.agent_phase.data_ptr(), steps_in_phase=self.steps_in_phase.data_ptr(),
+                        agent_out=out['agent'].data_ptr(), forward_success=fwd.data_ptr(), backward_success=bwd.data_ptr())
+    obs0 = self._get_obs_t() if self._last_obs_stale else self.last_obs
+    head = pair.head(sample=bool(sample), eps_out=out['eps'] if return_noise else None) if pair.gaussian else None
+    launch_out = out if self.nv >= 15 else {k: v for k, v in out.items() if k != 'info'}      # (the door's info dict of a pair launch is not offered)
+    self._launch_rollout(None, T, launch_out, policy=(pair, head, obs0, ps))
+    self._pair_counts = (fwd, bwd)
+    return out
+
+  @property
+  def pair_counts(self):
+    """(forward_success, backward_success) [N] int32 of the last rollout_agents launch: the phases that ended by success; None before the first"""
+    return self._pair_counts
 
   def evaluate_policy(self, policy, T, episodes=1, sample=False, reset_first=True):
     """`episodes` evaluation episodes of `policy` -- an MLPPolicy, a GaussianMLPPolicy (sample=False: at its mean) or a `PolicyPopulation` -- each a reset() launch plus ONE
@@ -494,13 +561,18 @@ class SawyerDoor:
     return {k: getattr(self, k).clone() for k in ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'steps_since_reset', 'interventions',
                                                   'steps_since_goal_change', 'lifelong_return_t', 'obj_init', 'last_obs', 'fail_count')} | {
                                                       'counter': int(self._cfg.counter), 'total_step_count': self.total_step_count,
-                                                      'last_obs_stale': bool(self._last_obs_stale)}
+                                                      'last_obs_stale': bool(self._last_obs_stale)} | (
+                                                          {} if self.agent_phase is None else {'agent_phase': self.agent_phase.clone(),
+                                                                                               'steps_in_phase': self.steps_in_phase.clone()})
 
   def load_state_dict(self, sd):
     for k in ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'steps_since_reset', 'interventions', 'steps_since_goal_change',
               'lifelong_return_t', 'obj_init', 'last_obs', 'fail_count'):
       if k in sd:
         getattr(self, k).copy_(sd[k])
+    if 'agent_phase' in sd:                                # (the agent pair's state: in the dict once a pair launch has allocated it, and only then)
+      self.agent_phase = sd['agent_phase'].to(self.device, torch.int8).clone()
+      self.steps_in_phase = sd['steps_in_phase'].to(self.device, torch.int32).clone()
     self._cfg.counter = int(sd['counter'])
     self.total_step_count = int(sd['total_step_count'])
     self._last_obs_stale = bool(sd.get('last_obs_stale', 'last_obs' not in sd))      # (a dict without the row leaves the env's own, which belongs to another state)

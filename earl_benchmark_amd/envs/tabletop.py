@@ -399,6 +399,8 @@ class TabletopManipulation:
     from ..policy import AgentPair
     if not isinstance(pair, AgentPair):
       raise ValueError('rollout_agents: pair is an AgentPair')
+    if (pair.obs_dim, pair.act_dim) != (12, 3):
+      raise ValueError(f'rollout_agents: an AgentPair of observation width {pair.obs_dim} and action width {pair.act_dim}; the tabletop takes 12 and 3')
     if self.NOBJ != 1:
       raise NotImplementedError('rollout_agents: single-object env only')
     if self._cfg.goal_change_frequency > 0:

@@ -317,21 +317,27 @@ class AgentPair:
   packing order and is what the kernel reads: write into it in place.  switch_every: steps after which the acting agent hands over, one int for both or (forward,
   reset); switch_on_success: also hand over after a step whose success flag is set; backward_goal: the goal row the reset agent is conditioned on -- 'initial' (the
   env's initial state, resolved by the env at launch), None (the reset agent keeps seeing the task goal) or a 6-vector in goal-table format.
-  A second hidden layer may be at most 128 wide (EARL_PAIR_MAX_H2: two weight sets share one wave's registers); one hidden layer may have every width."""
+  A second hidden layer may be at most 128 wide (EARL_PAIR_MAX_H2: two weight sets share one wave's registers); one hidden layer may have every width.
+  obs_dim / act_dim: the agents' widths -- the tabletop's 12 / 3 by default; 14 / 4 for the Sawyer door and peg (earl_sawyer_pair_rollout), where the backward goal is
+  a row of 7 values in the Sawyer goal format, the rows are padded to a stride of whole 16-byte pieces as PolicyPopulation's, and no width limit applies (the weights
+  are read from memory at every step)."""
 
-  def __init__(self, forward, backward, switch_every=200, switch_on_success=True, backward_goal='initial', device=None):
+  def __init__(self, forward, backward, switch_every=200, switch_on_success=True, backward_goal='initial', device=None, obs_dim=OBS_DIM, act_dim=ACT_DIM):
+    self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+    tabletop = (self.obs_dim, self.act_dim) == (OBS_DIM, ACT_DIM)
+    self.goal_dim = 6 if tabletop else 7
     members = [forward, backward]
     if not all(isinstance(m, MLPPolicy) for m in members):
       raise ValueError('AgentPair: forward and backward are MLPPolicy / GaussianMLPPolicy')
     for m in members:
-      require_tabletop_widths(m, 'AgentPair')
+      require_widths(m, 'AgentPair', self.obs_dim, self.act_dim)
     template = forward
     for p, m in enumerate(members):
       for what in ('__class__', 'dims', 'hidden_act', 'out_act') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
         if getattr(m, what) != getattr(template, what):
           raise ValueError(f'AgentPair: member {p} has {what.strip("_")} = {getattr(m, what)!r}, member 0 has {getattr(template, what)!r} '
                            '(the two agents of a pair share one architecture)')
-    if len(template.dims) == 4 and template.dims[2] > _abi.PAIR_MAX_H2:
+    if tabletop and len(template.dims) == 4 and template.dims[2] > _abi.PAIR_MAX_H2:
       raise ValueError(f'AgentPair: second hidden width {template.dims[2]} > {_abi.PAIR_MAX_H2} (EARL_PAIR_MAX_H2: two weight sets share one wave\'s registers)')
     se = (switch_every, switch_every) if np.ndim(switch_every) == 0 else tuple(switch_every)
     if len(se) != 2 or any(int(v) != v or int(v) < 1 for v in se):
@@ -341,13 +347,16 @@ class AgentPair:
       self.backward_goal = backward_goal
     else:
       g = torch.as_tensor(np.asarray(backward_goal, dtype=np.float64) if not torch.is_tensor(backward_goal) else backward_goal).detach().to('cpu', torch.float64).reshape(-1)
-      if g.numel() != 6:
-        raise ValueError(f"AgentPair: backward_goal is 'initial', None or ONE goal row of 6 values, got {g.numel()}")
+      if g.numel() != self.goal_dim:
+        raise ValueError(f"AgentPair: backward_goal is 'initial', None or ONE goal row of {self.goal_dim} values, got {g.numel()}")
       self.backward_goal = g.clone()
     self.template, self.gaussian = template, isinstance(template, GaussianMLPPolicy)
     self.dims, self.hidden_act, self.out_act, self.macs = list(template.dims), template.hidden_act, template.out_act, template.macs
     self.n_params = sum(n * (k + 1) for k, n in zip(self.dims[:-1], self.dims[1:]))
-    self.params = torch.stack([m.params.detach().to('cpu', torch.float32) for m in members]).contiguous()
+    host = torch.stack([m.params.detach().to('cpu', torch.float32) for m in members])
+    if not tabletop and host.shape[1] % 4:               # (the Sawyer kernel reads both agents' rows in 16-byte pieces)
+      host = torch.nn.functional.pad(host, (0, -host.shape[1] % 4))
+    self.params = host.contiguous()
     self.to(template.device if device is None else device)
 
   @property
@@ -371,12 +380,20 @@ class AgentPair:
     return self.template.head(sample=sample, eps_out=eps_out)
 
   def goal_row(self, env):
-    """the reset agent's goal row as a float64 tensor [6] on the pair's device, or None; 'initial' is `env.initial_state`"""
+    """the reset agent's goal row as a float64 tensor [6] (Sawyer widths: [7]) on the pair's device, or None; 'initial' is `env.initial_state` (the Sawyer door: the one
+    row of `env.initial_states`; the peg has fifteen, so the caller picks one)"""
     if self.backward_goal is None:
       return None
     if self._goal_dev is not None:
       return self._goal_dev
-    init = np.asarray(env.initial_state, dtype=np.float64).reshape(-1)
+    if self.goal_dim == 7:
+      rows = np.asarray(env.initial_states, dtype=np.float64).reshape(-1, 7)
+      if len(rows) != 1:
+        raise ValueError(f"AgentPair: backward_goal='initial' needs ONE initial state and env.initial_states has {len(rows)} rows: pass the row to condition the "
+                         'reset agent on (backward_goal=env.initial_states[k])')
+      init = rows[0]
+    else:
+      init = np.asarray(env.initial_state, dtype=np.float64).reshape(-1)
     if self._initial_dev is None or not np.array_equal(self._initial_dev[0], init):      # one upload per (pair, device, initial state), not one per launch
       self._initial_dev = (init.copy(), torch.as_tensor(init, device=self.device).contiguous())
     return self._initial_dev[1]
@@ -394,11 +411,12 @@ class AgentPair:
     layers = [(w.cpu().clone(), b.cpu().clone()) for w, b in self._layers_of(self.params[int(k)].detach())]
     t = self.template
     if self.gaussian:
-      return GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, device=self.device)
-    return MLPPolicy(layers, t.hidden_act, t.out_act, device=self.device)
+      return GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, device=self.device,
+                               obs_dim=self.obs_dim, act_dim=self.act_dim)
+    return MLPPolicy(layers, t.hidden_act, t.out_act, device=self.device, obs_dim=self.obs_dim, act_dim=self.act_dim)
 
   def __call__(self, obs, phase):
-    """obs [..., N, 12], phase [N] or [..., N] (0 forward, 1 reset) -> actions [..., N, 3] (Gaussian agents: at the mean): torch's statement -- close to the kernel,
+    """obs [..., N, obs_dim], phase [N] or [..., N] (0 forward, 1 reset) -> actions [..., N, act_dim] (Gaussian agents: at the mean): torch's statement -- close to the kernel,
     not bit-identical"""
     ph = torch.as_tensor(phase, device=obs.device).bool()
     acts = []
@@ -409,6 +427,6 @@ class AgentPair:
         x = torch.addmm(b, x, w.t())
         if l + 1 < len(layers):
           x = torch.relu(x) if self.hidden_act == 'relu' else torch.tanh(x)
-      x = x[:, :ACT_DIM]                                             # (Gaussian agents: the mean)
-      acts.append((torch.tanh(x) if self.out_act == 'tanh' else x).reshape(*obs.shape[:-1], ACT_DIM))
+      x = x[:, :self.act_dim]                                        # (Gaussian agents: the mean)
+      acts.append((torch.tanh(x) if self.out_act == 'tanh' else x).reshape(*obs.shape[:-1], self.act_dim))
     return torch.where(ph[..., None], acts[1], acts[0])

@@ -325,6 +325,38 @@ int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collisio
 int earl_sawyer_population_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                    const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
                                    const uint64_t* clock, float* actions, const earl_sawyer_out* out, const earl_episode_summary* summary, earl_stream_t stream);
+/* ---- the same closed loop for the AGENT PAIR of autonomous RL: a forward and a reset agent alternating inside one rollout ----
+ * earl_agent_pair is earl_tabletop.h's struct, as it is, used with these sizes: backward_goal ONE row of 7 doubles in the Sawyer goal format (as a row of st->goal);
+ * agent_out [T, n]; forward_success / backward_success [n] (one launch is one episode).  policy->params is [2, param_stride]: row 0 the forward agent, row 1 the
+ * reset agent, both of policy's architecture and head.  There is no EARL_PAIR_MAX_H2 limit here: the weights are read from memory at every step, not held in registers.
+ * Per env and env step, in this order (the order is the contract):
+ *   1. the action is computed from the observation the env last emitted (earl_sawyer_policy_rollout's rule: obs0 at step 0, row t - 1 as emitted afterwards) by the
+ *      network of the env's current `phase` (0 forward, anything else reset) at policy->params + phase * param_stride; the arithmetic is unchanged;
+ *   2. with a head, the step's Philox block is the one earl_sawyer_policy_rollout makes ({0x504F4C00, global id, ev}): it does not depend on the phase;
+ *   3. agent_out, actions and eps_out are written;
+ *   4. the env step runs as in the single-policy kernel, failure guard, rollback and fail_count included; reward and success refer to the goal in force DURING the
+ *      step, which is the env's row of st->goal;
+ *   5. steps_in_phase += 1 (a rolled-back step counts, with success 0), and the env hands over if (switch_on_success && success) || steps_in_phase >=
+ *      switch_every[phase]: phase ^= 1, steps_in_phase = 0; forward_success / backward_success of the phase that ended is incremented if switch_on_success && success
+ *      (a step where the clock ran out as well counts as ended by success); step 0 of the launch starts both counters at 0.
+ *      Entering the reset phase with backward_goal != NULL, the env's row of st->goal becomes backward_goal.  Entering the forward phase with cfg->n_goal_rows > 0, it
+ *      becomes the goal-table row of the lifelong switch's draw for this step (draw index 0xFFFE, global id, ev = cfg->step_counter + clock[1] + t; the same u01 and
+ *      clamp); with n_goal_rows == 0 the goal stays.  Whenever the row changes, the goal block of this step's emitted observation row (out->obs, or the carried row of
+ *      st->last_obs) is patched exactly as the lifelong switch patches it: the next action sees the new goal, this step's reward used the old one;
+ *   6. phase and steps_in_phase are stored after every env step, so a time slice of the peg's schedule that another wavefront takes finds them, the counters and
+ *      agent_out's predecessors under the release / acquire that carries qpos and the summary words.
+ * Unlike the tabletop, whose goal_idx a pair launch leaves alone, st->goal IS the goal in force here and is left as such at launch exit: there is no separate entry
+ * rule (an env in the reset phase starts from whatever its row of st->goal holds), and every other entry point keeps working on the state.
+ * Never switching (switch_every > T, switch_on_success = 0) with all envs in phase 0 the launch is bit-identical to earl_sawyer_policy_rollout with row 0: outputs,
+ * actions, eps, state, fail_count; all envs in phase 1 with backward_goal = NULL, to the same with row 1.  actions, every pointer of `out` and the pair's three output
+ * pointers may be NULL, as in earl_sawyer_population_rollout; without out->obs the env's row of st->last_obs is carried.  On the door, out->info receives only what the
+ * lifelong switch leaves on a goal-switch row (the door's info dict of a pair launch is not offered); the peg's is written in the kernel as ever.
+ * EARL_ERR_ARG before any HIP call: everything earl_sawyer_population_rollout refuses with pop = NULL, and NULL pair / phase / steps_in_phase, switch_every[k] < 1,
+ * switch_on_success not 0 or 1, param_stride below the parameter count or not a multiple of 4, cfg->goal_change_frequency > 0 (the pair IS the lifelong mechanism),
+ * backward_goal != NULL with cfg->n_goal_rows == 0 (the forward goal could not be restored). */
+int earl_sawyer_pair_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                             const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                             const uint64_t* clock, float* actions, const earl_sawyer_out* out, earl_stream_t stream);
 /* The policy contract on the host (libearl_host.so; host pointers): actions [n, A] of n observation rows obs [n, dims[0]], dims[0] in 1..256, hidden widths in 1..256,
  * the last layer A wide (head = NULL) or 2 A wide (rows 0..A-1 the mean, A..2A-1 the raw log_std), A >= 1.  eps [n, A] = the standard-normal draws to use with a
  * head in EARL_HEAD_SAMPLE mode; NULL (or EARL_HEAD_MEAN, or no head) evaluates the mean / the deterministic policy.  policy->out_act is applied last, as on the

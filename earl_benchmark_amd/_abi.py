@@ -203,6 +203,9 @@ SIGNATURES = {
     # ... for the forward / reset agent pair: pair after policy (backward_goal a row of 7, agent_out [T, n], the counters [n])
     'earl_sawyer_pair_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(MlpPolicy), _P(AgentPair), _P(GaussianHead), C.c_void_p,
                                  C.c_int32, C.c_void_p, C.c_void_p, _P(SawyerOut), C.c_void_p],
+    # the closed loop inside the minitaur rollout kernels: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
+    'earl_minitaur_policy_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_void_p, _P(MinitaurOut), C.c_void_p],
     'earl_minitaur_reset': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_minitaur_cfg_size': [],
     'earl_debug_set_minitaur_stepper': [C.c_int],

@@ -248,79 +248,16 @@ __device__ __forceinline__ void sawyer_emit(Shared<NV>& s, const typename ModelO
 
 
 // ------------------------------------------------------------------------------------------------ the policy phase of sawyer_policy_rollout_kernel
-// A float32 MLP 14 -> H1 (-> H2) -> 4 | 8 evaluated by the 16 lanes of an env between two env steps, under the contract of policy_math.h / tabletop_policy.h:
-// acc = b_j; for k ascending: acc = fmaf(x_k, W_jk, acc).  No LDS (the stepper's workgroups leave none): a layer's activations live in registers, element k on
-// lane k & 15 of the env's group in register k >> 4, and x_k reaches the group's other lanes by a width-16 __shfl (ds_bpermute_b32: the LDS crossbar, no allocation).
-// Lane `sub` owns outputs j = 16 i + sub.  One pass of pol_layer's outer loop carries FOUR of them (i = 4 g .. 4 g + 3): four independent fmaf chains per lane share
-// every x_k, so a shuffle feeds four multiply-adds and the chains hide one another's latency.  Weights come from global memory (params is [N][K] row-major, as
-// torch.nn.Linear.weight): a lane walks its own rows in 16-byte pieces, so every cache line it touches is used whole over consecutive loads, and the four env
-// groups of a wave read the same addresses (one fetch serves them).  The network sits in L2 (14 -> 256 -> 256 -> 4: 280 KB).
-// Register arrays are indexed by constants only: instead of indexing by the (runtime) k-tile / output-group number the arrays are rotated by one tile per iteration.
-template <bool VEC>
-__device__ __forceinline__ void pol_layer(const float* __restrict__ W, const float* __restrict__ B, const int K, const int N, const int kind, const int sub,
-                                          float (&h)[16]) {
-#pragma clang fp contract(off)
-  float out[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) out[i] = 0.f;
-  const int nt = (N + 15) >> 4, nk = (K + 15) >> 4;
-#pragma unroll 1
-  for (int g = 0; g < 4; ++g) {
-    float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
-    if (4 * g < nt) {                                   // (wave-uniform)
-      // rows past the layer's last one (a width that is not a multiple of 64; the 4- or 8-wide output layer) are clamped: computed on row N - 1 and never read
-      const int j0 = min(64 * g + sub, N - 1), j1 = min(64 * g + 16 + sub, N - 1), j2 = min(64 * g + 32 + sub, N - 1), j3 = min(64 * g + 48 + sub, N - 1);
-      const float* __restrict__ w0 = W + (size_t)j0 * K;
-      const float* __restrict__ w1 = W + (size_t)j1 * K;
-      const float* __restrict__ w2 = W + (size_t)j2 * K;
-      const float* __restrict__ w3 = W + (size_t)j3 * K;
-      r0 = B[j0]; r1 = B[j1]; r2 = B[j2]; r3 = B[j3];
-      float cur[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) cur[i] = h[i];
-#pragma unroll 1
-      for (int kt = 0; kt < nk; ++kt) {
-        const float x = cur[0];
-        if constexpr (VEC) {                            // K a multiple of 16, rows 16-byte aligned
-#pragma unroll
-          for (int kk = 0; kk < 16; kk += 4) {
-            const float4 v0 = *reinterpret_cast<const float4*>(w0 + 16 * kt + kk), v1 = *reinterpret_cast<const float4*>(w1 + 16 * kt + kk);
-            const float4 v2 = *reinterpret_cast<const float4*>(w2 + 16 * kt + kk), v3 = *reinterpret_cast<const float4*>(w3 + 16 * kt + kk);
-            const float x0 = __shfl(x, kk, 16), x1 = __shfl(x, kk + 1, 16), x2 = __shfl(x, kk + 2, 16), x3 = __shfl(x, kk + 3, 16);
-            r0 = __builtin_fmaf(x0, v0.x, r0); r1 = __builtin_fmaf(x0, v1.x, r1); r2 = __builtin_fmaf(x0, v2.x, r2); r3 = __builtin_fmaf(x0, v3.x, r3);
-            r0 = __builtin_fmaf(x1, v0.y, r0); r1 = __builtin_fmaf(x1, v1.y, r1); r2 = __builtin_fmaf(x1, v2.y, r2); r3 = __builtin_fmaf(x1, v3.y, r3);
-            r0 = __builtin_fmaf(x2, v0.z, r0); r1 = __builtin_fmaf(x2, v1.z, r1); r2 = __builtin_fmaf(x2, v2.z, r2); r3 = __builtin_fmaf(x2, v3.z, r3);
-            r0 = __builtin_fmaf(x3, v0.w, r0); r1 = __builtin_fmaf(x3, v1.w, r1); r2 = __builtin_fmaf(x3, v2.w, r2); r3 = __builtin_fmaf(x3, v3.w, r3);
-          }
-        } else {                                        // the input layer: K = 14, rows 56 bytes apart
-#pragma unroll
-          for (int kk = 0; kk < 16; ++kk) {
-            const int k = 16 * kt + kk;
-            if (k < K) {                                // (wave-uniform)
-              const float xk = __shfl(x, kk, 16);
-              r0 = __builtin_fmaf(xk, w0[k], r0); r1 = __builtin_fmaf(xk, w1[k], r1); r2 = __builtin_fmaf(xk, w2[k], r2); r3 = __builtin_fmaf(xk, w3[k], r3);
-            }
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 15; ++i) cur[i] = cur[i + 1];
-      }
-      r0 = earl::policy_act(r0, kind); r1 = earl::policy_act(r1, kind); r2 = earl::policy_act(r2, kind); r3 = earl::policy_act(r3, kind);
-    }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) out[i] = out[i + 4];   // after the four passes group g's results stand at out[4 g .. 4 g + 3]
-    out[12] = r0; out[13] = r1; out[14] = r2; out[15] = r3;
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) h[i] = out[i];
-}
+// A float32 MLP 14 -> H1 (-> H2) -> 4 | 8 evaluated by the 16 lanes of an env between two env steps, under the contract of policy_math.h / tabletop_policy.h.  The layer
+// itself -- activations in registers, element k on lane k & 15 in register k >> 4, x_k by a width-16 __shfl, four fmaf chains per lane, weight rows in 16-byte pieces --
+// is pol_layer<16, ..> of policy_lane_group.h, shared with the minitaur (32 lanes per env).
+#include "policy_lane_group.h"
 
 // the action of env step t of one env, on all 16 lanes of its group: observation (element `sub` on lane `sub`, 0 beyond 13) -> MLP -> head -> float4.
 // `row` = t n + env; a group that is not live computes on zeros and writes nothing.
 // The policy's kernel arguments are read HERE, through the kernel-argument pointer the caller passed through an empty asm (the register-pinning recipe of DESIGN 2, on
 // scalar registers): read as `a.pol...` they are loaded once at kernel entry and held in some twenty scalar registers across the whole env-step loop -- through substep, where the
 // scalar file is full already; the extra scalar spills took vector registers away and the stepper's own constants went to scratch, reloaded inside the timestep loop.
-#define EARL_KARG __attribute__((address_space(4)))
 __device__ __noinline__ float4 sawyer_policy_action(const uint64_t ka_bits, const uint64_t ev, const uint32_t gid, const uint64_t seed, const double* __restrict__ seen, const int env,
                                                        const size_t row, const int sub, const bool live) {
 #pragma clang fp contract(off)
@@ -348,14 +285,14 @@ __device__ __noinline__ float4 sawyer_policy_action(const uint64_t ka_bits, cons
     int8_t* agent_out = ka->pair_agent;
     if (sub == 0 && live && agent_out) agent_out[row] = (int8_t)ph;
   }
-  pol_layer<false>(w, w + (size_t)d1 * d0, d0, d1, hidden_act, sub, h);
+  pol_layer<16, false>(w, w + (size_t)d1 * d0, d0, d1, hidden_act, sub, h);
   w += (size_t)d1 * (d0 + 1);
   if (n_layers == 3) {
-    pol_layer<true>(w, w + (size_t)d2 * d1, d1, d2, hidden_act, sub, h);
+    pol_layer<16, true>(w, w + (size_t)d2 * d1, d1, d2, hidden_act, sub, h);
     w += (size_t)d2 * (d1 + 1);
   }
   const int KL = n_layers == 3 ? d2 : d1, NL = n_layers == 3 ? d3 : d2;
-  pol_layer<true>(w, w + (size_t)NL * KL, KL, NL, EARL_ACT_NONE, sub, h);       // lane j < NL holds output j
+  pol_layer<16, true>(w, w + (size_t)NL * KL, KL, NL, EARL_ACT_NONE, sub, h);       // lane j < NL holds output j
   float u;
   if (ka->gauss) {
     // lanes 0..3 are the head's four dimensions: mean on the lane itself, raw log_std four lanes up

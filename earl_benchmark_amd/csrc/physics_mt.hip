@@ -6,6 +6,7 @@
 // earl_minitaur_reset.  A translation unit of its own so that the three builds compile side by side.
 #include "minitaur_device.h"
 #include "physics_stepper.h"
+#include "policy_math.h"
 
 namespace {
 #include "minitaur_stepper.h"
@@ -48,6 +49,46 @@ int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_mode
   if (g_mt_stepper) minitaur_kernel<false, true><<<solo_grid(cfg->n, a.solo, EARL_MT_WPB), 64 * EARL_MT_WPB, 0, (hipStream_t)stream>>>(a);
   else minitaur_kernel<false, false><<<solo_grid(cfg->n, a.solo, Lim<22>::WPB), block_for<22>(), 0, (hipStream_t)stream>>>(a);
   return launched("minitaur_rollout");
+}
+// include/earl_physics.h: T closed-loop env steps in one launch, the policy evaluated by the 32 lanes that own the env.  The launch forms are
+// earl_minitaur_rollout_clocked's (one-wave kernel in its three shapes, two-wave kernel); the generic substep<22> comparison build has no policy form
+int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                 const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
+                                 const earl_minitaur_out* out, earl_stream_t stream) {
+  if (!model24 || !cfg || !st || !out || !policy || !obs0 || !actions || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
+  if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
+  if (!out->obs || !out->reward || !out->done || !out->success || !cfg->goal_table || cfg->n_goals < 1 || cfg->num_substeps < 0) return EARL_ERR_ARG;
+  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;
+  if (!policy->params || ((uintptr_t)policy->params & 15) || policy->precision != 0) return EARL_ERR_ARG;      // (16-byte loads of the weight rows)
+  if (policy->n_layers != 2 && policy->n_layers != 3) return EARL_ERR_ARG;
+  if (policy->dims[0] != 32 || policy->dims[policy->n_layers] != (head ? 16 : 8)) return EARL_ERR_ARG;
+  for (int l = 1; l < policy->n_layers; ++l)
+    if (policy->dims[l] < 16 || policy->dims[l] > earl::kPolicyMaxWidth || policy->dims[l] % 16) return EARL_ERR_ARG;
+  if (policy->n_layers == 2 && policy->dims[3] != 0) return EARL_ERR_ARG;
+  if (policy->hidden_act != EARL_ACT_RELU && policy->hidden_act != EARL_ACT_TANH) return EARL_ERR_ARG;
+  // the reference env raises on an action outside +-(1 + 0.01); a kernel cannot, and the open-loop replay of the returned actions must not either: bounded policies only
+  if (policy->out_act != EARL_ACT_TANH) return EARL_ERR_ARG;
+  if (head) {
+    if (head->mode != EARL_HEAD_MEAN && head->mode != EARL_HEAD_SAMPLE) return EARL_ERR_ARG;
+    if (head->log_std_map != EARL_LOGSTD_CLAMP && head->log_std_map != EARL_LOGSTD_TANH) return EARL_ERR_ARG;
+    if (!(head->log_std_min >= -20.0f && head->log_std_max <= 4.0f && head->log_std_min <= head->log_std_max)) return EARL_ERR_ARG;      // (NaN fails every comparison)
+  }
+  if (!g_mt_stepper) return EARL_ERR_ARG;                 // (earl_debug_set_minitaur_stepper(0): no policy form)
+  if (cfg->n == 0 || T == 0) return EARL_OK;
+  if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_policy_rollout")) return rc;
+  MinitaurPolicyArgs a;
+  static_cast<MinitaurArgs&>(a) = MinitaurArgs{model24, col, *cfg, *st, *out, nullptr, T, nullptr, nullptr, solo_mode(cfg->n), clock};
+  a.pol = *policy;
+  a.head = head ? *head : earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr};
+  a.gauss = head ? 1 : 0;
+  a.obs0 = obs0;
+  a.act_out = actions;
+  if (a.solo == 0 && cfg->num_substeps > 0 && (g_mt_duo > 0 || (g_mt_duo < 0 && mt_use_duo(cfg->n)))) {      // the plain entry point's rule
+    minitaur_policy_duo_kernel<<<(unsigned)((cfg->n + 16 * MT_DUO_PAIRS / 4 - 1) / (4 * MT_DUO_PAIRS)), 128 * MT_DUO_PAIRS, 0, (hipStream_t)stream>>>(a);
+    return launched("minitaur_policy_rollout (two waves per SIMD)");
+  }
+  minitaur_policy_kernel<false, true><<<solo_grid(cfg->n, a.solo, EARL_MT_WPB), 64 * EARL_MT_WPB, 0, (hipStream_t)stream>>>(a);
+  return launched("minitaur_policy_rollout");
 }
 int earl_minitaur_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                           const float* action, int32_t T, const earl_minitaur_out* out, earl_stream_t stream) {

@@ -1,6 +1,6 @@
 // policy_math.h -- the arithmetic of the in-kernel policies, stated once for every unit that evaluates one: the activations (relu_f32, tanh_f32), the Gaussian
 // head (exp_f32, normal_quantile_f32, the log-std maps, gaussian_head_action) and the draw index of its Philox stream.  Included by tabletop_policy.h (the tabletop
-// kernels and their host twin) and by physics_env_sawyer.h (the Sawyer door / peg rollout with a policy): it needs the ABI structs and nothing of either env.
+// kernels and their host twin), by physics_env_sawyer.h (the Sawyer door / peg rollout with a policy) and by physics_env_minitaur.h (the minitaur's): it needs the ABI structs and nothing of any env.
 // Every function body states `fp contract(off)` itself: the tabletop units are compiled with -ffp-contract=off anyway, the stepper units run under
 // `fp contract(fast)` (physics_stepper.h), and these functions are a bit-exact contract in both.
 #pragma once

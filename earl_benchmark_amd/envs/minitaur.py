@@ -104,6 +104,7 @@ class Minitaur:
     self.observation_space = Box(-np.inf, np.inf, (self.OBS_DIM,), np.float32)        # :179, :481-488
     self._counter = 0
     self._last_success = torch.zeros(n, dtype=torch.bool, device=dev)
+    self._last_obs_stale = False      # last_obs no longer describes (state, goal): set by set_state() / reset_goal(), cleared by whatever rewrites every row
     self.reset()
     self.interventions.zero_()
 
@@ -132,6 +133,8 @@ class Minitaur:
       _abi.check(self._lib.earl_minitaur_reset(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st),
                                                None if m is None else m.data_ptr(), obs.data_ptr(), self._stream()), 'earl_minitaur_reset')
       self.interventions += 1 if m is None else m.to(torch.int32)
+    if m is None:
+      self._last_obs_stale = False
     self._counter += 1
     return obs[0].cpu().numpy() if self.scalar_api else obs
 
@@ -161,8 +164,79 @@ class Minitaur:
         if int(self._cfg.goal_change_frequency) > 0:
           self.lifelong_return_t += res['reward'].sum(0)
         self._last_success = res['success'][-1]
+        self._last_obs_stale = False                       # (every env's last_obs row was rewritten)
     self.total_step_count += T
     return res
+
+  def _check_policy(self, policy, who):
+    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy of this env's widths on this env's device whose output is bounded"""
+    from ..policy import AgentPair, GaussianMLPPolicy, MLPPolicy, PolicyPopulation
+    if isinstance(policy, PolicyPopulation):
+      raise NotImplementedError(f'{who}: a PolicyPopulation on the minitaur is not offered (one MLPPolicy / GaussianMLPPolicy per launch; populations run on the tabletop, '
+                                'the Sawyer door and the Sawyer peg)')
+    if isinstance(policy, AgentPair):
+      raise NotImplementedError(f'{who}: an AgentPair on the minitaur is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
+    if not isinstance(policy, MLPPolicy):
+      raise ValueError(f'{who}: an MLPPolicy or a GaussianMLPPolicy')
+    if (policy.obs_dim, policy.act_dim) != (OBS_DIM, ACT_DIM):
+      raise ValueError(f'{who}: a policy of observation width {policy.obs_dim} and action width {policy.act_dim}; this env takes {OBS_DIM} and {ACT_DIM} '
+                       f'(MLPPolicy(..., obs_dim={OBS_DIM}, act_dim={ACT_DIM}))')
+    if policy.device != self.device:
+      raise ValueError(f'{who}: the policy is on {policy.device}, the env on {self.device} (policy.to(device))')
+    gaussian = isinstance(policy, GaussianMLPPolicy)
+    if policy.out_act != 'tanh':
+      given = 'GaussianMLPPolicy(..., squash=False)' if gaussian else f'MLPPolicy(..., out_act={policy.out_act!r})'
+      raise ValueError(f'{who}: {given} is unbounded; the reference env raises on an action outside +-{ACTION_BOUND + ACTION_EPS} and a kernel cannot, so the minitaur '
+                       "takes bounded policies only: MLPPolicy(..., out_act='tanh') or GaussianMLPPolicy(..., squash=True)")
+    return gaussian
+
+  def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
+    """Closed loop in ONE launch of the rollout kernel (include/earl_physics.h: earl_minitaur_policy_rollout): `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy` built
+    with obs_dim=32, act_dim=8 and a bounded output (out_act='tanh' / squash=True) -- is evaluated between the env steps by the 32 lanes that own the env: observation ->
+    float32 MLP -> action -> env step.
+    -> rollout()'s dict plus 'actions' [T, N, 8] float32 (as the policy produced them) and, with return_noise=True, 'eps' [T, N, 8] (the standard-normal draws as
+    used).  Bit-identical to rollout(out['actions']) from the same state.  The first action is computed from the observation the env last returned (`last_obs`: the row
+    the previous step / rollout / reset emitted, so T launches of one step equal one launch of T); after set_state() or reset_goal() from _get_obs() of the
+    current state and goal.  reset_first=True calls reset() before (a launch of its own).  A Gaussian policy is sampled inside the kernel (sample=True: tanh(mean +
+    exp(log_std) eps), eps from the env's Philox stream keyed by seed, global env id and step counter) or evaluated at its mean (sample=False); both flags are for
+    Gaussian policies only."""
+    gaussian = self._check_policy(policy, 'rollout_policy')
+    if not gaussian and (return_noise or not sample):
+      raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
+    T = int(T)
+    if T < 1:
+      raise ValueError(f'rollout_policy: T = {T} < 1')
+    if reset_first:
+      self.reset()
+    with torch.cuda.device(self.device):
+      res = out if out is not None else self._new_out((T,))
+      if 'actions' not in res:
+        res['actions'] = torch.empty(T, self.num_envs, ACT_DIM, dtype=torch.float32, device=self.device)
+      if return_noise and 'eps' not in res:
+        res['eps'] = torch.empty(T, self.num_envs, ACT_DIM, dtype=torch.float32, device=self.device)
+      # what the policy sees first: the observation the env last returned (st.last_obs, goal entries as patched); after set_state() / reset_goal() that row no longer
+      # describes the env and the observation of the current state and goal is recomputed
+      obs0 = (self._get_obs_t() if self._last_obs_stale else self.last_obs).contiguous()
+      head = policy.head(sample=bool(sample), eps_out=res['eps'] if return_noise else None) if gaussian else None
+      o = _abi.MinitaurOut(obs=res['obs'].data_ptr(), reward=res['reward'].data_ptr(), done=res['done'].data_ptr(), success=res['success'].data_ptr(),
+                           status=res['status'].data_ptr())
+      self._cfg.step_counter = self.total_step_count
+      _abi.check(self._lib.earl_minitaur_policy_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), C.byref(policy.struct),
+                                                        None if head is None else C.byref(head), obs0.data_ptr(), T, None, res['actions'].data_ptr(), C.byref(o),
+                                                        self._stream()), 'earl_minitaur_policy_rollout')
+      if int(self._cfg.goal_change_frequency) > 0:
+        self.lifelong_return_t += res['reward'].sum(0)
+      self._last_success = res['success'][-1]
+      self._last_obs_stale = False                         # (every env's last_obs row was rewritten)
+    self.total_step_count += T
+    return res
+
+  def rollout_agents(self, pair, T, **kw):
+    raise NotImplementedError('rollout_agents: an AgentPair on the minitaur is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
+
+  def evaluate_policy(self, policy, T, **kw):
+    raise NotImplementedError('evaluate_policy: episode summaries on the minitaur are not offered (rollout_policy returns every step; evaluate_policy runs on the '
+                              'tabletop, the Sawyer door and the Sawyer peg)')
 
   def step(self, action):
     """-> (obs [N,32], reward [N], done [N], info{success, status}); gym 4-tuple of numpy / python scalars with scalar_api"""
@@ -209,18 +283,23 @@ class Minitaur:
 
   def _graph_advance(self, T, out):
     self.total_step_count += T
+    self._last_obs_stale = False
     self._last_success = out['success'][-1]
 
   def _graph_info(self, out):
     return {'success': out['success'], 'status': out['status']}
 
-  def _get_obs(self):
-    """GetObservation + goal of the CURRENT state (:541-546): no simulation, the newest observed torques"""
+  def _get_obs_t(self):
+    """_get_obs() as the [N, 32] tensor, whatever scalar_api says"""
     md, dr = torch.tensor([int(x) for x in self.model.tables['motor_dof']], device=self.device), torch.tensor(self.model.tables['motor_direction'], device=self.device)
     ang = self.qpos[:, md + 1] * dr
     vel = self.qvel[:, md] * dr
     q = self.qpos[:, 3:7]
-    obs = torch.cat([ang, vel, self.observed_torque, q[:, 1:4], q[:, 0:1], self.qpos[:, 0:2], self.goal_t], 1)
+    return torch.cat([ang, vel, self.observed_torque, q[:, 1:4], q[:, 0:1], self.qpos[:, 0:2], self.goal_t], 1)
+
+  def _get_obs(self):
+    """GetObservation + goal of the CURRENT state (:541-546): no simulation, the newest observed torques"""
+    obs = self._get_obs_t()
     return obs[0].cpu().numpy() if self.scalar_api else obs
 
   get_obs = _get_obs
@@ -252,12 +331,14 @@ class Minitaur:
     else:
       m = torch.as_tensor(mask, device=self.device).bool()
       self.goal_t[m] = g[m]
+    self._last_obs_stale = True                            # (last_obs carries the old goal entries: rollout_policy recomputes its first observation)
 
   @property
   def goal(self):
     return self.goal_t[0].cpu().numpy() if self.scalar_api else self.goal_t
 
   def set_state(self, qpos, qvel):
+    self._last_obs_stale = True                            # (last_obs no longer belongs to the state: rollout_policy recomputes its first observation)
     self.qpos.copy_(torch.as_tensor(qpos, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.NQ))
     self.qvel.copy_(torch.as_tensor(qvel, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.NV))
 
@@ -265,10 +346,14 @@ class Minitaur:
             'interventions', 'fail_count', 'lifelong_return_t', 'last_obs')
 
   def state_dict(self):
-    return {k: getattr(self, k).clone() for k in self._STATE} | {'counter': self._counter, 'total_step_count': self.total_step_count}
+    return {k: getattr(self, k).clone() for k in self._STATE} | {'counter': self._counter, 'total_step_count': self.total_step_count,
+                                                                 'last_obs_stale': bool(self._last_obs_stale)}
 
   def load_state_dict(self, sd):
+    self._last_obs_stale = bool(sd.get('last_obs_stale', False))      # (a dict written before the flag existed: not stale)
     for k, v in sd.items():
+      if k == 'last_obs_stale':
+        continue
       if k == 'counter':
         self._counter = int(v)
       elif k == 'total_step_count':

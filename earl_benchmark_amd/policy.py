@@ -13,6 +13,11 @@ The Sawyer door and peg take the same two classes with obs_dim=14, act_dim=4 (in
   pi = MLPPolicy(layers, 'relu', 'tanh', device='cuda', obs_dim=14, act_dim=4)
   out = door.rollout_policy(pi, T=300)                                                          # rollout()'s dict plus 'actions' [T, N, 4], ONE launch
 
+The minitaur takes them with obs_dim=32, act_dim=8 and a bounded output (include/earl_physics.h: earl_minitaur_policy_rollout):
+
+  pi = MLPPolicy(layers, 'relu', 'tanh', device='cuda', obs_dim=32, act_dim=8)                  # or GaussianMLPPolicy(..., squash=True, obs_dim=32, act_dim=8)
+  out = minitaur.rollout_policy(pi, T=250)                                                      # rollout()'s dict plus 'actions' [T, N, 8], ONE launch
+
 `GaussianMLPPolicy` is the SAC-style actor with a tanh-Gaussian head, 12 -> hidden (-> hidden) -> 6 (rows 0..2 mean, rows 3..5 raw log_std), for
 earl_tabletop_policy_rollout_gaussian: the actions are SAMPLED inside the kernel from the env's counter-based RNG.
 
@@ -76,7 +81,7 @@ class MLPPolicy:
   OUT_DIM, OUT_WHAT = ACT_DIM, 'action'
 
   def __init__(self, layers, hidden_act='relu', out_act='tanh', device='cpu', obs_dim=OBS_DIM, act_dim=ACT_DIM):
-    """obs_dim / act_dim: the env's observation and action widths -- the tabletop's 12 / 3 by default, 14 / 4 for the Sawyer door and peg (`env.rollout_policy`)"""
+    """obs_dim / act_dim: the env's observation and action widths -- the tabletop's 12 / 3 by default, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur (`env.rollout_policy`)"""
     name = type(self).__name__                                        # (MLPPolicy's own messages read as they always did)
     self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
     if self.obs_dim < 1 or self.act_dim < 1:

@@ -534,6 +534,32 @@ int earl_minitaur_rollout(const void* model24, const earl_collision_model* col, 
  * kernel honours it: the two-wave and one-wave kernels and the generic stepper (earl_debug_set_minitaur_stepper(0)).  earl_minitaur_rollout is this with clock = NULL. */
 int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                                   const float* action, int32_t T, const uint64_t* clock, const earl_minitaur_out* out, earl_stream_t stream);
+/* ---- closed loop: an MLP policy evaluated INSIDE the minitaur rollout kernels ----
+ * T closed-loop env steps in ONE launch: between two env steps the 32 lanes that own an env evaluate the policy, observation -> float32 MLP 32 -> hidden (-> hidden) -> 8
+ * -> action -> next env step.  earl_mlp_policy / earl_gaussian_head are earl_tabletop.h's, with dims[0] = 32 and dims[n_layers] = 8 (head = NULL) or 16 (head given:
+ * output rows 0..7 the mean, rows 8..15 the raw log_std); hidden widths multiples of 16 in 16..256; policy->params 16-byte aligned (weight rows are read in 16-byte pieces).
+ * Per env and env step t, in this order:
+ *   1. input: at t = 0 the env's row of obs0 [n, 32] (device); at t > 0 row t - 1 of THIS launch's out->obs exactly as emitted -- the repeated row of a rolled-back step
+ *      and the goal entries 30 / 31 patched by a lifelong goal switch included -- each double rounded once to float32;
+ *   2. network: the contract of earl_tabletop_policy_rollout (acc = b_j; k ascending: acc = fmaf(x_k, W_jk, acc); relu_f32, tanh_f32; the head's exp_f32,
+ *      normal_quantile_f32, log_std maps and u = fmaf(exp_f32(ls), eps, mean): csrc/policy_math.h); earl_mlp_policy_forward_cpu below states it on the host;
+ *   3. head: TWO Philox4x32-10 blocks per (env, env step), key = cfg->seed, block b in {0, 1} with counter words {0x504F4C00 + b, cfg->env_offset + env, ev lo, ev hi},
+ *      ev = cfg->step_counter + clock[1] + t (the value the goal-switch draw of that step uses; its draw index is 0xFFFE, the reset's are 0x4D00 .. 0x4D06: the streams
+ *      are disjoint); words x, y, z, w of block b -> action dimensions 4 b .. 4 b + 3, each as normal_quantile_f32(word >> 8);
+ *   4. stores: actions[t] ([T, n, 8] device, required) and head->eps_out[t] ([T, n, 8] or NULL, written in both modes);
+ *   5. the env step of earl_minitaur_rollout_clocked on exactly the float32 values stored in actions[t] (clipped to +-1.01, leg model, failure guard, rollback, reward,
+ *      success, done, goal switch, state rows: the same statements).
+ * The launch is therefore bit-identical to earl_minitaur_rollout_clocked fed with the actions it returns: outputs, state rows, fail_count, last_obs, counters.
+ * clock as for earl_minitaur_rollout_clocked (may be NULL).  The kernel is picked by the plain entry point's rule (one-wave kernel in its three launch shapes, two-wave
+ * kernel; earl_debug_set_solo_mt, earl_debug_set_minitaur_duo); both forms return the same bits.
+ * EARL_ERR_ARG before any HIP call: everything earl_minitaur_rollout_clocked refuses, NULL policy / obs0 / actions, dims[0] != 32, a last layer that is not 8 (16 with a
+ * head) wide, hidden widths outside the rule, n_layers not 2 or 3, precision != 0, misaligned or NULL params, unknown activations, head fields out of range (as
+ * earl_tabletop_policy_rollout_gaussian), and out_act != EARL_ACT_TANH: the reference env raises on an action outside +-(1 + 0.01), a kernel cannot, and the open-loop
+ * replay of the returned actions must not raise either, so the minitaur takes bounded policies only.  The generic-stepper comparison build
+ * (earl_debug_set_minitaur_stepper(0)) has no policy form: EARL_ERR_ARG.  n = 0 or T = 0: EARL_OK, nothing launched. */
+int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                 const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
+                                 const earl_minitaur_out* out, earl_stream_t stream);
 /* reset the envs with mask[i] != 0 (NULL = all); obs [n, 32] (may be NULL) is written for the reset envs only */
 int earl_minitaur_reset(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                         const uint8_t* mask, double* obs, earl_stream_t stream);

@@ -2,6 +2,7 @@
 // stepper's own entry points earl_physics_step / _forward (nv = 23 forwarded to physics_kitchen.hip, 64 lanes per env to physics_l64.hip), the Sawyer env's
 // entry points (the door's eight-wave rollout forwarded to physics_w8.hip), the collision-table cone cache of all units, and the size queries and debug switches.
 #include "physics_stepper.h"
+#include "policy_check.h"
 #include "policy_math.h"
 
 #include <mutex>
@@ -168,41 +169,16 @@ static int sawyer_closed_loop(const earl_link_model* model, const earl_collision
   if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal) return EARL_ERR_ARG;
   if (!out->obs && !st->last_obs) return EARL_ERR_ARG;    // (without out->obs the env's row of last_obs is the one observation row the launch keeps)
   if (nv != 10 && nv != 15) return EARL_ERR_ARG;
-  if (!policy->params || ((uintptr_t)policy->params & 15) || policy->precision != 0) return EARL_ERR_ARG;      // (16-byte loads of the weight rows)
-  if (policy->n_layers != 2 && policy->n_layers != 3) return EARL_ERR_ARG;
-  if (policy->dims[0] != 14 || policy->dims[policy->n_layers] != (head ? 8 : 4)) return EARL_ERR_ARG;
-  for (int l = 1; l < policy->n_layers; ++l)
-    if (policy->dims[l] < 16 || policy->dims[l] > earl::kPolicyMaxWidth || policy->dims[l] % 16) return EARL_ERR_ARG;
-  if (policy->n_layers == 2 && policy->dims[3] != 0) return EARL_ERR_ARG;
-  if (policy->hidden_act != EARL_ACT_RELU && policy->hidden_act != EARL_ACT_TANH) return EARL_ERR_ARG;
-  if (policy->out_act != EARL_ACT_NONE && policy->out_act != EARL_ACT_TANH) return EARL_ERR_ARG;
-  if (head) {
-    if (head->mode != EARL_HEAD_MEAN && head->mode != EARL_HEAD_SAMPLE) return EARL_ERR_ARG;
-    if (head->log_std_map != EARL_LOGSTD_CLAMP && head->log_std_map != EARL_LOGSTD_TANH) return EARL_ERR_ARG;
-    if (!(head->log_std_min >= -20.0f && head->log_std_max <= 4.0f && head->log_std_min <= head->log_std_max)) return EARL_ERR_ARG;      // (NaN fails every comparison)
-  }
+  // the policy's contract (policy_check.h); the weight rows are read in 16-byte pieces, so params is aligned and every stride a multiple of 4 floats
+  if (earl::contract::check_policy(*policy, 14, 4, head, earl::contract::kParamsAligned16, nullptr)) return EARL_ERR_ARG;
   if (cfg->frame_skip < 0 || cfg->att_hand < 0 || cfg->att_right < 0 || cfg->att_left < 0 || cfg->att_obj < 0) return EARL_ERR_ARG;
   if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;
   if (cfg->n_goal_rows > 0 && !cfg->goal_table) return EARL_ERR_ARG;
   if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && (!st->obj_init || cfg->att_grasp < 0 || cfg->att_lpad < 0 || cfg->att_rpad < 0)) return EARL_ERR_ARG;
   if (nv == 15 && cfg->obj_kind >= 1 && out->info && !st->obj_init) return EARL_ERR_ARG;
-  if (pop) {
-    // the tabletop population's rules (include/earl_tabletop.h), and strides of whole 16-byte pieces: every member's rows are read as float4
-    int64_t count = 0;
-    for (int l = 0; l < policy->n_layers; ++l) count += (int64_t)policy->dims[l + 1] * (policy->dims[l] + 1);
-    if (pop->n_policies < 1 || pop->envs_per_policy < 16 || pop->envs_per_policy % 16 || pop->param_stride < count || pop->param_stride % 4) return EARL_ERR_ARG;
-    if (cfg->env_offset < 0) return EARL_ERR_ARG;
-    if (cfg->n > 0 && ((int64_t)cfg->env_offset + cfg->n - 1) / pop->envs_per_policy >= pop->n_policies) return EARL_ERR_ARG;
-  }
+  if (pop && earl::contract::check_population(*policy, *pop, cfg->env_offset, cfg->n, 16, 4, nullptr)) return EARL_ERR_ARG;
   if (paired) {
-    // include/earl_physics.h, earl_sawyer_pair_rollout: the tabletop pair's rules, the population's stride rule, and a backward goal only where the forward one can be restored
-    int64_t count = 0;
-    for (int l = 0; l < policy->n_layers; ++l) count += (int64_t)policy->dims[l + 1] * (policy->dims[l] + 1);
-    if (!pair || !pair->phase || !pair->steps_in_phase) return EARL_ERR_ARG;
-    if (pair->switch_every[0] < 1 || pair->switch_every[1] < 1) return EARL_ERR_ARG;
-    if (pair->switch_on_success != 0 && pair->switch_on_success != 1) return EARL_ERR_ARG;
-    if (pair->param_stride < count || pair->param_stride % 4) return EARL_ERR_ARG;
-    if (cfg->goal_change_frequency > 0) return EARL_ERR_ARG;               // (the pair IS the lifelong mechanism)
+    if (earl::contract::check_pair(*policy, pair, cfg->goal_change_frequency, 4, nullptr)) return EARL_ERR_ARG;
     if (pair->backward_goal && cfg->n_goal_rows == 0) return EARL_ERR_ARG;   // (the forward goal could not be restored)
   }
   if (g_lpe == 64) return EARL_ERR_ARG;                   // (the 64-lane measurement builds: no policy form)
@@ -211,7 +187,7 @@ static int sawyer_closed_loop(const earl_link_model* model, const earl_collision
   SawyerPolicyArgs a;
   static_cast<SawyerArgs&>(a) = SawyerArgs{model, col, *cfg, *st, nullptr, T, *out, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
   a.pol = *policy;
-  a.head = head ? *head : earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr};
+  a.head = head ? *head : earl::contract::default_head();
   a.gauss = head ? 1 : 0;
   a.obs0 = obs0;
   a.act_out = actions;

@@ -6,6 +6,7 @@
 // earl_minitaur_reset.  A translation unit of its own so that the three builds compile side by side.
 #include "minitaur_device.h"
 #include "physics_stepper.h"
+#include "policy_check.h"
 #include "policy_math.h"
 
 namespace {
@@ -59,27 +60,16 @@ int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model
   if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
   if (!out->obs || !out->reward || !out->done || !out->success || !cfg->goal_table || cfg->n_goals < 1 || cfg->num_substeps < 0) return EARL_ERR_ARG;
   if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;
-  if (!policy->params || ((uintptr_t)policy->params & 15) || policy->precision != 0) return EARL_ERR_ARG;      // (16-byte loads of the weight rows)
-  if (policy->n_layers != 2 && policy->n_layers != 3) return EARL_ERR_ARG;
-  if (policy->dims[0] != 32 || policy->dims[policy->n_layers] != (head ? 16 : 8)) return EARL_ERR_ARG;
-  for (int l = 1; l < policy->n_layers; ++l)
-    if (policy->dims[l] < 16 || policy->dims[l] > earl::kPolicyMaxWidth || policy->dims[l] % 16) return EARL_ERR_ARG;
-  if (policy->n_layers == 2 && policy->dims[3] != 0) return EARL_ERR_ARG;
-  if (policy->hidden_act != EARL_ACT_RELU && policy->hidden_act != EARL_ACT_TANH) return EARL_ERR_ARG;
-  // the reference env raises on an action outside +-(1 + 0.01); a kernel cannot, and the open-loop replay of the returned actions must not either: bounded policies only
-  if (policy->out_act != EARL_ACT_TANH) return EARL_ERR_ARG;
-  if (head) {
-    if (head->mode != EARL_HEAD_MEAN && head->mode != EARL_HEAD_SAMPLE) return EARL_ERR_ARG;
-    if (head->log_std_map != EARL_LOGSTD_CLAMP && head->log_std_map != EARL_LOGSTD_TANH) return EARL_ERR_ARG;
-    if (!(head->log_std_min >= -20.0f && head->log_std_max <= 4.0f && head->log_std_min <= head->log_std_max)) return EARL_ERR_ARG;      // (NaN fails every comparison)
-  }
+  // the policy's contract (policy_check.h).  The reference env raises on an action outside +-(1 + 0.01); a kernel cannot, and the open-loop replay of the returned
+  // actions must not either: bounded policies only
+  if (earl::contract::check_policy(*policy, 32, 8, head, earl::contract::kParamsAligned16 | earl::contract::kBoundedOutput, nullptr)) return EARL_ERR_ARG;
   if (!g_mt_stepper) return EARL_ERR_ARG;                 // (earl_debug_set_minitaur_stepper(0): no policy form)
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_policy_rollout")) return rc;
   MinitaurPolicyArgs a;
   static_cast<MinitaurArgs&>(a) = MinitaurArgs{model24, col, *cfg, *st, *out, nullptr, T, nullptr, nullptr, solo_mode(cfg->n), clock};
   a.pol = *policy;
-  a.head = head ? *head : earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr};
+  a.head = head ? *head : earl::contract::default_head();
   a.gauss = head ? 1 : 0;
   a.obs0 = obs0;
   a.act_out = actions;

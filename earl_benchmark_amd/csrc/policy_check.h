@@ -1,0 +1,106 @@
+// policy_check.h -- the host-side contract of a closed-loop launch's policy arguments (earl_mlp_policy, earl_gaussian_head, earl_policy_population, earl_agent_pair),
+// stated once for every entry point that takes them: the tabletop's four (tabletop_policy.h, both libraries), the Sawyer door / peg's three (physics.hip), the
+// minitaur's (physics_mt.hip) and earl_mlp_policy_forward_cpu (tabletop_host.cpp).  Host only; it needs the ABI structs and kPolicyMaxWidth and nothing of any env.
+// What differs between the callers is an argument: the widths, the rules below, the population's group size, the stride multiple.  Every check returns EARL_OK or
+// EARL_ERR_ARG; `err` is NULL (the physics entry points return the bare code) or kErrLen bytes that receive the message (the tabletop's thread-local g_err).
+#pragma once
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+
+#include "policy_math.h"
+
+namespace earl {
+namespace contract {
+
+constexpr size_t kErrLen = 512;
+
+inline int refuse(char* err, const char* fmt, ...) {
+  if (err) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(err, kErrLen, fmt, ap);
+    va_end(ap);
+  }
+  return EARL_ERR_ARG;
+}
+
+// what an entry point asks of a policy beyond the common rules: params 16-byte aligned (the stepper units read the weight rows in 16-byte pieces); out_act tanh
+// (the minitaur: the reference env raises on an action outside +-(1 + 0.01) and a kernel cannot)
+enum : unsigned { kParamsAligned16 = 1u, kBoundedOutput = 2u };
+
+// the head of a launch without one (the kernels' argument structs always carry a head)
+inline earl_gaussian_head default_head() { return earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr}; }
+
+// floats of one policy in the packing order W_0, b_0, W_1, b_1, ...  (after check_form: n_layers is 2 or 3)
+inline int64_t mlp_param_count(const earl_mlp_policy& p) {
+  int64_t count = 0;
+  for (int l = 0; l < p.n_layers; ++l) count += (int64_t)p.dims[l + 1] * (p.dims[l] + 1);
+  return count;
+}
+
+// precision, layer count and activations: what holds whatever the widths are
+inline int check_form(const earl_mlp_policy& p, char* err) {
+  if (p.precision != 0) return refuse(err, "policy precision = %d: only 0 (fp32) exists", p.precision);
+  if (p.n_layers != 2 && p.n_layers != 3) return refuse(err, "policy n_layers = %d: 2 (one hidden layer) or 3 (two)", p.n_layers);
+  if (p.hidden_act != EARL_ACT_RELU && p.hidden_act != EARL_ACT_TANH) return refuse(err, "policy hidden_act = %d", p.hidden_act);
+  if (p.out_act != EARL_ACT_NONE && p.out_act != EARL_ACT_TANH) return refuse(err, "policy out_act = %d", p.out_act);
+  return EARL_OK;
+}
+
+inline int check_head(const earl_gaussian_head& h, char* err) {
+  if (h.mode != EARL_HEAD_MEAN && h.mode != EARL_HEAD_SAMPLE) return refuse(err, "head mode = %d", h.mode);
+  if (h.log_std_map != EARL_LOGSTD_CLAMP && h.log_std_map != EARL_LOGSTD_TANH) return refuse(err, "head log_std_map = %d", h.log_std_map);
+  if (!(h.log_std_min >= -20.0f && h.log_std_max <= 4.0f && h.log_std_min <= h.log_std_max))       // (NaN fails every comparison)
+    return refuse(err, "head log_std bounds [%g, %g]: finite, min <= max, inside [-20, 4]", (double)h.log_std_min, (double)h.log_std_max);
+  return EARL_OK;
+}
+
+// one policy obs_dim -> hidden (-> hidden) -> act_dim of an in-kernel launch; head: NULL, or the Gaussian head of a last layer 2 act_dim wide (mean, raw log_std)
+inline int check_policy(const earl_mlp_policy& p, int obs_dim, int act_dim, const earl_gaussian_head* head, unsigned rules, char* err) {
+  if (!p.params) return refuse(err, "policy params is NULL");
+  if ((rules & kParamsAligned16) && ((uintptr_t)p.params & 15)) return refuse(err, "policy params is not 16-byte aligned");
+  if (int rc = check_form(p, err)) return rc;
+  const int out_dim = head ? 2 * act_dim : act_dim;
+  if (p.dims[0] != obs_dim || p.dims[p.n_layers] != out_dim)
+    return refuse(err, "policy dims: input %d, output %d (want %d and %d)", p.dims[0], p.dims[p.n_layers], obs_dim, out_dim);
+  for (int l = 1; l < p.n_layers; ++l)
+    if (p.dims[l] < 16 || p.dims[l] > kPolicyMaxWidth || p.dims[l] % 16) return refuse(err, "policy hidden width %d: a multiple of 16 in 16..256", p.dims[l]);
+  if (p.n_layers == 2 && p.dims[3] != 0) return refuse(err, "policy dims[3] = %d is unused and must be 0", p.dims[3]);
+  if ((rules & kBoundedOutput) && p.out_act != EARL_ACT_TANH) return refuse(err, "policy out_act = %d: this env takes bounded policies only (EARL_ACT_TANH)", p.out_act);
+  return head ? check_head(*head, err) : EARL_OK;
+}
+
+// a population of checked policies over the envs with global ids env_offset .. env_offset + n - 1: `group` envs share their weights' loads (16 everywhere today), and
+// the rows of params are `stride_multiple` floats apart at least (4 where a member's rows are read in 16-byte pieces)
+inline int check_population(const earl_mlp_policy& p, const earl_policy_population& pop, int32_t env_offset, int32_t n, int group, int stride_multiple, char* err) {
+  if (pop.n_policies < 1) return refuse(err, "population n_policies = %d < 1", pop.n_policies);
+  if (pop.envs_per_policy < group || pop.envs_per_policy % group)
+    return refuse(err, "population envs_per_policy = %d: a multiple of %d, >= %d", pop.envs_per_policy, group, group);
+  const int64_t count = mlp_param_count(p);
+  if (pop.param_stride < count) return refuse(err, "population param_stride = %lld < %lld parameters of one policy", (long long)pop.param_stride, (long long)count);
+  if (pop.param_stride % stride_multiple) return refuse(err, "population param_stride = %lld: a multiple of %d", (long long)pop.param_stride, stride_multiple);
+  if (env_offset < 0) return refuse(err, "population: env_offset = %d < 0", env_offset);
+  const int64_t last = (int64_t)env_offset + n - 1;
+  if (n > 0 && last / pop.envs_per_policy >= pop.n_policies)
+    return refuse(err, "population: global env id %lld runs policy %lld of %d", (long long)last, (long long)(last / pop.envs_per_policy), pop.n_policies);
+  return EARL_OK;
+}
+
+// the forward / reset pair of a checked policy; goal_change_frequency: the env's (the pair IS the lifelong mechanism)
+inline int check_pair(const earl_mlp_policy& p, const earl_agent_pair* pair, int32_t goal_change_frequency, int stride_multiple, char* err) {
+  if (!pair) return refuse(err, "pair is NULL");
+  if (!pair->phase || !pair->steps_in_phase) return refuse(err, "pair phase/steps_in_phase is NULL");
+  for (int k = 0; k < 2; ++k)
+    if (pair->switch_every[k] < 1) return refuse(err, "pair switch_every[%d] = %d < 1", k, pair->switch_every[k]);
+  if (pair->switch_on_success != 0 && pair->switch_on_success != 1) return refuse(err, "pair switch_on_success = %d", pair->switch_on_success);
+  const int64_t count = mlp_param_count(p);
+  if (pair->param_stride < count) return refuse(err, "pair param_stride = %lld < %lld parameters of one agent", (long long)pair->param_stride, (long long)count);
+  if (pair->param_stride % stride_multiple) return refuse(err, "pair param_stride = %lld: a multiple of %d", (long long)pair->param_stride, stride_multiple);
+  if (goal_change_frequency > 0)
+    return refuse(err, "pair: goal_change_frequency = %d > 0 (the pair is the lifelong mechanism: the two clocks would fight over the same draw)", goal_change_frequency);
+  return EARL_OK;
+}
+
+}  // namespace contract
+}  // namespace earl

@@ -135,7 +135,7 @@ int earl_tabletop_eval_episodes_cpu(const earl_tabletop_cfg* cfg, const earl_tab
 }
 int earl_tabletop_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, int32_t episodes, int32_t T,
                                      int32_t reset_first, const earl_tabletop_out* out, float* act_out) {
-  if (int rc = check_policy(cfg, st, policy, episodes, T, reset_first, out)) return rc;
+  if (int rc = check_policy(cfg, st, policy, nullptr, episodes, T, reset_first, out)) return rc;
   if (cfg->n == 0) return EARL_OK;
   const PolicyArgs a{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, thresholds()}, *policy, act_out, episodes, reset_first};
   if (cfg->goal_change_frequency > 0 || cfg->auto_reset) for_each_env(cfg->n, [&](int i) { policy_rollout_env<true>(a, i, a.p.params); });
@@ -220,21 +220,14 @@ int earl_tabletop3_reward_cpu(int32_t n, const float* obs, int32_t reward_type, 
 // include/earl_physics.h: the policy contract as plain loops, any input / action width (the oracle of the Sawyer rollout's in-kernel policy)
 int32_t earl_mlp_policy_forward_cpu(const earl_mlp_policy* p, const earl_gaussian_head* h, int32_t n, const float* obs, const float* eps, float* actions) {
   if (!p || !p->params || !obs || !actions || n < 0) return fail(EARL_ERR_ARG, "policy/params/obs/actions is NULL or n < 0");
-  if (p->precision != 0) return fail(EARL_ERR_ARG, "policy precision = %d: only 0 (fp32) exists", p->precision);
-  if (p->n_layers != 2 && p->n_layers != 3) return fail(EARL_ERR_ARG, "policy n_layers = %d: 2 (one hidden layer) or 3 (two)", p->n_layers);
-  for (int l = 0; l < p->n_layers; ++l)
+  if (int rc = contract::check_form(*p, g_err)) return rc;
+  for (int l = 0; l < p->n_layers; ++l)                    // (its own width rule: any width 1..256 at every position, the input included)
     if (p->dims[l] < 1 || p->dims[l] > kPolicyMaxWidth) return fail(EARL_ERR_ARG, "policy dims[%d] = %d: 1..256", l, p->dims[l]);
   const int NL = p->dims[p->n_layers];
   if (NL < 1 || NL > kPolicyMaxWidth || (h && NL % 2)) return fail(EARL_ERR_ARG, "policy output width %d", NL);
-  if (p->hidden_act != EARL_ACT_RELU && p->hidden_act != EARL_ACT_TANH) return fail(EARL_ERR_ARG, "policy hidden_act = %d", p->hidden_act);
-  if (p->out_act != EARL_ACT_NONE && p->out_act != EARL_ACT_TANH) return fail(EARL_ERR_ARG, "policy out_act = %d", p->out_act);
-  if (h) {
-    if (h->mode != EARL_HEAD_MEAN && h->mode != EARL_HEAD_SAMPLE) return fail(EARL_ERR_ARG, "head mode = %d", h->mode);
-    if (h->log_std_map != EARL_LOGSTD_CLAMP && h->log_std_map != EARL_LOGSTD_TANH) return fail(EARL_ERR_ARG, "head log_std_map = %d", h->log_std_map);
-    if (!(h->log_std_min >= -20.0f && h->log_std_max <= 4.0f && h->log_std_min <= h->log_std_max)) return fail(EARL_ERR_ARG, "head log_std bounds");
-  }
+  if (h && contract::check_head(*h, g_err)) return EARL_ERR_ARG;
   const int A = h ? NL / 2 : NL;
-  earl_gaussian_head head = h ? *h : earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr};
+  earl_gaussian_head head = h ? *h : contract::default_head();
   if (!eps) head.mode = EARL_HEAD_MEAN;
   for_each_env(n, [&](int i) {
     float buf[2][kPolicyMaxWidth];

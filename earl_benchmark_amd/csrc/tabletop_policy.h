@@ -14,6 +14,7 @@
 // Held on the device by tests/test_policy_widths_gpu.py: every instantiation (NT2 x GENERAL x head x POP, and the pair's) and every hidden width 16 .. 256 at
 // every layer position against the host twin bit for bit, the wide shapes also against an exact integer reference (the lane maps).
 #pragma once
+#include "policy_check.h"
 #include "policy_math.h"
 #include "tabletop_hostside.h"
 #include "tabletop_step.h"
@@ -70,20 +71,14 @@ __host__ __device__ __forceinline__ void episode_sum_store(const earl_episode_su
 
 namespace hostside {
 
-inline int check_policy(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, int32_t episodes, int32_t T,
-                        int32_t reset_first, const earl_tabletop_out* out, int out_dim = EARL_TABLETOP_ACT_DIM) {
+// the deterministic entry point (h == NULL: a 3-wide last layer) or the Gaussian head's (6-wide, then the head's rules): the env's checks, the policy's
+// (policy_check.h), the launch's own
+inline int check_policy(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_gaussian_head* h, int32_t episodes, int32_t T,
+                        int32_t reset_first, const earl_tabletop_out* out) {
+  static_assert(sizeof g_err >= contract::kErrLen, "policy_check.h writes its messages into g_err");
   if (int rc = check_common(cfg, st, 1)) return rc;
   if (!p || !out) return fail(EARL_ERR_ARG, "policy/out is NULL");
-  if (!p->params) return fail(EARL_ERR_ARG, "policy params is NULL");
-  if (p->precision != 0) return fail(EARL_ERR_ARG, "policy precision = %d: only 0 (fp32) exists", p->precision);
-  if (p->n_layers != 2 && p->n_layers != 3) return fail(EARL_ERR_ARG, "policy n_layers = %d: 2 (one hidden layer) or 3 (two)", p->n_layers);
-  if (p->dims[0] != EARL_TABLETOP_OBS_DIM || p->dims[p->n_layers] != out_dim)
-    return fail(EARL_ERR_ARG, "policy dims: input %d, output %d (want 12 and %d)", p->dims[0], p->dims[p->n_layers], out_dim);
-  for (int l = 1; l < p->n_layers; ++l)
-    if (p->dims[l] < 16 || p->dims[l] > kPolicyMaxWidth || p->dims[l] % 16) return fail(EARL_ERR_ARG, "policy hidden width %d: a multiple of 16 in 16..256", p->dims[l]);
-  if (p->n_layers == 2 && p->dims[3] != 0) return fail(EARL_ERR_ARG, "policy dims[3] = %d is unused and must be 0", p->dims[3]);
-  if (p->hidden_act != EARL_ACT_RELU && p->hidden_act != EARL_ACT_TANH) return fail(EARL_ERR_ARG, "policy hidden_act = %d", p->hidden_act);
-  if (p->out_act != EARL_ACT_NONE && p->out_act != EARL_ACT_TANH) return fail(EARL_ERR_ARG, "policy out_act = %d", p->out_act);
+  if (int rc = contract::check_policy(*p, EARL_TABLETOP_OBS_DIM, EARL_TABLETOP_ACT_DIM, h, 0, g_err)) return rc;
   if (T < 1) return fail(EARL_ERR_ARG, "T = %d < 1", T);
   if (episodes < 1) return fail(EARL_ERR_ARG, "episodes = %d < 1", episodes);
   if (reset_first != 0 && reset_first != 1) return fail(EARL_ERR_ARG, "reset_first = %d", reset_first);
@@ -91,34 +86,18 @@ inline int check_policy(const earl_tabletop_cfg* cfg, const earl_tabletop_state*
   return EARL_OK;
 }
 
-// the Gaussian-head entry points: the policy's checks with a 6-wide last layer (mean, raw log_std), then the head's
+// the Gaussian-head entry points: the head is not optional
 inline int check_policy_gaussian(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_gaussian_head* h,
                                  int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out) {
-  if (int rc = check_policy(cfg, st, p, episodes, T, reset_first, out, 2 * EARL_TABLETOP_ACT_DIM)) return rc;
   if (!h) return fail(EARL_ERR_ARG, "head is NULL");
-  if (h->mode != EARL_HEAD_MEAN && h->mode != EARL_HEAD_SAMPLE) return fail(EARL_ERR_ARG, "head mode = %d", h->mode);
-  if (h->log_std_map != EARL_LOGSTD_CLAMP && h->log_std_map != EARL_LOGSTD_TANH) return fail(EARL_ERR_ARG, "head log_std_map = %d", h->log_std_map);
-  if (!(h->log_std_min >= -20.0f && h->log_std_max <= 4.0f && h->log_std_min <= h->log_std_max))       // (NaN fails every comparison)
-    return fail(EARL_ERR_ARG, "head log_std bounds [%g, %g]: finite, min <= max, inside [-20, 4]", (double)h->log_std_min, (double)h->log_std_max);
-  return EARL_OK;
+  return check_policy(cfg, st, p, h, episodes, T, reset_first, out);
 }
 
-// earl_tabletop_population_rollout: the checks of the head's single-policy entry point, then the population's
+// earl_tabletop_population_rollout: the checks of the head's single-policy entry point, then the population's (one member per 16-env workgroup, any stride)
 inline int check_population(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_policy_population* pop,
                             const earl_gaussian_head* h, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out) {
-  if (int rc = h ? check_policy_gaussian(cfg, st, p, h, episodes, T, reset_first, out) : check_policy(cfg, st, p, episodes, T, reset_first, out)) return rc;
-  if (!pop) return EARL_OK;
-  if (pop->n_policies < 1) return fail(EARL_ERR_ARG, "population n_policies = %d < 1", pop->n_policies);
-  if (pop->envs_per_policy < kPolicyEnvsPerWg || pop->envs_per_policy % kPolicyEnvsPerWg)
-    return fail(EARL_ERR_ARG, "population envs_per_policy = %d: a multiple of 16, >= 16", pop->envs_per_policy);
-  int64_t count = 0;
-  for (int l = 0; l < p->n_layers; ++l) count += (int64_t)p->dims[l + 1] * (p->dims[l] + 1);
-  if (pop->param_stride < count) return fail(EARL_ERR_ARG, "population param_stride = %lld < %lld parameters of one policy", (long long)pop->param_stride, (long long)count);
-  if (cfg->env_offset < 0) return fail(EARL_ERR_ARG, "population: env_offset = %d < 0", cfg->env_offset);
-  if (cfg->n > 0 && ((int64_t)cfg->env_offset + cfg->n - 1) / pop->envs_per_policy >= pop->n_policies)
-    return fail(EARL_ERR_ARG, "population: global env id %lld runs policy %lld of %d", (long long)cfg->env_offset + cfg->n - 1,
-                ((long long)cfg->env_offset + cfg->n - 1) / pop->envs_per_policy, pop->n_policies);
-  return EARL_OK;
+  if (int rc = check_policy(cfg, st, p, h, episodes, T, reset_first, out)) return rc;
+  return pop ? contract::check_population(*p, *pop, cfg->env_offset, cfg->n, kPolicyEnvsPerWg, 1, g_err) : EARL_OK;
 }
 
 inline PopulationArgs population_args(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_policy_population* pop,
@@ -126,26 +105,17 @@ inline PopulationArgs population_args(const earl_tabletop_cfg* cfg, const earl_t
                                       const earl_episode_summary* sum, const Thresholds& th) {
   PopulationArgs a;
   static_cast<PolicyArgs&>(a) = PolicyArgs{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, th}, *p, act_out, episodes, reset_first};
-  a.head = h ? *h : earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr};
+  a.head = h ? *h : contract::default_head();
   a.pop = pop ? *pop : earl_policy_population{1, 0, 0};
   a.sum = sum ? *sum : earl_episode_summary{nullptr, nullptr, nullptr};
   return a;
 }
 
-// earl_tabletop_pair_rollout: the checks of the head's single-policy entry point, then the pair's
+// earl_tabletop_pair_rollout: the checks of the head's single-policy entry point, then the pair's (any stride) and the register budget of two weight sets
 inline int check_pair(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_agent_pair* pair, const earl_gaussian_head* h,
                       int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out) {
-  if (int rc = h ? check_policy_gaussian(cfg, st, p, h, episodes, T, reset_first, out) : check_policy(cfg, st, p, episodes, T, reset_first, out)) return rc;
-  if (!pair) return fail(EARL_ERR_ARG, "pair is NULL");
-  if (!pair->phase || !pair->steps_in_phase) return fail(EARL_ERR_ARG, "pair phase/steps_in_phase is NULL");
-  for (int k = 0; k < 2; ++k)
-    if (pair->switch_every[k] < 1) return fail(EARL_ERR_ARG, "pair switch_every[%d] = %d < 1", k, pair->switch_every[k]);
-  if (pair->switch_on_success != 0 && pair->switch_on_success != 1) return fail(EARL_ERR_ARG, "pair switch_on_success = %d", pair->switch_on_success);
-  int64_t count = 0;
-  for (int l = 0; l < p->n_layers; ++l) count += (int64_t)p->dims[l + 1] * (p->dims[l] + 1);
-  if (pair->param_stride < count) return fail(EARL_ERR_ARG, "pair param_stride = %lld < %lld parameters of one agent", (long long)pair->param_stride, (long long)count);
-  if (cfg->goal_change_frequency > 0)
-    return fail(EARL_ERR_ARG, "pair: goal_change_frequency = %d > 0 (the pair is the lifelong mechanism: the two clocks would fight over the same draw)", cfg->goal_change_frequency);
+  if (int rc = check_policy(cfg, st, p, h, episodes, T, reset_first, out)) return rc;
+  if (int rc = contract::check_pair(*p, pair, cfg->goal_change_frequency, 1, g_err)) return rc;
   if (p->n_layers == 3 && p->dims[2] > kPairMaxH2)
     return fail(EARL_ERR_ARG, "pair: second hidden width %d > EARL_PAIR_MAX_H2 = %d (two weight sets in one wave's registers)", p->dims[2], kPairMaxH2);
   return EARL_OK;
@@ -155,7 +125,7 @@ inline PairArgs pair_args(const earl_tabletop_cfg* cfg, const earl_tabletop_stat
                           int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out, const Thresholds& th) {
   PairArgs a;
   static_cast<PolicyArgs&>(a) = PolicyArgs{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, th}, *p, act_out, episodes, reset_first};
-  a.head = h ? *h : earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr};
+  a.head = h ? *h : contract::default_head();
   a.pair = *pair;
   return a;
 }

@@ -19,7 +19,7 @@ void launch_policy(const PolicyArgs& a, bool general, dim3 grid, hipStream_t s) 
 
 extern "C" int earl_tabletop_policy_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, int32_t episodes,
                                             int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out, earl_stream_t stream) {
-  if (int rc = check_policy(cfg, st, policy, episodes, T, reset_first, out)) return rc;      // (before any HIP call: testable without a GPU)
+  if (int rc = check_policy(cfg, st, policy, nullptr, episodes, T, reset_first, out)) return rc;      // (before any HIP call: testable without a GPU)
   if (cfg->n == 0) return EARL_OK;
   const PolicyArgs a{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, thresholds()}, *policy, act_out, episodes, reset_first};
   const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;

@@ -21,6 +21,7 @@ import torch
 
 from .. import _abi, physics
 from ..spaces import Box
+from . import physics_policy_rollout as closed_loop
 from .physics_step_graph import PhysicsStepGraph
 
 INT32_MAX = 2**31 - 1
@@ -122,6 +123,11 @@ class Minitaur:
                 done=torch.empty(*lead, self.num_envs, dtype=torch.bool, **kw), success=torch.empty(*lead, self.num_envs, dtype=torch.bool, **kw),
                 status=torch.empty(*lead, self.num_envs, dtype=torch.uint8, **kw))
 
+  @staticmethod
+  def _out_struct(res):
+    return _abi.MinitaurOut(obs=res['obs'].data_ptr(), reward=res['reward'].data_ptr(), done=res['done'].data_ptr(), success=res['success'].data_ptr(),
+                            status=res['status'].data_ptr())
+
   # ------------------------------------------------------------------ gym-style API
   def reset(self, mask=None):
     """GoalConditionedMinitaurBulletEnv.reset (:476-479) of the (masked) envs -> obs [N, 32] (numpy [32] with scalar_api)"""
@@ -155,81 +161,36 @@ class Minitaur:
       T = int(torch.as_tensor(actions).shape[0])
       a = self._actions(actions, (T,))
       res = out if out is not None else self._new_out((T,))
-      o = _abi.MinitaurOut(obs=res['obs'].data_ptr(), reward=res['reward'].data_ptr(), done=res['done'].data_ptr(), success=res['success'].data_ptr(),
-                           status=res['status'].data_ptr())
       self._cfg.step_counter = self.total_step_count
       if T > 0:
         _abi.check(self._lib.earl_minitaur_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), a.data_ptr(), T,
-                                                   C.byref(o), self._stream()), 'earl_minitaur_rollout')
-        if int(self._cfg.goal_change_frequency) > 0:
-          self.lifelong_return_t += res['reward'].sum(0)
-        self._last_success = res['success'][-1]
-        self._last_obs_stale = False                       # (every env's last_obs row was rewritten)
-    self.total_step_count += T
+                                                   C.byref(self._out_struct(res)), self._stream()), 'earl_minitaur_rollout')
+        closed_loop.finish(self, T, res['reward'], res['success'][-1])
     return res
 
   def _check_policy(self, policy, who):
     """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy of this env's widths on this env's device whose output is bounded"""
-    from ..policy import AgentPair, GaussianMLPPolicy, MLPPolicy, PolicyPopulation
+    from ..policy import AgentPair, PolicyPopulation, require_widths
     if isinstance(policy, PolicyPopulation):
       raise NotImplementedError(f'{who}: a PolicyPopulation on the minitaur is not offered (one MLPPolicy / GaussianMLPPolicy per launch; populations run on the tabletop, '
                                 'the Sawyer door and the Sawyer peg)')
     if isinstance(policy, AgentPair):
       raise NotImplementedError(f'{who}: an AgentPair on the minitaur is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
-    if not isinstance(policy, MLPPolicy):
-      raise ValueError(f'{who}: an MLPPolicy or a GaussianMLPPolicy')
-    if (policy.obs_dim, policy.act_dim) != (OBS_DIM, ACT_DIM):
-      raise ValueError(f'{who}: a policy of observation width {policy.obs_dim} and action width {policy.act_dim}; this env takes {OBS_DIM} and {ACT_DIM} '
-                       f'(MLPPolicy(..., obs_dim={OBS_DIM}, act_dim={ACT_DIM}))')
-    if policy.device != self.device:
-      raise ValueError(f'{who}: the policy is on {policy.device}, the env on {self.device} (policy.to(device))')
-    gaussian = isinstance(policy, GaussianMLPPolicy)
-    if policy.out_act != 'tanh':
-      given = 'GaussianMLPPolicy(..., squash=False)' if gaussian else f'MLPPolicy(..., out_act={policy.out_act!r})'
-      raise ValueError(f'{who}: {given} is unbounded; the reference env raises on an action outside +-{ACTION_BOUND + ACTION_EPS} and a kernel cannot, so the minitaur '
-                       "takes bounded policies only: MLPPolicy(..., out_act='tanh') or GaussianMLPPolicy(..., squash=True)")
-    return gaussian
+    return require_widths(policy, who, OBS_DIM, ACT_DIM, env=self, bounded=ACTION_BOUND + ACTION_EPS)
+
+  def _launch_policy(self, policy, head, obs0, T, out):
+    """hook of physics_policy_rollout: earl_minitaur_policy_rollout"""
+    self._cfg.step_counter = self.total_step_count
+    with torch.cuda.device(self.device):
+      _abi.check(self._lib.earl_minitaur_policy_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), C.byref(policy.struct),
+                                                        None if head is None else C.byref(head), obs0.data_ptr(), T, None, out['actions'].data_ptr(),
+                                                        C.byref(self._out_struct(out)), self._stream()), 'earl_minitaur_policy_rollout')
 
   def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """Closed loop in ONE launch of the rollout kernel (include/earl_physics.h: earl_minitaur_policy_rollout): `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy` built
-    with obs_dim=32, act_dim=8 and a bounded output (out_act='tanh' / squash=True) -- is evaluated between the env steps by the 32 lanes that own the env: observation ->
-    float32 MLP -> action -> env step.
-    -> rollout()'s dict plus 'actions' [T, N, 8] float32 (as the policy produced them) and, with return_noise=True, 'eps' [T, N, 8] (the standard-normal draws as
-    used).  Bit-identical to rollout(out['actions']) from the same state.  The first action is computed from the observation the env last returned (`last_obs`: the row
-    the previous step / rollout / reset emitted, so T launches of one step equal one launch of T); after set_state() or reset_goal() from _get_obs() of the
-    current state and goal.  reset_first=True calls reset() before (a launch of its own).  A Gaussian policy is sampled inside the kernel (sample=True: tanh(mean +
-    exp(log_std) eps), eps from the env's Philox stream keyed by seed, global env id and step counter) or evaluated at its mean (sample=False); both flags are for
-    Gaussian policies only."""
-    gaussian = self._check_policy(policy, 'rollout_policy')
-    if not gaussian and (return_noise or not sample):
-      raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
-    T = int(T)
-    if T < 1:
-      raise ValueError(f'rollout_policy: T = {T} < 1')
-    if reset_first:
-      self.reset()
-    with torch.cuda.device(self.device):
-      res = out if out is not None else self._new_out((T,))
-      if 'actions' not in res:
-        res['actions'] = torch.empty(T, self.num_envs, ACT_DIM, dtype=torch.float32, device=self.device)
-      if return_noise and 'eps' not in res:
-        res['eps'] = torch.empty(T, self.num_envs, ACT_DIM, dtype=torch.float32, device=self.device)
-      # what the policy sees first: the observation the env last returned (st.last_obs, goal entries as patched); after set_state() / reset_goal() that row no longer
-      # describes the env and the observation of the current state and goal is recomputed
-      obs0 = (self._get_obs_t() if self._last_obs_stale else self.last_obs).contiguous()
-      head = policy.head(sample=bool(sample), eps_out=res['eps'] if return_noise else None) if gaussian else None
-      o = _abi.MinitaurOut(obs=res['obs'].data_ptr(), reward=res['reward'].data_ptr(), done=res['done'].data_ptr(), success=res['success'].data_ptr(),
-                           status=res['status'].data_ptr())
-      self._cfg.step_counter = self.total_step_count
-      _abi.check(self._lib.earl_minitaur_policy_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), C.byref(policy.struct),
-                                                        None if head is None else C.byref(head), obs0.data_ptr(), T, None, res['actions'].data_ptr(), C.byref(o),
-                                                        self._stream()), 'earl_minitaur_policy_rollout')
-      if int(self._cfg.goal_change_frequency) > 0:
-        self.lifelong_return_t += res['reward'].sum(0)
-      self._last_success = res['success'][-1]
-      self._last_obs_stale = False                         # (every env's last_obs row was rewritten)
-    self.total_step_count += T
-    return res
+    """physics_policy_rollout's closed loop (its docstring is the contract) on earl_minitaur_policy_rollout: `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy` built with
+    obs_dim=32, act_dim=8 and a bounded output (out_act='tanh' / squash=True), evaluated by the 32 lanes that own the env.
+    -> rollout()'s dict plus 'actions' [T, N, 8] and, with return_noise=True, 'eps' [T, N, 8]"""
+    return closed_loop.rollout_policy(self, policy, T, reset_first, sample, return_noise, out)
 
   def rollout_agents(self, pair, T, **kw):
     raise NotImplementedError('rollout_agents: an AgentPair on the minitaur is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
@@ -269,12 +230,10 @@ class Minitaur:
       self._cfg.step_counter = sc
 
   def _graph_step(self, t, action, out, clock):
-    o = _abi.MinitaurOut(obs=out['obs'].data_ptr(), reward=out['reward'].data_ptr(), done=out['done'].data_ptr(), success=out['success'].data_ptr(),
-                         status=out['status'].data_ptr())
     self._cfg.step_counter = t                             # the goal-switch draws of the captured step t: clock[1] + t
     with torch.cuda.device(self.device):
       _abi.check(self._lib.earl_minitaur_rollout_clocked(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), action.data_ptr(), 1,
-                                                         clock, C.byref(o), self._stream()), 'earl_minitaur_rollout_clocked')
+                                                         clock, C.byref(self._out_struct(out)), self._stream()), 'earl_minitaur_rollout_clocked')
       if int(self._cfg.goal_change_frequency) > 0:
         self.lifelong_return_t += out['reward'].reshape(1, -1).sum(0)
 

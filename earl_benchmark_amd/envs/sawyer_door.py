@@ -20,6 +20,7 @@ import torch
 
 from .. import _abi, physics
 from ..spaces import Box
+from . import physics_policy_rollout as closed_loop
 from .physics_step_graph import PhysicsStepGraph
 
 INT32_MAX = 2**31 - 1
@@ -214,11 +215,7 @@ class SawyerDoor:
     """T env steps and their bookkeeping; policy: None (the actions are given) or what _issue_rollout takes for the closed loop"""
     self._cfg.step_counter = self.total_step_count
     self._issue_rollout(actions, T, out, policy=policy)
-    self.total_step_count += T
-    if self._cfg.goal_change_frequency:
-      self.lifelong_return_t += out['reward'].reshape(T, -1).sum(0, dtype=torch.float64)
-    self._last_success = out['success'][-1] if out['success'].dim() == 2 else out['success']
-    self._last_obs_stale = False                           # (every env's last_obs row was rewritten)
+    closed_loop.finish(self, T, out['reward'], out['success'][-1] if out['success'].dim() == 2 else out['success'])
 
   def _issue_rollout(self, actions, T, out, clock=None, policy=None, summary=None):
     """the launches of T env steps into `out` (the door's info launch included); clock: the device words of earl_sawyer_rollout_clocked (None: earl_sawyer_rollout);
@@ -367,49 +364,19 @@ class SawyerDoor:
 
   def _check_policy(self, policy, who):
     """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy / PolicyPopulation of this env's widths on this env's device"""
-    from ..policy import GaussianMLPPolicy, MLPPolicy, PolicyPopulation
-    population = isinstance(policy, PolicyPopulation)
-    if not population and not isinstance(policy, MLPPolicy):
-      raise ValueError(f'{who}: an MLPPolicy, a GaussianMLPPolicy or a PolicyPopulation of them (an AgentPair goes to rollout_agents)')
-    if (policy.obs_dim, policy.act_dim) != (self.OBS_DIM, 4):
-      raise ValueError(f'{who}: a policy of observation width {policy.obs_dim} and action width {policy.act_dim}; this env takes {self.OBS_DIM} and 4 '
-                       '(MLPPolicy(..., obs_dim=14, act_dim=4))')
-    if policy.device != self.device:
-      raise ValueError(f'{who}: the policy is on {policy.device}, the env on {self.device} (policy.to(device))')
-    if population:
-      lo, hi = int(self._cfg.env_offset), int(self._cfg.env_offset) + self.num_envs - 1
-      if lo < 0 or hi // policy.envs_per_policy >= policy.n_policies:
-        raise ValueError(f'{who}: global env ids {lo} .. {hi} need members up to {hi // policy.envs_per_policy} of {policy.n_policies}')
-    return policy.gaussian if population else isinstance(policy, GaussianMLPPolicy)
+    from ..policy import require_widths
+    return require_widths(policy, who, self.OBS_DIM, 4, env=self)
+
+  def _launch_policy(self, policy, head, obs0, T, out, summary=None):
+    """hook of physics_policy_rollout: earl_sawyer_population_rollout"""
+    self._cfg.step_counter = self.total_step_count
+    self._issue_rollout(None, T, out, policy=(policy, head, obs0), summary=summary)
 
   def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """Closed loop in ONE launch of the rollout kernel (include/earl_physics.h: earl_sawyer_population_rollout): `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy`
-    built with obs_dim=14, act_dim=4, or a `PolicyPopulation` of them (the env with global id g runs member g // envs_per_policy; same returns) -- is evaluated between the env steps by the lanes that own the env: observation -> float32 MLP -> action -> env step.
-    -> rollout()'s dict plus 'actions' [T, N, 4] float32 (as the policy produced them) and, with return_noise=True, 'eps' [T, N, 4] (the standard-normal draws as
-    used).  Bit-identical to rollout(out['actions']) from the same state.  The first action is computed from the observation the env last returned (`last_obs`: the row
-    the previous step / rollout / reset emitted, so T launches of one step equal one launch of T); after set_state() or reset_goal() from _get_obs() of the
-    current state and goal.  reset_first=True calls reset() before (a launch of its own).  A Gaussian policy is sampled inside the kernel (sample=True: tanh(mean + exp(log_std) eps), eps from the env's Philox
-    stream keyed by seed, global env id and step counter) or evaluated at its mean (sample=False); both flags are for Gaussian policies only."""
-    gaussian = self._check_policy(policy, 'rollout_policy')
-    if not gaussian and (return_noise or not sample):
-      raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
-    T = int(T)
-    if T < 1:
-      raise ValueError(f'rollout_policy: T = {T} < 1')
-    if reset_first:
-      self.reset()
-    out = out if out is not None else self._new_out((T,))
-    if 'actions' not in out:
-      out['actions'] = torch.empty(T, self.num_envs, 4, dtype=torch.float32, device=self.device)
-    if return_noise and 'eps' not in out:
-      out['eps'] = torch.empty(T, self.num_envs, 4, dtype=torch.float32, device=self.device)
-    # what the policy sees first: the observation the env last returned (st.last_obs: the row the previous step / rollout / reset emitted, goal block as patched) --
-    # T launches of one step then consume the very rows one launch of T consumes; after set_state() / reset_goal() that row no longer describes the env and the
-    # observation of the current state and goal is recomputed
-    obs0 = self._get_obs_t() if self._last_obs_stale else self.last_obs
-    head = policy.head(sample=bool(sample), eps_out=out['eps'] if return_noise else None) if gaussian else None
-    self._launch_rollout(None, T, out, policy=(policy, head, obs0))
-    return out
+    """physics_policy_rollout's closed loop (its docstring is the contract) on earl_sawyer_population_rollout: `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy` built
+    with obs_dim=14, act_dim=4, or a `PolicyPopulation` of them (the env with global id g runs member g // envs_per_policy; same returns).
+    -> rollout()'s dict plus 'actions' [T, N, 4] and, with return_noise=True, 'eps' [T, N, 4]"""
+    return closed_loop.rollout_policy(self, policy, T, reset_first, sample, return_noise, out)
 
   def rollout_agents(self, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
     """The forward / reset agent pair of autonomous RL alternating inside ONE launch of the rollout kernel (include/earl_physics.h: earl_sawyer_pair_rollout): `pair` -- an
@@ -419,40 +386,25 @@ class SawyerDoor:
     phase it becomes the goal-table row the lifelong switch would draw at that step.  `goal_t` IS the goal in force and stays as the launch leaves it.
     -> rollout_policy()'s dict plus 'agent' [T, N] int8 (the agent that computed the action); the door's dict has no 'info' (the peg's is written in the kernel and stays).
     Bookkeeping, the first observation, sample / return_noise and reset_first as rollout_policy.  `env.pair_counts`: the phases of this launch that ended by success."""
-    from ..policy import AgentPair
-    if not isinstance(pair, AgentPair):
-      raise ValueError('rollout_agents: pair is an AgentPair')
-    if (pair.obs_dim, pair.act_dim) != (self.OBS_DIM, 4):
-      raise ValueError(f'rollout_agents: a pair of observation width {pair.obs_dim} and action width {pair.act_dim}; this env takes {self.OBS_DIM} and 4 '
-                       '(AgentPair(..., obs_dim=14, act_dim=4))')
-    if pair.device != self.device:
-      raise ValueError(f'rollout_agents: the pair is on {pair.device}, the env on {self.device} (pair.to(device))')
+    from ..policy import require_widths
+    gaussian = require_widths(pair, 'rollout_agents', self.OBS_DIM, 4, env=self, pair=True)
     if self._cfg.goal_change_frequency > 0:
       raise ValueError('rollout_agents: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
                        'not under a LifelongWrapper, whose clock would fight the pair\'s over the same draw')
-    if not pair.gaussian and (return_noise or not sample):
-      raise ValueError('rollout_agents: sample=False / return_noise=True need Gaussian agents (MLPPolicy agents are deterministic)')
-    T = int(T)
-    if T < 1:
-      raise ValueError(f'rollout_agents: T = {T} < 1')
     goal = pair.goal_row(self)                              # ('initial' on the peg: a ValueError naming env.initial_states)
-    if reset_first:
-      self.reset()
     n, kw = self.num_envs, dict(device=self.device)
+    T, out, head, obs0 = closed_loop.prepare(self, 'rollout_agents', pair, gaussian, T, reset_first, sample, return_noise, out,
+                                             what='Gaussian agents (MLPPolicy agents are deterministic)',
+                                             new_out=lambda lead: self._new_out(lead, info=self.nv >= 15 and self.info_mode == 'full'))
     if self.agent_phase is None:
       self.agent_phase = torch.zeros(n, dtype=torch.int8, **kw)
       self.steps_in_phase = torch.zeros(n, dtype=torch.int32, **kw)
-    if out is None:
-      out = self._new_out((T,), info=self.nv >= 15 and self.info_mode == 'full')
-    for k, shape, dt in (('actions', (T, n, 4), torch.float32), ('agent', (T, n), torch.int8)) + ((('eps', (T, n, 4), torch.float32),) if return_noise else ()):
-      if k not in out:
-        out[k] = torch.empty(*shape, dtype=dt, **kw)
+    if 'agent' not in out:
+      out['agent'] = torch.empty(T, n, dtype=torch.int8, **kw)
     fwd, bwd = torch.empty(n, dtype=torch.int32, **kw), torch.empty(n, dtype=torch.int32, **kw)
     ps = _abi.AgentPair(switch_every=(C.c_int32 * 2)(*pair.switch_every), switch_on_success=int(pair.switch_on_success), pad_=0, param_stride=pair.stride,
                         backward_goal=_ptr(goal), phase=self.agent_phase.data_ptr(), steps_in_phase=self.steps_in_phase.data_ptr(),
                         agent_out=out['agent'].data_ptr(), forward_success=fwd.data_ptr(), backward_success=bwd.data_ptr())
-    obs0 = self._get_obs_t() if self._last_obs_stale else self.last_obs
-    head = pair.head(sample=bool(sample), eps_out=out['eps'] if return_noise else None) if pair.gaussian else None
     launch_out = out if self.nv >= 15 else {k: v for k, v in out.items() if k != 'info'}      # (the door's info dict of a pair launch is not offered)
     self._launch_rollout(None, T, launch_out, policy=(pair, head, obs0, ps))
     self._pair_counts = (fwd, bwd)
@@ -491,13 +443,8 @@ class SawyerDoor:
       obs0 = self._get_obs_t() if self._last_obs_stale else self.last_obs
       head = policy.head(sample=bool(sample), eps_out=None) if gaussian else None
       summary = _abi.EpisodeSummary(ret=ret[e].data_ptr(), success_last=succ[e].data_ptr(), first_success=first[e].data_ptr())
-      self._cfg.step_counter = self.total_step_count
-      self._issue_rollout(None, T, {}, policy=(policy, head, obs0), summary=summary)
-      self.total_step_count += T
-      if self._cfg.goal_change_frequency:
-        self.lifelong_return_t += ret[e]
-      self._last_success = succ[e]
-      self._last_obs_stale = False                         # (every env's last_obs row was rewritten)
+      self._launch_policy(policy, head, obs0, T, {}, summary=summary)
+      closed_loop.finish(self, T, ret[e], succ[e])
       guard[e] = self.fail_count - before
     return {'ret': ret, 'success': succ, 'first_success': first, 'guard_steps': guard}
 

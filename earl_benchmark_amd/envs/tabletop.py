@@ -308,10 +308,9 @@ class TabletopManipulation:
     eps from the env's Philox stream keyed by the global env id and the step's counter), sample=False evaluates the actor at its mean;
     return_noise=True appends eps [E,T,N,3], the standard-normal draws as used.  Both are for Gaussian policies only.
     A `PolicyPopulation` goes to earl_tabletop_population_rollout: the env with global id g runs member g // envs_per_policy, same returns."""
-    from ..policy import GaussianMLPPolicy, PolicyPopulation, require_tabletop_widths
+    from ..policy import PolicyPopulation, require_widths
+    gaussian = require_widths(policy, 'rollout_policy', 12, 3, env=self)
     population = isinstance(policy, PolicyPopulation)
-    require_tabletop_widths(policy.template if population else policy, 'rollout_policy')
-    gaussian = policy.gaussian if population else isinstance(policy, GaussianMLPPolicy)
     if not gaussian and (return_noise or not sample):
       raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
     if self.NOBJ != 1:
@@ -323,8 +322,6 @@ class TabletopManipulation:
       if episodes not in (None, 1):
         raise ValueError('rollout_policy: a continuing rollout (reset_first=False) is one episode')
       E, lead = 1, (int(T), self.num_envs)
-    if policy.device != self.device:
-      raise ValueError(f'rollout_policy: the policy is on {policy.device}, the env on {self.device} (policy.to(device))')
     with self._ctx():
       if out is None:
         outs, ostruct = self._new_out(lead)
@@ -334,7 +331,7 @@ class TabletopManipulation:
       actions = torch.empty(*lead, 3, dtype=torch.float32, device=self.device)
       eps = torch.empty(*lead, 3, dtype=torch.float32, device=self.device) if return_noise else None
       if population:
-        rc = self._population_launch(policy, E, int(T), reset_first, ostruct, actions, eps, sample, None)
+        rc = self._population_launch(policy, gaussian, E, int(T), reset_first, ostruct, actions, eps, sample, None)
       elif gaussian:
         head = policy.head(sample=bool(sample), eps_out=eps)
         rc = self._lib.earl_tabletop_policy_rollout_gaussian(self._cfg_ref, self._st_ref, C.byref(policy.struct), C.byref(head), E, int(T),
@@ -350,12 +347,11 @@ class TabletopManipulation:
       return outs + (actions, eps)
     return outs + (actions,)
 
-  def _population_launch(self, policy, E, T, reset_first, ostruct, actions, eps, sample, summary):
+  def _population_launch(self, policy, gaussian, E, T, reset_first, ostruct, actions, eps, sample, summary):
     """earl_tabletop_population_rollout for a PolicyPopulation (pop) or one policy (pop = NULL); -> the return code"""
-    from ..policy import GaussianMLPPolicy, PolicyPopulation
-    population = isinstance(policy, PolicyPopulation)
-    head = policy.head(sample=bool(sample), eps_out=eps) if (policy.gaussian if population else isinstance(policy, GaussianMLPPolicy)) else None
-    return self._lib.earl_tabletop_population_rollout(self._cfg_ref, self._st_ref, C.byref(policy.struct), C.byref(policy.pop_struct) if population else None,
+    head = policy.head(sample=bool(sample), eps_out=eps) if gaussian else None
+    pop = getattr(policy, 'pop_struct', None)
+    return self._lib.earl_tabletop_population_rollout(self._cfg_ref, self._st_ref, C.byref(policy.struct), None if pop is None else C.byref(pop),
                                                       None if head is None else C.byref(head), E, T, int(bool(reset_first)), C.byref(ostruct), _ptr(actions),
                                                       None if summary is None else C.byref(summary), self._stream())
 
@@ -366,22 +362,19 @@ class TabletopManipulation:
     -> {'ret': [E, N] float64 undiscounted return (the float32 step rewards summed in float64, t ascending), 'success': [E, N] bool success at the last step,
         'first_success': [E, N] int32 first successful step, -1 if none}; each equals its definition applied to what rollout_policy would have returned.
     Philox counter and total_step_count advance as in rollout_policy."""
-    from ..policy import GaussianMLPPolicy, PolicyPopulation, require_tabletop_widths
-    require_tabletop_widths(policy.template if isinstance(policy, PolicyPopulation) else policy, 'evaluate_policy')
-    gaussian = policy.gaussian if isinstance(policy, PolicyPopulation) else isinstance(policy, GaussianMLPPolicy)
+    from ..policy import require_widths
+    gaussian = require_widths(policy, 'evaluate_policy', 12, 3, env=self)
     if sample and not gaussian:
       raise ValueError('evaluate_policy: sample=True needs a Gaussian policy (an MLPPolicy is deterministic)')
     if self.NOBJ != 1:
       raise NotImplementedError('evaluate_policy: single-object env only')
-    if policy.device != self.device:
-      raise ValueError(f'evaluate_policy: the policy is on {policy.device}, the env on {self.device} (policy.to(device))')
     E, T, n = int(episodes), int(T), self.num_envs
     with self._ctx():
       ret = torch.empty(E, n, dtype=torch.float64, device=self.device)
       succ = torch.empty(E, n, dtype=torch.bool, device=self.device)
       first = torch.empty(E, n, dtype=torch.int32, device=self.device)
       summary = _abi.EpisodeSummary(ret=ret.data_ptr(), success_last=succ.data_ptr(), first_success=first.data_ptr())
-      rc = self._population_launch(policy, E, T, True, _abi.TabletopOut(None, None, None, None), None, None, sample, summary)
+      rc = self._population_launch(policy, gaussian, E, T, True, _abi.TabletopOut(None, None, None, None), None, None, sample, summary)
     self._check(rc, 'population_rollout')
     self._cfg.counter += E * (T + 1)
     self.total_step_count += E * T
@@ -396,17 +389,14 @@ class TabletopManipulation:
     -> (obs [T,N,D], reward [T,N], done, success, actions [T,N,3], agent [T,N] int8 = the agent that computed the action) -- with a leading E axis when
     reset_first=True; return_noise=True (Gaussian agents) appends eps.  `env.pair_counts` = (forward phases, reset phases) [E, N] that ended by success in
     this launch.  The reset agent sees pair.backward_goal in its observation's goal slots; `goal_idx` keeps the env's task goal throughout."""
-    from ..policy import AgentPair
-    if not isinstance(pair, AgentPair):
-      raise ValueError('rollout_agents: pair is an AgentPair')
-    if (pair.obs_dim, pair.act_dim) != (12, 3):
-      raise ValueError(f'rollout_agents: an AgentPair of observation width {pair.obs_dim} and action width {pair.act_dim}; the tabletop takes 12 and 3')
+    from ..policy import require_widths
+    gaussian = require_widths(pair, 'rollout_agents', 12, 3, env=self, pair=True)
     if self.NOBJ != 1:
       raise NotImplementedError('rollout_agents: single-object env only')
     if self._cfg.goal_change_frequency > 0:
       raise ValueError('rollout_agents: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
                        'not under a LifelongWrapper, whose clock would fight the pair\'s over the same draw')
-    if not pair.gaussian and (return_noise or not sample):
+    if not gaussian and (return_noise or not sample):
       raise ValueError('rollout_agents: sample=False / return_noise=True need Gaussian agents (MLPPolicy agents are deterministic)')
     if reset_first:
       E = 1 if episodes is None else int(episodes)
@@ -415,8 +405,6 @@ class TabletopManipulation:
       if episodes not in (None, 1):
         raise ValueError('rollout_agents: a continuing rollout (reset_first=False) is one episode')
       E, lead = 1, (int(T), self.num_envs)
-    if pair.device != self.device:
-      raise ValueError(f'rollout_agents: the pair is on {pair.device}, the env on {self.device} (pair.to(device))')
     with self._ctx():
       if self.agent_phase is None:
         self.agent_phase = torch.zeros(self.num_envs, dtype=torch.int8, device=self.device)
@@ -435,7 +423,7 @@ class TabletopManipulation:
       ps = _abi.AgentPair(switch_every=(_abi.C.c_int32 * 2)(*pair.switch_every), switch_on_success=int(pair.switch_on_success), pad_=0, param_stride=pair.stride,
                           backward_goal=_ptr(goal), phase=self.agent_phase.data_ptr(), steps_in_phase=self.steps_in_phase.data_ptr(),
                           agent_out=agent.data_ptr(), forward_success=fwd.data_ptr(), backward_success=bwd.data_ptr())
-      head = pair.head(sample=bool(sample), eps_out=eps) if pair.gaussian else None
+      head = pair.head(sample=bool(sample), eps_out=eps) if gaussian else None
       rc = self._lib.earl_tabletop_pair_rollout(self._cfg_ref, self._st_ref, C.byref(pair.struct), C.byref(ps), None if head is None else C.byref(head), E, int(T),
                                                 int(bool(reset_first)), C.byref(ostruct), actions.data_ptr(), self._stream())
     self._check(rc, 'pair_rollout')

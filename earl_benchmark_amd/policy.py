@@ -184,17 +184,34 @@ class GaussianMLPPolicy(MLPPolicy):
     return torch.tanh(u) if self.squash else u
 
 
-def require_widths(policy, who, obs_dim, act_dim):
-  """a container or a launch of declared widths takes networks of those widths only (the tabletop's 12 -> .. -> 3 unless said otherwise)"""
+def require_widths(policy, who, obs_dim, act_dim, env=None, pair=False, bounded=None):
+  """The one check of a policy against the widths it is to have -> is it Gaussian.  env=None: a container of declared widths (the tabletop's 12 -> .. -> 3 unless
+  said otherwise) takes networks of those widths only.  env given (its `device`, `num_envs`, `_cfg.env_offset`): a launch of `who` on that env -- the type (an
+  MLPPolicy, a GaussianMLPPolicy or a PolicyPopulation of them; pair=True: an AgentPair), the env's widths, the env's device, and a population's members against the
+  env's global ids.  bounded: None, or the bound outside which the env's reference raises on an action (the minitaur): an unbounded output is refused."""
+  if env is not None and not isinstance(policy, AgentPair if pair else (MLPPolicy, PolicyPopulation)):
+    raise ValueError(f'{who}: ' + ('pair is an AgentPair' if pair else 'an MLPPolicy, a GaussianMLPPolicy or a PolicyPopulation of them (an AgentPair goes to rollout_agents)'))
+  what, ctor = ('an AgentPair', 'AgentPair') if pair else ('a policy', 'MLPPolicy')
   od, ad = getattr(policy, 'obs_dim', OBS_DIM), getattr(policy, 'act_dim', ACT_DIM)
   if (od, ad) != (obs_dim, act_dim):
-    takes = f'the tabletop takes {OBS_DIM} and {ACT_DIM}' if (obs_dim, act_dim) == (OBS_DIM, ACT_DIM) else f'{obs_dim} and {act_dim} were declared'
-    raise ValueError(f'{who}: a policy of observation width {od} and action width {ad}; {takes}')
-
-
-def require_tabletop_widths(policy, who):
-  """the tabletop kernels (and the pair container built for them) take 12 -> .. -> 3 networks only"""
-  require_widths(policy, who, OBS_DIM, ACT_DIM)
+    takes = (f'the tabletop takes {OBS_DIM} and {ACT_DIM}' if (obs_dim, act_dim) == (OBS_DIM, ACT_DIM) else
+             f'{obs_dim} and {act_dim} were declared' if env is None else f'this env takes {obs_dim} and {act_dim} ({ctor}(..., obs_dim={obs_dim}, act_dim={act_dim}))')
+    raise ValueError(f'{who}: {what} of observation width {od} and action width {ad}; {takes}')
+  gaussian = policy.gaussian if isinstance(policy, (PolicyPopulation, AgentPair)) else isinstance(policy, GaussianMLPPolicy)
+  if env is None:
+    return gaussian
+  if policy.device != env.device:
+    noun = 'pair' if pair else 'policy'
+    raise ValueError(f'{who}: the {noun} is on {policy.device}, the env on {env.device} ({noun}.to(device))')
+  if isinstance(policy, PolicyPopulation):
+    lo, hi = int(env._cfg.env_offset), int(env._cfg.env_offset) + env.num_envs - 1
+    if lo < 0 or hi // policy.envs_per_policy >= policy.n_policies:
+      raise ValueError(f'{who}: global env ids {lo} .. {hi} need members up to {hi // policy.envs_per_policy} of {policy.n_policies}')
+  if bounded is not None and policy.out_act != 'tanh':
+    given = 'GaussianMLPPolicy(..., squash=False)' if gaussian else f'MLPPolicy(..., out_act={policy.out_act!r})'
+    raise ValueError(f'{who}: {given} is unbounded; the reference env raises on an action outside +-{bounded} and a kernel cannot, so this env takes bounded '
+                     "policies only: MLPPolicy(..., out_act='tanh') or GaussianMLPPolicy(..., squash=True)")
+  return gaussian
 
 
 class PolicyPopulation:

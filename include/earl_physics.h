@@ -298,9 +298,9 @@ int earl_sawyer_rollout_clocked(const earl_link_model* model, const earl_collisi
  * 0xFFFF: the streams are disjoint); words x, y, z, w -> action dimensions 0 .. 3.  head->eps_out (may be NULL) is [T, n, 4] here, written in both modes.
  * actions [T, n, 4] (device, required) receives the actions as the policy produced them; the launch is bit-identical to earl_sawyer_rollout_clocked fed with it:
  * outputs, state left behind, counters.  clock as for earl_sawyer_rollout_clocked (may be NULL).
- * EARL_ERR_ARG before any HIP call: NULL policy / obs0 / actions / out->obs, dims[0] != 14, a last layer that is not 4 (8 with a head) wide, hidden widths outside the
- * rule, n_layers not 2 or 3, activations or head fields out of range (as earl_tabletop_policy_rollout_gaussian), precision != 0, misaligned params, T < 1, nv not 10 or
- * 15, and everything earl_sawyer_rollout refuses.  The 64-lanes-per-env measurement builds (earl_debug_set_physics_lanes(64)) have no policy form: EARL_ERR_ARG. */
+ * EARL_ERR_ARG before any HIP call: the policy and head rules of earl_tabletop.h's argument contract with the widths 14 / 4, and this entry point's own: NULL policy /
+ * obs0 / actions / out->obs, policy->params not 16-byte aligned, T < 1, nv not 10 or 15, and everything earl_sawyer_rollout refuses.  The 64-lanes-per-env measurement
+ * builds (earl_debug_set_physics_lanes(64)) have no policy form: EARL_ERR_ARG. */
 int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
                                const earl_sawyer_out* out, earl_stream_t stream);
@@ -319,9 +319,8 @@ int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collisio
  *            required) is the one observation row the launch keeps: every emitted row, the rollback's re-emission and the goal switch's patch are written to it, and
  *            the policy of step t + 1 reads it (lane by lane what that lane wrote; across a time slice under the release / acquire that carries qpos).  The state
  *            left behind, last_obs included, equals the full launch's.
- * EARL_ERR_ARG before any HIP call: everything earl_sawyer_policy_rollout refuses (but NULL actions / out->obs), and G % 16 != 0, G < 16, P < 1, param_stride below
- * the parameter count, param_stride % 4 != 0 (every member's rows are read in 16-byte pieces), env_offset < 0 with pop, (env_offset + n - 1) / G >= P,
- * out->obs == NULL with st->last_obs == NULL. */
+ * EARL_ERR_ARG before any HIP call: everything earl_sawyer_policy_rollout refuses (but NULL actions / out->obs), the contract's population rules, and this entry
+ * point's own: param_stride % 4 != 0 (every member's rows are read in 16-byte pieces), out->obs == NULL with st->last_obs == NULL. */
 int earl_sawyer_population_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                    const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
                                    const uint64_t* clock, float* actions, const earl_sawyer_out* out, const earl_episode_summary* summary, earl_stream_t stream);
@@ -351,9 +350,8 @@ int earl_sawyer_population_rollout(const earl_link_model* model, const earl_coll
  * actions, eps, state, fail_count; all envs in phase 1 with backward_goal = NULL, to the same with row 1.  actions, every pointer of `out` and the pair's three output
  * pointers may be NULL, as in earl_sawyer_population_rollout; without out->obs the env's row of st->last_obs is carried.  On the door, out->info receives only what the
  * lifelong switch leaves on a goal-switch row (the door's info dict of a pair launch is not offered); the peg's is written in the kernel as ever.
- * EARL_ERR_ARG before any HIP call: everything earl_sawyer_population_rollout refuses with pop = NULL, and NULL pair / phase / steps_in_phase, switch_every[k] < 1,
- * switch_on_success not 0 or 1, param_stride below the parameter count or not a multiple of 4, cfg->goal_change_frequency > 0 (the pair IS the lifelong mechanism),
- * backward_goal != NULL with cfg->n_goal_rows == 0 (the forward goal could not be restored). */
+ * EARL_ERR_ARG before any HIP call: everything earl_sawyer_population_rollout refuses with pop = NULL, the contract's pair rules, and this entry point's own:
+ * param_stride not a multiple of 4, backward_goal != NULL with cfg->n_goal_rows == 0 (the forward goal could not be restored). */
 int earl_sawyer_pair_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                              const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_gaussian_head* head, const double* obs0, int32_t T,
                              const uint64_t* clock, float* actions, const earl_sawyer_out* out, earl_stream_t stream);
@@ -552,10 +550,10 @@ int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_mode
  * The launch is therefore bit-identical to earl_minitaur_rollout_clocked fed with the actions it returns: outputs, state rows, fail_count, last_obs, counters.
  * clock as for earl_minitaur_rollout_clocked (may be NULL).  The kernel is picked by the plain entry point's rule (one-wave kernel in its three launch shapes, two-wave
  * kernel; earl_debug_set_solo_mt, earl_debug_set_minitaur_duo); both forms return the same bits.
- * EARL_ERR_ARG before any HIP call: everything earl_minitaur_rollout_clocked refuses, NULL policy / obs0 / actions, dims[0] != 32, a last layer that is not 8 (16 with a
- * head) wide, hidden widths outside the rule, n_layers not 2 or 3, precision != 0, misaligned or NULL params, unknown activations, head fields out of range (as
- * earl_tabletop_policy_rollout_gaussian), and out_act != EARL_ACT_TANH: the reference env raises on an action outside +-(1 + 0.01), a kernel cannot, and the open-loop
- * replay of the returned actions must not raise either, so the minitaur takes bounded policies only.  The generic-stepper comparison build
+ * EARL_ERR_ARG before any HIP call: everything earl_minitaur_rollout_clocked refuses, the policy and head rules of earl_tabletop.h's argument contract with the widths
+ * 32 / 8, and this entry point's own: NULL policy / obs0 / actions, policy->params not 16-byte aligned, and out_act != EARL_ACT_TANH: the reference env raises on an
+ * action outside +-(1 + 0.01), a kernel cannot, and the open-loop replay of the returned actions must not raise either, so the minitaur takes bounded policies only.
+ * The generic-stepper comparison build
  * (earl_debug_set_minitaur_stepper(0)) has no policy form: EARL_ERR_ARG.  n = 0 or T = 0: EARL_OK, nothing launched. */
 int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                                  const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,

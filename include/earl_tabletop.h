@@ -118,7 +118,22 @@ int earl_tabletop_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tableto
 /* ---- closed loop: an MLP policy evaluated INSIDE the rollout kernel ----
  * The reference's evaluation / training loop is closed (`obs = env.reset(); while not done: obs, ... = env.step(policy(obs))`); the entry points above
  * need every action up front.  This one takes the policy instead: a float32 MLP 12 -> hidden (-> hidden) -> 3, evaluated on gfx950 with
- * v_mfma_f32_16x16x4_f32 next to the fp64 recurrence, weights resident in registers for the whole launch. */
+ * v_mfma_f32_16x16x4_f32 next to the fp64 recurrence, weights resident in registers for the whole launch.
+ *
+ * THE ARGUMENT CONTRACT of every closed-loop entry point -- the four of this header, and earl_physics.h's earl_sawyer_policy_rollout, earl_sawyer_population_rollout,
+ * earl_sawyer_pair_rollout and earl_minitaur_policy_rollout -- is one set of rules (csrc/policy_check.h states them once; tests/test_policy_contract.py holds every
+ * entry point to them).  Each returns EARL_ERR_ARG before any HIP call for
+ *   policy      NULL params; precision != 0; n_layers not 2 or 3; dims[0] != the env's observation width; dims[n_layers] != the env's action width (head == NULL) or
+ *               twice it (head given); a hidden width that is not a multiple of 16 in 16..256; dims[3] != 0 with two layers; hidden_act not EARL_ACT_RELU / _TANH;
+ *               out_act not EARL_ACT_NONE / _TANH
+ *   head        mode not EARL_HEAD_MEAN / _SAMPLE; log_std_map not EARL_LOGSTD_CLAMP / _TANH; bounds that are not finite, min <= max and inside [-20, 4]
+ *   population  P < 1; G < 16 or G % 16 != 0; param_stride below the parameter count of one policy (the sum of dims[l+1] (dims[l] + 1)); cfg->env_offset < 0;
+ *               (env_offset + n - 1) / G >= P
+ *   pair        NULL pair / phase / steps_in_phase; switch_every[k] < 1; switch_on_success not 0 or 1; param_stride below the parameter count;
+ *               cfg->goal_change_frequency > 0 (the pair IS the lifelong mechanism: the two clocks would fight over the same draw)
+ * with the widths 12 / 3 here, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur.  The differences are three, each listed with its entry point: the stepper
+ * units read the weight rows in 16-byte pieces (params 16-byte aligned, param_stride % 4 == 0), the minitaur takes bounded policies only (out_act == EARL_ACT_TANH),
+ * and this header's pair holds two weight sets in registers (EARL_PAIR_MAX_H2). */
 enum { EARL_ACT_NONE = 0, EARL_ACT_RELU = 1, EARL_ACT_TANH = 2 };
 typedef struct earl_mlp_policy {
   int32_t n_layers;     /* linear layers: 2 (one hidden) or 3 (two hidden) */
@@ -197,8 +212,8 @@ typedef struct earl_episode_summary {   /* every pointer may be NULL; rows [epis
  *            this launch's own out->reward / out->success, exactly, whether or not out's pointers / act_out are given (evaluation without any [T] array).
  * Everything else as the two single-policy entry points: reset_first / episodes rules, every `out` pointer / act_out / eps_out may be NULL (`out` itself
  * may not), Philox counter use episodes * (T + 1) resp. T, the Gaussian draw contract (seed, global env id, counter), lifelong switching and auto-reset,
- * argument errors before any HIP call -- to which it adds: G % 16 != 0, G < 16, P < 1, param_stride below the parameter count, env_offset < 0 with pop,
- * (env_offset + n - 1) / G >= P, head and dims[n_layers] disagreeing.  Single-object env only (the 3-object variant has no policy entry point). */
+ * argument errors before any HIP call: the contract's policy, head and (with pop) population rules.  Single-object env only (the 3-object variant has no policy
+ * entry point). */
 int earl_tabletop_population_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
                                      const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
                                      const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary, earl_stream_t stream);
@@ -240,10 +255,8 @@ typedef struct earl_agent_pair {
  * steps_in_phase = 0 at each episode's reset.  Launch exit: phase, steps_in_phase and goal_idx are stored.
  * Never switching (switch_every > T, switch_on_success = 0, all envs in phase 0) the launch is bit-identical to the single-policy entry point of the same
  * head on row 0.  Everything else as those entry points: reset_first / episodes rules, NULL-able outputs / act_out / eps_out, Philox counter use
- * episodes * (T + 1) resp. T, argument errors before any HIP call -- to which it adds: NULL pair / phase / steps_in_phase, switch_every[k] < 1,
- * switch_on_success not 0 or 1, param_stride below the parameter count, cfg->goal_change_frequency > 0 (the pair IS the lifelong mechanism: the two clocks
- * would fight over the same draw), and a second hidden layer wider than EARL_PAIR_MAX_H2 (two weight sets share the registers of one wave per SIMD; one
- * hidden layer may have every legal width).  Single-object env only. */
+ * episodes * (T + 1) resp. T, argument errors before any HIP call: the contract's policy, head and pair rules, and this entry point's own: a second hidden layer
+ * wider than EARL_PAIR_MAX_H2 (two weight sets share the registers of one wave per SIMD; one hidden layer may have every legal width).  Single-object env only. */
 #define EARL_PAIR_MAX_H2 128
 int earl_tabletop_pair_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair,
                                const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out,

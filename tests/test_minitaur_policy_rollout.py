@@ -19,6 +19,7 @@ import torch
 
 from conftest import REPO
 from earl_benchmark_amd import _abi
+from policy_struct_helpers import aligned_params, head, variant as variant_of
 from test_sawyer_policy_rollout import forward_cpu, pack, random_layers
 
 CSRC = os.path.join(REPO, 'earl_benchmark_amd', 'csrc')
@@ -40,10 +41,7 @@ def test_argument_errors_from_the_hip_library_need_no_gpu():
   lib = _abi.load()
   layers = random_layers([32, 16, 8], seed=0)
   pol, keep = pack(layers, 'relu', 'tanh')
-  aligned = np.zeros(keep.size + 8, np.float32)                          # a 16-byte aligned home for the parameters
-  off = (-aligned.ctypes.data % 16) // 4
-  aligned[off:off + keep.size] = keep
-  pol.params = aligned.ctypes.data + 4 * off
+  aligned = aligned_params(pol, keep)
   buf = np.zeros(4096, np.float64)                                       # never read: every call below returns before any HIP call
   p = buf.ctypes.data
 
@@ -63,13 +61,7 @@ def test_argument_errors_from_the_hip_library_need_no_gpu():
     return _abi.MinitaurOut(**d)
 
   def variant(base=pol, **kw):
-    d = dict(n_layers=base.n_layers, dims=tuple(base.dims), hidden_act=base.hidden_act, out_act=base.out_act, precision=base.precision, params=base.params)
-    d.update(kw)
-    d['dims'] = (C.c_int32 * 4)(*d['dims'])
-    return _abi.MlpPolicy(**d)
-
-  def head(mode=_abi.HEAD_SAMPLE, m=_abi.LOGSTD_TANH, lo=-5.0, hi=2.0):
-    return _abi.GaussianHead(mode=mode, log_std_map=m, log_std_min=lo, log_std_max=hi, eps_out=None)
+    return variant_of(base, **kw)
 
   cfg, st, out = cfg_of(), st_of(), out_of()
 

@@ -18,6 +18,7 @@ import torch
 
 from conftest import REPO
 from earl_benchmark_amd import _abi
+from policy_struct_helpers import aligned_params, head as head_of, variant as variant_of
 from test_sawyer_policy_rollout import forward_cpu, pack, random_layers
 
 CSRC = os.path.join(REPO, 'earl_benchmark_amd', 'csrc')
@@ -153,9 +154,7 @@ def test_new_argument_errors_need_no_gpu():
   pol, keep = pack(layers, 'relu', 'tanh')
   count = keep.size                                                       # 308
   assert count == 308 and count % 4 == 0
-  aligned = np.zeros(2 * (count + 8) + 8, np.float32)                     # a 16-byte aligned home for two agents
-  off = (-aligned.ctypes.data % 16) // 4
-  pol.params = aligned.ctypes.data + 4 * off
+  aligned = aligned_params(pol, keep, rows=2)                               # a 16-byte aligned home for two agents
   buf = np.zeros(4096, np.float64)
   p = buf.ctypes.data
   st = _abi.SawyerState(qpos=p, qvel=p, mocap_pos=p, goal=p, last_obs=p, steps_since_goal_change=p)
@@ -170,16 +169,13 @@ def test_new_argument_errors_need_no_gpu():
                           agent_out=agent, forward_success=fs, backward_success=bs)
 
   def variant(**kw):
-    d = dict(n_layers=pol.n_layers, dims=tuple(pol.dims), hidden_act=pol.hidden_act, out_act=pol.out_act, precision=pol.precision, params=pol.params)
-    d.update(kw)
-    d['dims'] = (C.c_int32 * 4)(*d['dims'])
-    return _abi.MlpPolicy(**d)
+    return variant_of(pol, **kw)
 
   def call(model=p, nv=10, cfg=cfg(), st=st, pol=pol, pair=pair(), head=None, obs0=p, T=4, actions=p, out=out):
     ref = lambda s: None if s is None else C.byref(s)
     return lib.earl_sawyer_pair_rollout(model, None, nv, ref(cfg), ref(st), ref(pol), ref(pair), ref(head), obs0, T, None, actions, ref(out), None)
 
-  head = _abi.GaussianHead(mode=_abi.HEAD_SAMPLE, log_std_map=_abi.LOGSTD_TANH, log_std_min=-5.0, log_std_max=2.0, eps_out=None)
+  head = head_of()
   for kw in (dict(), dict(nv=15), dict(actions=None), dict(out=out_no_obs), dict(out=out_no_obs, actions=None, pair=pair(agent=None, fs=None, bs=None)),
              dict(pair=pair(stride=count + 4)), dict(pair=pair(se=(1, 1), sos=0)), dict(pair=pair(goal=p)), dict(cfg=cfg(rows=0)), dict(cfg=cfg(rows=15), pair=pair(goal=p)),
              dict(pol=variant(dims=(14, 16, 8, 0)), head=head, pair=pair(stride=376)), dict(pol=variant(dims=(14, 16, 256, 4), n_layers=3), pair=pair(stride=8192))):

@@ -21,6 +21,7 @@ import torch
 
 from conftest import REPO
 from earl_benchmark_amd import _abi
+from policy_struct_helpers import aligned_params, head, variant as variant_of
 
 CSRC = os.path.join(REPO, 'earl_benchmark_amd', 'csrc')
 
@@ -177,10 +178,7 @@ def test_argument_errors_from_the_hip_library_need_no_gpu():
   lib = _abi.load()
   layers = random_layers([14, 16, 4], seed=0)
   pol, keep = pack(layers, 'relu', 'tanh')
-  aligned = np.zeros(keep.size + 8, np.float32)                          # a 16-byte aligned home for the parameters
-  off = (-aligned.ctypes.data % 16) // 4
-  aligned[off:off + keep.size] = keep
-  pol.params = aligned.ctypes.data + 4 * off
+  aligned = aligned_params(pol, keep)
   cfg = _abi.SawyerCfg(n=8, frame_skip=5)
   buf = np.zeros(4096, np.float64)                                       # never read: every call below returns before any HIP call
   p = buf.ctypes.data
@@ -188,13 +186,7 @@ def test_argument_errors_from_the_hip_library_need_no_gpu():
   out = _abi.SawyerOut(obs=p)
 
   def variant(base=pol, **kw):
-    d = dict(n_layers=base.n_layers, dims=tuple(base.dims), hidden_act=base.hidden_act, out_act=base.out_act, precision=base.precision, params=base.params)
-    d.update(kw)
-    d['dims'] = (C.c_int32 * 4)(*d['dims'])
-    return _abi.MlpPolicy(**d)
-
-  def head(mode=_abi.HEAD_SAMPLE, m=_abi.LOGSTD_TANH, lo=-5.0, hi=2.0):
-    return _abi.GaussianHead(mode=mode, log_std_map=m, log_std_min=lo, log_std_max=hi, eps_out=None)
+    return variant_of(base, **kw)
 
   def call(model=p, nv=10, cfg=cfg, st=st, pol=pol, head=None, obs0=p, T=4, actions=p, out=out):
     ref = lambda s: None if s is None else C.byref(s)

@@ -19,6 +19,7 @@ import torch
 
 from conftest import REPO
 from earl_benchmark_amd import _abi
+from policy_struct_helpers import aligned_params, head as head_of, variant as variant_of
 from test_sawyer_policy_rollout import forward_cpu, pack, random_layers
 
 CSRC = os.path.join(REPO, 'earl_benchmark_amd', 'csrc')
@@ -125,9 +126,7 @@ def test_new_argument_errors_need_no_gpu():
   pol, keep = pack(layers, 'relu', 'tanh')
   count = keep.size                                                       # 14 * 16 + 16 + 16 * 4 + 4 = 308
   assert count == 308 and count % 4 == 0
-  aligned = np.zeros(4 * (count + 8), np.float32)                         # a 16-byte aligned home for four members
-  off = (-aligned.ctypes.data % 16) // 4
-  pol.params = aligned.ctypes.data + 4 * off
+  aligned = aligned_params(pol, keep, rows=4)                               # a 16-byte aligned home for four members
   buf = np.zeros(4096, np.float64)
   p = buf.ctypes.data
   st = _abi.SawyerState(qpos=p, qvel=p, mocap_pos=p, goal=p, last_obs=p)
@@ -142,10 +141,7 @@ def test_new_argument_errors_need_no_gpu():
     return _abi.PolicyPopulation(n_policies=P, envs_per_policy=G, param_stride=stride)
 
   def variant(**kw):
-    d = dict(n_layers=pol.n_layers, dims=tuple(pol.dims), hidden_act=pol.hidden_act, out_act=pol.out_act, precision=pol.precision, params=pol.params)
-    d.update(kw)
-    d['dims'] = (C.c_int32 * 4)(*d['dims'])
-    return _abi.MlpPolicy(**d)
+    return variant_of(pol, **kw)
 
   def call(model=p, nv=10, cfg=cfg(0), st=st, pol=pol, pop=pop(), head=None, obs0=p, T=4, actions=p, out=out, summary=summ):
     ref = lambda s: None if s is None else C.byref(s)
@@ -155,7 +151,7 @@ def test_new_argument_errors_need_no_gpu():
   for kw in (dict(), dict(pop=None), dict(summary=None), dict(actions=None), dict(out=out_no_obs), dict(out=out_no_obs, actions=None, pop=None, summary=None),
              dict(pop=pop(stride=count + 4)), dict(pop=pop(G=1040)), dict(cfg=cfg(0, env_offset=7)), dict(summary=_abi.EpisodeSummary()), dict(nv=15)):
     assert call(**kw) == _abi.EARL_OK, kw
-  head = _abi.GaussianHead(mode=_abi.HEAD_SAMPLE, log_std_map=_abi.LOGSTD_TANH, log_std_min=-5.0, log_std_max=2.0, eps_out=None)
+  head = head_of()
   assert call(pol=variant(dims=(14, 16, 8, 0)), head=head, pop=pop(stride=376)) == _abi.EARL_OK
   bad = [dict(pop=pop(G=24)), dict(pop=pop(G=8)), dict(pop=pop(G=0)), dict(pop=pop(G=-16)),                              # G % 16, G < 16
          dict(pop=pop(P=0)), dict(pop=pop(P=-1)),                                                                        # P < 1

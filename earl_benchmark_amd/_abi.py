@@ -206,6 +206,9 @@ SIGNATURES = {
     # the closed loop inside the minitaur rollout kernels: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
     'earl_minitaur_policy_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, _P(MinitaurOut), C.c_void_p],
+    # the closed loop inside the kitchen rollout kernel: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
+    'earl_kitchen_policy_rollout': [C.c_void_p, C.c_void_p, _P(KitchenParams), _P(KitchenCfg), _P(KitchenState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.c_void_p, _P(KitchenOut), C.c_void_p],
     'earl_minitaur_reset': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_minitaur_cfg_size': [],
     'earl_debug_set_minitaur_stepper': [C.c_int],

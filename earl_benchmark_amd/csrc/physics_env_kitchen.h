@@ -83,6 +83,90 @@ __device__ __forceinline__ double kit_norm_diff(const double* a, const double* b
   }
   return sqrt(d);
 }
+
+// ------------------------------------------------------------------------------------------------ the policy phase of the policy kernels (earl_kitchen_policy_rollout)
+// The rollout's arguments (action unused) plus the policy.  A struct of its own so that the plain kernels' argument stays what it was
+struct KitchenPolicyArgs : KitchenRolloutArgs {
+  earl_mlp_policy pol;           // dims[0] = 46, dims[n_layers] = 9 (18 with the head)
+  earl_gaussian_head head;       // read when gauss != 0
+  int gauss;
+  const double* obs0;            // [n, 46]: what the policy sees at step 0
+  float* act_out;                // [T, n, 9]: the actions as the policy produced them (earl_kitchen_rollout_clocked fed with it walks through the same bits)
+};
+static_assert(std::is_standard_layout<KitchenRolloutArgs>::value && std::is_trivially_copyable<KitchenPolicyArgs>::value, "the policy phase reads KitchenPolicyArgs as laid out in the kernel-argument segment");
+#include "policy_lane_group.h"
+// A float32 MLP 46 -> H1 (-> H2) -> 9 | 18 evaluated by the 32 lanes of an env between two env steps: element k of a layer on lane k & 31 in register k >> 5.  The input
+// layer is pol_layer<32, false> (rows of 46 floats = 184 bytes are no whole 16-byte pieces; its second k-tile holds 14 elements), every later one pol_layer<32, true>
+// (hidden widths are multiples of 16 and params is 16-byte aligned, so every later row starts on a 16-byte boundary).
+// -> the action's element `sub` on lanes 0 .. 8 of the group, as stored in act_out.
+// `seen`: the env's row of 46 doubles the policy sees (NULL at step 0: the env's row of obs0); `row` = t n + env.  A group that is not live (an idle group of the last
+// wave / workgroup, a solo launch's shadow) computes on zeros and stores nothing: the row of the env an idle group shadows is written by another wave, and a read of it
+// would race with that wave; the shadow of a solo launch takes the live group's action from its own wave afterwards (kit_step_action).
+// The policy's kernel arguments are read HERE, through the kernel-argument pointer the caller passed through an empty asm: read as `a.pol...` they would be loaded once at
+// kernel entry and held in scalar registers across every timestep (see sawyer_policy_action).  Nothing of the policy lives across a timestep.
+__device__ __noinline__ float kitchen_policy_action(const uint64_t ka_bits, const uint64_t ev, const uint32_t gid, const uint64_t seed, const double* __restrict__ seen, const int env,
+                                                    const size_t row, const int sub, const bool live) {
+#pragma clang fp contract(off)
+  const EARL_KARG KitchenPolicyArgs* ka = (const EARL_KARG KitchenPolicyArgs*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ka_bits >> 32)) << 32) |
+                                                                              (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ka_bits));
+  const int n_layers = ka->pol.n_layers, d1 = ka->pol.dims[1], d2 = ka->pol.dims[2], d3 = ka->pol.dims[3];
+  const int hidden_act = ka->pol.hidden_act, out_act = ka->pol.out_act;
+  if (!seen) seen = ka->obs0 + (size_t)env * 46;       // step 0
+  float h[8];
+  // each double rounded once to float32; lane `sub` reads the elements lane `sub` stored (sub and sub + 32)
+  h[0] = live ? (float)seen[sub] : 0.f;
+  h[1] = (live && sub + 32 < 46) ? (float)seen[sub + 32] : 0.f;
+#pragma unroll
+  for (int i = 2; i < 8; ++i) h[i] = 0.f;
+  const float* w = ka->pol.params;
+  pol_layer<32, false>(w, w + (size_t)d1 * 46, 46, d1, hidden_act, sub, h);
+  w += (size_t)d1 * (46 + 1);
+  if (n_layers == 3) {
+    pol_layer<32, true>(w, w + (size_t)d2 * d1, d1, d2, hidden_act, sub, h);
+    w += (size_t)d2 * (d1 + 1);
+  }
+  const int KL = n_layers == 3 ? d2 : d1, NL = n_layers == 3 ? d3 : d2;
+  pol_layer<32, true>(w, w + (size_t)NL * KL, KL, NL, EARL_ACT_NONE, sub, h);       // lane j < NL holds output j
+  const int d = sub < 9 ? sub : 8;                     // this lane's action dimension (lanes 9 .. 31 repeat dimension 8 and store nothing)
+  float u;
+  if (ka->gauss) {
+    // lanes 0 .. 8 are the head's nine dimensions: mean on the lane itself, raw log_std nine lanes up
+    const float mean = __shfl(h[0], d, 32), raw = __shfl(h[0], d + 9, 32);
+    // THREE Philox blocks per (env, env step), counter words {kGaussDraw + b, global id, ev}: ev = the step's sensor-noise counter (cfg.counter plus the clock word of a
+    // graph-captured launch, plus t), whose draw indices are 0x4B00 + j: the streams are disjoint.  Words x, y, z, w of block b serve action dimensions 4 b .. 4 b + 3;
+    // block 2 uses x only.
+    const int c = d & 3;
+    const earl::U4 b = earl::philox4x32_10(earl::U4{earl::kGaussDraw + (uint32_t)(d >> 2), gid, (uint32_t)ev, (uint32_t)(ev >> 32)}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float eps = earl::normal_quantile_f32((c == 0 ? b.x : (c == 1 ? b.y : (c == 2 ? b.z : b.w))) >> 8);
+    u = earl::gaussian_head_action(earl_gaussian_head{ka->head.mode, ka->head.log_std_map, ka->head.log_std_min, ka->head.log_std_max, nullptr}, out_act, mean, raw, eps);
+    float* eps_out = ka->head.eps_out;
+    if (sub < 9 && live && eps_out) eps_out[row * 9 + sub] = eps;
+  } else {
+    u = earl::policy_act(h[0], out_act);
+  }
+  float* act_out = ka->act_out;
+  if (sub < 9 && live) act_out[row * 9 + sub] = u;
+  return u;
+}
+// the action component `kk` of env step t as this lane's double, before the env step's own [-1, 1] clip, computed by the policy.  `A` is the policy kernel's argument
+// struct (a template so that the plain kernels, which name this call in a discarded statement, never instantiate it)
+template <class A>
+__device__ __forceinline__ double kit_policy_step(const A& a, const int t, const int n, const int env, const int sub, const int grp, const int kk, const bool live) {
+#pragma clang fp contract(off)
+  const size_t row = (size_t)t * n + env;
+  // what the policy sees: the row this env emitted last, exactly as it stands in out.obs (sensor noise included, a rolled-back step's repeated row), each double
+  // rounded to float32; at step 0 the caller's obs0.  Lane `sub` reads the elements lane `sub` wrote (the observation loop and the rollback both store elements
+  // sub and sub + 32 from lane `sub`), after the agent-scope fence that ends every env step.
+  const double* seen = t > 0 ? a.out.obs + (row - n) * 46 : nullptr;
+  const uint64_t ev = a.cfg.counter + (a.clock ? a.clock[0] : 0) + (uint64_t)t;      // the step's sensor-noise counter (read per step, like the noise's)
+  // (offset 0 of the kernel-argument segment is the kernel's one argument, the KitchenPolicyArgs)
+  const EARL_KARG void* ka = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ka));
+  const float u = kitchen_policy_action((uint64_t)ka, ev, (uint32_t)(a.cfg.env_offset + env), a.cfg.seed, seen, env, row, sub, live);
+  // the env step consumes the float32 values stored in act_out: lanes 0 .. 8 of the live group hold them.  The second group of a one-env-per-wave launch (solo >= 1)
+  // is the first one's shadow and steps with the bits of the live group's action (wave-wide shuffle; the choice is wave-uniform)
+  return (double)__shfl(u, a.solo >= 1 ? kk : grp * 32 + kk, 64);
+}
 // DUO (solo == 3, round 5): the FOUR waves of the workgroup, one per SIMD, work on its one env (substep's ROLE 1 - 4).  Per timestep all run the kinematics; then, side by
 // side: wave 0 (B, owns the env) the constraint rows, wave 1 (A) the mass matrix into wave 0's LDS block, wave 2 the bias forces, wave 3 the bounding tests and the collision
 // phases (contact records into wave 0's block); barrier X; wave 1 builds the equality Hessian in wave 0's block while wave 0 does the contact rows and its right-hand side;
@@ -93,168 +177,12 @@ __device__ __forceinline__ double kit_norm_diff(const double* a, const double* b
 // 1 / 3 do its mass matrix, bias forces, equality Hessian and K10's factor (ROLE 5); the same barriers, shared by the workgroup's two envs.
 template <int DUO>
 __global__ __launch_bounds__(64 * Lim<23>::WPB) void kitchen_rollout_kernel(const KitchenRolloutArgs a) {
-#pragma clang fp contract(off)
-  constexpr int NV = 23, LPE = 32, EPW = 64 / LPE, WPB = Lim<NV>::WPB;
-  __shared__ alignas(16) typename ModelOf<NV>::T m;
-  __shared__ alignas(16) BlkTable<Lim<NV>::MB, Lim<NV>::KBT> bt;
-  __shared__ alignas(16) Shared<NV> sh[EPW * WPB];
-  __shared__ earl_kitchen_params kp;
-  stage_blocks(bt, a.col);
-  stage_kb<NV>(bt, a.m, a.col);
-  if (threadIdx.x == 0) kp = a.p;
-  stage_model(m, a.m);                                  // (ends with the workgroup barrier)
-  const earl_kitchen_cfg& cfg = a.cfg;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), sub = lane % LPE, grp = lane / LPE, n = cfg.n;
-  if (a.solo >= 2 && DUO == 0 && wave > 0) return;          // (after stage_model's barrier; the DUO form keeps all four waves: its later barriers count them)
-  const bool role_a = DUO == 1 ? wave >= 1 : (DUO == 2 && (wave & 1));      // the helper waves: compute, store nothing outside LDS
-  const int env_raw = a.solo >= 2 ? (DUO == 2 ? (int)(blockIdx.x * 2 + (wave >> 1)) : (int)blockIdx.x) : (a.solo == 1 ? (int)(blockIdx.x * WPB + wave) : (int)((blockIdx.x * WPB + wave) * EPW + grp));
-  const bool live = env_raw < n && (a.solo == 0 || grp == 0) && !role_a;
-  const int env = env_raw < n ? env_raw : n - 1;
-  Shared<NV>& s = sh[wave * EPW + grp];
-  Shared<NV>* const peer = DUO == 1 ? &sh[grp] : (DUO == 2 ? &sh[(wave ^ 1) * EPW + grp] : nullptr);      // helpers: the owner's block of the same 32-lane group; owners: their helper's (wave 1 of the four-wave form)
-  load_state<NV>(s, m, a.st.qpos + (size_t)env * NV, a.st.qvel + (size_t)env * NV, sub);
-  for (int k = sub; k < (int)(sizeof(s.M.v) / sizeof(double)); k += LPE) s.M.v[k] = 0.0;      // (entries between different trees are never written, K5)
-  for (int k = sub; k < (int)(sizeof(s.hwst.Hw.v) / sizeof(double)); k += LPE) s.hwst.Hw.v[k] = 0.0;   // (nor the structural zeros of the equality Hessian, K9)
-  if (sub < 3) s.mocap[sub] = a.st.mocap_pos[(size_t)env * 3 + sub];
-  fence();
-  const Q4 mq = ldq(cfg.mocap_quat_dev);
-  if constexpr (DUO != 0) {
-    __syncthreads();                                    // wave 0's mass matrix is zeroed before wave 1 writes into it
-    if (role_a) {
-      for (int t = 0; t < a.T; ++t) {
-        __syncthreads();                                // barrier 0: wave 0 is through the env step's bookkeeping (a diverged env went back to its stored state); the step's targets are published
-        const double ctrl_a[EARL_MAXACT] = {peer->duo_ctrl[0], peer->duo_ctrl[1], 0, 0};
-        for (int ts = 0; ts < cfg.frame_skip; ++ts) {
-          if (sub < NV) { s.qp[sub] = peer->qp[sub]; s.qv[sub] = peer->qv[sub]; }
-          fence();
-          if constexpr (DUO == 2) substep<NV, LPE, true, 5>(s, m, bt, a.col, sub, grp, mq, ctrl_a, false, nullptr, nullptr, peer);      // (barriers X, Y, Z inside)
-          else if (wave == 1) substep<NV, LPE, true, 1>(s, m, bt, a.col, sub, grp, mq, ctrl_a, false, nullptr, nullptr, peer);
-          else if (wave == 2) substep<NV, LPE, true, 3>(s, m, bt, a.col, sub, grp, mq, ctrl_a, false, nullptr, nullptr, peer);
-          else substep<NV, LPE, true, 4>(s, m, bt, a.col, sub, grp, mq, ctrl_a, false, nullptr, nullptr, peer);
-          __syncthreads();                              // barrier 2: wave 0 has integrated
-        }
-      }
-      return;
-    }
-  }
-  int steps = a.st.steps_since_reset[env];
-  const int kk = sub < 9 ? sub : 8;                     // this lane's action component
-#ifdef EARL_PHYS_PROF
-  const unsigned long long wave_t0 = __builtin_readcyclecounter();
-#endif
-  for (int t = 0; t < a.T; ++t) {
-    const size_t row = (size_t)t * n + env;
-    // ---- KitchenV0.step up to do_simulation (kitchen_action_kernel): mocap target, the nine position targets
-    const double mocap_prev = s.mocap[sub < 3 ? sub : 0];      // the target before this step's action: a diverged step goes back to it
-    {
-      const double x = (double)a.action[row * 9 + kk];
-      const double c = x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x);
-      const double ak = kp.act_mid[kk] + c * kp.act_amp[kk];
-      if (sub < 3) {
-        const double y = s.mocap[sub] + ak * kp.mocap_range[sub];
-        s.mocap[sub] = y < kp.mocap_clip_lower[sub] ? kp.mocap_clip_lower[sub] : (y > kp.mocap_clip_upper[sub] ? kp.mocap_clip_upper[sub] : y);
-      }
-      if (sub < 9) {
-        const double v = ak < kp.vel_bound[sub][0] ? kp.vel_bound[sub][0] : (ak > kp.vel_bound[sub][1] ? kp.vel_bound[sub][1] : ak);
-        const double y = a.st.last_qp_robot[(size_t)env * 9 + sub] + v * kp.step_duration;
-        s.kit.targets[sub] = y < kp.pos_bound[sub][0] ? kp.pos_bound[sub][0] : (y > kp.pos_bound[sub][1] ? kp.pos_bound[sub][1] : y);
-      }
-    }
-    fence();
-    const double ctrl[EARL_MAXACT] = {s.kit.targets[0], s.kit.targets[1], 0, 0};      // do_simulation: ctrl[i] = targets[i] for i < nu = 2
-    if (sub < 3 && live) a.st.mocap_pos[(size_t)env * 3 + sub] = s.mocap[sub];
-    fence();
-    if constexpr (DUO != 0) {
-      if (sub < 2) s.duo_ctrl[sub] = ctrl[sub];
-      __syncthreads();                                  // barrier 0
-      for (int ts = 0; ts < cfg.frame_skip; ++ts) {
-        if constexpr (DUO == 2) substep<NV, LPE, true, 6>(s, m, bt, a.col, sub, grp, mq, ctrl, ts > 0, nullptr, nullptr, peer);     // (barriers X, Y, Z inside; `peer`: its helper's block, where that leaves K10's factor)
-        else substep<NV, LPE, true, 2>(s, m, bt, a.col, sub, grp, mq, ctrl, ts > 0, nullptr, nullptr, &sh[EPW + grp]);
-        __syncthreads();                                // barrier 2
-      }
-    } else
-    for (int ts = 0; ts < cfg.frame_skip; ++ts) substep<NV, LPE, true>(s, m, bt, a.col, sub, grp, mq, ctrl, ts > 0, nullptr, nullptr);
-    const bool bad_lane = sub < NV && !(fabs(s.qp[sub]) < EARL_BAD_VALUE && fabs(s.qv[sub]) < EARL_BAD_VALUE);
-    const bool failed = group_any<LPE>(bad_lane, grp);
-    if (failed) {
-      // rolled back to the last stable state (the rows in HBM); returns its last stable observation, reward 0 (kitchen_guard / finish kernels)
-      load_state<NV>(s, m, a.st.qpos + (size_t)env * NV, a.st.qvel + (size_t)env * NV, sub);
-      if (sub < 3) {                                      // ... incl. the mocap target that pulled it there (att_xpos keeps the last stable positions)
-        s.mocap[sub] = mocap_prev;
-        if (live) a.st.mocap_pos[(size_t)env * 3 + sub] = mocap_prev;
-      }
-      if (live) {
-        for (int k = sub; k < 46; k += LPE) a.out.obs[row * 46 + k] = a.st.last_obs[(size_t)env * 46 + k];
-        if (sub == 0) {
-          a.out.reward[row] = 0.0; a.out.success[row] = 0;
-          if (a.st.fail_count) a.st.fail_count[env] += 1;
-        }
-      }
-    } else {
-      if (live) store_state<NV>(s, m, a.st.qpos + (size_t)env * NV, a.st.qvel + (size_t)env * NV, sub);
-      // attachments at the kinematics of the last timestep's start (written only for a step that ended finite); the eight task sites for the reward
-      if (sub < m.n_att && live) {
-        const V3 p = attachment<NV>(s, m, sub);
-        double* o = a.st.att_xpos + ((size_t)env * m.n_att + sub) * 3;
-        o[0] = p.x; o[1] = p.y; o[2] = p.z;
-      }
-      if (sub < 8) {
-        const V3 p = attachment<NV>(s, m, cfg.site_att[sub]);
-        s.kit.sites[sub][0] = p.x; s.kit.sites[sub][1] = p.y; s.kit.sites[sub][2] = p.z;
-      }
-      // Robot.get_obs + KitchenV0._get_obs: 46 draws of U(-1, 1) per env (uniform_kernel: one Philox block = two draws), then kitchen_obs_kernel
-      if (cfg.sensor_noise && sub < 23) {
-        const uint64_t ctr = cfg.counter + (a.clock ? a.clock[0] : 0) + (uint64_t)t;      // + the clock word of a graph-captured launch (earl_kitchen_rollout_clocked)
-        const earl::U4 b = earl::philox4x32_10(earl::U4{0x4B00u + (uint32_t)sub, (uint32_t)(cfg.env_offset + env), (uint32_t)ctr, (uint32_t)(ctr >> 32)},
-                                               (uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32));
-        const double lo = -1.0, hi = 1.0;
-        s.kit.noise[2 * sub] = lo + (hi - lo) * earl::u01(b.x, b.y);
-        s.kit.noise[2 * sub + 1] = lo + (hi - lo) * earl::u01(b.z, b.w);
-      }
-      fence();
-      for (int k = sub; k < 46; k += LPE) {
-        double v;
-        if (k < 23) {
-          v = s.qp[k];
-          if (cfg.sensor_noise) v = v + (kp.robot_noise_ratio * kp.pos_noise_amp[k]) * s.kit.noise[k < 9 ? k : k + 9];
-        } else {
-          v = a.st.goal[(size_t)env * 23 + (k - 23)];
-        }
-        s.kit.obs[k] = v;
-        if (live) {
-          a.out.obs[row * 46 + k] = v;
-          a.st.last_obs[(size_t)env * 46 + k] = v;
-          if (k < 9) a.st.last_qp_robot[(size_t)env * 9 + k] = v;
-        }
-      }
-      fence();
-      if (sub == 0 && live) {                           // kitchen.py:141-183 (kitchen_reward_kernel)
-        const double* o = s.kit.obs;
-        const double dist = kit_norm_diff(o + 9, o + 32, 14);
-        double r = -10 * dist;
-        const int start[8] = {9, 11, 13, 15, 17, 19, 20, 22}, len[8] = {2, 2, 2, 2, 2, 1, 2, 1};
-        bool reaching = false;
-        for (int c = 0; c < 8; ++c) {
-          if (kit_norm_diff(o + start[c], o + start[c] + 23, len[c]) < len[c] * 0.01) r += 1;
-          else if (!reaching) {
-            reaching = true;
-            r += -0.5 * kit_norm_diff(s.mocap, s.kit.sites[c], 3);
-          }
-        }
-        a.out.reward[row] = r;
-        a.out.success[row] = dist <= 0.3;
-      }
-    }
-    ++steps;
-    if (sub == 0 && live) {
-      if (a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
-      a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");    // the next step reads last_qp_robot (and, after a failure, the state rows) back through global memory
-    fence();
-  }
-#ifdef EARL_PHYS_PROF
-  if (lane == 0 && blockIdx.x * WPB + wave < 4096) g_wave_cycles[blockIdx.x * WPB + wave] = __builtin_readcyclecounter() - wave_t0;
-#endif
-  if (sub == 0 && live) a.st.steps_since_reset[env] = steps;
+#include "physics_env_kitchen_rollout.inc"
+}
+// The same kernel with the policy inside (earl_kitchen_policy_rollout), all three launch forms.  `a` must stay the kernel's ONLY argument: the policy phase reads
+// a.pol / a.head / a.gauss / a.obs0 / a.act_out through the kernel-argument segment pointer.  The helper waves of the several-wave forms (DUO 1, 2) take no part in the
+// policy phase: the owner wave computes the action where the plain kernel loads it, before barrier 0, where they wait as they do in the plain kernel.
+template <int DUO>
+__global__ __launch_bounds__(64 * Lim<23>::WPB) void kitchen_policy_rollout_kernel(const KitchenPolicyArgs a) {
+#include "physics_env_kitchen_rollout.inc"
 }

@@ -1,9 +1,12 @@
 // physics_kitchen.hip -- fifth build of the articulated-body stepper: the KITCHEN (BASELINE configs[3]).
 //
 // The stepper (physics_stepper.h) instantiated for nv = 23 (32 lanes per env, arm block + fixtures solver, joint couplings, dry friction, springs, force-limited actuators) plus the kitchen env
-// kernels (physics_env_kitchen.h: the per-step kernels, the fused rollout) and the entry points earl_kitchen_step / earl_kitchen_rollout; earl_physics_step / _forward of the
+// kernels (physics_env_kitchen.h: the per-step kernels, the fused rollout, the fused rollout with an MLP policy inside) and the entry points earl_kitchen_step / earl_kitchen_rollout /
+// earl_kitchen_policy_rollout; earl_physics_step / _forward of the
 // main unit forward nv = 23 here.  A translation unit of its own (round 5): the main unit's compile time was 50 s with it.
 #include "physics_stepper.h"
+#include "policy_check.h"
+#include "policy_math.h"
 
 namespace {
 #include "physics_env_kitchen.h"
@@ -62,6 +65,31 @@ int earl_kitchen_rollout_clocked(const void* model, const earl_collision_model* 
   else if (k.solo == 4) kitchen_rollout_kernel<2><<<(cfg->n + 1) / 2, block_for<23>(), 0, (hipStream_t)stream>>>(k);
   else kitchen_rollout_kernel<0><<<solo_grid(cfg->n, k.solo, Lim<23>::WPB), block_for<23>(), 0, (hipStream_t)stream>>>(k);
   return launched("kitchen_rollout");
+}
+// include/earl_physics.h: T closed-loop env steps in one launch, the policy evaluated by the 32 lanes that own the env.  The launch forms are
+// earl_kitchen_rollout_clocked's, chosen here by the same rule; the kernels are instantiated in physics_kitchen_policy.hip
+int earl_kitchen_policy_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                                const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                                const uint64_t* clock, float* actions, const earl_kitchen_out* out, earl_stream_t stream) {
+  if (!model || !params || !cfg || !st || !policy || !obs0 || !actions || !out || cfg->n < 0 || T < 0 || cfg->n_att < 10 || cfg->n_att > 32 || cfg->frame_skip < 0) return EARL_ERR_ARG;
+  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !st->last_qp_robot || !st->att_xpos || !st->steps_since_reset || !st->last_obs) return EARL_ERR_ARG;
+  if (!out->obs || !out->reward || !out->done || !out->success || !cfg->mocap_quat_dev) return EARL_ERR_ARG;
+  for (int k = 0; k < 8; ++k) if (cfg->site_att[k] < 0 || cfg->site_att[k] >= cfg->n_att) return EARL_ERR_ARG;
+  // the policy's contract (policy_check.h).  The reference clips the action silently, so an unbounded output is taken (unlike the minitaur's)
+  if (earl::contract::check_policy(*policy, 46, 9, head, earl::contract::kParamsAligned16, nullptr)) return EARL_ERR_ARG;
+  if (cfg->n == 0 || T == 0) return EARL_OK;
+  if (int rc = check_cone(col, false, (hipStream_t)stream, "kitchen_policy_rollout")) return rc;
+  KitchenPolicyArgs k;
+  static_cast<KitchenRolloutArgs&>(k) = KitchenRolloutArgs{model, col, *params, *cfg, *st, *out, nullptr, T, solo_mode(cfg->n), clock};
+  k.pol = *policy;
+  k.head = head ? *head : earl::contract::default_head();
+  k.gauss = head ? 1 : 0;
+  k.obs0 = obs0;
+  k.act_out = actions;
+  if (k.solo == 2 && g_solo < 0) k.solo = 3;      // the plain entry point's rule
+  if (g_solo < 0 && k.solo == 1 && cfg->n <= 2 * cu_count()) k.solo = 4;
+  earl_unit_kitchen_policy_rollout(&k, stream);      // physics_kitchen_policy.hip holds the kernels
+  return launched("kitchen_policy_rollout");
 }
 int earl_kitchen_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                          const earl_kitchen_state* st, const float* action, int32_t T, const earl_kitchen_out* out, earl_stream_t stream) {

@@ -1,4 +1,4 @@
-// physics_launch.h -- host helpers of the five stepper units (physics.hip, physics_w8.hip, physics_l64.hip, physics_kitchen.hip, physics_mt.hip):
+// physics_launch.h -- host helpers of the six stepper units (physics.hip, physics_w8.hip, physics_l64.hip, physics_kitchen.hip, physics_kitchen_policy.hip, physics_mt.hip):
 // launch checks, the calls from one unit into another, launch geometry and the profiling build's hooks.  Included after physics_stepper.h and the
 // unit's env kernels; what sits in the anonymous namespace here is the including unit's own copy.
 #pragma once
@@ -9,6 +9,8 @@ extern "C" __attribute__((visibility("hidden"))) int earl_unit_table_cone(const 
 extern "C" __attribute__((visibility("hidden"))) void earl_unit_l64_physics(const void* pargs, int nv, int integrate, void* stream);
 extern "C" __attribute__((visibility("hidden"))) void earl_unit_l64_sawyer_rollout(const void* sawyer_args, int nv, void* stream);
 extern "C" __attribute__((visibility("hidden"))) void earl_unit_kitchen_physics(const void* pargs, int integrate, void* stream);      // physics_kitchen.hip: nv = 23
+// the kitchen rollout with the policy inside (physics_kitchen_policy.hip): earl_kitchen_policy_rollout hands it its KitchenPolicyArgs, launch form chosen (solo)
+extern "C" __attribute__((visibility("hidden"))) void earl_unit_kitchen_policy_rollout(const void* kitchen_policy_args, void* stream);
 // the door's eight-wave rollout (physics_w8.hip): earl_sawyer_rollout(_clocked) hands it its argument struct (the clock included); earl_sawyer_rollout_door_w8 is
 // exported like the other entry points
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_w8_sawyer_rollout(const void* sawyer_args, void* stream);

@@ -29,6 +29,7 @@ import torch
 
 from .. import _abi, glue, physics, tables
 from ..spaces import Box
+from . import physics_policy_rollout as closed_loop
 from .physics_step_graph import PhysicsStepGraph
 
 INT32_MAX = 2**31 - 1
@@ -117,6 +118,8 @@ class Kitchen:
                                  last_qp_robot=self.last_qp_robot.data_ptr(), att_xpos=self.att.data_ptr(), steps_since_reset=self.steps_since_reset.data_ptr(),
                                  fail_count=self.fail_count.data_ptr(), last_obs=self.last_obs.data_ptr(), **{k: v.data_ptr() for k, v in self._scr.items()})
     self.action_space = Box(-1.0, 1.0, (self.N_ROBOT,), np.float32)              # kitchen_multitask_v0.py:78-80
+    self._last_success = torch.zeros(n, dtype=torch.bool, device=dev)
+    self._last_obs_stale = False      # last_obs no longer describes (state, goal): set by set_state() / reset_goal(), cleared by whatever rewrites every row
     self.observation_space = Box(-8.0, 8.0, (self.OBS_DIM,), np.float64)         # :82-84
     with torch.cuda.device(dev):
       self._reset_states = self._settle_reset_states()
@@ -188,6 +191,8 @@ class Kitchen:
       obs = self._observe(noise=True)
       obs = torch.where(m[:, None], obs, prev)
       self.last_obs.copy_(obs)
+    if mask is None:
+      self._last_obs_stale = False
     self._counter += 1
     return obs[0].cpu().numpy() if self.scalar_api else obs
 
@@ -227,6 +232,7 @@ class Kitchen:
     self._counter += 1
     self.total_step_count += 1
     self._last_success = suc
+    self._last_obs_stale = False
     if self.scalar_api:
       return obs[0].cpu().numpy(), float(rew[0]), bool(done[0]), info
     return obs, rew, done, info
@@ -272,6 +278,7 @@ class Kitchen:
     self._counter += T
     self.total_step_count += T
     self._last_success = out['success'][-1]
+    self._last_obs_stale = False
 
   def _graph_info(self, out):
     return {'success': out['success'], 'is_successful': out['success'], 'status': out['status']}
@@ -325,6 +332,7 @@ class Kitchen:
       self._counter += T
       self.total_step_count += T
       self._last_success = res['success'][-1]
+      self._last_obs_stale = False
       return res
     res = out if out is not None else {}
     sc, self.scalar_api = self.scalar_api, False          # (the step loop stacks batched tensors; with scalar_api step() returns numpy / python scalars)
@@ -335,6 +343,62 @@ class Kitchen:
     res['obs'] = torch.stack([r[0] for r in rows]); res['reward'] = torch.stack([r[1] for r in rows]); res['done'] = torch.stack([r[2] for r in rows])
     res['success'] = torch.stack([r[3]['success'] for r in rows]); res['status'] = torch.stack([r[3]['status'] for r in rows])
     return res
+
+  # ------------------------------------------------------------------ closed loop, the policy inside the rollout kernel
+  def _new_out(self, lead):
+    n, kw = self.num_envs, dict(device=self.device)
+    return dict(obs=torch.empty(*lead, n, self.OBS_DIM, dtype=torch.float64, **kw), reward=torch.empty(*lead, n, dtype=torch.float64, **kw),
+                done=torch.empty(*lead, n, dtype=torch.bool, **kw), success=torch.empty(*lead, n, dtype=torch.bool, **kw),
+                status=torch.empty(*lead, n, dtype=torch.uint8, **kw))
+
+  def _check_policy(self, policy, who):
+    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy of this env's widths on this env's device.  The reference clips the action silently
+    (kitchen_multitask_v0.py:92): an unbounded output is taken"""
+    from ..policy import AgentPair, PolicyPopulation, require_widths
+    if isinstance(policy, PolicyPopulation):
+      raise NotImplementedError(f'{who}: a PolicyPopulation on the kitchen is not offered (one MLPPolicy / GaussianMLPPolicy per launch; populations run on the tabletop, '
+                                'the Sawyer door and the Sawyer peg)')
+    if isinstance(policy, AgentPair):
+      raise NotImplementedError(f'{who}: an AgentPair on the kitchen is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
+    if self.scalar_api:
+      raise ValueError(f'{who}: scalar_api returns one env\'s numpy rows; the closed-loop launch returns batched tensors (Kitchen(..., scalar_api=False))')
+    if int(self._cfg.goal_change_frequency) > 0:
+      raise ValueError(f'{who}: the kitchen\'s lifelong goal switch runs on the host (goal_change_frequency > 0) and cannot happen inside the launch, as make_step_graph says')
+    return require_widths(policy, who, self.OBS_DIM, self.N_ROBOT, env=self)
+
+  def _launch_policy(self, policy, head, obs0, T, out):
+    """hook of physics_policy_rollout: earl_kitchen_policy_rollout; the sensor-noise counter advances by T"""
+    o = _abi.KitchenOut(obs=out['obs'].data_ptr(), reward=out['reward'].data_ptr(), done=out['done'].data_ptr(), success=out['success'].data_ptr(),
+                        status=out['status'].data_ptr())
+    self._cfg.counter = self._counter
+    with torch.cuda.device(self.device):
+      _abi.check(self._lib.earl_kitchen_policy_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._params), C.byref(self._cfg), C.byref(self._st),
+                                                       C.byref(policy.struct), None if head is None else C.byref(head), obs0.data_ptr(), T, None,
+                                                       out['actions'].data_ptr(), C.byref(o), self._stream()), 'earl_kitchen_policy_rollout')
+    self._counter += T
+
+  def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
+    """physics_policy_rollout's closed loop (its docstring is the contract) on earl_kitchen_policy_rollout: `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy` built
+    with obs_dim=46, act_dim=9 (bounded or not: the env clips), evaluated by the 32 lanes that own the env.  The policy sees the observation rows as emitted, sensor
+    noise included; after set_state() / reset_goal() its first observation is a fresh reading (one noise draw: the counter advances by T + 1).
+    -> rollout()'s dict plus 'actions' [T, N, 9] and, with return_noise=True, 'eps' [T, N, 9]"""
+    return closed_loop.rollout_policy(self, policy, T, reset_first, sample, return_noise, out)
+
+  def rollout_agents(self, pair, T, **kw):
+    raise NotImplementedError('rollout_agents: an AgentPair on the kitchen is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
+
+  def evaluate_policy(self, policy, T, **kw):
+    raise NotImplementedError('evaluate_policy: episode summaries on the kitchen are not offered (rollout_policy returns every step; evaluate_policy runs on the '
+                              'tabletop, the Sawyer door and the Sawyer peg)')
+
+  def _get_obs_t(self):
+    """a fresh reading as _get_obs() makes it (a noise draw on the current counter, last_qp_robot updated), as the [N, 46] tensor whatever scalar_api says, and
+    written to last_obs: the row a first step in its failure guard repeats"""
+    with torch.cuda.device(self.device):
+      obs = self._observe(noise=True)
+      self.last_obs.copy_(obs)
+    self._counter += 1
+    return obs
 
   def _get_obs(self):
     with torch.cuda.device(self.device):
@@ -373,6 +437,7 @@ class Kitchen:
     else:
       m = torch.as_tensor(mask, device=self.device).bool()
       self.goal_t[m] = g[m]
+    self._last_obs_stale = True                            # (last_obs carries the old goal entries: rollout_policy takes a fresh reading first)
 
   def get_task(self):
     return self._task
@@ -385,16 +450,21 @@ class Kitchen:
     return self.goal_t[0].cpu().numpy() if self.scalar_api else self.goal_t
 
   def set_state(self, qpos, qvel):
+    self._last_obs_stale = True                            # (last_obs no longer belongs to the state: rollout_policy takes a fresh reading first)
     self.qpos.copy_(torch.as_tensor(qpos, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.NV))
     self.qvel.copy_(torch.as_tensor(qvel, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.NV))
 
   def state_dict(self):
     keys = ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'last_qp_robot', 'att', 'steps_since_reset', 'interventions', 'fail_count', 'lifelong_return_t',
             'steps_since_goal_change', 'last_obs')
-    return {k: getattr(self, k).clone() for k in keys} | {'counter': self._counter, 'total_step_count': self.total_step_count}
+    return {k: getattr(self, k).clone() for k in keys} | {'counter': self._counter, 'total_step_count': self.total_step_count,
+                                                          'last_obs_stale': bool(self._last_obs_stale)}
 
   def load_state_dict(self, sd):
+    self._last_obs_stale = bool(sd.get('last_obs_stale', False))      # (a dict written before the flag existed: not stale)
     for k, v in sd.items():
+      if k == 'last_obs_stale':
+        continue
       if k == 'counter':
         self._counter = int(v)
       elif k == 'total_step_count':

@@ -1,5 +1,5 @@
-"""The closed loop of the stepper envs (door, peg, minitaur) as their `rollout_policy` offers it: what the envs share around the ONE launch of their rollout kernel
-with a policy inside it (include/earl_physics.h: earl_sawyer_population_rollout, earl_minitaur_policy_rollout), next to `PhysicsStepGraph`.  The env's side is a few
+"""The closed loop of the stepper envs (door, peg, minitaur, kitchen) as their `rollout_policy` offers it: what the envs share around the ONE launch of their rollout kernel
+with a policy inside it (include/earl_physics.h: earl_sawyer_population_rollout, earl_minitaur_policy_rollout, earl_kitchen_policy_rollout), next to `PhysicsStepGraph`.  The env's side is a few
 hooks: `_check_policy(policy, who)` -> is it Gaussian (policy.require_widths with the env's widths and rules), `_new_out((T,))`, `reset()`, `last_obs` /
 `_last_obs_stale` / `_get_obs_t()`, and `_launch_policy(policy, head, obs0, T, out)`: the launch itself.
 

@@ -18,6 +18,11 @@ The minitaur takes them with obs_dim=32, act_dim=8 and a bounded output (include
   pi = MLPPolicy(layers, 'relu', 'tanh', device='cuda', obs_dim=32, act_dim=8)                  # or GaussianMLPPolicy(..., squash=True, obs_dim=32, act_dim=8)
   out = minitaur.rollout_policy(pi, T=250)                                                      # rollout()'s dict plus 'actions' [T, N, 8], ONE launch
 
+The kitchen takes them with obs_dim=46, act_dim=9, bounded or not -- the env clips the action as the reference does (include/earl_physics.h: earl_kitchen_policy_rollout):
+
+  pi = MLPPolicy(layers, 'relu', 'tanh', device='cuda', obs_dim=46, act_dim=9)                  # or GaussianMLPPolicy(..., obs_dim=46, act_dim=9)
+  out = kitchen.rollout_policy(pi, T=400)                                                       # rollout()'s dict plus 'actions' [T, N, 9], ONE launch
+
 `GaussianMLPPolicy` is the SAC-style actor with a tanh-Gaussian head, 12 -> hidden (-> hidden) -> 6 (rows 0..2 mean, rows 3..5 raw log_std), for
 earl_tabletop_policy_rollout_gaussian: the actions are SAMPLED inside the kernel from the env's counter-based RNG.
 
@@ -81,7 +86,7 @@ class MLPPolicy:
   OUT_DIM, OUT_WHAT = ACT_DIM, 'action'
 
   def __init__(self, layers, hidden_act='relu', out_act='tanh', device='cpu', obs_dim=OBS_DIM, act_dim=ACT_DIM):
-    """obs_dim / act_dim: the env's observation and action widths -- the tabletop's 12 / 3 by default, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur (`env.rollout_policy`)"""
+    """obs_dim / act_dim: the env's observation and action widths -- the tabletop's 12 / 3 by default, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur, 46 / 9 for the kitchen (`env.rollout_policy`)"""
     name = type(self).__name__                                        # (MLPPolicy's own messages read as they always did)
     self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
     if self.obs_dim < 1 or self.act_dim < 1:

@@ -459,6 +459,34 @@ int earl_kitchen_rollout(const void* model24, const earl_collision_model* col, c
 int earl_kitchen_rollout_clocked(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                                  const earl_kitchen_state* st, const float* action /* [T, n, 9] */, int32_t T, const uint64_t* clock, const earl_kitchen_out* out,
                                  earl_stream_t stream);
+/* ---- closed loop: an MLP policy evaluated INSIDE the kitchen rollout kernel ----
+ * T closed-loop env steps of every env in ONE launch of the kitchen rollout kernel: between two env steps the 32 lanes that own an env evaluate the policy, observation ->
+ * float32 MLP 46 -> hidden (-> hidden) -> 9 -> action -> next env step, so the waves drift apart over the whole rollout as they do in earl_kitchen_rollout (a captured
+ * loop of T one-step launches waits for the slowest wave T times).  earl_mlp_policy / earl_gaussian_head are earl_tabletop.h's, with dims[0] = 46 and dims[n_layers] = 9
+ * (head = NULL) or 18 (head given: output rows 0..8 the mean, rows 9..17 the raw log_std); hidden widths multiples of 16 in 16..256; policy->params 16-byte aligned
+ * (the rows of every layer after the first are read in 16-byte pieces; the input layer's rows, 184 bytes, are read element by element).
+ * Per env and env step t, in this order:
+ *   1. input: at t = 0 the env's row of obs0 [n, 46] (device); at t > 0 the row the env emitted at step t - 1 exactly as it stands in out->obs -- the sensor noise and
+ *      the repeated row of a rolled-back step included (the same bits stand in the env's row of st->last_obs) -- each double rounded once to float32;
+ *   2. network: the contract of earl_tabletop_policy_rollout (acc = b_j; k ascending: acc = fmaf(x_k, W_jk, acc); relu_f32, tanh_f32; the head's exp_f32,
+ *      normal_quantile_f32, log_std maps and u = fmaf(exp_f32(ls), eps, mean): csrc/policy_math.h); earl_mlp_policy_forward_cpu above states it on the host;
+ *   3. head: THREE Philox4x32-10 blocks per (env, env step), key = cfg->seed, block b in {0, 1, 2} with counter words {0x504F4C00 + b, cfg->env_offset + env, ev lo, ev hi},
+ *      ev = cfg->counter + clock[0] + t (the step's sensor-noise counter; the noise's draw indices are 0x4B00 + j: the streams are disjoint); words x, y, z, w of block b ->
+ *      action dimensions 4 b .. 4 b + 3 (block 2: x only), each as normal_quantile_f32(word >> 8);
+ *   4. stores: actions[t] ([T, n, 9] device, required) and head->eps_out[t] ([T, n, 9] or NULL, written in both modes);
+ *   5. the env step of earl_kitchen_rollout_clocked on exactly the float32 values stored in actions[t], through its own clip to [-1, 1] -- the reference clips silently
+ *      (kitchen_multitask_v0.py:92), so an unbounded policy (out_act == EARL_ACT_NONE) is taken, unlike on the minitaur -- then failure guard, rollback of the state and
+ *      the mocap target, noise, reward, bookkeeping: the same statements.
+ * The launch is therefore bit-identical to earl_kitchen_rollout_clocked fed with the actions it returns: every array of `out`, qpos, qvel, mocap_pos, last_qp_robot,
+ * last_obs, att_xpos, steps_since_reset, fail_count.  clock as for earl_kitchen_rollout_clocked (may be NULL).  The launch form is picked by that entry point's rule
+ * (earl_debug_set_solo: two envs per wave, one env per wave, one env per workgroup on one, four or two waves; in the several-wave forms the env's owner wave evaluates the
+ * policy); all five forms return the same bits.
+ * EARL_ERR_ARG before any HIP call: everything earl_kitchen_rollout_clocked refuses, the policy and head rules of earl_tabletop.h's argument contract with the widths
+ * 46 / 9, and this entry point's own: NULL policy / obs0 / actions, policy->params not 16-byte aligned.  n = 0 or T = 0: EARL_OK, nothing launched.
+ * The lifelong wrapper's goal switch is not part of it, as for earl_kitchen_rollout. */
+int earl_kitchen_policy_rollout(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                                const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                                const uint64_t* clock, float* actions, const earl_kitchen_out* out, earl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Minitaur env (BASELINE configs[4]) on the same stepper: floating base + 16 hinges (nv = 22, nq = 23), four connect

@@ -121,7 +121,7 @@ int earl_tabletop_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tableto
  * v_mfma_f32_16x16x4_f32 next to the fp64 recurrence, weights resident in registers for the whole launch.
  *
  * THE ARGUMENT CONTRACT of every closed-loop entry point -- the four of this header, and earl_physics.h's earl_sawyer_policy_rollout, earl_sawyer_population_rollout,
- * earl_sawyer_pair_rollout and earl_minitaur_policy_rollout -- is one set of rules (csrc/policy_check.h states them once; tests/test_policy_contract.py holds every
+ * earl_sawyer_pair_rollout, earl_minitaur_policy_rollout and earl_kitchen_policy_rollout -- is one set of rules (csrc/policy_check.h states them once; tests/test_policy_contract.py holds every
  * entry point to them).  Each returns EARL_ERR_ARG before any HIP call for
  *   policy      NULL params; precision != 0; n_layers not 2 or 3; dims[0] != the env's observation width; dims[n_layers] != the env's action width (head == NULL) or
  *               twice it (head given); a hidden width that is not a multiple of 16 in 16..256; dims[3] != 0 with two layers; hidden_act not EARL_ACT_RELU / _TANH;
@@ -131,7 +131,7 @@ int earl_tabletop_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tableto
  *               (env_offset + n - 1) / G >= P
  *   pair        NULL pair / phase / steps_in_phase; switch_every[k] < 1; switch_on_success not 0 or 1; param_stride below the parameter count;
  *               cfg->goal_change_frequency > 0 (the pair IS the lifelong mechanism: the two clocks would fight over the same draw)
- * with the widths 12 / 3 here, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur.  The differences are three, each listed with its entry point: the stepper
+ * with the widths 12 / 3 here, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur, 46 / 9 for the kitchen.  The differences are three, each listed with its entry point: the stepper
  * units read the weight rows in 16-byte pieces (params 16-byte aligned, param_stride % 4 == 0), the minitaur takes bounded policies only (out_act == EARL_ACT_TANH),
  * and this header's pair holds two weight sets in registers (EARL_PAIR_MAX_H2). */
 enum { EARL_ACT_NONE = 0, EARL_ACT_RELU = 1, EARL_ACT_TANH = 2 };

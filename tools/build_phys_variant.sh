@@ -7,10 +7,10 @@ tag=$1; shift
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fPIC"
 U=../../tools/ubench
 mkdir -p $U
-for u in physics physics_w8 physics_mt physics_l64 physics_kitchen; do
+for u in physics physics_w8 physics_mt physics_l64 physics_kitchen physics_kitchen_policy; do
   /opt/rocm/bin/hipcc $FLAGS "$@" -c -o $U/${u}_$tag.o $u.hip &
 done
 wait
-/opt/rocm/bin/hipcc $FLAGS -shared -o $U/libearl_phys_$tag.so tabletop.o glue.o $U/physics_$tag.o $U/physics_w8_$tag.o $U/physics_mt_$tag.o $U/physics_l64_$tag.o $U/physics_kitchen_$tag.o
+/opt/rocm/bin/hipcc $FLAGS -shared -o $U/libearl_phys_$tag.so tabletop.o glue.o $U/physics_$tag.o $U/physics_w8_$tag.o $U/physics_mt_$tag.o $U/physics_l64_$tag.o $U/physics_kitchen_$tag.o $U/physics_kitchen_policy_$tag.o
 rm -f $U/physics*_$tag.o
 echo built libearl_phys_$tag.so

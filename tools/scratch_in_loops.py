@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""VERDICT r04 item 4 "no scratch inside any timestep loop": where do the rollout kernels' scratch (spill) instructions sit?  Compiles the five stepper units (csrc/physics.hip, physics_kitchen.hip, physics_mt.hip, physics_w8.hip, physics_l64.hip) to
-gfx950 assembly (device only), finds every loop of each rollout kernel (the Sawyer and minitaur rollouts with the policy inside, sawyer_policy_rollout_kernel and minitaur_policy_kernel, included) (a backward branch to a label), nests them by extent and reports the scratch_load / scratch_store count of the
+"""VERDICT r04 item 4 "no scratch inside any timestep loop": where do the rollout kernels' scratch (spill) instructions sit?  Compiles the six stepper units (csrc/physics.hip, physics_kitchen.hip, physics_kitchen_policy.hip, physics_mt.hip, physics_w8.hip, physics_l64.hip) to
+gfx950 assembly (device only), finds every loop of each rollout kernel (the Sawyer, kitchen and minitaur rollouts with the policy inside, sawyer_policy_rollout_kernel, kitchen_policy_rollout_kernel and minitaur_policy_kernel, included) (a backward branch to a label), nests them by extent and reports the scratch_load / scratch_store count of the
 kernel, of its env-step loop (the largest loop) and of its TIMESTEP loop (the largest loop strictly inside the env-step loop that holds more than a third of it: the stepper's body).
   python tools/scratch_in_loops.py > profiles/r05_scratch_report.txt          (no GPU needed; ~2 min)
   python tools/scratch_in_loops.py --policy-duo          additionally lists the minitaur's two-wave kernel with the policy inside (minitaur_policy_duo_kernel: a slot-loop line
@@ -14,7 +14,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'earl_benchmark_amd', 'csrc')
 FLAGS = '--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fPIC --cuda-device-only -S'.split()
-KERNELS = ('sawyer_rollout_kernel', 'sawyer_policy_rollout_kernel', 'kitchen_rollout_kernel', 'minitaur_kernel', 'minitaur_policy_kernel', 'minitaur_duo_kernel', 'physics_kernel')
+KERNELS = ('sawyer_rollout_kernel', 'sawyer_policy_rollout_kernel', 'kitchen_rollout_kernel', 'kitchen_policy_rollout_kernel', 'minitaur_kernel', 'minitaur_policy_kernel', 'minitaur_duo_kernel', 'physics_kernel')
 POLICY_DUO = ('minitaur_policy_duo_kernel',)      # report(..., kernels=KERNELS + POLICY_DUO) / --policy-duo
 
 
@@ -66,7 +66,7 @@ def report(unit, lines, kernels=KERNELS):
 
 def main():
   kernels = KERNELS + (POLICY_DUO if '--policy-duo' in sys.argv[1:] else ())
-  for unit in ('physics.hip', 'physics_kitchen.hip', 'physics_mt.hip', 'physics_w8.hip', 'physics_l64.hip'):
+  for unit in ('physics.hip', 'physics_kitchen.hip', 'physics_kitchen_policy.hip', 'physics_mt.hip', 'physics_w8.hip', 'physics_l64.hip'):
     with tempfile.NamedTemporaryFile(suffix='.s') as f:
       subprocess.run(['/opt/rocm/bin/hipcc'] + FLAGS + ['-o', f.name, os.path.join(CSRC, unit)], check=True, stderr=subprocess.DEVNULL)
       lines = open(f.name).read().split('\n')

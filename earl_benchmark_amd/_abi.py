@@ -60,6 +60,10 @@ class AgentPair(C.Structure):          # struct earl_agent_pair (include/earl_ta
               ('phase', C.c_void_p), ('steps_in_phase', C.c_void_p), ('agent_out', C.c_void_p), ('forward_success', C.c_void_p), ('backward_success', C.c_void_p)]
 
 
+class BackwardGoals(C.Structure):      # struct earl_backward_goals (include/earl_physics.h)
+  _fields_ = [('table', C.c_void_p), ('n_rows', C.c_int32), ('pad_', C.c_int32), ('row', C.c_void_p), ('row_out', C.c_void_p)]
+
+
 PAIR_MAX_H2 = 128                      # EARL_PAIR_MAX_H2: the widest second hidden layer of an agent pair
 
 
@@ -203,6 +207,9 @@ SIGNATURES = {
     # ... for the forward / reset agent pair: pair after policy (backward_goal a row of 7, agent_out [T, n], the counters [n])
     'earl_sawyer_pair_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(MlpPolicy), _P(AgentPair), _P(GaussianHead), C.c_void_p,
                                  C.c_int32, C.c_void_p, C.c_void_p, _P(SawyerOut), C.c_void_p],
+    # ... in its general form: pop and goals after pair, summary after `out`, each NULL or given
+    'earl_sawyer_agents_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(MlpPolicy), _P(AgentPair), _P(PolicyPopulation), _P(BackwardGoals),
+                                   _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _P(SawyerOut), _P(EpisodeSummary), C.c_void_p],
     # the closed loop inside the minitaur rollout kernels: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
     'earl_minitaur_policy_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, _P(MinitaurOut), C.c_void_p],

@@ -160,11 +160,11 @@ int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model
 // population's member per env, every [T] output optional, per-env episode summaries.  The launch forms are
 // earl_sawyer_rollout's (door: four one-wave workgroups per CU, eight waves per CU above 4096 envs; peg: whole rollouts or the time-sliced queue); the 64-lane
 // measurement builds (earl_debug_set_physics_lanes(64)) and the door's time-sliced measurement variant have no policy form
-// (the body of the closed-loop entry points: a population with summaries, or an agent pair -- never both)
+// (the body of the closed-loop entry points: a population, summaries, an agent pair and its table of backward goals, each there or not)
 static int sawyer_closed_loop(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
-                              const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_agent_pair* pair, bool paired, const earl_gaussian_head* head,
-                              const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_sawyer_out* out, const earl_episode_summary* summary,
-                              earl_stream_t stream) {
+                              const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_agent_pair* pair, bool paired, const earl_backward_goals* goals,
+                              const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_sawyer_out* out,
+                              const earl_episode_summary* summary, earl_stream_t stream) {
   if (!model || !cfg || !st || !out || !policy || !obs0 || T < 1 || cfg->n < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal) return EARL_ERR_ARG;
   if (!out->obs && !st->last_obs) return EARL_ERR_ARG;    // (without out->obs the env's row of last_obs is the one observation row the launch keeps)
@@ -180,6 +180,8 @@ static int sawyer_closed_loop(const earl_link_model* model, const earl_collision
   if (paired) {
     if (earl::contract::check_pair(*policy, pair, cfg->goal_change_frequency, 4, nullptr)) return EARL_ERR_ARG;
     if (pair->backward_goal && cfg->n_goal_rows == 0) return EARL_ERR_ARG;   // (the forward goal could not be restored)
+    if (pop && earl::contract::check_pair_population(*pop, *pair, nullptr)) return EARL_ERR_ARG;
+    if (goals && earl::contract::check_backward_goals(*goals, *pair, cfg->n_goal_rows, nullptr)) return EARL_ERR_ARG;
   }
   if (g_lpe == 64) return EARL_ERR_ARG;                   // (the 64-lane measurement builds: no policy form)
   if (cfg->n == 0) return EARL_OK;
@@ -199,7 +201,10 @@ static int sawyer_closed_loop(const earl_link_model* model, const earl_collision
   a.pair_phase = paired ? pair->phase : nullptr;
   a.pair_sip = paired ? pair->steps_in_phase : nullptr;
   a.pair_stride = paired ? pair->param_stride : 0;
-  a.pair_goal = paired ? pair->backward_goal : nullptr;
+  a.pair_goal = !paired ? nullptr : (goals ? goals->table : pair->backward_goal);      // (the ONE fixed row: the table of one row)
+  a.pair_goal_rows = !paired ? 0 : (goals ? goals->n_rows : (pair->backward_goal ? 1 : 0));
+  a.pair_row = paired && goals ? goals->row : nullptr;
+  a.pair_row_out = paired && goals ? goals->row_out : nullptr;
   a.pair_se[0] = paired ? pair->switch_every[0] : 0;
   a.pair_se[1] = paired ? pair->switch_every[1] : 0;
   a.pair_sos = paired ? pair->switch_on_success : 0;
@@ -221,13 +226,20 @@ static int sawyer_closed_loop(const earl_link_model* model, const earl_collision
 int earl_sawyer_population_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                    const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
                                    const uint64_t* clock, float* actions, const earl_sawyer_out* out, const earl_episode_summary* summary, earl_stream_t stream) {
-  return sawyer_closed_loop(model, col, nv, cfg, st, policy, pop, nullptr, false, head, obs0, T, clock, actions, out, summary, stream);
+  return sawyer_closed_loop(model, col, nv, cfg, st, policy, pop, nullptr, false, nullptr, head, obs0, T, clock, actions, out, summary, stream);
 }
-// the forward / reset agent pair: the same launch with the phase state machine switched on (no population, no summary)
+// the forward / reset agent pair in its general form: a population of pairs, a table of backward goals and summaries, each NULL or given
+int earl_sawyer_agents_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop, const earl_backward_goals* goals,
+                               const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_sawyer_out* out,
+                               const earl_episode_summary* summary, earl_stream_t stream) {
+  return sawyer_closed_loop(model, col, nv, cfg, st, policy, pop, pair, true, goals, head, obs0, T, clock, actions, out, summary, stream);
+}
+// the forward / reset agent pair: the same launch with the phase state machine switched on (no population, no table, no summary)
 int earl_sawyer_pair_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                              const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_gaussian_head* head, const double* obs0, int32_t T,
                              const uint64_t* clock, float* actions, const earl_sawyer_out* out, earl_stream_t stream) {
-  return sawyer_closed_loop(model, col, nv, cfg, st, policy, nullptr, pair, true, head, obs0, T, clock, actions, out, nullptr, stream);
+  return earl_sawyer_agents_rollout(model, col, nv, cfg, st, policy, pair, nullptr, nullptr, head, obs0, T, clock, actions, out, nullptr, stream);
 }
 // one policy, every [T] row kept: the population entry point without a population and without a summary (the same launch, bit for bit)
 int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,

@@ -33,12 +33,17 @@ struct SawyerPolicyArgs : SawyerArgs {
   int8_t* pair_phase;            // [n] 0 forward, anything else reset; the network of the phase starts at pol.params + phase * pair_stride
   int32_t* pair_sip;             // [n] steps the env has spent in its phase
   int64_t pair_stride;           // floats between the two agents' rows (a multiple of 4)
-  const double* pair_goal;       // NULL or the ONE row of 7 doubles that becomes the env's st.goal row on entering the reset phase
+  const double* pair_goal;       // NULL or the table [pair_goal_rows, 7] of backward goals: entering the reset phase, a drawn row of it becomes the env's st.goal row
+                                 // (earl_sawyer_pair_rollout's ONE fixed row is the table of one row)
   int pair_se[2];                // switch_every
   int pair_sos;                  // switch_on_success
   int8_t* pair_agent;            // NULL or [T, n]
   int32_t* pair_fs;              // NULL or [n]: forward phases that ended by success (step 0 of the launch starts them at 0)
   int32_t* pair_bs;              // NULL or [n]: reset phases that ended by success
+  // earl_sawyer_agents_rollout: the backward-goal table (earl_backward_goals).  `pair_goal` above is its base; written by ONE lane of the env, never read by the kernel
+  int pair_goal_rows;            // rows of pair_goal (1 for the fixed row; 0 with pair_goal == NULL)
+  int32_t* pair_row;             // NULL or [n]: the table row the env's reset goal came from, stored at every entry into the reset phase
+  int32_t* pair_row_out;         // NULL or [T, n]: the row drawn at env step t, -1 at a step without a draw
 };
 
 // Work queue of the time-sliced rollout (earl_sawyer_state.sched: progress[G] then lock[G], zero on entry).  An env group's state is in HBM after every env

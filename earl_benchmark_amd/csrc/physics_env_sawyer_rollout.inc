@@ -163,11 +163,15 @@
     // door with goal switching: slot 7 of EVERY row's info block is this kernel's to write -- 0, or 1 on a goal-switch row (below) -- so that earl_sawyer_door_info never reads
     // a marker the caller left behind (ADVICE r05: the Python side used to zero the column with a launch of its own before every call)
     if (NV < 15 && gcf > 0 && a.out.info && sub == 11 && live) a.out.info[row * EARL_SAWYER_INFO + 7] = 0.0;
-    // does this step end with a new goal row?  The lifelong switch's clock, or -- POLICY, earl_sawyer_pair_rollout -- a handover of the agent pair that changes the goal:
-    // `fixed` is then the row to install (entering the reset phase) or NULL (entering the forward phase: the lifelong switch's own draw)
+    // does this step end with a new goal row?  The lifelong switch's clock, or -- POLICY, earl_sawyer_agents_rollout -- a handover of the agent pair that changes the goal:
+    // `fixed` is then the table of `fixed_rows` backward goals to draw from (entering the reset phase; earl_sawyer_pair_rollout's ONE row is the table of one row) or NULL
+    // (entering the forward phase: the lifelong switch's own draw from cfg.goal_table)
     // (the plain kernels: `POLICY && ...` folds away in the front end, and their statements -- and machine code -- are what they were)
     [[maybe_unused]] bool pair_sw = false;
     [[maybe_unused]] const double* fixed = nullptr;
+    [[maybe_unused]] int fixed_rows = 0;
+    [[maybe_unused]] int32_t* row_of = nullptr;          // earl_backward_goals.row / row_out: where lane 7 of the env leaves the drawn row
+    [[maybe_unused]] int32_t* row_at = nullptr;
     [[maybe_unused]] bool pair_on = false;
     if constexpr (POLICY) {
       // The pair's state machine (include/earl_physics.h, item 5), worked out by all 16 lanes of the env from the same words: the step's success flag from lane 0, phase
@@ -193,10 +197,13 @@
         if (over) {
           ph ^= 1;
           sip = 0;
-          if (ph) { fixed = ka->pair_goal; pair_sw = fixed != nullptr; }      // entering the reset phase: the backward row, if there is one
+          if (ph) { fixed = ka->pair_goal; fixed_rows = ka->pair_goal_rows; row_of = ka->pair_row; pair_sw = fixed != nullptr; }      // entering the reset phase: a row of the backward table, if there is one
           else pair_sw = cfg.n_goal_rows > 0;                                   // entering the forward phase: the lifelong switch's draw for this step
         }
         if (sub == 0 && live) { pair_phase[env] = (int8_t)ph; pair_sip[env] = sip; }
+        // row_out: -1 at every step of a live env, overwritten below by the same lane on a step that draws (like slot 7 of the door's info block above)
+        row_at = ka->pair_row_out;
+        if (row_at && sub == 7 && live) row_at[row] = -1;
       }
     }
     if ((gcf > 0 && ++sgc >= gcf) || (POLICY && pair_sw)) {
@@ -207,11 +214,22 @@
         // the host's step counter plus the clock word of a graph-captured launch (earl_sawyer_rollout_clocked), read here -- a goal-switch step -- and not at kernel
         // entry: a value held across the rollout loop costs the time-sliced peg build 32 B of scratch per lane and the 64-lane door build two AGPRs
         const uint64_t ev = cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t;
-        const earl::U4 b = earl::philox4x32_10(earl::U4{0xFFFEu, (uint32_t)(cfg.env_offset + env), (uint32_t)ev, (uint32_t)(ev >> 32)},
+        // ONE draw, by direction: the lifelong switch's (index 0xFFFE, cfg.goal_table) or -- POLICY, entering the reset phase -- the backward table's (index 0xFFFD, free:
+        // the reset draws with 0 .. 31, 0xFFF0 .. 0xFFF2 and 0xFFFF, the head with 0x504F4C00); the same counter words, u01 and clamp
+        const uint32_t draw = (POLICY && fixed) ? 0xFFFDu : 0xFFFEu;
+        const int rows = (POLICY && fixed) ? fixed_rows : cfg.n_goal_rows;
+        const double* const table = (POLICY && fixed) ? fixed : cfg.goal_table;
+        const earl::U4 b = earl::philox4x32_10(earl::U4{draw, (uint32_t)(cfg.env_offset + env), (uint32_t)ev, (uint32_t)(ev >> 32)},
                                                (uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32));
-        int grow = (int)(earl::u01(b.x, b.y) * (double)cfg.n_goal_rows);
-        grow = grow < cfg.n_goal_rows ? grow : cfg.n_goal_rows - 1;
-        const double gv = (POLICY && fixed) ? fixed[sub - 7] : cfg.goal_table[(size_t)grow * 7 + (sub - 7)];
+        int grow = (int)(earl::u01(b.x, b.y) * (double)rows);
+        grow = grow < rows ? grow : rows - 1;
+        const double gv = table[(size_t)grow * 7 + (sub - 7)];
+        if constexpr (POLICY) {
+          if (fixed && sub == 7) {
+            if (row_of) row_of[env] = grow;
+            if (row_at) row_at[row] = grow;
+          }
+        }
         if (NV < 15 && a.out.info && sub >= 11) {
           // the door's info dict is worked out after the launch from the emitted rows (earl_sawyer_door_info), whose goal block is about to change: this
           // row's info slots 0-2 carry the target the row's reward was computed with, slot 7 marks it (evaluate_state runs before reset_goal:

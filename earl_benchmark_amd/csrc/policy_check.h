@@ -1,5 +1,5 @@
 // policy_check.h -- the host-side contract of a closed-loop launch's policy arguments (earl_mlp_policy, earl_gaussian_head, earl_policy_population, earl_agent_pair),
-// stated once for every entry point that takes them: the tabletop's four (tabletop_policy.h, both libraries), the Sawyer door / peg's three (physics.hip), the
+// stated once for every entry point that takes them: the tabletop's four (tabletop_policy.h, both libraries), the Sawyer door / peg's four (physics.hip), the
 // minitaur's (physics_mt.hip) and earl_mlp_policy_forward_cpu (tabletop_host.cpp).  Host only; it needs the ABI structs and kPolicyMaxWidth and nothing of any env.
 // What differs between the callers is an argument: the widths, the rules below, the population's group size, the stride multiple.  Every check returns EARL_OK or
 // EARL_ERR_ARG; `err` is NULL (the physics entry points return the bare code) or kErrLen bytes that receive the message (the tabletop's thread-local g_err).
@@ -99,6 +99,25 @@ inline int check_pair(const earl_mlp_policy& p, const earl_agent_pair* pair, int
   if (pair->param_stride % stride_multiple) return refuse(err, "pair param_stride = %lld: a multiple of %d", (long long)pair->param_stride, stride_multiple);
   if (goal_change_frequency > 0)
     return refuse(err, "pair: goal_change_frequency = %d > 0 (the pair is the lifelong mechanism: the two clocks would fight over the same draw)", goal_change_frequency);
+  return EARL_OK;
+}
+
+// a population of PAIRS (earl_sawyer_agents_rollout): params is [P, 2, pair->param_stride], so a member's two rows fit between two members' starts
+inline int check_pair_population(const earl_policy_population& pop, const earl_agent_pair& pair, char* err) {
+  if (pop.param_stride < 2 * pair.param_stride)
+    return refuse(err, "population param_stride = %lld < 2 x pair param_stride = %lld (a member is a forward and a reset row)", (long long)pop.param_stride,
+                  (long long)(2 * pair.param_stride));
+  return EARL_OK;
+}
+
+// the reset agent's table of backward goals next to a checked pair; n_goal_rows: the env's forward goal table (0: the forward goal could not be restored).
+// A template: the struct is include/earl_physics.h's, which only the stepper units see
+template <class Goals>
+inline int check_backward_goals(const Goals& goals, const earl_agent_pair& pair, int32_t n_goal_rows, char* err) {
+  if (!goals.table) return refuse(err, "backward goals: table is NULL");
+  if (goals.n_rows < 1) return refuse(err, "backward goals: n_rows = %d < 1", goals.n_rows);
+  if (pair.backward_goal) return refuse(err, "backward goals: a table AND pair backward_goal (one of them)");
+  if (n_goal_rows == 0) return refuse(err, "backward goals: the env has no goal table (the forward goal could not be restored)");
   return EARL_OK;
 }
 

@@ -110,6 +110,7 @@ class SawyerDoor:
     self.fail_count = torch.zeros(n, dtype=torch.int32, **kw)                 # env steps rolled back by the failure guard (include/earl_physics.h)
     self.agent_phase = self.steps_in_phase = None      # the agent pair's per-env state (rollout_agents allocates it: 0 forward / 1 reset, steps spent in the phase)
     self._pair_counts = None
+    self.backward_row = None          # [N] int32 once a pair launch has drawn from a table of backward goals: the row each env's reset goal came from, -1 = none yet
     self._last_obs_stale = False      # last_obs no longer describes (state, goal): set by set_state() / reset_goal(), cleared by whatever rewrites every row
     self.total_step_count = 0
 
@@ -221,7 +222,8 @@ class SawyerDoor:
     """the launches of T env steps into `out` (the door's info launch included); clock: the device words of earl_sawyer_rollout_clocked (None: earl_sawyer_rollout);
     policy: None, or (policy or population, head struct or None, obs0) -- earl_sawyer_population_rollout computes the actions itself and leaves them in
     out['actions']; then `out` may lack any key, 'obs' included (the env's row of last_obs carries the observation), and summary is None or an _abi.EpisodeSummary;
-    or (AgentPair, head struct or None, obs0, _abi.AgentPair) -- earl_sawyer_pair_rollout"""
+    or (AgentPair or PairPopulation, head struct or None, obs0, _abi.AgentPair, _abi.PolicyPopulation or None, _abi.BackwardGoals or None) -- earl_sawyer_agents_rollout,
+    with the same `out` and summary rules"""
     info = out.get('info')
     in_kernel = info is not None and self.nv >= 15        # the peg's dict needs simulator state: the rollout kernel's epilogue writes it
     # door, lifelong goal switching: the kernel leaves the PRE-switch target on goal-switch rows (slots 0-2, marker in slot 7) for earl_sawyer_door_info
@@ -231,11 +233,12 @@ class SawyerDoor:
     with torch.cuda.device(self.device):
       if self.sched is not None and T > 1 and self._uses_queue(T):
         self.sched.zero_()                                 # (the queue of the time-sliced schedule: zero on entry)
-      if policy is not None and len(policy) == 4:
-        pi, head, obs0, ps = policy
-        _abi.check(self._lib.earl_sawyer_pair_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pi.struct), C.byref(ps),
-                                                      None if head is None else C.byref(head), obs0.data_ptr(), T, clock, _ptr(out.get('actions')), C.byref(o),
-                                                      self._stream()), 'earl_sawyer_pair_rollout')
+      if policy is not None and len(policy) == 6:
+        pi, head, obs0, ps, pop, goals = policy
+        ref = lambda x: None if x is None else C.byref(x)
+        _abi.check(self._lib.earl_sawyer_agents_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pi.struct), C.byref(ps),
+                                                        ref(pop), ref(goals), ref(head), obs0.data_ptr(), T, clock, _ptr(out.get('actions')), C.byref(o), ref(summary),
+                                                        self._stream()), 'earl_sawyer_agents_rollout')
       elif policy is not None:
         pi, head, obs0 = policy
         pop = getattr(pi, 'pop_struct', None)             # a PolicyPopulation: the env with global id g runs member g // envs_per_policy
@@ -276,11 +279,15 @@ class SawyerDoor:
       if self.agent_phase is not None:                     # (a reset env starts with the forward agent)
         self.agent_phase.zero_()
         self.steps_in_phase.zero_()
+      if self.backward_row is not None:
+        self.backward_row.fill_(-1)
     else:
       self.interventions += mask.to(torch.int32)
       if self.agent_phase is not None:
         self.agent_phase.masked_fill_(mask.bool(), 0)
         self.steps_in_phase.masked_fill_(mask.bool(), 0)
+      if self.backward_row is not None:
+        self.backward_row.masked_fill_(mask.bool(), -1)
       obs = torch.where(mask.bool()[:, None], obs, obs_prev)
     return obs[0].cpu().numpy() if self.scalar_api else obs
 
@@ -378,37 +385,89 @@ class SawyerDoor:
     -> rollout()'s dict plus 'actions' [T, N, 4] and, with return_noise=True, 'eps' [T, N, 4]"""
     return closed_loop.rollout_policy(self, policy, T, reset_first, sample, return_noise, out)
 
-  def rollout_agents(self, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """The forward / reset agent pair of autonomous RL alternating inside ONE launch of the rollout kernel (include/earl_physics.h: earl_sawyer_pair_rollout): `pair` -- an
-    `AgentPair` built with obs_dim=14, act_dim=4 -- drives every env by the agent of its phase (`env.agent_phase`: 0 forward, 1 reset; `env.steps_in_phase`) and hands it
-    over after pair.switch_every[phase] steps or, with pair.switch_on_success, after a step whose success flag is set.  Entering the reset phase the env's goal becomes
-    pair.backward_goal ('initial': env.initial_states[0] on the door, its only row; the peg has fifteen and wants the row itself; None: the goal stays); entering the forward
-    phase it becomes the goal-table row the lifelong switch would draw at that step.  `goal_t` IS the goal in force and stays as the launch leaves it.
-    -> rollout_policy()'s dict plus 'agent' [T, N] int8 (the agent that computed the action); the door's dict has no 'info' (the peg's is written in the kernel and stays).
-    Bookkeeping, the first observation, sample / return_noise and reset_first as rollout_policy.  `env.pair_counts`: the phases of this launch that ended by success."""
+  def _check_agents(self, pair, who):
+    """-> is it Gaussian; `pair`: an AgentPair or a PairPopulation of this env's widths on this env's device, and no LifelongWrapper"""
     from ..policy import require_widths
-    gaussian = require_widths(pair, 'rollout_agents', self.OBS_DIM, 4, env=self, pair=True)
+    gaussian = require_widths(pair, who, self.OBS_DIM, 4, env=self, pair=True, pairs=True)
     if self._cfg.goal_change_frequency > 0:
-      raise ValueError('rollout_agents: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
+      raise ValueError(f'{who}: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
                        'not under a LifelongWrapper, whose clock would fight the pair\'s over the same draw')
-    goal = pair.goal_row(self)                              # ('initial' on the peg: a ValueError naming env.initial_states)
+    return gaussian
+
+  def _agent_structs(self, pair, goal, table, out):
+    """the pair's per-env state (allocated at its first use) and what _issue_rollout takes after (pair, head, obs0) -> (_abi.AgentPair, population struct or None,
+    _abi.BackwardGoals or None), (forward_success, backward_success)"""
+    n, kw = self.num_envs, dict(device=self.device)
+    if self.agent_phase is None:
+      self.agent_phase = torch.zeros(n, dtype=torch.int8, **kw)
+      self.steps_in_phase = torch.zeros(n, dtype=torch.int32, **kw)
+    if table is not None and self.backward_row is None:
+      self.backward_row = torch.full((n,), -1, dtype=torch.int32, **kw)
+    fwd, bwd = torch.empty(n, dtype=torch.int32, **kw), torch.empty(n, dtype=torch.int32, **kw)
+    ps = _abi.AgentPair(switch_every=(C.c_int32 * 2)(*pair.switch_every), switch_on_success=int(pair.switch_on_success), pad_=0, param_stride=pair.pair_stride,
+                        backward_goal=_ptr(goal), phase=self.agent_phase.data_ptr(), steps_in_phase=self.steps_in_phase.data_ptr(),
+                        agent_out=_ptr(out.get('agent')), forward_success=fwd.data_ptr(), backward_success=bwd.data_ptr())
+    goals = None if table is None else _abi.BackwardGoals(table=table.data_ptr(), n_rows=int(table.shape[0]), pad_=0, row=self.backward_row.data_ptr(),
+                                                          row_out=_ptr(out.get('backward_row')))
+    return (ps, getattr(pair, 'pop_struct', None), goals), (fwd, bwd)
+
+  def rollout_agents(self, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
+    """The forward / reset agent pair of autonomous RL alternating inside ONE launch of the rollout kernel (include/earl_physics.h: earl_sawyer_agents_rollout): `pair` -- an
+    `AgentPair` built with obs_dim=14, act_dim=4, or a `PairPopulation` of them (the env with global id g runs pair g // envs_per_policy) -- drives every env by the agent
+    of its phase (`env.agent_phase`: 0 forward, 1 reset; `env.steps_in_phase`) and hands it over after pair.switch_every[phase] steps or, with pair.switch_on_success,
+    after a step whose success flag is set.  Entering the reset phase the env's goal becomes pair.backward_goal ('initial': env.initial_states[0] on the door, its only
+    row; the peg has fifteen and wants the row itself, or the whole table; None: the goal stays) or, with a table of backward goals (an array [R, 7], or
+    'initial_states' on the peg), a row of it drawn from the env's counter-based RNG (seed, global id, step: draw index 0xFFFD); entering the forward phase it becomes the
+    goal-table row the lifelong switch would draw at that step.  `goal_t` IS the goal in force and stays as the launch leaves it.
+    -> rollout_policy()'s dict plus 'agent' [T, N] int8 (the agent that computed the action) and, with a table, 'backward_row' [T, N] int32 (the row drawn at that step,
+    -1 elsewhere; `env.backward_row` [N]: the row each env's reset goal came from, -1 before its first entry and after its reset); the door's dict has no 'info' (the
+    peg's is written in the kernel and stays).
+    Bookkeeping, the first observation, sample / return_noise and reset_first as rollout_policy.  `env.pair_counts`: the phases of this launch that ended by success."""
+    gaussian = self._check_agents(pair, 'rollout_agents')
+    table = pair.goal_table(self)
+    goal = None if table is not None else pair.goal_row(self)      # ('initial' on the peg: a ValueError naming env.initial_states)
     n, kw = self.num_envs, dict(device=self.device)
     T, out, head, obs0 = closed_loop.prepare(self, 'rollout_agents', pair, gaussian, T, reset_first, sample, return_noise, out,
                                              what='Gaussian agents (MLPPolicy agents are deterministic)',
                                              new_out=lambda lead: self._new_out(lead, info=self.nv >= 15 and self.info_mode == 'full'))
-    if self.agent_phase is None:
-      self.agent_phase = torch.zeros(n, dtype=torch.int8, **kw)
-      self.steps_in_phase = torch.zeros(n, dtype=torch.int32, **kw)
     if 'agent' not in out:
       out['agent'] = torch.empty(T, n, dtype=torch.int8, **kw)
-    fwd, bwd = torch.empty(n, dtype=torch.int32, **kw), torch.empty(n, dtype=torch.int32, **kw)
-    ps = _abi.AgentPair(switch_every=(C.c_int32 * 2)(*pair.switch_every), switch_on_success=int(pair.switch_on_success), pad_=0, param_stride=pair.stride,
-                        backward_goal=_ptr(goal), phase=self.agent_phase.data_ptr(), steps_in_phase=self.steps_in_phase.data_ptr(),
-                        agent_out=out['agent'].data_ptr(), forward_success=fwd.data_ptr(), backward_success=bwd.data_ptr())
+    if table is not None and 'backward_row' not in out:
+      out['backward_row'] = torch.empty(T, n, dtype=torch.int32, **kw)
+    structs, counts = self._agent_structs(pair, goal, table, out)
     launch_out = out if self.nv >= 15 else {k: v for k, v in out.items() if k != 'info'}      # (the door's info dict of a pair launch is not offered)
-    self._launch_rollout(None, T, launch_out, policy=(pair, head, obs0, ps))
-    self._pair_counts = (fwd, bwd)
+    self._launch_rollout(None, T, launch_out, policy=(pair, head, obs0) + structs)
+    self._pair_counts = counts
     return out
+
+  def evaluate_agents(self, pair, T, sample=True):
+    """T steps of `pair` -- an `AgentPair` or a `PairPopulation` -- continuing from the current state, as rollout_agents runs them, in ONE launch that writes only per-env
+    summaries (include/earl_physics.h: earl_sawyer_agents_rollout with `actions` and every [T] pointer NULL; the env's row of last_obs carries the observation): no tensor
+    with a T axis is allocated.
+    -> {'ret': [N] float64 (the float32 step rewards summed in float64, t ascending; each against the goal in force during its step), 'success': [N] bool success at the
+        last step, 'first_success': [N] int32 first successful step or -1, 'guard_steps': [N] int32 steps the failure guard rolled back, 'forward_success' /
+        'backward_success': [N] int32 phases that ended by success (`env.pair_counts`)}: each equals its definition applied to what rollout_agents would have returned.
+    State and bookkeeping end as after rollout_agents.  sample=False: Gaussian agents at their mean."""
+    gaussian = self._check_agents(pair, 'evaluate_agents')
+    if not gaussian and not sample:
+      raise ValueError('evaluate_agents: sample=False needs Gaussian agents (MLPPolicy agents are deterministic)')
+    T, n, kw = int(T), self.num_envs, dict(device=self.device)
+    if T < 1:
+      raise ValueError(f'evaluate_agents: T = {T} < 1')
+    table = pair.goal_table(self)
+    goal = None if table is not None else pair.goal_row(self)
+    ret, succ = torch.empty(n, dtype=torch.float64, **kw), torch.empty(n, dtype=torch.bool, **kw)
+    first = torch.empty(n, dtype=torch.int32, **kw)
+    before = self.fail_count.clone()
+    obs0 = (self._get_obs_t() if self._last_obs_stale else self.last_obs).contiguous()
+    head = pair.head(sample=bool(sample), eps_out=None) if gaussian else None
+    summary = _abi.EpisodeSummary(ret=ret.data_ptr(), success_last=succ.data_ptr(), first_success=first.data_ptr())
+    structs, counts = self._agent_structs(pair, goal, table, {})
+    self._cfg.step_counter = self.total_step_count
+    self._issue_rollout(None, T, {}, policy=(pair, head, obs0) + structs, summary=summary)
+    closed_loop.finish(self, T, ret, succ)
+    self._pair_counts = counts
+    return {'ret': ret, 'success': succ, 'first_success': first, 'guard_steps': self.fail_count - before, 'forward_success': counts[0], 'backward_success': counts[1]}
 
   @property
   def pair_counts(self):
@@ -510,7 +569,8 @@ class SawyerDoor:
                                                       'counter': int(self._cfg.counter), 'total_step_count': self.total_step_count,
                                                       'last_obs_stale': bool(self._last_obs_stale)} | (
                                                           {} if self.agent_phase is None else {'agent_phase': self.agent_phase.clone(),
-                                                                                               'steps_in_phase': self.steps_in_phase.clone()})
+                                                                                               'steps_in_phase': self.steps_in_phase.clone()}) | (
+                                                              {} if self.backward_row is None else {'backward_row': self.backward_row.clone()})
 
   def load_state_dict(self, sd):
     for k in ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'steps_since_reset', 'interventions', 'steps_since_goal_change',
@@ -520,6 +580,8 @@ class SawyerDoor:
     if 'agent_phase' in sd:                                # (the agent pair's state: in the dict once a pair launch has allocated it, and only then)
       self.agent_phase = sd['agent_phase'].to(self.device, torch.int8).clone()
       self.steps_in_phase = sd['steps_in_phase'].to(self.device, torch.int32).clone()
+    if 'backward_row' in sd:                               # (likewise: once a launch has drawn from a table of backward goals)
+      self.backward_row = sd['backward_row'].to(self.device, torch.int32).clone()
     self._cfg.counter = int(sd['counter'])
     self.total_step_count = int(sd['total_step_count'])
     self._last_obs_stale = bool(sd.get('last_obs_stale', 'last_obs' not in sd))      # (a dict without the row leaves the env's own, which belongs to another state)

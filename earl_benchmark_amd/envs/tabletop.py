@@ -389,7 +389,9 @@ class TabletopManipulation:
     -> (obs [T,N,D], reward [T,N], done, success, actions [T,N,3], agent [T,N] int8 = the agent that computed the action) -- with a leading E axis when
     reset_first=True; return_noise=True (Gaussian agents) appends eps.  `env.pair_counts` = (forward phases, reset phases) [E, N] that ended by success in
     this launch.  The reset agent sees pair.backward_goal in its observation's goal slots; `goal_idx` keeps the env's task goal throughout."""
-    from ..policy import require_widths
+    from ..policy import PairPopulation, require_widths
+    if not isinstance(pair, PairPopulation) and (getattr(pair, 'backward_goals', None) is not None or (isinstance(getattr(pair, 'backward_goal', None), str) and pair.backward_goal == 'initial_states')):
+      raise ValueError('rollout_agents: a table of backward goals runs on the Sawyer door and peg only (earl_sawyer_agents_rollout); the tabletop pair takes ONE row')
     gaussian = require_widths(pair, 'rollout_agents', 12, 3, env=self, pair=True)
     if self.NOBJ != 1:
       raise NotImplementedError('rollout_agents: single-object env only')

@@ -50,7 +50,15 @@ after a fixed number of steps or as soon as the acting agent has succeeded, insi
 
   pair = AgentPair(forward_pi, backward_pi, switch_every=(200, 200), switch_on_success=True, backward_goal='initial', device='cuda')
   obs, reward, done, success, actions, agent = env.rollout_agents(pair, T=1000)                       # the training stream: continuing, agent [T, N] int8 = who acted
-  env.agent_phase, env.steps_in_phase, env.pair_counts                                                # the state the next launch continues from; successes of the last one"""
+  env.agent_phase, env.steps_in_phase, env.pair_counts                                                # the state the next launch continues from; successes of the last one
+
+The Sawyer door and peg take pairs of 14 / 4 agents in the general form (include/earl_physics.h: earl_sawyer_agents_rollout): a TABLE of backward goals the reset
+agent's goal is drawn from at every handover, a `PairPopulation` of P pairs in one launch, and summaries instead of [T] arrays.
+
+  pair = AgentPair(f, b, switch_every=(200, 200), backward_goal='initial_states', obs_dim=14, act_dim=4)       # or backward_goal=rows [R, 7]
+  out = peg.rollout_agents(pair, T=1000)                                                              # ... plus 'backward_row' [T, N] int32: the row drawn, -1 elsewhere
+  pairs = PairPopulation([pair_0, ..., pair_511], envs_per_policy=16, device='cuda')                  # .params [P, 2, stride], written in place
+  s = peg.evaluate_agents(pairs, T=1000)                                                              # {'ret', 'success', 'first_success', 'guard_steps', 'forward_success', 'backward_success'}: [N]"""
 import numpy as np
 import torch
 
@@ -189,26 +197,29 @@ class GaussianMLPPolicy(MLPPolicy):
     return torch.tanh(u) if self.squash else u
 
 
-def require_widths(policy, who, obs_dim, act_dim, env=None, pair=False, bounded=None):
+def require_widths(policy, who, obs_dim, act_dim, env=None, pair=False, bounded=None, pairs=False):
   """The one check of a policy against the widths it is to have -> is it Gaussian.  env=None: a container of declared widths (the tabletop's 12 -> .. -> 3 unless
   said otherwise) takes networks of those widths only.  env given (its `device`, `num_envs`, `_cfg.env_offset`): a launch of `who` on that env -- the type (an
-  MLPPolicy, a GaussianMLPPolicy or a PolicyPopulation of them; pair=True: an AgentPair), the env's widths, the env's device, and a population's members against the
-  env's global ids.  bounded: None, or the bound outside which the env's reference raises on an action (the minitaur): an unbounded output is refused."""
-  if env is not None and not isinstance(policy, AgentPair if pair else (MLPPolicy, PolicyPopulation)):
-    raise ValueError(f'{who}: ' + ('pair is an AgentPair' if pair else 'an MLPPolicy, a GaussianMLPPolicy or a PolicyPopulation of them (an AgentPair goes to rollout_agents)'))
+  MLPPolicy, a GaussianMLPPolicy or a PolicyPopulation of them; pair=True: an AgentPair, with pairs=True also a PairPopulation), the env's widths, the env's device,
+  and a population's members against the env's global ids.  bounded: None, or the bound outside which the env's reference raises on an action (the minitaur): an unbounded output is refused."""
+  if env is not None and pair and isinstance(policy, PairPopulation) and not pairs:
+    raise ValueError(f'{who}: a PairPopulation runs on the Sawyer door and peg only (earl_sawyer_agents_rollout); this env takes ONE AgentPair')
+  if env is not None and not isinstance(policy, (AgentPair, PairPopulation) if pair else (MLPPolicy, PolicyPopulation)):
+    raise ValueError(f'{who}: ' + (('pair is an AgentPair' + (' or a PairPopulation' if pairs else '')) if pair else
+                                   'an MLPPolicy, a GaussianMLPPolicy or a PolicyPopulation of them (an AgentPair goes to rollout_agents)'))
   what, ctor = ('an AgentPair', 'AgentPair') if pair else ('a policy', 'MLPPolicy')
   od, ad = getattr(policy, 'obs_dim', OBS_DIM), getattr(policy, 'act_dim', ACT_DIM)
   if (od, ad) != (obs_dim, act_dim):
     takes = (f'the tabletop takes {OBS_DIM} and {ACT_DIM}' if (obs_dim, act_dim) == (OBS_DIM, ACT_DIM) else
              f'{obs_dim} and {act_dim} were declared' if env is None else f'this env takes {obs_dim} and {act_dim} ({ctor}(..., obs_dim={obs_dim}, act_dim={act_dim}))')
     raise ValueError(f'{who}: {what} of observation width {od} and action width {ad}; {takes}')
-  gaussian = policy.gaussian if isinstance(policy, (PolicyPopulation, AgentPair)) else isinstance(policy, GaussianMLPPolicy)
+  gaussian = policy.gaussian if isinstance(policy, (PolicyPopulation, AgentPair, PairPopulation)) else isinstance(policy, GaussianMLPPolicy)
   if env is None:
     return gaussian
   if policy.device != env.device:
     noun = 'pair' if pair else 'policy'
     raise ValueError(f'{who}: the {noun} is on {policy.device}, the env on {env.device} ({noun}.to(device))')
-  if isinstance(policy, PolicyPopulation):
+  if isinstance(policy, (PolicyPopulation, PairPopulation)):
     lo, hi = int(env._cfg.env_offset), int(env._cfg.env_offset) + env.num_envs - 1
     if lo < 0 or hi // policy.envs_per_policy >= policy.n_policies:
       raise ValueError(f'{who}: global env ids {lo} .. {hi} need members up to {hi // policy.envs_per_policy} of {policy.n_policies}')
@@ -347,7 +358,9 @@ class AgentPair:
   A second hidden layer may be at most 128 wide (EARL_PAIR_MAX_H2: two weight sets share one wave's registers); one hidden layer may have every width.
   obs_dim / act_dim: the agents' widths -- the tabletop's 12 / 3 by default; 14 / 4 for the Sawyer door and peg (earl_sawyer_pair_rollout), where the backward goal is
   a row of 7 values in the Sawyer goal format, the rows are padded to a stride of whole 16-byte pieces as PolicyPopulation's, and no width limit applies (the weights
-  are read from memory at every step)."""
+  are read from memory at every step).  There backward_goal may also be a TABLE [R, 7], R >= 2 (kept as `.backward_goals`; `.backward_goal` is then None), or
+  'initial_states' (the env's `initial_states`, resolved at launch: the peg's fifteen rows, the door's one, which behaves as 'initial'): at every entry into the
+  reset phase the env's goal is a row of the table drawn from the env's counter-based RNG (earl_sawyer_agents_rollout; `env.backward_row`)."""
 
   def __init__(self, forward, backward, switch_every=200, switch_on_success=True, backward_goal='initial', device=None, obs_dim=OBS_DIM, act_dim=ACT_DIM):
     self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
@@ -370,8 +383,16 @@ class AgentPair:
     if len(se) != 2 or any(int(v) != v or int(v) < 1 for v in se):
       raise ValueError(f'AgentPair: switch_every = {switch_every!r}: one int >= 1, or (forward, reset)')
     self.switch_every, self.switch_on_success = (int(se[0]), int(se[1])), bool(switch_on_success)
-    if backward_goal is None or (isinstance(backward_goal, str) and backward_goal == 'initial'):
+    self.backward_goals = None                           # Sawyer widths: a TABLE of goal rows [R, 7], R >= 2 (the reset agent's goal is drawn from it at every handover)
+    table = None
+    if not tabletop and not isinstance(backward_goal, str) and backward_goal is not None:
+      table = backward_goal.detach().cpu().numpy() if torch.is_tensor(backward_goal) else np.asarray(backward_goal)
+      table = table if table.ndim == 2 and table.shape[0] >= 2 and table.shape[1] == self.goal_dim else None
+    if backward_goal is None or (isinstance(backward_goal, str) and (backward_goal == 'initial' or (backward_goal == 'initial_states' and not tabletop))):
       self.backward_goal = backward_goal
+    elif table is not None:
+      self.backward_goal = None
+      self.backward_goals = torch.as_tensor(np.ascontiguousarray(table, dtype=np.float64)).clone()
     else:
       g = torch.as_tensor(np.asarray(backward_goal, dtype=np.float64) if not torch.is_tensor(backward_goal) else backward_goal).detach().to('cpu', torch.float64).reshape(-1)
       if g.numel() != self.goal_dim:
@@ -390,6 +411,8 @@ class AgentPair:
   def stride(self):
     return int(self.params.shape[1])
 
+  pair_stride = stride                                               # (floats between the two agents' rows: PairPopulation's name for it)
+
   def to(self, device):
     dev = torch.device(device)
     if dev.type == 'cuda' and dev.index is None:
@@ -398,6 +421,8 @@ class AgentPair:
     self.params = self.params.to(dev).contiguous()
     self._goal_dev = None if not torch.is_tensor(self.backward_goal) else self.backward_goal.to(dev).contiguous()
     self._initial_dev = None                                         # ('initial' as numpy, its row on `dev`), filled by goal_row
+    self._goals_dev = None if self.backward_goals is None else self.backward_goals.to(dev).contiguous()
+    self._initial_states_dev = None                                  # ('initial_states' as numpy, its rows on `dev`), filled by goal_table
     dims = self.dims + [0] * (4 - len(self.dims))
     self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
                                  out_act=_abi.ACTIVATIONS[self.out_act], precision=0, params=self.params.data_ptr())
@@ -406,9 +431,23 @@ class AgentPair:
   def head(self, sample=True, eps_out=None):
     return self.template.head(sample=sample, eps_out=eps_out)
 
+  def goal_table(self, env):
+    """the reset agent's TABLE of goal rows as a float64 tensor [R, 7], R >= 2, on the pair's device, or None (then goal_row is the rule): a table given as
+    backward_goal, or 'initial_states' on an env whose `initial_states` has more than one row (the peg's fifteen; the door's single row behaves as 'initial')"""
+    if self._goals_dev is not None:
+      return self._goals_dev
+    if not (isinstance(self.backward_goal, str) and self.backward_goal == 'initial_states'):
+      return None
+    rows = np.asarray(env.initial_states, dtype=np.float64).reshape(-1, 7)
+    if len(rows) < 2:
+      return None
+    if self._initial_states_dev is None or not np.array_equal(self._initial_states_dev[0], rows):      # one upload per (pair, device, table), not one per launch
+      self._initial_states_dev = (rows.copy(), torch.as_tensor(rows, device=self.device).contiguous())
+    return self._initial_states_dev[1]
+
   def goal_row(self, env):
     """the reset agent's goal row as a float64 tensor [6] (Sawyer widths: [7]) on the pair's device, or None; 'initial' is `env.initial_state` (the Sawyer door: the one
-    row of `env.initial_states`; the peg has fifteen, so the caller picks one)"""
+    row of `env.initial_states`; the peg has fifteen, so the caller picks one -- or asks for 'initial_states', the whole table: goal_table)"""
     if self.backward_goal is None:
       return None
     if self._goal_dev is not None:
@@ -457,3 +496,107 @@ class AgentPair:
       x = x[:, :self.act_dim]                                        # (Gaussian agents: the mean)
       acts.append((torch.tanh(x) if self.out_act == 'tanh' else x).reshape(*obs.shape[:-1], self.act_dim))
     return torch.where(ph[..., None], acts[1], acts[0])
+
+
+class PairPopulation:
+  """P forward / reset pairs of ONE architecture, head, switch rule and backward goal behind struct earl_policy_population next to struct earl_agent_pair
+  (earl_sawyer_agents_rollout): `pairs` is a list of `AgentPair` built with obs_dim=14, act_dim=4 -- only the parameters differ.  The env with GLOBAL id g runs pair
+  g // envs_per_policy (a multiple of 16).  `.params` [P, 2, stride] float32 holds every pair's rows (0 forward, 1 reset) in MLPPolicy's packing order and is what the
+  kernel reads: write into it in place."""
+  SHARED = ('gaussian', 'dims', 'hidden_act', 'out_act', 'switch_every', 'switch_on_success')
+  SHARED_HEAD = ('squash', 'log_std_bounds', 'log_std_map')
+
+  def __init__(self, pairs, envs_per_policy=16, device=None):
+    G = int(envs_per_policy)
+    if G < 16 or G % 16:
+      raise ValueError(f'PairPopulation: envs_per_policy = {envs_per_policy}: a multiple of 16, >= 16')
+    members = list(pairs)
+    if not members or not all(isinstance(m, AgentPair) for m in members):
+      raise ValueError('PairPopulation: a non-empty list of AgentPair')
+    t = members[0]
+    self.obs_dim, self.act_dim = t.obs_dim, t.act_dim
+    for m in members:
+      require_widths(m, 'PairPopulation', 14, 4)
+    for p, m in enumerate(members):
+      for what in self.SHARED:
+        if getattr(m, what) != getattr(t, what):
+          raise ValueError(f'PairPopulation: member {p} has {what} = {getattr(m, what)!r}, member 0 has {getattr(t, what)!r} '
+                           '(the pairs of a population share one architecture, head, switch rule and backward goal)')
+      for what in self.SHARED_HEAD if t.gaussian else ():
+        if getattr(m.template, what) != getattr(t.template, what):
+          raise ValueError(f'PairPopulation: member {p} has {what} = {getattr(m.template, what)!r}, member 0 has {getattr(t.template, what)!r} '
+                           '(the pairs of a population share one architecture, head, switch rule and backward goal)')
+      if not self._same_goal(m, t):
+        shown = lambda a: a.backward_goals if a.backward_goals is not None else a.backward_goal
+        raise ValueError(f'PairPopulation: member {p} has backward_goal = {shown(m)!r}, member 0 has {shown(t)!r} '
+                         '(the pairs of a population share one architecture, head, switch rule and backward goal)')
+    self.envs_per_policy, self.n_policies = G, len(members)
+    self.gaussian, self.dims, self.hidden_act, self.out_act, self.macs, self.n_params = t.gaussian, list(t.dims), t.hidden_act, t.out_act, t.macs, t.n_params
+    self.switch_every, self.switch_on_success = t.switch_every, t.switch_on_success
+    self.backward_goal, self.backward_goals = t.backward_goal, t.backward_goals
+    self._head_of = t.template                                        # (a policy of the members' head: only its head settings are used)
+    self.params = torch.stack([m.params.detach().to('cpu', torch.float32) for m in members]).contiguous()      # [P, 2, stride]
+    self.to(t.device if device is None else device)
+
+  @staticmethod
+  def _same_goal(a, b):
+    ga, gb = (a.backward_goals, a.backward_goal), (b.backward_goals, b.backward_goal)
+    for x, y in zip(ga, gb):
+      if torch.is_tensor(x) or torch.is_tensor(y):
+        if not (torch.is_tensor(x) and torch.is_tensor(y) and x.shape == y.shape and bool((x == y).all())):
+          return False
+      elif x != y:
+        return False
+    return True
+
+  @property
+  def pair_stride(self):
+    """floats between the two agents' rows of one pair"""
+    return int(self.params.shape[2])
+
+  @property
+  def stride(self):
+    """floats between two pairs"""
+    return 2 * self.pair_stride
+
+  def to(self, device):
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+      dev = torch.device('cuda', torch.cuda.current_device())
+    self.device = dev
+    self.params = self.params.to(dev).contiguous()
+    dims = self.dims + [0] * (4 - len(self.dims))
+    self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
+                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=0, params=self.params.data_ptr())
+    self.pop_struct = _abi.PolicyPopulation(n_policies=self.n_policies, envs_per_policy=self.envs_per_policy, param_stride=self.stride)
+    self._goals = self.pair(0)                                         # resolves and caches the backward goal on `dev` (goal_row / goal_table)
+    return self
+
+  def head(self, sample=True, eps_out=None):
+    return self._head_of.head(sample=sample, eps_out=eps_out)
+
+  def goal_row(self, env):
+    return self._goals.goal_row(env)
+
+  def goal_table(self, env):
+    return self._goals.goal_table(env)
+
+  def pair(self, p):
+    """pair p as an AgentPair of its own (a copy of its rows of .params)"""
+    rows = self.params[int(p)].detach().cpu()
+    t = self._head_of
+    agents = []
+    for row in rows:
+      layers, at = [], 0
+      for k, n in zip(self.dims[:-1], self.dims[1:]):
+        layers.append((row[at:at + n * k].reshape(n, k).clone(), row[at + n * k:at + n * k + n].clone()))
+        at += n * k + n
+      agents.append(GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, obs_dim=14, act_dim=4)
+                    if self.gaussian else MLPPolicy(layers, t.hidden_act, t.out_act, obs_dim=14, act_dim=4))
+    goal = self.backward_goals if self.backward_goals is not None else self.backward_goal
+    return AgentPair(agents[0], agents[1], switch_every=self.switch_every, switch_on_success=self.switch_on_success, backward_goal=goal, device=self.device,
+                     obs_dim=14, act_dim=4)
+
+  def policy_index(self, global_ids):
+    """the pair each GLOBAL env id runs"""
+    return torch.div(torch.as_tensor(global_ids), self.envs_per_policy, rounding_mode='floor')

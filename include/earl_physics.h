@@ -355,6 +355,32 @@ int earl_sawyer_population_rollout(const earl_link_model* model, const earl_coll
 int earl_sawyer_pair_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                              const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_gaussian_head* head, const double* obs0, int32_t T,
                              const uint64_t* clock, float* actions, const earl_sawyer_out* out, earl_stream_t stream);
+/* ---- the agent pair in its general form: a TABLE of backward goals, a POPULATION of pairs, episode SUMMARIES -- each NULL or given, in any combination ----
+ * earl_sawyer_pair_rollout is this call with pop = goals = summary = NULL, bit for bit; its six items are the contract, with these additions.
+ *   goals    Entering the reset phase, the env's row of st->goal becomes table[r], r = min((int)(u01(b.x, b.y) * n_rows), n_rows - 1), where b is the Philox4x32-10 block
+ *            {0xFFFD, global env id, ev lo, ev hi} under key cfg->seed, ev = cfg->step_counter + clock[1] + t: the counter words, u01 and clamp of the forward entry's
+ *            0xFFFE draw.  Draw index 0xFFFD is free: the reset uses 0 .. 31, 0xFFF0 .. 0xFFF2 and 0xFFFF, the goal switch 0xFFFE, the head 0x504F4C00.  The
+ *            observation patch, the door's info marker and the agent-scope fence are item 5's.  goals->row[env] = r and row_out[t n + env] = r at such a step; row_out is
+ *            -1 at every other step of a live env.  The draw depends on seed, global id and step only: not on n, the shard, or how the steps are cut into launches.
+ *            A table of ONE row equals earl_sawyer_pair_rollout with pair->backward_goal = that row.
+ *   pop      policy->params is [P, 2, pair->param_stride]: the env with GLOBAL id g runs the pair of member g / G at policy->params + (g / G) * pop->param_stride, row 0
+ *            the forward agent, row 1 the reset agent.  Bit-identical to cutting the batch at the multiples of G and running earl_sawyer_pair_rollout on each piece.
+ *   summary  as in earl_sawyer_population_rollout, rows [n]: each word is its definition applied to what out->reward / out->success hold or would hold -- reward and
+ *            success against the goal in force DURING the step.  actions and every pointer of `out` may be NULL, as for a pair.
+ * EARL_ERR_ARG before any HIP call: everything earl_sawyer_pair_rollout refuses; with pop, earl_sawyer_population_rollout's population rules and pop->param_stride <
+ * 2 * pair->param_stride; goals with a NULL table or n_rows < 1, goals together with pair->backward_goal != NULL, goals with cfg->n_goal_rows == 0 (the forward goal
+ * could not be restored). */
+typedef struct earl_backward_goals {
+  const double* table;   /* device, [n_rows, 7], Sawyer goal format (a row of st->goal) */
+  int32_t  n_rows;       /* >= 1 */
+  int32_t  pad_;
+  int32_t* row;          /* NULL or [n], caller-owned: the table row the env's reset goal came from; written at every entry into the reset phase, never read */
+  int32_t* row_out;      /* NULL or [T, n]: the row drawn at env step t, -1 at a step without a draw */
+} earl_backward_goals;
+int earl_sawyer_agents_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop, const earl_backward_goals* goals,
+                               const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_sawyer_out* out,
+                               const earl_episode_summary* summary, earl_stream_t stream);
 /* The policy contract on the host (libearl_host.so; host pointers): actions [n, A] of n observation rows obs [n, dims[0]], dims[0] in 1..256, hidden widths in 1..256,
  * the last layer A wide (head = NULL) or 2 A wide (rows 0..A-1 the mean, A..2A-1 the raw log_std), A >= 1.  eps [n, A] = the standard-normal draws to use with a
  * head in EARL_HEAD_SAMPLE mode; NULL (or EARL_HEAD_MEAN, or no head) evaluates the mean / the deterministic policy.  policy->out_act is applied last, as on the

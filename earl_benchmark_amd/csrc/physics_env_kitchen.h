@@ -91,7 +91,12 @@ struct KitchenPolicyArgs : KitchenRolloutArgs {
   earl_gaussian_head head;       // read when gauss != 0
   int gauss;
   const double* obs0;            // [n, 46]: what the policy sees at step 0
-  float* act_out;                // [T, n, 9]: the actions as the policy produced them (earl_kitchen_rollout_clocked fed with it walks through the same bits)
+  float* act_out;                // [T, n, 9] or NULL: the actions as the policy produced them (earl_kitchen_rollout_clocked fed with it walks through the same bits)
+  int pop_G;                     // earl_kitchen_population_rollout: envs per member of a population (0: one policy); the env with global id g reads its parameters at pol.params + (g / pop_G) pop_stride
+  int64_t pop_stride;            // floats between consecutive members (a multiple of 4: every member's rows after the input layer are read in 16-byte pieces)
+  double* sum_ret;               // earl_episode_summary of the launch, each NULL or [n]: lane 0 of the env's owner wave keeps its three words up to date in HBM after every env step
+  uint8_t* sum_last;             // (step 0 initialises them)
+  int32_t* sum_first;
 };
 static_assert(std::is_standard_layout<KitchenRolloutArgs>::value && std::is_trivially_copyable<KitchenPolicyArgs>::value, "the policy phase reads KitchenPolicyArgs as laid out in the kernel-argument segment");
 #include "policy_lane_group.h"
@@ -102,6 +107,9 @@ static_assert(std::is_standard_layout<KitchenRolloutArgs>::value && std::is_triv
 // `seen`: the env's row of 46 doubles the policy sees (NULL at step 0: the env's row of obs0); `row` = t n + env.  A group that is not live (an idle group of the last
 // wave / workgroup, a solo launch's shadow) computes on zeros and stores nothing: the row of the env an idle group shadows is written by another wave, and a read of it
 // would race with that wave; the shadow of a solo launch takes the live group's action from its own wave afterwards (kit_step_action).
+// A population: `gid` picks the member, gid / pop_G.  A group that is not live comes with the id of the env it shadows (the kernel clamps `env` to n - 1, a solo shadow has
+// its wave-mate's), so the rows it reads are those of a member that exists: no id at or beyond env_offset + n is ever formed.  (The helper waves of the several-wave forms
+// never get here.)
 // The policy's kernel arguments are read HERE, through the kernel-argument pointer the caller passed through an empty asm: read as `a.pol...` they would be loaded once at
 // kernel entry and held in scalar registers across every timestep (see sawyer_policy_action).  Nothing of the policy lives across a timestep.
 __device__ __noinline__ float kitchen_policy_action(const uint64_t ka_bits, const uint64_t ev, const uint32_t gid, const uint64_t seed, const double* __restrict__ seen, const int env,
@@ -119,6 +127,8 @@ __device__ __noinline__ float kitchen_policy_action(const uint64_t ka_bits, cons
 #pragma unroll
   for (int i = 2; i < 8; ++i) h[i] = 0.f;
   const float* w = ka->pol.params;
+  const int pop_G = ka->pop_G;
+  if (pop_G > 0) w += (size_t)(gid / (uint32_t)pop_G) * (size_t)ka->pop_stride;
   pol_layer<32, false>(w, w + (size_t)d1 * 46, 46, d1, hidden_act, sub, h);
   w += (size_t)d1 * (46 + 1);
   if (n_layers == 3) {
@@ -145,7 +155,7 @@ __device__ __noinline__ float kitchen_policy_action(const uint64_t ka_bits, cons
     u = earl::policy_act(h[0], out_act);
   }
   float* act_out = ka->act_out;
-  if (sub < 9 && live) act_out[row * 9 + sub] = u;
+  if (sub < 9 && live && act_out) act_out[row * 9 + sub] = u;
   return u;
 }
 // the action component `kk` of env step t as this lane's double, before the env step's own [-1, 1] clip, computed by the policy.  `A` is the policy kernel's argument
@@ -157,7 +167,8 @@ __device__ __forceinline__ double kit_policy_step(const A& a, const int t, const
   // what the policy sees: the row this env emitted last, exactly as it stands in out.obs (sensor noise included, a rolled-back step's repeated row), each double
   // rounded to float32; at step 0 the caller's obs0.  Lane `sub` reads the elements lane `sub` wrote (the observation loop and the rollback both store elements
   // sub and sub + 32 from lane `sub`), after the agent-scope fence that ends every env step.
-  const double* seen = t > 0 ? a.out.obs + (row - n) * 46 : nullptr;
+  // (out.obs == NULL, earl_kitchen_population_rollout: the env's row of st.last_obs, which holds the same bits: the observation loop writes both, the rollback leaves it)
+  const double* seen = t > 0 ? (a.out.obs ? a.out.obs + (row - n) * 46 : a.st.last_obs + (size_t)env * 46) : nullptr;
   const uint64_t ev = a.cfg.counter + (a.clock ? a.clock[0] : 0) + (uint64_t)t;      // the step's sensor-noise counter (read per step, like the noise's)
   // (offset 0 of the kernel-argument segment is the kernel's one argument, the KitchenPolicyArgs)
   const EARL_KARG void* ka = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();

@@ -85,6 +85,8 @@
     for (int ts = 0; ts < cfg.frame_skip; ++ts) substep<NV, LPE, true>(s, m, bt, a.col, sub, grp, mq, ctrl, ts > 0, nullptr, nullptr);
     const bool bad_lane = sub < NV && !(fabs(s.qp[sub]) < EARL_BAD_VALUE && fabs(s.qv[sub]) < EARL_BAD_VALUE);
     const bool failed = group_any<LPE>(bad_lane, grp);
+    [[maybe_unused]] double rew = 0.0;                // POLICY: what out.reward / out.success hold or would hold for this step, for the episode summary
+    [[maybe_unused]] uint8_t suc = 0;
     if (failed) {
       // rolled back to the last stable state (the rows in HBM); returns its last stable observation, reward 0 (kitchen_guard / finish kernels)
       load_state<NV>(s, m, a.st.qpos + (size_t)env * NV, a.st.qvel + (size_t)env * NV, sub);
@@ -92,6 +94,14 @@
         s.mocap[sub] = mocap_prev;
         if (live) a.st.mocap_pos[(size_t)env * 3 + sub] = mocap_prev;
       }
+      if constexpr (POLICY) {
+        // (POLICY only: the plain kernels keep their statements, and with them their machine code.  Without out.obs nothing is re-emitted: the env's row of st.last_obs
+        // stands; reward 0 and success 0 go out with the summary below)
+        if (live) {
+          if (a.out.obs) for (int k = sub; k < 46; k += LPE) a.out.obs[row * 46 + k] = a.st.last_obs[(size_t)env * 46 + k];
+          if (sub == 0 && a.st.fail_count) a.st.fail_count[env] += 1;
+        }
+      } else
       if (live) {
         for (int k = sub; k < 46; k += LPE) a.out.obs[row * 46 + k] = a.st.last_obs[(size_t)env * 46 + k];
         if (sub == 0) {
@@ -131,7 +141,8 @@
         }
         s.kit.obs[k] = v;
         if (live) {
-          a.out.obs[row * 46 + k] = v;
+          if constexpr (POLICY) { if (a.out.obs) a.out.obs[row * 46 + k] = v; }
+          else a.out.obs[row * 46 + k] = v;
           a.st.last_obs[(size_t)env * 46 + k] = v;
           if (k < 9) a.st.last_qp_robot[(size_t)env * 9 + k] = v;
         }
@@ -150,11 +161,39 @@
             r += -0.5 * kit_norm_diff(s.mocap, s.kit.sites[c], 3);
           }
         }
+        if constexpr (POLICY) { rew = r; suc = dist <= 0.3; }      // (stored after the branch, with the summary)
+        else {
         a.out.reward[row] = r;
         a.out.success[row] = dist <= 0.3;
+        }
       }
     }
     ++steps;
+    if constexpr (POLICY) {
+      // reward and success of the step (a rolled-back step: 0 and 0) to their rows, each NULL or given, and into the env's episode summary: each word is its definition
+      // applied to exactly these values.  Lane 0 of the env's OWNER wave (`live` excludes the helper waves, which left for their own loop above).  The summary pointers are
+      // read through the kernel-argument segment here, where they are used (see kitchen_policy_action on why)
+      if (sub == 0 && live) {
+        const double r_t = failed ? 0.0 : rew;
+        const uint8_t s_t = failed ? (uint8_t)0 : suc;
+        if (a.out.reward) a.out.reward[row] = r_t;
+        if (a.out.success) a.out.success[row] = s_t;
+        const EARL_KARG void* kap = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kap));
+        const EARL_KARG KitchenPolicyArgs* ka = (const EARL_KARG KitchenPolicyArgs*)kap;
+        double* const sum_ret = ka->sum_ret;
+        uint8_t* const sum_last = ka->sum_last;
+        int32_t* const sum_first = ka->sum_first;
+        if (sum_ret) sum_ret[env] = (t > 0 ? sum_ret[env] : 0.0) + r_t;      // sum over t ascending of reward_t
+        if (sum_last) sum_last[env] = s_t;                                   // (the one of step T - 1 stays)
+        if (sum_first) {
+          const int32_t f = t > 0 ? sum_first[env] : -1;
+          sum_first[env] = (f < 0 && s_t) ? t : f;
+        }
+        if (a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
+        if (a.out.done) a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
+      }
+    } else
     if (sub == 0 && live) {
       if (a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
       a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;

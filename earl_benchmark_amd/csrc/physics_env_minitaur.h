@@ -44,7 +44,12 @@ struct MinitaurPolicyArgs : MinitaurArgs {
   earl_gaussian_head head;       // read when gauss != 0
   int gauss;
   const double* obs0;            // [n, 32]: what the policy sees at step 0
-  float* act_out;                // [T, n, 8]: the actions as the policy produced them (earl_minitaur_rollout_clocked fed with it walks through the same bits)
+  float* act_out;                // [T, n, 8] or NULL: the actions as the policy produced them (earl_minitaur_rollout_clocked fed with it walks through the same bits)
+  int pop_G;                     // earl_minitaur_population_rollout: envs per member of a population (0: one policy); the env with global id g reads its parameters at pol.params + (g / pop_G) pop_stride
+  int64_t pop_stride;            // floats between consecutive members (a multiple of 4: every member's rows are read in 16-byte pieces)
+  double* sum_ret;               // earl_episode_summary of the launch, each NULL or [n]: lane 0 of the env keeps its three words up to date in HBM after every env step
+  uint8_t* sum_last;             // (step 0 initialises them)
+  int32_t* sum_first;
 };
 static_assert(std::is_standard_layout<MinitaurArgs>::value && std::is_trivially_copyable<MinitaurPolicyArgs>::value, "the policy phase reads MinitaurPolicyArgs as laid out in the kernel-argument segment");
 #include "policy_lane_group.h"
@@ -53,6 +58,8 @@ static_assert(std::is_standard_layout<MinitaurArgs>::value && std::is_trivially_
 // `seen`: the env's row of 32 doubles the policy sees (NULL at step 0: the env's row of obs0); `row` = t n + env.  A group that is not live (an idle group of the last
 // wave / workgroup, a solo launch's shadow) computes on zeros and stores nothing: the row of the env it shadows is written by other lanes -- of another wave in the packed
 // forms -- and a read of it would race with them; what such a group simulates is never stored.
+// A population: `gid` picks the member, gid / pop_G.  A group that is not live comes with the id of the env it shadows (the callers clamp `env` to n - 1, a solo shadow has
+// its wave-mate's), so the rows it reads are those of a member that exists: no id at or beyond env_offset + n is ever formed.
 // The policy's kernel arguments are read HERE, through the kernel-argument pointer the caller passed through an empty asm: read as `a.pol...` they would be loaded once at
 // kernel entry and held in scalar registers across every timestep (see sawyer_policy_action).  Nothing of the policy lives across a timestep.
 __device__ __noinline__ float minitaur_policy_action(const uint64_t ka_bits, const uint64_t ev, const uint32_t gid, const uint64_t seed, const double* __restrict__ seen, const int env,
@@ -68,6 +75,8 @@ __device__ __noinline__ float minitaur_policy_action(const uint64_t ka_bits, con
 #pragma unroll
   for (int i = 1; i < 8; ++i) h[i] = 0.f;
   const float* w = ka->pol.params;
+  const int pop_G = ka->pop_G;
+  if (pop_G > 0) w += (size_t)(gid / (uint32_t)pop_G) * (size_t)ka->pop_stride;
   pol_layer<32, true>(w, w + (size_t)d1 * 32, 32, d1, hidden_act, sub, h);
   w += (size_t)d1 * (32 + 1);
   if (n_layers == 3) {
@@ -93,7 +102,7 @@ __device__ __noinline__ float minitaur_policy_action(const uint64_t ka_bits, con
     u = earl::policy_act(h[0], out_act);
   }
   float* act_out = ka->act_out;
-  if (sub < 8 && live) act_out[row * 8 + sub] = u;
+  if (sub < 8 && live && act_out) act_out[row * 8 + sub] = u;
   return u;
 }
 // the action of env step t, as eight clipped doubles on every lane of the group: given (the plain kernels) or computed here (POLICY).  `A` is the kernel's argument struct
@@ -105,7 +114,8 @@ __device__ __forceinline__ void mt_step_action(const A& a, const int t, const in
     // what the policy sees: the row this env emitted last, exactly as it stands in out.obs (a rolled-back step's repeated row, the goal entries a goal switch patched),
     // each double rounded to float32; at step 0 the caller's obs0.  Lane `sub` reads the element lane `sub` wrote (observe, the rollback and the goal switch all store
     // element `sub` from lane `sub`), after the agent-scope fence that ends every env step.
-    const double* seen = t > 0 ? a.out.obs + (row - n) * 32 : nullptr;
+    // (out.obs == NULL, earl_minitaur_population_rollout: the env's row of st.last_obs, the one observation row such a launch keeps)
+    const double* seen = t > 0 ? (a.out.obs ? a.out.obs + (row - n) * 32 : a.st.last_obs + (size_t)env * 32) : nullptr;
     const uint64_t ev = a.cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t;      // (read per step, like the goal switch's)
     // (offset 0 of the kernel-argument segment is the kernel's one argument, the MinitaurPolicyArgs)
     const EARL_KARG void* ka = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();

@@ -54,11 +54,21 @@
     const int steps = s.ev.steps + 1;
     double goal0 = s.ev.goal[0], goal1 = s.ev.goal[1];
     double v;
+    [[maybe_unused]] double rew = 0.0;                // POLICY: what out.reward / out.success hold or would hold for this step, for the episode summary
+    [[maybe_unused]] uint8_t suc = 0;
     if (failed) {
       load_state<NV>(s, m, a.st.qpos + (size_t)env * m.nq, a.st.qvel + (size_t)env * NV, sub);
       if (sub < 8) {
         s.ev.oh[sub] = a.st.overheat[(size_t)env * 8 + sub]; s.ev.en[sub] = a.st.motor_enabled[(size_t)env * 8 + sub] != 0 ? 1 : 0; s.ev.obs_t[sub] = a.st.observed_torque[(size_t)env * 8 + sub];
       }
+      if constexpr (POLICY) {
+        // (POLICY only, as in the one-wave kernel: without out.obs the env's row of st.last_obs stays; reward 0 and success 0 go out with the summary below)
+        if (a.out.obs) {
+          v = t > 0 ? a.out.obs[(row - n) * 32 + sub] : (a.st.last_obs ? a.st.last_obs[(size_t)env * 32 + sub] : NAN);
+          if (live) a.out.obs[row * 32 + sub] = v;
+        }
+        if (live && sub == 0 && a.st.fail_count) a.st.fail_count[env] += 1;
+      } else {
       v = t > 0 ? a.out.obs[(row - n) * 32 + sub] : (a.st.last_obs ? a.st.last_obs[(size_t)env * 32 + sub] : NAN);
       if (live) {
         a.out.obs[row * 32 + sub] = v;
@@ -66,6 +76,7 @@
           a.out.reward[row] = 0.0; a.out.success[row] = 0;
           if (a.st.fail_count) a.st.fail_count[env] += 1;
         }
+      }
       }
       fence();
     } else {
@@ -92,6 +103,19 @@
         if (sub < 8) {
           a.st.overheat[(size_t)env * 8 + sub] = s.ev.oh[sub]; a.st.motor_enabled[(size_t)env * 8 + sub] = s.ev.en[sub] ? 1 : 0; a.st.observed_torque[(size_t)env * 8 + sub] = s.ev.obs_t[sub];
         }
+        if constexpr (POLICY) {
+          // row t of out.obs, or -- out.obs == NULL -- the env's row of st.last_obs, the one observation row such a launch keeps (see the one-wave kernel)
+          (a.out.obs ? a.out.obs + row * 32 : a.st.last_obs + (size_t)env * 32)[sub] = v;
+          if (sub == 0) {                               // the same expressions as below, kept for the stores after the branch
+            const double* o = s.kit.obs;
+            const double xd = o[28] - goal0, yd = o[29] - goal1;
+            double dotp = 0.0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) dotp = fma(o[16 + k], o[8 + k], dotp);
+            rew = cfg.distance_weight * (-fabs(xd) - fabs(yd)) - cfg.energy_weight * (fabs(dotp) * m.dt);
+            suc = sqrt(xd * xd + yd * yd) < cfg.success_radius;
+          }
+        } else {
         a.out.obs[row * 32 + sub] = v;
         if (sub == 0) {                                 // _reward (minitaur_gym_env.py:505-521) = compute_reward (:529-535) on this observation; is_successful :495-503
           const double* o = s.kit.obs;
@@ -102,11 +126,37 @@
           a.out.reward[row] = cfg.distance_weight * (-fabs(xd) - fabs(yd)) - cfg.energy_weight * (fabs(dotp) * m.dt);
           a.out.success[row] = sqrt(xd * xd + yd * yd) < cfg.success_radius;
         }
+        }
       }
     }
+    if constexpr (POLICY) {
+      // reward and success of the step (a rolled-back step: 0 and 0) to their rows, each NULL or given, and into the env's episode summary, whose pointers are read
+      // through the kernel-argument segment here, where they are used (as in the one-wave kernel)
+      if (sub == 0 && live) {
+        const double r_t = failed ? 0.0 : rew;
+        const uint8_t s_t = failed ? (uint8_t)0 : suc;
+        if (a.out.reward) a.out.reward[row] = r_t;
+        if (a.out.success) a.out.success[row] = s_t;
+        const EARL_KARG void* kp = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kp));
+        const EARL_KARG MinitaurPolicyArgs* ka = (const EARL_KARG MinitaurPolicyArgs*)kp;
+        double* const sum_ret = ka->sum_ret;
+        uint8_t* const sum_last = ka->sum_last;
+        int32_t* const sum_first = ka->sum_first;
+        if (sum_ret) sum_ret[env] = (t > 0 ? sum_ret[env] : 0.0) + r_t;      // sum over t ascending of reward_t
+        if (sum_last) sum_last[env] = s_t;                                   // (the one of step T - 1 stays)
+        if (sum_first) {
+          const int32_t f = t > 0 ? sum_first[env] : -1;
+          sum_first[env] = (f < 0 && s_t) ? t : f;
+        }
+        if (a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
+        if (a.out.done) a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
+      }
+    } else {
     if (sub == 0 && live) {
       if (a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
       a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
+    }
     }
     int sgc = s.ev.sgc;
     fence();
@@ -115,6 +165,9 @@
       int gi = (int)(mt_draw(cfg, 0xFFFEu, env, cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t) * (double)cfg.n_goals);
       gi = gi >= cfg.n_goals ? cfg.n_goals - 1 : gi;
       goal0 = cfg.goal_table[2 * gi]; goal1 = cfg.goal_table[2 * gi + 1];
+      if constexpr (POLICY) {
+        if (live && sub >= 30) (a.out.obs ? a.out.obs + row * 32 : a.st.last_obs + (size_t)env * 32)[sub] = sub == 30 ? goal0 : goal1;
+      } else
       if (live && sub >= 30) a.out.obs[row * 32 + sub] = sub == 30 ? goal0 : goal1;
       if (live && sub == 0) { a.st.goal[(size_t)env * 2] = goal0; a.st.goal[(size_t)env * 2 + 1] = goal1; }
     }
@@ -224,6 +277,9 @@
           if (a.st.steps_since_reset) a.st.steps_since_reset[env] = s.ev.steps;
           if (gcf > 0) a.st.steps_since_goal_change[env] = s.ev.sgc;
         }
+        if constexpr (POLICY) {                         // (without out.obs the env's row of last_obs was kept current step by step)
+          if (a.out.obs && a.st.last_obs && a.T > 0) a.st.last_obs[(size_t)env * 32 + sub] = a.out.obs[((size_t)(a.T - 1) * n + env) * 32 + sub];
+        } else
         if (a.st.last_obs && a.T > 0) a.st.last_obs[(size_t)env * 32 + sub] = a.out.obs[((size_t)(a.T - 1) * n + env) * 32 + sub];
       }
     }

@@ -2,7 +2,7 @@
 //
 // The stepper (physics_stepper.h) instantiated for nv = 23 (32 lanes per env, arm block + fixtures solver, joint couplings, dry friction, springs, force-limited actuators) plus the kitchen env
 // kernels (physics_env_kitchen.h: the per-step kernels, the fused rollout, the fused rollout with an MLP policy inside) and the entry points earl_kitchen_step / earl_kitchen_rollout /
-// earl_kitchen_policy_rollout; earl_physics_step / _forward of the
+// earl_kitchen_policy_rollout / earl_kitchen_population_rollout; earl_physics_step / _forward of the
 // main unit forward nv = 23 here.  A translation unit of its own (round 5): the main unit's compile time was 50 s with it.
 #include "physics_stepper.h"
 #include "policy_check.h"
@@ -66,17 +66,21 @@ int earl_kitchen_rollout_clocked(const void* model, const earl_collision_model* 
   else kitchen_rollout_kernel<0><<<solo_grid(cfg->n, k.solo, Lim<23>::WPB), block_for<23>(), 0, (hipStream_t)stream>>>(k);
   return launched("kitchen_rollout");
 }
-// include/earl_physics.h: T closed-loop env steps in one launch, the policy evaluated by the 32 lanes that own the env.  The launch forms are
-// earl_kitchen_rollout_clocked's, chosen here by the same rule; the kernels are instantiated in physics_kitchen_policy.hip
-int earl_kitchen_policy_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
-                                const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T,
-                                const uint64_t* clock, float* actions, const earl_kitchen_out* out, earl_stream_t stream) {
-  if (!model || !params || !cfg || !st || !policy || !obs0 || !actions || !out || cfg->n < 0 || T < 0 || cfg->n_att < 10 || cfg->n_att > 32 || cfg->frame_skip < 0) return EARL_ERR_ARG;
+// include/earl_physics.h: T closed-loop env steps in one launch, the policy evaluated by the 32 lanes that own the env -- one policy or a population's member per env,
+// every [T] output optional, per-env episode summaries.  The launch forms are earl_kitchen_rollout_clocked's, chosen here by the same rule; the kernels are
+// instantiated in physics_kitchen_policy.hip
+int earl_kitchen_population_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                                    const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head,
+                                    const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_kitchen_out* out,
+                                    const earl_episode_summary* summary, earl_stream_t stream) {
+  if (!model || !params || !cfg || !st || !policy || !obs0 || !out || cfg->n < 0 || T < 0 || cfg->n_att < 10 || cfg->n_att > 32 || cfg->frame_skip < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !st->last_qp_robot || !st->att_xpos || !st->steps_since_reset || !st->last_obs) return EARL_ERR_ARG;
-  if (!out->obs || !out->reward || !out->done || !out->success || !cfg->mocap_quat_dev) return EARL_ERR_ARG;
+  if (!cfg->mocap_quat_dev) return EARL_ERR_ARG;
   for (int k = 0; k < 8; ++k) if (cfg->site_att[k] < 0 || cfg->site_att[k] >= cfg->n_att) return EARL_ERR_ARG;
-  // the policy's contract (policy_check.h).  The reference clips the action silently, so an unbounded output is taken (unlike the minitaur's)
+  // the policy's contract (policy_check.h).  The reference clips the action silently, so an unbounded output is taken (unlike the minitaur's).  A population: groups
+  // of 16 envs, every member's rows read in 16-byte pieces
   if (earl::contract::check_policy(*policy, 46, 9, head, earl::contract::kParamsAligned16, nullptr)) return EARL_ERR_ARG;
+  if (pop && earl::contract::check_population(*policy, *pop, cfg->env_offset, cfg->n, 16, 4, nullptr)) return EARL_ERR_ARG;
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "kitchen_policy_rollout")) return rc;
   KitchenPolicyArgs k;
@@ -86,10 +90,22 @@ int earl_kitchen_policy_rollout(const void* model, const earl_collision_model* c
   k.gauss = head ? 1 : 0;
   k.obs0 = obs0;
   k.act_out = actions;
+  k.pop_G = pop ? pop->envs_per_policy : 0;
+  k.pop_stride = pop ? pop->param_stride : 0;
+  k.sum_ret = summary ? summary->ret : nullptr;
+  k.sum_last = summary ? summary->success_last : nullptr;
+  k.sum_first = summary ? summary->first_success : nullptr;
   if (k.solo == 2 && g_solo < 0) k.solo = 3;      // the plain entry point's rule
   if (g_solo < 0 && k.solo == 1 && cfg->n <= 2 * cu_count()) k.solo = 4;
   earl_unit_kitchen_policy_rollout(&k, stream);      // physics_kitchen_policy.hip holds the kernels
   return launched("kitchen_policy_rollout");
+}
+// one policy, every [T] row kept: the population entry point without a population and without a summary (the same launch, bit for bit)
+int earl_kitchen_policy_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                                const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                                const uint64_t* clock, float* actions, const earl_kitchen_out* out, earl_stream_t stream) {
+  if (!actions || !out || !out->obs || !out->reward || !out->done || !out->success) return EARL_ERR_ARG;
+  return earl_kitchen_population_rollout(model, col, params, cfg, st, policy, nullptr, head, obs0, T, clock, actions, out, nullptr, stream);
 }
 int earl_kitchen_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                          const earl_kitchen_state* st, const float* action, int32_t T, const earl_kitchen_out* out, earl_stream_t stream) {

@@ -51,18 +51,21 @@ int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_mode
   else minitaur_kernel<false, false><<<solo_grid(cfg->n, a.solo, Lim<22>::WPB), block_for<22>(), 0, (hipStream_t)stream>>>(a);
   return launched("minitaur_rollout");
 }
-// include/earl_physics.h: T closed-loop env steps in one launch, the policy evaluated by the 32 lanes that own the env.  The launch forms are
-// earl_minitaur_rollout_clocked's (one-wave kernel in its three shapes, two-wave kernel); the generic substep<22> comparison build has no policy form
-int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
-                                 const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
-                                 const earl_minitaur_out* out, earl_stream_t stream) {
-  if (!model24 || !cfg || !st || !out || !policy || !obs0 || !actions || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
+// include/earl_physics.h: T closed-loop env steps in one launch, the policy evaluated by the 32 lanes that own the env -- one policy or a population's member per env,
+// every [T] output optional, per-env episode summaries.  The launch forms are earl_minitaur_rollout_clocked's (one-wave kernel in its three shapes, two-wave kernel);
+// the generic substep<22> comparison build has no policy form
+int earl_minitaur_population_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                     const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                                     const uint64_t* clock, float* actions, const earl_minitaur_out* out, const earl_episode_summary* summary, earl_stream_t stream) {
+  if (!model24 || !cfg || !st || !out || !policy || !obs0 || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
-  if (!out->obs || !out->reward || !out->done || !out->success || !cfg->goal_table || cfg->n_goals < 1 || cfg->num_substeps < 0) return EARL_ERR_ARG;
+  if (!out->obs && !st->last_obs) return EARL_ERR_ARG;    // (without out->obs the env's row of last_obs is the one observation row the launch keeps)
+  if (!cfg->goal_table || cfg->n_goals < 1 || cfg->num_substeps < 0) return EARL_ERR_ARG;
   if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;
   // the policy's contract (policy_check.h).  The reference env raises on an action outside +-(1 + 0.01); a kernel cannot, and the open-loop replay of the returned
-  // actions must not either: bounded policies only
+  // actions must not either: bounded policies only.  A population: groups of 16 envs, every member's rows read in 16-byte pieces
   if (earl::contract::check_policy(*policy, 32, 8, head, earl::contract::kParamsAligned16 | earl::contract::kBoundedOutput, nullptr)) return EARL_ERR_ARG;
+  if (pop && earl::contract::check_population(*policy, *pop, cfg->env_offset, cfg->n, 16, 4, nullptr)) return EARL_ERR_ARG;
   if (!g_mt_stepper) return EARL_ERR_ARG;                 // (earl_debug_set_minitaur_stepper(0): no policy form)
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_policy_rollout")) return rc;
@@ -73,12 +76,24 @@ int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model
   a.gauss = head ? 1 : 0;
   a.obs0 = obs0;
   a.act_out = actions;
+  a.pop_G = pop ? pop->envs_per_policy : 0;
+  a.pop_stride = pop ? pop->param_stride : 0;
+  a.sum_ret = summary ? summary->ret : nullptr;
+  a.sum_last = summary ? summary->success_last : nullptr;
+  a.sum_first = summary ? summary->first_success : nullptr;
   if (a.solo == 0 && cfg->num_substeps > 0 && (g_mt_duo > 0 || (g_mt_duo < 0 && mt_use_duo(cfg->n)))) {      // the plain entry point's rule
     minitaur_policy_duo_kernel<<<(unsigned)((cfg->n + 16 * MT_DUO_PAIRS / 4 - 1) / (4 * MT_DUO_PAIRS)), 128 * MT_DUO_PAIRS, 0, (hipStream_t)stream>>>(a);
     return launched("minitaur_policy_rollout (two waves per SIMD)");
   }
   minitaur_policy_kernel<false, true><<<solo_grid(cfg->n, a.solo, EARL_MT_WPB), 64 * EARL_MT_WPB, 0, (hipStream_t)stream>>>(a);
   return launched("minitaur_policy_rollout");
+}
+// one policy, every [T] row kept: the population entry point without a population and without a summary (the same launch, bit for bit)
+int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                 const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
+                                 const earl_minitaur_out* out, earl_stream_t stream) {
+  if (!actions || !out || !out->obs || !out->reward || !out->done || !out->success) return EARL_ERR_ARG;
+  return earl_minitaur_population_rollout(model24, col, cfg, st, policy, nullptr, head, obs0, T, clock, actions, out, nullptr, stream);
 }
 int earl_minitaur_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                           const float* action, int32_t T, const earl_minitaur_out* out, earl_stream_t stream) {

@@ -351,13 +351,14 @@ class Kitchen:
                 done=torch.empty(*lead, n, dtype=torch.bool, **kw), success=torch.empty(*lead, n, dtype=torch.bool, **kw),
                 status=torch.empty(*lead, n, dtype=torch.uint8, **kw))
 
-  def _check_policy(self, policy, who):
-    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy of this env's widths on this env's device.  The reference clips the action silently
+  def _check_policy(self, policy, who, population=False):
+    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy of this env's widths on this env's device; population=True (rollout_population,
+    evaluate_population): or a PolicyPopulation of them whose members cover this env's global ids.  The reference clips the action silently
     (kitchen_multitask_v0.py:92): an unbounded output is taken"""
     from ..policy import AgentPair, PolicyPopulation, require_widths
-    if isinstance(policy, PolicyPopulation):
-      raise NotImplementedError(f'{who}: a PolicyPopulation on the kitchen is not offered (one MLPPolicy / GaussianMLPPolicy per launch; populations run on the tabletop, '
-                                'the Sawyer door and the Sawyer peg)')
+    if isinstance(policy, PolicyPopulation) and not population:
+      raise NotImplementedError(f'{who}: a PolicyPopulation on the kitchen goes to rollout_population / evaluate_population ({who} takes one MLPPolicy / '
+                                'GaussianMLPPolicy per launch)')
     if isinstance(policy, AgentPair):
       raise NotImplementedError(f'{who}: an AgentPair on the kitchen is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
     if self.scalar_api:
@@ -366,15 +367,18 @@ class Kitchen:
       raise ValueError(f'{who}: the kitchen\'s lifelong goal switch runs on the host (goal_change_frequency > 0) and cannot happen inside the launch, as make_step_graph says')
     return require_widths(policy, who, self.OBS_DIM, self.N_ROBOT, env=self)
 
-  def _launch_policy(self, policy, head, obs0, T, out):
-    """hook of physics_policy_rollout: earl_kitchen_policy_rollout; the sensor-noise counter advances by T"""
-    o = _abi.KitchenOut(obs=out['obs'].data_ptr(), reward=out['reward'].data_ptr(), done=out['done'].data_ptr(), success=out['success'].data_ptr(),
-                        status=out['status'].data_ptr())
+  def _launch_policy(self, policy, head, obs0, T, out, summary=None):
+    """hook of physics_policy_rollout: earl_kitchen_population_rollout (a single policy: pop = NULL, which is earl_kitchen_policy_rollout bit for bit); `out` may lack
+    any key, 'obs' included (the env's row of last_obs then carries the observation); summary: None or an _abi.EpisodeSummary.  The sensor-noise counter advances by T"""
+    ptr = lambda k: None if out.get(k) is None else out[k].data_ptr()
+    o = _abi.KitchenOut(obs=ptr('obs'), reward=ptr('reward'), done=ptr('done'), success=ptr('success'), status=ptr('status'))
+    pop = getattr(policy, 'pop_struct', None)              # a PolicyPopulation: the env with global id g runs member g // envs_per_policy
     self._cfg.counter = self._counter
     with torch.cuda.device(self.device):
-      _abi.check(self._lib.earl_kitchen_policy_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._params), C.byref(self._cfg), C.byref(self._st),
-                                                       C.byref(policy.struct), None if head is None else C.byref(head), obs0.data_ptr(), T, None,
-                                                       out['actions'].data_ptr(), C.byref(o), self._stream()), 'earl_kitchen_policy_rollout')
+      _abi.check(self._lib.earl_kitchen_population_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._params), C.byref(self._cfg), C.byref(self._st),
+                                                           C.byref(policy.struct), None if pop is None else C.byref(pop), None if head is None else C.byref(head),
+                                                           obs0.data_ptr(), T, None, ptr('actions'), C.byref(o), None if summary is None else C.byref(summary),
+                                                           self._stream()), 'earl_kitchen_population_rollout')
     self._counter += T
 
   def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
@@ -388,8 +392,19 @@ class Kitchen:
     raise NotImplementedError('rollout_agents: an AgentPair on the kitchen is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
 
   def evaluate_policy(self, policy, T, **kw):
-    raise NotImplementedError('evaluate_policy: episode summaries on the kitchen are not offered (rollout_policy returns every step; evaluate_policy runs on the '
-                              'tabletop, the Sawyer door and the Sawyer peg)')
+    raise NotImplementedError('evaluate_policy: episode summaries on the kitchen are evaluate_population\'s (it takes one policy as well as a PolicyPopulation); '
+                              'evaluate_policy runs on the tabletop, the Sawyer door and the Sawyer peg')
+
+  def rollout_population(self, pop, T, reset_first=False, sample=True, return_noise=False, out=None):
+    """rollout_policy for a `PolicyPopulation(..., obs_dim=46, act_dim=9)`: the env with global id g runs member g // envs_per_policy, every member in the ONE
+    launch (physics_policy_rollout.rollout_population; earl_kitchen_population_rollout).  -> rollout_policy's dict"""
+    return closed_loop.rollout_population(self, pop, T, reset_first, sample, return_noise, out)
+
+  def evaluate_population(self, policy_or_pop, T, episodes=1, sample=False, reset_first=True):
+    """physics_policy_rollout.evaluate (its docstring is the contract) on earl_kitchen_population_rollout: per-env episode summaries of one policy or of a
+    `PolicyPopulation`, no tensor with a T axis.  The sensor-noise counter advances by T per launch (plus the fresh reading when last_obs is stale).
+    -> {'ret', 'success', 'first_success', 'guard_steps'}, each [episodes, N]"""
+    return closed_loop.evaluate(self, 'evaluate_population', policy_or_pop, T, episodes, sample, reset_first)
 
   def _get_obs_t(self):
     """a fresh reading as _get_obs() makes it (a noise draw on the current counter, last_qp_robot updated), as the [N, 46] tensor whatever scalar_api says, and

@@ -168,23 +168,29 @@ class Minitaur:
         closed_loop.finish(self, T, res['reward'], res['success'][-1])
     return res
 
-  def _check_policy(self, policy, who):
-    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy of this env's widths on this env's device whose output is bounded"""
+  def _check_policy(self, policy, who, population=False):
+    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy of this env's widths on this env's device whose output is bounded; population=True
+    (rollout_population, evaluate_population): or a PolicyPopulation of them whose members cover this env's global ids"""
     from ..policy import AgentPair, PolicyPopulation, require_widths
-    if isinstance(policy, PolicyPopulation):
-      raise NotImplementedError(f'{who}: a PolicyPopulation on the minitaur is not offered (one MLPPolicy / GaussianMLPPolicy per launch; populations run on the tabletop, '
-                                'the Sawyer door and the Sawyer peg)')
+    if isinstance(policy, PolicyPopulation) and not population:
+      raise NotImplementedError(f'{who}: a PolicyPopulation on the minitaur goes to rollout_population / evaluate_population ({who} takes one MLPPolicy / '
+                                'GaussianMLPPolicy per launch)')
     if isinstance(policy, AgentPair):
       raise NotImplementedError(f'{who}: an AgentPair on the minitaur is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
     return require_widths(policy, who, OBS_DIM, ACT_DIM, env=self, bounded=ACTION_BOUND + ACTION_EPS)
 
-  def _launch_policy(self, policy, head, obs0, T, out):
-    """hook of physics_policy_rollout: earl_minitaur_policy_rollout"""
+  def _launch_policy(self, policy, head, obs0, T, out, summary=None):
+    """hook of physics_policy_rollout: earl_minitaur_population_rollout (a single policy: pop = NULL, which is earl_minitaur_policy_rollout bit for bit); `out` may
+    lack any key, 'obs' included (the env's row of last_obs then carries the observation); summary: None or an _abi.EpisodeSummary"""
     self._cfg.step_counter = self.total_step_count
+    ptr = lambda k: None if out.get(k) is None else out[k].data_ptr()
+    o = _abi.MinitaurOut(obs=ptr('obs'), reward=ptr('reward'), done=ptr('done'), success=ptr('success'), status=ptr('status'))
+    pop = getattr(policy, 'pop_struct', None)              # a PolicyPopulation: the env with global id g runs member g // envs_per_policy
     with torch.cuda.device(self.device):
-      _abi.check(self._lib.earl_minitaur_policy_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), C.byref(policy.struct),
-                                                        None if head is None else C.byref(head), obs0.data_ptr(), T, None, out['actions'].data_ptr(),
-                                                        C.byref(self._out_struct(out)), self._stream()), 'earl_minitaur_policy_rollout')
+      _abi.check(self._lib.earl_minitaur_population_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), C.byref(policy.struct),
+                                                            None if pop is None else C.byref(pop), None if head is None else C.byref(head), obs0.data_ptr(), T, None,
+                                                            ptr('actions'), C.byref(o), None if summary is None else C.byref(summary), self._stream()),
+                 'earl_minitaur_population_rollout')
 
   def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
     """physics_policy_rollout's closed loop (its docstring is the contract) on earl_minitaur_policy_rollout: `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy` built with
@@ -196,8 +202,18 @@ class Minitaur:
     raise NotImplementedError('rollout_agents: an AgentPair on the minitaur is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
 
   def evaluate_policy(self, policy, T, **kw):
-    raise NotImplementedError('evaluate_policy: episode summaries on the minitaur are not offered (rollout_policy returns every step; evaluate_policy runs on the '
-                              'tabletop, the Sawyer door and the Sawyer peg)')
+    raise NotImplementedError('evaluate_policy: episode summaries on the minitaur are evaluate_population\'s (it takes one policy as well as a PolicyPopulation); '
+                              'evaluate_policy runs on the tabletop, the Sawyer door and the Sawyer peg')
+
+  def rollout_population(self, pop, T, reset_first=False, sample=True, return_noise=False, out=None):
+    """rollout_policy for a `PolicyPopulation(..., obs_dim=32, act_dim=8)` of bounded policies: the env with global id g runs member g // envs_per_policy, every
+    member in the ONE launch (physics_policy_rollout.rollout_population; earl_minitaur_population_rollout).  -> rollout_policy's dict"""
+    return closed_loop.rollout_population(self, pop, T, reset_first, sample, return_noise, out)
+
+  def evaluate_population(self, policy_or_pop, T, episodes=1, sample=False, reset_first=True):
+    """physics_policy_rollout.evaluate (its docstring is the contract) on earl_minitaur_population_rollout: per-env episode summaries of one policy or of a
+    `PolicyPopulation`, no tensor with a T axis.  -> {'ret', 'success', 'first_success', 'guard_steps'}, each [episodes, N]"""
+    return closed_loop.evaluate(self, 'evaluate_population', policy_or_pop, T, episodes, sample, reset_first)
 
   def step(self, action):
     """-> (obs [N,32], reward [N], done [N], info{success, status}); gym 4-tuple of numpy / python scalars with scalar_api"""

@@ -513,6 +513,29 @@ int earl_kitchen_rollout_clocked(const void* model24, const earl_collision_model
 int earl_kitchen_policy_rollout(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                                 const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T,
                                 const uint64_t* clock, float* actions, const earl_kitchen_out* out, earl_stream_t stream);
+/* ---- the same closed loop for a POPULATION of policies, with per-env episode summaries and without any [T] array ----
+ * earl_policy_population / earl_episode_summary are earl_tabletop.h's, as they are.  One episode per launch: the summary rows are [n].
+ *   pop      NULL = one policy: bit-identical to earl_kitchen_policy_rollout, which is this call with pop = summary = NULL.  Otherwise the env with GLOBAL id
+ *            g = cfg->env_offset + i runs member g / G, whose parameters start at policy->params + (g / G) * param_stride.  The member depends on the global id only: not on
+ *            n, the shard split, the launch form, or which wave or 32-lane group holds the env; env_offset need not be a multiple of anything, and a wave whose two envs
+ *            belong to two members is correct, only slower.  The launch is bit-identical to cutting the batch at the global ids that are multiples of G and running
+ *            earl_kitchen_policy_rollout on each piece (env_offset = its first global id, n = its length, the matching state rows) with that member's parameters:
+ *            outputs, actions, eps_out, every state row, fail_count, counters.
+ *   summary  NULL, or rows [n]: ret = sum over t ascending of reward_t (float64, the doubles as out->reward holds or would hold them); success_last = the success flag of
+ *            step T - 1; first_success = the smallest t with success, or -1.  Rolled-back rows count with reward 0 and success 0.  The lane that stores the env's reward
+ *            keeps the three words up to date in device memory after every env step (step 0 initialises them); nothing of them lives in a register across a timestep.
+ *   actions and every pointer of `out`, out->obs included, may be NULL (`out` itself may not).  With out->obs == NULL the env's row of st->last_obs -- which every
+ *            kitchen rollout keeps current step by step, and a rolled-back step leaves standing -- is the row the policy of step t + 1 reads, each lane reading what it
+ *            stored itself, behind the fence that ends an env step.  The state left behind, last_obs included, equals the full launch's.
+ * In the several-wave forms the env's owner wave does the policy phase and the summary stores; a 32-lane group that is not live (an idle group of the last wave, a
+ * one-env-per-wave launch's shadow) evaluates on zeros with the rows of the member of the env it shadows, which is always an env of the batch.
+ * EARL_ERR_ARG before any HIP call: everything earl_kitchen_policy_rollout refuses (but NULL actions / out pointers), the contract's population rules with group size 16
+ * (csrc/policy_check.h: check_population, the member range against the global ids included), param_stride % 4 != 0 (every member's rows are read in 16-byte pieces).
+ * st->last_obs is required as ever.  n = 0 or T = 0: EARL_OK, nothing launched. */
+int earl_kitchen_population_rollout(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                                    const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head,
+                                    const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_kitchen_out* out,
+                                    const earl_episode_summary* summary, earl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Minitaur env (BASELINE configs[4]) on the same stepper: floating base + 16 hinges (nv = 22, nq = 23), four connect
@@ -612,6 +635,29 @@ int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_mode
 int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                                  const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
                                  const earl_minitaur_out* out, earl_stream_t stream);
+/* ---- the same closed loop for a POPULATION of policies, with per-env episode summaries and without any [T] array ----
+ * earl_policy_population / earl_episode_summary are earl_tabletop.h's, as they are.  One episode per launch: the summary rows are [n].
+ *   pop      NULL = one policy: bit-identical to earl_minitaur_policy_rollout, which is this call with pop = summary = NULL.  Otherwise the env with GLOBAL id
+ *            g = cfg->env_offset + i runs member g / G, whose parameters start at policy->params + (g / G) * param_stride.  The member depends on the global id only: not on
+ *            n, the shard split, the launch form (one-wave kernel in its three shapes, two-wave kernel), or which wave or 32-lane group holds the env; env_offset need not
+ *            be a multiple of anything, and a wave whose two envs belong to two members is correct, only slower.  The launch is bit-identical to cutting the batch at the
+ *            global ids that are multiples of G and running earl_minitaur_policy_rollout on each piece (env_offset = its first global id, n = its length, the matching
+ *            state rows) with that member's parameters: outputs, actions, eps_out, every state row, fail_count, counters.
+ *   summary  NULL, or rows [n]: ret = sum over t ascending of reward_t (float64, the doubles as out->reward holds or would hold them); success_last = the success flag of
+ *            step T - 1; first_success = the smallest t with success, or -1.  Rolled-back rows count with reward 0 and success 0.  Lane 0 of the env, which stores its
+ *            reward, keeps the three words up to date in device memory after every env step (step 0 initialises them); nothing of them lives in a register across a timestep.
+ *   actions and every pointer of `out`, out->obs included, may be NULL (`out` itself may not).  With out->obs == NULL the env's row of st->last_obs (then required; with
+ *            out->obs it may be NULL as ever) is the one observation row the launch keeps: every emitted row is written to it, a rolled-back step leaves it standing, a goal
+ *            switch patches its entries 30 / 31, and the policy of step t + 1 reads it, each lane reading what it stored itself, behind the fence that ends an env step.
+ *            The state left behind, last_obs included, equals the full launch's.
+ * A 32-lane group that is not live (an idle group of the last wave or workgroup, a one-env-per-wave launch's shadow) evaluates on zeros with the rows of the member of the
+ * env it shadows, which is always an env of the batch: no id at or beyond cfg->env_offset + n is ever formed.
+ * EARL_ERR_ARG before any HIP call: everything earl_minitaur_policy_rollout refuses (but NULL actions / out pointers) -- bounded policies only and no generic-stepper form
+ * included --, the contract's population rules with group size 16 (csrc/policy_check.h: check_population, the member range against the global ids included),
+ * param_stride % 4 != 0 (every member's rows are read in 16-byte pieces), out->obs == NULL with st->last_obs == NULL.  n = 0 or T = 0: EARL_OK, nothing launched. */
+int earl_minitaur_population_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                     const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                                     const uint64_t* clock, float* actions, const earl_minitaur_out* out, const earl_episode_summary* summary, earl_stream_t stream);
 /* reset the envs with mask[i] != 0 (NULL = all); obs [n, 32] (may be NULL) is written for the reset envs only */
 int earl_minitaur_reset(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                         const uint8_t* mask, double* obs, earl_stream_t stream);

@@ -121,7 +121,7 @@ int earl_tabletop_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tableto
  * v_mfma_f32_16x16x4_f32 next to the fp64 recurrence, weights resident in registers for the whole launch.
  *
  * THE ARGUMENT CONTRACT of every closed-loop entry point -- the four of this header, and earl_physics.h's earl_sawyer_policy_rollout, earl_sawyer_population_rollout,
- * earl_sawyer_pair_rollout, earl_minitaur_policy_rollout and earl_kitchen_policy_rollout -- is one set of rules (csrc/policy_check.h states them once; tests/test_policy_contract.py holds every
+ * earl_sawyer_pair_rollout, earl_minitaur_policy_rollout, earl_minitaur_population_rollout, earl_kitchen_policy_rollout and earl_kitchen_population_rollout -- is one set of rules (csrc/policy_check.h states them once; tests/test_policy_contract.py holds every
  * entry point to them).  Each returns EARL_ERR_ARG before any HIP call for
  *   policy      NULL params; precision != 0; n_layers not 2 or 3; dims[0] != the env's observation width; dims[n_layers] != the env's action width (head == NULL) or
  *               twice it (head given); a hidden width that is not a multiple of 16 in 16..256; dims[3] != 0 with two layers; hidden_act not EARL_ACT_RELU / _TANH;

@@ -1,0 +1,73 @@
+"""What tests/test_minitaur_population.py and tests/test_kitchen_population.py share (a plain module: no tests, no fixtures): the population rows of the
+malformed-argument table, the well-formed combinations, and the compile-time reading of one unit."""
+import ctypes as C
+import json
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+from conftest import REPO
+from earl_benchmark_amd import _abi
+
+CSRC = os.path.join(REPO, 'earl_benchmark_amd', 'csrc')
+HIPCC = '/opt/rocm/bin/hipcc'
+PARENT = os.path.join(REPO, 'tests', 'golden', 'population_parent_build.json')
+
+
+def pop_struct(n_policies=4, envs_per_policy=16, param_stride=4096):
+  return _abi.PolicyPopulation(n_policies=n_policies, envs_per_policy=envs_per_policy, param_stride=param_stride)
+
+
+def population_rows(count, n):
+  """malformed populations for a policy of `count` parameters over n envs at env_offset 0 (check_population of csrc/policy_check.h, group 16, stride multiple 4)"""
+  stride = (count + 3) // 4 * 4
+  need = (n + 15) // 16
+  return [pop_struct(0, 16, stride), pop_struct(-1, 16, stride), pop_struct(need, 8, stride), pop_struct(need, 0, stride), pop_struct(need, 24, stride),
+          pop_struct(need, -16, stride), pop_struct(need, 16, count - 1), pop_struct(need, 16, stride + 1), pop_struct(need, 16, stride + 2),
+          pop_struct(need, 16, 0), pop_struct(need - 1, 16, stride)]
+
+
+def declared(name, n_args, after, before):
+  src = re.sub(r'/\*.*?\*/', '', open(os.path.join(REPO, 'include', 'earl_physics.h')).read(), flags=re.S)
+  m = re.search(r'int\s+' + name + r'\s*\((.*?)\)\s*;', src, flags=re.S)
+  assert m, name + ' is not declared'
+  assert len(m.group(1).split(',')) == len(_abi.SIGNATURES[name]) == n_args
+  assert src.index(after) < m.start() < src.index(before)
+  lib, host = _abi.load(), C.CDLL(_abi.HOST_LIB_PATH)
+  assert hasattr(lib, name) and not hasattr(host, name)
+  sig = _abi.SIGNATURES[name]
+  assert sig[-2]._type_ is _abi.EpisodeSummary and any(getattr(a, '_type_', None) is _abi.PolicyPopulation for a in sig)
+
+
+def summaries(p):
+  return [None, _abi.EpisodeSummary(ret=p, success_last=p, first_success=p), _abi.EpisodeSummary(ret=p), _abi.EpisodeSummary(first_success=p)]
+
+
+def compile_unit(unit, tmp_path):
+  """-> (scratch tool, assembly lines, resources per kernel) of one unit cross-compiled with the scratch tool's flags"""
+  from test_kitchen_policy_rollout import resources
+  if shutil.which(HIPCC) is None:
+    pytest.skip('needs hipcc (cross-compiles without a GPU)')
+  sys.path.insert(0, os.path.join(REPO, 'tools'))
+  try:
+    import scratch_in_loops as tool
+  finally:
+    sys.path.pop(0)
+  asm = tmp_path / (unit + '.s')
+  r = subprocess.run([HIPCC, *tool.FLAGS, '-Rpass-analysis=kernel-resource-usage', '-o', str(asm), os.path.join(CSRC, unit)], capture_output=True, text=True, timeout=900)
+  assert r.returncode == 0, r.stderr[-2000:]
+  return tool, open(asm).read().split('\n'), resources(r.stderr)
+
+
+def parent_build():
+  """the recorded parent build, or a skip when this compiler is not the one it was recorded with"""
+  want = json.load(open(PARENT))
+  version = subprocess.run([HIPCC, '--version'], capture_output=True, text=True).stdout
+  if want['compiler'] not in version:
+    pytest.skip('the parent build was recorded with another compiler: ' + want['compiler'])
+  return want
+

@@ -216,9 +216,14 @@ SIGNATURES = {
     # ... for a population of policies with per-env summaries: pop after policy, summary after `out`; actions and every pointer of `out` may be NULL
     'earl_minitaur_population_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MlpPolicy), _P(PolicyPopulation), _P(GaussianHead), C.c_void_p,
                                          C.c_int32, C.c_void_p, C.c_void_p, _P(MinitaurOut), _P(EpisodeSummary), C.c_void_p],
+    'earl_minitaur_agents_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MlpPolicy), _P(AgentPair), _P(PolicyPopulation), _P(BackwardGoals),
+                                     _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _P(MinitaurOut), _P(EpisodeSummary), C.c_void_p],
     'earl_kitchen_population_rollout': [C.c_void_p, C.c_void_p, _P(KitchenParams), _P(KitchenCfg), _P(KitchenState), _P(MlpPolicy), _P(PolicyPopulation), _P(GaussianHead),
                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _P(KitchenOut), _P(EpisodeSummary), C.c_void_p],
     # the closed loop inside the kitchen rollout kernel: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
+    'earl_kitchen_agents_rollout': [C.c_void_p, C.c_void_p, _P(KitchenParams), _P(KitchenCfg), _P(KitchenState), _P(MlpPolicy), _P(AgentPair), _P(PolicyPopulation),
+                                    _P(BackwardGoals), C.c_void_p, C.c_int32, _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _P(KitchenOut),
+                                    _P(EpisodeSummary), C.c_void_p],
     'earl_kitchen_policy_rollout': [C.c_void_p, C.c_void_p, _P(KitchenParams), _P(KitchenCfg), _P(KitchenState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p, _P(KitchenOut), C.c_void_p],
     'earl_minitaur_reset': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_void_p, C.c_void_p],

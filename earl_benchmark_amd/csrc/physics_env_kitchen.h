@@ -97,6 +97,22 @@ struct KitchenPolicyArgs : KitchenRolloutArgs {
   double* sum_ret;               // earl_episode_summary of the launch, each NULL or [n]: lane 0 of the env's owner wave keeps its three words up to date in HBM after every env step
   uint8_t* sum_last;             // (step 0 initialises them)
   int32_t* sum_first;
+  // earl_kitchen_agents_rollout: the forward / reset agent pair (pair_phase == NULL: no pair, and nothing below is read).  As SawyerPolicyArgs': the env's phase word
+  // travels through HBM like the summary words, and every field is read through the kernel-argument segment where it is used
+  int8_t* pair_phase;            // [n] 0 forward, anything else reset; the network of the phase starts at pol.params (+ the member's offset) + phase * pair_stride
+  int32_t* pair_sip;             // [n] steps the env has spent in its phase
+  int64_t pair_stride;           // floats between the two agents' rows (a multiple of 4)
+  const double* pair_goal;       // NULL or the table [pair_goal_rows, 23] of backward goals: entering the reset phase, a drawn row of it becomes the env's st.goal row
+  const double* pair_fwd;        // NULL or the table [pair_fwd_rows, 23] of forward goals: entering the forward phase, likewise (NULL: the goal stays)
+  int pair_goal_rows;            // (1 for pair->backward_goal, the table of one row; 0 with pair_goal == NULL)
+  int pair_fwd_rows;
+  int pair_se[2];                // switch_every
+  int pair_sos;                  // switch_on_success
+  int8_t* pair_agent;            // NULL or [T, n]
+  int32_t* pair_fs;              // NULL or [n]: forward phases that ended by success (step 0 of the launch starts them at 0)
+  int32_t* pair_bs;              // NULL or [n]: reset phases that ended by success
+  int32_t* pair_row;             // NULL or [n]: earl_backward_goals.row
+  int32_t* pair_row_out;         // NULL or [T, n]: earl_backward_goals.row_out
 };
 static_assert(std::is_standard_layout<KitchenRolloutArgs>::value && std::is_trivially_copyable<KitchenPolicyArgs>::value, "the policy phase reads KitchenPolicyArgs as laid out in the kernel-argument segment");
 #include "policy_lane_group.h"
@@ -129,6 +145,15 @@ __device__ __noinline__ float kitchen_policy_action(const uint64_t ka_bits, cons
   const float* w = ka->pol.params;
   const int pop_G = ka->pop_G;
   if (pop_G > 0) w += (size_t)(gid / (uint32_t)pop_G) * (size_t)ka->pop_stride;
+  // an agent pair: the network of the env's phase, the word lane 0 of the owner wave stored after the last handover decision (a wave whose two envs are in two phases
+  // walks two sets of rows, like a wave of two members).  A group that is not live reads the word of the env it shadows
+  const int8_t* pair_phase = ka->pair_phase;
+  if (pair_phase) {
+    const int ph = pair_phase[env] != 0 ? 1 : 0;
+    if (ph) w += (size_t)ka->pair_stride;
+    int8_t* agent_out = ka->pair_agent;
+    if (sub == 0 && live && agent_out) agent_out[row] = (int8_t)ph;
+  }
   pol_layer<32, false>(w, w + (size_t)d1 * 46, 46, d1, hidden_act, sub, h);
   w += (size_t)d1 * (46 + 1);
   if (n_layers == 3) {
@@ -177,6 +202,66 @@ __device__ __forceinline__ double kit_policy_step(const A& a, const int t, const
   // the env step consumes the float32 values stored in act_out: lanes 0 .. 8 of the live group hold them.  The second group of a one-env-per-wave launch (solo >= 1)
   // is the first one's shadow and steps with the bits of the live group's action (wave-wide shuffle; the choice is wave-uniform)
   return (double)__shfl(u, a.solo >= 1 ? kk : grp * 32 + kk, 64);
+}
+// The agent pair's handover after env step t (include/earl_physics.h, earl_kitchen_agents_rollout, items 5 and 6), worked out by the 32 lanes of the env's owner wave
+// from the same words: the step's success flag from lane 0 of the live group, phase and steps_in_phase from HBM, where that lane stores them again -- nothing of the
+// pair lives across a timestep.  The pair's kernel arguments are read through the kernel-argument segment here, where they are used (see kitchen_policy_action on why).
+// The goal in force IS the env's row of st.goal, which the observation loop reads at every step: a handover that changes it stores the new row there and patches entries
+// 23 .. 45 of the row the env emitted at this step (row t of out.obs if given, and the env's row of st.last_obs), each entry by the lane that emitted it; this step's
+// reward was computed before, from the row as emitted.  Called by the policy kernels only; `a`'s own members are KitchenRolloutArgs'
+template <class A>
+__device__ __forceinline__ void kit_pair_handover(const A& a, const int t, const int env, const size_t row, const int sub, const int grp, const bool live, const bool failed,
+                                                  const uint8_t suc) {
+#pragma clang fp contract(off)
+  const EARL_KARG void* kap = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kap));
+  const EARL_KARG KitchenPolicyArgs* ka = (const EARL_KARG KitchenPolicyArgs*)kap;
+  int8_t* const pair_phase = ka->pair_phase;
+  if (!pair_phase) return;                               // (wave-uniform)
+  int32_t* const pair_sip = ka->pair_sip;
+  // (the second group of a one-env-per-wave launch is the first one's shadow and takes the live group's flag: the same branches)
+  const bool by_s = ka->pair_sos != 0 && __shfl((int)((!failed && suc) ? 1 : 0), a.solo >= 1 ? 0 : grp * 32, 64) != 0;
+  int ph = pair_phase[env] != 0 ? 1 : 0;
+  int sip = pair_sip[env] + 1;                           // (a rolled-back step counts, with success 0)
+  const bool over = by_s || sip >= (ph ? ka->pair_se[1] : ka->pair_se[0]);
+  int32_t* const row_at = ka->pair_row_out;
+  if (sub == 0 && live) {
+    int32_t* const fs = ka->pair_fs;
+    int32_t* const bs = ka->pair_bs;
+    if (fs) fs[env] = (t > 0 ? fs[env] : 0) + ((by_s && ph == 0) ? 1 : 0);      // (a step where the clock ran out as well counts as ended by success)
+    if (bs) bs[env] = (t > 0 ? bs[env] : 0) + ((by_s && ph != 0) ? 1 : 0);
+    if (row_at) row_at[row] = -1;                        // overwritten below by the same lane on a step that draws
+  }
+  if (over) {
+    ph ^= 1;
+    sip = 0;
+    // entering the reset phase: a row of the backward table (draw index 0xFFFD); entering the forward phase: a row of the forward table (0xFFFE).  The draw's counter
+    // words, u01 and clamp are earl_sawyer_agents_rollout's, ev the step's sensor-noise counter (the noise draws with 0x4B00 + j, the head with 0x504F4C00 + b)
+    const double* const table = ph ? ka->pair_goal : ka->pair_fwd;
+    if (table) {
+      const int rows = ph ? ka->pair_goal_rows : ka->pair_fwd_rows;
+      const uint64_t ev = a.cfg.counter + (a.clock ? a.clock[0] : 0) + (uint64_t)t;
+      const earl::U4 b = earl::philox4x32_10(earl::U4{ph ? 0xFFFDu : 0xFFFEu, (uint32_t)(a.cfg.env_offset + env), (uint32_t)ev, (uint32_t)(ev >> 32)},
+                                             (uint32_t)a.cfg.seed, (uint32_t)(a.cfg.seed >> 32));
+      int gi = (int)(earl::u01(b.x, b.y) * (double)rows);
+      gi = gi < rows ? gi : rows - 1;
+      if (live) {
+        for (int k = sub; k < 46; k += 32) {
+          if (k < 23) continue;
+          const double gv = table[(size_t)gi * 23 + (k - 23)];
+          a.st.goal[(size_t)env * 23 + (k - 23)] = gv;
+          if (a.out.obs) a.out.obs[row * 46 + k] = gv;
+          a.st.last_obs[(size_t)env * 46 + k] = gv;
+        }
+        if (sub == 0 && ph) {
+          int32_t* const row_of = ka->pair_row;
+          if (row_of) row_of[env] = gi;
+          if (row_at) row_at[row] = gi;
+        }
+      }
+    }
+  }
+  if (sub == 0 && live) { pair_phase[env] = (int8_t)ph; pair_sip[env] = sip; }
 }
 // DUO (solo == 3, round 5): the FOUR waves of the workgroup, one per SIMD, work on its one env (substep's ROLE 1 - 4).  Per timestep all run the kinematics; then, side by
 // side: wave 0 (B, owns the env) the constraint rows, wave 1 (A) the mass matrix into wave 0's LDS block, wave 2 the bias forces, wave 3 the bounding tests and the collision

@@ -198,6 +198,7 @@
       if (a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
       a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
     }
+    if constexpr (POLICY) kit_pair_handover(a, t, env, row, sub, grp, live, failed, suc);      // earl_kitchen_agents_rollout: the pair's state machine and its goal rows (the owner wave)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");    // the next step reads last_qp_robot (and, after a failure, the state rows) back through global memory
     fence();
   }

@@ -50,6 +50,20 @@ struct MinitaurPolicyArgs : MinitaurArgs {
   double* sum_ret;               // earl_episode_summary of the launch, each NULL or [n]: lane 0 of the env keeps its three words up to date in HBM after every env step
   uint8_t* sum_last;             // (step 0 initialises them)
   int32_t* sum_first;
+  // earl_minitaur_agents_rollout: the forward / reset agent pair (pair_phase == NULL: no pair, and nothing below is read).  As SawyerPolicyArgs': the env's phase word
+  // travels through HBM like the summary words, and every field is read through the kernel-argument segment where it is used
+  int8_t* pair_phase;            // [n] 0 forward, anything else reset; the network of the phase starts at pol.params (+ the member's offset) + phase * pair_stride
+  int32_t* pair_sip;             // [n] steps the env has spent in its phase
+  int64_t pair_stride;           // floats between the two agents' rows (a multiple of 4)
+  const double* pair_goal;       // NULL or the table [pair_goal_rows, 2] of backward goals: entering the reset phase, a drawn row of it becomes the env's st.goal row
+  int pair_goal_rows;            // (1 for pair->backward_goal, the table of one row; 0 with pair_goal == NULL)
+  int pair_sos;                  // switch_on_success
+  int pair_se[2];                // switch_every
+  int8_t* pair_agent;            // NULL or [T, n]
+  int32_t* pair_fs;              // NULL or [n]: forward phases that ended by success (step 0 of the launch starts them at 0)
+  int32_t* pair_bs;              // NULL or [n]: reset phases that ended by success
+  int32_t* pair_row;             // NULL or [n]: earl_backward_goals.row
+  int32_t* pair_row_out;         // NULL or [T, n]: earl_backward_goals.row_out
 };
 static_assert(std::is_standard_layout<MinitaurArgs>::value && std::is_trivially_copyable<MinitaurPolicyArgs>::value, "the policy phase reads MinitaurPolicyArgs as laid out in the kernel-argument segment");
 #include "policy_lane_group.h"
@@ -77,6 +91,15 @@ __device__ __noinline__ float minitaur_policy_action(const uint64_t ka_bits, con
   const float* w = ka->pol.params;
   const int pop_G = ka->pop_G;
   if (pop_G > 0) w += (size_t)(gid / (uint32_t)pop_G) * (size_t)ka->pop_stride;
+  // an agent pair: the network of the env's phase, the word lane 0 stored after the last handover decision (a wave whose two envs are in two phases walks two sets of
+  // rows, like a wave of two members).  A group that is not live reads the word of the env it shadows
+  const int8_t* pair_phase = ka->pair_phase;
+  if (pair_phase) {
+    const int ph = pair_phase[env] != 0 ? 1 : 0;
+    if (ph) w += (size_t)ka->pair_stride;
+    int8_t* agent_out = ka->pair_agent;
+    if (sub == 0 && live && agent_out) agent_out[row] = (int8_t)ph;
+  }
   pol_layer<32, true>(w, w + (size_t)d1 * 32, 32, d1, hidden_act, sub, h);
   w += (size_t)d1 * (32 + 1);
   if (n_layers == 3) {
@@ -128,6 +151,57 @@ __device__ __forceinline__ void mt_step_action(const A& a, const int t, const in
 #pragma unroll
     for (int k = 0; k < 8; ++k) a64[k] = earl::mt_clipd((double)a.action[row * 8 + k], -1.01, 1.01);      // (the front end raises beyond the reference's bound)
   }
+}
+// The agent pair's handover after env step t (include/earl_physics.h, earl_minitaur_agents_rollout, items 5 and 6), worked out by all 32 lanes of the env from the same
+// words: the step's success flag from lane 0, phase and steps_in_phase from HBM, where lane 0 stores them again -- nothing of the pair lives across a timestep.  The
+// pair's kernel arguments are read through the kernel-argument segment here, where they are used (see minitaur_policy_action on why).  A handover that changes the goal
+// leaves the new one in goal0 / goal1 and in the env's row of st.goal, and patches entries 30 / 31 of the row the env emitted at this step, as the lifelong switch does
+// (which a pair launch never runs: goal_change_frequency > 0 is refused).  Called by the policy kernels only; `a`'s own members are MinitaurArgs'
+template <class A>
+__device__ __forceinline__ void mt_pair_handover(const A& a, const int t, const int env, const size_t row, const int sub, const bool live, const bool failed, const uint8_t suc,
+                                                 double& goal0, double& goal1) {
+#pragma clang fp contract(off)
+  const EARL_KARG void* kp = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  const EARL_KARG MinitaurPolicyArgs* ka = (const EARL_KARG MinitaurPolicyArgs*)kp;
+  int8_t* const pair_phase = ka->pair_phase;
+  if (!pair_phase) return;                               // (wave-uniform)
+  int32_t* const pair_sip = ka->pair_sip;
+  const bool by_s = ka->pair_sos != 0 && __shfl((int)((!failed && suc) ? 1 : 0), 0, 32) != 0;
+  int ph = pair_phase[env] != 0 ? 1 : 0;
+  int sip = pair_sip[env] + 1;                           // (a rolled-back step counts, with success 0)
+  const bool over = by_s || sip >= (ph ? ka->pair_se[1] : ka->pair_se[0]);
+  int32_t* const row_at = ka->pair_row_out;
+  if (sub == 0 && live) {
+    int32_t* const fs = ka->pair_fs;
+    int32_t* const bs = ka->pair_bs;
+    if (fs) fs[env] = (t > 0 ? fs[env] : 0) + ((by_s && ph == 0) ? 1 : 0);      // (a step where the clock ran out as well counts as ended by success)
+    if (bs) bs[env] = (t > 0 ? bs[env] : 0) + ((by_s && ph != 0) ? 1 : 0);
+    if (row_at) row_at[row] = -1;                        // overwritten below by the same lane on a step that draws
+  }
+  if (over) {
+    ph ^= 1;
+    sip = 0;
+    // entering the reset phase: a row of the backward table, if there is one (draw index 0xFFFD); entering the forward phase: the lifelong switch's draw for this step
+    // (0xFFFE, cfg.goal_table).  The same counter words, u01 and clamp
+    const double* const table = ph ? ka->pair_goal : a.cfg.goal_table;
+    if (table) {
+      const int rows = ph ? ka->pair_goal_rows : a.cfg.n_goals;
+      int gi = (int)(mt_draw(a.cfg, ph ? 0xFFFDu : 0xFFFEu, env, a.cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t) * (double)rows);
+      gi = gi >= rows ? rows - 1 : gi;
+      goal0 = table[2 * gi]; goal1 = table[2 * gi + 1];
+      if (live && sub >= 30) (a.out.obs ? a.out.obs + row * 32 : a.st.last_obs + (size_t)env * 32)[sub] = sub == 30 ? goal0 : goal1;
+      if (live && sub == 0) {
+        a.st.goal[(size_t)env * 2] = goal0; a.st.goal[(size_t)env * 2 + 1] = goal1;
+        if (ph) {
+          int32_t* const row_of = ka->pair_row;
+          if (row_of) row_of[env] = gi;
+          if (row_at) row_at[row] = gi;
+        }
+      }
+    }
+  }
+  if (sub == 0 && live) { pair_phase[env] = (int8_t)ph; pair_sip[env] = sip; }
 }
 template <bool RESET, bool ARROW>
 __global__ __launch_bounds__(64 * mt_wpb<ARROW>(), ARROW ? EARL_MT_BLOCKS : 1) void minitaur_kernel(const MinitaurArgs a) {

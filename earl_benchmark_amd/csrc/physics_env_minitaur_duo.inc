@@ -158,6 +158,7 @@
       a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
     }
     }
+    if constexpr (POLICY) mt_pair_handover(a, t, env, row, sub, live, failed, suc, goal0, goal1);      // earl_minitaur_agents_rollout: the new goal goes to s.ev.goal below and to st.goal
     int sgc = s.ev.sgc;
     fence();
     if (gcf > 0 && ++sgc >= gcf) {                      // LifelongWrapper.step (lifelong_wrapper.py:36-42): new goal, the observation re-read with it

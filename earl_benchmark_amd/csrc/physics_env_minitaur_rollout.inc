@@ -242,6 +242,7 @@
         a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
       }
       }
+      if constexpr (POLICY) mt_pair_handover(a, t, env, row, sub, live, failed, suc, goal0, goal1);      // earl_minitaur_agents_rollout: the pair's state machine and its goal rows
       if (gcf > 0 && ++sgc >= gcf) {                      // LifelongWrapper.step (lifelong_wrapper.py:36-42): new goal, the observation re-read with it
         sgc = 0;
         int gi = (int)(mt_draw(cfg, 0xFFFEu, env, cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t) * (double)cfg.n_goals);

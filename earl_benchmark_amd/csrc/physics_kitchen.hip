@@ -69,10 +69,12 @@ int earl_kitchen_rollout_clocked(const void* model, const earl_collision_model* 
 // include/earl_physics.h: T closed-loop env steps in one launch, the policy evaluated by the 32 lanes that own the env -- one policy or a population's member per env,
 // every [T] output optional, per-env episode summaries.  The launch forms are earl_kitchen_rollout_clocked's, chosen here by the same rule; the kernels are
 // instantiated in physics_kitchen_policy.hip
-int earl_kitchen_population_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
-                                    const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head,
-                                    const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_kitchen_out* out,
-                                    const earl_episode_summary* summary, earl_stream_t stream) {
+// (the body of the closed-loop entry points: a population, summaries, an agent pair with its backward goals and the forward table, each there or not)
+static int kitchen_closed_loop(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                               const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_agent_pair* pair, bool paired,
+                               const earl_backward_goals* goals, const double* forward_goals, int32_t n_forward_goals, const earl_gaussian_head* head,
+                               const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_kitchen_out* out,
+                               const earl_episode_summary* summary, earl_stream_t stream) {
   if (!model || !params || !cfg || !st || !policy || !obs0 || !out || cfg->n < 0 || T < 0 || cfg->n_att < 10 || cfg->n_att > 32 || cfg->frame_skip < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !st->last_qp_robot || !st->att_xpos || !st->steps_since_reset || !st->last_obs) return EARL_ERR_ARG;
   if (!cfg->mocap_quat_dev) return EARL_ERR_ARG;
@@ -81,6 +83,15 @@ int earl_kitchen_population_rollout(const void* model, const earl_collision_mode
   // of 16 envs, every member's rows read in 16-byte pieces
   if (earl::contract::check_policy(*policy, 46, 9, head, earl::contract::kParamsAligned16, nullptr)) return EARL_ERR_ARG;
   if (pop && earl::contract::check_population(*policy, *pop, cfg->env_offset, cfg->n, 16, 4, nullptr)) return EARL_ERR_ARG;
+  const bool forward = paired && forward_goals && n_forward_goals >= 1;
+  if (paired) {
+    // (the kitchen has no lifelong switch of its own: goal_change_frequency 0)
+    if (earl::contract::check_pair(*policy, pair, 0, 4, nullptr)) return EARL_ERR_ARG;
+    if (pop && earl::contract::check_pair_population(*pop, *pair, nullptr)) return EARL_ERR_ARG;
+    if (n_forward_goals < 0) return EARL_ERR_ARG;
+    if (pair->backward_goal && !forward) return EARL_ERR_ARG;      // (the forward goal could not be restored)
+    if (goals && earl::contract::check_backward_goals(*goals, *pair, forward ? n_forward_goals : 0, nullptr)) return EARL_ERR_ARG;
+  }
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "kitchen_policy_rollout")) return rc;
   KitchenPolicyArgs k;
@@ -95,10 +106,39 @@ int earl_kitchen_population_rollout(const void* model, const earl_collision_mode
   k.sum_ret = summary ? summary->ret : nullptr;
   k.sum_last = summary ? summary->success_last : nullptr;
   k.sum_first = summary ? summary->first_success : nullptr;
+  k.pair_phase = paired ? pair->phase : nullptr;
+  k.pair_sip = paired ? pair->steps_in_phase : nullptr;
+  k.pair_stride = paired ? pair->param_stride : 0;
+  k.pair_goal = !paired ? nullptr : (goals ? goals->table : pair->backward_goal);      // (the ONE fixed row: the table of one row)
+  k.pair_goal_rows = !paired ? 0 : (goals ? goals->n_rows : (pair->backward_goal ? 1 : 0));
+  k.pair_fwd = forward ? forward_goals : nullptr;
+  k.pair_fwd_rows = forward ? n_forward_goals : 0;
+  k.pair_se[0] = paired ? pair->switch_every[0] : 0;
+  k.pair_se[1] = paired ? pair->switch_every[1] : 0;
+  k.pair_sos = paired ? pair->switch_on_success : 0;
+  k.pair_agent = paired ? pair->agent_out : nullptr;
+  k.pair_fs = paired ? pair->forward_success : nullptr;
+  k.pair_bs = paired ? pair->backward_success : nullptr;
+  k.pair_row = paired && goals ? goals->row : nullptr;
+  k.pair_row_out = paired && goals ? goals->row_out : nullptr;
   if (k.solo == 2 && g_solo < 0) k.solo = 3;      // the plain entry point's rule
   if (g_solo < 0 && k.solo == 1 && cfg->n <= 2 * cu_count()) k.solo = 4;
   earl_unit_kitchen_policy_rollout(&k, stream);      // physics_kitchen_policy.hip holds the kernels
   return launched("kitchen_policy_rollout");
+}
+int earl_kitchen_population_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                                    const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head,
+                                    const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_kitchen_out* out,
+                                    const earl_episode_summary* summary, earl_stream_t stream) {
+  return kitchen_closed_loop(model, col, params, cfg, st, policy, pop, nullptr, false, nullptr, nullptr, 0, head, obs0, T, clock, actions, out, summary, stream);
+}
+// include/earl_physics.h: the forward / reset agent pair inside the same launch -- a population of pairs, a table of backward goals, the forward table and summaries
+int earl_kitchen_agents_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                                const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop,
+                                const earl_backward_goals* goals, const double* forward_goals, int32_t n_forward_goals, const earl_gaussian_head* head, const double* obs0,
+                                int32_t T, const uint64_t* clock, float* actions, const earl_kitchen_out* out, const earl_episode_summary* summary, earl_stream_t stream) {
+  return kitchen_closed_loop(model, col, params, cfg, st, policy, pop, pair, true, goals, forward_goals, n_forward_goals, head, obs0, T, clock, actions, out, summary,
+                             stream);
 }
 // one policy, every [T] row kept: the population entry point without a population and without a summary (the same launch, bit for bit)
 int earl_kitchen_policy_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,

@@ -54,9 +54,11 @@ int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_mode
 // include/earl_physics.h: T closed-loop env steps in one launch, the policy evaluated by the 32 lanes that own the env -- one policy or a population's member per env,
 // every [T] output optional, per-env episode summaries.  The launch forms are earl_minitaur_rollout_clocked's (one-wave kernel in its three shapes, two-wave kernel);
 // the generic substep<22> comparison build has no policy form
-int earl_minitaur_population_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
-                                     const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
-                                     const uint64_t* clock, float* actions, const earl_minitaur_out* out, const earl_episode_summary* summary, earl_stream_t stream) {
+// (the body of the closed-loop entry points: a population, summaries, an agent pair and its table of backward goals, each there or not)
+static int minitaur_closed_loop(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_agent_pair* pair, bool paired, const earl_backward_goals* goals,
+                                const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_minitaur_out* out,
+                                const earl_episode_summary* summary, earl_stream_t stream) {
   if (!model24 || !cfg || !st || !out || !policy || !obs0 || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
   if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
   if (!out->obs && !st->last_obs) return EARL_ERR_ARG;    // (without out->obs the env's row of last_obs is the one observation row the launch keeps)
@@ -66,6 +68,12 @@ int earl_minitaur_population_rollout(const void* model24, const earl_collision_m
   // actions must not either: bounded policies only.  A population: groups of 16 envs, every member's rows read in 16-byte pieces
   if (earl::contract::check_policy(*policy, 32, 8, head, earl::contract::kParamsAligned16 | earl::contract::kBoundedOutput, nullptr)) return EARL_ERR_ARG;
   if (pop && earl::contract::check_population(*policy, *pop, cfg->env_offset, cfg->n, 16, 4, nullptr)) return EARL_ERR_ARG;
+  if (paired) {
+    // the pair's handover IS the goal switch of autonomous RL: check_pair refuses goal_change_frequency > 0 (both would draw with index 0xFFFE at the same step)
+    if (earl::contract::check_pair(*policy, pair, cfg->goal_change_frequency, 4, nullptr)) return EARL_ERR_ARG;
+    if (pop && earl::contract::check_pair_population(*pop, *pair, nullptr)) return EARL_ERR_ARG;
+    if (goals && earl::contract::check_backward_goals(*goals, *pair, cfg->n_goals, nullptr)) return EARL_ERR_ARG;
+  }
   if (!g_mt_stepper) return EARL_ERR_ARG;                 // (earl_debug_set_minitaur_stepper(0): no policy form)
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_policy_rollout")) return rc;
@@ -81,12 +89,37 @@ int earl_minitaur_population_rollout(const void* model24, const earl_collision_m
   a.sum_ret = summary ? summary->ret : nullptr;
   a.sum_last = summary ? summary->success_last : nullptr;
   a.sum_first = summary ? summary->first_success : nullptr;
+  a.pair_phase = paired ? pair->phase : nullptr;
+  a.pair_sip = paired ? pair->steps_in_phase : nullptr;
+  a.pair_stride = paired ? pair->param_stride : 0;
+  a.pair_goal = !paired ? nullptr : (goals ? goals->table : pair->backward_goal);      // (the ONE fixed row: the table of one row)
+  a.pair_goal_rows = !paired ? 0 : (goals ? goals->n_rows : (pair->backward_goal ? 1 : 0));
+  a.pair_sos = paired ? pair->switch_on_success : 0;
+  a.pair_se[0] = paired ? pair->switch_every[0] : 0;
+  a.pair_se[1] = paired ? pair->switch_every[1] : 0;
+  a.pair_agent = paired ? pair->agent_out : nullptr;
+  a.pair_fs = paired ? pair->forward_success : nullptr;
+  a.pair_bs = paired ? pair->backward_success : nullptr;
+  a.pair_row = paired && goals ? goals->row : nullptr;
+  a.pair_row_out = paired && goals ? goals->row_out : nullptr;
   if (a.solo == 0 && cfg->num_substeps > 0 && (g_mt_duo > 0 || (g_mt_duo < 0 && mt_use_duo(cfg->n)))) {      // the plain entry point's rule
     minitaur_policy_duo_kernel<<<(unsigned)((cfg->n + 16 * MT_DUO_PAIRS / 4 - 1) / (4 * MT_DUO_PAIRS)), 128 * MT_DUO_PAIRS, 0, (hipStream_t)stream>>>(a);
     return launched("minitaur_policy_rollout (two waves per SIMD)");
   }
   minitaur_policy_kernel<false, true><<<solo_grid(cfg->n, a.solo, EARL_MT_WPB), 64 * EARL_MT_WPB, 0, (hipStream_t)stream>>>(a);
   return launched("minitaur_policy_rollout");
+}
+int earl_minitaur_population_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                     const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
+                                     const uint64_t* clock, float* actions, const earl_minitaur_out* out, const earl_episode_summary* summary, earl_stream_t stream) {
+  return minitaur_closed_loop(model24, col, cfg, st, policy, pop, nullptr, false, nullptr, head, obs0, T, clock, actions, out, summary, stream);
+}
+// include/earl_physics.h: the forward / reset agent pair inside the same launch -- a population of pairs, a table of backward goals and summaries, each NULL or given
+int earl_minitaur_agents_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                 const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop, const earl_backward_goals* goals,
+                                 const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_minitaur_out* out,
+                                 const earl_episode_summary* summary, earl_stream_t stream) {
+  return minitaur_closed_loop(model24, col, cfg, st, policy, pop, pair, true, goals, head, obs0, T, clock, actions, out, summary, stream);
 }
 // one policy, every [T] row kept: the population entry point without a population and without a summary (the same launch, bit for bit)
 int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,

@@ -120,6 +120,10 @@ class Kitchen:
     self.action_space = Box(-1.0, 1.0, (self.N_ROBOT,), np.float32)              # kitchen_multitask_v0.py:78-80
     self._last_success = torch.zeros(n, dtype=torch.bool, device=dev)
     self._last_obs_stale = False      # last_obs no longer describes (state, goal): set by set_state() / reset_goal(), cleared by whatever rewrites every row
+    self.agent_phase = self.steps_in_phase = None      # the agent pair's per-env state (rollout_pair allocates it: 0 forward / 1 reset, steps spent in the phase)
+    self._pair_counts = None
+    self.backward_row = None          # [N] int32 once a pair launch has drawn from a table of backward goals: the row each env's reset goal came from, -1 = none yet
+    self._forward_goals = torch.tensor(np.atleast_2d(self._goal_states), **kw).reshape(-1, 23).contiguous()      # [R, 23]: what a pair's forward entry draws from
     self.observation_space = Box(-8.0, 8.0, (self.OBS_DIM,), np.float64)         # :82-84
     with torch.cuda.device(dev):
       self._reset_states = self._settle_reset_states()
@@ -185,6 +189,7 @@ class Kitchen:
       self.steps_since_reset[m] = 0
       self.steps_since_goal_change[m] = 0
       self.interventions += m.to(torch.int32)
+      closed_loop.reset_pair_state(self, None if mask is None else m)      # (a reset env starts with the forward agent)
       # set_state -> sim.forward(): site positions of the reset state (nothing integrated)
       self.att.copy_(self.model.forward(self.qpos, self.qvel, self.mocap_pos, self.mocap_quat, torch.zeros(n, 2, dtype=torch.float64, device=self.device))[2])
       prev = self.last_obs.clone()
@@ -360,20 +365,44 @@ class Kitchen:
       raise NotImplementedError(f'{who}: a PolicyPopulation on the kitchen goes to rollout_population / evaluate_population ({who} takes one MLPPolicy / '
                                 'GaussianMLPPolicy per launch)')
     if isinstance(policy, AgentPair):
-      raise NotImplementedError(f'{who}: an AgentPair on the kitchen is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
+      raise NotImplementedError(f'{who}: an AgentPair on the kitchen goes to rollout_pair / evaluate_pair ({who} takes one policy per env and launch)')
     if self.scalar_api:
       raise ValueError(f'{who}: scalar_api returns one env\'s numpy rows; the closed-loop launch returns batched tensors (Kitchen(..., scalar_api=False))')
     if int(self._cfg.goal_change_frequency) > 0:
       raise ValueError(f'{who}: the kitchen\'s lifelong goal switch runs on the host (goal_change_frequency > 0) and cannot happen inside the launch, as make_step_graph says')
     return require_widths(policy, who, self.OBS_DIM, self.N_ROBOT, env=self)
 
-  def _launch_policy(self, policy, head, obs0, T, out, summary=None):
+  def _check_pair(self, pair, who):
+    """-> is it Gaussian; `pair`: an AgentPair or a PairPopulation of this env's widths on this env's device; batched tensors only, and no LifelongWrapper"""
+    from ..policy import require_widths
+    if self.scalar_api:
+      raise ValueError(f'{who}: scalar_api returns one env\'s numpy rows; the closed-loop launch returns batched tensors (Kitchen(..., scalar_api=False))')
+    if int(self._cfg.goal_change_frequency) > 0:
+      raise ValueError(f'{who}: the kitchen\'s lifelong goal switch runs on the host (goal_change_frequency > 0) and cannot happen inside the launch, as make_step_graph says')
+    return require_widths(pair, who, self.OBS_DIM, self.N_ROBOT, env=self, pair=True, pairs=True)
+
+  @property
+  def initial_states(self):
+    """get_init_states(): the rows an AgentPair's backward_goal='initial_states' draws from ('initial' wants ONE row)"""
+    return np.atleast_2d(self.get_init_states())
+
+  def _launch_policy(self, policy, head, obs0, T, out, summary=None, pair=None):
     """hook of physics_policy_rollout: earl_kitchen_population_rollout (a single policy: pop = NULL, which is earl_kitchen_policy_rollout bit for bit); `out` may lack
-    any key, 'obs' included (the env's row of last_obs then carries the observation); summary: None or an _abi.EpisodeSummary.  The sensor-noise counter advances by T"""
+    any key, 'obs' included (the env's row of last_obs then carries the observation); summary: None or an _abi.EpisodeSummary; pair: None, or what
+    physics_policy_rollout.pair_structs returns (earl_kitchen_agents_rollout, the forward table being the env's goal states).  The sensor-noise counter advances by T"""
     ptr = lambda k: None if out.get(k) is None else out[k].data_ptr()
+    ref = lambda s: None if s is None else C.byref(s)
     o = _abi.KitchenOut(obs=ptr('obs'), reward=ptr('reward'), done=ptr('done'), success=ptr('success'), status=ptr('status'))
     pop = getattr(policy, 'pop_struct', None)              # a PolicyPopulation: the env with global id g runs member g // envs_per_policy
     self._cfg.counter = self._counter
+    if pair is not None:
+      with torch.cuda.device(self.device):
+        _abi.check(self._lib.earl_kitchen_agents_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._params), C.byref(self._cfg), C.byref(self._st),
+                                                         C.byref(policy.struct), C.byref(pair[0]), ref(pair[1]), ref(pair[2]), self._forward_goals.data_ptr(),
+                                                         int(self._forward_goals.shape[0]), ref(head), obs0.data_ptr(), T, None, ptr('actions'), C.byref(o), ref(summary),
+                                                         self._stream()), 'earl_kitchen_agents_rollout')
+      self._counter += T
+      return
     with torch.cuda.device(self.device):
       _abi.check(self._lib.earl_kitchen_population_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._params), C.byref(self._cfg), C.byref(self._st),
                                                            C.byref(policy.struct), None if pop is None else C.byref(pop), None if head is None else C.byref(head),
@@ -389,7 +418,26 @@ class Kitchen:
     return closed_loop.rollout_policy(self, policy, T, reset_first, sample, return_noise, out)
 
   def rollout_agents(self, pair, T, **kw):
-    raise NotImplementedError('rollout_agents: an AgentPair on the kitchen is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
+    raise NotImplementedError('rollout_agents: an AgentPair on the kitchen goes to rollout_pair / evaluate_pair (rollout_agents is the tabletop\'s, the Sawyer door\'s '
+                              'and the Sawyer peg\'s name for it)')
+
+  def rollout_pair(self, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
+    """physics_policy_rollout.rollout_pair (its docstring is the contract) on earl_kitchen_agents_rollout: `pair` -- an `AgentPair(..., obs_dim=46, act_dim=9)` or a
+    `PairPopulation` of them.  A goal row is a qpos of 23 values; backward_goal='initial_states' is the table of get_init_states() (the reference resets from its six
+    'all_pairs' rows), 'initial' its one row where there is one; entering the forward phase the goal becomes a row of the env's goal states.  Batched tensors only
+    (scalar_api=False), not under a LifelongWrapper.
+    -> rollout_policy()'s dict plus 'agent' [T, N] int8 and, with a table of backward goals, 'backward_row' [T, N] int32"""
+    return closed_loop.rollout_pair(self, pair, T, reset_first, sample, return_noise, out)
+
+  def evaluate_pair(self, pair, T, sample=True):
+    """physics_policy_rollout.evaluate_pair on earl_kitchen_agents_rollout: T steps of `pair` from the current state with per-env summaries only.
+    -> {'ret', 'success', 'first_success', 'guard_steps', 'forward_success', 'backward_success'}, each [N]"""
+    return closed_loop.evaluate_pair(self, pair, T, sample)
+
+  @property
+  def pair_counts(self):
+    """(forward_success, backward_success) [N] int32 of the last pair launch: the phases that ended by success; None before the first"""
+    return self._pair_counts
 
   def evaluate_policy(self, policy, T, **kw):
     raise NotImplementedError('evaluate_policy: episode summaries on the kitchen are evaluate_population\'s (it takes one policy as well as a PolicyPopulation); '
@@ -473,7 +521,10 @@ class Kitchen:
     keys = ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'last_qp_robot', 'att', 'steps_since_reset', 'interventions', 'fail_count', 'lifelong_return_t',
             'steps_since_goal_change', 'last_obs')
     return {k: getattr(self, k).clone() for k in keys} | {'counter': self._counter, 'total_step_count': self.total_step_count,
-                                                          'last_obs_stale': bool(self._last_obs_stale)}
+                                                          'last_obs_stale': bool(self._last_obs_stale)} | {
+                                                              k: getattr(self, k).clone() for k in self._PAIR_STATE if getattr(self, k) is not None}
+
+  _PAIR_STATE = ('agent_phase', 'steps_in_phase', 'backward_row')      # in the dict once a pair launch has allocated them, and only then
 
   def load_state_dict(self, sd):
     self._last_obs_stale = bool(sd.get('last_obs_stale', False))      # (a dict written before the flag existed: not stale)
@@ -484,5 +535,7 @@ class Kitchen:
         self._counter = int(v)
       elif k == 'total_step_count':
         self.total_step_count = int(v)
+      elif k in self._PAIR_STATE:
+        setattr(self, k, v.to(self.device).clone())
       else:
         getattr(self, k).copy_(v)

@@ -105,6 +105,9 @@ class Minitaur:
     self.observation_space = Box(-np.inf, np.inf, (self.OBS_DIM,), np.float32)        # :179, :481-488
     self._counter = 0
     self._last_success = torch.zeros(n, dtype=torch.bool, device=dev)
+    self.agent_phase = self.steps_in_phase = None      # the agent pair's per-env state (rollout_pair allocates it: 0 forward / 1 reset, steps spent in the phase)
+    self._pair_counts = None
+    self.backward_row = None          # [N] int32 once a pair launch has drawn from a table of backward goals: the row each env's reset goal came from, -1 = none yet
     self._last_obs_stale = False      # last_obs no longer describes (state, goal): set by set_state() / reset_goal(), cleared by whatever rewrites every row
     self.reset()
     self.interventions.zero_()
@@ -139,6 +142,7 @@ class Minitaur:
       _abi.check(self._lib.earl_minitaur_reset(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st),
                                                None if m is None else m.data_ptr(), obs.data_ptr(), self._stream()), 'earl_minitaur_reset')
       self.interventions += 1 if m is None else m.to(torch.int32)
+      closed_loop.reset_pair_state(self, m)                # (a reset env starts with the forward agent)
     if m is None:
       self._last_obs_stale = False
     self._counter += 1
@@ -176,16 +180,38 @@ class Minitaur:
       raise NotImplementedError(f'{who}: a PolicyPopulation on the minitaur goes to rollout_population / evaluate_population ({who} takes one MLPPolicy / '
                                 'GaussianMLPPolicy per launch)')
     if isinstance(policy, AgentPair):
-      raise NotImplementedError(f'{who}: an AgentPair on the minitaur is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
+      raise NotImplementedError(f'{who}: an AgentPair on the minitaur goes to rollout_pair / evaluate_pair ({who} takes one policy per env and launch)')
     return require_widths(policy, who, OBS_DIM, ACT_DIM, env=self, bounded=ACTION_BOUND + ACTION_EPS)
 
-  def _launch_policy(self, policy, head, obs0, T, out, summary=None):
+  def _check_pair(self, pair, who):
+    """-> is it Gaussian; `pair`: an AgentPair or a PairPopulation of this env's widths on this env's device whose output is bounded, and no LifelongWrapper"""
+    from ..policy import require_widths
+    gaussian = require_widths(pair, who, OBS_DIM, ACT_DIM, env=self, pair=True, bounded=ACTION_BOUND + ACTION_EPS, pairs=True)
+    if self._cfg.goal_change_frequency > 0:
+      raise ValueError(f'{who}: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
+                       'not under a LifelongWrapper (goal_change_frequency > 0), whose clock would fight the pair\'s over the same draw')
+    return gaussian
+
+  @property
+  def initial_states(self):
+    """[1, 2]: where the reset pose stands (x, y), the goal row an AgentPair's backward_goal='initial' resolves to"""
+    return self._reset_qpos[:2].cpu().numpy().reshape(1, 2)
+
+  def _launch_policy(self, policy, head, obs0, T, out, summary=None, pair=None):
     """hook of physics_policy_rollout: earl_minitaur_population_rollout (a single policy: pop = NULL, which is earl_minitaur_policy_rollout bit for bit); `out` may
-    lack any key, 'obs' included (the env's row of last_obs then carries the observation); summary: None or an _abi.EpisodeSummary"""
+    lack any key, 'obs' included (the env's row of last_obs then carries the observation); summary: None or an _abi.EpisodeSummary; pair: None, or what
+    physics_policy_rollout.pair_structs returns (earl_minitaur_agents_rollout)"""
     self._cfg.step_counter = self.total_step_count
     ptr = lambda k: None if out.get(k) is None else out[k].data_ptr()
+    ref = lambda s: None if s is None else C.byref(s)
     o = _abi.MinitaurOut(obs=ptr('obs'), reward=ptr('reward'), done=ptr('done'), success=ptr('success'), status=ptr('status'))
     pop = getattr(policy, 'pop_struct', None)              # a PolicyPopulation: the env with global id g runs member g // envs_per_policy
+    if pair is not None:
+      with torch.cuda.device(self.device):
+        _abi.check(self._lib.earl_minitaur_agents_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), C.byref(policy.struct),
+                                                          C.byref(pair[0]), ref(pair[1]), ref(pair[2]), ref(head), obs0.data_ptr(), T, None, ptr('actions'), C.byref(o),
+                                                          ref(summary), self._stream()), 'earl_minitaur_agents_rollout')
+      return
     with torch.cuda.device(self.device):
       _abi.check(self._lib.earl_minitaur_population_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), C.byref(policy.struct),
                                                             None if pop is None else C.byref(pop), None if head is None else C.byref(head), obs0.data_ptr(), T, None,
@@ -199,7 +225,25 @@ class Minitaur:
     return closed_loop.rollout_policy(self, policy, T, reset_first, sample, return_noise, out)
 
   def rollout_agents(self, pair, T, **kw):
-    raise NotImplementedError('rollout_agents: an AgentPair on the minitaur is not offered (the forward / reset pair runs on the tabletop, the Sawyer door and the Sawyer peg)')
+    raise NotImplementedError('rollout_agents: an AgentPair on the minitaur goes to rollout_pair / evaluate_pair (rollout_agents is the tabletop\'s, the Sawyer door\'s '
+                              'and the Sawyer peg\'s name for it)')
+
+  def rollout_pair(self, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
+    """physics_policy_rollout.rollout_pair (its docstring is the contract) on earl_minitaur_agents_rollout: `pair` -- an `AgentPair(..., obs_dim=32, act_dim=8)` of
+    bounded agents or a `PairPopulation` of them.  A goal row is (x, y); backward_goal='initial' is the reset pose's, and entering the forward phase the goal becomes a
+    row of the env's twelve goal locations.  Not under a LifelongWrapper.
+    -> rollout_policy()'s dict plus 'agent' [T, N] int8 and, with a table of backward goals, 'backward_row' [T, N] int32"""
+    return closed_loop.rollout_pair(self, pair, T, reset_first, sample, return_noise, out)
+
+  def evaluate_pair(self, pair, T, sample=True):
+    """physics_policy_rollout.evaluate_pair on earl_minitaur_agents_rollout: T steps of `pair` from the current state with per-env summaries only.
+    -> {'ret', 'success', 'first_success', 'guard_steps', 'forward_success', 'backward_success'}, each [N]"""
+    return closed_loop.evaluate_pair(self, pair, T, sample)
+
+  @property
+  def pair_counts(self):
+    """(forward_success, backward_success) [N] int32 of the last pair launch: the phases that ended by success; None before the first"""
+    return self._pair_counts
 
   def evaluate_policy(self, policy, T, **kw):
     raise NotImplementedError('evaluate_policy: episode summaries on the minitaur are evaluate_population\'s (it takes one policy as well as a PolicyPopulation); '
@@ -319,10 +363,12 @@ class Minitaur:
 
   _STATE = ('qpos', 'qvel', 'goal_t', 'motor_param', 'observed_torque', 'overheat', 'motor_enabled', 'steps_since_reset', 'steps_since_goal_change',
             'interventions', 'fail_count', 'lifelong_return_t', 'last_obs')
+  _PAIR_STATE = ('agent_phase', 'steps_in_phase', 'backward_row')      # in the dict once a pair launch has allocated them, and only then
 
   def state_dict(self):
     return {k: getattr(self, k).clone() for k in self._STATE} | {'counter': self._counter, 'total_step_count': self.total_step_count,
-                                                                 'last_obs_stale': bool(self._last_obs_stale)}
+                                                                 'last_obs_stale': bool(self._last_obs_stale)} | {
+                                                                     k: getattr(self, k).clone() for k in self._PAIR_STATE if getattr(self, k) is not None}
 
   def load_state_dict(self, sd):
     self._last_obs_stale = bool(sd.get('last_obs_stale', False))      # (a dict written before the flag existed: not stale)
@@ -333,5 +379,7 @@ class Minitaur:
         self._counter = int(v)
       elif k == 'total_step_count':
         self.total_step_count = int(v)
+      elif k in self._PAIR_STATE:
+        setattr(self, k, v.to(self.device).clone())
       else:
         getattr(self, k).copy_(v)

@@ -3,7 +3,9 @@ with a policy inside it (include/earl_physics.h: earl_sawyer_population_rollout,
 hooks: `_check_policy(policy, who)` -> is it Gaussian (policy.require_widths with the env's widths and rules), `_new_out((T,))`, `reset()`, `last_obs` /
 `_last_obs_stale` / `_get_obs_t()`, and `_launch_policy(policy, head, obs0, T, out)`: the launch itself.  The minitaur and the kitchen also share `rollout_population`
 and `evaluate` below: their `_check_policy` takes `population=True` (a PolicyPopulation is then taken, require_widths checking its members against the env's global
-ids) and their `_launch_policy` takes `summary=` (None or an _abi.EpisodeSummary) and an `out` that may lack any key.
+ids) and their `_launch_policy` takes `summary=` (None or an _abi.EpisodeSummary) and an `out` that may lack any key.  `rollout_pair` / `evaluate_pair` below are the
+forward / reset agent pair of such an env (earl_minitaur_agents_rollout, earl_kitchen_agents_rollout): its hooks are `_check_pair(pair, who)` -> is it Gaussian and `_launch_policy(..., pair=)`,
+which takes what `pair_structs` returns.
 
 What rollout_policy promises, for every such env (A = the env's action width): closed loop in ONE launch of the rollout kernel, `policy` evaluated between the env
 steps by the lanes that own the env: observation -> float32 MLP -> action -> env step.
@@ -103,3 +105,99 @@ def evaluate(env, who, policy, T, episodes=1, sample=False, reset_first=True):
       finish(env, T, ret[e], succ[e])
       guard[e] = env.fail_count - before
   return {'ret': ret, 'success': succ, 'first_success': first, 'guard_steps': guard}
+
+
+# ---------------------------------------------------------------------------------------------------------------- the forward / reset agent pair
+def pair_structs(env, pair, out):
+  """the pair's per-env state (`env.agent_phase`, `env.steps_in_phase`, with a table `env.backward_row`: allocated at their first use) and the structs of one launch
+  -> (_abi.AgentPair, population struct or None, _abi.BackwardGoals or None), (forward_success, backward_success)"""
+  import ctypes as C
+  from .. import _abi
+  ptr = lambda t: None if t is None else t.data_ptr()
+  n, kw = env.num_envs, dict(device=env.device)
+  table = pair.goal_table(env)
+  goal = None if table is not None else pair.goal_row(env)
+  with torch.cuda.device(env.device):
+    if env.agent_phase is None:
+      env.agent_phase = torch.zeros(n, dtype=torch.int8, **kw)
+      env.steps_in_phase = torch.zeros(n, dtype=torch.int32, **kw)
+    if table is not None and env.backward_row is None:
+      env.backward_row = torch.full((n,), -1, dtype=torch.int32, **kw)
+    fwd, bwd = torch.empty(n, dtype=torch.int32, **kw), torch.empty(n, dtype=torch.int32, **kw)
+  ps = _abi.AgentPair(switch_every=(C.c_int32 * 2)(*pair.switch_every), switch_on_success=int(pair.switch_on_success), pad_=0, param_stride=pair.pair_stride,
+                      backward_goal=ptr(goal), phase=env.agent_phase.data_ptr(), steps_in_phase=env.steps_in_phase.data_ptr(),
+                      agent_out=ptr(out.get('agent')), forward_success=fwd.data_ptr(), backward_success=bwd.data_ptr())
+  goals = None if table is None else _abi.BackwardGoals(table=table.data_ptr(), n_rows=int(table.shape[0]), pad_=0, row=env.backward_row.data_ptr(),
+                                                        row_out=ptr(out.get('backward_row')))
+  return (ps, getattr(pair, 'pop_struct', None), goals, (goal, table)), (fwd, bwd)      # (goal, table: kept alive until the launch is issued)
+
+
+def reset_pair_state(env, mask=None):
+  """reset() of the (masked) envs: a reset env starts with the forward agent, and its reset goal came from no row yet"""
+  if env.agent_phase is not None:
+    if mask is None:
+      env.agent_phase.zero_()
+      env.steps_in_phase.zero_()
+    else:
+      env.agent_phase.masked_fill_(mask.bool(), 0)
+      env.steps_in_phase.masked_fill_(mask.bool(), 0)
+  if env.backward_row is not None:
+    if mask is None:
+      env.backward_row.fill_(-1)
+    else:
+      env.backward_row.masked_fill_(mask.bool(), -1)
+
+
+def rollout_pair(env, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
+  """The forward / reset agent pair of autonomous RL alternating inside ONE launch of the env's rollout kernel (include/earl_physics.h: earl_minitaur_agents_rollout,
+  earl_kitchen_agents_rollout):
+  `pair` -- an `AgentPair` of the env's widths or a `PairPopulation` of them (the env with global id g runs pair g // envs_per_policy) -- drives every env by the agent
+  of its phase (`env.agent_phase`: 0 forward, 1 reset; `env.steps_in_phase`) and hands it over after pair.switch_every[phase] steps or, with pair.switch_on_success,
+  after a step whose success flag is set.  Entering the reset phase the env's goal becomes pair.backward_goal ('initial': the one row of `env.initial_states`; None: the
+  goal stays) or, with a table of backward goals (an array [R, goal_dim], or 'initial_states'), a row of it drawn from the env's counter-based RNG (seed, global id,
+  step: draw index 0xFFFD); entering the forward phase it becomes a row of the env's forward goal table, drawn as the lifelong switch draws.  `goal_t` IS the goal in
+  force and stays as the launch leaves it.
+  -> rollout_policy()'s dict plus 'agent' [T, N] int8 (the agent that computed the action) and, with a table, 'backward_row' [T, N] int32 (the row drawn at that step,
+  -1 elsewhere; `env.backward_row` [N]: the row each env's reset goal came from, -1 before its first entry and after its reset).
+  Bookkeeping, the first observation, sample / return_noise and reset_first as rollout_policy.  `env.pair_counts`: the phases of this launch that ended by success."""
+  gaussian = env._check_pair(pair, 'rollout_pair')
+  n, kw = env.num_envs, dict(device=env.device)
+  T, out, head, obs0 = prepare(env, 'rollout_pair', pair, gaussian, T, reset_first, sample, return_noise, out, what='Gaussian agents (MLPPolicy agents are deterministic)')
+  with torch.cuda.device(env.device):
+    if 'agent' not in out:
+      out['agent'] = torch.empty(T, n, dtype=torch.int8, **kw)
+    if pair.goal_table(env) is not None and 'backward_row' not in out:
+      out['backward_row'] = torch.empty(T, n, dtype=torch.int32, **kw)
+  structs, counts = pair_structs(env, pair, out)
+  env._launch_policy(pair, head, obs0, T, out, pair=structs)
+  finish(env, T, out['reward'], out['success'][-1])
+  env._pair_counts = counts
+  return out
+
+
+def evaluate_pair(env, pair, T, sample=True):
+  """T steps of `pair` -- an `AgentPair` or a `PairPopulation` -- continuing from the current state, as rollout_pair runs them, in ONE launch that writes only per-env
+  summaries (`actions` and every [T] pointer NULL; the env's row of last_obs carries the observation): no tensor with a T axis is allocated.
+  -> {'ret': [N] float64 (the step rewards summed t ascending, each against the goal in force during its step), 'success': [N] bool success at the last step,
+      'first_success': [N] int32 first successful step or -1, 'guard_steps': [N] int32 steps the failure guard rolled back, 'forward_success' / 'backward_success':
+      [N] int32 phases that ended by success (`env.pair_counts`)}: each equals its definition applied to what rollout_pair would have returned.
+  State and bookkeeping end as after rollout_pair.  sample=False: Gaussian agents at their mean."""
+  from .. import _abi
+  gaussian = env._check_pair(pair, 'evaluate_pair')
+  if not gaussian and not sample:
+    raise ValueError('evaluate_pair: sample=False needs Gaussian agents (MLPPolicy agents are deterministic)')
+  T, n, kw = int(T), env.num_envs, dict(device=env.device)
+  if T < 1:
+    raise ValueError(f'evaluate_pair: T = {T} < 1')
+  with torch.cuda.device(env.device):
+    ret, succ = torch.empty(n, dtype=torch.float64, **kw), torch.empty(n, dtype=torch.bool, **kw)
+    first = torch.empty(n, dtype=torch.int32, **kw)
+    before = env.fail_count.clone()
+    obs0 = (env._get_obs_t() if env._last_obs_stale else env.last_obs).contiguous()
+  head = pair.head(sample=bool(sample), eps_out=None) if gaussian else None
+  summary = _abi.EpisodeSummary(ret=ret.data_ptr(), success_last=succ.data_ptr(), first_success=first.data_ptr())
+  structs, counts = pair_structs(env, pair, {})
+  env._launch_policy(pair, head, obs0, T, {}, summary=summary, pair=structs)
+  finish(env, T, ret, succ)
+  env._pair_counts = counts
+  return {'ret': ret, 'success': succ, 'first_success': first, 'guard_steps': env.fail_count - before, 'forward_success': counts[0], 'backward_success': counts[1]}

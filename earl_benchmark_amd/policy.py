@@ -197,6 +197,10 @@ class GaussianMLPPolicy(MLPPolicy):
     return torch.tanh(u) if self.squash else u
 
 
+GOAL_DIMS = {(OBS_DIM, ACT_DIM): 6, (14, 4): 7, (32, 8): 2, (46, 9): 23}      # width of an AgentPair's backward goal by the agents' widths
+PAIR_POPULATION_WIDTHS = ((14, 4), (32, 8), (46, 9))                          # the envs whose pair launch takes a population of pairs
+
+
 def require_widths(policy, who, obs_dim, act_dim, env=None, pair=False, bounded=None, pairs=False):
   """The one check of a policy against the widths it is to have -> is it Gaussian.  env=None: a container of declared widths (the tabletop's 12 -> .. -> 3 unless
   said otherwise) takes networks of those widths only.  env given (its `device`, `num_envs`, `_cfg.env_offset`): a launch of `who` on that env -- the type (an
@@ -360,12 +364,14 @@ class AgentPair:
   a row of 7 values in the Sawyer goal format, the rows are padded to a stride of whole 16-byte pieces as PolicyPopulation's, and no width limit applies (the weights
   are read from memory at every step).  There backward_goal may also be a TABLE [R, 7], R >= 2 (kept as `.backward_goals`; `.backward_goal` is then None), or
   'initial_states' (the env's `initial_states`, resolved at launch: the peg's fifteen rows, the door's one, which behaves as 'initial'): at every entry into the
-  reset phase the env's goal is a row of the table drawn from the env's counter-based RNG (earl_sawyer_agents_rollout; `env.backward_row`)."""
+  reset phase the env's goal is a row of the table drawn from the env's counter-based RNG (earl_sawyer_agents_rollout; `env.backward_row`).
+  32 / 8 is the minitaur and 46 / 9 the kitchen (earl_minitaur_agents_rollout, earl_kitchen_agents_rollout; `env.rollout_pair`): the same rules with a goal row of 2
+  values (x, y; 'initial' is the reset pose's) and of 23 (a qpos; 'initial_states' is the table of `get_init_states()`, 'initial' its one row where there is one)."""
 
   def __init__(self, forward, backward, switch_every=200, switch_on_success=True, backward_goal='initial', device=None, obs_dim=OBS_DIM, act_dim=ACT_DIM):
     self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
     tabletop = (self.obs_dim, self.act_dim) == (OBS_DIM, ACT_DIM)
-    self.goal_dim = 6 if tabletop else 7
+    self.goal_dim = GOAL_DIMS.get((self.obs_dim, self.act_dim), 7)      # the env's goal row: 6 tabletop, 7 Sawyer door / peg, 2 minitaur (x, y), 23 kitchen (a qpos)
     members = [forward, backward]
     if not all(isinstance(m, MLPPolicy) for m in members):
       raise ValueError('AgentPair: forward and backward are MLPPolicy / GaussianMLPPolicy')
@@ -438,7 +444,7 @@ class AgentPair:
       return self._goals_dev
     if not (isinstance(self.backward_goal, str) and self.backward_goal == 'initial_states'):
       return None
-    rows = np.asarray(env.initial_states, dtype=np.float64).reshape(-1, 7)
+    rows = np.asarray(env.initial_states, dtype=np.float64).reshape(-1, self.goal_dim)
     if len(rows) < 2:
       return None
     if self._initial_states_dev is None or not np.array_equal(self._initial_states_dev[0], rows):      # one upload per (pair, device, table), not one per launch
@@ -452,8 +458,8 @@ class AgentPair:
       return None
     if self._goal_dev is not None:
       return self._goal_dev
-    if self.goal_dim == 7:
-      rows = np.asarray(env.initial_states, dtype=np.float64).reshape(-1, 7)
+    if self.goal_dim != 6:
+      rows = np.asarray(env.initial_states, dtype=np.float64).reshape(-1, self.goal_dim)
       if len(rows) != 1:
         raise ValueError(f"AgentPair: backward_goal='initial' needs ONE initial state and env.initial_states has {len(rows)} rows: pass the row to condition the "
                          'reset agent on (backward_goal=env.initial_states[k])')
@@ -500,7 +506,8 @@ class AgentPair:
 
 class PairPopulation:
   """P forward / reset pairs of ONE architecture, head, switch rule and backward goal behind struct earl_policy_population next to struct earl_agent_pair
-  (earl_sawyer_agents_rollout): `pairs` is a list of `AgentPair` built with obs_dim=14, act_dim=4 -- only the parameters differ.  The env with GLOBAL id g runs pair
+  (earl_sawyer_agents_rollout, earl_minitaur_agents_rollout, earl_kitchen_agents_rollout): `pairs` is a list of `AgentPair` of one env's widths (obs_dim=14,
+  act_dim=4 on the Sawyer door and peg; 32 / 8 on the minitaur; 46 / 9 on the kitchen) -- only the parameters differ.  The env with GLOBAL id g runs pair
   g // envs_per_policy (a multiple of 16).  `.params` [P, 2, stride] float32 holds every pair's rows (0 forward, 1 reset) in MLPPolicy's packing order and is what the
   kernel reads: write into it in place."""
   SHARED = ('gaussian', 'dims', 'hidden_act', 'out_act', 'switch_every', 'switch_on_success')
@@ -515,8 +522,9 @@ class PairPopulation:
       raise ValueError('PairPopulation: a non-empty list of AgentPair')
     t = members[0]
     self.obs_dim, self.act_dim = t.obs_dim, t.act_dim
+    widths = (t.obs_dim, t.act_dim) if (t.obs_dim, t.act_dim) in PAIR_POPULATION_WIDTHS else (14, 4)
     for m in members:
-      require_widths(m, 'PairPopulation', 14, 4)
+      require_widths(m, 'PairPopulation', *widths)
     for p, m in enumerate(members):
       for what in self.SHARED:
         if getattr(m, what) != getattr(t, what):
@@ -591,11 +599,12 @@ class PairPopulation:
       for k, n in zip(self.dims[:-1], self.dims[1:]):
         layers.append((row[at:at + n * k].reshape(n, k).clone(), row[at + n * k:at + n * k + n].clone()))
         at += n * k + n
-      agents.append(GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, obs_dim=14, act_dim=4)
-                    if self.gaussian else MLPPolicy(layers, t.hidden_act, t.out_act, obs_dim=14, act_dim=4))
+      agents.append(GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, obs_dim=self.obs_dim,
+                                      act_dim=self.act_dim)
+                    if self.gaussian else MLPPolicy(layers, t.hidden_act, t.out_act, obs_dim=self.obs_dim, act_dim=self.act_dim))
     goal = self.backward_goals if self.backward_goals is not None else self.backward_goal
     return AgentPair(agents[0], agents[1], switch_every=self.switch_every, switch_on_success=self.switch_on_success, backward_goal=goal, device=self.device,
-                     obs_dim=14, act_dim=4)
+                     obs_dim=self.obs_dim, act_dim=self.act_dim)
 
   def policy_index(self, global_ids):
     """the pair each GLOBAL env id runs"""

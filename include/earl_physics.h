@@ -371,7 +371,8 @@ int earl_sawyer_pair_rollout(const earl_link_model* model, const earl_collision_
  * 2 * pair->param_stride; goals with a NULL table or n_rows < 1, goals together with pair->backward_goal != NULL, goals with cfg->n_goal_rows == 0 (the forward goal
  * could not be restored). */
 typedef struct earl_backward_goals {
-  const double* table;   /* device, [n_rows, 7], Sawyer goal format (a row of st->goal) */
+  const double* table;   /* device, [n_rows, W], a row of the env's st->goal: W = 7 on the Sawyer door and peg (the Sawyer goal format), 2 on the minitaur (x, y),
+                            23 on the kitchen (a qpos) */
   int32_t  n_rows;       /* >= 1 */
   int32_t  pad_;
   int32_t* row;          /* NULL or [n], caller-owned: the table row the env's reset goal came from; written at every entry into the reset phase, never read */
@@ -447,7 +448,7 @@ typedef struct earl_kitchen_cfg {
 typedef struct earl_kitchen_state {
   double* qpos; double* qvel;    /* [n, 23] */
   double* mocap_pos;             /* [n, 3] */
-  const double* goal;            /* [n, 23] */
+  double* goal;                  /* [n, 23] the goal in force; read by every entry point, written by earl_kitchen_agents_rollout only (a handover of the agent pair) */
   double* last_qp_robot;         /* [n, 9] robot joints of the newest (noisy) observation: Robot_VelAct.ctrl_velocity_limits starts from them */
   double* att_xpos;              /* [n, n_att, 3] attachment positions the stepper leaves (kinematics of the last timestep's start) */
   int32_t* steps_since_reset;    /* [n] */
@@ -536,6 +537,45 @@ int earl_kitchen_population_rollout(const void* model24, const earl_collision_mo
                                     const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head,
                                     const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_kitchen_out* out,
                                     const earl_episode_summary* summary, earl_stream_t stream);
+/* ---- the forward / reset AGENT PAIR inside the same launch: a POPULATION of pairs, a TABLE of backward goals, episode SUMMARIES -- each NULL or given ----
+ * earl_agent_pair is earl_tabletop.h's struct and earl_backward_goals the one above, as they are, with the kitchen's sizes: a goal row is 23 doubles (a qpos: a row of
+ * st->goal), pair->backward_goal ONE such row, goals->table [n_rows, 23], forward_goals [n_forward_goals, 23] (device); agent_out [T, n]; forward_success /
+ * backward_success [n] (one launch is one episode).  policy->params is [2, pair->param_stride] -- row 0 the forward agent, row 1 the reset agent, both of policy's
+ * architecture and head -- or, with pop, [P, 2, pair->param_stride] at pop->param_stride.  pair = NULL is refused: it is not an alias of earl_kitchen_population_rollout.
+ * Per env and env step t, in this order (the order is the contract; the six items are earl_sawyer_pair_rollout's):
+ *   1. the action is computed from the observation the env last emitted (earl_kitchen_policy_rollout's rule: obs0 at step 0, afterwards the row of step t - 1 as it
+ *      stands, the goal block a handover patched included) by the network of the env's current `phase` (0 forward, anything else reset) of its member, at
+ *      policy->params + (g / G) * pop->param_stride + phase * pair->param_stride; the arithmetic is unchanged;
+ *   2. with a head, the step's THREE Philox blocks are the ones earl_kitchen_policy_rollout makes ({0x504F4C00 + b, global id, ev}, ev = cfg->counter + clock[0] + t):
+ *      they do not depend on the phase;
+ *   3. agent_out[t n + env], actions and eps_out are written;
+ *   4. the env step runs as in the single-policy kernel, failure guard, rollback and fail_count included; reward and success refer to the goal in force DURING the
+ *      step: the reward reads the goal from the observation as emitted, before any patch;
+ *   5. steps_in_phase += 1 (a rolled-back step counts, with success 0), and the env hands over if (switch_on_success && success) || steps_in_phase >=
+ *      switch_every[phase]: phase ^= 1, steps_in_phase = 0; forward_success / backward_success of the phase that ended is incremented if switch_on_success && success
+ *      (a step where the clock ran out as well counts as ended by success); step 0 of the launch starts both counters at 0.
+ *      Entering the reset phase, the env's row of st->goal becomes pair->backward_goal, or with `goals` table[r], r = min((int)(u01(b.x, b.y) * n_rows), n_rows - 1), where
+ *      b is the Philox4x32-10 block {0xFFFD, global env id, ev lo, ev hi} under key cfg->seed (earl_sawyer_agents_rollout's draw, with this env's ev; the sensor noise
+ *      draws with 0x4B00 + j, the head with 0x504F4C00 + b); goals->row[env] = r and row_out[t n + env] = r at such a step, row_out is -1 at every other step of a live
+ *      env; with neither the goal stays.  Entering the forward phase with forward_goals, it becomes forward_goals[r], r from the 0xFFFE draw of the same form over
+ *      n_forward_goals rows (one row: r = 0 whatever the draw, so a table of one row is a fixed row); without, the goal stays.  Whenever the row changes, entries
+ *      23 .. 45 of this step's emitted observation row are patched, in row t of out->obs if given AND in the env's row of st->last_obs, which the kitchen always keeps:
+ *      the next action sees the new goal, this step's reward used the old one;
+ *   6. phase and steps_in_phase are stored after every env step; in the several-wave forms the env's owner wave does all of this.  st->goal is left as the goal in
+ *      force at launch exit: there is no separate entry rule, and every other entry point keeps working on the state.
+ * Identities: never switching (switch_every > T, switch_on_success = 0) with all envs in phase 0 is bit-identical to earl_kitchen_population_rollout with row 0 of every
+ * member -- outputs, actions, eps, state, fail_count, summary; all envs in phase 1 with no backward goal, to the same with row 1.  pop equals cutting the batch at the
+ * global ids that are multiples of G.  summary equals its definitions.  A `goals` table of ONE row equals pair->backward_goal = that row.  Nothing depends on n, the
+ * shard split, the launch form (all five of earl_debug_set_solo) or how T steps are cut into launches.  actions, every pointer of `out`, the pair's three output pointers
+ * and goals->row / row_out may be NULL.
+ * EARL_ERR_ARG before any HIP call: everything earl_kitchen_population_rollout refuses, the contract's pair rules (csrc/policy_check.h: NULL pair / phase /
+ * steps_in_phase, switch_every < 1, switch_on_success other than 0 / 1, param_stride below the parameter count), param_stride % 4 != 0, pop->param_stride <
+ * 2 * pair->param_stride, goals with a NULL table or n_rows < 1, goals together with pair->backward_goal, n_forward_goals < 0, and a backward goal or table given with
+ * forward_goals == NULL or n_forward_goals < 1 (the forward goal could not be restored).  n = 0 or T = 0: EARL_OK, nothing launched. */
+int earl_kitchen_agents_rollout(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
+                                const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop,
+                                const earl_backward_goals* goals, const double* forward_goals, int32_t n_forward_goals, const earl_gaussian_head* head, const double* obs0,
+                                int32_t T, const uint64_t* clock, float* actions, const earl_kitchen_out* out, const earl_episode_summary* summary, earl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Minitaur env (BASELINE configs[4]) on the same stepper: floating base + 16 hinges (nv = 22, nq = 23), four connect
@@ -658,6 +698,46 @@ int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model
 int earl_minitaur_population_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                                      const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
                                      const uint64_t* clock, float* actions, const earl_minitaur_out* out, const earl_episode_summary* summary, earl_stream_t stream);
+/* ---- the forward / reset AGENT PAIR inside the same launch: a POPULATION of pairs, a TABLE of backward goals, episode SUMMARIES -- each NULL or given ----
+ * earl_agent_pair is earl_tabletop.h's struct and earl_backward_goals the one above, as they are, with the minitaur's sizes: a goal row is 2 doubles (x, y: a row of
+ * st->goal), pair->backward_goal ONE such row, goals->table [n_rows, 2]; agent_out [T, n]; forward_success / backward_success [n] (one launch is one episode).
+ * policy->params is [2, pair->param_stride] -- row 0 the forward agent, row 1 the reset agent, both of policy's architecture and head -- or, with pop,
+ * [P, 2, pair->param_stride] at pop->param_stride.  pair = NULL is refused: it is not an alias of earl_minitaur_population_rollout.
+ * Per env and env step t, in this order (the order is the contract; the six items are earl_sawyer_pair_rollout's):
+ *   1. the action is computed from the observation the env last emitted (earl_minitaur_policy_rollout's rule: obs0 at step 0, afterwards row t - 1 as it stands, the goal
+ *      entries a handover patched included) by the network of the env's current `phase` (0 forward, anything else reset) of its member, at
+ *      policy->params + (g / G) * pop->param_stride + phase * pair->param_stride; the arithmetic is unchanged;
+ *   2. with a head, the step's TWO Philox blocks are the ones earl_minitaur_policy_rollout makes ({0x504F4C00 + b, global id, ev}, ev = cfg->step_counter + clock[1] + t):
+ *      they do not depend on the phase;
+ *   3. agent_out[t n + env], actions and eps_out are written;
+ *   4. the env step runs as in the single-policy kernels, failure guard, rollback and fail_count included; reward and success refer to the goal in force DURING the
+ *      step, which is the env's row of st->goal;
+ *   5. steps_in_phase += 1 (a rolled-back step counts, with success 0), and the env hands over if (switch_on_success && success) || steps_in_phase >=
+ *      switch_every[phase]: phase ^= 1, steps_in_phase = 0; forward_success / backward_success of the phase that ended is incremented if switch_on_success && success
+ *      (a step where the clock ran out as well counts as ended by success); step 0 of the launch starts both counters at 0.
+ *      Entering the reset phase, the env's row of st->goal becomes pair->backward_goal, or with `goals` table[r], r = min((int)(u01(b.x, b.y) * n_rows), n_rows - 1), where
+ *      b is the Philox4x32-10 block {0xFFFD, global env id, ev lo, ev hi} under key cfg->seed (earl_sawyer_agents_rollout's draw: the counter words, u01 and clamp of the
+ *      0xFFFE draw; index 0xFFFD is free here too: the reset draws with 0x4D00 .. 0x4D06, the head with 0x504F4C00 / 0x504F4C01); goals->row[env] = r and
+ *      row_out[t n + env] = r at such a step, row_out is -1 at every other step of a live env; with neither the goal stays.  Entering the forward phase, it becomes the
+ *      cfg->goal_table row of the 0xFFFE draw of this step, the lifelong switch's expression.  Whenever the row changes, entries 30 / 31 of this step's emitted observation
+ *      row (row t of out->obs, or the carried row of st->last_obs) are patched: the next action sees the new goal, this step's reward used the old one;
+ *   6. phase and steps_in_phase are stored after every env step (in the two-wave kernel by the first-half wave, next to the goal switch; the new goal is the one its
+ *      later steps observe).  st->goal is left as the goal in force at launch exit: there is no separate entry rule, and every other entry point keeps working on the state.
+ * The pair's handover IS the goal switch of autonomous RL: cfg->goal_change_frequency > 0 is refused (the lifelong switch and a forward entry would both draw with index
+ * 0xFFFE at the same step; running both is not offered).
+ * Identities: never switching (switch_every > T, switch_on_success = 0) with all envs in phase 0 is bit-identical to earl_minitaur_population_rollout with row 0 of every
+ * member -- outputs, actions, eps, state, fail_count, summary; all envs in phase 1 with no backward goal, to the same with row 1.  pop equals cutting the batch at the
+ * global ids that are multiples of G.  summary equals its definitions, reward and success against the goal in force during the step.  A `goals` table of ONE row equals
+ * pair->backward_goal = that row.  Nothing depends on n, the shard split, the launch form (one-wave kernel in its three shapes, two-wave kernel) or how T steps are cut into
+ * launches.  actions, every pointer of `out`, the pair's three output pointers and goals->row / row_out may be NULL.
+ * EARL_ERR_ARG before any HIP call: everything earl_minitaur_population_rollout refuses (no generic-stepper form included), the contract's pair rules
+ * (csrc/policy_check.h: NULL pair / phase / steps_in_phase, switch_every < 1, switch_on_success other than 0 / 1, param_stride below the parameter count), param_stride
+ * % 4 != 0, pop->param_stride < 2 * pair->param_stride, goals with a NULL table or n_rows < 1, goals together with pair->backward_goal, cfg->goal_change_frequency > 0.
+ * n = 0 or T = 0: EARL_OK, nothing launched. */
+int earl_minitaur_agents_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                 const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop, const earl_backward_goals* goals,
+                                 const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_minitaur_out* out,
+                                 const earl_episode_summary* summary, earl_stream_t stream);
 /* reset the envs with mask[i] != 0 (NULL = all); obs [n, 32] (may be NULL) is written for the reset envs only */
 int earl_minitaur_reset(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                         const uint8_t* mask, double* obs, earl_stream_t stream);

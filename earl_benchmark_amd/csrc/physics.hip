@@ -170,47 +170,21 @@ static int sawyer_closed_loop(const earl_link_model* model, const earl_collision
   if (!out->obs && !st->last_obs) return EARL_ERR_ARG;    // (without out->obs the env's row of last_obs is the one observation row the launch keeps)
   if (nv != 10 && nv != 15) return EARL_ERR_ARG;
   // the policy's contract (policy_check.h); the weight rows are read in 16-byte pieces, so params is aligned and every stride a multiple of 4 floats
-  if (earl::contract::check_policy(*policy, 14, 4, head, earl::contract::kParamsAligned16, nullptr)) return EARL_ERR_ARG;
+  if (paired && !pair) return EARL_ERR_ARG;
+  if (earl::contract::check_closed_loop(*policy, 14, 4, earl::contract::kParamsAligned16, head, pop, cfg->env_offset, cfg->n, paired ? pair : nullptr,
+                                        cfg->goal_change_frequency, goals, cfg->n_goal_rows, nullptr))
+    return EARL_ERR_ARG;
   if (cfg->frame_skip < 0 || cfg->att_hand < 0 || cfg->att_right < 0 || cfg->att_left < 0 || cfg->att_obj < 0) return EARL_ERR_ARG;
   if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;
   if (cfg->n_goal_rows > 0 && !cfg->goal_table) return EARL_ERR_ARG;
   if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && (!st->obj_init || cfg->att_grasp < 0 || cfg->att_lpad < 0 || cfg->att_rpad < 0)) return EARL_ERR_ARG;
   if (nv == 15 && cfg->obj_kind >= 1 && out->info && !st->obj_init) return EARL_ERR_ARG;
-  if (pop && earl::contract::check_population(*policy, *pop, cfg->env_offset, cfg->n, 16, 4, nullptr)) return EARL_ERR_ARG;
-  if (paired) {
-    if (earl::contract::check_pair(*policy, pair, cfg->goal_change_frequency, 4, nullptr)) return EARL_ERR_ARG;
-    if (pair->backward_goal && cfg->n_goal_rows == 0) return EARL_ERR_ARG;   // (the forward goal could not be restored)
-    if (pop && earl::contract::check_pair_population(*pop, *pair, nullptr)) return EARL_ERR_ARG;
-    if (goals && earl::contract::check_backward_goals(*goals, *pair, cfg->n_goal_rows, nullptr)) return EARL_ERR_ARG;
-  }
   if (g_lpe == 64) return EARL_ERR_ARG;                   // (the 64-lane measurement builds: no policy form)
   if (cfg->n == 0) return EARL_OK;
   if (int rc = check_cone(col, true, (hipStream_t)stream, "sawyer_policy_rollout")) return rc;
   SawyerPolicyArgs a;
   static_cast<SawyerArgs&>(a) = SawyerArgs{model, col, *cfg, *st, nullptr, T, *out, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
-  a.pol = *policy;
-  a.head = head ? *head : earl::contract::default_head();
-  a.gauss = head ? 1 : 0;
-  a.obs0 = obs0;
-  a.act_out = actions;
-  a.pop_G = pop ? pop->envs_per_policy : 0;
-  a.pop_stride = pop ? pop->param_stride : 0;
-  a.sum_ret = summary ? summary->ret : nullptr;
-  a.sum_last = summary ? summary->success_last : nullptr;
-  a.sum_first = summary ? summary->first_success : nullptr;
-  a.pair_phase = paired ? pair->phase : nullptr;
-  a.pair_sip = paired ? pair->steps_in_phase : nullptr;
-  a.pair_stride = paired ? pair->param_stride : 0;
-  a.pair_goal = !paired ? nullptr : (goals ? goals->table : pair->backward_goal);      // (the ONE fixed row: the table of one row)
-  a.pair_goal_rows = !paired ? 0 : (goals ? goals->n_rows : (pair->backward_goal ? 1 : 0));
-  a.pair_row = paired && goals ? goals->row : nullptr;
-  a.pair_row_out = paired && goals ? goals->row_out : nullptr;
-  a.pair_se[0] = paired ? pair->switch_every[0] : 0;
-  a.pair_se[1] = paired ? pair->switch_every[1] : 0;
-  a.pair_sos = paired ? pair->switch_on_success : 0;
-  a.pair_agent = paired ? pair->agent_out : nullptr;
-  a.pair_fs = paired ? pair->forward_success : nullptr;
-  a.pair_bs = paired ? pair->backward_success : nullptr;
+  fill_closed_loop(a, *policy, head, obs0, actions, pop, summary, paired ? pair : nullptr, goals, nullptr, 0);      // (the forward goals are cfg->goal_table's)
   if (nv == 10) {
     if (g_door_variant == 2 || (g_door_variant != 1 && cfg->n > 4096)) return earl_unit_w8_sawyer_policy_rollout(&a, stream);
     sawyer_policy_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);

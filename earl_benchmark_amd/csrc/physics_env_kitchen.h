@@ -86,36 +86,9 @@ __device__ __forceinline__ double kit_norm_diff(const double* a, const double* b
 
 // ------------------------------------------------------------------------------------------------ the policy phase of the policy kernels (earl_kitchen_policy_rollout)
 // The rollout's arguments (action unused) plus the policy.  A struct of its own so that the plain kernels' argument stays what it was
-struct KitchenPolicyArgs : KitchenRolloutArgs {
-  earl_mlp_policy pol;           // dims[0] = 46, dims[n_layers] = 9 (18 with the head)
-  earl_gaussian_head head;       // read when gauss != 0
-  int gauss;
-  const double* obs0;            // [n, 46]: what the policy sees at step 0
-  float* act_out;                // [T, n, 9] or NULL: the actions as the policy produced them (earl_kitchen_rollout_clocked fed with it walks through the same bits)
-  int pop_G;                     // earl_kitchen_population_rollout: envs per member of a population (0: one policy); the env with global id g reads its parameters at pol.params + (g / pop_G) pop_stride
-  int64_t pop_stride;            // floats between consecutive members (a multiple of 4: every member's rows after the input layer are read in 16-byte pieces)
-  double* sum_ret;               // earl_episode_summary of the launch, each NULL or [n]: lane 0 of the env's owner wave keeps its three words up to date in HBM after every env step
-  uint8_t* sum_last;             // (step 0 initialises them)
-  int32_t* sum_first;
-  // earl_kitchen_agents_rollout: the forward / reset agent pair (pair_phase == NULL: no pair, and nothing below is read).  As SawyerPolicyArgs': the env's phase word
-  // travels through HBM like the summary words, and every field is read through the kernel-argument segment where it is used
-  int8_t* pair_phase;            // [n] 0 forward, anything else reset; the network of the phase starts at pol.params (+ the member's offset) + phase * pair_stride
-  int32_t* pair_sip;             // [n] steps the env has spent in its phase
-  int64_t pair_stride;           // floats between the two agents' rows (a multiple of 4)
-  const double* pair_goal;       // NULL or the table [pair_goal_rows, 23] of backward goals: entering the reset phase, a drawn row of it becomes the env's st.goal row
-  const double* pair_fwd;        // NULL or the table [pair_fwd_rows, 23] of forward goals: entering the forward phase, likewise (NULL: the goal stays)
-  int pair_goal_rows;            // (1 for pair->backward_goal, the table of one row; 0 with pair_goal == NULL)
-  int pair_fwd_rows;
-  int pair_se[2];                // switch_every
-  int pair_sos;                  // switch_on_success
-  int8_t* pair_agent;            // NULL or [T, n]
-  int32_t* pair_fs;              // NULL or [n]: forward phases that ended by success (step 0 of the launch starts them at 0)
-  int32_t* pair_bs;              // NULL or [n]: reset phases that ended by success
-  int32_t* pair_row;             // NULL or [n]: earl_backward_goals.row
-  int32_t* pair_row_out;         // NULL or [T, n]: earl_backward_goals.row_out
-};
+#include "policy_closed_loop.h"
+struct KitchenPolicyArgs : ClosedLoopArgs<KitchenRolloutArgs> {};      // pol.dims[0] = 46, pol.dims[n_layers] = 9 (18 with the head); goal rows of 23
 static_assert(std::is_standard_layout<KitchenRolloutArgs>::value && std::is_trivially_copyable<KitchenPolicyArgs>::value, "the policy phase reads KitchenPolicyArgs as laid out in the kernel-argument segment");
-#include "policy_lane_group.h"
 // A float32 MLP 46 -> H1 (-> H2) -> 9 | 18 evaluated by the 32 lanes of an env between two env steps: element k of a layer on lane k & 31 in register k >> 5.  The input
 // layer is pol_layer<32, false> (rows of 46 floats = 184 bytes are no whole 16-byte pieces; its second k-tile holds 14 elements), every later one pol_layer<32, true>
 // (hidden widths are multiples of 16 and params is 16-byte aligned, so every later row starts on a 16-byte boundary).
@@ -131,8 +104,7 @@ static_assert(std::is_standard_layout<KitchenRolloutArgs>::value && std::is_triv
 __device__ __noinline__ float kitchen_policy_action(const uint64_t ka_bits, const uint64_t ev, const uint32_t gid, const uint64_t seed, const double* __restrict__ seen, const int env,
                                                     const size_t row, const int sub, const bool live) {
 #pragma clang fp contract(off)
-  const EARL_KARG KitchenPolicyArgs* ka = (const EARL_KARG KitchenPolicyArgs*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ka_bits >> 32)) << 32) |
-                                                                              (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ka_bits));
+  const EARL_KARG KitchenPolicyArgs* ka = cl_kernarg<KitchenPolicyArgs>(ka_bits);
   const int n_layers = ka->pol.n_layers, d1 = ka->pol.dims[1], d2 = ka->pol.dims[2], d3 = ka->pol.dims[3];
   const int hidden_act = ka->pol.hidden_act, out_act = ka->pol.out_act;
   if (!seen) seen = ka->obs0 + (size_t)env * 46;       // step 0
@@ -142,18 +114,7 @@ __device__ __noinline__ float kitchen_policy_action(const uint64_t ka_bits, cons
   h[1] = (live && sub + 32 < 46) ? (float)seen[sub + 32] : 0.f;
 #pragma unroll
   for (int i = 2; i < 8; ++i) h[i] = 0.f;
-  const float* w = ka->pol.params;
-  const int pop_G = ka->pop_G;
-  if (pop_G > 0) w += (size_t)(gid / (uint32_t)pop_G) * (size_t)ka->pop_stride;
-  // an agent pair: the network of the env's phase, the word lane 0 of the owner wave stored after the last handover decision (a wave whose two envs are in two phases
-  // walks two sets of rows, like a wave of two members).  A group that is not live reads the word of the env it shadows
-  const int8_t* pair_phase = ka->pair_phase;
-  if (pair_phase) {
-    const int ph = pair_phase[env] != 0 ? 1 : 0;
-    if (ph) w += (size_t)ka->pair_stride;
-    int8_t* agent_out = ka->pair_agent;
-    if (sub == 0 && live && agent_out) agent_out[row] = (int8_t)ph;
-  }
+  const float* w = cl_policy_weights(ka, gid, env, row, sub == 0 && live);      // (the member's rows, the network of the pair's phase)
   pol_layer<32, false>(w, w + (size_t)d1 * 46, 46, d1, hidden_act, sub, h);
   w += (size_t)d1 * (46 + 1);
   if (n_layers == 3) {
@@ -196,9 +157,7 @@ __device__ __forceinline__ double kit_policy_step(const A& a, const int t, const
   const double* seen = t > 0 ? (a.out.obs ? a.out.obs + (row - n) * 46 : a.st.last_obs + (size_t)env * 46) : nullptr;
   const uint64_t ev = a.cfg.counter + (a.clock ? a.clock[0] : 0) + (uint64_t)t;      // the step's sensor-noise counter (read per step, like the noise's)
   // (offset 0 of the kernel-argument segment is the kernel's one argument, the KitchenPolicyArgs)
-  const EARL_KARG void* ka = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(ka));
-  const float u = kitchen_policy_action((uint64_t)ka, ev, (uint32_t)(a.cfg.env_offset + env), a.cfg.seed, seen, env, row, sub, live);
+  const float u = kitchen_policy_action((uint64_t)cl_kernarg<KitchenPolicyArgs>(), ev, (uint32_t)(a.cfg.env_offset + env), a.cfg.seed, seen, env, row, sub, live);
   // the env step consumes the float32 values stored in act_out: lanes 0 .. 8 of the live group hold them.  The second group of a one-env-per-wave launch (solo >= 1)
   // is the first one's shadow and steps with the bits of the live group's action (wave-wide shuffle; the choice is wave-uniform)
   return (double)__shfl(u, a.solo >= 1 ? kk : grp * 32 + kk, 64);
@@ -213,55 +172,21 @@ template <class A>
 __device__ __forceinline__ void kit_pair_handover(const A& a, const int t, const int env, const size_t row, const int sub, const int grp, const bool live, const bool failed,
                                                   const uint8_t suc) {
 #pragma clang fp contract(off)
-  const EARL_KARG void* kap = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kap));
-  const EARL_KARG KitchenPolicyArgs* ka = (const EARL_KARG KitchenPolicyArgs*)kap;
-  int8_t* const pair_phase = ka->pair_phase;
-  if (!pair_phase) return;                               // (wave-uniform)
-  int32_t* const pair_sip = ka->pair_sip;
+  const EARL_KARG KitchenPolicyArgs* ka = cl_kernarg<KitchenPolicyArgs>();
   // (the second group of a one-env-per-wave launch is the first one's shadow and takes the live group's flag: the same branches)
-  const bool by_s = ka->pair_sos != 0 && __shfl((int)((!failed && suc) ? 1 : 0), a.solo >= 1 ? 0 : grp * 32, 64) != 0;
-  int ph = pair_phase[env] != 0 ? 1 : 0;
-  int sip = pair_sip[env] + 1;                           // (a rolled-back step counts, with success 0)
-  const bool over = by_s || sip >= (ph ? ka->pair_se[1] : ka->pair_se[0]);
-  int32_t* const row_at = ka->pair_row_out;
-  if (sub == 0 && live) {
-    int32_t* const fs = ka->pair_fs;
-    int32_t* const bs = ka->pair_bs;
-    if (fs) fs[env] = (t > 0 ? fs[env] : 0) + ((by_s && ph == 0) ? 1 : 0);      // (a step where the clock ran out as well counts as ended by success)
-    if (bs) bs[env] = (t > 0 ? bs[env] : 0) + ((by_s && ph != 0) ? 1 : 0);
-    if (row_at) row_at[row] = -1;                        // overwritten below by the same lane on a step that draws
-  }
-  if (over) {
-    ph ^= 1;
-    sip = 0;
-    // entering the reset phase: a row of the backward table (draw index 0xFFFD); entering the forward phase: a row of the forward table (0xFFFE).  The draw's counter
-    // words, u01 and clamp are earl_sawyer_agents_rollout's, ev the step's sensor-noise counter (the noise draws with 0x4B00 + j, the head with 0x504F4C00 + b)
-    const double* const table = ph ? ka->pair_goal : ka->pair_fwd;
-    if (table) {
-      const int rows = ph ? ka->pair_goal_rows : ka->pair_fwd_rows;
-      const uint64_t ev = a.cfg.counter + (a.clock ? a.clock[0] : 0) + (uint64_t)t;
-      const earl::U4 b = earl::philox4x32_10(earl::U4{ph ? 0xFFFDu : 0xFFFEu, (uint32_t)(a.cfg.env_offset + env), (uint32_t)ev, (uint32_t)(ev >> 32)},
-                                             (uint32_t)a.cfg.seed, (uint32_t)(a.cfg.seed >> 32));
-      int gi = (int)(earl::u01(b.x, b.y) * (double)rows);
-      gi = gi < rows ? gi : rows - 1;
-      if (live) {
-        for (int k = sub; k < 46; k += 32) {
-          if (k < 23) continue;
-          const double gv = table[(size_t)gi * 23 + (k - 23)];
-          a.st.goal[(size_t)env * 23 + (k - 23)] = gv;
-          if (a.out.obs) a.out.obs[row * 46 + k] = gv;
-          a.st.last_obs[(size_t)env * 46 + k] = gv;
-        }
-        if (sub == 0 && ph) {
-          int32_t* const row_of = ka->pair_row;
-          if (row_of) row_of[env] = gi;
-          if (row_at) row_at[row] = gi;
-        }
-      }
-    }
-  }
-  if (sub == 0 && live) { pair_phase[env] = (int8_t)ph; pair_sip[env] = sip; }
+  const bool success = __shfl((int)((!failed && suc) ? 1 : 0), a.solo >= 1 ? 0 : grp * 32, 64) != 0;
+  // ev: the step's sensor-noise counter (the noise draws with 0x4B00 + j, the head with 0x504F4C00 + b)
+  cl_pair_handover(ka, t, env, row, sub == 0 && live, success, (uint32_t)(a.cfg.env_offset + env), a.cfg.seed, a.cfg.counter, a.clock, ka->pair_fwd, ka->pair_fwd_rows,
+                   [&](const double* table, const int gi) {
+                     if (!live) return;
+                     for (int k = sub; k < 46; k += 32) {
+                       if (k < 23) continue;
+                       const double gv = table[(size_t)gi * 23 + (k - 23)];
+                       a.st.goal[(size_t)env * 23 + (k - 23)] = gv;
+                       if (a.out.obs) a.out.obs[row * 46 + k] = gv;
+                       a.st.last_obs[(size_t)env * 46 + k] = gv;
+                     }
+                   });
 }
 // DUO (solo == 3, round 5): the FOUR waves of the workgroup, one per SIMD, work on its one env (substep's ROLE 1 - 4).  Per timestep all run the kinematics; then, side by
 // side: wave 0 (B, owns the env) the constraint rows, wave 1 (A) the mass matrix into wave 0's LDS block, wave 2 the bias forces, wave 3 the bounding tests and the collision

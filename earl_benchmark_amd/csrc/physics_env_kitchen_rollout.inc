@@ -178,18 +178,7 @@
         const uint8_t s_t = failed ? (uint8_t)0 : suc;
         if (a.out.reward) a.out.reward[row] = r_t;
         if (a.out.success) a.out.success[row] = s_t;
-        const EARL_KARG void* kap = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(kap));
-        const EARL_KARG KitchenPolicyArgs* ka = (const EARL_KARG KitchenPolicyArgs*)kap;
-        double* const sum_ret = ka->sum_ret;
-        uint8_t* const sum_last = ka->sum_last;
-        int32_t* const sum_first = ka->sum_first;
-        if (sum_ret) sum_ret[env] = (t > 0 ? sum_ret[env] : 0.0) + r_t;      // sum over t ascending of reward_t
-        if (sum_last) sum_last[env] = s_t;                                   // (the one of step T - 1 stays)
-        if (sum_first) {
-          const int32_t f = t > 0 ? sum_first[env] : -1;
-          sum_first[env] = (f < 0 && s_t) ? t : f;
-        }
+        cl_episode_summary(cl_kernarg<KitchenPolicyArgs>(), t, env, r_t, s_t);
         if (a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
         if (a.out.done) a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
       }

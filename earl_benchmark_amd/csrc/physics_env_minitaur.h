@@ -39,34 +39,9 @@ template <bool ARROW> constexpr int mt_wpb() { return ARROW ? EARL_MT_WPB : Lim<
 
 // ------------------------------------------------------------------------------------------------ the policy phase of the two policy kernels (earl_minitaur_policy_rollout)
 // The rollout's arguments (action unused) plus the policy.  A struct of its own so that the plain kernels' argument stays what it was
-struct MinitaurPolicyArgs : MinitaurArgs {
-  earl_mlp_policy pol;           // dims[0] = 32, dims[n_layers] = 8 (16 with the head)
-  earl_gaussian_head head;       // read when gauss != 0
-  int gauss;
-  const double* obs0;            // [n, 32]: what the policy sees at step 0
-  float* act_out;                // [T, n, 8] or NULL: the actions as the policy produced them (earl_minitaur_rollout_clocked fed with it walks through the same bits)
-  int pop_G;                     // earl_minitaur_population_rollout: envs per member of a population (0: one policy); the env with global id g reads its parameters at pol.params + (g / pop_G) pop_stride
-  int64_t pop_stride;            // floats between consecutive members (a multiple of 4: every member's rows are read in 16-byte pieces)
-  double* sum_ret;               // earl_episode_summary of the launch, each NULL or [n]: lane 0 of the env keeps its three words up to date in HBM after every env step
-  uint8_t* sum_last;             // (step 0 initialises them)
-  int32_t* sum_first;
-  // earl_minitaur_agents_rollout: the forward / reset agent pair (pair_phase == NULL: no pair, and nothing below is read).  As SawyerPolicyArgs': the env's phase word
-  // travels through HBM like the summary words, and every field is read through the kernel-argument segment where it is used
-  int8_t* pair_phase;            // [n] 0 forward, anything else reset; the network of the phase starts at pol.params (+ the member's offset) + phase * pair_stride
-  int32_t* pair_sip;             // [n] steps the env has spent in its phase
-  int64_t pair_stride;           // floats between the two agents' rows (a multiple of 4)
-  const double* pair_goal;       // NULL or the table [pair_goal_rows, 2] of backward goals: entering the reset phase, a drawn row of it becomes the env's st.goal row
-  int pair_goal_rows;            // (1 for pair->backward_goal, the table of one row; 0 with pair_goal == NULL)
-  int pair_sos;                  // switch_on_success
-  int pair_se[2];                // switch_every
-  int8_t* pair_agent;            // NULL or [T, n]
-  int32_t* pair_fs;              // NULL or [n]: forward phases that ended by success (step 0 of the launch starts them at 0)
-  int32_t* pair_bs;              // NULL or [n]: reset phases that ended by success
-  int32_t* pair_row;             // NULL or [n]: earl_backward_goals.row
-  int32_t* pair_row_out;         // NULL or [T, n]: earl_backward_goals.row_out
-};
+#include "policy_closed_loop.h"
+struct MinitaurPolicyArgs : ClosedLoopArgs<MinitaurArgs> {};      // pol.dims[0] = 32, pol.dims[n_layers] = 8 (16 with the head); goal rows of 2
 static_assert(std::is_standard_layout<MinitaurArgs>::value && std::is_trivially_copyable<MinitaurPolicyArgs>::value, "the policy phase reads MinitaurPolicyArgs as laid out in the kernel-argument segment");
-#include "policy_lane_group.h"
 // A float32 MLP 32 -> H1 (-> H2) -> 8 | 16 evaluated by the 32 lanes of an env between two env steps (pol_layer<32, true>: element k of a layer on lane k & 31 in register
 // k >> 5; K = 32 makes the input layer a vector layer too).  -> the action's element `sub` on lanes 0 .. 7 of the group, as stored in act_out.
 // `seen`: the env's row of 32 doubles the policy sees (NULL at step 0: the env's row of obs0); `row` = t n + env.  A group that is not live (an idle group of the last
@@ -79,8 +54,7 @@ static_assert(std::is_standard_layout<MinitaurArgs>::value && std::is_trivially_
 __device__ __noinline__ float minitaur_policy_action(const uint64_t ka_bits, const uint64_t ev, const uint32_t gid, const uint64_t seed, const double* __restrict__ seen, const int env,
                                                      const size_t row, const int sub, const bool live) {
 #pragma clang fp contract(off)
-  const EARL_KARG MinitaurPolicyArgs* ka = (const EARL_KARG MinitaurPolicyArgs*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ka_bits >> 32)) << 32) |
-                                                                                (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ka_bits));
+  const EARL_KARG MinitaurPolicyArgs* ka = cl_kernarg<MinitaurPolicyArgs>(ka_bits);
   const int n_layers = ka->pol.n_layers, d1 = ka->pol.dims[1], d2 = ka->pol.dims[2], d3 = ka->pol.dims[3];
   const int hidden_act = ka->pol.hidden_act, out_act = ka->pol.out_act;
   if (!seen) seen = ka->obs0 + (size_t)env * 32;       // step 0
@@ -88,18 +62,7 @@ __device__ __noinline__ float minitaur_policy_action(const uint64_t ka_bits, con
   h[0] = live ? (float)seen[sub] : 0.f;
 #pragma unroll
   for (int i = 1; i < 8; ++i) h[i] = 0.f;
-  const float* w = ka->pol.params;
-  const int pop_G = ka->pop_G;
-  if (pop_G > 0) w += (size_t)(gid / (uint32_t)pop_G) * (size_t)ka->pop_stride;
-  // an agent pair: the network of the env's phase, the word lane 0 stored after the last handover decision (a wave whose two envs are in two phases walks two sets of
-  // rows, like a wave of two members).  A group that is not live reads the word of the env it shadows
-  const int8_t* pair_phase = ka->pair_phase;
-  if (pair_phase) {
-    const int ph = pair_phase[env] != 0 ? 1 : 0;
-    if (ph) w += (size_t)ka->pair_stride;
-    int8_t* agent_out = ka->pair_agent;
-    if (sub == 0 && live && agent_out) agent_out[row] = (int8_t)ph;
-  }
+  const float* w = cl_policy_weights(ka, gid, env, row, sub == 0 && live);      // (the member's rows, the network of the pair's phase)
   pol_layer<32, true>(w, w + (size_t)d1 * 32, 32, d1, hidden_act, sub, h);
   w += (size_t)d1 * (32 + 1);
   if (n_layers == 3) {
@@ -141,9 +104,7 @@ __device__ __forceinline__ void mt_step_action(const A& a, const int t, const in
     const double* seen = t > 0 ? (a.out.obs ? a.out.obs + (row - n) * 32 : a.st.last_obs + (size_t)env * 32) : nullptr;
     const uint64_t ev = a.cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t;      // (read per step, like the goal switch's)
     // (offset 0 of the kernel-argument segment is the kernel's one argument, the MinitaurPolicyArgs)
-    const EARL_KARG void* ka = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    const float u = minitaur_policy_action((uint64_t)ka, ev, (uint32_t)(a.cfg.env_offset + env), a.cfg.seed, seen, env, row, sub, live);
+    const float u = minitaur_policy_action((uint64_t)cl_kernarg<MinitaurPolicyArgs>(), ev, (uint32_t)(a.cfg.env_offset + env), a.cfg.seed, seen, env, row, sub, live);
     // the env step consumes the float32 values stored in act_out: lanes 0 .. 7 hold them
 #pragma unroll
     for (int k = 0; k < 8; ++k) a64[k] = earl::mt_clipd((double)__shfl(u, k, 32), -1.01, 1.01);
@@ -161,47 +122,14 @@ template <class A>
 __device__ __forceinline__ void mt_pair_handover(const A& a, const int t, const int env, const size_t row, const int sub, const bool live, const bool failed, const uint8_t suc,
                                                  double& goal0, double& goal1) {
 #pragma clang fp contract(off)
-  const EARL_KARG void* kp = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kp));
-  const EARL_KARG MinitaurPolicyArgs* ka = (const EARL_KARG MinitaurPolicyArgs*)kp;
-  int8_t* const pair_phase = ka->pair_phase;
-  if (!pair_phase) return;                               // (wave-uniform)
-  int32_t* const pair_sip = ka->pair_sip;
-  const bool by_s = ka->pair_sos != 0 && __shfl((int)((!failed && suc) ? 1 : 0), 0, 32) != 0;
-  int ph = pair_phase[env] != 0 ? 1 : 0;
-  int sip = pair_sip[env] + 1;                           // (a rolled-back step counts, with success 0)
-  const bool over = by_s || sip >= (ph ? ka->pair_se[1] : ka->pair_se[0]);
-  int32_t* const row_at = ka->pair_row_out;
-  if (sub == 0 && live) {
-    int32_t* const fs = ka->pair_fs;
-    int32_t* const bs = ka->pair_bs;
-    if (fs) fs[env] = (t > 0 ? fs[env] : 0) + ((by_s && ph == 0) ? 1 : 0);      // (a step where the clock ran out as well counts as ended by success)
-    if (bs) bs[env] = (t > 0 ? bs[env] : 0) + ((by_s && ph != 0) ? 1 : 0);
-    if (row_at) row_at[row] = -1;                        // overwritten below by the same lane on a step that draws
-  }
-  if (over) {
-    ph ^= 1;
-    sip = 0;
-    // entering the reset phase: a row of the backward table, if there is one (draw index 0xFFFD); entering the forward phase: the lifelong switch's draw for this step
-    // (0xFFFE, cfg.goal_table).  The same counter words, u01 and clamp
-    const double* const table = ph ? ka->pair_goal : a.cfg.goal_table;
-    if (table) {
-      const int rows = ph ? ka->pair_goal_rows : a.cfg.n_goals;
-      int gi = (int)(mt_draw(a.cfg, ph ? 0xFFFDu : 0xFFFEu, env, a.cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t) * (double)rows);
-      gi = gi >= rows ? rows - 1 : gi;
-      goal0 = table[2 * gi]; goal1 = table[2 * gi + 1];
-      if (live && sub >= 30) (a.out.obs ? a.out.obs + row * 32 : a.st.last_obs + (size_t)env * 32)[sub] = sub == 30 ? goal0 : goal1;
-      if (live && sub == 0) {
-        a.st.goal[(size_t)env * 2] = goal0; a.st.goal[(size_t)env * 2 + 1] = goal1;
-        if (ph) {
-          int32_t* const row_of = ka->pair_row;
-          if (row_of) row_of[env] = gi;
-          if (row_at) row_at[row] = gi;
-        }
-      }
-    }
-  }
-  if (sub == 0 && live) { pair_phase[env] = (int8_t)ph; pair_sip[env] = sip; }
+  const bool success = __shfl((int)((!failed && suc) ? 1 : 0), 0, 32) != 0;
+  // entering the forward phase: the lifelong switch's draw for this step (0xFFFE, cfg.goal_table), with its counter words
+  cl_pair_handover(cl_kernarg<MinitaurPolicyArgs>(), t, env, row, sub == 0 && live, success, (uint32_t)(a.cfg.env_offset + env), a.cfg.seed, a.cfg.step_counter,
+                   a.clock ? a.clock + 1 : nullptr, a.cfg.goal_table, a.cfg.n_goals, [&](const double* table, const int gi) {
+                     goal0 = table[2 * gi]; goal1 = table[2 * gi + 1];
+                     if (live && sub >= 30) (a.out.obs ? a.out.obs + row * 32 : a.st.last_obs + (size_t)env * 32)[sub] = sub == 30 ? goal0 : goal1;
+                     if (live && sub == 0) { a.st.goal[(size_t)env * 2] = goal0; a.st.goal[(size_t)env * 2 + 1] = goal1; }
+                   });
 }
 template <bool RESET, bool ARROW>
 __global__ __launch_bounds__(64 * mt_wpb<ARROW>(), ARROW ? EARL_MT_BLOCKS : 1) void minitaur_kernel(const MinitaurArgs a) {

@@ -16,35 +16,8 @@ struct SawyerArgs {
   const uint64_t* clock;         // earl_sawyer_rollout_clocked: DEVICE words added to cfg.counter / cfg.step_counter (NULL = zero); [1] is read where a goal-switch draw is made
 };
 // earl_sawyer_policy_rollout: the rollout's arguments (action unused) plus the policy.  A struct of its own so that the plain kernels' argument stays what it was
-struct SawyerPolicyArgs : SawyerArgs {
-  earl_mlp_policy pol;           // dims[0] = 14, dims[n_layers] = 4 (8 with the head)
-  earl_gaussian_head head;       // read when gauss != 0
-  int gauss;
-  const double* obs0;            // [n, 14]: what the policy sees at step 0
-  float* act_out;                // NULL or [T, n, 4]: the actions as the policy produced them (the open-loop entry points fed with it walk through the same bits)
-  // earl_sawyer_population_rollout (new fields go HERE, never into SawyerArgs: the plain kernels' argument and machine code stay what they were)
-  int pop_G;                     // envs per member of a population (0: one policy); the env with global id g reads its parameters at pol.params + (g / pop_G) pop_stride
-  int64_t pop_stride;            // floats between consecutive members (a multiple of 4: every member's rows are read in 16-byte pieces)
-  double* sum_ret;               // earl_episode_summary of the launch, each NULL or [n]: lane 0 of the env keeps its three words up to date in HBM after every env step
-  uint8_t* sum_last;             // (step 0 initialises them), so a time slice handed to another wave finds them where it finds qpos
-  int32_t* sum_first;
-  // earl_sawyer_pair_rollout: the forward / reset agent pair (pair_phase == NULL: no pair, and nothing below is read).  The env's phase word travels through HBM like the
-  // summary words: lane 0 stores it after the handover decision, an agent-scope fence follows, and all 16 lanes read it back where the next action is computed
-  int8_t* pair_phase;            // [n] 0 forward, anything else reset; the network of the phase starts at pol.params + phase * pair_stride
-  int32_t* pair_sip;             // [n] steps the env has spent in its phase
-  int64_t pair_stride;           // floats between the two agents' rows (a multiple of 4)
-  const double* pair_goal;       // NULL or the table [pair_goal_rows, 7] of backward goals: entering the reset phase, a drawn row of it becomes the env's st.goal row
-                                 // (earl_sawyer_pair_rollout's ONE fixed row is the table of one row)
-  int pair_se[2];                // switch_every
-  int pair_sos;                  // switch_on_success
-  int8_t* pair_agent;            // NULL or [T, n]
-  int32_t* pair_fs;              // NULL or [n]: forward phases that ended by success (step 0 of the launch starts them at 0)
-  int32_t* pair_bs;              // NULL or [n]: reset phases that ended by success
-  // earl_sawyer_agents_rollout: the backward-goal table (earl_backward_goals).  `pair_goal` above is its base; written by ONE lane of the env, never read by the kernel
-  int pair_goal_rows;            // rows of pair_goal (1 for the fixed row; 0 with pair_goal == NULL)
-  int32_t* pair_row;             // NULL or [n]: the table row the env's reset goal came from, stored at every entry into the reset phase
-  int32_t* pair_row_out;         // NULL or [T, n]: the row drawn at env step t, -1 at a step without a draw
-};
+#include "policy_closed_loop.h"
+struct SawyerPolicyArgs : ClosedLoopArgs<SawyerArgs> {};      // pol.dims[0] = 14, pol.dims[n_layers] = 4 (8 with the head); goal rows of 7
 
 // Work queue of the time-sliced rollout (earl_sawyer_state.sched: progress[G] then lock[G], zero on entry).  An env group's state is in HBM after every env
 // step (the failure guard's "last stable state"), so ANY wave can take the group's next slice of env steps; a wave claims the unlocked group that has come
@@ -255,8 +228,7 @@ __device__ __forceinline__ void sawyer_emit(Shared<NV>& s, const typename ModelO
 // ------------------------------------------------------------------------------------------------ the policy phase of sawyer_policy_rollout_kernel
 // A float32 MLP 14 -> H1 (-> H2) -> 4 | 8 evaluated by the 16 lanes of an env between two env steps, under the contract of policy_math.h / tabletop_policy.h.  The layer
 // itself -- activations in registers, element k on lane k & 15 in register k >> 4, x_k by a width-16 __shfl, four fmaf chains per lane, weight rows in 16-byte pieces --
-// is pol_layer<16, ..> of policy_lane_group.h, shared with the minitaur (32 lanes per env).
-#include "policy_lane_group.h"
+// is pol_layer<16, ..> of policy_lane_group.h, shared with the minitaur and the kitchen (32 lanes per env).
 
 // the action of env step t of one env, on all 16 lanes of its group: observation (element `sub` on lane `sub`, 0 beyond 13) -> MLP -> head -> float4.
 // `row` = t n + env; a group that is not live computes on zeros and writes nothing.
@@ -266,10 +238,7 @@ __device__ __forceinline__ void sawyer_emit(Shared<NV>& s, const typename ModelO
 __device__ __noinline__ float4 sawyer_policy_action(const uint64_t ka_bits, const uint64_t ev, const uint32_t gid, const uint64_t seed, const double* __restrict__ seen, const int env,
                                                        const size_t row, const int sub, const bool live) {
 #pragma clang fp contract(off)
-  // (`ka_bits`: the kernel's own kernel-argument pointer, handed over by the caller -- inside a called function __builtin_amdgcn_kernarg_segment_ptr() is null -- and
-  // made wave-uniform again, so that the reads below are scalar loads)
-  const EARL_KARG SawyerPolicyArgs* ka = (const EARL_KARG SawyerPolicyArgs*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ka_bits >> 32)) << 32) |
-                                                                            (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ka_bits));
+  const EARL_KARG SawyerPolicyArgs* ka = cl_kernarg<SawyerPolicyArgs>(ka_bits);
   const int n_layers = ka->pol.n_layers, d0 = ka->pol.dims[0], d1 = ka->pol.dims[1], d2 = ka->pol.dims[2], d3 = ka->pol.dims[3];
   const int hidden_act = ka->pol.hidden_act, out_act = ka->pol.out_act;
   if (!seen) seen = ka->obs0 + (size_t)env * 14;       // step 0
@@ -277,19 +246,7 @@ __device__ __noinline__ float4 sawyer_policy_action(const uint64_t ka_bits, cons
   h[0] = (sub < 14 && live) ? (float)seen[sub] : 0.f;
 #pragma unroll
   for (int i = 1; i < 16; ++i) h[i] = 0.f;
-  // a population: the member of this env, from its GLOBAL id alone (a wave whose four envs belong to two members walks two sets of rows: correct, only slower)
-  const int pop_G = ka->pop_G;
-  const float* w = ka->pol.params;
-  if (pop_G > 0) w += (size_t)(gid / (uint32_t)pop_G) * (size_t)ka->pop_stride;
-  // an agent pair: the network of the env's phase, the word lane 0 stored after the last handover decision (a wave whose four envs are in two phases walks two sets
-  // of rows, like a wave of two members)
-  const int8_t* pair_phase = ka->pair_phase;
-  if (pair_phase) {
-    const int ph = pair_phase[env] != 0 ? 1 : 0;
-    if (ph) w += (size_t)ka->pair_stride;
-    int8_t* agent_out = ka->pair_agent;
-    if (sub == 0 && live && agent_out) agent_out[row] = (int8_t)ph;
-  }
+  const float* w = cl_policy_weights(ka, gid, env, row, sub == 0 && live);      // (the member's rows, the network of the pair's phase)
   pol_layer<16, false>(w, w + (size_t)d1 * d0, d0, d1, hidden_act, sub, h);
   w += (size_t)d1 * (d0 + 1);
   if (n_layers == 3) {
@@ -331,9 +288,7 @@ __device__ __forceinline__ float4 sawyer_step_action(const A& a, const int t, co
     const double* seen = t > 0 ? (a.out.obs ? a.out.obs + ((size_t)(t - 1) * n + env) * 14 : a.st.last_obs + (size_t)env * 14) : nullptr;
     const uint64_t ev = a.cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t;      // (read per step, like the goal switch's: see there)
     // (offset 0 of the kernel-argument segment is the kernel's one argument, the SawyerPolicyArgs: see sawyer_policy_rollout_kernel)
-    const EARL_KARG void* ka = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    return sawyer_policy_action((uint64_t)ka, ev, (uint32_t)(a.cfg.env_offset + env), a.cfg.seed, seen, env, (size_t)t * n + env, sub, live);
+    return sawyer_policy_action((uint64_t)cl_kernarg<SawyerPolicyArgs>(), ev, (uint32_t)(a.cfg.env_offset + env), a.cfg.seed, seen, env, (size_t)t * n + env, sub, live);
   } else {
     return *reinterpret_cast<const float4*>(a.action + ((size_t)t * n + env) * 4);
   }

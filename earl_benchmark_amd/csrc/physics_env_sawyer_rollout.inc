@@ -142,18 +142,7 @@
         const uint8_t s_t = failed ? (uint8_t)0 : suc;
         if (a.out.reward) a.out.reward[row] = r_t;
         if (a.out.success) a.out.success[row] = s_t;
-        const EARL_KARG void* kp = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(kp));
-        const EARL_KARG SawyerPolicyArgs* ka = (const EARL_KARG SawyerPolicyArgs*)kp;
-        double* const sum_ret = ka->sum_ret;
-        uint8_t* const sum_last = ka->sum_last;
-        int32_t* const sum_first = ka->sum_first;
-        if (sum_ret) sum_ret[env] = (t > 0 ? sum_ret[env] : 0.0) + (double)r_t;      // sum over t ascending of (double)reward_t
-        if (sum_last) sum_last[env] = s_t;                                               // (the one of step T - 1 stays)
-        if (sum_first) {
-          const int32_t f = t > 0 ? sum_first[env] : -1;
-          sum_first[env] = (f < 0 && s_t) ? t : f;
-        }
+        cl_episode_summary(cl_kernarg<SawyerPolicyArgs>(), t, env, (double)r_t, s_t);
       }
     }
     fence();
@@ -177,30 +166,17 @@
       // The pair's state machine (include/earl_physics.h, item 5), worked out by all 16 lanes of the env from the same words: the step's success flag from lane 0, phase
       // and steps_in_phase from HBM, where lane 0 stores them again -- nothing of it lives across substep.  The pointers are read through the kernel-argument segment
       // here, where they are used (see sawyer_policy_action on why).
-      const EARL_KARG void* kp = (const EARL_KARG void*)__builtin_amdgcn_kernarg_segment_ptr();
-      asm volatile("" : "+s"(kp));
-      const EARL_KARG SawyerPolicyArgs* ka = (const EARL_KARG SawyerPolicyArgs*)kp;
+      const EARL_KARG SawyerPolicyArgs* ka = cl_kernarg<SawyerPolicyArgs>();
       int8_t* const pair_phase = ka->pair_phase;
       if (pair_phase) {                                  // (wave-uniform)
         pair_on = true;
-        int32_t* const pair_sip = ka->pair_sip;
-        const bool by_s = ka->pair_sos != 0 && __shfl((int)((!failed && suc) ? 1 : 0), 0, 16) != 0;
-        int ph = pair_phase[env] != 0 ? 1 : 0;
-        int sip = pair_sip[env] + 1;                     // (a rolled-back step counts, with success 0)
-        const bool over = by_s || sip >= (ph ? ka->pair_se[1] : ka->pair_se[0]);
-        if (sub == 0 && live) {
-          int32_t* const fs = ka->pair_fs;
-          int32_t* const bs = ka->pair_bs;
-          if (fs) fs[env] = (t > 0 ? fs[env] : 0) + ((by_s && ph == 0) ? 1 : 0);      // (a step where the clock ran out as well counts as ended by success)
-          if (bs) bs[env] = (t > 0 ? bs[env] : 0) + ((by_s && ph != 0) ? 1 : 0);
-        }
-        if (over) {
-          ph ^= 1;
-          sip = 0;
+        int ph, sip;
+        if (cl_pair_decide(ka, t, env, sub == 0 && live, __shfl((int)((!failed && suc) ? 1 : 0), 0, 16) != 0, ph, sip)) {
+          // (the draw itself is the lifelong switch's ONE Philox call below, by direction: the shared handover's would be a second one in this body)
           if (ph) { fixed = ka->pair_goal; fixed_rows = ka->pair_goal_rows; row_of = ka->pair_row; pair_sw = fixed != nullptr; }      // entering the reset phase: a row of the backward table, if there is one
           else pair_sw = cfg.n_goal_rows > 0;                                   // entering the forward phase: the lifelong switch's draw for this step
         }
-        if (sub == 0 && live) { pair_phase[env] = (int8_t)ph; pair_sip[env] = sip; }
+        if (sub == 0 && live) { pair_phase[env] = (int8_t)ph; ka->pair_sip[env] = sip; }
         // row_out: -1 at every step of a live env, overwritten below by the same lane on a step that draws (like slot 7 of the door's info block above)
         row_at = ka->pair_row_out;
         if (row_at && sub == 7 && live) row_at[row] = -1;

@@ -81,46 +81,17 @@ static int kitchen_closed_loop(const void* model, const earl_collision_model* co
   for (int k = 0; k < 8; ++k) if (cfg->site_att[k] < 0 || cfg->site_att[k] >= cfg->n_att) return EARL_ERR_ARG;
   // the policy's contract (policy_check.h).  The reference clips the action silently, so an unbounded output is taken (unlike the minitaur's).  A population: groups
   // of 16 envs, every member's rows read in 16-byte pieces
-  if (earl::contract::check_policy(*policy, 46, 9, head, earl::contract::kParamsAligned16, nullptr)) return EARL_ERR_ARG;
-  if (pop && earl::contract::check_population(*policy, *pop, cfg->env_offset, cfg->n, 16, 4, nullptr)) return EARL_ERR_ARG;
+  // (the kitchen has no lifelong switch of its own: goal_change_frequency 0; its forward goals come with the call)
+  if (paired && (!pair || n_forward_goals < 0)) return EARL_ERR_ARG;
   const bool forward = paired && forward_goals && n_forward_goals >= 1;
-  if (paired) {
-    // (the kitchen has no lifelong switch of its own: goal_change_frequency 0)
-    if (earl::contract::check_pair(*policy, pair, 0, 4, nullptr)) return EARL_ERR_ARG;
-    if (pop && earl::contract::check_pair_population(*pop, *pair, nullptr)) return EARL_ERR_ARG;
-    if (n_forward_goals < 0) return EARL_ERR_ARG;
-    if (pair->backward_goal && !forward) return EARL_ERR_ARG;      // (the forward goal could not be restored)
-    if (goals && earl::contract::check_backward_goals(*goals, *pair, forward ? n_forward_goals : 0, nullptr)) return EARL_ERR_ARG;
-  }
+  if (earl::contract::check_closed_loop(*policy, 46, 9, earl::contract::kParamsAligned16, head, pop, cfg->env_offset, cfg->n, paired ? pair : nullptr, 0, goals,
+                                        forward ? n_forward_goals : 0, nullptr))
+    return EARL_ERR_ARG;
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "kitchen_policy_rollout")) return rc;
   KitchenPolicyArgs k;
   static_cast<KitchenRolloutArgs&>(k) = KitchenRolloutArgs{model, col, *params, *cfg, *st, *out, nullptr, T, solo_mode(cfg->n), clock};
-  k.pol = *policy;
-  k.head = head ? *head : earl::contract::default_head();
-  k.gauss = head ? 1 : 0;
-  k.obs0 = obs0;
-  k.act_out = actions;
-  k.pop_G = pop ? pop->envs_per_policy : 0;
-  k.pop_stride = pop ? pop->param_stride : 0;
-  k.sum_ret = summary ? summary->ret : nullptr;
-  k.sum_last = summary ? summary->success_last : nullptr;
-  k.sum_first = summary ? summary->first_success : nullptr;
-  k.pair_phase = paired ? pair->phase : nullptr;
-  k.pair_sip = paired ? pair->steps_in_phase : nullptr;
-  k.pair_stride = paired ? pair->param_stride : 0;
-  k.pair_goal = !paired ? nullptr : (goals ? goals->table : pair->backward_goal);      // (the ONE fixed row: the table of one row)
-  k.pair_goal_rows = !paired ? 0 : (goals ? goals->n_rows : (pair->backward_goal ? 1 : 0));
-  k.pair_fwd = forward ? forward_goals : nullptr;
-  k.pair_fwd_rows = forward ? n_forward_goals : 0;
-  k.pair_se[0] = paired ? pair->switch_every[0] : 0;
-  k.pair_se[1] = paired ? pair->switch_every[1] : 0;
-  k.pair_sos = paired ? pair->switch_on_success : 0;
-  k.pair_agent = paired ? pair->agent_out : nullptr;
-  k.pair_fs = paired ? pair->forward_success : nullptr;
-  k.pair_bs = paired ? pair->backward_success : nullptr;
-  k.pair_row = paired && goals ? goals->row : nullptr;
-  k.pair_row_out = paired && goals ? goals->row_out : nullptr;
+  fill_closed_loop(k, *policy, head, obs0, actions, pop, summary, paired ? pair : nullptr, goals, forward ? forward_goals : nullptr, forward ? n_forward_goals : 0);
   if (k.solo == 2 && g_solo < 0) k.solo = 3;      // the plain entry point's rule
   if (g_solo < 0 && k.solo == 1 && cfg->n <= 2 * cu_count()) k.solo = 4;
   earl_unit_kitchen_policy_rollout(&k, stream);      // physics_kitchen_policy.hip holds the kernels

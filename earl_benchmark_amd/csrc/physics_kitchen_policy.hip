@@ -5,6 +5,7 @@
 // instantiation of the same body changes the inliner's decisions for the lambdas of the split timestep (a local function with one call site is inlined at any size) and
 // with them the plain kernels' schedule and register assignment.  Here the plain kernels stay byte-identical, and the two units compile side by side.
 #include "physics_stepper.h"
+#include "policy_check.h"
 #include "policy_math.h"
 
 namespace {

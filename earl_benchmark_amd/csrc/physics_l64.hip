@@ -2,6 +2,7 @@
 // (physics_kernel<10 | 15, 64, *>, sawyer_rollout_kernel<10 | 15, 64>): the measurement / test switch earl_debug_set_physics_lanes(64), which the parity tests use to show
 // that results do not depend on the lane layout.  A translation unit of its own (round 5) so that the main unit does not carry them: a third of its compile time.
 #include "physics_stepper.h"
+#include "policy_check.h"
 #include "policy_math.h"
 
 namespace {

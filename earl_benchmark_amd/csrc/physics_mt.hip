@@ -66,42 +66,17 @@ static int minitaur_closed_loop(const void* model24, const earl_collision_model*
   if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;
   // the policy's contract (policy_check.h).  The reference env raises on an action outside +-(1 + 0.01); a kernel cannot, and the open-loop replay of the returned
   // actions must not either: bounded policies only.  A population: groups of 16 envs, every member's rows read in 16-byte pieces
-  if (earl::contract::check_policy(*policy, 32, 8, head, earl::contract::kParamsAligned16 | earl::contract::kBoundedOutput, nullptr)) return EARL_ERR_ARG;
-  if (pop && earl::contract::check_population(*policy, *pop, cfg->env_offset, cfg->n, 16, 4, nullptr)) return EARL_ERR_ARG;
-  if (paired) {
-    // the pair's handover IS the goal switch of autonomous RL: check_pair refuses goal_change_frequency > 0 (both would draw with index 0xFFFE at the same step)
-    if (earl::contract::check_pair(*policy, pair, cfg->goal_change_frequency, 4, nullptr)) return EARL_ERR_ARG;
-    if (pop && earl::contract::check_pair_population(*pop, *pair, nullptr)) return EARL_ERR_ARG;
-    if (goals && earl::contract::check_backward_goals(*goals, *pair, cfg->n_goals, nullptr)) return EARL_ERR_ARG;
-  }
+  // (the pair's handover IS the goal switch of autonomous RL: goal_change_frequency > 0 is refused with a pair -- both would draw with index 0xFFFE at the same step)
+  if (paired && !pair) return EARL_ERR_ARG;
+  if (earl::contract::check_closed_loop(*policy, 32, 8, earl::contract::kParamsAligned16 | earl::contract::kBoundedOutput, head, pop, cfg->env_offset, cfg->n,
+                                        paired ? pair : nullptr, cfg->goal_change_frequency, goals, cfg->n_goals, nullptr))
+    return EARL_ERR_ARG;
   if (!g_mt_stepper) return EARL_ERR_ARG;                 // (earl_debug_set_minitaur_stepper(0): no policy form)
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_policy_rollout")) return rc;
   MinitaurPolicyArgs a;
   static_cast<MinitaurArgs&>(a) = MinitaurArgs{model24, col, *cfg, *st, *out, nullptr, T, nullptr, nullptr, solo_mode(cfg->n), clock};
-  a.pol = *policy;
-  a.head = head ? *head : earl::contract::default_head();
-  a.gauss = head ? 1 : 0;
-  a.obs0 = obs0;
-  a.act_out = actions;
-  a.pop_G = pop ? pop->envs_per_policy : 0;
-  a.pop_stride = pop ? pop->param_stride : 0;
-  a.sum_ret = summary ? summary->ret : nullptr;
-  a.sum_last = summary ? summary->success_last : nullptr;
-  a.sum_first = summary ? summary->first_success : nullptr;
-  a.pair_phase = paired ? pair->phase : nullptr;
-  a.pair_sip = paired ? pair->steps_in_phase : nullptr;
-  a.pair_stride = paired ? pair->param_stride : 0;
-  a.pair_goal = !paired ? nullptr : (goals ? goals->table : pair->backward_goal);      // (the ONE fixed row: the table of one row)
-  a.pair_goal_rows = !paired ? 0 : (goals ? goals->n_rows : (pair->backward_goal ? 1 : 0));
-  a.pair_sos = paired ? pair->switch_on_success : 0;
-  a.pair_se[0] = paired ? pair->switch_every[0] : 0;
-  a.pair_se[1] = paired ? pair->switch_every[1] : 0;
-  a.pair_agent = paired ? pair->agent_out : nullptr;
-  a.pair_fs = paired ? pair->forward_success : nullptr;
-  a.pair_bs = paired ? pair->backward_success : nullptr;
-  a.pair_row = paired && goals ? goals->row : nullptr;
-  a.pair_row_out = paired && goals ? goals->row_out : nullptr;
+  fill_closed_loop(a, *policy, head, obs0, actions, pop, summary, paired ? pair : nullptr, goals, nullptr, 0);      // (the forward goals are cfg->goal_table's)
   if (a.solo == 0 && cfg->num_substeps > 0 && (g_mt_duo > 0 || (g_mt_duo < 0 && mt_use_duo(cfg->n)))) {      // the plain entry point's rule
     minitaur_policy_duo_kernel<<<(unsigned)((cfg->n + 16 * MT_DUO_PAIRS / 4 - 1) / (4 * MT_DUO_PAIRS)), 128 * MT_DUO_PAIRS, 0, (hipStream_t)stream>>>(a);
     return launched("minitaur_policy_rollout (two waves per SIMD)");

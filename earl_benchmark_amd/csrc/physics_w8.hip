@@ -13,6 +13,7 @@
                                 // slower one: 60.3 against 57.5 ms.)
 #define EARL_NO_PREFETCH 1      // no prefetch of the first near block's pair record: the second wave hides that latency, the 22 registers are worth more
 #include "physics_stepper.h"
+#include "policy_check.h"
 #include "policy_math.h"
 
 namespace {

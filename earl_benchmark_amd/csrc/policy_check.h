@@ -1,6 +1,6 @@
 // policy_check.h -- the host-side contract of a closed-loop launch's policy arguments (earl_mlp_policy, earl_gaussian_head, earl_policy_population, earl_agent_pair),
 // stated once for every entry point that takes them: the tabletop's four (tabletop_policy.h, both libraries), the Sawyer door / peg's four (physics.hip), the
-// minitaur's (physics_mt.hip) and earl_mlp_policy_forward_cpu (tabletop_host.cpp).  Host only; it needs the ABI structs and kPolicyMaxWidth and nothing of any env.
+// minitaur's (physics_mt.hip), the kitchen's (physics_kitchen.hip) and earl_mlp_policy_forward_cpu (tabletop_host.cpp).  Host only; it needs the ABI structs and kPolicyMaxWidth and nothing of any env.
 // What differs between the callers is an argument: the widths, the rules below, the population's group size, the stride multiple.  Every check returns EARL_OK or
 // EARL_ERR_ARG; `err` is NULL (the physics entry points return the bare code) or kErrLen bytes that receive the message (the tabletop's thread-local g_err).
 #pragma once
@@ -119,6 +119,26 @@ inline int check_backward_goals(const Goals& goals, const earl_agent_pair& pair,
   if (pair.backward_goal) return refuse(err, "backward goals: a table AND pair backward_goal (one of them)");
   if (n_goal_rows == 0) return refuse(err, "backward goals: the env has no goal table (the forward goal could not be restored)");
   return EARL_OK;
+}
+
+// The whole contract of a closed-loop launch of a stepper env (Sawyer, minitaur, kitchen), in the order the entry points applied it: the policy obs_dim -> .. ->
+// act_dim under `rules` with its head; the population (NULL: one policy) over the global ids env_offset .. env_offset + n - 1; the pair (NULL: none) with the env's
+// goal_change_frequency, its population and its table of backward goals (NULL: none).  n_forward_rows: the rows of the forward goal table the launch can draw from; a
+// pair with a backward goal -- one row or a table -- needs one at least (the forward goal could not be restored).  Everywhere: groups of 16 envs share their weights'
+// loads, and every stride is a multiple of 4 floats (the rows are read in 16-byte pieces)
+template <class Goals>
+inline int check_closed_loop(const earl_mlp_policy& p, int obs_dim, int act_dim, unsigned rules, const earl_gaussian_head* head, const earl_policy_population* pop,
+                             int32_t env_offset, int32_t n, const earl_agent_pair* pair, int32_t goal_change_frequency, const Goals* goals, int32_t n_forward_rows,
+                             char* err) {
+  if (int rc = check_policy(p, obs_dim, act_dim, head, rules, err)) return rc;
+  if (pop)
+    if (int rc = check_population(p, *pop, env_offset, n, 16, 4, err)) return rc;
+  if (!pair) return EARL_OK;
+  if (int rc = check_pair(p, pair, goal_change_frequency, 4, err)) return rc;
+  if (pair->backward_goal && n_forward_rows < 1) return refuse(err, "pair backward_goal: the env has no forward goal table (the forward goal could not be restored)");
+  if (pop)
+    if (int rc = check_pair_population(*pop, *pair, err)) return rc;
+  return goals ? check_backward_goals(*goals, *pair, n_forward_rows, err) : EARL_OK;
 }
 
 }  // namespace contract

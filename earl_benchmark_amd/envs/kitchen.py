@@ -521,21 +521,18 @@ class Kitchen:
     keys = ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'last_qp_robot', 'att', 'steps_since_reset', 'interventions', 'fail_count', 'lifelong_return_t',
             'steps_since_goal_change', 'last_obs')
     return {k: getattr(self, k).clone() for k in keys} | {'counter': self._counter, 'total_step_count': self.total_step_count,
-                                                          'last_obs_stale': bool(self._last_obs_stale)} | {
-                                                              k: getattr(self, k).clone() for k in self._PAIR_STATE if getattr(self, k) is not None}
+                                                          'last_obs_stale': bool(self._last_obs_stale)} | closed_loop.pair_state_dict(self)
 
-  _PAIR_STATE = ('agent_phase', 'steps_in_phase', 'backward_row')      # in the dict once a pair launch has allocated them, and only then
 
   def load_state_dict(self, sd):
     self._last_obs_stale = bool(sd.get('last_obs_stale', False))      # (a dict written before the flag existed: not stale)
+    closed_loop.load_pair_state(self, sd)
     for k, v in sd.items():
-      if k == 'last_obs_stale':
+      if k == 'last_obs_stale' or k in closed_loop.PAIR_STATE:
         continue
       if k == 'counter':
         self._counter = int(v)
       elif k == 'total_step_count':
         self.total_step_count = int(v)
-      elif k in self._PAIR_STATE:
-        setattr(self, k, v.to(self.device).clone())
       else:
         getattr(self, k).copy_(v)

@@ -1,11 +1,15 @@
-"""The closed loop of the stepper envs (door, peg, minitaur, kitchen) as their `rollout_policy` offers it: what the envs share around the ONE launch of their rollout kernel
-with a policy inside it (include/earl_physics.h: earl_sawyer_population_rollout, earl_minitaur_policy_rollout, earl_kitchen_policy_rollout), next to `PhysicsStepGraph`.  The env's side is a few
-hooks: `_check_policy(policy, who)` -> is it Gaussian (policy.require_widths with the env's widths and rules), `_new_out((T,))`, `reset()`, `last_obs` /
-`_last_obs_stale` / `_get_obs_t()`, and `_launch_policy(policy, head, obs0, T, out)`: the launch itself.  The minitaur and the kitchen also share `rollout_population`
-and `evaluate` below: their `_check_policy` takes `population=True` (a PolicyPopulation is then taken, require_widths checking its members against the env's global
-ids) and their `_launch_policy` takes `summary=` (None or an _abi.EpisodeSummary) and an `out` that may lack any key.  `rollout_pair` / `evaluate_pair` below are the
-forward / reset agent pair of such an env (earl_minitaur_agents_rollout, earl_kitchen_agents_rollout): its hooks are `_check_pair(pair, who)` -> is it Gaussian and `_launch_policy(..., pair=)`,
-which takes what `pair_structs` returns.
+"""The closed loop of the stepper envs (door, peg, minitaur, kitchen): what the envs share around the ONE launch of their rollout kernel with a policy inside it
+(include/earl_physics.h: earl_{sawyer,minitaur,kitchen}_population_rollout and earl_{sawyer,minitaur,kitchen}_agents_rollout), next to `PhysicsStepGraph`.  Every
+function below takes the env and serves all of them; the env's side is ONE set of hooks:
+  `_check_policy(policy, who, population=False)` -> is it Gaussian (policy.require_widths with the env's widths and rules; population=True: a PolicyPopulation is taken
+      as well, its members checked against the env's global ids -- the Sawyer envs take one everywhere);
+  `_check_pair(pair, who)` -> is it Gaussian, for an AgentPair or a PairPopulation;
+  `_launch_policy(policy, head, obs0, T, out, summary=None, pair=None)`: the launch itself.  `out` may lack any key, 'obs' included (the env's row of last_obs then
+      carries the observation); summary: None or an _abi.EpisodeSummary; pair: None, or what `pair_structs` returns;
+  `_new_out((T,))`, and optionally `_new_pair_out((T,))` where a pair launch offers other keys (the door: no 'info'); `reset()`; `last_obs` / `_last_obs_stale` /
+      `_get_obs_t()`; the pair's state `agent_phase` / `steps_in_phase` / `backward_row` (None until `pair_structs` allocates it) and `_pair_counts`.
+The public names differ by env for history's sake -- the Sawyer envs' rollout_agents / evaluate_agents / evaluate_policy are rollout_pair / evaluate_pair / evaluate
+here -- so each takes `who`, the name its messages carry.
 
 What rollout_policy promises, for every such env (A = the env's action width): closed loop in ONE launch of the rollout kernel, `policy` evaluated between the env
 steps by the lanes that own the env: observation -> float32 MLP -> action -> env step.
@@ -108,6 +112,12 @@ def evaluate(env, who, policy, T, episodes=1, sample=False, reset_first=True):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the forward / reset agent pair
+def backward_goal(env, pair):
+  """-> (the ONE goal row of the reset phase or None, the table of rows or None): at most one is given ('initial' on an env with several initial states: a ValueError)"""
+  table = pair.goal_table(env)
+  return (None if table is not None else pair.goal_row(env)), table
+
+
 def pair_structs(env, pair, out):
   """the pair's per-env state (`env.agent_phase`, `env.steps_in_phase`, with a table `env.backward_row`: allocated at their first use) and the structs of one launch
   -> (_abi.AgentPair, population struct or None, _abi.BackwardGoals or None), (forward_success, backward_success)"""
@@ -115,8 +125,7 @@ def pair_structs(env, pair, out):
   from .. import _abi
   ptr = lambda t: None if t is None else t.data_ptr()
   n, kw = env.num_envs, dict(device=env.device)
-  table = pair.goal_table(env)
-  goal = None if table is not None else pair.goal_row(env)
+  goal, table = backward_goal(env, pair)
   with torch.cuda.device(env.device):
     if env.agent_phase is None:
       env.agent_phase = torch.zeros(n, dtype=torch.int8, **kw)
@@ -148,9 +157,24 @@ def reset_pair_state(env, mask=None):
       env.backward_row.masked_fill_(mask.bool(), -1)
 
 
-def rollout_pair(env, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
-  """The forward / reset agent pair of autonomous RL alternating inside ONE launch of the env's rollout kernel (include/earl_physics.h: earl_minitaur_agents_rollout,
-  earl_kitchen_agents_rollout):
+PAIR_STATE = ('agent_phase', 'steps_in_phase', 'backward_row')
+
+
+def pair_state_dict(env):
+  """the pair's part of state_dict(): in the dict once a pair launch has allocated it, and only then"""
+  return {k: getattr(env, k).clone() for k in PAIR_STATE if getattr(env, k) is not None}
+
+
+def load_pair_state(env, sd):
+  """the pair's part of load_state_dict(): the keys of `sd` that are the pair's (a dict without them leaves the env's own)"""
+  for k in PAIR_STATE:
+    if k in sd:
+      setattr(env, k, sd[k].to(env.device, torch.int8 if k == 'agent_phase' else torch.int32).clone())
+
+
+def rollout_pair(env, pair, T, reset_first=False, sample=True, return_noise=False, out=None, who='rollout_pair'):
+  """The forward / reset agent pair of autonomous RL alternating inside ONE launch of the env's rollout kernel (include/earl_physics.h: earl_sawyer_agents_rollout,
+  earl_minitaur_agents_rollout, earl_kitchen_agents_rollout):
   `pair` -- an `AgentPair` of the env's widths or a `PairPopulation` of them (the env with global id g runs pair g // envs_per_policy) -- drives every env by the agent
   of its phase (`env.agent_phase`: 0 forward, 1 reset; `env.steps_in_phase`) and hands it over after pair.switch_every[phase] steps or, with pair.switch_on_success,
   after a step whose success flag is set.  Entering the reset phase the env's goal becomes pair.backward_goal ('initial': the one row of `env.initial_states`; None: the
@@ -160,9 +184,11 @@ def rollout_pair(env, pair, T, reset_first=False, sample=True, return_noise=Fals
   -> rollout_policy()'s dict plus 'agent' [T, N] int8 (the agent that computed the action) and, with a table, 'backward_row' [T, N] int32 (the row drawn at that step,
   -1 elsewhere; `env.backward_row` [N]: the row each env's reset goal came from, -1 before its first entry and after its reset).
   Bookkeeping, the first observation, sample / return_noise and reset_first as rollout_policy.  `env.pair_counts`: the phases of this launch that ended by success."""
-  gaussian = env._check_pair(pair, 'rollout_pair')
+  gaussian = env._check_pair(pair, who)
+  backward_goal(env, pair)                                 # (its ValueError comes before any reset)
   n, kw = env.num_envs, dict(device=env.device)
-  T, out, head, obs0 = prepare(env, 'rollout_pair', pair, gaussian, T, reset_first, sample, return_noise, out, what='Gaussian agents (MLPPolicy agents are deterministic)')
+  T, out, head, obs0 = prepare(env, who, pair, gaussian, T, reset_first, sample, return_noise, out, what='Gaussian agents (MLPPolicy agents are deterministic)',
+                               new_out=getattr(env, '_new_pair_out', None))
   with torch.cuda.device(env.device):
     if 'agent' not in out:
       out['agent'] = torch.empty(T, n, dtype=torch.int8, **kw)
@@ -175,7 +201,7 @@ def rollout_pair(env, pair, T, reset_first=False, sample=True, return_noise=Fals
   return out
 
 
-def evaluate_pair(env, pair, T, sample=True):
+def evaluate_pair(env, pair, T, sample=True, who='evaluate_pair'):
   """T steps of `pair` -- an `AgentPair` or a `PairPopulation` -- continuing from the current state, as rollout_pair runs them, in ONE launch that writes only per-env
   summaries (`actions` and every [T] pointer NULL; the env's row of last_obs carries the observation): no tensor with a T axis is allocated.
   -> {'ret': [N] float64 (the step rewards summed t ascending, each against the goal in force during its step), 'success': [N] bool success at the last step,
@@ -183,12 +209,12 @@ def evaluate_pair(env, pair, T, sample=True):
       [N] int32 phases that ended by success (`env.pair_counts`)}: each equals its definition applied to what rollout_pair would have returned.
   State and bookkeeping end as after rollout_pair.  sample=False: Gaussian agents at their mean."""
   from .. import _abi
-  gaussian = env._check_pair(pair, 'evaluate_pair')
+  gaussian = env._check_pair(pair, who)
   if not gaussian and not sample:
-    raise ValueError('evaluate_pair: sample=False needs Gaussian agents (MLPPolicy agents are deterministic)')
+    raise ValueError(f'{who}: sample=False needs Gaussian agents (MLPPolicy agents are deterministic)')
   T, n, kw = int(T), env.num_envs, dict(device=env.device)
   if T < 1:
-    raise ValueError(f'evaluate_pair: T = {T} < 1')
+    raise ValueError(f'{who}: T = {T} < 1')
   with torch.cuda.device(env.device):
     ret, succ = torch.empty(n, dtype=torch.float64, **kw), torch.empty(n, dtype=torch.bool, **kw)
     first = torch.empty(n, dtype=torch.int32, **kw)

@@ -212,17 +212,17 @@ class SawyerDoor:
             # the reference's per-step info dict (evaluate_state: sawyer_door.py:127-139 / sawyer_peg.py:165-184), slots _abi.SAWYER_INFO_KEYS
             'info': torch.empty(*lead, self.num_envs, _abi.SAWYER_INFO, dtype=torch.float64, **kw)}
 
-  def _launch_rollout(self, actions, T, out, policy=None):
-    """T env steps and their bookkeeping; policy: None (the actions are given) or what _issue_rollout takes for the closed loop"""
+  def _launch_rollout(self, actions, T, out):
+    """T env steps of given actions and their bookkeeping"""
     self._cfg.step_counter = self.total_step_count
-    self._issue_rollout(actions, T, out, policy=policy)
+    self._issue_rollout(actions, T, out)
     closed_loop.finish(self, T, out['reward'], out['success'][-1] if out['success'].dim() == 2 else out['success'])
 
-  def _issue_rollout(self, actions, T, out, clock=None, policy=None, summary=None):
+  def _issue_rollout(self, actions, T, out, clock=None, policy=None, summary=None, pair=None):
     """the launches of T env steps into `out` (the door's info launch included); clock: the device words of earl_sawyer_rollout_clocked (None: earl_sawyer_rollout);
     policy: None, or (policy or population, head struct or None, obs0) -- earl_sawyer_population_rollout computes the actions itself and leaves them in
     out['actions']; then `out` may lack any key, 'obs' included (the env's row of last_obs carries the observation), and summary is None or an _abi.EpisodeSummary;
-    or (AgentPair or PairPopulation, head struct or None, obs0, _abi.AgentPair, _abi.PolicyPopulation or None, _abi.BackwardGoals or None) -- earl_sawyer_agents_rollout,
+    pair: None, or with policy = (AgentPair or PairPopulation, head struct or None, obs0) what physics_policy_rollout.pair_structs returns -- earl_sawyer_agents_rollout,
     with the same `out` and summary rules"""
     info = out.get('info')
     in_kernel = info is not None and self.nv >= 15        # the peg's dict needs simulator state: the rollout kernel's epilogue writes it
@@ -233,8 +233,8 @@ class SawyerDoor:
     with torch.cuda.device(self.device):
       if self.sched is not None and T > 1 and self._uses_queue(T):
         self.sched.zero_()                                 # (the queue of the time-sliced schedule: zero on entry)
-      if policy is not None and len(policy) == 6:
-        pi, head, obs0, ps, pop, goals = policy
+      if pair is not None:
+        (pi, head, obs0), (ps, pop, goals) = policy, pair[:3]
         ref = lambda x: None if x is None else C.byref(x)
         _abi.check(self._lib.earl_sawyer_agents_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pi.struct), C.byref(ps),
                                                         ref(pop), ref(goals), ref(head), obs0.data_ptr(), T, clock, _ptr(out.get('actions')), C.byref(o), ref(summary),
@@ -273,21 +273,12 @@ class SawyerDoor:
                                              self._reset_state[0].data_ptr(), self._reset_state[1].data_ptr(), _ptr(mask),
                                              obs.data_ptr(), self._stream()), 'earl_sawyer_reset')
     self._cfg.counter += 1
+    closed_loop.reset_pair_state(self, mask)               # (a reset env starts with the forward agent)
     if mask is None:
       self.interventions += 1
       self._last_obs_stale = False
-      if self.agent_phase is not None:                     # (a reset env starts with the forward agent)
-        self.agent_phase.zero_()
-        self.steps_in_phase.zero_()
-      if self.backward_row is not None:
-        self.backward_row.fill_(-1)
     else:
       self.interventions += mask.to(torch.int32)
-      if self.agent_phase is not None:
-        self.agent_phase.masked_fill_(mask.bool(), 0)
-        self.steps_in_phase.masked_fill_(mask.bool(), 0)
-      if self.backward_row is not None:
-        self.backward_row.masked_fill_(mask.bool(), -1)
       obs = torch.where(mask.bool()[:, None], obs, obs_prev)
     return obs[0].cpu().numpy() if self.scalar_api else obs
 
@@ -369,15 +360,22 @@ class SawyerDoor:
     self._launch_rollout(self._actions(a, (T,)), T, out)
     return out
 
-  def _check_policy(self, policy, who):
-    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy / PolicyPopulation of this env's widths on this env's device"""
+  def _check_policy(self, policy, who, population=True):
+    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy / PolicyPopulation of this env's widths on this env's device (a population is taken everywhere)"""
+    del population
     from ..policy import require_widths
     return require_widths(policy, who, self.OBS_DIM, 4, env=self)
 
-  def _launch_policy(self, policy, head, obs0, T, out, summary=None):
-    """hook of physics_policy_rollout: earl_sawyer_population_rollout"""
+  def _launch_policy(self, policy, head, obs0, T, out, summary=None, pair=None):
+    """hook of physics_policy_rollout: earl_sawyer_population_rollout, or -- pair: what physics_policy_rollout.pair_structs returns -- earl_sawyer_agents_rollout"""
     self._cfg.step_counter = self.total_step_count
-    self._issue_rollout(None, T, out, policy=(policy, head, obs0), summary=summary)
+    if pair is not None and self.nv < 15:                  # (the door's info dict of a pair launch is not offered: a caller's 'info' rows stay as they are)
+      out = {k: v for k, v in out.items() if k != 'info'}
+    self._issue_rollout(None, T, out, policy=(policy, head, obs0), summary=summary, pair=pair)
+
+  def _new_pair_out(self, lead):
+    """hook of physics_policy_rollout: the dict of a pair launch -- the door's has no 'info' (the peg's is written in the kernel and stays)"""
+    return self._new_out(lead, info=self.nv >= 15 and self.info_mode == 'full')
 
   def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
     """physics_policy_rollout's closed loop (its docstring is the contract) on earl_sawyer_population_rollout: `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy` built
@@ -385,7 +383,7 @@ class SawyerDoor:
     -> rollout()'s dict plus 'actions' [T, N, 4] and, with return_noise=True, 'eps' [T, N, 4]"""
     return closed_loop.rollout_policy(self, policy, T, reset_first, sample, return_noise, out)
 
-  def _check_agents(self, pair, who):
+  def _check_pair(self, pair, who):
     """-> is it Gaussian; `pair`: an AgentPair or a PairPopulation of this env's widths on this env's device, and no LifelongWrapper"""
     from ..policy import require_widths
     gaussian = require_widths(pair, who, self.OBS_DIM, 4, env=self, pair=True, pairs=True)
@@ -393,23 +391,6 @@ class SawyerDoor:
       raise ValueError(f'{who}: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
                        'not under a LifelongWrapper, whose clock would fight the pair\'s over the same draw')
     return gaussian
-
-  def _agent_structs(self, pair, goal, table, out):
-    """the pair's per-env state (allocated at its first use) and what _issue_rollout takes after (pair, head, obs0) -> (_abi.AgentPair, population struct or None,
-    _abi.BackwardGoals or None), (forward_success, backward_success)"""
-    n, kw = self.num_envs, dict(device=self.device)
-    if self.agent_phase is None:
-      self.agent_phase = torch.zeros(n, dtype=torch.int8, **kw)
-      self.steps_in_phase = torch.zeros(n, dtype=torch.int32, **kw)
-    if table is not None and self.backward_row is None:
-      self.backward_row = torch.full((n,), -1, dtype=torch.int32, **kw)
-    fwd, bwd = torch.empty(n, dtype=torch.int32, **kw), torch.empty(n, dtype=torch.int32, **kw)
-    ps = _abi.AgentPair(switch_every=(C.c_int32 * 2)(*pair.switch_every), switch_on_success=int(pair.switch_on_success), pad_=0, param_stride=pair.pair_stride,
-                        backward_goal=_ptr(goal), phase=self.agent_phase.data_ptr(), steps_in_phase=self.steps_in_phase.data_ptr(),
-                        agent_out=_ptr(out.get('agent')), forward_success=fwd.data_ptr(), backward_success=bwd.data_ptr())
-    goals = None if table is None else _abi.BackwardGoals(table=table.data_ptr(), n_rows=int(table.shape[0]), pad_=0, row=self.backward_row.data_ptr(),
-                                                          row_out=_ptr(out.get('backward_row')))
-    return (ps, getattr(pair, 'pop_struct', None), goals), (fwd, bwd)
 
   def rollout_agents(self, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
     """The forward / reset agent pair of autonomous RL alternating inside ONE launch of the rollout kernel (include/earl_physics.h: earl_sawyer_agents_rollout): `pair` -- an
@@ -423,22 +404,7 @@ class SawyerDoor:
     -1 elsewhere; `env.backward_row` [N]: the row each env's reset goal came from, -1 before its first entry and after its reset); the door's dict has no 'info' (the
     peg's is written in the kernel and stays).
     Bookkeeping, the first observation, sample / return_noise and reset_first as rollout_policy.  `env.pair_counts`: the phases of this launch that ended by success."""
-    gaussian = self._check_agents(pair, 'rollout_agents')
-    table = pair.goal_table(self)
-    goal = None if table is not None else pair.goal_row(self)      # ('initial' on the peg: a ValueError naming env.initial_states)
-    n, kw = self.num_envs, dict(device=self.device)
-    T, out, head, obs0 = closed_loop.prepare(self, 'rollout_agents', pair, gaussian, T, reset_first, sample, return_noise, out,
-                                             what='Gaussian agents (MLPPolicy agents are deterministic)',
-                                             new_out=lambda lead: self._new_out(lead, info=self.nv >= 15 and self.info_mode == 'full'))
-    if 'agent' not in out:
-      out['agent'] = torch.empty(T, n, dtype=torch.int8, **kw)
-    if table is not None and 'backward_row' not in out:
-      out['backward_row'] = torch.empty(T, n, dtype=torch.int32, **kw)
-    structs, counts = self._agent_structs(pair, goal, table, out)
-    launch_out = out if self.nv >= 15 else {k: v for k, v in out.items() if k != 'info'}      # (the door's info dict of a pair launch is not offered)
-    self._launch_rollout(None, T, launch_out, policy=(pair, head, obs0) + structs)
-    self._pair_counts = counts
-    return out
+    return closed_loop.rollout_pair(self, pair, T, reset_first, sample, return_noise, out, who='rollout_agents')
 
   def evaluate_agents(self, pair, T, sample=True):
     """T steps of `pair` -- an `AgentPair` or a `PairPopulation` -- continuing from the current state, as rollout_agents runs them, in ONE launch that writes only per-env
@@ -448,26 +414,7 @@ class SawyerDoor:
         last step, 'first_success': [N] int32 first successful step or -1, 'guard_steps': [N] int32 steps the failure guard rolled back, 'forward_success' /
         'backward_success': [N] int32 phases that ended by success (`env.pair_counts`)}: each equals its definition applied to what rollout_agents would have returned.
     State and bookkeeping end as after rollout_agents.  sample=False: Gaussian agents at their mean."""
-    gaussian = self._check_agents(pair, 'evaluate_agents')
-    if not gaussian and not sample:
-      raise ValueError('evaluate_agents: sample=False needs Gaussian agents (MLPPolicy agents are deterministic)')
-    T, n, kw = int(T), self.num_envs, dict(device=self.device)
-    if T < 1:
-      raise ValueError(f'evaluate_agents: T = {T} < 1')
-    table = pair.goal_table(self)
-    goal = None if table is not None else pair.goal_row(self)
-    ret, succ = torch.empty(n, dtype=torch.float64, **kw), torch.empty(n, dtype=torch.bool, **kw)
-    first = torch.empty(n, dtype=torch.int32, **kw)
-    before = self.fail_count.clone()
-    obs0 = (self._get_obs_t() if self._last_obs_stale else self.last_obs).contiguous()
-    head = pair.head(sample=bool(sample), eps_out=None) if gaussian else None
-    summary = _abi.EpisodeSummary(ret=ret.data_ptr(), success_last=succ.data_ptr(), first_success=first.data_ptr())
-    structs, counts = self._agent_structs(pair, goal, table, {})
-    self._cfg.step_counter = self.total_step_count
-    self._issue_rollout(None, T, {}, policy=(pair, head, obs0) + structs, summary=summary)
-    closed_loop.finish(self, T, ret, succ)
-    self._pair_counts = counts
-    return {'ret': ret, 'success': succ, 'first_success': first, 'guard_steps': self.fail_count - before, 'forward_success': counts[0], 'backward_success': counts[1]}
+    return closed_loop.evaluate_pair(self, pair, T, sample, who='evaluate_agents')
 
   @property
   def pair_counts(self):
@@ -482,30 +429,7 @@ class SawyerDoor:
         'first_success': [E, N] int32 first successful step, -1 if none, 'guard_steps': [E, N] int32 env steps the failure guard rolled back (the growth of fail_count over
         the episode: such steps count with reward 0 and no success, and a summary must not hide them)}; the first three equal their definitions applied to what
     rollout_policy would have returned.  reset_first=False: one episode that continues from the current state.  State and bookkeeping end as after rollout_policy."""
-    gaussian = self._check_policy(policy, 'evaluate_policy')
-    if sample and not gaussian:
-      raise ValueError('evaluate_policy: sample=True needs a Gaussian policy (an MLPPolicy is deterministic)')
-    E, T, n = int(episodes), int(T), self.num_envs
-    if T < 1 or E < 1:
-      raise ValueError(f'evaluate_policy: T = {T}, episodes = {E}: both >= 1')
-    if not reset_first and E != 1:
-      raise ValueError('evaluate_policy: a continuing evaluation (reset_first=False) is one episode')
-    kw = dict(device=self.device)
-    ret = torch.empty(E, n, dtype=torch.float64, **kw)
-    succ = torch.empty(E, n, dtype=torch.bool, **kw)
-    first = torch.empty(E, n, dtype=torch.int32, **kw)
-    guard = torch.empty(E, n, dtype=torch.int32, **kw)
-    for e in range(E):
-      if reset_first:
-        self.reset()
-      before = self.fail_count.clone()
-      obs0 = self._get_obs_t() if self._last_obs_stale else self.last_obs
-      head = policy.head(sample=bool(sample), eps_out=None) if gaussian else None
-      summary = _abi.EpisodeSummary(ret=ret[e].data_ptr(), success_last=succ[e].data_ptr(), first_success=first[e].data_ptr())
-      self._launch_policy(policy, head, obs0, T, {}, summary=summary)
-      closed_loop.finish(self, T, ret[e], succ[e])
-      guard[e] = self.fail_count - before
-    return {'ret': ret, 'success': succ, 'first_success': first, 'guard_steps': guard}
+    return closed_loop.evaluate(self, 'evaluate_policy', policy, T, episodes, sample, reset_first)
 
   def _get_obs_t(self):
     obs = torch.empty(self.num_envs, self.OBS_DIM, dtype=torch.float64, device=self.device)
@@ -567,21 +491,14 @@ class SawyerDoor:
     return {k: getattr(self, k).clone() for k in ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'steps_since_reset', 'interventions',
                                                   'steps_since_goal_change', 'lifelong_return_t', 'obj_init', 'last_obs', 'fail_count')} | {
                                                       'counter': int(self._cfg.counter), 'total_step_count': self.total_step_count,
-                                                      'last_obs_stale': bool(self._last_obs_stale)} | (
-                                                          {} if self.agent_phase is None else {'agent_phase': self.agent_phase.clone(),
-                                                                                               'steps_in_phase': self.steps_in_phase.clone()}) | (
-                                                              {} if self.backward_row is None else {'backward_row': self.backward_row.clone()})
+                                                      'last_obs_stale': bool(self._last_obs_stale)} | closed_loop.pair_state_dict(self)
 
   def load_state_dict(self, sd):
     for k in ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'steps_since_reset', 'interventions', 'steps_since_goal_change',
               'lifelong_return_t', 'obj_init', 'last_obs', 'fail_count'):
       if k in sd:
         getattr(self, k).copy_(sd[k])
-    if 'agent_phase' in sd:                                # (the agent pair's state: in the dict once a pair launch has allocated it, and only then)
-      self.agent_phase = sd['agent_phase'].to(self.device, torch.int8).clone()
-      self.steps_in_phase = sd['steps_in_phase'].to(self.device, torch.int32).clone()
-    if 'backward_row' in sd:                               # (likewise: once a launch has drawn from a table of backward goals)
-      self.backward_row = sd['backward_row'].to(self.device, torch.int32).clone()
+    closed_loop.load_pair_state(self, sd)                  # (the agent pair's state: in the dict once a pair launch has allocated it, and only then)
     self._cfg.counter = int(sd['counter'])
     self.total_step_count = int(sd['total_step_count'])
     self._last_obs_stale = bool(sd.get('last_obs_stale', 'last_obs' not in sd))      # (a dict without the row leaves the env's own, which belongs to another state)

@@ -63,6 +63,17 @@ def compile_unit(unit, tmp_path):
   return tool, open(asm).read().split('\n'), resources(r.stderr)
 
 
+def policy_fields(env_header, struct, plain):
+  """-> (the members of the plain struct, the closed-loop fields the policy struct obtains -- csrc/policy_closed_loop.h's ClosedLoopArgs<plain>, of which `struct`
+  derives and to which it adds nothing --, the text of that header): where a source-text test looks for a policy kernel's arguments"""
+  hdr = open(os.path.join(CSRC, env_header)).read()
+  shared_hdr = open(os.path.join(CSRC, 'policy_closed_loop.h')).read()
+  assert re.search(r'struct %s : ClosedLoopArgs<%s> \{\};' % (struct, plain), hdr), struct
+  plain_body = re.search(r'struct %s \{(.*?)\n\};' % plain, hdr, flags=re.S).group(1)
+  fields = re.search(r'struct ClosedLoopArgs : Plain \{(.*?)\n\};', shared_hdr, flags=re.S).group(1)
+  return plain_body, fields, shared_hdr
+
+
 def parent_build():
   """the recorded parent build, or a skip when this compiler is not the one it was recorded with"""
   want = json.load(open(PARENT))

@@ -139,8 +139,11 @@ def test_the_new_rules_stand_next_to_check_pair():
   src = open(os.path.join(CSRC, 'policy_check.h')).read()
   at = src.index('inline int check_pair(')
   assert src.index('inline int check_pair_population(') > at and src.index('inline int check_backward_goals(') > at
+  # the entry points apply them through the ONE closed-loop contract, which stands after them in the same header
+  whole = src[src.index('inline int check_closed_loop('):]
+  assert 'check_pair_population(' in whole and 'check_backward_goals(' in whole and src.index('inline int check_closed_loop(') > src.index('inline int check_backward_goals(')
   host = open(os.path.join(CSRC, 'physics.hip')).read()
-  assert 'check_pair_population(' in host and 'check_backward_goals(' in host and 'never both' not in host
+  assert 'check_closed_loop(' in host and 'never both' not in host
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. the Python surface
@@ -310,8 +313,8 @@ def test_the_sawyer_envs_offer_the_surface():
 # ---------------------------------------------------------------------------------------------------------------- 4. where the table's fields live
 def test_the_table_fields_live_in_the_policy_arguments_only():
   hdr = open(os.path.join(CSRC, 'physics_env_sawyer.h')).read()
-  plain = re.search(r'struct SawyerArgs \{(.*?)\n\};', hdr, flags=re.S).group(1)
-  policy = re.search(r'struct SawyerPolicyArgs : SawyerArgs \{(.*?)\n\};', hdr, flags=re.S).group(1)
+  from population_no_gpu import policy_fields
+  plain, policy, _ = policy_fields('physics_env_sawyer.h', 'SawyerPolicyArgs', 'SawyerArgs')
   for field in ('pair_goal', 'pair_goal_rows', 'pair_row', 'pair_row_out'):
     assert re.search(r'\b%s;' % field, policy) and field not in plain, field
   body = open(os.path.join(CSRC, 'physics_env_sawyer_rollout.inc')).read()

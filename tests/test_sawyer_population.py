@@ -188,12 +188,14 @@ def test_the_kernels_that_run_a_population_keep_the_timestep_loop_free_of_scratc
   finally:
     sys.path.pop(0)
   hdr = open(os.path.join(CSRC, 'physics_env_sawyer.h')).read()
-  plain = re.search(r'struct SawyerArgs \{(.*?)\n\};', hdr, flags=re.S).group(1)
-  policy = re.search(r'struct SawyerPolicyArgs : SawyerArgs \{(.*?)\n\};', hdr, flags=re.S).group(1)
+  from population_no_gpu import policy_fields
+  plain, policy, shared_hdr = policy_fields('physics_env_sawyer.h', 'SawyerPolicyArgs', 'SawyerArgs')
   for field in ('pop_G', 'pop_stride', 'sum_ret', 'sum_last', 'sum_first'):
     assert re.search(r'\b%s;' % field, policy) and field not in plain, field
   body = open(os.path.join(CSRC, 'physics_env_sawyer_rollout.inc')).read()
-  assert 'ka->pop_G' in hdr and 'ka->sum_ret' in body
+  # (the member's rows and the summary update are csrc/policy_closed_loop.h's, which sawyer_policy_action and the rollout body call)
+  assert 'ka->pop_G' in shared_hdr and 'ka->sum_ret' in shared_hdr and 'cl_policy_weights(ka' in hdr and 'cl_episode_summary(' in body
+  assert not re.search(r'\ba\.(pop_|sum_)\w+', hdr + body + shared_hdr.split('// ---')[1])      # never as a member of the kernel's argument
   kernels = set(re.findall(r'void (\w+)\(const SawyerPolicyArgs a\)', hdr))
   assert kernels == {'sawyer_policy_rollout_kernel'} and 'sawyer_policy_rollout_kernel' in tool.KERNELS
   want = {'physics.hip': {'<10, 16, false>', '<15, 16, false>', '<15, 16, true>'}, 'physics_w8.hip': {'<10, 16, false>'}}

@@ -59,6 +59,35 @@ void launch_physics(const PArgs& a, hipStream_t st) {
   else physics_kernel<NV, 16, INTEGRATE><<<grid_for<NV, 16>(a.n), block_for<NV>(), 0, st>>>(a);
 }
 
+enum SawyerUse { kObserve, kReset, kStep };      // the rules of an env's cfg / st by what the entry point does: read the state | write what a rollout will read | step (nv, out given)
+bool sawyer_args_ok(SawyerUse use, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st, int32_t nv = 0, const earl_sawyer_out* out = nullptr) {
+  if (cfg->n < 0 || !st->qpos || !st->qvel || !st->mocap_pos || !st->goal) return false;
+  if (use == kObserve) return true;
+  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return false;   // (NULL is allowed without goal switching only: the reset clears the counter the rollout reads)
+  if (cfg->n_goal_rows > 0 && !cfg->goal_table) return false;
+  const bool dense_peg = cfg->obj_kind >= 1 && cfg->reward_type != 0;      // its reward reads what the reset keeps in obj_init, and the pad / grasp attachments
+  if (dense_peg && !st->obj_init) return false;
+  if (use == kReset) return true;
+  if (cfg->frame_skip < 0 || cfg->att_hand < 0 || cfg->att_right < 0 || cfg->att_left < 0 || cfg->att_obj < 0) return false;
+  if (dense_peg && (cfg->att_grasp < 0 || cfg->att_lpad < 0 || cfg->att_rpad < 0)) return false;
+  return !(nv == 15 && cfg->obj_kind >= 1 && out->info && !st->obj_init);     // (so does the peg's info dict: without it the rows were left unwritten)
+}
+// the launch form of a rollout of nv = 10 / 15, for the plain and the closed-loop entry point alike
+enum class SawyerForm { L64, DoorSliced, DoorW8, Door, PegSliced, Peg };
+int peg_slice() { return g_peg_sliced >= 2 ? g_peg_sliced : EARL_PEG_SLICE; }
+SawyerForm sawyer_form(int32_t nv, int n, int32_t T, const earl_sawyer_state* st, bool policy) {
+  if (g_lpe == 64) return SawyerForm::L64;                // (measurement builds: no policy form, the closed-loop entry point refuses them)
+  if (nv == 10) {
+    // variant 3 (measurement: the one-wave build under the peg's work queue, tools/bench_variant.py) has no policy kernel, so the closed loop reads it as 0, by batch
+    // size -- on purpose unlike the plain entry point, where 3 stays on the one-wave build at every batch size, also where the queue cannot run (no sched, T = 1)
+    const int v = policy && g_door_variant == 3 ? 0 : g_door_variant;
+    if (v == 3 && st->sched && T > 1) return SawyerForm::DoorSliced;
+    return v == 2 || (v == 0 && n > 4096) ? SawyerForm::DoorW8 : SawyerForm::Door;      // eight waves per CU: wins from two rounds of 4096 envs on
+  }
+  // more workgroups than the GPU holds at once (one four-wave workgroup = 16 envs per CU): time-sliced schedule, one persistent workgroup per CU
+  return st->sched && g_peg_sliced && grid_for<15, 16>(n) > cu_count() && T > 1 ? SawyerForm::PegSliced : SawyerForm::Peg;
+}
+
 std::mutex g_cone_mu;
 std::unordered_map<const void*, int> g_cone_seen;
 }  // namespace
@@ -115,40 +144,20 @@ int earl_physics_forward(const void* model, const earl_collision_model* col, int
 
 int earl_sawyer_rollout_clocked(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                 const float* action, int32_t T, const uint64_t* clock, const earl_sawyer_out* out, earl_stream_t stream) {
-  if (!model || !cfg || !st || !out || !action || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !out->obs) return EARL_ERR_ARG;
-  if (cfg->frame_skip < 0 || cfg->att_hand < 0 || cfg->att_right < 0 || cfg->att_left < 0 || cfg->att_obj < 0) return EARL_ERR_ARG;
-  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;   // (NULL is allowed without goal switching only)
-  if (cfg->n_goal_rows > 0 && !cfg->goal_table) return EARL_ERR_ARG;
-  if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && (!st->obj_init || cfg->att_grasp < 0 || cfg->att_lpad < 0 || cfg->att_rpad < 0))
-    return EARL_ERR_ARG;                                  // the peg's dense reward needs the reset-time state and the pad / grasp attachments
-  if (nv == 15 && cfg->obj_kind >= 1 && out->info && !st->obj_init) return EARL_ERR_ARG;     // (so does the peg's info dict: without it the rows were left unwritten)
+  if (!model || !cfg || !st || !out || !action || T < 0 || !out->obs || !sawyer_args_ok(kStep, cfg, st, nv, out)) return EARL_ERR_ARG;
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (nv != 10 && nv != 15) return EARL_ERR_ARG;
   if (int rc = check_cone(col, true, (hipStream_t)stream, "sawyer_rollout")) return rc;
   SawyerArgs a{model, col, *cfg, *st, action, T, *out, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
-  if (nv == 10 && g_lpe != 64 && g_door_variant == 3 && st->sched && T > 1) {
-    // (measurement switch: the single-wave build, four workgroups per CU, under the time-sliced work queue of the peg -- tools/bench_variant.py)
-    a.slice = g_peg_sliced >= 2 ? g_peg_sliced : EARL_PEG_SLICE;
-    sawyer_rollout_kernel<10, 16, true><<<4 * cu_count(), block_for<10>(), 0, (hipStream_t)stream>>>(a);
-    return launched("sawyer_rollout (door, time-sliced)");
+  switch (sawyer_form(nv, cfg->n, T, st, false)) {
+    case SawyerForm::DoorSliced: a.slice = peg_slice(); sawyer_rollout_kernel<10, 16, true><<<4 * cu_count(), block_for<10>(), 0, (hipStream_t)stream>>>(a);
+      return launched("sawyer_rollout (door, time-sliced)");
+    case SawyerForm::DoorW8: return earl_unit_w8_sawyer_rollout(&a, stream);
+    case SawyerForm::L64: earl_unit_l64_sawyer_rollout(&a, nv, stream); break;
+    case SawyerForm::Door: sawyer_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a); break;
+    case SawyerForm::PegSliced: a.slice = peg_slice(); sawyer_rollout_kernel<15, 16, true><<<cu_count(), block_for<15>(), 0, (hipStream_t)stream>>>(a); break;
+    case SawyerForm::Peg: sawyer_rollout_kernel<15, 16><<<grid_for<15, 16>(cfg->n), block_for<15>(), 0, (hipStream_t)stream>>>(a); break;
   }
-  if (nv == 10 && g_lpe != 64 && (g_door_variant == 2 || (g_door_variant == 0 && cfg->n > 4096)))
-    return earl_unit_w8_sawyer_rollout(&a, stream);      // eight waves per CU: wins from two rounds of 4096 envs on
-  if (nv == 10) {
-    if (g_lpe == 64) earl_unit_l64_sawyer_rollout(&a, 10, stream);
-    else sawyer_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
-  } else if (nv == 15) {
-    if (g_lpe == 64) earl_unit_l64_sawyer_rollout(&a, 15, stream);
-    else {
-      // more workgroups than the GPU holds at once (one four-wave workgroup = 16 envs per CU): time-sliced schedule, one persistent workgroup per CU
-      const int cus = cu_count();
-      if (st->sched && g_peg_sliced && grid_for<15, 16>(cfg->n) > cus && T > 1) {
-        a.slice = g_peg_sliced >= 2 ? g_peg_sliced : EARL_PEG_SLICE;
-        sawyer_rollout_kernel<15, 16, true><<<cus, block_for<15>(), 0, (hipStream_t)stream>>>(a);
-      } else sawyer_rollout_kernel<15, 16><<<grid_for<15, 16>(cfg->n), block_for<15>(), 0, (hipStream_t)stream>>>(a);
-    }
-  } else return EARL_ERR_ARG;
   return launched("sawyer_rollout");
 }
 int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
@@ -157,43 +166,31 @@ int earl_sawyer_rollout(const earl_link_model* model, const earl_collision_model
 }
 
 // include/earl_physics.h: T closed-loop env steps in one launch of the rollout kernel, the policy evaluated by the wave that owns the env -- one policy or a
-// population's member per env, every [T] output optional, per-env episode summaries.  The launch forms are
-// earl_sawyer_rollout's (door: four one-wave workgroups per CU, eight waves per CU above 4096 envs; peg: whole rollouts or the time-sliced queue); the 64-lane
-// measurement builds (earl_debug_set_physics_lanes(64)) and the door's time-sliced measurement variant have no policy form
+// population's member per env, every [T] output optional, per-env episode summaries.  The launch forms are earl_sawyer_rollout's, by the same rule (sawyer_form)
 // (the body of the closed-loop entry points: a population, summaries, an agent pair and its table of backward goals, each there or not)
 static int sawyer_closed_loop(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                               const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_agent_pair* pair, bool paired, const earl_backward_goals* goals,
                               const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_sawyer_out* out,
                               const earl_episode_summary* summary, earl_stream_t stream) {
-  if (!model || !cfg || !st || !out || !policy || !obs0 || T < 1 || cfg->n < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal) return EARL_ERR_ARG;
+  if (!model || !cfg || !st || !out || !policy || !obs0 || T < 1 || (nv != 10 && nv != 15) || !sawyer_args_ok(kStep, cfg, st, nv, out)) return EARL_ERR_ARG;      // (T = 0 is an error here)
   if (!out->obs && !st->last_obs) return EARL_ERR_ARG;    // (without out->obs the env's row of last_obs is the one observation row the launch keeps)
-  if (nv != 10 && nv != 15) return EARL_ERR_ARG;
   // the policy's contract (policy_check.h); the weight rows are read in 16-byte pieces, so params is aligned and every stride a multiple of 4 floats
   if (paired && !pair) return EARL_ERR_ARG;
   if (earl::contract::check_closed_loop(*policy, 14, 4, earl::contract::kParamsAligned16, head, pop, cfg->env_offset, cfg->n, paired ? pair : nullptr,
                                         cfg->goal_change_frequency, goals, cfg->n_goal_rows, nullptr))
     return EARL_ERR_ARG;
-  if (cfg->frame_skip < 0 || cfg->att_hand < 0 || cfg->att_right < 0 || cfg->att_left < 0 || cfg->att_obj < 0) return EARL_ERR_ARG;
-  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;
-  if (cfg->n_goal_rows > 0 && !cfg->goal_table) return EARL_ERR_ARG;
-  if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && (!st->obj_init || cfg->att_grasp < 0 || cfg->att_lpad < 0 || cfg->att_rpad < 0)) return EARL_ERR_ARG;
-  if (nv == 15 && cfg->obj_kind >= 1 && out->info && !st->obj_init) return EARL_ERR_ARG;
   if (g_lpe == 64) return EARL_ERR_ARG;                   // (the 64-lane measurement builds: no policy form)
   if (cfg->n == 0) return EARL_OK;
   if (int rc = check_cone(col, true, (hipStream_t)stream, "sawyer_policy_rollout")) return rc;
   SawyerPolicyArgs a;
   static_cast<SawyerArgs&>(a) = SawyerArgs{model, col, *cfg, *st, nullptr, T, *out, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
   fill_closed_loop(a, *policy, head, obs0, actions, pop, summary, paired ? pair : nullptr, goals, nullptr, 0);      // (the forward goals are cfg->goal_table's)
-  if (nv == 10) {
-    if (g_door_variant == 2 || (g_door_variant != 1 && cfg->n > 4096)) return earl_unit_w8_sawyer_policy_rollout(&a, stream);
-    sawyer_policy_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
-  } else {
-    const int cus = cu_count();
-    if (st->sched && g_peg_sliced && grid_for<15, 16>(cfg->n) > cus && T > 1) {
-      a.slice = g_peg_sliced >= 2 ? g_peg_sliced : EARL_PEG_SLICE;
-      sawyer_policy_rollout_kernel<15, 16, true><<<cus, block_for<15>(), 0, (hipStream_t)stream>>>(a);
-    } else sawyer_policy_rollout_kernel<15, 16><<<grid_for<15, 16>(cfg->n), block_for<15>(), 0, (hipStream_t)stream>>>(a);
+  switch (sawyer_form(nv, cfg->n, T, st, true)) {
+    case SawyerForm::DoorW8: return earl_unit_w8_sawyer_policy_rollout(&a, stream);
+    case SawyerForm::Door: sawyer_policy_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a); break;
+    case SawyerForm::PegSliced: a.slice = peg_slice(); sawyer_policy_rollout_kernel<15, 16, true><<<cu_count(), block_for<15>(), 0, (hipStream_t)stream>>>(a); break;
+    case SawyerForm::Peg: sawyer_policy_rollout_kernel<15, 16><<<grid_for<15, 16>(cfg->n), block_for<15>(), 0, (hipStream_t)stream>>>(a); break;
+    default: return EARL_ERR_ARG;                           // (L64 was refused above; the closed loop never gets DoorSliced)
   }
   return launched("sawyer_policy_rollout");
 }
@@ -226,14 +223,10 @@ int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collisio
 int earl_sawyer_reset(const earl_link_model* model, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                       const double* reset_qpos, const double* reset_qvel, const uint8_t* mask, double* obs,
                       earl_stream_t stream) {
-  if (!model || !cfg || !st || !reset_qpos || !reset_qvel || cfg->n < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal) return EARL_ERR_ARG;
+  if (!model || !cfg || !st || !reset_qpos || !reset_qvel || !sawyer_args_ok(kReset, cfg, st)) return EARL_ERR_ARG;
   if (cfg->obj_dof < 0 || cfg->obj_dof >= nv || cfg->obj_kind < 0 || cfg->obj_kind > 2) return EARL_ERR_ARG;
   if (cfg->obj_kind >= 1 && cfg->obj_dof + 6 > nv) return EARL_ERR_ARG;
   if (cfg->obj_kind == 2 && (cfg->n_wide <= 0 || !cfg->wide_table)) return EARL_ERR_ARG;
-  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;   // (the reset clears the counter the rollout will read)
-  if (cfg->n_goal_rows > 0 && !cfg->goal_table) return EARL_ERR_ARG;
-  if (cfg->obj_kind >= 1 && cfg->reward_type != 0 && !st->obj_init) return EARL_ERR_ARG;      // (the peg's dense reward reads what the reset keeps there)
   if (cfg->n == 0) return EARL_OK;
   SawyerArgs a{model, nullptr, *cfg, *st, nullptr, 0, earl_sawyer_out{nullptr, nullptr, nullptr, nullptr, nullptr}, reset_qpos, reset_qvel, mask, obs, 0, 0, nullptr};
   if (nv == 10) sawyer_reset_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);
@@ -244,8 +237,7 @@ int earl_sawyer_reset(const earl_link_model* model, int32_t nv, const earl_sawye
 
 int earl_sawyer_observe(const earl_link_model* model, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st, double* obs,
                         earl_stream_t stream) {
-  if (!model || !cfg || !st || !obs || cfg->n < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal) return EARL_ERR_ARG;
+  if (!model || !cfg || !st || !obs || !sawyer_args_ok(kObserve, cfg, st)) return EARL_ERR_ARG;
   if (cfg->n == 0) return EARL_OK;
   SawyerArgs a{model, nullptr, *cfg, *st, nullptr, 0, earl_sawyer_out{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, nullptr, obs, 1, 0, nullptr};
   if (nv == 10) sawyer_reset_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a);

@@ -14,6 +14,20 @@ namespace {
 
 #include "physics_launch.h"
 
+// the rules of an env's cfg / st that every entry point has; fused: the rollout kernels', which hold the attachment rows in 32 lanes and read the mocap orientation themselves
+static bool kitchen_args_ok(const earl_kitchen_cfg* cfg, const earl_kitchen_state* st, bool fused) {
+  if (cfg->n < 0 || cfg->n_att < 10 || cfg->frame_skip < 0 || (fused && (cfg->n_att > 32 || !cfg->mocap_quat_dev))) return false;
+  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !st->last_qp_robot || !st->att_xpos || !st->steps_since_reset || !st->last_obs) return false;
+  for (int k = 0; k < 8; ++k) if (cfg->site_att[k] < 0 || cfg->site_att[k] >= cfg->n_att) return false;
+  return true;
+}
+// the launch form of a fused rollout, for the plain and the closed-loop entry point alike: solo_mode's value, by default promoted to the multi-wave forms
+static int kitchen_solo(int n) {
+  const int solo = solo_mode(n);
+  if (g_solo < 0 && solo == 2) return 3;   // one env per workgroup: four waves per env (rows | mass matrix | bias forces | collision, then one wave's active set)
+  return g_solo < 0 && solo == 1 && n <= 2 * cu_count() ? 4 : solo;      // 4: at most two envs per CU: two envs per workgroup, two waves per env
+}
+
 extern "C" {
 
 void earl_unit_kitchen_physics(const void* pargs, int integrate, void* stream) {
@@ -24,11 +38,9 @@ void earl_unit_kitchen_physics(const void* pargs, int integrate, void* stream) {
 }
 int earl_kitchen_step(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                       const earl_kitchen_state* st, const float* action, const earl_kitchen_out* out, earl_stream_t stream) {
-  if (!model || !params || !cfg || !st || !action || !out || cfg->n < 0 || cfg->n_att < 10 || cfg->frame_skip < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !st->last_qp_robot || !st->att_xpos || !st->steps_since_reset || !st->last_obs) return EARL_ERR_ARG;
+  if (!model || !params || !cfg || !st || !action || !out || !kitchen_args_ok(cfg, st, false)) return EARL_ERR_ARG;
   if (!st->action64 || !st->ctrl9 || !st->qpos_bak || !st->qvel_bak || !st->sites || !st->bad || !st->mocap_bak || !st->att_bak || (cfg->sensor_noise && !st->noise)) return EARL_ERR_ARG;
   if (!out->obs || !out->reward || !out->done || !out->success) return EARL_ERR_ARG;
-  for (int k = 0; k < 8; ++k) if (cfg->site_att[k] < 0 || cfg->site_att[k] >= cfg->n_att) return EARL_ERR_ARG;
   const int n = cfg->n;
   if (n == 0) return EARL_OK;
   const hipStream_t hs = (hipStream_t)stream;
@@ -52,15 +64,11 @@ int earl_kitchen_step(const void* model, const earl_collision_model* col, const 
 
 int earl_kitchen_rollout_clocked(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                                  const earl_kitchen_state* st, const float* action, int32_t T, const uint64_t* clock, const earl_kitchen_out* out, earl_stream_t stream) {
-  if (!model || !params || !cfg || !st || !action || !out || cfg->n < 0 || T < 0 || cfg->n_att < 10 || cfg->n_att > 32 || cfg->frame_skip < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !st->last_qp_robot || !st->att_xpos || !st->steps_since_reset || !st->last_obs) return EARL_ERR_ARG;
-  if (!out->obs || !out->reward || !out->done || !out->success || !cfg->mocap_quat_dev) return EARL_ERR_ARG;
-  for (int k = 0; k < 8; ++k) if (cfg->site_att[k] < 0 || cfg->site_att[k] >= cfg->n_att) return EARL_ERR_ARG;
+  if (!model || !params || !cfg || !st || !action || !out || T < 0 || !kitchen_args_ok(cfg, st, true)) return EARL_ERR_ARG;
+  if (!out->obs || !out->reward || !out->done || !out->success) return EARL_ERR_ARG;
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "kitchen_rollout")) return rc;
-  KitchenRolloutArgs k{model, col, *params, *cfg, *st, *out, action, T, solo_mode(cfg->n), clock};
-  if (k.solo == 2 && g_solo < 0) k.solo = 3;   // one env per workgroup: four waves per env (rows | mass matrix | bias forces | collision, then one wave's active set)
-  if (g_solo < 0 && k.solo == 1 && cfg->n <= 2 * cu_count()) k.solo = 4;      // at most two envs per CU: two envs per workgroup, two waves per env
+  KitchenRolloutArgs k{model, col, *params, *cfg, *st, *out, action, T, kitchen_solo(cfg->n), clock};
   if (k.solo == 3) kitchen_rollout_kernel<1><<<cfg->n, block_for<23>(), 0, (hipStream_t)stream>>>(k);
   else if (k.solo == 4) kitchen_rollout_kernel<2><<<(cfg->n + 1) / 2, block_for<23>(), 0, (hipStream_t)stream>>>(k);
   else kitchen_rollout_kernel<0><<<solo_grid(cfg->n, k.solo, Lim<23>::WPB), block_for<23>(), 0, (hipStream_t)stream>>>(k);
@@ -75,10 +83,7 @@ static int kitchen_closed_loop(const void* model, const earl_collision_model* co
                                const earl_backward_goals* goals, const double* forward_goals, int32_t n_forward_goals, const earl_gaussian_head* head,
                                const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_kitchen_out* out,
                                const earl_episode_summary* summary, earl_stream_t stream) {
-  if (!model || !params || !cfg || !st || !policy || !obs0 || !out || cfg->n < 0 || T < 0 || cfg->n_att < 10 || cfg->n_att > 32 || cfg->frame_skip < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->mocap_pos || !st->goal || !st->last_qp_robot || !st->att_xpos || !st->steps_since_reset || !st->last_obs) return EARL_ERR_ARG;
-  if (!cfg->mocap_quat_dev) return EARL_ERR_ARG;
-  for (int k = 0; k < 8; ++k) if (cfg->site_att[k] < 0 || cfg->site_att[k] >= cfg->n_att) return EARL_ERR_ARG;
+  if (!model || !params || !cfg || !st || !policy || !obs0 || !out || T < 0 || !kitchen_args_ok(cfg, st, true)) return EARL_ERR_ARG;
   // the policy's contract (policy_check.h).  The reference clips the action silently, so an unbounded output is taken (unlike the minitaur's).  A population: groups
   // of 16 envs, every member's rows read in 16-byte pieces
   // (the kitchen has no lifelong switch of its own: goal_change_frequency 0; its forward goals come with the call)
@@ -90,10 +95,8 @@ static int kitchen_closed_loop(const void* model, const earl_collision_model* co
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "kitchen_policy_rollout")) return rc;
   KitchenPolicyArgs k;
-  static_cast<KitchenRolloutArgs&>(k) = KitchenRolloutArgs{model, col, *params, *cfg, *st, *out, nullptr, T, solo_mode(cfg->n), clock};
+  static_cast<KitchenRolloutArgs&>(k) = KitchenRolloutArgs{model, col, *params, *cfg, *st, *out, nullptr, T, kitchen_solo(cfg->n), clock};
   fill_closed_loop(k, *policy, head, obs0, actions, pop, summary, paired ? pair : nullptr, goals, forward ? forward_goals : nullptr, forward ? n_forward_goals : 0);
-  if (k.solo == 2 && g_solo < 0) k.solo = 3;      // the plain entry point's rule
-  if (g_solo < 0 && k.solo == 1 && cfg->n <= 2 * cu_count()) k.solo = 4;
   earl_unit_kitchen_policy_rollout(&k, stream);      // physics_kitchen_policy.hip holds the kernels
   return launched("kitchen_policy_rollout");
 }

@@ -29,41 +29,48 @@ bool mt_use_duo(int n) {
   return 16 * rounds_two < 10 * rounds_one;
 }
 
+// the launch form of a rollout, for the plain and the closed-loop entry point alike.  Duo: two waves per SIMD by role (minitaur_duo_kernel, 16 envs per workgroup of eight waves)
+enum class MtForm { Generic, Duo, Tree };      // for batches that fill the chip's wave slots in the packed form anyway; Generic: substep<22>, the comparison build (no policy form)
+MtForm minitaur_form(int n, int solo, int num_substeps) {
+  if (!g_mt_stepper) return MtForm::Generic;
+  return solo == 0 && num_substeps > 0 && (g_mt_duo > 0 || (g_mt_duo < 0 && mt_use_duo(n))) ? MtForm::Duo : MtForm::Tree;      // (num_substeps = 0: nothing to split)
+}
+// the rules of an env's cfg / st that every entry point has
+bool minitaur_args_ok(const earl_minitaur_cfg* cfg, const earl_minitaur_state* st) {
+  if (cfg->n < 0 || !cfg->goal_table || cfg->n_goals < 1) return false;
+  if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return false;
+  return cfg->goal_change_frequency <= 0 || st->steps_since_goal_change;   // (NULL is allowed without goal switching only: the reset clears the counter the rollout reads)
+}
+
 }  // namespace
 
 extern "C" {
 
 int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                                   const float* action, int32_t T, const uint64_t* clock, const earl_minitaur_out* out, earl_stream_t stream) {
-  if (!model24 || !cfg || !st || !out || !action || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
-  if (!out->obs || !out->reward || !out->done || !out->success || !cfg->goal_table || cfg->n_goals < 1 || cfg->num_substeps < 0) return EARL_ERR_ARG;
-  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;   // (NULL is allowed without goal switching only)
+  if (!model24 || !cfg || !st || !out || !action || T < 0 || !minitaur_args_ok(cfg, st)) return EARL_ERR_ARG;
+  if (!out->obs || !out->reward || !out->done || !out->success || cfg->num_substeps < 0) return EARL_ERR_ARG;
   if (cfg->n == 0 || T == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_rollout")) return rc;
   MinitaurArgs a{model24, col, *cfg, *st, *out, action, T, nullptr, nullptr, solo_mode(cfg->n), clock};
-  // two waves per SIMD by role (minitaur_duo_kernel: 16 envs per workgroup of eight waves) for batches that fill the chip's wave slots in the packed form anyway
-  if (g_mt_stepper && a.solo == 0 && cfg->num_substeps > 0 && (g_mt_duo > 0 || (g_mt_duo < 0 && mt_use_duo(cfg->n)))) {      // (num_substeps = 0: nothing to split)
+  const MtForm form = minitaur_form(cfg->n, a.solo, cfg->num_substeps);
+  if (form == MtForm::Duo) {
     minitaur_duo_kernel<<<(unsigned)((cfg->n + 16 * MT_DUO_PAIRS / 4 - 1) / (4 * MT_DUO_PAIRS)), 128 * MT_DUO_PAIRS, 0, (hipStream_t)stream>>>(a);
     return launched("minitaur_rollout (two waves per SIMD)");
   }
-  if (g_mt_stepper) minitaur_kernel<false, true><<<solo_grid(cfg->n, a.solo, EARL_MT_WPB), 64 * EARL_MT_WPB, 0, (hipStream_t)stream>>>(a);
+  if (form == MtForm::Tree) minitaur_kernel<false, true><<<solo_grid(cfg->n, a.solo, EARL_MT_WPB), 64 * EARL_MT_WPB, 0, (hipStream_t)stream>>>(a);
   else minitaur_kernel<false, false><<<solo_grid(cfg->n, a.solo, Lim<22>::WPB), block_for<22>(), 0, (hipStream_t)stream>>>(a);
   return launched("minitaur_rollout");
 }
 // include/earl_physics.h: T closed-loop env steps in one launch, the policy evaluated by the 32 lanes that own the env -- one policy or a population's member per env,
-// every [T] output optional, per-env episode summaries.  The launch forms are earl_minitaur_rollout_clocked's (one-wave kernel in its three shapes, two-wave kernel);
-// the generic substep<22> comparison build has no policy form
+// every [T] output optional, per-env episode summaries.  The launch forms are earl_minitaur_rollout_clocked's, by the same rule (minitaur_form)
 // (the body of the closed-loop entry points: a population, summaries, an agent pair and its table of backward goals, each there or not)
 static int minitaur_closed_loop(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                                 const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_agent_pair* pair, bool paired, const earl_backward_goals* goals,
                                 const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_minitaur_out* out,
                                 const earl_episode_summary* summary, earl_stream_t stream) {
-  if (!model24 || !cfg || !st || !out || !policy || !obs0 || T < 0 || cfg->n < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
+  if (!model24 || !cfg || !st || !out || !policy || !obs0 || T < 0 || !minitaur_args_ok(cfg, st) || cfg->num_substeps < 0) return EARL_ERR_ARG;
   if (!out->obs && !st->last_obs) return EARL_ERR_ARG;    // (without out->obs the env's row of last_obs is the one observation row the launch keeps)
-  if (!cfg->goal_table || cfg->n_goals < 1 || cfg->num_substeps < 0) return EARL_ERR_ARG;
-  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;
   // the policy's contract (policy_check.h).  The reference env raises on an action outside +-(1 + 0.01); a kernel cannot, and the open-loop replay of the returned
   // actions must not either: bounded policies only.  A population: groups of 16 envs, every member's rows read in 16-byte pieces
   // (the pair's handover IS the goal switch of autonomous RL: goal_change_frequency > 0 is refused with a pair -- both would draw with index 0xFFFE at the same step)
@@ -77,7 +84,7 @@ static int minitaur_closed_loop(const void* model24, const earl_collision_model*
   MinitaurPolicyArgs a;
   static_cast<MinitaurArgs&>(a) = MinitaurArgs{model24, col, *cfg, *st, *out, nullptr, T, nullptr, nullptr, solo_mode(cfg->n), clock};
   fill_closed_loop(a, *policy, head, obs0, actions, pop, summary, paired ? pair : nullptr, goals, nullptr, 0);      // (the forward goals are cfg->goal_table's)
-  if (a.solo == 0 && cfg->num_substeps > 0 && (g_mt_duo > 0 || (g_mt_duo < 0 && mt_use_duo(cfg->n)))) {      // the plain entry point's rule
+  if (minitaur_form(cfg->n, a.solo, cfg->num_substeps) == MtForm::Duo) {
     minitaur_policy_duo_kernel<<<(unsigned)((cfg->n + 16 * MT_DUO_PAIRS / 4 - 1) / (4 * MT_DUO_PAIRS)), 128 * MT_DUO_PAIRS, 0, (hipStream_t)stream>>>(a);
     return launched("minitaur_policy_rollout (two waves per SIMD)");
   }
@@ -109,10 +116,7 @@ int earl_minitaur_rollout(const void* model24, const earl_collision_model* col, 
 }
 int earl_minitaur_reset(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                         const uint8_t* mask, double* obs, earl_stream_t stream) {
-  if (!model24 || !cfg || !st || cfg->n < 0) return EARL_ERR_ARG;
-  if (!st->qpos || !st->qvel || !st->goal || !st->motor_param || !st->observed_torque || !st->overheat || !st->motor_enabled) return EARL_ERR_ARG;
-  if (!cfg->goal_table || !cfg->reset_qpos || cfg->n_goals < 1 || cfg->settle_steps < 0) return EARL_ERR_ARG;
-  if (cfg->goal_change_frequency > 0 && !st->steps_since_goal_change) return EARL_ERR_ARG;   // (the reset clears the counter the rollout will read)
+  if (!model24 || !cfg || !st || !minitaur_args_ok(cfg, st) || !cfg->reset_qpos || cfg->settle_steps < 0) return EARL_ERR_ARG;
   if (cfg->n == 0) return EARL_OK;
   if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_reset")) return rc;
   MinitaurArgs a{model24, col, *cfg, *st, earl_minitaur_out{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr, 0, mask, obs, solo_mode(cfg->n), nullptr};

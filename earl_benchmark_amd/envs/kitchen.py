@@ -21,7 +21,6 @@ right counter and the floor are not collided).  **PARITY WITH MUJOCO IS UNPINNED
 run here.  What is pinned: the numpy glue around the simulator (bit-exact on goldens recorded from the reference's own methods),
 the model tables' provenance, and the kernel against this build's CPU statement (oracle/physics_oracle.LinkModel).
 """
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -30,7 +29,7 @@ import torch
 from .. import _abi, glue, physics, tables
 from ..spaces import Box
 from . import physics_policy_rollout as closed_loop
-from .physics_step_graph import PhysicsStepGraph
+from .physics_env import PhysicsEnv
 
 INT32_MAX = 2**31 - 1
 FRAME_SKIP = 40                                           # kitchen_multitask_v0.py:40
@@ -52,8 +51,13 @@ class _Cfg(_abi.KitchenCfg):
   goal_change_frequency = 0
 
 
-class Kitchen:
+class Kitchen(PhysicsEnv):
   OBS_DIM, NV, N_ROBOT, N_OBJ = 46, 23, 9, 14
+  ENV, ACT_DIM, _OUT_STRUCT = 'the kitchen', N_ROBOT, _abi.KitchenOut      # (the reference clips the action silently, kitchen_multitask_v0.py:92: an unbounded policy is taken)
+  _HOST_LIFELONG = True               # (LifelongWrapper's goal switch is made by step(), on the host)
+  _GRAPH_COUNTER = 'counter'          # a captured step's sensor-noise draws: clock[0] + t
+  _STATE = ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'last_qp_robot', 'att', 'steps_since_reset', 'interventions', 'fail_count', 'lifelong_return_t',
+            'steps_since_goal_change', 'last_obs')
 
   def __init__(self, task='all_pairs', reward_type='dense', num_envs=1, device='cuda', seed=0, env_offset=0, scalar_api=None,
                sensor_noise=True, contacts=True, reset_at_goal=False, auto_reset=False, info='full'):
@@ -119,10 +123,6 @@ class Kitchen:
                                  fail_count=self.fail_count.data_ptr(), last_obs=self.last_obs.data_ptr(), **{k: v.data_ptr() for k, v in self._scr.items()})
     self.action_space = Box(-1.0, 1.0, (self.N_ROBOT,), np.float32)              # kitchen_multitask_v0.py:78-80
     self._last_success = torch.zeros(n, dtype=torch.bool, device=dev)
-    self._last_obs_stale = False      # last_obs no longer describes (state, goal): set by set_state() / reset_goal(), cleared by whatever rewrites every row
-    self.agent_phase = self.steps_in_phase = None      # the agent pair's per-env state (rollout_pair allocates it: 0 forward / 1 reset, steps spent in the phase)
-    self._pair_counts = None
-    self.backward_row = None          # [N] int32 once a pair launch has drawn from a table of backward goals: the row each env's reset goal came from, -1 = none yet
     self._forward_goals = torch.tensor(np.atleast_2d(self._goal_states), **kw).reshape(-1, 23).contiguous()      # [R, 23]: what a pair's forward entry draws from
     self.observation_space = Box(-8.0, 8.0, (self.OBS_DIM,), np.float64)         # :82-84
     with torch.cuda.device(dev):
@@ -131,13 +131,6 @@ class Kitchen:
     self.interventions.zero_()
 
   # ------------------------------------------------------------------ internals
-  @property
-  def unwrapped(self):
-    return self
-
-  def _stream(self):
-    return torch.cuda.current_stream(self.device).cuda_stream
-
   def _uniform(self, k, stream_id, lo, hi, n=None):
     n = self.num_envs if n is None else n
     out = torch.empty(n, k, dtype=torch.float64, device=self.device)
@@ -209,11 +202,8 @@ class Kitchen:
       a = torch.as_tensor(np.asarray(action, dtype=np.float32) if not torch.is_tensor(action) else action, device=self.device)
       a = a.to(torch.float32).reshape(n, self.N_ROBOT).contiguous()
       if out is None:
-        out = dict(obs=torch.empty(n, self.OBS_DIM, dtype=torch.float64, device=self.device), reward=torch.empty(n, dtype=torch.float64, device=self.device),
-                   done=torch.empty(n, dtype=torch.bool, device=self.device), success=torch.empty(n, dtype=torch.bool, device=self.device),
-                   status=torch.empty(n, dtype=torch.uint8, device=self.device))
-      o = _abi.KitchenOut(obs=out['obs'].data_ptr(), reward=out['reward'].data_ptr(), done=out['done'].data_ptr(), success=out['success'].data_ptr(),
-                          status=out['status'].data_ptr())
+        out = self._new_out(())
+      o = self._out_struct(out)
       self._cfg.counter = self._counter
       if self._fused_step:             # ONE launch: the fused rollout kernel with T = 1 (bit-identical to earl_kitchen_step's eight launches, tests/test_kitchen_gpu.py)
         _abi.check(self._lib.earl_kitchen_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._params), C.byref(self._cfg), C.byref(self._st),
@@ -242,48 +232,22 @@ class Kitchen:
       return obs[0].cpu().numpy(), float(rew[0]), bool(done[0]), info
     return obs, rew, done, info
 
-  def make_step_graph(self, T, policy=None):
-    """Closed-loop stepping without the per-call host cost: T step() launches (the fused rollout with T = 1, sensor noise drawn on the replay's counters)
-    captured into a HIP graph, replayed with one host call (see `PhysicsStepGraph`).  The lifelong goal switch runs on the host: ValueError with
-    goal_change_frequency > 0.  The graph's info is 'success' / 'is_successful' / 'status', not the full env_info."""
-    return PhysicsStepGraph(self, T, policy)
-
-  # hooks of PhysicsStepGraph: one captured step = the clocked fused launch with T = 1 into the graph's output rows
-  _graph_bounds = None
-
+  # hooks of PhysicsStepGraph: one captured step = the clocked fused launch with T = 1 into the graph's output rows (sensor noise drawn on the replay's counters).  The
+  # lifelong goal switch runs on the host and is refused; the graph's info is 'success' / 'is_successful' / 'status', not the full env_info
   def _graph_check(self):
     if int(self._cfg.goal_change_frequency) > 0:
       raise ValueError('kitchen: the lifelong goal switch runs on the host (goal_change_frequency > 0) and cannot be captured by make_step_graph')
 
-  def _new_graph_out(self, T):
-    n, kw = self.num_envs, dict(device=self.device)
-    return dict(obs=torch.empty(T, n, self.OBS_DIM, dtype=torch.float64, **kw), reward=torch.empty(T, n, dtype=torch.float64, **kw),
-                done=torch.empty(T, n, dtype=torch.bool, **kw), success=torch.empty(T, n, dtype=torch.bool, **kw), status=torch.empty(T, n, dtype=torch.uint8, **kw))
-
-  @contextlib.contextmanager
-  def _graph_capture(self):
-    c = self._cfg.counter
-    try:
-      yield
-    finally:
-      self._cfg.counter = c
-
   def _graph_step(self, t, action, out, clock):
-    o = _abi.KitchenOut(obs=out['obs'].data_ptr(), reward=out['reward'].data_ptr(), done=out['done'].data_ptr(), success=out['success'].data_ptr(),
-                        status=out['status'].data_ptr())
+    o = self._out_struct(out)
     self._cfg.counter = t                                  # the noise draws of the captured step t: clock[0] + t
     with torch.cuda.device(self.device):
       _abi.check(self._lib.earl_kitchen_rollout_clocked(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._params), C.byref(self._cfg),
                                                         C.byref(self._st), action.data_ptr(), 1, clock, C.byref(o), self._stream()), 'earl_kitchen_rollout_clocked')
 
-  def _graph_clock(self):
-    return self._counter, self.total_step_count
-
   def _graph_advance(self, T, out):
     self._counter += T
-    self.total_step_count += T
-    self._last_success = out['success'][-1]
-    self._last_obs_stale = False
+    super()._graph_advance(T, out)
 
   def _graph_info(self, out):
     return {'success': out['success'], 'is_successful': out['success'], 'status': out['status']}
@@ -329,8 +293,7 @@ class Kitchen:
                              ('success', (T, n), torch.bool), ('status', (T, n), torch.uint8)):
           if k not in res or res[k].shape != shape or res[k].dtype != dt:
             res[k] = torch.empty(shape, dtype=dt, **kw)
-        o = _abi.KitchenOut(obs=res['obs'].data_ptr(), reward=res['reward'].data_ptr(), done=res['done'].data_ptr(), success=res['success'].data_ptr(),
-                            status=res['status'].data_ptr())
+        o = self._out_struct(res)
         self._cfg.counter = self._counter
         _abi.check(self._lib.earl_kitchen_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._params), C.byref(self._cfg), C.byref(self._st),
                                                   a.data_ptr(), T, C.byref(o), self._stream()), 'earl_kitchen_rollout')
@@ -350,37 +313,6 @@ class Kitchen:
     return res
 
   # ------------------------------------------------------------------ closed loop, the policy inside the rollout kernel
-  def _new_out(self, lead):
-    n, kw = self.num_envs, dict(device=self.device)
-    return dict(obs=torch.empty(*lead, n, self.OBS_DIM, dtype=torch.float64, **kw), reward=torch.empty(*lead, n, dtype=torch.float64, **kw),
-                done=torch.empty(*lead, n, dtype=torch.bool, **kw), success=torch.empty(*lead, n, dtype=torch.bool, **kw),
-                status=torch.empty(*lead, n, dtype=torch.uint8, **kw))
-
-  def _check_policy(self, policy, who, population=False):
-    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy of this env's widths on this env's device; population=True (rollout_population,
-    evaluate_population): or a PolicyPopulation of them whose members cover this env's global ids.  The reference clips the action silently
-    (kitchen_multitask_v0.py:92): an unbounded output is taken"""
-    from ..policy import AgentPair, PolicyPopulation, require_widths
-    if isinstance(policy, PolicyPopulation) and not population:
-      raise NotImplementedError(f'{who}: a PolicyPopulation on the kitchen goes to rollout_population / evaluate_population ({who} takes one MLPPolicy / '
-                                'GaussianMLPPolicy per launch)')
-    if isinstance(policy, AgentPair):
-      raise NotImplementedError(f'{who}: an AgentPair on the kitchen goes to rollout_pair / evaluate_pair ({who} takes one policy per env and launch)')
-    if self.scalar_api:
-      raise ValueError(f'{who}: scalar_api returns one env\'s numpy rows; the closed-loop launch returns batched tensors (Kitchen(..., scalar_api=False))')
-    if int(self._cfg.goal_change_frequency) > 0:
-      raise ValueError(f'{who}: the kitchen\'s lifelong goal switch runs on the host (goal_change_frequency > 0) and cannot happen inside the launch, as make_step_graph says')
-    return require_widths(policy, who, self.OBS_DIM, self.N_ROBOT, env=self)
-
-  def _check_pair(self, pair, who):
-    """-> is it Gaussian; `pair`: an AgentPair or a PairPopulation of this env's widths on this env's device; batched tensors only, and no LifelongWrapper"""
-    from ..policy import require_widths
-    if self.scalar_api:
-      raise ValueError(f'{who}: scalar_api returns one env\'s numpy rows; the closed-loop launch returns batched tensors (Kitchen(..., scalar_api=False))')
-    if int(self._cfg.goal_change_frequency) > 0:
-      raise ValueError(f'{who}: the kitchen\'s lifelong goal switch runs on the host (goal_change_frequency > 0) and cannot happen inside the launch, as make_step_graph says')
-    return require_widths(pair, who, self.OBS_DIM, self.N_ROBOT, env=self, pair=True, pairs=True)
-
   @property
   def initial_states(self):
     """get_init_states(): the rows an AgentPair's backward_goal='initial_states' draws from ('initial' wants ONE row)"""
@@ -392,7 +324,7 @@ class Kitchen:
     physics_policy_rollout.pair_structs returns (earl_kitchen_agents_rollout, the forward table being the env's goal states).  The sensor-noise counter advances by T"""
     ptr = lambda k: None if out.get(k) is None else out[k].data_ptr()
     ref = lambda s: None if s is None else C.byref(s)
-    o = _abi.KitchenOut(obs=ptr('obs'), reward=ptr('reward'), done=ptr('done'), success=ptr('success'), status=ptr('status'))
+    o = self._out_struct(out)
     pop = getattr(policy, 'pop_struct', None)              # a PolicyPopulation: the env with global id g runs member g // envs_per_policy
     self._cfg.counter = self._counter
     if pair is not None:
@@ -405,54 +337,9 @@ class Kitchen:
       return
     with torch.cuda.device(self.device):
       _abi.check(self._lib.earl_kitchen_population_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._params), C.byref(self._cfg), C.byref(self._st),
-                                                           C.byref(policy.struct), None if pop is None else C.byref(pop), None if head is None else C.byref(head),
-                                                           obs0.data_ptr(), T, None, ptr('actions'), C.byref(o), None if summary is None else C.byref(summary),
+                                                           C.byref(policy.struct), ref(pop), ref(head), obs0.data_ptr(), T, None, ptr('actions'), C.byref(o), ref(summary),
                                                            self._stream()), 'earl_kitchen_population_rollout')
     self._counter += T
-
-  def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """physics_policy_rollout's closed loop (its docstring is the contract) on earl_kitchen_policy_rollout: `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy` built
-    with obs_dim=46, act_dim=9 (bounded or not: the env clips), evaluated by the 32 lanes that own the env.  The policy sees the observation rows as emitted, sensor
-    noise included; after set_state() / reset_goal() its first observation is a fresh reading (one noise draw: the counter advances by T + 1).
-    -> rollout()'s dict plus 'actions' [T, N, 9] and, with return_noise=True, 'eps' [T, N, 9]"""
-    return closed_loop.rollout_policy(self, policy, T, reset_first, sample, return_noise, out)
-
-  def rollout_agents(self, pair, T, **kw):
-    raise NotImplementedError('rollout_agents: an AgentPair on the kitchen goes to rollout_pair / evaluate_pair (rollout_agents is the tabletop\'s, the Sawyer door\'s '
-                              'and the Sawyer peg\'s name for it)')
-
-  def rollout_pair(self, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """physics_policy_rollout.rollout_pair (its docstring is the contract) on earl_kitchen_agents_rollout: `pair` -- an `AgentPair(..., obs_dim=46, act_dim=9)` or a
-    `PairPopulation` of them.  A goal row is a qpos of 23 values; backward_goal='initial_states' is the table of get_init_states() (the reference resets from its six
-    'all_pairs' rows), 'initial' its one row where there is one; entering the forward phase the goal becomes a row of the env's goal states.  Batched tensors only
-    (scalar_api=False), not under a LifelongWrapper.
-    -> rollout_policy()'s dict plus 'agent' [T, N] int8 and, with a table of backward goals, 'backward_row' [T, N] int32"""
-    return closed_loop.rollout_pair(self, pair, T, reset_first, sample, return_noise, out)
-
-  def evaluate_pair(self, pair, T, sample=True):
-    """physics_policy_rollout.evaluate_pair on earl_kitchen_agents_rollout: T steps of `pair` from the current state with per-env summaries only.
-    -> {'ret', 'success', 'first_success', 'guard_steps', 'forward_success', 'backward_success'}, each [N]"""
-    return closed_loop.evaluate_pair(self, pair, T, sample)
-
-  @property
-  def pair_counts(self):
-    """(forward_success, backward_success) [N] int32 of the last pair launch: the phases that ended by success; None before the first"""
-    return self._pair_counts
-
-  def evaluate_policy(self, policy, T, **kw):
-    raise NotImplementedError('evaluate_policy: episode summaries on the kitchen are evaluate_population\'s (it takes one policy as well as a PolicyPopulation); '
-                              'evaluate_policy runs on the tabletop, the Sawyer door and the Sawyer peg')
-
-  def rollout_population(self, pop, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """rollout_policy for a `PolicyPopulation(..., obs_dim=46, act_dim=9)`: the env with global id g runs member g // envs_per_policy, every member in the ONE
-    launch (physics_policy_rollout.rollout_population; earl_kitchen_population_rollout).  -> rollout_policy's dict"""
-    return closed_loop.rollout_population(self, pop, T, reset_first, sample, return_noise, out)
-
-  def evaluate_population(self, policy_or_pop, T, episodes=1, sample=False, reset_first=True):
-    """physics_policy_rollout.evaluate (its docstring is the contract) on earl_kitchen_population_rollout: per-env episode summaries of one policy or of a
-    `PolicyPopulation`, no tensor with a T axis.  The sensor-noise counter advances by T per launch (plus the fresh reading when last_obs is stale).
-    -> {'ret', 'success', 'first_success', 'guard_steps'}, each [episodes, N]"""
-    return closed_loop.evaluate(self, 'evaluate_population', policy_or_pop, T, episodes, sample, reset_first)
 
   def _get_obs_t(self):
     """a fresh reading as _get_obs() makes it (a noise draw on the current counter, last_qp_robot updated), as the [N, 46] tensor whatever scalar_api says, and
@@ -493,46 +380,8 @@ class Kitchen:
   def get_next_goal(self):
     return self._goal_states[0]
 
-  def reset_goal(self, goal=None, mask=None):
-    g = torch.as_tensor(self.get_next_goal() if goal is None else goal, dtype=torch.float64, device=self.device).expand(self.num_envs, 23)
-    if mask is None:
-      self.goal_t.copy_(g)
-    else:
-      m = torch.as_tensor(mask, device=self.device).bool()
-      self.goal_t[m] = g[m]
-    self._last_obs_stale = True                            # (last_obs carries the old goal entries: rollout_policy takes a fresh reading first)
-
   def get_task(self):
     return self._task
 
   def get_init_states(self):
     return self._initial_states
-
-  @property
-  def goal(self):
-    return self.goal_t[0].cpu().numpy() if self.scalar_api else self.goal_t
-
-  def set_state(self, qpos, qvel):
-    self._last_obs_stale = True                            # (last_obs no longer belongs to the state: rollout_policy takes a fresh reading first)
-    self.qpos.copy_(torch.as_tensor(qpos, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.NV))
-    self.qvel.copy_(torch.as_tensor(qvel, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.NV))
-
-  def state_dict(self):
-    keys = ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'last_qp_robot', 'att', 'steps_since_reset', 'interventions', 'fail_count', 'lifelong_return_t',
-            'steps_since_goal_change', 'last_obs')
-    return {k: getattr(self, k).clone() for k in keys} | {'counter': self._counter, 'total_step_count': self.total_step_count,
-                                                          'last_obs_stale': bool(self._last_obs_stale)} | closed_loop.pair_state_dict(self)
-
-
-  def load_state_dict(self, sd):
-    self._last_obs_stale = bool(sd.get('last_obs_stale', False))      # (a dict written before the flag existed: not stale)
-    closed_loop.load_pair_state(self, sd)
-    for k, v in sd.items():
-      if k == 'last_obs_stale' or k in closed_loop.PAIR_STATE:
-        continue
-      if k == 'counter':
-        self._counter = int(v)
-      elif k == 'total_step_count':
-        self.total_step_count = int(v)
-      else:
-        getattr(self, k).copy_(v)

@@ -13,7 +13,6 @@ this build's own authoring on this build's own stepper (MuJoCo-style soft constr
 [UPSTREAM pybullet_envs.bullet.minitaur_env_randomizer, restated from memory] is built in the reset kernel: battery voltage, motor damping, base /
 leg-link / motor masses, foot friction, through the semantics of the reference's own setters (envs/minitaur.py:468-508).  DESIGN.md section 14.
 """
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -22,7 +21,7 @@ import torch
 from .. import _abi, physics
 from ..spaces import Box
 from . import physics_policy_rollout as closed_loop
-from .physics_step_graph import PhysicsStepGraph
+from .physics_env import PhysicsEnv
 
 INT32_MAX = 2**31 - 1
 NUM_SUBSTEPS, SETTLE_STEPS = 5, 100                       # minitaur_gym_env.py:25, 161-164; :265-269
@@ -56,8 +55,14 @@ class _Cfg(_abi.MinitaurCfg):
   pass
 
 
-class Minitaur:
-  OBS_DIM, NV, NQ = OBS_DIM, 22, 23
+class Minitaur(PhysicsEnv):
+  OBS_DIM, ACT_DIM, NV, NQ = OBS_DIM, ACT_DIM, 22, 23
+  ENV, _OUT_STRUCT = 'the minitaur', _abi.MinitaurOut
+  _BOUNDED = ACTION_BOUND + ACTION_EPS                     # minitaur_gym_env.py:276-281: the reference raises outside it, so a policy's output is bounded
+  _PAIR_LIFELONG = 'a LifelongWrapper (goal_change_frequency > 0)'
+  _graph_bounds = (-ACTION_BOUND - ACTION_EPS, ACTION_BOUND + ACTION_EPS)      # (flagged per step, see _actions)
+  _STATE = ('qpos', 'qvel', 'goal_t', 'motor_param', 'observed_torque', 'overheat', 'motor_enabled', 'steps_since_reset', 'steps_since_goal_change',
+            'interventions', 'fail_count', 'lifelong_return_t', 'last_obs')
 
   def __init__(self, num_envs=1, device='cuda', seed=0, env_offset=0, scalar_api=None, env_randomizer=True, contacts=True, reset_at_goal=False,
                auto_reset=False, reward_type='dense'):
@@ -105,31 +110,8 @@ class Minitaur:
     self.observation_space = Box(-np.inf, np.inf, (self.OBS_DIM,), np.float32)        # :179, :481-488
     self._counter = 0
     self._last_success = torch.zeros(n, dtype=torch.bool, device=dev)
-    self.agent_phase = self.steps_in_phase = None      # the agent pair's per-env state (rollout_pair allocates it: 0 forward / 1 reset, steps spent in the phase)
-    self._pair_counts = None
-    self.backward_row = None          # [N] int32 once a pair launch has drawn from a table of backward goals: the row each env's reset goal came from, -1 = none yet
-    self._last_obs_stale = False      # last_obs no longer describes (state, goal): set by set_state() / reset_goal(), cleared by whatever rewrites every row
     self.reset()
     self.interventions.zero_()
-
-  # ------------------------------------------------------------------ internals
-  @property
-  def unwrapped(self):
-    return self
-
-  def _stream(self):
-    return torch.cuda.current_stream(self.device).cuda_stream
-
-  def _new_out(self, lead):
-    kw = dict(device=self.device)
-    return dict(obs=torch.empty(*lead, self.num_envs, self.OBS_DIM, dtype=torch.float64, **kw), reward=torch.empty(*lead, self.num_envs, dtype=torch.float64, **kw),
-                done=torch.empty(*lead, self.num_envs, dtype=torch.bool, **kw), success=torch.empty(*lead, self.num_envs, dtype=torch.bool, **kw),
-                status=torch.empty(*lead, self.num_envs, dtype=torch.uint8, **kw))
-
-  @staticmethod
-  def _out_struct(res):
-    return _abi.MinitaurOut(obs=res['obs'].data_ptr(), reward=res['reward'].data_ptr(), done=res['done'].data_ptr(), success=res['success'].data_ptr(),
-                            status=res['status'].data_ptr())
 
   # ------------------------------------------------------------------ gym-style API
   def reset(self, mask=None):
@@ -172,26 +154,6 @@ class Minitaur:
         closed_loop.finish(self, T, res['reward'], res['success'][-1])
     return res
 
-  def _check_policy(self, policy, who, population=False):
-    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy of this env's widths on this env's device whose output is bounded; population=True
-    (rollout_population, evaluate_population): or a PolicyPopulation of them whose members cover this env's global ids"""
-    from ..policy import AgentPair, PolicyPopulation, require_widths
-    if isinstance(policy, PolicyPopulation) and not population:
-      raise NotImplementedError(f'{who}: a PolicyPopulation on the minitaur goes to rollout_population / evaluate_population ({who} takes one MLPPolicy / '
-                                'GaussianMLPPolicy per launch)')
-    if isinstance(policy, AgentPair):
-      raise NotImplementedError(f'{who}: an AgentPair on the minitaur goes to rollout_pair / evaluate_pair ({who} takes one policy per env and launch)')
-    return require_widths(policy, who, OBS_DIM, ACT_DIM, env=self, bounded=ACTION_BOUND + ACTION_EPS)
-
-  def _check_pair(self, pair, who):
-    """-> is it Gaussian; `pair`: an AgentPair or a PairPopulation of this env's widths on this env's device whose output is bounded, and no LifelongWrapper"""
-    from ..policy import require_widths
-    gaussian = require_widths(pair, who, OBS_DIM, ACT_DIM, env=self, pair=True, bounded=ACTION_BOUND + ACTION_EPS, pairs=True)
-    if self._cfg.goal_change_frequency > 0:
-      raise ValueError(f'{who}: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
-                       'not under a LifelongWrapper (goal_change_frequency > 0), whose clock would fight the pair\'s over the same draw')
-    return gaussian
-
   @property
   def initial_states(self):
     """[1, 2]: where the reset pose stands (x, y), the goal row an AgentPair's backward_goal='initial' resolves to"""
@@ -204,7 +166,7 @@ class Minitaur:
     self._cfg.step_counter = self.total_step_count
     ptr = lambda k: None if out.get(k) is None else out[k].data_ptr()
     ref = lambda s: None if s is None else C.byref(s)
-    o = _abi.MinitaurOut(obs=ptr('obs'), reward=ptr('reward'), done=ptr('done'), success=ptr('success'), status=ptr('status'))
+    o = self._out_struct(out)
     pop = getattr(policy, 'pop_struct', None)              # a PolicyPopulation: the env with global id g runs member g // envs_per_policy
     if pair is not None:
       with torch.cuda.device(self.device):
@@ -214,50 +176,8 @@ class Minitaur:
       return
     with torch.cuda.device(self.device):
       _abi.check(self._lib.earl_minitaur_population_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), C.byref(policy.struct),
-                                                            None if pop is None else C.byref(pop), None if head is None else C.byref(head), obs0.data_ptr(), T, None,
-                                                            ptr('actions'), C.byref(o), None if summary is None else C.byref(summary), self._stream()),
+                                                            ref(pop), ref(head), obs0.data_ptr(), T, None, ptr('actions'), C.byref(o), ref(summary), self._stream()),
                  'earl_minitaur_population_rollout')
-
-  def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """physics_policy_rollout's closed loop (its docstring is the contract) on earl_minitaur_policy_rollout: `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy` built with
-    obs_dim=32, act_dim=8 and a bounded output (out_act='tanh' / squash=True), evaluated by the 32 lanes that own the env.
-    -> rollout()'s dict plus 'actions' [T, N, 8] and, with return_noise=True, 'eps' [T, N, 8]"""
-    return closed_loop.rollout_policy(self, policy, T, reset_first, sample, return_noise, out)
-
-  def rollout_agents(self, pair, T, **kw):
-    raise NotImplementedError('rollout_agents: an AgentPair on the minitaur goes to rollout_pair / evaluate_pair (rollout_agents is the tabletop\'s, the Sawyer door\'s '
-                              'and the Sawyer peg\'s name for it)')
-
-  def rollout_pair(self, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """physics_policy_rollout.rollout_pair (its docstring is the contract) on earl_minitaur_agents_rollout: `pair` -- an `AgentPair(..., obs_dim=32, act_dim=8)` of
-    bounded agents or a `PairPopulation` of them.  A goal row is (x, y); backward_goal='initial' is the reset pose's, and entering the forward phase the goal becomes a
-    row of the env's twelve goal locations.  Not under a LifelongWrapper.
-    -> rollout_policy()'s dict plus 'agent' [T, N] int8 and, with a table of backward goals, 'backward_row' [T, N] int32"""
-    return closed_loop.rollout_pair(self, pair, T, reset_first, sample, return_noise, out)
-
-  def evaluate_pair(self, pair, T, sample=True):
-    """physics_policy_rollout.evaluate_pair on earl_minitaur_agents_rollout: T steps of `pair` from the current state with per-env summaries only.
-    -> {'ret', 'success', 'first_success', 'guard_steps', 'forward_success', 'backward_success'}, each [N]"""
-    return closed_loop.evaluate_pair(self, pair, T, sample)
-
-  @property
-  def pair_counts(self):
-    """(forward_success, backward_success) [N] int32 of the last pair launch: the phases that ended by success; None before the first"""
-    return self._pair_counts
-
-  def evaluate_policy(self, policy, T, **kw):
-    raise NotImplementedError('evaluate_policy: episode summaries on the minitaur are evaluate_population\'s (it takes one policy as well as a PolicyPopulation); '
-                              'evaluate_policy runs on the tabletop, the Sawyer door and the Sawyer peg')
-
-  def rollout_population(self, pop, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """rollout_policy for a `PolicyPopulation(..., obs_dim=32, act_dim=8)` of bounded policies: the env with global id g runs member g // envs_per_policy, every
-    member in the ONE launch (physics_policy_rollout.rollout_population; earl_minitaur_population_rollout).  -> rollout_policy's dict"""
-    return closed_loop.rollout_population(self, pop, T, reset_first, sample, return_noise, out)
-
-  def evaluate_population(self, policy_or_pop, T, episodes=1, sample=False, reset_first=True):
-    """physics_policy_rollout.evaluate (its docstring is the contract) on earl_minitaur_population_rollout: per-env episode summaries of one policy or of a
-    `PolicyPopulation`, no tensor with a T axis.  -> {'ret', 'success', 'first_success', 'guard_steps'}, each [episodes, N]"""
-    return closed_loop.evaluate(self, 'evaluate_population', policy_or_pop, T, episodes, sample, reset_first)
 
   def step(self, action):
     """-> (obs [N,32], reward [N], done [N], info{success, status}); gym 4-tuple of numpy / python scalars with scalar_api"""
@@ -267,28 +187,8 @@ class Minitaur:
       return obs[0].cpu().numpy(), float(rew[0]), bool(done[0]), {'success': float(suc[0])}
     return obs, rew, done, {'success': suc, 'status': res['status'][0]}
 
-  def make_step_graph(self, T, policy=None):
-    """Closed-loop stepping without the per-call host cost: T step() launches captured into a HIP graph, replayed with one host call (see `PhysicsStepGraph`).
-    An out-of-bounds action cannot raise inside the graph: g.check_actions() raises the reference's ValueError after a replay."""
-    return PhysicsStepGraph(self, T, policy)
-
-  # hooks of PhysicsStepGraph: one captured step = the clocked T = 1 launch into the graph's output rows
-  _graph_bounds = (-ACTION_BOUND - ACTION_EPS, ACTION_BOUND + ACTION_EPS)      # minitaur_gym_env.py:276-281 (flagged per step, see _actions)
-
-  def _graph_check(self):
-    pass
-
-  def _new_graph_out(self, T):
-    return self._new_out((T,))
-
-  @contextlib.contextmanager
-  def _graph_capture(self):
-    sc = self._cfg.step_counter
-    try:
-      yield
-    finally:
-      self._cfg.step_counter = sc
-
+  # hook of PhysicsStepGraph: one captured step = the clocked T = 1 launch into the graph's output rows; an out-of-bounds action cannot raise inside the graph:
+  # g.check_actions() raises the reference's ValueError after a replay
   def _graph_step(self, t, action, out, clock):
     self._cfg.step_counter = t                             # the goal-switch draws of the captured step t: clock[1] + t
     with torch.cuda.device(self.device):
@@ -296,14 +196,6 @@ class Minitaur:
                                                          clock, C.byref(self._out_struct(out)), self._stream()), 'earl_minitaur_rollout_clocked')
       if int(self._cfg.goal_change_frequency) > 0:
         self.lifelong_return_t += out['reward'].reshape(1, -1).sum(0)
-
-  def _graph_clock(self):
-    return self._counter, self.total_step_count
-
-  def _graph_advance(self, T, out):
-    self.total_step_count += T
-    self._last_obs_stale = False
-    self._last_success = out['success'][-1]
 
   def _graph_info(self, out):
     return {'success': out['success'], 'status': out['status']}
@@ -343,40 +235,4 @@ class Minitaur:
 
   def reset_goal(self, goal=None, mask=None):
     g = self.get_next_goal() if goal is None else np.asarray(goal, np.float64)
-    g = g[-2:] if g.shape[-1] == 30 else g                                          # :484-487
-    g = torch.as_tensor(g, dtype=torch.float64, device=self.device).expand(self.num_envs, 2)
-    if mask is None:
-      self.goal_t.copy_(g)
-    else:
-      m = torch.as_tensor(mask, device=self.device).bool()
-      self.goal_t[m] = g[m]
-    self._last_obs_stale = True                            # (last_obs carries the old goal entries: rollout_policy recomputes its first observation)
-
-  @property
-  def goal(self):
-    return self.goal_t[0].cpu().numpy() if self.scalar_api else self.goal_t
-
-  def set_state(self, qpos, qvel):
-    self._last_obs_stale = True                            # (last_obs no longer belongs to the state: rollout_policy recomputes its first observation)
-    self.qpos.copy_(torch.as_tensor(qpos, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.NQ))
-    self.qvel.copy_(torch.as_tensor(qvel, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.NV))
-
-  _STATE = ('qpos', 'qvel', 'goal_t', 'motor_param', 'observed_torque', 'overheat', 'motor_enabled', 'steps_since_reset', 'steps_since_goal_change',
-            'interventions', 'fail_count', 'lifelong_return_t', 'last_obs')
-
-  def state_dict(self):
-    return {k: getattr(self, k).clone() for k in self._STATE} | {'counter': self._counter, 'total_step_count': self.total_step_count,
-                                                                 'last_obs_stale': bool(self._last_obs_stale)} | closed_loop.pair_state_dict(self)
-
-  def load_state_dict(self, sd):
-    self._last_obs_stale = bool(sd.get('last_obs_stale', False))      # (a dict written before the flag existed: not stale)
-    closed_loop.load_pair_state(self, sd)
-    for k, v in sd.items():
-      if k == 'last_obs_stale' or k in closed_loop.PAIR_STATE:
-        continue
-      if k == 'counter':
-        self._counter = int(v)
-      elif k == 'total_step_count':
-        self.total_step_count = int(v)
-      else:
-        getattr(self, k).copy_(v)
+    super().reset_goal(g[-2:] if g.shape[-1] == 30 else g, mask)                    # :484-487

@@ -1,13 +1,13 @@
 """The closed loop of the stepper envs (door, peg, minitaur, kitchen): what the envs share around the ONE launch of their rollout kernel with a policy inside it
 (include/earl_physics.h: earl_{sawyer,minitaur,kitchen}_population_rollout and earl_{sawyer,minitaur,kitchen}_agents_rollout), next to `PhysicsStepGraph`.  Every
-function below takes the env and serves all of them; the env's side is ONE set of hooks:
-  `_check_policy(policy, who, population=False)` -> is it Gaussian (policy.require_widths with the env's widths and rules; population=True: a PolicyPopulation is taken
-      as well, its members checked against the env's global ids -- the Sawyer envs take one everywhere);
+function below takes the env and serves all of them; the env's side is ONE set of hooks, held by `PhysicsEnv` (envs/physics_env.py) unless said otherwise:
+  `_check_policy(policy, who, population=False)` -> is it Gaussian (policy.require_widths with the env's widths and rules, the subclass's class data; population=True:
+      a PolicyPopulation is taken as well, its members checked against the env's global ids -- the Sawyer envs take one everywhere);
   `_check_pair(pair, who)` -> is it Gaussian, for an AgentPair or a PairPopulation;
-  `_launch_policy(policy, head, obs0, T, out, summary=None, pair=None)`: the launch itself.  `out` may lack any key, 'obs' included (the env's row of last_obs then
-      carries the observation); summary: None or an _abi.EpisodeSummary; pair: None, or what `pair_structs` returns;
-  `_new_out((T,))`, and optionally `_new_pair_out((T,))` where a pair launch offers other keys (the door: no 'info'); `reset()`; `last_obs` / `_last_obs_stale` /
-      `_get_obs_t()`; the pair's state `agent_phase` / `steps_in_phase` / `backward_row` (None until `pair_structs` allocates it) and `_pair_counts`.
+  `_launch_policy(policy, head, obs0, T, out, summary=None, pair=None)`, the subclass's: the launch itself.  `out` may lack any key, 'obs' included (the env's row of
+      last_obs then carries the observation); summary: None or an _abi.EpisodeSummary; pair: None, or what `pair_structs` returns;
+  `_new_out((T,))`, and optionally `_new_pair_out((T,))` where a pair launch offers other keys (the door: no 'info'); the subclass's `reset()` and `_get_obs_t()`;
+      `last_obs` / `_last_obs_stale`; the pair's state `agent_phase` / `steps_in_phase` / `backward_row` (None until `pair_structs` allocates it) and `_pair_counts`.
 The public names differ by env for history's sake -- the Sawyer envs' rollout_agents / evaluate_agents / evaluate_policy are rollout_pair / evaluate_pair / evaluate
 here -- so each takes `who`, the name its messages carry.
 

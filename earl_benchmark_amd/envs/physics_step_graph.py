@@ -5,6 +5,9 @@ step makes is keyed by a counter the host passes BY VALUE in the cfg struct (the
 sensor noise: `counter`), and a capture would freeze that value.  So the captured launch of step t passes the OFFSET t, and the kernel adds a base it
 reads from a device word when it runs (`clock[0]` for `counter`, `clock[1]` for `step_counter`); replay() writes both words from the env's host
 counters before every replay.  A replay is then bit-identical to T eager step() calls.
+
+The env's side is ONE set of hooks on `PhysicsEnv` (envs/physics_env.py): `_graph_check`, `_new_graph_out`, `_graph_capture`, `_graph_clock`, `_graph_advance` and
+`_graph_bounds` are the base's (the cfg field a capture restores and the bounds are the subclass's class data); `_graph_step` and `_graph_info` are the subclass's.
 """
 import torch
 

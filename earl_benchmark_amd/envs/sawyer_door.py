@@ -12,7 +12,6 @@ pinned: the sparse success rule (bit-exact on the reference's demonstrations), t
 (the reference's recorded handle / hand positions), the reset pose (6 mm).  `SawyerXYZEnv.step` semantics are upstream
 metaworld behaviour restated from SURVEY.md Appendix D.
 """
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -21,7 +20,7 @@ import torch
 from .. import _abi, physics
 from ..spaces import Box
 from . import physics_policy_rollout as closed_loop
-from .physics_step_graph import PhysicsStepGraph
+from .physics_env import PhysicsEnv
 
 INT32_MAX = 2**31 - 1
 
@@ -47,10 +46,15 @@ def _ptr(t):
   return None if t is None else t.data_ptr()
 
 
-class SawyerDoor:
+class SawyerDoor(PhysicsEnv):
   """N independent Sawyer door envs; state (qpos, qvel, mocap) lives in HBM, every call is one kernel launch."""
 
-  OBS_DIM = 14
+  OBS_DIM, ACT_DIM = 14, 4
+  _OUT_STRUCT, _REWARD_DTYPE = _abi.SawyerOut, torch.float32
+  _POLICY_TAKES_POPULATION = True
+  _STATE = ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'steps_since_reset', 'interventions', 'steps_since_goal_change', 'lifelong_return_t', 'obj_init', 'last_obs',
+            'fail_count')
+  _STALE_WITHOUT_ROW = True                  # (a dict without the row leaves the env's own, which belongs to another state)
   MODEL = 'sawyer_door'
   RECORDED_HAND_INIT = (0.0, 0.4, 0.2)       # where the recorded episodes reset the hand (sawyer_door.py:33; reset_at_goal=True resets it elsewhere)
 
@@ -108,10 +112,6 @@ class SawyerDoor:
     self.lifelong_return_t = torch.zeros(n, dtype=torch.float64, **kw)
     self.last_obs = torch.zeros(n, self.OBS_DIM, dtype=torch.float64, **kw)   # SawyerXYZEnv._last_stable_obs [UPSTREAM]
     self.fail_count = torch.zeros(n, dtype=torch.int32, **kw)                 # env steps rolled back by the failure guard (include/earl_physics.h)
-    self.agent_phase = self.steps_in_phase = None      # the agent pair's per-env state (rollout_agents allocates it: 0 forward / 1 reset, steps spent in the phase)
-    self._pair_counts = None
-    self.backward_row = None          # [N] int32 once a pair launch has drawn from a table of backward goals: the row each env's reset goal came from, -1 = none yet
-    self._last_obs_stale = False      # last_obs no longer describes (state, goal): set by set_state() / reset_goal(), cleared by whatever rewrites every row
     self.total_step_count = 0
 
     cfg = _abi.SawyerCfg(n=n, env_offset=int(env_offset), reward_type=_abi.REWARD_TYPES[reward_type], horizon=INT32_MAX,
@@ -170,11 +170,13 @@ class SawyerDoor:
 
   # ------------------------------------------------------------------ internals
   @property
-  def unwrapped(self):
-    return self
+  def _counter(self):
+    """the reset counter, which this env keeps in its cfg (the base reads and writes it under this name)"""
+    return int(self._cfg.counter)
 
-  def _stream(self):
-    return torch.cuda.current_stream(self.device).cuda_stream
+  @_counter.setter
+  def _counter(self, c):
+    self._cfg.counter = int(c)
 
   def _settle_reset_hand(self):
     """sim.reset() + _reset_hand: (mocap <- hand_init_pos, ctrl <- [-1, 1], timesteps) from qpos0 until converged (see SETTLE_TIMESTEPS).
@@ -199,18 +201,19 @@ class SawyerDoor:
     return T > 1 and (self.nv >= 15 or self.door_queue)
 
   def _new_out(self, lead, info=None):
-    kw = dict(device=self.device)
-    if not (self.info_mode == 'full' if info is None else info):
-      out = self._new_out(lead, info=True)
-      del out['info']
-      return out
-    return {'obs': torch.empty(*lead, self.num_envs, self.OBS_DIM, dtype=torch.float64, **kw),
-            'reward': torch.empty(*lead, self.num_envs, dtype=torch.float32, **kw),
-            'done': torch.empty(*lead, self.num_envs, dtype=torch.bool, **kw),
-            'success': torch.empty(*lead, self.num_envs, dtype=torch.bool, **kw),
-            'status': torch.empty(*lead, self.num_envs, dtype=torch.uint8, **kw),
-            # the reference's per-step info dict (evaluate_state: sawyer_door.py:127-139 / sawyer_peg.py:165-184), slots _abi.SAWYER_INFO_KEYS
-            'info': torch.empty(*lead, self.num_envs, _abi.SAWYER_INFO, dtype=torch.float64, **kw)}
+    """the base's dict and, with info='full' (or info=True), 'info': the reference's per-step info dict (evaluate_state: sawyer_door.py:127-139 / sawyer_peg.py:165-184),
+    slots _abi.SAWYER_INFO_KEYS"""
+    out = super()._new_out(lead)
+    if self.info_mode == 'full' if info is None else info:
+      out['info'] = torch.empty(*lead, self.num_envs, _abi.SAWYER_INFO, dtype=torch.float64, device=self.device)
+    return out
+
+  def _out_struct(self, out, info=True):
+    """the base's struct and out['info'] (info=False: NULL, the rows are not the kernel's to write)"""
+    o = super()._out_struct(out)
+    if info and out.get('info') is not None:
+      o.info = out['info'].data_ptr()
+    return o
 
   def _launch_rollout(self, actions, T, out):
     """T env steps of given actions and their bookkeeping"""
@@ -228,8 +231,7 @@ class SawyerDoor:
     in_kernel = info is not None and self.nv >= 15        # the peg's dict needs simulator state: the rollout kernel's epilogue writes it
     # door, lifelong goal switching: the kernel leaves the PRE-switch target on goal-switch rows (slots 0-2, marker in slot 7) for earl_sawyer_door_info
     stash = info is not None and self.nv < 15 and bool(self._cfg.goal_change_frequency)
-    o = _abi.SawyerOut(obs=_ptr(out.get('obs')), reward=_ptr(out.get('reward')), done=_ptr(out.get('done')),
-                       success=_ptr(out.get('success')), status=_ptr(out.get('status')), info=_ptr(info) if (in_kernel or stash) else None)
+    o = self._out_struct(out, info=in_kernel or stash)
     with torch.cuda.device(self.device):
       if self.sched is not None and T > 1 and self._uses_queue(T):
         self.sched.zero_()                                 # (the queue of the time-sliced schedule: zero on entry)
@@ -288,40 +290,12 @@ class SawyerDoor:
     return (out['obs'][0].cpu().numpy(), float(out['reward'][0]), bool(out['done'][0]), self._info_dict(out)) if self.scalar_api else \
         (out['obs'], out['reward'], out['done'], self._info_dict(out))
 
-  def make_step_graph(self, T, policy=None):
-    """Closed-loop stepping without the per-call host cost: T step() launches captured into a HIP graph, replayed with one host call (see `PhysicsStepGraph`)."""
-    return PhysicsStepGraph(self, T, policy)
-
   # hooks of PhysicsStepGraph: one captured step = the clocked T = 1 launch (+ the door's info launch) into the graph's output rows
-  _graph_bounds = None
-
-  def _graph_check(self):
-    pass
-
-  def _new_graph_out(self, T):
-    return self._new_out((T,))
-
-  @contextlib.contextmanager
-  def _graph_capture(self):
-    sc = self._cfg.step_counter
-    try:
-      yield
-    finally:
-      self._cfg.step_counter = sc
-
   def _graph_step(self, t, action, out, clock):
     self._cfg.step_counter = t                             # the goal-switch draws of the captured step t: clock[1] + t
     self._issue_rollout(action, 1, out, clock)
     if self._cfg.goal_change_frequency:
       self.lifelong_return_t += out['reward'].reshape(1, -1).sum(0, dtype=torch.float64)
-
-  def _graph_clock(self):
-    return self._cfg.counter, self.total_step_count
-
-  def _graph_advance(self, T, out):
-    self.total_step_count += T
-    self._last_obs_stale = False
-    self._last_success = out['success'][-1]
 
   def _graph_info(self, out):
     return self._info_dict(out)
@@ -360,12 +334,6 @@ class SawyerDoor:
     self._launch_rollout(self._actions(a, (T,)), T, out)
     return out
 
-  def _check_policy(self, policy, who, population=True):
-    """-> is it Gaussian; `policy`: an MLPPolicy / GaussianMLPPolicy / PolicyPopulation of this env's widths on this env's device (a population is taken everywhere)"""
-    del population
-    from ..policy import require_widths
-    return require_widths(policy, who, self.OBS_DIM, 4, env=self)
-
   def _launch_policy(self, policy, head, obs0, T, out, summary=None, pair=None):
     """hook of physics_policy_rollout: earl_sawyer_population_rollout, or -- pair: what physics_policy_rollout.pair_structs returns -- earl_sawyer_agents_rollout"""
     self._cfg.step_counter = self.total_step_count
@@ -376,21 +344,6 @@ class SawyerDoor:
   def _new_pair_out(self, lead):
     """hook of physics_policy_rollout: the dict of a pair launch -- the door's has no 'info' (the peg's is written in the kernel and stays)"""
     return self._new_out(lead, info=self.nv >= 15 and self.info_mode == 'full')
-
-  def rollout_policy(self, policy, T, reset_first=False, sample=True, return_noise=False, out=None):
-    """physics_policy_rollout's closed loop (its docstring is the contract) on earl_sawyer_population_rollout: `policy` -- an `MLPPolicy` or a `GaussianMLPPolicy` built
-    with obs_dim=14, act_dim=4, or a `PolicyPopulation` of them (the env with global id g runs member g // envs_per_policy; same returns).
-    -> rollout()'s dict plus 'actions' [T, N, 4] and, with return_noise=True, 'eps' [T, N, 4]"""
-    return closed_loop.rollout_policy(self, policy, T, reset_first, sample, return_noise, out)
-
-  def _check_pair(self, pair, who):
-    """-> is it Gaussian; `pair`: an AgentPair or a PairPopulation of this env's widths on this env's device, and no LifelongWrapper"""
-    from ..policy import require_widths
-    gaussian = require_widths(pair, who, self.OBS_DIM, 4, env=self, pair=True, pairs=True)
-    if self._cfg.goal_change_frequency > 0:
-      raise ValueError(f'{who}: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
-                       'not under a LifelongWrapper, whose clock would fight the pair\'s over the same draw')
-    return gaussian
 
   def rollout_agents(self, pair, T, reset_first=False, sample=True, return_noise=False, out=None):
     """The forward / reset agent pair of autonomous RL alternating inside ONE launch of the rollout kernel (include/earl_physics.h: earl_sawyer_agents_rollout): `pair` -- an
@@ -415,11 +368,6 @@ class SawyerDoor:
         'backward_success': [N] int32 phases that ended by success (`env.pair_counts`)}: each equals its definition applied to what rollout_agents would have returned.
     State and bookkeeping end as after rollout_agents.  sample=False: Gaussian agents at their mean."""
     return closed_loop.evaluate_pair(self, pair, T, sample, who='evaluate_agents')
-
-  @property
-  def pair_counts(self):
-    """(forward_success, backward_success) [N] int32 of the last rollout_agents launch: the phases that ended by success; None before the first"""
-    return self._pair_counts
 
   def evaluate_policy(self, policy, T, episodes=1, sample=False, reset_first=True):
     """`episodes` evaluation episodes of `policy` -- an MLPPolicy, a GaussianMLPPolicy (sample=False: at its mean) or a `PolicyPopulation` -- each a reset() launch plus ONE
@@ -466,39 +414,3 @@ class SawyerDoor:
   # ------------------------------------------------------------------ goals (sawyer_door.py:96-109)
   def get_next_goal(self):
     return self.goal_states[0]
-
-  def reset_goal(self, goal=None, mask=None):
-    g = torch.as_tensor(self.get_next_goal() if goal is None else goal, dtype=torch.float64, device=self.device)
-    g = g.expand(self.num_envs, 7)
-    if mask is None:
-      self.goal_t.copy_(g)
-    else:
-      m = torch.as_tensor(mask, device=self.device).bool()
-      self.goal_t[m] = g[m]
-    self._last_obs_stale = True                            # (last_obs carries the old goal block: rollout_policy recomputes its first observation)
-
-  @property
-  def goal(self):
-    return self.goal_t[0].cpu().numpy() if self.scalar_api else self.goal_t
-
-  # ------------------------------------------------------------------ state access
-  def set_state(self, qpos, qvel):
-    self._last_obs_stale = True                            # (last_obs no longer belongs to the state: rollout_policy recomputes its first observation)
-    self.qpos.copy_(torch.as_tensor(qpos, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.nq))
-    self.qvel.copy_(torch.as_tensor(qvel, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.nv))
-
-  def state_dict(self):
-    return {k: getattr(self, k).clone() for k in ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'steps_since_reset', 'interventions',
-                                                  'steps_since_goal_change', 'lifelong_return_t', 'obj_init', 'last_obs', 'fail_count')} | {
-                                                      'counter': int(self._cfg.counter), 'total_step_count': self.total_step_count,
-                                                      'last_obs_stale': bool(self._last_obs_stale)} | closed_loop.pair_state_dict(self)
-
-  def load_state_dict(self, sd):
-    for k in ('qpos', 'qvel', 'mocap_pos', 'goal_t', 'steps_since_reset', 'interventions', 'steps_since_goal_change',
-              'lifelong_return_t', 'obj_init', 'last_obs', 'fail_count'):
-      if k in sd:
-        getattr(self, k).copy_(sd[k])
-    closed_loop.load_pair_state(self, sd)                  # (the agent pair's state: in the dict once a pair launch has allocated it, and only then)
-    self._cfg.counter = int(sd['counter'])
-    self.total_step_count = int(sd['total_step_count'])
-    self._last_obs_stale = bool(sd.get('last_obs_stale', 'last_obs' not in sd))      # (a dict without the row leaves the env's own, which belongs to another state)

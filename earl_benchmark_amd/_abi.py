@@ -64,6 +64,7 @@ class BackwardGoals(C.Structure):      # struct earl_backward_goals (include/ear
   _fields_ = [('table', C.c_void_p), ('n_rows', C.c_int32), ('pad_', C.c_int32), ('row', C.c_void_p), ('row_out', C.c_void_p)]
 
 
+PRECISION_BF16 = 16                    # EARL_PRECISION_BF16: earl_mlp_policy.precision of parameters stored as bf16 (the stepper envs; 0 = fp32)
 PAIR_MAX_H2 = 128                      # EARL_PAIR_MAX_H2: the widest second hidden layer of an agent pair
 
 

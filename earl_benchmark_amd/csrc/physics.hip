@@ -174,9 +174,9 @@ static int sawyer_closed_loop(const earl_link_model* model, const earl_collision
                               const earl_episode_summary* summary, earl_stream_t stream) {
   if (!model || !cfg || !st || !out || !policy || !obs0 || T < 1 || (nv != 10 && nv != 15) || !sawyer_args_ok(kStep, cfg, st, nv, out)) return EARL_ERR_ARG;      // (T = 0 is an error here)
   if (!out->obs && !st->last_obs) return EARL_ERR_ARG;    // (without out->obs the env's row of last_obs is the one observation row the launch keeps)
-  // the policy's contract (policy_check.h); the weight rows are read in 16-byte pieces, so params is aligned and every stride a multiple of 4 floats
+  // the policy's contract (policy_check.h); the weight rows are read in 16-byte pieces, so params is aligned and every stride a multiple of 4 floats (8 bf16 values)
   if (paired && !pair) return EARL_ERR_ARG;
-  if (earl::contract::check_closed_loop(*policy, 14, 4, earl::contract::kParamsAligned16, head, pop, cfg->env_offset, cfg->n, paired ? pair : nullptr,
+  if (earl::contract::check_closed_loop(*policy, 14, 4, earl::contract::kParamsAligned16 | earl::contract::kBf16Params, head, pop, cfg->env_offset, cfg->n, paired ? pair : nullptr,
                                         cfg->goal_change_frequency, goals, cfg->n_goal_rows, nullptr))
     return EARL_ERR_ARG;
   if (g_lpe == 64) return EARL_ERR_ARG;                   // (the 64-lane measurement builds: no policy form)
@@ -185,7 +185,14 @@ static int sawyer_closed_loop(const earl_link_model* model, const earl_collision
   SawyerPolicyArgs a;
   static_cast<SawyerArgs&>(a) = SawyerArgs{model, col, *cfg, *st, nullptr, T, *out, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
   fill_closed_loop(a, *policy, head, obs0, actions, pop, summary, paired ? pair : nullptr, goals, nullptr, 0);      // (the forward goals are cfg->goal_table's)
-  switch (sawyer_form(nv, cfg->n, T, st, true)) {
+  const SawyerForm form = sawyer_form(nv, cfg->n, T, st, true);
+  if (policy->precision == EARL_PRECISION_BF16) {         // the same forms with the parameters stored as bf16: the kernels of physics_bf16.hip / physics_w8_bf16.hip
+    if (form == SawyerForm::DoorW8) return earl_unit_w8_bf16_sawyer_policy_rollout(&a, stream);
+    if (form != SawyerForm::Door && form != SawyerForm::PegSliced && form != SawyerForm::Peg) return EARL_ERR_ARG;
+    if (form == SawyerForm::PegSliced) a.slice = peg_slice();
+    return earl_unit_bf16_sawyer_policy_rollout(&a, nv, form == SawyerForm::PegSliced ? 1 : 0, stream);
+  }
+  switch (form) {
     case SawyerForm::DoorW8: return earl_unit_w8_sawyer_policy_rollout(&a, stream);
     case SawyerForm::Door: sawyer_policy_rollout_kernel<10, 16><<<grid_for<10, 16>(cfg->n), block_for<10>(), 0, (hipStream_t)stream>>>(a); break;
     case SawyerForm::PegSliced: a.slice = peg_slice(); sawyer_policy_rollout_kernel<15, 16, true><<<cu_count(), block_for<15>(), 0, (hipStream_t)stream>>>(a); break;

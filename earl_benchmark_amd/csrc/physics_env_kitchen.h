@@ -114,7 +114,7 @@ __device__ __noinline__ float kitchen_policy_action(const uint64_t ka_bits, cons
   h[1] = (live && sub + 32 < 46) ? (float)seen[sub + 32] : 0.f;
 #pragma unroll
   for (int i = 2; i < 8; ++i) h[i] = 0.f;
-  const float* w = cl_policy_weights(ka, gid, env, row, sub == 0 && live);      // (the member's rows, the network of the pair's phase)
+  const pol_elem* w = cl_policy_weights(ka, gid, env, row, sub == 0 && live);      // (the member's rows, the network of the pair's phase)
   pol_layer<32, false>(w, w + (size_t)d1 * 46, 46, d1, hidden_act, sub, h);
   w += (size_t)d1 * (46 + 1);
   if (n_layers == 3) {

@@ -62,7 +62,7 @@ __device__ __noinline__ float minitaur_policy_action(const uint64_t ka_bits, con
   h[0] = live ? (float)seen[sub] : 0.f;
 #pragma unroll
   for (int i = 1; i < 8; ++i) h[i] = 0.f;
-  const float* w = cl_policy_weights(ka, gid, env, row, sub == 0 && live);      // (the member's rows, the network of the pair's phase)
+  const pol_elem* w = cl_policy_weights(ka, gid, env, row, sub == 0 && live);      // (the member's rows, the network of the pair's phase)
   pol_layer<32, true>(w, w + (size_t)d1 * 32, 32, d1, hidden_act, sub, h);
   w += (size_t)d1 * (32 + 1);
   if (n_layers == 3) {
@@ -152,9 +152,11 @@ __global__ __launch_bounds__(64 * mt_wpb<ARROW>(), ARROW ? EARL_MT_BLOCKS : 1) v
 // chip instead of two.  An env's per-step state (motor counters, command, goal, wrapper counters) lives in its LDS block (SharedMTData::ev) between the visits of wave A,
 // which also runs everything around the timesteps (action fetch and leg model, motor model, observation, reward, state rows).  Same expressions as the one-wave kernel.
 constexpr int MT_DUO_PAIRS = 4;
+#ifndef EARL_POLICY_BF16            // (physics_mt_bf16.hip holds the policy kernels only)
 __global__ __launch_bounds__(128 * MT_DUO_PAIRS, 1) void minitaur_duo_kernel(const MinitaurArgs a) {
 #include "physics_env_minitaur_duo.inc"
 }
+#endif
 // The two-wave kernel with the policy inside: wave A computes env step t's action where the plain kernel loads it (k == 0, after finish_step(t - 1)).  `a` must stay the ONLY argument
 __global__ __launch_bounds__(128 * MT_DUO_PAIRS, 1) void minitaur_policy_duo_kernel(const MinitaurPolicyArgs a) {
 #include "physics_env_minitaur_duo.inc"

@@ -246,7 +246,7 @@ __device__ __noinline__ float4 sawyer_policy_action(const uint64_t ka_bits, cons
   h[0] = (sub < 14 && live) ? (float)seen[sub] : 0.f;
 #pragma unroll
   for (int i = 1; i < 16; ++i) h[i] = 0.f;
-  const float* w = cl_policy_weights(ka, gid, env, row, sub == 0 && live);      // (the member's rows, the network of the pair's phase)
+  const pol_elem* w = cl_policy_weights(ka, gid, env, row, sub == 0 && live);      // (the member's rows, the network of the pair's phase)
   pol_layer<16, false>(w, w + (size_t)d1 * d0, d0, d1, hidden_act, sub, h);
   w += (size_t)d1 * (d0 + 1);
   if (n_layers == 3) {

@@ -89,7 +89,7 @@ static int kitchen_closed_loop(const void* model, const earl_collision_model* co
   // (the kitchen has no lifelong switch of its own: goal_change_frequency 0; its forward goals come with the call)
   if (paired && (!pair || n_forward_goals < 0)) return EARL_ERR_ARG;
   const bool forward = paired && forward_goals && n_forward_goals >= 1;
-  if (earl::contract::check_closed_loop(*policy, 46, 9, earl::contract::kParamsAligned16, head, pop, cfg->env_offset, cfg->n, paired ? pair : nullptr, 0, goals,
+  if (earl::contract::check_closed_loop(*policy, 46, 9, earl::contract::kParamsAligned16 | earl::contract::kBf16Params, head, pop, cfg->env_offset, cfg->n, paired ? pair : nullptr, 0, goals,
                                         forward ? n_forward_goals : 0, nullptr))
     return EARL_ERR_ARG;
   if (cfg->n == 0 || T == 0) return EARL_OK;
@@ -97,7 +97,8 @@ static int kitchen_closed_loop(const void* model, const earl_collision_model* co
   KitchenPolicyArgs k;
   static_cast<KitchenRolloutArgs&>(k) = KitchenRolloutArgs{model, col, *params, *cfg, *st, *out, nullptr, T, kitchen_solo(cfg->n), clock};
   fill_closed_loop(k, *policy, head, obs0, actions, pop, summary, paired ? pair : nullptr, goals, forward ? forward_goals : nullptr, forward ? n_forward_goals : 0);
-  earl_unit_kitchen_policy_rollout(&k, stream);      // physics_kitchen_policy.hip holds the kernels
+  if (policy->precision == EARL_PRECISION_BF16) earl_unit_kitchen_bf16_policy_rollout(&k, stream);      // physics_kitchen_policy_bf16.hip: parameters stored as bf16
+  else earl_unit_kitchen_policy_rollout(&k, stream);      // physics_kitchen_policy.hip holds the kernels
   return launched("kitchen_policy_rollout");
 }
 int earl_kitchen_population_rollout(const void* model, const earl_collision_model* col, const earl_kitchen_params* params, const earl_kitchen_cfg* cfg,

@@ -1,4 +1,4 @@
-// physics_launch.h -- host helpers of the six stepper units (physics.hip, physics_w8.hip, physics_l64.hip, physics_kitchen.hip, physics_kitchen_policy.hip, physics_mt.hip):
+// physics_launch.h -- host helpers of the stepper units (physics.hip, physics_w8.hip, physics_l64.hip, physics_kitchen.hip, physics_kitchen_policy.hip, physics_mt.hip and the four *_bf16.hip):
 // launch checks, the calls from one unit into another, launch geometry and the profiling build's hooks.  Included after physics_stepper.h and the
 // unit's env kernels; what sits in the anonymous namespace here is the including unit's own copy.
 #pragma once
@@ -16,6 +16,12 @@ extern "C" __attribute__((visibility("hidden"))) void earl_unit_kitchen_policy_r
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_w8_sawyer_rollout(const void* sawyer_args, void* stream);
 // the same hand-over for the rollout with the policy inside (earl_sawyer_policy_rollout; the argument is a SawyerPolicyArgs)
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_w8_sawyer_policy_rollout(const void* sawyer_policy_args, void* stream);
+// the units compiled with EARL_POLICY_BF16 (policy parameters stored as bf16: physics_bf16.hip, physics_w8_bf16.hip, physics_mt_bf16.hip,
+// physics_kitchen_policy_bf16.hip): the closed-loop entry points hand them the argument struct they filled, launch form chosen, when policy->precision says so
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_bf16_sawyer_policy_rollout(const void* sawyer_policy_args, int nv, int sliced, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_w8_bf16_sawyer_policy_rollout(const void* sawyer_policy_args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_mt_bf16_policy_rollout(const void* minitaur_policy_args, int duo, void* stream);
+extern "C" __attribute__((visibility("hidden"))) void earl_unit_kitchen_bf16_policy_rollout(const void* kitchen_policy_args, void* stream);
 extern "C" int earl_sawyer_rollout_door_w8(const earl_link_model* model, const earl_collision_model* col, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                            const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream);
 

@@ -75,7 +75,7 @@ static int minitaur_closed_loop(const void* model24, const earl_collision_model*
   // actions must not either: bounded policies only.  A population: groups of 16 envs, every member's rows read in 16-byte pieces
   // (the pair's handover IS the goal switch of autonomous RL: goal_change_frequency > 0 is refused with a pair -- both would draw with index 0xFFFE at the same step)
   if (paired && !pair) return EARL_ERR_ARG;
-  if (earl::contract::check_closed_loop(*policy, 32, 8, earl::contract::kParamsAligned16 | earl::contract::kBoundedOutput, head, pop, cfg->env_offset, cfg->n,
+  if (earl::contract::check_closed_loop(*policy, 32, 8, earl::contract::kParamsAligned16 | earl::contract::kBoundedOutput | earl::contract::kBf16Params, head, pop, cfg->env_offset, cfg->n,
                                         paired ? pair : nullptr, cfg->goal_change_frequency, goals, cfg->n_goals, nullptr))
     return EARL_ERR_ARG;
   if (!g_mt_stepper) return EARL_ERR_ARG;                 // (earl_debug_set_minitaur_stepper(0): no policy form)
@@ -84,7 +84,9 @@ static int minitaur_closed_loop(const void* model24, const earl_collision_model*
   MinitaurPolicyArgs a;
   static_cast<MinitaurArgs&>(a) = MinitaurArgs{model24, col, *cfg, *st, *out, nullptr, T, nullptr, nullptr, solo_mode(cfg->n), clock};
   fill_closed_loop(a, *policy, head, obs0, actions, pop, summary, paired ? pair : nullptr, goals, nullptr, 0);      // (the forward goals are cfg->goal_table's)
-  if (minitaur_form(cfg->n, a.solo, cfg->num_substeps) == MtForm::Duo) {
+  const bool duo = minitaur_form(cfg->n, a.solo, cfg->num_substeps) == MtForm::Duo;
+  if (policy->precision == EARL_PRECISION_BF16) return earl_unit_mt_bf16_policy_rollout(&a, duo ? 1 : 0, stream);      // physics_mt_bf16.hip: the same two kernels, parameters stored as bf16
+  if (duo) {
     minitaur_policy_duo_kernel<<<(unsigned)((cfg->n + 16 * MT_DUO_PAIRS / 4 - 1) / (4 * MT_DUO_PAIRS)), 128 * MT_DUO_PAIRS, 0, (hipStream_t)stream>>>(a);
     return launched("minitaur_policy_rollout (two waves per SIMD)");
   }

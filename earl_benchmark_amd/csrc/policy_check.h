@@ -26,13 +26,19 @@ inline int refuse(char* err, const char* fmt, ...) {
 }
 
 // what an entry point asks of a policy beyond the common rules: params 16-byte aligned (the stepper units read the weight rows in 16-byte pieces); out_act tanh
-// (the minitaur: the reference env raises on an action outside +-(1 + 0.01) and a kernel cannot)
-enum : unsigned { kParamsAligned16 = 1u, kBoundedOutput = 2u };
+// (the minitaur: the reference env raises on an action outside +-(1 + 0.01) and a kernel cannot); precision may be EARL_PRECISION_BF16 (the stepper entry points, whose
+// weights are read from memory at every step, and earl_mlp_policy_forward_cpu: params then holds uint16_t bf16 values, 16-byte aligned whatever the other rules say, and
+// every stride counts those elements and is a multiple of 8 of them.  Not the tabletop's: its weights sit in registers for the whole launch, so a narrower stored
+// format buys nothing there)
+enum : unsigned { kParamsAligned16 = 1u, kBoundedOutput = 2u, kBf16Params = 4u };
+
+// elements of the stored type in a 16-byte piece: what every stride of a launch whose rows are read in such pieces is a multiple of
+inline int stride_multiple(const earl_mlp_policy& p) { return p.precision == EARL_PRECISION_BF16 ? 8 : 4; }
 
 // the head of a launch without one (the kernels' argument structs always carry a head)
 inline earl_gaussian_head default_head() { return earl_gaussian_head{EARL_HEAD_MEAN, EARL_LOGSTD_CLAMP, 0.0f, 0.0f, nullptr}; }
 
-// floats of one policy in the packing order W_0, b_0, W_1, b_1, ...  (after check_form: n_layers is 2 or 3)
+// parameters (elements of the stored type) of one policy in the packing order W_0, b_0, W_1, b_1, ...  (after check_form: n_layers is 2 or 3)
 inline int64_t mlp_param_count(const earl_mlp_policy& p) {
   int64_t count = 0;
   for (int l = 0; l < p.n_layers; ++l) count += (int64_t)p.dims[l + 1] * (p.dims[l] + 1);
@@ -40,8 +46,11 @@ inline int64_t mlp_param_count(const earl_mlp_policy& p) {
 }
 
 // precision, layer count and activations: what holds whatever the widths are
-inline int check_form(const earl_mlp_policy& p, char* err) {
-  if (p.precision != 0) return refuse(err, "policy precision = %d: only 0 (fp32) exists", p.precision);
+inline int check_form(const earl_mlp_policy& p, char* err, unsigned rules = 0) {
+  if (p.precision == EARL_PRECISION_BF16 && !(rules & kBf16Params))
+    return refuse(err, "policy precision = %d (bf16): the stepper envs and earl_mlp_policy_forward_cpu take it; this entry point takes 0 (fp32) only", p.precision);
+  if (p.precision != 0 && p.precision != EARL_PRECISION_BF16) return refuse(err, "policy precision = %d: 0 (fp32) or %d (bf16)", p.precision, EARL_PRECISION_BF16);
+  if (p.precision == EARL_PRECISION_BF16 && ((uintptr_t)p.params & 15)) return refuse(err, "policy params (bf16) is not 16-byte aligned");
   if (p.n_layers != 2 && p.n_layers != 3) return refuse(err, "policy n_layers = %d: 2 (one hidden layer) or 3 (two)", p.n_layers);
   if (p.hidden_act != EARL_ACT_RELU && p.hidden_act != EARL_ACT_TANH) return refuse(err, "policy hidden_act = %d", p.hidden_act);
   if (p.out_act != EARL_ACT_NONE && p.out_act != EARL_ACT_TANH) return refuse(err, "policy out_act = %d", p.out_act);
@@ -60,7 +69,7 @@ inline int check_head(const earl_gaussian_head& h, char* err) {
 inline int check_policy(const earl_mlp_policy& p, int obs_dim, int act_dim, const earl_gaussian_head* head, unsigned rules, char* err) {
   if (!p.params) return refuse(err, "policy params is NULL");
   if ((rules & kParamsAligned16) && ((uintptr_t)p.params & 15)) return refuse(err, "policy params is not 16-byte aligned");
-  if (int rc = check_form(p, err)) return rc;
+  if (int rc = check_form(p, err, rules)) return rc;
   const int out_dim = head ? 2 * act_dim : act_dim;
   if (p.dims[0] != obs_dim || p.dims[p.n_layers] != out_dim)
     return refuse(err, "policy dims: input %d, output %d (want %d and %d)", p.dims[0], p.dims[p.n_layers], obs_dim, out_dim);
@@ -72,7 +81,7 @@ inline int check_policy(const earl_mlp_policy& p, int obs_dim, int act_dim, cons
 }
 
 // a population of checked policies over the envs with global ids env_offset .. env_offset + n - 1: `group` envs share their weights' loads (16 everywhere today), and
-// the rows of params are `stride_multiple` floats apart at least (4 where a member's rows are read in 16-byte pieces)
+// the rows of params are a multiple of `stride_multiple` elements apart (4 floats / 8 bf16 values where a member's rows are read in 16-byte pieces)
 inline int check_population(const earl_mlp_policy& p, const earl_policy_population& pop, int32_t env_offset, int32_t n, int group, int stride_multiple, char* err) {
   if (pop.n_policies < 1) return refuse(err, "population n_policies = %d < 1", pop.n_policies);
   if (pop.envs_per_policy < group || pop.envs_per_policy % group)
@@ -125,16 +134,16 @@ inline int check_backward_goals(const Goals& goals, const earl_agent_pair& pair,
 // act_dim under `rules` with its head; the population (NULL: one policy) over the global ids env_offset .. env_offset + n - 1; the pair (NULL: none) with the env's
 // goal_change_frequency, its population and its table of backward goals (NULL: none).  n_forward_rows: the rows of the forward goal table the launch can draw from; a
 // pair with a backward goal -- one row or a table -- needs one at least (the forward goal could not be restored).  Everywhere: groups of 16 envs share their weights'
-// loads, and every stride is a multiple of 4 floats (the rows are read in 16-byte pieces)
+// loads, and every stride is a multiple of 4 floats -- of 8 bf16 values -- (the rows are read in 16-byte pieces)
 template <class Goals>
 inline int check_closed_loop(const earl_mlp_policy& p, int obs_dim, int act_dim, unsigned rules, const earl_gaussian_head* head, const earl_policy_population* pop,
                              int32_t env_offset, int32_t n, const earl_agent_pair* pair, int32_t goal_change_frequency, const Goals* goals, int32_t n_forward_rows,
                              char* err) {
   if (int rc = check_policy(p, obs_dim, act_dim, head, rules, err)) return rc;
   if (pop)
-    if (int rc = check_population(p, *pop, env_offset, n, 16, 4, err)) return rc;
+    if (int rc = check_population(p, *pop, env_offset, n, 16, stride_multiple(p), err)) return rc;
   if (!pair) return EARL_OK;
-  if (int rc = check_pair(p, pair, goal_change_frequency, 4, err)) return rc;
+  if (int rc = check_pair(p, pair, goal_change_frequency, stride_multiple(p), err)) return rc;
   if (pair->backward_goal && n_forward_rows < 1) return refuse(err, "pair backward_goal: the env has no forward goal table (the forward goal could not be restored)");
   if (pop)
     if (int rc = check_pair_population(*pop, *pair, err)) return rc;

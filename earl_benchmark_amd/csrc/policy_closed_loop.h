@@ -16,7 +16,7 @@ struct ClosedLoopArgs : Plain {
   float* act_out;                // NULL or [T, n, A]: the actions as the policy produced them (the open-loop entry points fed with it walk through the same bits)
   // a population (earl_policy_population)
   int pop_G;                     // envs per member (0: one policy); the env with global id g reads its parameters at pol.params + (g / pop_G) pop_stride
-  int64_t pop_stride;            // floats between consecutive members (a multiple of 4: every member's rows are read in 16-byte pieces)
+  int64_t pop_stride;            // elements of the stored type between consecutive members (whole 16-byte pieces: a multiple of 4 floats, of 8 bf16 values)
   // earl_episode_summary of the launch, each NULL or [n]: lane 0 of the env keeps its three words up to date in HBM after every env step (step 0 initialises them), so
   // a time slice handed to another wave finds them where it finds qpos
   double* sum_ret;
@@ -26,7 +26,7 @@ struct ClosedLoopArgs : Plain {
   // stores it after the handover decision, an agent-scope fence follows, and all lanes of the env read it back where the next action is computed
   int8_t* pair_phase;            // [n] 0 forward, anything else reset; the network of the phase starts at pol.params (+ the member's offset) + phase * pair_stride
   int32_t* pair_sip;             // [n] steps the env has spent in its phase
-  int64_t pair_stride;           // floats between the two agents' rows (a multiple of 4)
+  int64_t pair_stride;           // elements between the two agents' rows (a multiple of 4 floats, of 8 bf16 values)
   const double* pair_goal;       // NULL or the table [pair_goal_rows, G] of backward goals: entering the reset phase, a drawn row of it becomes the env's st.goal row
   const double* pair_fwd;        // NULL or the table [pair_fwd_rows, G] of forward goals: entering the forward phase, likewise (the kitchen; the Sawyer and the minitaur
                                  // draw from their cfg's goal table and leave this NULL / 0)
@@ -95,10 +95,14 @@ __device__ __forceinline__ const EARL_KARG KA* cl_kernarg(const uint64_t bits) {
 
 // the weight rows of env `env` (global id `gid`): a population's member from the GLOBAL id alone (a wave whose envs belong to two members walks two sets of rows:
 // correct, only slower); an agent pair's network of the env's phase, the word lane 0 stored after the last handover decision (a group that is not live reads the word of
-// the env it shadows).  `lane0`: lane 0 of a live env, which leaves the phase in pair_agent[row]
+// the env it shadows).  `lane0`: lane 0 of a live env, which leaves the phase in pair_agent[row].  Both strides count elements of the stored type (pol_elem)
 template <class KA>
-__device__ __forceinline__ const float* cl_policy_weights(const EARL_KARG KA* ka, const uint32_t gid, const int env, const size_t row, const bool lane0) {
+__device__ __forceinline__ const pol_elem* cl_policy_weights(const EARL_KARG KA* ka, const uint32_t gid, const int env, const size_t row, const bool lane0) {
+#ifdef EARL_POLICY_BF16
+  const pol_elem* w = reinterpret_cast<const pol_elem*>(ka->pol.params);      // (precision == EARL_PRECISION_BF16: the field keeps its type, the elements are 2 bytes)
+#else
   const float* w = ka->pol.params;
+#endif
   const int pop_G = ka->pop_G;
   if (pop_G > 0) w += (size_t)(gid / (uint32_t)pop_G) * (size_t)ka->pop_stride;
   const int8_t* pair_phase = ka->pair_phase;

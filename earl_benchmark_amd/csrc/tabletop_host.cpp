@@ -220,7 +220,7 @@ int earl_tabletop3_reward_cpu(int32_t n, const float* obs, int32_t reward_type, 
 // include/earl_physics.h: the policy contract as plain loops, any input / action width (the oracle of the Sawyer rollout's in-kernel policy)
 int32_t earl_mlp_policy_forward_cpu(const earl_mlp_policy* p, const earl_gaussian_head* h, int32_t n, const float* obs, const float* eps, float* actions) {
   if (!p || !p->params || !obs || !actions || n < 0) return fail(EARL_ERR_ARG, "policy/params/obs/actions is NULL or n < 0");
-  if (int rc = contract::check_form(*p, g_err)) return rc;
+  if (int rc = contract::check_form(*p, g_err, contract::kBf16Params)) return rc;
   for (int l = 0; l < p->n_layers; ++l)                    // (its own width rule: any width 1..256 at every position, the input included)
     if (p->dims[l] < 1 || p->dims[l] > kPolicyMaxWidth) return fail(EARL_ERR_ARG, "policy dims[%d] = %d: 1..256", l, p->dims[l]);
   const int NL = p->dims[p->n_layers];
@@ -232,14 +232,21 @@ int32_t earl_mlp_policy_forward_cpu(const earl_mlp_policy* p, const earl_gaussia
   for_each_env(n, [&](int i) {
     float buf[2][kPolicyMaxWidth];
     const float* in = obs + (size_t)i * p->dims[0];
-    const float* w = p->params;
+    // parameter e of the packing order: the float32 itself, or (EARL_PRECISION_BF16) the stored uint16_t widened exactly, u << 16
+    const uint16_t* const stored = reinterpret_cast<const uint16_t*>(p->params);
+    const bool bf16 = p->precision == EARL_PRECISION_BF16;
+    auto param = [&](size_t e) {
+      if (!bf16) return p->params[e];
+      return __builtin_bit_cast(float, (uint32_t)stored[e] << 16);
+    };
+    size_t w = 0;
     for (int l = 0; l < p->n_layers; ++l) {
       const int K = p->dims[l], N = p->dims[l + 1];
-      const float* b = w + (size_t)N * K;
+      const size_t b = w + (size_t)N * K;
       float* dst = buf[l & 1];
       for (int j = 0; j < N; ++j) {
-        float acc = b[j];
-        for (int k = 0; k < K; ++k) acc = fmaf(in[k], w[(size_t)j * K + k], acc);
+        float acc = param(b + j);
+        for (int k = 0; k < K; ++k) acc = fmaf(in[k], param(w + (size_t)j * K + k), acc);
         dst[j] = l + 1 < p->n_layers ? policy_act(acc, p->hidden_act) : acc;
       }
       in = dst;

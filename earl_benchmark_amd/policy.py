@@ -23,6 +23,13 @@ The kitchen takes them with obs_dim=46, act_dim=9, bounded or not -- the env cli
   pi = MLPPolicy(layers, 'relu', 'tanh', device='cuda', obs_dim=46, act_dim=9)                  # or GaussianMLPPolicy(..., obs_dim=46, act_dim=9)
   out = kitchen.rollout_policy(pi, T=400)                                                       # rollout()'s dict plus 'actions' [T, N, 9], ONE launch
 
+On those four envs (door, peg, minitaur, kitchen) the parameters may be STORED as bf16 (include/earl_tabletop.h: EARL_PRECISION_BF16), which halves what the kernel loads per
+env step -- worth it for wide networks (256 x 256), not for narrow ones.  The arithmetic stays float32 on the exactly widened values:
+
+  pi = MLPPolicy(layers, 'relu', 'tanh', device='cuda', obs_dim=14, act_dim=4, param_dtype=torch.bfloat16)      # each parameter rounded once; pi.params is the bf16 tensor the kernel reads
+  out = door.rollout_policy(pi, T=300)                                                          # bit-identical to door.rollout_policy(pi.widened(), T=300)
+  pi32 = pi.widened()                                                                           # the float32 policy of exactly those values (what the tabletop takes)
+
 `GaussianMLPPolicy` is the SAC-style actor with a tanh-Gaussian head, 12 -> hidden (-> hidden) -> 6 (rows 0..2 mean, rows 3..5 raw log_std), for
 earl_tabletop_policy_rollout_gaussian: the actions are SAMPLED inside the kernel from the env's counter-based RNG.
 
@@ -66,6 +73,36 @@ from . import _abi
 
 OBS_DIM, ACT_DIM = 12, 3
 MIN_WIDTH, MAX_WIDTH = 16, 256
+PARAM_DTYPES = {torch.float32: 0, torch.bfloat16: _abi.PRECISION_BF16}      # param_dtype -> earl_mlp_policy.precision
+
+
+def _param_dtype(who, dtype):
+  if dtype not in PARAM_DTYPES:
+    raise ValueError(f'{who}: param_dtype must be torch.float32 or torch.bfloat16, got {dtype!r}')
+  return dtype
+
+
+def _piece(dtype, tabletop=False):
+  """elements of `dtype` in a 16-byte piece: what the stepper kernels read the rows of a container in, so what its stride is padded to (the tabletop's float32
+  rows are taken as they are)"""
+  return 8 if dtype == torch.bfloat16 else (1 if tabletop else 4)
+
+
+def _unpack(row, dims):
+  """one packed row (W0, b0, W1, b1, ...) -> [(W [n, k], b [n])] as views of it"""
+  layers, at = [], 0
+  for k, n in zip(dims[:-1], dims[1:]):
+    layers.append((row[at:at + n * k].reshape(n, k), row[at + n * k:at + n * k + n]))
+    at += n * k + n
+  return layers
+
+
+def _like(t, layers, device, param_dtype, obs_dim, act_dim):
+  """a policy of `t`'s class, activations and head over `layers`"""
+  if isinstance(t, GaussianMLPPolicy):
+    return GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, device=device, obs_dim=obs_dim,
+                             act_dim=act_dim, param_dtype=param_dtype)
+  return MLPPolicy(layers, t.hidden_act, t.out_act, device=device, obs_dim=obs_dim, act_dim=act_dim, param_dtype=param_dtype)
 
 
 def _layers_of_sequential(seq):
@@ -93,9 +130,14 @@ def _layers_of_sequential(seq):
 class MLPPolicy:
   OUT_DIM, OUT_WHAT = ACT_DIM, 'action'
 
-  def __init__(self, layers, hidden_act='relu', out_act='tanh', device='cpu', obs_dim=OBS_DIM, act_dim=ACT_DIM):
-    """obs_dim / act_dim: the env's observation and action widths -- the tabletop's 12 / 3 by default, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur, 46 / 9 for the kitchen (`env.rollout_policy`)"""
+  def __init__(self, layers, hidden_act='relu', out_act='tanh', device='cpu', obs_dim=OBS_DIM, act_dim=ACT_DIM, param_dtype=torch.float32):
+    """obs_dim / act_dim: the env's observation and action widths -- the tabletop's 12 / 3 by default, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur, 46 / 9 for the kitchen (`env.rollout_policy`).
+    param_dtype: the format the parameters are STORED in.  torch.bfloat16 (the door, the peg, the minitaur and the kitchen; earl_mlp_policy.precision =
+    EARL_PRECISION_BF16) rounds every parameter ONCE, with torch's round-to-nearest-even; `.params` is then the bf16 tensor the kernel reads (writable in place), and
+    `.layers` hold the widened float32 values, so pi(obs), pi.sample and make_step_graph(T, policy=pi) evaluate the network the kernel evaluates: bf16 is a storage
+    format, the arithmetic is float32 on the widened values, and a launch returns the bits of the float32 launch of pi.widened()."""
     name = type(self).__name__                                        # (MLPPolicy's own messages read as they always did)
+    self.param_dtype = _param_dtype(name, param_dtype)
     self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
     if self.obs_dim < 1 or self.act_dim < 1:
       raise ValueError(f'{name}: obs_dim = {obs_dim}, act_dim = {act_dim}: both >= 1')
@@ -124,6 +166,8 @@ class MLPPolicy:
       if h < MIN_WIDTH or h > MAX_WIDTH or h % 16:
         raise ValueError(f'{name}: hidden width {h}: a multiple of 16 in {MIN_WIDTH}..{MAX_WIDTH}')
     self.dims, self.hidden_act, self.out_act = dims, hidden_act, out_act or 'none'
+    if self.param_dtype != torch.float32:                             # rounded once; from here on the float32 values ARE the stored ones, widened
+      layers = [(w.to(self.param_dtype).to(torch.float32), b.to(self.param_dtype).to(torch.float32)) for w, b in layers]
     self._host_layers = layers
     self.macs = sum(a * b for a, b in zip(dims[:-1], dims[1:]))       # multiply-adds per env step
     self.to(device)
@@ -134,11 +178,20 @@ class MLPPolicy:
       dev = torch.device('cuda', torch.cuda.current_device())
     self.device = dev
     self.layers = [(w.to(dev).contiguous(), b.to(dev).contiguous()) for w, b in self._host_layers]
-    self.params = torch.cat([t.reshape(-1) for wb in self.layers for t in wb]).contiguous()      # W0, b0, W1, b1, ...
+    self.params = torch.cat([t.reshape(-1) for wb in self.layers for t in wb]).to(self.param_dtype).contiguous()      # W0, b0, W1, b1, ...  (bf16: exact, the values are widened bf16)
     dims = self.dims + [0] * (4 - len(self.dims))
     self.struct = _abi.MlpPolicy(n_layers=len(self.layers), dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
-                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=0, params=self.params.data_ptr())
+                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=PARAM_DTYPES[self.param_dtype], params=self.params.data_ptr())
     return self
+
+  def with_param_dtype(self, dtype):
+    """the policy of the values that stand in `.params` now, stored as `dtype` (torch.float32 | torch.bfloat16: rounded once), on the same device"""
+    layers = [(w.clone(), b.clone()) for w, b in _unpack(self.params.detach().to('cpu', torch.float32), self.dims)]
+    return _like(self, layers, self.device, _param_dtype(type(self).__name__, dtype), self.obs_dim, self.act_dim)
+
+  def widened(self):
+    """the float32 policy with exactly the stored values: the network a launch with this policy evaluates, bit for bit (and what the tabletop takes)"""
+    return self.with_param_dtype(torch.float32)
 
   def __call__(self, obs):
     x = obs.to(torch.float32)
@@ -157,7 +210,8 @@ class GaussianMLPPolicy(MLPPolicy):
   standard-normal eps -- torch's statement of csrc/tabletop_policy.h's contract, close to but not bit-identical with the kernel."""
   OUT_DIM, OUT_WHAT = 2 * ACT_DIM, 'mean and raw log_std of the action'
 
-  def __init__(self, layers, hidden_act='relu', squash=True, log_std_bounds=(-5.0, 2.0), log_std_map='tanh', device='cpu', obs_dim=OBS_DIM, act_dim=ACT_DIM):
+  def __init__(self, layers, hidden_act='relu', squash=True, log_std_bounds=(-5.0, 2.0), log_std_map='tanh', device='cpu', obs_dim=OBS_DIM, act_dim=ACT_DIM,
+               param_dtype=torch.float32):
     if isinstance(layers, torch.nn.Sequential):
       layers, hidden_act, last = _layers_of_sequential(layers)
       if last != 'none':
@@ -168,7 +222,7 @@ class GaussianMLPPolicy(MLPPolicy):
     if not (-20.0 <= lo <= hi <= 4.0):                       # (NaN fails the chain)
       raise ValueError(f'GaussianMLPPolicy: log_std_bounds {tuple(log_std_bounds)}: finite, min <= max, inside [-20, 4]')
     self.squash, self.log_std_bounds, self.log_std_map = bool(squash), (lo, hi), log_std_map
-    super().__init__(layers, hidden_act, 'tanh' if squash else 'none', device, obs_dim=obs_dim, act_dim=act_dim)
+    super().__init__(layers, hidden_act, 'tanh' if squash else 'none', device, obs_dim=obs_dim, act_dim=act_dim, param_dtype=param_dtype)
 
   def head(self, sample=True, eps_out=None):
     """struct earl_gaussian_head for one launch; eps_out: a float32 tensor [E, T, N, act_dim] on the policy's device, or None"""
@@ -220,6 +274,9 @@ def require_widths(policy, who, obs_dim, act_dim, env=None, pair=False, bounded=
   gaussian = policy.gaussian if isinstance(policy, (PolicyPopulation, AgentPair, PairPopulation)) else isinstance(policy, GaussianMLPPolicy)
   if env is None:
     return gaussian
+  if (obs_dim, act_dim) == (OBS_DIM, ACT_DIM) and getattr(policy, 'param_dtype', torch.float32) != torch.float32:
+    raise ValueError(f'{who}: the parameters are stored as {policy.param_dtype}; the tabletop holds its weights in registers for the whole launch and takes float32 '
+                     'only: pass .widened(), the float32 policy of exactly these values')
   if policy.device != env.device:
     noun = 'pair' if pair else 'policy'
     raise ValueError(f'{who}: the {noun} is on {policy.device}, the env on {env.device} ({noun}.to(device))')
@@ -238,9 +295,9 @@ class PolicyPopulation:
   """P members of one architecture behind struct earl_policy_population: `policies` is a list of MLPPolicy or of GaussianMLPPolicy (same dims, activations and,
   for the Gaussian head, squash / bounds / map -- only the parameters differ), or ONE template policy with `params` [P, n_params] (n_params <= the row length:
   a wider row is the stride).  The env with GLOBAL id g runs member g // envs_per_policy (a multiple of 16: a member owns whole 16-env workgroups of the kernel).
-  `.params` [P, stride] float32 holds every member in MLPPolicy's packing order (W0, b0, W1, b1, ...) and is what the kernel reads: write into it in place.
+  `.params` [P, stride] float32 (bf16 if the members store bf16: `param_dtype` is theirs, and a mixed list is refused) holds every member in MLPPolicy's packing order (W0, b0, W1, b1, ...) and is what the kernel reads: write into it in place.
   obs_dim / act_dim: the members' widths -- the tabletop's 12 / 3 by default, as MLPPolicy's; 14 / 4 for the Sawyer door and peg (earl_sawyer_population_rollout,
-  whose rows are then padded to a stride of whole 16-byte pieces)."""
+  whose rows are then padded to a stride of whole 16-byte pieces: 4 float32 or 8 bf16 elements -- the stride counts elements of the stored type)."""
 
   def __init__(self, policies, envs_per_policy=16, device=None, params=None, obs_dim=OBS_DIM, act_dim=ACT_DIM):
     self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
@@ -262,23 +319,28 @@ class PolicyPopulation:
       for m in members:
         require_widths(m, 'PolicyPopulation', self.obs_dim, self.act_dim)
       for p, m in enumerate(members):
-        for what in ('__class__', 'dims', 'hidden_act', 'out_act') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
+        for what in ('__class__', 'dims', 'hidden_act', 'out_act', 'param_dtype') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
           if getattr(m, what) != getattr(template, what):
             raise ValueError(f'PolicyPopulation: member {p} has {what.strip("_")} = {getattr(m, what)!r}, member 0 has {getattr(template, what)!r} '
                              '(the members of a population share one architecture)')
-    self.template, self.envs_per_policy = template, G
+    self.template, self.envs_per_policy, self.param_dtype = template, G, template.param_dtype
     self.gaussian = isinstance(template, GaussianMLPPolicy)
     self.dims, self.hidden_act, self.out_act, self.macs = list(template.dims), template.hidden_act, template.out_act, template.macs
     self.n_params = sum(n * (k + 1) for k, n in zip(self.dims[:-1], self.dims[1:]))
     if members is not None:
-      host = torch.stack([m.params.detach().to('cpu', torch.float32) for m in members])
+      host = torch.stack([m.params.detach().to('cpu', self.param_dtype) for m in members])
     else:
-      host = torch.as_tensor(params).detach().to('cpu', torch.float32)
+      given = params.dtype if torch.is_tensor(params) else None
+      if torch.bfloat16 in (given, self.param_dtype) and given != self.param_dtype:
+        raise ValueError(f'PolicyPopulation: params is {given or type(params).__name__}, the template policy stores {self.param_dtype} '
+                         '(template.with_param_dtype(...), or params.to(...): the rows are read as they are)')
+      host = torch.as_tensor(params).detach().to('cpu', self.param_dtype)
       if host.dim() != 2 or host.shape[0] < 1 or host.shape[1] < self.n_params:
         raise ValueError(f'PolicyPopulation: params {tuple(host.shape)}: [P, >= {self.n_params}] (one row per member, packed like MLPPolicy.params)')
     self.n_policies = int(host.shape[0])
-    if (self.obs_dim, self.act_dim) != (OBS_DIM, ACT_DIM) and host.shape[1] % 4:      # (the Sawyer kernel reads every member's rows in 16-byte pieces)
-      host = torch.nn.functional.pad(host, (0, -host.shape[1] % 4))
+    piece = _piece(self.param_dtype, (self.obs_dim, self.act_dim) == (OBS_DIM, ACT_DIM))      # (the stepper kernels read every member's rows in 16-byte pieces)
+    if host.shape[1] % piece:
+      host = torch.nn.functional.pad(host, (0, -host.shape[1] % piece))
     self.params = host.clone().contiguous()
     self.to(template.device if device is None else device)
 
@@ -294,9 +356,14 @@ class PolicyPopulation:
     self.params = self.params.to(dev).contiguous()
     dims = self.dims + [0] * (4 - len(self.dims))
     self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
-                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=0, params=self.params.data_ptr())
+                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=PARAM_DTYPES[self.param_dtype], params=self.params.data_ptr())
     self.pop_struct = _abi.PolicyPopulation(n_policies=self.n_policies, envs_per_policy=self.envs_per_policy, param_stride=self.stride)
     return self
+
+  def widened(self):
+    """the float32 population of exactly the stored values (MLPPolicy.widened)"""
+    return PolicyPopulation(self.template.widened(), self.envs_per_policy, device=self.device, params=self.params.detach().to('cpu', torch.float32),
+                            obs_dim=self.obs_dim, act_dim=self.act_dim)
 
   def head(self, sample=True, eps_out=None):
     return self.template.head(sample=sample, eps_out=eps_out)
@@ -312,13 +379,9 @@ class PolicyPopulation:
     return layers
 
   def member(self, p):
-    """member p as a policy of its own (a copy of its row of .params)"""
-    layers = [(w.clone(), b.clone()) for w, b in self._layers_of(self.params[int(p)].detach().cpu())]
-    t = self.template
-    if self.gaussian:
-      return GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, device=self.device,
-                               obs_dim=self.obs_dim, act_dim=self.act_dim)
-    return MLPPolicy(layers, t.hidden_act, t.out_act, device=self.device, obs_dim=self.obs_dim, act_dim=self.act_dim)
+    """member p as a policy of its own (a copy of its row of .params, stored in the population's param_dtype)"""
+    layers = [(w.clone(), b.clone()) for w, b in self._layers_of(self.params[int(p)].detach().to('cpu', torch.float32))]
+    return _like(self.template, layers, self.device, self.param_dtype, self.obs_dim, self.act_dim)
 
   def policy_index(self, global_ids):
     """the member each GLOBAL env id runs"""
@@ -340,7 +403,7 @@ class PolicyPopulation:
     grid = x.new_zeros(L, M * G, x.shape[-1])
     grid[:, slot] = x
     h = grid.reshape(L, M, G, -1).permute(1, 0, 2, 3).reshape(M, L * G, -1)
-    layers = self._layers_of(self.params[m0:m1 + 1].to(x.device))
+    layers = self._layers_of(self.params[m0:m1 + 1].to(x.device, torch.float32))      # (bf16 rows: widened first)
     for l, (w, b) in enumerate(layers):
       h = torch.baddbmm(b[:, None, :], h, w.transpose(1, 2))
       if l + 1 < len(layers):
@@ -379,7 +442,7 @@ class AgentPair:
       require_widths(m, 'AgentPair', self.obs_dim, self.act_dim)
     template = forward
     for p, m in enumerate(members):
-      for what in ('__class__', 'dims', 'hidden_act', 'out_act') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
+      for what in ('__class__', 'dims', 'hidden_act', 'out_act', 'param_dtype') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
         if getattr(m, what) != getattr(template, what):
           raise ValueError(f'AgentPair: member {p} has {what.strip("_")} = {getattr(m, what)!r}, member 0 has {getattr(template, what)!r} '
                            '(the two agents of a pair share one architecture)')
@@ -404,12 +467,13 @@ class AgentPair:
       if g.numel() != self.goal_dim:
         raise ValueError(f"AgentPair: backward_goal is 'initial', None or ONE goal row of {self.goal_dim} values, got {g.numel()}")
       self.backward_goal = g.clone()
-    self.template, self.gaussian = template, isinstance(template, GaussianMLPPolicy)
+    self.template, self.gaussian, self.param_dtype = template, isinstance(template, GaussianMLPPolicy), template.param_dtype
     self.dims, self.hidden_act, self.out_act, self.macs = list(template.dims), template.hidden_act, template.out_act, template.macs
     self.n_params = sum(n * (k + 1) for k, n in zip(self.dims[:-1], self.dims[1:]))
-    host = torch.stack([m.params.detach().to('cpu', torch.float32) for m in members])
-    if not tabletop and host.shape[1] % 4:               # (the Sawyer kernel reads both agents' rows in 16-byte pieces)
-      host = torch.nn.functional.pad(host, (0, -host.shape[1] % 4))
+    host = torch.stack([m.params.detach().to('cpu', self.param_dtype) for m in members])
+    piece = _piece(self.param_dtype, tabletop)           # (the stepper kernels read both agents' rows in 16-byte pieces)
+    if host.shape[1] % piece:
+      host = torch.nn.functional.pad(host, (0, -host.shape[1] % piece))
     self.params = host.contiguous()
     self.to(template.device if device is None else device)
 
@@ -431,8 +495,18 @@ class AgentPair:
     self._initial_states_dev = None                                  # ('initial_states' as numpy, its rows on `dev`), filled by goal_table
     dims = self.dims + [0] * (4 - len(self.dims))
     self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
-                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=0, params=self.params.data_ptr())
+                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=PARAM_DTYPES[self.param_dtype], params=self.params.data_ptr())
     return self
+
+  def with_param_dtype(self, dtype):
+    """the pair of the values that stand in `.params` now, its agents stored as `dtype` (MLPPolicy.with_param_dtype)"""
+    goal = self.backward_goals if self.backward_goals is not None else self.backward_goal
+    return AgentPair(self.agent(0).with_param_dtype(dtype), self.agent(1).with_param_dtype(dtype), switch_every=self.switch_every,
+                     switch_on_success=self.switch_on_success, backward_goal=goal, device=self.device, obs_dim=self.obs_dim, act_dim=self.act_dim)
+
+  def widened(self):
+    """the float32 pair of exactly the stored values (MLPPolicy.widened)"""
+    return self.with_param_dtype(torch.float32)
 
   def head(self, sample=True, eps_out=None):
     return self.template.head(sample=sample, eps_out=eps_out)
@@ -479,20 +553,16 @@ class AgentPair:
     return layers
 
   def agent(self, k):
-    """agent k (0 forward, 1 reset) as a policy of its own (a copy of its row of .params)"""
-    layers = [(w.cpu().clone(), b.cpu().clone()) for w, b in self._layers_of(self.params[int(k)].detach())]
-    t = self.template
-    if self.gaussian:
-      return GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, device=self.device,
-                               obs_dim=self.obs_dim, act_dim=self.act_dim)
-    return MLPPolicy(layers, t.hidden_act, t.out_act, device=self.device, obs_dim=self.obs_dim, act_dim=self.act_dim)
+    """agent k (0 forward, 1 reset) as a policy of its own (a copy of its row of .params, stored in the pair's param_dtype)"""
+    layers = [(w.clone(), b.clone()) for w, b in self._layers_of(self.params[int(k)].detach().to('cpu', torch.float32))]
+    return _like(self.template, layers, self.device, self.param_dtype, self.obs_dim, self.act_dim)
 
   def __call__(self, obs, phase):
     """obs [..., N, obs_dim], phase [N] or [..., N] (0 forward, 1 reset) -> actions [..., N, act_dim] (Gaussian agents: at the mean): torch's statement -- close to the kernel,
     not bit-identical"""
     ph = torch.as_tensor(phase, device=obs.device).bool()
     acts = []
-    for row in self.params.detach().to(obs.device):                  # the layers are views of .params: no copy, and in-place updates are seen
+    for row in self.params.detach().to(obs.device, torch.float32):   # the layers are views of .params: no copy, and in-place updates are seen (bf16 rows: widened first)
       x = obs.to(torch.float32).reshape(-1, obs.shape[-1])
       layers = self._layers_of(row)
       for l, (w, b) in enumerate(layers):
@@ -510,7 +580,7 @@ class PairPopulation:
   act_dim=4 on the Sawyer door and peg; 32 / 8 on the minitaur; 46 / 9 on the kitchen) -- only the parameters differ.  The env with GLOBAL id g runs pair
   g // envs_per_policy (a multiple of 16).  `.params` [P, 2, stride] float32 holds every pair's rows (0 forward, 1 reset) in MLPPolicy's packing order and is what the
   kernel reads: write into it in place."""
-  SHARED = ('gaussian', 'dims', 'hidden_act', 'out_act', 'switch_every', 'switch_on_success')
+  SHARED = ('gaussian', 'dims', 'hidden_act', 'out_act', 'param_dtype', 'switch_every', 'switch_on_success')
   SHARED_HEAD = ('squash', 'log_std_bounds', 'log_std_map')
 
   def __init__(self, pairs, envs_per_policy=16, device=None):
@@ -540,10 +610,10 @@ class PairPopulation:
                          '(the pairs of a population share one architecture, head, switch rule and backward goal)')
     self.envs_per_policy, self.n_policies = G, len(members)
     self.gaussian, self.dims, self.hidden_act, self.out_act, self.macs, self.n_params = t.gaussian, list(t.dims), t.hidden_act, t.out_act, t.macs, t.n_params
-    self.switch_every, self.switch_on_success = t.switch_every, t.switch_on_success
+    self.switch_every, self.switch_on_success, self.param_dtype = t.switch_every, t.switch_on_success, t.param_dtype
     self.backward_goal, self.backward_goals = t.backward_goal, t.backward_goals
     self._head_of = t.template                                        # (a policy of the members' head: only its head settings are used)
-    self.params = torch.stack([m.params.detach().to('cpu', torch.float32) for m in members]).contiguous()      # [P, 2, stride]
+    self.params = torch.stack([m.params.detach().to('cpu', self.param_dtype) for m in members]).contiguous()      # [P, 2, stride]
     self.to(t.device if device is None else device)
 
   @staticmethod
@@ -575,7 +645,7 @@ class PairPopulation:
     self.params = self.params.to(dev).contiguous()
     dims = self.dims + [0] * (4 - len(self.dims))
     self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
-                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=0, params=self.params.data_ptr())
+                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=PARAM_DTYPES[self.param_dtype], params=self.params.data_ptr())
     self.pop_struct = _abi.PolicyPopulation(n_policies=self.n_policies, envs_per_policy=self.envs_per_policy, param_stride=self.stride)
     self._goals = self.pair(0)                                         # resolves and caches the backward goal on `dev` (goal_row / goal_table)
     return self
@@ -591,20 +661,15 @@ class PairPopulation:
 
   def pair(self, p):
     """pair p as an AgentPair of its own (a copy of its rows of .params)"""
-    rows = self.params[int(p)].detach().cpu()
-    t = self._head_of
-    agents = []
-    for row in rows:
-      layers, at = [], 0
-      for k, n in zip(self.dims[:-1], self.dims[1:]):
-        layers.append((row[at:at + n * k].reshape(n, k).clone(), row[at + n * k:at + n * k + n].clone()))
-        at += n * k + n
-      agents.append(GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, obs_dim=self.obs_dim,
-                                      act_dim=self.act_dim)
-                    if self.gaussian else MLPPolicy(layers, t.hidden_act, t.out_act, obs_dim=self.obs_dim, act_dim=self.act_dim))
+    rows = self.params[int(p)].detach().to('cpu', torch.float32)
+    agents = [_like(self._head_of, [(w.clone(), b.clone()) for w, b in _unpack(row, self.dims)], 'cpu', self.param_dtype, self.obs_dim, self.act_dim) for row in rows]
     goal = self.backward_goals if self.backward_goals is not None else self.backward_goal
     return AgentPair(agents[0], agents[1], switch_every=self.switch_every, switch_on_success=self.switch_on_success, backward_goal=goal, device=self.device,
                      obs_dim=self.obs_dim, act_dim=self.act_dim)
+
+  def widened(self):
+    """the float32 pairs of exactly the stored values (MLPPolicy.widened)"""
+    return PairPopulation([self.pair(p).widened() for p in range(self.n_policies)], self.envs_per_policy, device=self.device)
 
   def policy_index(self, global_ids):
     """the pair each GLOBAL env id runs"""

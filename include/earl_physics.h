@@ -300,7 +300,9 @@ int earl_sawyer_rollout_clocked(const earl_link_model* model, const earl_collisi
  * outputs, state left behind, counters.  clock as for earl_sawyer_rollout_clocked (may be NULL).
  * EARL_ERR_ARG before any HIP call: the policy and head rules of earl_tabletop.h's argument contract with the widths 14 / 4, and this entry point's own: NULL policy /
  * obs0 / actions / out->obs, policy->params not 16-byte aligned, T < 1, nv not 10 or 15, and everything earl_sawyer_rollout refuses.  The 64-lanes-per-env measurement
- * builds (earl_debug_set_physics_lanes(64)) have no policy form: EARL_ERR_ARG. */
+ * builds (earl_debug_set_physics_lanes(64)) have no policy form: EARL_ERR_ARG.
+ * policy->precision == EARL_PRECISION_BF16 (earl_tabletop.h): params holds uint16_t bf16 values, 16-byte aligned; each widens exactly (u << 16) into the same fmaf chain, so the
+ * launch returns the bits of the fp32 launch fed with the widened values. */
 int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
                                const earl_sawyer_out* out, earl_stream_t stream);
@@ -320,7 +322,9 @@ int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collisio
  *            the policy of step t + 1 reads it (lane by lane what that lane wrote; across a time slice under the release / acquire that carries qpos).  The state
  *            left behind, last_obs included, equals the full launch's.
  * EARL_ERR_ARG before any HIP call: everything earl_sawyer_policy_rollout refuses (but NULL actions / out->obs), the contract's population rules, and this entry
- * point's own: param_stride % 4 != 0 (every member's rows are read in 16-byte pieces), out->obs == NULL with st->last_obs == NULL. */
+ * point's own: param_stride % 4 != 0 (every member's rows are read in 16-byte pieces), out->obs == NULL with st->last_obs == NULL.
+ * policy->precision == EARL_PRECISION_BF16 (earl_tabletop.h): params holds uint16_t bf16 values, 16-byte aligned, every param_stride counts those elements and is a multiple
+ * of 8; each value widens exactly (u << 16) into the same fmaf chain, so the launch returns the bits of the fp32 launch fed with the widened values. */
 int earl_sawyer_population_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                    const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
                                    const uint64_t* clock, float* actions, const earl_sawyer_out* out, const earl_episode_summary* summary, earl_stream_t stream);
@@ -351,7 +355,9 @@ int earl_sawyer_population_rollout(const earl_link_model* model, const earl_coll
  * pointers may be NULL, as in earl_sawyer_population_rollout; without out->obs the env's row of st->last_obs is carried.  On the door, out->info receives only what the
  * lifelong switch leaves on a goal-switch row (the door's info dict of a pair launch is not offered); the peg's is written in the kernel as ever.
  * EARL_ERR_ARG before any HIP call: everything earl_sawyer_population_rollout refuses with pop = NULL, the contract's pair rules, and this entry point's own:
- * param_stride not a multiple of 4, backward_goal != NULL with cfg->n_goal_rows == 0 (the forward goal could not be restored). */
+ * param_stride not a multiple of 4, backward_goal != NULL with cfg->n_goal_rows == 0 (the forward goal could not be restored).
+ * policy->precision == EARL_PRECISION_BF16 (earl_tabletop.h): params holds uint16_t bf16 values, 16-byte aligned, every param_stride counts those elements and is a multiple
+ * of 8; each value widens exactly (u << 16) into the same fmaf chain, so the launch returns the bits of the fp32 launch fed with the widened values. */
 int earl_sawyer_pair_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                              const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_gaussian_head* head, const double* obs0, int32_t T,
                              const uint64_t* clock, float* actions, const earl_sawyer_out* out, earl_stream_t stream);
@@ -378,6 +384,8 @@ typedef struct earl_backward_goals {
   int32_t* row;          /* NULL or [n], caller-owned: the table row the env's reset goal came from; written at every entry into the reset phase, never read */
   int32_t* row_out;      /* NULL or [T, n]: the row drawn at env step t, -1 at a step without a draw */
 } earl_backward_goals;
+/* policy->precision == EARL_PRECISION_BF16 (earl_tabletop.h): params holds uint16_t bf16 values, 16-byte aligned, every param_stride counts those elements and is a multiple
+ * of 8; each value widens exactly (u << 16) into the same fmaf chain, so the launch returns the bits of the fp32 launch fed with the widened values. */
 int earl_sawyer_agents_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop, const earl_backward_goals* goals,
                                const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_sawyer_out* out,
@@ -385,7 +393,9 @@ int earl_sawyer_agents_rollout(const earl_link_model* model, const earl_collisio
 /* The policy contract on the host (libearl_host.so; host pointers): actions [n, A] of n observation rows obs [n, dims[0]], dims[0] in 1..256, hidden widths in 1..256,
  * the last layer A wide (head = NULL) or 2 A wide (rows 0..A-1 the mean, A..2A-1 the raw log_std), A >= 1.  eps [n, A] = the standard-normal draws to use with a
  * head in EARL_HEAD_SAMPLE mode; NULL (or EARL_HEAD_MEAN, or no head) evaluates the mean / the deterministic policy.  policy->out_act is applied last, as on the
- * device.  The oracle of the in-kernel policies' actions; EARL_OK or EARL_ERR_ARG.  (Not the `_cpu` twin of a device entry point: there is none.) */
+ * device.  The oracle of the in-kernel policies' actions; EARL_OK or EARL_ERR_ARG.  (Not the `_cpu` twin of a device entry point: there is none.)
+ * policy->precision == EARL_PRECISION_BF16: params holds uint16_t bf16 values (16-byte aligned), each widened exactly (u << 16) before it enters the chain -- the host
+ * statement of the stepper envs' bf16 launches, equal bit for bit to this call with precision = 0 on the widened values. */
 int32_t earl_mlp_policy_forward_cpu(const earl_mlp_policy* policy, const earl_gaussian_head* head, int32_t n, const float* obs, const float* eps, float* actions);
 /* the contract's scalar functions as compiled into libearl_host.so (csrc/policy_math.h): tanh_f32, exp_f32 and normal_quantile_f32 of a 24-bit k = word >> 8 */
 float earl_tanh_f32(float x);
@@ -510,7 +520,9 @@ int earl_kitchen_rollout_clocked(const void* model24, const earl_collision_model
  * policy); all five forms return the same bits.
  * EARL_ERR_ARG before any HIP call: everything earl_kitchen_rollout_clocked refuses, the policy and head rules of earl_tabletop.h's argument contract with the widths
  * 46 / 9, and this entry point's own: NULL policy / obs0 / actions, policy->params not 16-byte aligned.  n = 0 or T = 0: EARL_OK, nothing launched.
- * The lifelong wrapper's goal switch is not part of it, as for earl_kitchen_rollout. */
+ * The lifelong wrapper's goal switch is not part of it, as for earl_kitchen_rollout.
+ * policy->precision == EARL_PRECISION_BF16 (earl_tabletop.h): params holds uint16_t bf16 values, 16-byte aligned; each widens exactly (u << 16) into the same fmaf chain, so the
+ * launch returns the bits of the fp32 launch fed with the widened values. */
 int earl_kitchen_policy_rollout(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                                 const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T,
                                 const uint64_t* clock, float* actions, const earl_kitchen_out* out, earl_stream_t stream);
@@ -532,7 +544,9 @@ int earl_kitchen_policy_rollout(const void* model24, const earl_collision_model*
  * one-env-per-wave launch's shadow) evaluates on zeros with the rows of the member of the env it shadows, which is always an env of the batch.
  * EARL_ERR_ARG before any HIP call: everything earl_kitchen_policy_rollout refuses (but NULL actions / out pointers), the contract's population rules with group size 16
  * (csrc/policy_check.h: check_population, the member range against the global ids included), param_stride % 4 != 0 (every member's rows are read in 16-byte pieces).
- * st->last_obs is required as ever.  n = 0 or T = 0: EARL_OK, nothing launched. */
+ * st->last_obs is required as ever.  n = 0 or T = 0: EARL_OK, nothing launched.
+ * policy->precision == EARL_PRECISION_BF16 (earl_tabletop.h): params holds uint16_t bf16 values, 16-byte aligned, every param_stride counts those elements and is a multiple
+ * of 8; each value widens exactly (u << 16) into the same fmaf chain, so the launch returns the bits of the fp32 launch fed with the widened values. */
 int earl_kitchen_population_rollout(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                                     const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head,
                                     const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_kitchen_out* out,
@@ -571,7 +585,9 @@ int earl_kitchen_population_rollout(const void* model24, const earl_collision_mo
  * EARL_ERR_ARG before any HIP call: everything earl_kitchen_population_rollout refuses, the contract's pair rules (csrc/policy_check.h: NULL pair / phase /
  * steps_in_phase, switch_every < 1, switch_on_success other than 0 / 1, param_stride below the parameter count), param_stride % 4 != 0, pop->param_stride <
  * 2 * pair->param_stride, goals with a NULL table or n_rows < 1, goals together with pair->backward_goal, n_forward_goals < 0, and a backward goal or table given with
- * forward_goals == NULL or n_forward_goals < 1 (the forward goal could not be restored).  n = 0 or T = 0: EARL_OK, nothing launched. */
+ * forward_goals == NULL or n_forward_goals < 1 (the forward goal could not be restored).  n = 0 or T = 0: EARL_OK, nothing launched.
+ * policy->precision == EARL_PRECISION_BF16 (earl_tabletop.h): params holds uint16_t bf16 values, 16-byte aligned, every param_stride counts those elements and is a multiple
+ * of 8; each value widens exactly (u << 16) into the same fmaf chain, so the launch returns the bits of the fp32 launch fed with the widened values. */
 int earl_kitchen_agents_rollout(const void* model24, const earl_collision_model* col, const struct earl_kitchen_params* params, const earl_kitchen_cfg* cfg,
                                 const earl_kitchen_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop,
                                 const earl_backward_goals* goals, const double* forward_goals, int32_t n_forward_goals, const earl_gaussian_head* head, const double* obs0,
@@ -671,7 +687,9 @@ int earl_minitaur_rollout_clocked(const void* model24, const earl_collision_mode
  * 32 / 8, and this entry point's own: NULL policy / obs0 / actions, policy->params not 16-byte aligned, and out_act != EARL_ACT_TANH: the reference env raises on an
  * action outside +-(1 + 0.01), a kernel cannot, and the open-loop replay of the returned actions must not raise either, so the minitaur takes bounded policies only.
  * The generic-stepper comparison build
- * (earl_debug_set_minitaur_stepper(0)) has no policy form: EARL_ERR_ARG.  n = 0 or T = 0: EARL_OK, nothing launched. */
+ * (earl_debug_set_minitaur_stepper(0)) has no policy form: EARL_ERR_ARG.  n = 0 or T = 0: EARL_OK, nothing launched.
+ * policy->precision == EARL_PRECISION_BF16 (earl_tabletop.h): params holds uint16_t bf16 values, 16-byte aligned; each widens exactly (u << 16) into the same fmaf chain, so the
+ * launch returns the bits of the fp32 launch fed with the widened values. */
 int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                                  const earl_mlp_policy* policy, const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions,
                                  const earl_minitaur_out* out, earl_stream_t stream);
@@ -694,7 +712,9 @@ int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model
  * env it shadows, which is always an env of the batch: no id at or beyond cfg->env_offset + n is ever formed.
  * EARL_ERR_ARG before any HIP call: everything earl_minitaur_policy_rollout refuses (but NULL actions / out pointers) -- bounded policies only and no generic-stepper form
  * included --, the contract's population rules with group size 16 (csrc/policy_check.h: check_population, the member range against the global ids included),
- * param_stride % 4 != 0 (every member's rows are read in 16-byte pieces), out->obs == NULL with st->last_obs == NULL.  n = 0 or T = 0: EARL_OK, nothing launched. */
+ * param_stride % 4 != 0 (every member's rows are read in 16-byte pieces), out->obs == NULL with st->last_obs == NULL.  n = 0 or T = 0: EARL_OK, nothing launched.
+ * policy->precision == EARL_PRECISION_BF16 (earl_tabletop.h): params holds uint16_t bf16 values, 16-byte aligned, every param_stride counts those elements and is a multiple
+ * of 8; each value widens exactly (u << 16) into the same fmaf chain, so the launch returns the bits of the fp32 launch fed with the widened values. */
 int earl_minitaur_population_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                                      const earl_mlp_policy* policy, const earl_policy_population* pop, const earl_gaussian_head* head, const double* obs0, int32_t T,
                                      const uint64_t* clock, float* actions, const earl_minitaur_out* out, const earl_episode_summary* summary, earl_stream_t stream);
@@ -733,7 +753,9 @@ int earl_minitaur_population_rollout(const void* model24, const earl_collision_m
  * EARL_ERR_ARG before any HIP call: everything earl_minitaur_population_rollout refuses (no generic-stepper form included), the contract's pair rules
  * (csrc/policy_check.h: NULL pair / phase / steps_in_phase, switch_every < 1, switch_on_success other than 0 / 1, param_stride below the parameter count), param_stride
  * % 4 != 0, pop->param_stride < 2 * pair->param_stride, goals with a NULL table or n_rows < 1, goals together with pair->backward_goal, cfg->goal_change_frequency > 0.
- * n = 0 or T = 0: EARL_OK, nothing launched. */
+ * n = 0 or T = 0: EARL_OK, nothing launched.
+ * policy->precision == EARL_PRECISION_BF16 (earl_tabletop.h): params holds uint16_t bf16 values, 16-byte aligned, every param_stride counts those elements and is a multiple
+ * of 8; each value widens exactly (u << 16) into the same fmaf chain, so the launch returns the bits of the fp32 launch fed with the widened values. */
 int earl_minitaur_agents_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                                  const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop, const earl_backward_goals* goals,
                                  const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_minitaur_out* out,

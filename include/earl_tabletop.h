@@ -123,7 +123,8 @@ int earl_tabletop_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tableto
  * THE ARGUMENT CONTRACT of every closed-loop entry point -- the four of this header, and earl_physics.h's earl_sawyer_policy_rollout, earl_sawyer_population_rollout,
  * earl_sawyer_pair_rollout, earl_minitaur_policy_rollout, earl_minitaur_population_rollout, earl_kitchen_policy_rollout and earl_kitchen_population_rollout -- is one set of rules (csrc/policy_check.h states them once; tests/test_policy_contract.py holds every
  * entry point to them).  Each returns EARL_ERR_ARG before any HIP call for
- *   policy      NULL params; precision != 0; n_layers not 2 or 3; dims[0] != the env's observation width; dims[n_layers] != the env's action width (head == NULL) or
+ *   policy      NULL params; precision != 0 (the stepper envs of earl_physics.h: neither 0 nor EARL_PRECISION_BF16; with bf16: params not 16-byte aligned, a
+ *               param_stride -- counted in elements of the stored type everywhere -- that is not a multiple of 8 or lies below the parameter count); n_layers not 2 or 3; dims[0] != the env's observation width; dims[n_layers] != the env's action width (head == NULL) or
  *               twice it (head given); a hidden width that is not a multiple of 16 in 16..256; dims[3] != 0 with two layers; hidden_act not EARL_ACT_RELU / _TANH;
  *               out_act not EARL_ACT_NONE / _TANH
  *   head        mode not EARL_HEAD_MEAN / _SAMPLE; log_std_map not EARL_LOGSTD_CLAMP / _TANH; bounds that are not finite, min <= max and inside [-20, 4]
@@ -135,13 +136,19 @@ int earl_tabletop_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tableto
  * units read the weight rows in 16-byte pieces (params 16-byte aligned, param_stride % 4 == 0), the minitaur takes bounded policies only (out_act == EARL_ACT_TANH),
  * and this header's pair holds two weight sets in registers (EARL_PAIR_MAX_H2). */
 enum { EARL_ACT_NONE = 0, EARL_ACT_RELU = 1, EARL_ACT_TANH = 2 };
+/* earl_mlp_policy.precision: the STORED format of the parameters, named by its bits.  bf16 is a storage format only: a stored value u is the float32 whose bit
+ * pattern is (uint32_t)u << 16 (subnormals, +-0 and +-inf as they are) and enters the same fmaf chain in the same order, so a launch is bit-identical to the fp32
+ * launch fed with the widened values.  Taken by the closed-loop entry points of the door, the peg, the minitaur and the kitchen and by earl_mlp_policy_forward_cpu
+ * (earl_physics.h); every entry point of this header refuses it (the tabletop's weights sit in registers for the whole launch). */
+#define EARL_PRECISION_BF16 16
 typedef struct earl_mlp_policy {
   int32_t n_layers;     /* linear layers: 2 (one hidden) or 3 (two hidden) */
   int32_t dims[4];      /* dims[0] = 12, dims[n_layers] = 3 (6 with a Gaussian head, below); hidden widths multiples of 16 in 16..256; unused = 0 */
   int32_t hidden_act;   /* EARL_ACT_RELU or EARL_ACT_TANH */
   int32_t out_act;      /* EARL_ACT_NONE (the env clips to [-1, 1] itself, tabletop_manipulation.py:130) or EARL_ACT_TANH */
-  int32_t precision;    /* 0 = fp32; anything else is EARL_ERR_ARG (reserved) */
-  const float* params;  /* layer by layer: W_l [dims[l+1], dims[l]] row-major (= torch.nn.Linear.weight), then b_l [dims[l+1]] */
+  int32_t precision;    /* 0 = fp32; EARL_PRECISION_BF16 where an entry point says so (earl_physics.h); anything else is EARL_ERR_ARG */
+  const float* params;  /* layer by layer: W_l [dims[l+1], dims[l]] row-major (= torch.nn.Linear.weight), then b_l [dims[l+1]].  precision ==
+                           EARL_PRECISION_BF16: the same order in uint16_t bf16 values, biases too (the field keeps its type, the caller casts), 16-byte aligned */
 } earl_mlp_policy;
 
 /* reset (reset_first = 1) + T closed-loop steps, `episodes` times, in ONE launch.  Step t's action is pi(o), o the float32 observation the env last

@@ -1,21 +1,13 @@
 """What tests/test_minitaur_population.py and tests/test_kitchen_population.py share (a plain module: no tests, no fixtures): the population rows of the
-malformed-argument table, the well-formed combinations, and the compile-time reading of one unit."""
+malformed-argument table, the well-formed combinations, and where a source-text test finds a policy kernel's arguments."""
 import ctypes as C
-import json
 import os
 import re
-import shutil
-import subprocess
-import sys
-
-import pytest
 
 from conftest import REPO
 from earl_benchmark_amd import _abi
 
 CSRC = os.path.join(REPO, 'earl_benchmark_amd', 'csrc')
-HIPCC = '/opt/rocm/bin/hipcc'
-PARENT = os.path.join(REPO, 'tests', 'golden', 'population_parent_build.json')
 
 
 def pop_struct(n_policies=4, envs_per_policy=16, param_stride=4096):
@@ -47,22 +39,6 @@ def summaries(p):
   return [None, _abi.EpisodeSummary(ret=p, success_last=p, first_success=p), _abi.EpisodeSummary(ret=p), _abi.EpisodeSummary(first_success=p)]
 
 
-def compile_unit(unit, tmp_path):
-  """-> (scratch tool, assembly lines, resources per kernel) of one unit cross-compiled with the scratch tool's flags"""
-  from test_kitchen_policy_rollout import resources
-  if shutil.which(HIPCC) is None:
-    pytest.skip('needs hipcc (cross-compiles without a GPU)')
-  sys.path.insert(0, os.path.join(REPO, 'tools'))
-  try:
-    import scratch_in_loops as tool
-  finally:
-    sys.path.pop(0)
-  asm = tmp_path / (unit + '.s')
-  r = subprocess.run([HIPCC, *tool.FLAGS, '-Rpass-analysis=kernel-resource-usage', '-o', str(asm), os.path.join(CSRC, unit)], capture_output=True, text=True, timeout=900)
-  assert r.returncode == 0, r.stderr[-2000:]
-  return tool, open(asm).read().split('\n'), resources(r.stderr)
-
-
 def policy_fields(env_header, struct, plain):
   """-> (the members of the plain struct, the closed-loop fields the policy struct obtains -- csrc/policy_closed_loop.h's ClosedLoopArgs<plain>, of which `struct`
   derives and to which it adds nothing --, the text of that header): where a source-text test looks for a policy kernel's arguments"""
@@ -72,13 +48,3 @@ def policy_fields(env_header, struct, plain):
   plain_body = re.search(r'struct %s \{(.*?)\n\};' % plain, hdr, flags=re.S).group(1)
   fields = re.search(r'struct ClosedLoopArgs : Plain \{(.*?)\n\};', shared_hdr, flags=re.S).group(1)
   return plain_body, fields, shared_hdr
-
-
-def parent_build():
-  """the recorded parent build, or a skip when this compiler is not the one it was recorded with"""
-  want = json.load(open(PARENT))
-  version = subprocess.run([HIPCC, '--version'], capture_output=True, text=True).stdout
-  if want['compiler'] not in version:
-    pytest.skip('the parent build was recorded with another compiler: ' + want['compiler'])
-  return want
-

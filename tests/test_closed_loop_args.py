@@ -6,77 +6,43 @@ without a GPU:
   2. every policy kernel of the five units keeps that build's occupancy, LDS and scratch bytes, takes no more VGPRs, AGPRs or SGPRs, and has no scratch
      instruction inside a timestep loop;
   3. the closed-loop fields are declared once under csrc/, and no *_closed_loop body assigns one itself.
-The golden was recorded by `record()` below on the parent commit's csrc, with the flags of tools/scratch_in_loops.py."""
+The golden was recorded by `golden_of()` below on the parent commit's csrc, with the flags of tools/scratch_in_loops.py."""
 import os
 import re
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-import population_no_gpu as shared
-from conftest import GOLDEN
+import kernel_build
 
 UNITS = ('physics.hip', 'physics_w8.hip', 'physics_mt.hip', 'physics_kitchen.hip', 'physics_kitchen_policy.hip')
 PLAIN_UNITS = ('physics.hip', 'physics_w8.hip')
-PARENT = os.path.join(GOLDEN, 'closed_loop_parent_build.json')
 FIELDS = ('pol', 'head', 'gauss', 'obs0', 'act_out', 'pop_G', 'pop_stride', 'sum_ret', 'sum_last', 'sum_first', 'pair_phase', 'pair_sip', 'pair_stride', 'pair_goal',
           'pair_fwd', 'pair_goal_rows', 'pair_fwd_rows', 'pair_se', 'pair_sos', 'pair_agent', 'pair_fs', 'pair_bs', 'pair_row', 'pair_row_out')
 
 
-def sgprs(asm):
-  """{demangled kernel name: .sgpr_count} from the code-object metadata at the end of a unit's assembly"""
-  out, name = {}, None
-  for ln in asm:
-    m = re.match(r'\s+(?:- )?\.(name|sgpr_count):\s+(\S+)', ln)
-    if m and m.group(1) == 'name':
-      name = m.group(2)
-    elif m and name:
-      full = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip().replace('(anonymous namespace)::', '')
-      out[re.sub(r'^void ', '', full).split('(')[0]] = int(m.group(2))
-  return out
-
-
-def record(tmp_path):
-  """the five units of shared.CSRC cross-compiled side by side -> {unit: (scratch tool, assembly lines, resources per kernel with 'sgpr')}"""
-  def one(unit):
-    tool, asm, res = shared.compile_unit(unit, tmp_path)
-    count = sgprs(asm)
-    return tool, asm, {k: dict(v, sgpr=count[k]) for k, v in res.items()}
-  with ThreadPoolExecutor(len(UNITS)) as pool:
-    return dict(zip(UNITS, pool.map(one, UNITS)))
-
-
 def golden_of(units, compiler):
-  from test_kitchen_policy_rollout import digest, normalised_functions
-  plain = {u: {k: [len(b), digest(b)] for k, b in normalised_functions(units[u][1]).items() if 'policy' not in k} for u in PLAIN_UNITS}
+  """the golden of `units` (kernel_build.units(UNITS) on the parent commit's csrc) under kernel_build.compiler_version()'s name `compiler`"""
   return {'compiler': compiler,
           'what': 'the build before csrc/policy_closed_loop.h, cross-compiled with the flags of tools/scratch_in_loops.py: a digest per plain function of physics.hip and '
                   'physics_w8.hip (gfx950 assembly, comment lines and label numbers aside: [lines, sha256]) and the resources of every policy kernel of the five units '
                   '(tests/test_closed_loop_args.py)',
-          'plain_functions': plain,
-          'policy_kernel_resources': {u: {k: v for k, v in units[u][2].items() if 'policy' in k} for u in UNITS}}
+          'plain_functions': {u: {k: v for k, v in units[u].digests.items() if 'policy' not in k} for u in PLAIN_UNITS},
+          'policy_kernel_resources': {u: {k: v for k, v in units[u].resources.items() if 'policy' in k} for u in UNITS}}
 
 
 @pytest.fixture(scope='module')
-def units(tmp_path_factory):
-  import json
-  want = json.load(open(PARENT))
-  version = subprocess.run([shared.HIPCC, '--version'], capture_output=True, text=True).stdout
-  if want['compiler'] not in version:
-    pytest.skip('the parent build was recorded with another compiler: ' + want['compiler'])
-  return want, record(tmp_path_factory.mktemp('closed_loop_asm'))
+def units():
+  return kernel_build.recorded('closed_loop_parent_build.json'), kernel_build.units(UNITS)
 
 
 def test_plain_sawyer_functions_are_byte_identical_to_the_build_before(units):
-  from test_kitchen_policy_rollout import digest, normalised_functions
   want, got = units
   for unit in PLAIN_UNITS:
     plain = want['plain_functions'][unit]
-    fns = {k: b for k, b in normalised_functions(got[unit][1]).items() if 'policy' not in k}
+    fns = {k: v for k, v in got[unit].digests.items() if 'policy' not in k}
     assert set(fns) == set(plain), sorted(set(fns) ^ set(plain))
-    for name, (n_lines, sha) in plain.items():
-      assert (len(fns[name]), digest(fns[name])) == (n_lines, sha), (unit, name)
+    for name, lines_and_sha in plain.items():
+      assert fns[name] == lines_and_sha, (unit, name)
   names = ' '.join(want['plain_functions']['physics.hip'])
   for k in ('sawyer_rollout_kernelILi10ELi16ELb0E', 'sawyer_rollout_kernelILi10ELi16ELb1E', 'sawyer_rollout_kernelILi15ELi16ELb0E', 'sawyer_rollout_kernelILi15ELi16ELb1E',
             'sawyer_reset_kernelILi10E', 'sawyer_reset_kernelILi15E', 'sawyer_door_reward_kernel', 'sawyer_door_info_kernel', 'physics_kernelILi10E', 'physics_kernelILi15E'):
@@ -86,9 +52,10 @@ def test_plain_sawyer_functions_are_byte_identical_to_the_build_before(units):
 
 def test_every_policy_kernel_keeps_its_resources(units):
   want, got = units
+  tool = kernel_build.tool()
   seen = 0
   for unit in UNITS:
-    tool, asm, res = got[unit]
+    res = got[unit].resources
     was_unit = want['policy_kernel_resources'][unit]
     assert {k for k in res if 'policy' in k} == set(was_unit), unit
     for k, was in sorted(was_unit.items()):
@@ -97,19 +64,14 @@ def test_every_policy_kernel_keeps_its_resources(units):
       assert (now['occupancy'], now['lds'], now['scratch']) == (was['occupancy'], was['lds'], was['scratch']), (k, was, now)
       assert now['vgpr'] <= was['vgpr'] and now['agpr'] <= was['agpr'] and now['sgpr'] <= was['sgpr'], (k, was, now)
       seen += 1
-    for ln in tool.report(unit, asm, tool.KERNELS + tool.POLICY_DUO):
-      if 'policy' not in ln:
-        continue
-      print(ln)
-      if 'timestep loop' in ln:
-        assert ln.rstrip().endswith(': 0'), ln
-      else:      # (the two-wave minitaur kernel has one slot loop and no timestep loop: its scratch bytes are held above)
-        assert 'no scratch at all' in ln or 'no inner loop' in ln or 'slot loop' in ln, ln
+    # (the two-wave minitaur kernel has one slot loop and no timestep loop: its scratch bytes are held above)
+    kernel_build.check_scratch_lines([ln for ln in got[unit].scratch_report(tool.KERNELS + tool.POLICY_DUO) if 'policy' in ln],
+                                     otherwise=('no scratch at all', 'no inner loop', 'slot loop'))
   assert seen >= 9      # door, peg, peg time-sliced, door eight-wave, minitaur one-wave and two-wave, kitchen x 3
 
 
 def sources():
-  return {f: open(os.path.join(shared.CSRC, f)).read() for f in sorted(os.listdir(shared.CSRC)) if f.endswith(('.h', '.hip', '.inc', '.cpp'))}
+  return {f: open(os.path.join(kernel_build.CSRC, f)).read() for f in sorted(os.listdir(kernel_build.CSRC)) if f.endswith(('.h', '.hip', '.inc', '.cpp'))}
 
 
 def test_the_fields_are_declared_once_and_filled_once():

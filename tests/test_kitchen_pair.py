@@ -14,11 +14,12 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_build
 import population_no_gpu as shared
 from conftest import REPO
 from earl_benchmark_amd import _abi
 from policy_struct_helpers import aligned_params, head, variant
-from test_minitaur_pair import declared, goals_struct, pair_rows, pair_struct, parent_build
+from test_minitaur_pair import declared, goals_struct, pair_rows, pair_struct
 from test_sawyer_policy_rollout import pack, random_layers
 
 NAME = 'earl_kitchen_agents_rollout'
@@ -185,29 +186,23 @@ def test_python_refusals_and_the_pair_classes():
     env.rollout_pair(pair, 3)
 
 
-def test_plain_kernels_are_byte_identical_and_the_kernels_that_run_the_pair_keep_their_resources(tmp_path):
+def test_plain_kernels_are_byte_identical_and_the_kernels_that_run_the_pair_keep_their_resources():
   """physics_kitchen.hip and physics_kitchen_policy.hip cross-compiled once each.  Measured: every form occupancy 1 and LDS 162,048 bytes, 256 VGPR,
   AGPR 256 / 232 / 234 for <0> / <1> / <2> (before: 256 / 230 / 232), no scratch instruction inside a timestep loop; <1> and <2> none in the kernel at all"""
-  from test_kitchen_policy_rollout import digest, normalised_functions
-  want = parent_build()
-  _, asm, _ = shared.compile_unit('physics_kitchen.hip', tmp_path)
-  got = normalised_functions(asm)
+  want = kernel_build.recorded('pair_parent_build.json')
+  got = kernel_build.unit('physics_kitchen.hip').digests
   plain = want['plain_functions']['physics_kitchen.hip']
-  for name, (n_lines, sha) in plain.items():
-    assert (len(got[name]), digest(got[name])) == (n_lines, sha), name
+  for name, lines_and_sha in plain.items():
+    assert got[name] == lines_and_sha, name
   assert set(got) == set(plain)
-  tool, asm, res = shared.compile_unit('physics_kitchen_policy.hip', tmp_path)
+  unit = kernel_build.unit('physics_kitchen_policy.hip')
+  res = unit.resources
   assert {k for k in res if 'policy' in k} == {f'kitchen_policy_rollout_kernel<{duo}>' for duo in (0, 1, 2)}      # one kernel per form: no instantiation of its own
   for duo in (0, 1, 2):
     k = f'kitchen_policy_rollout_kernel<{duo}>'
     was, now = want['policy_kernel_resources'][k], res[k]
     print(k, was, '->', now)
     assert (now['occupancy'], now['lds']) == (was['occupancy'], was['lds']) and now['vgpr'] <= 256 and now['agpr'] <= 256
-  listing = tool.report('physics_kitchen_policy.hip', asm)
+  listing = unit.scratch_report()
   assert len(listing) == 3, listing
-  for ln in listing:
-    print(ln)
-    if 'timestep loop' in ln:
-      assert ln.rstrip().endswith(': 0'), ln
-    else:
-      assert 'no scratch at all' in ln, ln
+  kernel_build.check_scratch_lines(listing, otherwise=('no scratch at all',))

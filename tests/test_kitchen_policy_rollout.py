@@ -8,25 +8,20 @@ rollout kernel.  What can be held without a GPU:
      numbers aside); the policy kernels keep the plain kernels' occupancy and LDS and have no scratch instruction inside their timestep loops.
 tests/test_kitchen_policy_rollout_gpu.py holds the launch itself."""
 import ctypes as C
-import hashlib
-import json
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, REPO
+import kernel_build
+from conftest import REPO
 from earl_benchmark_amd import _abi
 from policy_struct_helpers import aligned_params, head, variant as variant_of
 from test_sawyer_policy_rollout import pack, random_layers
 
 CSRC = os.path.join(REPO, 'earl_benchmark_amd', 'csrc')
-HIPCC = '/opt/rocm/bin/hipcc'
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. declared, bound, exported
@@ -177,101 +172,36 @@ def test_python_refusals_need_no_gpu():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. compile time
-def normalised_functions(lines):
-  """{mangled name: the function's assembly lines} with comments, blank lines and the numbers of local labels removed"""
-  out, i = {}, 0
-  while i < len(lines):
-    m = re.match(r'^(_Z\w+):\s', lines[i])
-    if m:
-      end = next(j for j in range(i, len(lines)) if lines[j].startswith('.Lfunc_end'))
-      body = []
-      for ln in lines[i + 1:end]:
-        ln = ln.split(';')[0].rstrip()
-        if ln.strip():
-          body.append(re.sub(r'\.Ltmp\d+', '.Ltmp', re.sub(r'\.LBB\d+_', '.LBB_', ln)))
-      out[m.group(1)] = body
-      i = end
-    i += 1
-  return out
-
-
-def digest(body):
-  return hashlib.sha256('\n'.join(body).encode()).hexdigest()
-
-
-@pytest.fixture(scope='module')
-def kitchen_units(tmp_path_factory):
-  """physics_kitchen.hip and physics_kitchen_policy.hip cross-compiled once with the scratch tool's flags -> {unit: (assembly lines, resource remarks)}"""
-  if shutil.which(HIPCC) is None:
-    pytest.skip('needs hipcc (cross-compiles without a GPU)')
-  sys.path.insert(0, os.path.join(REPO, 'tools'))
-  try:
-    import scratch_in_loops as tool
-  finally:
-    sys.path.pop(0)
-  d = tmp_path_factory.mktemp('kitchen_asm')
-  procs = {}
-  for unit in ('physics_kitchen.hip', 'physics_kitchen_policy.hip'):
-    procs[unit] = subprocess.Popen([HIPCC, *tool.FLAGS, '-Rpass-analysis=kernel-resource-usage', '-o', str(d / (unit + '.s')), os.path.join(CSRC, unit)],
-                                   stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-  res = {}
-  for unit, pr in procs.items():
-    _, err = pr.communicate(timeout=900)
-    assert pr.returncode == 0, err[-2000:]
-    res[unit] = (open(d / (unit + '.s')).read().split('\n'), err)
-  return tool, res
-
-
-def test_plain_kitchen_kernels_are_byte_identical_to_the_build_before(kitchen_units):
-  _, res = kitchen_units
-  want = json.load(open(os.path.join(GOLDEN, 'kitchen_plain_kernels_asm.json')))
-  version = subprocess.run([HIPCC, '--version'], capture_output=True, text=True).stdout
-  if want['compiler'] not in version:
-    pytest.skip('the digests were recorded with another compiler: ' + want['compiler'])
-  got = normalised_functions(res['physics_kitchen.hip'][0])
+def test_plain_kitchen_kernels_are_byte_identical_to_the_build_before():
+  want = kernel_build.recorded('kitchen_plain_kernels_asm.json', what='the digests')
+  got = kernel_build.unit('physics_kitchen.hip').digests
   assert set(got) == set(want['functions']), sorted(set(got) ^ set(want['functions']))      # no policy kernel, no policy function in this unit
   names = ' '.join(want['functions'])
   for k in ('kitchen_rollout_kernelILi0E', 'kitchen_rollout_kernelILi1E', 'kitchen_rollout_kernelILi2E', 'kitchen_pre_kernel', 'kitchen_guard_kernel',
             'kitchen_finish_kernel', 'physics_kernelILi23ELi32ELb1E', 'physics_kernelILi23ELi32ELb0E'):
     assert k in names, k
-  for name, (n_lines, sha) in want['functions'].items():
-    assert (len(got[name]), digest(got[name])) == (n_lines, sha), name
+  for name, lines_and_sha in want['functions'].items():
+    assert got[name] == lines_and_sha, name
 
 
-def resources(remarks):
-  """{demangled kernel name: dict(vgpr, agpr, scratch, occupancy, lds)} from -Rpass-analysis=kernel-resource-usage"""
-  blocks = re.findall(r'Function Name: (\S+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+).*?'
-                      r'LDS Size \[bytes/block\]: (\d+)', remarks, flags=re.S)
-  res = {}
-  for mangled, vgpr, agpr, scratch, occ, lds in blocks:
-    name = subprocess.run(['c++filt', mangled], capture_output=True, text=True).stdout.strip().replace('(anonymous namespace)::', '')
-    res[re.sub(r'^void ', '', name).split('(')[0]] = dict(vgpr=int(vgpr), agpr=int(agpr), scratch=int(scratch), occupancy=int(occ), lds=int(lds))
-  return res
-
-
-def test_policy_kernels_keep_the_plain_kernels_occupancy_lds_and_scratch_free_timestep_loops(kitchen_units):
+def test_policy_kernels_keep_the_plain_kernels_occupancy_lds_and_scratch_free_timestep_loops():
   """Measured: every form occupancy 1 and LDS 162,048 bytes; <1> and <2> no scratch instruction in the kernel at all, <0> none inside its timestep
   loop (the plain <0> likewise keeps a few outside it)"""
-  tool, res = kitchen_units
-  assert 'kitchen_policy_rollout_kernel' in tool.KERNELS
-  plain, policy = resources(res['physics_kitchen.hip'][1]), resources(res['physics_kitchen_policy.hip'][1])
+  plain_unit, policy_unit = kernel_build.unit('physics_kitchen.hip'), kernel_build.unit('physics_kitchen_policy.hip')
+  assert 'kitchen_policy_rollout_kernel' in kernel_build.tool().KERNELS
+  plain, policy = plain_unit.resources, policy_unit.resources
   for duo in (0, 1, 2):
     a, b = plain[f'kitchen_rollout_kernel<{duo}>'], policy[f'kitchen_policy_rollout_kernel<{duo}>']
     print(duo, a, b)
     assert (b['occupancy'], b['lds']) == (a['occupancy'], a['lds']), (duo, a, b)
     assert b['vgpr'] <= 256 and b['agpr'] <= 256
   assert not any('kitchen_rollout_kernel' in k for k in policy) and not any('policy' in k for k in plain)
-  listing = tool.report('physics_kitchen_policy.hip', res['physics_kitchen_policy.hip'][0])
+  listing = policy_unit.scratch_report()
   assert len(listing) == 3 and all('kitchen_policy_rollout_kernel' in ln for ln in listing), listing
-  for ln in listing + tool.report('physics_kitchen.hip', res['physics_kitchen.hip'][0]):
-    print(ln)
-    # the rules of tests/test_no_scratch_in_timestep_loops.py
-    if 'timestep loop' in ln:
-      assert ln.rstrip().endswith(': 0'), ln
-    else:
-      assert 'no scratch at all' in ln or 'no inner loop' in ln or 'no loop' in ln, ln
+  # the rules of tests/test_no_scratch_in_timestep_loops.py
+  kernel_build.check_scratch_lines(listing + plain_unit.scratch_report(), otherwise=('no scratch at all', 'no inner loop', 'no loop'))
   # the policy phase is a called function (nothing of it is live across a timestep) and adds no LDS
-  asm = res['physics_kitchen_policy.hip'][0]
+  asm = policy_unit.asm
   assert sum('s_swappc_b64' in ln for ln in asm) == 3                    # one call per kernel, in the env-step loop
   assert any(re.match(r'^_ZN\w*kitchen_policy_action\w*:', ln) for ln in asm)
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_build
 import population_no_gpu as shared
 from earl_benchmark_amd import _abi
 from policy_struct_helpers import aligned_params, head, variant
@@ -159,21 +160,16 @@ def test_python_refusals_by_member_and_field():
     env.evaluate_population(pop, 3)
 
 
-def test_policy_kernels_keep_their_occupancy_lds_and_scratch_free_timestep_loops(tmp_path):
+def test_policy_kernels_keep_their_occupancy_lds_and_scratch_free_timestep_loops():
   """physics_kitchen_policy.hip cross-compiled once.  Measured: every form occupancy 1 and LDS 162,048 bytes, no scratch instruction inside a
   timestep loop; <1> and <2> none in the kernel at all"""
-  tool, asm, res = shared.compile_unit('physics_kitchen_policy.hip', tmp_path)
-  want = shared.parent_build()
+  unit = kernel_build.unit('physics_kitchen_policy.hip')
+  want, res = kernel_build.recorded('population_parent_build.json'), unit.resources
   for duo in (0, 1, 2):
     k = f'kitchen_policy_rollout_kernel<{duo}>'
     was, now = want['policy_kernel_resources'][k], res[k]
     print(k, was, '->', now)
     assert (now['occupancy'], now['lds']) == (was['occupancy'], was['lds']) and now['vgpr'] <= 256 and now['agpr'] <= 256
-  listing = tool.report('physics_kitchen_policy.hip', asm)
+  listing = unit.scratch_report()
   assert len(listing) == 3, listing
-  for ln in listing:
-    print(ln)
-    if 'timestep loop' in ln:
-      assert ln.rstrip().endswith(': 0'), ln
-    else:
-      assert 'no scratch at all' in ln, ln
+  kernel_build.check_scratch_lines(listing, otherwise=('no scratch at all',))

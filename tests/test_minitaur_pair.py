@@ -7,7 +7,6 @@
      pair, keep that build's occupancy and LDS, the one-wave kernel has no scratch instruction at all and the two-wave kernel stays within the plain one's bounds.
 tests/test_minitaur_pair_gpu.py holds the launches."""
 import ctypes as C
-import json
 import os
 import re
 
@@ -15,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_build
 import population_no_gpu as shared
 from conftest import REPO
 from earl_benchmark_amd import _abi
@@ -22,7 +22,6 @@ from policy_struct_helpers import aligned_params, head, variant
 from test_sawyer_policy_rollout import pack, random_layers
 
 NAME = 'earl_minitaur_agents_rollout'
-PARENT = os.path.join(REPO, 'tests', 'golden', 'pair_parent_build.json')
 
 
 def declared(name, n_args, after, before):
@@ -30,14 +29,6 @@ def declared(name, n_args, after, before):
   shared.declared(name, n_args, after, before)
   sig = _abi.SIGNATURES[name]
   assert any(getattr(a, '_type_', None) is _abi.AgentPair for a in sig) and any(getattr(a, '_type_', None) is _abi.BackwardGoals for a in sig)
-
-
-def parent_build():
-  want = json.load(open(PARENT))
-  import subprocess
-  if want['compiler'] not in subprocess.run([shared.HIPCC, '--version'], capture_output=True, text=True).stdout:
-    pytest.skip('the parent build was recorded with another compiler: ' + want['compiler'])
-  return want
 
 
 def pair_struct(p, stride, se=(3, 2), sos=1, goal=None, phase=True, sip=True, outs=True):
@@ -223,23 +214,22 @@ def test_python_refusals_and_the_pair_classes():
     env.rollout_pair(pair, 3)
 
 
-def test_plain_kernels_are_byte_identical_and_the_kernels_that_run_the_pair_keep_their_resources(tmp_path):
+def test_plain_kernels_are_byte_identical_and_the_kernels_that_run_the_pair_keep_their_resources():
   """physics_mt.hip cross-compiled once.  Measured: one-wave policy kernel 256 VGPR / 178 AGPR (before: 172), no scratch instruction in the kernel,
   occupancy 1, LDS 88,208; two-wave policy kernel 12 loads and 6 stores in its slot loop (before: 10 and 3), occupancy 2, LDS 158,512"""
-  from test_kitchen_policy_rollout import digest, normalised_functions
-  tool, asm, res = shared.compile_unit('physics_mt.hip', tmp_path)
-  want = parent_build()
-  got = normalised_functions(asm)
+  unit, tool = kernel_build.unit('physics_mt.hip'), kernel_build.tool()
+  want = kernel_build.recorded('pair_parent_build.json')
+  got, res = unit.digests, unit.resources
   plain = want['plain_functions']['physics_mt.hip']
-  for name, (n_lines, sha) in plain.items():
-    assert (len(got[name]), digest(got[name])) == (n_lines, sha), name
+  for name, lines_and_sha in plain.items():
+    assert got[name] == lines_and_sha, name
   assert {k for k in got if 'policy' not in k} == set(plain)
   assert {k for k in res if 'policy' in k} == {'minitaur_policy_kernel<false, true>', 'minitaur_policy_duo_kernel'}      # one kernel per form: no instantiation of its own
   for k in ('minitaur_policy_kernel<false, true>', 'minitaur_policy_duo_kernel'):
     was, now = want['policy_kernel_resources'][k], res[k]
     print(k, was, '->', now)
     assert (now['occupancy'], now['lds']) == (was['occupancy'], was['lds']) and now['vgpr'] <= 256 and now['agpr'] <= 256
-  lines = tool.report('physics_mt.hip', asm, kernels=tool.KERNELS + tool.POLICY_DUO)
+  lines = unit.scratch_report(tool.KERNELS + tool.POLICY_DUO)
   one = [ln for ln in lines if 'minitaur_policy_kernel<false, true>' in ln]
   duo = [ln for ln in lines if 'minitaur_policy_duo_kernel' in ln]
   assert len(one) == 1 and len(duo) == 1, lines

@@ -9,20 +9,16 @@ tests/test_minitaur_policy_rollout_gpu.py holds the launch itself."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import kernel_build
 from conftest import REPO
 from earl_benchmark_amd import _abi
 from policy_struct_helpers import aligned_params, head, variant as variant_of
 from test_sawyer_policy_rollout import forward_cpu, pack, random_layers
-
-CSRC = os.path.join(REPO, 'earl_benchmark_amd', 'csrc')
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. declared, bound, exported
@@ -141,37 +137,23 @@ def test_policy_classes_take_the_minitaur_widths_and_the_other_envs_refuse_them(
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. compile time
-@pytest.mark.skipif(shutil.which('/opt/rocm/bin/hipcc') is None, reason='needs hipcc (cross-compiles without a GPU)')
-def test_policy_kernels_keep_the_plain_kernels_occupancy_lds_and_scratch_bounds(tmp_path):
+def test_policy_kernels_keep_the_plain_kernels_occupancy_lds_and_scratch_bounds():
   """physics_mt.hip cross-compiled once with the tool's flags: register, LDS and scratch counts only.
   Measured: one-wave policy kernel no scratch instruction at all, occupancy 1, LDS 88,208; two-wave policy kernel 8 loads and 2 stores in its slot
   loop (plain: 12 and 3), occupancy 2, LDS 158,512"""
-  sys.path.insert(0, os.path.join(REPO, 'tools'))
-  try:
-    import scratch_in_loops as tool
-  finally:
-    sys.path.pop(0)
+  unit, tool = kernel_build.unit('physics_mt.hip'), kernel_build.tool()
   assert 'minitaur_policy_kernel' in tool.KERNELS and not any('duo' in k and 'policy' in k for k in tool.KERNELS)
-  asm = tmp_path / 'physics_mt.s'
-  r = subprocess.run(['/opt/rocm/bin/hipcc', *tool.FLAGS, '-Rpass-analysis=kernel-resource-usage', '-o', str(asm), os.path.join(CSRC, 'physics_mt.hip')],
-                     capture_output=True, text=True, timeout=900)
-  assert r.returncode == 0, r.stderr[-2000:]
-  text = open(asm).read().split('\n')
-  default = tool.report('physics_mt.hip', text)
+  default = unit.scratch_report()
   assert not any('minitaur_policy_duo_kernel' in ln for ln in default)   # the default listing keeps ONE slot-loop line
   assert sum('slot loop' in ln for ln in default) == 1
   one = [ln for ln in default if 'minitaur_policy_kernel<false, true>' in ln]
   assert len(one) == 1, default
-  assert 'no scratch at all' in one[0] or ('timestep loop' in one[0] and one[0].rstrip().endswith(': 0')), one[0]
-  duo = [ln for ln in tool.report('physics_mt.hip', text, kernels=tool.KERNELS + tool.POLICY_DUO) if 'minitaur_policy_duo_kernel' in ln]
+  kernel_build.check_scratch_lines(one, otherwise=('no scratch at all',))
+  duo = [ln for ln in unit.scratch_report(tool.KERNELS + tool.POLICY_DUO) if 'minitaur_policy_duo_kernel' in ln]
   assert len(duo) == 1 and 'slot loop' in duo[0], duo
-  print(one[0]); print(duo[0])
+  print(duo[0])
   m = re.search(r': (\d+) loads, (\d+) stores$', duo[0].rstrip())
   assert m and int(m.group(1)) <= 64 and int(m.group(2)) <= 8, duo[0]     # the bounds of tests/test_no_scratch_in_timestep_loops.py for the plain two-wave kernel
-  blocks = re.findall(r'Function Name: (\S+).*?Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)', r.stderr, flags=re.S)
-  res = {}
-  for mangled, occ, lds in blocks:
-    name = subprocess.run(['c++filt', mangled], capture_output=True, text=True).stdout.strip().replace('(anonymous namespace)::', '')
-    res[re.sub(r'^void ', '', name).split('(')[0]] = (int(occ), int(lds))
+  res = {k: (v['occupancy'], v['lds']) for k, v in unit.resources.items()}
   assert res['minitaur_policy_kernel<false, true>'] == res['minitaur_kernel<false, true>'], res
   assert res['minitaur_policy_duo_kernel'] == res['minitaur_duo_kernel'], res

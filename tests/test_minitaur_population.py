@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_build
 import population_no_gpu as shared
 from earl_benchmark_amd import _abi
 from policy_struct_helpers import aligned_params, head, variant
@@ -164,26 +165,25 @@ def test_python_refusals_by_member_and_field():
     env.evaluate_population(pop, 3)
 
 
-def test_plain_kernels_are_byte_identical_and_the_policy_kernels_keep_their_resources(tmp_path):
+def test_plain_kernels_are_byte_identical_and_the_policy_kernels_keep_their_resources():
   """physics_mt.hip cross-compiled once.  Measured: one-wave policy kernel 256 VGPR / 172 AGPR, no scratch instruction in the kernel, occupancy 1,
   LDS 88,208; two-wave policy kernel 10 loads and 3 stores in its slot loop (plain: 12 and 3), occupancy 2, LDS 158,512"""
-  from test_kitchen_policy_rollout import digest, normalised_functions
-  tool, asm, res = shared.compile_unit('physics_mt.hip', tmp_path)
-  want = shared.parent_build()
-  got = normalised_functions(asm)
-  for name, (n_lines, sha) in want['minitaur_plain_functions'].items():
-    assert (len(got[name]), digest(got[name])) == (n_lines, sha), name
+  unit, tool = kernel_build.unit('physics_mt.hip'), kernel_build.tool()
+  want = kernel_build.recorded('population_parent_build.json')
+  got, res = unit.digests, unit.resources
+  for name, lines_and_sha in want['minitaur_plain_functions'].items():
+    assert got[name] == lines_and_sha, name
   assert {k for k in got if 'policy' not in k} == set(want['minitaur_plain_functions'])
   for k in ('minitaur_policy_kernel<false, true>', 'minitaur_policy_duo_kernel'):
     was, now = want['policy_kernel_resources'][k], res[k]
     print(k, was, '->', now)
     assert (now['occupancy'], now['lds']) == (was['occupancy'], was['lds']) and now['vgpr'] <= 256 and now['agpr'] <= 256
-  lines = tool.report('physics_mt.hip', asm, kernels=tool.KERNELS + tool.POLICY_DUO)
+  lines = unit.scratch_report(tool.KERNELS + tool.POLICY_DUO)
   one = [ln for ln in lines if 'minitaur_policy_kernel<false, true>' in ln]
   duo = [ln for ln in lines if 'minitaur_policy_duo_kernel' in ln]
   assert len(one) == 1 and len(duo) == 1, lines
-  print(one[0]); print(duo[0])
-  assert 'no scratch at all' in one[0] or ('timestep loop' in one[0] and one[0].rstrip().endswith(': 0')), one[0]
+  print(duo[0])
+  kernel_build.check_scratch_lines(one, otherwise=('no scratch at all',))
   import re
   m = re.search(r': (\d+) loads, (\d+) stores$', duo[0].rstrip())
   assert m and int(m.group(1)) <= 64 and int(m.group(2)) <= 8, duo[0]     # the bounds of tests/test_no_scratch_in_timestep_loops.py for the plain two-wave kernel

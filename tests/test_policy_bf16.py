@@ -11,14 +11,13 @@ held without a GPU:
 tests/test_policy_bf16_gpu.py holds the launches."""
 import ctypes as C
 import re
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 import torch
 
+import kernel_build
 import policy_bf16_cases as B
-import population_no_gpu as shared
 from earl_benchmark_amd import _abi
 from policy_struct_helpers import variant
 from test_sawyer_policy_rollout import random_layers
@@ -370,16 +369,15 @@ BF16_UNITS = {'physics_bf16.hip': 'physics.hip', 'physics_w8_bf16.hip': 'physics
               'physics_kitchen_policy_bf16.hip': 'physics_kitchen_policy.hip'}
 
 
-def test_the_bf16_units_keep_occupancy_and_lds_and_have_no_scratch_in_a_timestep_loop(tmp_path):
+def test_the_bf16_units_keep_occupancy_and_lds_and_have_no_scratch_in_a_timestep_loop():
   import json
   import os
   from conftest import GOLDEN
   want = json.load(open(os.path.join(GOLDEN, 'closed_loop_parent_build.json')))['policy_kernel_resources']      # the float32 policy kernels (tests/test_closed_loop_args.py holds them to it)
-  with ThreadPoolExecutor(len(BF16_UNITS)) as pool:
-    built = dict(zip(BF16_UNITS, pool.map(lambda u: shared.compile_unit(u, tmp_path), BF16_UNITS)))
+  built, tool = kernel_build.units(BF16_UNITS), kernel_build.tool()
   seen = 0
   for unit, twin in BF16_UNITS.items():
-    tool, asm, res = built[unit]
+    res = built[unit].resources
     kernels = {k: v for k, v in res.items() if 'policy' in k}
     assert all(k.startswith('bf16::') for k in kernels), sorted(kernels)             # a kernel trace tells the two forms apart
     assert {k.replace('bf16::', '') for k in kernels} == set(want[twin]), (unit, sorted(kernels))
@@ -389,18 +387,14 @@ def test_the_bf16_units_keep_occupancy_and_lds_and_have_no_scratch_in_a_timestep
       print(unit, k, now, 'float32:', fp32)
       assert (now['occupancy'], now['lds']) == (fp32['occupancy'], fp32['lds']), (k, now, fp32)
       seen += 1
-    lines = [ln for ln in tool.report(unit, asm, tool.KERNELS + tool.POLICY_DUO) if 'policy' in ln]
+    lines = [ln for ln in built[unit].scratch_report(tool.KERNELS + tool.POLICY_DUO) if 'policy' in ln]
     assert len(lines) == len(kernels), lines
-    for ln in lines:
-      print(ln)
-      if 'timestep loop' in ln:
-        assert ln.rstrip().endswith(': 0'), ln
-      else:      # (the two-wave minitaur kernel has one slot loop and no timestep loop, like its float32 form)
-        assert 'no scratch at all' in ln or 'slot loop' in ln, ln
+    # (the two-wave minitaur kernel has one slot loop and no timestep loop, like its float32 form)
+    kernel_build.check_scratch_lines(lines, otherwise=('no scratch at all', 'slot loop'))
   assert seen == 9      # door, peg, peg time-sliced, door eight-wave, minitaur one-wave and two-wave, kitchen x 3
   # the weight path: 16-byte loads in the function that evaluates the policy
   for unit in BF16_UNITS:
-    asm = built[unit][1]
+    asm = built[unit].asm
     start = next(i for i, ln in enumerate(asm) if re.match(r'^_Z\w*policy_action\w*:', ln))
     end = next(i for i in range(start, len(asm)) if asm[i].startswith('.Lfunc_end'))
     body = '\n'.join(asm[start:end])

@@ -12,8 +12,6 @@ Without a GPU, through csrc/libearl_host.so (the host twin) -- and csrc/libearl_
 tests/test_policy_pair_gpu.py holds the device to the host twin bit for bit."""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -21,11 +19,12 @@ import pytest
 import torch
 
 import hip_harness as hx
+import kernel_build
 from conftest import REPO
 from earl_benchmark_amd import _abi
 from gaussian_policy_helpers import GaussPolicy, head_struct
 from pair_helpers import (INITIAL, OUT, Pair, PairState, assert_bits, goal_draw, handover_rule, pair_rollout, pair_struct, single_rollout, still_pair, with_goal_row)
-from test_policy_rollout import CSRC, Policy, final_state, restore, snapshot
+from test_policy_rollout import Policy, final_state, restore, snapshot
 
 CPU = 'cpu'
 OFFSET = 3
@@ -594,24 +593,10 @@ def test_lifelong_wrapper_refuses_and_the_three_object_env_has_no_pair_entry():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 10. kernel resources
-FIGURES = ('TotalSGPRs', 'VGPRs', 'AGPRs', 'ScratchSize [bytes/lane]', 'Occupancy [waves/SIMD]', 'LDS Size [bytes/block]')
-
-
-@pytest.mark.skipif(shutil.which('/opt/rocm/bin/hipcc') is None, reason='needs hipcc (cross-compiles without a GPU)')
-def test_the_pair_kernels_have_no_scratch_and_the_recorded_figures(tmp_path):
-  flags = re.search(r'^HIPFLAGS\s*\?=\s*(.*)$', open(os.path.join(CSRC, 'Makefile')).read(), flags=re.M).group(1).replace('$(ARCH)', 'gfx950').split()
-  r = subprocess.run(['/opt/rocm/bin/hipcc', *flags, '--cuda-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', str(tmp_path / 'pair.o'),
-                      os.path.join(CSRC, 'tabletop_policy_pair.hip')], capture_output=True, text=True, timeout=1200)
-  assert r.returncode == 0, r.stderr[-2000:]
-  now = {}
-  for blk in r.stderr.split('remark: Function Name: ')[1:]:
-    now[blk.split()[0]] = tuple(int(re.search(re.escape(f) + r': (\d+)', blk).group(1)) for f in FIGURES)
+def test_the_pair_kernels_have_no_scratch_and_the_recorded_figures():
+  now = kernel_build.unit('tabletop_policy_pair.hip').figures
   assert len(now) == 6 and all('policy_pair_kernel' in k for k in now), sorted(now)      # NT2 in {0, 1, 2} x {deterministic, Gaussian head}
-  recorded = {}
-  for line in open(os.path.join(REPO, 'profiles', 'policy_kernel_resources.txt')):
-    if line.startswith('Name: '):
-      parts = dict(p.split(': ') for p in line.strip().split(';'))
-      recorded.setdefault(parts['Name'], []).append(tuple(int(parts[f]) for f in FIGURES))
+  recorded = kernel_build.recorded_figures()
   for name, fig in now.items():
     print(name, fig)
     assert fig[3] == 0, (name, 'scratch', fig[3])

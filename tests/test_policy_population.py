@@ -11,7 +11,6 @@ tests/test_policy_population_gpu.py holds the device to the host twin bit for bi
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,11 +18,12 @@ import pytest
 import torch
 
 import hip_harness as hx
+import kernel_build
 from conftest import REPO
 from earl_benchmark_amd import _abi
 from gaussian_policy_helpers import GaussPolicy, gaussian_rollout, head_struct
 from population_helpers import (OUT, SUMMARY, Population, assert_bits, members_needed, per_policy_launches, population_rollout, summary_by_definition)
-from test_policy_rollout import CSRC, Policy, final_state, policy_rollout, restore, snapshot
+from test_policy_rollout import Policy, final_state, policy_rollout, restore, snapshot
 
 CPU = 'cpu'
 OFFSET = 3
@@ -407,30 +407,15 @@ def test_the_three_object_env_has_no_population_entry():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 7. kernel resources
-FIGURES = ('TotalSGPRs', 'VGPRs', 'AGPRs', 'ScratchSize [bytes/lane]', 'Occupancy [waves/SIMD]', 'LDS Size [bytes/block]')
-
-
-@pytest.mark.skipif(shutil.which('/opt/rocm/bin/hipcc') is None, reason='needs hipcc (cross-compiles without a GPU)')
-def test_existing_kernels_keep_their_recorded_figures_and_the_new_ones_have_no_scratch(tmp_path):
-  flags = re.search(r'^HIPFLAGS\s*\?=\s*(.*)$', open(os.path.join(CSRC, 'Makefile')).read(), flags=re.M).group(1).replace('$(ARCH)', 'gfx950').split()
-  units = ('tabletop_policy', 'tabletop_policy_gaussian', 'tabletop_policy_population')
-  procs = [subprocess.Popen(['/opt/rocm/bin/hipcc', *flags, '--cuda-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', str(tmp_path / f'{u}.o'),
-                             os.path.join(CSRC, f'{u}.hip')], stdout=subprocess.DEVNULL, stderr=open(tmp_path / f'{u}.txt', 'w')) for u in units]
-  for p in procs:
-    assert p.wait(timeout=1200) == 0, open(tmp_path / f'{units[procs.index(p)]}.txt').read()[-2000:]
+def test_existing_kernels_keep_their_recorded_figures_and_the_new_ones_have_no_scratch():
   now = {}
-  for u in units:
-    for blk in open(tmp_path / f'{u}.txt').read().split('remark: Function Name: ')[1:]:
-      now[blk.split()[0]] = tuple(int(re.search(re.escape(f) + r': (\d+)', blk).group(1)) for f in FIGURES)
+  for unit in kernel_build.units(('tabletop_policy.hip', 'tabletop_policy_gaussian.hip', 'tabletop_policy_population.hip')).values():
+    now.update(unit.figures)
   old = {k: v for k, v in now.items() if 'policy_rollout_kernel' in k}
   new = {k: v for k, v in now.items() if 'policy_population_kernel' in k}
   assert len(old) == 20 and len(new) == 20 and len(now) == 40, sorted(now)
   # every line on record of a kernel that still exists says what the compiler says now (the record was written before this feature and appended to after)
-  recorded = {}
-  for line in open(os.path.join(REPO, 'profiles', 'policy_kernel_resources.txt')):
-    if line.startswith('Name: '):
-      parts = dict(p.split(': ') for p in line.strip().split(';'))
-      recorded.setdefault(parts['Name'], []).append(tuple(int(parts[f]) for f in FIGURES))
+  recorded = kernel_build.recorded_figures()
   for name, fig in old.items():
     assert len(recorded.get(name, [])) >= 2 and all(r == fig for r in recorded[name]), (name, fig, recorded.get(name))
   for name, fig in new.items():

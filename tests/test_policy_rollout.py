@@ -10,7 +10,6 @@ Without a GPU, through csrc/libearl_host.so (the kernel's own header, csrc/table
 tests/test_policy_rollout_gpu.py holds the device to the host bit for bit."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 from fractions import Fraction
 
@@ -19,6 +18,7 @@ import pytest
 import torch
 
 import hip_harness as hx
+import kernel_build
 from conftest import REPO
 from earl_benchmark_amd import _abi
 from oracle import tabletop_oracle as orc
@@ -421,14 +421,8 @@ def test_rollout_policy_on_the_host_through_the_loader_and_the_wrappers():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6. no scratch
-@pytest.mark.skipif(shutil.which('/opt/rocm/bin/hipcc') is None, reason='needs hipcc (cross-compiles without a GPU)')
-def test_no_instantiation_of_the_policy_kernel_uses_scratch(tmp_path):
-  import re
-  flags = re.search(r'^HIPFLAGS\s*\?=\s*(.*)$', open(os.path.join(CSRC, 'Makefile')).read(), flags=re.M).group(1).replace('$(ARCH)', 'gfx950').split()
-  r = subprocess.run(['/opt/rocm/bin/hipcc', *flags, '--cuda-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', str(tmp_path / 'p.o'),
-                      os.path.join(CSRC, 'tabletop_policy.hip')], capture_output=True, text=True, timeout=900)
-  assert r.returncode == 0, r.stderr[-2000:]
-  blocks = re.findall(r'Function Name: (\S*policy_rollout_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+)', r.stderr, flags=re.S)
-  assert len(blocks) == 10, blocks                                      # NT2 = 0..4 x GENERAL
-  for name, scratch in blocks:
-    assert scratch == '0', (name, scratch)
+def test_no_instantiation_of_the_policy_kernel_uses_scratch():
+  figures = {k: fig for k, fig in kernel_build.unit('tabletop_policy.hip').figures.items() if 'policy_rollout_kernel' in k}
+  assert len(figures) == 10, figures                                    # NT2 = 0..4 x GENERAL
+  for name, fig in figures.items():
+    assert fig[3] == 0, (name, fig[3])

@@ -9,14 +9,12 @@ tests/test_sawyer_population_gpu.py holds the launches."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import kernel_build
 from conftest import REPO
 from earl_benchmark_amd import _abi
 from policy_struct_helpers import aligned_params, head as head_of, variant as variant_of
@@ -176,17 +174,12 @@ def test_new_argument_errors_need_no_gpu():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. compile time
-@pytest.mark.skipif(shutil.which('/opt/rocm/bin/hipcc') is None, reason='needs hipcc (cross-compiles without a GPU)')
-def test_the_kernels_that_run_a_population_keep_the_timestep_loop_free_of_scratch_and_the_occupancy(tmp_path):
+def test_the_kernels_that_run_a_population_keep_the_timestep_loop_free_of_scratch_and_the_occupancy():
   """A population and a summary are wave-uniform runtime branches inside the four existing sawyer_policy_rollout_kernel instantiations (no new instantiation, no
   sibling kernel): each has zero scratch instructions inside its timestep loop (tools/scratch_in_loops.py's count) and the occupancy and LDS of the
   sawyer_rollout_kernel instantiation of the same template arguments in the same unit.  That these ARE the kernels a population runs: the member offset and the
   summary pointers are fields of SawyerPolicyArgs, read by sawyer_policy_action and the rollout body, and no other kernel takes that struct."""
-  sys.path.insert(0, os.path.join(REPO, 'tools'))
-  try:
-    import scratch_in_loops as tool
-  finally:
-    sys.path.pop(0)
+  tool = kernel_build.tool()
   hdr = open(os.path.join(CSRC, 'physics_env_sawyer.h')).read()
   from population_no_gpu import policy_fields
   plain, policy, shared_hdr = policy_fields('physics_env_sawyer.h', 'SawyerPolicyArgs', 'SawyerArgs')
@@ -199,21 +192,11 @@ def test_the_kernels_that_run_a_population_keep_the_timestep_loop_free_of_scratc
   kernels = set(re.findall(r'void (\w+)\(const SawyerPolicyArgs a\)', hdr))
   assert kernels == {'sawyer_policy_rollout_kernel'} and 'sawyer_policy_rollout_kernel' in tool.KERNELS
   want = {'physics.hip': {'<10, 16, false>', '<15, 16, false>', '<15, 16, true>'}, 'physics_w8.hip': {'<10, 16, false>'}}
-  for unit, insts in want.items():
-    asm = tmp_path / (unit + '.s')
-    r = subprocess.run(['/opt/rocm/bin/hipcc', *tool.FLAGS, '-Rpass-analysis=kernel-resource-usage', '-o', str(asm), os.path.join(CSRC, unit)],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lines = [ln for ln in tool.report(unit, open(asm).read().split('\n')) if 'sawyer_policy_rollout_kernel' in ln]
+  for unit_name, insts in want.items():
+    unit = kernel_build.unit(unit_name)
+    lines = [ln for ln in unit.scratch_report() if 'sawyer_policy_rollout_kernel' in ln]
     assert {re.search(r'sawyer_policy_rollout_kernel(<[^>]*>)', ln).group(1) for ln in lines} == insts, lines
-    for ln in lines:
-      assert 'no scratch at all' in ln or ('timestep loop' in ln and ln.rstrip().endswith(': 0')), ln
-    blocks = re.findall(r'Function Name: (\S+).*?Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)', r.stderr, flags=re.S)
-    res = {}
-    for mangled, occ, lds in blocks:
-      name = subprocess.run(['c++filt', mangled], capture_output=True, text=True).stdout.strip().replace('(anonymous namespace)::', '')
-      m = re.match(r'void (sawyer_(?:policy_)?rollout_kernel)(<[^>]*>)', name)
-      if m:
-        res[(m.group(1), m.group(2))] = (int(occ), int(lds))
+    kernel_build.check_scratch_lines(lines, otherwise=('no scratch at all',))
+    res = {k: (v['occupancy'], v['lds']) for k, v in unit.resources.items() if 'rollout_kernel<' in k}
     for inst in insts:
-      assert res[('sawyer_policy_rollout_kernel', inst)] == res[('sawyer_rollout_kernel', inst)], (unit, inst, res)
+      assert res['sawyer_policy_rollout_kernel' + inst] == res['sawyer_rollout_kernel' + inst], (unit_name, inst, res)

@@ -13,6 +13,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'earl_benchmark_amd', 'csrc')
+UNITS = ('physics.hip', 'physics_kitchen.hip', 'physics_kitchen_policy.hip', 'physics_mt.hip', 'physics_w8.hip', 'physics_l64.hip')
 FLAGS = '--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fPIC --cuda-device-only -S'.split()
 KERNELS = ('sawyer_rollout_kernel', 'sawyer_policy_rollout_kernel', 'kitchen_rollout_kernel', 'kitchen_policy_rollout_kernel', 'minitaur_kernel', 'minitaur_policy_kernel', 'minitaur_duo_kernel', 'physics_kernel')
 POLICY_DUO = ('minitaur_policy_duo_kernel',)      # report(..., kernels=KERNELS + POLICY_DUO) / --policy-duo
@@ -64,14 +65,21 @@ def report(unit, lines, kernels=KERNELS):
   return out
 
 
+def listing(assembly_of, kernels=KERNELS):
+  """the whole report, line by line: report() of every unit of UNITS in order, where assembly_of(unit) returns that unit's assembly lines"""
+  for unit in UNITS:
+    yield from report(unit, assembly_of(unit), kernels)
+
+
+def compile_to_assembly(unit):
+  with tempfile.NamedTemporaryFile(suffix='.s') as f:
+    subprocess.run(['/opt/rocm/bin/hipcc'] + FLAGS + ['-o', f.name, os.path.join(CSRC, unit)], check=True, stderr=subprocess.DEVNULL)
+    return open(f.name).read().split('\n')
+
+
 def main():
-  kernels = KERNELS + (POLICY_DUO if '--policy-duo' in sys.argv[1:] else ())
-  for unit in ('physics.hip', 'physics_kitchen.hip', 'physics_kitchen_policy.hip', 'physics_mt.hip', 'physics_w8.hip', 'physics_l64.hip'):
-    with tempfile.NamedTemporaryFile(suffix='.s') as f:
-      subprocess.run(['/opt/rocm/bin/hipcc'] + FLAGS + ['-o', f.name, os.path.join(CSRC, unit)], check=True, stderr=subprocess.DEVNULL)
-      lines = open(f.name).read().split('\n')
-    for ln in report(unit, lines, kernels):
-      print(ln)
+  for ln in listing(compile_to_assembly, KERNELS + (POLICY_DUO if '--policy-duo' in sys.argv[1:] else ())):
+    print(ln)
 
 
 if __name__ == '__main__':

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from .. import _abi
+from ..policy import PairPopulation, PolicyPopulation, require_widths
 from ..spaces import Box
 
 INT32_MAX = 2**31 - 1
@@ -308,44 +309,61 @@ class TabletopManipulation:
     eps from the env's Philox stream keyed by the global env id and the step's counter), sample=False evaluates the actor at its mean;
     return_noise=True appends eps [E,T,N,3], the standard-normal draws as used.  Both are for Gaussian policies only.
     A `PolicyPopulation` goes to earl_tabletop_population_rollout: the env with global id g runs member g // envs_per_policy, same returns."""
-    from ..policy import PolicyPopulation, require_widths
-    gaussian = require_widths(policy, 'rollout_policy', 12, 3, env=self)
-    population = isinstance(policy, PolicyPopulation)
+    gaussian = self._closed_loop_policy('rollout_policy', policy)
     if not gaussian and (return_noise or not sample):
       raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
-    if self.NOBJ != 1:
-      raise NotImplementedError('rollout_policy: single-object env only')
-    if reset_first:
-      E = 1 if episodes is None else int(episodes)
-      lead = (E, int(T), self.num_envs)
-    else:
-      if episodes not in (None, 1):
-        raise ValueError('rollout_policy: a continuing rollout (reset_first=False) is one episode')
-      E, lead = 1, (int(T), self.num_envs)
+    T = int(T)
+    E, lead = self._closed_loop_shape('rollout_policy', T, episodes, reset_first)
     with self._ctx():
-      if out is None:
-        outs, ostruct = self._new_out(lead)
-      else:
-        outs = tuple(out)
-        ostruct = self._out_struct(outs, lead)
-      actions = torch.empty(*lead, 3, dtype=torch.float32, device=self.device)
-      eps = torch.empty(*lead, 3, dtype=torch.float32, device=self.device) if return_noise else None
-      if population:
-        rc = self._population_launch(policy, gaussian, E, int(T), reset_first, ostruct, actions, eps, sample, None)
+      outs, ostruct, actions, eps = self._closed_loop_out(lead, out, return_noise)
+      if isinstance(policy, PolicyPopulation):
+        rc = self._population_launch(policy, gaussian, E, T, reset_first, ostruct, actions, eps, sample, None)
       elif gaussian:
         head = policy.head(sample=bool(sample), eps_out=eps)
-        rc = self._lib.earl_tabletop_policy_rollout_gaussian(self._cfg_ref, self._st_ref, C.byref(policy.struct), C.byref(head), E, int(T),
+        rc = self._lib.earl_tabletop_policy_rollout_gaussian(self._cfg_ref, self._st_ref, C.byref(policy.struct), C.byref(head), E, T,
                                                              int(bool(reset_first)), C.byref(ostruct), actions.data_ptr(), self._stream())
       else:
-        rc = self._lib.earl_tabletop_policy_rollout(self._cfg_ref, self._st_ref, C.byref(policy.struct), E, int(T), int(bool(reset_first)), C.byref(ostruct),
+        rc = self._lib.earl_tabletop_policy_rollout(self._cfg_ref, self._st_ref, C.byref(policy.struct), E, T, int(bool(reset_first)), C.byref(ostruct),
                                                     actions.data_ptr(), self._stream())
-    self._check(rc, 'policy_rollout')
-    self._cfg.counter += E * (int(T) + 1) if reset_first else int(T)
-    self.total_step_count += E * int(T)
-    self._last_success = outs[3][-1, -1] if reset_first else outs[3][-1]
+    self._closed_loop_done(rc, 'policy_rollout', E, T, reset_first, outs[3])
     if return_noise:
       return outs + (actions, eps)
     return outs + (actions,)
+
+  # what rollout_policy, evaluate_policy and rollout_agents share: the refusals, the launch shape, the allocations and the bookkeeping after the launch
+  def _closed_loop_policy(self, who, policy, pair=False):
+    """the refusals every closed-loop launch begins with -> is the policy Gaussian"""
+    gaussian = require_widths(policy, who, 12, 3, env=self, pair=pair)
+    if self.NOBJ != 1:
+      raise NotImplementedError(f'{who}: single-object env only')
+    return gaussian
+
+  def _closed_loop_shape(self, who, T, episodes, reset_first):
+    """-> (E, lead): `episodes` (default 1) episodes of reset() + T steps [E, T, N], or T continuing steps [T, N]"""
+    if reset_first:
+      E = 1 if episodes is None else int(episodes)
+      return E, (E, T, self.num_envs)
+    if episodes not in (None, 1):
+      raise ValueError(f'{who}: a continuing rollout (reset_first=False) is one episode')
+    return 1, (T, self.num_envs)
+
+  def _closed_loop_out(self, lead, out, return_noise):
+    """-> (outs, their struct, actions, eps or None): `out` as given by the caller, or fresh tensors"""
+    if out is None:
+      outs, ostruct = self._new_out(lead)
+    else:
+      outs = tuple(out)
+      ostruct = self._out_struct(outs, lead)
+    actions = torch.empty(*lead, 3, dtype=torch.float32, device=self.device)
+    eps = torch.empty(*lead, 3, dtype=torch.float32, device=self.device) if return_noise else None
+    return outs, ostruct, actions, eps
+
+  def _closed_loop_done(self, rc, what, E, T, reset_first, success):
+    """after the launch: its status, the Philox counter (every reset and every step took one), and the success flags of the last step"""
+    self._check(rc, what)
+    self._cfg.counter += E * (T + 1) if reset_first else T
+    self.total_step_count += E * T
+    self._last_success = success[(-1,) * (success.dim() - 1)]
 
   def _population_launch(self, policy, gaussian, E, T, reset_first, ostruct, actions, eps, sample, summary):
     """earl_tabletop_population_rollout for a PolicyPopulation (pop) or one policy (pop = NULL); -> the return code"""
@@ -362,12 +380,9 @@ class TabletopManipulation:
     -> {'ret': [E, N] float64 undiscounted return (the float32 step rewards summed in float64, t ascending), 'success': [E, N] bool success at the last step,
         'first_success': [E, N] int32 first successful step, -1 if none}; each equals its definition applied to what rollout_policy would have returned.
     Philox counter and total_step_count advance as in rollout_policy."""
-    from ..policy import require_widths
-    gaussian = require_widths(policy, 'evaluate_policy', 12, 3, env=self)
+    gaussian = self._closed_loop_policy('evaluate_policy', policy)
     if sample and not gaussian:
       raise ValueError('evaluate_policy: sample=True needs a Gaussian policy (an MLPPolicy is deterministic)')
-    if self.NOBJ != 1:
-      raise NotImplementedError('evaluate_policy: single-object env only')
     E, T, n = int(episodes), int(T), self.num_envs
     with self._ctx():
       ret = torch.empty(E, n, dtype=torch.float64, device=self.device)
@@ -375,10 +390,7 @@ class TabletopManipulation:
       first = torch.empty(E, n, dtype=torch.int32, device=self.device)
       summary = _abi.EpisodeSummary(ret=ret.data_ptr(), success_last=succ.data_ptr(), first_success=first.data_ptr())
       rc = self._population_launch(policy, gaussian, E, T, True, _abi.TabletopOut(None, None, None, None), None, None, sample, summary)
-    self._check(rc, 'population_rollout')
-    self._cfg.counter += E * (T + 1)
-    self.total_step_count += E * T
-    self._last_success = succ[-1]
+    self._closed_loop_done(rc, 'population_rollout', E, T, True, succ)
     return {'ret': ret, 'success': succ, 'first_success': first}
 
   def rollout_agents(self, pair, T, episodes=None, reset_first=False, sample=True, return_noise=False, out=None):
@@ -389,36 +401,22 @@ class TabletopManipulation:
     -> (obs [T,N,D], reward [T,N], done, success, actions [T,N,3], agent [T,N] int8 = the agent that computed the action) -- with a leading E axis when
     reset_first=True; return_noise=True (Gaussian agents) appends eps.  `env.pair_counts` = (forward phases, reset phases) [E, N] that ended by success in
     this launch.  The reset agent sees pair.backward_goal in its observation's goal slots; `goal_idx` keeps the env's task goal throughout."""
-    from ..policy import PairPopulation, require_widths
     if not isinstance(pair, PairPopulation) and (getattr(pair, 'backward_goals', None) is not None or (isinstance(getattr(pair, 'backward_goal', None), str) and pair.backward_goal == 'initial_states')):
       raise ValueError('rollout_agents: a table of backward goals runs on the Sawyer door and peg only (earl_sawyer_agents_rollout); the tabletop pair takes ONE row')
-    gaussian = require_widths(pair, 'rollout_agents', 12, 3, env=self, pair=True)
-    if self.NOBJ != 1:
-      raise NotImplementedError('rollout_agents: single-object env only')
+    gaussian = self._closed_loop_policy('rollout_agents', pair, pair=True)
     if self._cfg.goal_change_frequency > 0:
       raise ValueError('rollout_agents: the agent pair IS the lifelong mechanism (the forward handover makes the lifelong switch\'s goal draw): '
                        'not under a LifelongWrapper, whose clock would fight the pair\'s over the same draw')
     if not gaussian and (return_noise or not sample):
       raise ValueError('rollout_agents: sample=False / return_noise=True need Gaussian agents (MLPPolicy agents are deterministic)')
-    if reset_first:
-      E = 1 if episodes is None else int(episodes)
-      lead = (E, int(T), self.num_envs)
-    else:
-      if episodes not in (None, 1):
-        raise ValueError('rollout_agents: a continuing rollout (reset_first=False) is one episode')
-      E, lead = 1, (int(T), self.num_envs)
+    T = int(T)
+    E, lead = self._closed_loop_shape('rollout_agents', T, episodes, reset_first)
     with self._ctx():
       if self.agent_phase is None:
         self.agent_phase = torch.zeros(self.num_envs, dtype=torch.int8, device=self.device)
         self.steps_in_phase = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
-      if out is None:
-        outs, ostruct = self._new_out(lead)
-      else:
-        outs = tuple(out)
-        ostruct = self._out_struct(outs, lead)
-      actions = torch.empty(*lead, 3, dtype=torch.float32, device=self.device)
+      outs, ostruct, actions, eps = self._closed_loop_out(lead, out, return_noise)
       agent = torch.empty(*lead, dtype=torch.int8, device=self.device)
-      eps = torch.empty(*lead, 3, dtype=torch.float32, device=self.device) if return_noise else None
       fwd = torch.empty(E, self.num_envs, dtype=torch.int32, device=self.device)
       bwd = torch.empty(E, self.num_envs, dtype=torch.int32, device=self.device)
       goal = pair.goal_row(self)
@@ -426,12 +424,9 @@ class TabletopManipulation:
                           backward_goal=_ptr(goal), phase=self.agent_phase.data_ptr(), steps_in_phase=self.steps_in_phase.data_ptr(),
                           agent_out=agent.data_ptr(), forward_success=fwd.data_ptr(), backward_success=bwd.data_ptr())
       head = pair.head(sample=bool(sample), eps_out=eps) if gaussian else None
-      rc = self._lib.earl_tabletop_pair_rollout(self._cfg_ref, self._st_ref, C.byref(pair.struct), C.byref(ps), None if head is None else C.byref(head), E, int(T),
+      rc = self._lib.earl_tabletop_pair_rollout(self._cfg_ref, self._st_ref, C.byref(pair.struct), C.byref(ps), None if head is None else C.byref(head), E, T,
                                                 int(bool(reset_first)), C.byref(ostruct), actions.data_ptr(), self._stream())
-    self._check(rc, 'pair_rollout')
-    self._cfg.counter += E * (int(T) + 1) if reset_first else int(T)
-    self.total_step_count += E * int(T)
-    self._last_success = outs[3][-1, -1] if reset_first else outs[3][-1]
+    self._closed_loop_done(rc, 'pair_rollout', E, T, reset_first, outs[3])
     self._pair_counts = (fwd, bwd)
     if return_noise:
       return outs + (actions, agent, eps)

@@ -66,6 +66,8 @@ agent's goal is drawn from at every handover, a `PairPopulation` of P pairs in o
   out = peg.rollout_agents(pair, T=1000)                                                              # ... plus 'backward_row' [T, N] int32: the row drawn, -1 elsewhere
   pairs = PairPopulation([pair_0, ..., pair_511], envs_per_policy=16, device='cuda')                  # .params [P, 2, stride], written in place
   s = peg.evaluate_agents(pairs, T=1000)                                                              # {'ret', 'success', 'first_success', 'guard_steps', 'forward_success', 'backward_success'}: [N]"""
+import operator
+
 import numpy as np
 import torch
 
@@ -88,17 +90,74 @@ def _piece(dtype, tabletop=False):
   return 8 if dtype == torch.bfloat16 else (1 if tabletop else 4)
 
 
-def _unpack(row, dims):
-  """one packed row (W0, b0, W1, b1, ...) -> [(W [n, k], b [n])] as views of it"""
+def _padded(host, piece):
+  """rows [..., n] -> rows of whole `piece`s, zero-filled"""
+  return torch.nn.functional.pad(host, (0, -host.shape[-1] % piece)) if host.shape[-1] % piece else host
+
+
+def _unpack(rows, dims):
+  """packed rows [..., stride] (W0, b0, W1, b1, ...) -> [(W [..., n, k], b [..., n])] as views of them"""
   layers, at = [], 0
   for k, n in zip(dims[:-1], dims[1:]):
-    layers.append((row[at:at + n * k].reshape(n, k), row[at + n * k:at + n * k + n]))
+    layers.append((rows[..., at:at + n * k].reshape(*rows.shape[:-1], n, k), rows[..., at + n * k:at + n * k + n]))
     at += n * k + n
   return layers
 
 
-def _like(t, layers, device, param_dtype, obs_dim, act_dim):
-  """a policy of `t`'s class, activations and head over `layers`"""
+def _forward(obs, layers, hidden_act, act_dim):
+  """the network as torch ops: obs [..., obs_dim] -> (the first act_dim outputs, every output) before the output activation"""
+  x = obs.to(torch.float32)
+  for l, (w, b) in enumerate(layers):
+    x = torch.addmm(b, x.reshape(-1, x.shape[-1]), w.t()).reshape(*x.shape[:-1], w.shape[0])
+    if l + 1 < len(layers):
+      x = torch.relu(x) if hidden_act == 'relu' else torch.tanh(x)
+  return x[..., :act_dim], x
+
+
+def _require_shared(who, members, attrs, clause):
+  """every member's `attrs` ('a', or 'template.a': shown as 'a') equal member 0's"""
+  for p, m in enumerate(members):
+    for what in attrs:
+      get = operator.attrgetter(what)
+      if get(m) != get(members[0]):
+        raise ValueError(f'{who}: member {p} has {what.rpartition(".")[2].strip("_")} = {get(m)!r}, member 0 has {get(members[0])!r} ({clause})')
+
+
+class _PackedMLP:
+  """What the four containers share: the architecture's scalars, `.params` on a device and struct earl_mlp_policy over it."""
+  SHARED = ('__class__', 'dims', 'hidden_act', 'out_act', 'param_dtype')      # what the members of a container have in common, and for a Gaussian head:
+  SHARED_HEAD = ('squash', 'log_std_bounds', 'log_std_map')
+
+  def _describe(self, dims, hidden_act, out_act, gaussian, param_dtype):
+    self.dims, self.hidden_act, self.out_act, self.gaussian, self.param_dtype = list(dims), hidden_act, out_act, gaussian, param_dtype
+    self.macs = sum(k * n for k, n in zip(dims[:-1], dims[1:]))          # multiply-adds per env step
+    self.n_params = sum(n * (k + 1) for k, n in zip(dims[:-1], dims[1:]))
+
+  def _describe_like(self, t):
+    self._describe(t.dims, t.hidden_act, t.out_act, t.gaussian, t.param_dtype)
+
+  def to(self, device):
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+      dev = torch.device('cuda', torch.cuda.current_device())
+    self.device = dev
+    self._place()
+    dims = self.dims + [0] * (4 - len(self.dims))
+    self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
+                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=PARAM_DTYPES[self.param_dtype], params=self.params.data_ptr())
+    return self
+
+  def _place(self):
+    """(to's hook) `.params` onto `.device`, and what a container keeps next to it"""
+    self.params = self.params.to(self.device).contiguous()
+
+  def _population(self):
+    return _abi.PolicyPopulation(n_policies=self.n_policies, envs_per_policy=self.envs_per_policy, param_stride=self.stride)
+
+
+def _like(t, row, device, param_dtype, obs_dim, act_dim):
+  """a policy of `t`'s class, architecture and head over a copy of the packed `row`"""
+  layers = [(w.clone(), b.clone()) for w, b in _unpack(row.detach().to('cpu', torch.float32), t.dims)]
   if isinstance(t, GaussianMLPPolicy):
     return GaussianMLPPolicy(layers, t.hidden_act, squash=t.squash, log_std_bounds=t.log_std_bounds, log_std_map=t.log_std_map, device=device, obs_dim=obs_dim,
                              act_dim=act_dim, param_dtype=param_dtype)
@@ -127,7 +186,7 @@ def _layers_of_sequential(seq):
   return layers, hidden.pop(), acts[-1]
 
 
-class MLPPolicy:
+class MLPPolicy(_PackedMLP):
   OUT_DIM, OUT_WHAT = ACT_DIM, 'action'
 
   def __init__(self, layers, hidden_act='relu', out_act='tanh', device='cpu', obs_dim=OBS_DIM, act_dim=ACT_DIM, param_dtype=torch.float32):
@@ -137,7 +196,7 @@ class MLPPolicy:
     `.layers` hold the widened float32 values, so pi(obs), pi.sample and make_step_graph(T, policy=pi) evaluate the network the kernel evaluates: bf16 is a storage
     format, the arithmetic is float32 on the widened values, and a launch returns the bits of the float32 launch of pi.widened()."""
     name = type(self).__name__                                        # (MLPPolicy's own messages read as they always did)
-    self.param_dtype = _param_dtype(name, param_dtype)
+    param_dtype = _param_dtype(name, param_dtype)
     self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
     if self.obs_dim < 1 or self.act_dim < 1:
       raise ValueError(f'{name}: obs_dim = {obs_dim}, act_dim = {act_dim}: both >= 1')
@@ -165,41 +224,27 @@ class MLPPolicy:
     for h in dims[1:-1]:
       if h < MIN_WIDTH or h > MAX_WIDTH or h % 16:
         raise ValueError(f'{name}: hidden width {h}: a multiple of 16 in {MIN_WIDTH}..{MAX_WIDTH}')
-    self.dims, self.hidden_act, self.out_act = dims, hidden_act, out_act or 'none'
-    if self.param_dtype != torch.float32:                             # rounded once; from here on the float32 values ARE the stored ones, widened
-      layers = [(w.to(self.param_dtype).to(torch.float32), b.to(self.param_dtype).to(torch.float32)) for w, b in layers]
+    self._describe(dims, hidden_act, out_act or 'none', isinstance(self, GaussianMLPPolicy), param_dtype)
+    if param_dtype != torch.float32:                                  # rounded once; from here on the float32 values ARE the stored ones, widened
+      layers = [(w.to(param_dtype).to(torch.float32), b.to(param_dtype).to(torch.float32)) for w, b in layers]
     self._host_layers = layers
-    self.macs = sum(a * b for a, b in zip(dims[:-1], dims[1:]))       # multiply-adds per env step
     self.to(device)
 
-  def to(self, device):
-    dev = torch.device(device)
-    if dev.type == 'cuda' and dev.index is None:
-      dev = torch.device('cuda', torch.cuda.current_device())
-    self.device = dev
-    self.layers = [(w.to(dev).contiguous(), b.to(dev).contiguous()) for w, b in self._host_layers]
+  def _place(self):
+    self.layers = [(w.to(self.device).contiguous(), b.to(self.device).contiguous()) for w, b in self._host_layers]
     self.params = torch.cat([t.reshape(-1) for wb in self.layers for t in wb]).to(self.param_dtype).contiguous()      # W0, b0, W1, b1, ...  (bf16: exact, the values are widened bf16)
-    dims = self.dims + [0] * (4 - len(self.dims))
-    self.struct = _abi.MlpPolicy(n_layers=len(self.layers), dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
-                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=PARAM_DTYPES[self.param_dtype], params=self.params.data_ptr())
-    return self
 
   def with_param_dtype(self, dtype):
     """the policy of the values that stand in `.params` now, stored as `dtype` (torch.float32 | torch.bfloat16: rounded once), on the same device"""
-    layers = [(w.clone(), b.clone()) for w, b in _unpack(self.params.detach().to('cpu', torch.float32), self.dims)]
-    return _like(self, layers, self.device, _param_dtype(type(self).__name__, dtype), self.obs_dim, self.act_dim)
+    return _like(self, self.params, self.device, _param_dtype(type(self).__name__, dtype), self.obs_dim, self.act_dim)
 
   def widened(self):
     """the float32 policy with exactly the stored values: the network a launch with this policy evaluates, bit for bit (and what the tabletop takes)"""
     return self.with_param_dtype(torch.float32)
 
   def __call__(self, obs):
-    x = obs.to(torch.float32)
-    for l, (w, b) in enumerate(self.layers):
-      x = torch.addmm(b, x, w.t())
-      kind = self.hidden_act if l + 1 < len(self.layers) else self.out_act
-      x = torch.relu(x) if kind == 'relu' else torch.tanh(x) if kind == 'tanh' else x
-    return x
+    x, _ = _forward(obs, self.layers, self.hidden_act, self.act_dim)
+    return torch.tanh(x) if self.out_act == 'tanh' else x
 
 
 class GaussianMLPPolicy(MLPPolicy):
@@ -231,12 +276,8 @@ class GaussianMLPPolicy(MLPPolicy):
                              eps_out=None if eps_out is None else eps_out.data_ptr())
 
   def _mean_and_log_std(self, obs):
-    x = obs.to(torch.float32)
-    for l, (w, b) in enumerate(self.layers):
-      x = torch.addmm(b, x.reshape(-1, x.shape[-1]), w.t()).reshape(*x.shape[:-1], w.shape[0])
-      if l + 1 < len(self.layers):
-        x = torch.relu(x) if self.hidden_act == 'relu' else torch.tanh(x)
-    mean, raw = x[..., :self.act_dim], x[..., self.act_dim:]
+    mean, x = _forward(obs, self.layers, self.hidden_act, self.act_dim)
+    raw = x[..., self.act_dim:]
     lo, hi = self.log_std_bounds
     log_std = lo + 0.5 * (hi - lo) * (torch.tanh(raw) + 1.0) if self.log_std_map == 'tanh' else torch.clamp(raw, lo, hi)
     return mean, log_std
@@ -291,7 +332,7 @@ def require_widths(policy, who, obs_dim, act_dim, env=None, pair=False, bounded=
   return gaussian
 
 
-class PolicyPopulation:
+class PolicyPopulation(_PackedMLP):
   """P members of one architecture behind struct earl_policy_population: `policies` is a list of MLPPolicy or of GaussianMLPPolicy (same dims, activations and,
   for the Gaussian head, squash / bounds / map -- only the parameters differ), or ONE template policy with `params` [P, n_params] (n_params <= the row length:
   a wider row is the stride).  The env with GLOBAL id g runs member g // envs_per_policy (a multiple of 16: a member owns whole 16-env workgroups of the kernel).
@@ -318,15 +359,9 @@ class PolicyPopulation:
       template = members[0]
       for m in members:
         require_widths(m, 'PolicyPopulation', self.obs_dim, self.act_dim)
-      for p, m in enumerate(members):
-        for what in ('__class__', 'dims', 'hidden_act', 'out_act', 'param_dtype') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
-          if getattr(m, what) != getattr(template, what):
-            raise ValueError(f'PolicyPopulation: member {p} has {what.strip("_")} = {getattr(m, what)!r}, member 0 has {getattr(template, what)!r} '
-                             '(the members of a population share one architecture)')
-    self.template, self.envs_per_policy, self.param_dtype = template, G, template.param_dtype
-    self.gaussian = isinstance(template, GaussianMLPPolicy)
-    self.dims, self.hidden_act, self.out_act, self.macs = list(template.dims), template.hidden_act, template.out_act, template.macs
-    self.n_params = sum(n * (k + 1) for k, n in zip(self.dims[:-1], self.dims[1:]))
+      _require_shared('PolicyPopulation', members, self.SHARED + (self.SHARED_HEAD if template.gaussian else ()), 'the members of a population share one architecture')
+    self.template, self.envs_per_policy = template, G
+    self._describe_like(template)
     if members is not None:
       host = torch.stack([m.params.detach().to('cpu', self.param_dtype) for m in members])
     else:
@@ -339,26 +374,16 @@ class PolicyPopulation:
         raise ValueError(f'PolicyPopulation: params {tuple(host.shape)}: [P, >= {self.n_params}] (one row per member, packed like MLPPolicy.params)')
     self.n_policies = int(host.shape[0])
     piece = _piece(self.param_dtype, (self.obs_dim, self.act_dim) == (OBS_DIM, ACT_DIM))      # (the stepper kernels read every member's rows in 16-byte pieces)
-    if host.shape[1] % piece:
-      host = torch.nn.functional.pad(host, (0, -host.shape[1] % piece))
-    self.params = host.clone().contiguous()
+    self.params = _padded(host, piece).clone().contiguous()
     self.to(template.device if device is None else device)
 
   @property
   def stride(self):
     return int(self.params.shape[1])
 
-  def to(self, device):
-    dev = torch.device(device)
-    if dev.type == 'cuda' and dev.index is None:
-      dev = torch.device('cuda', torch.cuda.current_device())
-    self.device = dev
-    self.params = self.params.to(dev).contiguous()
-    dims = self.dims + [0] * (4 - len(self.dims))
-    self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
-                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=PARAM_DTYPES[self.param_dtype], params=self.params.data_ptr())
-    self.pop_struct = _abi.PolicyPopulation(n_policies=self.n_policies, envs_per_policy=self.envs_per_policy, param_stride=self.stride)
-    return self
+  def _place(self):
+    super()._place()
+    self.pop_struct = self._population()
 
   def widened(self):
     """the float32 population of exactly the stored values (MLPPolicy.widened)"""
@@ -368,20 +393,9 @@ class PolicyPopulation:
   def head(self, sample=True, eps_out=None):
     return self.template.head(sample=sample, eps_out=eps_out)
 
-  def _layers_of(self, rows):
-    """rows [..., stride] -> [(W [..., out, in], b [..., out]), ...] views in the packing order"""
-    layers, at = [], 0
-    for k, n in zip(self.dims[:-1], self.dims[1:]):
-      w = rows[..., at:at + n * k].reshape(*rows.shape[:-1], n, k)
-      b = rows[..., at + n * k:at + n * k + n]
-      layers.append((w, b))
-      at += n * k + n
-    return layers
-
   def member(self, p):
     """member p as a policy of its own (a copy of its row of .params, stored in the population's param_dtype)"""
-    layers = [(w.clone(), b.clone()) for w, b in self._layers_of(self.params[int(p)].detach().to('cpu', torch.float32))]
-    return _like(self.template, layers, self.device, self.param_dtype, self.obs_dim, self.act_dim)
+    return _like(self.template, self.params[int(p)], self.device, self.param_dtype, self.obs_dim, self.act_dim)
 
   def policy_index(self, global_ids):
     """the member each GLOBAL env id runs"""
@@ -403,7 +417,7 @@ class PolicyPopulation:
     grid = x.new_zeros(L, M * G, x.shape[-1])
     grid[:, slot] = x
     h = grid.reshape(L, M, G, -1).permute(1, 0, 2, 3).reshape(M, L * G, -1)
-    layers = self._layers_of(self.params[m0:m1 + 1].to(x.device, torch.float32))      # (bf16 rows: widened first)
+    layers = _unpack(self.params[m0:m1 + 1].to(x.device, torch.float32), self.dims)     # (bf16 rows: widened first)
     for l, (w, b) in enumerate(layers):
       h = torch.baddbmm(b[:, None, :], h, w.transpose(1, 2))
       if l + 1 < len(layers):
@@ -416,7 +430,7 @@ class PolicyPopulation:
     return out.reshape(*lead, N, A)
 
 
-class AgentPair:
+class AgentPair(_PackedMLP):
   """The forward and the reset (backward) agent behind struct earl_agent_pair: both `MLPPolicy`, or both `GaussianMLPPolicy`, of one architecture (dims, activations
   and, for the Gaussian head, squash / bounds / map -- only the parameters differ).  `.params` [2, stride] float32 holds row 0 = forward, row 1 = reset in MLPPolicy's
   packing order and is what the kernel reads: write into it in place.  switch_every: steps after which the acting agent hands over, one int for both or (forward,
@@ -441,11 +455,7 @@ class AgentPair:
     for m in members:
       require_widths(m, 'AgentPair', self.obs_dim, self.act_dim)
     template = forward
-    for p, m in enumerate(members):
-      for what in ('__class__', 'dims', 'hidden_act', 'out_act', 'param_dtype') + (('squash', 'log_std_bounds', 'log_std_map') if isinstance(template, GaussianMLPPolicy) else ()):
-        if getattr(m, what) != getattr(template, what):
-          raise ValueError(f'AgentPair: member {p} has {what.strip("_")} = {getattr(m, what)!r}, member 0 has {getattr(template, what)!r} '
-                           '(the two agents of a pair share one architecture)')
+    _require_shared('AgentPair', members, self.SHARED + (self.SHARED_HEAD if template.gaussian else ()), 'the two agents of a pair share one architecture')
     if tabletop and len(template.dims) == 4 and template.dims[2] > _abi.PAIR_MAX_H2:
       raise ValueError(f'AgentPair: second hidden width {template.dims[2]} > {_abi.PAIR_MAX_H2} (EARL_PAIR_MAX_H2: two weight sets share one wave\'s registers)')
     se = (switch_every, switch_every) if np.ndim(switch_every) == 0 else tuple(switch_every)
@@ -467,14 +477,10 @@ class AgentPair:
       if g.numel() != self.goal_dim:
         raise ValueError(f"AgentPair: backward_goal is 'initial', None or ONE goal row of {self.goal_dim} values, got {g.numel()}")
       self.backward_goal = g.clone()
-    self.template, self.gaussian, self.param_dtype = template, isinstance(template, GaussianMLPPolicy), template.param_dtype
-    self.dims, self.hidden_act, self.out_act, self.macs = list(template.dims), template.hidden_act, template.out_act, template.macs
-    self.n_params = sum(n * (k + 1) for k, n in zip(self.dims[:-1], self.dims[1:]))
+    self.template = template
+    self._describe_like(template)
     host = torch.stack([m.params.detach().to('cpu', self.param_dtype) for m in members])
-    piece = _piece(self.param_dtype, tabletop)           # (the stepper kernels read both agents' rows in 16-byte pieces)
-    if host.shape[1] % piece:
-      host = torch.nn.functional.pad(host, (0, -host.shape[1] % piece))
-    self.params = host.contiguous()
+    self.params = _padded(host, _piece(self.param_dtype, tabletop)).contiguous()      # (the stepper kernels read both agents' rows in 16-byte pieces)
     self.to(template.device if device is None else device)
 
   @property
@@ -483,20 +489,13 @@ class AgentPair:
 
   pair_stride = stride                                               # (floats between the two agents' rows: PairPopulation's name for it)
 
-  def to(self, device):
-    dev = torch.device(device)
-    if dev.type == 'cuda' and dev.index is None:
-      dev = torch.device('cuda', torch.cuda.current_device())
-    self.device = dev
-    self.params = self.params.to(dev).contiguous()
+  def _place(self):
+    super()._place()
+    dev = self.device
     self._goal_dev = None if not torch.is_tensor(self.backward_goal) else self.backward_goal.to(dev).contiguous()
     self._initial_dev = None                                         # ('initial' as numpy, its row on `dev`), filled by goal_row
     self._goals_dev = None if self.backward_goals is None else self.backward_goals.to(dev).contiguous()
     self._initial_states_dev = None                                  # ('initial_states' as numpy, its rows on `dev`), filled by goal_table
-    dims = self.dims + [0] * (4 - len(self.dims))
-    self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
-                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=PARAM_DTYPES[self.param_dtype], params=self.params.data_ptr())
-    return self
 
   def with_param_dtype(self, dtype):
     """the pair of the values that stand in `.params` now, its agents stored as `dtype` (MLPPolicy.with_param_dtype)"""
@@ -544,18 +543,9 @@ class AgentPair:
       self._initial_dev = (init.copy(), torch.as_tensor(init, device=self.device).contiguous())
     return self._initial_dev[1]
 
-  def _layers_of(self, row):
-    """one row of .params -> [(W [n, k], b [n])] as views of it, in MLPPolicy's packing order"""
-    layers, at = [], 0
-    for k, n in zip(self.dims[:-1], self.dims[1:]):
-      layers.append((row[at:at + n * k].reshape(n, k), row[at + n * k:at + n * k + n]))
-      at += n * k + n
-    return layers
-
   def agent(self, k):
     """agent k (0 forward, 1 reset) as a policy of its own (a copy of its row of .params, stored in the pair's param_dtype)"""
-    layers = [(w.clone(), b.clone()) for w, b in self._layers_of(self.params[int(k)].detach().to('cpu', torch.float32))]
-    return _like(self.template, layers, self.device, self.param_dtype, self.obs_dim, self.act_dim)
+    return _like(self.template, self.params[int(k)], self.device, self.param_dtype, self.obs_dim, self.act_dim)
 
   def __call__(self, obs, phase):
     """obs [..., N, obs_dim], phase [N] or [..., N] (0 forward, 1 reset) -> actions [..., N, act_dim] (Gaussian agents: at the mean): torch's statement -- close to the kernel,
@@ -563,25 +553,18 @@ class AgentPair:
     ph = torch.as_tensor(phase, device=obs.device).bool()
     acts = []
     for row in self.params.detach().to(obs.device, torch.float32):   # the layers are views of .params: no copy, and in-place updates are seen (bf16 rows: widened first)
-      x = obs.to(torch.float32).reshape(-1, obs.shape[-1])
-      layers = self._layers_of(row)
-      for l, (w, b) in enumerate(layers):
-        x = torch.addmm(b, x, w.t())
-        if l + 1 < len(layers):
-          x = torch.relu(x) if self.hidden_act == 'relu' else torch.tanh(x)
-      x = x[:, :self.act_dim]                                        # (Gaussian agents: the mean)
+      x, _ = _forward(obs.to(torch.float32).reshape(-1, obs.shape[-1]), _unpack(row, self.dims), self.hidden_act, self.act_dim)      # (Gaussian agents: the mean)
       acts.append((torch.tanh(x) if self.out_act == 'tanh' else x).reshape(*obs.shape[:-1], self.act_dim))
     return torch.where(ph[..., None], acts[1], acts[0])
 
 
-class PairPopulation:
+class PairPopulation(_PackedMLP):
   """P forward / reset pairs of ONE architecture, head, switch rule and backward goal behind struct earl_policy_population next to struct earl_agent_pair
   (earl_sawyer_agents_rollout, earl_minitaur_agents_rollout, earl_kitchen_agents_rollout): `pairs` is a list of `AgentPair` of one env's widths (obs_dim=14,
   act_dim=4 on the Sawyer door and peg; 32 / 8 on the minitaur; 46 / 9 on the kitchen) -- only the parameters differ.  The env with GLOBAL id g runs pair
   g // envs_per_policy (a multiple of 16).  `.params` [P, 2, stride] float32 holds every pair's rows (0 forward, 1 reset) in MLPPolicy's packing order and is what the
   kernel reads: write into it in place."""
   SHARED = ('gaussian', 'dims', 'hidden_act', 'out_act', 'param_dtype', 'switch_every', 'switch_on_success')
-  SHARED_HEAD = ('squash', 'log_std_bounds', 'log_std_map')
 
   def __init__(self, pairs, envs_per_policy=16, device=None):
     G = int(envs_per_policy)
@@ -595,22 +578,15 @@ class PairPopulation:
     widths = (t.obs_dim, t.act_dim) if (t.obs_dim, t.act_dim) in PAIR_POPULATION_WIDTHS else (14, 4)
     for m in members:
       require_widths(m, 'PairPopulation', *widths)
+    clause = 'the pairs of a population share one architecture, head, switch rule and backward goal'
+    _require_shared('PairPopulation', members, self.SHARED + (tuple('template.' + a for a in self.SHARED_HEAD) if t.gaussian else ()), clause)
     for p, m in enumerate(members):
-      for what in self.SHARED:
-        if getattr(m, what) != getattr(t, what):
-          raise ValueError(f'PairPopulation: member {p} has {what} = {getattr(m, what)!r}, member 0 has {getattr(t, what)!r} '
-                           '(the pairs of a population share one architecture, head, switch rule and backward goal)')
-      for what in self.SHARED_HEAD if t.gaussian else ():
-        if getattr(m.template, what) != getattr(t.template, what):
-          raise ValueError(f'PairPopulation: member {p} has {what} = {getattr(m.template, what)!r}, member 0 has {getattr(t.template, what)!r} '
-                           '(the pairs of a population share one architecture, head, switch rule and backward goal)')
       if not self._same_goal(m, t):
         shown = lambda a: a.backward_goals if a.backward_goals is not None else a.backward_goal
-        raise ValueError(f'PairPopulation: member {p} has backward_goal = {shown(m)!r}, member 0 has {shown(t)!r} '
-                         '(the pairs of a population share one architecture, head, switch rule and backward goal)')
+        raise ValueError(f'PairPopulation: member {p} has backward_goal = {shown(m)!r}, member 0 has {shown(t)!r} ({clause})')
     self.envs_per_policy, self.n_policies = G, len(members)
-    self.gaussian, self.dims, self.hidden_act, self.out_act, self.macs, self.n_params = t.gaussian, list(t.dims), t.hidden_act, t.out_act, t.macs, t.n_params
-    self.switch_every, self.switch_on_success, self.param_dtype = t.switch_every, t.switch_on_success, t.param_dtype
+    self._describe_like(t)
+    self.switch_every, self.switch_on_success = t.switch_every, t.switch_on_success
     self.backward_goal, self.backward_goals = t.backward_goal, t.backward_goals
     self._head_of = t.template                                        # (a policy of the members' head: only its head settings are used)
     self.params = torch.stack([m.params.detach().to('cpu', self.param_dtype) for m in members]).contiguous()      # [P, 2, stride]
@@ -637,18 +613,10 @@ class PairPopulation:
     """floats between two pairs"""
     return 2 * self.pair_stride
 
-  def to(self, device):
-    dev = torch.device(device)
-    if dev.type == 'cuda' and dev.index is None:
-      dev = torch.device('cuda', torch.cuda.current_device())
-    self.device = dev
-    self.params = self.params.to(dev).contiguous()
-    dims = self.dims + [0] * (4 - len(self.dims))
-    self.struct = _abi.MlpPolicy(n_layers=len(self.dims) - 1, dims=(_abi.C.c_int32 * 4)(*dims), hidden_act=_abi.ACTIVATIONS[self.hidden_act],
-                                 out_act=_abi.ACTIVATIONS[self.out_act], precision=PARAM_DTYPES[self.param_dtype], params=self.params.data_ptr())
-    self.pop_struct = _abi.PolicyPopulation(n_policies=self.n_policies, envs_per_policy=self.envs_per_policy, param_stride=self.stride)
-    self._goals = self.pair(0)                                         # resolves and caches the backward goal on `dev` (goal_row / goal_table)
-    return self
+  def _place(self):
+    super()._place()
+    self.pop_struct = self._population()
+    self._goals = self.pair(0)                                         # resolves and caches the backward goal on the device (goal_row / goal_table)
 
   def head(self, sample=True, eps_out=None):
     return self._head_of.head(sample=sample, eps_out=eps_out)
@@ -661,8 +629,7 @@ class PairPopulation:
 
   def pair(self, p):
     """pair p as an AgentPair of its own (a copy of its rows of .params)"""
-    rows = self.params[int(p)].detach().to('cpu', torch.float32)
-    agents = [_like(self._head_of, [(w.clone(), b.clone()) for w, b in _unpack(row, self.dims)], 'cpu', self.param_dtype, self.obs_dim, self.act_dim) for row in rows]
+    agents = [_like(self._head_of, row, 'cpu', self.param_dtype, self.obs_dim, self.act_dim) for row in self.params[int(p)]]
     goal = self.backward_goals if self.backward_goals is not None else self.backward_goal
     return AgentPair(agents[0], agents[1], switch_every=self.switch_every, switch_on_success=self.switch_on_success, backward_goal=goal, device=self.device,
                      obs_dim=self.obs_dim, act_dim=self.act_dim)

@@ -104,11 +104,12 @@ __device__ __forceinline__ void move(Env<NOBJ>& e, double a0, double a1, double 
     }
   } else {
 #pragma unroll
-    for (int k = 0; k < NOBJ; ++k)  // static indexing keeps q[] in registers
-      if (e.attached == k) {
-        e.q[2 + 2 * k] = clipd(e.q[2 + 2 * k] + ddx, -2.8, 2.8);
-        e.q[3 + 2 * k] = clipd(e.q[3 + 2 * k] + ddy, -2.8, 2.8);
-      }
+    for (int k = 0; k < NOBJ; ++k) {  // a select per object, not a branch: the compiler folds the branches into ONE update at q[2 + 2 attached], and the
+      const bool held = e.attached == k;  // dynamic index puts q[] into scratch (56 bytes per lane in every NOBJ = 3 kernel); the selects keep it in registers
+      const double nx = clipd(e.q[2 + 2 * k] + ddx, -2.8, 2.8), ny = clipd(e.q[3 + 2 * k] + ddy, -2.8, 2.8);
+      e.q[2 + 2 * k] = held ? nx : e.q[2 + 2 * k];
+      e.q[3 + 2 * k] = held ? ny : e.q[3 + 2 * k];
+    }
   }
   e.q[0] = nfx;
   e.q[1] = nfy;

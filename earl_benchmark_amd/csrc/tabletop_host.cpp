@@ -209,6 +209,21 @@ int earl_tabletop3_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop
 int earl_tabletop3_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, float* obs) {
   return do_reset<3>(cfg, st, mask, nullptr, obs);
 }
+// host twin of earl_tabletop3_policy_rollout: the single-object loops (tabletop_policy.h) on Lane<3> and the 20-wide observation
+int earl_tabletop3_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_policy_population* pop,
+                                      const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out,
+                                      const earl_episode_summary* summary) {
+  if (int rc = check_population(cfg, st, policy, pop, head, episodes, T, reset_first, out, 3)) return rc;
+  if (cfg->n == 0) return EARL_OK;
+  const PopulationArgs a = population_args(cfg, st, policy, pop, head, episodes, T, reset_first, out, act_out, summary, thresholds());
+  const bool general = cfg->auto_reset != 0;
+  for_each_env(cfg->n, [&](int i) {
+    const float* params = a.p.params + population_param_offset(a.pop, a.k.cfg.env_offset + i);
+    if (head) general ? gaussian_rollout_env<true, 3>(a, i, params, &a.sum) : gaussian_rollout_env<false, 3>(a, i, params, &a.sum);
+    else general ? policy_rollout_env<true, 3>(a, i, params, &a.sum) : policy_rollout_env<false, 3>(a, i, params, &a.sum);
+  });
+  return EARL_OK;
+}
 int earl_tabletop3_reward_cpu(int32_t n, const float* obs, int32_t reward_type, float* reward, uint8_t* success) {
   if (n < 0 || !obs) return fail(EARL_ERR_ARG, "bad n/obs");
   if (reward_type != EARL_REWARD_SPARSE && reward_type != EARL_REWARD_DENSE) return fail(EARL_ERR_ARG, "reward_type = %d", reward_type);

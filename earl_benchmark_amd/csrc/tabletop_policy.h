@@ -4,7 +4,9 @@
 // Gaussian head (12 -> hidden (-> hidden) -> 6, actions sampled inside the launch: earl_tabletop_policy_rollout_gaussian) is instantiated in
 // tabletop_policy_gaussian.hip; its sampling contract follows the deterministic one below.  Both heads for a POPULATION of policies (every 16-env workgroup its own
 // member's parameters) with per-episode summaries (earl_tabletop_population_rollout) are instantiated in tabletop_policy_population.hip; the kernel body the
-// three units share is tabletop_policy_kernel.inc.
+// three units share is tabletop_policy_kernel.inc.  The THREE-object env's closed loop (20 -> hidden (-> hidden) -> 3 or 6, one policy or a population, summaries:
+// earl_tabletop3_policy_rollout) is the same body with NOBJ = 3, instantiated in tabletop3_policy.hip; the env's side below (policy_episode_begin, policy_env_step) and the host
+// twin's loops take the object count as a template argument.
 //
 // The policy arithmetic is a contract, stated here once for both builds:
 //   pre-activation   acc = b_j;  for k = 0 .. K-1 ascending:  acc = fmaf(x_k, W_jk, acc)     (float32, one rounding per fused multiply-add)
@@ -72,13 +74,13 @@ __host__ __device__ __forceinline__ void episode_sum_store(const earl_episode_su
 namespace hostside {
 
 // the deterministic entry point (h == NULL: a 3-wide last layer) or the Gaussian head's (6-wide, then the head's rules): the env's checks, the policy's
-// (policy_check.h), the launch's own
+// (policy_check.h), the launch's own.  nobj = 3: the three-object env's (earl_tabletop3_policy_rollout), 20 observations wide
 inline int check_policy(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_gaussian_head* h, int32_t episodes, int32_t T,
-                        int32_t reset_first, const earl_tabletop_out* out) {
+                        int32_t reset_first, const earl_tabletop_out* out, int nobj = 1) {
   static_assert(sizeof g_err >= contract::kErrLen, "policy_check.h writes its messages into g_err");
-  if (int rc = check_common(cfg, st, 1)) return rc;
+  if (int rc = check_common(cfg, st, nobj)) return rc;
   if (!p || !out) return fail(EARL_ERR_ARG, "policy/out is NULL");
-  if (int rc = contract::check_policy(*p, EARL_TABLETOP_OBS_DIM, EARL_TABLETOP_ACT_DIM, h, 0, g_err)) return rc;
+  if (int rc = contract::check_policy(*p, nobj == 3 ? EARL_TABLETOP3_OBS_DIM : EARL_TABLETOP_OBS_DIM, EARL_TABLETOP_ACT_DIM, h, 0, g_err)) return rc;
   if (T < 1) return fail(EARL_ERR_ARG, "T = %d < 1", T);
   if (episodes < 1) return fail(EARL_ERR_ARG, "episodes = %d < 1", episodes);
   if (reset_first != 0 && reset_first != 1) return fail(EARL_ERR_ARG, "reset_first = %d", reset_first);
@@ -95,8 +97,8 @@ inline int check_policy_gaussian(const earl_tabletop_cfg* cfg, const earl_tablet
 
 // earl_tabletop_population_rollout: the checks of the head's single-policy entry point, then the population's (one member per 16-env workgroup, any stride)
 inline int check_population(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_policy_population* pop,
-                            const earl_gaussian_head* h, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out) {
-  if (int rc = check_policy(cfg, st, p, h, episodes, T, reset_first, out)) return rc;
+                            const earl_gaussian_head* h, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, int nobj = 1) {
+  if (int rc = check_policy(cfg, st, p, h, episodes, T, reset_first, out, nobj)) return rc;
   return pop ? contract::check_population(*p, *pop, cfg->env_offset, cfg->n, kPolicyEnvsPerWg, 1, g_err) : EARL_OK;
 }
 
@@ -139,16 +141,16 @@ __host__ __device__ __forceinline__ size_t population_param_offset(const earl_po
 
 // the env's side of one closed-loop launch, shared by the kernel's env lanes and the host loop: what happens to ONE env before episode e's first step
 // (reset_body's reset on register state, or nothing) and the observation the first action is computed from
-template <bool GENERAL>
-__device__ __forceinline__ void policy_episode_begin(const PolicyArgs& a, int i, int e, Lane<1>& L, float (&g)[6], float (&o)[12]) {
+template <bool GENERAL, int NOBJ>
+__device__ __forceinline__ void policy_episode_begin(const PolicyArgs& a, int i, int e, Lane<NOBJ>& L, float (&g)[Dims<NOBJ>::NG], float (&o)[Dims<NOBJ>::NOBS]) {
   if (a.reset_first) {                              // reset_body: Philox counter of episode e's reset = cfg.counter + e (T + 1)
-    L.goal_idx = reset_env<1>(L.e, a.k.cfg, a.k.cfg.counter + (uint64_t)e * (uint64_t)(a.k.T + 1), i, a.k.st.goal_table, nullptr, a.k.th);
+    L.goal_idx = reset_env<NOBJ>(L.e, a.k.cfg, a.k.cfg.counter + (uint64_t)e * (uint64_t)(a.k.T + 1), i, a.k.st.goal_table, nullptr, a.k.th);
     L.steps = 0;
     L.sgc = 0;
     L.resets += 1;
-    load_goal<1>(a.k.st.goal_table, L.goal_idx, g);
+    load_goal<NOBJ>(a.k.st.goal_table, L.goal_idx, g);
   }
-  make_obs<1>(L.e, g, o);
+  make_obs<NOBJ>(L.e, g, o);
 }
 
 // the Philox counter of step t of episode e: what wrapped_step gets, and what keys the Gaussian head's draw of that step
@@ -157,9 +159,9 @@ __device__ __forceinline__ uint64_t policy_step_counter(const PolicyArgs& a, int
 }
 
 // one closed-loop step of one env given the policy's action (a0, a1, a2): act_out, wrapped_step, outputs
-template <bool GENERAL>
-__device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int e, int t, Lane<1>& L, float (&g)[6], float a0, float a1, float a2, float (&o)[12],
-                                                float& reward, bool& succ) {
+template <bool GENERAL, int NOBJ>
+__device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int e, int t, Lane<NOBJ>& L, float (&g)[Dims<NOBJ>::NG], float a0, float a1, float a2,
+                                                float (&o)[Dims<NOBJ>::NOBS], float& reward, bool& succ) {
   const size_t row = ((size_t)e * (size_t)a.k.T + (size_t)t) * (size_t)a.k.cfg.n + (size_t)i;
   if (a.act_out) {
     float* ap = a.act_out + row * 3;
@@ -167,14 +169,15 @@ __device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int 
   }
   const uint64_t counter = policy_step_counter(a, e, t);
   bool done;
-  wrapped_step<1, GENERAL>(a.k, i, counter, L, g, a0, a1, a2, o, reward, done, succ);
-  if (a.k.out.obs) store_obs<1>(a.k.out.obs + row * 12, o);
+  wrapped_step<NOBJ, GENERAL>(a.k, i, counter, L, g, a0, a1, a2, o, reward, done, succ);
+  if (a.k.out.obs) store_obs<NOBJ>(a.k.out.obs + row * Dims<NOBJ>::NOBS, o);
   if (a.k.out.reward) a.k.out.reward[row] = reward;
   if (a.k.out.done) a.k.out.done[row] = done;
   if (a.k.out.success) a.k.out.success[row] = succ;
 }
-template <bool GENERAL>
-__device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int e, int t, Lane<1>& L, float (&g)[6], float a0, float a1, float a2, float (&o)[12]) {
+template <bool GENERAL, int NOBJ>
+__device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int e, int t, Lane<NOBJ>& L, float (&g)[Dims<NOBJ>::NG], float a0, float a1, float a2,
+                                                float (&o)[Dims<NOBJ>::NOBS]) {
   float reward;
   bool succ;
   policy_env_step<GENERAL>(a, i, e, t, L, g, a0, a1, a2, o, reward, succ);
@@ -277,7 +280,7 @@ __device__ __forceinline__ void pair_env_step(const PairArgs& a, int i, int e, i
 // ------------------------------------------------------------------------------------------------
 // host twin: the MLP as the plain loops of the contract, one env at a time
 // ------------------------------------------------------------------------------------------------
-inline void mlp_layers(const earl_mlp_policy& p, const float* params, const float (&x)[12], float* act, int last_act) {
+inline void mlp_layers(const earl_mlp_policy& p, const float* params, const float* x, float* act, int last_act) {      // x: the p.dims[0] inputs
   float h[2][kPolicyMaxWidth];
   const float* in = x;
   const float* w = params;
@@ -295,15 +298,15 @@ inline void mlp_layers(const earl_mlp_policy& p, const float* params, const floa
     w = b + N;
   }
 }
-inline void mlp_forward(const earl_mlp_policy& p, const float* params, const float (&x)[12], float (&act)[3]) { mlp_layers(p, params, x, act, p.out_act); }
+inline void mlp_forward(const earl_mlp_policy& p, const float* params, const float* x, float (&act)[3]) { mlp_layers(p, params, x, act, p.out_act); }
 
 // `params`: the parameters this env runs (a population: its member's); `sum`: NULL or the per-episode summary arrays
-template <bool GENERAL>
+template <bool GENERAL, int NOBJ = 1>
 inline void policy_rollout_env(const PolicyArgs& a, int i, const float* params, const earl_episode_summary* sum = nullptr) {
-  Lane<1> L;
-  load_lane<1>(a.k, i, L);
-  float g[6], o[12];
-  load_goal<1>(a.k.st.goal_table, L.goal_idx, g);
+  Lane<NOBJ> L;
+  load_lane<NOBJ>(a.k, i, L);
+  float g[Dims<NOBJ>::NG], o[Dims<NOBJ>::NOBS];
+  load_goal<NOBJ>(a.k.st.goal_table, L.goal_idx, g);
   for (int e = 0; e < a.episodes; ++e) {
     policy_episode_begin<GENERAL>(a, i, e, L, g, o);
     EpisodeSum es;
@@ -317,16 +320,16 @@ inline void policy_rollout_env(const PolicyArgs& a, int i, const float* params, 
     }
     if (sum) episode_sum_store(*sum, (size_t)e * (size_t)a.k.cfg.n + (size_t)i, es);
   }
-  store_lane<1>(a.k, i, L);
+  store_lane<NOBJ>(a.k, i, L);
 }
 
 // the Gaussian head: the 6-wide last layer without activation, then the contract's head per dimension
-template <bool GENERAL>
+template <bool GENERAL, int NOBJ = 1>
 inline void gaussian_rollout_env(const GaussianPolicyArgs& a, int i, const float* params, const earl_episode_summary* sum = nullptr) {
-  Lane<1> L;
-  load_lane<1>(a.k, i, L);
-  float g[6], o[12];
-  load_goal<1>(a.k.st.goal_table, L.goal_idx, g);
+  Lane<NOBJ> L;
+  load_lane<NOBJ>(a.k, i, L);
+  float g[Dims<NOBJ>::NG], o[Dims<NOBJ>::NOBS];
+  load_goal<NOBJ>(a.k.st.goal_table, L.goal_idx, g);
   for (int e = 0; e < a.episodes; ++e) {
     policy_episode_begin<GENERAL>(a, i, e, L, g, o);
     EpisodeSum es;
@@ -348,7 +351,7 @@ inline void gaussian_rollout_env(const GaussianPolicyArgs& a, int i, const float
     }
     if (sum) episode_sum_store(*sum, (size_t)e * (size_t)a.k.cfg.n + (size_t)i, es);
   }
-  store_lane<1>(a.k, i, L);
+  store_lane<NOBJ>(a.k, i, L);
 }
 
 // the agent pair: per step the network of the env's phase, the head's draw (phase-independent), pair_env_step
@@ -399,7 +402,7 @@ inline void pair_rollout_env(const PairArgs& a, int i, bool gauss) {
 // ------------------------------------------------------------------------------------------------
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-constexpr int kPolX = 0;                                             // LDS floats: observation rows [16][12]
+constexpr int kPolX = 0;                                             // LDS floats: observation rows [16][12] (NOBJ = 3: [16][20], every image below 128 floats later: XS in the body)
 constexpr int kPolH1 = 16 * 12;                                      // hidden activations [16][H1]
 constexpr int kPolH2 = kPolH1 + 16 * kPolicyMaxWidth;                // [16][H2]
 constexpr int kPolAct = kPolH2 + 16 * kPolicyMaxWidth;               // actions [16][4]
@@ -447,11 +450,13 @@ __device__ __forceinline__ int pol_idx(int row, int k, int K) { return row * K +
 template <int NT2, bool GENERAL, bool GAUSS = false>
 __global__ __launch_bounds__(256) void policy_rollout_kernel(const typename PolicyArgsOf<GAUSS>::type a) {
   constexpr bool POP = false;
+  constexpr int NOBJ = 1;
 #include "tabletop_policy_kernel.inc"
 }
 template <int NT2, bool GENERAL, bool GAUSS>
 __global__ __launch_bounds__(256) void policy_population_kernel(const PopulationArgs a) {
   constexpr bool POP = true;
+  constexpr int NOBJ = 1;
 #include "tabletop_policy_kernel.inc"
 }
 #endif  // EARL_HOST_BUILD

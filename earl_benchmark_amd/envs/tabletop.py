@@ -308,7 +308,9 @@ class TabletopManipulation:
     A `GaussianMLPPolicy` goes to earl_tabletop_policy_rollout_gaussian: sample=True draws the actions inside the kernel (tanh(mean + exp(log_std) eps),
     eps from the env's Philox stream keyed by the global env id and the step's counter), sample=False evaluates the actor at its mean;
     return_noise=True appends eps [E,T,N,3], the standard-normal draws as used.  Both are for Gaussian policies only.
-    A `PolicyPopulation` goes to earl_tabletop_population_rollout: the env with global id g runs member g // envs_per_policy, same returns."""
+    A `PolicyPopulation` goes to earl_tabletop_population_rollout: the env with global id g runs member g // envs_per_policy, same returns.
+    The three-object env takes the same three classes built with obs_dim=20, act_dim=3 and returns the same tuple with obs [.., 20], every form through
+    earl_tabletop3_policy_rollout; bit-identical to reset() + rollout(actions) per episode / rollout(actions) fed with the returned actions."""
     gaussian = self._closed_loop_policy('rollout_policy', policy)
     if not gaussian and (return_noise or not sample):
       raise ValueError('rollout_policy: sample=False / return_noise=True need a GaussianMLPPolicy (an MLPPolicy is deterministic)')
@@ -316,7 +318,7 @@ class TabletopManipulation:
     E, lead = self._closed_loop_shape('rollout_policy', T, episodes, reset_first)
     with self._ctx():
       outs, ostruct, actions, eps = self._closed_loop_out(lead, out, return_noise)
-      if isinstance(policy, PolicyPopulation):
+      if isinstance(policy, PolicyPopulation) or self.NOBJ != 1:
         rc = self._population_launch(policy, gaussian, E, T, reset_first, ostruct, actions, eps, sample, None)
       elif gaussian:
         head = policy.head(sample=bool(sample), eps_out=eps)
@@ -333,6 +335,8 @@ class TabletopManipulation:
   # what rollout_policy, evaluate_policy and rollout_agents share: the refusals, the launch shape, the allocations and the bookkeeping after the launch
   def _closed_loop_policy(self, who, policy, pair=False):
     """the refusals every closed-loop launch begins with -> is the policy Gaussian"""
+    if self.NOBJ == 3 and not pair and (getattr(policy, 'obs_dim', 12), getattr(policy, 'act_dim', 3)) == (20, 3):
+      return require_widths(policy, who, 20, 3, env=self)               # the three-object env's own widths: earl_tabletop3_policy_rollout
     gaussian = require_widths(policy, who, 12, 3, env=self, pair=pair)
     if self.NOBJ != 1:
       raise NotImplementedError(f'{who}: single-object env only')
@@ -366,12 +370,14 @@ class TabletopManipulation:
     self._last_success = success[(-1,) * (success.dim() - 1)]
 
   def _population_launch(self, policy, gaussian, E, T, reset_first, ostruct, actions, eps, sample, summary):
-    """earl_tabletop_population_rollout for a PolicyPopulation (pop) or one policy (pop = NULL); -> the return code"""
+    """earl_tabletop_population_rollout (the three-object env: earl_tabletop3_policy_rollout, the same arguments) for a PolicyPopulation (pop) or one policy
+    (pop = NULL); -> the return code"""
     head = policy.head(sample=bool(sample), eps_out=eps) if gaussian else None
     pop = getattr(policy, 'pop_struct', None)
-    return self._lib.earl_tabletop_population_rollout(self._cfg_ref, self._st_ref, C.byref(policy.struct), None if pop is None else C.byref(pop),
-                                                      None if head is None else C.byref(head), E, T, int(bool(reset_first)), C.byref(ostruct), _ptr(actions),
-                                                      None if summary is None else C.byref(summary), self._stream())
+    launch = self._lib.earl_tabletop_population_rollout if self.NOBJ == 1 else self._lib.earl_tabletop3_policy_rollout
+    return launch(self._cfg_ref, self._st_ref, C.byref(policy.struct), None if pop is None else C.byref(pop),
+                  None if head is None else C.byref(head), E, T, int(bool(reset_first)), C.byref(ostruct), _ptr(actions),
+                  None if summary is None else C.byref(summary), self._stream())
 
   def evaluate_policy(self, policy, T, episodes=1, sample=False):
     """`episodes` evaluation episodes (each reset() + T closed-loop steps) of `policy` -- an MLPPolicy, a GaussianMLPPolicy (sample=False: at its mean) or a

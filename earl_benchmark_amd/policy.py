@@ -13,6 +13,13 @@ The Sawyer door and peg take the same two classes with obs_dim=14, act_dim=4 (in
   pi = MLPPolicy(layers, 'relu', 'tanh', device='cuda', obs_dim=14, act_dim=4)
   out = door.rollout_policy(pi, T=300)                                                          # rollout()'s dict plus 'actions' [T, N, 4], ONE launch
 
+The three-object tabletop takes the same classes with obs_dim=20, act_dim=3 (include/earl_tabletop.h: earl_tabletop3_policy_rollout), packed as the tabletop's
+(float32, rows as they are), a `PolicyPopulation` of them included; what it returns is the single-object env's with obs [.., 20]:
+
+  pi = MLPPolicy(layers, 'relu', 'tanh', device='cuda', obs_dim=20, act_dim=3)                  # or GaussianMLPPolicy(..., obs_dim=20, act_dim=3)
+  obs, reward, done, success, actions = env3.rollout_policy(pi, T=200, episodes=4)              # ONE launch
+  s = env3.evaluate_policy(PolicyPopulation([...], obs_dim=20, act_dim=3), T=200)               # summaries only
+
 The minitaur takes them with obs_dim=32, act_dim=8 and a bounded output (include/earl_physics.h: earl_minitaur_policy_rollout):
 
   pi = MLPPolicy(layers, 'relu', 'tanh', device='cuda', obs_dim=32, act_dim=8)                  # or GaussianMLPPolicy(..., squash=True, obs_dim=32, act_dim=8)
@@ -74,6 +81,7 @@ import torch
 from . import _abi
 
 OBS_DIM, ACT_DIM = 12, 3
+TABLETOP_WIDTHS = ((OBS_DIM, ACT_DIM), (20, ACT_DIM))      # the single-object and the three-object tabletop: weights in registers, float32 only, rows taken as they are
 MIN_WIDTH, MAX_WIDTH = 16, 256
 PARAM_DTYPES = {torch.float32: 0, torch.bfloat16: _abi.PRECISION_BF16}      # param_dtype -> earl_mlp_policy.precision
 
@@ -190,7 +198,7 @@ class MLPPolicy(_PackedMLP):
   OUT_DIM, OUT_WHAT = ACT_DIM, 'action'
 
   def __init__(self, layers, hidden_act='relu', out_act='tanh', device='cpu', obs_dim=OBS_DIM, act_dim=ACT_DIM, param_dtype=torch.float32):
-    """obs_dim / act_dim: the env's observation and action widths -- the tabletop's 12 / 3 by default, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur, 46 / 9 for the kitchen (`env.rollout_policy`).
+    """obs_dim / act_dim: the env's observation and action widths -- the tabletop's 12 / 3 by default, 20 / 3 for the three-object tabletop, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur, 46 / 9 for the kitchen (`env.rollout_policy`).
     param_dtype: the format the parameters are STORED in.  torch.bfloat16 (the door, the peg, the minitaur and the kitchen; earl_mlp_policy.precision =
     EARL_PRECISION_BF16) rounds every parameter ONCE, with torch's round-to-nearest-even; `.params` is then the bf16 tensor the kernel reads (writable in place), and
     `.layers` hold the widened float32 values, so pi(obs), pi.sample and make_step_graph(T, policy=pi) evaluate the network the kernel evaluates: bf16 is a storage
@@ -315,7 +323,7 @@ def require_widths(policy, who, obs_dim, act_dim, env=None, pair=False, bounded=
   gaussian = policy.gaussian if isinstance(policy, (PolicyPopulation, AgentPair, PairPopulation)) else isinstance(policy, GaussianMLPPolicy)
   if env is None:
     return gaussian
-  if (obs_dim, act_dim) == (OBS_DIM, ACT_DIM) and getattr(policy, 'param_dtype', torch.float32) != torch.float32:
+  if (obs_dim, act_dim) in TABLETOP_WIDTHS and getattr(policy, 'param_dtype', torch.float32) != torch.float32:
     raise ValueError(f'{who}: the parameters are stored as {policy.param_dtype}; the tabletop holds its weights in registers for the whole launch and takes float32 '
                      'only: pass .widened(), the float32 policy of exactly these values')
   if policy.device != env.device:
@@ -373,7 +381,7 @@ class PolicyPopulation(_PackedMLP):
       if host.dim() != 2 or host.shape[0] < 1 or host.shape[1] < self.n_params:
         raise ValueError(f'PolicyPopulation: params {tuple(host.shape)}: [P, >= {self.n_params}] (one row per member, packed like MLPPolicy.params)')
     self.n_policies = int(host.shape[0])
-    piece = _piece(self.param_dtype, (self.obs_dim, self.act_dim) == (OBS_DIM, ACT_DIM))      # (the stepper kernels read every member's rows in 16-byte pieces)
+    piece = _piece(self.param_dtype, (self.obs_dim, self.act_dim) in TABLETOP_WIDTHS)      # (the stepper kernels read every member's rows in 16-byte pieces)
     self.params = _padded(host, piece).clone().contiguous()
     self.to(template.device if device is None else device)
 

@@ -132,7 +132,7 @@ int earl_tabletop_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tableto
  *               (env_offset + n - 1) / G >= P
  *   pair        NULL pair / phase / steps_in_phase; switch_every[k] < 1; switch_on_success not 0 or 1; param_stride below the parameter count;
  *               cfg->goal_change_frequency > 0 (the pair IS the lifelong mechanism: the two clocks would fight over the same draw)
- * with the widths 12 / 3 here, 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur, 46 / 9 for the kitchen.  The differences are three, each listed with its entry point: the stepper
+ * with the widths 12 / 3 here (20 / 3 for earl_tabletop3_policy_rollout), 14 / 4 for the Sawyer door and peg, 32 / 8 for the minitaur, 46 / 9 for the kitchen.  The differences are three, each listed with its entry point: the stepper
  * units read the weight rows in 16-byte pieces (params 16-byte aligned, param_stride % 4 == 0), the minitaur takes bounded policies only (out_act == EARL_ACT_TANH),
  * and this header's pair holds two weight sets in registers (EARL_PAIR_MAX_H2). */
 enum { EARL_ACT_NONE = 0, EARL_ACT_RELU = 1, EARL_ACT_TANH = 2 };
@@ -143,7 +143,7 @@ enum { EARL_ACT_NONE = 0, EARL_ACT_RELU = 1, EARL_ACT_TANH = 2 };
 #define EARL_PRECISION_BF16 16
 typedef struct earl_mlp_policy {
   int32_t n_layers;     /* linear layers: 2 (one hidden) or 3 (two hidden) */
-  int32_t dims[4];      /* dims[0] = 12, dims[n_layers] = 3 (6 with a Gaussian head, below); hidden widths multiples of 16 in 16..256; unused = 0 */
+  int32_t dims[4];      /* dims[0] = 12 (the 3-object variant: 20), dims[n_layers] = 3 (6 with a Gaussian head, below); hidden widths multiples of 16 in 16..256; unused = 0 */
   int32_t hidden_act;   /* EARL_ACT_RELU or EARL_ACT_TANH */
   int32_t out_act;      /* EARL_ACT_NONE (the env clips to [-1, 1] itself, tabletop_manipulation.py:130) or EARL_ACT_TANH */
   int32_t precision;    /* 0 = fp32; EARL_PRECISION_BF16 where an entry point says so (earl_physics.h); anything else is EARL_ERR_ARG */
@@ -219,8 +219,8 @@ typedef struct earl_episode_summary {   /* every pointer may be NULL; rows [epis
  *            this launch's own out->reward / out->success, exactly, whether or not out's pointers / act_out are given (evaluation without any [T] array).
  * Everything else as the two single-policy entry points: reset_first / episodes rules, every `out` pointer / act_out / eps_out may be NULL (`out` itself
  * may not), Philox counter use episodes * (T + 1) resp. T, the Gaussian draw contract (seed, global env id, counter), lifelong switching and auto-reset,
- * argument errors before any HIP call: the contract's policy, head and (with pop) population rules.  Single-object env only (the 3-object variant has no policy
- * entry point). */
+ * argument errors before any HIP call: the contract's policy, head and (with pop) population rules.  Single-object env (the 3-object variant's is
+ * earl_tabletop3_policy_rollout, below). */
 int earl_tabletop_population_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
                                      const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
                                      const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary, earl_stream_t stream);
@@ -301,6 +301,22 @@ int earl_tabletop3_reset(const earl_tabletop_cfg* cfg, const earl_tabletop_state
 int earl_tabletop3_reward(int32_t n, const float* obs, int32_t reward_type, float* reward, uint8_t* success,
                           earl_stream_t stream);
 
+/* The closed loop of the 3-object variant in ONE launch: earl_tabletop_population_rollout's general form on qpos [n,8] and the 20-wide observation -- the
+ * deterministic policy (head == NULL: policy->dims[n_layers] == 3) or the Gaussian head (head != NULL: == 6), one policy (pop == NULL) or a population, [T] outputs
+ * and / or per-episode summaries (summary == NULL: none).  policy->dims[0] == EARL_TABLETOP3_OBS_DIM; everything else is the argument contract above (float32
+ * only: precision != 0 is EARL_ERR_ARG -- the weights live in registers; EARL_ERR_ARG before any HIP call; n == 0 returns EARL_OK).
+ * out rows [episodes, T, n, ..] with obs 20 wide, act_out [episodes, T, n, 3], head->eps_out [episodes, T, n, 3], summary rows [episodes, n]; each may be NULL
+ * (`out` itself may not).  Bit-identical to the open-loop entry points fed with act_out -- outputs, state left behind, wrapper counters, Philox counter use:
+ *   reset_first = 1: for each episode e, earl_tabletop3_reset (all envs, counter cfg->counter + e (T + 1)) followed by earl_tabletop3_rollout of T steps from
+ *                    the next counter (episodes * (T + 1) counter values in all);
+ *   reset_first = 0: earl_tabletop3_rollout (episodes must be 1; T counter values), auto-reset included.
+ * The policy arithmetic, the head, its draw (one Philox block per (env, step): seed, global env id, the step's counter; words x, y, z), EARL_HEAD_MEAN == the
+ * deterministic launch on rows 0..2 of the last layer, the population's addressing (global id g runs member g / G) and the summaries are those of the single-object
+ * entry points, word for word.  The agent pair has no 3-object form. */
+int earl_tabletop3_policy_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
+                                  const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
+                                  const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary, earl_stream_t stream);
+
 /* ---- host build: the `_cpu` entry points (BASELINE.json configs[0] "1 env, CPU ... plumbing, no GPU") ----
  * csrc/libearl_host.so = the SAME per-env functions the gfx950 kernels run (csrc/tabletop_device.h, tabletop_step.h, philox.h), compiled for the host by
  * g++ with -ffp-contract=off; one OpenMP iteration per env where a kernel has one lane per env.  Same structs, same arguments minus the stream, HOST
@@ -337,6 +353,10 @@ int earl_tabletop3_step_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_st
 int earl_tabletop3_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t T, const float* act, const earl_tabletop_out* out);
 int earl_tabletop3_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, float* obs);
 int earl_tabletop3_reward_cpu(int32_t n, const float* obs, int32_t reward_type, float* reward, uint8_t* success);
+/* host twin of earl_tabletop3_policy_rollout: the same plain loops as the single-object twins, on the 20-wide observation; bit-identical under the sparse reward */
+int earl_tabletop3_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
+                                      const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
+                                      const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary);
 int earl_host_set_threads(int n);        /* OpenMP threads of the calls above (n <= 0: query); returns the count in force */
 const char* earl_host_version(void);
 const char* earl_host_last_error(void);

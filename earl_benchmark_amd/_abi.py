@@ -167,6 +167,8 @@ SIGNATURES = {
     'earl_tabletop3_reward': [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_tabletop3_policy_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), _P(PolicyPopulation), _P(GaussianHead), C.c_int32, C.c_int32, C.c_int32,
                                       _P(TabletopOut), C.c_void_p, _P(EpisodeSummary), C.c_void_p],
+    'earl_tabletop3_pair_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), _P(AgentPair), _P(GaussianHead), C.c_int32, C.c_int32, C.c_int32, _P(TabletopOut),
+                                    C.c_void_p, C.c_void_p],
     'earl_debug_set_rollout_impl': [C.c_int],
     'earl_debug_set_rollout_wgs_per_cu': [C.c_int],
     'earl_debug_read_ws_profile': [C.c_void_p, C.c_int32],

@@ -224,6 +224,15 @@ int earl_tabletop3_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_t
   });
   return EARL_OK;
 }
+// host twin of earl_tabletop3_pair_rollout: pair_rollout_env (tabletop_policy.h) on Lane<3>, the 20-wide observation and the 10-wide goal row
+int earl_tabletop3_pair_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair,
+                                    const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out) {
+  if (int rc = check_pair(cfg, st, policy, pair, head, episodes, T, reset_first, out, 3)) return rc;
+  if (cfg->n == 0) return EARL_OK;
+  const PairArgs a = pair_args(cfg, st, policy, pair, head, episodes, T, reset_first, out, act_out, thresholds(), 3);
+  for_each_env(cfg->n, [&](int i) { pair_rollout_env<3>(a, i, head != nullptr); });
+  return EARL_OK;
+}
 int earl_tabletop3_reward_cpu(int32_t n, const float* obs, int32_t reward_type, float* reward, uint8_t* success) {
   if (n < 0 || !obs) return fail(EARL_ERR_ARG, "bad n/obs");
   if (reward_type != EARL_REWARD_SPARSE && reward_type != EARL_REWARD_DENSE) return fail(EARL_ERR_ARG, "reward_type = %d", reward_type);

@@ -6,7 +6,8 @@
 // member's parameters) with per-episode summaries (earl_tabletop_population_rollout) are instantiated in tabletop_policy_population.hip; the kernel body the
 // three units share is tabletop_policy_kernel.inc.  The THREE-object env's closed loop (20 -> hidden (-> hidden) -> 3 or 6, one policy or a population, summaries:
 // earl_tabletop3_policy_rollout) is the same body with NOBJ = 3, instantiated in tabletop3_policy.hip; the env's side below (policy_episode_begin, policy_env_step) and the host
-// twin's loops take the object count as a template argument.
+// twin's loops take the object count as a template argument.  The agent pair's env side (pair_env_step and its neighbours) takes it too: earl_tabletop_pair_rollout is
+// tabletop_policy_pair.hip, the three-object env's earl_tabletop3_pair_rollout tabletop3_pair.hip.
 //
 // The policy arithmetic is a contract, stated here once for both builds:
 //   pre-activation   acc = b_j;  for k = 0 .. K-1 ascending:  acc = fmaf(x_k, W_jk, acc)     (float32, one rounding per fused multiply-add)
@@ -47,7 +48,7 @@ struct PopulationArgs : GaussianPolicyArgs {
   earl_policy_population pop;
   earl_episode_summary sum;
 };
-// earl_tabletop_pair_rollout: both heads take this one (head unused without one).  p.params is [2, pair.param_stride]
+// earl_tabletop_pair_rollout / earl_tabletop3_pair_rollout: both heads take this one (head unused without one).  p.params is [2, pair.param_stride]
 struct PairArgs : GaussianPolicyArgs {
   earl_agent_pair pair;
 };
@@ -113,10 +114,11 @@ inline PopulationArgs population_args(const earl_tabletop_cfg* cfg, const earl_t
   return a;
 }
 
-// earl_tabletop_pair_rollout: the checks of the head's single-policy entry point, then the pair's (any stride) and the register budget of two weight sets
+// earl_tabletop_pair_rollout (nobj = 3: earl_tabletop3_pair_rollout): the checks of the head's single-policy entry point, then the pair's (any stride) and the register
+// budget of two weight sets
 inline int check_pair(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_agent_pair* pair, const earl_gaussian_head* h,
-                      int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out) {
-  if (int rc = check_policy(cfg, st, p, h, episodes, T, reset_first, out)) return rc;
+                      int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, int nobj = 1) {
+  if (int rc = check_policy(cfg, st, p, h, episodes, T, reset_first, out, nobj)) return rc;
   if (int rc = contract::check_pair(*p, pair, cfg->goal_change_frequency, 1, g_err)) return rc;
   if (p->n_layers == 3 && p->dims[2] > kPairMaxH2)
     return fail(EARL_ERR_ARG, "pair: second hidden width %d > EARL_PAIR_MAX_H2 = %d (two weight sets in one wave's registers)", p->dims[2], kPairMaxH2);
@@ -124,7 +126,8 @@ inline int check_pair(const earl_tabletop_cfg* cfg, const earl_tabletop_state* s
 }
 
 inline PairArgs pair_args(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* p, const earl_agent_pair* pair, const earl_gaussian_head* h,
-                          int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out, const Thresholds& th) {
+                          int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out, const Thresholds& th,
+                          [[maybe_unused]] int nobj = 1) {      // (nobj: not read -- PairArgs has no width of its own; taken so that the call reads as check_pair's)
   PairArgs a;
   static_cast<PolicyArgs&>(a) = PolicyArgs{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, th}, *p, act_out, episodes, reset_first};
   a.head = h ? *h : contract::default_head();
@@ -184,7 +187,8 @@ __device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int 
 }
 
 // ------------------------------------------------------------------------------------------------
-// The agent pair (include/earl_tabletop.h: earl_tabletop_pair_rollout), the env's side, shared by the kernel's env lanes (tabletop_policy_pair.hip) and the
+// The agent pair (include/earl_tabletop.h: earl_tabletop_pair_rollout; NOBJ = 3: earl_tabletop3_pair_rollout), the env's side, shared by the kernels' env lanes
+// (tabletop_policy_pair.hip, tabletop3_pair.hip) and the
 // host loop: the phase state of one env and what a step does to it.  The order of pair_env_step IS the contract of record's items 3 .. 6.
 // ------------------------------------------------------------------------------------------------
 struct PairLane {
@@ -193,26 +197,30 @@ struct PairLane {
   int fs, bs;  // forward / reset phases of this episode that ended by success
 };
 
-// the goal in force: the reset agent's row if there is one, otherwise the env's stored task goal
-__device__ __forceinline__ void pair_goal(const PairArgs& a, const Lane<1>& L, int phase, float (&g)[6]) {
+// the goal in force: the reset agent's row if there is one, otherwise the env's stored task goal.  NOBJ = 3 (earl_tabletop3_pair_rollout): a 10-wide row
+template <int NOBJ = 1>
+__device__ __forceinline__ void pair_goal(const PairArgs& a, const Lane<NOBJ>& L, int phase, float (&g)[Dims<NOBJ>::NG]) {
   if (phase && a.pair.backward_goal) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) g[k] = (float)a.pair.backward_goal[k];
+    for (int k = 0; k < Dims<NOBJ>::NG; ++k) g[k] = (float)a.pair.backward_goal[k];
   } else {
-    load_goal<1>(a.k.st.goal_table, L.goal_idx, g);
+    load_goal<NOBJ>(a.k.st.goal_table, L.goal_idx, g);
   }
 }
 
-__device__ __forceinline__ void pair_load(const PairArgs& a, int i, const Lane<1>& L, PairLane& P, float (&g)[6]) {
+template <int NOBJ = 1>
+__device__ __forceinline__ void pair_load(const PairArgs& a, int i, const Lane<NOBJ>& L, PairLane& P, float (&g)[Dims<NOBJ>::NG]) {
   P.phase = a.pair.phase[i] != 0;
   P.sip = a.pair.steps_in_phase[i];
   P.fs = 0;
   P.bs = 0;
-  pair_goal(a, L, P.phase, g);
+  pair_goal<NOBJ>(a, L, P.phase, g);
 }
 
 // episode e's begin: policy_episode_begin, and a reset puts the env into the forward phase
-__device__ __forceinline__ void pair_episode_begin(const PairArgs& a, int i, int e, Lane<1>& L, PairLane& P, float (&g)[6], float (&o)[12]) {
+template <int NOBJ = 1>
+__device__ __forceinline__ void pair_episode_begin(const PairArgs& a, int i, int e, Lane<NOBJ>& L, PairLane& P, float (&g)[Dims<NOBJ>::NG],
+                                                   float (&o)[Dims<NOBJ>::NOBS]) {
   if (a.reset_first) {
     P.phase = 0;
     P.sip = 0;
@@ -222,22 +230,26 @@ __device__ __forceinline__ void pair_episode_begin(const PairArgs& a, int i, int
   policy_episode_begin<true>(a, i, e, L, g, o);
 }
 
+template <int NOBJ = 1>      // (not used: the counters have no width; a template like its neighbours so that a caller names the object count throughout)
 __device__ __forceinline__ void pair_episode_end(const PairArgs& a, int i, int e, const PairLane& P) {
   const size_t row = (size_t)e * (size_t)a.k.cfg.n + (size_t)i;
   if (a.pair.forward_success) a.pair.forward_success[row] = P.fs;
   if (a.pair.backward_success) a.pair.backward_success[row] = P.bs;
 }
 
-__device__ __forceinline__ void pair_store(const PairArgs& a, int i, const Lane<1>& L, const PairLane& P) {
-  store_lane<1>(a.k, i, L);
+template <int NOBJ = 1>
+__device__ __forceinline__ void pair_store(const PairArgs& a, int i, const Lane<NOBJ>& L, const PairLane& P) {
+  store_lane<NOBJ>(a.k, i, L);
   a.k.st.goal_idx[i] = L.goal_idx;                  // (store_lane writes it under lifelong / reset only)
   a.pair.phase[i] = (int8_t)P.phase;
   a.pair.steps_in_phase[i] = P.sip;
 }
 
 // one closed-loop step of one env given ITS agent's action: agent_out, act_out, wrapped_step, the handover, outputs
-__device__ __forceinline__ void pair_env_step(const PairArgs& a, int i, int e, int t, Lane<1>& L, PairLane& P, float (&g)[6], float a0, float a1, float a2,
-                                              float (&o)[12]) {
+template <int NOBJ = 1>
+__device__ __forceinline__ void pair_env_step(const PairArgs& a, int i, int e, int t, Lane<NOBJ>& L, PairLane& P, float (&g)[Dims<NOBJ>::NG], float a0, float a1,
+                                              float a2, float (&o)[Dims<NOBJ>::NOBS]) {
+  constexpr int NG = Dims<NOBJ>::NG, NOBS = Dims<NOBJ>::NOBS;      // the goal slots of the observation: o[NOBS - NG ..] = o[NQ + 2 ..]
   const size_t row = ((size_t)e * (size_t)a.k.T + (size_t)t) * (size_t)a.k.cfg.n + (size_t)i;
   if (a.pair.agent_out) a.pair.agent_out[row] = (int8_t)P.phase;
   if (a.act_out) {
@@ -248,7 +260,7 @@ __device__ __forceinline__ void pair_env_step(const PairArgs& a, int i, int e, i
   const int resets = L.resets;
   float reward;
   bool done, succ;
-  wrapped_step<1, true>(a.k, i, counter, L, g, a0, a1, a2, o, reward, done, succ);
+  wrapped_step<NOBJ, true>(a.k, i, counter, L, g, a0, a1, a2, o, reward, done, succ);
   if (L.resets != resets) {                         // auto-reset: back to the forward agent (g is the new task goal already), nothing else
     P.phase = 0;
     P.sip = 0;
@@ -264,13 +276,13 @@ __device__ __forceinline__ void pair_env_step(const PairArgs& a, int i, int e, i
       P.sip = 0;
       if (P.phase == 0) L.goal_idx = sample_goal(a.k.cfg, counter, i, nullptr);      // the draw the lifelong switch makes
       if (P.phase == 0 || a.pair.backward_goal) {
-        pair_goal(a, L, P.phase, g);
+        pair_goal<NOBJ>(a, L, P.phase, g);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) o[6 + k] = g[k];                                   // obs re-read with the new goal
+        for (int k = 0; k < NG; ++k) o[NOBS - NG + k] = g[k];                          // obs re-read with the new goal
       }
     }
   }
-  if (a.k.out.obs) store_obs<1>(a.k.out.obs + row * 12, o);
+  if (a.k.out.obs) store_obs<NOBJ>(a.k.out.obs + row * NOBS, o);
   if (a.k.out.reward) a.k.out.reward[row] = reward;
   if (a.k.out.done) a.k.out.done[row] = done;
   if (a.k.out.success) a.k.out.success[row] = succ;
@@ -355,14 +367,15 @@ inline void gaussian_rollout_env(const GaussianPolicyArgs& a, int i, const float
 }
 
 // the agent pair: per step the network of the env's phase, the head's draw (phase-independent), pair_env_step
+template <int NOBJ = 1>
 inline void pair_rollout_env(const PairArgs& a, int i, bool gauss) {
-  Lane<1> L;
-  load_lane<1>(a.k, i, L);
+  Lane<NOBJ> L;
+  load_lane<NOBJ>(a.k, i, L);
   PairLane P;
-  float g[6], o[12];
-  pair_load(a, i, L, P, g);
+  float g[Dims<NOBJ>::NG], o[Dims<NOBJ>::NOBS];
+  pair_load<NOBJ>(a, i, L, P, g);
   for (int e = 0; e < a.episodes; ++e) {
-    pair_episode_begin(a, i, e, L, P, g, o);
+    pair_episode_begin<NOBJ>(a, i, e, L, P, g, o);
     for (int t = 0; t < a.k.T; ++t) {
       const float* params = a.p.params + (size_t)P.phase * (size_t)a.pair.param_stride;
       float act[3];
@@ -380,11 +393,11 @@ inline void pair_rollout_env(const PairArgs& a, int i, bool gauss) {
       } else {
         mlp_forward(a.p, params, o, act);
       }
-      pair_env_step(a, i, e, t, L, P, g, act[0], act[1], act[2], o);
+      pair_env_step<NOBJ>(a, i, e, t, L, P, g, act[0], act[1], act[2], o);
     }
-    pair_episode_end(a, i, e, P);
+    pair_episode_end<NOBJ>(a, i, e, P);
   }
-  pair_store(a, i, L, P);
+  pair_store<NOBJ>(a, i, L, P);
 }
 
 #else

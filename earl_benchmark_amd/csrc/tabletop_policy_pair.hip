@@ -1,9 +1,10 @@
 // tabletop_policy_pair.hip -- earl_tabletop_pair_rollout (include/earl_tabletop.h): the closed-loop tabletop rollout with the forward / reset agent pair of
 // autonomous RL alternating inside ONE launch.  The env's side (phase state, handover rule, goal overlay) is tabletop_policy.h's pair_env_step, shared with the host
-// twin; this unit holds the kernel, a body of its own: the forty single-policy / population kernels are not routed through it.
+// twin; this unit holds the kernel, a body of its own: the forty single-policy / population kernels and the three-object env's twenty are not routed through it, and the
+// three-object env's pair (earl_tabletop3_pair_rollout) is tabletop3_pair.hip, which restates this body at NOBJ = 3 with more of its operands in LDS.
 // TWIN: the step body below restates tabletop_policy_kernel.inc's (layer 0, hidden layer, output chain, head, fence) once per agent.  Each env's action is held
 // bit for bit to that chain, so a change to the arithmetic or its order in either file is mirrored in the other by hand (tests/test_policy_pair.py, test 1, and
-// tests/test_policy_pair_gpu.py compare the two).
+// tests/test_policy_pair_gpu.py compare the two); tabletop3_pair.hip carries the same note towards this file.
 //
 // The workgroup is the single-policy kernel's: 16 envs (the M of v_mfma_f32_16x16x4_f32) x four waves, env state on lanes 0..15 of wave 0 for the whole launch,
 // the same lane maps and LDS image layout (tabletop_policy.h).  What differs:

@@ -335,8 +335,8 @@ class TabletopManipulation:
   # what rollout_policy, evaluate_policy and rollout_agents share: the refusals, the launch shape, the allocations and the bookkeeping after the launch
   def _closed_loop_policy(self, who, policy, pair=False):
     """the refusals every closed-loop launch begins with -> is the policy Gaussian"""
-    if self.NOBJ == 3 and not pair and (getattr(policy, 'obs_dim', 12), getattr(policy, 'act_dim', 3)) == (20, 3):
-      return require_widths(policy, who, 20, 3, env=self)               # the three-object env's own widths: earl_tabletop3_policy_rollout
+    if self.NOBJ == 3 and (getattr(policy, 'obs_dim', 12), getattr(policy, 'act_dim', 3)) == (20, 3):
+      return require_widths(policy, who, 20, 3, env=self, pair=pair)    # the three-object env's own widths: earl_tabletop3_policy_rollout / earl_tabletop3_pair_rollout
     gaussian = require_widths(policy, who, 12, 3, env=self, pair=pair)
     if self.NOBJ != 1:
       raise NotImplementedError(f'{who}: single-object env only')
@@ -400,7 +400,8 @@ class TabletopManipulation:
     return {'ret': ret, 'success': succ, 'first_success': first}
 
   def rollout_agents(self, pair, T, episodes=None, reset_first=False, sample=True, return_noise=False, out=None):
-    """The forward / reset agent pair of autonomous RL alternating inside ONE kernel launch (include/earl_tabletop.h: earl_tabletop_pair_rollout): every env is
+    """The forward / reset agent pair of autonomous RL alternating inside ONE kernel launch (include/earl_tabletop.h: earl_tabletop_pair_rollout; the three-object env with a
+    20-wide pair, `AgentPair(f, b, ..., obs_dim=20, act_dim=3)`: earl_tabletop3_pair_rollout, the goal row 10 wide): every env is
     driven by the agent of its phase (`env.agent_phase`: 0 forward, 1 reset) and handed over after pair.switch_every[phase] steps or, with
     pair.switch_on_success, after a step whose success flag is set.  The default is the continuing form -- T steps from the current state, the training
     stream; reset_first=True: `episodes` evaluation episodes, each reset() + T steps starting with the forward agent.
@@ -430,8 +431,9 @@ class TabletopManipulation:
                           backward_goal=_ptr(goal), phase=self.agent_phase.data_ptr(), steps_in_phase=self.steps_in_phase.data_ptr(),
                           agent_out=agent.data_ptr(), forward_success=fwd.data_ptr(), backward_success=bwd.data_ptr())
       head = pair.head(sample=bool(sample), eps_out=eps) if gaussian else None
-      rc = self._lib.earl_tabletop_pair_rollout(self._cfg_ref, self._st_ref, C.byref(pair.struct), C.byref(ps), None if head is None else C.byref(head), E, T,
-                                                int(bool(reset_first)), C.byref(ostruct), actions.data_ptr(), self._stream())
+      launch = self._lib.earl_tabletop_pair_rollout if self.NOBJ == 1 else self._lib.earl_tabletop3_pair_rollout
+      rc = launch(self._cfg_ref, self._st_ref, C.byref(pair.struct), C.byref(ps), None if head is None else C.byref(head), E, T, int(bool(reset_first)),
+                  C.byref(ostruct), actions.data_ptr(), self._stream())
     self._closed_loop_done(rc, 'pair_rollout', E, T, reset_first, outs[3])
     self._pair_counts = (fwd, bwd)
     if return_noise:

@@ -300,7 +300,7 @@ class GaussianMLPPolicy(MLPPolicy):
     return torch.tanh(u) if self.squash else u
 
 
-GOAL_DIMS = {(OBS_DIM, ACT_DIM): 6, (14, 4): 7, (32, 8): 2, (46, 9): 23}      # width of an AgentPair's backward goal by the agents' widths
+GOAL_DIMS = {(OBS_DIM, ACT_DIM): 6, (20, ACT_DIM): 10, (14, 4): 7, (32, 8): 2, (46, 9): 23}      # width of an AgentPair's backward goal by the agents' widths
 PAIR_POPULATION_WIDTHS = ((14, 4), (32, 8), (46, 9))                          # the envs whose pair launch takes a population of pairs
 
 
@@ -445,7 +445,8 @@ class AgentPair(_PackedMLP):
   reset); switch_on_success: also hand over after a step whose success flag is set; backward_goal: the goal row the reset agent is conditioned on -- 'initial' (the
   env's initial state, resolved by the env at launch), None (the reset agent keeps seeing the task goal) or a 6-vector in goal-table format.
   A second hidden layer may be at most 128 wide (EARL_PAIR_MAX_H2: two weight sets share one wave's registers); one hidden layer may have every width.
-  obs_dim / act_dim: the agents' widths -- the tabletop's 12 / 3 by default; 14 / 4 for the Sawyer door and peg (earl_sawyer_pair_rollout), where the backward goal is
+  obs_dim / act_dim: the agents' widths -- the tabletop's 12 / 3 by default; 20 / 3 for the three-object tabletop (earl_tabletop3_pair_rollout: the same rules with a
+  goal row of 10 values, 'initial' = [0, 0, 2.5, 0, 2.5, -1, 2.5, 1, -1, -1]); 14 / 4 for the Sawyer door and peg (earl_sawyer_pair_rollout), where the backward goal is
   a row of 7 values in the Sawyer goal format, the rows are padded to a stride of whole 16-byte pieces as PolicyPopulation's, and no width limit applies (the weights
   are read from memory at every step).  There backward_goal may also be a TABLE [R, 7], R >= 2 (kept as `.backward_goals`; `.backward_goal` is then None), or
   'initial_states' (the env's `initial_states`, resolved at launch: the peg's fifteen rows, the door's one, which behaves as 'initial'): at every entry into the
@@ -455,8 +456,8 @@ class AgentPair(_PackedMLP):
 
   def __init__(self, forward, backward, switch_every=200, switch_on_success=True, backward_goal='initial', device=None, obs_dim=OBS_DIM, act_dim=ACT_DIM):
     self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
-    tabletop = (self.obs_dim, self.act_dim) == (OBS_DIM, ACT_DIM)
-    self.goal_dim = GOAL_DIMS.get((self.obs_dim, self.act_dim), 7)      # the env's goal row: 6 tabletop, 7 Sawyer door / peg, 2 minitaur (x, y), 23 kitchen (a qpos)
+    tabletop = (self.obs_dim, self.act_dim) in TABLETOP_WIDTHS        # (12 / 3, and the three-object env's 20 / 3: earl_tabletop3_pair_rollout)
+    self.goal_dim = GOAL_DIMS.get((self.obs_dim, self.act_dim), 7)      # the env's goal row: 6 tabletop (three objects: 10), 7 Sawyer door / peg, 2 minitaur (x, y), 23 kitchen (a qpos)
     members = [forward, backward]
     if not all(isinstance(m, MLPPolicy) for m in members):
       raise ValueError('AgentPair: forward and backward are MLPPolicy / GaussianMLPPolicy')
@@ -533,13 +534,13 @@ class AgentPair(_PackedMLP):
     return self._initial_states_dev[1]
 
   def goal_row(self, env):
-    """the reset agent's goal row as a float64 tensor [6] (Sawyer widths: [7]) on the pair's device, or None; 'initial' is `env.initial_state` (the Sawyer door: the one
+    """the reset agent's goal row as a float64 tensor [6] (three-object tabletop: [10]; Sawyer widths: [7]) on the pair's device, or None; 'initial' is `env.initial_state` (the Sawyer door: the one
     row of `env.initial_states`; the peg has fifteen, so the caller picks one -- or asks for 'initial_states', the whole table: goal_table)"""
     if self.backward_goal is None:
       return None
     if self._goal_dev is not None:
       return self._goal_dev
-    if self.goal_dim != 6:
+    if (self.obs_dim, self.act_dim) not in TABLETOP_WIDTHS:
       rows = np.asarray(env.initial_states, dtype=np.float64).reshape(-1, self.goal_dim)
       if len(rows) != 1:
         raise ValueError(f"AgentPair: backward_goal='initial' needs ONE initial state and env.initial_states has {len(rows)} rows: pass the row to condition the "

@@ -234,7 +234,7 @@ typedef struct earl_agent_pair {
   int32_t switch_on_success;   /* 1 = also hand over after a step whose success flag is set; 0 = the clocks only */
   int32_t pad_;                /* unused (keeps param_stride 8-byte aligned in every compiler's layout) */
   int64_t param_stride;        /* floats between the two rows of policy->params; >= the parameter count of one policy */
-  const double* backward_goal; /* NULL, or ONE goal row (6 doubles, goal-table format) the reset agent is conditioned on */
+  const double* backward_goal; /* NULL, or ONE goal row (6 doubles, goal-table format; the 3-object variant: 10) the reset agent is conditioned on */
   int8_t*  phase;              /* [n] caller-owned state: 0 forward, 1 reset */
   int32_t* steps_in_phase;     /* [n] caller-owned state: steps the env has spent in its phase */
   int8_t*  agent_out;          /* NULL or [episodes, T, n]: the agent that computed the action of step t */
@@ -263,7 +263,8 @@ typedef struct earl_agent_pair {
  * Never switching (switch_every > T, switch_on_success = 0, all envs in phase 0) the launch is bit-identical to the single-policy entry point of the same
  * head on row 0.  Everything else as those entry points: reset_first / episodes rules, NULL-able outputs / act_out / eps_out, Philox counter use
  * episodes * (T + 1) resp. T, argument errors before any HIP call: the contract's policy, head and pair rules, and this entry point's own: a second hidden layer
- * wider than EARL_PAIR_MAX_H2 (two weight sets share the registers of one wave per SIMD; one hidden layer may have every legal width).  Single-object env only. */
+ * wider than EARL_PAIR_MAX_H2 (two weight sets share the registers of one wave per SIMD; one hidden layer may have every legal width).  This entry point is the single-object env's;
+ * the 3-object variant's is earl_tabletop3_pair_rollout, below. */
 #define EARL_PAIR_MAX_H2 128
 int earl_tabletop_pair_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair,
                                const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out,
@@ -312,10 +313,22 @@ int earl_tabletop3_reward(int32_t n, const float* obs, int32_t reward_type, floa
  *   reset_first = 0: earl_tabletop3_rollout (episodes must be 1; T counter values), auto-reset included.
  * The policy arithmetic, the head, its draw (one Philox block per (env, step): seed, global env id, the step's counter; words x, y, z), EARL_HEAD_MEAN == the
  * deterministic launch on rows 0..2 of the last layer, the population's addressing (global id g runs member g / G) and the summaries are those of the single-object
- * entry points, word for word.  The agent pair has no 3-object form. */
+ * entry points, word for word.  The agent pair's 3-object form is earl_tabletop3_pair_rollout. */
 int earl_tabletop3_policy_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
                                   const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
                                   const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary, earl_stream_t stream);
+
+/* The AGENT PAIR on the 3-object variant in ONE launch: earl_tabletop_pair_rollout on qpos [n,8] and the 20-wide observation.  policy->dims[0] ==
+ * EARL_TABLETOP3_OBS_DIM; pair->backward_goal is NULL or ONE goal row of 10 doubles (goal-table format); out->obs rows are 20 wide.  The contract is items 1..6 of
+ * earl_tabletop_pair_rollout, word for word: the network of the env's phase, the phase-independent Philox draw, agent_out / act_out, the wrapped env step (the
+ * 3-object one), auto-reset -> phase 0, handover by clock or success.  Entering the forward phase, goal_idx = the draw of this step's counter (draw 0) and the
+ * observation's goal slots 10..19 are re-read with the goal in force; entering the reset phase with a backward_goal leaves goal_idx alone.  Launch entry and exit,
+ * reset_first / episodes, NULL-able outputs and Philox counter use as there.  Never switching, the launch is bit-identical to earl_tabletop3_policy_rollout with
+ * one policy on row 0.  Argument errors before any HIP call: the 3-object env's (wide_init, goal_change_frequency), the contract's policy / head / pair rules, and a
+ * second hidden layer wider than EARL_PAIR_MAX_H2.  n == 0 returns EARL_OK. */
+int earl_tabletop3_pair_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair,
+                                const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out,
+                                earl_stream_t stream);
 
 /* ---- host build: the `_cpu` entry points (BASELINE.json configs[0] "1 env, CPU ... plumbing, no GPU") ----
  * csrc/libearl_host.so = the SAME per-env functions the gfx950 kernels run (csrc/tabletop_device.h, tabletop_step.h, philox.h), compiled for the host by
@@ -357,6 +370,9 @@ int earl_tabletop3_reward_cpu(int32_t n, const float* obs, int32_t reward_type, 
 int earl_tabletop3_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
                                       const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
                                       const earl_tabletop_out* out, float* act_out, const earl_episode_summary* summary);
+/* host twin of earl_tabletop3_pair_rollout: earl_tabletop_pair_rollout_cpu's loops on the 3-object env; every pointer of `pair` is a HOST pointer; refuses the same shapes */
+int earl_tabletop3_pair_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair,
+                                    const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out);
 int earl_host_set_threads(int n);        /* OpenMP threads of the calls above (n <= 0: query); returns the count in force */
 const char* earl_host_version(void);
 const char* earl_host_last_error(void);

@@ -10,6 +10,7 @@ import os
 EARL_OK = 0
 REWARD_SPARSE, REWARD_DENSE = 0, 1
 REWARD_TYPES = {'sparse': REWARD_SPARSE, 'dense': REWARD_DENSE}
+TABLETOP3_EVAL_CHUNK = 8    # EARL_TABLETOP3_EVAL_CHUNK: the chunk length of earl_tabletop3_eval_episodes' fused launch
 
 
 class TabletopCfg(C.Structure):
@@ -165,11 +166,13 @@ SIGNATURES = {
     'earl_tabletop3_rollout': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_void_p, _P(TabletopOut), C.c_void_p],
     'earl_tabletop3_reset': [_P(TabletopCfg), _P(TabletopState), C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_tabletop3_reward': [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    'earl_tabletop3_eval_episodes': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _P(TabletopOut), C.c_void_p],
     'earl_tabletop3_policy_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), _P(PolicyPopulation), _P(GaussianHead), C.c_int32, C.c_int32, C.c_int32,
                                       _P(TabletopOut), C.c_void_p, _P(EpisodeSummary), C.c_void_p],
     'earl_tabletop3_pair_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), _P(AgentPair), _P(GaussianHead), C.c_int32, C.c_int32, C.c_int32, _P(TabletopOut),
                                     C.c_void_p, C.c_void_p],
     'earl_debug_set_rollout_impl': [C.c_int],
+    'earl_debug_set_rollout3_form': [C.c_int],
     'earl_debug_set_rollout_wgs_per_cu': [C.c_int],
     'earl_debug_read_ws_profile': [C.c_void_p, C.c_int32],
     # include/earl_glue.h

@@ -209,6 +209,24 @@ int earl_tabletop3_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop
 int earl_tabletop3_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, float* obs) {
   return do_reset<3>(cfg, st, mask, nullptr, obs);
 }
+// host twin of earl_tabletop3_eval_episodes: the plain loop over the reset and the rollout above
+int earl_tabletop3_eval_episodes_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t episodes, int32_t T, const float* act,
+                                     int64_t act_episode_stride, const earl_tabletop_out* out) {
+  if (episodes < 0) return fail(EARL_ERR_ARG, "episodes = %d < 0", episodes);
+  if (act_episode_stride < 0) return fail(EARL_ERR_ARG, "negative action stride");
+  if (int rc = check_common(cfg, st, 3)) return rc;
+  if (!act || !out) return fail(EARL_ERR_ARG, "act/out is NULL");
+  if (T < 0) return fail(EARL_ERR_ARG, "T = %d < 0", T);
+  for (int32_t e = 0; e < episodes; ++e) {
+    earl_tabletop_cfg c = *cfg;
+    c.counter += (uint64_t)e * (uint64_t)(T + 1);
+    const size_t rows = (size_t)e * (size_t)T * (size_t)cfg->n;
+    const earl_tabletop_out o{out->obs ? out->obs + rows * 20 : nullptr, out->reward ? out->reward + rows : nullptr, out->done ? out->done + rows : nullptr,
+                              out->success ? out->success + rows : nullptr, nullptr};
+    if (int rc = do_rollout<3>(&c, st, T, act + (size_t)e * (size_t)act_episode_stride, &o, true)) return rc;
+  }
+  return EARL_OK;
+}
 // host twin of earl_tabletop3_policy_rollout: the single-object loops (tabletop_policy.h) on Lane<3> and the 20-wide observation
 int earl_tabletop3_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_policy_population* pop,
                                       const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out,

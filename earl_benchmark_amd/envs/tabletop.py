@@ -272,9 +272,7 @@ class TabletopManipulation:
     """`episodes` evaluation episodes of every env, back to back (each = reset() + T steps), in ONE kernel launch when the fused kernel
     applies (include/earl_tabletop.h: earl_tabletop_eval_episodes).  actions [T, N, 3] (replayed by every episode; give `episodes`) or
     [E, T, N, 3].  -> (obs [E,T,N,D], reward [E,T,N], done [E,T,N], success [E,T,N]); bit-identical to E calls of
-    rollout(actions, reset_first=True)."""
-    if self.NOBJ != 1:
-      raise NotImplementedError('rollout_episodes: single-object env only')
+    rollout(actions, reset_first=True).  The three-object env goes through earl_tabletop3_eval_episodes and returns obs [E,T,N,20]."""
     with self._ctx():
       a = torch.as_tensor(actions, device=self.device)
       if a.dim() == 4:
@@ -292,7 +290,8 @@ class TabletopManipulation:
       else:
         outs = tuple(out)
         ostruct = self._out_struct(outs, (E, T, self.num_envs))
-      rc = self._lib.earl_tabletop_eval_episodes(self._cfg_ref, self._st_ref, E, T, act.data_ptr(), stride, C.byref(ostruct), self._stream())
+      fn = self._lib.earl_tabletop_eval_episodes if self.NOBJ == 1 else self._lib.earl_tabletop3_eval_episodes
+      rc = fn(self._cfg_ref, self._st_ref, E, T, act.data_ptr(), stride, C.byref(ostruct), self._stream())
     self._check(rc, 'eval_episodes')
     self._cfg.counter += E * (T + 1)
     self.total_step_count += E * T

@@ -302,6 +302,21 @@ int earl_tabletop3_reset(const earl_tabletop_cfg* cfg, const earl_tabletop_state
 int earl_tabletop3_reward(int32_t n, const float* obs, int32_t reward_type, float* reward, uint8_t* success,
                           earl_stream_t stream);
 
+/* earl_tabletop_eval_episodes for the 3-object variant: `episodes` evaluation episodes per env, back to back.  Episode e is earl_tabletop3_reset (all envs,
+ * Philox counter cfg->counter + e (T + 1)) followed by earl_tabletop3_rollout of T steps from the next counter, its outputs at rows [e, T, n, ..] of `out`
+ * (obs [episodes, T, n, 20]), its actions at act + e * act_episode_stride floats (T * n * 3: a contiguous [episodes, T, n, 3] array; 0: every episode replays
+ * the same [T, n, 3]).  Bit-identical to that sequence of calls: the four outputs (the dense reward included), the state left behind (qpos [n, 8], attached,
+ * goal_idx, steps_since_reset, num_interventions) and the Philox counter use, episodes * (T + 1); nothing depends on n, on the shard split (draws are keyed by the
+ * global env id) or on the launch form.  EARL_ERR_ARG before any HIP call for episodes < 0, T < 0, a negative stride, act / out NULL and the 3-object env's own
+ * rules (wide_init, goal_change_frequency); episodes == 0 or n == 0 returns EARL_OK; T == 0 does the resets only.
+ * ONE role-split launch walks all episodes (csrc/tabletop3_rollout_ws.h: a compute wave for the recurrence, loader and storer waves around it, several episodes
+ * in flight while the batch fills at most half the CUs) when cfg->auto_reset == 0, all four `out` pointers are given, T is a multiple of
+ * EARL_TABLETOP3_EVAL_CHUNK and at least twice it, episodes * T < 2^24, and out->obs is 16-byte aligned, out->reward / done / success 4-byte aligned (any
+ * allocation is; a slice of a larger array need not be); any other legal call is executed as the sequence, with the same bits. */
+#define EARL_TABLETOP3_EVAL_CHUNK 8
+int earl_tabletop3_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t episodes, int32_t T,
+                                 const float* act, int64_t act_episode_stride, const earl_tabletop_out* out, earl_stream_t stream);
+
 /* The closed loop of the 3-object variant in ONE launch: earl_tabletop_population_rollout's general form on qpos [n,8] and the 20-wide observation -- the
  * deterministic policy (head == NULL: policy->dims[n_layers] == 3) or the Gaussian head (head != NULL: == 6), one policy (pop == NULL) or a population, [T] outputs
  * and / or per-episode summaries (summary == NULL: none).  policy->dims[0] == EARL_TABLETOP3_OBS_DIM; everything else is the argument contract above (float32
@@ -366,6 +381,9 @@ int earl_tabletop3_step_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_st
 int earl_tabletop3_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t T, const float* act, const earl_tabletop_out* out);
 int earl_tabletop3_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, float* obs);
 int earl_tabletop3_reward_cpu(int32_t n, const float* obs, int32_t reward_type, float* reward, uint8_t* success);
+/* host twin of earl_tabletop3_eval_episodes: the plain loop, per episode earl_tabletop3_reset_cpu then earl_tabletop3_rollout_cpu */
+int earl_tabletop3_eval_episodes_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t episodes, int32_t T,
+                                     const float* act, int64_t act_episode_stride, const earl_tabletop_out* out);
 /* host twin of earl_tabletop3_policy_rollout: the same plain loops as the single-object twins, on the 20-wide observation; bit-identical under the sparse reward */
 int earl_tabletop3_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy,
                                       const earl_policy_population* pop, const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first,
@@ -382,6 +400,9 @@ const char* earl_host_last_error(void);
  * lifelong switching and auto-reset are off and all four outputs are requested), 1 = always the plain
  * one-lane-per-env kernel.  Both produce bit-identical outputs.  Returns the previous setting. */
 int earl_debug_set_rollout_impl(int impl);
+/* Test/bench hook: the launch form of earl_tabletop3_eval_episodes.  0 = automatic, 1 = always the sequence of existing kernels, 2 = fused, but all episodes
+ * on one group of workgroups (no episodes in flight).  All three produce bit-identical results.  Returns the previous setting. */
+int earl_debug_set_rollout3_form(int form);
 int earl_debug_set_rollout_wgs_per_cu(int k);
 /* Diagnostic: per-workgroup cycle sums of the instrumented rollout variant (impl 9); blocks until the copy is done. */
 int earl_debug_read_ws_profile(uint64_t* out, int32_t n_words);

@@ -171,6 +171,8 @@ SIGNATURES = {
                                       _P(TabletopOut), C.c_void_p, _P(EpisodeSummary), C.c_void_p],
     'earl_tabletop3_pair_rollout': [_P(TabletopCfg), _P(TabletopState), _P(MlpPolicy), _P(AgentPair), _P(GaussianHead), C.c_int32, C.c_int32, C.c_int32, _P(TabletopOut),
                                     C.c_void_p, C.c_void_p],
+    'earl_tabletop_branch_rollout': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _P(EpisodeSummary), C.c_void_p, C.c_void_p],
+    'earl_tabletop3_branch_rollout': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _P(EpisodeSummary), C.c_void_p, C.c_void_p],
     'earl_debug_set_rollout_impl': [C.c_int],
     'earl_debug_set_rollout3_form': [C.c_int],
     'earl_debug_set_rollout_wgs_per_cu': [C.c_int],

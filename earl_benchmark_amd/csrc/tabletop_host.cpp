@@ -102,9 +102,45 @@ int do_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int3
   return EARL_OK;
 }
 
+// The branch launch on the host: one OpenMP iteration per (branch, tile of kTile envs) of the flattened range -- the device's workgroups -- each env of a tile through
+// branch_body, the function the kernel runs.
+template <int NOBJ>
+int do_branch(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t stride,
+              const earl_episode_summary* summary, float* last_obs) {
+  long long blocks;
+  if (int rc = check_branch(cfg, st, NOBJ, K, H, act, stride, summary, last_obs, &blocks)) return rc;
+  if (blocks == 0) return EARL_OK;
+  static_assert(kTile == kBranchBlock, "a tile of the twin is a workgroup of the device launch");
+  const BranchArgs b{KArgs{*cfg, *st, earl_tabletop_out{nullptr, nullptr, nullptr, nullptr, nullptr}, act, nullptr, nullptr, nullptr, H, thresholds()},
+                     (long long)stride, summary ? *summary : earl_episode_summary{nullptr, nullptr, nullptr}, last_obs};
+  const long long tiles = blocks / K;
+  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  const int n = cfg->n;
+#pragma omp parallel for schedule(static) if (blocks >= 4)
+  for (long long j = 0; j < blocks; ++j) {
+    const int k = (int)(j / tiles);
+    const long long i0 = (j - k * tiles) * kTile;
+    const int m = n - i0 < kTile ? (int)(n - i0) : kTile;
+    for (int i = (int)i0; i < (int)i0 + m; ++i) {
+      if (general) branch_body<NOBJ, true>(b, i, k);
+      else branch_body<NOBJ, false>(b, i, k);
+    }
+  }
+  return EARL_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int earl_tabletop_branch_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
+                                     const earl_episode_summary* summary, float* last_obs) {
+  return do_branch<1>(cfg, st, K, H, act, act_branch_stride, summary, last_obs);
+}
+int earl_tabletop3_branch_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
+                                      const earl_episode_summary* summary, float* last_obs) {
+  return do_branch<3>(cfg, st, K, H, act, act_branch_stride, summary, last_obs);
+}
 
 int earl_tabletop_step_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const float* act, const int32_t* next_goal_idx,
                            const earl_tabletop_out* out) {

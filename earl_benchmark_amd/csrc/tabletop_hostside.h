@@ -80,6 +80,25 @@ inline int check_common(const earl_tabletop_cfg* cfg, const earl_tabletop_state*
   return EARL_OK;
 }
 
+// The argument rules of earl_tabletop[3]_branch_rollout and of its host twin (include/earl_tabletop.h), in the header's order.  The device launch is a 1-D grid
+// of K * ceil(n / kBranchBlock) workgroups of kBranchBlock lanes; the twin refuses the grids the device refuses.  *blocks = that count (0: nothing to do).
+constexpr int kBranchBlock = 64;
+inline int check_branch(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int nobj, int32_t K, int32_t H, const float* act, int64_t stride,
+                        const earl_episode_summary* summary, const float* last_obs, long long* blocks) {
+  *blocks = 0;
+  if (int rc = check_common(cfg, st, nobj)) return rc;
+  if (!act) return fail(EARL_ERR_ARG, "act is NULL");
+  if (K < 0) return fail(EARL_ERR_ARG, "K = %d < 0", K);
+  if (H < 0) return fail(EARL_ERR_ARG, "H = %d < 0", H);
+  if (stride < 0) return fail(EARL_ERR_ARG, "negative action stride");
+  if (stride != 0 && stride < (int64_t)H * cfg->n * 3) return fail(EARL_ERR_ARG, "action stride %lld is neither 0 nor >= H * n * 3 = %lld", (long long)stride, (long long)H * cfg->n * 3);
+  if (!summary && !last_obs) return fail(EARL_ERR_ARG, "summary and last_obs are both NULL");
+  const long long tiles = ((long long)cfg->n + kBranchBlock - 1) / kBranchBlock, nb = tiles * K;
+  if (nb > 0x7fffffffll || nb * kBranchBlock > 0xffffffffll)
+    return fail(EARL_ERR_ARG, "K = %d branches of %lld workgroups do not fit one launch (2^31 - 1 workgroups, 2^32 - 1 lanes)", K, tiles);
+  if (H > 0) *blocks = nb;
+  return EARL_OK;
+}
 
 }  // namespace hostside
 }  // namespace earl

@@ -180,6 +180,61 @@ __device__ __forceinline__ void rollout_body(const KArgs& a, int i) {
   store_lane<NOBJ>(a, i, L);
 }
 
+// earl_tabletop[3]_branch_rollout: K candidate action sequences per env, scored from the CURRENT state.  `a` is the rollout's argument block (T = the horizon
+// H of a branch, `out` unused, `st` read and never written); the rest is what a branch adds.
+struct BranchArgs {
+  KArgs a;
+  long long act_branch_stride;  // floats between the [H, n, 3] blocks of consecutive branches; 0 = one block for all
+  earl_episode_summary sum;     // rows [K, n]; any pointer may be NULL
+  float* last_obs;              // NULL or [K, n, NOBS]: the row out->obs[H-1] of the equivalent rollout
+};
+
+// Branch k of env i: rollout_body's loop (same loads, same prefetch, same wrapped_step, same counters) with the per-step stores replaced by the three
+// reducers of earl_episode_summary held in registers, and without store_lane -- the state is where it was when the launch ends.
+template <int NOBJ, bool GENERAL>
+__device__ __forceinline__ void branch_body(const BranchArgs& b, int i, int k) {
+  const KArgs& a = b.a;
+  const int n = a.cfg.n;
+  Lane<NOBJ> L;
+  load_lane<NOBJ>(a, i, L);
+  float g[Dims<NOBJ>::NG];
+  load_goal<NOBJ>(a.st.goal_table, L.goal_idx, g);
+  const float* act = a.act + (size_t)k * (size_t)b.act_branch_stride;
+  double ret = 0.0;
+  bool succ_last = false;
+  int first = -1;
+  float o[Dims<NOBJ>::NOBS] = {};
+  constexpr int PF = 8;  // as rollout_body: the actions are state-independent
+  for (int t0 = 0; t0 < a.T; t0 += PF) {
+    float av[PF][3];
+#pragma unroll
+    for (int j = 0; j < PF; ++j) {
+      const int t = t0 + j < a.T ? t0 + j : a.T - 1;
+      const float* ap = act + ((size_t)t * n + i) * 3;
+      av[j][0] = ap[0];
+      av[j][1] = ap[1];
+      av[j][2] = ap[2];
+    }
+#pragma unroll
+    for (int j = 0; j < PF; ++j) {
+      const int t = t0 + j;
+      if (t < a.T) {
+        float reward;
+        bool done, succ;
+        wrapped_step<NOBJ, GENERAL>(a, i, a.cfg.counter + (uint64_t)t, L, g, av[j][0], av[j][1], av[j][2], o, reward, done, succ);
+        ret += (double)reward;
+        succ_last = succ;
+        if (succ && first < 0) first = t;
+      }
+    }
+  }
+  const size_t row = (size_t)k * n + i;
+  if (b.sum.ret) b.sum.ret[row] = ret;
+  if (b.sum.success_last) b.sum.success_last[row] = succ_last;
+  if (b.sum.first_success) b.sum.first_success[row] = first;
+  if (b.last_obs) store_obs<NOBJ>(b.last_obs + row * Dims<NOBJ>::NOBS, o);
+}
+
 template <int NOBJ>
 __device__ __forceinline__ void reset_body(const KArgs& a, int i) {
   Lane<NOBJ> L;

@@ -474,6 +474,43 @@ class TabletopManipulation:
     self._last_success = outs[3][-1]
     return outs
 
+  def rollout_branches(self, actions, last_obs=True, out=None):
+    """K candidate action sequences of H steps scored per env FROM THE CURRENT STATE in one kernel launch (include/earl_tabletop.h:
+    earl_tabletop_branch_rollout): actions [K, H, N, 3] -> {'ret' [K, N] float64, 'success' [K, N] bool (the success of step H - 1), 'first_success' [K, N]
+    int32 (-1: none), 'last_obs' [K, N, D] float32}.  Row k is what rollout(actions[k]) would return next, reduced (ret = the float64 sum of its float32
+    rewards), lifelong goal draws and auto-reset draws included; the env is left exactly as found -- state, counters, the Philox counter.  What a shooting
+    planner (random shooting, CEM, MPPI) asks for.  `last_obs=False` leaves that array out.  `out`: an optional dict of preallocated tensors under the same
+    keys; a key that is missing or None is not computed."""
+    a = torch.as_tensor(actions, device=self.device)
+    n = self.num_envs
+    if a.dim() != 4 or a.shape[2] != n or a.shape[3] != 3:
+      raise ValueError(f'rollout_branches: actions must be [K, H, N, 3] = [K, H, {n}, 3], got {list(a.shape)} (one plan for every env is [1, H, {n}, 3])')
+    K, H = int(a.shape[0]), int(a.shape[1])
+    kw = dict(device=self.device)
+    want = {'ret': ((K, n), torch.float64), 'success': ((K, n), torch.bool), 'first_success': ((K, n), torch.int32),
+            'last_obs': ((K, n, self.OBS_DIM), torch.float32)}
+    if out is None:
+      res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items() if k != 'last_obs' or last_obs}
+    else:
+      if set(out) - set(want):
+        raise ValueError(f'rollout_branches: out holds {sorted(set(out) - set(want))}; the keys are {list(want)}')
+      res = {k: t for k, t in out.items() if t is not None}
+      for k, t in res.items():
+        shape, dt = want[k]
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+          raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
+    if not res:
+      raise ValueError('rollout_branches: nothing to compute (every key of out is missing or None)')
+    if K == 0 or H == 0:                                             # (the entry point writes nothing then: no branch, or no step to reduce)
+      raise ValueError(f'rollout_branches: K = {K}, H = {H}: at least one branch of at least one step')
+    with self._ctx():
+      act = self._actions(a, (K, H, n))
+      summary = _abi.EpisodeSummary(ret=_ptr(res.get('ret')), success_last=_ptr(res.get('success')), first_success=_ptr(res.get('first_success')))
+      fn = self._lib.earl_tabletop_branch_rollout if self.NOBJ == 1 else self._lib.earl_tabletop3_branch_rollout
+      rc = fn(self._cfg_ref, self._st_ref, K, H, act.data_ptr(), H * n * 3, C.byref(summary), _ptr(res.get('last_obs')), self._stream())
+    self._check(rc, 'branch_rollout')
+    return res                                                       # (no counter advance, no step count: nothing happened to the env)
+
   def _observe(self, want=('obs',)):
     kw = dict(device=self.device)
     n = self.num_envs

@@ -345,6 +345,32 @@ int earl_tabletop3_pair_rollout(const earl_tabletop_cfg* cfg, const earl_tableto
                                 const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out,
                                 earl_stream_t stream);
 
+/* ---- branches: K candidate action sequences per env scored FROM THE CURRENT STATE, the state left as it is ----
+ * Every entry point above advances the envs or starts them from a reset.  A shooting planner (random shooting, CEM, MPPI -- the model-predictive control loops
+ * around envs/tabletop_manipulation.py:128-138 that copy the env, step the copy and throw it away: `sim = copy.deepcopy(env); for a in plan: _, r, _, _ =
+ * sim.step(a)`) asks what WOULD happen: K plans of H steps per env, one return and one success flag each, nothing kept.  One launch runs one lane per
+ * (branch, env), reads 12 B of actions per env-step and stores nothing inside the loop.
+ *   equivalence  branch k equals earl_tabletop_rollout(cfg, <a private copy of st>, H, act + k * act_branch_stride, out) with the same cfg->counter, bit for bit:
+ *                step t of EVERY branch uses counter cfg->counter + t, so all branches see the same lifelong goal draws and the same auto-reset draws (common
+ *                random numbers), and a branch predicts exactly what the next real rollout with those actions will produce.
+ *   act          act_branch_stride = H * n * 3: a contiguous [K, H, n, 3] array; 0: every branch replays one [H, n, 3] block.
+ *   summary      NULL, or rows [K, n] with earl_episode_summary's definitions: ret the float64 sum over t ascending of the float32 reward, success_last the
+ *                success of step H - 1, first_success the first step with success or -1.
+ *   last_obs     NULL, or [K, n, 12]: the row out->obs[H - 1] of that rollout, after a goal switch's re-read, exactly as the rollout emits it.
+ *                Each of the four pointers may be NULL in any combination.
+ *   state        `st` is read and never written -- qpos, attached, goal_idx, the four wrapper arrays -- and *counter_base is not read.  The caller does not
+ *                advance its counter.
+ * EARL_ERR_ARG before any HIP call for: everything the other entry points refuse in cfg / st; act NULL; K < 0; H < 0; a negative stride; a stride that is neither 0
+ * nor >= H * n * 3; summary == NULL && last_obs == NULL; a grid that does not fit one launch -- the launch is 1-D, K * ceil(n / EARL_BRANCH_BLOCK) workgroups of
+ * EARL_BRANCH_BLOCK lanes (the branch comes from the workgroup's index: K is a planner's large dimension), and that count may not exceed 2^31 - 1 nor the lanes
+ * 2^32 - 1.  n == 0, K == 0 or H == 0 returns EARL_OK, launches nothing and writes nothing. */
+#define EARL_BRANCH_BLOCK 64
+int earl_tabletop_branch_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
+                                 const earl_episode_summary* summary, float* last_obs, earl_stream_t stream);
+/* the same on the 3-object variant: qpos [n,8], last_obs [K, n, 20], branch k equal to earl_tabletop3_rollout on a private copy of the state (auto-reset included) */
+int earl_tabletop3_branch_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
+                                  const earl_episode_summary* summary, float* last_obs, earl_stream_t stream);
+
 /* ---- host build: the `_cpu` entry points (BASELINE.json configs[0] "1 env, CPU ... plumbing, no GPU") ----
  * csrc/libearl_host.so = the SAME per-env functions the gfx950 kernels run (csrc/tabletop_device.h, tabletop_step.h, philox.h), compiled for the host by
  * g++ with -ffp-contract=off; one OpenMP iteration per env where a kernel has one lane per env.  Same structs, same arguments minus the stream, HOST
@@ -391,7 +417,14 @@ int earl_tabletop3_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_t
 /* host twin of earl_tabletop3_pair_rollout: earl_tabletop_pair_rollout_cpu's loops on the 3-object env; every pointer of `pair` is a HOST pointer; refuses the same shapes */
 int earl_tabletop3_pair_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_agent_pair* pair,
                                     const earl_gaussian_head* head, int32_t episodes, int32_t T, int32_t reset_first, const earl_tabletop_out* out, float* act_out);
-int earl_host_set_threads(int n);        /* OpenMP threads of the calls above (n <= 0: query); returns the count in force */
+/* host twins of earl_tabletop_branch_rollout / earl_tabletop3_branch_rollout: the kernel's per-(branch, env) function, one OpenMP iteration per (branch, 64 envs);
+ * bit-identical to earl_tabletop[3]_rollout_cpu branch by branch under both rewards, and to the device under the sparse one (dense: success_last, first_success
+ * and last_obs bit for bit, ret within 1e-6 relative of the sum of |reward|); they refuse what the device entry points refuse, the grid included */
+int earl_tabletop_branch_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
+                                     const earl_episode_summary* summary, float* last_obs);
+int earl_tabletop3_branch_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
+                                      const earl_episode_summary* summary, float* last_obs);
+int earl_host_set_threads(int n);       /* OpenMP threads of the calls above (n <= 0: query); returns the count in force */
 const char* earl_host_version(void);
 const char* earl_host_last_error(void);
 

@@ -56,6 +56,11 @@ class EpisodeSummary(C.Structure):     # struct earl_episode_summary (include/ea
   _fields_ = [('ret', C.c_void_p), ('success_last', C.c_void_p), ('first_success', C.c_void_p)]
 
 
+class PlanParams(C.Structure):         # struct earl_plan_params (include/earl_tabletop.h)
+  _fields_ = [('K', C.c_int32), ('H', C.c_int32), ('iterations', C.c_int32), ('iteration0', C.c_int32), ('sigma', C.c_float * 3), ('noise_counter', C.c_uint32),
+              ('inv_temperature', C.c_double)]
+
+
 class AgentPair(C.Structure):          # struct earl_agent_pair (include/earl_tabletop.h)
   _fields_ = [('switch_every', C.c_int32 * 2), ('switch_on_success', C.c_int32), ('pad_', C.c_int32), ('param_stride', C.c_int64), ('backward_goal', C.c_void_p),
               ('phase', C.c_void_p), ('steps_in_phase', C.c_void_p), ('agent_out', C.c_void_p), ('forward_success', C.c_void_p), ('backward_success', C.c_void_p)]
@@ -173,6 +178,9 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p],
     'earl_tabletop_branch_rollout': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _P(EpisodeSummary), C.c_void_p, C.c_void_p],
     'earl_tabletop3_branch_rollout': [_P(TabletopCfg), _P(TabletopState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _P(EpisodeSummary), C.c_void_p, C.c_void_p],
+    'earl_tabletop_plan_mppi': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams)] + [C.c_void_p] * 7,
+    'earl_tabletop3_plan_mppi': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams)] + [C.c_void_p] * 7,
+    'earl_tabletop_plan_candidates': [_P(TabletopCfg), _P(PlanParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_debug_set_rollout_impl': [C.c_int],
     'earl_debug_set_rollout3_form': [C.c_int],
     'earl_debug_set_rollout_wgs_per_cu': [C.c_int],

@@ -4,6 +4,7 @@
 // Host pointers, no stream, no HIP runtime.  This library is loaded only when a caller ASKS for device='cpu'; nothing falls back to it,
 // and nothing here touches oracle/ (the oracle is the checker of both builds).
 #include <cstdint>
+#include <vector>
 
 #include "tabletop_hostside.h"
 #include "tabletop_step.h"
@@ -129,9 +130,91 @@ int do_branch(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32
   return EARL_OK;
 }
 
+// The planner on the host (include/earl_tabletop.h, "MPPI planning"): per iteration the score pass over the device's (branch, 64 envs) workgroups, then per env the
+// weights once and per step the integer sums in ascending k -- tabletop_step.h's plan_* functions, the ones the kernels run.
+template <int NOBJ>
+int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* pp, const float* mean, float* plan, double* ret, double* ret0,
+            double* best_ret, int32_t* best_k) {
+  if (!st) return fail(EARL_ERR_ARG, "cfg/state is NULL");
+  long long blocks, ublocks;
+  if (int rc = check_plan(cfg, st, NOBJ, pp, 0, mean, plan, ret, &blocks, &ublocks)) return rc;
+  if (blocks == 0) return EARL_OK;
+  PlanArgs p = plan_args(cfg, st, pp, mean, thresholds());
+  p.plan = plan;
+  p.ret = ret;
+  const int n = cfg->n, K = pp->K, H = pp->H;
+  const long long tiles = blocks / K;
+  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  for (int it = 0; it < pp->iterations; ++it) {
+    const bool last = it + 1 == pp->iterations;
+    p.mean = it ? plan : mean;
+    p.word0 = kPlanDraw | (uint32_t)(pp->iteration0 + it);
+    p.ret0 = ret0 ? ret0 + (size_t)it * n : nullptr;
+#pragma omp parallel for schedule(static) if (blocks >= 4)
+    for (long long b = 0; b < blocks; ++b) {
+      const int k = (int)(b / tiles);
+      const long long i0 = (b - k * tiles) * kTile;
+      const int m = n - i0 < kTile ? (int)(n - i0) : kTile;
+      for (int i = (int)i0; i < (int)i0 + m; ++i) {
+        if (general) plan_score_body<NOBJ, true>(p, i, k);
+        else plan_score_body<NOBJ, false>(p, i, k);
+      }
+    }
+#pragma omp parallel for schedule(static, kChunk) if (n >= 4 * kChunk)
+    for (int i = 0; i < n; ++i) {
+      double beta = -INFINITY;
+      int bk = 0;
+      for (int k = 0; k < K; ++k) plan_best(ret[(size_t)k * n + i], k, beta, bk);
+      std::vector<int32_t> Wk(K);                          // once per (k, env), as the update kernel shares them through LDS
+      for (int k = 0; k < K; ++k) Wk[k] = plan_weight(ret[(size_t)k * n + i], beta, p.inv_temperature);
+      for (int t = 0; t < H; ++t) {
+        float m[3];
+        plan_mean(p, i, t, m);
+        int64_t A[3] = {0, 0, 0}, S = 0;
+        for (int k = 0; k < K; ++k) {
+          const int32_t W = Wk[k];
+          S += W;
+          if (W != 0 && k > 0) plan_accumulate(p, i, (uint32_t)k, (uint32_t)t, m, W, A);
+        }
+        float* dst = plan + ((size_t)t * n + i) * 3;
+        for (int d = 0; d < 3; ++d) dst[d] = plan_new_mean(m[d], A[d], S);
+      }
+      if (last && best_ret) best_ret[i] = beta;
+      if (last && best_k) best_k[i] = bk;
+    }
+  }
+  return EARL_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int earl_tabletop_plan_mppi_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan,
+                                double* ret, double* ret0, double* best_ret, int32_t* best_k) {
+  return do_plan<1>(cfg, st, params, mean, plan, ret, ret0, best_ret, best_k);
+}
+int earl_tabletop3_plan_mppi_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan,
+                                 double* ret, double* ret0, double* best_ret, int32_t* best_k) {
+  return do_plan<3>(cfg, st, params, mean, plan, ret, ret0, best_ret, best_k);
+}
+int earl_tabletop_plan_candidates_cpu(const earl_tabletop_cfg* cfg, const earl_plan_params* params, int32_t j, const float* mean, float* act_out) {
+  long long blocks, ublocks;
+  if (int rc = check_plan(cfg, nullptr, 1, params, j, mean, act_out, nullptr, &blocks, &ublocks)) return rc;
+  if (blocks == 0) return EARL_OK;
+  PlanArgs p = plan_args(cfg, nullptr, params, mean, thresholds());
+  p.word0 = kPlanDraw | (uint32_t)j;
+  const long long tiles = blocks / params->K;
+  const int n = cfg->n;
+#pragma omp parallel for schedule(static) if (blocks >= 4)
+  for (long long b = 0; b < blocks; ++b) {
+    const int k = (int)(b / tiles);
+    const long long i0 = (b - k * tiles) * kTile;
+    const int m = n - i0 < kTile ? (int)(n - i0) : kTile;
+    for (int i = (int)i0; i < (int)i0 + m; ++i) plan_candidates_body(p, i, k, act_out);
+  }
+  return EARL_OK;
+}
 
 int earl_tabletop_branch_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
                                      const earl_episode_summary* summary, float* last_obs) {

@@ -100,5 +100,47 @@ inline int check_branch(const earl_tabletop_cfg* cfg, const earl_tabletop_state*
   return EARL_OK;
 }
 
+// The argument rules of earl_tabletop[3]_plan_mppi, of earl_tabletop_plan_candidates (st == NULL, j = the iteration: no env state, no iteration range, no
+// temperature, `out` = act_out) and of their host twins, in the header's order.  *blocks = the score launch's workgroups, *ublocks = the update launch's
+// (kPlanUpdateSteps waves of kBranchBlock envs each); both 0 when n == 0.
+constexpr int kPlanUpdateSteps = EARL_PLAN_UPDATE_STEPS;
+inline int check_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int nobj, const earl_plan_params* p, int32_t j, const float* mean, const void* out,
+                      const double* ret, long long* blocks, long long* ublocks) {
+  *blocks = *ublocks = 0;
+  if (st) {
+    if (int rc = check_common(cfg, st, nobj)) return rc;
+  } else {
+    if (!cfg) return fail(EARL_ERR_ARG, "cfg is NULL");
+    if (cfg->n < 0) return fail(EARL_ERR_ARG, "n = %d < 0", cfg->n);
+  }
+  if (!p) return fail(EARL_ERR_ARG, "params is NULL");
+  if (!mean || !out) return fail(EARL_ERR_ARG, st ? "mean/plan is NULL" : "mean/act_out is NULL");
+  if (st && !ret) return fail(EARL_ERR_ARG, "ret is NULL: it is the workspace between the score and the update launch");
+  if (p->K < 1 || p->K > 65536) return fail(EARL_ERR_ARG, "K = %d: 1 .. 65536", p->K);
+  if (p->H < 1 || p->H > 65536) return fail(EARL_ERR_ARG, "H = %d: 1 .. 65536", p->H);
+  if (st) {
+    if (p->iterations < 1 || p->iteration0 < 0 || (long long)p->iteration0 + p->iterations > 256)
+      return fail(EARL_ERR_ARG, "iterations = %d from iteration0 = %d: at least one, inside 0 .. 255", p->iterations, p->iteration0);
+    if (!std::isfinite(p->inv_temperature) || !(p->inv_temperature > 0)) return fail(EARL_ERR_ARG, "inv_temperature = %g: finite and > 0", p->inv_temperature);
+  } else if (j < 0 || j > 255) {
+    return fail(EARL_ERR_ARG, "iteration %d: 0 .. 255", j);
+  }
+  for (int d = 0; d < 3; ++d)
+    if (!std::isfinite(p->sigma[d]) || !(p->sigma[d] >= 0)) return fail(EARL_ERR_ARG, "sigma[%d] = %g: finite and >= 0", d, (double)p->sigma[d]);
+  const long long tiles = ((long long)cfg->n + kBranchBlock - 1) / kBranchBlock, nb = tiles * p->K;
+  const long long ub = tiles * ((p->H + kPlanUpdateSteps - 1) / kPlanUpdateSteps);
+  if (nb > 0x7fffffffll || nb * kBranchBlock > 0xffffffffll)
+    return fail(EARL_ERR_ARG, "K = %d branches of %lld workgroups do not fit one launch (2^31 - 1 workgroups, 2^32 - 1 lanes)", p->K, tiles);
+  if (st && (ub > 0x7fffffffll || ub * kBranchBlock * kPlanUpdateSteps > 0xffffffffll))
+    return fail(EARL_ERR_ARG, "H = %d steps of %lld env tiles do not fit the update launch (2^31 - 1 workgroups, 2^32 - 1 lanes)", p->H, tiles);
+  if (st && out != (const void*)mean) {
+    const uintptr_t a = (uintptr_t)mean, b = (uintptr_t)out, bytes = (uintptr_t)p->H * (uintptr_t)cfg->n * 12u;
+    if (a < b + bytes && b < a + bytes) return fail(EARL_ERR_ARG, "plan overlaps mean without being the same array");
+  }
+  *blocks = nb;
+  *ublocks = ub;
+  return EARL_OK;
+}
+
 }  // namespace hostside
 }  // namespace earl

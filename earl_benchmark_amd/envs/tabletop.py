@@ -511,6 +511,81 @@ class TabletopManipulation:
     self._check(rc, 'branch_rollout')
     return res                                                       # (no counter advance, no step count: nothing happened to the env)
 
+  def _plan_params(self, who, K, H, iterations, iteration0, sigma, temperature, noise_counter):
+    s = torch.as_tensor(sigma, dtype=torch.float32).reshape(-1).tolist()
+    if len(s) not in (1, 3):
+      raise ValueError(f'{who}: sigma is a number or three, one per action dimension')
+    if not temperature > 0:
+      raise ValueError(f'{who}: temperature = {temperature} must be > 0')
+    nc = self._cfg.counter if noise_counter is None else int(noise_counter)   # (None: the low word of the env's Philox counter -- fresh noise per control step)
+    return _abi.PlanParams(K=int(K), H=int(H), iterations=int(iterations), iteration0=int(iteration0), sigma=(C.c_float * 3)(*(s * 3 if len(s) == 1 else s)),
+                           noise_counter=nc & 0xFFFFFFFF, inv_temperature=1.0 / float(temperature))
+
+  def _plan_mean(self, who, mean, horizon):
+    n = self.num_envs
+    if mean is None:
+      if horizon is None:
+        raise ValueError(f'{who}: give mean [H, N, 3] or horizon')
+      return torch.zeros(int(horizon), n, 3, dtype=torch.float32, device=self.device)
+    m = torch.as_tensor(mean, device=self.device)
+    if m.dim() != 3 or m.shape[1] != n or m.shape[2] != 3 or (horizon is not None and m.shape[0] != horizon):
+      raise ValueError(f'{who}: mean must be [H, N, 3] = [{"H" if horizon is None else horizon}, {n}, 3], got {list(m.shape)}')
+    return self._actions(m, (int(m.shape[0]), n))
+
+  def plan_mppi(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, out=None):
+    """`iterations` MPPI iterations on the device from the CURRENT state (include/earl_tabletop.h: earl_tabletop_plan_mppi): K candidates per env -- the mean plan
+    itself and K - 1 copies with clipped Gaussian noise of scale `sigma` (a number or three) -- scored as rollout_branches scores them, the mean moved to their
+    average under the weights exp((ret - max ret) / temperature).  The candidates are never in memory: the noise is made inside the scoring kernel and made again
+    inside the update.  mean [H, N, 3] (None: zeros of [horizon, N, 3]) -> {'plan' [H, N, 3] float32, 'ret' [K, N] float64 (the last iteration's returns),
+    'ret0' [iterations, N] float64 (the return of the plan entering each iteration), 'best_ret' [N] float64, 'best_k' [N] int32 (plan_candidates(...)[best_k] is
+    that candidate)}.  `noise_counter=None` takes the low 32 bits of the env's Philox counter, so successive control steps draw fresh noise; `iteration0` numbers
+    the first iteration (iterations in one call == as many calls of one, numbered on).  `out`: an optional dict of preallocated tensors under the same keys; a
+    key that is missing or None is not computed, except 'ret' (the workspace of the call), which is then allocated; out['plan'] may be the `mean` tensor.  The env
+    is left exactly as found -- state, counters, the Philox counter."""
+    m = self._plan_mean('plan_mppi', mean, horizon)
+    n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
+    pp = self._plan_params('plan_mppi', K, H, I, iteration0, sigma, temperature, noise_counter)
+    kw = dict(device=self.device)
+    want = {'plan': ((H, n, 3), torch.float32), 'ret': ((K, n), torch.float64), 'ret0': ((I, n), torch.float64), 'best_ret': ((n,), torch.float64),
+            'best_k': ((n,), torch.int32)}
+    if K < 1 or H < 1 or I < 1:
+      raise ValueError(f'plan_mppi: K = {K}, H = {H}, iterations = {I}: at least one of each')
+    if out is None:
+      res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
+    else:
+      if set(out) - set(want):
+        raise ValueError(f'plan_mppi: out holds {sorted(set(out) - set(want))}; the keys are {list(want)}')
+      res = {k: t for k, t in out.items() if t is not None}
+      for k, t in res.items():
+        shape, dt = want[k]
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+          raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
+      if 'plan' not in res:
+        raise ValueError("plan_mppi: out['plan'] is what the call computes")
+      if 'ret' not in res:
+        res['ret'] = torch.empty(K, n, dtype=torch.float64, **kw)
+    with self._ctx():
+      fn = self._lib.earl_tabletop_plan_mppi if self.NOBJ == 1 else self._lib.earl_tabletop3_plan_mppi
+      rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), m.data_ptr(), res['plan'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
+              _ptr(res.get('best_k')), self._stream())
+    self._check(rc, 'plan_mppi')
+    return res                                                       # (no counter advance, no step count: nothing happened to the env)
+
+  def plan_candidates(self, mean, K, sigma=0.3, iteration=0, noise_counter=None):
+    """the K candidates of plan_mppi's iteration `iteration` around `mean` [H, N, 3], written out: [K, H, N, 3] float32, row 0 the clipped mean -- what
+    rollout_branches takes (earl_tabletop_plan_candidates).  With plan_mppi's `noise_counter` (None: the env's counter, unchanged by plan_mppi) they are the
+    candidates that call scored."""
+    m = self._plan_mean('plan_candidates', mean, None)
+    H = int(m.shape[0])
+    pp = self._plan_params('plan_candidates', K, H, 1, 0, sigma, 1.0, noise_counter)
+    if int(K) < 1 or H < 1:
+      raise ValueError(f'plan_candidates: K = {K}, H = {H}: at least one of each')
+    act = torch.empty(int(K), H, self.num_envs, 3, dtype=torch.float32, device=self.device)
+    with self._ctx():
+      rc = self._lib.earl_tabletop_plan_candidates(self._cfg_ref, C.byref(pp), int(iteration), m.data_ptr(), act.data_ptr(), self._stream())
+    self._check(rc, 'plan_candidates')
+    return act
+
   def _observe(self, want=('obs',)):
     kw = dict(device=self.device)
     n = self.num_envs

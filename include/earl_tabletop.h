@@ -371,6 +371,63 @@ int earl_tabletop_branch_rollout(const earl_tabletop_cfg* cfg, const earl_tablet
 int earl_tabletop3_branch_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
                                   const earl_episode_summary* summary, float* last_obs, earl_stream_t stream);
 
+/* ---- MPPI planning: I iterations of sample -> score -> reweight on the device, the candidates never in memory, the env left as it is ----
+ * The planner the branch launch was made for (model-predictive path integral control around envs/tabletop_manipulation.py:128-138: K noisy copies of a mean plan
+ * rolled out on copies of the env, the mean moved to their exponentially weighted average).  The noise is generated inside the scoring kernel and REGENERATED
+ * inside the update kernel from the same Philox counters, so one iteration reads the [H, n, 3] mean and a [K, n] array of returns and nothing else.  Per
+ * iteration two launches on the caller's stream (score, update); no host synchronisation, no allocation: the call can be captured into a HIP graph.
+ * For iteration j = iteration0 + i (i = 0 .. iterations - 1), env `env` with global id g = cfg->env_offset + env, and the plan entering the iteration `mean`
+ * (the argument for i = 0, the previous iteration's result afterwards):
+ *   1 clipped mean  m[t][d] = clip(mean[t][d]) in float32, clip(x) = (y = x > -1 ? x : -1; y < 1 ? y : 1) = min(max(x, -1), 1).
+ *   2 candidates    branch 0 is the plan itself, a_0 = m.  For k >= 1: a_k[t][d] = clip(fmaf(sigma[d], eps, m[t][d])), eps = normal_quantile_f32(word_d >> 8)
+ *                   (csrc/policy_math.h; exported by the host library as earl_normal_quantile_f32), words x, y, z of ONE Philox4x32-10 block serving d = 0, 1, 2:
+ *                   key = cfg->seed, counter words = {0x504C4E00 | j, g, (k << 16) | t, noise_counter}.  Word 0 collides with no other draw of this library
+ *                   (the envs use 0 .. 2048, the Gaussian head 0x504F4C00).  The draws depend on (seed, g, j, k, t, noise_counter) only: not on n, not on
+ *                   the shard split.
+ *   3 scores        ret[k][env] = earl_episode_summary.ret of earl_tabletop[3]_branch_rollout fed with those candidates: the same wrapped step, step t of every
+ *                   branch at counter cfg->counter + t (common random numbers, lifelong and auto-reset draws included), the float64 sum over t ascending of
+ *                   the float32 reward.
+ *   4 weights       beta = max_k ret[k];  x_k = (float)((ret[k] - beta) * inv_temperature) (two float64 roundings);  w_k = exp_f32(x_k) (csrc/policy_math.h;
+ *                   earl_exp_f32);  W_k = (double)w_k * 2^24 rounded to nearest-even as int64 (0 .. 2^24);  S = sum_k W_k (>= 2^24: the best branch has W = 2^24).
+ *   5 update        delta = a_k[t][d] - m[t][d] (one float32 subtraction);  D_k = (double)delta * 2^20 rounded to nearest-even as int64;  A = sum_k W_k * D_k in
+ *                   int64 (|A| < 2^62 for K <= 2^16);  mean'[t][d] = clip(m[t][d] + (float)((double)A / ((double)S * 2^20))), (double)A rounded to nearest.
+ *                   Integer sums are associative: the result does not depend on how the K branches are spread over lanes, waves and workgroups.
+ *   6 outputs       plan [H, n, 3] float32: the mean after the last iteration; it may be the pointer `mean` itself (the in-place call), any other overlap of
+ *                   the two arrays is refused.  ret [K, n] float64, REQUIRED: the workspace between the two launches; the last iteration's returns on exit.
+ *                   ret0 NULL or [iterations, n] float64: the return of the plan entering each iteration (branch 0).  best_ret NULL or [n] float64: beta of
+ *                   the last iteration.  best_k NULL or [n] int32: the smallest k attaining it (earl_tabletop_plan_candidates recovers that candidate).
+ *   7 non-finite    clip() maps a NaN of `mean` to -1 and +-Inf to +-1, so every candidate is finite whatever `mean` holds.  A NaN return (a NaN in the
+ *                   state under the dense reward) never wins: beta is the largest return that is not NaN, -Inf if there is none; x_k that is NaN (a NaN
+ *                   return, or Inf - Inf) gives W_k = 0; if S == 0 (no branch has a weight) the update is skipped, mean' = m.  best_k is the smallest k
+ *                   with ret[k] == beta when beta > -Inf, and 0 otherwise.  Nothing of this faults, and `st` is never written.
+ *   chaining        `iterations` iterations in one call equal that many calls with iterations = 1 and iteration0 = j, each fed the previous plan, bit for bit.
+ *   state           `st` is read and never written, *counter_base is not read, and the caller does not advance its counter: the env is as earl_tabletop_branch_rollout
+ *                   leaves it.
+ * EARL_ERR_ARG before any HIP call for: everything the other entry points refuse in cfg / st; params, mean, plan or ret NULL; K or H outside 1 .. 65536;
+ * iterations < 1, iteration0 < 0, iteration0 + iterations > 256; a sigma that is negative or not finite; an inv_temperature that is not finite or <= 0; plan
+ * overlapping mean without being equal to it; a grid that does not fit: the score launch is the branch launch's (K * ceil(n / 64) workgroups, earl_tabletop_branch_rollout's
+ * limits), the update launch ceil(n / 64) * ceil(H / EARL_PLAN_UPDATE_STEPS) workgroups of 64 * EARL_PLAN_UPDATE_STEPS lanes under the same two limits.
+ * n == 0 returns EARL_OK, launches nothing and writes nothing. */
+typedef struct earl_plan_params {
+  int32_t K;               /* candidates per env, branch 0 (the plan itself) included: 1 .. 65536 */
+  int32_t H;               /* steps of a plan: 1 .. 65536 */
+  int32_t iterations;      /* I >= 1 */
+  int32_t iteration0;      /* index of the first iteration (a word of the noise counter): >= 0, iteration0 + iterations <= 256 */
+  float sigma[3];          /* noise scale per action dimension, finite, >= 0 */
+  uint32_t noise_counter;  /* a word of the noise counter: a fresh value per control step gives fresh noise */
+  double inv_temperature;  /* 1 / lambda, finite, > 0 */
+} earl_plan_params;
+#define EARL_PLAN_UPDATE_STEPS 8
+int earl_tabletop_plan_mppi(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan, double* ret,
+                            double* ret0, double* best_ret, int32_t* best_k, earl_stream_t stream);
+/* the same on the 3-object variant (qpos [n,8]; scores equal to earl_tabletop3_branch_rollout's) */
+int earl_tabletop3_plan_mppi(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan, double* ret,
+                             double* ret0, double* best_ret, int32_t* best_k, earl_stream_t stream);
+/* Item 2 written out for ONE iteration j (0 .. 255): act_out [K, H, n, 3] float32, what earl_tabletop[3]_branch_rollout takes.  It reads cfg->n, env_offset and seed
+ * and params->K, H, sigma and noise_counter only (no env state: one entry point serves both envs).  EARL_ERR_ARG for cfg, params, mean or act_out NULL, n < 0, K or
+ * H outside 1 .. 65536, j outside 0 .. 255, a bad sigma and the branch launch's grid limits; n == 0 returns EARL_OK and writes nothing. */
+int earl_tabletop_plan_candidates(const earl_tabletop_cfg* cfg, const earl_plan_params* params, int32_t j, const float* mean, float* act_out, earl_stream_t stream);
+
 /* ---- host build: the `_cpu` entry points (BASELINE.json configs[0] "1 env, CPU ... plumbing, no GPU") ----
  * csrc/libearl_host.so = the SAME per-env functions the gfx950 kernels run (csrc/tabletop_device.h, tabletop_step.h, philox.h), compiled for the host by
  * g++ with -ffp-contract=off; one OpenMP iteration per env where a kernel has one lane per env.  Same structs, same arguments minus the stream, HOST
@@ -424,7 +481,15 @@ int earl_tabletop_branch_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_ta
                                      const earl_episode_summary* summary, float* last_obs);
 int earl_tabletop3_branch_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
                                       const earl_episode_summary* summary, float* last_obs);
-int earl_host_set_threads(int n);       /* OpenMP threads of the calls above (n <= 0: query); returns the count in force */
+/* host twins of earl_tabletop[3]_plan_mppi and earl_tabletop_plan_candidates: the kernels' per-lane functions (csrc/tabletop_step.h) in plain loops, the integer sums
+ * in ascending k.  Bit-identical to the device in every output under the sparse reward; under the dense one ret / ret0 / best_ret within the branch launch's bound
+ * (1e-6 relative of the sum of |reward|) and the plans not comparable.  They refuse what the device entry points refuse, the grids included. */
+int earl_tabletop_plan_mppi_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan,
+                                double* ret, double* ret0, double* best_ret, int32_t* best_k);
+int earl_tabletop3_plan_mppi_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan,
+                                 double* ret, double* ret0, double* best_ret, int32_t* best_k);
+int earl_tabletop_plan_candidates_cpu(const earl_tabletop_cfg* cfg, const earl_plan_params* params, int32_t j, const float* mean, float* act_out);
+int earl_host_set_threads(int n);      /* OpenMP threads of the calls above (n <= 0: query); returns the count in force */
 const char* earl_host_version(void);
 const char* earl_host_last_error(void);
 

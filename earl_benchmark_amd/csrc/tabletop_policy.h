@@ -6,8 +6,8 @@
 // member's parameters) with per-episode summaries (earl_tabletop_population_rollout) are instantiated in tabletop_policy_population.hip; the kernel body the
 // three units share is tabletop_policy_kernel.inc.  The THREE-object env's closed loop (20 -> hidden (-> hidden) -> 3 or 6, one policy or a population, summaries:
 // earl_tabletop3_policy_rollout) is the same body with NOBJ = 3, instantiated in tabletop3_policy.hip; the env's side below (policy_episode_begin, policy_env_step) and the host
-// twin's loops take the object count as a template argument.  The agent pair's env side (pair_env_step and its neighbours) takes it too: earl_tabletop_pair_rollout is
-// tabletop_policy_pair.hip, the three-object env's earl_tabletop3_pair_rollout tabletop3_pair.hip.
+// twin's loops take the object count as a template argument.  The agent pair's env side (pair_env_step and its neighbours) takes it too, and so does its kernel, one text
+// for both envs (tabletop_pair_kernel.h): earl_tabletop_pair_rollout is its NOBJ = 1 in tabletop_policy_pair.hip, earl_tabletop3_pair_rollout its NOBJ = 3 in tabletop3_pair.hip.
 //
 // The policy arithmetic is a contract, stated here once for both builds:
 //   pre-activation   acc = b_j;  for k = 0 .. K-1 ascending:  acc = fmaf(x_k, W_jk, acc)     (float32, one rounding per fused multiply-add)
@@ -52,7 +52,7 @@ struct PopulationArgs : GaussianPolicyArgs {
 struct PairArgs : GaussianPolicyArgs {
   earl_agent_pair pair;
 };
-// the widest second hidden layer of an agent pair: two weight sets share the 512 registers of one wave per SIMD (tabletop_policy_pair.hip has the table)
+// the widest second hidden layer of an agent pair: two weight sets share the 512 registers of one wave per SIMD (tabletop_pair_kernel.h has the table)
 constexpr int kPairMaxH2 = EARL_PAIR_MAX_H2;
 // the per-episode summary of one env, kept in registers over the T steps (earl_episode_summary)
 struct EpisodeSum {
@@ -187,9 +187,8 @@ __device__ __forceinline__ void policy_env_step(const PolicyArgs& a, int i, int 
 }
 
 // ------------------------------------------------------------------------------------------------
-// The agent pair (include/earl_tabletop.h: earl_tabletop_pair_rollout; NOBJ = 3: earl_tabletop3_pair_rollout), the env's side, shared by the kernels' env lanes
-// (tabletop_policy_pair.hip, tabletop3_pair.hip) and the
-// host loop: the phase state of one env and what a step does to it.  The order of pair_env_step IS the contract of record's items 3 .. 6.
+// The agent pair (include/earl_tabletop.h: earl_tabletop_pair_rollout; NOBJ = 3: earl_tabletop3_pair_rollout), the env's side, shared by the kernel's env lanes
+// (tabletop_pair_kernel.h) and the host loop: the phase state of one env and what a step does to it.  The order of pair_env_step IS the contract of record's items 3 .. 6.
 // ------------------------------------------------------------------------------------------------
 struct PairLane {
   int phase;   // 0 forward, 1 reset

@@ -3,8 +3,8 @@
 // int NOBJ (1, or 3: the three-object env -- Lane<3>, 20 observations, five k-steps of layer 0, the LDS images after the observation's moved up), and the kernel argument `a`.
 // It is text, not a function: routed through a __forceinline__ function the single-policy kernels compile to different register allocations
 // (profiles/policy_kernel_resources.txt), and their twenty instantiations are to stay exactly what they were.
-// TWIN: tabletop_policy_pair.hip restates this step body (layer 0, hidden layer, output chain, head, fence) per agent; the pair's actions are held bit for bit to
-// this chain, so a change to the arithmetic or its order here is mirrored there by hand (tests/test_policy_pair.py, test 1, compares the two).
+// TWIN: tabletop_pair_kernel.h restates this step body (layer 0, hidden layer, output chain, head, fence) per agent, once for both envs; the pair's actions are held bit
+// for bit to this chain, so a change to the arithmetic or its order here is mirrored there by hand (tests/test_policy_pair.py and tests/test_tabletop3_pair.py, test 1, compare the two).
   constexpr int NOBS = Dims<NOBJ>::NOBS, KS0 = NOBS / 4;               // layer 0's K and its k-steps (12: 3, 20: 5; no padding)
   constexpr int XS = kPolicyEnvsPerWg * (NOBS - 12);                   // floats by which the wider observation image moves everything behind it
   constexpr int NOUT = GAUSS ? 6 : 3, ACTW = GAUSS ? 8 : 4, WO_OFF = (GAUSS ? kPolWoG : kPolWo) + XS;

@@ -139,6 +139,11 @@ class Unit:
     return {k: [len(b), digest(b)] for k, b in self.functions.items()}
 
   @functools.cached_property
+  def nameless_digests(self):
+    """`digests` with each function's own mangled name in its body (the .amdhsa_kernel and .section lines) replaced by a fixed token: comparable across a rename"""
+    return {k: [len(b), digest([ln.replace(k, 'OWN_NAME') for ln in b])] for k, b in self.functions.items()}
+
+  @functools.cached_property
   def resources(self):
     """{demangled kernel name: dict(vgpr, agpr, scratch, occupancy, lds, sgpr)}"""
     count = sgprs(self.asm)

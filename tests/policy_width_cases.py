@@ -2,7 +2,7 @@
 instantiation and every width, and the host twin alone meets the sensitivity condition on every case) and tests/test_policy_widths_gpu.py /
 tests/test_sawyer_policy_widths_gpu.py (the device against the host twin on these cases).
 
-The launchers' dispatch rule, restated (csrc/tabletop_policy.hip, tabletop_policy_gaussian.hip, tabletop_policy_population.hip, tabletop_policy_pair.hip):
+The launchers' dispatch rule, restated (csrc/tabletop_policy.hip, tabletop_policy_gaussian.hip, tabletop_policy_population.hip, tabletop_pair_kernel.h):
   NT2     = ceil(dims[2] / 64) with two hidden layers, 0 with one              (the pair: 0 .. 2, EARL_PAIR_MAX_H2 = 128)
   GENERAL = goal_change_frequency > 0 or auto_reset                           (the pair: always)
   GAUSS   = a head is given
@@ -45,9 +45,9 @@ def instantiation(entry, hidden, cfg_kw, head):
 
 def name_of(inst):
   entry, nt2, general, gauss = inst
-  kernel = {'single': 'policy_rollout_kernel', 'population': 'policy_population_kernel', 'pair': 'policy_pair_kernel'}[entry]
+  kernel = {'single': 'policy_rollout_kernel', 'population': 'policy_population_kernel', 'pair': 'pair_kernel'}[entry]
   if entry == 'pair':                                                   # (no GENERAL parameter: the pair's step is always the general one)
-    return f'{kernel}<NT2 = {nt2}, GAUSS = {str(gauss).lower()}>'
+    return f'{kernel}<NOBJ = 1, NT2 = {nt2}, GAUSS = {str(gauss).lower()}>'
   return f'{kernel}<NT2 = {nt2}, GENERAL = {str(general).lower()}, GAUSS = {str(gauss).lower()}>'
 
 

@@ -1,4 +1,4 @@
-"""The width and instantiation matrix of the tabletop policy kernels on the MI355X (csrc/tabletop_policy.h, tabletop_policy_kernel.inc, tabletop_policy_pair.hip):
+"""The width and instantiation matrix of the tabletop policy kernels on the MI355X (csrc/tabletop_policy.h, tabletop_policy_kernel.inc, tabletop_pair_kernel.h):
 every hidden width 16 .. 256 at every layer position and every one of the 46 instantiations (single 10 + Gaussian 10 + population 20 + pair 6) runs on the device
 and is held to the host twin bit for bit -- actions, draws, observations, rewards, flags, the state left behind -- on the smallest launch that has a full, a middle
 and a ragged workgroup (n = 40, env_offset = 3, T = 12).  tests/policy_width_cases.py holds the tables; tests/test_policy_math.py shows without a GPU that they
@@ -74,7 +74,7 @@ def test_population_device_equals_host_twin_bit_for_bit(hidden, head, form):
 # ---------------------------------------------------------------------------------------------------------------- 3. the pair kernel, every width it takes
 @pytest.mark.parametrize('hidden,head', W.PAIR_CASES, ids=lambda v: 'x'.join(map(str, v)) if isinstance(v, tuple) else v)
 def test_pair_device_equals_host_twin_bit_for_bit(hidden, head):
-  """switch_every = (7, 5), switch_on_success = 1, T = 12: both clocks run out inside the launch.  Dispatch: policy_pair_kernel<NT2, GAUSS>, NT2 = 0 for the 16
+  """switch_every = (7, 5), switch_on_success = 1, T = 12: both clocks run out inside the launch.  Dispatch: pair_kernel<NOBJ = 1, NT2, GAUSS>, NT2 = 0 for the 16
   one-hidden-layer widths, 1 for H2 16 .. 64, 2 for H2 80 .. 128 and (128, 128): its 6 instantiations.  Observed (one MI355X): no difference on any of the 50 cases"""
   inst = W.instantiation('pair', hidden, {}, head)
   (got, end_d, ps_d), (want, end_h, ps_h) = W.pair_run(GPU, hidden, head), W.pair_run(CPU, hidden, head)

@@ -10,7 +10,8 @@ Without a GPU, through csrc/libearl_host.so (the host twin) -- and csrc/libearl_
   7. every argument error from both libraries; n = 0;
   8. AgentPair(obs_dim=20, act_dim=3) and TabletopManipulation3Obj.rollout_agents on device='cpu'; the pinned refusals (the one test here that also passes without
      the entry point: it pins what must not change);
-  9. the six kernels of csrc/tabletop3_pair.hip: no scratch, within 512 registers, the figures on record (cross-compiled).
+  9. the six kernels of csrc/tabletop3_pair.hip: no scratch, within 512 registers, the figures on record; the twelve kernels of csrc/tabletop_pair_kernel.h (this unit's
+     and csrc/tabletop_policy_pair.hip's) are instruction for instruction the kernels of the build before they became one text (cross-compiled).
 tests/test_tabletop3_pair_gpu.py holds the device to the host twin bit for bit."""
 import ctypes as C
 import re
@@ -504,15 +505,33 @@ def test_wrappers_forward_and_the_lifelong_wrapper_refuses():
 def test_the_six_kernels_have_no_scratch_and_the_recorded_figures():
   built = kernel_build.units(('tabletop3_pair.hip', 'tabletop_policy_pair.hip'))
   now = built['tabletop3_pair.hip'].figures
-  assert len(now) == 6 and all('tabletop3_pair_kernel' in k for k in now), sorted(now)      # NT2 in {0, 1, 2} x {deterministic, Gaussian head}
+  assert len(now) == 6 and all('4earl11pair_kernelILi3E' in k for k in now), sorted(now)      # pair_kernel<NOBJ = 3, NT2, GAUSS>: NT2 in {0, 1, 2} x {deterministic, Gaussian head}
   recorded = kernel_build.recorded_figures()
   for name, fig in now.items():
     print(name, fig)
     assert fig[3] == 0, (name, 'scratch', fig[3])
     assert fig[1] + fig[2] <= 512, (name, 'registers', fig[1] + fig[2])
     assert recorded.get(name) == [fig], (name, fig, recorded.get(name))
-  assert [k for k in recorded if 'tabletop3_pair_kernel' in k and k not in now] == []
+  assert [k for k in recorded if ('4earl11pair_kernelILi3E' in k or 'tabletop3_pair_kernel' in k) and k not in now] == []      # (nor a line under the kernel's earlier name)
   single = built['tabletop_policy_pair.hip'].figures                         # the single-object pair keeps its six recorded lines
   assert len(single) == 6
   for name, fig in single.items():
     assert recorded.get(name) == [fig], (name, fig, recorded.get(name))
+
+
+# unit -> (its kernels' names now, their names in the build on record: one __global__ template <NT2, GAUSS> per unit then)
+RENAMED = {'tabletop_policy_pair.hip': ('_ZN4earl11pair_kernelILi1E', '_ZN4earl18policy_pair_kernelI'), 'tabletop3_pair.hip': ('_ZN4earl11pair_kernelILi3E', '_ZN4earl21tabletop3_pair_kernelI')}
+
+
+def test_the_twelve_kernels_are_instruction_for_instruction_the_build_before_they_became_one_text():
+  want = kernel_build.recorded('tabletop_pair_parent_build.json')['kernels']
+  built = kernel_build.units(RENAMED)
+  now = {}
+  for unit, (new, old) in RENAMED.items():
+    for name, dig in built[unit].nameless_digests.items():
+      assert name.startswith(new), (unit, name)                             # (the units hold no other function)
+      now[old + name[len(new):]] = dig
+  assert len(want) == 12 and sorted(now) == sorted(want), (sorted(now), sorted(want))
+  for name in want:
+    print(name, now[name], want[name])
+  assert now == want, sorted(k for k in want if now[k] != want[k])

@@ -8,7 +8,9 @@ time of their own; the shipped kernel's timings are those of tools/policy_rollou
                                                                                           # wave 0 (the draws run on wave 1 under the output layer's phase)
   python tools/prof_policy.py --pair [--out profiles/policy_pair_phases.json]             # the agent-pair kernel with clock-only switching (every workgroup uniform)
                                                                                           # beside the single-policy kernel on the same env form: the probe's
-                                                                                          # legs (k) and (c), continuing form, switch_every = (25, 25)"""
+                                                                                          # legs (k) and (c), continuing form, switch_every = (25, 25).  The stamps
+                                                                                          # are in csrc/tabletop_pair_kernel.h's pair_kernel; the stamped build
+                                                                                          # recompiles the one-object unit only, so they read pair_kernel<1, ..>"""
 import argparse
 import ctypes as C
 import json

@@ -3,11 +3,13 @@
 // (-DEARL_HOST_BUILD: earl_rt.h -> host_shim.h) with -ffp-contract=off, one OpenMP iteration per env where a kernel has one lane per env.
 // Host pointers, no stream, no HIP runtime.  This library is loaded only when a caller ASKS for device='cpu'; nothing falls back to it,
 // and nothing here touches oracle/ (the oracle is the checker of both builds).
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
 #include "tabletop_hostside.h"
 #include "tabletop_step.h"
+#include "tabletop_mpc.h"
 #include "tabletop_policy.h"
 #include "../../include/earl_physics.h"
 
@@ -186,10 +188,92 @@ int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const e
   return EARL_OK;
 }
 
+// The receding-horizon loop on the host (include/earl_tabletop.h, "receding-horizon MPPI control"): one OpenMP iteration per env -- the device's workgroup -- holds
+// the env and its plan for all T steps; per iteration the K scores in ascending k (mpc_score, the kernel's), the weights once, per plan row the integer sums in
+// ascending k; then the real step (mpc_act, the kernel's) and the shift.
+template <int NOBJ, bool GENERAL>
+void mpc_env(const MpcArgs& x, int i) {
+  const KArgs& a = x.p.a;
+  const int n = a.cfg.n, H = a.T, K = x.p.K;
+  std::vector<float> P((size_t)H * 3);
+  for (int t = 0; t < H; ++t)
+    for (int d = 0; d < 3; ++d) P[(size_t)t * 3 + d] = x.m.plan[((size_t)t * n + i) * 3 + d];
+  std::vector<double> ret(K);
+  std::vector<int32_t> Wk(K);
+  Lane<NOBJ> L;
+  load_lane<NOBJ>(a, i, L);
+  float g[Dims<NOBJ>::NG];
+  load_goal<NOBJ>(a.st.goal_table, L.goal_idx, g);
+  PlanArgs q = x.p;
+  auto row = [&](int t, float (&m)[3]) {
+    for (int d = 0; d < 3; ++d) m[d] = plan_clip(P[(size_t)t * 3 + d]);
+  };
+  for (int s = 0; s < x.T; ++s) {
+    const uint64_t counter = a.cfg.counter + (uint64_t)s;
+    q.noise_counter = x.p.noise_counter + (uint32_t)s;
+    for (int it = 0; it < x.iterations; ++it) {
+      q.word0 = kPlanDraw | (uint32_t)(x.iteration0 + it);
+      double beta = -INFINITY;
+      int bk = 0;
+      for (int k = 0; k < K; ++k) {
+        ret[k] = mpc_score<NOBJ, GENERAL>(q, i, k, counter, L, g, row);
+        plan_best(ret[k], k, beta, bk);
+      }
+      if (x.m.ret0) x.m.ret0[((size_t)s * x.iterations + it) * n + i] = ret[0];
+      int64_t S = 0;
+      for (int k = 0; k < K; ++k) S += Wk[k] = plan_weight(ret[k], beta, q.inv_temperature);
+      for (int t = 0; t < H; ++t) {
+        float m[3];
+        row(t, m);
+        int64_t A[3] = {0, 0, 0};
+        for (int k = 1; k < K; ++k)
+          if (Wk[k] != 0) plan_accumulate(q, i, (uint32_t)k, (uint32_t)t, m, Wk[k], A);
+        for (int d = 0; d < 3; ++d) P[(size_t)t * 3 + d] = plan_new_mean(m[d], A[d], S);
+      }
+      if (it + 1 == x.iterations && x.m.best_ret) x.m.best_ret[(size_t)s * n + i] = beta;
+    }
+    const float act[3] = {P[0], P[1], P[2]};
+    const bool done = mpc_act<NOBJ, GENERAL>(x, i, s, counter, L, g, act, true);
+    if (GENERAL && done && a.cfg.auto_reset) {
+      std::fill(P.begin(), P.end(), 0.0f);
+    } else {
+      for (int t = 0; t + 1 < H; ++t)
+        for (int d = 0; d < 3; ++d) P[(size_t)t * 3 + d] = P[(size_t)(t + 1) * 3 + d];
+    }
+  }
+  for (int t = 0; t < H; ++t)
+    for (int d = 0; d < 3; ++d) x.m.plan[((size_t)t * n + i) * 3 + d] = P[(size_t)t * 3 + d];
+  store_lane<NOBJ>(a, i, L);
+}
+
+template <int NOBJ>
+int do_mpc(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* pp, int32_t T, const earl_tabletop_out* out, const earl_mpc_out* mpc) {
+  int lanes;
+  if (int rc = check_mpc(cfg, st, NOBJ, pp, T, out, mpc, &lanes)) return rc;
+  if (lanes == 0) return EARL_OK;
+  const MpcArgs x = mpc_args(cfg, st, pp, T, out, mpc);
+  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  const int n = cfg->n;
+#pragma omp parallel for schedule(dynamic, 1) if (n >= 4)
+  for (int i = 0; i < n; ++i) {
+    if (general) mpc_env<NOBJ, true>(x, i);
+    else mpc_env<NOBJ, false>(x, i);
+  }
+  return EARL_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
+int earl_tabletop_mpc_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
+                                  const earl_mpc_out* mpc) {
+  return do_mpc<1>(cfg, st, params, T, out, mpc);
+}
+int earl_tabletop3_mpc_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
+                                   const earl_mpc_out* mpc) {
+  return do_mpc<3>(cfg, st, params, T, out, mpc);
+}
 int earl_tabletop_plan_mppi_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan,
                                 double* ret, double* ret0, double* best_ret, int32_t* best_k) {
   return do_plan<1>(cfg, st, params, mean, plan, ret, ret0, best_ret, best_k);

@@ -586,6 +586,54 @@ class TabletopManipulation:
     self._check(rc, 'plan_candidates')
     return act
 
+  def rollout_mpc(self, T, plan=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, out=None):
+    """T steps of receding-horizon MPPI control in ONE kernel launch (include/earl_tabletop.h: earl_tabletop_mpc_rollout): per step plan_mppi from the current
+    state with the warm start, rollout of the plan's first action, the plan shifted by one step (zeroed for an env that auto-reset) -- bit for bit the loop
+        for s in range(T): plan_mppi(plan, ..., out={'plan': plan}); rollout(plan[:1]); plan = cat(plan[1:], plan[-1:])
+    with the env's state, the plan and the K returns on chip throughout.  plan [H, N, 3] (None: zeros of [horizon, N, 3]) -> {'obs' [T, N, D], 'reward' [T, N],
+    'done' [T, N], 'success' [T, N], 'actions' [T, N, 3] (the executed ones), 'plan' [H, N, 3] (the warm start of the next call), 'ret0' [T, iterations, N]
+    float64, 'best_ret' [T, N] float64}.  `noise_counter=None` takes the low 32 bits of the env's Philox counter (step s adds s), as plan_mppi does at each step
+    of that loop.  `out`: an optional dict of preallocated tensors under the same keys; a key that is missing or None is not computed, except 'plan', which is
+    then allocated; out['plan'] may be the `plan` tensor (the call is in place on it).  Advances the Philox counter and total_step_count by T, like rollout()."""
+    n, T, K, I = self.num_envs, int(T), int(K), int(iterations)
+    p0 = self._plan_mean('rollout_mpc', plan, horizon)
+    H = int(p0.shape[0])
+    pp = self._plan_params('rollout_mpc', K, H, I, iteration0, sigma, temperature, noise_counter)
+    if T < 1 or K < 1 or H < 1 or I < 1:
+      raise ValueError(f'rollout_mpc: T = {T}, K = {K}, H = {H}, iterations = {I}: at least one of each')
+    if K > _abi.MPC_MAX_K or H > _abi.MPC_MAX_H:
+      raise ValueError(f'rollout_mpc: K = {K}, H = {H}: at most {_abi.MPC_MAX_K} branches (one per lane of a workgroup) of {_abi.MPC_MAX_H} steps')
+    kw = dict(device=self.device)
+    want = {'obs': ((T, n, self.OBS_DIM), torch.float32), 'reward': ((T, n), torch.float32), 'done': ((T, n), torch.bool), 'success': ((T, n), torch.bool),
+            'actions': ((T, n, 3), torch.float32), 'plan': ((H, n, 3), torch.float32), 'ret0': ((T, I, n), torch.float64), 'best_ret': ((T, n), torch.float64)}
+    if out is None:
+      res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
+    else:
+      if set(out) - set(want):
+        raise ValueError(f'rollout_mpc: out holds {sorted(set(out) - set(want))}; the keys are {list(want)}')
+      res = {k: t for k, t in out.items() if t is not None}
+      for k, t in res.items():
+        shape, dt = want[k]
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+          raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
+      if not any(k in res for k in ('obs', 'reward', 'done', 'success')):
+        raise ValueError('rollout_mpc: out holds none of obs, reward, done, success')
+      if 'plan' not in res:
+        res['plan'] = torch.empty(H, n, 3, dtype=torch.float32, **kw)
+    with self._ctx():
+      if res['plan'].data_ptr() != p0.data_ptr():
+        res['plan'].copy_(p0)                                          # (the entry point is in place on the plan)
+      ostruct = _abi.TabletopOut(_ptr(res.get('obs')), _ptr(res.get('reward')), _ptr(res.get('done')), _ptr(res.get('success')))
+      mpc = _abi.MpcOut(act=_ptr(res.get('actions')), plan=res['plan'].data_ptr(), ret0=_ptr(res.get('ret0')), best_ret=_ptr(res.get('best_ret')))
+      fn = self._lib.earl_tabletop_mpc_rollout if self.NOBJ == 1 else self._lib.earl_tabletop3_mpc_rollout
+      rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), T, C.byref(ostruct), C.byref(mpc), self._stream())
+    self._check(rc, 'mpc_rollout')
+    self._cfg.counter += T                                             # real step s used counter + s (its look-ahead step t: counter + s + t)
+    self.total_step_count += T
+    if 'success' in res:
+      self._last_success = res['success'][-1]
+    return res
+
   def _observe(self, want=('obs',)):
     kw = dict(device=self.device)
     n = self.num_envs

@@ -428,6 +428,41 @@ int earl_tabletop3_plan_mppi(const earl_tabletop_cfg* cfg, const earl_tabletop_s
  * H outside 1 .. 65536, j outside 0 .. 255, a bad sigma and the branch launch's grid limits; n == 0 returns EARL_OK and writes nothing. */
 int earl_tabletop_plan_candidates(const earl_tabletop_cfg* cfg, const earl_plan_params* params, int32_t j, const float* mean, float* act_out, earl_stream_t stream);
 
+/* ---- receding-horizon MPPI control: T real steps of plan -> act -> shift in ONE launch ----
+ * What a planner is called for (the model-predictive control loop around envs/tabletop_manipulation.py:128-138: plan from the current state, execute the first
+ * action, shift the plan by one step, plan again).  The call is DEFINED by composition of the entry points above.  Let c0 = cfg->counter and P_0 = the `plan`
+ * buffer on entry.  For real step s = 0 .. T - 1:
+ *   1 plan    P'_s = the `plan` output of earl_tabletop[3]_plan_mppi on the state before step s, called with cfg->counter = c0 + s, mean = P_s and `params` with
+ *             noise_counter replaced by (uint32)(params->noise_counter + s); iterations and iteration0 as given.  Row s of ret0 ([T, iterations, n]) is that
+ *             call's ret0, row s of best_ret ([T, n]) its best_ret.
+ *   2 act     a_s = P'_s[0] (already clipped).  Row s of `out` (rows [T, n], as earl_tabletop[3]_rollout) and the new state are what
+ *             earl_tabletop[3]_rollout(T = 1, act = a_s) produces at cfg->counter = c0 + s;  act[s] = a_s.
+ *   3 shift   P_{s+1}[t] = P'_s[t + 1] for t < H - 1, P_{s+1}[H - 1] = P'_s[H - 1].  Exception: an env whose step s came out `done` while cfg->auto_reset is set
+ *             gets P_{s+1} = 0 in all H rows -- a new episode does not inherit the old plan.
+ *   4 exit    `plan` holds P_T; the state, the wrapper arrays and num_interventions are as T one-step rollouts leave them; the caller advances its counter by T.
+ *             Two calls of T1 and T2 steps (the second with counter c0 + T1 and noise_counter + T1) equal one call of T1 + T2, bit for bit.
+ * As properties: look-ahead step t of real step s uses env counter c0 + s + t; the noise uses Philox word 0 0x504C4E00 | j, the global env id, (k << 16) | t and
+ * noise_counter + s; nothing depends on n or on the shard split.  Items 4-5 of the planner's contract are integer sums, so the result does not depend on how the
+ * launch spreads the K branches over lanes and waves: the fused launch equals the composed calls bit for bit under both rewards.
+ *   launch    one workgroup per env for all T steps, its lanes the K branches (ceil(K / 64) waves); no cooperative launch, no flag between workgroups, no
+ *             allocation, no host synchronisation, no [K, n] workspace: the only memory touched is what the caller passes.  *counter_base is not read.
+ * EARL_ERR_ARG before any HIP call for: everything earl_tabletop[3]_plan_mppi refuses (its grid limits included); out NULL or every pointer of it NULL; mpc NULL or
+ * mpc->plan NULL; T < 0; K > EARL_MPC_MAX_K (one branch per lane of one workgroup); H > EARL_MPC_MAX_H; n workgroups of 64 * ceil(K / 64) lanes beyond 2^32 - 1
+ * lanes.  T == 0 or n == 0 returns EARL_OK, launches nothing and writes nothing. */
+#define EARL_MPC_MAX_K 1024
+#define EARL_MPC_MAX_H 256
+typedef struct earl_mpc_out {
+  float* act;       /* NULL or [T, n, 3]: the action executed at each real step */
+  float* plan;      /* REQUIRED [H, n, 3], in/out: the warm start on entry, the shifted plan for the next call on exit */
+  double* ret0;     /* NULL or [T, iterations, n]: the return of the plan entering each iteration of each real step */
+  double* best_ret; /* NULL or [T, n]: beta of the last iteration of each real step */
+} earl_mpc_out;
+int earl_tabletop_mpc_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
+                              const earl_mpc_out* mpc, earl_stream_t stream);
+/* the same on the 3-object variant (qpos [n,8], obs rows of 20) */
+int earl_tabletop3_mpc_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
+                               const earl_mpc_out* mpc, earl_stream_t stream);
+
 /* ---- host build: the `_cpu` entry points (BASELINE.json configs[0] "1 env, CPU ... plumbing, no GPU") ----
  * csrc/libearl_host.so = the SAME per-env functions the gfx950 kernels run (csrc/tabletop_device.h, tabletop_step.h, philox.h), compiled for the host by
  * g++ with -ffp-contract=off; one OpenMP iteration per env where a kernel has one lane per env.  Same structs, same arguments minus the stream, HOST
@@ -489,6 +524,13 @@ int earl_tabletop_plan_mppi_cpu(const earl_tabletop_cfg* cfg, const earl_tableto
 int earl_tabletop3_plan_mppi_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan,
                                  double* ret, double* ret0, double* best_ret, int32_t* best_k);
 int earl_tabletop_plan_candidates_cpu(const earl_tabletop_cfg* cfg, const earl_plan_params* params, int32_t j, const float* mean, float* act_out);
+/* host twins of earl_tabletop[3]_mpc_rollout: one OpenMP iteration per env, the kernel's per-lane functions (csrc/tabletop_mpc.h) with the branches in ascending k.
+ * Bit-identical to the composition of the `_cpu` planner and rollout under both rewards, and to the device under the sparse one (dense: the device's exp moves
+ * the plans apart after the first step; not comparable).  They refuse what the device entry points refuse. */
+int earl_tabletop_mpc_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
+                                  const earl_mpc_out* mpc);
+int earl_tabletop3_mpc_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
+                                   const earl_mpc_out* mpc);
 int earl_host_set_threads(int n);      /* OpenMP threads of the calls above (n <= 0: query); returns the count in force */
 const char* earl_host_version(void);
 const char* earl_host_last_error(void);

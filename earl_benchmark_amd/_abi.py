@@ -68,6 +68,13 @@ class MpcOut(C.Structure):             # struct earl_mpc_out (include/earl_table
 MPC_MAX_K, MPC_MAX_H = 1024, 256       # EARL_MPC_MAX_K, EARL_MPC_MAX_H
 
 
+class PlanValue(C.Structure):          # struct earl_plan_value (include/earl_tabletop.h)
+  _fields_ = [('discount', C.c_double), ('value', C.POINTER(MlpPolicy))]
+
+
+PLAN_VALUE_MAX_H1 = 16                 # EARL_PLAN_VALUE_MAX_H1: the widest first hidden layer of a two-hidden-layer value network
+
+
 class AgentPair(C.Structure):          # struct earl_agent_pair (include/earl_tabletop.h)
   _fields_ = [('switch_every', C.c_int32 * 2), ('switch_on_success', C.c_int32), ('pad_', C.c_int32), ('param_stride', C.c_int64), ('backward_goal', C.c_void_p),
               ('phase', C.c_void_p), ('steps_in_phase', C.c_void_p), ('agent_out', C.c_void_p), ('forward_success', C.c_void_p), ('backward_success', C.c_void_p)]
@@ -190,6 +197,10 @@ SIGNATURES = {
     'earl_tabletop_plan_candidates': [_P(TabletopCfg), _P(PlanParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_tabletop_mpc_rollout': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), C.c_int32, _P(TabletopOut), _P(MpcOut), C.c_void_p],
     'earl_tabletop3_mpc_rollout': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), C.c_int32, _P(TabletopOut), _P(MpcOut), C.c_void_p],
+    'earl_tabletop_plan_mppi_value': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue)] + [C.c_void_p] * 7,
+    'earl_tabletop3_plan_mppi_value': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue)] + [C.c_void_p] * 7,
+    'earl_tabletop_mpc_rollout_value': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue), C.c_int32, _P(TabletopOut), _P(MpcOut), C.c_void_p],
+    'earl_tabletop3_mpc_rollout_value': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue), C.c_int32, _P(TabletopOut), _P(MpcOut), C.c_void_p],
     'earl_debug_set_rollout_impl': [C.c_int],
     'earl_debug_set_rollout3_form': [C.c_int],
     'earl_debug_set_rollout_wgs_per_cu': [C.c_int],

@@ -133,15 +133,20 @@ int do_branch(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32
 }
 
 // The planner on the host (include/earl_tabletop.h, "MPPI planning"): per iteration the score pass over the device's (branch, 64 envs) workgroups, then per env the
-// weights once and per step the integer sums in ascending k -- tabletop_step.h's plan_* functions, the ones the kernels run.
-template <int NOBJ>
-int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* pp, const float* mean, float* plan, double* ret, double* ret0,
-            double* best_ret, int32_t* best_k) {
+// weights once and per step the integer sums in ascending k -- tabletop_step.h's plan_* functions, the ones the kernels run.  VALUE: the `_value` twins (the score of
+// tabletop_value.h, as plan_score_kernel<.., true>).
+template <int NOBJ, bool VALUE>
+int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* pp, const earl_plan_value* pv, const float* mean, float* plan,
+            double* ret, double* ret0, double* best_ret, int32_t* best_k) {
   if (!st) return fail(EARL_ERR_ARG, "cfg/state is NULL");
   long long blocks, ublocks;
   if (int rc = check_plan(cfg, st, NOBJ, pp, 0, mean, plan, ret, &blocks, &ublocks)) return rc;
+  if constexpr (VALUE)
+    if (int rc = check_plan_value(pv, Dims<NOBJ>::NOBS)) return rc;
   if (blocks == 0) return EARL_OK;
-  PlanArgs p = plan_args(cfg, st, pp, mean, thresholds());
+  PlanValueArgs p{};
+  static_cast<PlanArgs&>(p) = plan_args(cfg, st, pp, mean, thresholds());
+  if constexpr (VALUE) p.v = ValueArgs{pv->discount, pv->value ? *pv->value : earl_mlp_policy{}};
   p.plan = plan;
   p.ret = ret;
   const int n = cfg->n, K = pp->K, H = pp->H;
@@ -158,8 +163,8 @@ int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const e
       const long long i0 = (b - k * tiles) * kTile;
       const int m = n - i0 < kTile ? (int)(n - i0) : kTile;
       for (int i = (int)i0; i < (int)i0 + m; ++i) {
-        if (general) plan_score_body<NOBJ, true>(p, i, k);
-        else plan_score_body<NOBJ, false>(p, i, k);
+        if (general) plan_score_body<NOBJ, true, VALUE>(p, i, k, &p.v);
+        else plan_score_body<NOBJ, false, VALUE>(p, i, k, &p.v);
       }
     }
 #pragma omp parallel for schedule(static, kChunk) if (n >= 4 * kChunk)
@@ -191,8 +196,8 @@ int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const e
 // The receding-horizon loop on the host (include/earl_tabletop.h, "receding-horizon MPPI control"): one OpenMP iteration per env -- the device's workgroup -- holds
 // the env and its plan for all T steps; per iteration the K scores in ascending k (mpc_score, the kernel's), the weights once, per plan row the integer sums in
 // ascending k; then the real step (mpc_act, the kernel's) and the shift.
-template <int NOBJ, bool GENERAL>
-void mpc_env(const MpcArgs& x, int i) {
+template <int NOBJ, bool GENERAL, bool VALUE>
+void mpc_env(const MpcValueArgs& x, int i) {
   const KArgs& a = x.p.a;
   const int n = a.cfg.n, H = a.T, K = x.p.K;
   std::vector<float> P((size_t)H * 3);
@@ -216,7 +221,7 @@ void mpc_env(const MpcArgs& x, int i) {
       double beta = -INFINITY;
       int bk = 0;
       for (int k = 0; k < K; ++k) {
-        ret[k] = mpc_score<NOBJ, GENERAL>(q, i, k, counter, L, g, row);
+        ret[k] = mpc_score<NOBJ, GENERAL, VALUE>(q, i, k, counter, L, g, row, &x.v);
         plan_best(ret[k], k, beta, bk);
       }
       if (x.m.ret0) x.m.ret0[((size_t)s * x.iterations + it) * n + i] = ret[0];
@@ -246,18 +251,23 @@ void mpc_env(const MpcArgs& x, int i) {
   store_lane<NOBJ>(a, i, L);
 }
 
-template <int NOBJ>
-int do_mpc(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* pp, int32_t T, const earl_tabletop_out* out, const earl_mpc_out* mpc) {
+template <int NOBJ, bool VALUE>
+int do_mpc(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* pp, const earl_plan_value* pv, int32_t T, const earl_tabletop_out* out,
+           const earl_mpc_out* mpc) {
   int lanes;
   if (int rc = check_mpc(cfg, st, NOBJ, pp, T, out, mpc, &lanes)) return rc;
+  if constexpr (VALUE)
+    if (int rc = check_plan_value(pv, Dims<NOBJ>::NOBS)) return rc;
   if (lanes == 0) return EARL_OK;
-  const MpcArgs x = mpc_args(cfg, st, pp, T, out, mpc);
+  MpcValueArgs x{};
+  static_cast<MpcArgs&>(x) = mpc_args(cfg, st, pp, T, out, mpc);
+  if constexpr (VALUE) x.v = ValueArgs{pv->discount, pv->value ? *pv->value : earl_mlp_policy{}};
   const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
   const int n = cfg->n;
 #pragma omp parallel for schedule(dynamic, 1) if (n >= 4)
   for (int i = 0; i < n; ++i) {
-    if (general) mpc_env<NOBJ, true>(x, i);
-    else mpc_env<NOBJ, false>(x, i);
+    if (general) mpc_env<NOBJ, true, VALUE>(x, i);
+    else mpc_env<NOBJ, false, VALUE>(x, i);
   }
   return EARL_OK;
 }
@@ -268,19 +278,35 @@ extern "C" {
 
 int earl_tabletop_mpc_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
                                   const earl_mpc_out* mpc) {
-  return do_mpc<1>(cfg, st, params, T, out, mpc);
+  return do_mpc<1, false>(cfg, st, params, nullptr, T, out, mpc);
 }
 int earl_tabletop3_mpc_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
                                    const earl_mpc_out* mpc) {
-  return do_mpc<3>(cfg, st, params, T, out, mpc);
+  return do_mpc<3, false>(cfg, st, params, nullptr, T, out, mpc);
+}
+int earl_tabletop_mpc_rollout_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv, int32_t T,
+                                        const earl_tabletop_out* out, const earl_mpc_out* mpc) {
+  return do_mpc<1, true>(cfg, st, params, pv, T, out, mpc);
+}
+int earl_tabletop3_mpc_rollout_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv, int32_t T,
+                                         const earl_tabletop_out* out, const earl_mpc_out* mpc) {
+  return do_mpc<3, true>(cfg, st, params, pv, T, out, mpc);
 }
 int earl_tabletop_plan_mppi_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan,
                                 double* ret, double* ret0, double* best_ret, int32_t* best_k) {
-  return do_plan<1>(cfg, st, params, mean, plan, ret, ret0, best_ret, best_k);
+  return do_plan<1, false>(cfg, st, params, nullptr, mean, plan, ret, ret0, best_ret, best_k);
 }
 int earl_tabletop3_plan_mppi_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan,
                                  double* ret, double* ret0, double* best_ret, int32_t* best_k) {
-  return do_plan<3>(cfg, st, params, mean, plan, ret, ret0, best_ret, best_k);
+  return do_plan<3, false>(cfg, st, params, nullptr, mean, plan, ret, ret0, best_ret, best_k);
+}
+int earl_tabletop_plan_mppi_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                      const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k) {
+  return do_plan<1, true>(cfg, st, params, pv, mean, plan, ret, ret0, best_ret, best_k);
+}
+int earl_tabletop3_plan_mppi_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                       const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k) {
+  return do_plan<3, true>(cfg, st, params, pv, mean, plan, ret, ret0, best_ret, best_k);
 }
 int earl_tabletop_plan_candidates_cpu(const earl_tabletop_cfg* cfg, const earl_plan_params* params, int32_t j, const float* mean, float* act_out) {
   long long blocks, ublocks;

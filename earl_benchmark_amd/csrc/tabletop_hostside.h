@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "tabletop_device.h"
+#include "policy_check.h"   // contract::check_policy: the value network of the `_value` planner calls (check_plan_value below)
 
 namespace earl {
 namespace hostside {
@@ -139,6 +140,19 @@ inline int check_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* s
   }
   *blocks = nb;
   *ublocks = ub;
+  return EARL_OK;
+}
+
+// What earl_tabletop[3]_plan_mppi_value and earl_tabletop[3]_mpc_rollout_value (and their host twins) refuse beyond check_plan / check_mpc: the discount, and the value
+// network obs_dim -> hidden (-> hidden) -> 1 under the policy contract (policy_check.h) with the lane's register budget on its first hidden layer.
+constexpr int kPlanValueMaxH1 = EARL_PLAN_VALUE_MAX_H1;
+inline int check_plan_value(const earl_plan_value* pv, int obs_dim) {
+  if (!pv) return fail(EARL_ERR_ARG, "value block is NULL (discount = 1 and value = NULL is the value-free call)");
+  if (!(pv->discount > 0.0 && pv->discount <= 1.0)) return fail(EARL_ERR_ARG, "discount = %g: 0 < discount <= 1", pv->discount);   // (NaN fails both comparisons)
+  if (!pv->value) return EARL_OK;
+  if (int rc = contract::check_policy(*pv->value, obs_dim, 1, nullptr, 0, g_err)) return rc;
+  if (pv->value->n_layers == 3 && pv->value->dims[1] > kPlanValueMaxH1)
+    return fail(EARL_ERR_ARG, "value network: first hidden width %d of two > %d (a lane holds that layer in registers)", pv->value->dims[1], kPlanValueMaxH1);
   return EARL_OK;
 }
 

@@ -17,6 +17,11 @@ struct MpcArgs {
   int32_t iteration0;
 };
 
+// earl_tabletop[3]_mpc_rollout_value: the loop's block followed by the discount and the value network (as PlanValueArgs after PlanArgs)
+struct MpcValueArgs : MpcArgs {
+  ValueArgs v;
+};
+
 // the env word by word (the struct's padding stays where it is: a whole-struct copy out of LDS goes through private memory)
 template <int NOBJ>
 __device__ __forceinline__ void copy_lane(Lane<NOBJ>& dst, const Lane<NOBJ>& src) {
@@ -30,15 +35,18 @@ __device__ __forceinline__ void copy_lane(Lane<NOBJ>& dst, const Lane<NOBJ>& src
   dst.resets = src.resets;
 }
 
-// the return of branch k of env i from the state (L, g) -- plan_score_body's loop on a COPY of the registers the real env lives in, look-ahead step t at `counter` + t
-template <int NOBJ, bool GENERAL, class Row>
-__device__ __forceinline__ double mpc_score(const PlanArgs& q, int i, int k, uint64_t counter, const Lane<NOBJ>& L, const float (&g)[Dims<NOBJ>::NG], Row&& row) {
+// the return of branch k of env i from the state (L, g) -- plan_score_body's loop on a COPY of the registers the real env lives in, look-ahead step t at `counter` + t.
+// VALUE (v != NULL): the discounted sum and the value network on the last row, as plan_score_body<.., true>
+template <int NOBJ, bool GENERAL, bool VALUE = false, class Row>
+__device__ __forceinline__ double mpc_score(const PlanArgs& q, int i, int k, uint64_t counter, const Lane<NOBJ>& L, const float (&g)[Dims<NOBJ>::NG], Row&& row,
+                                            const ValueArgs* v = nullptr) {
   Lane<NOBJ> B;
   copy_lane<NOBJ>(B, L);
   float gb[Dims<NOBJ>::NG];
 #pragma unroll
   for (int j = 0; j < Dims<NOBJ>::NG; ++j) gb[j] = g[j];
   double ret = 0.0;
+  [[maybe_unused]] double disc = 1.0;
   float o[Dims<NOBJ>::NOBS];
   for (int t = 0; t < q.a.T; ++t) {
     float m[3];
@@ -47,8 +55,20 @@ __device__ __forceinline__ double mpc_score(const PlanArgs& q, int i, int k, uin
     if (k > 0) plan_candidate(q, i, (uint32_t)k, (uint32_t)t, m, c);
     float reward;
     bool done, succ;
-    wrapped_step<NOBJ, GENERAL>(q.a, i, counter + (uint64_t)t, B, gb, c[0], c[1], c[2], o, reward, done, succ);
-    ret += (double)reward;
+    if constexpr (VALUE) {   // (the last step without its auto-reset, the row made again after the loop: plan_score_body)
+      wrapped_step<NOBJ, GENERAL>(q.a, i, counter + (uint64_t)t, B, gb, c[0], c[1], c[2], o, reward, done, succ, nullptr, t + 1 < q.a.T);
+      value_accumulate(ret, disc, reward, v->discount);
+    } else {
+      wrapped_step<NOBJ, GENERAL>(q.a, i, counter + (uint64_t)t, B, gb, c[0], c[1], c[2], o, reward, done, succ);
+      ret += (double)reward;
+    }
+  }
+  if constexpr (VALUE) {
+    if (v->net.params) {
+      float ov[Dims<NOBJ>::NOBS];
+      make_obs<NOBJ>(B.e, gb, ov);
+      ret = value_terminal<Dims<NOBJ>::NOBS>(*v, ov, ret, disc);
+    }
   }
   return ret;
 }

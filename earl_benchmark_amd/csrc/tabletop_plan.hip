@@ -2,7 +2,8 @@
 // sample -> score -> reweight with the K candidate plans never in memory.  Per iteration two launches on the caller's stream, ordered by the stream alone (no
 // cooperative launch, no grid-wide barrier, no flag between workgroups); the per-lane functions are tabletop_step.h's plan_*, shared with the host twin.
 //
-// plan_score_kernel   the branch launch's shape: one lane per (branch, env), a wave = 64 consecutive envs of ONE branch (so `k == 0`, the plan itself, is
+// plan_score_kernel   (tabletop_plan_kernel.inc: one text with tabletop_plan_value.hip)
+//                     the branch launch's shape: one lane per (branch, env), a wave = 64 consecutive envs of ONE branch (so `k == 0`, the plan itself, is
 //                     wave-uniform), a workgroup = that wave, 1-D grid of K * ceil(n / 64).  Per env-step a lane loads 12 B of the mean, makes one Philox block
 //                     and three quantiles, and stores nothing; at the end one float64 (and ret0 for k = 0).  No LDS.
 // plan_update_kernel  one lane per (env, step): a workgroup is 64 consecutive envs x kPlanUpdateSteps steps, wave w = step t0 + w, so that what all steps of an
@@ -25,13 +26,6 @@ using namespace earl::hostside;
 namespace {
 
 constexpr int kPlanChunk = 64;   // branches whose weights an update workgroup holds at a time
-
-template <int NOBJ, bool GENERAL>
-__global__ __launch_bounds__(kBranchBlock) void plan_score_kernel(const PlanArgs p, const unsigned tiles) {
-  const unsigned k = blockIdx.x / tiles;
-  const unsigned i = (blockIdx.x - k * tiles) * kBranchBlock + threadIdx.x;
-  if (i < (unsigned)p.a.cfg.n) plan_score_body<NOBJ, GENERAL>(p, (int)i, (int)k);
-}
 
 __global__ __launch_bounds__(kBranchBlock) void plan_candidates_kernel(const PlanArgs p, float* __restrict__ act_out, const unsigned tiles) {
   const unsigned k = blockIdx.x / tiles;
@@ -92,33 +86,18 @@ __global__ __launch_bounds__(kBranchBlock* kPlanUpdateSteps) void plan_update_ke
   }
 }
 
-template <int NOBJ>
-int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* pp, const float* mean, float* plan, double* ret, double* ret0,
-            double* best_ret, int32_t* best_k, earl_stream_t stream) {
-  long long blocks, ublocks;
-  if (int rc = check_plan(cfg, st, NOBJ, pp, 0, mean, plan, ret, &blocks, &ublocks)) return rc;
-  if (blocks == 0) return EARL_OK;
-  PlanArgs p = plan_args(cfg, st, pp, mean, thresholds());
-  p.plan = plan;
-  p.ret = ret;
-  const unsigned tiles = (unsigned)(blocks / pp->K);
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
-  const hipStream_t s = (hipStream_t)stream;
-  for (int it = 0; it < pp->iterations; ++it) {
-    const bool last = it + 1 == pp->iterations;
-    p.mean = it ? plan : mean;
-    p.word0 = kPlanDraw | (uint32_t)(pp->iteration0 + it);
-    p.ret0 = ret0 ? ret0 + (size_t)it * cfg->n : nullptr;
-    p.best_ret = last ? best_ret : nullptr;
-    p.best_k = last ? best_k : nullptr;
-    if (general) plan_score_kernel<NOBJ, true><<<dim3((unsigned)blocks), kBranchBlock, 0, s>>>(p, tiles);
-    else plan_score_kernel<NOBJ, false><<<dim3((unsigned)blocks), kBranchBlock, 0, s>>>(p, tiles);
-    plan_update_kernel<<<dim3((unsigned)ublocks), kBranchBlock * kPlanUpdateSteps, 0, s>>>(p, tiles);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EARL_ERR_LAUNCH, "plan kernels: %s", hipGetErrorString(e));
-  }
-  return EARL_OK;
+}  // namespace
+
+// the update launch, for this unit's do_plan and for tabletop_plan_value.hip's (the update sees returns only: one kernel serves both)
+namespace earl {
+void plan_update_launch(const PlanArgs& p, unsigned tiles, unsigned ublocks, earl_stream_t stream) {
+  plan_update_kernel<<<dim3(ublocks), kBranchBlock * kPlanUpdateSteps, 0, (hipStream_t)stream>>>(p, tiles);
 }
+}  // namespace earl
+
+namespace {
+
+#include "tabletop_plan_kernel.inc"   // plan_score_kernel and do_plan: one text with tabletop_plan_value.hip
 
 }  // namespace
 
@@ -127,13 +106,13 @@ extern "C" {
 int earl_tabletop_plan_mppi(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan, double* ret,
                             double* ret0, double* best_ret, int32_t* best_k, earl_stream_t stream) {
   if (!st) return fail(EARL_ERR_ARG, "cfg/state is NULL");
-  return do_plan<1>(cfg, st, params, mean, plan, ret, ret0, best_ret, best_k, stream);
+  return do_plan<1>(cfg, st, params, nullptr, mean, plan, ret, ret0, best_ret, best_k, stream);
 }
 
 int earl_tabletop3_plan_mppi(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan, double* ret,
                              double* ret0, double* best_ret, int32_t* best_k, earl_stream_t stream) {
   if (!st) return fail(EARL_ERR_ARG, "cfg/state is NULL");
-  return do_plan<3>(cfg, st, params, mean, plan, ret, ret0, best_ret, best_k, stream);
+  return do_plan<3>(cfg, st, params, nullptr, mean, plan, ret, ret0, best_ret, best_k, stream);
 }
 
 int earl_tabletop_plan_candidates(const earl_tabletop_cfg* cfg, const earl_plan_params* params, int32_t j, const float* mean, float* act_out, earl_stream_t stream) {

@@ -5,6 +5,7 @@
 #pragma once
 #include "tabletop_device.h"
 #include "policy_math.h"   // exp_f32, normal_quantile_f32: the planner's noise and weights (plan_* below)
+#include "tabletop_value.h"   // the discounted score with a terminal value (plan_score_body<.., true>)
 
 namespace earl {
 
@@ -84,10 +85,12 @@ __device__ __forceinline__ void store_obs(float* __restrict__ dst, const float (
 
 // One wrapped step on register state.  `counter` is the Philox counter of THIS step.
 // GENERAL = lifelong goal switching and auto-reset compiled in (they drag the Philox generator into the loop).
+// reset_ok = false (the LAST look-ahead step of a planner branch scored with a terminal value, whose env copy is thrown away): the auto-reset is left out, so that
+// (L, g) stay the state the returned row was made from and make_obs(L.e, g) gives that row again.
 template <int NOBJ, bool GENERAL>
 __device__ __forceinline__ void wrapped_step(const KArgs& a, int i, uint64_t counter, Lane<NOBJ>& L,
                                              float (&g)[Dims<NOBJ>::NG], float a0, float a1, float a2,
-                                             float (&o)[Dims<NOBJ>::NOBS], float& reward, bool& done, bool& succ, double* r64 = nullptr) {
+                                             float (&o)[Dims<NOBJ>::NOBS], float& reward, bool& done, bool& succ, double* r64 = nullptr, bool reset_ok = true) {
   move<NOBJ>(L.e, rescale_action(a0), rescale_action(a1), rescale_action(a2), a.th);
   make_obs<NOBJ>(L.e, g, o);
   double r;
@@ -110,7 +113,7 @@ __device__ __forceinline__ void wrapped_step(const KArgs& a, int i, uint64_t cou
     }
   }
   if constexpr (GENERAL)
-  if (done && a.cfg.auto_reset) {  // batched-only extension; the outputs above stay the terminal ones
+  if (done && a.cfg.auto_reset && reset_ok) {  // batched-only extension; the outputs above stay the terminal ones
     L.goal_idx = reset_env<NOBJ>(L.e, a.cfg, counter, i, a.st.goal_table, a.next_goal_idx, a.th);
     load_goal<NOBJ>(a.st.goal_table, L.goal_idx, g);
     L.steps = 0;
@@ -269,6 +272,17 @@ inline PlanArgs plan_args(const earl_tabletop_cfg* cfg, const earl_tabletop_stat
   return p;
 }
 
+// earl_tabletop[3]_plan_mppi_value: the planner's block followed by the discount and the value network.  A derived struct, so that every function above and below
+// takes it as the PlanArgs it starts with and the value-free launches pass what they always passed
+struct PlanValueArgs : PlanArgs {
+  ValueArgs v;
+};
+
+#ifndef EARL_HOST_BUILD
+// the update launch of one iteration (tabletop_plan.hip: ublocks workgroups of kBranchBlock * kPlanUpdateSteps lanes on `stream`), for the units that score
+void plan_update_launch(const PlanArgs& p, unsigned tiles, unsigned ublocks, earl_stream_t stream);
+#endif
+
 // item 1 (and the clip of item 2 and 5): min(max(x, -1), 1) as two compare-and-selects, NaN -> -1
 __device__ __forceinline__ float plan_clip(float x) {
   const float y = x > -1.0f ? x : -1.0f;
@@ -292,15 +306,18 @@ __device__ __forceinline__ void plan_candidate(const PlanArgs& p, int i, uint32_
 }
 
 // item 3: branch k of env i.  branch_body's loop (same state loads, same wrapped_step, same counters, eight steps of the mean in flight) with the candidate of
-// the step made in registers; one word stored.
-template <int NOBJ, bool GENERAL>
-__device__ __forceinline__ void plan_score_body(const PlanArgs& p, int i, int k) {
+// the step made in registers; one word stored.  VALUE (the `_value` entry points; v != NULL): item 3 as tabletop_value.h states it -- the discounted sum, and the value
+// network on the last step's row (what branch_body stores as last_obs).  That row is made AGAIN after the loop from the state the last step left (its auto-reset is
+// left out: the copy is thrown away), so that no observation stays live through the loop's register peak.
+template <int NOBJ, bool GENERAL, bool VALUE = false>
+__device__ __forceinline__ void plan_score_body(const PlanArgs& p, int i, int k, const ValueArgs* v = nullptr) {
   const KArgs& a = p.a;
   Lane<NOBJ> L;
   load_lane<NOBJ>(a, i, L);
   float g[Dims<NOBJ>::NG];
   load_goal<NOBJ>(a.st.goal_table, L.goal_idx, g);
   double ret = 0.0;
+  [[maybe_unused]] double disc = 1.0;
   float o[Dims<NOBJ>::NOBS];
   constexpr int PF = 8;
   for (int t0 = 0; t0 < a.T; t0 += PF) {
@@ -315,9 +332,21 @@ __device__ __forceinline__ void plan_score_body(const PlanArgs& p, int i, int k)
         if (k > 0) plan_candidate(p, i, (uint32_t)k, (uint32_t)t, mv[j], c);
         float reward;
         bool done, succ;
-        wrapped_step<NOBJ, GENERAL>(a, i, a.cfg.counter + (uint64_t)t, L, g, c[0], c[1], c[2], o, reward, done, succ);
-        ret += (double)reward;
+        if constexpr (VALUE) {
+          wrapped_step<NOBJ, GENERAL>(a, i, a.cfg.counter + (uint64_t)t, L, g, c[0], c[1], c[2], o, reward, done, succ, nullptr, t + 1 < a.T);
+          value_accumulate(ret, disc, reward, v->discount);
+        } else {
+          wrapped_step<NOBJ, GENERAL>(a, i, a.cfg.counter + (uint64_t)t, L, g, c[0], c[1], c[2], o, reward, done, succ);
+          ret += (double)reward;
+        }
       }
+    }
+  }
+  if constexpr (VALUE) {
+    if (v->net.params) {
+      float ov[Dims<NOBJ>::NOBS];
+      make_obs<NOBJ>(L.e, g, ov);
+      ret = value_terminal<Dims<NOBJ>::NOBS>(*v, ov, ret, disc);
     }
   }
   p.ret[(size_t)k * a.cfg.n + i] = ret;

@@ -532,7 +532,29 @@ class TabletopManipulation:
       raise ValueError(f'{who}: mean must be [H, N, 3] = [{"H" if horizon is None else horizon}, {n}, 3], got {list(m.shape)}')
     return self._actions(m, (int(m.shape[0]), n))
 
-  def plan_mppi(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, out=None):
+  def _plan_value(self, who, discount, value):
+    """-> None (discount 1.0 and no value network: the value-free entry points, called exactly as before those keywords existed) or the struct earl_plan_value of
+    the `_value` ones (with the network's struct kept alive beside it)"""
+    if value is None and float(discount) == 1.0:
+      return None
+    if not (float(discount) > 0.0 and float(discount) <= 1.0):
+      raise ValueError(f'{who}: discount = {discount}: 0 < discount <= 1')
+    if value is None:
+      return _abi.PlanValue(discount=float(discount), value=None)
+    from ..policy import GaussianMLPPolicy, MLPPolicy
+    if not isinstance(value, MLPPolicy) or isinstance(value, GaussianMLPPolicy):
+      raise ValueError(f'{who}: value is an MLPPolicy(layers, hidden_act, out_act, obs_dim={self.OBS_DIM}, act_dim=1): a network from the observation to one number')
+    require_widths(value, who, self.OBS_DIM, 1, env=self)
+    if value.param_dtype != torch.float32:
+      raise ValueError(f'{who}: the value network stores its parameters as {value.param_dtype}; float32 only (pass .widened())')
+    if len(value.dims) == 4 and value.dims[1] > _abi.PLAN_VALUE_MAX_H1:
+      raise ValueError(f'{who}: a value network of two hidden layers has a first one of at most {_abi.PLAN_VALUE_MAX_H1} (a lane holds it in registers), got '
+                       f'{value.dims[1]}; one hidden layer may be 256 wide')
+    pv = _abi.PlanValue(discount=float(discount), value=C.pointer(value.struct))
+    pv._keep = value
+    return pv
+
+  def plan_mppi(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, out=None, discount=1.0, value=None):
     """`iterations` MPPI iterations on the device from the CURRENT state (include/earl_tabletop.h: earl_tabletop_plan_mppi): K candidates per env -- the mean plan
     itself and K - 1 copies with clipped Gaussian noise of scale `sigma` (a number or three) -- scored as rollout_branches scores them, the mean moved to their
     average under the weights exp((ret - max ret) / temperature).  The candidates are never in memory: the noise is made inside the scoring kernel and made again
@@ -541,7 +563,12 @@ class TabletopManipulation:
     that candidate)}.  `noise_counter=None` takes the low 32 bits of the env's Philox counter, so successive control steps draw fresh noise; `iteration0` numbers
     the first iteration (iterations in one call == as many calls of one, numbered on).  `out`: an optional dict of preallocated tensors under the same keys; a
     key that is missing or None is not computed, except 'ret' (the workspace of the call), which is then allocated; out['plan'] may be the `mean` tensor.  The env
-    is left exactly as found -- state, counters, the Philox counter."""
+    is left exactly as found -- state, counters, the Philox counter.
+    `discount` (0 < gamma <= 1) and `value` (an `MLPPolicy(layers, hidden_act, 'none' or 'tanh', obs_dim=D, act_dim=1)` on the env's device: V from the observation
+    to one number) change the score of a candidate from the plain sum of its H rewards to  sum_t gamma^t r_t + gamma^H V(o_H)  (earl_tabletop_plan_mppi_value): the
+    network is evaluated inside the scoring kernel on the last look-ahead observation of every branch, no [K, N, D] tensor and no extra launch in between.  Under
+    the sparse reward that is what lets a short horizon see a goal further than H steps away.  One hidden layer may be 256 wide; of two, the first is at most
+    16 (_abi.PLAN_VALUE_MAX_H1).  With both defaults the call is the value-free entry point, exactly as before."""
     m = self._plan_mean('plan_mppi', mean, horizon)
     n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
     pp = self._plan_params('plan_mppi', K, H, I, iteration0, sigma, temperature, noise_counter)
@@ -564,10 +591,16 @@ class TabletopManipulation:
         raise ValueError("plan_mppi: out['plan'] is what the call computes")
       if 'ret' not in res:
         res['ret'] = torch.empty(K, n, dtype=torch.float64, **kw)
+    pv = self._plan_value('plan_mppi', discount, value)
     with self._ctx():
-      fn = self._lib.earl_tabletop_plan_mppi if self.NOBJ == 1 else self._lib.earl_tabletop3_plan_mppi
-      rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), m.data_ptr(), res['plan'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
-              _ptr(res.get('best_k')), self._stream())
+      if pv is None:
+        fn = self._lib.earl_tabletop_plan_mppi if self.NOBJ == 1 else self._lib.earl_tabletop3_plan_mppi
+        rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), m.data_ptr(), res['plan'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
+                _ptr(res.get('best_k')), self._stream())
+      else:
+        fn = self._lib.earl_tabletop_plan_mppi_value if self.NOBJ == 1 else self._lib.earl_tabletop3_plan_mppi_value
+        rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), C.byref(pv), m.data_ptr(), res['plan'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')),
+                _ptr(res.get('best_ret')), _ptr(res.get('best_k')), self._stream())
     self._check(rc, 'plan_mppi')
     return res                                                       # (no counter advance, no step count: nothing happened to the env)
 
@@ -586,7 +619,8 @@ class TabletopManipulation:
     self._check(rc, 'plan_candidates')
     return act
 
-  def rollout_mpc(self, T, plan=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, out=None):
+  def rollout_mpc(self, T, plan=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, out=None, discount=1.0,
+                  value=None):
     """T steps of receding-horizon MPPI control in ONE kernel launch (include/earl_tabletop.h: earl_tabletop_mpc_rollout): per step plan_mppi from the current
     state with the warm start, rollout of the plan's first action, the plan shifted by one step (zeroed for an env that auto-reset) -- bit for bit the loop
         for s in range(T): plan_mppi(plan, ..., out={'plan': plan}); rollout(plan[:1]); plan = cat(plan[1:], plan[-1:])
@@ -594,7 +628,9 @@ class TabletopManipulation:
     'done' [T, N], 'success' [T, N], 'actions' [T, N, 3] (the executed ones), 'plan' [H, N, 3] (the warm start of the next call), 'ret0' [T, iterations, N]
     float64, 'best_ret' [T, N] float64}.  `noise_counter=None` takes the low 32 bits of the env's Philox counter (step s adds s), as plan_mppi does at each step
     of that loop.  `out`: an optional dict of preallocated tensors under the same keys; a key that is missing or None is not computed, except 'plan', which is
-    then allocated; out['plan'] may be the `plan` tensor (the call is in place on it).  Advances the Philox counter and total_step_count by T, like rollout()."""
+    then allocated; out['plan'] may be the `plan` tensor (the call is in place on it).  Advances the Philox counter and total_step_count by T, like rollout().
+    `discount` and `value` are plan_mppi's: every planning step of the loop scores its candidates by  sum_t gamma^t r_t + gamma^H V(o_H)  with the value network
+    evaluated inside the same launch (earl_tabletop_mpc_rollout_value); with both defaults the call is the value-free entry point, exactly as before."""
     n, T, K, I = self.num_envs, int(T), int(K), int(iterations)
     p0 = self._plan_mean('rollout_mpc', plan, horizon)
     H = int(p0.shape[0])
@@ -603,6 +639,7 @@ class TabletopManipulation:
       raise ValueError(f'rollout_mpc: T = {T}, K = {K}, H = {H}, iterations = {I}: at least one of each')
     if K > _abi.MPC_MAX_K or H > _abi.MPC_MAX_H:
       raise ValueError(f'rollout_mpc: K = {K}, H = {H}: at most {_abi.MPC_MAX_K} branches (one per lane of a workgroup) of {_abi.MPC_MAX_H} steps')
+    pv = self._plan_value('rollout_mpc', discount, value)
     kw = dict(device=self.device)
     want = {'obs': ((T, n, self.OBS_DIM), torch.float32), 'reward': ((T, n), torch.float32), 'done': ((T, n), torch.bool), 'success': ((T, n), torch.bool),
             'actions': ((T, n, 3), torch.float32), 'plan': ((H, n, 3), torch.float32), 'ret0': ((T, I, n), torch.float64), 'best_ret': ((T, n), torch.float64)}
@@ -625,8 +662,12 @@ class TabletopManipulation:
         res['plan'].copy_(p0)                                          # (the entry point is in place on the plan)
       ostruct = _abi.TabletopOut(_ptr(res.get('obs')), _ptr(res.get('reward')), _ptr(res.get('done')), _ptr(res.get('success')))
       mpc = _abi.MpcOut(act=_ptr(res.get('actions')), plan=res['plan'].data_ptr(), ret0=_ptr(res.get('ret0')), best_ret=_ptr(res.get('best_ret')))
-      fn = self._lib.earl_tabletop_mpc_rollout if self.NOBJ == 1 else self._lib.earl_tabletop3_mpc_rollout
-      rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), T, C.byref(ostruct), C.byref(mpc), self._stream())
+      if pv is None:
+        fn = self._lib.earl_tabletop_mpc_rollout if self.NOBJ == 1 else self._lib.earl_tabletop3_mpc_rollout
+        rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), T, C.byref(ostruct), C.byref(mpc), self._stream())
+      else:
+        fn = self._lib.earl_tabletop_mpc_rollout_value if self.NOBJ == 1 else self._lib.earl_tabletop3_mpc_rollout_value
+        rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), C.byref(pv), T, C.byref(ostruct), C.byref(mpc), self._stream())
     self._check(rc, 'mpc_rollout')
     self._cfg.counter += T                                             # real step s used counter + s (its look-ahead step t: counter + s + t)
     self.total_step_count += T

@@ -463,6 +463,46 @@ int earl_tabletop_mpc_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_
 int earl_tabletop3_mpc_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
                                const earl_mpc_out* mpc, earl_stream_t stream);
 
+/* ---- discounted MPPI with a terminal value: the planner and the control loop above with ret = sum_t gamma^t r_t + gamma^H V(o_H), V evaluated inside the kernels ----
+ * Under the sparse reward the undiscounted H-step sum is blind whenever the goal is more than H steps away: every branch returns the same value and the plan does
+ * not move.  A short-horizon sampling planner handles that with a discount and a learned value function at the end of the look-ahead.  The four entry points below
+ * are earl_tabletop[3]_plan_mppi and earl_tabletop[3]_mpc_rollout with ONE item of their contracts replaced: everything written above for those calls -- items 1, 2
+ * and 4 - 7 of the planner, chaining, state, counters, the noise counter words, the MPC composition (with earl_tabletop[3]_plan_mppi_value as its planner) and every
+ * refusal -- holds word for word.  Item 3 becomes, per (branch k, env):
+ *   3 scores   d_0 = 1.0, ret = 0.0.  For t = 0 .. H - 1 ascending: ret = ret + d_t * (double)r_t -- the product rounded to float64, then the sum rounded, no fused
+ *              multiply-add -- and d_{t+1} = d_t * gamma (one float64 rounding).  r_t is the float32 reward of the same wrapped step at the same counter as before
+ *              (common random numbers unchanged).  d_t depends on t only: it keeps running across an auto-reset inside the look-ahead.
+ *              value != NULL: v = the float32 output of the network on the branch's LAST observation row -- exactly what earl_tabletop[3]_branch_rollout writes to
+ *              last_obs[k][env] (after a lifelong goal switch: the re-read row; after an auto-reset: the terminal row) -- and ret = ret + d_H * (double)v, rounded
+ *              the same way.  The network is a float32 MLP obs -> hidden (-> hidden) -> 1 under the policy contract of this header: acc = b_j; k ascending:
+ *              acc = fmaf(x_k, W_jk, acc); hidden_act on the hidden layers, out_act (EARL_ACT_NONE or EARL_ACT_TANH) on the output; relu / tanh_f32 of
+ *              csrc/policy_math.h.  earl_mlp_policy_forward_cpu (earl_physics.h) with a 1-wide last layer and head = NULL states it on the host.
+ *   non-finite values need no new rule: a NaN v gives a NaN return, which item 7 handles (W_k = 0, never beta); a +Inf return becomes beta, every x_k is then NaN
+ *              (Inf - Inf) or -Inf, so S == 0 and the update is skipped.  Nothing faults.
+ *   identity   discount == 1.0 and value == NULL: every output equals the value-free entry point's bit for bit (1.0 * r is exact).
+ *   launch     the same launches as the value-free calls: each lane evaluates the network itself on the observation row it holds in registers, the weights read at
+ *              wave-uniform addresses.  No [K, n, obs] tensor, no extra launch, no LDS beyond the value-free kernels'.
+ * EARL_PLAN_VALUE_MAX_H1: a lane holds the FIRST hidden layer of a two-hidden-layer network in registers (the second is streamed into the output, as the only
+ * hidden layer of a one-hidden-layer network is: those may be 256 wide).  16 is what every MPC kernel holds at 128 VGPRs under 1024-lane workgroups WITHOUT
+ * scratch: the constants of the env step that the compiler keeps in registers across the whole control loop leave the network about 40 registers next to the
+ * observation row, and 32, 48 and 64 spill (12 - 28, 20 - 76 and 96 - 148 bytes per lane).  It may be lowered, never raised.
+ * EARL_ERR_ARG before any HIP call for: everything the value-free entry point refuses; pv NULL; a discount that is NaN, <= 0 or > 1; a value network the policy
+ * contract refuses with the env's observation width (12 / 20), action width 1 and no head (NULL params, precision != 0, n_layers, a hidden width that is not a multiple of 16
+ * in 16..256, dims[3] != 0 with two layers, the activation enums); n_layers == 3 with dims[1] > EARL_PLAN_VALUE_MAX_H1. */
+#define EARL_PLAN_VALUE_MAX_H1 16
+typedef struct earl_plan_value {
+  double discount;               /* gamma: finite, 0 < gamma <= 1 */
+  const earl_mlp_policy* value;  /* NULL: no terminal term.  Otherwise V: obs -> 1 (dims[0] = 12 / 20, dims[n_layers] = 1, precision 0) */
+} earl_plan_value;
+int earl_tabletop_plan_mppi_value(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                  const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k, earl_stream_t stream);
+int earl_tabletop3_plan_mppi_value(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                   const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k, earl_stream_t stream);
+int earl_tabletop_mpc_rollout_value(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv, int32_t T,
+                                    const earl_tabletop_out* out, const earl_mpc_out* mpc, earl_stream_t stream);
+int earl_tabletop3_mpc_rollout_value(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv, int32_t T,
+                                     const earl_tabletop_out* out, const earl_mpc_out* mpc, earl_stream_t stream);
+
 /* ---- host build: the `_cpu` entry points (BASELINE.json configs[0] "1 env, CPU ... plumbing, no GPU") ----
  * csrc/libearl_host.so = the SAME per-env functions the gfx950 kernels run (csrc/tabletop_device.h, tabletop_step.h, philox.h), compiled for the host by
  * g++ with -ffp-contract=off; one OpenMP iteration per env where a kernel has one lane per env.  Same structs, same arguments minus the stream, HOST
@@ -531,6 +571,17 @@ int earl_tabletop_mpc_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_table
                                   const earl_mpc_out* mpc);
 int earl_tabletop3_mpc_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
                                    const earl_mpc_out* mpc);
+/* host twins of earl_tabletop[3]_plan_mppi_value / earl_tabletop[3]_mpc_rollout_value: the twins above with the kernels' own per-lane functions of
+ * csrc/tabletop_value.h; the value network's params is a HOST pointer.  Bit-identical to the device in every output under the sparse reward (the network's
+ * arithmetic is the policy contract's); under the dense reward as the value-free twins.  They refuse what the device entry points refuse. */
+int earl_tabletop_plan_mppi_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                      const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k);
+int earl_tabletop3_plan_mppi_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                       const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k);
+int earl_tabletop_mpc_rollout_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv, int32_t T,
+                                        const earl_tabletop_out* out, const earl_mpc_out* mpc);
+int earl_tabletop3_mpc_rollout_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv, int32_t T,
+                                         const earl_tabletop_out* out, const earl_mpc_out* mpc);
 int earl_host_set_threads(int n);      /* OpenMP threads of the calls above (n <= 0: query); returns the count in force */
 const char* earl_host_version(void);
 const char* earl_host_last_error(void);

@@ -100,7 +100,7 @@ int do_step(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const f
   if (!act || !out) return fail(EARL_ERR_ARG, "act/out is NULL");
   if (cfg->n == 0) return EARL_OK;
   KArgs a{*cfg, *st, *out, act, ngi, nullptr, nullptr, 1, thresholds()};
-  if (cfg->goal_change_frequency > 0 || cfg->auto_reset)
+  if (is_general(cfg))
     step_kernel<NOBJ, true><<<grid_for(cfg->n), kBlock, 0, (hipStream_t)stream>>>(a);
   else
     step_kernel<NOBJ, false><<<grid_for(cfg->n), kBlock, 0, (hipStream_t)stream>>>(a);
@@ -123,7 +123,7 @@ int do_rollout(const earl_tabletop_cfg* cfg_in, const earl_tabletop_state* st, i
   if (T < 0) return fail(EARL_ERR_ARG, "T = %d < 0", T);
   if (cfg->n == 0) return EARL_OK;
   if (T == 0) return reset_first ? do_reset<NOBJ>(cfg, st, nullptr, nullptr, nullptr, stream) : EARL_OK;
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  const bool general = is_general(cfg);
   if constexpr (NOBJ == 1) {
     // the common case (no lifelong switching, no auto-reset, all outputs requested): wave-specialised kernel
     if (!general && out->obs && out->reward && out->done && out->success && g_rollout_impl != 1) {
@@ -278,7 +278,7 @@ int earl_tabletop_eval_episodes(const earl_tabletop_cfg* cfg, const earl_tableto
   if (!act || !out) return fail(EARL_ERR_ARG, "act/out is NULL");
   if (T < 0) return fail(EARL_ERR_ARG, "T = %d < 0", T);
   if (episodes == 0 || cfg->n == 0) return EARL_OK;
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  const bool general = is_general(cfg);
   // one launch walks all episodes when the wave-specialised kernel applies and episodes end on its chunk boundaries (8 steps)
   const bool fused = episodes > 1 && !general && out->obs && out->reward && out->done && out->success && (g_rollout_impl == 0 || g_rollout_impl == 29 || g_rollout_impl == 36 || g_rollout_impl == 38 || (g_rollout_impl >= 40 && g_rollout_impl <= 46)) &&
                      T % 8 == 0 && T >= 16 && (long long)episodes * T < (1 << 24);

@@ -1,14 +1,14 @@
 // tabletop_branch.hip -- earl_tabletop_branch_rollout / earl_tabletop3_branch_rollout (include/earl_tabletop.h): K candidate action sequences of H steps scored
 // per env FROM THE CURRENT STATE in one launch, the state left as it was -- what a shooting planner (random shooting, CEM, MPPI) asks of a simulator.
 //
-// One lane per (branch, env): branch_body (tabletop_step.h) is rollout_body's loop with the per-step stores replaced by three reducers in registers.  A wave is
+// One lane per (branch, env): branch_body (tabletop_plan.h) is rollout_body's loop with the per-step stores replaced by three reducers in registers.  A wave is
 // 64 consecutive envs of ONE branch, so the three dword action loads of a step cover 768 contiguous bytes; a workgroup is that one wave (no LDS, no barrier, no
 // atomics: nothing ties waves together, and a batch of 70 envs costs two waves per branch, not four).  The grid is 1-D, K * ceil(n / 64) workgroups, the branch
 // taken from blockIdx.x: K is the large dimension of a planner and grid.y ends at 65,535.  Per env-step a lane reads 12 B and stores nothing.
 #include <hip/hip_runtime.h>
 
 #include "tabletop_hostside.h"
-#include "tabletop_step.h"
+#include "tabletop_plan.h"
 
 using namespace earl;
 using namespace earl::hostside;
@@ -32,7 +32,7 @@ int do_branch(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32
                      (long long)stride, summary ? *summary : earl_episode_summary{nullptr, nullptr, nullptr}, last_obs};
   const unsigned tiles = (unsigned)(blocks / K);
   const dim3 grid((unsigned)blocks);
-  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) branch_kernel<NOBJ, true><<<grid, kBranchBlock, 0, (hipStream_t)stream>>>(b, tiles);
+  if (is_general(cfg)) branch_kernel<NOBJ, true><<<grid, kBranchBlock, 0, (hipStream_t)stream>>>(b, tiles);
   else branch_kernel<NOBJ, false><<<grid, kBranchBlock, 0, (hipStream_t)stream>>>(b, tiles);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(EARL_ERR_LAUNCH, "branch_kernel: %s", hipGetErrorString(e));

@@ -1,6 +1,8 @@
 // tabletop_host.cpp -- the `_cpu` entry points of include/earl_tabletop.h (BASELINE configs[0]: "1 env, CPU ... plumbing, no GPU"):
-// the SAME per-env functions the gfx950 kernels run (tabletop_device.h, tabletop_step.h, philox.h), compiled for the host by g++
-// (-DEARL_HOST_BUILD: earl_rt.h -> host_shim.h) with -ffp-contract=off, one OpenMP iteration per env where a kernel has one lane per env.
+// the SAME per-env functions the gfx950 kernels run (tabletop_device.h, tabletop_step.h, philox.h; the planners' tabletop_plan.h, tabletop_value.h, tabletop_mpc.h;
+// the policies' tabletop_policy.h), compiled for the host by g++ (-DEARL_HOST_BUILD: earl_rt.h -> host_shim.h) with -ffp-contract=off, one OpenMP iteration per env
+// where a kernel has one lane per env.  This file owns only the walks: for_each_env, rollout_tiles, for_each_branch_tile (the branch-shaped launches' (branch, tile)
+// range) and update_env (one env's reweighting, for the planner and the receding-horizon loop); no arithmetic of an env or a planner is stated here.
 // Host pointers, no stream, no HIP runtime.  This library is loaded only when a caller ASKS for device='cpu'; nothing falls back to it,
 // and nothing here touches oracle/ (the oracle is the checker of both builds).
 #include <algorithm>
@@ -8,7 +10,7 @@
 #include <vector>
 
 #include "tabletop_hostside.h"
-#include "tabletop_step.h"
+#include "tabletop_plan.h"
 #include "tabletop_mpc.h"
 #include "tabletop_policy.h"
 #include "../../include/earl_physics.h"
@@ -73,7 +75,7 @@ int do_step(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const f
   if (!act || !out) return fail(EARL_ERR_ARG, "act/out is NULL");
   if (cfg->n == 0) return EARL_OK;
   const KArgs a{*cfg, *st, *out, act, ngi, nullptr, nullptr, 1, thresholds()};
-  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) for_each_env(cfg->n, [&](int i) { step_body<NOBJ, true>(a, i); });
+  if (is_general(cfg)) for_each_env(cfg->n, [&](int i) { step_body<NOBJ, true>(a, i); });
   else for_each_env(cfg->n, [&](int i) { step_body<NOBJ, false>(a, i); });
   return EARL_OK;
 }
@@ -100,41 +102,89 @@ int do_rollout(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int3
   }
   if (T == 0) return EARL_OK;
   const KArgs a{c2, *st, *out, act, nullptr, nullptr, nullptr, T, thresholds()};
-  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) rollout_tiles<NOBJ, true>(a);
+  if (is_general(cfg)) rollout_tiles<NOBJ, true>(a);
   else rollout_tiles<NOBJ, false>(a);
   return EARL_OK;
 }
 
-// The branch launch on the host: one OpenMP iteration per (branch, tile of kTile envs) of the flattened range -- the device's workgroups -- each env of a tile through
-// branch_body, the function the kernel runs.
+// The evaluation episodes on the host: the plain loop over the reset and the rollout above, episode e at counter + e * (T + 1)
+template <int NOBJ>
+int do_eval(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t episodes, int32_t T, const float* act, int64_t act_episode_stride,
+            const earl_tabletop_out* out) {
+  if (episodes < 0) return fail(EARL_ERR_ARG, "episodes = %d < 0", episodes);
+  if (act_episode_stride < 0) return fail(EARL_ERR_ARG, "negative action stride");
+  if (int rc = check_common(cfg, st, NOBJ)) return rc;
+  if (!act || !out) return fail(EARL_ERR_ARG, "act/out is NULL");
+  if (T < 0) return fail(EARL_ERR_ARG, "T = %d < 0", T);
+  for (int32_t e = 0; e < episodes; ++e) {
+    earl_tabletop_cfg c = *cfg;
+    c.counter += (uint64_t)e * (uint64_t)(T + 1);
+    const size_t rows = (size_t)e * (size_t)T * (size_t)cfg->n;
+    const earl_tabletop_out o{out->obs ? out->obs + rows * Dims<NOBJ>::NOBS : nullptr, out->reward ? out->reward + rows : nullptr, out->done ? out->done + rows : nullptr,
+                              out->success ? out->success + rows : nullptr, nullptr};
+    if (int rc = do_rollout<NOBJ>(&c, st, T, act + (size_t)e * (size_t)act_episode_stride, &o, true)) return rc;
+  }
+  return EARL_OK;
+}
+
+// The (branch, tile of kTile envs) walk of the branch-shaped launches (branch, score, candidates) on the host, stated once: one OpenMP iteration per workgroup of
+// the device's flattened 1-D grid of `blocks` = K * tiles, f(i, k) for every live env i of the tile.
+template <class F>
+inline void for_each_branch_tile(long long blocks, int K, int n, F&& f) {
+  static_assert(kTile == kBranchBlock, "a tile of the twin is a workgroup of the device launch");
+  const long long tiles = blocks / K;
+#pragma omp parallel for schedule(static) if (blocks >= 4)
+  for (long long j = 0; j < blocks; ++j) {
+    const int k = (int)(j / tiles);
+    const long long i0 = (j - k * tiles) * kTile;
+    const int m = n - i0 < kTile ? (int)(n - i0) : kTile;
+    for (int i = (int)i0; i < (int)i0 + m; ++i) f(i, k);
+  }
+}
+
+// One reweighting of ONE env (items 4-5 of the planner's contract), stated once for the planner and the receding-horizon loop: beta / best_k over the K returns in
+// ascending k, the weights once per k, then per plan row the integer sums in ascending k (branch 0 is the mean and adds nothing; W == 0 is skipped) and plan_new_mean.
+// ret(k) = return k; row(t, m) = the CLIPPED row t of the plan entering; put(t, d, v) = word d of row t of the plan leaving.  -> (beta, best_k)
+template <class Ret, class Row, class Put>
+inline std::pair<double, int> update_env(const PlanArgs& p, int i, Ret&& ret, Row&& row, Put&& put) {
+  double beta = -INFINITY;
+  int bk = 0;
+  for (int k = 0; k < p.K; ++k) plan_best(ret(k), k, beta, bk);
+  std::vector<int32_t> Wk(p.K);                            // once per (k, env), as the update kernel shares them through LDS
+  for (int k = 0; k < p.K; ++k) Wk[k] = plan_weight(ret(k), beta, p.inv_temperature);
+  for (int t = 0; t < p.a.T; ++t) {
+    float m[3];
+    row(t, m);
+    int64_t A[3] = {0, 0, 0}, S = 0;
+    for (int k = 0; k < p.K; ++k) {
+      const int32_t W = Wk[k];
+      S += W;
+      if (W != 0 && k > 0) plan_accumulate(p, i, (uint32_t)k, (uint32_t)t, m, W, A);
+    }
+    for (int d = 0; d < 3; ++d) put(t, d, plan_new_mean(m[d], A[d], S));
+  }
+  return {beta, bk};
+}
+
+// The branch launch on the host: each env of each (branch, tile) through branch_body, the function the kernel runs.
 template <int NOBJ>
 int do_branch(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t stride,
               const earl_episode_summary* summary, float* last_obs) {
   long long blocks;
   if (int rc = check_branch(cfg, st, NOBJ, K, H, act, stride, summary, last_obs, &blocks)) return rc;
   if (blocks == 0) return EARL_OK;
-  static_assert(kTile == kBranchBlock, "a tile of the twin is a workgroup of the device launch");
   const BranchArgs b{KArgs{*cfg, *st, earl_tabletop_out{nullptr, nullptr, nullptr, nullptr, nullptr}, act, nullptr, nullptr, nullptr, H, thresholds()},
                      (long long)stride, summary ? *summary : earl_episode_summary{nullptr, nullptr, nullptr}, last_obs};
-  const long long tiles = blocks / K;
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
-  const int n = cfg->n;
-#pragma omp parallel for schedule(static) if (blocks >= 4)
-  for (long long j = 0; j < blocks; ++j) {
-    const int k = (int)(j / tiles);
-    const long long i0 = (j - k * tiles) * kTile;
-    const int m = n - i0 < kTile ? (int)(n - i0) : kTile;
-    for (int i = (int)i0; i < (int)i0 + m; ++i) {
-      if (general) branch_body<NOBJ, true>(b, i, k);
-      else branch_body<NOBJ, false>(b, i, k);
-    }
-  }
+  const bool general = is_general(cfg);
+  for_each_branch_tile(blocks, K, cfg->n, [&](int i, int k) {
+    if (general) branch_body<NOBJ, true>(b, i, k);
+    else branch_body<NOBJ, false>(b, i, k);
+  });
   return EARL_OK;
 }
 
-// The planner on the host (include/earl_tabletop.h, "MPPI planning"): per iteration the score pass over the device's (branch, 64 envs) workgroups, then per env the
-// weights once and per step the integer sums in ascending k -- tabletop_step.h's plan_* functions, the ones the kernels run.  VALUE: the `_value` twins (the score of
-// tabletop_value.h, as plan_score_kernel<.., true>).
+// The planner on the host (include/earl_tabletop.h, "MPPI planning"): per iteration the score pass over the device's (branch, 64 envs) workgroups, then update_env
+// per env -- tabletop_plan.h's plan_* functions, the ones the kernels run.  VALUE: the `_value` twins (the score of tabletop_value.h, as plan_score_kernel<.., true>).
 template <int NOBJ, bool VALUE>
 int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* pp, const earl_plan_value* pv, const float* mean, float* plan,
             double* ret, double* ret0, double* best_ret, int32_t* best_k) {
@@ -146,65 +196,40 @@ int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const e
   if (blocks == 0) return EARL_OK;
   PlanValueArgs p{};
   static_cast<PlanArgs&>(p) = plan_args(cfg, st, pp, mean, thresholds());
-  if constexpr (VALUE) p.v = ValueArgs{pv->discount, pv->value ? *pv->value : earl_mlp_policy{}};
+  if constexpr (VALUE) p.v = value_args(pv);
   p.plan = plan;
   p.ret = ret;
-  const int n = cfg->n, K = pp->K, H = pp->H;
-  const long long tiles = blocks / K;
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  const int n = cfg->n, K = pp->K;
+  const bool general = is_general(cfg);
   for (int it = 0; it < pp->iterations; ++it) {
     const bool last = it + 1 == pp->iterations;
     p.mean = it ? plan : mean;
     p.word0 = kPlanDraw | (uint32_t)(pp->iteration0 + it);
     p.ret0 = ret0 ? ret0 + (size_t)it * n : nullptr;
-#pragma omp parallel for schedule(static) if (blocks >= 4)
-    for (long long b = 0; b < blocks; ++b) {
-      const int k = (int)(b / tiles);
-      const long long i0 = (b - k * tiles) * kTile;
-      const int m = n - i0 < kTile ? (int)(n - i0) : kTile;
-      for (int i = (int)i0; i < (int)i0 + m; ++i) {
-        if (general) plan_score_body<NOBJ, true, VALUE>(p, i, k, &p.v);
-        else plan_score_body<NOBJ, false, VALUE>(p, i, k, &p.v);
-      }
-    }
-#pragma omp parallel for schedule(static, kChunk) if (n >= 4 * kChunk)
-    for (int i = 0; i < n; ++i) {
-      double beta = -INFINITY;
-      int bk = 0;
-      for (int k = 0; k < K; ++k) plan_best(ret[(size_t)k * n + i], k, beta, bk);
-      std::vector<int32_t> Wk(K);                          // once per (k, env), as the update kernel shares them through LDS
-      for (int k = 0; k < K; ++k) Wk[k] = plan_weight(ret[(size_t)k * n + i], beta, p.inv_temperature);
-      for (int t = 0; t < H; ++t) {
-        float m[3];
-        plan_mean(p, i, t, m);
-        int64_t A[3] = {0, 0, 0}, S = 0;
-        for (int k = 0; k < K; ++k) {
-          const int32_t W = Wk[k];
-          S += W;
-          if (W != 0 && k > 0) plan_accumulate(p, i, (uint32_t)k, (uint32_t)t, m, W, A);
-        }
-        float* dst = plan + ((size_t)t * n + i) * 3;
-        for (int d = 0; d < 3; ++d) dst[d] = plan_new_mean(m[d], A[d], S);
-      }
+    for_each_branch_tile(blocks, K, n, [&](int i, int k) {
+      if (general) plan_score_body<NOBJ, true, VALUE>(p, i, k, &p.v);
+      else plan_score_body<NOBJ, false, VALUE>(p, i, k, &p.v);
+    });
+    for_each_env(n, [&](int i) {
+      const auto [beta, bk] = update_env(p, i, [&](int k) { return ret[(size_t)k * n + i]; }, [&](int t, float (&m)[3]) { plan_mean(p, i, t, m); },
+                                         [&](int t, int d, float v) { plan[((size_t)t * n + i) * 3 + d] = v; });
       if (last && best_ret) best_ret[i] = beta;
       if (last && best_k) best_k[i] = bk;
-    }
+    });
   }
   return EARL_OK;
 }
 
 // The receding-horizon loop on the host (include/earl_tabletop.h, "receding-horizon MPPI control"): one OpenMP iteration per env -- the device's workgroup -- holds
-// the env and its plan for all T steps; per iteration the K scores in ascending k (mpc_score, the kernel's), the weights once, per plan row the integer sums in
-// ascending k; then the real step (mpc_act, the kernel's) and the shift.
+// the env and its plan for all T steps; per iteration the K scores in ascending k (mpc_score, the kernel's) and update_env on the env's own plan; then the real
+// step (mpc_act, the kernel's) and the shift.
 template <int NOBJ, bool GENERAL, bool VALUE>
 void mpc_env(const MpcValueArgs& x, int i) {
   const KArgs& a = x.p.a;
   const int n = a.cfg.n, H = a.T, K = x.p.K;
   std::vector<float> P((size_t)H * 3);
-  for (int t = 0; t < H; ++t)
-    for (int d = 0; d < 3; ++d) P[(size_t)t * 3 + d] = x.m.plan[((size_t)t * n + i) * 3 + d];
+  for (int e = 0; e < H * 3; ++e) P[e] = x.m.plan[((size_t)(e / 3) * n + i) * 3 + e % 3];
   std::vector<double> ret(K);
-  std::vector<int32_t> Wk(K);
   Lane<NOBJ> L;
   load_lane<NOBJ>(a, i, L);
   float g[Dims<NOBJ>::NG];
@@ -218,36 +243,17 @@ void mpc_env(const MpcValueArgs& x, int i) {
     q.noise_counter = x.p.noise_counter + (uint32_t)s;
     for (int it = 0; it < x.iterations; ++it) {
       q.word0 = kPlanDraw | (uint32_t)(x.iteration0 + it);
-      double beta = -INFINITY;
-      int bk = 0;
-      for (int k = 0; k < K; ++k) {
-        ret[k] = mpc_score<NOBJ, GENERAL, VALUE>(q, i, k, counter, L, g, row, &x.v);
-        plan_best(ret[k], k, beta, bk);
-      }
+      for (int k = 0; k < K; ++k) ret[k] = mpc_score<NOBJ, GENERAL, VALUE>(q, i, k, counter, L, g, row, &x.v);
       if (x.m.ret0) x.m.ret0[((size_t)s * x.iterations + it) * n + i] = ret[0];
-      int64_t S = 0;
-      for (int k = 0; k < K; ++k) S += Wk[k] = plan_weight(ret[k], beta, q.inv_temperature);
-      for (int t = 0; t < H; ++t) {
-        float m[3];
-        row(t, m);
-        int64_t A[3] = {0, 0, 0};
-        for (int k = 1; k < K; ++k)
-          if (Wk[k] != 0) plan_accumulate(q, i, (uint32_t)k, (uint32_t)t, m, Wk[k], A);
-        for (int d = 0; d < 3; ++d) P[(size_t)t * 3 + d] = plan_new_mean(m[d], A[d], S);
-      }
+      const double beta = update_env(q, i, [&](int k) { return ret[k]; }, row, [&](int t, int d, float v) { P[(size_t)t * 3 + d] = v; }).first;
       if (it + 1 == x.iterations && x.m.best_ret) x.m.best_ret[(size_t)s * n + i] = beta;
     }
     const float act[3] = {P[0], P[1], P[2]};
     const bool done = mpc_act<NOBJ, GENERAL>(x, i, s, counter, L, g, act, true);
-    if (GENERAL && done && a.cfg.auto_reset) {
-      std::fill(P.begin(), P.end(), 0.0f);
-    } else {
-      for (int t = 0; t + 1 < H; ++t)
-        for (int d = 0; d < 3; ++d) P[(size_t)t * 3 + d] = P[(size_t)(t + 1) * 3 + d];
-    }
+    if (GENERAL && done && a.cfg.auto_reset) std::fill(P.begin(), P.end(), 0.0f);
+    else std::copy(P.begin() + 3, P.end(), P.begin());   // (the shift; the last row stays, repeated)
   }
-  for (int t = 0; t < H; ++t)
-    for (int d = 0; d < 3; ++d) x.m.plan[((size_t)t * n + i) * 3 + d] = P[(size_t)t * 3 + d];
+  for (int e = 0; e < H * 3; ++e) x.m.plan[((size_t)(e / 3) * n + i) * 3 + e % 3] = P[e];
   store_lane<NOBJ>(a, i, L);
 }
 
@@ -261,8 +267,8 @@ int do_mpc(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const ea
   if (lanes == 0) return EARL_OK;
   MpcValueArgs x{};
   static_cast<MpcArgs&>(x) = mpc_args(cfg, st, pp, T, out, mpc);
-  if constexpr (VALUE) x.v = ValueArgs{pv->discount, pv->value ? *pv->value : earl_mlp_policy{}};
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  if constexpr (VALUE) x.v = value_args(pv);
+  const bool general = is_general(cfg);
   const int n = cfg->n;
 #pragma omp parallel for schedule(dynamic, 1) if (n >= 4)
   for (int i = 0; i < n; ++i) {
@@ -314,15 +320,7 @@ int earl_tabletop_plan_candidates_cpu(const earl_tabletop_cfg* cfg, const earl_p
   if (blocks == 0) return EARL_OK;
   PlanArgs p = plan_args(cfg, nullptr, params, mean, thresholds());
   p.word0 = kPlanDraw | (uint32_t)j;
-  const long long tiles = blocks / params->K;
-  const int n = cfg->n;
-#pragma omp parallel for schedule(static) if (blocks >= 4)
-  for (long long b = 0; b < blocks; ++b) {
-    const int k = (int)(b / tiles);
-    const long long i0 = (b - k * tiles) * kTile;
-    const int m = n - i0 < kTile ? (int)(n - i0) : kTile;
-    for (int i = (int)i0; i < (int)i0 + m; ++i) plan_candidates_body(p, i, k, act_out);
-  }
+  for_each_branch_tile(blocks, params->K, cfg->n, [&](int i, int k) { plan_candidates_body(p, i, k, act_out); });
   return EARL_OK;
 }
 
@@ -347,27 +345,14 @@ int earl_tabletop_reset_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tab
 }
 int earl_tabletop_eval_episodes_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t episodes, int32_t T, const float* act,
                                     int64_t act_episode_stride, const earl_tabletop_out* out) {
-  if (episodes < 0) return fail(EARL_ERR_ARG, "episodes = %d < 0", episodes);
-  if (act_episode_stride < 0) return fail(EARL_ERR_ARG, "negative action stride");
-  if (int rc = check_common(cfg, st, 1)) return rc;
-  if (!act || !out) return fail(EARL_ERR_ARG, "act/out is NULL");
-  if (T < 0) return fail(EARL_ERR_ARG, "T = %d < 0", T);
-  for (int32_t e = 0; e < episodes; ++e) {
-    earl_tabletop_cfg c = *cfg;
-    c.counter += (uint64_t)e * (uint64_t)(T + 1);
-    const size_t rows = (size_t)e * (size_t)T * (size_t)cfg->n;
-    const earl_tabletop_out o{out->obs ? out->obs + rows * 12 : nullptr, out->reward ? out->reward + rows : nullptr, out->done ? out->done + rows : nullptr,
-                              out->success ? out->success + rows : nullptr, nullptr};
-    if (int rc = do_rollout<1>(&c, st, T, act + (size_t)e * (size_t)act_episode_stride, &o, true)) return rc;
-  }
-  return EARL_OK;
+  return do_eval<1>(cfg, st, episodes, T, act, act_episode_stride, out);
 }
 int earl_tabletop_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, int32_t episodes, int32_t T,
                                      int32_t reset_first, const earl_tabletop_out* out, float* act_out) {
   if (int rc = check_policy(cfg, st, policy, nullptr, episodes, T, reset_first, out)) return rc;
   if (cfg->n == 0) return EARL_OK;
   const PolicyArgs a{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, thresholds()}, *policy, act_out, episodes, reset_first};
-  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) for_each_env(cfg->n, [&](int i) { policy_rollout_env<true>(a, i, a.p.params); });
+  if (is_general(cfg)) for_each_env(cfg->n, [&](int i) { policy_rollout_env<true>(a, i, a.p.params); });
   else for_each_env(cfg->n, [&](int i) { policy_rollout_env<false>(a, i, a.p.params); });
   return EARL_OK;
 }
@@ -379,7 +364,7 @@ int earl_tabletop_policy_rollout_gaussian_cpu(const earl_tabletop_cfg* cfg, cons
   GaussianPolicyArgs a;
   static_cast<PolicyArgs&>(a) = PolicyArgs{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, thresholds()}, *policy, act_out, episodes, reset_first};
   a.head = *head;
-  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) for_each_env(cfg->n, [&](int i) { gaussian_rollout_env<true>(a, i, a.p.params); });
+  if (is_general(cfg)) for_each_env(cfg->n, [&](int i) { gaussian_rollout_env<true>(a, i, a.p.params); });
   else for_each_env(cfg->n, [&](int i) { gaussian_rollout_env<false>(a, i, a.p.params); });
   return EARL_OK;
 }
@@ -389,7 +374,7 @@ int earl_tabletop_population_rollout_cpu(const earl_tabletop_cfg* cfg, const ear
   if (int rc = check_population(cfg, st, policy, pop, head, episodes, T, reset_first, out)) return rc;
   if (cfg->n == 0) return EARL_OK;
   const PopulationArgs a = population_args(cfg, st, policy, pop, head, episodes, T, reset_first, out, act_out, summary, thresholds());
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  const bool general = is_general(cfg);
   for_each_env(cfg->n, [&](int i) {                       // the env with global id env_offset + i runs its member's parameters
     const float* params = a.p.params + population_param_offset(a.pop, a.k.cfg.env_offset + i);
     if (head) general ? gaussian_rollout_env<true>(a, i, params, &a.sum) : gaussian_rollout_env<false>(a, i, params, &a.sum);
@@ -438,23 +423,9 @@ int earl_tabletop3_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop
 int earl_tabletop3_reset_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const uint8_t* mask, float* obs) {
   return do_reset<3>(cfg, st, mask, nullptr, obs);
 }
-// host twin of earl_tabletop3_eval_episodes: the plain loop over the reset and the rollout above
 int earl_tabletop3_eval_episodes_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t episodes, int32_t T, const float* act,
                                      int64_t act_episode_stride, const earl_tabletop_out* out) {
-  if (episodes < 0) return fail(EARL_ERR_ARG, "episodes = %d < 0", episodes);
-  if (act_episode_stride < 0) return fail(EARL_ERR_ARG, "negative action stride");
-  if (int rc = check_common(cfg, st, 3)) return rc;
-  if (!act || !out) return fail(EARL_ERR_ARG, "act/out is NULL");
-  if (T < 0) return fail(EARL_ERR_ARG, "T = %d < 0", T);
-  for (int32_t e = 0; e < episodes; ++e) {
-    earl_tabletop_cfg c = *cfg;
-    c.counter += (uint64_t)e * (uint64_t)(T + 1);
-    const size_t rows = (size_t)e * (size_t)T * (size_t)cfg->n;
-    const earl_tabletop_out o{out->obs ? out->obs + rows * 20 : nullptr, out->reward ? out->reward + rows : nullptr, out->done ? out->done + rows : nullptr,
-                              out->success ? out->success + rows : nullptr, nullptr};
-    if (int rc = do_rollout<3>(&c, st, T, act + (size_t)e * (size_t)act_episode_stride, &o, true)) return rc;
-  }
-  return EARL_OK;
+  return do_eval<3>(cfg, st, episodes, T, act, act_episode_stride, out);
 }
 // host twin of earl_tabletop3_policy_rollout: the single-object loops (tabletop_policy.h) on Lane<3> and the 20-wide observation
 int earl_tabletop3_policy_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_mlp_policy* policy, const earl_policy_population* pop,

@@ -10,6 +10,7 @@
 #include "policy_check.h"   // contract::check_policy: the value network of the `_value` planner calls (check_plan_value below)
 
 namespace earl {
+struct ValueArgs;   // tabletop_value.h: complete wherever value_args (below) is called; not included here, so that the units that never plan do not depend on it
 namespace hostside {
 
 inline thread_local char g_err[512] = "";
@@ -80,6 +81,9 @@ inline int check_common(const earl_tabletop_cfg* cfg, const earl_tabletop_state*
     return fail(EARL_ERR_ARG, "3-object variant: wide_init / lifelong do not exist in the reference class");
   return EARL_OK;
 }
+
+// GENERAL of the kernels and the host loops: lifelong goal switching or the auto-reset is on (wrapped_step, tabletop_step.h)
+inline bool is_general(const earl_tabletop_cfg* cfg) { return cfg->goal_change_frequency > 0 || cfg->auto_reset; }
 
 // The argument rules of earl_tabletop[3]_branch_rollout and of its host twin (include/earl_tabletop.h), in the header's order.  The device launch is a 1-D grid
 // of K * ceil(n / kBranchBlock) workgroups of kBranchBlock lanes; the twin refuses the grids the device refuses.  *blocks = that count (0: nothing to do).
@@ -155,6 +159,9 @@ inline int check_plan_value(const earl_plan_value* pv, int obs_dim) {
     return fail(EARL_ERR_ARG, "value network: first hidden width %d of two > %d (a lane holds that layer in registers)", pv->value->dims[1], kPlanValueMaxH1);
   return EARL_OK;
 }
+
+// the checked block of a `_value` call as the launch carries it; value == NULL: no terminal term
+template <class V = ValueArgs> inline V value_args(const earl_plan_value* pv) { return V{pv->discount, pv->value ? *pv->value : earl_mlp_policy{}}; }
 
 }  // namespace hostside
 }  // namespace earl

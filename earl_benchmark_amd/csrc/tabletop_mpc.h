@@ -1,11 +1,11 @@
 // tabletop_mpc.h -- earl_tabletop[3]_mpc_rollout (include/earl_tabletop.h, "receding-horizon MPPI control"): what the gfx950 kernel (tabletop_mpc.hip: one
 // workgroup per env, one lane per branch) and the host twin (tabletop_host.cpp: one OpenMP iteration per env, the branches in ascending k) share.  The arithmetic
-// is tabletop_step.h's: wrapped_step, plan_clip, plan_candidate, plan_best / plan_best_merge, plan_weight, plan_accumulate, plan_new_mean.  The functions here only
-// say which plan rows, counters and output rows they are called with; the plan lives with the caller (LDS / a host array) behind `row(t, m)`, which hands out the
-// CLIPPED row t of the plan entering the iteration.
+// is tabletop_step.h's wrapped_step and tabletop_plan.h's plan_clip, plan_candidate, plan_best / plan_best_merge, plan_weight, plan_accumulate, plan_new_mean.  This
+// file owns the loop's argument blocks and argument rules, mpc_score and mpc_act: they only say which plan rows, counters and output rows those functions are called
+// with; the plan lives with the caller (LDS / a host array) behind `row(t, m)`, which hands out the CLIPPED row t of the plan entering the iteration.
 #pragma once
 #include "tabletop_hostside.h"
-#include "tabletop_step.h"
+#include "tabletop_plan.h"
 
 namespace earl {
 

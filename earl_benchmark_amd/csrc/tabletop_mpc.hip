@@ -1,6 +1,6 @@
 // tabletop_mpc.hip -- earl_tabletop_mpc_rollout / earl_tabletop3_mpc_rollout (include/earl_tabletop.h, "receding-horizon MPPI control"): T real steps of
 // plan -> act -> shift in ONE launch, equal bit for bit to the composition of earl_tabletop[3]_plan_mppi and the one-step rollout.  No cooperative launch, no flag
-// between workgroups; the per-lane functions are tabletop_step.h's (through tabletop_mpc.h), shared with the host twin.
+// between workgroups; the per-lane functions are tabletop_step.h's and tabletop_plan.h's (through tabletop_mpc.h), shared with the host twin.
 //
 // mpc_kernel  (tabletop_mpc_kernel.inc: one text with tabletop_mpc_value.hip)
 //             a workgroup owns ONE env for the whole launch; its lanes are the K branches, 64 * ceil(K / 64) of them, lane k >= K idle in the score pass.

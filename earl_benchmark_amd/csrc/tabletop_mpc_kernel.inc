@@ -174,12 +174,12 @@ int do_mpc(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const ea
   LoopArgs x{};
   static_cast<MpcArgs&>(x) = mpc_args(cfg, st, pp, T, out, mpc);
 #ifdef EARL_PLAN_VALUE
-  x.v = ValueArgs{pv->discount, pv->value ? *pv->value : earl_mlp_policy{}};
+  x.v = value_args(pv);
 #endif
   const size_t lds = mpc_lds_bytes<NOBJ>(pp->H, pp->K);
   const hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)cfg->n), block((unsigned)lanes);
-  if (cfg->goal_change_frequency > 0 || cfg->auto_reset) mpc_kernel<NOBJ, true><<<grid, block, lds, s>>>(x);
+  if (is_general(cfg)) mpc_kernel<NOBJ, true><<<grid, block, lds, s>>>(x);
   else mpc_kernel<NOBJ, false><<<grid, block, lds, s>>>(x);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(EARL_ERR_LAUNCH, "mpc_kernel: %s", hipGetErrorString(e));

@@ -1,6 +1,6 @@
 // tabletop_plan.hip -- earl_tabletop_plan_mppi / earl_tabletop3_plan_mppi / earl_tabletop_plan_candidates (include/earl_tabletop.h, "MPPI planning"): I iterations of
 // sample -> score -> reweight with the K candidate plans never in memory.  Per iteration two launches on the caller's stream, ordered by the stream alone (no
-// cooperative launch, no grid-wide barrier, no flag between workgroups); the per-lane functions are tabletop_step.h's plan_*, shared with the host twin.
+// cooperative launch, no grid-wide barrier, no flag between workgroups); the per-lane functions are tabletop_plan.h's plan_*, shared with the host twin.
 //
 // plan_score_kernel   (tabletop_plan_kernel.inc: one text with tabletop_plan_value.hip)
 //                     the branch launch's shape: one lane per (branch, env), a wave = 64 consecutive envs of ONE branch (so `k == 0`, the plan itself, is
@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tabletop_hostside.h"
-#include "tabletop_step.h"
+#include "tabletop_plan.h"
 
 using namespace earl;
 using namespace earl::hostside;

@@ -36,12 +36,12 @@ int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const e
   ScoreArgs p{};
   static_cast<PlanArgs&>(p) = plan_args(cfg, st, pp, mean, thresholds());
 #ifdef EARL_PLAN_VALUE
-  p.v = ValueArgs{pv->discount, pv->value ? *pv->value : earl_mlp_policy{}};
+  p.v = value_args(pv);
 #endif
   p.plan = plan;
   p.ret = ret;
   const unsigned tiles = (unsigned)(blocks / pp->K);
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  const bool general = is_general(cfg);
   const hipStream_t s = (hipStream_t)stream;
   for (int it = 0; it < pp->iterations; ++it) {
     const bool last = it + 1 == pp->iterations;

@@ -2,13 +2,13 @@
 // planner of tabletop_plan.hip with the score  ret = sum_t gamma^t r_t + gamma^H V(o_H),  the value network evaluated inside the score kernel.
 //
 // The SAME kernel text as tabletop_plan.hip's plan_score_kernel (tabletop_plan_kernel.inc), compiled with EARL_PLAN_VALUE: the argument block is PlanValueArgs and the
-// per-lane body is plan_score_body<.., true> (tabletop_step.h; the discounted sum and the network are tabletop_value.h's, shared with the host twin).  A translation
+// per-lane body is plan_score_body<.., true> (tabletop_plan.h; the discounted sum and the network are tabletop_value.h's, shared with the host twin).  A translation
 // unit of its own, the project's idiom for a second build: tabletop_plan.hip compiles to what it compiled to before, and the namespace `value` tells these kernels
 // from the value-free ones of the same name in a kernel trace.  The update launch is tabletop_plan.hip's (it sees returns only).
 #include <hip/hip_runtime.h>
 
 #include "tabletop_hostside.h"
-#include "tabletop_step.h"
+#include "tabletop_plan.h"
 
 using namespace earl;
 using namespace earl::hostside;

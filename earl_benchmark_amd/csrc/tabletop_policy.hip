@@ -22,7 +22,7 @@ extern "C" int earl_tabletop_policy_rollout(const earl_tabletop_cfg* cfg, const 
   if (int rc = check_policy(cfg, st, policy, nullptr, episodes, T, reset_first, out)) return rc;      // (before any HIP call: testable without a GPU)
   if (cfg->n == 0) return EARL_OK;
   const PolicyArgs a{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, thresholds()}, *policy, act_out, episodes, reset_first};
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  const bool general = is_general(cfg);
   const dim3 grid((unsigned)((cfg->n + kPolicyEnvsPerWg - 1) / kPolicyEnvsPerWg));
   const hipStream_t s = (hipStream_t)stream;
   // one instantiation per number of N-tiles a wave owns in the hidden -> hidden layer (its weights are that many x 64 registers per lane)

@@ -26,7 +26,7 @@ extern "C" int earl_tabletop_policy_rollout_gaussian(const earl_tabletop_cfg* cf
   GaussianPolicyArgs a;
   static_cast<PolicyArgs&>(a) = PolicyArgs{KArgs{*cfg, *st, *out, nullptr, nullptr, nullptr, nullptr, T, thresholds()}, *policy, act_out, episodes, reset_first};
   a.head = *head;
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  const bool general = is_general(cfg);
   const dim3 grid((unsigned)((cfg->n + kPolicyEnvsPerWg - 1) / kPolicyEnvsPerWg));
   const hipStream_t s = (hipStream_t)stream;
   switch (policy->n_layers == 3 ? (policy->dims[2] + 63) / 64 : 0) {      // as earl_tabletop_policy_rollout: N-tiles per wave of the hidden -> hidden layer

@@ -37,7 +37,7 @@ extern "C" int earl_tabletop_population_rollout(const earl_tabletop_cfg* cfg, co
   if (int rc = check_population(cfg, st, policy, pop, head, episodes, T, reset_first, out)) return rc;      // (before any HIP call: testable without a GPU)
   if (cfg->n == 0) return EARL_OK;
   const PopulationArgs a = population_args(cfg, st, policy, pop, head, episodes, T, reset_first, out, act_out, summary, thresholds());
-  const bool general = cfg->goal_change_frequency > 0 || cfg->auto_reset;
+  const bool general = is_general(cfg);
   // workgroups aligned to global env ids: the first one starts (env_offset mod 16) ids before the shard
   const int64_t lead = cfg->env_offset & (kPolicyEnvsPerWg - 1);
   const dim3 grid((unsigned)((lead + cfg->n + kPolicyEnvsPerWg - 1) / kPolicyEnvsPerWg));

@@ -556,7 +556,7 @@ int earl_tabletop_branch_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_ta
                                      const earl_episode_summary* summary, float* last_obs);
 int earl_tabletop3_branch_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
                                       const earl_episode_summary* summary, float* last_obs);
-/* host twins of earl_tabletop[3]_plan_mppi and earl_tabletop_plan_candidates: the kernels' per-lane functions (csrc/tabletop_step.h) in plain loops, the integer sums
+/* host twins of earl_tabletop[3]_plan_mppi and earl_tabletop_plan_candidates: the kernels' per-lane functions (csrc/tabletop_plan.h) in plain loops, the integer sums
  * in ascending k.  Bit-identical to the device in every output under the sparse reward; under the dense one ret / ret0 / best_ret within the branch launch's bound
  * (1e-6 relative of the sum of |reward|) and the plans not comparable.  They refuse what the device entry points refuse, the grids included. */
 int earl_tabletop_plan_mppi_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const float* mean, float* plan,

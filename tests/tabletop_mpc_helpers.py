@@ -27,10 +27,10 @@ OUTS = OUT4 + EXTRA                                       # every optional point
 
 # ---------------------------------------------------------------------------------------------------- one call
 def run_mpc(side, sc, plan, K, T, fill, I=1, sigma=0.3, inv_t=1.0, nc=7, iteration0=0, null=(), n_call=None, T_call=None, cfg_over=None, out_null=False,
-            mpc_null=False, params_null=False, tell=None):
+            mpc_null=False, params_null=False, tell=None, value=None):
   """one call -> (rc, results, Bands); results: clones of the state arrays ('st.*'), the optional outputs ('out.*', pre-filled with the pattern) and the plan
   ('io.plan').  Names in `null`: the seven optional outputs, 'plan', the state's arrays.  *_call / cfg_over / tell: what the call is TOLD, the buffers keeping
-  their sizes"""
+  their sizes.  value: None = earl_tabletop[3]_mpc_rollout; a tabletop_value_helpers.Value = earl_tabletop[3]_mpc_rollout_value"""
   n, H, D = sc.n, int(plan.shape[0]), sc.obs_dim
   r = ta.Run(side, fill, null)
   st = r.state(sc)
@@ -40,25 +40,21 @@ def run_mpc(side, sc, plan, K, T, fill, I=1, sigma=0.3, inv_t=1.0, nc=7, iterati
   r.blank('out.ret0', (T, I, n), torch.float64, n)
   r.blank('out.best_ret', (T, n), torch.float64, n)
   mpc = _abi.MpcOut(act=r.ptr('out.act'), plan=None if p is None else p.data_ptr(), ret0=r.ptr('out.ret0'), best_ret=r.ptr('out.best_ret'))
-  pp = h.params(K, H, I, sigma, inv_t, nc, iteration0)
-  for k, v in (tell or {}).items():
-    if k == 'sigma':
-      pp.sigma = (C.c_float * 3)(*v)
-    else:
-      setattr(pp, k, v)
+  pp = h.told(h.params(K, H, I, sigma, inv_t, nc, iteration0), tell)
+  fn, pv, keep = h.entry(side, sc, 'mpc_rollout', value, r)
   cfg = sc.cfg(**(cfg_over or {}))
   if n_call is not None:
     cfg.n = n_call
-  fn = getattr(side.lib, ta._pfx(sc) + 'mpc_rollout')
-  rc = fn(C.byref(cfg), C.byref(st), None if params_null else C.byref(pp), T if T_call is None else T_call, None if out_null else C.byref(out),
+  rc = fn(C.byref(cfg), C.byref(st), None if params_null else C.byref(pp), *pv, T if T_call is None else T_call, None if out_null else C.byref(out),
           None if mpc_null else C.byref(mpc), side.stream)
   side.sync()
+  del keep
   return rc, {k: v[3].clone() for k, v in r.b.bufs.items() if k.startswith(('st.', 'out.', 'io.'))}, r.b
 
 
 def run_ok(side, sc, plan, K, T, fill, **kw):
   rc, res, b = run_mpc(side, sc, plan, K, T, fill, **kw)
-  _abi.check(rc, 'mpc_rollout', side.lib)
+  _abi.check(rc, 'mpc_rollout' if kw.get('value') is None else 'mpc_rollout_value', side.lib)
   return res, b
 
 
@@ -85,14 +81,14 @@ def shift(plan, done, auto_reset):
   return nxt
 
 
-def composed(side, sc, plan, K, T, I=1, sigma=0.3, inv_t=1.0, nc=7, iteration0=0):
+def composed(side, sc, plan, K, T, I=1, sigma=0.3, inv_t=1.0, nc=7, iteration0=0, value=None):
   """the header's definition, call by call -> the fused call's results under the same keys, and what the coverage conditions read: 'rets' [T, K, n] (the last
-  iteration's returns of each step), 'dones' [T, n], 'plans' [T + 1, H, n, 3] (P_0 .. P_T)"""
+  iteration's returns of each step), 'dones' [T, n], 'plans' [T + 1, H, n, 3] (P_0 .. P_T).  value: the planner of every step is earl_tabletop[3]_plan_mppi_value"""
   cur, P = sc, np.asarray(plan, F32)
   rows = {k: [] for k in OUTS}
   rets, plans = [], [P]
   for s in range(T):
-    res, b = h.run_ok(side, cur, P, K, 0x00, I=I, sigma=sigma, inv_t=inv_t, nc=(nc + s) & 0xFFFFFFFF, iteration0=iteration0)
+    res, b = h.run_ok(side, cur, P, K, 0x00, I=I, sigma=sigma, inv_t=inv_t, nc=(nc + s) & 0xFFFFFFFF, iteration0=iteration0, value=value)
     b.check('the reference\'s plan_mppi')
     tb.state_untouched(res, cur, 'the reference\'s plan_mppi')
     Pp = res['out.plan'].cpu().numpy()
@@ -117,11 +113,12 @@ def composed(side, sc, plan, K, T, I=1, sigma=0.3, inv_t=1.0, nc=7, iteration0=0
 _REF = {}
 
 
-def reference(side, cs, T, key=None, sc=None, plan=None, K=None, **over):
-  key = ((id(cs), T) if key is None else key, side.device)
+def reference(side, cs, T, key=None, sc=None, plan=None, K=None, value=None, **over):
+  """the composed reference, made once per (case and T, or key; value specification; side); the entry keeps the specification's net alive (tabletop_plan_helpers.reference)"""
+  key = ((id(cs), T) if key is None else key, None if value is None else value.key, side.device)
   if key not in _REF:
-    _REF[key] = composed(side, cs.sc if sc is None else sc, cs.mean if plan is None else plan, cs.K if K is None else K, T, **{**cs.kw, **over})
-  return _REF[key]
+    _REF[key] = (value, composed(side, cs.sc if sc is None else sc, cs.mean if plan is None else plan, cs.K if K is None else K, T, value=value, **{**cs.kw, **over}))
+  return _REF[key][1]
 
 
 def compare(got, ref, what, skip=()):
@@ -147,12 +144,12 @@ def check_coverage(cs, ref, general=False):
     assert bool(any((h.weights(r, cs.kw['inv_t'])[0] == 0).any() for r in rets)), 'no W_k == 0 under the dense reward'
 
 
-def check_case(side, cs, T, key=None, sc=None, plan=None, K=None, **over):
+def check_case(side, cs, T, key=None, sc=None, plan=None, K=None, value=None, **over):
   """both fills: bands intact, every output overwritten, the two runs equal; every output, the final plan and the final state equal to the composed reference"""
   sc, plan, K = cs.sc if sc is None else sc, cs.mean if plan is None else plan, cs.K if K is None else K
-  ref = reference(side, cs, T, key, sc, plan, K, **over)
-  what = f'mpc T={T} {cs.what}' + (f' [{key}]' if key is not None else '')
-  res = ta.both_fills(run_ok, side, sc, plan, K, T, what=what, **{**cs.kw, **over})
+  ref = reference(side, cs, T, key, sc, plan, K, value, **over)
+  what = f'mpc T={T} {cs.what}' + (f' [{key}]' if key is not None else '') + (f' {value.what}' if value is not None else '')
+  res = ta.both_fills(run_ok, side, sc, plan, K, T, what=what, value=value, **{**cs.kw, **over})
   compare(res, ref, what)
   return res
 

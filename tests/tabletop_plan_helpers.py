@@ -149,18 +149,20 @@ def branch_returns(side, sc, act):
   return res['out.ret'].cpu().numpy()
 
 
-def oracle(side, sc, mean, K, I, sigma, inv_t, nc, iteration0=0, fast=False):
-  """-> the five outputs as host tensors under 'out.*', and 'iters': per iteration dict(act, m, ret, W, tail) for the coverage conditions"""
+def oracle(side, sc, mean, K, I, sigma, inv_t, nc, iteration0=0, fast=False, value=None):
+  """-> the five outputs as host tensors under 'out.*', and 'iters': per iteration dict(act, m, ret, W, tail, ..) for the coverage conditions.  value (a
+  tabletop_value_helpers.Value): the returns are its discounted sums of K existing rollouts plus the net on the last rows, not the branch launch's"""
   H, n = int(mean.shape[0]), sc.n
   cfg = sc.cfg()
   plan, ret0, iters = np.asarray(mean, F32), np.empty((I, n), F64), []
   for i in range(I):
     act, m, tail = candidates(cfg, K, H, iteration0 + i, sigma, nc, plan)
-    ret = branch_returns(side, sc, act)
+    more = dict(ret=branch_returns(side, sc, act)) if value is None else value.returns(side, sc, act)
+    ret = more['ret']
     W, beta, bk = weights(ret, inv_t)
     plan = (update_fast if fast else update)(act, m, W)
     ret0[i] = ret[0]
-    iters.append(dict(act=act, m=m, ret=ret, W=W, tail=tail, plan=plan))
+    iters.append(dict(act=act, m=m, W=W, tail=tail, plan=plan, bk=bk, **more))
   out = {'out.plan': plan, 'out.ret': ret, 'out.ret0': ret0, 'out.best_ret': beta, 'out.best_k': bk}
   return {**{k: ta._t(v) for k, v in out.items()}, 'iters': iters}
 
@@ -172,10 +174,30 @@ def params(K, H, I, sigma, inv_t, nc, iteration0=0):
                          inv_temperature=float(inv_t))
 
 
+def told(pp, tell):
+  """pp with the fields of `tell` set: earl_plan_params as the call is TOLD them, the buffers keeping their sizes"""
+  for k, v in (tell or {}).items():
+    if k == 'sigma':
+      pp.sigma = (C.c_float * 3)(*v)
+    else:
+      setattr(pp, k, v)
+  return pp
+
+
+def entry(side, sc, name, value, r):
+  """-> (the entry point `name` of the scene's env -- its `_value` form when a value specification is given --, that form's extra argument as a tuple, what must
+  stay alive until the call returns); the net's parameters go into r's banded buffer 'in.value'"""
+  if value is None:
+    return getattr(side.lib, ta._pfx(sc) + name), (), None
+  pv, keep = value.block(r)
+  return getattr(side.lib, ta._pfx(sc) + name + '_value'), (None if pv is None else C.byref(pv),), (pv, keep)
+
+
 def run_plan(side, sc, mean, K, fill, I=1, sigma=0.3, inv_t=1.0, nc=7, iteration0=0, null=(), alias=False, n_call=None, cfg_over=None, mean_null=False,
-             params_null=False, plan_ptr=None, tell=None):
+             params_null=False, plan_ptr=None, tell=None, value=None):
   """one call -> (rc, results, Bands).  `alias`: plan is the mean's buffer (which then counts as the output 'plan').  tell: fields of earl_plan_params as the call
-  is TOLD them, the buffers keeping their sizes; plan_ptr: the plan's address as a function of the mean's"""
+  is TOLD them, the buffers keeping their sizes; plan_ptr: the plan's address as a function of the mean's.  value: None = earl_tabletop[3]_plan_mppi; a
+  tabletop_value_helpers.Value = earl_tabletop[3]_plan_mppi_value with its discount, net and the block as told"""
   n, H = sc.n, int(mean.shape[0])
   r = ta.Run(side, fill, null)
   st = r.state(sc)
@@ -188,28 +210,24 @@ def run_plan(side, sc, mean, K, fill, I=1, sigma=0.3, inv_t=1.0, nc=7, iteration
   r.blank('out.ret0', (I, n), torch.float64, n)
   r.blank('out.best_ret', (n,), torch.float64, n)
   r.blank('out.best_k', (n,), torch.int32, n)
-  pp = params(K, H, I, sigma, inv_t, nc, iteration0)
-  for k, v in (tell or {}).items():
-    if k == 'sigma':
-      pp.sigma = (C.c_float * 3)(*v)
-    else:
-      setattr(pp, k, v)
+  pp = told(params(K, H, I, sigma, inv_t, nc, iteration0), tell)
+  fn, pv, keep = entry(side, sc, 'plan_mppi', value, r)
   cfg = sc.cfg(**(cfg_over or {}))
   if n_call is not None:
     cfg.n = n_call
   pl = None if plan is None else plan.data_ptr()
   if plan_ptr is not None:
     pl = plan_ptr(m.data_ptr())
-  fn = getattr(side.lib, ta._pfx(sc) + 'plan_mppi')
-  rc = fn(C.byref(cfg), C.byref(st), None if params_null else C.byref(pp), None if mean_null else m.data_ptr(), pl, r.ptr('out.ret'), r.ptr('out.ret0'),
+  rc = fn(C.byref(cfg), C.byref(st), None if params_null else C.byref(pp), *pv, None if mean_null else m.data_ptr(), pl, r.ptr('out.ret'), r.ptr('out.ret0'),
           r.ptr('out.best_ret'), r.ptr('out.best_k'), side.stream)
   side.sync()
+  del keep
   return rc, {k: v[3].clone() for k, v in r.b.bufs.items() if k.startswith(('st.', 'out.'))}, r.b
 
 
 def run_ok(side, sc, mean, K, fill, **kw):
   rc, res, b = run_plan(side, sc, mean, K, fill, **kw)
-  _abi.check(rc, 'plan_mppi', side.lib)
+  _abi.check(rc, 'plan_mppi' if kw.get('value') is None else 'plan_mppi_value', side.lib)
   return res, b
 
 
@@ -218,12 +236,7 @@ def run_candidates(side, sc, mean, K, fill, j=0, sigma=0.3, nc=7, n_call=None, m
   r = ta.Run(side, fill)
   m = r.put('in.mean', mean, n * 3)
   a = r.blank('out.act', (K, H, n, 3), torch.float32, n * 3)
-  pp = params(K, H, 1, sigma, 1.0, nc)
-  for k, v in (tell or {}).items():
-    if k == 'sigma':
-      pp.sigma = (C.c_float * 3)(*v)
-    else:
-      setattr(pp, k, v)
+  pp = told(params(K, H, 1, sigma, 1.0, nc), tell)
   cfg = sc.cfg()
   if n_call is not None:
     cfg.n = n_call
@@ -260,13 +273,14 @@ def case(*args, **kw):
 _REF = {}
 
 
-def reference(cs, side, key=None, sc=None, mean=None, K=None, **over):
-  key = (id(cs) if key is None else key, side.device)
+def reference(cs, side, key=None, sc=None, mean=None, K=None, value=None, fast=False, **over):
+  """the oracle of the case, made once per (case or key, value specification, side); the entry keeps the specification's net alive, so that its id stays its own"""
+  key = (id(cs) if key is None else key, None if value is None else value.key, side.device)
   if key not in _REF:
     kw = {**cs.kw, **over}
-    _REF[key] = oracle(side, cs.sc if sc is None else sc, cs.mean if mean is None else mean, cs.K if K is None else K, kw['I'], kw['sigma'], kw['inv_t'], kw['nc'],
-                       kw['iteration0'])
-  return _REF[key]
+    _REF[key] = (value, oracle(side, cs.sc if sc is None else sc, cs.mean if mean is None else mean, cs.K if K is None else K, kw['I'], kw['sigma'], kw['inv_t'], kw['nc'],
+                               kw['iteration0'], fast=fast, value=value))
+  return _REF[key][1]
 
 
 def check_coverage(cs, ref):
@@ -290,13 +304,20 @@ def state_untouched(res, sc, what):
   tb.state_untouched(res, sc, what)
 
 
-def check_case(side, cs, key=None, sc=None, mean=None, K=None, alias=False, **over):
-  """both fills: bands intact, every output overwritten; the state untouched; every output equal to the oracle, bit for bit"""
+def check_case(side, cs, key=None, sc=None, mean=None, K=None, alias=False, value=None, fast=False, nan_returns=False, **over):
+  """both fills: bands intact, every output overwritten; the state untouched; every output equal to the oracle, bit for bit.  nan_returns: the case has NaN returns,
+  whose sign and payload the contract leaves open (the oracle's are numpy's, the device's its own): ret and ret0 are NaN in the same places and equal elsewhere"""
   sc, mean, K = cs.sc if sc is None else sc, cs.mean if mean is None else mean, cs.K if K is None else K
-  ref = reference(cs, side, key, sc, mean, K, **over)
-  res = ta.both_fills(run_ok, side, sc, mean, K, what=cs.what, alias=alias, **{**cs.kw, **over})
-  state_untouched(res, sc, cs.what)
-  compare(res, ref, cs.what)
+  ref = reference(cs, side, key, sc, mean, K, value, fast, **over)
+  what = cs.what if value is None else f'{cs.what} {value.what}'
+  res = ta.both_fills(run_ok, side, sc, mean, K, what=what, alias=alias, value=value, **{**cs.kw, **over})
+  state_untouched(res, sc, what)
+  if nan_returns:
+    compare(res, ref, what, ['plan', 'best_ret', 'best_k'])
+    for k in ('ret', 'ret0'):
+      ta.same(res['out.' + k].cpu(), ref['out.' + k].cpu(), f'{what}: {k}', atol=0.0)
+  else:
+    compare(res, ref, what)
   return res
 
 

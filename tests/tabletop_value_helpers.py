@@ -1,6 +1,7 @@
 """Drivers and the oracles of earl_tabletop[3]_plan_mppi_value / earl_tabletop[3]_mpc_rollout_value (include/earl_tabletop.h, "discounted MPPI with a terminal value")
 for tests/test_tabletop_value.py (libearl_host.so) and tests/test_tabletop_value_gpu.py (libearl_hip.so); a plain module on tests/tabletop_abi.py's banded buffers and
-the scenes, cases and integer oracle of tests/tabletop_plan_helpers.py / tabletop_mpc_helpers.py.
+the scenes, cases, drivers, integer oracle and composed reference of tests/tabletop_plan_helpers.py / tabletop_mpc_helpers.py, which take a `Value` (below) as `value=`:
+the `_value` entry point in place of the plain one, the oracle's returns from `Value.returns` in place of the branch launch.
 
 THE PLANNER'S ORACLE uses none of the new code:
   candidates   tabletop_plan_helpers.candidates (a numpy Philox, the policy-math host build), checked against the existing earl_tabletop_plan_candidates of the side
@@ -93,94 +94,33 @@ def distance_net(nobj):
   return Net(D, (16,), 'relu', 'none', layers=[(W0, np.zeros(16, F32)), (Wo, np.zeros(1, F32))])
 
 
-# ---------------------------------------------------------------------------------------------------- one call
-def _pv(r, gamma, vnet, pv_null=False, net_tell=None, params_null=False):
-  """-> (earl_plan_value or None, what must stay alive)"""
-  if pv_null:
-    return None, None
-  if vnet is None:
-    return _abi.PlanValue(discount=gamma, value=None), None
-  buf = r.put('in.value', vnet.params, len(vnet.params))
-  s = vnet.struct(None if params_null else buf.data_ptr(), **(net_tell or {}))
-  return _abi.PlanValue(discount=gamma, value=C.pointer(s)), s
+# ---------------------------------------------------------------------------------------------------- the value specification
+class Value:
+  """what `value=` of tabletop_plan_helpers.run_plan / run_ok / oracle and tabletop_mpc_helpers.run_mpc / run_ok / composed takes: the `_value` entry point with this
+  discount and net (None: no terminal term), and the block as the call is TOLD it -- pv_null: the earl_plan_value pointer itself NULL; net_tell: fields of the net's
+  earl_mlp_policy; value_params_null: its parameter pointer NULL.  For the oracle: `returns`, the discounted sums"""
 
+  def __init__(self, net=None, gamma=GAMMA, pv_null=False, net_tell=None, value_params_null=False):
+    self.net, self.gamma, self.pv_null, self.net_tell, self.value_params_null = net, gamma, pv_null, net_tell, value_params_null
+    self.key = (id(net), gamma)                            # of a cached reference (which keeps the net alive)
+    self.what = f'gamma={gamma} {net.what if net else "no value"}'
 
-def run_plan(side, sc, mean, K, fill, gamma=GAMMA, vnet=None, I=1, sigma=0.3, inv_t=1.0, nc=7, iteration0=0, null=(), alias=False, n_call=None, cfg_over=None,
-             mean_null=False, params_null=False, plan_ptr=None, tell=None, pv_null=False, net_tell=None, value_params_null=False):
-  """tabletop_plan_helpers.run_plan on the `_value` entry point"""
-  n, H = sc.n, int(mean.shape[0])
-  r = ta.Run(side, fill, null)
-  st = r.state(sc)
-  if alias:
-    mm = plan = r.put('out.plan', mean, n * 3)
-  else:
-    mm = r.put('in.mean', mean, n * 3)
-    plan = r.blank('out.plan', (H, n, 3), torch.float32, n * 3)
-  r.blank('out.ret', (K, n), torch.float64, n)
-  r.blank('out.ret0', (I, n), torch.float64, n)
-  r.blank('out.best_ret', (n,), torch.float64, n)
-  r.blank('out.best_k', (n,), torch.int32, n)
-  pp = h.params(K, H, I, sigma, inv_t, nc, iteration0)
-  for k, v in (tell or {}).items():
-    if k == 'sigma':
-      pp.sigma = (C.c_float * 3)(*v)
-    else:
-      setattr(pp, k, v)
-  pv, keep = _pv(r, gamma, vnet, pv_null, net_tell, value_params_null)
-  cfg = sc.cfg(**(cfg_over or {}))
-  if n_call is not None:
-    cfg.n = n_call
-  pl = None if plan is None else plan.data_ptr()
-  if plan_ptr is not None:
-    pl = plan_ptr(mm.data_ptr())
-  fn = getattr(side.lib, ta._pfx(sc) + 'plan_mppi_value')
-  rc = fn(C.byref(cfg), C.byref(st), None if params_null else C.byref(pp), None if pv is None else C.byref(pv), None if mean_null else mm.data_ptr(), pl,
-          r.ptr('out.ret'), r.ptr('out.ret0'), r.ptr('out.best_ret'), r.ptr('out.best_k'), side.stream)
-  side.sync()
-  del keep
-  return rc, {k: v[3].clone() for k, v in r.b.bufs.items() if k.startswith(('st.', 'out.'))}, r.b
+  def block(self, r):
+    """-> (earl_plan_value or None, what must stay alive); the parameters in r's banded buffer 'in.value'"""
+    if self.pv_null:
+      return None, None
+    if self.net is None:
+      return _abi.PlanValue(discount=self.gamma, value=None), None
+    buf = r.put('in.value', self.net.params, len(self.net.params))
+    s = self.net.struct(None if self.value_params_null else buf.data_ptr(), **(self.net_tell or {}))
+    return _abi.PlanValue(discount=self.gamma, value=C.pointer(s)), s
 
-
-def run_ok(side, sc, mean, K, fill, **kw):
-  rc, res, b = run_plan(side, sc, mean, K, fill, **kw)
-  _abi.check(rc, 'plan_mppi_value', side.lib)
-  return res, b
-
-
-def run_mpc(side, sc, plan, K, T, fill, gamma=GAMMA, vnet=None, I=1, sigma=0.3, inv_t=1.0, nc=7, iteration0=0, null=(), n_call=None, T_call=None, cfg_over=None,
-            out_null=False, mpc_null=False, params_null=False, tell=None, pv_null=False, net_tell=None, value_params_null=False):
-  """tabletop_mpc_helpers.run_mpc on the `_value` entry point"""
-  n, H, D = sc.n, int(plan.shape[0]), sc.obs_dim
-  r = ta.Run(side, fill, null)
-  st = r.state(sc)
-  p = None if 'plan' in r.null else r.put('io.plan', plan, n * 3)
-  out = r.out((T, n), D)
-  r.blank('out.act', (T, n, 3), torch.float32, n * 3)
-  r.blank('out.ret0', (T, I, n), torch.float64, n)
-  r.blank('out.best_ret', (T, n), torch.float64, n)
-  mpc = _abi.MpcOut(act=r.ptr('out.act'), plan=None if p is None else p.data_ptr(), ret0=r.ptr('out.ret0'), best_ret=r.ptr('out.best_ret'))
-  pp = h.params(K, H, I, sigma, inv_t, nc, iteration0)
-  for k, v in (tell or {}).items():
-    if k == 'sigma':
-      pp.sigma = (C.c_float * 3)(*v)
-    else:
-      setattr(pp, k, v)
-  pv, keep = _pv(r, gamma, vnet, pv_null, net_tell, value_params_null)
-  cfg = sc.cfg(**(cfg_over or {}))
-  if n_call is not None:
-    cfg.n = n_call
-  fn = getattr(side.lib, ta._pfx(sc) + 'mpc_rollout_value')
-  rc = fn(C.byref(cfg), C.byref(st), None if params_null else C.byref(pp), None if pv is None else C.byref(pv), T if T_call is None else T_call,
-          None if out_null else C.byref(out), None if mpc_null else C.byref(mpc), side.stream)
-  side.sync()
-  del keep
-  return rc, {k: v[3].clone() for k, v in r.b.bufs.items() if k.startswith(('st.', 'out.', 'io.'))}, r.b
-
-
-def run_mpc_ok(side, sc, plan, K, T, fill, **kw):
-  rc, res, b = run_mpc(side, sc, plan, K, T, fill, **kw)
-  _abi.check(rc, 'mpc_rollout_value', side.lib)
-  return res, b
+  def returns(self, side, sc, act):
+    """item 3 of the `_value` contract for the candidates act [K, H, n, 3], with none of the new code -> dict(ret, plain, abs, V, last)"""
+    rew, last = branch_rollouts(side, sc, act)
+    V = None if self.net is None else self.net.forward(last)
+    ret, plain, absr = discounted(rew, self.gamma, V)
+    return dict(ret=ret, plain=plain, abs=absr, V=V, last=last)
 
 
 # ---------------------------------------------------------------------------------------------------- the planner's oracle
@@ -211,50 +151,13 @@ def discounted(rew, gamma, V=None):
   return ret, plain, np.abs(rew.astype(F64)).sum(1)
 
 
-def oracle(side, sc, mean, K, I, sigma, inv_t, nc, gamma, vnet, iteration0=0, fast=False):
-  H, n = int(mean.shape[0]), sc.n
-  cfg = sc.cfg()
-  plan, ret0, iters = np.asarray(mean, F32), np.empty((I, n), F64), []
-  for i in range(I):
-    act, mm, tail = h.candidates(cfg, K, H, iteration0 + i, sigma, nc, plan)
-    rew, last = branch_rollouts(side, sc, act)
-    V = None if vnet is None else vnet.forward(last)
-    ret, plain, absr = discounted(rew, gamma, V)
-    W, beta, bk = h.weights(ret, inv_t)
-    plan = (h.update_fast if fast else h.update)(act, mm, W)
-    ret0[i] = ret[0]
-    iters.append(dict(act=act, m=mm, ret=ret, plain=plain, W=W, V=V, last=last, plan=plan, abs=absr, bk=bk))
-  out = {'out.plan': plan, 'out.ret': ret, 'out.ret0': ret0, 'out.best_ret': beta, 'out.best_k': bk}
-  return {**{k: ta._t(v) for k, v in out.items()}, 'iters': iters}
+def reference(side, cs, vnet, gamma=GAMMA, **kw):
+  return h.reference(cs, side, value=Value(vnet, gamma), **kw)
 
 
-_REF = {}
-
-
-def reference(side, cs, vnet, gamma=GAMMA, key=None, sc=None, mean=None, K=None, fast=False, **over):
-  key = ((id(cs), id(vnet), gamma) if key is None else key, side.device)
-  if key not in _REF:
-    kw = {**cs.kw, **over}
-    _REF[key] = oracle(side, cs.sc if sc is None else sc, cs.mean if mean is None else mean, cs.K if K is None else K, kw['I'], kw['sigma'], kw['inv_t'], kw['nc'], gamma,
-                       vnet, kw['iteration0'], fast=fast)
-  return _REF[key]
-
-
-def check_case(side, cs, vnet, gamma=GAMMA, key=None, sc=None, mean=None, K=None, alias=False, fast=False, nan_returns=False, **over):
-  """both fills: bands intact, every output overwritten; the state untouched; every output equal to the oracle, bit for bit.  nan_returns: the case has NaN returns,
-  whose sign and payload the contract leaves open (the oracle's are numpy's, the device's its own): ret and ret0 are NaN in the same places and equal elsewhere"""
-  sc, mean, K = cs.sc if sc is None else sc, cs.mean if mean is None else mean, cs.K if K is None else K
-  ref = reference(side, cs, vnet, gamma, key, sc, mean, K, fast=fast, **over)
-  what = f'{cs.what} gamma={gamma} {vnet.what if vnet else "no value"}'
-  res = ta.both_fills(run_ok, side, sc, mean, K, what=what, alias=alias, gamma=gamma, vnet=vnet, **{**cs.kw, **over})
-  tb.state_untouched(res, sc, what)
-  if nan_returns:
-    h.compare(res, ref, what, ['plan', 'best_ret', 'best_k'])
-    for k in ('ret', 'ret0'):
-      ta.same(res['out.' + k].cpu(), ref['out.' + k].cpu(), f'{what}: {k}', atol=0.0)
-  else:
-    h.compare(res, ref, what)
-  return res
+def check_case(side, cs, vnet, gamma=GAMMA, **kw):
+  """tabletop_plan_helpers.check_case on the `_value` entry point: both fills, the state untouched, every output equal to the oracle"""
+  return h.check_case(side, cs, value=Value(vnet, gamma), **kw)
 
 
 def check_coverage(side, cs, vnet, ref):
@@ -281,10 +184,10 @@ def check_candidates_entry(side, cs):
 
 def check_pointers(side, cs, vnet, full):
   for name in h.OPTIONAL:
-    res = ta.both_fills(run_ok, side, cs.sc, cs.mean, cs.K, what=f'{cs.what} without {name}', null=(name,), vnet=vnet, **cs.kw)
+    res = ta.both_fills(h.run_ok, side, cs.sc, cs.mean, cs.K, what=f'{cs.what} without {name}', null=(name,), value=Value(vnet), **cs.kw)
     assert 'out.' + name not in res
     h.compare(res, full, f'{cs.what} without {name}', [k for k in OUTS if k != name])
-  res = ta.both_fills(run_ok, side, cs.sc, cs.mean, cs.K, what=f'{cs.what} in place', alias=True, vnet=vnet, **cs.kw)
+  res = ta.both_fills(h.run_ok, side, cs.sc, cs.mean, cs.K, what=f'{cs.what} in place', alias=True, value=Value(vnet), **cs.kw)
   h.compare(res, full, f'{cs.what} in place')
 
 
@@ -295,30 +198,30 @@ def check_identity(side, cs, T=3):
   loop, b = m.run_ok(side, cs.sc, cs.mean, cs.K, T, 0x00, **cs.kw)
   for vnet in (None, net(D, (16, 16), 'tanh', 'tanh', zero=True), net(D, (48,), 'relu', 'none', zero=True)):
     what = f'{cs.what} gamma = 1, {"no network" if vnet is None else "zero " + vnet.what}'
-    res = ta.both_fills(run_ok, side, cs.sc, cs.mean, cs.K, what=what, gamma=1.0, vnet=vnet, **cs.kw)
+    res = ta.both_fills(h.run_ok, side, cs.sc, cs.mean, cs.K, what=what, value=Value(vnet, 1.0), **cs.kw)
     h.compare(res, free, what)
-    res = ta.both_fills(run_mpc_ok, side, cs.sc, cs.mean, cs.K, T, what='mpc ' + what, gamma=1.0, vnet=vnet, **cs.kw)
+    res = ta.both_fills(m.run_ok, side, cs.sc, cs.mean, cs.K, T, what='mpc ' + what, value=Value(vnet, 1.0), **cs.kw)
     m.compare(res, loop, 'mpc ' + what)
 
 
 def check_chaining(side, cs, vnet, I=3):
   kw = {**cs.kw, 'I': I}
-  whole, b = run_ok(side, cs.sc, cs.mean, cs.K, 0x00, vnet=vnet, **kw)
+  whole, b = h.run_ok(side, cs.sc, cs.mean, cs.K, 0x00, value=Value(vnet), **kw)
   plan, ret0 = cs.mean, []
   for j in range(I):
-    one, b = run_ok(side, cs.sc, plan, cs.K, 0xFF, vnet=vnet, **{**kw, 'I': 1, 'iteration0': j})
+    one, b = h.run_ok(side, cs.sc, plan, cs.K, 0xFF, value=Value(vnet), **{**kw, 'I': 1, 'iteration0': j})
     b.check(f'chaining, call {j}')
     plan = one['out.plan'].cpu().numpy()
     ret0.append(one['out.ret0'].cpu())
   h.compare(one, whole, 'chained calls vs one call', ['plan', 'ret', 'best_ret', 'best_k'])
   ta.same(torch.cat(ret0), whole['out.ret0'].cpu(), 'chained calls vs one call: ret0')
-  h.compare(whole, oracle(side, cs.sc, cs.mean, cs.K, I, kw['sigma'], kw['inv_t'], kw['nc'], GAMMA, vnet), 'three iterations vs the oracle')
+  h.compare(whole, h.oracle(side, cs.sc, cs.mean, cs.K, I, kw['sigma'], kw['inv_t'], kw['nc'], value=Value(vnet)), 'three iterations vs the oracle')
 
 
 def check_shards(side, cs, vnet):
   full = check_case(side, cs, vnet)
   for lo, hi in ((0, 40), (40, 70)):
-    part, b = run_ok(side, tb.shard(cs.sc, lo, hi), np.ascontiguousarray(cs.mean[:, lo:hi]), cs.K, 0x00, vnet=vnet, **cs.kw)
+    part, b = h.run_ok(side, tb.shard(cs.sc, lo, hi), np.ascontiguousarray(cs.mean[:, lo:hi]), cs.K, 0x00, value=Value(vnet), **cs.kw)
     b.check(f'shard {lo}..{hi}')
     for k in OUTS:
       whole = full['out.' + k]
@@ -371,57 +274,20 @@ def check_steering(side, nobj):
 
 
 # ---------------------------------------------------------------------------------------------------- MPC: the composed reference
-def composed(side, sc, plan, K, T, gamma, vnet, I=1, sigma=0.3, inv_t=1.0, nc=7, iteration0=0):
-  """tabletop_mpc_helpers.composed with earl_tabletop[3]_plan_mppi_value as the planner"""
-  cur, P = sc, np.asarray(plan, F32)
-  rows = {k: [] for k in m.OUTS}
-  rets, plans = [], [P]
-  for s in range(T):
-    res, b = run_ok(side, cur, P, K, 0x00, gamma=gamma, vnet=vnet, I=I, sigma=sigma, inv_t=inv_t, nc=(nc + s) & 0xFFFFFFFF, iteration0=iteration0)
-    b.check('the reference\'s plan_mppi_value')
-    Pp = res['out.plan'].cpu().numpy()
-    out, b = ta.run_rollout(side, cur, np.ascontiguousarray(Pp[:1]), 0x00)
-    b.check('the reference\'s rollout')
-    for k in m.OUT4:
-      rows[k].append(out['out.' + k].cpu()[0])
-    rows['act'].append(ta._t(Pp[0]))
-    rows['ret0'].append(res['out.ret0'].cpu())
-    rows['best_ret'].append(res['out.best_ret'].cpu())
-    rets.append(res['out.ret'].cpu().numpy())
-    P = m.shift(Pp, out['out.done'].cpu().numpy()[0], bool(cur.cfg().auto_reset))
-    plans.append(P)
-    cur = m.after(sc, out, sc.counter + s + 1)
-  ref = {'out.' + k: torch.stack(v) for k, v in rows.items()}
-  ref['io.plan'] = ta._t(P)
-  ref.update({'st.' + k: ta._t(cur.state[k]) for k in ta.STATE})
-  ref.update(rets=np.stack(rets), dones=ref['out.done'].numpy().astype(bool), plans=np.stack(plans))
-  return ref
+def mpc_reference(side, cs, T, vnet, gamma=GAMMA, **kw):
+  return m.reference(side, cs, T, value=Value(vnet, gamma), **kw)
 
 
-_MREF = {}
-
-
-def mpc_reference(side, cs, T, vnet, gamma=GAMMA, key=None, sc=None, K=None, **over):
-  key = ((id(cs), T, id(vnet), gamma) if key is None else key, side.device)
-  if key not in _MREF:
-    _MREF[key] = composed(side, cs.sc if sc is None else sc, cs.mean, cs.K if K is None else K, T, gamma, vnet, **{**cs.kw, **over})
-  return _MREF[key]
-
-
-def check_mpc_case(side, cs, T, vnet, gamma=GAMMA, key=None, sc=None, K=None, **over):
-  sc, K = cs.sc if sc is None else sc, cs.K if K is None else K
-  ref = mpc_reference(side, cs, T, vnet, gamma, key, sc, K, **over)
-  what = f'mpc T={T} {cs.what} gamma={gamma} {vnet.what if vnet else "no value"}'
-  res = ta.both_fills(run_mpc_ok, side, sc, cs.mean, K, T, what=what, gamma=gamma, vnet=vnet, **{**cs.kw, **over})
-  m.compare(res, ref, what)
-  return res
+def check_mpc_case(side, cs, T, vnet, gamma=GAMMA, **kw):
+  """tabletop_mpc_helpers.check_case on the `_value` entry point, against the composition with earl_tabletop[3]_plan_mppi_value as the planner"""
+  return m.check_case(side, cs, T, value=Value(vnet, gamma), **kw)
 
 
 def check_mpc_chaining(side, cs, vnet, T1=4, T2=5):
   whole = check_mpc_case(side, cs, T1 + T2, vnet)
-  a, b = run_mpc_ok(side, cs.sc, cs.mean, cs.K, T1, 0x00, vnet=vnet, **cs.kw)
+  a, b = m.run_ok(side, cs.sc, cs.mean, cs.K, T1, 0x00, value=Value(vnet), **cs.kw)
   nxt = m.after(cs.sc, a, cs.sc.counter + T1)
-  z, b = run_mpc_ok(side, nxt, a['io.plan'].cpu().numpy(), cs.K, T2, 0xFF, vnet=vnet, **{**cs.kw, 'nc': cs.kw['nc'] + T1})
+  z, b = m.run_ok(side, nxt, a['io.plan'].cpu().numpy(), cs.K, T2, 0xFF, value=Value(vnet), **{**cs.kw, 'nc': cs.kw['nc'] + T1})
   b.check('chaining, second call')
   for k in whole:
     if k.startswith('out.'):
@@ -489,21 +355,21 @@ def check_refusals(side, cs, T=3):
   D = cs.sc.obs_dim
   one = net(D, (48,), 'relu')
   for what, kw in h.refusals(cs):
-    rc, res, b = run_plan(side, cs.sc, cs.mean, cs.K, 0xFF, vnet=one, **{**cs.kw, **kw})
+    rc, res, b = h.run_plan(side, cs.sc, cs.mean, cs.K, 0xFF, value=Value(one), **{**cs.kw, **kw})
     assert rc == -1 and side.lib.earl_last_error(), f'{cs.what} {what}: rc = {rc}'
     b.check(f'{cs.what} {what}')
     ta.assert_untouched(res, cs.sc, f'{cs.what} {what}')
   for what, kw in m.refusals(cs):
-    rc, res, b = run_mpc(side, cs.sc, cs.mean, cs.K, T, 0xFF, vnet=one, **{**cs.kw, **kw})
+    rc, res, b = m.run_mpc(side, cs.sc, cs.mean, cs.K, T, 0xFF, value=Value(one), **{**cs.kw, **kw})
     assert rc == -1 and side.lib.earl_last_error(), f'mpc {cs.what} {what}: rc = {rc}'
     b.check(f'mpc {cs.what} {what}')
     m.assert_untouched(res, cs.sc, cs.mean, f'mpc {cs.what} {what}')
   for what, vnet, kw in value_refusals(D):
-    rc, res, b = run_plan(side, cs.sc, cs.mean, cs.K, 0xFF, **{**cs.kw, 'vnet': vnet, **kw})
+    rc, res, b = h.run_plan(side, cs.sc, cs.mean, cs.K, 0xFF, value=Value(vnet, **kw), **cs.kw)
     assert rc == -1 and side.lib.earl_last_error(), f'{cs.what} {what}: rc = {rc}'
     b.check(f'{cs.what} {what}')
     ta.assert_untouched(res, cs.sc, f'{cs.what} {what}')
-    rc, res, b = run_mpc(side, cs.sc, cs.mean, cs.K, T, 0xFF, **{**cs.kw, 'vnet': vnet, **kw})
+    rc, res, b = m.run_mpc(side, cs.sc, cs.mean, cs.K, T, 0xFF, value=Value(vnet, **kw), **cs.kw)
     assert rc == -1 and side.lib.earl_last_error(), f'mpc {cs.what} {what}: rc = {rc}'
     b.check(f'mpc {cs.what} {what}')
     m.assert_untouched(res, cs.sc, cs.mean, f'mpc {cs.what} {what}')
@@ -511,23 +377,23 @@ def check_refusals(side, cs, T=3):
   assert getattr(side.lib, ta._pfx(cs.sc) + 'plan_mppi_value')(*([None] * 10), side.stream) == -1       # cfg / st NULL: nothing to band
   assert getattr(side.lib, ta._pfx(cs.sc) + 'mpc_rollout_value')(None, None, None, None, 1, None, None, side.stream) == -1
   for fill in ta.FILLS:
-    rc, res, b = run_plan(side, cs.sc, cs.mean, cs.K, fill, vnet=one, n_call=0, **cs.kw)
+    rc, res, b = h.run_plan(side, cs.sc, cs.mean, cs.K, fill, value=Value(one), n_call=0, **cs.kw)
     assert rc == 0
     b.check('plan n = 0')
     ta.assert_untouched(res, cs.sc, 'plan n = 0')
     for what, kw in (('n = 0', dict(n_call=0)), ('T = 0', dict(T_call=0))):
-      rc, res, b = run_mpc(side, cs.sc, cs.mean, cs.K, T, fill, vnet=one, **{**cs.kw, **kw})
+      rc, res, b = m.run_mpc(side, cs.sc, cs.mean, cs.K, T, fill, value=Value(one), **{**cs.kw, **kw})
       assert rc == 0, what
       b.check('mpc ' + what)
       m.assert_untouched(res, cs.sc, cs.mean, 'mpc ' + what)
-  rc, res, b = run_plan(side, cs.sc, cs.mean, cs.K, 0xFF, vnet=one, n_call=0, gamma=2.0, **cs.kw)
+  rc, res, b = h.run_plan(side, cs.sc, cs.mean, cs.K, 0xFF, value=Value(one, 2.0), n_call=0, **cs.kw)
   assert rc == -1, 'a bad discount is refused before n = 0 returns'
 
 
 def check_mpc_pointers(side, cs, T, vnet, full):
   for name in m.OUTS:
     what = f'mpc {cs.what} without {name}'
-    res = ta.both_fills(run_mpc_ok, side, cs.sc, cs.mean, cs.K, T, what=what, null=(name,), vnet=vnet, **cs.kw)
+    res = ta.both_fills(m.run_ok, side, cs.sc, cs.mean, cs.K, T, what=what, null=(name,), value=Value(vnet), **cs.kw)
     assert 'out.' + name not in res
     m.compare(res, full, what)
 
@@ -537,16 +403,16 @@ def check_device_vs_host(cs, vnet, dev, host, T=4):
   """sparse: the planner's and the loop's outputs bit for bit.  dense: ONE planner iteration, ret / ret0 / best_ret within 1e-6 * (sum_t |r_t| + |V|), the sums and V
   from the twin's own rollouts of the candidates; the plans not compared"""
   kw = cs.kw if cs.rt == 'sparse' else {**cs.kw, 'I': 1}
-  d, b = run_ok(dev, cs.sc, cs.mean, cs.K, 0x00, vnet=vnet, **kw)
+  d, b = h.run_ok(dev, cs.sc, cs.mean, cs.K, 0x00, value=Value(vnet), **kw)
   b.check(cs.what + ' device')
-  hh, b = run_ok(host, cs.sc, cs.mean, cs.K, 0x00, vnet=vnet, **kw)
+  hh, b = h.run_ok(host, cs.sc, cs.mean, cs.K, 0x00, value=Value(vnet), **kw)
   if cs.rt == 'sparse':
     h.compare(d, hh, cs.what + ' device vs host')
-    dm, b = run_mpc_ok(dev, cs.sc, cs.mean, cs.K, T, 0x00, vnet=vnet, **cs.kw)
+    dm, b = m.run_ok(dev, cs.sc, cs.mean, cs.K, T, 0x00, value=Value(vnet), **cs.kw)
     b.check(cs.what + ' mpc device')
-    hm, b = run_mpc_ok(host, cs.sc, cs.mean, cs.K, T, 0x00, vnet=vnet, **cs.kw)
+    hm, b = m.run_ok(host, cs.sc, cs.mean, cs.K, T, 0x00, value=Value(vnet), **cs.kw)
     return m.compare(dm, hm, cs.what + ' mpc device vs host')
-  it = oracle(host, cs.sc, cs.mean, cs.K, 1, kw['sigma'], kw['inv_t'], kw['nc'], GAMMA, vnet, kw['iteration0'])['iters'][0]
+  it = h.oracle(host, cs.sc, cs.mean, cs.K, 1, kw['sigma'], kw['inv_t'], kw['nc'], kw['iteration0'], value=Value(vnet))['iters'][0]
   bound = 1e-6 * (it['abs'] + (0 if it['V'] is None else np.abs(it['V'].astype(F64))))
   for name, bnd in (('ret', bound), ('ret0', bound[:1]), ('best_ret', bound.max(0))):
     err = (d['out.' + name].cpu() - hh['out.' + name].cpu()).abs().numpy()
@@ -584,7 +450,7 @@ def check_python(device, nobj, K=4, H=6, I=2, T=4, seed=3):
   sc.state = {k: getattr(u, names.get(k, k)).cpu().numpy().copy() for k in ta.STATE}
   sc.goal_table = u.goal_table.cpu().numpy().copy()
   sc._cfg, sc.counter = _abi.TabletopCfg.from_buffer_copy(u._cfg), int(u._cfg.counter)
-  abi, b = run_ok(side, sc, mean.cpu().numpy(), K, 0x00, gamma=GAMMA, vnet=vnet, I=I, sigma=(0.5, 0.5, 0.8), inv_t=2.0, nc=11)
+  abi, b = h.run_ok(side, sc, mean.cpu().numpy(), K, 0x00, value=Value(vnet), I=I, sigma=(0.5, 0.5, 0.8), inv_t=2.0, nc=11)
   for k in OUTS:
     ta.same(got[k].cpu(), abi['out.' + k].cpu(), f'plan_mppi(discount, value) vs the ABI route ({device}): {k}')
   plain = env.plan_mppi(mean, **kw)
@@ -593,7 +459,7 @@ def check_python(device, nobj, K=4, H=6, I=2, T=4, seed=3):
   for k in OUTS:
     ta.same(same[k].cpu(), plain[k].cpu(), f'plan_mppi with the default keywords: {k}')
   loop = env.rollout_mpc(T, mean, discount=GAMMA, value=pi, **kw)
-  abi, b = run_mpc_ok(side, sc, mean.cpu().numpy(), K, T, 0x00, gamma=GAMMA, vnet=vnet, I=I, sigma=(0.5, 0.5, 0.8), inv_t=2.0, nc=11)
+  abi, b = m.run_ok(side, sc, mean.cpu().numpy(), K, T, 0x00, value=Value(vnet), I=I, sigma=(0.5, 0.5, 0.8), inv_t=2.0, nc=11)
   for k, name in (('obs', 'obs'), ('reward', 'reward'), ('actions', 'act'), ('plan', None), ('ret0', 'ret0'), ('best_ret', 'best_ret')):
     ta.same(loop[k].cpu(), abi['io.plan' if name is None else 'out.' + name].cpu(), f'rollout_mpc(discount, value) vs the ABI route ({device}): {k}')
   a, c = twin.rollout_mpc(T, mean, **kw), tb.make_env(nobj, device).rollout_mpc(T, mean, discount=1.0, value=None, **kw)

@@ -423,14 +423,17 @@ def test_small_case_exactly_in_fractions_with_the_tanh_map_and_the_squashing():
 
 
 def test_the_stamped_profiling_build_links_every_unit_of_the_library():
-  """tools/build_policy_stamped.sh rebuilds the policy units with stamps and links them with the shipped objects: every unit of the Makefile's SRC must be on
-  its link line, or tools/prof_policy.py's load of the stamped library fails on the first missing symbol"""
+  """tools/build_policy_stamped.sh rebuilds the policy units with stamps and links them with the shipped objects, whose list it takes from the Makefile
+  (`make print-objects`): every unit of the Makefile's SRC must be on its link line, or tools/prof_policy.py's load of the stamped library fails on the first missing
+  symbol.  The script runs here with the compiler replaced by `echo`: the lines it would run are read, nothing is built"""
   src = re.search(r'^SRC\s*=\s*(.*)$', open(os.path.join(CSRC, 'Makefile')).read(), flags=re.M).group(1).split()
-  script = open(os.path.join(REPO, 'tools', 'build_policy_stamped.sh')).read()
+  r = subprocess.run(['bash', os.path.join(REPO, 'tools', 'build_policy_stamped.sh')], env={**os.environ, 'HIPCC': 'echo'}, capture_output=True, text=True)
+  assert r.returncode == 0, r.stderr
+  script = r.stdout
   link = next(line for line in script.splitlines() if '-shared' in line)
   for unit in src:
     stem = unit[:-len('.hip')]
-    assert f'{stem}.o' in link or f'{stem}_stamped.o' in link, unit
+    assert (f' {stem}.o' in link) != (f'/{stem}_stamped.o' in link), unit                # (once: the shipped object or the stamped one)
   for unit in ('tabletop_policy', 'tabletop_policy_gaussian'):
     assert f'{unit}_stamped.o' in link and f'-o ../../tools/ubench/{unit}_stamped.o {unit}.hip' in script
   assert 'earl_debug_read_policy_gaussian_profile' in open(os.path.join(CSRC, 'tabletop_policy_gaussian.hip')).read()

@@ -1,5 +1,5 @@
 """earl_tabletop_branch_rollout / earl_tabletop3_branch_rollout (include/earl_tabletop.h) without a GPU: the host twins of csrc/libearl_host.so -- branch_body
-(csrc/tabletop_step.h), the function the kernel runs -- through tests/tabletop_branch_helpers.py, the Python path on device='cpu', and the build of
+(csrc/tabletop_plan.h), the function the kernel runs -- through tests/tabletop_branch_helpers.py, the Python path on device='cpu', and the build of
 csrc/tabletop_branch.hip.  The reference is the same library's earl_tabletop[3]_rollout_cpu called K times on fresh copies of the state and reduced in numpy;
 every word is bit-exact, under both rewards.
 

@@ -1,5 +1,5 @@
 """earl_tabletop_plan_mppi / earl_tabletop3_plan_mppi / earl_tabletop_plan_candidates (include/earl_tabletop.h, "MPPI planning") without a GPU: the host twins of
-csrc/libearl_host.so -- tabletop_step.h's plan_* functions, the ones the kernels run -- through tests/tabletop_plan_helpers.py, the Python path on device='cpu',
+csrc/libearl_host.so -- tabletop_plan.h's plan_* functions, the ones the kernels run -- through tests/tabletop_plan_helpers.py, the Python path on device='cpu',
 and the build of csrc/tabletop_plan.hip.  The oracle (that module's docstring) uses none of the planner's code: a numpy Philox, the policy-math host build, the
 library's EXISTING earl_tabletop[3]_branch_rollout_cpu for the returns, Python integers for the update.  Every output is bit-exact, under both rewards.
 

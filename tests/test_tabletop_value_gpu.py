@@ -131,13 +131,13 @@ def test_sixteen_waves_with_the_widest_network(side, host, nobj):
   """K = 1024 at n = 2, H = 2: every lane of the largest workgroup scores a branch and evaluates D -> EARL_PLAN_VALUE_MAX_H1 -> 256 -> 1"""
   cs = h.case(nobj, 'sparse', n=2, K=1024, H=2, I=1, general=nobj == 3)
   vnet = v.net(cs.sc.obs_dim, (v.MAX_H1, 256), 'tanh', 'none', seed=4)
-  d, b = v.run_mpc_ok(side, cs.sc, cs.mean, cs.K, 2, 0x00, vnet=vnet, **cs.kw)
+  d, b = v.m.run_ok(side, cs.sc, cs.mean, cs.K, 2, 0x00, value=v.Value(vnet), **cs.kw)
   b.check('sixteen waves')
-  hh, b = v.run_mpc_ok(host, cs.sc, cs.mean, cs.K, 2, 0xFF, vnet=vnet, **cs.kw)
+  hh, b = v.m.run_ok(host, cs.sc, cs.mean, cs.K, 2, 0xFF, value=v.Value(vnet), **cs.kw)
   v.m.compare(d, hh, 'sixteen waves: device vs host')
-  p, b = v.run_ok(side, cs.sc, cs.mean, cs.K, 0x00, vnet=vnet, **cs.kw)
+  p, b = h.run_ok(side, cs.sc, cs.mean, cs.K, 0x00, value=v.Value(vnet), **cs.kw)
   b.check('K = 1024, planner')
-  ph, b = v.run_ok(host, cs.sc, cs.mean, cs.K, 0xFF, vnet=vnet, **cs.kw)
+  ph, b = h.run_ok(host, cs.sc, cs.mean, cs.K, 0xFF, value=v.Value(vnet), **cs.kw)
   h.compare(p, ph, 'K = 1024, planner: device vs host')
 
 

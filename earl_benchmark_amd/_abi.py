@@ -75,6 +75,14 @@ class PlanValue(C.Structure):          # struct earl_plan_value (include/earl_ta
 PLAN_VALUE_MAX_H1 = 16                 # EARL_PLAN_VALUE_MAX_H1: the widest first hidden layer of a two-hidden-layer value network
 
 
+class CemParams(C.Structure):          # struct earl_cem_params (include/earl_tabletop.h)
+  _fields_ = [('K', C.c_int32), ('H', C.c_int32), ('iterations', C.c_int32), ('iteration0', C.c_int32), ('elites', C.c_int32), ('sigma', C.c_float * 3),
+              ('noise_counter', C.c_uint32), ('alpha', C.c_float), ('std_min', C.c_float), ('std_max', C.c_float)]
+
+
+CEM_MAX_K = 1024                       # EARL_CEM_MAX_K
+
+
 class AgentPair(C.Structure):          # struct earl_agent_pair (include/earl_tabletop.h)
   _fields_ = [('switch_every', C.c_int32 * 2), ('switch_on_success', C.c_int32), ('pad_', C.c_int32), ('param_stride', C.c_int64), ('backward_goal', C.c_void_p),
               ('phase', C.c_void_p), ('steps_in_phase', C.c_void_p), ('agent_out', C.c_void_p), ('forward_success', C.c_void_p), ('backward_success', C.c_void_p)]
@@ -201,6 +209,11 @@ SIGNATURES = {
     'earl_tabletop3_plan_mppi_value': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue)] + [C.c_void_p] * 7,
     'earl_tabletop_mpc_rollout_value': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue), C.c_int32, _P(TabletopOut), _P(MpcOut), C.c_void_p],
     'earl_tabletop3_mpc_rollout_value': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue), C.c_int32, _P(TabletopOut), _P(MpcOut), C.c_void_p],
+    'earl_tabletop_plan_cem': [_P(TabletopCfg), _P(TabletopState), _P(CemParams), _P(PlanValue)] + [C.c_void_p] * 9,
+    'earl_tabletop3_plan_cem': [_P(TabletopCfg), _P(TabletopState), _P(CemParams), _P(PlanValue)] + [C.c_void_p] * 9,
+    'earl_tabletop_cem_candidates': [_P(TabletopCfg), _P(CemParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    'earl_tabletop_mpc_rollout_cem': [_P(TabletopCfg), _P(TabletopState), _P(CemParams), _P(PlanValue), C.c_int32, _P(TabletopOut), _P(MpcOut), C.c_void_p],
+    'earl_tabletop3_mpc_rollout_cem': [_P(TabletopCfg), _P(TabletopState), _P(CemParams), _P(PlanValue), C.c_int32, _P(TabletopOut), _P(MpcOut), C.c_void_p],
     'earl_debug_set_rollout_impl': [C.c_int],
     'earl_debug_set_rollout3_form': [C.c_int],
     'earl_debug_set_rollout_wgs_per_cu': [C.c_int],

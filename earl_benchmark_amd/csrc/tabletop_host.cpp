@@ -1,8 +1,9 @@
 // tabletop_host.cpp -- the `_cpu` entry points of include/earl_tabletop.h (BASELINE configs[0]: "1 env, CPU ... plumbing, no GPU"):
-// the SAME per-env functions the gfx950 kernels run (tabletop_device.h, tabletop_step.h, philox.h; the planners' tabletop_plan.h, tabletop_value.h, tabletop_mpc.h;
+// the SAME per-env functions the gfx950 kernels run (tabletop_device.h, tabletop_step.h, philox.h; the planners' tabletop_plan.h, tabletop_value.h, tabletop_mpc.h, tabletop_cem.h;
 // the policies' tabletop_policy.h), compiled for the host by g++ (-DEARL_HOST_BUILD: earl_rt.h -> host_shim.h) with -ffp-contract=off, one OpenMP iteration per env
 // where a kernel has one lane per env.  This file owns only the walks: for_each_env, rollout_tiles, for_each_branch_tile (the branch-shaped launches' (branch, tile)
-// range) and update_env (one env's reweighting, for the planner and the receding-horizon loop); no arithmetic of an env or a planner is stated here.
+// range), update_env (one env's MPPI reweighting) and cem_update_env (one env's CEM refit), each for its planner and its receding-horizon loop; no arithmetic of an env or
+// a planner is stated here.
 // Host pointers, no stream, no HIP runtime.  This library is loaded only when a caller ASKS for device='cpu'; nothing falls back to it,
 // and nothing here touches oracle/ (the oracle is the checker of both builds).
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include "tabletop_hostside.h"
 #include "tabletop_plan.h"
 #include "tabletop_mpc.h"
+#include "tabletop_cem.h"
 #include "tabletop_policy.h"
 #include "../../include/earl_physics.h"
 
@@ -278,10 +280,165 @@ int do_mpc(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const ea
   return EARL_OK;
 }
 
+
+// One CEM refit of ONE env (items 4-5 of the CEM contract), stated once for the planner and the receding-horizon loop: beta / best_k and the ranks over the K returns,
+// the elites in ascending k, then per plan row the two integer moments over the elites (branch 0 adds nothing) and cem_new_mean / cem_new_std.
+// ret(k) = return k; row(t, m, s) = the clipped mean and clamped std of row t entering; put(t, d, mean', std').  -> (beta, best_k)
+template <class Ret, class Row, class Put>
+inline std::pair<double, int> cem_update_env(const PlanArgs& p, int i, int E, float alpha, float lo, float hi, Ret&& ret, Row&& row, Put&& put) {
+  double beta = -INFINITY;
+  int bk = 0;
+  std::vector<int> elite;
+  for (int k = 0; k < p.K; ++k) {
+    const double r = ret(k);
+    plan_best(r, k, beta, bk);
+    int rank = 0;
+    for (int k2 = 0; k2 < p.K; ++k2) rank += cem_before(ret(k2), k2, r, k) ? 1 : 0;
+    if (cem_elite(r, rank, E)) elite.push_back(k);
+  }
+  const int32_t Ne = (int32_t)elite.size();
+  for (int t = 0; t < p.a.T; ++t) {
+    float m[3], s[3];
+    row(t, m, s);
+    int64_t A1[3] = {0, 0, 0}, A2[3] = {0, 0, 0};
+    for (int k : elite)
+      if (k > 0) cem_accumulate(p, i, (uint32_t)k, (uint32_t)t, m, s, A1, A2);
+    for (int d = 0; d < 3; ++d) put(t, d, cem_new_mean(m[d], A1[d], Ne, alpha), cem_new_std(s[d], A1[d], A2[d], Ne, alpha, lo, hi));
+  }
+  return {beta, bk};
+}
+
+// The CEM planner on the host (include/earl_tabletop.h, "CEM planning"): do_plan's walk with tabletop_cem.h's functions, the ones the kernels run
+template <int NOBJ>
+int do_cem(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* cp, const earl_plan_value* pv, const float* mean, const float* std0,
+           float* plan, float* std_out, double* ret, double* ret0, double* best_ret, int32_t* best_k) {
+  if (!st) return fail(EARL_ERR_ARG, "cfg/state is NULL");
+  long long blocks, ublocks;
+  if (int rc = check_cem(cfg, st, NOBJ, Dims<NOBJ>::NOBS, cp, pv, 0, mean, std0, plan, std_out, ret, &blocks, &ublocks)) return rc;
+  if (blocks == 0) return EARL_OK;
+  CemArgs c = cem_args(cfg, st, cp, pv, mean, std0, thresholds());
+  c.p.plan = plan;
+  c.p.ret = ret;
+  c.std_out = std_out;
+  const int n = cfg->n, K = cp->K;
+  const bool general = is_general(cfg), value = pv != nullptr;
+  for (int it = 0; it < cp->iterations; ++it) {
+    const bool last = it + 1 == cp->iterations;
+    c.p.mean = it ? plan : mean;
+    c.std_in = it ? std_out : std0;
+    c.p.word0 = kCemDraw | (uint32_t)(cp->iteration0 + it);
+    c.p.ret0 = ret0 ? ret0 + (size_t)it * n : nullptr;
+    for_each_branch_tile(blocks, K, n, [&](int i, int k) {
+      if (general) value ? cem_score_body<NOBJ, true, true>(c, i, k) : cem_score_body<NOBJ, true, false>(c, i, k);
+      else value ? cem_score_body<NOBJ, false, true>(c, i, k) : cem_score_body<NOBJ, false, false>(c, i, k);
+    });
+    for_each_env(n, [&](int i) {
+      const auto [beta, bk] = cem_update_env(
+          c.p, i, c.E, c.alpha, c.std_min, c.std_max, [&](int k) { return ret[(size_t)k * n + i]; },
+          [&](int t, float (&m)[3], float (&s)[3]) {
+            plan_mean(c.p, i, t, m);
+            cem_std(c, i, t, s);
+          },
+          [&](int t, int d, float mv, float sv) {
+            plan[((size_t)t * n + i) * 3 + d] = mv;
+            std_out[((size_t)t * n + i) * 3 + d] = sv;
+          });
+      if (last && best_ret) best_ret[i] = beta;
+      if (last && best_k) best_k[i] = bk;
+    });
+  }
+  return EARL_OK;
+}
+
+// The receding-horizon CEM loop on the host: mpc_env with the CEM score and refit; the std starts from sclamp(sigma) at every real step
+template <int NOBJ, bool GENERAL>
+void cem_mpc_env(const CemMpcArgs& c, int i) {
+  const MpcArgs& x = c.x;
+  const KArgs& a = x.p.a;
+  const int n = a.cfg.n, H = a.T, K = x.p.K;
+  std::vector<float> P((size_t)H * 3), S((size_t)H * 3);
+  for (int e = 0; e < H * 3; ++e) P[e] = x.m.plan[((size_t)(e / 3) * n + i) * 3 + e % 3];
+  std::vector<double> ret(K);
+  Lane<NOBJ> L;
+  load_lane<NOBJ>(a, i, L);
+  float g[Dims<NOBJ>::NG];
+  load_goal<NOBJ>(a.st.goal_table, L.goal_idx, g);
+  PlanArgs q = x.p;
+  auto row = [&](int t, float (&m)[3], float (&s)[3]) {
+    for (int d = 0; d < 3; ++d) {
+      m[d] = plan_clip(P[(size_t)t * 3 + d]);
+      s[d] = S[(size_t)t * 3 + d];
+    }
+  };
+  for (int s = 0; s < x.T; ++s) {
+    const uint64_t counter = a.cfg.counter + (uint64_t)s;
+    q.noise_counter = x.p.noise_counter + (uint32_t)s;
+    for (int e = 0; e < H * 3; ++e) S[e] = cem_sclamp(x.p.sigma[e % 3], c.std_min, c.std_max);
+    for (int it = 0; it < x.iterations; ++it) {
+      q.word0 = kCemDraw | (uint32_t)(x.iteration0 + it);
+      for (int k = 0; k < K; ++k) ret[k] = cem_mpc_score<NOBJ, GENERAL>(q, i, k, counter, L, g, row);
+      if (x.m.ret0) x.m.ret0[((size_t)s * x.iterations + it) * n + i] = ret[0];
+      const double beta = cem_update_env(q, i, c.E, c.alpha, c.std_min, c.std_max, [&](int k) { return ret[k]; }, row, [&](int t, int d, float mv, float sv) {
+                            P[(size_t)t * 3 + d] = mv;
+                            S[(size_t)t * 3 + d] = sv;
+                          }).first;
+      if (it + 1 == x.iterations && x.m.best_ret) x.m.best_ret[(size_t)s * n + i] = beta;
+    }
+    const float act[3] = {P[0], P[1], P[2]};
+    const bool done = mpc_act<NOBJ, GENERAL>(x, i, s, counter, L, g, act, true);
+    if (GENERAL && done && a.cfg.auto_reset) std::fill(P.begin(), P.end(), 0.0f);
+    else std::copy(P.begin() + 3, P.end(), P.begin());   // (the shift; the last row stays, repeated)
+  }
+  for (int e = 0; e < H * 3; ++e) x.m.plan[((size_t)(e / 3) * n + i) * 3 + e % 3] = P[e];
+  store_lane<NOBJ>(a, i, L);
+}
+
+template <int NOBJ>
+int do_cem_mpc(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* cp, const earl_plan_value* pv, int32_t T, const earl_tabletop_out* out,
+               const earl_mpc_out* mpc) {
+  int lanes;
+  if (int rc = check_cem_mpc(cfg, st, NOBJ, cp, pv, T, out, mpc, &lanes)) return rc;
+  if (lanes == 0) return EARL_OK;
+  const CemMpcArgs c = cem_mpc_args(cfg, st, cp, T, out, mpc);
+  const bool general = is_general(cfg);
+  const int n = cfg->n;
+#pragma omp parallel for schedule(dynamic, 1) if (n >= 4)
+  for (int i = 0; i < n; ++i) {
+    if (general) cem_mpc_env<NOBJ, true>(c, i);
+    else cem_mpc_env<NOBJ, false>(c, i);
+  }
+  return EARL_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
+int earl_tabletop_plan_cem_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, const float* mean,
+                               const float* std0, float* plan, float* std, double* ret, double* ret0, double* best_ret, int32_t* best_k) {
+  return do_cem<1>(cfg, st, params, pv, mean, std0, plan, std, ret, ret0, best_ret, best_k);
+}
+int earl_tabletop3_plan_cem_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, const float* mean,
+                                const float* std0, float* plan, float* std, double* ret, double* ret0, double* best_ret, int32_t* best_k) {
+  return do_cem<3>(cfg, st, params, pv, mean, std0, plan, std, ret, ret0, best_ret, best_k);
+}
+int earl_tabletop_cem_candidates_cpu(const earl_tabletop_cfg* cfg, const earl_cem_params* params, int32_t j, const float* mean, const float* std, float* act_out) {
+  long long blocks, ublocks;
+  if (int rc = check_cem(cfg, nullptr, 1, 0, params, nullptr, j, mean, std, act_out, nullptr, nullptr, &blocks, &ublocks)) return rc;
+  if (blocks == 0) return EARL_OK;
+  CemArgs c = cem_args(cfg, nullptr, params, nullptr, mean, std, thresholds());
+  c.p.word0 = kCemDraw | (uint32_t)j;
+  for_each_branch_tile(blocks, params->K, cfg->n, [&](int i, int k) { cem_candidates_body(c, i, k, act_out); });
+  return EARL_OK;
+}
+int earl_tabletop_mpc_rollout_cem_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, int32_t T,
+                                      const earl_tabletop_out* out, const earl_mpc_out* mpc) {
+  return do_cem_mpc<1>(cfg, st, params, pv, T, out, mpc);
+}
+int earl_tabletop3_mpc_rollout_cem_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, int32_t T,
+                                       const earl_tabletop_out* out, const earl_mpc_out* mpc) {
+  return do_cem_mpc<3>(cfg, st, params, pv, T, out, mpc);
+}
 int earl_tabletop_mpc_rollout_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, int32_t T, const earl_tabletop_out* out,
                                   const earl_mpc_out* mpc) {
   return do_mpc<1, false>(cfg, st, params, nullptr, T, out, mpc);

@@ -619,8 +619,79 @@ class TabletopManipulation:
     self._check(rc, 'plan_candidates')
     return act
 
+  def _cem_params(self, who, K, H, iterations, iteration0, elites, sigma, noise_counter, alpha, std_min, std_max):
+    s = torch.as_tensor(sigma, dtype=torch.float32).reshape(-1).tolist()
+    if len(s) not in (1, 3):
+      raise ValueError(f'{who}: sigma is a number or three, one per action dimension')
+    K, E = int(K), int(elites)
+    if K < 1 or K > _abi.CEM_MAX_K or E < 1 or E > K:
+      raise ValueError(f'{who}: K = {K}, elites = {E}: 1 <= elites <= K <= {_abi.CEM_MAX_K}')
+    if not (0.0 <= float(alpha) < 1.0) or not (0.0 <= float(std_min) <= float(std_max) < float('inf')):
+      raise ValueError(f'{who}: alpha = {alpha}, std_min = {std_min}, std_max = {std_max}: 0 <= alpha < 1 and 0 <= std_min <= std_max, all finite')
+    nc = self._cfg.counter if noise_counter is None else int(noise_counter)   # (None: the low word of the env's Philox counter, as plan_mppi)
+    return _abi.CemParams(K=K, H=int(H), iterations=int(iterations), iteration0=int(iteration0), elites=E, sigma=(C.c_float * 3)(*(s * 3 if len(s) == 1 else s)),
+                          noise_counter=nc & 0xFFFFFFFF, alpha=float(alpha), std_min=float(std_min), std_max=float(std_max))
+
+  def plan_cem(self, mean=None, horizon=None, K=64, elites=8, iterations=1, sigma=0.3, std=None, alpha=0.0, std_min=0.0, std_max=2.0, iteration0=0, noise_counter=None,
+               out=None, discount=1.0, value=None):
+    """`iterations` iterations of the cross-entropy method on the device from the CURRENT state (include/earl_tabletop.h: earl_tabletop_plan_cem): K candidates per
+    env -- the mean plan itself and K - 1 copies with clipped Gaussian noise of a scale per (step, env, dimension) -- scored as rollout_branches scores them; the
+    `elites` best refit the mean AND the std (smoothed by `alpha`, the std kept inside [std_min, std_max]), so the search widens or narrows by itself inside the
+    launch.  The candidates are never in memory; the update makes only the elites again.  mean [H, N, 3] (None: zeros of [horizon, N, 3]); std [H, N, 3] (None:
+    every row `sigma`, a number or three) -> {'plan' [H, N, 3], 'std' [H, N, 3] float32, 'ret' [K, N] float64, 'ret0' [iterations, N] float64, 'best_ret' [N]
+    float64, 'best_k' [N] int32 (cem_candidates(...)[best_k] is that candidate)}.  `noise_counter`, `iteration0`, `discount`, `value` and `out` are plan_mppi's;
+    'plan', 'std' and 'ret' are allocated when `out` leaves them out, out['plan'] may be the `mean` tensor and out['std'] the `std` tensor.  The env is left
+    exactly as found."""
+    m = self._plan_mean('plan_cem', mean, horizon)
+    n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
+    if H < 1 or I < 1:
+      raise ValueError(f'plan_cem: H = {H}, iterations = {I}: at least one of each')
+    cp = self._cem_params('plan_cem', K, H, I, iteration0, elites, sigma, noise_counter, alpha, std_min, std_max)
+    s0 = None if std is None else self._plan_mean('plan_cem (std)', std, H)
+    kw = dict(device=self.device)
+    want = {'plan': ((H, n, 3), torch.float32), 'std': ((H, n, 3), torch.float32), 'ret': ((K, n), torch.float64), 'ret0': ((I, n), torch.float64),
+            'best_ret': ((n,), torch.float64), 'best_k': ((n,), torch.int32)}
+    if out is None:
+      res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
+    else:
+      if set(out) - set(want):
+        raise ValueError(f'plan_cem: out holds {sorted(set(out) - set(want))}; the keys are {list(want)}')
+      res = {k: t for k, t in out.items() if t is not None}
+      for k, t in res.items():
+        shape, dt = want[k]
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+          raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
+      if 'plan' not in res:
+        raise ValueError("plan_cem: out['plan'] is what the call computes")
+      for k in ('std', 'ret'):
+        if k not in res:
+          res[k] = torch.empty(*want[k][0], dtype=want[k][1], **kw)
+    pv = self._plan_value('plan_cem', discount, value)
+    with self._ctx():
+      fn = self._lib.earl_tabletop_plan_cem if self.NOBJ == 1 else self._lib.earl_tabletop3_plan_cem
+      rc = fn(self._cfg_ref, self._st_ref, C.byref(cp), None if pv is None else C.byref(pv), m.data_ptr(), _ptr(s0), res['plan'].data_ptr(), res['std'].data_ptr(),
+              res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')), _ptr(res.get('best_k')), self._stream())
+    self._check(rc, 'plan_cem')
+    return res                                                       # (no counter advance, no step count: nothing happened to the env)
+
+  def cem_candidates(self, mean, K, sigma=0.3, std=None, iteration=0, noise_counter=None):
+    """the K candidates of plan_cem's iteration `iteration` around `mean` [H, N, 3] with the std `std` [H, N, 3] (None: `sigma`), written out: [K, H, N, 3]
+    float32, row 0 the clipped mean -- what rollout_branches takes (earl_tabletop_cem_candidates).  The std is clamped into plan_cem's default [std_min, std_max] =
+    [0, 2] first, so with plan_cem's `noise_counter` and those defaults they are the candidates that call scored."""
+    m = self._plan_mean('cem_candidates', mean, None)
+    H = int(m.shape[0])
+    if H < 1:
+      raise ValueError('cem_candidates: H = 0')
+    cp = self._cem_params('cem_candidates', K, H, 1, 0, 1, sigma, noise_counter, 0.0, 0.0, 2.0)
+    s0 = None if std is None else self._plan_mean('cem_candidates (std)', std, H)
+    act = torch.empty(int(K), H, self.num_envs, 3, dtype=torch.float32, device=self.device)
+    with self._ctx():
+      rc = self._lib.earl_tabletop_cem_candidates(self._cfg_ref, C.byref(cp), int(iteration), m.data_ptr(), _ptr(s0), act.data_ptr(), self._stream())
+    self._check(rc, 'cem_candidates')
+    return act
+
   def rollout_mpc(self, T, plan=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, out=None, discount=1.0,
-                  value=None):
+                  value=None, method='mppi', elites=8, alpha=0.0, std_min=0.0, std_max=2.0):
     """T steps of receding-horizon MPPI control in ONE kernel launch (include/earl_tabletop.h: earl_tabletop_mpc_rollout): per step plan_mppi from the current
     state with the warm start, rollout of the plan's first action, the plan shifted by one step (zeroed for an env that auto-reset) -- bit for bit the loop
         for s in range(T): plan_mppi(plan, ..., out={'plan': plan}); rollout(plan[:1]); plan = cat(plan[1:], plan[-1:])
@@ -630,11 +701,25 @@ class TabletopManipulation:
     of that loop.  `out`: an optional dict of preallocated tensors under the same keys; a key that is missing or None is not computed, except 'plan', which is
     then allocated; out['plan'] may be the `plan` tensor (the call is in place on it).  Advances the Philox counter and total_step_count by T, like rollout().
     `discount` and `value` are plan_mppi's: every planning step of the loop scores its candidates by  sum_t gamma^t r_t + gamma^H V(o_H)  with the value network
-    evaluated inside the same launch (earl_tabletop_mpc_rollout_value); with both defaults the call is the value-free entry point, exactly as before."""
+    evaluated inside the same launch (earl_tabletop_mpc_rollout_value); with both defaults the call is the value-free entry point, exactly as before.
+    `method='cem'` plans every step with plan_cem instead (earl_tabletop_mpc_rollout_cem: `elites`, `alpha`, `std_min`, `std_max` are plan_cem's, the std starts
+    from `sigma` at every step, `temperature` is ignored, and a `discount` / `value` other than the defaults is refused: that loop has no value build).  Under
+    the default 'mppi' those four keywords must keep their defaults."""
+    if method not in ('mppi', 'cem'):
+      raise ValueError(f"rollout_mpc: method = {method!r}: 'mppi' or 'cem'")
+    if method == 'mppi' and (elites, alpha, std_min, std_max) != (8, 0.0, 0.0, 2.0):
+      raise ValueError("rollout_mpc: elites, alpha, std_min and std_max belong to method='cem'")
     n, T, K, I = self.num_envs, int(T), int(K), int(iterations)
     p0 = self._plan_mean('rollout_mpc', plan, horizon)
     H = int(p0.shape[0])
-    pp = self._plan_params('rollout_mpc', K, H, I, iteration0, sigma, temperature, noise_counter)
+    if method == 'cem':
+      if T < 1 or H < 1 or I < 1:
+        raise ValueError(f'rollout_mpc: T = {T}, H = {H}, iterations = {I}: at least one of each')
+      pp = self._cem_params('rollout_mpc', K, H, I, iteration0, elites, sigma, noise_counter, alpha, std_min, std_max)
+      if self._plan_value('rollout_mpc', discount, value) is not None:
+        raise ValueError("rollout_mpc: method='cem' takes no discount or value network (earl_tabletop_mpc_rollout_cem refuses them); compose plan_cem and rollout")
+    else:
+      pp = self._plan_params('rollout_mpc', K, H, I, iteration0, sigma, temperature, noise_counter)
     if T < 1 or K < 1 or H < 1 or I < 1:
       raise ValueError(f'rollout_mpc: T = {T}, K = {K}, H = {H}, iterations = {I}: at least one of each')
     if K > _abi.MPC_MAX_K or H > _abi.MPC_MAX_H:
@@ -662,7 +747,10 @@ class TabletopManipulation:
         res['plan'].copy_(p0)                                          # (the entry point is in place on the plan)
       ostruct = _abi.TabletopOut(_ptr(res.get('obs')), _ptr(res.get('reward')), _ptr(res.get('done')), _ptr(res.get('success')))
       mpc = _abi.MpcOut(act=_ptr(res.get('actions')), plan=res['plan'].data_ptr(), ret0=_ptr(res.get('ret0')), best_ret=_ptr(res.get('best_ret')))
-      if pv is None:
+      if method == 'cem':
+        fn = self._lib.earl_tabletop_mpc_rollout_cem if self.NOBJ == 1 else self._lib.earl_tabletop3_mpc_rollout_cem
+        rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), None, T, C.byref(ostruct), C.byref(mpc), self._stream())
+      elif pv is None:
         fn = self._lib.earl_tabletop_mpc_rollout if self.NOBJ == 1 else self._lib.earl_tabletop3_mpc_rollout
         rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), T, C.byref(ostruct), C.byref(mpc), self._stream())
       else:

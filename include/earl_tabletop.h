@@ -503,6 +503,63 @@ int earl_tabletop_mpc_rollout_value(const earl_tabletop_cfg* cfg, const earl_tab
 int earl_tabletop3_mpc_rollout_value(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv, int32_t T,
                                      const earl_tabletop_out* out, const earl_mpc_out* mpc, earl_stream_t stream);
 
+/* ---- CEM planning: the cross-entropy method on the same launches -- elites instead of weights, a refitted std per (step, env, dim) ----
+ * The planner of PETS, PlaNet and TD-MPC around envs/tabletop_manipulation.py:128-138: K noisy copies of a mean plan, the E best of them refit mean AND standard
+ * deviation.  The update regenerates only the E elites from their counters (MPPI's regenerates all K), and the refitted std widens or narrows the search inside the
+ * launch.  Per iteration two launches on the caller's stream (score, update); no host synchronisation, no allocation: the calls can be captured into a HIP graph.
+ * For iteration j = iteration0 + i, env with global id g = cfg->env_offset + env, the entering plan `mean` and the entering std (`std0` for i = 0, the previous
+ * iteration's results afterwards):
+ *   1 clipped mean and clamped std   m = clip(mean) as MPPI item 1.  s = sclamp(std), sclamp(x) = (y = x > std_min ? x : std_min; y < std_max ? y : std_max): a NaN
+ *                   maps to std_min.  With std0 == NULL every row's std is sclamp(sigma[d]).
+ *   2 candidates    branch 0 is m.  For k >= 1: a_k[t][d] = clip(fmaf(s[t][d], eps, m[t][d])), eps as MPPI item 2: the quantile of words x, y, z of one Philox block,
+ *                   key and counter words MPPI's except word 0 = 0x43454D00 | j, which collides with nothing (the envs use 0 .. 2048, the Gaussian head 0x504F4C00,
+ *                   MPPI 0x504C4E00).
+ *   3 scores        pv == NULL: MPPI item 3, the plain float64 sum.  Otherwise item 3 of the `_value` block word for word: the discounted sum, V on the last row, its
+ *                   rules (EARL_PLAN_VALUE_MAX_H1 included).  pv = {1.0, NULL} equals pv == NULL bit for bit.
+ *   4 elites        a total order over the K branches: k stands before k' iff ret[k] is not NaN and ret[k'] is NaN; or neither is NaN and ret[k] > ret[k']; or
+ *                   (ret[k] == ret[k'], or both are NaN) and k < k'.  rank_k = the number of branches before k.  k is an elite iff rank_k < E and ret[k] is not NaN;
+ *                   Ne = the number of elites.  The elite set is defined by this order and by nothing in the implementation.  best_ret and best_k: MPPI items 4, 7.
+ *   5 update        per (t, d), over the elites in any order, every sum integer: D_k = rint((double)(a_k - m) * 2^20) as int64 (the subtraction one float32
+ *                   operation; |D_k| <= 2^21, branch 0 has D = 0).  A1 = sum D_k, A2 = sum D_k^2, V = Ne * A2 - A1^2: exact in int64 (A2 < 2^52, Ne * A2 and
+ *                   A1^2 <= 2^62, V >= 0).  e_mean = m + (float)((double)A1 / ((double)Ne * 2^20)).  e_std = sqrtf((float)((double)V / ((double)Ne * (double)Ne *
+ *                   2^40))), the float32 square root, correctly rounded.  mean' = clip(fmaf(alpha, m - e_mean, e_mean)); std' = sclamp(fmaf(alpha, s - e_std, e_std)).
+ *                   Ne == 0 (every return NaN): mean' = m, std' = s.
+ *   6 outputs       plan [H, n, 3]: may be `mean` itself.  std [H, n, 3], REQUIRED: the workspace between iterations and the result; may be `std0` itself.  Any
+ *                   other overlap among the four arrays is refused.  ret [K, n], REQUIRED.  ret0, best_ret, best_k: as MPPI.
+ *   7 chaining, state, non-finite   as MPPI: I iterations in one call equal I calls of one, each fed the previous plan and std; `st` is never written; nothing
+ *                   faults on NaN or Inf in mean, std0 or the state.
+ * EARL_ERR_ARG before any HIP call for: everything earl_tabletop[3]_plan_mppi refuses; K > EARL_CEM_MAX_K; elites outside 1 .. K; an alpha that is not finite or
+ * outside [0, 1); std_min / std_max not finite or not 0 <= std_min <= std_max; std NULL; the overlaps of item 6; with pv, what the `_value` calls refuse.
+ * n == 0 returns EARL_OK and writes nothing.
+ * earl_tabletop_cem_candidates: item 2 written out for ONE iteration j (0 .. 255), act_out [K, H, n, 3], for both envs; std NULL: sigma.  It reads cfg->n, env_offset
+ * and seed and params->K, H, sigma, noise_counter, std_min and std_max only, and refuses what earl_tabletop_plan_candidates refuses and those fields' ranges.
+ * earl_tabletop[3]_mpc_rollout_cem: earl_tabletop[3]_mpc_rollout, DEFINED by the same composition with earl_tabletop[3]_plan_cem as its planner: real step s plans
+ * with cfg->counter = c0 + s, noise_counter + s, mean = P_s and std0 = NULL -- the search starts from sigma at every control step, so there is no std to carry or
+ * shift; act, shift, the zeroed plan after an auto-reset and exit are that block's items 2 - 4; two calls of T1 and T2 equal one of T1 + T2.  One workgroup per env,
+ * one lane per branch, the elites ranked in LDS.  It refuses what earl_tabletop[3]_mpc_rollout and earl_tabletop[3]_plan_cem refuse, under EARL_MPC_MAX_H and
+ * EARL_CEM_MAX_K; T == 0 or n == 0 returns EARL_OK and writes nothing.  pv != NULL is REFUSED (EARL_ERR_ARG), by the device call and by its twin: with the value
+ * network inside, the three-object auto-reset kernel does not fit 128 VGPRs under 1024-lane workgroups without scratch (12 bytes per lane), and no spilling
+ * kernel is shipped.  pv stays in the signature for the day it fits; the discounted loop is the composition of earl_tabletop[3]_plan_cem and the one-step rollout. */
+#define EARL_CEM_MAX_K 1024
+typedef struct earl_cem_params {
+  int32_t K, H, iterations, iteration0;   /* as earl_plan_params; K in 1 .. EARL_CEM_MAX_K */
+  int32_t elites;                          /* E: 1 .. K */
+  float sigma[3];                          /* the std of every row when no std0 is given; finite, >= 0 */
+  uint32_t noise_counter;
+  float alpha;                             /* smoothing: finite, 0 <= alpha < 1 */
+  float std_min, std_max;                  /* finite, 0 <= std_min <= std_max */
+} earl_cem_params;
+int earl_tabletop_plan_cem(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, const float* mean,
+                           const float* std0, float* plan, float* std, double* ret, double* ret0, double* best_ret, int32_t* best_k, earl_stream_t stream);
+int earl_tabletop3_plan_cem(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, const float* mean,
+                            const float* std0, float* plan, float* std, double* ret, double* ret0, double* best_ret, int32_t* best_k, earl_stream_t stream);
+int earl_tabletop_cem_candidates(const earl_tabletop_cfg* cfg, const earl_cem_params* params, int32_t j, const float* mean, const float* std, float* act_out,
+                                 earl_stream_t stream);
+int earl_tabletop_mpc_rollout_cem(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, int32_t T,
+                                  const earl_tabletop_out* out, const earl_mpc_out* mpc, earl_stream_t stream);
+int earl_tabletop3_mpc_rollout_cem(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, int32_t T,
+                                   const earl_tabletop_out* out, const earl_mpc_out* mpc, earl_stream_t stream);
+
 /* ---- host build: the `_cpu` entry points (BASELINE.json configs[0] "1 env, CPU ... plumbing, no GPU") ----
  * csrc/libearl_host.so = the SAME per-env functions the gfx950 kernels run (csrc/tabletop_device.h, tabletop_step.h, philox.h), compiled for the host by
  * g++ with -ffp-contract=off; one OpenMP iteration per env where a kernel has one lane per env.  Same structs, same arguments minus the stream, HOST
@@ -582,6 +639,18 @@ int earl_tabletop_mpc_rollout_value_cpu(const earl_tabletop_cfg* cfg, const earl
                                         const earl_tabletop_out* out, const earl_mpc_out* mpc);
 int earl_tabletop3_mpc_rollout_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv, int32_t T,
                                          const earl_tabletop_out* out, const earl_mpc_out* mpc);
+/* host twins of earl_tabletop[3]_plan_cem, earl_tabletop_cem_candidates and earl_tabletop[3]_mpc_rollout_cem: the kernels' per-lane functions (csrc/tabletop_cem.h) in
+ * plain loops.  Items 4 - 5 are integer: bit-identical to the device in every output under the sparse reward; under the dense one ret, ret0 and best_ret within
+ * 1e-6 relative of the sum of |reward| and the plans not comparable.  They refuse what the device entry points refuse. */
+int earl_tabletop_plan_cem_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, const float* mean,
+                               const float* std0, float* plan, float* std, double* ret, double* ret0, double* best_ret, int32_t* best_k);
+int earl_tabletop3_plan_cem_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, const float* mean,
+                                const float* std0, float* plan, float* std, double* ret, double* ret0, double* best_ret, int32_t* best_k);
+int earl_tabletop_cem_candidates_cpu(const earl_tabletop_cfg* cfg, const earl_cem_params* params, int32_t j, const float* mean, const float* std, float* act_out);
+int earl_tabletop_mpc_rollout_cem_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, int32_t T,
+                                      const earl_tabletop_out* out, const earl_mpc_out* mpc);
+int earl_tabletop3_mpc_rollout_cem_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_cem_params* params, const earl_plan_value* pv, int32_t T,
+                                       const earl_tabletop_out* out, const earl_mpc_out* mpc);
 int earl_host_set_threads(int n);      /* OpenMP threads of the calls above (n <= 0: query); returns the count in force */
 const char* earl_host_version(void);
 const char* earl_host_last_error(void);

@@ -75,6 +75,13 @@ class PlanValue(C.Structure):          # struct earl_plan_value (include/earl_ta
 PLAN_VALUE_MAX_H1 = 16                 # EARL_PLAN_VALUE_MAX_H1: the widest first hidden layer of a two-hidden-layer value network
 
 
+class PlanPrior(C.Structure):          # struct earl_plan_prior (include/earl_tabletop.h)
+  _fields_ = [('policy', C.POINTER(MlpPolicy)), ('branches', C.c_int32), ('sigma', C.c_float * 3), ('act', C.c_void_p)]
+
+
+PLAN_PRIOR_MAX_H1 = 16                 # EARL_PLAN_PRIOR_MAX_H1: the widest first hidden layer of a two-hidden-layer policy prior
+
+
 class CemParams(C.Structure):          # struct earl_cem_params (include/earl_tabletop.h)
   _fields_ = [('K', C.c_int32), ('H', C.c_int32), ('iterations', C.c_int32), ('iteration0', C.c_int32), ('elites', C.c_int32), ('sigma', C.c_float * 3),
               ('noise_counter', C.c_uint32), ('alpha', C.c_float), ('std_min', C.c_float), ('std_max', C.c_float)]
@@ -209,6 +216,8 @@ SIGNATURES = {
     'earl_tabletop3_plan_mppi_value': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue)] + [C.c_void_p] * 7,
     'earl_tabletop_mpc_rollout_value': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue), C.c_int32, _P(TabletopOut), _P(MpcOut), C.c_void_p],
     'earl_tabletop3_mpc_rollout_value': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue), C.c_int32, _P(TabletopOut), _P(MpcOut), C.c_void_p],
+    'earl_tabletop_plan_mppi_prior': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue), _P(PlanPrior)] + [C.c_void_p] * 7,
+    'earl_tabletop3_plan_mppi_prior': [_P(TabletopCfg), _P(TabletopState), _P(PlanParams), _P(PlanValue), _P(PlanPrior)] + [C.c_void_p] * 7,
     'earl_tabletop_plan_cem': [_P(TabletopCfg), _P(TabletopState), _P(CemParams), _P(PlanValue)] + [C.c_void_p] * 9,
     'earl_tabletop3_plan_cem': [_P(TabletopCfg), _P(TabletopState), _P(CemParams), _P(PlanValue)] + [C.c_void_p] * 9,
     'earl_tabletop_cem_candidates': [_P(TabletopCfg), _P(CemParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],

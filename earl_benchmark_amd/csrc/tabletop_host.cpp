@@ -1,5 +1,5 @@
 // tabletop_host.cpp -- the `_cpu` entry points of include/earl_tabletop.h (BASELINE configs[0]: "1 env, CPU ... plumbing, no GPU"):
-// the SAME per-env functions the gfx950 kernels run (tabletop_device.h, tabletop_step.h, philox.h; the planners' tabletop_plan.h, tabletop_value.h, tabletop_mpc.h, tabletop_cem.h;
+// the SAME per-env functions the gfx950 kernels run (tabletop_device.h, tabletop_step.h, philox.h; the planners' tabletop_plan.h, tabletop_value.h, tabletop_mpc.h, tabletop_cem.h, tabletop_prior.h;
 // the policies' tabletop_policy.h), compiled for the host by g++ (-DEARL_HOST_BUILD: earl_rt.h -> host_shim.h) with -ffp-contract=off, one OpenMP iteration per env
 // where a kernel has one lane per env.  This file owns only the walks: for_each_env, rollout_tiles, for_each_branch_tile (the branch-shaped launches' (branch, tile)
 // range), update_env (one env's MPPI reweighting) and cem_update_env (one env's CEM refit), each for its planner and its receding-horizon loop; no arithmetic of an env or
@@ -14,6 +14,7 @@
 #include "tabletop_plan.h"
 #include "tabletop_mpc.h"
 #include "tabletop_cem.h"
+#include "tabletop_prior.h"
 #include "tabletop_policy.h"
 #include "../../include/earl_physics.h"
 
@@ -146,9 +147,10 @@ inline void for_each_branch_tile(long long blocks, int K, int n, F&& f) {
 
 // One reweighting of ONE env (items 4-5 of the planner's contract), stated once for the planner and the receding-horizon loop: beta / best_k over the K returns in
 // ascending k, the weights once per k, then per plan row the integer sums in ascending k (branch 0 is the mean and adds nothing; W == 0 is skipped) and plan_new_mean.
-// ret(k) = return k; row(t, m) = the CLIPPED row t of the plan entering; put(t, d, v) = word d of row t of the plan leaving.  -> (beta, best_k)
-template <class Ret, class Row, class Put>
-inline std::pair<double, int> update_env(const PlanArgs& p, int i, Ret&& ret, Row&& row, Put&& put) {
+// ret(k) = return k; row(t, m) = the CLIPPED row t of the plan entering; put(t, d, v) = word d of row t of the plan leaving; acc(k, t, m, W, A) = item 5 of branch
+// k >= 1 (plan_accumulate wherever the candidate is made again; the `_prior` twin reads its prior branches back).  -> (beta, best_k)
+template <class Ret, class Row, class Put, class Acc>
+inline std::pair<double, int> update_env_with(const PlanArgs& p, Ret&& ret, Row&& row, Put&& put, Acc&& acc) {
   double beta = -INFINITY;
   int bk = 0;
   for (int k = 0; k < p.K; ++k) plan_best(ret(k), k, beta, bk);
@@ -161,11 +163,16 @@ inline std::pair<double, int> update_env(const PlanArgs& p, int i, Ret&& ret, Ro
     for (int k = 0; k < p.K; ++k) {
       const int32_t W = Wk[k];
       S += W;
-      if (W != 0 && k > 0) plan_accumulate(p, i, (uint32_t)k, (uint32_t)t, m, W, A);
+      if (W != 0 && k > 0) acc(k, t, m, W, A);
     }
     for (int d = 0; d < 3; ++d) put(t, d, plan_new_mean(m[d], A[d], S));
   }
   return {beta, bk};
+}
+template <class Ret, class Row, class Put>
+inline std::pair<double, int> update_env(const PlanArgs& p, int i, Ret&& ret, Row&& row, Put&& put) {
+  return update_env_with(p, ret, row, put,
+                    [&](int k, int t, const float (&m)[3], int32_t W, int64_t (&A)[3]) { plan_accumulate(p, i, (uint32_t)k, (uint32_t)t, m, W, A); });
 }
 
 // The branch launch on the host: each env of each (branch, tile) through branch_body, the function the kernel runs.
@@ -220,6 +227,63 @@ int do_plan(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const e
     });
   }
   return EARL_OK;
+}
+
+// The planner with policy-prior branches on the host (include/earl_tabletop.h, "MPPI with policy-prior branches"): do_plan's walk; a (branch, tile) of 1 <= k <= P runs
+// tabletop_prior.h's prior_score_body, every other one plan_score_body, and update_env reads the prior branches back through prior_accumulate -- the device's three launches
+template <int NOBJ, bool VALUE>
+int do_plan_prior_v(const PlanPriorArgs& p0, const earl_plan_params* pp, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k,
+                    long long blocks) {
+  PlanPriorArgs p = p0;
+  const int n = p.a.cfg.n, K = pp->K, P = p.pr.P;
+  const bool general = is_general(&p.a.cfg);
+  for (int it = 0; it < pp->iterations; ++it) {
+    const bool last = it + 1 == pp->iterations;
+    p.mean = it ? plan : mean;
+    p.word0 = kPlanDraw | (uint32_t)(pp->iteration0 + it);
+    p.ret0 = ret0 ? ret0 + (size_t)it * n : nullptr;
+    for_each_branch_tile(blocks, K, n, [&](int i, int k) {
+      if (k >= 1 && k <= P) {
+        if (general) prior_score_body<NOBJ, true, VALUE>(p, i, k);
+        else prior_score_body<NOBJ, false, VALUE>(p, i, k);
+      } else {
+        if (general) plan_score_body<NOBJ, true, VALUE>(p, i, k, &p.v);
+        else plan_score_body<NOBJ, false, VALUE>(p, i, k, &p.v);
+      }
+    });
+    for_each_env(n, [&](int i) {
+      const auto [beta, bk] = update_env_with(
+          p, [&](int k) { return ret[(size_t)k * n + i]; }, [&](int t, float (&m)[3]) { plan_mean(p, i, t, m); },
+          [&](int t, int d, float v) { plan[((size_t)t * n + i) * 3 + d] = v; },
+          [&](int k, int t, const float (&m)[3], int32_t W, int64_t (&A)[3]) {
+            if (k <= P) prior_accumulate(p, i, (uint32_t)k, (uint32_t)t, m, W, A);
+            else plan_accumulate(p, i, (uint32_t)k, (uint32_t)t, m, W, A);
+          });
+      if (last && best_ret) best_ret[i] = beta;
+      if (last && best_k) best_k[i] = bk;
+    });
+  }
+  return EARL_OK;
+}
+
+template <int NOBJ>
+int do_plan_prior(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* pp, const earl_plan_value* pv, const earl_plan_prior* prior,
+                  const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k) {
+  if (!st) return fail(EARL_ERR_ARG, "cfg/state is NULL");
+  long long blocks, ublocks;
+  if (int rc = check_plan(cfg, st, NOBJ, pp, 0, mean, plan, ret, &blocks, &ublocks)) return rc;
+  if (pv)
+    if (int rc = check_plan_value(pv, Dims<NOBJ>::NOBS)) return rc;
+  if (int rc = check_plan_prior(cfg, pp, prior, Dims<NOBJ>::NOBS, mean, plan, ret)) return rc;
+  if (blocks == 0) return EARL_OK;
+  PlanPriorArgs p{};
+  static_cast<PlanArgs&>(p) = plan_args(cfg, st, pp, mean, thresholds());
+  if (pv) p.v = value_args(pv);
+  p.pr = prior_args(prior);
+  p.plan = plan;
+  p.ret = ret;
+  return pv ? do_plan_prior_v<NOBJ, true>(p, pp, mean, plan, ret, ret0, best_ret, best_k, blocks)
+            : do_plan_prior_v<NOBJ, false>(p, pp, mean, plan, ret, ret0, best_ret, best_k, blocks);
 }
 
 // The receding-horizon loop on the host (include/earl_tabletop.h, "receding-horizon MPPI control"): one OpenMP iteration per env -- the device's workgroup -- holds
@@ -470,6 +534,14 @@ int earl_tabletop_plan_mppi_value_cpu(const earl_tabletop_cfg* cfg, const earl_t
 int earl_tabletop3_plan_mppi_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
                                        const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k) {
   return do_plan<3, true>(cfg, st, params, pv, mean, plan, ret, ret0, best_ret, best_k);
+}
+int earl_tabletop_plan_mppi_prior_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                      const earl_plan_prior* prior, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k) {
+  return do_plan_prior<1>(cfg, st, params, pv, prior, mean, plan, ret, ret0, best_ret, best_k);
+}
+int earl_tabletop3_plan_mppi_prior_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                       const earl_plan_prior* prior, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k) {
+  return do_plan_prior<3>(cfg, st, params, pv, prior, mean, plan, ret, ret0, best_ret, best_k);
 }
 int earl_tabletop_plan_candidates_cpu(const earl_tabletop_cfg* cfg, const earl_plan_params* params, int32_t j, const float* mean, float* act_out) {
   long long blocks, ublocks;

@@ -554,7 +554,22 @@ class TabletopManipulation:
     pv._keep = value
     return pv
 
-  def plan_mppi(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, out=None, discount=1.0, value=None):
+  def _plan_prior_check(self, who, prior, P, K):
+    """what a policy prior must be before the call: an MLPPolicy from the observation to the three action dimensions, float32, on the env's device, no Gaussian head"""
+    from ..policy import GaussianMLPPolicy, MLPPolicy
+    if not isinstance(prior, MLPPolicy) or isinstance(prior, GaussianMLPPolicy):
+      raise ValueError(f'{who}: prior is an MLPPolicy(layers, hidden_act, out_act, obs_dim={self.OBS_DIM}, act_dim=3) without a Gaussian head')
+    require_widths(prior, who, self.OBS_DIM, 3, env=self)
+    if prior.param_dtype != torch.float32:
+      raise ValueError(f'{who}: the prior stores its parameters as {prior.param_dtype}; float32 only (pass .widened())')
+    if len(prior.dims) == 4 and prior.dims[1] > _abi.PLAN_PRIOR_MAX_H1:
+      raise ValueError(f'{who}: a prior of two hidden layers has a first one of at most {_abi.PLAN_PRIOR_MAX_H1} (a lane holds it in registers), got {prior.dims[1]}; '
+                       'one hidden layer may be 256 wide')
+    if P < 0 or P >= K:
+      raise ValueError(f'{who}: prior_branches = {P}: 0 .. K - 1 = {K - 1} (branch 0 is the plan itself)')
+
+  def plan_mppi(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, out=None, discount=1.0, value=None,
+                prior=None, prior_branches=0, prior_sigma=0.0):
     """`iterations` MPPI iterations on the device from the CURRENT state (include/earl_tabletop.h: earl_tabletop_plan_mppi): K candidates per env -- the mean plan
     itself and K - 1 copies with clipped Gaussian noise of scale `sigma` (a number or three) -- scored as rollout_branches scores them, the mean moved to their
     average under the weights exp((ret - max ret) / temperature).  The candidates are never in memory: the noise is made inside the scoring kernel and made again
@@ -568,7 +583,13 @@ class TabletopManipulation:
     to one number) change the score of a candidate from the plain sum of its H rewards to  sum_t gamma^t r_t + gamma^H V(o_H)  (earl_tabletop_plan_mppi_value): the
     network is evaluated inside the scoring kernel on the last look-ahead observation of every branch, no [K, N, D] tensor and no extra launch in between.  Under
     the sparse reward that is what lets a short horizon see a goal further than H steps away.  One hidden layer may be 256 wide; of two, the first is at most
-    16 (_abi.PLAN_VALUE_MAX_H1).  With both defaults the call is the value-free entry point, exactly as before."""
+    16 (_abi.PLAN_VALUE_MAX_H1).  With both defaults the call is the value-free entry point, exactly as before.
+    `prior` (an `MLPPolicy(layers, hidden_act, out_act, obs_dim=D, act_dim=3)` on the env's device, float32, no Gaussian head) makes the candidates 1 .. `prior_branches`
+    closed-loop rollouts under that policy instead of noise around the mean (earl_tabletop_plan_mppi_prior): at every look-ahead step the lane that owns the branch
+    evaluates the policy on the observation its own env copy just produced and adds `prior_sigma` (a number or three) times the branch's noise.  The result gains
+    'prior_actions' [prior_branches, H, N, 3] float32, the actions those branches took in the last iteration (also the call's workspace: allocated when `out` leaves
+    it out).  One hidden layer may be 256 wide; of two, the first is at most 16 (_abi.PLAN_PRIOR_MAX_H1).  `discount` / `value` combine with it as above.  With
+    prior=None the call is the entry point it was before the keyword existed."""
     m = self._plan_mean('plan_mppi', mean, horizon)
     n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
     pp = self._plan_params('plan_mppi', K, H, I, iteration0, sigma, temperature, noise_counter)
@@ -577,6 +598,13 @@ class TabletopManipulation:
             'best_k': ((n,), torch.int32)}
     if K < 1 or H < 1 or I < 1:
       raise ValueError(f'plan_mppi: K = {K}, H = {H}, iterations = {I}: at least one of each')
+    P = int(prior_branches)
+    if prior is None:
+      if P != 0:
+        raise ValueError(f'plan_mppi: prior_branches = {P} without a prior')
+    else:
+      self._plan_prior_check('plan_mppi', prior, P, K)
+      want['prior_actions'] = ((P, H, n, 3), torch.float32)
     if out is None:
       res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
     else:
@@ -591,9 +619,20 @@ class TabletopManipulation:
         raise ValueError("plan_mppi: out['plan'] is what the call computes")
       if 'ret' not in res:
         res['ret'] = torch.empty(K, n, dtype=torch.float64, **kw)
+      if prior is not None and 'prior_actions' not in res:
+        res['prior_actions'] = torch.empty(P, H, n, 3, dtype=torch.float32, **kw)
     pv = self._plan_value('plan_mppi', discount, value)
     with self._ctx():
-      if pv is None:
+      if prior is not None:
+        ps = torch.as_tensor(prior_sigma, dtype=torch.float32).reshape(-1).tolist()
+        if len(ps) not in (1, 3):
+          raise ValueError('plan_mppi: prior_sigma is a number or three, one per action dimension')
+        pr = _abi.PlanPrior(policy=C.pointer(prior.struct), branches=P, sigma=(C.c_float * 3)(*(ps * 3 if len(ps) == 1 else ps)),
+                            act=res['prior_actions'].data_ptr() if P else None)
+        fn = self._lib.earl_tabletop_plan_mppi_prior if self.NOBJ == 1 else self._lib.earl_tabletop3_plan_mppi_prior
+        rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), C.byref(pv) if pv is not None else None, C.byref(pr), m.data_ptr(), res['plan'].data_ptr(),
+                res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')), _ptr(res.get('best_k')), self._stream())
+      elif pv is None:
         fn = self._lib.earl_tabletop_plan_mppi if self.NOBJ == 1 else self._lib.earl_tabletop3_plan_mppi
         rc = fn(self._cfg_ref, self._st_ref, C.byref(pp), m.data_ptr(), res['plan'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
                 _ptr(res.get('best_k')), self._stream())

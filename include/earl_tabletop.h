@@ -503,6 +503,47 @@ int earl_tabletop_mpc_rollout_value(const earl_tabletop_cfg* cfg, const earl_tab
 int earl_tabletop3_mpc_rollout_value(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv, int32_t T,
                                      const earl_tabletop_out* out, const earl_mpc_out* mpc, earl_stream_t stream);
 
+/* ---- MPPI with policy-prior branches: P of the K candidates rolled out closed loop under a policy, the policy evaluated inside the score kernel ----
+ * A TD-MPC-style planner proposes a few of its candidates with a learned policy pi: they carry the search where Gaussian noise around a zero or stale mean never
+ * gets (under the sparse reward with the goal further than H steps away, every noise branch scores the same).  The two entry points below are
+ * earl_tabletop[3]_plan_mppi (pv == NULL) or earl_tabletop[3]_plan_mppi_value (pv != NULL: the `_value` block, item 3 included) with TWO items of the contract
+ * amended; everything else written for those calls -- items 1, 3, 4, 6, 7, chaining, state, counters, the noise counter words and every refusal -- holds word for word.
+ *   2 candidates, branches 1 <= k <= P (P = prior->branches).  x_t = the float32 observation row the branch's env last produced: at t = 0 _get_obs() of the incoming
+ *              state; afterwards the row the wrapped step t - 1 emitted (after a lifelong goal switch: the re-read row; after an auto-reset inside the look-ahead:
+ *              the terminal row) -- exactly what earl_tabletop[3]_policy_rollout(reset_first = 0) feeds its policy.  u = pi(x_t) under the policy contract of this
+ *              header: acc = b_j; k ascending: acc = fmaf(x_k, W_jk, acc); relu / tanh_f32 of csrc/policy_math.h on the hidden layers, out_act on the output
+ *              (earl_mlp_policy_forward_cpu with head = NULL states it on the host).  a_k[t][d] = clip(fmaf(prior->sigma[d], eps, u[d])), eps from the SAME Philox
+ *              block item 2 assigns to (j, g, k, t, noise_counter): same word 0, no new draw id.  clip maps a NaN of u to -1, so every candidate stays finite whatever
+ *              the weights hold.  a_k is stored to prior->act[k - 1][t][env][d].  Branch 0 and the branches k > P are as they were.  The prior branches are made
+ *              again in every iteration j with that iteration's noise word, so `chaining` holds as it stands (prior->act then holds the last iteration's rows).
+ *   5 update   for k <= P the update reads a_k back from prior->act instead of making it again; delta, D_k (|D_k| <= 2^21 still: both operands lie in [-1, 1]), the
+ *              integer sums and mean' are unchanged.
+ *   identity   branches == 0 (policy and act may then be NULL): every output equals earl_tabletop[3]_plan_mppi (pv == NULL) or earl_tabletop[3]_plan_mppi_value bit
+ *              for bit.
+ *   launch     per iteration three launches on the caller's stream: the score launch over the K - P branches that are not prior branches (plan_mppi's kernel body),
+ *              a score launch of the same shape over the P prior branches (a wave is 64 envs of ONE branch, so the policy's weights are wave-uniform scalar loads:
+ *              the noise branches pay nothing for the network, in registers or in time), and the update.  No allocation, no host synchronisation: the call can be
+ *              captured.  `st` is never written and the caller does not advance its counter.
+ * EARL_PLAN_PRIOR_MAX_H1: a lane holds the FIRST hidden layer of a two-hidden-layer policy in registers, the second is streamed into the three outputs (as the only
+ * hidden layer of a one-hidden-layer policy is: those may be 256 wide).  The network runs inside the look-ahead loop, next to the env state; the score kernels are
+ * 64-lane workgroups without a 128-VGPR cap and compile without scratch at 16 (DESIGN 8 has the table).
+ * EARL_ERR_ARG before any HIP call for: everything the underlying call refuses (with pv: the `_value` block's refusals); prior NULL; branches < 0 or >= K; a prior
+ * sigma that is negative or not finite; with branches > 0: policy or act NULL, a network the policy contract refuses with the env's observation width (12 / 20),
+ * action width 3 and no head (csrc/policy_check.h), n_layers == 3 with dims[1] > EARL_PLAN_PRIOR_MAX_H1, act overlapping mean, plan or ret. */
+#define EARL_PLAN_PRIOR_MAX_H1 16
+typedef struct earl_plan_prior {
+  const earl_mlp_policy* policy;  /* obs -> 3: dims[0] = 12 / 20, dims[n_layers] = 3, precision 0, no head */
+  int32_t branches;               /* P: 0 .. K - 1 */
+  float sigma[3];                 /* noise added to the policy's action, finite, >= 0 */
+  float* act;                     /* [P, H, n, 3]: the workspace between the score and the update launch AND an output (the prior branches' actions of the last iteration) */
+} earl_plan_prior;
+int earl_tabletop_plan_mppi_prior(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                  const earl_plan_prior* prior, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k,
+                                  earl_stream_t stream);
+int earl_tabletop3_plan_mppi_prior(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                   const earl_plan_prior* prior, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k,
+                                   earl_stream_t stream);
+
 /* ---- CEM planning: the cross-entropy method on the same launches -- elites instead of weights, a refitted std per (step, env, dim) ----
  * The planner of PETS, PlaNet and TD-MPC around envs/tabletop_manipulation.py:128-138: K noisy copies of a mean plan, the E best of them refit mean AND standard
  * deviation.  The update regenerates only the E elites from their counters (MPPI's regenerates all K), and the refitted std widens or narrows the search inside the
@@ -639,6 +680,13 @@ int earl_tabletop_mpc_rollout_value_cpu(const earl_tabletop_cfg* cfg, const earl
                                         const earl_tabletop_out* out, const earl_mpc_out* mpc);
 int earl_tabletop3_mpc_rollout_value_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv, int32_t T,
                                          const earl_tabletop_out* out, const earl_mpc_out* mpc);
+/* host twins of earl_tabletop[3]_plan_mppi_prior: the planner's twin with the kernels' own per-lane functions of csrc/tabletop_prior.h; the policy's params and
+ * prior->act are HOST pointers.  Bit-identical to the device in every output, prior->act included, under the sparse reward; under the dense one as the twins above.
+ * They refuse what the device entry points refuse. */
+int earl_tabletop_plan_mppi_prior_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                      const earl_plan_prior* prior, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k);
+int earl_tabletop3_plan_mppi_prior_cpu(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, const earl_plan_params* params, const earl_plan_value* pv,
+                                       const earl_plan_prior* prior, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k);
 /* host twins of earl_tabletop[3]_plan_cem, earl_tabletop_cem_candidates and earl_tabletop[3]_mpc_rollout_cem: the kernels' per-lane functions (csrc/tabletop_cem.h) in
  * plain loops.  Items 4 - 5 are integer: bit-identical to the device in every output under the sparse reward; under the dense one ret, ret0 and best_ret within
  * 1e-6 relative of the sum of |reward| and the plans not comparable.  They refuse what the device entry points refuse. */

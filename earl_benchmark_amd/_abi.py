@@ -140,6 +140,10 @@ class SawyerOut(C.Structure):
   _fields_ = [('obs', C.c_void_p), ('reward', C.c_void_p), ('done', C.c_void_p), ('success', C.c_void_p), ('status', C.c_void_p), ('info', C.c_void_p)]
 
 
+class SawyerBranchWs(C.Structure):   # struct earl_sawyer_branch_ws (include/earl_physics.h): one device block of earl_sawyer_branch_ws_bytes() bytes
+  _fields_ = [('base', C.c_void_p), ('bytes', C.c_int64)]
+
+
 SAWYER_INFO = 8       # EARL_SAWYER_INFO; slots EARL_INFO_* (include/earl_physics.h)
 SAWYER_INFO_KEYS = ('success', 'near_object', 'grasp_success', 'grasp_reward', 'in_place_reward', 'obj_to_target', 'unscaled_reward')
 STEP_DIVERGED = 1     # EARL_STEP_DIVERGED (include/earl_physics.h)
@@ -270,6 +274,10 @@ SIGNATURES = {
     # ... in its general form: pop and goals after pair, summary after `out`, each NULL or given
     'earl_sawyer_agents_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(MlpPolicy), _P(AgentPair), _P(PolicyPopulation), _P(BackwardGoals),
                                    _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _P(SawyerOut), _P(EpisodeSummary), C.c_void_p],
+    # K action plans per env scored from the current state: K, H, act, the stride between branches (floats), clock, the workspace, summary, last_obs, fail
+    'earl_sawyer_branch_ws_bytes': [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int64)],
+    'earl_sawyer_branch_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                   _P(SawyerBranchWs), _P(EpisodeSummary), C.c_void_p, C.c_void_p, C.c_void_p],
     # the closed loop inside the minitaur rollout kernels: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
     'earl_minitaur_policy_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, _P(MinitaurOut), C.c_void_p],

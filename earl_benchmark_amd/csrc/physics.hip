@@ -227,6 +227,63 @@ int earl_sawyer_policy_rollout(const earl_link_model* model, const earl_collisio
   return earl_sawyer_population_rollout(model, col, nv, cfg, st, policy, nullptr, head, obs0, T, clock, actions, out, nullptr, stream);
 }
 
+// include/earl_physics.h: K action plans per env scored from the current state in ONE launch over K n virtual envs (kernels: physics_branch.hip, physics_branch_w8.hip).
+// The workspace block, carved here: [V, nv + 1] qpos (rows of the model's nq), [V, nv] qvel, [V, 3] mocap_pos, [V, 7] goal, [V, 14] carried observation rows (unused when
+// the caller's last_obs takes them), then int32 [V] goal-switch counters and [2 ceil(V / 4)] work queue; V = K n
+static int64_t sawyer_branch_bytes(int32_t nv, int64_t V) { return V * (int64_t)((nv + 1 + nv + 3 + 7 + 14) * sizeof(double) + sizeof(int32_t)) + 2 * ((V + 3) / 4) * (int64_t)sizeof(int32_t); }
+int earl_sawyer_branch_ws_bytes(int32_t nv, int32_t K, int32_t n, int64_t* bytes) {
+  if (!bytes || (nv != 10 && nv != 15) || K < 0 || n < 0 || (int64_t)K * n > INT32_MAX) return EARL_ERR_ARG;
+  *bytes = sawyer_branch_bytes(nv, (int64_t)K * n);
+  return EARL_OK;
+}
+int earl_sawyer_branch_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
+                               const earl_episode_summary* summary, double* last_obs, int32_t* fail, earl_stream_t stream) {
+  const earl_sawyer_out none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (!model || !cfg || !st || !act || !ws || K < 0 || H < 0 || (nv != 10 && nv != 15) || !sawyer_args_ok(kStep, cfg, st, nv, &none)) return EARL_ERR_ARG;
+  const int n = cfg->n;
+  if (act_branch_stride < 0 || (act_branch_stride != 0 && act_branch_stride < (int64_t)H * n * 4)) return EARL_ERR_ARG;
+  if (!(summary && (summary->ret || summary->success_last || summary->first_success)) && !last_obs && !fail) return EARL_ERR_ARG;      // (nothing to compute)
+  const int64_t V = (int64_t)K * n;
+  if (V > INT32_MAX) return EARL_ERR_ARG;
+  if (V > 0 && (!ws->base || (reinterpret_cast<uintptr_t>(ws->base) & 7) != 0 || ws->bytes < sawyer_branch_bytes(nv, V))) return EARL_ERR_ARG;
+  if (g_lpe == 64) return EARL_ERR_ARG;                   // (the 64-lane measurement builds: no branch form)
+  if (V == 0 || H == 0) return EARL_OK;
+  if (int rc = check_cone(col, true, (hipStream_t)stream, "sawyer_branch_rollout")) return rc;
+  double* d = static_cast<double*>(ws->base);
+  earl_sawyer_state vs{};                                 // the virtual envs' state: the workspace's rows (steps_since_reset, last_obs, fail_count: NULL, a branch keeps none)
+  vs.qpos = d; d += V * (nv + 1);
+  vs.qvel = d; d += V * nv;
+  vs.mocap_pos = d; d += V * 3;
+  vs.goal = d; d += V * 7;
+  double* const rows = d; d += V * 14;
+  int32_t* w = reinterpret_cast<int32_t*>(d);
+  vs.steps_since_goal_change = cfg->goal_change_frequency > 0 ? w : nullptr; w += V;
+  vs.obj_init = st->obj_init;                             // (read only, indexed by the env: v % n)
+  SawyerBranchArgs a;
+  static_cast<SawyerArgs&>(a) = SawyerArgs{model, col, *cfg, vs, act, H, none, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
+  a.cfg.n = (int)V;
+  a.n_env = n;
+  a.act_stride = act_branch_stride;
+  a.obs_row = last_obs ? last_obs : rows;
+  a.br_ret = summary ? summary->ret : nullptr;
+  a.br_last = summary ? summary->success_last : nullptr;
+  a.br_first = summary ? summary->first_success : nullptr;
+  a.br_fail = fail;
+  // the form by the number of virtual envs, with the closed loop's reading of the door variants; the queue is always there, so the peg's time-sliced form is sawyer_form's to choose
+  a.st.sched = w;
+  const SawyerForm form = sawyer_form(nv, (int)V, H, &a.st, true);
+  if (form == SawyerForm::PegSliced) a.slice = peg_slice();
+  else a.st.sched = nullptr;                              // (the replicate kernel clears the queue only where it is used)
+  if (int rc = earl_unit_branch_replicate(&a, st, nv, stream)) return rc;
+  switch (form) {
+    case SawyerForm::DoorW8: return earl_unit_branch_w8_sawyer_rollout(&a, stream);
+    case SawyerForm::Door: case SawyerForm::Peg: return earl_unit_branch_sawyer_rollout(&a, nv, 0, stream);
+    case SawyerForm::PegSliced: return earl_unit_branch_sawyer_rollout(&a, nv, 1, stream);
+    default: return EARL_ERR_ARG;                         // (L64 was refused above; the policy reading never gives DoorSliced)
+  }
+}
+
 int earl_sawyer_reset(const earl_link_model* model, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                       const double* reset_qpos, const double* reset_qvel, const uint8_t* mask, double* obs,
                       earl_stream_t stream) {

@@ -18,6 +18,18 @@ struct SawyerArgs {
 // earl_sawyer_policy_rollout: the rollout's arguments (action unused) plus the policy.  A struct of its own so that the plain kernels' argument stays what it was
 #include "policy_closed_loop.h"
 struct SawyerPolicyArgs : ClosedLoopArgs<SawyerArgs> {};      // pol.dims[0] = 14, pol.dims[n_layers] = 4 (8 with the head); goal rows of 7
+// earl_sawyer_branch_rollout: the rollout's arguments over the K n VIRTUAL envs of the launch -- cfg.n = K n, st = the [K n] rows of the caller's workspace (st.obj_init:
+// the env's own [n] rows; steps_since_reset, last_obs, fail_count NULL), every pointer of `out` NULL -- plus what a branch reads and keeps.  A struct of its own, like
+// SawyerPolicyArgs and for its reason; the fields below are read through the kernel-argument segment where they are used (policy_closed_loop.h)
+struct SawyerBranchArgs : SawyerArgs {
+  int n_env;                     // the env's n: virtual env v is branch k = v / n_env of env i = v % n_env
+  int64_t act_stride;            // floats between two branches' [T, n_env, 4] blocks of `action` (0: one block for all)
+  double* obs_row;               // [K n, 14] the one observation row a virtual env keeps: the caller's last_obs output, or the workspace's rows
+  double* br_ret;                // the branch's episode summary and its count of rolled-back steps, each NULL or [K n]: kept as cl_episode_summary keeps a summary
+  uint8_t* br_last;
+  int32_t* br_first;
+  int32_t* br_fail;
+};
 
 // Work queue of the time-sliced rollout (earl_sawyer_state.sched: progress[G] then lock[G], zero on entry).  An env group's state is in HBM after every env
 // step (the failure guard's "last stable state"), so ANY wave can take the group's next slice of env steps; a wave claims the unlocked group that has come
@@ -294,6 +306,34 @@ __device__ __forceinline__ float4 sawyer_step_action(const A& a, const int t, co
   }
 }
 
+// ------------------------------------------------------------------------------------------------ the pieces of sawyer_branch_rollout_kernel (BRANCH)
+// Every SawyerBranchArgs field is read through the kernel-argument segment here, where it is used (policy_closed_loop.h on why): nothing of a branch's bookkeeping
+// lives across a timestep.
+// the env a virtual env is a branch of: i = v % n_env
+__device__ __forceinline__ int sawyer_branch_env(const int v) { return v % cl_kernarg<SawyerBranchArgs>()->n_env; }
+// the action of env step t of virtual env v: row (t, i) of branch v / n_env's block
+__device__ __forceinline__ float4 sawyer_branch_action(const int t, const int v) {
+  const EARL_KARG SawyerBranchArgs* ka = cl_kernarg<SawyerBranchArgs>();
+  const int n = ka->n_env, k = v / n, i = v - k * n;
+  return *reinterpret_cast<const float4*>(ka->action + (size_t)k * (size_t)ka->act_stride + ((size_t)t * n + i) * 4);
+}
+// the virtual env's summary and rolled-back steps after env step t, by lane 0 of the live env: cl_episode_summary's three words, each its definition applied to the
+// step's reward and success as a rollout would have stored them (a rolled-back step: 0 and 0), and the number of such steps; step 0 initialises all four
+__device__ __forceinline__ void sawyer_branch_summary(const int t, const int v, const double r_t, const uint8_t s_t, const bool failed) {
+  const EARL_KARG SawyerBranchArgs* ka = cl_kernarg<SawyerBranchArgs>();
+  double* const ret = ka->br_ret;
+  uint8_t* const last = ka->br_last;
+  int32_t* const first = ka->br_first;
+  int32_t* const fail = ka->br_fail;
+  if (ret) ret[v] = (t > 0 ? ret[v] : 0.0) + r_t;                      // sum over t ascending of (double)reward_t
+  if (last) last[v] = s_t;                                             // (the one of step T - 1 stays)
+  if (first) {
+    const int32_t f = t > 0 ? first[v] : -1;
+    first[v] = (f < 0 && s_t) ? t : f;
+  }
+  if (fail) fail[v] = (t > 0 ? fail[v] : 0) + (failed ? 1 : 0);
+}
+
 #ifndef EARL_WAVES_PER_EU
 #define EARL_WAVES_PER_EU 1
 #endif
@@ -302,6 +342,7 @@ __device__ __forceinline__ float4 sawyer_step_action(const A& a, const int t, co
 template <int NV, int LPE, bool SLICED = false>
 __global__ __launch_bounds__(64 * Lim<NV>::WPB, EARL_WAVES_PER_EU) void sawyer_rollout_kernel(const SawyerArgs a) {
   constexpr bool POLICY = false;
+  constexpr bool BRANCH = false;
 #include "physics_env_sawyer_rollout.inc"
 }
 // The same rollout with the policy inside (earl_sawyer_policy_rollout): 16 lanes per env only (the policy phase is laid out over an env's 16 lanes)
@@ -312,6 +353,18 @@ template <int NV, int LPE, bool SLICED = false>
 __global__ __launch_bounds__(64 * Lim<NV>::WPB, EARL_WAVES_PER_EU) void sawyer_policy_rollout_kernel(const SawyerPolicyArgs a) {
   static_assert(LPE == 16, "the policy phase is laid out over 16 lanes per env");
   constexpr bool POLICY = true;
+  constexpr bool BRANCH = false;
+#include "physics_env_sawyer_rollout.inc"
+}
+// The same rollout over the K n virtual envs of a branch launch (earl_sawyer_branch_rollout; instantiated in physics_branch.hip and physics_branch_w8.hip only): every
+// action given, no [T] row written, the state rows the workspace's.  `a` must stay the kernel's ONLY argument, as for the policy kernel: the branch's fields are read
+// through the kernel-argument segment pointer cast to SawyerBranchArgs*
+static_assert(std::is_trivially_copyable<SawyerBranchArgs>::value, "the branch pieces read SawyerBranchArgs as laid out in the kernel-argument segment");
+template <int NV, int LPE, bool SLICED = false>
+__global__ __launch_bounds__(64 * Lim<NV>::WPB, EARL_WAVES_PER_EU) void sawyer_branch_rollout_kernel(const SawyerBranchArgs a) {
+  static_assert(LPE == 16, "the branch launch has the 16-lane forms only");
+  constexpr bool POLICY = false;
+  constexpr bool BRANCH = true;
 #include "physics_env_sawyer_rollout.inc"
 }
 

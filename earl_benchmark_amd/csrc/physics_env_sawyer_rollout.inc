@@ -1,6 +1,8 @@
 // physics_env_sawyer_rollout.inc -- the body of the Sawyer door / peg rollout kernels (physics_env_sawyer.h): sawyer_rollout_kernel includes it with POLICY = false
 // (every action given), sawyer_policy_rollout_kernel with POLICY = true (the action of env step t computed by the env's own 16 lanes from the observation the env
-// last emitted).  Template parameters NV, LPE, SLICED and the kernel argument `a` are the including kernel's.
+// last emitted), sawyer_branch_rollout_kernel with BRANCH = true (the K n virtual envs of earl_sawyer_branch_rollout: `a.cfg.n` is their number, `env` a virtual env, the rows
+// of `a.st` the workspace's; actions given per branch, no [T] row written, per-branch summaries).  Template parameters NV, LPE, SLICED and the kernel argument `a` are
+// the including kernel's.
   static_assert(LPE >= 14, "the observation is written by 14 lanes");
   constexpr int EPW = 64 / LPE, WPB = Lim<NV>::WPB;
   __shared__ alignas(16) typename ModelOf<NV>::T m;
@@ -39,7 +41,9 @@
   int sgc = gcf > 0 ? a.st.steps_since_goal_change[env] : 0;
   RSTART();
   for (int t = t_begin; t < t_end; ++t) {
-    const float4 act = sawyer_step_action<POLICY>(a, t, n, env, sub, live);
+    float4 act;
+    if constexpr (BRANCH) act = sawyer_branch_action(t, env);      // (`env` is the virtual env v, `n` their number K n_env: see SawyerBranchArgs)
+    else act = sawyer_step_action<POLICY>(a, t, n, env, sub, live);
     // set_xyz_action [UPSTREAM]: clip, float32 product with the scale, float64 add, box clip
     const float cx = fminf(fmaxf(act.x, -1.f), 1.f) * scale, cy = fminf(fmaxf(act.y, -1.f), 1.f) * scale, cz = fminf(fmaxf(act.z, -1.f), 1.f) * scale;
     if (sub < 3) {                                      // lane k moves coordinate k
@@ -82,12 +86,22 @@
       carried = a.out.obs == nullptr;
       obs_row = carried ? a.st.last_obs + (size_t)env * 14 : a.out.obs + row * 14;
     }
+    // BRANCH: the virtual env's row of SawyerBranchArgs.obs_row is the one row it keeps, carried as the population launch carries st.last_obs; obj_init is the env's own
+    // row, i = v % n_env (worked out here, where it is used: nothing of it lives across the timesteps above)
+    [[maybe_unused]] const double* br_obj_init = nullptr;
+    if constexpr (BRANCH) {
+      carried = true;
+      obs_row = cl_kernarg<SawyerBranchArgs>()->obs_row + (size_t)env * 14;
+      if (a.st.obj_init) br_obj_init = a.st.obj_init + (size_t)sawyer_branch_env(env) * 6;
+    }
     // failure guard (MuJoCo's mj_checkPos / mj_checkVel; metaworld's `except MujocoException` in SawyerXYZEnv.step [UPSTREAM]): an env whose
     // state went NaN or beyond EARL_BAD_VALUE is rolled back to its last stable state (the rows in HBM) and re-emits its last stable
     // observation with reward 0; its neighbours in the wavefront never see it (a group only reads its own LDS block)
     const bool bad_lane = (sub < NV && !(fabs(s.qp[sub]) < EARL_BAD_VALUE && fabs(s.qv[sub]) < EARL_BAD_VALUE)) || (sub < 4 && !(fabs(s.bq[sub]) < 2.0));
     const bool failed = group_any<LPE>(bad_lane, grp);
-    if constexpr (POLICY)
+    if constexpr (BRANCH)
+      sawyer_emit<NV>(s, m, cfg, sub, live && !failed, a.st.goal + (size_t)env * 7, obs_row, &rew, &suc, br_obj_init, (double)act.w, nullptr, nullptr);
+    else if constexpr (POLICY)
       sawyer_emit<NV>(s, m, cfg, sub, live && !failed, a.st.goal + (size_t)env * 7, obs_row, &rew, &suc, a.st.obj_init ? a.st.obj_init + (size_t)env * 6 : nullptr,
                       (double)act.w, nullptr, (NV >= 15 && a.out.info) ? a.out.info + row * EARL_SAWYER_INFO : nullptr);
     else
@@ -95,7 +109,7 @@
                     a.out.success ? a.out.success + row : nullptr, a.st.obj_init ? a.st.obj_init + (size_t)env * 6 : nullptr, (double)act.w, nullptr,
                     (NV >= 15 && a.out.info) ? a.out.info + row * EARL_SAWYER_INFO : nullptr);
     RSTAMP(14);
-    if (sub == 0 && live && a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
+    if (!BRANCH && sub == 0 && live && a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;      // (BRANCH: no [T] row of any kind; `!BRANCH && ...` folds away like `POLICY && ...` below)
     if (!failed) {
       // this state is the env's last stable one from here on
       if (live) {
@@ -116,8 +130,11 @@
       load_state<NV>(s, m, a.st.qpos + (size_t)env * m.nq, a.st.qvel + (size_t)env * NV, sub);
       if (sub < 3) s.mocap[sub] = a.st.mocap_pos[(size_t)env * 3 + sub];
       if (live) {
-        if constexpr (POLICY) {
-          if (!carried) {          // (a carried row IS the last stable observation already; reward 0 and success 0 are written with the summary below)
+        if constexpr (BRANCH) {
+          // (the carried row IS the last stable observation -- before the first stable step the env's row of st->last_obs, which the replicate kernel put there;
+          // reward 0, success 0 and the count of such steps are written with the summary below; the env's fail_count is not a branch's to touch)
+        } else if constexpr (POLICY) {
+          if (!carried) {        // (a carried row IS the last stable observation already; reward 0 and success 0 are written with the summary below)
             const double* prev = t > 0 ? a.out.obs + ((size_t)(t - 1) * n + env) * 14 : (a.st.last_obs ? a.st.last_obs + (size_t)env * 14 : nullptr);
             if (sub < 14) a.out.obs[row * 14 + sub] = prev ? prev[sub] : __builtin_nan("");
           }
@@ -131,8 +148,13 @@
           if (a.st.fail_count) a.st.fail_count[env] += 1;
         }
         }
-        if (NV >= 15 && a.out.info && sub < EARL_SAWYER_INFO) a.out.info[row * EARL_SAWYER_INFO + sub] = 0.0;
+        if (!BRANCH && NV >= 15 && a.out.info && sub < EARL_SAWYER_INFO) a.out.info[row * EARL_SAWYER_INFO + sub] = 0.0;
       }
+    }
+    if constexpr (BRANCH) {
+      // reward and success of the step as a rollout would have stored them (a rolled-back step: 0 and 0) into the virtual env's summary, in device memory after every
+      // env step like the population launch's: a time slice another wave takes finds the words under sched_release / sched_claim
+      if (sub == 0 && live) sawyer_branch_summary(t, env, (double)(failed ? 0.f : rew), failed ? (uint8_t)0 : suc, failed);
     }
     if constexpr (POLICY) {
       // reward and success of the step (a rolled-back step: 0 and 0) to their rows, and into the env's episode summary: each word is its definition applied to exactly
@@ -148,10 +170,10 @@
     fence();
     ++steps;
     RSTAMP(15);
-    if (sub == 0 && live && a.out.done) a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
+    if (!BRANCH && sub == 0 && live && a.out.done) a.out.done[row] =(cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
     // door with goal switching: slot 7 of EVERY row's info block is this kernel's to write -- 0, or 1 on a goal-switch row (below) -- so that earl_sawyer_door_info never reads
     // a marker the caller left behind (ADVICE r05: the Python side used to zero the column with a launch of its own before every call)
-    if (NV < 15 && gcf > 0 && a.out.info && sub == 11 && live) a.out.info[row * EARL_SAWYER_INFO + 7] = 0.0;
+    if (!BRANCH && NV < 15 && gcf > 0 && a.out.info && sub == 11 && live) a.out.info[row * EARL_SAWYER_INFO + 7] = 0.0;
     // does this step end with a new goal row?  The lifelong switch's clock, or -- POLICY, earl_sawyer_agents_rollout -- a handover of the agent pair that changes the goal:
     // `fixed` is then the table of `fixed_rows` backward goals to draw from (entering the reset phase; earl_sawyer_pair_rollout's ONE row is the table of one row) or NULL
     // (entering the forward phase: the lifelong switch's own draw from cfg.goal_table)
@@ -195,7 +217,10 @@
         const uint32_t draw = (POLICY && fixed) ? 0xFFFDu : 0xFFFEu;
         const int rows = (POLICY && fixed) ? fixed_rows : cfg.n_goal_rows;
         const double* const table = (POLICY && fixed) ? fixed : cfg.goal_table;
-        const earl::U4 b = earl::philox4x32_10(earl::U4{draw, (uint32_t)(cfg.env_offset + env), (uint32_t)ev, (uint32_t)(ev >> 32)},
+        // (BRANCH: the id is the ENV's, cfg.env_offset + v % n_env, never the virtual index: every branch of an env sees the draw the env's next rollout will see)
+        int gid_env = env;
+        if constexpr (BRANCH) gid_env = sawyer_branch_env(env);
+        const earl::U4 b = earl::philox4x32_10(earl::U4{draw, (uint32_t)(cfg.env_offset + gid_env), (uint32_t)ev, (uint32_t)(ev >> 32)},
                                                (uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32));
         int grow = (int)(earl::u01(b.x, b.y) * (double)rows);
         grow = grow < rows ? grow : rows - 1;
@@ -206,7 +231,7 @@
             if (row_at) row_at[row] = grow;
           }
         }
-        if (NV < 15 && a.out.info && sub >= 11) {
+        if (!BRANCH && NV < 15 && a.out.info && sub >= 11) {
           // the door's info dict is worked out after the launch from the emitted rows (earl_sawyer_door_info), whose goal block is about to change: this
           // row's info slots 0-2 carry the target the row's reward was computed with, slot 7 marks it (evaluate_state runs before reset_goal:
           // lifelong_wrapper.py:30-44; include/earl_physics.h)
@@ -214,7 +239,7 @@
           if (sub == 11) a.out.info[row * EARL_SAWYER_INFO + 7] = 1.0;
         }
         a.st.goal[(size_t)env * 7 + (sub - 7)] = gv;
-        if constexpr (POLICY) obs_row[sub] = gv;
+        if constexpr (POLICY || BRANCH) obs_row[sub] = gv;
         else a.out.obs[row * 14 + sub] = gv;
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");      // the next step's observation reads the goal row back through global memory
@@ -224,7 +249,8 @@
   }
   if (live) {
     // (qpos / qvel / mocap_pos were written back after the last stable step)
-    if constexpr (POLICY) {      // (a carried row is in place)
+    if constexpr (BRANCH) {      // (the carried row is in place; st.last_obs and st.steps_since_reset are NULL here, the goal-switch counter below is the workspace's)
+    } else if constexpr (POLICY) {      // (a carried row is in place)
       if (t_end == a.T && a.st.last_obs && a.out.obs && a.T > 0 && sub < 14) a.st.last_obs[(size_t)env * 14 + sub] = a.out.obs[((size_t)(a.T - 1) * n + env) * 14 + sub];
     } else
     if (t_end == a.T && a.st.last_obs && a.T > 0 && sub < 14) a.st.last_obs[(size_t)env * 14 + sub] = a.out.obs[((size_t)(a.T - 1) * n + env) * 14 + sub];

@@ -22,6 +22,11 @@ extern "C" __attribute__((visibility("hidden"))) int earl_unit_bf16_sawyer_polic
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_w8_bf16_sawyer_policy_rollout(const void* sawyer_policy_args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_mt_bf16_policy_rollout(const void* minitaur_policy_args, int duo, void* stream);
 extern "C" __attribute__((visibility("hidden"))) void earl_unit_kitchen_bf16_policy_rollout(const void* kitchen_policy_args, void* stream);
+// the branch launch (physics_branch.hip, physics_branch_w8.hip): earl_sawyer_branch_rollout hands them the SawyerBranchArgs it filled -- first to the replicate kernel
+// (src_state: the env's own earl_sawyer_state, whose [n] rows become the workspace's [K n]; it also clears the work queue), then to the rollout kernel of the form chosen
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_replicate(const void* sawyer_branch_args, const void* src_state, int nv, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_sawyer_rollout(const void* sawyer_branch_args, int nv, int sliced, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_w8_sawyer_rollout(const void* sawyer_branch_args, void* stream);
 extern "C" int earl_sawyer_rollout_door_w8(const earl_link_model* model, const earl_collision_model* col, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                            const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream);
 

@@ -171,6 +171,10 @@ class PhysicsEnv:
     raise NotImplementedError(f'evaluate_policy: episode summaries on {self.ENV} are evaluate_population\'s (it takes one policy as well as a PolicyPopulation); '
                               'evaluate_policy runs on the tabletop, the Sawyer door and the Sawyer peg')
 
+  def rollout_branches(self, actions, K=None, clock=None):
+    raise NotImplementedError(f'rollout_branches: scoring K action plans from the current state is not built for {self.ENV or type(self).__name__} '
+                              '(it runs on the tabletops, the Sawyer door and the Sawyer peg)')
+
   @property
   def pair_counts(self):
     """(forward_success, backward_success) [N] int32 of the last pair launch: the phases that ended by success; None before the first"""

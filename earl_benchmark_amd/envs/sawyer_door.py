@@ -334,6 +334,53 @@ class SawyerDoor(PhysicsEnv):
     self._launch_rollout(self._actions(a, (T,)), T, out)
     return out
 
+  def _branch_ws(self, K):
+    """the workspace of a branch launch of K branches (include/earl_physics.h: earl_sawyer_branch_ws): one device block, allocated at the first use and cached per K"""
+    cache = self.__dict__.setdefault('_branch_ws_cache', {})
+    if K not in cache:
+      need = C.c_int64(0)
+      _abi.check(self._lib.earl_sawyer_branch_ws_bytes(self.nv, K, self.num_envs, C.byref(need)), 'earl_sawyer_branch_ws_bytes')
+      block = torch.empty(max(need.value, 8) // 8 + 1, dtype=torch.float64, device=self.device)
+      cache[K] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
+    return cache[K][1]
+
+  def rollout_branches(self, actions, K=None, clock=None):
+    """K candidate action sequences of H steps scored per env FROM THE CURRENT STATE in one launch of the rollout kernel over K N virtual envs (include/earl_physics.h:
+    earl_sawyer_branch_rollout): actions [K, H, N, 4] float32 -- or [H, N, 4] with K= for K replays of one block --
+    -> {'ret' [K, N] float64, 'success' [K, N] bool (the success of step H - 1), 'first_success' [K, N] int32 (-1: none), 'last_obs' [K, N, 14] float64,
+        'fail' [K, N] int32 (steps the failure guard rolled back)}.
+    Row k is what rollout(actions[k]) would return next, reduced (ret = the float64 sum of its float32 rewards), lifelong goal draws included: every branch of an env
+    sees the env's own draws.  The env is left exactly as found -- state, goals, counters, last_obs, fail_count: nothing happened to it.  What a shooting planner
+    (random shooting, CEM, MPPI) asks for.  clock: None, or the device address of the two uint64 words of earl_sawyer_rollout_clocked (a captured launch)."""
+    a = torch.as_tensor(actions, device=self.device)
+    n = self.num_envs
+    if K is None:
+      if a.dim() != 4 or a.shape[2] != n or a.shape[3] != 4:
+        raise ValueError(f'rollout_branches: actions must be [K, H, N, 4] = [K, H, {n}, 4], got {list(a.shape)} (one block for K branches: [H, {n}, 4] with K=)')
+      K, H, stride = int(a.shape[0]), int(a.shape[1]), int(a.shape[1]) * n * 4
+      act = self._actions(a, (K, H))
+    else:
+      if a.dim() != 3 or a.shape[1] != n or a.shape[2] != 4:
+        raise ValueError(f'rollout_branches: with K= actions must be [H, N, 4] = [H, {n}, 4], got {list(a.shape)}')
+      K, H, stride = int(K), int(a.shape[0]), 0
+      act = self._actions(a, (H,))
+    if K < 1 or H < 1:                                                 # (the entry point writes nothing then: no branch, or no step to reduce)
+      raise ValueError(f'rollout_branches: K = {K}, H = {H}: at least one branch of at least one step')
+    if K * n > INT32_MAX:
+      raise ValueError(f'rollout_branches: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
+    kw = dict(device=self.device)
+    res = {'ret': torch.empty(K, n, dtype=torch.float64, **kw), 'success': torch.empty(K, n, dtype=torch.bool, **kw),
+           'first_success': torch.empty(K, n, dtype=torch.int32, **kw), 'last_obs': torch.empty(K, n, self.OBS_DIM, dtype=torch.float64, **kw),
+           'fail': torch.empty(K, n, dtype=torch.int32, **kw)}
+    summary = _abi.EpisodeSummary(ret=res['ret'].data_ptr(), success_last=res['success'].data_ptr(), first_success=res['first_success'].data_ptr())
+    self._cfg.step_counter = self.total_step_count
+    with torch.cuda.device(self.device):
+      ws = self._branch_ws(K)
+      _abi.check(self._lib.earl_sawyer_branch_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, K, H, act.data_ptr(), stride,
+                                                      clock, C.byref(ws), C.byref(summary), res['last_obs'].data_ptr(), res['fail'].data_ptr(), self._stream()),
+                 'earl_sawyer_branch_rollout')
+    return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
+
   def _launch_policy(self, policy, head, obs0, T, out, summary=None, pair=None):
     """hook of physics_policy_rollout: earl_sawyer_population_rollout, or -- pair: what physics_policy_rollout.pair_structs returns -- earl_sawyer_agents_rollout"""
     self._cfg.step_counter = self.total_step_count

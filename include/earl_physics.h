@@ -390,6 +390,48 @@ int earl_sawyer_agents_rollout(const earl_link_model* model, const earl_collisio
                                const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop, const earl_backward_goals* goals,
                                const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_sawyer_out* out,
                                const earl_episode_summary* summary, earl_stream_t stream);
+
+/* ---- branches: K candidate action sequences per env scored FROM THE CURRENT STATE, the state left as it is ----
+ * earl_tabletop_branch_rollout's contract (earl_tabletop.h) restated for the door (nv = 10) and the peg (nv = 15): what a shooting planner (random shooting, CEM,
+ * MPPI) asks of a contact-rich env -- K plans of H steps per env, one return, one success flag, one last observation and one count of rolled-back steps each,
+ * nothing kept.  ONE launch of the rollout kernel over the K n virtual envs v = k n + i (branch k of env i), in front of it one small kernel that copies the env's
+ * [n] state rows into the workspace's [K n]; no [H] row is written anywhere.
+ *   equivalence  branch (k, i) equals earl_sawyer_rollout_clocked(model, col, nv, cfg, <a private copy of st>, act + k * act_branch_stride, H, clock, out) restricted to
+ *                env i, bit for bit:  summary->ret[k n + i] = the float64 sum over t ascending of the float32 out->reward[t][i];  success_last = out->success[H - 1][i];
+ *                first_success = the first t with success, or -1;  last_obs[k][i] = out->obs[H - 1][i] exactly as emitted -- the goal block a lifelong switch patched,
+ *                the repeated row of a rolled-back step and, when step 0 itself diverges, the env's row of st->last_obs (NaN if that is NULL) included;
+ *                fail[k n + i] = the number of steps with status == EARL_STEP_DIVERGED.  A rolled-back step restores the BRANCH's own last stable state; before its
+ *                first stable step that is the state in `st`.
+ *   draws        step t of EVERY branch uses ev = cfg->step_counter + clock[1] + t, and the Philox id is the env's global id cfg->env_offset + i, never the virtual
+ *                index: all branches see the same lifelong goal draws (common random numbers), and each predicts what the next real rollout with those actions will do.
+ *   act          float32, device.  act_branch_stride (in floats) == H * n * 4: a contiguous [K, H, n, 4] array; 0: every branch replays one [H, n, 4] block.
+ *   state        `st` is read and never written: qpos, qvel, mocap_pos, goal, both step counters, obj_init, last_obs, fail_count -- and st->sched, which is not even read.
+ *   ws           what the launch mutates: per virtual env the last stable qpos / qvel / mocap_pos, the goal row, the goal-switch counter and the one carried observation
+ *                row (last_obs itself when given), and the work queue of the time-sliced peg form.  ONE device block: base 8-byte aligned, bytes >= what
+ *                earl_sawyer_branch_ws_bytes(nv, K, n, &bytes) reports (0 for K n == 0; monotone in K and in n); the call carves it and refuses a block that is too
+ *                small.  The caller prepares NOTHING in it -- the call fills every row it reads and clears the queue itself -- and nothing in it outlives the call: the
+ *                same block serves any later call that fits.  No allocation, no host synchronisation: after one eager call with the same `col` (the friction-cone check
+ *                reads the table's cone word once per address) the call can be captured into a HIP graph.
+ *   outputs      summary (rows [K n]; the struct or any of its three pointers NULL), last_obs ([K, n, 14] or NULL) and fail ([K n] or NULL) in any combination, but not
+ *                all five pointers NULL.  earl_sawyer_out.info has no counterpart here.
+ *   forms        chosen by the number of VIRTUAL envs K n with earl_sawyer_rollout's rules: the door's one-wave build, its eight-wave build above 4096, the peg, and the
+ *                peg's time-sliced schedule when the grid exceeds the CU count and H > 1 (the queue is the workspace's).  Those forms are held bit-identical to each
+ *                other, which is what makes the equivalence above independent of K.  earl_debug_set_door_variant(3) is read as 0, as the closed loop reads it; under
+ *                earl_debug_set_physics_lanes(64) the call returns EARL_ERR_ARG (the 64-lane measurement builds have no branch form).
+ * EARL_ERR_ARG before any HIP call for: everything earl_sawyer_rollout_clocked refuses in model / cfg / st (goal switching without its counter, a goal count without its
+ * table, peg dense reward without obj_init), nv not 10 or 15; act or ws NULL; K < 0; H < 0; a negative stride, or one that is neither 0 nor >= H * n * 4; all five outputs
+ * NULL; K * n beyond 2^31 - 1; with K n > 0: ws->base NULL or misaligned, ws->bytes too small.  n == 0, K == 0 or H == 0 returns EARL_OK, launches nothing and writes
+ * nothing. */
+typedef struct earl_sawyer_branch_ws {
+  void*   base;    /* device, 8-byte aligned; NULL-able if K n == 0 */
+  int64_t bytes;   /* size of the block at `base` */
+} earl_sawyer_branch_ws;
+/* *bytes = the size of the workspace of a branch launch of K branches of n envs; EARL_ERR_ARG for bytes == NULL, nv not 10 or 15, K < 0, n < 0, K * n beyond 2^31 - 1 */
+int earl_sawyer_branch_ws_bytes(int32_t nv, int32_t K, int32_t n, int64_t* bytes);
+int earl_sawyer_branch_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
+                               const earl_episode_summary* summary, double* last_obs, int32_t* fail, earl_stream_t stream);
+
 /* The policy contract on the host (libearl_host.so; host pointers): actions [n, A] of n observation rows obs [n, dims[0]], dims[0] in 1..256, hidden widths in 1..256,
  * the last layer A wide (head = NULL) or 2 A wide (rows 0..A-1 the mean, A..2A-1 the raw log_std), A >= 1.  eps [n, A] = the standard-normal draws to use with a
  * head in EARL_HEAD_SAMPLE mode; NULL (or EARL_HEAD_MEAN, or no head) evaluates the mean / the deterministic policy.  policy->out_act is applied last, as on the

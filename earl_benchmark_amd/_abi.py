@@ -144,6 +144,12 @@ class SawyerBranchWs(C.Structure):   # struct earl_sawyer_branch_ws (include/ear
   _fields_ = [('base', C.c_void_p), ('bytes', C.c_int64)]
 
 
+class SawyerPlanParams(C.Structure):   # struct earl_sawyer_plan_params (include/earl_physics.h): earl_plan_params with four action dimensions
+  _fields_ = [('K', C.c_int32), ('H', C.c_int32), ('iterations', C.c_int32), ('iteration0', C.c_int32), ('sigma', C.c_float * 4), ('noise_counter', C.c_uint32),
+              ('inv_temperature', C.c_double)]
+
+
+SAWYER_PLAN_MAX_K = 8192   # EARL_SAWYER_PLAN_MAX_K
 SAWYER_INFO = 8       # EARL_SAWYER_INFO; slots EARL_INFO_* (include/earl_physics.h)
 SAWYER_INFO_KEYS = ('success', 'near_object', 'grasp_success', 'grasp_reward', 'in_place_reward', 'obj_to_target', 'unscaled_reward')
 STEP_DIVERGED = 1     # EARL_STEP_DIVERGED (include/earl_physics.h)
@@ -278,6 +284,11 @@ SIGNATURES = {
     'earl_sawyer_branch_ws_bytes': [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int64)],
     'earl_sawyer_branch_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                    _P(SawyerBranchWs), _P(EpisodeSummary), C.c_void_p, C.c_void_p, C.c_void_p],
+    # the MPPI planner around that launch: params, mean, plan, ret, ret0, best_ret, best_k, fail, clock, the workspace (nv, K, H, n -> its size); its candidates written out
+    'earl_sawyer_plan_ws_bytes': [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int64)],
+    'earl_sawyer_plan_mppi': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(SawyerPlanParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(SawyerBranchWs), C.c_void_p],
+    'earl_sawyer_plan_candidates': [_P(SawyerCfg), _P(SawyerPlanParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     # the closed loop inside the minitaur rollout kernels: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
     'earl_minitaur_policy_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, _P(MinitaurOut), C.c_void_p],
@@ -348,6 +359,9 @@ HOST_SIGNATURES = {name + '_cpu': argtypes[:-1] for name, argtypes in SIGNATURES
 # actions, no twin of a device entry point -- and the contract's scalar functions; name -> (argtypes, restype)
 HOST_EXTRA_SIGNATURES = {
     'earl_mlp_policy_forward_cpu': ([_P(MlpPolicy), _P(GaussianHead), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
+    # the host twins of the Sawyer planner's two kernels (no host stepper: the update takes the returns): cfg, params, j, mean, act_out | act, ret, plan, ret0_row, best_ret, best_k
+    'earl_sawyer_plan_candidates_cpu': ([_P(SawyerCfg), _P(SawyerPlanParams), C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
+    'earl_sawyer_plan_update_cpu': ([_P(SawyerCfg), _P(SawyerPlanParams), C.c_int32] + [C.c_void_p] * 7, C.c_int32),
     'earl_tanh_f32': ([C.c_float], C.c_float),
     'earl_exp_f32': ([C.c_float], C.c_float),
     'earl_normal_quantile_f32': ([C.c_uint32], C.c_float),

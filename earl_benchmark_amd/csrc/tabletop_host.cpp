@@ -3,7 +3,7 @@
 // the policies' tabletop_policy.h), compiled for the host by g++ (-DEARL_HOST_BUILD: earl_rt.h -> host_shim.h) with -ffp-contract=off, one OpenMP iteration per env
 // where a kernel has one lane per env.  This file owns only the walks: for_each_env, rollout_tiles, for_each_branch_tile (the branch-shaped launches' (branch, tile)
 // range), update_env (one env's MPPI reweighting) and cem_update_env (one env's CEM refit), each for its planner and its receding-horizon loop; no arithmetic of an env or
-// a planner is stated here.
+// a planner is stated here.  Also the two host twins of the Sawyer door / peg planner (sawyer_plan.h: the candidates and the reweighting; the Sawyer stepper has no host build).
 // Host pointers, no stream, no HIP runtime.  This library is loaded only when a caller ASKS for device='cpu'; nothing falls back to it,
 // and nothing here touches oracle/ (the oracle is the checker of both builds).
 #include <algorithm>
@@ -16,6 +16,7 @@
 #include "tabletop_cem.h"
 #include "tabletop_prior.h"
 #include "tabletop_policy.h"
+#include "sawyer_plan.h"   // the door / peg planner's candidates and reweighting (earl_sawyer_plan_candidates_cpu, earl_sawyer_plan_update_cpu)
 #include "../../include/earl_physics.h"
 
 #ifdef _OPENMP
@@ -732,6 +733,64 @@ int32_t earl_mlp_policy_forward_cpu(const earl_mlp_policy* p, const earl_gaussia
 float earl_tanh_f32(float x) { return tanh_f32(x); }
 float earl_exp_f32(float x) { return exp_f32(x); }
 float earl_normal_quantile_f32(uint32_t k24) { return normal_quantile_f32(k24 & 0xFFFFFFu); }
+
+// include/earl_physics.h: the Sawyer planner's own arithmetic as plain loops over sawyer_plan.h's per-element functions -- the candidates kernel's, one row of n envs per
+// (k, t), and the update kernel's, one env at a time with k ascending (integer sums: the kernel's split over lanes gives the same bits).  No host stepper: the returns
+// of the update are the caller's.
+int32_t earl_sawyer_plan_candidates_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_params* params, int32_t j, const float* mean, float* act_out) {
+  if (int rc = check_sawyer_plan(SawyerPlanCall::Candidates, cfg, params, j, mean, act_out)) return rc;
+  if (cfg->n == 0) return EARL_OK;
+  SawyerPlanArgs p = sawyer_plan_args(cfg, params, mean);
+  p.word0 = kPlanDraw | (uint32_t)j;
+  const long long rows = (long long)p.K * p.H;
+#pragma omp parallel for schedule(static) if (rows * p.n >= 4096)
+  for (long long kt = 0; kt < rows; ++kt) {
+    const int k = (int)(kt / p.H), t = (int)(kt - (long long)k * p.H);
+    for (int i = 0; i < p.n; ++i) {
+      float m[4], c[4];
+      splan_mean(p, i, t, m);
+      splan_candidate(p, i, (uint32_t)k, (uint32_t)t, m, c);
+      float* dst = act_out + splan_act_index(p, i, k, t);
+      for (int d = 0; d < 4; ++d) dst[d] = c[d];
+    }
+  }
+  return EARL_OK;
+}
+int32_t earl_sawyer_plan_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_params* params, int32_t j, const float* mean, const float* act, const double* ret,
+                                    float* plan, double* ret0_row, double* best_ret, int32_t* best_k) {
+  if (int rc = check_sawyer_plan(SawyerPlanCall::Update, cfg, params, j, mean, plan)) return rc;
+  if (!act || !ret) return fail(EARL_ERR_ARG, "act/ret is NULL");
+  SawyerPlanArgs p = sawyer_plan_args(cfg, params, mean);
+  p.plan = plan;
+  p.ret = ret;
+  const int n = p.n, K = p.K;
+  for_each_env(n, [&](int i) {
+    double beta = -INFINITY;
+    int bk = 0;
+    for (int k = 0; k < K; ++k) plan_best(ret[(size_t)k * n + i], k, beta, bk);
+    std::vector<int32_t> Wk(K);
+    for (int k = 0; k < K; ++k) Wk[k] = plan_weight(ret[(size_t)k * n + i], beta, p.inv_temperature);
+    for (int t = 0; t < p.H; ++t) {
+      float m[4];
+      splan_mean(p, i, t, m);
+      int64_t A[4] = {0, 0, 0, 0}, S = 0;
+      for (int k = 0; k < K; ++k) {
+        const int32_t W = Wk[k];
+        S += W;
+        if (W != 0 && k > 0) {
+          const float* src = act + splan_act_index(p, i, k, t);
+          const float c[4] = {src[0], src[1], src[2], src[3]};
+          splan_accumulate(c, m, W, A);
+        }
+      }
+      for (int d = 0; d < 4; ++d) plan[((size_t)t * n + i) * 4 + d] = plan_new_mean(m[d], A[d], S);
+    }
+    if (ret0_row) ret0_row[i] = ret[i];
+    if (best_ret) best_ret[i] = beta;
+    if (best_k) best_k[i] = bk;
+  });
+  return EARL_OK;
+}
 
 int earl_host_set_threads(int n) {
 #ifdef _OPENMP

@@ -175,6 +175,18 @@ class PhysicsEnv:
     raise NotImplementedError(f'rollout_branches: scoring K action plans from the current state is not built for {self.ENV or type(self).__name__} '
                               '(it runs on the tabletops, the Sawyer door and the Sawyer peg)')
 
+  def _no_planner(self, who):
+    return NotImplementedError(f'{who}: the MPPI planner is not built for {self.ENV or type(self).__name__} (it runs on the tabletops, the Sawyer door and the Sawyer peg)')
+
+  def plan_mppi(self, *args, **kwargs):
+    raise self._no_planner('plan_mppi')
+
+  def plan_candidates(self, *args, **kwargs):
+    raise self._no_planner('plan_candidates')
+
+  def mpc_rollout(self, *args, **kwargs):
+    raise self._no_planner('mpc_rollout')
+
   @property
   def pair_counts(self):
     """(forward_success, backward_success) [N] int32 of the last pair launch: the phases that ended by success; None before the first"""

@@ -381,6 +381,131 @@ class SawyerDoor(PhysicsEnv):
                  'earl_sawyer_branch_rollout')
     return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
 
+  # ------------------------------------------------------------------ MPPI on top of the branch launch (include/earl_physics.h: earl_sawyer_plan_mppi)
+  def _plan_ws(self, K, H):
+    """the workspace of a planner call (the branch launch's block and the [K, H, N, 4] candidates behind it): one device block, cached per (K, H) like _branch_ws"""
+    cache = self.__dict__.setdefault('_plan_ws_cache', {})
+    if (K, H) not in cache:
+      need = C.c_int64(0)
+      _abi.check(self._lib.earl_sawyer_plan_ws_bytes(self.nv, K, H, self.num_envs, C.byref(need)), 'earl_sawyer_plan_ws_bytes')
+      block = torch.empty(max(need.value, 8) // 8 + 1, dtype=torch.float64, device=self.device)
+      cache[(K, H)] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
+    return cache[(K, H)][1]
+
+  def _plan_mean(self, who, mean, horizon):
+    n = self.num_envs
+    if mean is None:
+      if horizon is None:
+        raise ValueError(f'{who}: give mean [H, N, 4] or horizon')
+      return torch.zeros(int(horizon), n, 4, dtype=torch.float32, device=self.device)
+    m = torch.as_tensor(mean, device=self.device)
+    if m.dim() != 3 or m.shape[1] != n or m.shape[2] != 4 or (horizon is not None and m.shape[0] != horizon):
+      raise ValueError(f'{who}: mean must be [H, N, 4] = [{"H" if horizon is None else horizon}, {n}, 4], got {list(m.shape)}')
+    return self._actions(m, (int(m.shape[0]),))
+
+  def _plan_params(self, who, K, H, iterations, iteration0, sigma, temperature, noise_counter):
+    s = torch.as_tensor(sigma, dtype=torch.float32).reshape(-1).tolist()
+    if len(s) not in (1, 4):
+      raise ValueError(f'{who}: sigma is a number or four, one per action dimension (x, y, z, gripper)')
+    if not float(temperature) > 0.0:
+      raise ValueError(f'{who}: temperature = {temperature}: > 0')
+    if not 1 <= int(K) <= _abi.SAWYER_PLAN_MAX_K:
+      raise ValueError(f'{who}: K = {K}: 1 .. {_abi.SAWYER_PLAN_MAX_K} candidates per env (branch 0, the plan itself, included)')
+    if int(H) < 1 or int(iterations) < 1:
+      raise ValueError(f'{who}: H = {H}, iterations = {iterations}: at least one of each')
+    nc = self.total_step_count if noise_counter is None else int(noise_counter)   # (None: the low word of the env's step count -- fresh noise per control step)
+    return _abi.SawyerPlanParams(K=int(K), H=int(H), iterations=int(iterations), iteration0=int(iteration0), sigma=(C.c_float * 4)(*(s * 4 if len(s) == 1 else s)),
+                                 noise_counter=nc & 0xFFFFFFFF, inv_temperature=1.0 / float(temperature))
+
+  def plan_mppi(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, clock=None, out=None):
+    """`iterations` MPPI iterations on the device from the CURRENT state (include/earl_physics.h: earl_sawyer_plan_mppi): K candidates per env -- the mean plan itself and
+    K - 1 copies with clipped Gaussian noise of scale `sigma` (a number or four: x, y, z, gripper) -- scored by the branch launch exactly as rollout_branches scores them,
+    the mean moved to their average under the weights exp((ret - max ret) / temperature), in integer sums.  Per iteration three launches (candidates, the branch
+    launch, update); no allocation and no host synchronisation in the call.  mean [H, N, 4] (None: zeros of [horizon, N, 4]) ->
+    {'plan' [H, N, 4] float32, 'ret' [K, N] float64 (the last iteration's returns), 'ret0' [iterations, N] float64 (the return of the plan entering each iteration),
+     'best_ret' [N] float64, 'best_k' [N] int32 (plan_candidates(...)[best_k] is that candidate), 'fail' [K, N] int32 (steps of the last iteration the failure guard
+     rolled back: they count with reward 0)}.
+    `noise_counter=None` takes the low 32 bits of env.total_step_count, so successive control steps draw fresh noise (a captured call replays the noise it was captured
+    with); `iteration0` numbers the first iteration (iterations in one call == as many calls of one, numbered on).  `out`: an optional dict of preallocated tensors under
+    the same keys; a key that is missing or None is not computed, except 'ret' (the branch launch writes it), which is then allocated; out['plan'] may be the `mean`
+    tensor.  clock: as rollout_branches.  The env is left exactly as found -- state, goals, counters, last_obs, fail_count."""
+    m = self._plan_mean('plan_mppi', mean, horizon)
+    n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
+    pp = self._plan_params('plan_mppi', K, H, I, iteration0, sigma, temperature, noise_counter)
+    if K * n > INT32_MAX:
+      raise ValueError(f'plan_mppi: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
+    kw = dict(device=self.device)
+    want = {'plan': ((H, n, 4), torch.float32), 'ret': ((K, n), torch.float64), 'ret0': ((I, n), torch.float64), 'best_ret': ((n,), torch.float64),
+            'best_k': ((n,), torch.int32), 'fail': ((K, n), torch.int32)}
+    if out is None:
+      res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
+    else:
+      if set(out) - set(want):
+        raise ValueError(f'plan_mppi: out holds {sorted(set(out) - set(want))}; the keys are {list(want)}')
+      res = {k: t for k, t in out.items() if t is not None}
+      for k, t in res.items():
+        shape, dt = want[k]
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+          raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
+      if 'plan' not in res:
+        raise ValueError("plan_mppi: out['plan'] is what the call computes")
+      if 'ret' not in res:
+        res['ret'] = torch.empty(K, n, dtype=torch.float64, **kw)
+    self._cfg.step_counter = self.total_step_count
+    with torch.cuda.device(self.device):
+      ws = self._plan_ws(K, H)
+      _abi.check(self._lib.earl_sawyer_plan_mppi(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pp), m.data_ptr(),
+                                                 res['plan'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')), _ptr(res.get('best_k')),
+                                                 _ptr(res.get('fail')), clock, C.byref(ws), self._stream()), 'earl_sawyer_plan_mppi')
+    return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
+
+  def plan_candidates(self, mean, K, sigma=0.3, iteration=0, noise_counter=None):
+    """the K candidates of plan_mppi's iteration `iteration` around `mean` [H, N, 4], written out: [K, H, N, 4] float32, row 0 the clipped mean (all four words: the
+    gripper too) -- what rollout_branches takes (earl_sawyer_plan_candidates; plan_mppi runs the same kernel).  With plan_mppi's `noise_counter` (None: the env's step
+    count, unchanged by plan_mppi) they are the candidates that call scored."""
+    m = self._plan_mean('plan_candidates', mean, None)
+    H = int(m.shape[0])
+    pp = self._plan_params('plan_candidates', K, H, 1, 0, sigma, 1.0, noise_counter)
+    act = torch.empty(int(K), H, self.num_envs, 4, dtype=torch.float32, device=self.device)
+    with torch.cuda.device(self.device):
+      _abi.check(self._lib.earl_sawyer_plan_candidates(self._cfg_ref, C.byref(pp), int(iteration), m.data_ptr(), act.data_ptr(), self._stream()),
+                 'earl_sawyer_plan_candidates')
+    return act
+
+  def mpc_rollout(self, T, plan=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, noise_counter=None, out=None):
+    """T steps of receding-horizon MPPI control, DEFINED as this composition of public methods (one call each per control step, no host synchronisation in the loop):
+        P = plan.clone()  (None: zeros of [horizon, N, 4]);  nc0 = noise_counter  (None: the low 32 bits of env.total_step_count at entry)
+        for s in range(T):
+          plan_mppi(P, K=, iterations=, sigma=, temperature=, noise_counter=(nc0 + s) mod 2^32, out={'plan': P, 'ret0': ret0[s], 'best_ret': best_ret[s]})
+          row s of the result = rollout(P[:1], out=<views of row s>);  act[s] = P[0]
+          P[t] <- P[t + 1] for t < H - 1  (the last row stays)
+    -> rollout()'s dict with a leading [T] ('obs' [T, N, 14], 'reward', 'done', 'success', 'status' [T, N], 'info' with info='full') plus 'act' [T, N, 4] float32,
+       'plan' [H, N, 4] (the shifted plan after the last step: what the next call continues from), 'ret0' [T, iterations, N] and 'best_ret' [T, N] float64.
+    The env advances by T steps (total_step_count, counters, last_obs: as T calls of rollout).  `done` rows are reported and nothing is reset: the Sawyer kernels have no
+    auto-reset, so a caller that wants episodes resets between calls.  `out`: an optional dict of preallocated [T, ...] tensors under rollout()'s keys.  A fused
+    one-launch loop is not built for these envs (the score and the update would need a grid-wide join inside the stepper kernel)."""
+    T = int(T)
+    if T < 1:
+      raise ValueError(f'mpc_rollout: T = {T}: at least one control step')
+    P = self._plan_mean('mpc_rollout', plan, horizon).clone()
+    n, H, K, I = self.num_envs, int(P.shape[0]), int(K), int(iterations)
+    self._plan_params('mpc_rollout', K, H, I, 0, sigma, temperature, noise_counter)      # (the argument errors, before anything moves)
+    nc0 = self.total_step_count if noise_counter is None else int(noise_counter)
+    kw = dict(device=self.device)
+    res = self._new_out((T,)) if out is None else dict(out)
+    res.update(act=torch.empty(T, n, 4, dtype=torch.float32, **kw), ret0=torch.empty(T, I, n, dtype=torch.float64, **kw), best_ret=torch.empty(T, n, dtype=torch.float64, **kw))
+    rows = [k for k in res if k not in ('act', 'ret0', 'best_ret')]
+    ret = torch.empty(K, n, dtype=torch.float64, **kw)
+    for s in range(T):
+      self.plan_mppi(P, K=K, iterations=I, sigma=sigma, temperature=temperature, noise_counter=(nc0 + s) & 0xFFFFFFFF,
+                     out={'plan': P, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]})
+      self.rollout(P[:1], out={k: res[k][s:s + 1] for k in rows})
+      res['act'][s].copy_(P[0])
+      if H > 1:
+        P[:-1] = P[1:].clone()
+    res['plan'] = P
+    return res
+
   def _launch_policy(self, policy, head, obs0, T, out, summary=None, pair=None):
     """hook of physics_policy_rollout: earl_sawyer_population_rollout, or -- pair: what physics_policy_rollout.pair_structs returns -- earl_sawyer_agents_rollout"""
     self._cfg.step_counter = self.total_step_count

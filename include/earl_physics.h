@@ -432,6 +432,74 @@ int earl_sawyer_branch_rollout(const earl_link_model* model, const earl_collisio
                                int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
                                const earl_episode_summary* summary, double* last_obs, int32_t* fail, earl_stream_t stream);
 
+/* ---- MPPI planning on the door and the peg: I iterations of sample -> score -> reweight on the device, the env left as it is ----
+ * The planner the branch launch was made for: earl_tabletop_plan_mppi's contract (earl_tabletop.h, "MPPI planning", items 1 - 7) with FOUR action dimensions.  Unlike
+ * the tabletop's, the candidates go THROUGH MEMORY: an env step here costs tens of thousands of cycles and the whole [K, H, n, 4] array of a realistic call is about a
+ * megabyte, so the scoring launch is earl_sawyer_branch_rollout itself, untouched, between two small kernels.  Per iteration on the caller's stream: the candidates
+ * kernel, earl_sawyer_branch_rollout (its replicate kernel and its rollout kernel), the update kernel; no allocation, no host synchronisation: after one eager call
+ * with the same `col` (the branch launch's rule) the call can be captured into a HIP graph.  noise_counter is a host word: a captured call replays the same noise.
+ * For iteration j = iteration0 + i (i = 0 .. iterations - 1), env `env` with global id g = cfg->env_offset + env, and the plan entering the iteration `mean` (the
+ * argument for i = 0, the previous iteration's result afterwards):
+ *   1 clipped mean  m[t][d] = clip(mean[t][d]) in float32 for d = 0 .. 3, clip(x) = (y = x > -1 ? x : -1; y < 1 ? y : 1) = min(max(x, -1), 1).  ALL FOUR dimensions are
+ *                   clipped, the gripper word included; the rollout kernel itself clips only x, y, z (set_xyz_action) and takes the gripper word as given.
+ *   2 candidates    branch 0 is the plan itself, a_0 = m.  For k >= 1: a_k[t][d] = clip(fmaf(sigma[d], eps_d, m[t][d])), eps_d = normal_quantile_f32(word_d >> 8)
+ *                   (csrc/policy_math.h; earl_normal_quantile_f32), words x, y, z, w of ONE Philox4x32-10 block serving d = 0, 1, 2, 3: key = cfg->seed, counter
+ *                   words = {0x504C4E00 | j, g, (k << 16) | t, noise_counter}.  Word 0 collides with no other draw of the Sawyer envs (they use 0 .. 31, 0xFFF0 .. 0xFFF2
+ *                   and 0xFFFD .. 0xFFFF, the Gaussian head 0x504F4C00).  The draws depend on (seed, g, j, k, t, noise_counter) only: not on n, not on the shard split.
+ *   3 scores        ret[k][env] = summary->ret of earl_sawyer_branch_rollout fed with those candidates (act_branch_stride = H * n * 4) and the caller's `clock`: goal
+ *                   switches inside the look-ahead and rolled-back steps (reward 0) count exactly as that call defines them.  The metaworld rewards are
+ *                   non-negative, so a rolled-back step never scores above an honest one.
+ *   4 weights       beta = max_k ret[k];  x_k = (float)((ret[k] - beta) * inv_temperature) (two float64 roundings);  w_k = exp_f32(x_k) (csrc/policy_math.h;
+ *                   earl_exp_f32);  W_k = (double)w_k * 2^24 rounded to nearest-even as int64 (0 .. 2^24);  S = sum_k W_k (>= 2^24: the best branch has W = 2^24).
+ *   5 update        delta = a_k[t][d] - m[t][d] (one float32 subtraction);  D_k = (double)delta * 2^20 rounded to nearest-even as int64;  A = sum_k W_k * D_k in
+ *                   int64 (|A| < 2^59 for K <= 8192);  mean'[t][d] = clip(m[t][d] + (float)((double)A / ((double)S * 2^20))), (double)A rounded to nearest.
+ *                   Integer sums are associative: the result does not depend on how the K branches are spread over lanes, waves and workgroups.
+ *   6 outputs       plan [H, n, 4] float32, REQUIRED: the mean after the last iteration; it may be the pointer `mean` itself (the in-place call), any other overlap of
+ *                   the two arrays is refused.  ret [K, n] float64, REQUIRED: the last iteration's returns on exit.  ret0 NULL or [iterations, n] float64: the
+ *                   return of the plan entering each iteration (branch 0).  best_ret NULL or [n] float64: beta of the last iteration.  best_k NULL or [n] int32:
+ *                   the smallest k attaining it (earl_sawyer_plan_candidates recovers that candidate).  fail NULL or [K, n] int32: the last iteration's count of
+ *                   rolled-back steps per branch (earl_sawyer_branch_rollout's `fail`).
+ *   7 non-finite    clip() maps a NaN of `mean` to -1 and +-Inf to +-1, so every candidate is finite whatever `mean` holds.  A NaN return never wins: beta is the
+ *                   largest return that is not NaN, -Inf if there is none; x_k that is NaN (a NaN return, or Inf - Inf) gives W_k = 0; if S == 0 (no branch has a
+ *                   weight) the update is skipped, mean' = m.  best_k is the smallest k with ret[k] == beta when beta > -Inf, and 0 otherwise.  Nothing of this faults.
+ *   chaining        `iterations` iterations in one call equal that many calls with iterations = 1 and iteration0 = j, each fed the previous plan, bit for bit.
+ *   state           `st` is read and never written, as in the branch launch: the env is as earl_sawyer_branch_rollout leaves it.
+ *   ws              ONE block as earl_sawyer_branch_ws describes it, of at least earl_sawyer_plan_ws_bytes(nv, K, H, n, &bytes) bytes: the branch launch's workspace
+ *                   and behind it the [K, H, n, 4] candidates of the current iteration (the call aligns them to 16 bytes itself).  The size is monotone in K, H
+ *                   and n and 0 for K n == 0.  The caller prepares nothing in it and nothing in it outlives the call.
+ * EARL_ERR_ARG before any HIP call for: everything earl_sawyer_branch_rollout refuses in model / col / cfg / st / nv; params, mean, plan, ret or ws NULL; K outside
+ * 1 .. EARL_SAWYER_PLAN_MAX_K (one env's integer weights are held in 32 KB of LDS); H outside 1 .. 65536; iterations < 1, iteration0 < 0, iteration0 + iterations > 256;
+ * a sigma that is negative or not finite; an inv_temperature that is not finite or <= 0; plan overlapping mean without being equal to it; K * n beyond 2^31 - 1; with
+ * n > 0 a ws block that is NULL, misaligned (8 bytes) or too small.  n == 0 returns EARL_OK, launches nothing and writes nothing.  Under
+ * earl_debug_set_physics_lanes(64) the call returns EARL_ERR_ARG, as the branch launch does. */
+typedef struct earl_sawyer_plan_params {
+  int32_t K;               /* candidates per env, branch 0 (the plan itself) included: 1 .. EARL_SAWYER_PLAN_MAX_K */
+  int32_t H;               /* steps of a plan: 1 .. 65536 */
+  int32_t iterations;      /* I >= 1 */
+  int32_t iteration0;      /* index of the first iteration (a word of the noise counter): >= 0, iteration0 + iterations <= 256 */
+  float sigma[4];          /* noise scale per action dimension (x, y, z, gripper), finite, >= 0 */
+  uint32_t noise_counter;  /* a word of the noise counter: a fresh value per control step gives fresh noise */
+  double inv_temperature;  /* 1 / lambda, finite, > 0 */
+} earl_sawyer_plan_params;
+#define EARL_SAWYER_PLAN_MAX_K 8192
+/* *bytes = the size of the workspace of a planner call; EARL_ERR_ARG for bytes == NULL, nv not 10 or 15, K < 0, H < 0, n < 0, K * n beyond 2^31 - 1 */
+int earl_sawyer_plan_ws_bytes(int32_t nv, int32_t K, int32_t H, int32_t n, int64_t* bytes);
+int earl_sawyer_plan_mppi(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                          const earl_sawyer_plan_params* params, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k,
+                          int32_t* fail, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream);
+/* Item 2 written out for ONE iteration j (0 .. 255): act_out [K, H, n, 4] float32, 16-byte aligned, what earl_sawyer_branch_rollout takes; earl_sawyer_plan_mppi runs
+ * the same kernel.  It reads cfg->n, env_offset and seed and params->K, H, sigma and noise_counter only (no env state, no model: one entry point serves both envs).
+ * EARL_ERR_ARG for cfg, params, mean or act_out NULL, act_out misaligned, n < 0, K or H out of range, j outside 0 .. 255, a bad sigma, K * n beyond 2^31 - 1; n == 0
+ * returns EARL_OK and writes nothing. */
+int earl_sawyer_plan_candidates(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_params* params, int32_t j, const float* mean, float* act_out, earl_stream_t stream);
+/* Host twins of the planner's own arithmetic (libearl_host.so; host pointers; csrc/sawyer_plan.h in plain loops -- there is no host stepper, so the scores are the
+ * caller's).  earl_sawyer_plan_candidates_cpu: the call above (no alignment asked of act_out).  earl_sawyer_plan_update_cpu: items 4 - 7 of iteration j on GIVEN
+ * candidates act [K, H, n, 4] and returns ret [K, n] -> plan [H, n, 4] (may be `mean`), and ret0_row / best_ret / best_k, each NULL or [n].  It reads cfg->n and
+ * params->K, H and inv_temperature; its refusals are the planner's for those, for j and for the pointers. */
+int32_t earl_sawyer_plan_candidates_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_params* params, int32_t j, const float* mean, float* act_out);
+int32_t earl_sawyer_plan_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_params* params, int32_t j, const float* mean, const float* act, const double* ret,
+                                    float* plan, double* ret0_row, double* best_ret, int32_t* best_k);
+
 /* The policy contract on the host (libearl_host.so; host pointers): actions [n, A] of n observation rows obs [n, dims[0]], dims[0] in 1..256, hidden widths in 1..256,
  * the last layer A wide (head = NULL) or 2 A wide (rows 0..A-1 the mean, A..2A-1 the raw log_std), A >= 1.  eps [n, A] = the standard-normal draws to use with a
  * head in EARL_HEAD_SAMPLE mode; NULL (or EARL_HEAD_MEAN, or no head) evaluates the mean / the deterministic policy.  policy->out_act is applied last, as on the

@@ -149,7 +149,13 @@ class SawyerPlanParams(C.Structure):   # struct earl_sawyer_plan_params (include
               ('inv_temperature', C.c_double)]
 
 
+class SawyerCemParams(C.Structure):    # struct earl_sawyer_cem_params (include/earl_physics.h): earl_cem_params with four action dimensions
+  _fields_ = [('K', C.c_int32), ('H', C.c_int32), ('iterations', C.c_int32), ('iteration0', C.c_int32), ('elites', C.c_int32), ('sigma', C.c_float * 4),
+              ('noise_counter', C.c_uint32), ('alpha', C.c_float), ('std_min', C.c_float), ('std_max', C.c_float)]
+
+
 SAWYER_PLAN_MAX_K = 8192   # EARL_SAWYER_PLAN_MAX_K
+SAWYER_CEM_MAX_E = 1024    # EARL_SAWYER_CEM_MAX_E
 SAWYER_INFO = 8       # EARL_SAWYER_INFO; slots EARL_INFO_* (include/earl_physics.h)
 SAWYER_INFO_KEYS = ('success', 'near_object', 'grasp_success', 'grasp_reward', 'in_place_reward', 'obj_to_target', 'unscaled_reward')
 STEP_DIVERGED = 1     # EARL_STEP_DIVERGED (include/earl_physics.h)
@@ -289,6 +295,11 @@ SIGNATURES = {
     'earl_sawyer_plan_mppi': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(SawyerPlanParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(SawyerBranchWs), C.c_void_p],
     'earl_sawyer_plan_candidates': [_P(SawyerCfg), _P(SawyerPlanParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    # the CEM planner around the same launch: params, mean, std0, plan, std, ret, ret0, best_ret, best_k, elite, fail, clock, the workspace (earl_sawyer_plan_ws_bytes');
+    # its candidates written out (j, mean, std, act_out); its update on given candidates and returns (j, mean, std_in, act, ret, plan, std, ret0_row, best_ret, best_k, elite)
+    'earl_sawyer_plan_cem': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(SawyerCemParams)] + [C.c_void_p] * 11 + [_P(SawyerBranchWs), C.c_void_p],
+    'earl_sawyer_cem_candidates': [_P(SawyerCfg), _P(SawyerCemParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    'earl_sawyer_cem_update': [_P(SawyerCfg), _P(SawyerCemParams), C.c_int32] + [C.c_void_p] * 11,
     # the closed loop inside the minitaur rollout kernels: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
     'earl_minitaur_policy_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, _P(MinitaurOut), C.c_void_p],
@@ -362,6 +373,9 @@ HOST_EXTRA_SIGNATURES = {
     # the host twins of the Sawyer planner's two kernels (no host stepper: the update takes the returns): cfg, params, j, mean, act_out | act, ret, plan, ret0_row, best_ret, best_k
     'earl_sawyer_plan_candidates_cpu': ([_P(SawyerCfg), _P(SawyerPlanParams), C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
     'earl_sawyer_plan_update_cpu': ([_P(SawyerCfg), _P(SawyerPlanParams), C.c_int32] + [C.c_void_p] * 7, C.c_int32),
+    # the host twins of its CEM planner's two kernels: cfg, params, j, mean, std, act_out | std_in, act, ret, plan, std, ret0_row, best_ret, best_k, elite
+    'earl_sawyer_cem_candidates_cpu': ([_P(SawyerCfg), _P(SawyerCemParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
+    'earl_sawyer_cem_update_cpu': ([_P(SawyerCfg), _P(SawyerCemParams), C.c_int32] + [C.c_void_p] * 10, C.c_int32),
     'earl_tanh_f32': ([C.c_float], C.c_float),
     'earl_exp_f32': ([C.c_float], C.c_float),
     'earl_normal_quantile_f32': ([C.c_uint32], C.c_float),

@@ -3,7 +3,8 @@
 // the policies' tabletop_policy.h), compiled for the host by g++ (-DEARL_HOST_BUILD: earl_rt.h -> host_shim.h) with -ffp-contract=off, one OpenMP iteration per env
 // where a kernel has one lane per env.  This file owns only the walks: for_each_env, rollout_tiles, for_each_branch_tile (the branch-shaped launches' (branch, tile)
 // range), update_env (one env's MPPI reweighting) and cem_update_env (one env's CEM refit), each for its planner and its receding-horizon loop; no arithmetic of an env or
-// a planner is stated here.  Also the two host twins of the Sawyer door / peg planner (sawyer_plan.h: the candidates and the reweighting; the Sawyer stepper has no host build).
+// a planner is stated here.  Also the two host twins of the Sawyer door / peg planner (sawyer_plan.h: the candidates and the reweighting; the Sawyer stepper has no host build)
+// and the two of its CEM planner (sawyer_cem.h: the candidates and the refit, the elites by a sort under cem_before).
 // Host pointers, no stream, no HIP runtime.  This library is loaded only when a caller ASKS for device='cpu'; nothing falls back to it,
 // and nothing here touches oracle/ (the oracle is the checker of both builds).
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include "tabletop_prior.h"
 #include "tabletop_policy.h"
 #include "sawyer_plan.h"   // the door / peg planner's candidates and reweighting (earl_sawyer_plan_candidates_cpu, earl_sawyer_plan_update_cpu)
+#include "sawyer_cem.h"    // its CEM planner's candidates and refit (earl_sawyer_cem_candidates_cpu, earl_sawyer_cem_update_cpu)
 #include "../../include/earl_physics.h"
 
 #ifdef _OPENMP
@@ -784,6 +786,75 @@ int32_t earl_sawyer_plan_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawye
         }
       }
       for (int d = 0; d < 4; ++d) plan[((size_t)t * n + i) * 4 + d] = plan_new_mean(m[d], A[d], S);
+    }
+    if (ret0_row) ret0_row[i] = ret[i];
+    if (best_ret) best_ret[i] = beta;
+    if (best_k) best_k[i] = bk;
+  });
+  return EARL_OK;
+}
+
+// include/earl_physics.h, "CEM planning on the door and the peg": the same two walks over sawyer_cem.h's per-element functions.  The elites of an env are the first E of a
+// sort under cem_before (the order of item 4 itself, where the kernel runs a radix select over its keys) that are not NaN; the moments are integer sums, so the order
+// in which the elites are added gives the same bits as the kernel's split over lanes.
+int32_t earl_sawyer_cem_candidates_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_params* params, int32_t j, const float* mean, const float* std, float* act_out) {
+  if (int rc = check_sawyer_cem(SawyerCemCall::Candidates, cfg, params, j, mean, std, act_out, nullptr)) return rc;
+  if (cfg->n == 0) return EARL_OK;
+  SawyerCemArgs p = sawyer_cem_args(cfg, params, mean, std);
+  p.word0 = kCemDraw | (uint32_t)j;
+  const long long rows = (long long)p.K * p.H;
+#pragma omp parallel for schedule(static) if (rows * p.n >= 4096)
+  for (long long kt = 0; kt < rows; ++kt) {
+    const int k = (int)(kt / p.H), t = (int)(kt - (long long)k * p.H);
+    for (int i = 0; i < p.n; ++i) {
+      float m[4], s[4], c[4];
+      scem_mean(p, i, t, m);
+      scem_std(p, i, t, s);
+      scem_candidate(p, i, (uint32_t)k, (uint32_t)t, m, s, c);
+      float* dst = act_out + scem_act_index(p, i, k, t);
+      for (int d = 0; d < 4; ++d) dst[d] = c[d];
+    }
+  }
+  return EARL_OK;
+}
+int32_t earl_sawyer_cem_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_params* params, int32_t j, const float* mean, const float* std_in, const float* act,
+                                   const double* ret, float* plan, float* std, double* ret0_row, double* best_ret, int32_t* best_k, uint8_t* elite) {
+  if (int rc = check_sawyer_cem(SawyerCemCall::Update, cfg, params, j, mean, std_in, plan, std)) return rc;
+  if (!act || !ret) return fail(EARL_ERR_ARG, "act/ret is NULL");
+  SawyerCemArgs p = sawyer_cem_args(cfg, params, mean, std_in);
+  const int n = p.n, K = p.K;
+  for_each_env(n, [&](int i) {
+    double beta = -INFINITY;
+    int bk = 0;
+    std::vector<int> order(K);
+    for (int k = 0; k < K; ++k) {
+      plan_best(ret[(size_t)k * n + i], k, beta, bk);
+      order[k] = k;
+    }
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return cem_before(ret[(size_t)a * n + i], a, ret[(size_t)b * n + i], b); });
+    int32_t Ne = 0;
+    while (Ne < p.E && cem_elite(ret[(size_t)order[Ne] * n + i], Ne, p.E)) ++Ne;      // (the NaNs stand last: the first of them ends the elites)
+    if (elite) {
+      for (int k = 0; k < K; ++k) elite[(size_t)k * n + i] = 0;
+      for (int e = 0; e < Ne; ++e) elite[(size_t)order[e] * n + i] = 1;
+    }
+    for (int t = 0; t < p.H; ++t) {
+      float m[4], s[4];
+      scem_mean(p, i, t, m);
+      scem_std(p, i, t, s);
+      int64_t A1[4] = {0, 0, 0, 0}, A2[4] = {0, 0, 0, 0};
+      for (int e = 0; e < Ne; ++e) {
+        const int k = order[e];
+        if (k > 0) {
+          const float* src = act + scem_act_index(p, i, k, t);
+          const float c[4] = {src[0], src[1], src[2], src[3]};
+          scem_accumulate(c, m, A1, A2);
+        }
+      }
+      for (int d = 0; d < 4; ++d) {
+        plan[((size_t)t * n + i) * 4 + d] = cem_new_mean(m[d], A1[d], Ne, p.alpha);
+        std[((size_t)t * n + i) * 4 + d] = cem_new_std(s[d], A1[d], A2[d], Ne, p.alpha, p.std_min, p.std_max);
+      }
     }
     if (ret0_row) ret0_row[i] = ret[i];
     if (best_ret) best_ret[i] = beta;

@@ -187,6 +187,15 @@ class PhysicsEnv:
   def mpc_rollout(self, *args, **kwargs):
     raise self._no_planner('mpc_rollout')
 
+  def _no_cem(self, who):
+    return NotImplementedError(f'{who}: the CEM planner is not built for {self.ENV or type(self).__name__} (it runs on the tabletops, the Sawyer door and the Sawyer peg)')
+
+  def plan_cem(self, *args, **kwargs):
+    raise self._no_cem('plan_cem')
+
+  def cem_candidates(self, *args, **kwargs):
+    raise self._no_cem('cem_candidates')
+
   @property
   def pair_counts(self):
     """(forward_success, backward_success) [N] int32 of the last pair launch: the phases that ended by success; None before the first"""

@@ -472,7 +472,96 @@ class SawyerDoor(PhysicsEnv):
                  'earl_sawyer_plan_candidates')
     return act
 
-  def mpc_rollout(self, T, plan=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, noise_counter=None, out=None):
+  # ------------------------------------------------------------------ CEM on top of the branch launch (include/earl_physics.h: earl_sawyer_plan_cem)
+  def _cem_params(self, who, K, H, iterations, iteration0, elites, sigma, alpha, std_min, std_max, noise_counter, update=True):
+    s = torch.as_tensor(sigma, dtype=torch.float32).reshape(-1).tolist()
+    if len(s) not in (1, 4):
+      raise ValueError(f'{who}: sigma is a number or four, one per action dimension (x, y, z, gripper)')
+    if not 1 <= int(K) <= _abi.SAWYER_PLAN_MAX_K:
+      raise ValueError(f'{who}: K = {K}: 1 .. {_abi.SAWYER_PLAN_MAX_K} candidates per env (branch 0, the plan itself, included)')
+    if int(H) < 1 or int(iterations) < 1:
+      raise ValueError(f'{who}: H = {H}, iterations = {iterations}: at least one of each')
+    if update and not 1 <= int(elites) <= min(int(K), _abi.SAWYER_CEM_MAX_E):
+      raise ValueError(f'{who}: elites = {elites}: 1 .. min(K, {_abi.SAWYER_CEM_MAX_E}) = {min(int(K), _abi.SAWYER_CEM_MAX_E)}')
+    if update and not 0.0 <= float(alpha) < 1.0:
+      raise ValueError(f'{who}: alpha = {alpha}: 0 <= alpha < 1')
+    if not 0.0 <= float(std_min) <= float(std_max) < float('inf'):
+      raise ValueError(f'{who}: std_min = {std_min}, std_max = {std_max}: finite, 0 <= std_min <= std_max')
+    nc = self.total_step_count if noise_counter is None else int(noise_counter)   # (None: the low word of the env's step count -- fresh noise per control step)
+    return _abi.SawyerCemParams(K=int(K), H=int(H), iterations=int(iterations), iteration0=int(iteration0), elites=int(elites) if update else 1,
+                                sigma=(C.c_float * 4)(*(s * 4 if len(s) == 1 else s)), noise_counter=nc & 0xFFFFFFFF, alpha=float(alpha) if update else 0.0,
+                                std_min=float(std_min), std_max=float(std_max))
+
+  def _cem_std(self, who, std, H):
+    if std is None:
+      return None
+    t = torch.as_tensor(std, device=self.device)
+    if tuple(t.shape) != (H, self.num_envs, 4):
+      raise ValueError(f'{who}: std must be [H, N, 4] = [{H}, {self.num_envs}, 4], got {list(t.shape)}')
+    return t.to(torch.float32).contiguous()
+
+  def plan_cem(self, mean=None, horizon=None, K=64, elites=8, iterations=1, sigma=0.3, std=None, alpha=0.0, std_min=0.0, std_max=2.0, iteration0=0, noise_counter=None,
+               clock=None, out=None):
+    """`iterations` cross-entropy iterations on the device from the CURRENT state (include/earl_physics.h: earl_sawyer_plan_cem): K candidates per env -- the mean plan
+    itself and K - 1 copies with clipped Gaussian noise whose scale is a std per (step, env, dimension) -- scored by the branch launch exactly as rollout_branches
+    scores them; the `elites` best (NaN last, return descending, k ascending; found by a radix select, linear in K) refit the mean AND the std, in integer sums, with
+    smoothing `alpha` and the std held in [std_min, std_max].  `std` [H, N, 4] is the std entering (None: `sigma`, a number or four, in every row).  Per iteration three
+    launches (candidates, the branch launch, update); no allocation and no host synchronisation in the call.  mean [H, N, 4] (None: zeros of [horizon, N, 4]) ->
+    {'plan', 'std' [H, N, 4] float32, 'ret' [K, N] float64 (the last iteration's returns), 'ret0' [iterations, N] float64 (the return of the plan entering each
+     iteration), 'best_ret' [N] float64, 'best_k' [N] int32 (cem_candidates(...)[best_k] is that candidate), 'elite' [K, N] uint8 (1: an elite of the last iteration),
+     'fail' [K, N] int32 (steps of the last iteration the failure guard rolled back)}.
+    `noise_counter`, `iteration0`, `clock` and `out` are plan_mppi's: a key of `out` that is missing or None is not computed, except 'ret' and 'std' (the call needs
+    both), which are then allocated; out['plan'] may be the `mean` tensor and out['std'] the `std` tensor.  K goes to 8192, elites to min(K, 1024).  The env is left
+    exactly as found -- state, goals, counters, last_obs, fail_count."""
+    m = self._plan_mean('plan_cem', mean, horizon)
+    n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
+    cp = self._cem_params('plan_cem', K, H, I, iteration0, elites, sigma, alpha, std_min, std_max, noise_counter)
+    s0 = self._cem_std('plan_cem', std, H)
+    if K * n > INT32_MAX:
+      raise ValueError(f'plan_cem: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
+    kw = dict(device=self.device)
+    want = {'plan': ((H, n, 4), torch.float32), 'std': ((H, n, 4), torch.float32), 'ret': ((K, n), torch.float64), 'ret0': ((I, n), torch.float64),
+            'best_ret': ((n,), torch.float64), 'best_k': ((n,), torch.int32), 'elite': ((K, n), torch.uint8), 'fail': ((K, n), torch.int32)}
+    if out is None:
+      res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
+    else:
+      if set(out) - set(want):
+        raise ValueError(f'plan_cem: out holds {sorted(set(out) - set(want))}; the keys are {list(want)}')
+      res = {k: t for k, t in out.items() if t is not None}
+      for k, t in res.items():
+        shape, dt = want[k]
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+          raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
+      if 'plan' not in res:
+        raise ValueError("plan_cem: out['plan'] is what the call computes")
+      for k in ('ret', 'std'):
+        if k not in res:
+          res[k] = torch.empty(*want[k][0], dtype=want[k][1], **kw)
+    self._cfg.step_counter = self.total_step_count
+    with torch.cuda.device(self.device):
+      ws = self._plan_ws(K, H)
+      _abi.check(self._lib.earl_sawyer_plan_cem(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(cp), m.data_ptr(), _ptr(s0),
+                                                res['plan'].data_ptr(), res['std'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
+                                                _ptr(res.get('best_k')), _ptr(res.get('elite')), _ptr(res.get('fail')), clock, C.byref(ws), self._stream()),
+                 'earl_sawyer_plan_cem')
+    return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
+
+  def cem_candidates(self, mean, K, sigma=0.3, std=None, iteration=0, noise_counter=None, std_min=0.0, std_max=2.0):
+    """the K candidates of plan_cem's iteration `iteration` around `mean` [H, N, 4] with the std `std` [H, N, 4] (None: `sigma` in every row), written out:
+    [K, H, N, 4] float32, row 0 the clipped mean -- what rollout_branches takes (earl_sawyer_cem_candidates; plan_cem runs the same kernel).  With plan_cem's
+    `noise_counter` (None: the env's step count, unchanged by plan_cem), `std_min` and `std_max` they are the candidates that call scored."""
+    m = self._plan_mean('cem_candidates', mean, None)
+    H = int(m.shape[0])
+    cp = self._cem_params('cem_candidates', K, H, 1, 0, 1, sigma, 0.0, std_min, std_max, noise_counter, update=False)
+    s0 = self._cem_std('cem_candidates', std, H)
+    act = torch.empty(int(K), H, self.num_envs, 4, dtype=torch.float32, device=self.device)
+    with torch.cuda.device(self.device):
+      _abi.check(self._lib.earl_sawyer_cem_candidates(self._cfg_ref, C.byref(cp), int(iteration), m.data_ptr(), _ptr(s0), act.data_ptr(), self._stream()),
+                 'earl_sawyer_cem_candidates')
+    return act
+
+  def mpc_rollout(self, T, plan=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, noise_counter=None, out=None, method='mppi', elites=8, alpha=0.0,
+                  std_min=0.0, std_max=2.0):
     """T steps of receding-horizon MPPI control, DEFINED as this composition of public methods (one call each per control step, no host synchronisation in the loop):
         P = plan.clone()  (None: zeros of [horizon, N, 4]);  nc0 = noise_counter  (None: the low 32 bits of env.total_step_count at entry)
         for s in range(T):
@@ -483,22 +572,34 @@ class SawyerDoor(PhysicsEnv):
        'plan' [H, N, 4] (the shifted plan after the last step: what the next call continues from), 'ret0' [T, iterations, N] and 'best_ret' [T, N] float64.
     The env advances by T steps (total_step_count, counters, last_obs: as T calls of rollout).  `done` rows are reported and nothing is reset: the Sawyer kernels have no
     auto-reset, so a caller that wants episodes resets between calls.  `out`: an optional dict of preallocated [T, ...] tensors under rollout()'s keys.  A fused
-    one-launch loop is not built for these envs (the score and the update would need a grid-wide join inside the stepper kernel)."""
+    one-launch loop is not built for these envs (the score and the update would need a grid-wide join inside the stepper kernel).
+    method='cem': the same composition with plan_cem(P, K=, elites=, iterations=, sigma=, std=None, alpha=, std_min=, std_max=, noise_counter=...) as its planner --
+    the std restarts from `sigma` at every control step, as on the tabletops, so there is no std to carry or shift; `temperature` is not read."""
     T = int(T)
     if T < 1:
       raise ValueError(f'mpc_rollout: T = {T}: at least one control step')
+    if method not in ('mppi', 'cem'):
+      raise ValueError(f"mpc_rollout: method = {method!r}: 'mppi' or 'cem'")
     P = self._plan_mean('mpc_rollout', plan, horizon).clone()
     n, H, K, I = self.num_envs, int(P.shape[0]), int(K), int(iterations)
-    self._plan_params('mpc_rollout', K, H, I, 0, sigma, temperature, noise_counter)      # (the argument errors, before anything moves)
+    if method == 'cem':                                                                  # (the argument errors, before anything moves)
+      self._cem_params('mpc_rollout', K, H, I, 0, elites, sigma, alpha, std_min, std_max, noise_counter)
+    else:
+      self._plan_params('mpc_rollout', K, H, I, 0, sigma, temperature, noise_counter)
     nc0 = self.total_step_count if noise_counter is None else int(noise_counter)
     kw = dict(device=self.device)
     res = self._new_out((T,)) if out is None else dict(out)
     res.update(act=torch.empty(T, n, 4, dtype=torch.float32, **kw), ret0=torch.empty(T, I, n, dtype=torch.float64, **kw), best_ret=torch.empty(T, n, dtype=torch.float64, **kw))
     rows = [k for k in res if k not in ('act', 'ret0', 'best_ret')]
     ret = torch.empty(K, n, dtype=torch.float64, **kw)
+    std = torch.empty(H, n, 4, dtype=torch.float32, **kw) if method == 'cem' else None
     for s in range(T):
-      self.plan_mppi(P, K=K, iterations=I, sigma=sigma, temperature=temperature, noise_counter=(nc0 + s) & 0xFFFFFFFF,
-                     out={'plan': P, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]})
+      if method == 'cem':
+        self.plan_cem(P, K=K, elites=elites, iterations=I, sigma=sigma, alpha=alpha, std_min=std_min, std_max=std_max, noise_counter=(nc0 + s) & 0xFFFFFFFF,
+                      out={'plan': P, 'std': std, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]})
+      else:
+        self.plan_mppi(P, K=K, iterations=I, sigma=sigma, temperature=temperature, noise_counter=(nc0 + s) & 0xFFFFFFFF,
+                       out={'plan': P, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]})
       self.rollout(P[:1], out={k: res[k][s:s + 1] for k in rows})
       res['act'][s].copy_(P[0])
       if H > 1:

@@ -500,6 +500,66 @@ int32_t earl_sawyer_plan_candidates_cpu(const earl_sawyer_cfg* cfg, const earl_s
 int32_t earl_sawyer_plan_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_params* params, int32_t j, const float* mean, const float* act, const double* ret,
                                     float* plan, double* ret0_row, double* best_ret, int32_t* best_k);
 
+/* ---- CEM planning on the door and the peg: elites instead of weights, a refitted std per (step, env, dim), the elite set found in O(K) ----
+ * earl_tabletop_plan_cem's contract (earl_tabletop.h, "CEM planning", items 1 - 7) with FOUR action dimensions, around the same three launches per iteration as
+ * earl_sawyer_plan_mppi: a candidates kernel, earl_sawyer_branch_rollout untouched and through the public ABI, an update kernel.  The candidates go through memory,
+ * as MPPI's do here, so the update READS the elites back instead of regenerating them.  For iteration j = iteration0 + i, env with global id g = cfg->env_offset +
+ * env, the entering plan `mean` and the entering std (`std0` for i = 0, the previous iteration's results afterwards):
+ *   1 clipped mean and clamped std   m = clip(mean) on all four words, as MPPI item 1 above.  s = sclamp(std) per word, sclamp(x) = (y = x > std_min ? x : std_min;
+ *                   y < std_max ? y : std_max): a NaN maps to std_min.  With std0 == NULL every row's std is sclamp(sigma[d]).
+ *   2 candidates    branch 0 is m.  For k >= 1: a_k[t][d] = clip(fmaf(s[t][d], eps_d, m[t][d])), eps_d = normal_quantile_f32(word_d >> 8), words x, y, z, w of ONE
+ *                   Philox4x32-10 block serving d = 0 .. 3: key = cfg->seed, counter words = {0x43454D00 | j, g, (k << 16) | t, noise_counter}.  Word 0 collides with
+ *                   no other draw of the Sawyer envs: checked against the list of MPPI item 2 above -- they use 0 .. 31, 0xFFF0 .. 0xFFF2 and 0xFFFD .. 0xFFFF, the
+ *                   Gaussian head 0x504F4C00 and MPPI 0x504C4E00 .. 0x504C4EFF; 0x43454D00 .. 0x43454DFF meets none of these.
+ *   3 scores        ret[k][env] = summary->ret of earl_sawyer_branch_rollout fed with those candidates, exactly as earl_sawyer_plan_mppi calls it (act_branch_stride =
+ *                   H * n * 4, the caller's `clock`, `fail` of the last iteration).
+ *   4 elites        a total order over the K branches: k stands before k' iff ret[k] is not NaN and ret[k'] is NaN; or neither is NaN and ret[k] > ret[k']; or
+ *                   (ret[k] == ret[k'], or both are NaN) and k < k'.  rank_k = the number of branches before k.  k is an elite iff rank_k < E and ret[k] is not NaN;
+ *                   Ne = the number of elites.  The elite set is defined by this order and by nothing in the implementation (which is a radix select over the
+ *                   order's 64-bit keys: linear in K).  best_ret and best_k: MPPI items 6, 7.
+ *   5 update        per (t, d), over the elites in any order, every sum integer: D_k = rint((double)(a_k - m) * 2^20) as int64, a_k READ from the candidates (the
+ *                   subtraction one float32 operation; branch 0 has D = 0).  A1 = sum D_k, A2 = sum D_k^2, V = Ne * A2 - A1^2.  e_mean = m + (float)((double)A1 /
+ *                   ((double)Ne * 2^20)).  e_std = sqrtf((float)((double)V / ((double)Ne * (double)Ne * 2^40))), the float32 square root, correctly rounded.
+ *                   mean' = clip(fmaf(alpha, m - e_mean, e_mean)); std' = sclamp(fmaf(alpha, s - e_std, e_std)).  Ne == 0 (every return NaN): mean' = m, std' = s.
+ *                   Bounds: a_k and m lie in [-1, 1], so |D_k| <= 2^21 and D_k^2 <= 2^42; A2 <= Ne * 2^42 and |A1| <= Ne * 2^21.  Ne * A2 <= Ne^2 * 2^42 and
+ *                   A1^2 <= Ne^2 * 2^42 stay <= 2^62, exact in int64, only for Ne <= 2^10.  Hence elites is in 1 .. min(K, EARL_SAWYER_CEM_MAX_E) with
+ *                   EARL_SAWYER_CEM_MAX_E = 1024, while K itself goes to EARL_SAWYER_PLAN_MAX_K = 8192 (V >= 0 by Cauchy-Schwarz).
+ *   6 outputs       plan [H, n, 4]: may be `mean` itself.  std [H, n, 4], REQUIRED: the workspace between iterations and a result; may be `std0` itself.  Any other
+ *                   overlap among the four arrays is refused.  ret [K, n], REQUIRED.  ret0, best_ret, best_k, fail: as MPPI.  elite NULL or [K, n] uint8: 1 where
+ *                   branch k is an elite of the LAST iteration, 0 elsewhere.
+ *   7 chaining, state, non-finite   as MPPI: I iterations in one call equal I calls of one, each fed the previous plan and std; `st` is never written; nothing
+ *                   faults on NaN or Inf in mean, std0 or the state; a NaN return is never an elite.
+ *   ws              a block of earl_sawyer_plan_ws_bytes(nv, K, H, n, &bytes) bytes, the layout earl_sawyer_plan_mppi carves: there is no size function of its own.
+ * EARL_ERR_ARG before any HIP call for: everything earl_sawyer_plan_mppi refuses (there is no temperature); elites outside 1 .. min(K, EARL_SAWYER_CEM_MAX_E); an alpha
+ * that is not finite or outside [0, 1); std_min / std_max not finite or not 0 <= std_min <= std_max; std NULL; the overlaps of item 6; an act, act_out, plan or std that is
+ * not 16-byte aligned (a row is one 16-byte access; the host twins ask no alignment).  n == 0 returns EARL_OK and writes nothing.
+ * earl_sawyer_cem_candidates: item 2 written out for ONE iteration j (0 .. 255), act_out [K, H, n, 4], 16-byte aligned; std NULL: sigma.  It reads cfg->n, env_offset
+ * and seed and params->K, H, sigma, noise_counter, std_min and std_max only.
+ * earl_sawyer_cem_update: items 4 - 7 of iteration j on GIVEN device candidates act [K, H, n, 4] (16-byte aligned, every word in [-1, 1]) and returns ret [K, n]:
+ * the launch earl_sawyer_plan_cem itself makes after the branch launch, public so that the selection can be driven with crafted returns without stepping physics.
+ * std_in NULL: sigma.  plan may be `mean`, std may be `std_in`; ret0_row, best_ret, best_k ([n]) and elite ([K, n]) may each be NULL.  It reads cfg->n and params->K, H,
+ * elites, sigma, alpha, std_min and std_max. */
+#define EARL_SAWYER_CEM_MAX_E 1024
+typedef struct earl_sawyer_cem_params {
+  int32_t K, H, iterations, iteration0;   /* as earl_sawyer_plan_params; K in 1 .. EARL_SAWYER_PLAN_MAX_K */
+  int32_t elites;                          /* E: 1 .. min(K, EARL_SAWYER_CEM_MAX_E) */
+  float sigma[4];                          /* the std of every row when no std0 is given; finite, >= 0 */
+  uint32_t noise_counter;
+  float alpha;                             /* smoothing: finite, 0 <= alpha < 1 */
+  float std_min, std_max;                  /* finite, 0 <= std_min <= std_max */
+} earl_sawyer_cem_params;
+int earl_sawyer_plan_cem(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                         const earl_sawyer_cem_params* params, const float* mean, const float* std0, float* plan, float* std, double* ret, double* ret0,
+                         double* best_ret, int32_t* best_k, uint8_t* elite, int32_t* fail, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream);
+int earl_sawyer_cem_candidates(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_params* params, int32_t j, const float* mean, const float* std, float* act_out,
+                               earl_stream_t stream);
+int earl_sawyer_cem_update(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_params* params, int32_t j, const float* mean, const float* std_in, const float* act,
+                           const double* ret, float* plan, float* std, double* ret0_row, double* best_ret, int32_t* best_k, uint8_t* elite, earl_stream_t stream);
+/* Host twins (libearl_host.so; host pointers, no alignment asked): csrc/sawyer_cem.h in plain loops, the elites by a sort under the order of item 4. */
+int32_t earl_sawyer_cem_candidates_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_params* params, int32_t j, const float* mean, const float* std, float* act_out);
+int32_t earl_sawyer_cem_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_params* params, int32_t j, const float* mean, const float* std_in, const float* act,
+                                   const double* ret, float* plan, float* std, double* ret0_row, double* best_ret, int32_t* best_k, uint8_t* elite);
+
 /* The policy contract on the host (libearl_host.so; host pointers): actions [n, A] of n observation rows obs [n, dims[0]], dims[0] in 1..256, hidden widths in 1..256,
  * the last layer A wide (head = NULL) or 2 A wide (rows 0..A-1 the mean, A..2A-1 the raw log_std), A >= 1.  eps [n, A] = the standard-normal draws to use with a
  * head in EARL_HEAD_SAMPLE mode; NULL (or EARL_HEAD_MEAN, or no head) evaluates the mean / the deterministic policy.  policy->out_act is applied last, as on the

@@ -300,6 +300,15 @@ SIGNATURES = {
     'earl_sawyer_plan_cem': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(SawyerCemParams)] + [C.c_void_p] * 11 + [_P(SawyerBranchWs), C.c_void_p],
     'earl_sawyer_cem_candidates': [_P(SawyerCfg), _P(SawyerCemParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_sawyer_cem_update': [_P(SawyerCfg), _P(SawyerCemParams), C.c_int32] + [C.c_void_p] * 11,
+    # the branch launch and both planners with a discount and a terminal value net (struct earl_plan_value): pv after `clock` in the branch launch, after `params` in the
+    # planners; one size function for the three (nv, K, H, n; H = 0: the branch launch's own)
+    'earl_sawyer_value_ws_bytes': [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int64)],
+    'earl_sawyer_branch_rollout_value': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                         _P(PlanValue), _P(SawyerBranchWs), _P(EpisodeSummary), C.c_void_p, C.c_void_p, C.c_void_p],
+    'earl_sawyer_plan_mppi_value': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(SawyerPlanParams), _P(PlanValue)] + [C.c_void_p] * 8
+                                   + [_P(SawyerBranchWs), C.c_void_p],
+    'earl_sawyer_plan_cem_value': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(SawyerCemParams), _P(PlanValue)] + [C.c_void_p] * 11
+                                  + [_P(SawyerBranchWs), C.c_void_p],
     # the closed loop inside the minitaur rollout kernels: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
     'earl_minitaur_policy_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, _P(MinitaurOut), C.c_void_p],
@@ -376,6 +385,8 @@ HOST_EXTRA_SIGNATURES = {
     # the host twins of its CEM planner's two kernels: cfg, params, j, mean, std, act_out | std_in, act, ret, plan, std, ret0_row, best_ret, best_k, elite
     'earl_sawyer_cem_candidates_cpu': ([_P(SawyerCfg), _P(SawyerCemParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
     'earl_sawyer_cem_update_cpu': ([_P(SawyerCfg), _P(SawyerCemParams), C.c_int32] + [C.c_void_p] * 10, C.c_int32),
+    # the host twin of the planners' value kernel: pv, H, rows, last_obs [rows, 14], ret [rows] (the terminal term is added in place)
+    'earl_sawyer_value_terminal_cpu': ([_P(PlanValue), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
     'earl_tanh_f32': ([C.c_float], C.c_float),
     'earl_exp_f32': ([C.c_float], C.c_float),
     'earl_normal_quantile_f32': ([C.c_uint32], C.c_float),

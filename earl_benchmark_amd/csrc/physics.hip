@@ -236,9 +236,12 @@ int earl_sawyer_branch_ws_bytes(int32_t nv, int32_t K, int32_t n, int64_t* bytes
   *bytes = sawyer_branch_bytes(nv, (int64_t)K * n);
   return EARL_OK;
 }
-int earl_sawyer_branch_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
-                               int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
-                               const earl_episode_summary* summary, double* last_obs, int32_t* fail, earl_stream_t stream) {
+// the body of earl_sawyer_branch_rollout.  gamma NULL: the plain sum, the kernels of physics_branch.hip / physics_branch_w8.hip.  gamma given
+// (earl_sawyer_branch_rollout_value with discount != 1, sawyer_value.hip): the discounted sum, the same kernel text built with EARL_BRANCH_DISCOUNT
+// (physics_branch_value.hip / physics_branch_value_w8.hip), `disc` the [K n] words of the caller's block that carry d_t; same checks, same forms, same replicate kernel
+static int sawyer_branch_launch(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
+                                const earl_episode_summary* summary, double* last_obs, int32_t* fail, const double* gamma, double* disc, earl_stream_t stream) {
   const earl_sawyer_out none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (!model || !cfg || !st || !act || !ws || K < 0 || H < 0 || (nv != 10 && nv != 15) || !sawyer_args_ok(kStep, cfg, st, nv, &none)) return EARL_ERR_ARG;
   const int n = cfg->n;
@@ -260,7 +263,9 @@ int earl_sawyer_branch_rollout(const earl_link_model* model, const earl_collisio
   int32_t* w = reinterpret_cast<int32_t*>(d);
   vs.steps_since_goal_change = cfg->goal_change_frequency > 0 ? w : nullptr; w += V;
   vs.obj_init = st->obj_init;                             // (read only, indexed by the env: v % n)
-  SawyerBranchArgs a;
+  SawyerBranchValueArgs a;                                // (the plain kernels read its base, the SawyerBranchArgs)
+  a.gamma = gamma ? *gamma : 1.0;
+  a.br_disc = disc;
   static_cast<SawyerArgs&>(a) = SawyerArgs{model, col, *cfg, vs, act, H, none, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
   a.cfg.n = (int)V;
   a.n_env = n;
@@ -275,13 +280,37 @@ int earl_sawyer_branch_rollout(const earl_link_model* model, const earl_collisio
   const SawyerForm form = sawyer_form(nv, (int)V, H, &a.st, true);
   if (form == SawyerForm::PegSliced) a.slice = peg_slice();
   else a.st.sched = nullptr;                              // (the replicate kernel clears the queue only where it is used)
-  if (int rc = earl_unit_branch_replicate(&a, st, nv, stream)) return rc;
+  if (int rc = earl_unit_branch_replicate(static_cast<const SawyerBranchArgs*>(&a), st, nv, stream)) return rc;
+  if (gamma)
+    switch (form) {
+      case SawyerForm::DoorW8: return earl_unit_branch_value_w8_sawyer_rollout(&a, stream);
+      case SawyerForm::Door: case SawyerForm::Peg: return earl_unit_branch_value_sawyer_rollout(&a, nv, 0, stream);
+      case SawyerForm::PegSliced: return earl_unit_branch_value_sawyer_rollout(&a, nv, 1, stream);
+      default: return EARL_ERR_ARG;
+    }
   switch (form) {
-    case SawyerForm::DoorW8: return earl_unit_branch_w8_sawyer_rollout(&a, stream);
-    case SawyerForm::Door: case SawyerForm::Peg: return earl_unit_branch_sawyer_rollout(&a, nv, 0, stream);
-    case SawyerForm::PegSliced: return earl_unit_branch_sawyer_rollout(&a, nv, 1, stream);
+    case SawyerForm::DoorW8: return earl_unit_branch_w8_sawyer_rollout(static_cast<const SawyerBranchArgs*>(&a), stream);
+    case SawyerForm::Door: case SawyerForm::Peg: return earl_unit_branch_sawyer_rollout(static_cast<const SawyerBranchArgs*>(&a), nv, 0, stream);
+    case SawyerForm::PegSliced: return earl_unit_branch_sawyer_rollout(static_cast<const SawyerBranchArgs*>(&a), nv, 1, stream);
     default: return EARL_ERR_ARG;                         // (L64 was refused above; the policy reading never gives DoorSliced)
   }
+}
+int earl_sawyer_branch_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
+                               const earl_episode_summary* summary, double* last_obs, int32_t* fail, earl_stream_t stream) {
+  return sawyer_branch_launch(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, ws, summary, last_obs, fail, nullptr, nullptr, stream);
+}
+// for sawyer_value.hip (declared there: it includes no stepper header): the launch above with the discounted sum, and where the [K n, 14] carried observation rows of
+// a branch workspace start -- the rows the launch used when the caller gave no last_obs (the carve in sawyer_branch_launch: qpos, qvel, mocap_pos and goal rows before them)
+__attribute__((visibility("hidden"))) int earl_unit_sawyer_branch_discounted(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg,
+                                                                             const earl_sawyer_state* st, int32_t K, int32_t H, const float* act, int64_t act_branch_stride,
+                                                                             const uint64_t* clock, const earl_sawyer_branch_ws* ws, const earl_episode_summary* summary,
+                                                                             double* last_obs, int32_t* fail, double gamma, double* disc, earl_stream_t stream) {
+  if (!disc) return EARL_ERR_ARG;
+  return sawyer_branch_launch(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, ws, summary, last_obs, fail, &gamma, disc, stream);
+}
+__attribute__((visibility("hidden"))) double* earl_unit_sawyer_branch_rows(int32_t nv, int64_t V, void* base) {
+  return static_cast<double*>(base) + V * (int64_t)(nv + 1 + nv + 3 + 7);
 }
 
 int earl_sawyer_reset(const earl_link_model* model, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,

@@ -30,6 +30,21 @@ struct SawyerBranchArgs : SawyerArgs {
   int32_t* br_first;
   int32_t* br_fail;
 };
+// earl_sawyer_branch_rollout_value with discount != 1: the branch block followed by gamma and the branch's running discount.  A derived struct once more, so that
+// the plain branch kernels' argument -- and with it their code objects -- stays what it was.  d_t goes THROUGH THE WORKSPACE beside br_ret (br_disc, [K n] words of the
+// caller's block: after env step t the word holds d_{t+1}), because nothing of a branch may live across a timestep and in the time-sliced form another wave takes
+// the next slice; recomputing d_t from t at every step would cost t multiplications per step.  The bits are the recurrence's either way.
+struct SawyerBranchValueArgs : SawyerBranchArgs {
+  double gamma;                  // 0 < gamma < 1 (gamma == 1 runs the plain branch kernels)
+  double* br_disc;               // [K n]
+};
+// EARL_BRANCH_DISCOUNT: the compile-time flag of sawyer_branch_rollout_kernel, set by physics_branch_value.hip and physics_branch_value_w8.hip only (a define, like
+// EARL_DOOR_WPB: the kernel keeps its name and its template parameters, so the units without the define compile to what they compiled to before)
+#ifndef EARL_BRANCH_DISCOUNT
+#define EARL_BRANCH_DISCOUNT 0
+#endif
+constexpr bool kBranchDiscount = EARL_BRANCH_DISCOUNT != 0;
+using SawyerBranchKernelArgs = std::conditional<kBranchDiscount, SawyerBranchValueArgs, SawyerBranchArgs>::type;
 
 // Work queue of the time-sliced rollout (earl_sawyer_state.sched: progress[G] then lock[G], zero on entry).  An env group's state is in HBM after every env
 // step (the failure guard's "last stable state"), so ANY wave can take the group's next slice of env steps; a wave claims the unlocked group that has come
@@ -318,13 +333,28 @@ __device__ __forceinline__ float4 sawyer_branch_action(const int t, const int v)
   return *reinterpret_cast<const float4*>(ka->action + (size_t)k * (size_t)ka->act_stride + ((size_t)t * n + i) * 4);
 }
 // the virtual env's summary and rolled-back steps after env step t, by lane 0 of the live env: cl_episode_summary's three words, each its definition applied to the
-// step's reward and success as a rollout would have stored them (a rolled-back step: 0 and 0), and the number of such steps; step 0 initialises all four
+// step's reward and success as a rollout would have stored them (a rolled-back step: 0 and 0), and the number of such steps; step 0 initialises all four.
+// DISCOUNT (earl_sawyer_branch_rollout_value, discount != 1): ret is the discounted sum of include/earl_physics.h -- term = d_t * r_t; ret = ret + term;
+// d_{t+1} = d_t * gamma, three float64 roundings with contraction off (value_accumulate of tabletop_value.h, mirrored), d_0 = 1 and d_{t+1} kept in br_disc[v];
+// a rolled-back step adds 0 and still advances d.  gamma and br_disc are read through the kernel-argument segment here, like the other fields
+template <bool DISCOUNT>
 __device__ __forceinline__ void sawyer_branch_summary(const int t, const int v, const double r_t, const uint8_t s_t, const bool failed) {
   const EARL_KARG SawyerBranchArgs* ka = cl_kernarg<SawyerBranchArgs>();
   double* const ret = ka->br_ret;
   uint8_t* const last = ka->br_last;
   int32_t* const first = ka->br_first;
   int32_t* const fail = ka->br_fail;
+  if constexpr (DISCOUNT) {
+#pragma clang fp contract(off)
+    const EARL_KARG SawyerBranchValueArgs* kv = cl_kernarg<SawyerBranchValueArgs>();
+    double* const disc = kv->br_disc;
+    if (ret) {
+      const double d = t > 0 ? disc[v] : 1.0;
+      const double term = d * r_t;
+      ret[v] = (t > 0 ? ret[v] : 0.0) + term;
+      disc[v] = d * kv->gamma;
+    }
+  } else
   if (ret) ret[v] = (t > 0 ? ret[v] : 0.0) + r_t;                      // sum over t ascending of (double)reward_t
   if (last) last[v] = s_t;                                             // (the one of step T - 1 stays)
   if (first) {
@@ -360,8 +390,10 @@ __global__ __launch_bounds__(64 * Lim<NV>::WPB, EARL_WAVES_PER_EU) void sawyer_p
 // action given, no [T] row written, the state rows the workspace's.  `a` must stay the kernel's ONLY argument, as for the policy kernel: the branch's fields are read
 // through the kernel-argument segment pointer cast to SawyerBranchArgs*
 static_assert(std::is_trivially_copyable<SawyerBranchArgs>::value, "the branch pieces read SawyerBranchArgs as laid out in the kernel-argument segment");
+// (under EARL_BRANCH_DISCOUNT the argument is the SawyerBranchValueArgs and sawyer_branch_summary<true> keeps the discounted sum: the same text otherwise)
+static_assert(std::is_trivially_copyable<SawyerBranchValueArgs>::value, "the discounted summary reads SawyerBranchValueArgs as laid out in the kernel-argument segment");
 template <int NV, int LPE, bool SLICED = false>
-__global__ __launch_bounds__(64 * Lim<NV>::WPB, EARL_WAVES_PER_EU) void sawyer_branch_rollout_kernel(const SawyerBranchArgs a) {
+__global__ __launch_bounds__(64 * Lim<NV>::WPB, EARL_WAVES_PER_EU) void sawyer_branch_rollout_kernel(const SawyerBranchKernelArgs a) {
   static_assert(LPE == 16, "the branch launch has the 16-lane forms only");
   constexpr bool POLICY = false;
   constexpr bool BRANCH = true;

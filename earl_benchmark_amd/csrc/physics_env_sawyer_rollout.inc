@@ -154,7 +154,8 @@
     if constexpr (BRANCH) {
       // reward and success of the step as a rollout would have stored them (a rolled-back step: 0 and 0) into the virtual env's summary, in device memory after every
       // env step like the population launch's: a time slice another wave takes finds the words under sched_release / sched_claim
-      if (sub == 0 && live) sawyer_branch_summary(t, env, (double)(failed ? 0.f : rew), failed ? (uint8_t)0 : suc, failed);
+      // (kBranchDiscount -- the units built with EARL_BRANCH_DISCOUNT --: the sum is the discounted one, d_t beside it in the workspace)
+      if (sub == 0 && live) sawyer_branch_summary<kBranchDiscount>(t, env, (double)(failed ? 0.f : rew), failed ? (uint8_t)0 : suc, failed);
     }
     if constexpr (POLICY) {
       // reward and success of the step (a rolled-back step: 0 and 0) to their rows, and into the env's episode summary: each word is its definition applied to exactly

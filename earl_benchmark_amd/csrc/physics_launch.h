@@ -27,6 +27,9 @@ extern "C" __attribute__((visibility("hidden"))) void earl_unit_kitchen_bf16_pol
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_replicate(const void* sawyer_branch_args, const void* src_state, int nv, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_sawyer_rollout(const void* sawyer_branch_args, int nv, int sliced, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_w8_sawyer_rollout(const void* sawyer_branch_args, void* stream);
+// the same launch with the discounted sum (physics_branch_value.hip, physics_branch_value_w8.hip): the argument is a SawyerBranchValueArgs; the replicate kernel is the one above
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_value_sawyer_rollout(const void* sawyer_branch_value_args, int nv, int sliced, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_value_w8_sawyer_rollout(const void* sawyer_branch_value_args, void* stream);
 extern "C" int earl_sawyer_rollout_door_w8(const earl_link_model* model, const earl_collision_model* col, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                            const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream);
 

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sawyer_cem.h"
+#include "sawyer_value.h"   // the rules of earl_plan_value on these envs (earl_sawyer_plan_cem_value)
 #include "cem_select.h"
 
 using namespace earl;
@@ -185,22 +186,31 @@ int earl_sawyer_cem_update(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_par
   return launch_update(p, (hipStream_t)stream);
 }
 
-int earl_sawyer_plan_cem(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
-                         const earl_sawyer_cem_params* params, const float* mean, const float* std0, float* plan, float* std, double* ret, double* ret0,
-                         double* best_ret, int32_t* best_k, uint8_t* elite, int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
-                         earl_stream_t stream) {
+}  // extern "C"
+
+namespace {
+
+// The body of earl_sawyer_plan_cem and earl_sawyer_plan_cem_value: pv as in sawyer_plan.hip's plan_mppi -- NULL: item 3 is earl_sawyer_branch_rollout and the block
+// earl_sawyer_plan_ws_bytes'; otherwise earl_sawyer_branch_rollout_value and earl_sawyer_value_ws_bytes'.  Nothing else differs.
+int plan_cem(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+             const earl_sawyer_cem_params* params, const earl_plan_value* pv, const float* mean, const float* std0, float* plan, float* std, double* ret, double* ret0,
+             double* best_ret, int32_t* best_k, uint8_t* elite, int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream) {
   if (int rc = check_sawyer_cem(SawyerCemCall::Cem, cfg, params, 0, mean, std0, plan, std)) return rc;
+  if (int rc = check_sawyer_value(pv, g_err)) return rc;
   if (!ret) return fail(EARL_ERR_ARG, "ret is NULL: the branch launch writes it and the update reads it");
   if (!ws) return fail(EARL_ERR_ARG, "ws is NULL");
   if (misaligned16(plan) || misaligned16(std)) return fail(EARL_ERR_ARG, "plan / std is not 16-byte aligned: a row is one 16-byte store");
   const int n = cfg->n, K = params->K, H = params->H;
   int64_t branch = 0, need = 0;
-  if (earl_sawyer_branch_ws_bytes(nv, K, n, &branch) || earl_sawyer_plan_ws_bytes(nv, K, H, n, &need)) return fail(EARL_ERR_ARG, "nv = %d: 10 (door) or 15 (peg)", nv);
+  if (earl_sawyer_branch_ws_bytes(nv, K, n, &branch) || (pv ? earl_sawyer_value_ws_bytes(nv, K, H, n, &need) : earl_sawyer_plan_ws_bytes(nv, K, H, n, &need)))
+    return fail(EARL_ERR_ARG, "nv = %d: 10 (door) or 15 (peg)", nv);
   branch = round_up(branch, 8);
+  const int64_t scored = pv ? branch + (int64_t)K * n * 8 : branch;                   // (what the scoring call takes of the block: earl_sawyer_value_ws_bytes with H = 0)
   if (n > 0 && (!ws->base || (reinterpret_cast<uintptr_t>(ws->base) & 7) != 0 || ws->bytes < need))
     return fail(EARL_ERR_ARG, "ws: base %p (8-byte aligned), %lld bytes of the %lld needed", ws->base, (long long)ws->bytes, (long long)need);
   const earl_sawyer_branch_ws bws{ws->base, branch};
-  float* const act = n > 0 ? reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws->base) + (uintptr_t)branch + 15) & ~(uintptr_t)15) : plan;
+  const earl_sawyer_branch_ws vws{ws->base, scored};
+  float* const act = n > 0 ? reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws->base) + (uintptr_t)scored + 15) & ~(uintptr_t)15) : plan;
   const earl_episode_summary sum{ret, nullptr, nullptr};
   // everything the branch launch refuses in model / col / cfg / st / nv and the lane switch, decided by the branch launch itself: with H = 0 it returns after its
   // checks and before its first HIP call
@@ -220,13 +230,33 @@ int earl_sawyer_plan_cem(const earl_link_model* model, const earl_collision_mode
     p.best_k = last ? best_k : nullptr;
     p.elite = last ? elite : nullptr;
     if (int rc = launch_candidates(p, act, (hipStream_t)stream)) return rc;
-    if (int rc = earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, &bws, &sum, nullptr, last ? fail_count : nullptr, stream))
-      return fail(rc, "earl_sawyer_branch_rollout failed in iteration %d", params->iteration0 + it);
+    if (int rc = pv ? earl_sawyer_branch_rollout_value(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, pv, &vws, &sum, nullptr, last ? fail_count : nullptr, stream)
+                    : earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, &bws, &sum, nullptr, last ? fail_count : nullptr, stream))
+      return fail(rc, "earl_sawyer_branch_rollout%s failed in iteration %d", pv ? "_value" : "", params->iteration0 + it);
     if (int rc = launch_update(p, (hipStream_t)stream)) return rc;
     p.mean = plan;                                                                   // (the next iteration starts from this one's results, in place)
     p.std_in = std;
   }
   return EARL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int earl_sawyer_plan_cem(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                         const earl_sawyer_cem_params* params, const float* mean, const float* std0, float* plan, float* std, double* ret, double* ret0,
+                         double* best_ret, int32_t* best_k, uint8_t* elite, int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
+                         earl_stream_t stream) {
+  return plan_cem(model, col, nv, cfg, st, params, nullptr, mean, std0, plan, std, ret, ret0, best_ret, best_k, elite, fail_count, clock, ws, stream);
+}
+
+int earl_sawyer_plan_cem_value(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               const earl_sawyer_cem_params* params, const earl_plan_value* pv, const float* mean, const float* std0, float* plan, float* std, double* ret,
+                               double* ret0, double* best_ret, int32_t* best_k, uint8_t* elite, int32_t* fail_count, const uint64_t* clock,
+                               const earl_sawyer_branch_ws* ws, earl_stream_t stream) {
+  return plan_cem(model, col, nv, cfg, st, params, sawyer_value_plain(pv) ? nullptr : pv, mean, std0, plan, std, ret, ret0, best_ret, best_k, elite, fail_count, clock, ws,
+                  stream);
 }
 
 }  // extern "C"

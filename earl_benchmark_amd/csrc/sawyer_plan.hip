@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sawyer_plan.h"
+#include "sawyer_value.h"   // the rules of earl_plan_value on these envs (earl_sawyer_plan_mppi_value)
 
 using namespace earl;
 using namespace earl::hostside;
@@ -139,20 +140,31 @@ int earl_sawyer_plan_candidates(const earl_sawyer_cfg* cfg, const earl_sawyer_pl
   return launch_candidates(p, act_out, (hipStream_t)stream);
 }
 
-int earl_sawyer_plan_mppi(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
-                          const earl_sawyer_plan_params* params, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k,
-                          int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream) {
+}  // extern "C"
+
+namespace {
+
+// The body of earl_sawyer_plan_mppi and earl_sawyer_plan_mppi_value.  pv NULL (the value-free entry point, and `_value` with pv NULL or {1.0, NULL}): item 3 is
+// earl_sawyer_branch_rollout, the block earl_sawyer_plan_ws_bytes'.  Otherwise item 3 is earl_sawyer_branch_rollout_value (sawyer_value.hip) and the block
+// earl_sawyer_value_ws_bytes': that call's [K n] discounts sit between the branch launch's rows and the candidates.  Nothing else differs.
+int plan_mppi(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+              const earl_sawyer_plan_params* params, const earl_plan_value* pv, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k,
+              int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream) {
   if (int rc = check_sawyer_plan(SawyerPlanCall::Mppi, cfg, params, 0, mean, plan)) return rc;
+  if (int rc = check_sawyer_value(pv, g_err)) return rc;
   if (!ret) return fail(EARL_ERR_ARG, "ret is NULL: the branch launch writes it and the update reads it");
   if (!ws) return fail(EARL_ERR_ARG, "ws is NULL");
   const int n = cfg->n, K = params->K, H = params->H;
   int64_t branch = 0, need = 0;
-  if (earl_sawyer_branch_ws_bytes(nv, K, n, &branch) || earl_sawyer_plan_ws_bytes(nv, K, H, n, &need)) return fail(EARL_ERR_ARG, "nv = %d: 10 (door) or 15 (peg)", nv);
+  if (earl_sawyer_branch_ws_bytes(nv, K, n, &branch) || (pv ? earl_sawyer_value_ws_bytes(nv, K, H, n, &need) : earl_sawyer_plan_ws_bytes(nv, K, H, n, &need)))
+    return fail(EARL_ERR_ARG, "nv = %d: 10 (door) or 15 (peg)", nv);
   branch = round_up(branch, 8);
+  const int64_t scored = pv ? branch + (int64_t)K * n * 8 : branch;                   // (what the scoring call takes of the block: earl_sawyer_value_ws_bytes with H = 0)
   if (n > 0 && (!ws->base || (reinterpret_cast<uintptr_t>(ws->base) & 7) != 0 || ws->bytes < need))
     return fail(EARL_ERR_ARG, "ws: base %p (8-byte aligned), %lld bytes of the %lld needed", ws->base, (long long)ws->bytes, (long long)need);
   const earl_sawyer_branch_ws bws{ws->base, branch};
-  float* const act = n > 0 ? reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws->base) + (uintptr_t)branch + 15) & ~(uintptr_t)15) : plan;
+  const earl_sawyer_branch_ws vws{ws->base, scored};
+  float* const act = n > 0 ? reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws->base) + (uintptr_t)scored + 15) & ~(uintptr_t)15) : plan;
   const earl_episode_summary sum{ret, nullptr, nullptr};
   // everything the branch launch refuses in model / col / cfg / st / nv and the lane switch, decided by the branch launch itself: with H = 0 it returns after its
   // checks and before its first HIP call
@@ -170,13 +182,30 @@ int earl_sawyer_plan_mppi(const earl_link_model* model, const earl_collision_mod
     p.best_ret = last ? best_ret : nullptr;
     p.best_k = last ? best_k : nullptr;
     if (int rc = launch_candidates(p, act, (hipStream_t)stream)) return rc;
-    if (int rc = earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, &bws, &sum, nullptr, last ? fail_count : nullptr, stream))
-      return fail(rc, "earl_sawyer_branch_rollout failed in iteration %d", params->iteration0 + it);
+    if (int rc = pv ? earl_sawyer_branch_rollout_value(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, pv, &vws, &sum, nullptr, last ? fail_count : nullptr, stream)
+                    : earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, &bws, &sum, nullptr, last ? fail_count : nullptr, stream))
+      return fail(rc, "earl_sawyer_branch_rollout%s failed in iteration %d", pv ? "_value" : "", params->iteration0 + it);
     sawyer_plan_update_kernel<<<dim3((unsigned)n), kUpdateThreads, 0, (hipStream_t)stream>>>(p);
     if (int rc = launched("sawyer_plan_update_kernel")) return rc;
     p.mean = plan;                                                                   // (the next iteration starts from this one's result, in place)
   }
   return EARL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int earl_sawyer_plan_mppi(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                          const earl_sawyer_plan_params* params, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k,
+                          int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream) {
+  return plan_mppi(model, col, nv, cfg, st, params, nullptr, mean, plan, ret, ret0, best_ret, best_k, fail_count, clock, ws, stream);
+}
+
+int earl_sawyer_plan_mppi_value(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                const earl_sawyer_plan_params* params, const earl_plan_value* pv, const float* mean, float* plan, double* ret, double* ret0,
+                                double* best_ret, int32_t* best_k, int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream) {
+  return plan_mppi(model, col, nv, cfg, st, params, sawyer_value_plain(pv) ? nullptr : pv, mean, plan, ret, ret0, best_ret, best_k, fail_count, clock, ws, stream);
 }
 
 }  // extern "C"

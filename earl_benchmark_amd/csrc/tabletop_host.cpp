@@ -19,6 +19,7 @@
 #include "tabletop_policy.h"
 #include "sawyer_plan.h"   // the door / peg planner's candidates and reweighting (earl_sawyer_plan_candidates_cpu, earl_sawyer_plan_update_cpu)
 #include "sawyer_cem.h"    // its CEM planner's candidates and refit (earl_sawyer_cem_candidates_cpu, earl_sawyer_cem_update_cpu)
+#include "sawyer_value.h"  // the terminal value of both (earl_sawyer_value_terminal_cpu)
 #include "../../include/earl_physics.h"
 
 #ifdef _OPENMP
@@ -728,6 +729,23 @@ int32_t earl_mlp_policy_forward_cpu(const earl_mlp_policy* p, const earl_gaussia
     }
     for (int d = 0; d < A; ++d)
       actions[(size_t)i * A + d] = h ? gaussian_head_action(head, p->out_act, in[d], in[A + d], eps ? eps[(size_t)i * A + d] : 0.0f) : policy_act(in[d], p->out_act);
+  });
+  return EARL_OK;
+}
+// include/earl_physics.h, "discount and a terminal value on the door and the peg": the value kernel's work on given rows -- sawyer_value.h's per-element functions
+// around the loops above
+int32_t earl_sawyer_value_terminal_cpu(const earl_plan_value* pv, int32_t H, int32_t rows, const double* last_obs, double* ret) {
+  if (!pv || !last_obs || !ret || rows < 0 || H < 0) return fail(EARL_ERR_ARG, "pv/last_obs/ret is NULL, or rows or H < 0");
+  if (int rc = check_sawyer_value(pv, g_err, 0)) return rc;
+  if (!pv->value || rows == 0) return EARL_OK;
+  const double d_H = svalue_discount(pv->discount, H);
+  std::vector<float> x((size_t)rows * 14), V((size_t)rows);
+  for (size_t e = 0; e < x.size(); ++e) x[e] = svalue_row(last_obs[e]);
+  if (int rc = earl_mlp_policy_forward_cpu(pv->value, nullptr, rows, x.data(), nullptr, V.data())) return rc;
+  for_each_env(rows, [&](int i) {
+    bool nan_row = false;
+    for (int c = 0; c < 14; ++c) nan_row = nan_row || last_obs[(size_t)i * 14 + c] != last_obs[(size_t)i * 14 + c];
+    ret[i] = svalue_terminal(ret[i], d_H, V[i], nan_row);
   });
   return EARL_OK;
 }

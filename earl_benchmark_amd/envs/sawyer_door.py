@@ -344,16 +344,50 @@ class SawyerDoor(PhysicsEnv):
       cache[K] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
     return cache[K][1]
 
-  def rollout_branches(self, actions, K=None, clock=None):
+  def _plan_value(self, who, discount, value):
+    """-> None (discount 1.0 and no value network: the value-free entry points, called exactly as before those keywords existed) or the struct earl_plan_value of the
+    `_value` ones (include/earl_physics.h, "discount and a terminal value on the door and the peg"), with the network kept alive beside it"""
+    if value is None and float(discount) == 1.0:
+      return None
+    if not (float(discount) > 0.0 and float(discount) <= 1.0):
+      raise ValueError(f'{who}: discount = {discount}: 0 < discount <= 1')
+    if value is None:
+      return _abi.PlanValue(discount=float(discount), value=None)
+    from ..policy import GaussianMLPPolicy, MLPPolicy, require_widths
+    if not isinstance(value, MLPPolicy) or isinstance(value, GaussianMLPPolicy):
+      raise ValueError(f'{who}: value is an MLPPolicy(layers, hidden_act, out_act, obs_dim={self.OBS_DIM}, act_dim=1): a network from the observation to one number, '
+                       'without a Gaussian head')
+    require_widths(value, who, self.OBS_DIM, 1, env=self)
+    if value.param_dtype != torch.float32:
+      raise ValueError(f'{who}: the value network stores its parameters as {value.param_dtype}; float32 only (pass .widened()): no bf16 value network is built')
+    pv = _abi.PlanValue(discount=float(discount), value=C.pointer(value.struct))
+    pv._keep = value
+    return pv
+
+  def _value_ws(self, K, H):
+    """the workspace of a `_value` call (earl_sawyer_value_ws_bytes; H = 0: the branch launch's own): one device block, cached per (K, H) like _plan_ws"""
+    cache = self.__dict__.setdefault('_value_ws_cache', {})
+    if (K, H) not in cache:
+      need = C.c_int64(0)
+      _abi.check(self._lib.earl_sawyer_value_ws_bytes(self.nv, K, H, self.num_envs, C.byref(need)), 'earl_sawyer_value_ws_bytes')
+      block = torch.empty(max(need.value, 8) // 8 + 1, dtype=torch.float64, device=self.device)
+      cache[(K, H)] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
+    return cache[(K, H)][1]
+
+  def rollout_branches(self, actions, K=None, clock=None, discount=1.0, value=None):
     """K candidate action sequences of H steps scored per env FROM THE CURRENT STATE in one launch of the rollout kernel over K N virtual envs (include/earl_physics.h:
     earl_sawyer_branch_rollout): actions [K, H, N, 4] float32 -- or [H, N, 4] with K= for K replays of one block --
     -> {'ret' [K, N] float64, 'success' [K, N] bool (the success of step H - 1), 'first_success' [K, N] int32 (-1: none), 'last_obs' [K, N, 14] float64,
         'fail' [K, N] int32 (steps the failure guard rolled back)}.
     Row k is what rollout(actions[k]) would return next, reduced (ret = the float64 sum of its float32 rewards), lifelong goal draws included: every branch of an env
     sees the env's own draws.  The env is left exactly as found -- state, goals, counters, last_obs, fail_count: nothing happened to it.  What a shooting planner
-    (random shooting, CEM, MPPI) asks for.  clock: None, or the device address of the two uint64 words of earl_sawyer_rollout_clocked (a captured launch)."""
+    (random shooting, CEM, MPPI) asks for.  clock: None, or the device address of the two uint64 words of earl_sawyer_rollout_clocked (a captured launch).
+    discount=, value=: 'ret' becomes sum_t discount^t r_t + discount^H V(last_obs row) (earl_sawyer_branch_rollout_value): the sum in float64 in that order, a
+    rolled-back step adding 0 and still advancing the discount; `value` an MLPPolicy(layers, act, out_act, obs_dim=14, act_dim=1), float32, evaluated on the float32
+    rounding of the row by a kernel behind the rollout kernel; a row that holds a NaN gives a NaN.  The defaults make the call above, bit for bit."""
     a = torch.as_tensor(actions, device=self.device)
     n = self.num_envs
+    pv = self._plan_value('rollout_branches', discount, value)
     if K is None:
       if a.dim() != 4 or a.shape[2] != n or a.shape[3] != 4:
         raise ValueError(f'rollout_branches: actions must be [K, H, N, 4] = [K, H, {n}, 4], got {list(a.shape)} (one block for K branches: [H, {n}, 4] with K=)')
@@ -375,6 +409,12 @@ class SawyerDoor(PhysicsEnv):
     summary = _abi.EpisodeSummary(ret=res['ret'].data_ptr(), success_last=res['success'].data_ptr(), first_success=res['first_success'].data_ptr())
     self._cfg.step_counter = self.total_step_count
     with torch.cuda.device(self.device):
+      if pv is not None:
+        ws = self._value_ws(K, 0)
+        _abi.check(self._lib.earl_sawyer_branch_rollout_value(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, K, H, act.data_ptr(),
+                                                              stride, clock, C.byref(pv), C.byref(ws), C.byref(summary), res['last_obs'].data_ptr(),
+                                                              res['fail'].data_ptr(), self._stream()), 'earl_sawyer_branch_rollout_value')
+        return res
       ws = self._branch_ws(K)
       _abi.check(self._lib.earl_sawyer_branch_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, K, H, act.data_ptr(), stride,
                                                       clock, C.byref(ws), C.byref(summary), res['last_obs'].data_ptr(), res['fail'].data_ptr(), self._stream()),
@@ -417,7 +457,8 @@ class SawyerDoor(PhysicsEnv):
     return _abi.SawyerPlanParams(K=int(K), H=int(H), iterations=int(iterations), iteration0=int(iteration0), sigma=(C.c_float * 4)(*(s * 4 if len(s) == 1 else s)),
                                  noise_counter=nc & 0xFFFFFFFF, inv_temperature=1.0 / float(temperature))
 
-  def plan_mppi(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, clock=None, out=None):
+  def plan_mppi(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, clock=None, out=None, discount=1.0,
+                value=None):
     """`iterations` MPPI iterations on the device from the CURRENT state (include/earl_physics.h: earl_sawyer_plan_mppi): K candidates per env -- the mean plan itself and
     K - 1 copies with clipped Gaussian noise of scale `sigma` (a number or four: x, y, z, gripper) -- scored by the branch launch exactly as rollout_branches scores them,
     the mean moved to their average under the weights exp((ret - max ret) / temperature), in integer sums.  Per iteration three launches (candidates, the branch
@@ -428,8 +469,11 @@ class SawyerDoor(PhysicsEnv):
     `noise_counter=None` takes the low 32 bits of env.total_step_count, so successive control steps draw fresh noise (a captured call replays the noise it was captured
     with); `iteration0` numbers the first iteration (iterations in one call == as many calls of one, numbered on).  `out`: an optional dict of preallocated tensors under
     the same keys; a key that is missing or None is not computed, except 'ret' (the branch launch writes it), which is then allocated; out['plan'] may be the `mean`
-    tensor.  clock: as rollout_branches.  The env is left exactly as found -- state, goals, counters, last_obs, fail_count."""
+    tensor.  clock: as rollout_branches.  The env is left exactly as found -- state, goals, counters, last_obs, fail_count.
+    discount=, value=: the candidates are scored as rollout_branches(..., discount=, value=) scores them (earl_sawyer_plan_mppi_value) and nothing else changes; the
+    defaults make the call above, bit for bit."""
     m = self._plan_mean('plan_mppi', mean, horizon)
+    pv = self._plan_value('plan_mppi', discount, value)
     n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
     pp = self._plan_params('plan_mppi', K, H, I, iteration0, sigma, temperature, noise_counter)
     if K * n > INT32_MAX:
@@ -453,6 +497,12 @@ class SawyerDoor(PhysicsEnv):
         res['ret'] = torch.empty(K, n, dtype=torch.float64, **kw)
     self._cfg.step_counter = self.total_step_count
     with torch.cuda.device(self.device):
+      if pv is not None:
+        ws = self._value_ws(K, H)
+        _abi.check(self._lib.earl_sawyer_plan_mppi_value(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pp), C.byref(pv),
+                                                         m.data_ptr(), res['plan'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
+                                                         _ptr(res.get('best_k')), _ptr(res.get('fail')), clock, C.byref(ws), self._stream()), 'earl_sawyer_plan_mppi_value')
+        return res
       ws = self._plan_ws(K, H)
       _abi.check(self._lib.earl_sawyer_plan_mppi(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pp), m.data_ptr(),
                                                  res['plan'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')), _ptr(res.get('best_k')),
@@ -501,7 +551,7 @@ class SawyerDoor(PhysicsEnv):
     return t.to(torch.float32).contiguous()
 
   def plan_cem(self, mean=None, horizon=None, K=64, elites=8, iterations=1, sigma=0.3, std=None, alpha=0.0, std_min=0.0, std_max=2.0, iteration0=0, noise_counter=None,
-               clock=None, out=None):
+               clock=None, out=None, discount=1.0, value=None):
     """`iterations` cross-entropy iterations on the device from the CURRENT state (include/earl_physics.h: earl_sawyer_plan_cem): K candidates per env -- the mean plan
     itself and K - 1 copies with clipped Gaussian noise whose scale is a std per (step, env, dimension) -- scored by the branch launch exactly as rollout_branches
     scores them; the `elites` best (NaN last, return descending, k ascending; found by a radix select, linear in K) refit the mean AND the std, in integer sums, with
@@ -512,8 +562,10 @@ class SawyerDoor(PhysicsEnv):
      'fail' [K, N] int32 (steps of the last iteration the failure guard rolled back)}.
     `noise_counter`, `iteration0`, `clock` and `out` are plan_mppi's: a key of `out` that is missing or None is not computed, except 'ret' and 'std' (the call needs
     both), which are then allocated; out['plan'] may be the `mean` tensor and out['std'] the `std` tensor.  K goes to 8192, elites to min(K, 1024).  The env is left
-    exactly as found -- state, goals, counters, last_obs, fail_count."""
+    exactly as found -- state, goals, counters, last_obs, fail_count.
+    discount=, value=: as plan_mppi's (earl_sawyer_plan_cem_value): only the scores change; the defaults make the call above, bit for bit."""
     m = self._plan_mean('plan_cem', mean, horizon)
+    pv = self._plan_value('plan_cem', discount, value)
     n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
     cp = self._cem_params('plan_cem', K, H, I, iteration0, elites, sigma, alpha, std_min, std_max, noise_counter)
     s0 = self._cem_std('plan_cem', std, H)
@@ -539,6 +591,13 @@ class SawyerDoor(PhysicsEnv):
           res[k] = torch.empty(*want[k][0], dtype=want[k][1], **kw)
     self._cfg.step_counter = self.total_step_count
     with torch.cuda.device(self.device):
+      if pv is not None:
+        ws = self._value_ws(K, H)
+        _abi.check(self._lib.earl_sawyer_plan_cem_value(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(cp), C.byref(pv),
+                                                        m.data_ptr(), _ptr(s0), res['plan'].data_ptr(), res['std'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')),
+                                                        _ptr(res.get('best_ret')), _ptr(res.get('best_k')), _ptr(res.get('elite')), _ptr(res.get('fail')), clock,
+                                                        C.byref(ws), self._stream()), 'earl_sawyer_plan_cem_value')
+        return res
       ws = self._plan_ws(K, H)
       _abi.check(self._lib.earl_sawyer_plan_cem(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(cp), m.data_ptr(), _ptr(s0),
                                                 res['plan'].data_ptr(), res['std'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
@@ -561,7 +620,7 @@ class SawyerDoor(PhysicsEnv):
     return act
 
   def mpc_rollout(self, T, plan=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, noise_counter=None, out=None, method='mppi', elites=8, alpha=0.0,
-                  std_min=0.0, std_max=2.0):
+                  std_min=0.0, std_max=2.0, discount=1.0, value=None):
     """T steps of receding-horizon MPPI control, DEFINED as this composition of public methods (one call each per control step, no host synchronisation in the loop):
         P = plan.clone()  (None: zeros of [horizon, N, 4]);  nc0 = noise_counter  (None: the low 32 bits of env.total_step_count at entry)
         for s in range(T):
@@ -574,7 +633,8 @@ class SawyerDoor(PhysicsEnv):
     auto-reset, so a caller that wants episodes resets between calls.  `out`: an optional dict of preallocated [T, ...] tensors under rollout()'s keys.  A fused
     one-launch loop is not built for these envs (the score and the update would need a grid-wide join inside the stepper kernel).
     method='cem': the same composition with plan_cem(P, K=, elites=, iterations=, sigma=, std=None, alpha=, std_min=, std_max=, noise_counter=...) as its planner --
-    the std restarts from `sigma` at every control step, as on the tabletops, so there is no std to carry or shift; `temperature` is not read."""
+    the std restarts from `sigma` at every control step, as on the tabletops, so there is no std to carry or shift; `temperature` is not read.
+    discount=, value=: handed to the planner of every control step (both methods), which is all they change."""
     T = int(T)
     if T < 1:
       raise ValueError(f'mpc_rollout: T = {T}: at least one control step')
@@ -586,6 +646,7 @@ class SawyerDoor(PhysicsEnv):
       self._cem_params('mpc_rollout', K, H, I, 0, elites, sigma, alpha, std_min, std_max, noise_counter)
     else:
       self._plan_params('mpc_rollout', K, H, I, 0, sigma, temperature, noise_counter)
+    self._plan_value('mpc_rollout', discount, value)
     nc0 = self.total_step_count if noise_counter is None else int(noise_counter)
     kw = dict(device=self.device)
     res = self._new_out((T,)) if out is None else dict(out)
@@ -596,10 +657,10 @@ class SawyerDoor(PhysicsEnv):
     for s in range(T):
       if method == 'cem':
         self.plan_cem(P, K=K, elites=elites, iterations=I, sigma=sigma, alpha=alpha, std_min=std_min, std_max=std_max, noise_counter=(nc0 + s) & 0xFFFFFFFF,
-                      out={'plan': P, 'std': std, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]})
+                      out={'plan': P, 'std': std, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]}, discount=discount, value=value)
       else:
         self.plan_mppi(P, K=K, iterations=I, sigma=sigma, temperature=temperature, noise_counter=(nc0 + s) & 0xFFFFFFFF,
-                       out={'plan': P, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]})
+                       out={'plan': P, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]}, discount=discount, value=value)
       self.rollout(P[:1], out={k: res[k][s:s + 1] for k in rows})
       res['act'][s].copy_(P[0])
       if H > 1:

@@ -560,6 +560,51 @@ int32_t earl_sawyer_cem_candidates_cpu(const earl_sawyer_cfg* cfg, const earl_sa
 int32_t earl_sawyer_cem_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_params* params, int32_t j, const float* mean, const float* std_in, const float* act,
                                    const double* ret, float* plan, float* std, double* ret0_row, double* best_ret, int32_t* best_k, uint8_t* elite);
 
+/* ---- discount and a terminal value on the door and the peg: the branch launch and both planners with ret = sum_t gamma^t r_t + gamma^H V(o_H) ----
+ * Under the sparse reward the plain H-step sum is blind whenever the goal is more than H steps away (earl_tabletop.h, "discounted MPPI with a terminal value"); an env
+ * step here costs tens of thousands of cycles, so H stays short and the remedy matters more than on the tabletop.  Both parts travel in the tabletop's struct
+ * earl_plan_value.  For virtual env v = k n + i, with r_t, the rolled-back rule, success, first_success, fail and last_obs exactly as earl_sawyer_branch_rollout
+ * defines them:
+ *   discount   d_0 = 1.0, ret = 0.0; for t ascending: term = d_t * (double)r_t; ret = ret + term; d_{t+1} = d_t * gamma -- three float64 roundings per step, no fused
+ *              multiply-add (value_accumulate of csrc/tabletop_value.h).  A rolled-back step contributes r = 0 and still advances d.
+ *   terminal   ret = ret + d_H * (double)V(o_H), two float64 roundings.  o_H is the branch's last observation row exactly as `last_obs` returns it -- the patched goal
+ *              block of a goal switch, the repeated row of a rolled-back step, the env's own row of st->last_obs when step 0 diverges (NaN without one) --, each
+ *              double rounded to float32 as the closed-loop policy reads its rows.  V is evaluated under the policy contract (csrc/policy_math.h: acc = b_j; k ascending:
+ *              acc = fmaf(x_k, W_jk, acc); relu_f32 / tanh_f32, out_act last); earl_mlp_policy_forward_cpu with a 1-wide last layer and head = NULL states it on the host.
+ *              A row that holds a NaN gives ret = NaN whatever the network (relu_f32 would map a NaN pre-activation to 0 and hide it): the planners' "a NaN return
+ *              never wins" rules (MPPI item 7, CEM item 4) then apply unchanged.
+ *   network    pv->value: 14 -> hidden (-> hidden) -> 1, float32 (precision 0), no Gaussian head, hidden widths multiples of 16 up to 256 (the closed loop's
+ *              kPolicyMaxWidth: the 16 lanes of a virtual env evaluate it after the look-ahead, nothing is held in one lane's registers, so the tabletop's
+ *              EARL_PLAN_VALUE_MAX_H1 does not apply), params 16-byte aligned.  NULL: no terminal term.  With a network summary->ret is required.
+ *   identity   pv == NULL or {1.0, NULL}: the call IS the value-free entry point (it forwards; the workspace may then be that entry point's).  discount == 1.0 with a
+ *              network: the unchanged branch kernels followed by the value kernel, ret == plain ret + (double)V exactly.  Only discount != 1.0 reaches the rollout
+ *              kernel's discounted build (the same kernel text: csrc/physics_branch_value.hip, physics_branch_value_w8.hip), in all four launch forms; d_t travels
+ *              through [K n] words of the workspace beside ret, because nothing of a branch lives across a timestep and a time slice may be another wave's.
+ *   planners   earl_sawyer_plan_mppi_value / earl_sawyer_plan_cem_value: earl_sawyer_plan_mppi / earl_sawyer_plan_cem with item 3 ("scores") replaced by
+ *              earl_sawyer_branch_rollout_value and nothing else changed -- candidates, weights, elites, integer moments, chaining, non-finite rules, outputs.
+ *   ws         ONE size function for the three calls: earl_sawyer_value_ws_bytes(nv, K, H, n, &bytes) >= earl_sawyer_plan_ws_bytes(nv, K, H, n); H = 0 is what
+ *              earl_sawyer_branch_rollout_value needs (the branch launch's block and the [K n] discounts), H > 0 adds a planner's candidates.  Monotone in K, H and n,
+ *              0 for K n == 0.  No allocation and no host synchronisation; capture into a graph under the branch launch's rule.
+ * EARL_ERR_ARG before any HIP call for: everything the value-free entry point refuses; a discount that is NaN, <= 0 or > 1; a value network the rules above refuse
+ * (widths, a precision other than 0, the activation enums, dims[3] != 0 with one hidden layer, params NULL or misaligned); a network without summary->ret; a ws block
+ * that is NULL, misaligned or smaller than earl_sawyer_value_ws_bytes says.  There is no bf16 value network, no policy-prior branch and no fused control loop on these
+ * envs; the minitaur and the kitchen have no planner at all.
+ * Host twin (libearl_host.so; host pointers): earl_sawyer_value_terminal_cpu adds the terminal term to ret [rows] for given last_obs [rows, 14] -- d_H by the recurrence,
+ * the float32 rounding, the NaN rule and the two roundings through csrc/sawyer_value.h, the header the kernel uses; V by earl_mlp_policy_forward_cpu's loops.  pv->value
+ * NULL leaves ret as it is.  There is no host stepper, so the discounted sum itself has no twin.  Its refusals: pv, last_obs or ret NULL, rows < 0, H < 0, and pv's. */
+int earl_sawyer_value_ws_bytes(int32_t nv, int32_t K, int32_t H, int32_t n, int64_t* bytes);
+int earl_sawyer_branch_rollout_value(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                     int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_plan_value* pv,
+                                     const earl_sawyer_branch_ws* ws, const earl_episode_summary* summary, double* last_obs, int32_t* fail, earl_stream_t stream);
+int earl_sawyer_plan_mppi_value(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                const earl_sawyer_plan_params* params, const earl_plan_value* pv, const float* mean, float* plan, double* ret, double* ret0,
+                                double* best_ret, int32_t* best_k, int32_t* fail, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream);
+int earl_sawyer_plan_cem_value(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               const earl_sawyer_cem_params* params, const earl_plan_value* pv, const float* mean, const float* std0, float* plan, float* std, double* ret,
+                               double* ret0, double* best_ret, int32_t* best_k, uint8_t* elite, int32_t* fail, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
+                               earl_stream_t stream);
+int32_t earl_sawyer_value_terminal_cpu(const earl_plan_value* pv, int32_t H, int32_t rows, const double* last_obs, double* ret);
+
 /* The policy contract on the host (libearl_host.so; host pointers): actions [n, A] of n observation rows obs [n, dims[0]], dims[0] in 1..256, hidden widths in 1..256,
  * the last layer A wide (head = NULL) or 2 A wide (rows 0..A-1 the mean, A..2A-1 the raw log_std), A >= 1.  eps [n, A] = the standard-normal draws to use with a
  * head in EARL_HEAD_SAMPLE mode; NULL (or EARL_HEAD_MEAN, or no head) evaluates the mean / the deterministic policy.  policy->out_act is applied last, as on the

@@ -154,6 +154,10 @@ class SawyerCemParams(C.Structure):    # struct earl_sawyer_cem_params (include/
               ('noise_counter', C.c_uint32), ('alpha', C.c_float), ('std_min', C.c_float), ('std_max', C.c_float)]
 
 
+class SawyerPlanPrior(C.Structure):    # struct earl_sawyer_plan_prior (include/earl_physics.h): the LAST `branches` of the K candidates are a policy's closed-loop rollouts
+  _fields_ = [('policy', C.POINTER(MlpPolicy)), ('branches', C.c_int32), ('sigma', C.c_float * 4), ('obs0', C.c_void_p), ('act', C.c_void_p)]
+
+
 SAWYER_PLAN_MAX_K = 8192   # EARL_SAWYER_PLAN_MAX_K
 SAWYER_CEM_MAX_E = 1024    # EARL_SAWYER_CEM_MAX_E
 SAWYER_INFO = 8       # EARL_SAWYER_INFO; slots EARL_INFO_* (include/earl_physics.h)
@@ -265,6 +269,7 @@ SIGNATURES = {
     'earl_debug_set_physics_lanes': [C.c_int],
     'earl_debug_set_door_variant': [C.c_int],
     'earl_debug_set_peg_schedule': [C.c_int],
+    'earl_debug_set_sawyer_prior_launches': [C.c_int],
     'earl_kitchen_step': [C.c_void_p, C.c_void_p, _P(KitchenParams), _P(KitchenCfg), _P(KitchenState), C.c_void_p, _P(KitchenOut), C.c_void_p],
     'earl_kitchen_rollout': [C.c_void_p, C.c_void_p, _P(KitchenParams), _P(KitchenCfg), _P(KitchenState), C.c_void_p, C.c_int32, _P(KitchenOut), C.c_void_p],
     'earl_sawyer_rollout': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), C.c_void_p, C.c_int32, _P(SawyerOut), C.c_void_p],
@@ -309,6 +314,15 @@ SIGNATURES = {
                                    + [_P(SawyerBranchWs), C.c_void_p],
     'earl_sawyer_plan_cem_value': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(SawyerCemParams), _P(PlanValue)] + [C.c_void_p] * 11
                                   + [_P(SawyerBranchWs), C.c_void_p],
+    # the same three with policy-prior branches (struct earl_sawyer_plan_prior after pv; the branch launch also takes the iteration j and the noise counter of the prior
+    # branches' noise words, and WRITES the last `branches` blocks of act); one size function (nv, K, H, n; H = 0: the branch launch's own)
+    'earl_sawyer_prior_ws_bytes': [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int64)],
+    'earl_sawyer_branch_rollout_prior': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                         _P(PlanValue), _P(SawyerPlanPrior), C.c_int32, C.c_uint32, _P(SawyerBranchWs), _P(EpisodeSummary), C.c_void_p, C.c_void_p, C.c_void_p],
+    'earl_sawyer_plan_mppi_prior': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(SawyerPlanParams), _P(PlanValue), _P(SawyerPlanPrior)]
+                                   + [C.c_void_p] * 8 + [_P(SawyerBranchWs), C.c_void_p],
+    'earl_sawyer_plan_cem_prior': [C.c_void_p, C.c_void_p, C.c_int32, _P(SawyerCfg), _P(SawyerState), _P(SawyerCemParams), _P(PlanValue), _P(SawyerPlanPrior)]
+                                  + [C.c_void_p] * 11 + [_P(SawyerBranchWs), C.c_void_p],
     # the closed loop inside the minitaur rollout kernels: policy, head (NULL: deterministic), obs0, T, clock, actions before `out`
     'earl_minitaur_policy_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, _P(MinitaurOut), C.c_void_p],
@@ -387,6 +401,8 @@ HOST_EXTRA_SIGNATURES = {
     'earl_sawyer_cem_update_cpu': ([_P(SawyerCfg), _P(SawyerCemParams), C.c_int32] + [C.c_void_p] * 10, C.c_int32),
     # the host twin of the planners' value kernel: pv, H, rows, last_obs [rows, 14], ret [rows] (the terminal term is added in place)
     'earl_sawyer_value_terminal_cpu': ([_P(PlanValue), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
+    # the host twin of a prior branch's per-row arithmetic: cfg, prior, H, k, j, noise_counter, cem, obs [H, n, 14], act [H, n, 4]
+    'earl_sawyer_prior_actions_cpu': ([_P(SawyerCfg), _P(SawyerPlanPrior), C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
     'earl_tanh_f32': ([C.c_float], C.c_float),
     'earl_exp_f32': ([C.c_float], C.c_float),
     'earl_normal_quantile_f32': ([C.c_uint32], C.c_float),

@@ -4,6 +4,7 @@
 #include "physics_stepper.h"
 #include "policy_check.h"
 #include "policy_math.h"
+#include "sawyer_prior.h"
 
 #include <mutex>
 #include <unordered_map>
@@ -51,6 +52,7 @@ namespace {
 int g_peg_sliced = 1;     // earl_debug_set_peg_schedule
 int g_door_variant = 0;   // earl_debug_set_door_variant: 0 = by batch size, 1 = four single-wave workgroups per CU, 2 = one eight-wave workgroup per CU
 int g_lpe = 16;   // lanes per env (earl_debug_set_physics_lanes): 16 = four envs per wavefront, 64 = one wavefront per env
+int g_prior_fused = 1;   // earl_debug_set_sawyer_prior_launches: 1 = the prior branches of earl_sawyer_branch_rollout_prior inside ONE launch over all K n virtual envs (default), 0 = a launch of their own behind the plain one
 
 template <int NV, bool INTEGRATE>
 void launch_physics(const PArgs& a, hipStream_t st) {
@@ -238,10 +240,17 @@ int earl_sawyer_branch_ws_bytes(int32_t nv, int32_t K, int32_t n, int64_t* bytes
 }
 // the body of earl_sawyer_branch_rollout.  gamma NULL: the plain sum, the kernels of physics_branch.hip / physics_branch_w8.hip.  gamma given
 // (earl_sawyer_branch_rollout_value with discount != 1, sawyer_value.hip): the discounted sum, the same kernel text built with EARL_BRANCH_DISCOUNT
-// (physics_branch_value.hip / physics_branch_value_w8.hip), `disc` the [K n] words of the caller's block that carry d_t; same checks, same forms, same replicate kernel
+// (physics_branch_value.hip / physics_branch_value_w8.hip), `disc` the [K n] words of the caller's block that carry d_t; same checks, same forms, same replicate kernel.
+// pr NULL: ONE launch over all K n virtual envs, as ever.  pr given (earl_sawyer_branch_rollout_prior with P = pr->prior->branches >= 1, sawyer_value.hip; `disc` is then
+// required, the prior kernels being built with the discounted sum): by default still ONE launch, of sawyer_prior_rollout_kernel (physics_branch_prior.hip /
+// physics_branch_prior_w8.hip), in which the branches in front of K - P load their action; under earl_debug_set_sawyer_prior_launches(2) TWO launches on the caller's stream
+// over two contiguous ranges of v = k n + i -- the plain (or discounted) kernels over the first (K - P) n, then the prior kernel over the last P n, every row pointer
+// advanced here.  Each range has its replicate launch, its form by its own count of virtual envs and its own work queue (a queue's progress words end at T: the second
+// launch cannot reuse the first's).  The one-launch shape measured 1.5 - 1.9 x faster where K n fits one round of waves; the shapes give the same bits
 static int sawyer_branch_launch(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                 int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
-                                const earl_episode_summary* summary, double* last_obs, int32_t* fail, const double* gamma, double* disc, earl_stream_t stream) {
+                                const earl_episode_summary* summary, double* last_obs, int32_t* fail, const double* gamma, double* disc, const earl::SawyerPriorLaunch* pr,
+                                earl_stream_t stream) {
   const earl_sawyer_out none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (!model || !cfg || !st || !act || !ws || K < 0 || H < 0 || (nv != 10 && nv != 15) || !sawyer_args_ok(kStep, cfg, st, nv, &none)) return EARL_ERR_ARG;
   const int n = cfg->n;
@@ -251,54 +260,84 @@ static int sawyer_branch_launch(const earl_link_model* model, const earl_collisi
   if (V > INT32_MAX) return EARL_ERR_ARG;
   if (V > 0 && (!ws->base || (reinterpret_cast<uintptr_t>(ws->base) & 7) != 0 || ws->bytes < sawyer_branch_bytes(nv, V))) return EARL_ERR_ARG;
   if (g_lpe == 64) return EARL_ERR_ARG;                   // (the 64-lane measurement builds: no branch form)
+  const int P = pr ? pr->prior->branches : 0;
+  if (pr && (P < 1 || P >= K || !disc || !pr->sched || (act_branch_stride == 0 && H > 0))) return EARL_ERR_ARG;      // (checked by the entry point: sawyer_value.hip)
   if (V == 0 || H == 0) return EARL_OK;
   if (int rc = check_cone(col, true, (hipStream_t)stream, "sawyer_branch_rollout")) return rc;
-  double* d = static_cast<double*>(ws->base);
-  earl_sawyer_state vs{};                                 // the virtual envs' state: the workspace's rows (steps_since_reset, last_obs, fail_count: NULL, a branch keeps none)
-  vs.qpos = d; d += V * (nv + 1);
-  vs.qvel = d; d += V * nv;
-  vs.mocap_pos = d; d += V * 3;
-  vs.goal = d; d += V * 7;
-  double* const rows = d; d += V * 14;
-  int32_t* w = reinterpret_cast<int32_t*>(d);
-  vs.steps_since_goal_change = cfg->goal_change_frequency > 0 ? w : nullptr; w += V;
-  vs.obj_init = st->obj_init;                             // (read only, indexed by the env: v % n)
-  SawyerBranchValueArgs a;                                // (the plain kernels read its base, the SawyerBranchArgs)
-  a.gamma = gamma ? *gamma : 1.0;
-  a.br_disc = disc;
-  static_cast<SawyerArgs&>(a) = SawyerArgs{model, col, *cfg, vs, act, H, none, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
-  a.cfg.n = (int)V;
-  a.n_env = n;
-  a.act_stride = act_branch_stride;
-  a.obs_row = last_obs ? last_obs : rows;
-  a.br_ret = summary ? summary->ret : nullptr;
-  a.br_last = summary ? summary->success_last : nullptr;
-  a.br_first = summary ? summary->first_success : nullptr;
-  a.br_fail = fail;
-  // the form by the number of virtual envs, with the closed loop's reading of the door variants; the queue is always there, so the peg's time-sliced form is sawyer_form's to choose
-  a.st.sched = w;
-  const SawyerForm form = sawyer_form(nv, (int)V, H, &a.st, true);
-  if (form == SawyerForm::PegSliced) a.slice = peg_slice();
-  else a.st.sched = nullptr;                              // (the replicate kernel clears the queue only where it is used)
-  if (int rc = earl_unit_branch_replicate(static_cast<const SawyerBranchArgs*>(&a), st, nv, stream)) return rc;
-  if (gamma)
-    switch (form) {
-      case SawyerForm::DoorW8: return earl_unit_branch_value_w8_sawyer_rollout(&a, stream);
-      case SawyerForm::Door: case SawyerForm::Peg: return earl_unit_branch_value_sawyer_rollout(&a, nv, 0, stream);
-      case SawyerForm::PegSliced: return earl_unit_branch_value_sawyer_rollout(&a, nv, 1, stream);
-      default: return EARL_ERR_ARG;
+  // the carve of the whole call's block, whatever the ranges: [V, nv + 1] qpos, [V, nv] qvel, [V, 3] mocap_pos, [V, 7] goal, [V, 14] rows, then the int32 words
+  double* const base = static_cast<double*>(ws->base);
+  int32_t* const words = reinterpret_cast<int32_t*>(base + V * (int64_t)(nv + 1 + nv + 3 + 7 + 14));
+  // one launch over the virtual envs v0 .. v0 + Vr - 1 (whole branches: v0 a multiple of n, so v % n is the env inside the range too), `prior`: by the policy
+  const int64_t k_first = K - P;                          // the call's first prior branch
+  auto run = [&](const int64_t v0, const int64_t Vr, int32_t* const sched, const bool prior) -> int {
+    double* d = base;
+    earl_sawyer_state vs{};                               // the virtual envs' state: the workspace's rows (steps_since_reset, last_obs, fail_count: NULL, a branch keeps none)
+    vs.qpos = d + v0 * (nv + 1); d += V * (nv + 1);       // (rows of the model's nq <= nv + 1: a range's rows start where rows of nv + 1 would, and stay inside the block)
+    vs.qvel = d + v0 * nv; d += V * nv;
+    vs.mocap_pos = d + v0 * 3; d += V * 3;
+    vs.goal = d + v0 * 7; d += V * 7;
+    double* const rows = d + v0 * 14;
+    vs.steps_since_goal_change = cfg->goal_change_frequency > 0 ? words + v0 : nullptr;
+    vs.obj_init = st->obj_init;                           // (read only, indexed by the env: v % n)
+    SawyerBranchPriorArgs a{};                            // (the plain kernels read its base, the SawyerBranchArgs; the discounted ones the SawyerBranchValueArgs)
+    a.gamma = gamma ? *gamma : 1.0;
+    a.br_disc = disc ? disc + v0 : nullptr;
+    static_cast<SawyerArgs&>(a) = SawyerArgs{model, col, *cfg, vs, act + (v0 / n) * act_branch_stride, H, none, nullptr, nullptr, nullptr, nullptr, 0, 0, clock};
+    a.cfg.n = (int)Vr;
+    a.n_env = n;
+    a.act_stride = act_branch_stride;
+    a.obs_row = last_obs ? last_obs + v0 * 14 : rows;
+    a.br_ret = summary && summary->ret ? summary->ret + v0 : nullptr;
+    a.br_last = summary && summary->success_last ? summary->success_last + v0 : nullptr;
+    a.br_first = summary && summary->first_success ? summary->first_success + v0 : nullptr;
+    a.br_fail = fail ? fail + v0 : nullptr;
+    if (prior) {
+      a.pol = *pr->prior->policy;
+      a.obs0 = pr->prior->obs0;
+      a.prior_act = pr->prior->act;
+      for (int k = 0; k < 4; ++k) a.sigma[k] = pr->prior->sigma[k];
+      a.word0 = pr->word0;
+      a.noise_counter = pr->noise_counter;
+      a.k0 = (int)(k_first - v0 / n);
+      a.kbase = (int)(v0 / n);
     }
-  switch (form) {
-    case SawyerForm::DoorW8: return earl_unit_branch_w8_sawyer_rollout(static_cast<const SawyerBranchArgs*>(&a), stream);
-    case SawyerForm::Door: case SawyerForm::Peg: return earl_unit_branch_sawyer_rollout(static_cast<const SawyerBranchArgs*>(&a), nv, 0, stream);
-    case SawyerForm::PegSliced: return earl_unit_branch_sawyer_rollout(static_cast<const SawyerBranchArgs*>(&a), nv, 1, stream);
-    default: return EARL_ERR_ARG;                         // (L64 was refused above; the policy reading never gives DoorSliced)
-  }
+    // the form by the number of virtual envs of THIS launch, with the closed loop's reading of the door variants; the queue is always there, so the peg's time-sliced form is sawyer_form's to choose
+    a.st.sched = sched;
+    const SawyerForm form = sawyer_form(nv, (int)Vr, H, &a.st, true);
+    if (form == SawyerForm::PegSliced) a.slice = peg_slice();
+    else a.st.sched = nullptr;                            // (the replicate kernel clears the queue only where it is used)
+    if (int rc = earl_unit_branch_replicate(static_cast<const SawyerBranchArgs*>(&a), st, nv, stream)) return rc;
+    if (prior)
+      switch (form) {
+        case SawyerForm::DoorW8: return earl_unit_branch_prior_w8_sawyer_rollout(&a, stream);
+        case SawyerForm::Door: case SawyerForm::Peg: return earl_unit_branch_prior_sawyer_rollout(&a, nv, 0, stream);
+        case SawyerForm::PegSliced: return earl_unit_branch_prior_sawyer_rollout(&a, nv, 1, stream);
+        default: return EARL_ERR_ARG;
+      }
+    if (gamma)
+      switch (form) {
+        case SawyerForm::DoorW8: return earl_unit_branch_value_w8_sawyer_rollout(static_cast<const SawyerBranchValueArgs*>(&a), stream);
+        case SawyerForm::Door: case SawyerForm::Peg: return earl_unit_branch_value_sawyer_rollout(static_cast<const SawyerBranchValueArgs*>(&a), nv, 0, stream);
+        case SawyerForm::PegSliced: return earl_unit_branch_value_sawyer_rollout(static_cast<const SawyerBranchValueArgs*>(&a), nv, 1, stream);
+        default: return EARL_ERR_ARG;
+      }
+    switch (form) {
+      case SawyerForm::DoorW8: return earl_unit_branch_w8_sawyer_rollout(static_cast<const SawyerBranchArgs*>(&a), stream);
+      case SawyerForm::Door: case SawyerForm::Peg: return earl_unit_branch_sawyer_rollout(static_cast<const SawyerBranchArgs*>(&a), nv, 0, stream);
+      case SawyerForm::PegSliced: return earl_unit_branch_sawyer_rollout(static_cast<const SawyerBranchArgs*>(&a), nv, 1, stream);
+      default: return EARL_ERR_ARG;                       // (L64 was refused above; the policy reading never gives DoorSliced)
+    }
+  };
+  if (!pr) return run(0, V, words + V, false);
+  if (g_prior_fused) return run(0, V, words + V, true);   // ONE launch over all K n: the branches in front of K - P load their action inside the prior kernel
+  const int64_t V1 = (int64_t)(K - P) * n;
+  if (int rc = run(0, V1, words + V, false)) return rc;
+  return run(V1, V - V1, pr->sched, true);
 }
 int earl_sawyer_branch_rollout(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
                                const earl_episode_summary* summary, double* last_obs, int32_t* fail, earl_stream_t stream) {
-  return sawyer_branch_launch(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, ws, summary, last_obs, fail, nullptr, nullptr, stream);
+  return sawyer_branch_launch(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, ws, summary, last_obs, fail, nullptr, nullptr, nullptr, stream);
 }
 // for sawyer_value.hip (declared there: it includes no stepper header): the launch above with the discounted sum, and where the [K n, 14] carried observation rows of
 // a branch workspace start -- the rows the launch used when the caller gave no last_obs (the carve in sawyer_branch_launch: qpos, qvel, mocap_pos and goal rows before them)
@@ -307,7 +346,17 @@ __attribute__((visibility("hidden"))) int earl_unit_sawyer_branch_discounted(con
                                                                              const uint64_t* clock, const earl_sawyer_branch_ws* ws, const earl_episode_summary* summary,
                                                                              double* last_obs, int32_t* fail, double gamma, double* disc, earl_stream_t stream) {
   if (!disc) return EARL_ERR_ARG;
-  return sawyer_branch_launch(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, ws, summary, last_obs, fail, &gamma, disc, stream);
+  return sawyer_branch_launch(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, ws, summary, last_obs, fail, &gamma, disc, nullptr, stream);
+}
+// ... and with the last pr->prior->branches branches run by the policy (earl_sawyer_branch_rollout_prior, sawyer_value.hip, which owns the checks of `pr`): gamma == 1.0
+// runs the first range through the plain kernels, as the value-free call would; the prior kernels take gamma as it is.  The candidates are written, hence float*
+__attribute__((visibility("hidden"))) int earl_unit_sawyer_branch_prior(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg,
+                                                                        const earl_sawyer_state* st, int32_t K, int32_t H, float* act, int64_t act_branch_stride,
+                                                                        const uint64_t* clock, const earl_sawyer_branch_ws* ws, const earl_episode_summary* summary,
+                                                                        double* last_obs, int32_t* fail, double gamma, double* disc, const earl::SawyerPriorLaunch* pr,
+                                                                        earl_stream_t stream) {
+  if (!disc || !pr || !pr->prior) return EARL_ERR_ARG;
+  return sawyer_branch_launch(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, ws, summary, last_obs, fail, gamma == 1.0 ? nullptr : &gamma, disc, pr, stream);
 }
 __attribute__((visibility("hidden"))) double* earl_unit_sawyer_branch_rows(int32_t nv, int64_t V, void* base) {
   return static_cast<double*>(base) + V * (int64_t)(nv + 1 + nv + 3 + 7);
@@ -374,6 +423,11 @@ int earl_sawyer_cfg_size(void) { return (int)sizeof(earl_sawyer_cfg); }
 int earl_debug_set_peg_schedule(int sliced) {          // 0: one group per wave; 1: time-sliced, EARL_PEG_SLICE env steps per item; k >= 2: time-sliced, k env steps per item
   if (sliced < 0) return EARL_ERR_ARG;
   g_peg_sliced = sliced;
+  return EARL_OK;
+}
+int earl_debug_set_sawyer_prior_launches(int launches) {      // 1 (default): the prior branches inside ONE launch over all K n virtual envs; 2: a launch of their own behind the plain one
+  if (launches != 1 && launches != 2) return EARL_ERR_ARG;
+  g_prior_fused = launches == 1;
   return EARL_OK;
 }
 int earl_debug_set_door_variant(int v) {

@@ -45,6 +45,27 @@ struct SawyerBranchValueArgs : SawyerBranchArgs {
 #endif
 constexpr bool kBranchDiscount = EARL_BRANCH_DISCOUNT != 0;
 using SawyerBranchKernelArgs = std::conditional<kBranchDiscount, SawyerBranchValueArgs, SawyerBranchArgs>::type;
+// earl_sawyer_branch_rollout_prior (include/earl_physics.h, "policy-prior branches on the door and the peg"): the discounted block followed by the policy of the prior
+// branches and their noise.  A derived struct once more.  Virtual env v of the launch is branch kbase + v / n_env of the call; the launch's branches from k0 on are the
+// policy's (their block of `action` is written here, not read), those before it load their action as a plain branch does.  Two launch shapes use it (physics.hip):
+// ONE launch over all K n virtual envs (kbase = 0, k0 = K - P), or a launch over the last P n only, every row pointer advanced on the host (kbase = K - P, k0 = 0).
+struct SawyerBranchPriorArgs : SawyerBranchValueArgs {
+  earl_mlp_policy pol;           // 14 -> H1 (-> H2) -> 4, float32, one network
+  const double* obs0;            // [n_env, 14]: what the policy sees at step 0
+  float* prior_act;              // NULL or [P, T, n_env, 4]: the action rows once more (act_stride is the candidates' own)
+  float sigma[4];
+  uint32_t word0;                // the planner's draw word | the iteration (kPlanDraw | j, kCemDraw | j)
+  uint32_t noise_counter;
+  int k0;                        // the launch's first prior branch
+  int kbase;                     // the call's index of the launch's branch 0 (the noise words are keyed by the call's k)
+};
+// EARL_BRANCH_PRIOR: set by physics_branch_prior.hip and physics_branch_prior_w8.hip only (with EARL_BRANCH_DISCOUNT: gamma == 1 gives the plain sum's bits, 1.0 * r_t
+// and d * 1.0 being exact); it switches the branch pieces of the rollout body to the policy phase below and defines the fourth kernel, sawyer_prior_rollout_kernel
+#ifndef EARL_BRANCH_PRIOR
+#define EARL_BRANCH_PRIOR 0
+#endif
+constexpr bool kBranchPrior = EARL_BRANCH_PRIOR != 0;
+static_assert(!kBranchPrior || kBranchDiscount, "the prior kernels are built with the discounted sum");
 
 // Work queue of the time-sliced rollout (earl_sawyer_state.sched: progress[G] then lock[G], zero on entry).  An env group's state is in HBM after every env
 // step (the failure guard's "last stable state"), so ANY wave can take the group's next slice of env steps; a wave claims the unlocked group that has come
@@ -366,6 +387,10 @@ __device__ __forceinline__ void sawyer_branch_summary(const int t, const int v, 
 
 #ifndef EARL_WAVES_PER_EU
 #define EARL_WAVES_PER_EU 1
+#endif
+// the policy phase and the kernel of the prior branches (the units built with EARL_BRANCH_PRIOR only): a file of their own, which holds the FOURTH inclusion of the rollout body
+#if EARL_BRANCH_PRIOR
+#include "physics_env_sawyer_prior.inc"
 #endif
 // SLICED: the launch's work is a queue of (env group, slice of a.slice env steps) items (sched_claim above) taken by persistent waves, instead of one
 // whole rollout of one group per wave

@@ -1,8 +1,9 @@
 // physics_env_sawyer_rollout.inc -- the body of the Sawyer door / peg rollout kernels (physics_env_sawyer.h): sawyer_rollout_kernel includes it with POLICY = false
 // (every action given), sawyer_policy_rollout_kernel with POLICY = true (the action of env step t computed by the env's own 16 lanes from the observation the env
 // last emitted), sawyer_branch_rollout_kernel with BRANCH = true (the K n virtual envs of earl_sawyer_branch_rollout: `a.cfg.n` is their number, `env` a virtual env, the rows
-// of `a.st` the workspace's; actions given per branch, no [T] row written, per-branch summaries).  Template parameters NV, LPE, SLICED and the kernel argument `a` are
-// the including kernel's.
+// of `a.st` the workspace's; actions given per branch, no [T] row written, per-branch summaries), sawyer_prior_rollout_kernel with BRANCH = true in the units built with
+// EARL_BRANCH_PRIOR (the action of a prior branch computed by the policy on the row the virtual env carries).  Template parameters NV, LPE, SLICED and the kernel argument
+// `a` are the including kernel's.
   static_assert(LPE >= 14, "the observation is written by 14 lanes");
   constexpr int EPW = 64 / LPE, WPB = Lim<NV>::WPB;
   __shared__ alignas(16) typename ModelOf<NV>::T m;
@@ -42,7 +43,12 @@
   RSTART();
   for (int t = t_begin; t < t_end; ++t) {
     float4 act;
+#if EARL_BRANCH_PRIOR
+    // (sawyer_prior_rollout_kernel: a prior branch's action is the policy's on the row the branch carries, plus the planner's noise; it is stored where a plain branch loads it)
+    if constexpr (BRANCH) act = sawyer_prior_step_action(t, env, sub, live);
+#else
     if constexpr (BRANCH) act = sawyer_branch_action(t, env);      // (`env` is the virtual env v, `n` their number K n_env: see SawyerBranchArgs)
+#endif
     else act = sawyer_step_action<POLICY>(a, t, n, env, sub, live);
     // set_xyz_action [UPSTREAM]: clip, float32 product with the scale, float64 add, box clip
     const float cx = fminf(fmaxf(act.x, -1.f), 1.f) * scale, cy = fminf(fmaxf(act.y, -1.f), 1.f) * scale, cz = fminf(fmaxf(act.z, -1.f), 1.f) * scale;
@@ -60,7 +66,7 @@
       // lane: eight-wave door build 296 -> 212 B, peg 36 -> 0 B).  (Doing the same to the block pointer hides that it is an LDS address: 640 B.)
       // (Small model only: the peg build, with 512 registers, loses 2 % to the recomputation although its last 36 B of scratch go too.)
       int sub_ = sub, grp_ = grp;
-      if constexpr (POLICY) {
+      if constexpr (POLICY || (BRANCH && kBranchPrior)) {
         // (the policy phase is a call: what lives across it sits in the callee-saved registers or is spilled around it, and the allocator chose `sub` -- reloaded
         // here, at the head of every timestep.  The lane's index costs two instructions to read again and nothing to keep.)
         const int lane_ = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));

@@ -30,6 +30,10 @@ extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_w8_sawyer_
 // the same launch with the discounted sum (physics_branch_value.hip, physics_branch_value_w8.hip): the argument is a SawyerBranchValueArgs; the replicate kernel is the one above
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_value_sawyer_rollout(const void* sawyer_branch_value_args, int nv, int sliced, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_value_w8_sawyer_rollout(const void* sawyer_branch_value_args, void* stream);
+// the branch launch whose actions are a policy's (physics_branch_prior.hip, physics_branch_prior_w8.hip): the argument is a SawyerBranchPriorArgs over all K n virtual envs
+// of a call, or over the last P branches with its rows advanced by physics.hip; the replicate kernel is the one above
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_prior_sawyer_rollout(const void* sawyer_branch_prior_args, int nv, int sliced, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_branch_prior_w8_sawyer_rollout(const void* sawyer_branch_prior_args, void* stream);
 extern "C" int earl_sawyer_rollout_door_w8(const earl_link_model* model, const earl_collision_model* col, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                            const float* action, int32_t T, const earl_sawyer_out* out, earl_stream_t stream);
 

@@ -15,6 +15,9 @@
 
 #include "sawyer_plan.h"
 #include "sawyer_value.h"   // the rules of earl_plan_value on these envs (earl_sawyer_plan_mppi_value)
+#include "sawyer_prior.h"   // the rules of earl_sawyer_plan_prior and the `_prior` block (earl_sawyer_plan_mppi_prior)
+
+static_assert(earl::kSawyerPriorDraw == earl::kPlanDraw, "earl_sawyer_branch_rollout_prior draws the noise of MPPI's branch k");
 
 using namespace earl;
 using namespace earl::hostside;
@@ -147,19 +150,31 @@ namespace {
 // The body of earl_sawyer_plan_mppi and earl_sawyer_plan_mppi_value.  pv NULL (the value-free entry point, and `_value` with pv NULL or {1.0, NULL}): item 3 is
 // earl_sawyer_branch_rollout, the block earl_sawyer_plan_ws_bytes'.  Otherwise item 3 is earl_sawyer_branch_rollout_value (sawyer_value.hip) and the block
 // earl_sawyer_value_ws_bytes': that call's [K n] discounts sit between the branch launch's rows and the candidates.  Nothing else differs.
+// prior NULL: as above.  Otherwise (earl_sawyer_plan_mppi_prior with branches >= 1; pv as the caller gave it, NULL included) item 3 is earl_sawyer_branch_rollout_prior's
+// body with this planner's draw word, which OVERWRITES the last `branches` blocks of the candidates the kernel above it wrote; the block is earl_sawyer_prior_ws_bytes'.
+// The update kernel reads the candidates back and does not know.
 int plan_mppi(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
-              const earl_sawyer_plan_params* params, const earl_plan_value* pv, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k,
-              int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream) {
+              const earl_sawyer_plan_params* params, const earl_plan_value* pv, const earl_sawyer_plan_prior* prior, const float* mean, float* plan, double* ret, double* ret0,
+              double* best_ret, int32_t* best_k, int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream) {
   if (int rc = check_sawyer_plan(SawyerPlanCall::Mppi, cfg, params, 0, mean, plan)) return rc;
   if (int rc = check_sawyer_value(pv, g_err)) return rc;
+  if (prior) {
+    const uint64_t rows = (uint64_t)params->H * (uint64_t)cfg->n * 16u;
+    const void* const in[4] = {mean, plan, nullptr, nullptr};
+    const uint64_t in_bytes[4] = {rows, rows, 0, 0};
+    if (int rc = check_sawyer_prior(prior, params->K, params->H, cfg->n, in, in_bytes, g_err)) return rc;
+    if (prior->branches == 0) prior = nullptr;                                        // (the identity: from here on the `_value` call, launch for launch)
+  }
   if (!ret) return fail(EARL_ERR_ARG, "ret is NULL: the branch launch writes it and the update reads it");
   if (!ws) return fail(EARL_ERR_ARG, "ws is NULL");
   const int n = cfg->n, K = params->K, H = params->H;
   int64_t branch = 0, need = 0;
-  if (earl_sawyer_branch_ws_bytes(nv, K, n, &branch) || (pv ? earl_sawyer_value_ws_bytes(nv, K, H, n, &need) : earl_sawyer_plan_ws_bytes(nv, K, H, n, &need)))
+  if (earl_sawyer_branch_ws_bytes(nv, K, n, &branch) ||
+      (prior ? earl_sawyer_prior_ws_bytes(nv, K, H, n, &need) : (pv ? earl_sawyer_value_ws_bytes(nv, K, H, n, &need) : earl_sawyer_plan_ws_bytes(nv, K, H, n, &need))))
     return fail(EARL_ERR_ARG, "nv = %d: 10 (door) or 15 (peg)", nv);
   branch = round_up(branch, 8);
-  const int64_t scored = pv ? branch + (int64_t)K * n * 8 : branch;                   // (what the scoring call takes of the block: earl_sawyer_value_ws_bytes with H = 0)
+  // (what the scoring call takes of the block: earl_sawyer_prior_ws_bytes / earl_sawyer_value_ws_bytes with H = 0)
+  const int64_t scored = prior ? sawyer_prior_scored_bytes(branch, (int64_t)K * n) : (pv ? branch + (int64_t)K * n * 8 : branch);
   if (n > 0 && (!ws->base || (reinterpret_cast<uintptr_t>(ws->base) & 7) != 0 || ws->bytes < need))
     return fail(EARL_ERR_ARG, "ws: base %p (8-byte aligned), %lld bytes of the %lld needed", ws->base, (long long)ws->bytes, (long long)need);
   const earl_sawyer_branch_ws bws{ws->base, branch};
@@ -182,6 +197,11 @@ int plan_mppi(const earl_link_model* model, const earl_collision_model* col, int
     p.best_ret = last ? best_ret : nullptr;
     p.best_k = last ? best_k : nullptr;
     if (int rc = launch_candidates(p, act, (hipStream_t)stream)) return rc;
+    if (prior) {
+      if (int rc = earl_unit_sawyer_branch_scored_prior(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, pv, prior, p.word0, p.noise_counter, &vws, &sum, nullptr,
+                                                        last ? fail_count : nullptr, stream))
+        return rc == EARL_ERR_ARG ? rc : fail(rc, "earl_sawyer_branch_rollout_prior failed in iteration %d", params->iteration0 + it);
+    } else
     if (int rc = pv ? earl_sawyer_branch_rollout_value(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, pv, &vws, &sum, nullptr, last ? fail_count : nullptr, stream)
                     : earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, &bws, &sum, nullptr, last ? fail_count : nullptr, stream))
       return fail(rc, "earl_sawyer_branch_rollout%s failed in iteration %d", pv ? "_value" : "", params->iteration0 + it);
@@ -199,13 +219,23 @@ extern "C" {
 int earl_sawyer_plan_mppi(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                           const earl_sawyer_plan_params* params, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k,
                           int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream) {
-  return plan_mppi(model, col, nv, cfg, st, params, nullptr, mean, plan, ret, ret0, best_ret, best_k, fail_count, clock, ws, stream);
+  return plan_mppi(model, col, nv, cfg, st, params, nullptr, nullptr, mean, plan, ret, ret0, best_ret, best_k, fail_count, clock, ws, stream);
 }
 
 int earl_sawyer_plan_mppi_value(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                 const earl_sawyer_plan_params* params, const earl_plan_value* pv, const float* mean, float* plan, double* ret, double* ret0,
                                 double* best_ret, int32_t* best_k, int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws, earl_stream_t stream) {
-  return plan_mppi(model, col, nv, cfg, st, params, sawyer_value_plain(pv) ? nullptr : pv, mean, plan, ret, ret0, best_ret, best_k, fail_count, clock, ws, stream);
+  return plan_mppi(model, col, nv, cfg, st, params, sawyer_value_plain(pv) ? nullptr : pv, nullptr, mean, plan, ret, ret0, best_ret, best_k, fail_count, clock, ws, stream);
+}
+
+int earl_sawyer_plan_mppi_prior(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                const earl_sawyer_plan_params* params, const earl_plan_value* pv, const earl_sawyer_plan_prior* prior, const float* mean, float* plan,
+                                double* ret, double* ret0, double* best_ret, int32_t* best_k, int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
+                                earl_stream_t stream) {
+  if (!prior || !prior->policy) return fail(EARL_ERR_ARG, "prior / prior->policy is NULL");
+  // branches == 0 (after the struct's own rules, checked inside): exactly the `_value` call, which is the plain call for pv NULL or {1.0, NULL}
+  const bool none = prior->branches == 0;
+  return plan_mppi(model, col, nv, cfg, st, params, none && sawyer_value_plain(pv) ? nullptr : pv, prior, mean, plan, ret, ret0, best_ret, best_k, fail_count, clock, ws, stream);
 }
 
 }  // extern "C"

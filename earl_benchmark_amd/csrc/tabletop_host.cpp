@@ -749,6 +749,40 @@ int32_t earl_sawyer_value_terminal_cpu(const earl_plan_value* pv, int32_t H, int
   });
   return EARL_OK;
 }
+// include/earl_physics.h, "policy-prior branches on the door and the peg": the action rows of prior branch k for GIVEN observation rows -- the float32 rounding, the
+// loops above, then the planner's noise function (sawyer_plan.h: splan_candidate around u, with the prior's sigma; k >= 1 always, branch 0 being the plan).  cem != 0: the
+// block CEM's branch k would have drawn (tabletop_cem.h: kCemDraw).  No host stepper: the rows are the caller's
+int32_t earl_sawyer_prior_actions_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_prior* prior, int32_t H, int32_t k, int32_t j, uint32_t noise_counter, int32_t cem,
+                                      const double* obs, float* act) {
+  if (!cfg || !prior || !prior->policy || !obs || !act) return fail(EARL_ERR_ARG, "cfg/prior/policy/obs/act is NULL");
+  if (cfg->n < 0 || H < 0 || H > 65536 || k < 1 || k >= EARL_SAWYER_PLAN_MAX_K || j < 0 || j > 255)
+    return fail(EARL_ERR_ARG, "n = %d, H = %d, k = %d, j = %d: n >= 0, H in 0 .. 65536, k in 1 .. %d, j in 0 .. 255", cfg->n, H, k, j, EARL_SAWYER_PLAN_MAX_K - 1);
+  if (int rc = contract::check_policy(*prior->policy, 14, 4, nullptr, 0, g_err)) return rc;
+  for (int d = 0; d < 4; ++d)
+    if (!std::isfinite(prior->sigma[d]) || !(prior->sigma[d] >= 0)) return fail(EARL_ERR_ARG, "prior->sigma[%d] = %g: finite and >= 0", d, (double)prior->sigma[d]);
+  const size_t rows = (size_t)H * (size_t)cfg->n;
+  if (rows == 0) return EARL_OK;
+  std::vector<float> x(rows * 14), u(rows * 4);
+  for (size_t e = 0; e < x.size(); ++e) x[e] = svalue_row(obs[e]);
+  if (int rc = earl_mlp_policy_forward_cpu(prior->policy, nullptr, (int32_t)rows, x.data(), nullptr, u.data())) return rc;
+  SawyerPlanArgs p{};
+  p.seed = cfg->seed;
+  for (int d = 0; d < 4; ++d) p.sigma[d] = prior->sigma[d];
+  p.noise_counter = noise_counter;
+  p.word0 = (cem ? kCemDraw : kPlanDraw) | (uint32_t)j;
+  p.env_offset = cfg->env_offset;
+  p.n = cfg->n;
+  p.H = H;
+  for (int t = 0; t < H; ++t)
+    for (int i = 0; i < p.n; ++i) {
+      const size_t r = ((size_t)t * p.n + i) * 4;
+      const float m[4] = {u[r], u[r + 1], u[r + 2], u[r + 3]};
+      float c[4];
+      splan_candidate(p, i, (uint32_t)k, (uint32_t)t, m, c);
+      for (int d = 0; d < 4; ++d) act[r + d] = c[d];
+    }
+  return EARL_OK;
+}
 // the contract's scalar functions (csrc/policy_math.h), for callers that restate a policy on the host
 float earl_tanh_f32(float x) { return tanh_f32(x); }
 float earl_exp_f32(float x) { return exp_f32(x); }

@@ -171,7 +171,7 @@ class PhysicsEnv:
     raise NotImplementedError(f'evaluate_policy: episode summaries on {self.ENV} are evaluate_population\'s (it takes one policy as well as a PolicyPopulation); '
                               'evaluate_policy runs on the tabletop, the Sawyer door and the Sawyer peg')
 
-  def rollout_branches(self, actions, K=None, clock=None, **kwargs):      # (kwargs: discount= and value= of the envs that have the launch are refused like the rest)
+  def rollout_branches(self, actions, K=None, clock=None, **kwargs):      # (kwargs: discount=, value= and prior= / prior_branches= / prior_sigma= of the envs that have the launch are refused like the rest)
     raise NotImplementedError(f'rollout_branches: scoring K action plans from the current state is not built for {self.ENV or type(self).__name__} '
                               '(it runs on the tabletops, the Sawyer door and the Sawyer peg)')
 

@@ -374,7 +374,49 @@ class SawyerDoor(PhysicsEnv):
       cache[(K, H)] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
     return cache[(K, H)][1]
 
-  def rollout_branches(self, actions, K=None, clock=None, discount=1.0, value=None):
+  def _plan_prior(self, who, prior, P, K, prior_sigma):
+    """-> None (prior=None: the calls made before the keyword existed) or a function act -> the struct earl_sawyer_plan_prior of the `_prior` entry points
+    (include/earl_physics.h, "policy-prior branches on the door and the peg") around the [P, H, N, 4] tensor that receives the prior branches' actions, the policy and the
+    first observation kept alive beside it.  The argument errors mirror the tabletop's _plan_prior_check."""
+    P = int(P)
+    if prior is None:
+      if P != 0:
+        raise ValueError(f'{who}: prior_branches = {P} without a prior')
+      return None
+    from ..policy import GaussianMLPPolicy, MLPPolicy, require_widths
+    if not isinstance(prior, MLPPolicy) or isinstance(prior, GaussianMLPPolicy):
+      raise ValueError(f'{who}: prior is an MLPPolicy(layers, hidden_act, out_act, obs_dim={self.OBS_DIM}, act_dim=4) without a Gaussian head')
+    require_widths(prior, who, self.OBS_DIM, 4, env=self)
+    if prior.param_dtype != torch.float32:
+      raise ValueError(f'{who}: the prior stores its parameters as {prior.param_dtype}; float32 only (pass .widened()): no bf16 prior is built')
+    if P < 0 or P >= int(K):
+      raise ValueError(f'{who}: prior_branches = {P}: 0 .. K - 1 = {int(K) - 1} (branch 0 is the plan itself; the prior branches are the LAST ones)')
+    ps = torch.as_tensor(prior_sigma, dtype=torch.float32).reshape(-1).tolist()
+    if len(ps) not in (1, 4):
+      raise ValueError(f'{who}: prior_sigma is a number or four, one per action dimension (x, y, z, gripper)')
+    if not all(x >= 0.0 and x < float('inf') for x in ps):
+      raise ValueError(f'{who}: prior_sigma = {prior_sigma}: finite and >= 0')
+
+    def struct(act):
+      # what the policy sees at step 0, as rollout_policy takes it: the row the env emitted last, or a fresh observation where that row no longer belongs to the state
+      obs0 = (self._get_obs_t() if self._last_obs_stale else self.last_obs).contiguous() if P else None
+      pr = _abi.SawyerPlanPrior(policy=C.pointer(prior.struct), branches=P, sigma=(C.c_float * 4)(*(ps * 4 if len(ps) == 1 else ps)),
+                                obs0=obs0.data_ptr() if P else None, act=act.data_ptr() if P else None)
+      pr._keep = (prior, obs0, act)
+      return pr
+    return struct
+
+  def _prior_ws(self, K, H):
+    """the workspace of a `_prior` call (earl_sawyer_prior_ws_bytes; H = 0: the branch launch's own): one device block, cached per (K, H) like _plan_ws"""
+    cache = self.__dict__.setdefault('_prior_ws_cache', {})
+    if (K, H) not in cache:
+      need = C.c_int64(0)
+      _abi.check(self._lib.earl_sawyer_prior_ws_bytes(self.nv, K, H, self.num_envs, C.byref(need)), 'earl_sawyer_prior_ws_bytes')
+      block = torch.empty(max(need.value, 8) // 8 + 1, dtype=torch.float64, device=self.device)
+      cache[(K, H)] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
+    return cache[(K, H)][1]
+
+  def rollout_branches(self, actions, K=None, clock=None, discount=1.0, value=None, prior=None, prior_branches=0, prior_sigma=0.0, noise_counter=None, iteration=0):
     """K candidate action sequences of H steps scored per env FROM THE CURRENT STATE in one launch of the rollout kernel over K N virtual envs (include/earl_physics.h:
     earl_sawyer_branch_rollout): actions [K, H, N, 4] float32 -- or [H, N, 4] with K= for K replays of one block --
     -> {'ret' [K, N] float64, 'success' [K, N] bool (the success of step H - 1), 'first_success' [K, N] int32 (-1: none), 'last_obs' [K, N, 14] float64,
@@ -384,10 +426,17 @@ class SawyerDoor(PhysicsEnv):
     (random shooting, CEM, MPPI) asks for.  clock: None, or the device address of the two uint64 words of earl_sawyer_rollout_clocked (a captured launch).
     discount=, value=: 'ret' becomes sum_t discount^t r_t + discount^H V(last_obs row) (earl_sawyer_branch_rollout_value): the sum in float64 in that order, a
     rolled-back step adding 0 and still advancing the discount; `value` an MLPPolicy(layers, act, out_act, obs_dim=14, act_dim=1), float32, evaluated on the float32
-    rounding of the row by a kernel behind the rollout kernel; a row that holds a NaN gives a NaN.  The defaults make the call above, bit for bit."""
+    rounding of the row by a kernel behind the rollout kernel; a row that holds a NaN gives a NaN.  The defaults make the call above, bit for bit.
+    prior=, prior_branches=P, prior_sigma= (earl_sawyer_branch_rollout_prior): `actions` is then [K - P, H, N, 4] and P further branches, the LAST P of the K scored,
+    are closed-loop rollouts under `prior` -- an MLPPolicy(layers, hidden_act, out_act, obs_dim=14, act_dim=4), float32, no Gaussian head -- evaluated inside the rollout
+    kernel on the row the branch emitted last (at step 0 the env's current observation): a_t = clip(prior(obs_t) + prior_sigma * eps) with eps the noise MPPI's branch k
+    draws for (`iteration`, env, k, t, `noise_counter`; None: the env's step count).  The result gains 'prior_actions' [P, H, N, 4] and 'actions' [K, H, N, 4], the array
+    that was scored: rollout_branches(res['actions']) reproduces every row.  prior=None calls exactly what is called without the keywords."""
     a = torch.as_tensor(actions, device=self.device)
     n = self.num_envs
     pv = self._plan_value('rollout_branches', discount, value)
+    if prior is not None or int(prior_branches) != 0:
+      return self._rollout_branches_prior(a, K, clock, pv, prior, int(prior_branches), prior_sigma, noise_counter, int(iteration))
     if K is None:
       if a.dim() != 4 or a.shape[2] != n or a.shape[3] != 4:
         raise ValueError(f'rollout_branches: actions must be [K, H, N, 4] = [K, H, {n}, 4], got {list(a.shape)} (one block for K branches: [H, {n}, 4] with K=)')
@@ -419,6 +468,39 @@ class SawyerDoor(PhysicsEnv):
       _abi.check(self._lib.earl_sawyer_branch_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, K, H, act.data_ptr(), stride,
                                                       clock, C.byref(ws), C.byref(summary), res['last_obs'].data_ptr(), res['fail'].data_ptr(), self._stream()),
                  'earl_sawyer_branch_rollout')
+    return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
+
+  def _rollout_branches_prior(self, a, K, clock, pv, prior, P, prior_sigma, noise_counter, iteration):
+    """rollout_branches with prior=: actions [K - P, H, N, 4] -> its dict over all K branches plus 'prior_actions' and 'actions'"""
+    n = self.num_envs
+    if K is not None:
+      raise ValueError('rollout_branches: with prior= the call writes the prior branches\' blocks: actions [K - P, H, N, 4], not one block with K=')
+    if a.dim() != 4 or a.shape[2] != n or a.shape[3] != 4:
+      raise ValueError(f'rollout_branches: with prior= actions must be [K - P, H, N, 4] = [K - P, H, {n}, 4], got {list(a.shape)}')
+    K, H = int(a.shape[0]) + P, int(a.shape[1])
+    make = self._plan_prior('rollout_branches', prior, P, K, prior_sigma)
+    if K - P < 1 or H < 1:
+      raise ValueError(f'rollout_branches: K - P = {K - P}, H = {H}: at least one given branch of at least one step')
+    if not 0 <= iteration <= 255:
+      raise ValueError(f'rollout_branches: iteration = {iteration}: 0 .. 255')
+    if K * n > INT32_MAX:
+      raise ValueError(f'rollout_branches: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
+    kw = dict(device=self.device)
+    act = torch.empty(K, H, n, 4, dtype=torch.float32, **kw)
+    act[:K - P].copy_(self._actions(a, (K - P, H)))
+    res = {'ret': torch.empty(K, n, dtype=torch.float64, **kw), 'success': torch.empty(K, n, dtype=torch.bool, **kw),
+           'first_success': torch.empty(K, n, dtype=torch.int32, **kw), 'last_obs': torch.empty(K, n, self.OBS_DIM, dtype=torch.float64, **kw),
+           'fail': torch.empty(K, n, dtype=torch.int32, **kw), 'prior_actions': torch.empty(P, H, n, 4, dtype=torch.float32, **kw), 'actions': act}
+    summary = _abi.EpisodeSummary(ret=res['ret'].data_ptr(), success_last=res['success'].data_ptr(), first_success=res['first_success'].data_ptr())
+    nc = self.total_step_count if noise_counter is None else int(noise_counter)
+    self._cfg.step_counter = self.total_step_count
+    with torch.cuda.device(self.device):
+      pr = make(res['prior_actions'])
+      ws = self._prior_ws(K, 0)
+      _abi.check(self._lib.earl_sawyer_branch_rollout_prior(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, K, H, act.data_ptr(),
+                                                            H * n * 4, clock, C.byref(pv) if pv is not None else None, C.byref(pr), iteration, nc & 0xFFFFFFFF,
+                                                            C.byref(ws), C.byref(summary), res['last_obs'].data_ptr(), res['fail'].data_ptr(), self._stream()),
+                 'earl_sawyer_branch_rollout_prior')
     return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
 
   # ------------------------------------------------------------------ MPPI on top of the branch launch (include/earl_physics.h: earl_sawyer_plan_mppi)
@@ -458,7 +540,7 @@ class SawyerDoor(PhysicsEnv):
                                  noise_counter=nc & 0xFFFFFFFF, inv_temperature=1.0 / float(temperature))
 
   def plan_mppi(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, clock=None, out=None, discount=1.0,
-                value=None):
+                value=None, prior=None, prior_branches=0, prior_sigma=0.0):
     """`iterations` MPPI iterations on the device from the CURRENT state (include/earl_physics.h: earl_sawyer_plan_mppi): K candidates per env -- the mean plan itself and
     K - 1 copies with clipped Gaussian noise of scale `sigma` (a number or four: x, y, z, gripper) -- scored by the branch launch exactly as rollout_branches scores them,
     the mean moved to their average under the weights exp((ret - max ret) / temperature), in integer sums.  Per iteration three launches (candidates, the branch
@@ -471,16 +553,23 @@ class SawyerDoor(PhysicsEnv):
     the same keys; a key that is missing or None is not computed, except 'ret' (the branch launch writes it), which is then allocated; out['plan'] may be the `mean`
     tensor.  clock: as rollout_branches.  The env is left exactly as found -- state, goals, counters, last_obs, fail_count.
     discount=, value=: the candidates are scored as rollout_branches(..., discount=, value=) scores them (earl_sawyer_plan_mppi_value) and nothing else changes; the
-    defaults make the call above, bit for bit."""
+    defaults make the call above, bit for bit.
+    prior=, prior_branches=P, prior_sigma= (earl_sawyer_plan_mppi_prior): the LAST P of the K candidates are closed-loop rollouts under `prior` as in rollout_branches,
+    made again in every iteration with that iteration's noise word; they enter the weights and the average like any candidate.  The result gains 'prior_actions'
+    [P, H, N, 4] (the last iteration's; the candidates of the call are plan_candidates(...) with the last P rows replaced by it).  best_k >= K - P names a prior branch.
+    prior=None calls exactly what is called without the keywords."""
     m = self._plan_mean('plan_mppi', mean, horizon)
     pv = self._plan_value('plan_mppi', discount, value)
     n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
     pp = self._plan_params('plan_mppi', K, H, I, iteration0, sigma, temperature, noise_counter)
+    make = self._plan_prior('plan_mppi', prior, prior_branches, K, prior_sigma)
     if K * n > INT32_MAX:
       raise ValueError(f'plan_mppi: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
     kw = dict(device=self.device)
     want = {'plan': ((H, n, 4), torch.float32), 'ret': ((K, n), torch.float64), 'ret0': ((I, n), torch.float64), 'best_ret': ((n,), torch.float64),
             'best_k': ((n,), torch.int32), 'fail': ((K, n), torch.int32)}
+    if make is not None:
+      want['prior_actions'] = ((int(prior_branches), H, n, 4), torch.float32)
     if out is None:
       res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
     else:
@@ -495,8 +584,18 @@ class SawyerDoor(PhysicsEnv):
         raise ValueError("plan_mppi: out['plan'] is what the call computes")
       if 'ret' not in res:
         res['ret'] = torch.empty(K, n, dtype=torch.float64, **kw)
+      if make is not None and 'prior_actions' not in res:
+        res['prior_actions'] = torch.empty(*want['prior_actions'][0], dtype=torch.float32, **kw)
     self._cfg.step_counter = self.total_step_count
     with torch.cuda.device(self.device):
+      if make is not None:
+        pr = make(res['prior_actions'])
+        ws = self._prior_ws(K, H)
+        _abi.check(self._lib.earl_sawyer_plan_mppi_prior(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pp),
+                                                         C.byref(pv) if pv is not None else None, C.byref(pr), m.data_ptr(), res['plan'].data_ptr(), res['ret'].data_ptr(),
+                                                         _ptr(res.get('ret0')), _ptr(res.get('best_ret')), _ptr(res.get('best_k')), _ptr(res.get('fail')), clock,
+                                                         C.byref(ws), self._stream()), 'earl_sawyer_plan_mppi_prior')
+        return res
       if pv is not None:
         ws = self._value_ws(K, H)
         _abi.check(self._lib.earl_sawyer_plan_mppi_value(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pp), C.byref(pv),
@@ -551,7 +650,7 @@ class SawyerDoor(PhysicsEnv):
     return t.to(torch.float32).contiguous()
 
   def plan_cem(self, mean=None, horizon=None, K=64, elites=8, iterations=1, sigma=0.3, std=None, alpha=0.0, std_min=0.0, std_max=2.0, iteration0=0, noise_counter=None,
-               clock=None, out=None, discount=1.0, value=None):
+               clock=None, out=None, discount=1.0, value=None, prior=None, prior_branches=0, prior_sigma=0.0):
     """`iterations` cross-entropy iterations on the device from the CURRENT state (include/earl_physics.h: earl_sawyer_plan_cem): K candidates per env -- the mean plan
     itself and K - 1 copies with clipped Gaussian noise whose scale is a std per (step, env, dimension) -- scored by the branch launch exactly as rollout_branches
     scores them; the `elites` best (NaN last, return descending, k ascending; found by a radix select, linear in K) refit the mean AND the std, in integer sums, with
@@ -563,17 +662,23 @@ class SawyerDoor(PhysicsEnv):
     `noise_counter`, `iteration0`, `clock` and `out` are plan_mppi's: a key of `out` that is missing or None is not computed, except 'ret' and 'std' (the call needs
     both), which are then allocated; out['plan'] may be the `mean` tensor and out['std'] the `std` tensor.  K goes to 8192, elites to min(K, 1024).  The env is left
     exactly as found -- state, goals, counters, last_obs, fail_count.
-    discount=, value=: as plan_mppi's (earl_sawyer_plan_cem_value): only the scores change; the defaults make the call above, bit for bit."""
+    discount=, value=: as plan_mppi's (earl_sawyer_plan_cem_value): only the scores change; the defaults make the call above, bit for bit.
+    prior=, prior_branches=P, prior_sigma=: as plan_mppi's (earl_sawyer_plan_cem_prior): the LAST P candidates are closed-loop rollouts under `prior`, with CEM's noise
+    words scaled by `prior_sigma` (not by the std); a prior branch that ranks among the elites refits mean and std like any candidate, and on an exact tie the plan and
+    the noise branches come first (k ascending).  The result gains 'prior_actions' [P, H, N, 4]."""
     m = self._plan_mean('plan_cem', mean, horizon)
     pv = self._plan_value('plan_cem', discount, value)
     n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
     cp = self._cem_params('plan_cem', K, H, I, iteration0, elites, sigma, alpha, std_min, std_max, noise_counter)
+    make = self._plan_prior('plan_cem', prior, prior_branches, K, prior_sigma)
     s0 = self._cem_std('plan_cem', std, H)
     if K * n > INT32_MAX:
       raise ValueError(f'plan_cem: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
     kw = dict(device=self.device)
     want = {'plan': ((H, n, 4), torch.float32), 'std': ((H, n, 4), torch.float32), 'ret': ((K, n), torch.float64), 'ret0': ((I, n), torch.float64),
             'best_ret': ((n,), torch.float64), 'best_k': ((n,), torch.int32), 'elite': ((K, n), torch.uint8), 'fail': ((K, n), torch.int32)}
+    if make is not None:
+      want['prior_actions'] = ((int(prior_branches), H, n, 4), torch.float32)
     if out is None:
       res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
     else:
@@ -586,11 +691,20 @@ class SawyerDoor(PhysicsEnv):
           raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
       if 'plan' not in res:
         raise ValueError("plan_cem: out['plan'] is what the call computes")
-      for k in ('ret', 'std'):
+      for k in ('ret', 'std') + (('prior_actions',) if make is not None else ()):
         if k not in res:
           res[k] = torch.empty(*want[k][0], dtype=want[k][1], **kw)
     self._cfg.step_counter = self.total_step_count
     with torch.cuda.device(self.device):
+      if make is not None:
+        pr = make(res['prior_actions'])
+        ws = self._prior_ws(K, H)
+        _abi.check(self._lib.earl_sawyer_plan_cem_prior(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(cp),
+                                                        C.byref(pv) if pv is not None else None, C.byref(pr), m.data_ptr(), _ptr(s0), res['plan'].data_ptr(),
+                                                        res['std'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
+                                                        _ptr(res.get('best_k')), _ptr(res.get('elite')), _ptr(res.get('fail')), clock, C.byref(ws), self._stream()),
+                   'earl_sawyer_plan_cem_prior')
+        return res
       if pv is not None:
         ws = self._value_ws(K, H)
         _abi.check(self._lib.earl_sawyer_plan_cem_value(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(cp), C.byref(pv),
@@ -620,7 +734,7 @@ class SawyerDoor(PhysicsEnv):
     return act
 
   def mpc_rollout(self, T, plan=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, noise_counter=None, out=None, method='mppi', elites=8, alpha=0.0,
-                  std_min=0.0, std_max=2.0, discount=1.0, value=None):
+                  std_min=0.0, std_max=2.0, discount=1.0, value=None, prior=None, prior_branches=0, prior_sigma=0.0):
     """T steps of receding-horizon MPPI control, DEFINED as this composition of public methods (one call each per control step, no host synchronisation in the loop):
         P = plan.clone()  (None: zeros of [horizon, N, 4]);  nc0 = noise_counter  (None: the low 32 bits of env.total_step_count at entry)
         for s in range(T):
@@ -634,7 +748,8 @@ class SawyerDoor(PhysicsEnv):
     one-launch loop is not built for these envs (the score and the update would need a grid-wide join inside the stepper kernel).
     method='cem': the same composition with plan_cem(P, K=, elites=, iterations=, sigma=, std=None, alpha=, std_min=, std_max=, noise_counter=...) as its planner --
     the std restarts from `sigma` at every control step, as on the tabletops, so there is no std to carry or shift; `temperature` is not read.
-    discount=, value=: handed to the planner of every control step (both methods), which is all they change."""
+    discount=, value=: handed to the planner of every control step (both methods), which is all they change.
+    prior=, prior_branches=, prior_sigma=: likewise handed to the planner of every control step (prior=None: the planner is called without them, as before)."""
     T = int(T)
     if T < 1:
       raise ValueError(f'mpc_rollout: T = {T}: at least one control step')
@@ -647,6 +762,7 @@ class SawyerDoor(PhysicsEnv):
     else:
       self._plan_params('mpc_rollout', K, H, I, 0, sigma, temperature, noise_counter)
     self._plan_value('mpc_rollout', discount, value)
+    pkw = {} if self._plan_prior('mpc_rollout', prior, prior_branches, K, prior_sigma) is None else dict(prior=prior, prior_branches=prior_branches, prior_sigma=prior_sigma)
     nc0 = self.total_step_count if noise_counter is None else int(noise_counter)
     kw = dict(device=self.device)
     res = self._new_out((T,)) if out is None else dict(out)
@@ -654,13 +770,14 @@ class SawyerDoor(PhysicsEnv):
     rows = [k for k in res if k not in ('act', 'ret0', 'best_ret')]
     ret = torch.empty(K, n, dtype=torch.float64, **kw)
     std = torch.empty(H, n, 4, dtype=torch.float32, **kw) if method == 'cem' else None
+    pout = {'prior_actions': torch.empty(int(prior_branches), H, n, 4, dtype=torch.float32, **kw)} if pkw else {}      # (the planner's workspace: allocated once, not per step)
     for s in range(T):
       if method == 'cem':
         self.plan_cem(P, K=K, elites=elites, iterations=I, sigma=sigma, alpha=alpha, std_min=std_min, std_max=std_max, noise_counter=(nc0 + s) & 0xFFFFFFFF,
-                      out={'plan': P, 'std': std, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]}, discount=discount, value=value)
+                      out={'plan': P, 'std': std, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s], **pout}, discount=discount, value=value, **pkw)
       else:
         self.plan_mppi(P, K=K, iterations=I, sigma=sigma, temperature=temperature, noise_counter=(nc0 + s) & 0xFFFFFFFF,
-                       out={'plan': P, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]}, discount=discount, value=value)
+                       out={'plan': P, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s], **pout}, discount=discount, value=value, **pkw)
       self.rollout(P[:1], out={k: res[k][s:s + 1] for k in rows})
       res['act'][s].copy_(P[0])
       if H > 1:

@@ -587,8 +587,8 @@ int32_t earl_sawyer_cem_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer
  *              0 for K n == 0.  No allocation and no host synchronisation; capture into a graph under the branch launch's rule.
  * EARL_ERR_ARG before any HIP call for: everything the value-free entry point refuses; a discount that is NaN, <= 0 or > 1; a value network the rules above refuse
  * (widths, a precision other than 0, the activation enums, dims[3] != 0 with one hidden layer, params NULL or misaligned); a network without summary->ret; a ws block
- * that is NULL, misaligned or smaller than earl_sawyer_value_ws_bytes says.  There is no bf16 value network, no policy-prior branch and no fused control loop on these
- * envs; the minitaur and the kitchen have no planner at all.
+ * that is NULL, misaligned or smaller than earl_sawyer_value_ws_bytes says.  There is no bf16 value network and no fused control loop on these
+ * envs (policy-prior branches: the next section); the minitaur and the kitchen have no planner at all.
  * Host twin (libearl_host.so; host pointers): earl_sawyer_value_terminal_cpu adds the terminal term to ret [rows] for given last_obs [rows, 14] -- d_H by the recurrence,
  * the float32 rounding, the NaN rule and the two roundings through csrc/sawyer_value.h, the header the kernel uses; V by earl_mlp_policy_forward_cpu's loops.  pv->value
  * NULL leaves ret as it is.  There is no host stepper, so the discounted sum itself has no twin.  Its refusals: pv, last_obs or ret NULL, rows < 0, H < 0, and pv's. */
@@ -604,6 +604,67 @@ int earl_sawyer_plan_cem_value(const earl_link_model* model, const earl_collisio
                                double* ret0, double* best_ret, int32_t* best_k, uint8_t* elite, int32_t* fail, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
                                earl_stream_t stream);
 int32_t earl_sawyer_value_terminal_cpu(const earl_plan_value* pv, int32_t H, int32_t rows, const double* last_obs, double* ret);
+
+/* ---- policy-prior branches on the door and the peg: some of the K candidates are closed-loop rollouts under a learned policy ----
+ * The rewards here are sparse or contact-gated and K is small (an env step costs tens of thousands of cycles): zero-mean noise around a zero plan almost never reaches
+ * the handle or the peg, a learned forward agent does.  P of the K branches of a call are therefore driven by a policy that sees the branch's own observations.
+ *   placement  the prior branches are the LAST P: k = K - P .. K - 1.  (The tabletop's earl_tabletop_plan_prior uses 1 .. P; here the tail makes "the plain launch over the
+ *              first (K - P) n virtual envs, the prior launch over the rest" two contiguous ranges of v = k n + i.)  Branch 0 stays the plan itself; CEM's tie order
+ *              (k ascending) therefore prefers the plan and the noise branches over the prior on exact ties, and so does MPPI's best_k.
+ *   action     of prior branch k at step t of env i (global id g): x_t = the float32 rounding of the row the branch last emitted, exactly as it stands -- a rolled-back
+ *              step's repeated row, the goal block a lifelong switch patched -- and at t = 0 obs0[i]; u = the policy contract's output (csrc/policy_math.h;
+ *              earl_mlp_policy_forward_cpu states it on the host); a[t][d] = clip(fmaf(sigma[d], eps_d, u[d])) with eps_d from the SAME Philox block noise branch k
+ *              would have drawn for (j, g, k, t, noise_counter) (planner item 2: words x, y, z, w for d = 0 .. 3; word 0 is the calling planner's -- MPPI's for
+ *              earl_sawyer_branch_rollout_prior) and the planner's clip on all four words.  The row is stored into the branch's block of the [K, H, n, 4] array the call
+ *              scores, and into prior->act when given.  Everything else about the branch is the branch launch's contract: draws, rollback, summary, fail, common
+ *              random numbers over branches.
+ *   calls      earl_sawyer_branch_rollout_prior: earl_sawyer_branch_rollout_value with `act` float* [K, H, n, 4] -- the blocks of the first K - P branches are inputs,
+ *              the last P blocks outputs; a stride of 0 is refused when P > 0 -- and the iteration j (0 .. 255) and noise_counter of the noise words.
+ *              earl_sawyer_plan_mppi_prior / earl_sawyer_plan_cem_prior: the `_value` planners with item 3 replaced by that call: the candidates kernel still writes
+ *              the tail rows, the prior launch overwrites them, in every iteration with that iteration's noise word; the update kernels read the candidates back
+ *              and do not change, so `chaining` holds as it stands.  pv NULL: undiscounted, no network.
+ *   launches   P > 0: ONE launch of the prior kernel (csrc/physics_branch_prior.hip, physics_branch_prior_w8.hip: the rollout kernel's fourth inclusion, built with the
+ *              discounted sum only -- gamma == 1 gives the plain sum's bits) over all K n virtual envs behind the one replicate launch; the branches in front of K - P
+ *              load their action inside it as a plain branch does, and a wave that holds no prior branch never enters the policy phase.  The other shape -- the
+ *              untouched branch kernels over the first (K - P) n virtual envs, then the prior kernel over the last P n, each behind a replicate launch of its own and in
+ *              the form its own count of virtual envs selects -- is kept behind earl_debug_set_sawyer_prior_launches(2); it measured 1.5 - 1.9 x slower where K n fits
+ *              one round of waves.  The shapes and the forms are bit-identical.  Either way everything runs on the caller's stream: no second stream, no
+ *              event, capturable without parallel graph branches.
+ *   identities branches == 0 makes exactly the launches of the `_value` call (of the plain call when pv is NULL or {1.0, NULL}): the same bits.  After a call, feeding
+ *              the full [K, H, n, 4] array to earl_sawyer_branch_rollout[_value] reproduces every output of every branch bit for bit (the replay identity).
+ *   ws         earl_sawyer_prior_ws_bytes(nv, K, H, n, &bytes) >= earl_sawyer_value_ws_bytes(nv, K, H, n) for the three calls (H = 0: the branch call's own): the
+ *              `_value` block with a second work queue of 8 ceil(K n / 4) bytes (rounded up to 8) behind the [K n] discounts -- the time-sliced peg queue is per
+ *              launch, and the two-launch shape needs one for each -- and, H > 0, the candidates behind that.  Monotone in K, H and n, 0 for K n == 0.
+ * EARL_ERR_ARG before any HIP call for: everything the `_value` call refuses; prior or prior->policy NULL; branches outside 0 .. K - 1; a policy that is not
+ * 14 -> hidden (-> hidden) -> 4 with hidden widths multiples of 16 up to 256, float32 (precision 0: no bf16 prior), params 16-byte aligned, no Gaussian head, one network;
+ * a sigma that is not finite and >= 0; and with P > 0: obs0 NULL, a stride of 0, `act` or prior->act not 16-byte aligned, a stride that is no multiple of 4, K above
+ * EARL_SAWYER_PLAN_MAX_K or H above 65536 (the noise key), j outside 0 .. 255, prior->act overlapping an input (the candidates / mean / std0, obs0, the parameters);
+ * under earl_debug_set_physics_lanes(64) as the branch launch.
+ * Host twin (libearl_host.so; host pointers): earl_sawyer_prior_actions_cpu computes the [H, n, 4] action rows of prior branch k for GIVEN observation rows [H, n, 14]
+ * (row (t, i) = what the branch saw at step t), with earl_mlp_policy_forward_cpu's loops and the planner's noise function (csrc/sawyer_plan.h); cem != 0 takes CEM's
+ * draw word.  There is no host stepper, so that is all a twin can state.  prior->obs0 and prior->act are not read. */
+typedef struct earl_sawyer_plan_prior {
+  const earl_mlp_policy* policy;  /* 14 -> H1 (-> H2) -> 4, float32, no Gaussian head, one network (no population) */
+  int32_t branches;               /* P: 0 .. K - 1 */
+  float sigma[4];                 /* finite, >= 0 */
+  const double* obs0;             /* [n, 14] device: what the policy sees at step 0 (as earl_sawyer_population_rollout's obs0) */
+  float* act;                     /* NULL or [P, H, n, 4]: the prior branches' actions of the last iteration */
+} earl_sawyer_plan_prior;
+int earl_sawyer_prior_ws_bytes(int32_t nv, int32_t K, int32_t H, int32_t n, int64_t* bytes);
+int earl_sawyer_branch_rollout_prior(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                     int32_t K, int32_t H, float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_plan_value* pv,
+                                     const earl_sawyer_plan_prior* prior, int32_t j, uint32_t noise_counter, const earl_sawyer_branch_ws* ws,
+                                     const earl_episode_summary* summary, double* last_obs, int32_t* fail, earl_stream_t stream);
+int earl_sawyer_plan_mppi_prior(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                                const earl_sawyer_plan_params* params, const earl_plan_value* pv, const earl_sawyer_plan_prior* prior, const float* mean, float* plan,
+                                double* ret, double* ret0, double* best_ret, int32_t* best_k, int32_t* fail, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
+                                earl_stream_t stream);
+int earl_sawyer_plan_cem_prior(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
+                               const earl_sawyer_cem_params* params, const earl_plan_value* pv, const earl_sawyer_plan_prior* prior, const float* mean, const float* std0,
+                               float* plan, float* std, double* ret, double* ret0, double* best_ret, int32_t* best_k, uint8_t* elite, int32_t* fail, const uint64_t* clock,
+                               const earl_sawyer_branch_ws* ws, earl_stream_t stream);
+int32_t earl_sawyer_prior_actions_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_prior* prior, int32_t H, int32_t k, int32_t j, uint32_t noise_counter, int32_t cem,
+                                      const double* obs, float* act);
 
 /* The policy contract on the host (libearl_host.so; host pointers): actions [n, A] of n observation rows obs [n, dims[0]], dims[0] in 1..256, hidden widths in 1..256,
  * the last layer A wide (head = NULL) or 2 A wide (rows 0..A-1 the mean, A..2A-1 the raw log_std), A >= 1.  eps [n, A] = the standard-normal draws to use with a
@@ -1004,6 +1065,10 @@ int earl_debug_set_door_variant(int variant);
 /* measurement / test switch for the peg model's rollout: 1 (default) = time-sliced schedule when earl_sawyer_state.sched is given and the batch exceeds one round,
  * 0 = always one group per wave, k >= 2 = time-sliced with k env steps per work item.  Results are bit-identical. */
 int earl_debug_set_peg_schedule(int sliced);
+/* measurement / test switch for the launch shape of the policy-prior branches (earl_sawyer_branch_rollout_prior and the `_prior` planners): 1 (default) = ONE launch of the
+ * prior kernel over all K n virtual envs, the branches in front of K - P loading their action inside it; 2 = the untouched branch kernels over the first (K - P) n, then
+ * the prior kernel over the last P n.  Results are bit-identical. */
+int earl_debug_set_sawyer_prior_launches(int launches);
 
 /* sizeof(earl_link_model) as compiled into the library (bindings check their struct layout against it) */
 int earl_physics_model_size(void);

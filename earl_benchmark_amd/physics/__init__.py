@@ -96,9 +96,13 @@ def check_impedance_powers(d, keys, what):
 
 
 def load_link_model(name):
-  """-> (LinkModelStruct, dict of the npz arrays)"""
-  with np.load(os.path.join(MODEL_DIR, name + '_links.npz')) as z:
-    d = {k: z[k] for k in z.files}
+  """name of a shipped model, or a tables dict with the keys of its *_links.npz (tests: synthetic collision tables on a shipped link model)
+  -> (LinkModelStruct, dict of the arrays); a dict passes every structural assertion a file does"""
+  if isinstance(name, dict):
+    d, name = {k: np.asarray(v) for k, v in name.items()}, 'tables dict'
+  else:
+    with np.load(os.path.join(MODEL_DIR, name + '_links.npz')) as z:
+      d = {k: z[k] for k in z.files}
   nv, natt, nact = len(d['parent']), len(d['att_link']), len(d['act_joint'])
   big = nv > MAXV                               # the kitchen: struct earl_link_model24
   assert (nv <= MAXV24 and natt <= MAXATT24 if big else nv <= MAXV and natt <= MAXATT) and nact <= MAXACT
@@ -226,6 +230,14 @@ def load_collision_model(d):
   assert c.n_sph <= MAXSPH and c.n_box <= MAXBOX and c.n_pair <= MAXPAIR and c.n_cls <= MAXCLS
   nvm = len(d['parent'])
   assert c.n_blk <= (16 if small else (64 if nvm == 23 else (8 if nvm == 22 else 32))) and 0 < c.max_con <= (8 if small else MAXCON)      # Lim<NV>::MB, ::MC
+  # the kernels index with these and check none of them: the blocks partition the pair list in order, every pair of a block is against the block's box, and
+  # every index names something the table has
+  bb, be, prs = np.asarray(d['col_blk_begin'], np.int64), np.asarray(d['col_blk_end'], np.int64), np.asarray(d['col_pair'], np.int64).reshape(-1, 2)
+  assert c.n_blk > 0 and bb[0] == 0 and be[-1] == c.n_pair and (bb < be).all() and (bb[1:] == be[:-1]).all(), 'collision blocks: a partition of the pair list, in order'
+  assert (0 <= prs[:, 0]).all() and (prs[:, 0] < c.n_sph).all() and (0 <= prs[:, 1]).all() and (prs[:, 1] < c.n_box).all(), 'collision pairs: sphere / box index'
+  assert len(d['col_pair_cls']) == c.n_pair and (0 <= np.asarray(d['col_pair_cls'])).all() and (np.asarray(d['col_pair_cls']) < c.n_cls).all(), 'collision pairs: class index'
+  assert all((prs[bb[b]:be[b], 1] == int(d['col_blk_box'][b])).all() for b in range(c.n_blk)), "collision blocks: a block's pairs are against its box"
+  assert all((-1 <= np.asarray(d[k])).all() and (np.asarray(d[k]) < nvm).all() for k in ('col_sph_link', 'col_box_link', 'col_blk_link')), 'collision tables: link index'
   if nvm == 23:      # csrc/physics.hip Lim<23>::PACK: several near blocks share a pass of the group's 32 lanes; a block must fit one pass
     assert int(np.max(np.asarray(d['col_blk_end']) - np.asarray(d['col_blk_begin']))) <= 32, 'kitchen collision blocks: at most 32 pairs each'
   if nvm == 22:
@@ -285,6 +297,8 @@ class DeviceModel:
     self.lib = _abi.load()
     check_layouts(self.lib)
     self.struct, self.tables = load_link_model(name)
+    if isinstance(name, dict):
+      name = 'tables dict'
     self.col_struct = load_collision_model(self.tables) if contacts else None
     if self.col_struct is not None and (any(self.col_struct.pair_kind[i] == 2 for i in range(self.col_struct.n_pair)) or any(self.col_struct.cls_mu_tor[:])):
       # include/earl_physics.h: cylinder-vs-box pairs (pair_kind 2) and torsional rows (cls_mu_tor) exist in the C restatement's experimental tables only;

@@ -10,6 +10,7 @@ from oracle.tabletop_oracle import lib, _p
 
 class CModel:
   def __init__(self, name='sawyer_door', contacts=True):
+    """name: a shipped model, or a tables dict with the keys of its *_links.npz (earl_benchmark_amd.physics.load_link_model takes both)"""
     from earl_benchmark_amd import _abi, physics
     self._abi = _abi
     self.struct, self.tables = physics.load_link_model(name)

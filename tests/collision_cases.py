@@ -1,0 +1,628 @@
+"""Synthetic collision tables on the shipped Sawyer door / peg link models, exact contact geometry, and the closed-form response of one
+contact on the peg's free body (TEST INFRASTRUCTURE: a plain module -- no tests, no fixtures).
+
+Tables: `synth` keeps every structural key of the shipped *_links.npz (tree, joint types, attachments, weld, actuators, limits) and replaces every col_* key and
+max_contacts by a small set given as plain lists.  The block bounds are worked out here exactly as oracle/physics_oracle.py collision_primitives does for the shipped
+tables, once, for the device and for both restatements.  A table reaches a kernel only through earl_benchmark_amd.physics.load_link_model / load_collision_model.
+
+Exact geometry: sphere / point vs oriented box by case over the 27 regions, segment vs segment by enumeration of the nine candidate kinds -- neither uses the clamp
+expression / the clamp-reclamp iteration that the kernels and the restatements share.  Every function takes a field F (LD: numpy.longdouble, MP: mpmath at 240 bits)."""
+import itertools
+import os
+
+import mpmath
+import numpy as np
+
+import primitives_ref as pr                     # (sets mpmath.mp.prec = 240)
+from oracle import physics_oracle as po
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BOUNDARY_CLEARANCE = 1e-4                      # [m] every non-tie input sits at least this far from a region boundary / from a change of the closest-point kind
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ tables
+def shipped(name):
+  with np.load(os.path.join(REPO, 'earl_benchmark_amd', 'models', name + '_links.npz')) as z:
+    return {k: z[k] for k in z.files}
+
+
+def cls_row(mu=1.0, solref=(0.015, 1.0), solimp=(0.945, 0.97, 0.0055, 0.5, 2.0), margin=0.001, invw=10.0):
+  return dict(mu=mu, solref=solref, solimp=solimp, margin=margin, invw=invw)
+
+
+CLS_A = cls_row()
+CLS_B = cls_row(mu=2.0, solref=(0.02, 1.0), solimp=(0.85, 0.925, 0.0055, 0.5, 2.0), margin=0.002, invw=2.9)
+
+
+def box(link, pos, quat, half, kind=0):
+  q = np.asarray(quat, float)
+  return dict(link=link, pos=np.asarray(pos, float), quat=q / np.sqrt(q @ q), half=np.asarray(half, float), kind=kind)
+
+
+def capsule(link, pos, quat, radius, half_axis):
+  """capsule = a box record of kind 1: axis = the box frame's z, half = (radius, radius, half_axis + radius)"""
+  return box(link, pos, quat, (radius, radius, half_axis + radius), kind=1)
+
+
+def geom(link, pos, r=0.0, dir=(0.0, 0.0, 0.0), hl=0.0):
+  """sphere (r > 0), point (r = 0) or, for capsule blocks, an edge: the segment pos +- hl dir"""
+  d = np.asarray(dir, float)
+  return dict(link=link, pos=np.asarray(pos, float), r=float(r), dir=d / np.sqrt(d @ d) if d.any() else d, hl=float(hl))
+
+
+def block(box_index, geoms, cls=0, cap=1):
+  """pairs (g, box_index) for g in geoms, in this order; cls: one class for all or one per pair"""
+  return dict(box=box_index, geoms=list(geoms), cls=[cls] * len(geoms) if np.isscalar(cls) else list(cls), cap=cap)
+
+
+def synth(name, boxes, geoms, blocks, classes, max_con, gravity=None, drag=False, free_inertia=None, cone_elliptic=None):
+  """-> tables dict with the keys of name's *_links.npz"""
+  d = {k: v for k, v in shipped(name).items() if not k.startswith('col_') and k != 'max_contacts'}
+  nv = len(d['parent'])
+  if name == 'sawyer_peg':                      # what peg_alpha relies on (true of the shipped table)
+    assert not np.any(d['com'][14]) and not np.any(d['mass'][9:14]) and not np.any(d['jnt_armature'][9:15])
+  if gravity is not None:
+    d['gravity'] = np.asarray(gravity, float)
+  if not drag:
+    d['dof_drag_G'] = np.zeros(nv)
+  if free_inertia is not None:
+    d['inertia'] = d['inertia'].copy()
+    d['inertia'][14] = [free_inertia] * 3 + [0.0] * 3
+  if cone_elliptic is not None:
+    d['cone_elliptic'] = np.int32(cone_elliptic)
+  pairs, pcls, rows = [], [], []
+  for b in blocks:
+    links = {geoms[g]['link'] for g in b['geoms']}
+    assert len(links) == 1 and len(b['cls']) == len(b['geoms']) > 0
+    pts = np.array([geoms[g]['pos'] for g in b['geoms']])
+    ctr = pts.mean(0)
+    rad = max(np.sqrt(((geoms[g]['pos'] - ctr) ** 2).sum()) + geoms[g]['r'] + geoms[g]['hl'] for g in b['geoms'])
+    mmax = max(classes[c]['margin'] for c in b['cls'])
+    ext = np.array([geoms[g]['r'] + np.abs(geoms[g]['dir']) * geoms[g]['hl'] for g in b['geoms']])
+    lo, hi = (pts - ext).min(0), (pts + ext).max(0)
+    rows.append(dict(begin=len(pairs), end=len(pairs) + len(b['geoms']), box=b['box'], link=links.pop(), cap=b['cap'], center=ctr, reach=rad + mmax + 1e-6,
+                     obb_center=0.5 * (lo + hi), obb_half=0.5 * (hi - lo) + mmax + 1e-6))
+    pairs += [(g, b['box']) for g in b['geoms']]
+    pcls += b['cls']
+  col = lambda k, dt=float: np.array([r[k] for r in rows], dt)
+  d.update(col_sph_link=np.array([g['link'] for g in geoms], np.int32), col_sph_pos=np.array([g['pos'] for g in geoms]), col_sph_r=np.array([g['r'] for g in geoms]),
+           col_sph_dir=np.array([g['dir'] for g in geoms]), col_sph_hl=np.array([g['hl'] for g in geoms]),
+           col_box_kind=np.array([b['kind'] for b in boxes], np.int32), col_box_link=np.array([b['link'] for b in boxes], np.int32),
+           col_box_pos=np.array([b['pos'] for b in boxes]), col_box_quat=np.array([b['quat'] for b in boxes]), col_box_half=np.array([b['half'] for b in boxes]),
+           col_pair=np.array(pairs, np.int32).reshape(-1, 2), col_pair_cls=np.array(pcls, np.int32),
+           col_cls_mu=np.array([c['mu'] for c in classes]), col_cls_solref=np.array([c['solref'] for c in classes], float),
+           col_cls_solimp=np.array([c['solimp'] for c in classes], float), col_cls_margin=np.array([c['margin'] for c in classes]),
+           col_cls_invw=np.array([c['invw'] for c in classes]),
+           col_blk_begin=col('begin', np.int32), col_blk_end=col('end', np.int32), col_blk_box=col('box', np.int32), col_blk_link=col('link', np.int32),
+           col_blk_cap=col('cap', np.int32), col_blk_center=col('center'), col_blk_reach=col('reach'), col_blk_obb_center=col('obb_center'),
+           col_blk_obb_half=col('obb_half'), max_contacts=np.int32(max_con))
+  return d
+
+
+def expected_pairs(d, hits):
+  """the statement of the contact list that the tests hold every implementation to: of the pairs that touch (`hits`, any iterable of pair indices), the
+  first ones in list order, at most cap[b] per block, at most max_con in all"""
+  out = []
+  for b in range(len(d['col_blk_begin'])):
+    mine = [p for p in sorted(set(hits)) if d['col_blk_begin'][b] <= p < d['col_blk_end'][b]]
+    out += mine[:int(d['col_blk_cap'][b])]
+  return out[:int(d['max_contacts'])]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ exact geometry
+class LD:
+  num = staticmethod(lambda x: np.longdouble(float(x)))
+  sqrt = staticmethod(np.sqrt)
+
+
+class MP:
+  num = staticmethod(lambda x: mpmath.mpf(float(x)))
+  sqrt = staticmethod(mpmath.sqrt)
+
+
+def vec(F, v):
+  return [F.num(x) for x in v]
+
+
+def dot(a, b):
+  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
+
+
+def axpy(a, s, b):
+  return [a[k] + s * b[k] for k in range(3)]
+
+
+def sub(a, b):
+  return [a[k] - b[k] for k in range(3)]
+
+
+def rot(F, q):
+  """columns = images of the basis vectors under v -> q v conj(q), q normalised in F"""
+  w, x, y, z = vec(F, q)
+  n = F.sqrt(w * w + x * x + y * y + z * z)
+  w, x, y, z = w / n, x / n, y / n, z / n
+  return [[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+          [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+          [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]
+
+
+def mat_mul(A, B):
+  return [[sum(A[i][k] * B[k][j] for k in range(3)) for j in range(3)] for i in range(3)]
+
+
+def mat_vec(R, v):
+  return [dot(R[i], v) for i in range(3)]
+
+
+def mat_tvec(R, v):
+  return [R[0][i] * v[0] + R[1][i] * v[1] + R[2][i] * v[2] for i in range(3)]
+
+
+def frame(F, pos, quat, link, lpos, lquat=None):
+  """world position (and rotation) of a point / frame given in `link`'s frame (link < 0: the world)"""
+  p = vec(F, lpos)
+  R = rot(F, lquat) if lquat is not None else None
+  if link >= 0:
+    Rl = rot(F, quat[link])
+    p = axpy(vec(F, pos[link]), 1, mat_vec(Rl, p))
+    R = mat_mul(Rl, R) if R is not None else None
+  return p, R
+
+
+def sphere_box(F, c, r, pb, Rb, h):
+  """sphere of radius r (0: a point) at c against the box (centre pb, axes = columns of Rb, half extents h), from the definition: the nearest point of the box to a
+  centre outside it lies on the face, edge or vertex that the centre's region names; a centre inside leaves through the nearest of the six faces.
+  -> (region, [(dist, n, p), ...]): signed distance, unit normal from the box to the sphere, contact point = surface point + n dist / 2; more than one answer only where
+  the nearest face is not unique"""
+  x = mat_tvec(Rb, sub(c, pb))
+  h = vec(F, h)
+  r = F.num(r)
+  s = [-1 if x[i] < -h[i] else (1 if x[i] > h[i] else 0) for i in range(3)]
+  out = [i for i in range(3) if s[i]]
+  zero, one = F.num(0), F.num(1)
+  ans = []
+  if len(out) == 1:                             # face: distance along its axis
+    i = out[0]
+    nl = [zero] * 3; nl[i] = one * s[i]
+    q = list(x); q[i] = s[i] * h[i]
+    ans.append((s[i] * x[i] - h[i] - r, nl, q))
+  elif len(out) == 2:                           # edge: distance in the plane across it, the surface point keeps the coordinate along it
+    i, j = out
+    k = 3 - i - j
+    di, dj = x[i] - s[i] * h[i], x[j] - s[j] * h[j]
+    nd = F.sqrt(di * di + dj * dj)
+    nl = [zero] * 3; nl[i], nl[j] = di / nd, dj / nd
+    q = [zero] * 3; q[i], q[j], q[k] = s[i] * h[i], s[j] * h[j], x[k]
+    ans.append((nd - r, nl, q))
+  elif len(out) == 3:                           # vertex
+    q = [s[i] * h[i] for i in range(3)]
+    d = sub(x, q)
+    nd = F.sqrt(dot(d, d))
+    ans.append((nd - r, [d[k] / nd for k in range(3)], q))
+  else:                                         # inside: the six faces' gaps
+    gaps = [(h[i] - sg * x[i], i, sg) for i in range(3) for sg in (1, -1)]
+    gmin = min(g[0] for g in gaps)
+    for g, i, sg in gaps:
+      if g == gmin:
+        nl = [zero] * 3; nl[i] = one * sg
+        q = list(x); q[i] = sg * h[i]
+        ans.append((-g - r, nl, q))
+  res = []
+  for dist, nl, q in ans:
+    n = mat_vec(Rb, nl)
+    res.append((dist, n, axpy(axpy(pb, 1, mat_vec(Rb, q)), dist / 2, n)))
+  return tuple(s), res
+
+
+SEG_KINDS = ('II', 'A-', 'A+', 'B-', 'B+', 'E--', 'E-+', 'E+-', 'E++')
+
+
+def seg_seg(F, a, u, ha, b, v, hb):
+  """closest points of the segments a + s u (|s| <= ha) and b + t v (|t| <= hb) by enumeration: the interior-interior stationary point, the four projections of an
+  endpoint onto the other segment's interior, the four endpoint pairs; the minimum over the admissible ones -> [(kind, s, t, d2), ...] (all of those at the minimum)"""
+  ha, hb = F.num(ha), F.num(hb)
+  w = sub(a, b)
+  uu, vv, uv, uw, vw = dot(u, u), dot(v, v), dot(u, v), dot(u, w), dot(v, w)
+  cands = []
+  det = uu * vv - uv * uv
+  if det > 0:
+    s, t = (uv * vw - vv * uw) / det, (uu * vw - uv * uw) / det
+    if abs(s) <= ha and abs(t) <= hb:
+      cands.append(('II', s, t))
+  for sg, nm in ((-1, 'A-'), (1, 'A+')):        # endpoint of A onto B
+    t = (vw + sg * ha * uv) / vv
+    if abs(t) <= hb:
+      cands.append((nm, sg * ha, t))
+  for sg, nm in ((-1, 'B-'), (1, 'B+')):        # endpoint of B onto A
+    s = (sg * hb * uv - uw) / uu
+    if abs(s) <= ha:
+      cands.append((nm, s, sg * hb))
+  for sa, sb in itertools.product((-1, 1), (-1, 1)):
+    cands.append(('E' + '-+'[sa > 0] + '-+'[sb > 0], sa * ha, sb * hb))
+  full = []
+  for nm, s, t in cands:
+    d = sub(axpy(a, s, u), axpy(b, t, v))
+    full.append((nm, s, t, dot(d, d)))
+  dmin = min(c[3] for c in full)
+  return [c for c in full if c[3] == dmin]
+
+
+def edge_capsule(F, a, u, ha, b, v, hb, rad):
+  """edge (segment A) against a capsule of radius rad about segment B -> [(kind, dist, n, p), ...]: normal from the capsule's axis to the edge, contact point on the
+  capsule's surface + n dist / 2"""
+  res = []
+  for nm, s, t, d2 in seg_seg(F, a, u, ha, b, v, hb):
+    pc = axpy(b, t, v)
+    d = sub(axpy(a, s, u), pc)
+    nd = F.sqrt(d2)
+    n = [d[k] / nd for k in range(3)]
+    dist = nd - F.num(rad)
+    res.append((nm, dist, n, axpy(pc, F.num(rad) + dist / 2, n)))
+  return res
+
+
+def exact_contact(F, d, pos, quat, pi):
+  """the exact answers for pair pi of tables d with the links' world frames (pos, quat: float64, taken as exact) -> (label, [(dist, n, p), ...])"""
+  gi, bi = (int(x) for x in d['col_pair'][pi])
+  c, _ = frame(F, pos, quat, int(d['col_sph_link'][gi]), d['col_sph_pos'][gi])
+  pb, Rb = frame(F, pos, quat, int(d['col_box_link'][bi]), d['col_box_pos'][bi], d['col_box_quat'][bi])
+  h = d['col_box_half'][bi]
+  if int(d['col_box_kind'][bi]) == 1:
+    lk = int(d['col_sph_link'][gi])
+    u = vec(F, d['col_sph_dir'][gi])
+    if lk >= 0:
+      u = mat_vec(rot(F, quat[lk]), u)
+    v = [Rb[k][2] for k in range(3)]
+    res = edge_capsule(F, c, u, d['col_sph_hl'][gi], pb, v, F.num(h[2]) - F.num(h[0]), h[0])
+    return '|'.join(r[0] for r in res), [r[1:] for r in res]
+  return sphere_box(F, c, d['col_sph_r'][gi], pb, Rb, h)
+
+
+def as_float(v):
+  return np.array([float(x) for x in v])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ closed form (peg)
+def peg_alpha(d, cls, dist):
+  """One contact on the peg's free body, frictionless by symmetry (mpmath): gravity 0, qvel 0, one sphere at the origin of link 14 (= its centre of mass) against a
+  world-fixed box, elliptic cone, dist < margin.  The unconstrained acceleration of dofs 9-14 is zero; the normal row is n on the three slides and zero on the rotation
+  dofs (the contact point lies on the line through the centre of mass along n); only it has a reference acceleration arn = -k d r, r = dist - margin.  The minimiser of
+  1/2 a' M a + 1/2 |J a - aref|^2 / R0 is a = alpha n on the slides with alpha = arn / (1 + m R0), no angular acceleration: there (N, T) = (alpha - arn, 0), N < 0, which is
+  the cone's quadratic zone.  -> alpha"""
+  solref, solimp = d['col_cls_solref'][cls], d['col_cls_solimp'][cls]
+  r = mpmath.mpf(dist) - mpmath.mpf(float(d['col_cls_margin'][cls]))
+  assert r < 0
+  k, _ = pr.kb_ref(solref, solimp, float(d['timestep']))
+  imp = pr.impedance_ref(solimp, r)
+  R0 = max((1 - imp) / imp * mpmath.mpf(float(d['col_cls_invw'][cls])), mpmath.mpf('1e-15'))
+  return -k * imp * r / (1 + mpmath.mpf(float(d['mass'][14])) * R0)
+
+
+_Q = lambda ax, ang: np.concatenate([[np.cos(0.5 * ang)], np.sin(0.5 * ang) * np.asarray(ax, float) / np.linalg.norm(ax)])
+PEG_RHO = 0.01                                  # radius of the closed-form sphere
+
+
+def peg_closed_form_table(free_inertia=1e-4):
+  """three rotated world boxes a metre apart: the sphere (radius PEG_RHO) at the origin of link 14 against box 0 with class A and against box 1 with class B, a point
+  (radius 0) at the same place against box 2 with class A; no gravity, no drag row"""
+  boxes = [box(-1, (0.0, 0.6, 0.5), _Q((1, 2, 3), 0.7), (0.03, 0.05, 0.04)), box(-1, (0.0, 0.6, 1.5), _Q((-2, 1, 0.5), 1.9), (0.06, 0.02, 0.035)),
+           box(-1, (1.0, 0.6, 0.5), _Q((0.3, -1, 2), 2.6), (0.025, 0.045, 0.07))]
+  geoms = [geom(14, (0, 0, 0), PEG_RHO), geom(14, (0, 0, 0), 0.0)]
+  blocks = [block(0, [0], 0), block(1, [0], 1), block(2, [1], 0)]
+  return synth('sawyer_peg', boxes, geoms, blocks, [CLS_A, CLS_B], 12, gravity=(0, 0, 0), free_inertia=free_inertia)
+
+
+_DIRS = {1: (1.0,), 2: (0.6, 0.8), 3: (0.48, 0.6, 0.64)}      # unit offsets over a region's outside axes: every component >= 0.48
+_INNER = (0.35, -0.55, 0.7)                    # a centre's coordinates along the other axes, as fractions of the half extents
+
+
+def region_points(h, nd):
+  """one point per outside region of a box with half extents h, at distance nd from it: -> [(region, x_local)]; every coordinate is at least 0.48 nd / 0.3 h_i from the
+  planes |x_i| = h_i that bound the regions"""
+  out = []
+  for s in itertools.product((-1, 0, 1), repeat=3):
+    ax = [i for i in range(3) if s[i]]
+    if not ax:
+      continue
+    x = np.array([_INNER[i] * h[i] for i in range(3)])
+    for i, g in zip(ax, _DIRS[len(ax)][::(-1 if sum(s) < 0 else 1)]):
+      x[i] = s[i] * (h[i] + g * nd)
+    out.append((s, x))
+  return out
+
+
+def inside_points(h, gap):
+  """one centre inside the box near each of its six faces, `gap` below it (the other faces at least 0.3 h_i away) -> [((axis, sign), x_local)]"""
+  out = []
+  for i in range(3):
+    for sg in (1, -1):
+      x = np.array([_INNER[k] * h[k] for k in range(3)])
+      x[i] = sg * (h[i] - gap)
+      out.append(((i, sg), x))
+  return out
+
+
+def peg_closed_form_states(d):
+  """-> list of dict(qpos, pair, cls, hit): the free body's origin in every outside region and inside near every face of each of the three boxes; distances from deep
+  penetration to just inside the margin (hit) and just outside it (no contact); orientations of the body vary (the sphere sits at its origin)"""
+  q0 = np.array(d['qpos0'], float)
+  states, k = [], 0
+  for pi in range(3):
+    gi, bi = (int(x) for x in d['col_pair'][pi])
+    cls = int(d['col_pair_cls'][pi])
+    rho, margin = float(d['col_sph_r'][gi]), float(d['col_cls_margin'][cls])
+    h, pb = d['col_box_half'][bi], d['col_box_pos'][bi]
+    Rb = np.array([[float(x) for x in row] for row in rot(LD, d['col_box_quat'][bi])])
+    dists = [0.4 * margin, margin * (1 - 1e-6), margin * (1 + 1e-6)] + ([-0.006, -0.001] if rho > 0 else [])
+    pts = [(x, dist < margin) for dist in dists for _, x in region_points(h, rho + dist)] + [(x, True) for gap in (0.002, 0.006) for _, x in inside_points(h, gap)]
+    for x, hit in pts:
+      q = q0.copy()
+      q[9:12] = pb + Rb @ x
+      q[12:16] = _Q((np.sin(k), np.cos(2.0 * k), 0.3), 0.37 * k)
+      states.append(dict(qpos=q, pair=pi, cls=cls, hit=hit))
+      k += 1
+  return states
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ moving box, ties (peg)
+def peg_moving_box_table():
+  """the box rides on the free body (link 14, off its origin, rotated in it); a world-fixed sphere and a world-fixed point are tested against it"""
+  boxes = [box(14, (0.02, -0.01, 0.03), _Q((2, -1, 1), 1.1), (0.03, 0.05, 0.04))]
+  geoms = [geom(-1, (0.3, 0.5, 0.6), PEG_RHO), geom(-1, (-0.4, 0.7, 0.9), 0.0)]
+  return synth('sawyer_peg', boxes, geoms, [block(0, [0], 0), block(0, [1], 1)], [CLS_A, CLS_B], 12, free_inertia=1e-4)
+
+
+def peg_moving_box_states(d):
+  """the body posed so that the world sphere / point sits in every region of the moving box (and inside near every face) -> list of dict(qpos, pair, hit)"""
+  q0 = np.array(d['qpos0'], float)
+  Rl = np.array([[float(x) for x in row] for row in rot(LD, d['col_box_quat'][0])])
+  states, k = [], 0
+  for pi in range(2):
+    gi = int(d['col_pair'][pi][0])
+    rho, margin, h = float(d['col_sph_r'][gi]), float(d['col_cls_margin'][int(d['col_pair_cls'][pi])]), d['col_box_half'][0]
+    dists = [0.4 * margin, margin * (1 + 1e-6)] + ([-0.004] if rho > 0 else [])
+    pts = [(x, dist < margin) for dist in dists for _, x in region_points(h, rho + dist)] + [(x, True) for _, x in inside_points(h, 0.003)]
+    for x, hit in pts:
+      qb = _Q((np.cos(k), 0.4, np.sin(3.0 * k)), 0.5 + 0.41 * k)
+      Rw = np.array([[float(v) for v in row] for row in rot(LD, qb)])
+      q = q0.copy()
+      q[9:12] = d['col_sph_pos'][gi] - Rw @ (d['col_box_pos'][0] + Rl @ x)      # world sphere = body origin + Rw (box centre + Rl x)
+      q[12:16] = qb
+      states.append(dict(qpos=q, pair=pi, hit=hit))
+      k += 1
+  return states
+
+
+def peg_tie_table():
+  """an axis-aligned world box at the origin and the sphere at the origin of link 14 (three slides along the world axes from the world origin): the centre's box
+  coordinates are the slides' qpos exactly"""
+  return synth('sawyer_peg', [box(-1, (0, 0, 0), (1, 0, 0, 0), (0.0625, 0.0625, 0.125))], [geom(14, (0, 0, 0), PEG_RHO)], [block(0, [0], 0)], [CLS_A], 12)
+
+
+PEG_TIE_CENTRES = ((0.03125, 0.03125, 0.0), (0.03125, -0.03125, 0.015625), (-0.046875, 0.015625, 0.0), (0.046875, 0.046875, 0.109375), (0.0, 0.0, 0.0))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ lane-mapping tables
+SPH_R, FLOOR_TOP = 0.004, 0.3                  # the rows' spheres; the top face of the world box they rest on
+REST_ARM = np.array([0.2, -1.0, 0.1, 1.2, -0.1, 0.6, 0.3, 0.02, -0.015])      # within every limit; the hand's frame at this pose carries the arm-side sets
+
+
+def arm_frame(name, link=6, weld=False):
+  """world frame (pos, quat, 3x3) of an arm link at REST_ARM, by the numpy restatement's kinematics (weld: of the attachment the mocap weld holds)"""
+  lm = po.LinkModel(shipped(name))
+  q = np.array(lm.qpos0, float)
+  q[:9] = REST_ARM
+  pos, quat, _ = lm.kinematics(q)
+  if weld:
+    return lm.attachment(pos, quat, int(lm.weld_att))
+  return pos[link], quat[link], po.quat_mat(quat[link])
+
+
+def row_geoms(link, origin, n, hits, axis=0, up=2, lift=0.02):
+  """n spheres of radius SPH_R in a row along `axis` from `origin` (link frame), 4 mm apart: those in `hits` at the origin's height along `up`, the others `lift` above"""
+  out = []
+  for k in range(n):
+    p = np.array(origin, float)
+    p[axis] += 0.004 * k
+    p[up] += 0.0 if k in hits else lift
+    out.append(geom(link, p, SPH_R))
+  return out
+
+
+def peg_rows_table(rows, max_con, hand_rows=(), free_inertia=1e-4):
+  """rows: (n pairs, pair indices that touch, cap) per block -- spheres on the free body (link 14) over a world floor box (top face at FLOOR_TOP, turned about z), the body
+  lying 1 mm deep: in every state of peg_rows_states the spheres named in `hits` touch and no other does.  hand_rows: blocks of the same form listed FIRST, their spheres
+  on the hand (link 6) over a world box laid under the hand's frame at REST_ARM.
+  -> (tables, hits: the pair indices that touch when the hand is at REST_ARM and the body lies on the floor)"""
+  boxes = [box(-1, (0.1, 0.6, FLOOR_TOP - 0.02), _Q((0, 0, 1), 0.3), (0.5, 0.5, 0.02))]
+  geoms, blocks, hits = [], [], []
+  if hand_rows:
+    hp, hq, hR = arm_frame('sawyer_peg')
+    boxes.append(box(-1, hp + hR @ np.array([0.03, 0.0, 0.15 - (SPH_R - 0.001) - 0.02]), hq, (0.2, 0.2, 0.02)))     # its top face 1 mm into the spheres at local z = 0.15
+  npair = 0
+  for j, (n, hit, cap) in enumerate(hand_rows):
+    g0 = len(geoms)
+    geoms += row_geoms(6, (0.0, 0.01 * j, 0.15), n, hit)
+    blocks.append(block(1, range(g0, g0 + n), 0, cap))
+    hits += [npair + k for k in hit]; npair += n
+  for j, (n, hit, cap) in enumerate(rows):
+    g0 = len(geoms)
+    geoms += row_geoms(14, (-0.002 * n, 0.01 * j - 0.02, 0.0), n, hit)
+    blocks.append(block(0, range(g0, g0 + n), j % 2, cap))
+    hits += [npair + k for k in hit]; npair += n
+  return synth('sawyer_peg', boxes, geoms, blocks, [CLS_A, dict(CLS_A, mu=0.7, solref=(0.02, 1.0))], max_con, free_inertia=free_inertia), hits
+
+
+def rest_state(d, n, seed, hand_near=None, qvel_scale=0.0):
+  """n states with the arm at REST_ARM (hand_near[i] False: the shoulder lifted by 0.5 rad, which takes the hand's sets out of reach), the fingers and the mocap target
+  (within millimetres of the hand at REST_ARM, so that the weld does not dwarf the contacts) varied -- none of which moves the hand's frame
+  -> qpos, qvel, mocap_pos, mocap_quat, ctrl"""
+  rng = np.random.default_rng(seed)
+  nv = len(d['parent'])
+  qpos = np.tile(np.array(d['qpos0'], float), (n, 1))
+  qpos[:, :9] = REST_ARM
+  qpos[:, 7] = rng.uniform(0.005, 0.035, n); qpos[:, 8] = rng.uniform(-0.025, -0.005, n)
+  if hand_near is not None:
+    qpos[~np.asarray(hand_near, bool), 1] += 0.5
+  qvel = rng.normal(size=(n, nv)) * qvel_scale
+  wp, wq = arm_frame('sawyer_peg' if nv == 15 else 'sawyer_door', weld=True)
+  mp = wp + rng.normal(size=(n, 3)) * 0.002
+  mq = wq + rng.normal(size=(n, 4)) * 0.002
+  return qpos, qvel, mp, mq, qpos[:, 7:9] + rng.normal(size=(n, 2)) * 0.002
+
+
+def peg_rows_states(d, n, seed, body_on_floor=None, hand_near=None, qvel_scale=0.0):
+  """the free body lying on the floor box (body_on_floor[i] False: half a metre above it, out of every block's reach), moved about over it, turned about z and tilted by up
+  to 2 mrad (0.3 mm over the rows' 130 mm: the touching spheres stay between 0.3 and 1.7 mm deep, the lifted ones 18 mm clear)"""
+  qpos, qvel, mp, mq, ctrl = rest_state(d, n, seed, hand_near, qvel_scale)
+  rng = np.random.default_rng(seed + 1000)
+  on = np.ones(n, bool) if body_on_floor is None else np.asarray(body_on_floor, bool)
+  for i in range(n):
+    qpos[i, 9:12] = [0.1 + rng.uniform(-0.05, 0.05), 0.6 + rng.uniform(-0.05, 0.05), FLOOR_TOP + SPH_R - 0.001 + (0.0 if on[i] else 0.5)]
+    qz, qt = _Q((0, 0, 1), rng.uniform(-3, 3)), _Q((rng.normal(), rng.normal(), 0), rng.uniform(0, 0.002))
+    qpos[i, 12:16] = po.quat_mul(qt, qz)
+  return qpos, qvel, mp, mq, ctrl
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ door: edges vs capsules
+CAP_RAD, CAP_HALF, EDGE_HL = 0.008, 0.03, 0.02
+CLS_CAP = cls_row(solref=(0.01, 1.0), solimp=(0.97, 0.99, 0.01, 0.5, 2.0), margin=0.001, invw=4.8)
+CLS_WIDE = dict(CLS_CAP, margin=0.005)
+
+
+def _scene(i):
+  return np.array([0.05 * (i % 8) - 0.15, 0.06 * (i // 8), 0.25])           # origin of scene i in the hand's frame
+
+
+def door_segment_cases():
+  """one (edge, capsule) pair per closest-point kind, in a scene frame with the capsule's axis along z at the origin: -> [(label, edge centre, edge direction)]
+  (class CLS_WIDE: margin 5 mm, so that every case is a contact without fine placement; the clearances from a change of kind are millimetres)"""
+  r = CAP_RAD
+  cases = [('II', (r + 0.001, 0.002, 0.005), (0.1, 1.0, 0.3)),
+           ('A-', (0.03, 0.001, 0.01), (1.0, 0.2, 0.1)), ('A+', (0.03, 0.001, -0.01), (-1.0, 0.2, 0.1)),
+           ('B+', (0.006, 0.001, CAP_HALF + 0.006), (0.05, 1.0, 0.0)), ('B-', (0.006, 0.001, -CAP_HALF - 0.006), (0.05, 1.0, 0.0))]
+  for sa, sb in itertools.product((-1, 1), (-1, 1)):
+    cases.append(('E' + '-+'[sa > 0] + '-+'[sb > 0], (0.006, -sa * (EDGE_HL + 0.003), sb * (CAP_HALF + 0.006)), (0.0, 1.0, 0.05 * sb * -sa)))
+  cases += [('near-parallel, den > 1e-12', (r + 0.002, 0.0, 0.04), (1e-5, 0.0, 1.0)), ('near-parallel, den <= 1e-12', (r + 0.002, 0.001, 0.02), (5e-7, 0.0, 1.0)),
+            ('parallel', (0.0, r + 0.002, -0.015), (0.0, 0.0, 1.0)), ('meeting', (0.0, 0.0, 0.01), (1.0, 0.0, 0.0))]
+  return cases
+
+
+def door_scene_table(scenes, max_con=8, door_rows=()):
+  """scenes: per block (kind 'capsule' | 'box', [(edge centre, edge direction) | sphere centre, ...] in the scene frame, class index, cap) -- the edges / spheres ride on the
+  hand (link 6), the capsule (axis = scene z, at the scene's origin) / box (half 3 cm, centred 3 cm below the scene's origin) is fixed to the world where scene i lies when
+  the arm is at REST_ARM.  door_rows: blocks listed LAST, rows of spheres on the door (link 9) over a world box laid under them for the door angle -0.3.
+  classes: 0 CLS_CAP (margin 1 mm), 1 CLS_WIDE (margin 5 mm)"""
+  hp, hq, hR = arm_frame('sawyer_door')
+  boxes, geoms, blocks = [], [], []
+  for i, (kind, items, cls, cap) in enumerate(scenes):
+    o = _scene(i)
+    g0 = len(geoms)
+    if kind == 'capsule':
+      boxes.append(capsule(-1, hp + hR @ o, hq, CAP_RAD, CAP_HALF))
+      geoms += [geom(6, o + np.asarray(c, float), 0.0, e, EDGE_HL) for c, e in items]
+    else:
+      boxes.append(box(-1, hp + hR @ (o + [0, 0, -0.03]), hq, (0.03, 0.03, 0.03)))
+      geoms += [geom(6, o + np.asarray(c, float), SPH_R) for c in items]
+    blocks.append(block(len(boxes) - 1, range(g0, g0 + len(items)), cls, cap))
+  if door_rows:
+    lm = po.LinkModel(shipped('sawyer_door'))
+    q = np.zeros(10); q[:9] = REST_ARM; q[9] = -0.3
+    pos, quat, _ = lm.kinematics(q)
+    R9 = po.quat_mat(quat[9])
+    # (the box's face looks along the door's y: across its hinge axis, so that the contacts turn the door)
+    boxes.append(box(-1, pos[9] + R9 @ np.array([0.2, 0.1 - (SPH_R - 0.001) - 0.02, 0.0]), quat[9], (0.15, 0.02, 0.1)))
+    for j, (n, hit, cap) in enumerate(door_rows):
+      g0 = len(geoms)
+      geoms += row_geoms(9, (0.15, 0.1, 0.01 * j), n, hit, up=1)
+      blocks.append(block(len(boxes) - 1, range(g0, g0 + n), 0, cap))
+  return synth('sawyer_door', boxes, geoms, blocks, [CLS_CAP, CLS_WIDE], max_con)
+
+
+def crossing_edges(n, hits, gap_miss=0.003):
+  """n edges across a capsule (closest points interior to both), 3 mm apart along its axis: those in `hits` 0.5 mm inside its surface, the others gap_miss clear of it"""
+  t0 = -0.0015 * (n - 1)
+  return [((CAP_RAD + (-0.0005 if k in hits else gap_miss), 0.0, t0 + 0.003 * k), (0.02, 1.0, 0.01)) for k in range(n)]
+
+
+def door_states(d, n, seed, hand_near=None, door_near=None, qvel_scale=0.0):
+  """arm at REST_ARM or lifted out of reach; the door at -0.3 (its rows on their box) or at -1.2 (far)"""
+  qpos, qvel, mp, mq, ctrl = rest_state(d, n, seed, hand_near, qvel_scale)
+  qpos[:, 9] = -0.3
+  if door_near is not None:
+    qpos[~np.asarray(door_near, bool), 9] = -1.2
+  return qpos, qvel, mp, mq, ctrl
+
+
+ROW_CONFIGS = {                                   # name: (rows, max_con, hand_rows) of peg_rows_table
+  'size 1': ([(1, [0], 4)], 12, ()),
+  'size 15, last pair': ([(15, [14], 4)], 12, ()),
+  'size 16, last pair': ([(16, [15], 4)], 12, ()),
+  'size 17, only the second chunk': ([(17, [16], 4)], 12, ()),
+  'size 33, only the third chunk': ([(33, [32], 4)], 12, ()),
+  'size 33, last lane of a full chunk and the partial one': ([(33, [15, 31, 32], 4)], 12, ()),
+  'cap inside the first chunk': ([(33, [2, 3, 4, 5, 20], 2)], 12, ()),
+  'cap at the chunk boundary': ([(33, [13, 14, 15, 16, 17], 3)], 12, ()),
+  'cap in the second chunk': ([(33, [14, 15, 16, 17, 18], 3)], 12, ()),
+  'cap in the third chunk': ([(33, [15, 31, 32], 2)], 12, ()),
+  'max_con inside a block, a later block without a slot': ([(17, [0, 3, 8, 15, 16], 8), (5, [1, 2], 4)], 3, ()),
+  'max_con in the second chunk': ([(33, [1, 14, 16, 17, 30, 32], 8), (4, [0], 4)], 4, ()),
+  'cap and max_con at once': ([(17, [0, 1, 2], 2), (17, [14, 15, 16], 2), (3, [0, 1, 2], 3)], 4, ()),
+  'twelve slots over four blocks': ([(16, list(range(16)), 4), (15, list(range(15)), 4), (17, [0, 16], 4), (8, [3, 4, 5], 4)], 12, ()),
+  'hand block first': ([(17, [16], 4), (16, [0, 15], 1)], 12, [(5, [1, 2], 1), (17, [15, 16], 4)]),
+}
+
+_BOX2 = [(0, 0, 0.003), (0.01, 0, 0.0031), (0.0, 0.01, 0.02)]      # two spheres 1 mm into the scene's box, one 16 mm clear
+DOOR_CONFIGS = {                                  # name: (scenes, max_con, door_rows, the contact list when the hand and the door are both at their sets) of door_scene_table
+  'capsule run 5 + 5 + 5, a fourth 5 does not fit': ([('capsule', crossing_edges(5, [4]), 0, 1), ('capsule', crossing_edges(5, [0, 2]), 0, 1), ('capsule', crossing_edges(5, [1]), 0, 1),
+                                                     ('capsule', crossing_edges(5, [0, 4]), 0, 2)], 8, (), [4, 5, 11, 15, 19]),
+  'capsule block of 16': ([('capsule', crossing_edges(16, [0, 15]), 0, 2), ('capsule', crossing_edges(4, [3]), 0, 1)], 8, (), [0, 15, 19]),
+  'capsule block of 17': ([('capsule', crossing_edges(4, [0]), 0, 1), ('capsule', crossing_edges(17, [2, 15, 16]), 0, 2), ('capsule', crossing_edges(4, [3]), 0, 1)], 8, (), [0, 6, 19, 24]),
+  'capsule block of 17 first, hits in the second chunk only': ([('capsule', crossing_edges(17, [16]), 0, 2), ('capsule', crossing_edges(4, [1, 2]), 0, 1)], 8, (), [16, 18]),
+  'capsule, box, capsule': ([('capsule', crossing_edges(5, [1, 3]), 0, 1), ('box', _BOX2, 0, 8), ('capsule', crossing_edges(6, [0, 5]), 0, 2)], 8, (), [1, 5, 6, 8, 13]),
+  'box first, then a capsule run': ([('box', _BOX2, 0, 1), ('capsule', crossing_edges(5, [2]), 0, 1), ('capsule', crossing_edges(5, [0]), 0, 1)], 8, (), [0, 5, 8]),
+  'a capsule block near without a hit': ([('capsule', crossing_edges(5, []), 0, 1), ('capsule', crossing_edges(5, [2]), 0, 1)], 8, (), [7]),
+  'max_con inside a capsule run': ([('capsule', crossing_edges(5, [0, 1]), 0, 2), ('capsule', crossing_edges(5, [3, 4]), 0, 2), ('capsule', crossing_edges(5, [0]), 0, 1)], 3, (), [0, 1, 8]),
+  'hand sets first, door rows last': ([('capsule', crossing_edges(5, [1]), 0, 1), ('box', _BOX2, 0, 8)], 8, [(17, [0, 16], 4), (33, [32], 4)], [1, 5, 6, 8, 24, 57]),
+}
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ closed form: figures
+def closed_form_exact(d, lm, states):
+  """-> per state None (no contact) or (alpha, exact normal, group), mpmath -> float"""
+  out = []
+  for s in states:
+    if not s['hit']:
+      out.append(None)
+      continue
+    pos, quat, _ = lm.kinematics(s['qpos'])
+    _, ans = exact_contact(MP, d, pos, quat, s['pair'])
+    dist, n, _ = ans[0]
+    edge = abs(float(dist) - float(d['col_cls_margin'][s['cls']])) < 1e-8
+    out.append((float(peg_alpha(d, s['cls'], dist)), as_float(n), 'edge of the margin' if edge else 'interior'))
+  return out
+
+
+def closed_form_figures(d, lm, states, qacc, exact=None):
+  """qacc [len(states), 15] of some implementation on peg_closed_form_states against peg_alpha and the exact normal (mpmath), worst over the contact states of a group:
+  alpha: | |qacc[9:12]| / alpha - 1 |;  angle: | qacc[9:12] / |qacc[9:12]| - n |, the angle between qacc[9:12] and the exact normal (2 for a normal of the wrong sign);  angular: |qacc[12:15]|_max / alpha [rad / m].
+  Groups: 'edge of the margin' = contact states within 1e-8 m of the margin (alpha is proportional to r = dist - margin, which cancels there), 'interior' = the rest.
+  -> {group: dict(alpha, angle, angular, n)}"""
+  fig = {g: dict(alpha=0.0, angle=0.0, angular=0.0, n=0) for g in ('interior', 'edge of the margin')}
+  for i, e in enumerate(closed_form_exact(d, lm, states) if exact is None else exact):
+    if e is None:
+      continue
+    al, n, g = e
+    f = fig[g]
+    a = np.asarray(qacc[i], float)
+    mag = np.sqrt(a[9:12] @ a[9:12])
+    f['alpha'] = max(f['alpha'], abs(mag / al - 1.0))
+    f['angle'] = max(f['angle'], float(np.linalg.norm(a[9:12] / mag - n)) if mag > 0 else 2.0)
+    f['angular'] = max(f['angular'], float(np.abs(a[12:15]).max()) / al)
+    f['n'] += 1
+  return fig
+
+
+def print_figures(who, fig):
+  for g, f in fig.items():
+    print(f"COLL-FIG {who} vs closed form, {g} ({f['n']} states): alpha rel {f['alpha']:.3e}  angle {f['angle']:.3e}  angular/alpha {f['angular']:.3e} rad/m")

@@ -82,7 +82,7 @@ struct MTDims {
 // The collision model's pair records, once per workgroup in LDS (the generic kernels read them from global memory inside the timestep: one L2 round trip per
 // near block -- 6.2 k of this model's 56 k cycles per timestep)
 struct PairTabMT {
-  static constexpr int MP = 64;          // (the model has 52 pairs; checked by the host side)
+  static constexpr int MP = 64;          // (the model has 52 pairs; load_collision_model asserts n_pair <= MT_MAXPAIR = MP for nv == 22)
   double pos[MP][3], r[MP], margin[MP];
   int link[MP], cls[MP];
 };
@@ -489,7 +489,7 @@ __device__ __forceinline__ void substep_mt(SharedMT& s, const earl_link_model24&
       for (unsigned int r2 = rest; r2; r2 &= r2 - 1u) {
         const int b = __builtin_ctz(r2);
         const int sz = bt.end[b] - bt.begin[b];
-        if (used + sz > LPE) { if (used == 0) { taken = 1u << b; used = sz; if (sub < sz) { myb = b; myoff = 0; } } break; }      // (a block of more than 32 pairs goes alone; its tail is not tested: the host side refuses such tables)
+        if (used + sz > LPE) { if (used == 0) { taken = 1u << b; used = sz; if (sub < sz) { myb = b; myoff = 0; } } break; }      // (a block of more than 32 pairs goes alone; its tail is not tested: load_collision_model asserts every block <= MT_LPE = LPE pairs for nv == 22)
         if (sub >= used && sub < used + sz) { myb = b; myoff = used; }
         used += sz;
         taken |= 1u << b;

@@ -60,9 +60,10 @@ class Kitchen(PhysicsEnv):
             'steps_since_goal_change', 'last_obs')
 
   def __init__(self, task='all_pairs', reward_type='dense', num_envs=1, device='cuda', seed=0, env_offset=0, scalar_api=None,
-               sensor_noise=True, contacts=True, reset_at_goal=False, auto_reset=False, info='full'):
+               sensor_noise=True, contacts=True, reset_at_goal=False, auto_reset=False, info='full', model='kitchen'):
     """info: 'full' (default) = step() returns the reference's env_info (time, obs_dict incl. the noisy velocity readings, rewards, score, images);
-    'minimal' = only 'success' / 'is_successful' / 'status' (batched) or {} (scalar): no extra Philox draw, concatenation or host copies per step"""
+    'minimal' = only 'success' / 'is_successful' / 'status' (batched) or {} (scalar): no extra Philox draw, concatenation or host copies per step
+    model: the shipped tables' name, or a tables dict with the keys of kitchen_links.npz (tests: synthetic collision tables), passed to physics.DeviceModel"""
     if info not in ('full', 'minimal'):
       raise ValueError(f"info must be 'full' or 'minimal', got {info!r}")
     self.info_mode = info
@@ -92,7 +93,7 @@ class Kitchen(PhysicsEnv):
       raise KeyError(f'kitchen task {task!r}: the reference defines ' + ', '.join(tables.kitchen_tasks())) from None
     self._goal_states = tables.goal_states('kitchen')
     with torch.cuda.device(dev):
-      self.model = physics.DeviceModel('kitchen', device=dev, contacts=contacts)
+      self.model = physics.DeviceModel(model, device=dev, contacts=contacts)
     assert self.model.nv == self.NV
     names = self.model.att_names
     self._site_idx = torch.tensor([names.index(s) for s in glue.KITCHEN_SITES], device=dev)

@@ -65,7 +65,8 @@ class Minitaur(PhysicsEnv):
             'interventions', 'fail_count', 'lifelong_return_t', 'last_obs')
 
   def __init__(self, num_envs=1, device='cuda', seed=0, env_offset=0, scalar_api=None, env_randomizer=True, contacts=True, reset_at_goal=False,
-               auto_reset=False, reward_type='dense'):
+               auto_reset=False, reward_type='dense', model='minitaur'):
+    """model: the shipped tables' name, or a tables dict with the keys of minitaur_links.npz (tests: synthetic collision tables), passed to physics.DeviceModel"""
     if auto_reset or reset_at_goal:
       raise NotImplementedError('minitaur: auto_reset / reset_at_goal do not exist in the reference env')
     del reward_type                                          # (the reference's env has one reward: the loader's reward_type is not passed to it)
@@ -81,7 +82,7 @@ class Minitaur(PhysicsEnv):
     if self.scalar_api and n != 1:
       raise ValueError('scalar_api needs num_envs == 1')
     with torch.cuda.device(dev):
-      self.model = physics.DeviceModel('minitaur', device=dev, contacts=contacts)
+      self.model = physics.DeviceModel(model, device=dev, contacts=contacts)
     assert self.model.nv == self.NV and self.model.nq == self.NQ
     kw = dict(dtype=torch.float64, device=dev)
     self.qpos, self.qvel = torch.zeros(n, self.NQ, **kw), torch.zeros(n, self.NV, **kw)

@@ -17,6 +17,7 @@ from .. import _abi
 MAXV, MAXATT, MAXACT = 16, 8, 4
 MAXSPH, MAXBOX, MAXPAIR, MAXCLS, MAXCON, MAXBLK = 96, 16, 512, 16, 12, 64
 MAXV24, MAXATT24, MAXJEQ, MAXCONNECT = 24, 16, 8, 4
+MT_MAXPAIR, MT_LPE = 64, 32                     # csrc/minitaur_stepper.h PairTabMT::MP, MTDims::LPE (tests/test_collision_pyramid.py holds them to the header)
 MODEL_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'models')
 
 
@@ -240,10 +241,20 @@ def load_collision_model(d):
   assert all((-1 <= np.asarray(d[k])).all() and (np.asarray(d[k]) < nvm).all() for k in ('col_sph_link', 'col_box_link', 'col_blk_link')), 'collision tables: link index'
   if nvm == 23:      # csrc/physics.hip Lim<23>::PACK: several near blocks share a pass of the group's 32 lanes; a block must fit one pass
     assert int(np.max(np.asarray(d['col_blk_end']) - np.asarray(d['col_blk_begin']))) <= 32, 'kitchen collision blocks: at most 32 pairs each'
+    # csrc/physics_stepper.h K9 (Lim<23>::EXTRAS): the iteration's Hessian has the arm's block, every fixture's row against the arm and its diagonal -- no entry between
+    # two fixtures, so a contact may join the arm (the tree of link 0) or the world with at most ONE fixture (every other link: a single-dof tree, load_link_model)
+    par = [int(x) for x in d['parent']]
+    root = lambda l: l if par[l] < 0 else root(par[l])
+    fixture = np.array([root(l) != 0 for l in range(nvm)] + [False])      # (index -1: the world)
+    sl, xl = np.asarray(d['col_sph_link'], np.int64)[prs[:, 0]], np.asarray(d['col_box_link'], np.int64)[prs[:, 1]]
+    assert not (fixture[sl] & fixture[xl] & (sl != xl)).any(), 'kitchen collision pairs: a pair joins at most one fixture (sphere and box on two different fixture links)'
   if nvm == 22:
     # csrc/physics.hip (Lim<22>::CONNECT, K9): a contact's Jacobian is taken to touch the root body's six dofs and the sphere's own chain of at most
     # two hinges -- spheres ride on the root body or on such a chain, boxes are fixed to the world
     par = [int(x) for x in d['parent']]
+    # csrc/minitaur_stepper.h: the tree kernels stage the pair records in LDS (PairTabMT::MP of them) and pack the near blocks onto the group's MTDims::LPE lanes
+    assert c.n_pair <= MT_MAXPAIR, f'minitaur collision model: {c.n_pair} pairs, the tree stepper stages at most PairTabMT::MP = {MT_MAXPAIR} (csrc/minitaur_stepper.h)'
+    assert int(np.max(be - bb)) <= MT_LPE, f'minitaur collision blocks: at most MTDims::LPE = {MT_LPE} pairs each (csrc/minitaur_stepper.h), the largest has {int(np.max(be - bb))}'
     assert all(int(b) < 0 for b in d['col_box_link']), 'minitaur collision model: world-fixed boxes only'
     assert all(int(l) == 5 or (int(l) >= 6 and (par[int(l)] == 5 or (par[int(l)] >= 6 and par[par[int(l)]] == 5))) for l in d['col_sph_link']), 'sphere links: root body or a chain of <= 2 hinges'
   for dst, src in ((c.blk_begin, d['col_blk_begin']), (c.blk_end, d['col_blk_end']), (c.blk_box, d['col_blk_box']),

@@ -66,9 +66,9 @@ class CMinitaur:
   """host-array batch of minitaur envs on the C restatement (oracle_minitaur_reset / oracle_minitaur_rollout): the same call sequence and state
   layout as earl_benchmark_amd.envs.minitaur.Minitaur drives through the HIP library"""
 
-  def __init__(self, n, seed=0, env_offset=0, randomize=True, horizon=0, contacts=True, goal_change_frequency=0):
+  def __init__(self, n, seed=0, env_offset=0, randomize=True, horizon=0, contacts=True, goal_change_frequency=0, model='minitaur'):
     from earl_benchmark_amd.envs import minitaur as mt
-    self.cm = CModel('minitaur', contacts=contacts)
+    self.cm = CModel(model, contacts=contacts)
     self.n = n
     self.goal_table = np.ascontiguousarray(mt.GOAL_LOCATIONS, np.float64)
     self.reset_qpos = np.ascontiguousarray(self.cm.tables['qpos0'], np.float64)

@@ -1,5 +1,5 @@
-"""Synthetic collision tables on the shipped Sawyer door / peg link models, exact contact geometry, and the closed-form response of one
-contact on the peg's free body (TEST INFRASTRUCTURE: a plain module -- no tests, no fixtures).
+"""Synthetic collision tables on the shipped Sawyer door / peg, kitchen and minitaur link models, exact contact geometry, and the closed-form response of one
+contact on the peg's free body (elliptic cone) and on the kitchen's slide cabinet (pyramid cone) (TEST INFRASTRUCTURE: a plain module -- no tests, no fixtures).
 
 Tables: `synth` keeps every structural key of the shipped *_links.npz (tree, joint types, attachments, weld, actuators, limits) and replaces every col_* key and
 max_contacts by a small set given as plain lists.  The block bounds are worked out here exactly as oracle/physics_oracle.py collision_primitives does for the shipped
@@ -63,8 +63,10 @@ def synth(name, boxes, geoms, blocks, classes, max_con, gravity=None, drag=False
     assert not np.any(d['com'][14]) and not np.any(d['mass'][9:14]) and not np.any(d['jnt_armature'][9:15])
   if gravity is not None:
     d['gravity'] = np.asarray(gravity, float)
-  if not drag:
+  if not drag and name != 'minitaur':           # (the minitaur's tables carry no drag row, and its loader refuses one)
     d['dof_drag_G'] = np.zeros(nv)
+  if cone_elliptic is None and name in ('kitchen', 'minitaur'):      # the pyramid models: the key says so whether the shipped file carries it or not
+    cone_elliptic = 0
   if free_inertia is not None:
     d['inertia'] = d['inertia'].copy()
     d['inertia'][14] = [free_inertia] * 3 + [0.0] * 3
@@ -96,6 +98,8 @@ def synth(name, boxes, geoms, blocks, classes, max_con, gravity=None, drag=False
            col_blk_begin=col('begin', np.int32), col_blk_end=col('end', np.int32), col_blk_box=col('box', np.int32), col_blk_link=col('link', np.int32),
            col_blk_cap=col('cap', np.int32), col_blk_center=col('center'), col_blk_reach=col('reach'), col_blk_obb_center=col('obb_center'),
            col_blk_obb_half=col('obb_half'), max_contacts=np.int32(max_con))
+  if name == 'minitaur':                        # as shipped: no second bounding test (csrc/minitaur_stepper.h C0 has none)
+    del d['col_blk_obb_center'], d['col_blk_obb_half']
   return d
 
 
@@ -626,3 +630,312 @@ def closed_form_figures(d, lm, states, qacc, exact=None):
 def print_figures(who, fig):
   for g, f in fig.items():
     print(f"COLL-FIG {who} vs closed form, {g} ({f['n']} states): alpha rel {f['alpha']:.3e}  angle {f['angle']:.3e}  angular/alpha {f['angular']:.3e} rad/m")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ kitchen and minitaur: the pyramid-cone models
+# The kitchen's packed C1-C2 (csrc/physics_stepper.h Lim<23>::PACK: 32 lanes per env, two envs per wave, 64 blocks) and the minitaur tree stepper's own
+# (csrc/minitaur_stepper.h: 32 lanes per env, 8 blocks, 64 pairs staged in LDS): consecutive near blocks of the WAVE share a pass of the GROUP's 32 lanes.
+KITCHEN_REST = np.array([0.148, -1.768, 1.844, -2.477, 0.260, 0.713, 1.595, 0.02, 0.02])      # the arm near the env's initial pose, within every limit
+SLIDE, SLIDE_NEAR, SLIDE_FAR, TILT = 19, 0.05, 0.40, 0.5      # the slide cabinet: a slide along world x without a coupling; the rows' box is tilted about y by TILT
+CLS_K = [CLS_A, dict(CLS_A, mu=0.7, solref=(0.02, 1.0))]
+CLS_MT = [cls_row(mu=1.0, solref=(0.02, 1.0), solimp=(0.9, 0.95, 0.001, 0.5, 2.0), margin=0.001, invw=3.7),
+          cls_row(mu=0.5, solref=(0.02, 1.0), solimp=(0.9, 0.95, 0.001, 0.5, 2.0), margin=0.001, invw=0.43)]
+MT_Z = 0.2                                     # height of the minitaur's root body in the pose the rows are laid out for
+
+
+def link_frames(tables, qpos):
+  """world frames (pos [nv, 3], quat [nv, 4]) of a model's links, by the numpy restatement's kinematics; tables: a shipped name or a dict"""
+  lm = po.LinkModel(shipped(tables) if isinstance(tables, str) else tables)
+  pos, quat, _ = lm.kinematics(np.asarray(qpos, float))
+  return pos, quat
+
+
+def to_link(pos, quat, link, w):
+  """the world point w in `link`'s frame (link < 0: the world)"""
+  return np.asarray(w, float) if link < 0 else po.quat_mat(quat[link]).T @ (np.asarray(w, float) - pos[link])
+
+
+def kitchen_pose(slide=SLIDE_NEAR):
+  q = np.zeros(23)
+  q[:9] = KITCHEN_REST
+  q[SLIDE] = slide
+  return q
+
+
+def minitaur_pose(x=0.0, z=MT_Z):
+  q = np.array(shipped('minitaur')['qpos0'], float)
+  q[:7] = [x, 0.0, z, 1.0, 0.0, 0.0, 0.0]
+  return q
+
+
+def _row_centres(P0, ex, ey, en, j, n, hits, deep):
+  """row j on the face through P0 (in-plane axes ex, ey, outward normal en): n spheres of radius SPH_R 4 mm apart along ey, the row 10 mm along ex from the one before;
+  those in `hits` 1 mm into the face, those in `deep` with the CENTRE 1.5 mm below the face (inside the box), the others 20 mm clear"""
+  out = []
+  for k in range(n):
+    h = -0.0015 if k in deep else (SPH_R - 0.001 if k in hits else SPH_R + 0.02)
+    out.append(P0 + ex * (0.01 * j) + ey * (0.004 * (k - 0.5 * (n - 1))) + en * h)
+  return out
+
+
+def _add_rows(out, frames, rows, box_index, P0, R):
+  """rows: (link, n, hits, cap[, deep]) per block, laid on the face through P0 of box `box_index` (R: the box's world rotation) for the link frames `frames`;
+  out = (geoms, blocks, hits): appended to, hits as pair indices (`deep` ones included)"""
+  geoms, blocks, hits = out
+  npair = sum(len(b['geoms']) for b in blocks)
+  for j, row in enumerate(rows):
+    link, n, hit, cap = row[:4]
+    deep = row[4] if len(row) > 4 else ()
+    g0 = len(geoms)
+    geoms += [geom(link, to_link(*frames, link, w), SPH_R) for w in _row_centres(P0, R[:, 0], R[:, 1], R[:, 2], j, n, hit, deep)]
+    blocks.append(block(box_index, range(g0, g0 + n), j % 2, cap))
+    hits += [npair + k for k in sorted(set(hit) | set(deep))]
+    npair += n
+
+
+def kitchen_rows_table(rows, max_con, hand_rows=(), box_rides=False):
+  """rows: (n pairs, pair indices that touch, cap[, those with the centre inside the box]) per block -- spheres on the slide cabinet (link 19) in rows along y over a
+  world box whose face is tilted about y by TILT, so that its normal has a component along the slide: the contacts push the dof.  With the slide at SLIDE_NEAR the spheres named
+  touch and no other does; at SLIDE_FAR every block is out of reach.  box_rides: the box rides on link 19 instead and the spheres are fixed to the world.
+  hand_rows: blocks of the same form listed FIRST, their spheres on the hand (link 6) over a world box laid under the hand's frame at KITCHEN_REST.
+  -> (tables, hits: the pair indices that touch when the hand is at KITCHEN_REST and the slide at SLIDE_NEAR)"""
+  frames = link_frames('kitchen', kitchen_pose())
+  pos, quat = frames
+  assert np.array_equal(quat[SLIDE], [1.0, 0, 0, 0])
+  qb = _Q((0, 1, 0), -TILT if box_rides else TILT)          # (box riding: tilted the other way, so that the slide's +x takes the BOX away from the spheres)
+  Rb = po.quat_mat(qb)
+  P0 = pos[SLIDE] + np.array([-0.15, 0.1, -0.25])
+  bl, sl = (SLIDE, -1) if box_rides else (-1, SLIDE)
+  boxes = [box(bl, to_link(pos, quat, bl, P0 + 0.3 * Rb[:, 0] - 0.02 * Rb[:, 2]), qb, (0.45, 0.3, 0.02))]
+  out = ([], [], [])
+  if hand_rows:
+    hR = po.quat_mat(quat[6])
+    Ph = pos[6] + hR @ np.array([0.03, 0.0, 0.15])
+    boxes.append(box(-1, Ph + 0.15 * hR[:, 0] - 0.02 * hR[:, 2], quat[6], (0.3, 0.2, 0.02)))
+    _add_rows(out, frames, [(6,) + tuple(r) for r in hand_rows], 1, Ph, hR)
+  _add_rows(out, frames, [(sl,) + tuple(r) for r in rows], 0, P0, Rb)
+  return synth('kitchen', boxes, out[0], out[1], CLS_K, max_con), out[2]
+
+
+def kitchen_states(d, n, seed, hand_near=None, slide_near=None, qvel_scale=0.0):
+  """n states: the arm at KITCHEN_REST (hand_near[i] False: the elbow bent by a further 0.5 rad, which takes the hand's sets 12 cm beyond their reach and keeps the hand inside the env's mocap bounds), the slide at SLIDE_NEAR +- 1 mm (0.5 mm of depth;
+  slide_near[i] False: at SLIDE_FAR), the fingers, the other fixtures (inside their ranges) and the mocap target (millimetres from the weld's attachment) varied
+  -> qpos, qvel, mocap_pos, mocap_quat, ctrl"""
+  rng = np.random.default_rng(seed)
+  qpos = np.tile(kitchen_pose(), (n, 1))
+  lo, hi = np.asarray(d['jnt_range'], float).T
+  qpos[:, 9:] = lo[9:] + rng.uniform(0.2, 0.8, (n, 14)) * (hi[9:] - lo[9:])
+  qpos[:, 7:9] = rng.uniform(0.005, 0.035, (n, 2))
+  qpos[:, SLIDE] = SLIDE_NEAR + rng.uniform(-0.001, 0.001, n)
+  if hand_near is not None:
+    qpos[~np.asarray(hand_near, bool), 3] -= 0.5
+  if slide_near is not None:
+    qpos[~np.asarray(slide_near, bool), SLIDE] = SLIDE_FAR
+  qvel = rng.normal(size=(n, 23)) * qvel_scale
+  lm = po.LinkModel(shipped('kitchen'))
+  wp, wq = np.zeros((n, 3)), np.zeros((n, 4))
+  for i in range(n):                            # the weld's attachment in the env's own pose: the weld does not dwarf the contacts, wherever the arm is
+    pos, quat, _ = lm.kinematics(qpos[i])
+    wp[i], wq[i] = lm.attachment(pos, quat, int(lm.weld_att))
+  return qpos, qvel, wp + rng.normal(size=(n, 3)) * 0.002, wq + rng.normal(size=(n, 4)) * 0.002, qpos[:, 7:9] + rng.normal(size=(n, 2)) * 0.002
+
+
+def minitaur_rows_table(rows, max_con, rows_b=()):
+  """rows: (link, n pairs, pair indices that touch, cap[, those with the centre inside the box]) per block -- the spheres ride on `link` (the root body 5, an upper leg link
+  6 + 4 k / 8 + 4 k or a lower one 7 + 4 k / 9 + 4 k) and lie, with the root body at (0, 0, MT_Z) unturned and the legs at qpos0, in rows on the top face z = 0 of world box A
+  (|x| <= 0.3).  rows_b: blocks listed LAST, laid out the same way on world box B, a metre along x: they touch with the root body at x = 1, where A's are out of reach.
+  Turning the root body about z and moving it in the plane keeps every depth.  -> (tables, hits A, hits B: pair indices)"""
+  frames = link_frames('minitaur', minitaur_pose())
+  boxes = [box(-1, (0.0, 0.0, -0.02), (1, 0, 0, 0), (0.3, 0.4, 0.02)), box(-1, (1.0, 0.0, -0.02), (1, 0, 0, 0), (0.3, 0.4, 0.02))]
+  out = ([], [], [])
+  _add_rows(out, frames, rows, 0, np.array([-0.08, 0.0, 0.0]), np.eye(3))
+  na = len(out[2])
+  _add_rows(out, link_frames('minitaur', minitaur_pose(x=1.0)), rows_b, 1, np.array([0.92, 0.0, 0.0]), np.eye(3))
+  return synth('minitaur', boxes[:2 if rows_b else 1], out[0], out[1], CLS_MT, max_con), out[2][:na], out[2][na:]
+
+
+def minitaur_states(d, n, seed, where):
+  """where[i]: 'A' (the root body over box A), 'B' (over box B) or '-' (half a metre up: no block near); the root body moved by up to 2 cm in the plane and turned by up to
+  0.3 rad about z, the legs at qpos0, at rest -> qpos [n, 23], qvel [n, 22]"""
+  rng = np.random.default_rng(seed)
+  qpos = np.tile(minitaur_pose(), (n, 1))
+  for i in range(n):
+    qpos[i, 0:2] = rng.uniform(-0.02, 0.02, 2) + [1.0 if where[i] == 'B' else 0.0, 0.0]
+    qpos[i, 2] = MT_Z + (0.5 if where[i] == '-' else 0.0)
+    qpos[i, 3:7] = _Q((0, 0, 1), rng.uniform(-0.3, 0.3))
+  return qpos, np.zeros((n, 22))
+
+
+# name: (rows, max_con, hand_rows, box_rides) of kitchen_rows_table.  A pass of the packed walk takes consecutive near blocks while their pairs fit 32 lanes.
+KITCHEN_CONFIGS = {
+  'blocks of 1, 31 and 32: a pass filled exactly, hits in the last lanes': ([(1, [0], 4), (31, [30], 4), (32, [31], 4)], 12, [(32, [31], 4)], False),      # (a 32-pair hand block first: the passes stay 32 | 1 + 31 | 32)
+  '10 + 10 + 10, a 3 that does not fit; the cap binds in the first, a middle and the last block of the pass': ([(10, [1, 2, 3], 2), (10, [0, 5, 9], 2), (10, [7, 8, 9], 2), (3, [0, 1, 2], 2)], 12, [(2, [0, 1], 1)], False),      # (with the hand's 2-pair block the pass is 2 + 10 + 10 + 10: filled exactly)
+  '16 + 16': ([(16, [0, 15], 4), (16, [15], 4)], 12, (), False),
+  'a 32-pair block after a partial pass': ([(5, [4], 4), (32, [0, 31], 4), (2, [1], 2)], 12, (), False),
+  'max_con inside a block, a later near block without a slot': ([(10, [0, 3, 8, 9], 8), (10, [1, 2], 4)], 3, (), False),
+  'max_con between two passes': ([(20, [0, 5, 19], 4), (20, [3, 4], 4), (4, [0], 2)], 4, (), False),
+  '42 blocks, the slide\'s beyond index 32': ([(2, [1], 2)] * 8, 12, [(2, [1], 2)] + [(2, [], 2)] * 32 + [(2, [0], 2)], False),
+  'hand blocks first': ([(17, [16], 4), (16, [0, 15], 1)], 12, [(5, [1, 2], 1), (17, [15, 16], 4)], False),
+  'the box rides on the slide': ([(10, [0, 9], 2), (3, [1], 1)], 12, [(5, [4], 2)], True),
+  'centres inside the box': ([(10, [2], 4, [5, 9]), (4, [], 2, [0])], 12, (), False),
+}
+# env i of 64, two envs per wave: (none, hand), (slide, both), (hand, slide), (both, none) -- the wave's near set differs from the group's in both directions
+HAND_K = np.isin(np.arange(64) % 8, (1, 3, 4, 6))
+LAST_K = np.isin(np.arange(64) % 8, (2, 3, 5, 6))
+NEAR_K = np.isin(np.arange(64) % 8, (1, 2, 3, 5))     # tables with one group of sets: (none, near), (near, near), (none, near), (none, none)
+
+# name: (rows, max_con, rows_b) of minitaur_rows_table: at most 8 blocks, 64 pairs, 32 pairs per block
+MINITAUR_CONFIGS = {
+  '8 + 8 + 8 + 8: a pass filled exactly': ([(7, 8, [7], 4), (9, 8, [0], 4), (6, 8, [3], 4), (5, 8, [7], 4)], 12, ()),
+  '8 + 8 + 8 + 9: the fourth goes to the next pass; caps of 1': ([(7, 8, [7], 4), (11, 8, [0, 1], 1), (8, 8, [3], 4), (5, 9, [7, 8], 1)], 12, ()),      # (pairs 31 and 32 touch: the cap binds across lane 32 of the list)
+  'one block of 32': ([(13, 32, [0, 31], 4), (6, 4, [1], 2)], 12, ()),
+  '64 pairs, twelve contacts, two near blocks without a slot': ([(l, 8, [0, 7], 2) for l in (7, 9, 6, 8, 15, 17, 14, 5)], 12, ()),
+  'caps of 1, max_con inside a pass': ([(7, 8, [1, 2], 1), (9, 8, [0, 5], 1), (10, 8, [4, 5, 6], 3), (5, 8, [0], 1)], 4, ()),
+  'upper links, centres inside the box': ([(6, 5, [0], 4, [3]), (12, 6, [], 2, [5]), (16, 3, [1], 2)], 12, ()),
+  'disjoint near sets': ([(7, 8, [7], 4), (6, 9, [0, 8], 1)], 12, [(9, 8, [2], 2), (5, 20, [19], 4)]),
+}
+WHERE_A = [('-', 'A', 'A', '-', 'A', 'A')[i % 6] for i in range(64)]                                # two envs per wave: (none, all), (all, none), (all, all)
+WHERE_AB = [('A', 'B', 'B', 'A', '-', 'B', 'A', 'A')[i % 8] for i in range(64)]                      # (A, B), (B, A), (none, B), (A, A)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ exact geometry on the two models
+def region_cases(h, margin, radius):
+  """centres in a box's own frame: the 26 outside regions at 0.4 margin, 1e-9 m inside the margin and 1e-9 m outside it (radius > 0: and 4 mm deep), and inside the box 3 mm
+  below each face -> [(x_local, hit)]"""
+  dists = [0.4 * margin, margin * (1 - 1e-6), margin * (1 + 1e-6)] + ([-0.004] if radius > 0 else [])
+  return [(x, dist < margin) for dist in dists for _, x in region_points(h, radius + dist)] + [(x, True) for _, x in inside_points(h, 0.003)]
+
+
+def region_tables(name, qpos, bx, sph_links, radius, classes, chunk):
+  """bx: one box record, on its link.  For the link frames at qpos, every case of region_cases gets a sphere of its own, riding on one of sph_links (in turn) and placed in
+  that link's frame where the case wants its centre; one pair per block (cap 1), `chunk` cases per table (= its max_con, at most the model's block count)
+  -> [(tables, [dict(qpos, pair, hit)])]"""
+  pos, quat = link_frames(name, qpos)
+  pb, Rb = pos[bx['link']] + po.quat_mat(quat[bx['link']]) @ bx['pos'] if bx['link'] >= 0 else bx['pos'], po.quat_mat(bx['quat'])
+  if bx['link'] >= 0:
+    Rb = po.quat_mat(quat[bx['link']]) @ Rb
+  cases = region_cases(bx['half'], classes[0]['margin'], radius)
+  out = []
+  for a in range(0, len(cases), chunk):
+    part = cases[a:a + chunk]
+    geoms = [geom(sph_links[(a + k) % len(sph_links)], to_link(pos, quat, sph_links[(a + k) % len(sph_links)], pb + Rb @ x), radius) for k, (x, _) in enumerate(part)]
+    d = synth(name, [bx], geoms, [block(0, [k], 0, 1) for k in range(len(part))], classes, chunk)
+    out.append((d, [dict(qpos=np.asarray(qpos, float), pair=k, hit=hit) for k, (_, hit) in enumerate(part)]))
+  return out
+
+
+def kitchen_region_tables():
+  """a box riding on the microwave door (link 22, a hinge: the joint turns the box) against spheres on the hand, a finger and the world; a box riding on a finger
+  (link 7) against spheres on the slide cabinet, the microwave door, the other finger and the world; radius 0.01 and radius 0.  (No pair joins two fixtures: the kernel's
+  Hessian has no entry between two of them, and the loader refuses such a pair.)"""
+  q = kitchen_pose(0.21)
+  q[22], q[7], q[8] = -0.7, 0.013, 0.031
+  out = []
+  for radius in (PEG_RHO, 0.0):
+    out += region_tables('kitchen', q, box(22, (0.25, -0.04, 0.1), _Q((1, 2, 3), 0.7), (0.03, 0.05, 0.04)), (6, 7, -1), radius, [CLS_A], 12)
+    out += region_tables('kitchen', q, box(7, (0.0, 0.012, 0.05), _Q((-2, 1, 0.5), 1.9), (0.02, 0.015, 0.03)), (SLIDE, 22, 8, -1), radius, [CLS_B], 12)
+  return out
+
+
+MT_REGION_LINKS = (5, 6, 7, 8, 9, 14, 15, 16, 17)      # the root body; leg 0: both chains' upper and lower links; leg 2 the same
+
+
+def minitaur_region_tables():
+  """world-fixed rotated boxes (the loader allows no other) against spheres on the root body and on upper and lower links of two legs, both chains of each; the root body
+  turned; radius 0.01 and radius 0; 8 cases per table (the model's block count)"""
+  q = minitaur_pose()
+  q[0:7] = np.concatenate([[0.3, -0.2, 0.25], _Q((1, -2, 0.5), 0.8)])
+  q[7:] += 0.1 * np.sin(np.arange(16) * 1.7)
+  out = []
+  for radius in (PEG_RHO, 0.0):
+    out += region_tables('minitaur', q, box(-1, (0.3, -0.1, 0.1), _Q((1, 2, 3), 0.7), (0.03, 0.05, 0.04)), MT_REGION_LINKS, radius, [CLS_MT[0]], 8)
+  return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ closed form (kitchen, pyramid cone)
+def kitchen_closed_form_table():
+  """Two boxes ride on the slide cabinet (link 19: mass 0.34 kg, armature 0.01 kg, a slide along world x in a tree of its own, no coupling), axis-parallel to it; a
+  world-fixed sphere (radius PEG_RHO, class A) stands over the middle of box 0's +x face and a world-fixed point (class B) over the middle of box 1's -x face, each when the
+  slide is where kitchen_closed_form_states puts it.  In this copy of the tables the dof has no dry friction, spring, damping or gravity."""
+  pos, quat = link_frames('kitchen', kitchen_pose(0.0))
+  assert np.array_equal(quat[SLIDE], [1.0, 0, 0, 0])
+  boxes = [box(SLIDE, (-0.3, 0.3, 0.0), (1, 0, 0, 0), (0.03, 0.05, 0.04)), box(SLIDE, (0.5, -0.3, 0.2), (1, 0, 0, 0), (0.06, 0.02, 0.035))]
+  geoms = [geom(-1, pos[SLIDE] + boxes[0]['pos'] + [0.03 + KCF_Q[0], 0, 0], PEG_RHO), geom(-1, pos[SLIDE] + boxes[1]['pos'] + [-0.06 + KCF_Q[1], 0, 0], 0.0)]
+  d = synth('kitchen', boxes, geoms, [block(0, [0], 0), block(1, [1], 1)], [CLS_A, CLS_B], 12, gravity=(0, 0, 0))
+  for k in ('jnt_frictionloss', 'jnt_stiffness', 'jnt_damping'):
+    d[k] = np.array(d[k], float)
+    d[k][SLIDE] = 0.0
+  assert SLIDE not in list(d['jeq_joint1']) + list(d['jeq_joint2']) and int(d['jtype'][SLIDE]) == 1 and int(d['parent'][SLIDE]) == -1
+  return d
+
+
+KCF_Q = (0.1, 0.3)                             # the slide's position at which pair 0 / pair 1 has its surface point ON the face (dist = -radius for the sphere, 0 for the point)
+
+
+def kitchen_closed_form_states(d):
+  """the slide swept so that the sphere / the point goes from inside the box (2 and 6 mm below the face) over deep and shallow penetration to 1e-9 m inside the margin
+  (hit) and 1e-9 m outside it (no contact); the arm and the other fixtures varied, qvel = 0 -> list of dict(qpos, pair, cls, hit, sign: of the dof's acceleration)"""
+  states, k = [], 0
+  for pi, face_sign in ((0, 1.0), (1, -1.0)):
+    cls = int(d['col_pair_cls'][pi])
+    rho, margin = float(d['col_sph_r'][int(d['col_pair'][pi][0])]), float(d['col_cls_margin'][cls])
+    dists = [-rho - 0.006, -rho - 0.002, 0.4 * margin, margin * (1 - 1e-6), margin * (1 + 1e-6)] + ([-0.006, -0.001] if rho > 0 else [])
+    for dist in dists:
+      for rep in range(3):
+        q = kitchen_states(d, 1, 100 + k)[0][0]
+        q[SLIDE] = KCF_Q[pi] - face_sign * (dist + rho)       # the box moves with the slide: the centre's height over the face is the given distance + radius
+        states.append(dict(qpos=q, pair=pi, cls=cls, hit=dist < margin, sign=-face_sign))
+        k += 1
+  return states
+
+
+def kitchen_alpha(d, cls, dist):
+  """The slide dof's acceleration (magnitude) under one pyramid contact whose four edges all have the scalar Jacobian +-1 on it (face normal along the joint axis, tangents
+  across it), qvel = 0, nothing else acting on the dof (mpmath).  Each edge has the regulariser R = 2 mu^2 R0, R0 = max((1 - imp) / imp invw, 1e-15), so D = 1 / R, and the
+  reference acceleration a_ref = -k imp r, r = dist - margin (oracle/physics_oracle.py contact_rows); the timestep's problem min 1/2 M a^2 + 4 x 1/2 D (a - a_ref)^2
+  has a = 4 D a_ref / (M + 4 D), M = mass + armature of the link."""
+  solref, solimp = d['col_cls_solref'][cls], d['col_cls_solimp'][cls]
+  r = mpmath.mpf(dist) - mpmath.mpf(float(d['col_cls_margin'][cls]))
+  assert r < 0
+  k, _ = pr.kb_ref(solref, solimp, float(d['timestep']))
+  imp = pr.impedance_ref(solimp, r)
+  R0 = max((1 - imp) / imp * mpmath.mpf(float(d['col_cls_invw'][cls])), mpmath.mpf('1e-15'))
+  mu = mpmath.mpf(float(d['col_cls_mu'][cls]))
+  D = 1 / (2 * mu * mu * R0)
+  M = mpmath.mpf(float(d['mass'][SLIDE])) + mpmath.mpf(float(d['jnt_armature'][SLIDE]))
+  return 4 * D * (-k * imp * r) / (M + 4 * D)
+
+
+def kitchen_closed_form_exact(d, lm, states):
+  """-> per state None (no contact) or (signed acceleration of the slide dof, group), mpmath -> float; the exact distance is exact_contact's"""
+  out = []
+  for s in states:
+    if not s['hit']:
+      out.append(None)
+      continue
+    pos, quat, _ = lm.kinematics(s['qpos'])
+    _, ans = exact_contact(MP, d, pos, quat, s['pair'])
+    dist = ans[0][0]
+    edge = abs(float(dist) - float(d['col_cls_margin'][s['cls']])) < 1e-8
+    out.append((s['sign'] * float(kitchen_alpha(d, s['cls'], dist)), 'edge of the margin' if edge else 'interior'))
+  return out
+
+
+def kitchen_closed_form_figures(exact, qacc, free):
+  """qacc [len(states), 23] of some implementation and its contact-free qacc on the same states, worst over the contact states of a group:
+  alpha: |qacc[19] / a - 1|;  others: |qacc[j] - free[j]| over j != 19, relative to the state's largest |free| -> {group: dict(alpha, others, n)}"""
+  fig = {g: dict(alpha=0.0, others=0.0, n=0) for g in ('interior', 'edge of the margin')}
+  rest = np.arange(23) != SLIDE
+  for i, e in enumerate(exact):
+    if e is None:
+      continue
+    f = fig[e[1]]
+    f['alpha'] = max(f['alpha'], abs(float(qacc[i][SLIDE]) / e[0] - 1.0))
+    f['others'] = max(f['others'], float(np.abs(np.asarray(qacc[i])[rest] - np.asarray(free[i])[rest]).max() / np.abs(free[i]).max()))
+    f['n'] += 1
+  return fig
+
+
+def print_kitchen_figures(who, fig):
+  for g, f in fig.items():
+    print(f"COLL-FIG {who} vs pyramid closed form, {g} ({f['n']} states): alpha rel {f['alpha']:.3e}  other dofs vs contact-free {f['others']:.3e}")

@@ -98,11 +98,12 @@ def moving_box():
   return d, po.LinkModel(d), cc.peg_moving_box_states(d)
 
 
-def regions_against_exact(d, lm, states):
+def regions_against_exact(d, lm, states, alone=True):
+  """alone = False (tests/test_collision_pyramid.py): the table's other pairs may touch in the same state; the state's own pair is picked out of the list"""
   seen = set()
   for i, s in enumerate(states):
     pos, quat = frames(lm, s['qpos'])
-    got = lm.collide(pos, quat)
+    got = [c for c in lm.collide(pos, quat) if alone or c['pair'] == s['pair']]
     region, ans = cc.exact_contact(cc.LD, d, pos, quat, s['pair'])
     assert len(ans) == 1
     gi = int(d['col_pair'][s['pair']][0])

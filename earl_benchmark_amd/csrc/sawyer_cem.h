@@ -1,13 +1,13 @@
 // sawyer_cem.h -- what the Sawyer door / peg CEM planner (include/earl_physics.h, "CEM planning on the door and the peg": earl_sawyer_plan_cem,
 // earl_sawyer_cem_candidates, earl_sawyer_cem_update) computes per element, for the two kernels of sawyer_cem.hip and for the host twins of tabletop_host.cpp: the
-// argument block, the clamped std and the candidate of one (branch, step, env), and an elite's share of the two integer moments.  The dimension-free pieces of the
+// argument block, the argument rules, the clamped std of one (step, env), and an elite's share of the two integer moments.  The clipped row, the candidate of one
+// (branch, step, env) -- its scale here the clamped std -- and its place in memory are sawyer_shoot.h's, shared with the MPPI planner.  The dimension-free pieces of the
 // contract ARE the tabletop's, unedited: plan_clip, plan_best / plan_best_merge (tabletop_plan.h), cem_sclamp, cem_key, cem_before, cem_new_mean, cem_new_std and
 // the noise counter's word 0, kCemDraw (tabletop_cem.h).  What differs is FOUR action dimensions out of one Philox block and where the candidates live: in memory,
 // [K, H, n, 4], so item 5 reads an elite's candidate back instead of making it again.  The elite selection itself is cem_select.h's (device) or a sort (host).
 #pragma once
-#include "tabletop_hostside.h"   // fail: the thread-local message behind earl_last_error
+#include "sawyer_shoot.h"
 #include "tabletop_cem.h"
-#include "../../include/earl_physics.h"
 
 namespace earl {
 
@@ -94,12 +94,7 @@ inline int check_sawyer_cem(SawyerCemCall call, const earl_sawyer_cfg* cfg, cons
   return EARL_OK;
 }
 
-// item 1: row t of env i of the plan and of the std entering, all four words
-__device__ __forceinline__ void scem_mean(const SawyerCemArgs& p, int i, int t, float (&m)[4]) {
-  const float* mp = p.mean + ((size_t)t * p.n + i) * 4;
-#pragma unroll
-  for (int d = 0; d < 4; ++d) m[d] = plan_clip(mp[d]);
-}
+// item 1: row t of env i of the std entering, all four words clamped (the plan's row is sawyer_shoot.h's shoot_mean)
 __device__ __forceinline__ void scem_std(const SawyerCemArgs& p, int i, int t, float (&s)[4]) {
   if (p.std_in) {
     const float* sp = p.std_in + ((size_t)t * p.n + i) * 4;
@@ -111,28 +106,11 @@ __device__ __forceinline__ void scem_std(const SawyerCemArgs& p, int i, int t, f
   }
 }
 
-// item 2: candidate k of (step t, env i) around the clipped row m with the row's clamped std s -- the row itself for k == 0, else one Philox block and four quantiles
-__device__ __forceinline__ void scem_candidate(const SawyerCemArgs& p, int i, uint32_t k, uint32_t t, const float (&m)[4], const float (&s)[4], float (&c)[4]) {
-  if (k == 0) {
-#pragma unroll
-    for (int d = 0; d < 4; ++d) c[d] = m[d];
-    return;
-  }
-  const U4 b = philox4x32_10(U4{p.word0, (uint32_t)(p.env_offset + i), (k << 16) | t, p.noise_counter}, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-  c[0] = plan_clip(fmaf(s[0], normal_quantile_f32(b.x >> 8), m[0]));
-  c[1] = plan_clip(fmaf(s[1], normal_quantile_f32(b.y >> 8), m[1]));
-  c[2] = plan_clip(fmaf(s[2], normal_quantile_f32(b.z >> 8), m[2]));
-  c[3] = plan_clip(fmaf(s[3], normal_quantile_f32(b.w >> 8), m[3]));
-}
-
-// where candidate k of (step t, env i) lives in a [K, H, n, 4] array
-__device__ __forceinline__ size_t scem_act_index(const SawyerCemArgs& p, int i, int k, int t) { return (((size_t)k * p.H + t) * p.n + i) * 4; }
-
 // item 5: an elite's candidate c of (env, step), READ back from the candidates, added to the two moments around the clipped row m
 __device__ __forceinline__ void scem_accumulate(const float (&c)[4], const float (&m)[4], int64_t (&A1)[4], int64_t (&A2)[4]) {
 #pragma unroll
   for (int d = 0; d < 4; ++d) {
-    const int64_t D = (int64_t)(int32_t)__builtin_rint((double)(c[d] - m[d]) * 1048576.0);   // |D| <= 2^21
+    const int64_t D = shoot_delta(c[d], m[d]);
     A1[d] += D;
     A2[d] += D * D;
   }

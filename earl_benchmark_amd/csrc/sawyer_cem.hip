@@ -10,12 +10,12 @@
 //                                   env, where ranking every pair is O(K^2).  (3) Wave w takes the plan steps t = w, w + 8, ...: its 64 lanes split the compacted
 //                                   list, read each elite's float4 from the candidates, keep int64 A1[4], A2[4], join them by shuffles; lane 0 writes the plan row and
 //                                   the std row.  Row t of mean / std is read by the wave that writes it and by no other: plan == mean and std == std_in are safe.
-// The per-element functions are sawyer_cem.h's (tabletop_cem.h's and tabletop_plan.h's for the dimension-free items), shared with the host twins of tabletop_host.cpp.
+// The per-element functions are sawyer_cem.h's and, where the MPPI planner computes the same, sawyer_shoot.h's (tabletop_cem.h's and tabletop_plan.h's for the
+// dimension-free items), shared with the host twins of tabletop_host.cpp.  The workspace layout, the prologue of the call and the scoring call of an iteration are
+// sawyer_shoot.h's too.
 #include <hip/hip_runtime.h>
 
 #include "sawyer_cem.h"
-#include "sawyer_value.h"   // the rules of earl_plan_value on these envs (earl_sawyer_plan_cem_value)
-#include "sawyer_prior.h"   // the rules of earl_sawyer_plan_prior and the `_prior` block (earl_sawyer_plan_cem_prior)
 #include "cem_select.h"
 
 using namespace earl;
@@ -23,30 +23,18 @@ using namespace earl::hostside;
 
 namespace {
 
-constexpr int kCandThreads = 256;
-constexpr long long kCandMaxBlocks = 1 << 20;      // (the grid-stride loop takes what lies beyond: 2^28 candidates per pass)
 constexpr int kUpdateThreads = 512, kUpdateWaves = kUpdateThreads / 64, kPerLane = EARL_SAWYER_PLAN_MAX_K / kUpdateThreads;
 static_assert(kPerLane * kUpdateThreads == EARL_SAWYER_PLAN_MAX_K, "a lane's register keys cover K");
 using SelectLds = CemSelectLds<kUpdateThreads, kPerLane, EARL_SAWYER_CEM_MAX_E>;
 
 __global__ __launch_bounds__(kCandThreads) void sawyer_cem_candidates_kernel(const SawyerCemArgs p, float* __restrict__ act_out) {
-  const unsigned long long total = (unsigned long long)p.K * (unsigned long long)p.H * (unsigned long long)p.n;
-  const unsigned long long stride = (unsigned long long)gridDim.x * kCandThreads;
-  for (unsigned long long e = (unsigned long long)blockIdx.x * kCandThreads + threadIdx.x; e < total; e += stride) {
-    const unsigned long long kt = e / (unsigned)p.n;
-    const int i = (int)(e - kt * (unsigned)p.n), k = (int)(kt / (unsigned)p.H), t = (int)(kt - (unsigned long long)k * (unsigned)p.H);
+  shoot_for_each_candidate(p.K, p.H, p.n, [&](unsigned long long e, int i, int k, int t) {
     float m[4], s[4], c[4];
-    scem_mean(p, i, t, m);
+    shoot_mean(p.mean, p.n, i, t, m);
     scem_std(p, i, t, s);
-    scem_candidate(p, i, (uint32_t)k, (uint32_t)t, m, s, c);
-    *reinterpret_cast<float4*>(act_out + e * 4) = float4{c[0], c[1], c[2], c[3]};      // (e IS scem_act_index(p, i, k, t) / 4)
-  }
-}
-
-__device__ __forceinline__ int64_t wave_sum(int64_t v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor((long long)v, s);
-  return v;
+    shoot_candidate(p.word0, (uint32_t)(p.env_offset + i), (uint32_t)k, (uint32_t)t, p.noise_counter, p.seed, s, m, c);
+    *reinterpret_cast<float4*>(act_out + e * 4) = float4{c[0], c[1], c[2], c[3]};
+  });
 }
 
 __global__ __launch_bounds__(kUpdateThreads) void sawyer_cem_update_kernel(const SawyerCemArgs p) {
@@ -70,21 +58,7 @@ __global__ __launch_bounds__(kUpdateThreads) void sawyer_cem_update_kernel(const
       key[r] = cem_key(v);
     }
   }
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    const double ob = __shfl_xor(beta, s);
-    const int ok = __shfl_xor(bk, s);
-    plan_best_merge(ob, ok, beta, bk);
-  }
-  if (lane == 0) {
-    b_lds[wave] = beta;
-    k_lds[wave] = bk;
-  }
-  __syncthreads();
-  beta = b_lds[0];
-  bk = k_lds[0];
-#pragma unroll
-  for (int v = 1; v < kUpdateWaves; ++v) plan_best_merge(b_lds[v], k_lds[v], beta, bk);
+  block_best<kUpdateThreads>(beta, bk, b_lds, k_lds);
 
   // item 4, second half: the elites
   uint32_t mine;
@@ -100,13 +74,13 @@ __global__ __launch_bounds__(kUpdateThreads) void sawyer_cem_update_kernel(const
   // item 5: a wave per plan step, its lanes over the elites
   for (int t = wave; t < p.H; t += kUpdateWaves) {
     float m[4], s[4];
-    scem_mean(p, i, t, m);
+    shoot_mean(p.mean, n, i, t, m);
     scem_std(p, i, t, s);
     int64_t A1[4] = {0, 0, 0, 0}, A2[4] = {0, 0, 0, 0};
     for (int e = lane; e < Ne; e += 64) {
       const int k = (int)sel.elite[e];
       if (k > 0) {                                                                  // (branch 0 is the mean: D = 0)
-        const float4 v = *reinterpret_cast<const float4*>(p.act + scem_act_index(p, i, k, t));
+        const float4 v = *reinterpret_cast<const float4*>(p.act + shoot_act_index(p.H, n, i, k, t));
         const float c[4] = {v.x, v.y, v.z, v.w};
         scem_accumulate(c, m, A1, A2);
       }
@@ -132,15 +106,8 @@ __global__ __launch_bounds__(kUpdateThreads) void sawyer_cem_update_kernel(const
   }
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(EARL_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-  return EARL_OK;
-}
-
 int launch_candidates(const SawyerCemArgs& p, float* act_out, hipStream_t stream) {
-  const long long total = (long long)p.K * p.H * p.n, want = (total + kCandThreads - 1) / kCandThreads;
-  sawyer_cem_candidates_kernel<<<dim3((unsigned)(want < kCandMaxBlocks ? want : kCandMaxBlocks)), kCandThreads, 0, stream>>>(p, act_out);
+  sawyer_cem_candidates_kernel<<<shoot_candidates_grid(p.K, p.H, p.n), kCandThreads, 0, stream>>>(p, act_out);
   return launched("sawyer_cem_candidates_kernel");
 }
 
@@ -148,10 +115,6 @@ int launch_update(const SawyerCemArgs& p, hipStream_t stream) {
   sawyer_cem_update_kernel<<<dim3((unsigned)p.n), kUpdateThreads, 0, stream>>>(p);
   return launched("sawyer_cem_update_kernel");
 }
-
-int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
-bool misaligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; }
 
 }  // namespace
 
@@ -191,49 +154,23 @@ int earl_sawyer_cem_update(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_par
 
 namespace {
 
-// The body of earl_sawyer_plan_cem and earl_sawyer_plan_cem_value: pv as in sawyer_plan.hip's plan_mppi -- NULL: item 3 is earl_sawyer_branch_rollout and the block
-// earl_sawyer_plan_ws_bytes'; otherwise earl_sawyer_branch_rollout_value and earl_sawyer_value_ws_bytes'.  Nothing else differs.
-// prior: as in sawyer_plan.hip's plan_mppi -- NULL, or (earl_sawyer_plan_cem_prior, branches >= 1) item 3 is earl_sawyer_branch_rollout_prior's body with CEM's draw word,
-// which overwrites the last `branches` blocks of the candidates; the block is earl_sawyer_prior_ws_bytes'.  The update kernel reads the candidates back and does not know.
+// The body of the three entry points: pv and prior as in sawyer_plan.hip's plan_mppi, the draw word CEM's; the prologue and the scoring call are sawyer_shoot.h's
 int plan_cem(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
              const earl_sawyer_cem_params* params, const earl_plan_value* pv, const earl_sawyer_plan_prior* prior, const float* mean, const float* std0, float* plan, float* std,
              double* ret, double* ret0, double* best_ret, int32_t* best_k, uint8_t* elite, int32_t* fail_count, const uint64_t* clock, const earl_sawyer_branch_ws* ws,
              earl_stream_t stream) {
   if (int rc = check_sawyer_cem(SawyerCemCall::Cem, cfg, params, 0, mean, std0, plan, std)) return rc;
-  if (int rc = check_sawyer_value(pv, g_err)) return rc;
-  if (prior) {
-    const uint64_t rows = (uint64_t)params->H * (uint64_t)cfg->n * 16u;
-    const void* const in[4] = {mean, plan, std0, std};
-    const uint64_t in_bytes[4] = {rows, rows, rows, rows};
-    if (int rc = check_sawyer_prior(prior, params->K, params->H, cfg->n, in, in_bytes, g_err)) return rc;
-    if (prior->branches == 0) prior = nullptr;                                        // (the identity: from here on the `_value` call, launch for launch)
-  }
-  if (!ret) return fail(EARL_ERR_ARG, "ret is NULL: the branch launch writes it and the update reads it");
-  if (!ws) return fail(EARL_ERR_ARG, "ws is NULL");
-  if (misaligned16(plan) || misaligned16(std)) return fail(EARL_ERR_ARG, "plan / std is not 16-byte aligned: a row is one 16-byte store");
-  const int n = cfg->n, K = params->K, H = params->H;
-  int64_t branch = 0, need = 0;
-  if (earl_sawyer_branch_ws_bytes(nv, K, n, &branch) ||
-      (prior ? earl_sawyer_prior_ws_bytes(nv, K, H, n, &need) : (pv ? earl_sawyer_value_ws_bytes(nv, K, H, n, &need) : earl_sawyer_plan_ws_bytes(nv, K, H, n, &need))))
-    return fail(EARL_ERR_ARG, "nv = %d: 10 (door) or 15 (peg)", nv);
-  branch = round_up(branch, 8);
-  // (what the scoring call takes of the block: earl_sawyer_prior_ws_bytes / earl_sawyer_value_ws_bytes with H = 0)
-  const int64_t scored = prior ? sawyer_prior_scored_bytes(branch, (int64_t)K * n) : (pv ? branch + (int64_t)K * n * 8 : branch);
-  if (n > 0 && (!ws->base || (reinterpret_cast<uintptr_t>(ws->base) & 7) != 0 || ws->bytes < need))
-    return fail(EARL_ERR_ARG, "ws: base %p (8-byte aligned), %lld bytes of the %lld needed", ws->base, (long long)ws->bytes, (long long)need);
-  const earl_sawyer_branch_ws bws{ws->base, branch};
-  const earl_sawyer_branch_ws vws{ws->base, scored};
-  float* const act = n > 0 ? reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws->base) + (uintptr_t)scored + 15) & ~(uintptr_t)15) : plan;
-  const earl_episode_summary sum{ret, nullptr, nullptr};
-  // everything the branch launch refuses in model / col / cfg / st / nv and the lane switch, decided by the branch launch itself: with H = 0 it returns after its
-  // checks and before its first HIP call
-  if (int rc = earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, 0, act, 0, clock, &bws, &sum, nullptr, fail_count, stream))
-    return fail(rc, "earl_sawyer_branch_rollout refuses model / col / cfg / st / nv (or earl_debug_set_physics_lanes(64) is set)");
+  SawyerShoot s;
+  if (int rc = sawyer_shoot_open(model, col, nv, cfg, st, params, pv, prior, {mean, plan, std0, std},
+                                 misaligned16(plan) || misaligned16(std) ? "plan / std is not 16-byte aligned: a row is one 16-byte store" : nullptr, plan, ret, fail_count,
+                                 clock, ws, stream, &s))
+    return rc;
+  const int n = cfg->n;
   if (n == 0) return EARL_OK;
   SawyerCemArgs p = sawyer_cem_args(cfg, params, mean, std0);
   p.plan = plan;
   p.std_out = std;
-  p.act = act;
+  p.act = s.act;
   p.ret = ret;
   for (int it = 0; it < params->iterations; ++it) {
     const bool last = it + 1 == params->iterations;
@@ -242,15 +179,8 @@ int plan_cem(const earl_link_model* model, const earl_collision_model* col, int3
     p.best_ret = last ? best_ret : nullptr;
     p.best_k = last ? best_k : nullptr;
     p.elite = last ? elite : nullptr;
-    if (int rc = launch_candidates(p, act, (hipStream_t)stream)) return rc;
-    if (prior) {
-      if (int rc = earl_unit_sawyer_branch_scored_prior(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, pv, prior, p.word0, p.noise_counter, &vws, &sum, nullptr,
-                                                        last ? fail_count : nullptr, stream))
-        return rc == EARL_ERR_ARG ? rc : fail(rc, "earl_sawyer_branch_rollout_prior failed in iteration %d", params->iteration0 + it);
-    } else
-    if (int rc = pv ? earl_sawyer_branch_rollout_value(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, pv, &vws, &sum, nullptr, last ? fail_count : nullptr, stream)
-                    : earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, (int64_t)H * n * 4, clock, &bws, &sum, nullptr, last ? fail_count : nullptr, stream))
-      return fail(rc, "earl_sawyer_branch_rollout%s failed in iteration %d", pv ? "_value" : "", params->iteration0 + it);
+    if (int rc = launch_candidates(p, s.act, (hipStream_t)stream)) return rc;
+    if (int rc = sawyer_shoot_score(s, p.word0, it, last)) return rc;
     if (int rc = launch_update(p, (hipStream_t)stream)) return rc;
     p.mean = plan;                                                                   // (the next iteration starts from this one's results, in place)
     p.std_in = std;

@@ -1,12 +1,11 @@
 // sawyer_plan.h -- what the Sawyer door / peg MPPI planner (include/earl_physics.h, "MPPI planning": earl_sawyer_plan_mppi, earl_sawyer_plan_candidates) computes per
-// element, for the two kernels of sawyer_plan.hip and for the host twins of tabletop_host.cpp: the argument block, the candidate of one (branch, step, env) and the
-// reweighting's sum of one branch.  The dimension-free pieces of the contract -- plan_clip, plan_best / plan_best_merge, plan_weight, plan_new_mean and the noise
-// counter's word 0 (kPlanDraw) -- ARE tabletop_plan.h's: items 1, 4, 5 and 7 are the tabletop's verbatim.  What differs is item 2 (FOUR action dimensions out of
-// one Philox block, the gripper clipped like x, y, z) and where the candidates live: in memory, [K, H, n, 4], because the rollout that scores them reads them there.
+// element, for the two kernels of sawyer_plan.hip and for the host twins of tabletop_host.cpp: the argument block, the argument rules and the reweighting's sum of one
+// branch.  The clipped row, the candidate of one (branch, step, env) and its place in memory are sawyer_shoot.h's, shared with the CEM planner.  The dimension-free
+// pieces of the contract -- plan_clip, plan_best / plan_best_merge, plan_weight, plan_new_mean and the noise counter's word 0 (kPlanDraw) -- ARE tabletop_plan.h's:
+// items 1, 4, 5 and 7 are the tabletop's verbatim.  What differs is item 2 (FOUR action dimensions out of one Philox block, the gripper clipped like x, y, z) and where
+// the candidates live: in memory, [K, H, n, 4], because the rollout that scores them reads them there.
 #pragma once
-#include "tabletop_hostside.h"   // fail: the thread-local message behind earl_last_error
-#include "tabletop_plan.h"
-#include "../../include/earl_physics.h"
+#include "sawyer_shoot.h"
 
 namespace earl {
 
@@ -72,34 +71,10 @@ inline int check_sawyer_plan(SawyerPlanCall call, const earl_sawyer_cfg* cfg, co
   return EARL_OK;
 }
 
-// item 1: row t of env i of the plan entering, all four words clipped
-__device__ __forceinline__ void splan_mean(const SawyerPlanArgs& p, int i, int t, float (&m)[4]) {
-  const float* mp = p.mean + ((size_t)t * p.n + i) * 4;
-#pragma unroll
-  for (int d = 0; d < 4; ++d) m[d] = plan_clip(mp[d]);
-}
-
-// item 2: candidate k of (step t, env i) around the clipped row m -- the row itself for k == 0, else one Philox block and four quantiles
-__device__ __forceinline__ void splan_candidate(const SawyerPlanArgs& p, int i, uint32_t k, uint32_t t, const float (&m)[4], float (&c)[4]) {
-  if (k == 0) {
-#pragma unroll
-    for (int d = 0; d < 4; ++d) c[d] = m[d];
-    return;
-  }
-  const U4 b = philox4x32_10(U4{p.word0, (uint32_t)(p.env_offset + i), (k << 16) | t, p.noise_counter}, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-  c[0] = plan_clip(fmaf(p.sigma[0], normal_quantile_f32(b.x >> 8), m[0]));
-  c[1] = plan_clip(fmaf(p.sigma[1], normal_quantile_f32(b.y >> 8), m[1]));
-  c[2] = plan_clip(fmaf(p.sigma[2], normal_quantile_f32(b.z >> 8), m[2]));
-  c[3] = plan_clip(fmaf(p.sigma[3], normal_quantile_f32(b.w >> 8), m[3]));
-}
-
-// where candidate k of (step t, env i) lives in a [K, H, n, 4] array
-__device__ __forceinline__ size_t splan_act_index(const SawyerPlanArgs& p, int i, int k, int t) { return (((size_t)k * p.H + t) * p.n + i) * 4; }
-
 // item 5: a branch's candidate c of (env, step), READ back from the candidates, added with its weight to the four sums around the clipped row m
 __device__ __forceinline__ void splan_accumulate(const float (&c)[4], const float (&m)[4], int32_t W, int64_t (&A)[4]) {
 #pragma unroll
-  for (int d = 0; d < 4; ++d) A[d] += (int64_t)W * (int64_t)(int32_t)__builtin_rint((double)(c[d] - m[d]) * 1048576.0);   // |D| <= 2^21
+  for (int d = 0; d < 4; ++d) A[d] += (int64_t)W * shoot_delta(c[d], m[d]);
 }
 
 }  // namespace earl

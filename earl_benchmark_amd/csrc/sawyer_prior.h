@@ -1,7 +1,7 @@
 // sawyer_prior.h -- the host side of the policy-prior branches of the Sawyer door / peg planners (include/earl_physics.h, "policy-prior branches on the door and the
-// peg"): the argument rules of struct earl_sawyer_plan_prior, the workspace layout of the `_prior` calls and what physics.hip's branch launch takes for the prior
-// branches.  Host only.  The kernel is physics_env_sawyer.h's sawyer_prior_action (physics_branch_prior.hip, physics_branch_prior_w8.hip); the host twin of its per-row
-// arithmetic is tabletop_host.cpp's earl_sawyer_prior_actions_cpu.  Included by physics.hip, sawyer_value.hip, sawyer_plan.hip and sawyer_cem.hip.
+// peg"): the argument rules of struct earl_sawyer_plan_prior and what physics.hip's branch launch takes for the prior branches (the workspace layout of the `_prior`
+// calls is sawyer_shoot.h's sawyer_ws_layout).  Host only.  The kernel is physics_env_sawyer.h's sawyer_prior_action (physics_branch_prior.hip,
+// physics_branch_prior_w8.hip); the host twin of its per-row arithmetic is tabletop_host.cpp's earl_sawyer_prior_actions_cpu.  Included by physics.hip and sawyer_shoot.h.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -9,15 +9,6 @@
 #include "policy_check.h"
 #include "policy_math.h"
 #include "../../include/earl_physics.h"
-
-// the scoring call of the `_prior` planners (sawyer_value.hip): earl_sawyer_branch_rollout_prior after its checks, with the planner's own draw word
-extern "C" __attribute__((visibility("hidden"))) int earl_unit_sawyer_branch_scored_prior(const earl_link_model* model, const earl_collision_model* col, int32_t nv,
-                                                                                          const earl_sawyer_cfg* cfg, const earl_sawyer_state* st, int32_t K, int32_t H,
-                                                                                          float* act, int64_t act_branch_stride, const uint64_t* clock,
-                                                                                          const earl_plan_value* pv, const earl_sawyer_plan_prior* prior, uint32_t word0,
-                                                                                          uint32_t noise_counter, const earl_sawyer_branch_ws* ws,
-                                                                                          const earl_episode_summary* summary, double* last_obs, int32_t* fail_count,
-                                                                                          earl_stream_t stream);
 
 namespace earl {
 
@@ -31,13 +22,6 @@ struct SawyerPriorLaunch {
   uint32_t noise_counter;
   int32_t* sched;                        // the work queue of a prior launch of its OWN (the two-launch shape), 2 ceil(P n / 4) words (its replicate launch clears them where the time-sliced form runs)
 };
-
-inline int64_t sawyer_prior_round8(int64_t v) { return (v + 7) / 8 * 8; }
-// the second work queue of a `_prior` block: sized for any P < K, 2 ceil(K n / 4) int32 rounded up to 8 bytes
-inline int64_t sawyer_prior_queue_bytes(int64_t V) { return sawyer_prior_round8(2 * ((V + 3) / 4) * (int64_t)sizeof(int32_t)); }
-// The block of a `_prior` call: the branch launch's workspace (rounded up to 8 bytes: `branch`), the [K n] discounts (the prior kernels are built with the discounted sum
-// and always carry d_t), the prior launch's work queue, then -- a planner -- the candidates at the next 16-byte address.  -> the bytes in front of the candidates
-inline int64_t sawyer_prior_scored_bytes(int64_t branch, int64_t V) { return branch + V * 8 + sawyer_prior_queue_bytes(V); }
 
 inline bool sawyer_prior_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
   if (!a || !b || a_bytes == 0 || b_bytes == 0) return false;

@@ -7,13 +7,12 @@
 //                           rows, which already are those rows -- round it to float32 (element `sub` on lane `sub`), evaluate V with pol_layer<16, ..> of
 //                           policy_lane_group.h exactly as the closed loop's policy phase does (first layer K = 14: the element-wise path; then 16-byte pieces), and lane 0
 //                           does ret[v] += d_H * (double)V (sawyer_value.h, shared with the host twin).  One launch of K n evaluations per planner iteration, not per step.
-// No stepper header here: the unit compiles in seconds and reaches the stepper through two hidden calls into physics.hip.
+// Also earl_sawyer_branch_rollout_prior / earl_sawyer_prior_ws_bytes, and the ONE scoring call behind all of them and behind both planners' iterations
+// (earl_unit_sawyer_branch_scored: sawyer_shoot.h states it and the workspace layout it reads).
+// No stepper header here: the unit compiles in seconds and reaches the stepper through three hidden calls into physics.hip.
 #include <hip/hip_runtime.h>
 
-#include "sawyer_prior.h"
-#include "sawyer_value.h"
-#include "tabletop_hostside.h"   // fail: the thread-local message behind earl_last_error
-#include "../../include/earl_physics.h"
+#include "sawyer_shoot.h"   // the workspace layout and the declaration of the scoring call below
 
 using namespace earl;
 using namespace earl::hostside;
@@ -67,8 +66,6 @@ __global__ __launch_bounds__(kValueThreads) void sawyer_value_kernel(const Sawye
   if (sub == 0 && live) a.ret[v] = svalue_terminal(a.ret[v], a.d_H, policy_act(h[0], a.net.out_act), nan_row);
 }
 
-int64_t round_up(int64_t v, int64_t al) { return (v + al - 1) / al * al; }
-
 // the value kernel behind a branch launch over V virtual envs: rows = the caller's last_obs or the workspace's carried rows
 int launch_value(const earl_plan_value* pv, int32_t nv, int64_t V, int32_t H, double* last_obs, void* ws_base, double* ret, earl_stream_t stream) {
   SawyerValueArgs a{};
@@ -78,96 +75,63 @@ int launch_value(const earl_plan_value* pv, int32_t nv, int64_t V, int32_t H, do
   a.d_H = svalue_discount(pv->discount, H);
   a.V = (int32_t)V;
   sawyer_value_kernel<<<dim3((unsigned)((V + kValueEnvs - 1) / kValueEnvs)), kValueThreads, 0, (hipStream_t)stream>>>(a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(EARL_ERR_LAUNCH, "sawyer_value_kernel: %s", hipGetErrorString(e));
-  return EARL_OK;
+  return launched("sawyer_value_kernel");
 }
 
 }  // namespace
 
 extern "C" {
 
-// the block: the branch launch's workspace (rounded up to 8 bytes), then the [K n] discounts of a discounted launch, then -- H > 0, a planner's block -- the candidates
-// at the next 16-byte ADDRESS (8 bytes of slack), as earl_sawyer_plan_ws_bytes lays them out
-int earl_sawyer_value_ws_bytes(int32_t nv, int32_t K, int32_t H, int32_t n, int64_t* bytes) {
-  int64_t branch = 0;
-  if (!bytes || H < 0) return EARL_ERR_ARG;
-  if (int rc = earl_sawyer_branch_ws_bytes(nv, K, n, &branch)) return rc;
-  const int64_t V = (int64_t)K * n;
-  *bytes = V == 0 ? 0 : round_up(branch, 8) + V * 8 + (H > 0 ? 8 + V * H * 16 : 0);
-  return EARL_OK;
+// the Value and the Prior block of sawyer_shoot.h's sawyer_ws_layout
+int earl_sawyer_value_ws_bytes(int32_t nv, int32_t K, int32_t H, int32_t n, int64_t* bytes) { return sawyer_ws_bytes(nv, K, H, n, SawyerWs::Value, bytes); }
+int earl_sawyer_prior_ws_bytes(int32_t nv, int32_t K, int32_t H, int32_t n, int64_t* bytes) { return sawyer_ws_bytes(nv, K, H, n, SawyerWs::Prior, bytes); }
+
+// sawyer_shoot.h states the call.  The branch launch -- plain, discounted (physics.hip: the kernels built with EARL_BRANCH_DISCOUNT, d_t in the block's [K n] words) or
+// with the last prior->branches branches run by the policy (one launch of the prior kernel over all K n virtual envs, or two) -- then, with a network, the value kernel over
+// all K n rows.  Hidden: sawyer_plan.hip and sawyer_cem.hip call it once per iteration
+__attribute__((visibility("hidden"))) int earl_unit_sawyer_branch_scored(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg,
+                                                                         const earl_sawyer_state* st, int32_t K, int32_t H, float* act, int64_t act_branch_stride,
+                                                                         const uint64_t* clock, const earl_plan_value* pv, const earl_sawyer_plan_prior* prior, uint32_t word0,
+                                                                         uint32_t noise_counter, const earl_sawyer_branch_ws* ws, const earl_episode_summary* summary,
+                                                                         double* last_obs, int32_t* fail_count, earl_stream_t stream) {
+  if (!prior && sawyer_value_plain(pv)) return earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, ws, summary, last_obs, fail_count, stream);
+  if (int rc = check_sawyer_value(pv, g_err)) return rc;
+  if (pv && pv->value && !(summary && summary->ret)) return fail(EARL_ERR_ARG, "a value network without summary->ret: the terminal term has nothing to be added to");
+  if (!cfg || !ws || (prior && prior->branches < 1)) return fail(EARL_ERR_ARG, prior ? "cfg/ws/prior is NULL" : "cfg/ws is NULL");
+  if (prior && ((act_branch_stride == 0 && (int64_t)H * cfg->n > 0) || (act_branch_stride & 3) != 0 || misaligned16(act)))      // (no row, no block: the empty call)
+    return fail(EARL_ERR_ARG, "act_branch_stride = %lld, act %p: with prior branches the call WRITES their blocks, one 16-byte store per row -- a stride that is a multiple of 4 "
+                "and not 0, act 16-byte aligned", (long long)act_branch_stride, (const void*)act);
+  SawyerWsLayout L;
+  if (K < 0 || cfg->n < 0 || sawyer_ws_layout(nv, K, 0, cfg->n, prior ? SawyerWs::Prior : SawyerWs::Value, &L))
+    return fail(EARL_ERR_ARG, "nv = %d: 10 (door) or 15 (peg); K = %d, n = %d: not negative, K n at most 2^31 - 1", nv, K, cfg->n);
+  const int64_t V = (int64_t)K * cfg->n;
+  if (V > 0)
+    if (int rc = check_sawyer_ws(ws, L.need, prior ? " (earl_sawyer_prior_ws_bytes)" : " (earl_sawyer_value_ws_bytes)")) return rc;
+  const earl_sawyer_branch_ws bws{ws->base, L.branch};
+  const double gamma = pv ? pv->discount : 1.0;
+  char* const b = static_cast<char*>(ws->base);
+  // everything else the branch launch refuses is the branch launch's to refuse; V == 0 or H == 0: it returns EARL_OK after its checks and nothing is launched
+  int rc;
+  if (V == 0 || (!prior && gamma == 1.0)) {
+    rc = earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, &bws, summary, last_obs, fail_count, stream);
+  } else if (!prior) {
+    rc = earl_unit_sawyer_branch_discounted(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, &bws, summary, last_obs, fail_count, gamma,
+                                            reinterpret_cast<double*>(b + L.branch), stream);
+  } else {
+    const SawyerPriorLaunch pl{prior, word0, noise_counter, reinterpret_cast<int32_t*>(b + L.queue)};
+    rc = earl_unit_sawyer_branch_prior(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, &bws, summary, last_obs, fail_count, gamma,
+                                       reinterpret_cast<double*>(b + L.branch), &pl, stream);
+  }
+  if (rc || V == 0 || H == 0 || !pv || !pv->value) return rc;
+  return launch_value(pv, nv, V, H, last_obs, ws->base, summary->ret, stream);
 }
 
 int earl_sawyer_branch_rollout_value(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
                                      int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_plan_value* pv,
                                      const earl_sawyer_branch_ws* ws, const earl_episode_summary* summary, double* last_obs, int32_t* fail_count, earl_stream_t stream) {
-  if (sawyer_value_plain(pv)) return earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, ws, summary, last_obs, fail_count, stream);
-  if (int rc = check_sawyer_value(pv, g_err)) return rc;
-  if (pv->value && !(summary && summary->ret)) return fail(EARL_ERR_ARG, "a value network without summary->ret: the terminal term has nothing to be added to");
-  if (!cfg || !ws) return fail(EARL_ERR_ARG, "cfg/ws is NULL");
-  int64_t branch = 0, need = 0;
-  if (K < 0 || cfg->n < 0 || earl_sawyer_branch_ws_bytes(nv, K, cfg->n, &branch) || earl_sawyer_value_ws_bytes(nv, K, 0, cfg->n, &need))
-    return fail(EARL_ERR_ARG, "nv = %d: 10 (door) or 15 (peg); K = %d, n = %d: not negative, K n at most 2^31 - 1", nv, K, cfg->n);
-  const int64_t V = (int64_t)K * cfg->n;
-  if (V > 0 && (!ws->base || (reinterpret_cast<uintptr_t>(ws->base) & 7) != 0 || ws->bytes < need))
-    return fail(EARL_ERR_ARG, "ws: base %p (8-byte aligned), %lld bytes of the %lld needed (earl_sawyer_value_ws_bytes)", ws->base, (long long)ws->bytes, (long long)need);
-  branch = round_up(branch, 8);
-  const earl_sawyer_branch_ws bws{ws->base, branch};
-  // everything else the branch launch refuses is the branch launch's to refuse; V == 0 or H == 0: it returns EARL_OK after its checks and nothing is launched
-  int rc;
-  if (pv->discount == 1.0) {
-    rc = earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, &bws, summary, last_obs, fail_count, stream);
-  } else {
-    double* const disc = V > 0 ? reinterpret_cast<double*>(static_cast<char*>(ws->base) + branch) : nullptr;
-    rc = V > 0 ? earl_unit_sawyer_branch_discounted(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, &bws, summary, last_obs, fail_count, pv->discount, disc, stream)
-               : earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, &bws, summary, last_obs, fail_count, stream);
-  }
-  if (rc || V == 0 || H == 0 || !pv->value) return rc;
-  return launch_value(pv, nv, V, H, last_obs, ws->base, summary->ret, stream);
-}
-
-int earl_sawyer_prior_ws_bytes(int32_t nv, int32_t K, int32_t H, int32_t n, int64_t* bytes) {
-  int64_t value = 0;
-  if (!bytes) return EARL_ERR_ARG;
-  if (int rc = earl_sawyer_value_ws_bytes(nv, K, H, n, &value)) return rc;
-  const int64_t V = (int64_t)K * n;
-  *bytes = V == 0 ? 0 : value + sawyer_prior_queue_bytes(V);
-  return EARL_OK;
-}
-
-// The scoring call of the `_prior` entry points, `prior` checked by the caller (check_sawyer_prior) and prior->branches >= 1; word0 = the calling planner's draw word | the
-// iteration.  The branch launch with the last P branches run by the policy (physics.hip: one launch of the prior kernel over all K n virtual envs, or two), then -- a
-// network -- the value kernel over all K n rows.  Hidden: sawyer_plan.hip and sawyer_cem.hip call it once per iteration
-__attribute__((visibility("hidden"))) int earl_unit_sawyer_branch_scored_prior(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg,
-                                                                               const earl_sawyer_state* st, int32_t K, int32_t H, float* act, int64_t act_branch_stride,
-                                                                               const uint64_t* clock, const earl_plan_value* pv, const earl_sawyer_plan_prior* prior,
-                                                                               uint32_t word0, uint32_t noise_counter, const earl_sawyer_branch_ws* ws,
-                                                                               const earl_episode_summary* summary, double* last_obs, int32_t* fail_count, earl_stream_t stream) {
-  if (int rc = check_sawyer_value(pv, g_err)) return rc;
-  if (pv && pv->value && !(summary && summary->ret)) return fail(EARL_ERR_ARG, "a value network without summary->ret: the terminal term has nothing to be added to");
-  if (!cfg || !ws || !prior || prior->branches < 1) return fail(EARL_ERR_ARG, "cfg/ws/prior is NULL");
-  if ((act_branch_stride == 0 && (int64_t)H * cfg->n > 0) || (act_branch_stride & 3) != 0 || (reinterpret_cast<uintptr_t>(act) & 15) != 0)      // (no row, no block: the empty call)
-    return fail(EARL_ERR_ARG, "act_branch_stride = %lld, act %p: with prior branches the call WRITES their blocks, one 16-byte store per row -- a stride that is a multiple of 4 "
-                "and not 0, act 16-byte aligned", (long long)act_branch_stride, (const void*)act);
-  int64_t branch = 0, need = 0;
-  if (K < 0 || cfg->n < 0 || earl_sawyer_branch_ws_bytes(nv, K, cfg->n, &branch) || earl_sawyer_prior_ws_bytes(nv, K, 0, cfg->n, &need))
-    return fail(EARL_ERR_ARG, "nv = %d: 10 (door) or 15 (peg); K = %d, n = %d: not negative, K n at most 2^31 - 1", nv, K, cfg->n);
-  const int64_t V = (int64_t)K * cfg->n;
-  if (V > 0 && (!ws->base || (reinterpret_cast<uintptr_t>(ws->base) & 7) != 0 || ws->bytes < need))
-    return fail(EARL_ERR_ARG, "ws: base %p (8-byte aligned), %lld bytes of the %lld needed (earl_sawyer_prior_ws_bytes)", ws->base, (long long)ws->bytes, (long long)need);
-  branch = round_up(branch, 8);
-  const earl_sawyer_branch_ws bws{ws->base, branch};
-  int rc;
-  if (V == 0) {      // (nothing is launched; the branch launch's own refusals still apply)
-    rc = earl_sawyer_branch_rollout(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, &bws, summary, last_obs, fail_count, stream);
-  } else {
-    char* const b = static_cast<char*>(ws->base);
-    const SawyerPriorLaunch pl{prior, word0, noise_counter, reinterpret_cast<int32_t*>(b + branch + V * 8)};
-    rc = earl_unit_sawyer_branch_prior(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, &bws, summary, last_obs, fail_count, pv ? pv->discount : 1.0,
-                                       reinterpret_cast<double*>(b + branch), &pl, stream);
-  }
-  if (rc || V == 0 || H == 0 || !pv || !pv->value) return rc;
-  return launch_value(pv, nv, V, H, last_obs, ws->base, summary->ret, stream);
+  // (no prior: `act` is read only)
+  return earl_unit_sawyer_branch_scored(model, col, nv, cfg, st, K, H, const_cast<float*>(act), act_branch_stride, clock, pv, nullptr, 0, 0, ws, summary, last_obs, fail_count,
+                                        stream);
 }
 
 int earl_sawyer_branch_rollout_prior(const earl_link_model* model, const earl_collision_model* col, int32_t nv, const earl_sawyer_cfg* cfg, const earl_sawyer_state* st,
@@ -183,8 +147,8 @@ int earl_sawyer_branch_rollout_prior(const earl_link_model* model, const earl_co
   if (prior->branches == 0)
     return earl_sawyer_branch_rollout_value(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, pv, ws, summary, last_obs, fail_count, stream);
   if (j < 0 || j > 255) return fail(EARL_ERR_ARG, "iteration %d: 0 .. 255", j);
-  return earl_unit_sawyer_branch_scored_prior(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, pv, prior, kSawyerPriorDraw | (uint32_t)j, noise_counter, ws, summary,
-                                              last_obs, fail_count, stream);
+  return earl_unit_sawyer_branch_scored(model, col, nv, cfg, st, K, H, act, act_branch_stride, clock, pv, prior, kSawyerPriorDraw | (uint32_t)j, noise_counter, ws, summary, last_obs,
+                                        fail_count, stream);
 }
 
 }  // extern "C"

@@ -478,6 +478,24 @@ int do_cem_mpc(const earl_tabletop_cfg* cfg, const earl_tabletop_state* st, cons
   return EARL_OK;
 }
 
+// The candidates walk of both Sawyer planners, one row of n envs per (k, t): row(i, t, m, scale) gives the clipped row and the scale of the noise around it
+template <class Row>
+void sawyer_candidates_walk(const earl_sawyer_cfg* cfg, int K, int H, uint32_t word0, uint32_t noise_counter, float* act_out, Row row) {
+  const int n = cfg->n;
+  const long long rows = (long long)K * H;
+#pragma omp parallel for schedule(static) if (rows * n >= 4096)
+  for (long long kt = 0; kt < rows; ++kt) {
+    const int k = (int)(kt / H), t = (int)(kt - (long long)k * H);
+    for (int i = 0; i < n; ++i) {
+      float m[4], scale[4], c[4];
+      row(i, t, m, scale);
+      shoot_candidate(word0, (uint32_t)(cfg->env_offset + i), (uint32_t)k, (uint32_t)t, noise_counter, cfg->seed, scale, m, c);
+      float* dst = act_out + shoot_act_index(H, n, i, k, t);
+      for (int d = 0; d < 4; ++d) dst[d] = c[d];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -750,7 +768,7 @@ int32_t earl_sawyer_value_terminal_cpu(const earl_plan_value* pv, int32_t H, int
   return EARL_OK;
 }
 // include/earl_physics.h, "policy-prior branches on the door and the peg": the action rows of prior branch k for GIVEN observation rows -- the float32 rounding, the
-// loops above, then the planner's noise function (sawyer_plan.h: splan_candidate around u, with the prior's sigma; k >= 1 always, branch 0 being the plan).  cem != 0: the
+// loops above, then the planner's noise function (sawyer_shoot.h: shoot_candidate around u, with the prior's sigma; k >= 1 always, branch 0 being the plan).  cem != 0: the
 // block CEM's branch k would have drawn (tabletop_cem.h: kCemDraw).  No host stepper: the rows are the caller's
 int32_t earl_sawyer_prior_actions_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_prior* prior, int32_t H, int32_t k, int32_t j, uint32_t noise_counter, int32_t cem,
                                       const double* obs, float* act) {
@@ -765,20 +783,13 @@ int32_t earl_sawyer_prior_actions_cpu(const earl_sawyer_cfg* cfg, const earl_saw
   std::vector<float> x(rows * 14), u(rows * 4);
   for (size_t e = 0; e < x.size(); ++e) x[e] = svalue_row(obs[e]);
   if (int rc = earl_mlp_policy_forward_cpu(prior->policy, nullptr, (int32_t)rows, x.data(), nullptr, u.data())) return rc;
-  SawyerPlanArgs p{};
-  p.seed = cfg->seed;
-  for (int d = 0; d < 4; ++d) p.sigma[d] = prior->sigma[d];
-  p.noise_counter = noise_counter;
-  p.word0 = (cem ? kCemDraw : kPlanDraw) | (uint32_t)j;
-  p.env_offset = cfg->env_offset;
-  p.n = cfg->n;
-  p.H = H;
+  const uint32_t word0 = (cem ? kCemDraw : kPlanDraw) | (uint32_t)j;
   for (int t = 0; t < H; ++t)
-    for (int i = 0; i < p.n; ++i) {
-      const size_t r = ((size_t)t * p.n + i) * 4;
+    for (int i = 0; i < cfg->n; ++i) {
+      const size_t r = ((size_t)t * cfg->n + i) * 4;
       const float m[4] = {u[r], u[r + 1], u[r + 2], u[r + 3]};
       float c[4];
-      splan_candidate(p, i, (uint32_t)k, (uint32_t)t, m, c);
+      shoot_candidate(word0, (uint32_t)(cfg->env_offset + i), (uint32_t)k, (uint32_t)t, noise_counter, cfg->seed, prior->sigma, m, c);
       for (int d = 0; d < 4; ++d) act[r + d] = c[d];
     }
   return EARL_OK;
@@ -788,26 +799,16 @@ float earl_tanh_f32(float x) { return tanh_f32(x); }
 float earl_exp_f32(float x) { return exp_f32(x); }
 float earl_normal_quantile_f32(uint32_t k24) { return normal_quantile_f32(k24 & 0xFFFFFFu); }
 
-// include/earl_physics.h: the Sawyer planner's own arithmetic as plain loops over sawyer_plan.h's per-element functions -- the candidates kernel's, one row of n envs per
-// (k, t), and the update kernel's, one env at a time with k ascending (integer sums: the kernel's split over lanes gives the same bits).  No host stepper: the returns
+// include/earl_physics.h: the Sawyer planner's own arithmetic as plain loops over sawyer_shoot.h's and sawyer_plan.h's per-element functions -- the candidates kernel's (the
+// walk above) and the update kernel's, one env at a time with k ascending (integer sums: the kernel's split over lanes gives the same bits).  No host stepper: the returns
 // of the update are the caller's.
 int32_t earl_sawyer_plan_candidates_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_params* params, int32_t j, const float* mean, float* act_out) {
   if (int rc = check_sawyer_plan(SawyerPlanCall::Candidates, cfg, params, j, mean, act_out)) return rc;
   if (cfg->n == 0) return EARL_OK;
-  SawyerPlanArgs p = sawyer_plan_args(cfg, params, mean);
-  p.word0 = kPlanDraw | (uint32_t)j;
-  const long long rows = (long long)p.K * p.H;
-#pragma omp parallel for schedule(static) if (rows * p.n >= 4096)
-  for (long long kt = 0; kt < rows; ++kt) {
-    const int k = (int)(kt / p.H), t = (int)(kt - (long long)k * p.H);
-    for (int i = 0; i < p.n; ++i) {
-      float m[4], c[4];
-      splan_mean(p, i, t, m);
-      splan_candidate(p, i, (uint32_t)k, (uint32_t)t, m, c);
-      float* dst = act_out + splan_act_index(p, i, k, t);
-      for (int d = 0; d < 4; ++d) dst[d] = c[d];
-    }
-  }
+  sawyer_candidates_walk(cfg, params->K, params->H, kPlanDraw | (uint32_t)j, params->noise_counter, act_out, [&](int i, int t, float (&m)[4], float (&scale)[4]) {
+    shoot_mean(mean, cfg->n, i, t, m);
+    for (int d = 0; d < 4; ++d) scale[d] = params->sigma[d];
+  });
   return EARL_OK;
 }
 int32_t earl_sawyer_plan_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_plan_params* params, int32_t j, const float* mean, const float* act, const double* ret,
@@ -826,13 +827,13 @@ int32_t earl_sawyer_plan_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawye
     for (int k = 0; k < K; ++k) Wk[k] = plan_weight(ret[(size_t)k * n + i], beta, p.inv_temperature);
     for (int t = 0; t < p.H; ++t) {
       float m[4];
-      splan_mean(p, i, t, m);
+      shoot_mean(p.mean, n, i, t, m);
       int64_t A[4] = {0, 0, 0, 0}, S = 0;
       for (int k = 0; k < K; ++k) {
         const int32_t W = Wk[k];
         S += W;
         if (W != 0 && k > 0) {
-          const float* src = act + splan_act_index(p, i, k, t);
+          const float* src = act + shoot_act_index(p.H, n, i, k, t);
           const float c[4] = {src[0], src[1], src[2], src[3]};
           splan_accumulate(c, m, W, A);
         }
@@ -846,27 +847,17 @@ int32_t earl_sawyer_plan_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawye
   return EARL_OK;
 }
 
-// include/earl_physics.h, "CEM planning on the door and the peg": the same two walks over sawyer_cem.h's per-element functions.  The elites of an env are the first E of a
-// sort under cem_before (the order of item 4 itself, where the kernel runs a radix select over its keys) that are not NaN; the moments are integer sums, so the order
-// in which the elites are added gives the same bits as the kernel's split over lanes.
+// include/earl_physics.h, "CEM planning on the door and the peg": the same two walks over sawyer_shoot.h's and sawyer_cem.h's per-element functions.  The elites of an
+// env are the first E of a sort under cem_before (the order of item 4 itself, where the kernel runs a radix select over its keys) that are not NaN; the moments are
+// integer sums, so the order in which the elites are added gives the same bits as the kernel's split over lanes.
 int32_t earl_sawyer_cem_candidates_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_params* params, int32_t j, const float* mean, const float* std, float* act_out) {
   if (int rc = check_sawyer_cem(SawyerCemCall::Candidates, cfg, params, j, mean, std, act_out, nullptr)) return rc;
   if (cfg->n == 0) return EARL_OK;
-  SawyerCemArgs p = sawyer_cem_args(cfg, params, mean, std);
-  p.word0 = kCemDraw | (uint32_t)j;
-  const long long rows = (long long)p.K * p.H;
-#pragma omp parallel for schedule(static) if (rows * p.n >= 4096)
-  for (long long kt = 0; kt < rows; ++kt) {
-    const int k = (int)(kt / p.H), t = (int)(kt - (long long)k * p.H);
-    for (int i = 0; i < p.n; ++i) {
-      float m[4], s[4], c[4];
-      scem_mean(p, i, t, m);
-      scem_std(p, i, t, s);
-      scem_candidate(p, i, (uint32_t)k, (uint32_t)t, m, s, c);
-      float* dst = act_out + scem_act_index(p, i, k, t);
-      for (int d = 0; d < 4; ++d) dst[d] = c[d];
-    }
-  }
+  const SawyerCemArgs p = sawyer_cem_args(cfg, params, mean, std);
+  sawyer_candidates_walk(cfg, p.K, p.H, kCemDraw | (uint32_t)j, p.noise_counter, act_out, [&](int i, int t, float (&m)[4], float (&scale)[4]) {
+    shoot_mean(mean, p.n, i, t, m);
+    scem_std(p, i, t, scale);
+  });
   return EARL_OK;
 }
 int32_t earl_sawyer_cem_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer_cem_params* params, int32_t j, const float* mean, const float* std_in, const float* act,
@@ -892,13 +883,13 @@ int32_t earl_sawyer_cem_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer
     }
     for (int t = 0; t < p.H; ++t) {
       float m[4], s[4];
-      scem_mean(p, i, t, m);
+      shoot_mean(p.mean, n, i, t, m);
       scem_std(p, i, t, s);
       int64_t A1[4] = {0, 0, 0, 0}, A2[4] = {0, 0, 0, 0};
       for (int e = 0; e < Ne; ++e) {
         const int k = order[e];
         if (k > 0) {
-          const float* src = act + scem_act_index(p, i, k, t);
+          const float* src = act + shoot_act_index(p.H, n, i, k, t);
           const float c[4] = {src[0], src[1], src[2], src[3]};
           scem_accumulate(c, m, A1, A2);
         }

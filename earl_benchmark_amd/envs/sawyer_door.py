@@ -334,15 +334,19 @@ class SawyerDoor(PhysicsEnv):
     self._launch_rollout(self._actions(a, (T,)), T, out)
     return out
 
-  def _branch_ws(self, K):
-    """the workspace of a branch launch of K branches (include/earl_physics.h: earl_sawyer_branch_ws): one device block, allocated at the first use and cached per K"""
-    cache = self.__dict__.setdefault('_branch_ws_cache', {})
-    if K not in cache:
-      need = C.c_int64(0)
-      _abi.check(self._lib.earl_sawyer_branch_ws_bytes(self.nv, K, self.num_envs, C.byref(need)), 'earl_sawyer_branch_ws_bytes')
+  _WS_BYTES = {'branch': 'earl_sawyer_branch_ws_bytes', 'plan': 'earl_sawyer_plan_ws_bytes', 'value': 'earl_sawyer_value_ws_bytes', 'prior': 'earl_sawyer_prior_ws_bytes'}
+
+  def _ws(self, kind, K, H=0):
+    """the workspace (include/earl_physics.h: earl_sawyer_branch_ws) of a branch launch of K branches ('branch'), of a planner call ('plan': that block and the
+    [K, H, N, 4] candidates behind it) or of a `_value` / `_prior` call ('value', 'prior'; H = 0: the branch call's own): one device block, allocated at the first use
+    and cached per (kind, K, H)"""
+    cache = self.__dict__.setdefault('_ws_cache', {})
+    if (kind, K, H) not in cache:
+      name, need = self._WS_BYTES[kind], C.c_int64(0)
+      _abi.check(getattr(self._lib, name)(self.nv, K, *(() if kind == 'branch' else (H,)), self.num_envs, C.byref(need)), name)
       block = torch.empty(max(need.value, 8) // 8 + 1, dtype=torch.float64, device=self.device)
-      cache[K] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
-    return cache[K][1]
+      cache[(kind, K, H)] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
+    return cache[(kind, K, H)][1]
 
   def _plan_value(self, who, discount, value):
     """-> None (discount 1.0 and no value network: the value-free entry points, called exactly as before those keywords existed) or the struct earl_plan_value of the
@@ -363,16 +367,6 @@ class SawyerDoor(PhysicsEnv):
     pv = _abi.PlanValue(discount=float(discount), value=C.pointer(value.struct))
     pv._keep = value
     return pv
-
-  def _value_ws(self, K, H):
-    """the workspace of a `_value` call (earl_sawyer_value_ws_bytes; H = 0: the branch launch's own): one device block, cached per (K, H) like _plan_ws"""
-    cache = self.__dict__.setdefault('_value_ws_cache', {})
-    if (K, H) not in cache:
-      need = C.c_int64(0)
-      _abi.check(self._lib.earl_sawyer_value_ws_bytes(self.nv, K, H, self.num_envs, C.byref(need)), 'earl_sawyer_value_ws_bytes')
-      block = torch.empty(max(need.value, 8) // 8 + 1, dtype=torch.float64, device=self.device)
-      cache[(K, H)] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
-    return cache[(K, H)][1]
 
   def _plan_prior(self, who, prior, P, K, prior_sigma):
     """-> None (prior=None: the calls made before the keyword existed) or a function act -> the struct earl_sawyer_plan_prior of the `_prior` entry points
@@ -406,15 +400,13 @@ class SawyerDoor(PhysicsEnv):
       return pr
     return struct
 
-  def _prior_ws(self, K, H):
-    """the workspace of a `_prior` call (earl_sawyer_prior_ws_bytes; H = 0: the branch launch's own): one device block, cached per (K, H) like _plan_ws"""
-    cache = self.__dict__.setdefault('_prior_ws_cache', {})
-    if (K, H) not in cache:
-      need = C.c_int64(0)
-      _abi.check(self._lib.earl_sawyer_prior_ws_bytes(self.nv, K, H, self.num_envs, C.byref(need)), 'earl_sawyer_prior_ws_bytes')
-      block = torch.empty(max(need.value, 8) // 8 + 1, dtype=torch.float64, device=self.device)
-      cache[(K, H)] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
-    return cache[(K, H)][1]
+  def _branch_result(self, K):
+    """the dict of a branch launch over K branches and the struct earl_episode_summary over its rows"""
+    n, kw = self.num_envs, dict(device=self.device)
+    res = {'ret': torch.empty(K, n, dtype=torch.float64, **kw), 'success': torch.empty(K, n, dtype=torch.bool, **kw),
+           'first_success': torch.empty(K, n, dtype=torch.int32, **kw), 'last_obs': torch.empty(K, n, self.OBS_DIM, dtype=torch.float64, **kw),
+           'fail': torch.empty(K, n, dtype=torch.int32, **kw)}
+    return res, _abi.EpisodeSummary(ret=res['ret'].data_ptr(), success_last=res['success'].data_ptr(), first_success=res['first_success'].data_ptr())
 
   def rollout_branches(self, actions, K=None, clock=None, discount=1.0, value=None, prior=None, prior_branches=0, prior_sigma=0.0, noise_counter=None, iteration=0):
     """K candidate action sequences of H steps scored per env FROM THE CURRENT STATE in one launch of the rollout kernel over K N virtual envs (include/earl_physics.h:
@@ -451,20 +443,16 @@ class SawyerDoor(PhysicsEnv):
       raise ValueError(f'rollout_branches: K = {K}, H = {H}: at least one branch of at least one step')
     if K * n > INT32_MAX:
       raise ValueError(f'rollout_branches: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
-    kw = dict(device=self.device)
-    res = {'ret': torch.empty(K, n, dtype=torch.float64, **kw), 'success': torch.empty(K, n, dtype=torch.bool, **kw),
-           'first_success': torch.empty(K, n, dtype=torch.int32, **kw), 'last_obs': torch.empty(K, n, self.OBS_DIM, dtype=torch.float64, **kw),
-           'fail': torch.empty(K, n, dtype=torch.int32, **kw)}
-    summary = _abi.EpisodeSummary(ret=res['ret'].data_ptr(), success_last=res['success'].data_ptr(), first_success=res['first_success'].data_ptr())
+    res, summary = self._branch_result(K)
     self._cfg.step_counter = self.total_step_count
     with torch.cuda.device(self.device):
       if pv is not None:
-        ws = self._value_ws(K, 0)
+        ws = self._ws('value', K)
         _abi.check(self._lib.earl_sawyer_branch_rollout_value(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, K, H, act.data_ptr(),
                                                               stride, clock, C.byref(pv), C.byref(ws), C.byref(summary), res['last_obs'].data_ptr(),
                                                               res['fail'].data_ptr(), self._stream()), 'earl_sawyer_branch_rollout_value')
         return res
-      ws = self._branch_ws(K)
+      ws = self._ws('branch', K)
       _abi.check(self._lib.earl_sawyer_branch_rollout(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, K, H, act.data_ptr(), stride,
                                                       clock, C.byref(ws), C.byref(summary), res['last_obs'].data_ptr(), res['fail'].data_ptr(), self._stream()),
                  'earl_sawyer_branch_rollout')
@@ -488,15 +476,13 @@ class SawyerDoor(PhysicsEnv):
     kw = dict(device=self.device)
     act = torch.empty(K, H, n, 4, dtype=torch.float32, **kw)
     act[:K - P].copy_(self._actions(a, (K - P, H)))
-    res = {'ret': torch.empty(K, n, dtype=torch.float64, **kw), 'success': torch.empty(K, n, dtype=torch.bool, **kw),
-           'first_success': torch.empty(K, n, dtype=torch.int32, **kw), 'last_obs': torch.empty(K, n, self.OBS_DIM, dtype=torch.float64, **kw),
-           'fail': torch.empty(K, n, dtype=torch.int32, **kw), 'prior_actions': torch.empty(P, H, n, 4, dtype=torch.float32, **kw), 'actions': act}
-    summary = _abi.EpisodeSummary(ret=res['ret'].data_ptr(), success_last=res['success'].data_ptr(), first_success=res['first_success'].data_ptr())
+    res, summary = self._branch_result(K)
+    res.update(prior_actions=torch.empty(P, H, n, 4, dtype=torch.float32, **kw), actions=act)
     nc = self.total_step_count if noise_counter is None else int(noise_counter)
     self._cfg.step_counter = self.total_step_count
     with torch.cuda.device(self.device):
       pr = make(res['prior_actions'])
-      ws = self._prior_ws(K, 0)
+      ws = self._ws('prior', K)
       _abi.check(self._lib.earl_sawyer_branch_rollout_prior(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, K, H, act.data_ptr(),
                                                             H * n * 4, clock, C.byref(pv) if pv is not None else None, C.byref(pr), iteration, nc & 0xFFFFFFFF,
                                                             C.byref(ws), C.byref(summary), res['last_obs'].data_ptr(), res['fail'].data_ptr(), self._stream()),
@@ -504,16 +490,6 @@ class SawyerDoor(PhysicsEnv):
     return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
 
   # ------------------------------------------------------------------ MPPI on top of the branch launch (include/earl_physics.h: earl_sawyer_plan_mppi)
-  def _plan_ws(self, K, H):
-    """the workspace of a planner call (the branch launch's block and the [K, H, N, 4] candidates behind it): one device block, cached per (K, H) like _branch_ws"""
-    cache = self.__dict__.setdefault('_plan_ws_cache', {})
-    if (K, H) not in cache:
-      need = C.c_int64(0)
-      _abi.check(self._lib.earl_sawyer_plan_ws_bytes(self.nv, K, H, self.num_envs, C.byref(need)), 'earl_sawyer_plan_ws_bytes')
-      block = torch.empty(max(need.value, 8) // 8 + 1, dtype=torch.float64, device=self.device)
-      cache[(K, H)] = (block, _abi.SawyerBranchWs(base=block.data_ptr(), bytes=block.numel() * 8))
-    return cache[(K, H)][1]
-
   def _plan_mean(self, who, mean, horizon):
     n = self.num_envs
     if mean is None:
@@ -525,19 +501,63 @@ class SawyerDoor(PhysicsEnv):
       raise ValueError(f'{who}: mean must be [H, N, 4] = [{"H" if horizon is None else horizon}, {n}, 4], got {list(m.shape)}')
     return self._actions(m, (int(m.shape[0]),))
 
-  def _plan_params(self, who, K, H, iterations, iteration0, sigma, temperature, noise_counter):
+  def _shoot_params(self, who, K, H, iterations, sigma, noise_counter, temperature=None):
+    """what _plan_params and _cem_params share, in their order of refusal -> (sigma as four floats, the low word of the noise counter)"""
     s = torch.as_tensor(sigma, dtype=torch.float32).reshape(-1).tolist()
     if len(s) not in (1, 4):
       raise ValueError(f'{who}: sigma is a number or four, one per action dimension (x, y, z, gripper)')
-    if not float(temperature) > 0.0:
+    if temperature is not None and not float(temperature) > 0.0:
       raise ValueError(f'{who}: temperature = {temperature}: > 0')
     if not 1 <= int(K) <= _abi.SAWYER_PLAN_MAX_K:
       raise ValueError(f'{who}: K = {K}: 1 .. {_abi.SAWYER_PLAN_MAX_K} candidates per env (branch 0, the plan itself, included)')
     if int(H) < 1 or int(iterations) < 1:
       raise ValueError(f'{who}: H = {H}, iterations = {iterations}: at least one of each')
     nc = self.total_step_count if noise_counter is None else int(noise_counter)   # (None: the low word of the env's step count -- fresh noise per control step)
-    return _abi.SawyerPlanParams(K=int(K), H=int(H), iterations=int(iterations), iteration0=int(iteration0), sigma=(C.c_float * 4)(*(s * 4 if len(s) == 1 else s)),
-                                 noise_counter=nc & 0xFFFFFFFF, inv_temperature=1.0 / float(temperature))
+    return (C.c_float * 4)(*(s * 4 if len(s) == 1 else s)), nc & 0xFFFFFFFF
+
+  def _plan_params(self, who, K, H, iterations, iteration0, sigma, temperature, noise_counter):
+    s, nc = self._shoot_params(who, K, H, iterations, sigma, noise_counter, temperature)
+    return _abi.SawyerPlanParams(K=int(K), H=int(H), iterations=int(iterations), iteration0=int(iteration0), sigma=s, noise_counter=nc, inv_temperature=1.0 / float(temperature))
+
+  def _plan(self, method, m, params, s0, clock, out, pv, make, P):
+    """what plan_mppi and plan_cem do behind their own argument checks: the result dict (or the checked `out`), then earl_sawyer_plan_{mppi,cem}{,_value,_prior} -- `_prior`
+    with a prior (make: what _plan_prior returned), else `_value` with a struct earl_plan_value, else the entry point the call reached before those keywords existed"""
+    who, cem = 'plan_' + method, method == 'cem'
+    n, H, K, I = self.num_envs, int(params.H), int(params.K), int(params.iterations)
+    if K * n > INT32_MAX:
+      raise ValueError(f'{who}: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
+    kw = dict(device=self.device)
+    rows = ((H, n, 4), torch.float32)
+    want = {'plan': rows, **({'std': rows} if cem else {}), 'ret': ((K, n), torch.float64), 'ret0': ((I, n), torch.float64), 'best_ret': ((n,), torch.float64),
+            'best_k': ((n,), torch.int32), **({'elite': ((K, n), torch.uint8)} if cem else {}), 'fail': ((K, n), torch.int32)}
+    if make is not None:
+      want['prior_actions'] = ((int(P), H, n, 4), torch.float32)
+    if out is None:
+      res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
+    else:
+      if set(out) - set(want):
+        raise ValueError(f'{who}: out holds {sorted(set(out) - set(want))}; the keys are {list(want)}')
+      res = {k: t for k, t in out.items() if t is not None}
+      for k, t in res.items():
+        shape, dt = want[k]
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+          raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
+      if 'plan' not in res:
+        raise ValueError(f"{who}: out['plan'] is what the call computes")
+      for k in ('ret',) + (('std',) if cem else ()) + (('prior_actions',) if make is not None else ()):      # (what the call itself needs)
+        if k not in res:
+          res[k] = torch.empty(*want[k][0], dtype=want[k][1], **kw)
+    kind = 'plan' if make is None and pv is None else 'value' if make is None else 'prior'
+    name = f'earl_sawyer_plan_{method}' + {'plan': '', 'value': '_value', 'prior': '_prior'}[kind]
+    self._cfg.step_counter = self.total_step_count
+    with torch.cuda.device(self.device):
+      pr = make(res['prior_actions']) if make is not None else None
+      blocks = () if kind == 'plan' else (C.byref(pv) if pv is not None else None,) + ((C.byref(pr),) if make is not None else ())
+      arrays = (m.data_ptr(), _ptr(s0), res['plan'].data_ptr(), res['std'].data_ptr()) if cem else (m.data_ptr(), res['plan'].data_ptr())
+      rest = [_ptr(res.get(k)) for k in ('ret0', 'best_ret', 'best_k') + (('elite',) if cem else ()) + ('fail',)]
+      _abi.check(getattr(self._lib, name)(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(params), *blocks, *arrays,
+                                          res['ret'].data_ptr(), *rest, clock, C.byref(self._ws(kind, K, H)), self._stream()), name)
+    return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
 
   def plan_mppi(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, clock=None, out=None, discount=1.0,
                 value=None, prior=None, prior_branches=0, prior_sigma=0.0):
@@ -560,53 +580,10 @@ class SawyerDoor(PhysicsEnv):
     prior=None calls exactly what is called without the keywords."""
     m = self._plan_mean('plan_mppi', mean, horizon)
     pv = self._plan_value('plan_mppi', discount, value)
-    n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
+    H, K, I = int(m.shape[0]), int(K), int(iterations)
     pp = self._plan_params('plan_mppi', K, H, I, iteration0, sigma, temperature, noise_counter)
     make = self._plan_prior('plan_mppi', prior, prior_branches, K, prior_sigma)
-    if K * n > INT32_MAX:
-      raise ValueError(f'plan_mppi: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
-    kw = dict(device=self.device)
-    want = {'plan': ((H, n, 4), torch.float32), 'ret': ((K, n), torch.float64), 'ret0': ((I, n), torch.float64), 'best_ret': ((n,), torch.float64),
-            'best_k': ((n,), torch.int32), 'fail': ((K, n), torch.int32)}
-    if make is not None:
-      want['prior_actions'] = ((int(prior_branches), H, n, 4), torch.float32)
-    if out is None:
-      res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
-    else:
-      if set(out) - set(want):
-        raise ValueError(f'plan_mppi: out holds {sorted(set(out) - set(want))}; the keys are {list(want)}')
-      res = {k: t for k, t in out.items() if t is not None}
-      for k, t in res.items():
-        shape, dt = want[k]
-        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
-          raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
-      if 'plan' not in res:
-        raise ValueError("plan_mppi: out['plan'] is what the call computes")
-      if 'ret' not in res:
-        res['ret'] = torch.empty(K, n, dtype=torch.float64, **kw)
-      if make is not None and 'prior_actions' not in res:
-        res['prior_actions'] = torch.empty(*want['prior_actions'][0], dtype=torch.float32, **kw)
-    self._cfg.step_counter = self.total_step_count
-    with torch.cuda.device(self.device):
-      if make is not None:
-        pr = make(res['prior_actions'])
-        ws = self._prior_ws(K, H)
-        _abi.check(self._lib.earl_sawyer_plan_mppi_prior(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pp),
-                                                         C.byref(pv) if pv is not None else None, C.byref(pr), m.data_ptr(), res['plan'].data_ptr(), res['ret'].data_ptr(),
-                                                         _ptr(res.get('ret0')), _ptr(res.get('best_ret')), _ptr(res.get('best_k')), _ptr(res.get('fail')), clock,
-                                                         C.byref(ws), self._stream()), 'earl_sawyer_plan_mppi_prior')
-        return res
-      if pv is not None:
-        ws = self._value_ws(K, H)
-        _abi.check(self._lib.earl_sawyer_plan_mppi_value(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pp), C.byref(pv),
-                                                         m.data_ptr(), res['plan'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
-                                                         _ptr(res.get('best_k')), _ptr(res.get('fail')), clock, C.byref(ws), self._stream()), 'earl_sawyer_plan_mppi_value')
-        return res
-      ws = self._plan_ws(K, H)
-      _abi.check(self._lib.earl_sawyer_plan_mppi(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(pp), m.data_ptr(),
-                                                 res['plan'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')), _ptr(res.get('best_k')),
-                                                 _ptr(res.get('fail')), clock, C.byref(ws), self._stream()), 'earl_sawyer_plan_mppi')
-    return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
+    return self._plan('mppi', m, pp, None, clock, out, pv, make, prior_branches)
 
   def plan_candidates(self, mean, K, sigma=0.3, iteration=0, noise_counter=None):
     """the K candidates of plan_mppi's iteration `iteration` around `mean` [H, N, 4], written out: [K, H, N, 4] float32, row 0 the clipped mean (all four words: the
@@ -623,23 +600,15 @@ class SawyerDoor(PhysicsEnv):
 
   # ------------------------------------------------------------------ CEM on top of the branch launch (include/earl_physics.h: earl_sawyer_plan_cem)
   def _cem_params(self, who, K, H, iterations, iteration0, elites, sigma, alpha, std_min, std_max, noise_counter, update=True):
-    s = torch.as_tensor(sigma, dtype=torch.float32).reshape(-1).tolist()
-    if len(s) not in (1, 4):
-      raise ValueError(f'{who}: sigma is a number or four, one per action dimension (x, y, z, gripper)')
-    if not 1 <= int(K) <= _abi.SAWYER_PLAN_MAX_K:
-      raise ValueError(f'{who}: K = {K}: 1 .. {_abi.SAWYER_PLAN_MAX_K} candidates per env (branch 0, the plan itself, included)')
-    if int(H) < 1 or int(iterations) < 1:
-      raise ValueError(f'{who}: H = {H}, iterations = {iterations}: at least one of each')
+    s, nc = self._shoot_params(who, K, H, iterations, sigma, noise_counter)
     if update and not 1 <= int(elites) <= min(int(K), _abi.SAWYER_CEM_MAX_E):
       raise ValueError(f'{who}: elites = {elites}: 1 .. min(K, {_abi.SAWYER_CEM_MAX_E}) = {min(int(K), _abi.SAWYER_CEM_MAX_E)}')
     if update and not 0.0 <= float(alpha) < 1.0:
       raise ValueError(f'{who}: alpha = {alpha}: 0 <= alpha < 1')
     if not 0.0 <= float(std_min) <= float(std_max) < float('inf'):
       raise ValueError(f'{who}: std_min = {std_min}, std_max = {std_max}: finite, 0 <= std_min <= std_max')
-    nc = self.total_step_count if noise_counter is None else int(noise_counter)   # (None: the low word of the env's step count -- fresh noise per control step)
-    return _abi.SawyerCemParams(K=int(K), H=int(H), iterations=int(iterations), iteration0=int(iteration0), elites=int(elites) if update else 1,
-                                sigma=(C.c_float * 4)(*(s * 4 if len(s) == 1 else s)), noise_counter=nc & 0xFFFFFFFF, alpha=float(alpha) if update else 0.0,
-                                std_min=float(std_min), std_max=float(std_max))
+    return _abi.SawyerCemParams(K=int(K), H=int(H), iterations=int(iterations), iteration0=int(iteration0), elites=int(elites) if update else 1, sigma=s, noise_counter=nc,
+                                alpha=float(alpha) if update else 0.0, std_min=float(std_min), std_max=float(std_max))
 
   def _cem_std(self, who, std, H):
     if std is None:
@@ -668,56 +637,11 @@ class SawyerDoor(PhysicsEnv):
     the noise branches come first (k ascending).  The result gains 'prior_actions' [P, H, N, 4]."""
     m = self._plan_mean('plan_cem', mean, horizon)
     pv = self._plan_value('plan_cem', discount, value)
-    n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
+    H, K, I = int(m.shape[0]), int(K), int(iterations)
     cp = self._cem_params('plan_cem', K, H, I, iteration0, elites, sigma, alpha, std_min, std_max, noise_counter)
     make = self._plan_prior('plan_cem', prior, prior_branches, K, prior_sigma)
     s0 = self._cem_std('plan_cem', std, H)
-    if K * n > INT32_MAX:
-      raise ValueError(f'plan_cem: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
-    kw = dict(device=self.device)
-    want = {'plan': ((H, n, 4), torch.float32), 'std': ((H, n, 4), torch.float32), 'ret': ((K, n), torch.float64), 'ret0': ((I, n), torch.float64),
-            'best_ret': ((n,), torch.float64), 'best_k': ((n,), torch.int32), 'elite': ((K, n), torch.uint8), 'fail': ((K, n), torch.int32)}
-    if make is not None:
-      want['prior_actions'] = ((int(prior_branches), H, n, 4), torch.float32)
-    if out is None:
-      res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
-    else:
-      if set(out) - set(want):
-        raise ValueError(f'plan_cem: out holds {sorted(set(out) - set(want))}; the keys are {list(want)}')
-      res = {k: t for k, t in out.items() if t is not None}
-      for k, t in res.items():
-        shape, dt = want[k]
-        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
-          raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
-      if 'plan' not in res:
-        raise ValueError("plan_cem: out['plan'] is what the call computes")
-      for k in ('ret', 'std') + (('prior_actions',) if make is not None else ()):
-        if k not in res:
-          res[k] = torch.empty(*want[k][0], dtype=want[k][1], **kw)
-    self._cfg.step_counter = self.total_step_count
-    with torch.cuda.device(self.device):
-      if make is not None:
-        pr = make(res['prior_actions'])
-        ws = self._prior_ws(K, H)
-        _abi.check(self._lib.earl_sawyer_plan_cem_prior(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(cp),
-                                                        C.byref(pv) if pv is not None else None, C.byref(pr), m.data_ptr(), _ptr(s0), res['plan'].data_ptr(),
-                                                        res['std'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
-                                                        _ptr(res.get('best_k')), _ptr(res.get('elite')), _ptr(res.get('fail')), clock, C.byref(ws), self._stream()),
-                   'earl_sawyer_plan_cem_prior')
-        return res
-      if pv is not None:
-        ws = self._value_ws(K, H)
-        _abi.check(self._lib.earl_sawyer_plan_cem_value(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(cp), C.byref(pv),
-                                                        m.data_ptr(), _ptr(s0), res['plan'].data_ptr(), res['std'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')),
-                                                        _ptr(res.get('best_ret')), _ptr(res.get('best_k')), _ptr(res.get('elite')), _ptr(res.get('fail')), clock,
-                                                        C.byref(ws), self._stream()), 'earl_sawyer_plan_cem_value')
-        return res
-      ws = self._plan_ws(K, H)
-      _abi.check(self._lib.earl_sawyer_plan_cem(self.model.buf.data_ptr(), self.model.col_ptr, self.nv, self._cfg_ref, self._st_ref, C.byref(cp), m.data_ptr(), _ptr(s0),
-                                                res['plan'].data_ptr(), res['std'].data_ptr(), res['ret'].data_ptr(), _ptr(res.get('ret0')), _ptr(res.get('best_ret')),
-                                                _ptr(res.get('best_k')), _ptr(res.get('elite')), _ptr(res.get('fail')), clock, C.byref(ws), self._stream()),
-                 'earl_sawyer_plan_cem')
-    return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
+    return self._plan('cem', m, cp, s0, clock, out, pv, make, prior_branches)
 
   def cem_candidates(self, mean, K, sigma=0.3, std=None, iteration=0, noise_counter=None, std_min=0.0, std_max=2.0):
     """the K candidates of plan_cem's iteration `iteration` around `mean` [H, N, 4] with the std `std` [H, N, 4] (None: `sigma` in every row), written out:

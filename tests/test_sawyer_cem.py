@@ -374,7 +374,7 @@ def test_the_two_kernels_compile_without_scratch_and_the_unit_holds_nothing_else
   src = re.search(r'^SRC\s*=\s*(.*)$', mk, flags=re.M).group(1).split()
   assert src.count('sawyer_cem.hip') == 1 and len(src) == len(set(src))
   assert re.search(r'^sawyer_cem\.o:.*\bsawyer_cem\.h\b.*\bcem_select\.h\b', mk, flags=re.M)
-  text = ''.join(open(os.path.join(kernel_build.CSRC, f)).read() for f in ('sawyer_cem.hip', 'sawyer_cem.h', 'cem_select.h'))
+  text = ''.join(open(os.path.join(kernel_build.CSRC, f)).read() for f in ('sawyer_cem.hip', 'sawyer_cem.h', 'sawyer_shoot.h', 'cem_select.h'))
   assert not re.search(r'#include\s+"physics_', text), 'the planner reaches the branch launch through the public ABI only'
   select = open(os.path.join(kernel_build.CSRC, 'cem_select.h')).read()
   assert not re.search(r'sawyer|Sawyer|#include\s+"', select), 'the selection names no env and includes no project header: another update kernel can adopt it'

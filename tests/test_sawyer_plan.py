@@ -358,7 +358,7 @@ def test_the_two_kernels_compile_without_scratch_and_the_unit_holds_nothing_else
   src = re.search(r'^SRC\s*=\s*(.*)$', mk, flags=re.M).group(1).split()
   assert src.count('sawyer_plan.hip') == 1 and len(src) == len(set(src))
   assert [u for u in src if 'plan' in u and u.startswith(('sawyer', 'physics'))] == ['sawyer_plan.hip']
-  text = open(os.path.join(kernel_build.CSRC, 'sawyer_plan.hip')).read() + open(os.path.join(kernel_build.CSRC, 'sawyer_plan.h')).read()
+  text = ''.join(open(os.path.join(kernel_build.CSRC, f)).read() for f in ('sawyer_plan.hip', 'sawyer_plan.h', 'sawyer_shoot.h'))
   assert not re.search(r'#include\s+"physics_', text), 'the planner reaches the branch launch through the public ABI only'
   rollout_text = [f for f in sorted(os.listdir(kernel_build.CSRC)) if f.endswith(('.h', '.hip'))
                   and '#include "physics_env_sawyer_rollout.inc"' in open(os.path.join(kernel_build.CSRC, f)).read()]

@@ -198,6 +198,18 @@ class MinitaurOut(C.Structure):    # struct earl_minitaur_out
   _fields_ = [(k, C.c_void_p) for k in ('obs', 'reward', 'done', 'success', 'status')]
 
 
+class MinitaurBranchWs(C.Structure):   # struct earl_minitaur_branch_ws (include/earl_physics.h): one device block of earl_minitaur_branch_ws_bytes() bytes
+  _fields_ = [('base', C.c_void_p), ('bytes', C.c_int64)]
+
+
+class MinitaurPlanParams(C.Structure):   # struct earl_minitaur_plan_params (include/earl_physics.h): earl_sawyer_plan_params with eight action dimensions
+  _fields_ = [('K', C.c_int32), ('H', C.c_int32), ('iterations', C.c_int32), ('iteration0', C.c_int32), ('sigma', C.c_float * 8), ('noise_counter', C.c_uint32),
+              ('inv_temperature', C.c_double)]
+
+
+MINITAUR_PLAN_MAX_K = 8192   # EARL_MINITAUR_PLAN_MAX_K
+
+
 _P = C.POINTER
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/earl_tabletop.h one to one
 SIGNATURES = {
@@ -339,6 +351,14 @@ SIGNATURES = {
                                     _P(EpisodeSummary), C.c_void_p],
     'earl_kitchen_policy_rollout': [C.c_void_p, C.c_void_p, _P(KitchenParams), _P(KitchenCfg), _P(KitchenState), _P(MlpPolicy), _P(GaussianHead), C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p, _P(KitchenOut), C.c_void_p],
+    # K action plans per env scored from the current state: K, H, act, act_branch_stride, clock, the workspace (earl_minitaur_branch_ws_bytes), summary, last_obs, fail
+    'earl_minitaur_branch_ws_bytes': [C.c_int32, C.c_int32, _P(C.c_int64)],
+    'earl_minitaur_branch_rollout': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                     _P(MinitaurBranchWs), _P(EpisodeSummary), C.c_void_p, C.c_void_p, C.c_void_p],
+    # the MPPI planner around that launch: params, mean, plan, ret, ret0, best_ret, best_k, fail, clock, the workspace (earl_minitaur_plan_ws_bytes)
+    'earl_minitaur_plan_ws_bytes': [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int64)],
+    'earl_minitaur_plan_mppi': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), _P(MinitaurPlanParams)] + [C.c_void_p] * 8 + [_P(MinitaurBranchWs), C.c_void_p],
+    'earl_minitaur_plan_candidates': [_P(MinitaurCfg), _P(MinitaurPlanParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_minitaur_reset': [C.c_void_p, C.c_void_p, _P(MinitaurCfg), _P(MinitaurState), C.c_void_p, C.c_void_p, C.c_void_p],
     'earl_minitaur_cfg_size': [],
     'earl_debug_set_minitaur_stepper': [C.c_int],
@@ -396,7 +416,10 @@ HOST_EXTRA_SIGNATURES = {
     # the host twins of the Sawyer planner's two kernels (no host stepper: the update takes the returns): cfg, params, j, mean, act_out | act, ret, plan, ret0_row, best_ret, best_k
     'earl_sawyer_plan_candidates_cpu': ([_P(SawyerCfg), _P(SawyerPlanParams), C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
     'earl_sawyer_plan_update_cpu': ([_P(SawyerCfg), _P(SawyerPlanParams), C.c_int32] + [C.c_void_p] * 7, C.c_int32),
-    # the host twins of its CEM planner's two kernels: cfg, params, j, mean, std, act_out | std_in, act, ret, plan, std, ret0_row, best_ret, best_k, elite
+    # the host twins of the minitaur planner's two kernels, eight action dimensions: the Sawyer twins' argument lists
+    'earl_minitaur_plan_candidates_cpu': ([_P(MinitaurCfg), _P(MinitaurPlanParams), C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
+    'earl_minitaur_plan_update_cpu': ([_P(MinitaurCfg), _P(MinitaurPlanParams), C.c_int32] + [C.c_void_p] * 7, C.c_int32),
+    # the host twins of the Sawyer CEM planner's two kernels: cfg, params, j, mean, std, act_out | std_in, act, ret, plan, std, ret0_row, best_ret, best_k, elite
     'earl_sawyer_cem_candidates_cpu': ([_P(SawyerCfg), _P(SawyerCemParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
     'earl_sawyer_cem_update_cpu': ([_P(SawyerCfg), _P(SawyerCemParams), C.c_int32] + [C.c_void_p] * 10, C.c_int32),
     # the host twin of the planners' value kernel: pv, H, rows, last_obs [rows, 14], ret [rows] (the terminal term is added in place)

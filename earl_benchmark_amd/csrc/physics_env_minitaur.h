@@ -42,6 +42,39 @@ template <bool ARROW> constexpr int mt_wpb() { return ARROW ? EARL_MT_WPB : Lim<
 #include "policy_closed_loop.h"
 struct MinitaurPolicyArgs : ClosedLoopArgs<MinitaurArgs> {};      // pol.dims[0] = 32, pol.dims[n_layers] = 8 (16 with the head); goal rows of 2
 static_assert(std::is_standard_layout<MinitaurArgs>::value && std::is_trivially_copyable<MinitaurPolicyArgs>::value, "the policy phase reads MinitaurPolicyArgs as laid out in the kernel-argument segment");
+// ------------------------------------------------------------------------------------------------ the branch launch (earl_minitaur_branch_rollout; kernels: physics_mt_branch.hip)
+// The rollout's arguments over K n_env VIRTUAL envs v = k n_env + i: cfg.n is their number, `st` the [K n_env] rows of the caller's workspace (filled by
+// minitaur_branch_replicate_kernel in front of the rollout kernel; st.last_obs the one carried observation row, st.fail_count the caller's `fail`, st.steps_since_reset
+// NULL), every pointer of `out` NULL, `action` the [K, H, n_env, 8] candidates.  The fields below are read through the kernel-argument segment where they are used
+// (policy_closed_loop.h on why)
+struct MinitaurBranchArgs : MinitaurArgs {
+  int n_env;                     // the env's own n: the env of v is v % n_env, its branch v / n_env
+  int64_t act_stride;            // floats between consecutive branches' [H, n_env, 8] blocks (0: every branch replays one block)
+  double* br_ret;                // earl_episode_summary of the launch, each NULL or [K n_env]
+  uint8_t* br_last;
+  int32_t* br_first;
+};
+static_assert(std::is_trivially_copyable<MinitaurBranchArgs>::value, "the branch pieces read MinitaurBranchArgs as laid out in the kernel-argument segment");
+// the virtual env's episode summary after env step t, by lane 0: cl_episode_summary's three words, each its definition applied to the step's reward and success (a
+// rolled-back step: 0 and 0)
+__device__ __forceinline__ void mt_branch_summary(const int t, const int v, const double r_t, const uint8_t s_t) {
+  const EARL_KARG MinitaurBranchArgs* ka = cl_kernarg<MinitaurBranchArgs>();
+  double* const br_ret = ka->br_ret;
+  uint8_t* const br_last = ka->br_last;
+  int32_t* const br_first = ka->br_first;
+  if (br_ret) br_ret[v] = (t > 0 ? br_ret[v] : 0.0) + r_t;            // sum over t ascending of (double)reward_t
+  if (br_last) br_last[v] = s_t;                                      // (the one of step H - 1 stays)
+  if (br_first) {
+    const int32_t f = t > 0 ? br_first[v] : -1;
+    br_first[v] = (f < 0 && s_t) ? t : f;
+  }
+}
+// the env whose id a draw of `env` uses: `env` itself, or -- BRANCH, `env` a virtual env -- the env it is a branch of
+template <bool BRANCH>
+__device__ __forceinline__ int mt_draw_env(const int env) {
+  if constexpr (BRANCH) return env % cl_kernarg<MinitaurBranchArgs>()->n_env;
+  else return env;
+}
 // A float32 MLP 32 -> H1 (-> H2) -> 8 | 16 evaluated by the 32 lanes of an env between two env steps (pol_layer<32, true>: element k of a layer on lane k & 31 in register
 // k >> 5; K = 32 makes the input layer a vector layer too).  -> the action's element `sub` on lanes 0 .. 7 of the group, as stored in act_out.
 // `seen`: the env's row of 32 doubles the policy sees (NULL at step 0: the env's row of obs0); `row` = t n + env.  A group that is not live (an idle group of the last
@@ -96,7 +129,14 @@ template <bool POLICY, class A>
 __device__ __forceinline__ void mt_step_action(const A& a, const int t, const int n, const int env, const int sub, const bool live, double (&a64)[8]) {
 #pragma clang fp contract(off)
   const size_t row = (size_t)t * n + env;
-  if constexpr (POLICY) {
+  if constexpr (std::is_same<A, MinitaurBranchArgs>::value) {
+    // the branch launch: `env` is the virtual env v, its action row (k, t, i) of the [K, H, n_env, 8] candidates
+    const EARL_KARG MinitaurBranchArgs* ka = cl_kernarg<MinitaurBranchArgs>();
+    const int n_env = ka->n_env, k = env / n_env, i = env - k * n_env;
+    const float* ap = a.action + (size_t)k * (size_t)ka->act_stride + ((size_t)t * n_env + i) * 8;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) a64[d] = earl::mt_clipd((double)ap[d], -1.01, 1.01);
+  } else if constexpr (POLICY) {
     // what the policy sees: the row this env emitted last, exactly as it stands in out.obs (a rolled-back step's repeated row, the goal entries a goal switch patched),
     // each double rounded to float32; at step 0 the caller's obs0.  Lane `sub` reads the element lane `sub` wrote (observe, the rollback and the goal switch all store
     // element `sub` from lane `sub`), after the agent-scope fence that ends every env step.
@@ -131,6 +171,7 @@ __device__ __forceinline__ void mt_pair_handover(const A& a, const int t, const 
                      if (live && sub == 0) { a.st.goal[(size_t)env * 2] = goal0; a.st.goal[(size_t)env * 2 + 1] = goal1; }
                    });
 }
+#ifndef EARL_MT_BRANCH             // (physics_mt_branch.hip holds the branch kernels only)
 template <bool RESET, bool ARROW>
 __global__ __launch_bounds__(64 * mt_wpb<ARROW>(), ARROW ? EARL_MT_BLOCKS : 1) void minitaur_kernel(const MinitaurArgs a) {
 #include "physics_env_minitaur_rollout.inc"
@@ -142,6 +183,16 @@ __global__ __launch_bounds__(64 * mt_wpb<ARROW>(), ARROW ? EARL_MT_BLOCKS : 1) v
 #include "physics_env_minitaur_rollout.inc"
   static_assert(!RESET && ARROW, "the policy form derives from minitaur_kernel<false, true>");
 }
+#else
+// The branch form (earl_minitaur_branch_rollout), the body's third inclusion: BRANCH = true.  It takes the policy form's arms -- no [T] row, the summaries on lane 0, the
+// carried row handled as the population launch handles st.last_obs -- with the action loaded at (k, t, i) and every draw made with the ENV's id.  `a` must stay the
+// kernel's ONLY argument: the branch fields are read through the kernel-argument segment pointer
+template <bool RESET, bool ARROW>
+__global__ __launch_bounds__(64 * mt_wpb<ARROW>(), ARROW ? EARL_MT_BLOCKS : 1) void minitaur_branch_kernel(const MinitaurBranchArgs a) {
+#include "physics_env_minitaur_rollout.inc"
+  static_assert(!RESET && ARROW, "the branch form derives from minitaur_kernel<false, true>");
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------ two waves per SIMD by ROLE (round 6)
 // The one-wave kernel above needs all 512 registers of a SIMD lane (256 + 256 accumulation registers used as spill space): one wave per SIMD, the vector ALU issuing in
@@ -152,12 +203,19 @@ __global__ __launch_bounds__(64 * mt_wpb<ARROW>(), ARROW ? EARL_MT_BLOCKS : 1) v
 // chip instead of two.  An env's per-step state (motor counters, command, goal, wrapper counters) lives in its LDS block (SharedMTData::ev) between the visits of wave A,
 // which also runs everything around the timesteps (action fetch and leg model, motor model, observation, reward, state rows).  Same expressions as the one-wave kernel.
 constexpr int MT_DUO_PAIRS = 4;
-#ifndef EARL_POLICY_BF16            // (physics_mt_bf16.hip holds the policy kernels only)
+#if !defined(EARL_POLICY_BF16) && !defined(EARL_MT_BRANCH)      // (physics_mt_bf16.hip holds the policy kernels only, physics_mt_branch.hip the branch kernels)
 __global__ __launch_bounds__(128 * MT_DUO_PAIRS, 1) void minitaur_duo_kernel(const MinitaurArgs a) {
 #include "physics_env_minitaur_duo.inc"
 }
 #endif
 // The two-wave kernel with the policy inside: wave A computes env step t's action where the plain kernel loads it (k == 0, after finish_step(t - 1)).  `a` must stay the ONLY argument
+#ifndef EARL_MT_BRANCH
 __global__ __launch_bounds__(128 * MT_DUO_PAIRS, 1) void minitaur_policy_duo_kernel(const MinitaurPolicyArgs a) {
 #include "physics_env_minitaur_duo.inc"
 }
+#else
+// ... and the branch form of the two-wave kernel.  `a` must stay the ONLY argument
+__global__ __launch_bounds__(128 * MT_DUO_PAIRS, 1) void minitaur_branch_duo_kernel(const MinitaurBranchArgs a) {
+#include "physics_env_minitaur_duo.inc"
+}
+#endif

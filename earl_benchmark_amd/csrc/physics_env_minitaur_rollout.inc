@@ -1,6 +1,10 @@
 // the body of minitaur_kernel and of minitaur_policy_kernel (physics_env_minitaur.h): `a` is the kernel's argument, a MinitaurArgs or a MinitaurPolicyArgs
 #pragma clang fp contract(off)
-  constexpr bool POLICY = std::is_same<decltype(a), const MinitaurPolicyArgs>::value;
+  // BRANCH (minitaur_branch_kernel / minitaur_branch_duo_kernel, `a` a MinitaurBranchArgs): the K n virtual envs of earl_minitaur_branch_rollout -- `n` is their number, `env`
+  // a virtual env, the rows of `a.st` the workspace's.  It takes the POLICY arms as the population launch runs them (a.out.obs == NULL: one carried row, summaries), but for
+  // the action, which is given per branch, the pair, which it has none of, and the id of the goal-switch draw, which is the env's
+  constexpr bool BRANCH = std::is_same<decltype(a), const MinitaurBranchArgs>::value;
+  constexpr bool POLICY = std::is_same<decltype(a), const MinitaurPolicyArgs>::value || BRANCH;
   constexpr int NV = 22, LPE = 32, EPW = 64 / LPE, WPB = mt_wpb<ARROW>();
   using SH = std::conditional_t<ARROW, SharedMT, Shared<NV>>;
   __shared__ alignas(16) typename ModelOf<NV>::T m;
@@ -221,7 +225,8 @@
           const uint8_t s_t = failed ? (uint8_t)0 : suc;
           if (a.out.reward) a.out.reward[row] = r_t;
           if (a.out.success) a.out.success[row] = s_t;
-          cl_episode_summary(cl_kernarg<MinitaurPolicyArgs>(), t, env, r_t, s_t);
+          if constexpr (BRANCH) mt_branch_summary(t, env, r_t, s_t);      // (the same three words, rows [K n] of the caller's summary)
+          else cl_episode_summary(cl_kernarg<MinitaurPolicyArgs>(), t, env, r_t, s_t);
           if (a.out.status) a.out.status[row] = failed ? EARL_STEP_DIVERGED : 0;
           if (a.out.done) a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
         }
@@ -231,10 +236,11 @@
         a.out.done[row] = (cfg.horizon > 0 && steps >= cfg.horizon) ? 1 : 0;
       }
       }
-      if constexpr (POLICY) mt_pair_handover(a, t, env, row, sub, live, failed, suc, goal0, goal1);      // earl_minitaur_agents_rollout: the pair's state machine and its goal rows
+      if constexpr (POLICY && !BRANCH) mt_pair_handover(a, t, env, row, sub, live, failed, suc, goal0, goal1);      // earl_minitaur_agents_rollout: the pair's state machine and its goal rows
       if (gcf > 0 && ++sgc >= gcf) {                      // LifelongWrapper.step (lifelong_wrapper.py:36-42): new goal, the observation re-read with it
         sgc = 0;
-        int gi = (int)(mt_draw(cfg, 0xFFFEu, env, cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t) * (double)cfg.n_goals);
+        const int draw_env = mt_draw_env<BRANCH>(env);      // (BRANCH: the ENV's id, never the virtual index: every branch of an env sees the goal the env's next rollout will see)
+        int gi = (int)(mt_draw(cfg, 0xFFFEu, draw_env, cfg.step_counter + (a.clock ? a.clock[1] : 0) + (uint64_t)t) * (double)cfg.n_goals);
         gi = gi >= cfg.n_goals ? cfg.n_goals - 1 : gi;
         goal0 = cfg.goal_table[2 * gi]; goal1 = cfg.goal_table[2 * gi + 1];
         if constexpr (POLICY) {

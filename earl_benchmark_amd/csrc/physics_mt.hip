@@ -8,6 +8,8 @@
 #include "physics_stepper.h"
 #include "policy_check.h"
 #include "policy_math.h"
+#include "minitaur_branch_ws.h"
+#include "tabletop_hostside.h"   // fail: the thread-local message behind earl_last_error
 
 namespace {
 #include "minitaur_stepper.h"
@@ -15,6 +17,10 @@ namespace {
 }  // namespace
 
 #include "physics_launch.h"
+// the branch launch (physics_mt_branch.hip): earl_minitaur_branch_rollout hands it the MinitaurBranchArgs it filled -- first to the replicate kernel (src_state: the env's
+// own earl_minitaur_state, whose [n] rows become the workspace's [K n]), then to the rollout kernel of the form chosen
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_mt_branch_replicate(const void* minitaur_branch_args, const void* src_state, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int earl_unit_mt_branch_rollout(const void* minitaur_branch_args, int duo, void* stream);
 
 namespace {
 
@@ -111,6 +117,58 @@ int earl_minitaur_policy_rollout(const void* model24, const earl_collision_model
                                  const earl_minitaur_out* out, earl_stream_t stream) {
   if (!actions || !out || !out->obs || !out->reward || !out->done || !out->success) return EARL_ERR_ARG;
   return earl_minitaur_population_rollout(model24, col, cfg, st, policy, nullptr, head, obs0, T, clock, actions, out, nullptr, stream);
+}
+// include/earl_physics.h: K action plans per env scored from the current state in ONE launch over K n virtual envs (kernels: physics_mt_branch.hip).  The workspace
+// block is minitaur_branch_ws.h's
+int earl_minitaur_branch_ws_bytes(int32_t K, int32_t n, int64_t* bytes) {
+  if (!bytes || K < 0 || n < 0 || (int64_t)K * n > INT32_MAX) return EARL_ERR_ARG;
+  *bytes = earl::minitaur_branch_layout((int64_t)K * n).bytes;
+  return EARL_OK;
+}
+int earl_minitaur_branch_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                 int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_minitaur_branch_ws* ws,
+                                 const earl_episode_summary* summary, double* last_obs, int32_t* fail_count, earl_stream_t stream) {
+  using earl::hostside::fail;
+  if (!model24 || !cfg || !st) return fail(EARL_ERR_ARG, "minitaur_branch_rollout: model / cfg / st is NULL");
+  if (!minitaur_args_ok(cfg, st) || cfg->num_substeps < 0)
+    return fail(EARL_ERR_ARG, "minitaur_branch_rollout: cfg / st as earl_minitaur_rollout_clocked refuses them (n = %d, a NULL state row, goal switching without its counter, no goal table)", cfg->n);
+  if (!act || !ws) return fail(EARL_ERR_ARG, "minitaur_branch_rollout: act / ws is NULL");
+  if (K < 0 || H < 0) return fail(EARL_ERR_ARG, "minitaur_branch_rollout: K = %d, H = %d: both >= 0", K, H);
+  const int n = cfg->n;
+  if (act_branch_stride < 0 || (act_branch_stride != 0 && act_branch_stride < (int64_t)H * n * 8))
+    return fail(EARL_ERR_ARG, "minitaur_branch_rollout: action stride %lld is neither 0 nor >= H * n * 8 = %lld", (long long)act_branch_stride, (long long)H * n * 8);
+  if (!(summary && (summary->ret || summary->success_last || summary->first_success)) && !last_obs && !fail_count)
+    return fail(EARL_ERR_ARG, "minitaur_branch_rollout: all five outputs are NULL");      // (nothing to compute)
+  const int64_t V = (int64_t)K * n;
+  if (V > INT32_MAX) return fail(EARL_ERR_ARG, "minitaur_branch_rollout: K n = %lld virtual envs: at most 2^31 - 1", (long long)V);
+  const earl::MinitaurBranchLayout L = earl::minitaur_branch_layout(V);
+  if (V > 0 && (!ws->base || (reinterpret_cast<uintptr_t>(ws->base) & 7) != 0 || ws->bytes < L.bytes))
+    return fail(EARL_ERR_ARG, "minitaur_branch_rollout: ws: base %p (8-byte aligned), %lld bytes of the %lld needed", ws->base, (long long)ws->bytes, (long long)L.bytes);
+  if (!g_mt_stepper) return fail(EARL_ERR_ARG, "minitaur_branch_rollout: earl_debug_set_minitaur_stepper(0) has no branch form");      // (as it has no policy form)
+  if (V == 0 || H == 0) return EARL_OK;
+  if (int rc = check_cone(col, false, (hipStream_t)stream, "minitaur_branch_rollout")) return rc;
+  char* const base = static_cast<char*>(ws->base);
+  earl_minitaur_state vs{};                               // the virtual envs' state: the workspace's rows (steps_since_reset: NULL, a branch keeps none)
+  vs.qpos = reinterpret_cast<double*>(base + L.qpos);
+  vs.qvel = reinterpret_cast<double*>(base + L.qvel);
+  vs.goal = reinterpret_cast<double*>(base + L.goal);
+  vs.motor_param = reinterpret_cast<double*>(base + L.motor_param);
+  vs.observed_torque = reinterpret_cast<double*>(base + L.observed_torque);
+  vs.overheat = reinterpret_cast<int32_t*>(base + L.overheat);
+  vs.motor_enabled = reinterpret_cast<uint8_t*>(base + L.motor_enabled);
+  vs.steps_since_goal_change = cfg->goal_change_frequency > 0 ? reinterpret_cast<int32_t*>(base + L.sgc) : nullptr;
+  vs.fail_count = fail_count;                                   // (the replicate kernel clears it, a rolled-back step counts into it)
+  vs.last_obs = last_obs ? last_obs : reinterpret_cast<double*>(base + L.last_obs);      // the one carried row: step by step it IS the observation of the newest stable step
+  MinitaurBranchArgs a{};
+  static_cast<MinitaurArgs&>(a) = MinitaurArgs{model24, col, *cfg, vs, earl_minitaur_out{nullptr, nullptr, nullptr, nullptr, nullptr}, act, H, nullptr, nullptr, solo_mode((int)V), clock};
+  a.cfg.n = (int)V;
+  a.n_env = n;
+  a.act_stride = act_branch_stride;
+  a.br_ret = summary ? summary->ret : nullptr;
+  a.br_last = summary ? summary->success_last : nullptr;
+  a.br_first = summary ? summary->first_success : nullptr;
+  if (int rc = earl_unit_mt_branch_replicate(&a, st, stream)) return rc;
+  return earl_unit_mt_branch_rollout(&a, minitaur_form((int)V, a.solo, cfg->num_substeps) == MtForm::Duo ? 1 : 0, stream);
 }
 int earl_minitaur_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                           const float* action, int32_t T, const earl_minitaur_out* out, earl_stream_t stream) {

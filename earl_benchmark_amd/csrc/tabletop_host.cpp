@@ -18,6 +18,7 @@
 #include "tabletop_prior.h"
 #include "tabletop_policy.h"
 #include "sawyer_plan.h"   // the door / peg planner's candidates and reweighting (earl_sawyer_plan_candidates_cpu, earl_sawyer_plan_update_cpu)
+#include "minitaur_plan.h" // the minitaur planner's, eight action dimensions (earl_minitaur_plan_candidates_cpu, earl_minitaur_plan_update_cpu)
 #include "sawyer_cem.h"    // its CEM planner's candidates and refit (earl_sawyer_cem_candidates_cpu, earl_sawyer_cem_update_cpu)
 #include "sawyer_value.h"  // the terminal value of both (earl_sawyer_value_terminal_cpu)
 #include "../../include/earl_physics.h"
@@ -839,6 +840,62 @@ int32_t earl_sawyer_plan_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawye
         }
       }
       for (int d = 0; d < 4; ++d) plan[((size_t)t * n + i) * 4 + d] = plan_new_mean(m[d], A[d], S);
+    }
+    if (ret0_row) ret0_row[i] = ret[i];
+    if (best_ret) best_ret[i] = beta;
+    if (best_k) best_k[i] = bk;
+  });
+  return EARL_OK;
+}
+
+// include/earl_physics.h, "MPPI planning on the minitaur": the same two walks over minitaur_plan.h's per-element functions, eight action dimensions
+int32_t earl_minitaur_plan_candidates_cpu(const earl_minitaur_cfg* cfg, const earl_minitaur_plan_params* params, int32_t j, const float* mean, float* act_out) {
+  if (int rc = check_minitaur_plan(MinitaurPlanCall::Candidates, cfg, params, j, mean, act_out)) return rc;
+  const int n = cfg->n, K = params->K, H = params->H;
+  if (n == 0) return EARL_OK;
+  float sigma[8];
+  for (int d = 0; d < 8; ++d) sigma[d] = params->sigma[d];
+  const uint32_t word0 = kPlanDraw | (uint32_t)j;
+  const long long rows = (long long)K * H;
+#pragma omp parallel for schedule(static) if (rows * n >= 4096)
+  for (long long kt = 0; kt < rows; ++kt) {
+    const int k = (int)(kt / H), t = (int)(kt - (long long)k * H);
+    for (int i = 0; i < n; ++i) {
+      float m[8], c[8];
+      mtplan_mean(mean, n, i, t, m);
+      mtplan_candidate(word0, (uint32_t)(cfg->env_offset + i), (uint32_t)k, (uint32_t)t, params->noise_counter, cfg->seed, sigma, m, c);
+      float* dst = act_out + mtplan_act_index(H, n, i, k, t);
+      for (int d = 0; d < 8; ++d) dst[d] = c[d];
+    }
+  }
+  return EARL_OK;
+}
+int32_t earl_minitaur_plan_update_cpu(const earl_minitaur_cfg* cfg, const earl_minitaur_plan_params* params, int32_t j, const float* mean, const float* act, const double* ret,
+                                      float* plan, double* ret0_row, double* best_ret, int32_t* best_k) {
+  if (int rc = check_minitaur_plan(MinitaurPlanCall::Update, cfg, params, j, mean, plan)) return rc;
+  if (!act || !ret) return fail(EARL_ERR_ARG, "act/ret is NULL");
+  MinitaurPlanArgs p = minitaur_plan_args(cfg, params, mean);
+  const int n = p.n, K = p.K;
+  for_each_env(n, [&](int i) {
+    double beta = -INFINITY;
+    int bk = 0;
+    for (int k = 0; k < K; ++k) plan_best(ret[(size_t)k * n + i], k, beta, bk);
+    std::vector<int32_t> Wk(K);
+    for (int k = 0; k < K; ++k) Wk[k] = plan_weight(ret[(size_t)k * n + i], beta, p.inv_temperature);
+    for (int t = 0; t < p.H; ++t) {
+      float m[8];
+      mtplan_mean(p.mean, n, i, t, m);
+      int64_t A[8] = {0, 0, 0, 0, 0, 0, 0, 0}, S = 0;
+      for (int k = 0; k < K; ++k) {
+        const int32_t W = Wk[k];
+        S += W;
+        if (W != 0 && k > 0) {
+          const float* src = act + mtplan_act_index(p.H, n, i, k, t);
+          const float c[8] = {src[0], src[1], src[2], src[3], src[4], src[5], src[6], src[7]};
+          mtplan_accumulate(c, m, W, A);
+        }
+      }
+      for (int d = 0; d < 8; ++d) plan[((size_t)t * n + i) * 8 + d] = plan_new_mean(m[d], A[d], S);
     }
     if (ret0_row) ret0_row[i] = ret[i];
     if (best_ret) best_ret[i] = beta;

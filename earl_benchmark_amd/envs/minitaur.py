@@ -155,6 +155,189 @@ class Minitaur(PhysicsEnv):
         closed_loop.finish(self, T, res['reward'], res['success'][-1])
     return res
 
+  # ------------------------------------------------------------------ K action plans per env from the current state, and MPPI around them
+  # (names of their own: rollout_branches / plan_mppi / plan_candidates / mpc_rollout / plan_cem / cem_candidates stay PhysicsEnv's refusals on this env, as
+  # rollout_pair / evaluate_population stand beside rollout_agents / evaluate_policy)
+  _WS_BYTES = {'branch': 'earl_minitaur_branch_ws_bytes', 'plan': 'earl_minitaur_plan_ws_bytes'}
+
+  def _ws(self, kind, K, H=0):
+    """the workspace (include/earl_physics.h: earl_minitaur_branch_ws) of a branch launch of K branches ('branch') or of a planner call ('plan': that block and the
+    [K, H, N, 8] candidates behind it): one device block per kind, allocated at the first use, cached per (K, H) and grown when a larger one is asked for"""
+    cache = self.__dict__.setdefault('_ws_cache', {})
+    if (kind, K, H) not in cache:
+      name, need = self._WS_BYTES[kind], C.c_int64(0)
+      _abi.check(getattr(self._lib, name)(K, *(() if kind == 'branch' else (H,)), self.num_envs, C.byref(need)), name)
+      block = cache.get(kind)
+      if block is None or block.numel() * 8 < need.value:
+        if block is not None:
+          cache.setdefault('kept', []).append(block)         # (a captured graph may still hold the smaller block's address: it stays alive)
+        block = cache[kind] = torch.empty(max(need.value, 8) // 8 + 1, dtype=torch.float64, device=self.device)
+      cache[(kind, K, H)] = need.value
+    block = cache[kind]
+    return _abi.MinitaurBranchWs(base=block.data_ptr(), bytes=block.numel() * 8)
+
+  def _branch_actions(self, a):
+    """rollout's action check (it reads a flag back, so it raises on the host) -- but inside a captured region, where nothing can be read back: the kernel clips to the
+    reference's bound there, as a captured step does"""
+    if a.is_cuda and torch.cuda.is_current_stream_capturing():
+      return a.to(torch.float32).contiguous()
+    return self._actions(a, tuple(a.shape[:-2]))
+
+  def branch_rollout(self, actions, K=None, clock=None):
+    """K candidate action sequences of H steps scored per env FROM THE CURRENT STATE in one launch of the rollout kernel over K N virtual envs (include/earl_physics.h:
+    earl_minitaur_branch_rollout): actions [K, H, N, 8] float32 -- or [H, N, 8] with K= for K replays of one block --
+    -> {'ret' [K, N] float64, 'success' [K, N] bool (the success of step H - 1), 'first_success' [K, N] int32 (-1: none), 'last_obs' [K, N, 32] float64,
+        'fail' [K, N] int32 (steps the failure guard rolled back)}.
+    Row k is what rollout(actions[k]) would return next, reduced (ret = the float64 sum of its rewards, a rolled-back step adding 0), lifelong goal draws included:
+    every branch of an env sees the env's own draws.  An action outside the reference's bound raises its '{}th action out of bounds.' as rollout does (not while the
+    stream is being captured into a graph, where no flag can be read back: the kernel clips to that bound).  The env is left
+    exactly as found -- state, motors, goals, counters, last_obs, fail_count: nothing happened to it.  clock: None, or the device address of the two uint64 words of
+    earl_minitaur_rollout_clocked (a captured launch)."""
+    a = torch.as_tensor(actions, device=self.device)
+    n = self.num_envs
+    if K is None:
+      if a.dim() != 4 or a.shape[2] != n or a.shape[3] != ACT_DIM:
+        raise ValueError(f'branch_rollout: actions must be [K, H, N, 8] = [K, H, {n}, 8], got {list(a.shape)} (one block for K branches: [H, {n}, 8] with K=)')
+      K, H, stride = int(a.shape[0]), int(a.shape[1]), int(a.shape[1]) * n * ACT_DIM
+      act = self._branch_actions(a)
+    else:
+      if a.dim() != 3 or a.shape[1] != n or a.shape[2] != ACT_DIM:
+        raise ValueError(f'branch_rollout: with K= actions must be [H, N, 8] = [H, {n}, 8], got {list(a.shape)}')
+      K, H, stride = int(K), int(a.shape[0]), 0
+      act = self._branch_actions(a)
+    if K < 1 or H < 1:                                                 # (the entry point writes nothing then: no branch, or no step to reduce)
+      raise ValueError(f'branch_rollout: K = {K}, H = {H}: at least one branch of at least one step')
+    if K * n > INT32_MAX:
+      raise ValueError(f'branch_rollout: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
+    kw = dict(device=self.device)
+    res = {'ret': torch.empty(K, n, dtype=torch.float64, **kw), 'success': torch.empty(K, n, dtype=torch.bool, **kw),
+           'first_success': torch.empty(K, n, dtype=torch.int32, **kw), 'last_obs': torch.empty(K, n, OBS_DIM, dtype=torch.float64, **kw),
+           'fail': torch.empty(K, n, dtype=torch.int32, **kw)}
+    summary = _abi.EpisodeSummary(ret=res['ret'].data_ptr(), success_last=res['success'].data_ptr(), first_success=res['first_success'].data_ptr())
+    self._cfg.step_counter = self.total_step_count
+    with torch.cuda.device(self.device):
+      ws = self._ws('branch', K)
+      _abi.check(self._lib.earl_minitaur_branch_rollout(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), K, H, act.data_ptr(), stride,
+                                                        clock, C.byref(ws), C.byref(summary), res['last_obs'].data_ptr(), res['fail'].data_ptr(), self._stream()),
+                 'earl_minitaur_branch_rollout')
+    return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
+
+  def _plan_mean(self, who, mean, horizon):
+    n = self.num_envs
+    if mean is None:
+      if horizon is None:
+        raise ValueError(f'{who}: give mean [H, N, 8] or horizon')
+      return torch.zeros(int(horizon), n, ACT_DIM, dtype=torch.float32, device=self.device)
+    m = torch.as_tensor(mean, device=self.device)
+    if m.dim() != 3 or m.shape[1] != n or m.shape[2] != ACT_DIM or (horizon is not None and m.shape[0] != horizon):
+      raise ValueError(f'{who}: mean must be [H, N, 8] = [{"H" if horizon is None else horizon}, {n}, 8], got {list(m.shape)}')
+    return m.to(torch.float32).contiguous()                            # (the planner clips every word to +-1: a mean is not an action and raises nothing)
+
+  def _plan_params(self, who, K, H, iterations, iteration0, sigma, temperature, noise_counter):
+    s = torch.as_tensor(sigma, dtype=torch.float32).reshape(-1).tolist()
+    if len(s) not in (1, ACT_DIM):
+      raise ValueError(f'{who}: sigma is a number or eight, one per action dimension')
+    if not float(temperature) > 0.0:
+      raise ValueError(f'{who}: temperature = {temperature}: > 0')
+    if not 1 <= int(K) <= _abi.MINITAUR_PLAN_MAX_K:
+      raise ValueError(f'{who}: K = {K}: 1 .. {_abi.MINITAUR_PLAN_MAX_K} candidates per env (branch 0, the plan itself, included)')
+    if int(H) < 1 or int(iterations) < 1:
+      raise ValueError(f'{who}: H = {H}, iterations = {iterations}: at least one of each')
+    nc = self.total_step_count if noise_counter is None else int(noise_counter)   # (None: the low word of the env's step count -- fresh noise per control step)
+    return _abi.MinitaurPlanParams(K=int(K), H=int(H), iterations=int(iterations), iteration0=int(iteration0), sigma=(C.c_float * 8)(*(s * 8 if len(s) == 1 else s)),
+                                   noise_counter=nc & 0xFFFFFFFF, inv_temperature=1.0 / float(temperature))
+
+  def mppi_plan(self, mean=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, iteration0=0, noise_counter=None, clock=None, out=None):
+    """`iterations` MPPI iterations on the device from the CURRENT state (include/earl_physics.h: earl_minitaur_plan_mppi): K candidates per env -- the mean plan itself
+    and K - 1 copies with clipped Gaussian noise of scale `sigma` (a number or eight) -- scored by the branch launch exactly as branch_rollout scores them, the mean
+    moved to their average under the weights exp((ret - max ret) / temperature), in integer sums.  Per iteration three launches (candidates, the branch launch,
+    update); no allocation and no host synchronisation in the call once its workspace exists.  mean [H, N, 8] (None: zeros of [horizon, N, 8]; every word is clipped
+    to +-1) ->
+    {'plan' [H, N, 8] float32, 'ret' [K, N] float64 (the last iteration's returns), 'ret0' [iterations, N] float64 (the return of the plan entering each iteration),
+     'best_ret' [N] float64, 'best_k' [N] int32 (mppi_candidates(...)[best_k] is that candidate), 'fail' [K, N] int32 (steps of the last iteration the failure guard
+     rolled back: they count with reward 0, which on this env's negative reward is ABOVE an honest step)}.
+    `noise_counter=None` takes the low 32 bits of env.total_step_count, so successive control steps draw fresh noise (a captured call replays the noise it was captured
+    with); `iteration0` numbers the first iteration (iterations in one call == as many calls of one, numbered on).  `out`: an optional dict of preallocated tensors under
+    the same keys; a key that is missing or None is not computed, except 'ret' (the branch launch writes it), which is then allocated; out['plan'] may be the `mean`
+    tensor.  clock: as branch_rollout.  The env is left exactly as found."""
+    who = 'mppi_plan'
+    m = self._plan_mean(who, mean, horizon)
+    n, H, K, I = self.num_envs, int(m.shape[0]), int(K), int(iterations)
+    pp = self._plan_params(who, K, H, I, iteration0, sigma, temperature, noise_counter)
+    if K * n > INT32_MAX:
+      raise ValueError(f'{who}: K N = {K * n} virtual envs do not fit one launch (at most {INT32_MAX})')
+    kw = dict(device=self.device)
+    want = {'plan': ((H, n, ACT_DIM), torch.float32), 'ret': ((K, n), torch.float64), 'ret0': ((I, n), torch.float64), 'best_ret': ((n,), torch.float64),
+            'best_k': ((n,), torch.int32), 'fail': ((K, n), torch.int32)}
+    if out is None:
+      res = {k: torch.empty(*shape, dtype=dt, **kw) for k, (shape, dt) in want.items()}
+    else:
+      if set(out) - set(want):
+        raise ValueError(f'{who}: out holds {sorted(set(out) - set(want))}; the keys are {list(want)}')
+      res = {k: t for k, t in out.items() if t is not None}
+      for k, t in res.items():
+        shape, dt = want[k]
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+          raise ValueError(f'out[{k!r}] must be contiguous {dt} {shape} on {self.device}')
+      if 'plan' not in res:
+        raise ValueError(f"{who}: out['plan'] is what the call computes")
+      if 'ret' not in res:
+        res['ret'] = torch.empty(*want['ret'][0], dtype=want['ret'][1], **kw)
+    ptr = lambda k: None if res.get(k) is None else res[k].data_ptr()
+    self._cfg.step_counter = self.total_step_count
+    with torch.cuda.device(self.device):
+      _abi.check(self._lib.earl_minitaur_plan_mppi(self.model.buf.data_ptr(), self.model.col_ptr, C.byref(self._cfg), C.byref(self._st), C.byref(pp), m.data_ptr(),
+                                                   res['plan'].data_ptr(), res['ret'].data_ptr(), ptr('ret0'), ptr('best_ret'), ptr('best_k'), ptr('fail'), clock,
+                                                   C.byref(self._ws('plan', K, H)), self._stream()), 'earl_minitaur_plan_mppi')
+    return res                                                         # (no counter, no interventions, no stale flag: the env has not moved)
+
+  def mppi_candidates(self, mean, K, sigma=0.3, iteration=0, noise_counter=None):
+    """the K candidates of mppi_plan's iteration `iteration` around `mean` [H, N, 8], written out: [K, H, N, 8] float32, row 0 the clipped mean -- what branch_rollout
+    takes (earl_minitaur_plan_candidates; mppi_plan runs the same kernel).  With mppi_plan's `noise_counter` (None: the env's step count, unchanged by mppi_plan) they
+    are the candidates that call scored."""
+    m = self._plan_mean('mppi_candidates', mean, None)
+    H = int(m.shape[0])
+    pp = self._plan_params('mppi_candidates', K, H, 1, 0, sigma, 1.0, noise_counter)
+    act = torch.empty(int(K), H, self.num_envs, ACT_DIM, dtype=torch.float32, device=self.device)
+    with torch.cuda.device(self.device):
+      _abi.check(self._lib.earl_minitaur_plan_candidates(C.byref(self._cfg), C.byref(pp), int(iteration), m.data_ptr(), act.data_ptr(), self._stream()),
+                 'earl_minitaur_plan_candidates')
+    return act
+
+  def mppi_control(self, T, plan=None, horizon=None, K=64, iterations=1, sigma=0.3, temperature=1.0, noise_counter=None):
+    """T steps of receding-horizon MPPI control, DEFINED as this composition of public methods (one call each per control step; there is no fused launch):
+        P = plan.clone()  (None: zeros of [horizon, N, 8]);  nc0 = noise_counter  (None: the low 32 bits of env.total_step_count at entry)
+        for s in range(T):
+          mppi_plan(P, K=, iterations=, sigma=, temperature=, noise_counter=(nc0 + s) mod 2^32, out={'plan': P, 'ret': <scratch>, 'ret0': ret0[s], 'best_ret': best_ret[s]})
+          row s of the result = rollout(P[:1], out=<views of row s>);  actions[s] = P[0]
+          P[t] <- P[t + 1] for t < H - 1  (the last row stays)
+    -> rollout()'s dict with a leading [T] ('obs' [T, N, 32], 'reward', 'done', 'success', 'status' [T, N]) plus 'actions' [T, N, 8] float32, 'plan' [H, N, 8] (the
+       shifted plan after the last step: what the next call continues from), 'ret0' [T, iterations, N] and 'best_ret' [T, N] float64.
+    The loop adds no host synchronisation of its own (rollout's bounds check on the clipped plan row is the one each step has).  The env advances by T steps exactly
+    as T calls of rollout advance it."""
+    T = int(T)
+    if T < 1:
+      raise ValueError(f'mppi_control: T = {T}: at least one control step')
+    P = self._plan_mean('mppi_control', plan, horizon).clone()
+    n, H, K, I = self.num_envs, int(P.shape[0]), int(K), int(iterations)
+    self._plan_params('mppi_control', K, H, I, 0, sigma, temperature, noise_counter)      # (the argument errors, before anything moves)
+    nc0 = self.total_step_count if noise_counter is None else int(noise_counter)
+    kw = dict(device=self.device)
+    res = self._new_out((T,))
+    rows = list(res)
+    res.update(actions=torch.empty(T, n, ACT_DIM, dtype=torch.float32, **kw), ret0=torch.empty(T, I, n, dtype=torch.float64, **kw),
+               best_ret=torch.empty(T, n, dtype=torch.float64, **kw))
+    ret = torch.empty(K, n, dtype=torch.float64, **kw)
+    for s in range(T):
+      self.mppi_plan(P, K=K, iterations=I, sigma=sigma, temperature=temperature, noise_counter=(nc0 + s) & 0xFFFFFFFF,
+                     out={'plan': P, 'ret': ret, 'ret0': res['ret0'][s], 'best_ret': res['best_ret'][s]})
+      self.rollout(P[:1], out={k: res[k][s:s + 1] for k in rows})
+      res['actions'][s].copy_(P[0])
+      if H > 1:
+        P[:-1] = P[1:].clone()
+    res['plan'] = P
+    return res
+
   @property
   def initial_states(self):
     """[1, 2]: where the reset pose stands (x, y), the goal row an AgentPair's backward_goal='initial' resolves to"""

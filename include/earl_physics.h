@@ -588,7 +588,7 @@ int32_t earl_sawyer_cem_update_cpu(const earl_sawyer_cfg* cfg, const earl_sawyer
  * EARL_ERR_ARG before any HIP call for: everything the value-free entry point refuses; a discount that is NaN, <= 0 or > 1; a value network the rules above refuse
  * (widths, a precision other than 0, the activation enums, dims[3] != 0 with one hidden layer, params NULL or misaligned); a network without summary->ret; a ws block
  * that is NULL, misaligned or smaller than earl_sawyer_value_ws_bytes says.  There is no bf16 value network and no fused control loop on these
- * envs (policy-prior branches: the next section); the minitaur and the kitchen have no planner at all.
+ * envs (policy-prior branches: the next section); the minitaur has the plain MPPI planner only (earl_minitaur_plan_mppi), the kitchen has none.
  * Host twin (libearl_host.so; host pointers): earl_sawyer_value_terminal_cpu adds the terminal term to ret [rows] for given last_obs [rows, 14] -- d_H by the recurrence,
  * the float32 rounding, the NaN rule and the two roundings through csrc/sawyer_value.h, the header the kernel uses; V by earl_mlp_policy_forward_cpu's loops.  pv->value
  * NULL leaves ret as it is.  There is no host stepper, so the discounted sum itself has no twin.  Its refusals: pv, last_obs or ret NULL, rows < 0, H < 0, and pv's. */
@@ -1036,6 +1036,119 @@ int earl_minitaur_agents_rollout(const void* model24, const earl_collision_model
                                  const earl_mlp_policy* policy, const earl_agent_pair* pair, const earl_policy_population* pop, const earl_backward_goals* goals,
                                  const earl_gaussian_head* head, const double* obs0, int32_t T, const uint64_t* clock, float* actions, const earl_minitaur_out* out,
                                  const earl_episode_summary* summary, earl_stream_t stream);
+
+/* ---- branches on the minitaur: K candidate action sequences per env scored from the CURRENT state in one launch, the state left as it is ----
+ * earl_sawyer_branch_rollout's contract restated for this env: K plans of H steps per env, one return, one success flag, one first-success step, one last observation
+ * and one count of rolled-back steps each, nothing kept.  ONE launch of the rollout kernel over the K n virtual envs v = k n + i (branch k of env i), in front of it
+ * one small kernel that copies the env's [n] state rows into the workspace's [K n]; no [H] row is written anywhere.
+ *   equivalence  branch (k, i) equals earl_minitaur_rollout_clocked(model24, col, cfg, <a private copy of st>, act + k * act_branch_stride, H, clock, out) restricted to
+ *                env i, bit for bit:  summary->ret[k n + i] = the float64 sum over t ascending of out->reward[t][i] (a rolled-back step adds 0);  success_last =
+ *                out->success[H - 1][i];  first_success = the first t with success, or -1;  last_obs[k][i] = out->obs[H - 1][i] exactly as emitted -- entries 30 / 31
+ *                as a lifelong switch patched them, the repeated row of a rolled-back step and, when step 0 itself diverges, the env's row of st->last_obs (NaN if
+ *                that is NULL) included;  fail[k n + i] = the number of steps with status == EARL_STEP_DIVERGED.  A rolled-back step restores the BRANCH's own last
+ *                stable state (qpos, qvel, the motors' overheat counters, enabled flags and observed torques); before its first stable step that is the state in `st`.
+ *   draws        step t of EVERY branch uses the counter cfg->step_counter + clock[1] + t, and the Philox id is the env's global id cfg->env_offset + i, never the
+ *                virtual index: all branches of an env see the lifelong goal draws (stream 0xFFFE) the env's next rollout will see.
+ *   act          float32, device, [K, H, n, 8] in [-1, 1] (the kernel clips to +-1.01 as the rollout does).  act_branch_stride (in floats) == H * n * 8: a contiguous
+ *                array; 0: every branch replays one [H, n, 8] block.
+ *   state        `st` is read and never written: qpos, qvel, goal, motor_param, observed_torque, overheat, motor_enabled, the goal-switch counter, last_obs; no counter
+ *                moves (steps_since_reset and fail_count are not even read).
+ *   ws           what the launch mutates, per virtual env: the last stable qpos [23] and qvel [22], the goal, the eight motors' overheat counters, motor_enabled and
+ *                observed_torque, the goal-switch counter and the one carried observation row (last_obs itself when given); motor_param, which a branch only reads,
+ *                is copied beside them.  ONE device block: base 8-byte aligned, bytes >= what earl_minitaur_branch_ws_bytes(K, n, &bytes) reports (0 for K n == 0;
+ *                monotone in K and in n); the call carves it and refuses a block that is too small.  The caller prepares NOTHING in it and nothing in it outlives the
+ *                call.  No allocation, no host synchronisation: after one eager call with the same `col` (the friction-cone check reads the table's cone word once per
+ *                address) the call can be captured into a HIP graph.
+ *   outputs      summary (rows [K n]; the struct or any of its three pointers NULL), last_obs ([K, n, 32] or NULL) and fail ([K n] or NULL) in any combination, but not
+ *                all five pointers NULL.
+ *   forms        chosen by the number of VIRTUAL envs K n with earl_minitaur_rollout's rules: the tree-structured one-wave kernel in its three launch shapes and the
+ *                two-waves-per-SIMD kernel (earl_debug_set_solo_mt and earl_debug_set_minitaur_duo force them as they force the rollout's).  Those forms are held
+ *                bit-identical to each other, which is what makes the equivalence above independent of K.  Under earl_debug_set_minitaur_stepper(0) the call returns
+ *                EARL_ERR_ARG: the generic build agrees with the tree-structured one to rounding only, like the policy form.
+ * EARL_ERR_ARG before any HIP call, with a message in earl_last_error, for: everything earl_minitaur_rollout_clocked refuses in model / cfg / st; act or ws NULL; K < 0;
+ * H < 0; a negative stride, or one that is neither 0 nor >= H * n * 8; all five outputs NULL; K * n beyond 2^31 - 1; with K n > 0: ws->base NULL or misaligned, ws->bytes
+ * too small.  n == 0, K == 0 or H == 0 returns EARL_OK, launches nothing and writes nothing. */
+typedef struct earl_minitaur_branch_ws {
+  void*   base;    /* device, 8-byte aligned; NULL-able if K n == 0 */
+  int64_t bytes;   /* size of the block at `base` */
+} earl_minitaur_branch_ws;
+/* *bytes = the size of the workspace of a branch launch of K branches of n envs; EARL_ERR_ARG for bytes == NULL, K < 0, n < 0, K * n beyond 2^31 - 1 */
+int earl_minitaur_branch_ws_bytes(int32_t K, int32_t n, int64_t* bytes);
+int earl_minitaur_branch_rollout(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                                 int32_t K, int32_t H, const float* act, int64_t act_branch_stride, const uint64_t* clock, const earl_minitaur_branch_ws* ws,
+                                 const earl_episode_summary* summary, double* last_obs, int32_t* fail, earl_stream_t stream);
+
+/* ---- MPPI planning on the minitaur: I iterations of sample -> score -> reweight on the device, the env left as it is ----
+ * earl_sawyer_plan_mppi's contract with EIGHT action dimensions, around earl_minitaur_branch_rollout, untouched.  Per iteration on the caller's stream: the candidates
+ * kernel, earl_minitaur_branch_rollout (its replicate kernel and its rollout kernel), the update kernel; no allocation, no host synchronisation: after one eager call
+ * with the same `col` (the branch launch's rule) the call can be captured into a HIP graph.  noise_counter is a host word: a captured call replays the same noise.
+ * For iteration j = iteration0 + i (i = 0 .. iterations - 1), env `env` with global id g = cfg->env_offset + env, and the plan entering the iteration `mean` (the
+ * argument for i = 0, the previous iteration's result afterwards):
+ *   1 clipped mean  m[t][d] = clip(mean[t][d]) in float32 for d = 0 .. 7, clip(x) = (y = x > -1 ? x : -1; y < 1 ? y : 1) = min(max(x, -1), 1): every candidate lies
+ *                   inside the env's +-1 action bound.
+ *   2 candidates    branch 0 is the plan itself, a_0 = m.  For k >= 1: a_k[t][d] = clip(fmaf(sigma[d], eps_d, m[t][d])), eps_d = normal_quantile_f32(word_d >> 8)
+ *                   (csrc/policy_math.h; earl_normal_quantile_f32).  TWO Philox4x32-10 blocks, key = cfg->seed: words x, y, z, w of the block with counter words
+ *                   {0x504C4E00 | j, g, (k << 16) | t, noise_counter} serve d = 0 .. 3 -- the Sawyer planner's block: with equal seed, g, j, k, t, noise_counter, sigma
+ *                   and mean, words 0 .. 3 of a minitaur candidate are the Sawyer candidate's --, those of the block with bit 31 of word 2 set,
+ *                   {0x504C4E00 | j, g, 0x80000000 | (k << 16) | t, noise_counter}, serve d = 4 .. 7.  The bit is free: k <= 8191 < 2^15, t < 2^16.  Word 0 collides with
+ *                   no other draw of the minitaur (the reset's 0x4D00 .. 0x4D06, the goal switch's 0xFFFE, the pair's 0xFFFD, the Gaussian head 0x504F4C00).  The draws
+ *                   depend on (seed, g, j, k, t, noise_counter) only: not on n, not on the shard split.  The candidates live in memory, [K, H, n, 8] float32.
+ *   3 scores        ret[k][env] = summary->ret of earl_minitaur_branch_rollout fed with those candidates (act_branch_stride = H * n * 8) and the caller's `clock`: goal
+ *                   switches inside the look-ahead and rolled-back steps (reward 0) count exactly as that call defines them.  The minitaur's reward is dense and
+ *                   NEGATIVE (distance and energy terms): a rolled-back step scores 0, above an honest one -- `fail` tells which branches had any.
+ *   4 weights       beta = max_k ret[k];  x_k = (float)((ret[k] - beta) * inv_temperature) (two float64 roundings);  w_k = exp_f32(x_k) (csrc/policy_math.h;
+ *                   earl_exp_f32);  W_k = (double)w_k * 2^24 rounded to nearest-even as int64 (0 .. 2^24);  S = sum_k W_k (>= 2^24: the best branch has W = 2^24).
+ *   5 update        delta = a_k[t][d] - m[t][d] (one float32 subtraction);  D_k = (double)delta * 2^20 rounded to nearest-even as int64;  A = sum_k W_k * D_k in
+ *                   int64 per dimension (|A| < 2^59 for K <= 8192);  mean'[t][d] = clip(m[t][d] + (float)((double)A / ((double)S * 2^20))), (double)A rounded to
+ *                   nearest.  Integer sums are associative: the result does not depend on how the K branches are spread over lanes, waves and workgroups.
+ *   6 outputs       plan [H, n, 8] float32, REQUIRED: the mean after the last iteration; it may be the pointer `mean` itself (the in-place call), any other overlap of
+ *                   the two arrays is refused.  ret [K, n] float64, REQUIRED: the last iteration's returns on exit.  ret0 NULL or [iterations, n] float64: the
+ *                   return of the plan entering each iteration (branch 0).  best_ret NULL or [n] float64: beta of the last iteration.  best_k NULL or [n] int32:
+ *                   the smallest k attaining it (earl_minitaur_plan_candidates recovers that candidate).  fail NULL or [K, n] int32: the last iteration's count of
+ *                   rolled-back steps per branch (earl_minitaur_branch_rollout's `fail`).
+ *   7 non-finite    clip() maps a NaN of `mean` to -1 and +-Inf to +-1, so every candidate is finite whatever `mean` holds.  A NaN return never wins: beta is the
+ *                   largest return that is not NaN, -Inf if there is none; x_k that is NaN (a NaN return, or Inf - Inf) gives W_k = 0; if S == 0 (no branch has a
+ *                   weight) the update is skipped, mean' = m.  best_k is the smallest k with ret[k] == beta when beta > -Inf, and 0 otherwise.  Nothing of this faults.
+ *   chaining        `iterations` iterations in one call equal that many calls with iterations = 1 and iteration0 = j, each fed the previous plan, bit for bit.
+ *   determinism     the noise depends on (seed, global env id, j, k, t, noise_counter) only and the sums are integer: the plan is bit-identical across shard splits,
+ *                   launch forms and graph replays.
+ *   state           `st` is read and never written, as in the branch launch: the env is as earl_minitaur_branch_rollout leaves it.
+ *   ws              ONE block as earl_minitaur_branch_ws describes it, of at least earl_minitaur_plan_ws_bytes(K, H, n, &bytes) bytes: the branch launch's workspace
+ *                   and behind it the [K, H, n, 8] candidates of the current iteration at the next 16-byte address (the call aligns them itself).  The size is
+ *                   monotone in K, H and n and 0 for K n == 0.  The caller prepares nothing in it and nothing in it outlives the call.
+ * EARL_ERR_ARG before any HIP call, with a message in earl_last_error, for: everything earl_minitaur_branch_rollout refuses in model / col / cfg / st; params, mean, plan,
+ * ret or ws NULL; K outside 1 .. EARL_MINITAUR_PLAN_MAX_K (one env's integer weights are held in 32 KB of LDS); H outside 1 .. 65536; iterations < 1, iteration0 < 0,
+ * iteration0 + iterations > 256; a sigma that is negative or not finite; an inv_temperature that is not finite or <= 0; plan overlapping mean without being equal to it;
+ * K * n beyond 2^31 - 1; with n > 0 a ws block that is NULL, misaligned (8 bytes) or too small.  n == 0 returns EARL_OK, launches nothing and writes nothing.  Under
+ * earl_debug_set_minitaur_stepper(0) the call returns EARL_ERR_ARG, as the branch launch does. */
+typedef struct earl_minitaur_plan_params {
+  int32_t K;               /* candidates per env, branch 0 (the plan itself) included: 1 .. EARL_MINITAUR_PLAN_MAX_K */
+  int32_t H;               /* steps of a plan: 1 .. 65536 */
+  int32_t iterations;      /* I >= 1 */
+  int32_t iteration0;      /* index of the first iteration (a word of the noise counter): >= 0, iteration0 + iterations <= 256 */
+  float sigma[8];          /* noise scale per action dimension, finite, >= 0 */
+  uint32_t noise_counter;  /* a word of the noise counter: a fresh value per control step gives fresh noise */
+  double inv_temperature;  /* 1 / lambda, finite, > 0 */
+} earl_minitaur_plan_params;
+#define EARL_MINITAUR_PLAN_MAX_K 8192
+/* *bytes = the size of the workspace of a planner call; EARL_ERR_ARG for bytes == NULL, K < 0, H < 0, n < 0, K * n beyond 2^31 - 1 */
+int earl_minitaur_plan_ws_bytes(int32_t K, int32_t H, int32_t n, int64_t* bytes);
+int earl_minitaur_plan_mppi(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
+                            const earl_minitaur_plan_params* params, const float* mean, float* plan, double* ret, double* ret0, double* best_ret, int32_t* best_k,
+                            int32_t* fail, const uint64_t* clock, const earl_minitaur_branch_ws* ws, earl_stream_t stream);
+/* Item 2 written out for ONE iteration j (0 .. 255): act_out [K, H, n, 8] float32, 16-byte aligned, what earl_minitaur_branch_rollout takes; earl_minitaur_plan_mppi runs
+ * the same kernel.  It reads cfg->n, env_offset and seed and params->K, H, sigma and noise_counter only (no env state, no model).
+ * EARL_ERR_ARG for cfg, params, mean or act_out NULL, act_out misaligned, n < 0, K or H out of range, j outside 0 .. 255, a bad sigma, K * n beyond 2^31 - 1; n == 0
+ * returns EARL_OK and writes nothing. */
+int earl_minitaur_plan_candidates(const earl_minitaur_cfg* cfg, const earl_minitaur_plan_params* params, int32_t j, const float* mean, float* act_out, earl_stream_t stream);
+/* Host twins of the planner's own arithmetic (libearl_host.so; host pointers; csrc/minitaur_plan.h in plain loops -- there is no host stepper, so the scores are the
+ * caller's).  earl_minitaur_plan_candidates_cpu: the call above (no alignment asked of act_out).  earl_minitaur_plan_update_cpu: items 4 - 7 of iteration j on GIVEN
+ * candidates act [K, H, n, 8] and returns ret [K, n] -> plan [H, n, 8] (may be `mean`), and ret0_row / best_ret / best_k, each NULL or [n].  It reads cfg->n and
+ * params->K, H and inv_temperature; its refusals are the planner's for those, for j and for the pointers. */
+int32_t earl_minitaur_plan_candidates_cpu(const earl_minitaur_cfg* cfg, const earl_minitaur_plan_params* params, int32_t j, const float* mean, float* act_out);
+int32_t earl_minitaur_plan_update_cpu(const earl_minitaur_cfg* cfg, const earl_minitaur_plan_params* params, int32_t j, const float* mean, const float* act, const double* ret,
+                                      float* plan, double* ret0_row, double* best_ret, int32_t* best_k);
+
 /* reset the envs with mask[i] != 0 (NULL = all); obs [n, 32] (may be NULL) is written for the reset envs only */
 int earl_minitaur_reset(const void* model24, const earl_collision_model* col, const earl_minitaur_cfg* cfg, const earl_minitaur_state* st,
                         const uint8_t* mask, double* obs, earl_stream_t stream);
